@@ -15,7 +15,8 @@ batch of independent synthetic 4K VarDCT frames (workloa
 already resident in HBM. Frames are independent: no data-path collective inside a step ("scaling": "weak").
 The RCCL gather of finished pixels to rank 0 (north_star's "trivial gather", shard.gather_planes) is reported
 under "gather": on its own and overlapped with the next step's compute, for f32 planes and for RGB16 output.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0. A plain run times exactly --steps steps after --warmup and prints the headline; the gather and
+every other leg beside it (repetitions, roofline, end-to-end, CPU baseline, `also`) run only with --full.
 """
 import argparse
 import ctypes as C
@@ -37,6 +38,8 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md); 6290 GB/s is t
 # non-fused f32 VALU issue peak: 1024 SIMDs x one wave-instruction (64 lanes) per 2 cycles at the 2.4 GHz maximum clock
 # (MI355X_MICROARCH.md "Per-instruction cycle constants": v_add_f32 / v_mul_f32 2 cyc per wave64 on a SIMD-32)
 VALU_PEAK_GINST = 1024 * 2.4 / 2.0  # 1228.8 G wave-instructions / s
+DUMP_BUDGET = 60 * 1000 * 1000  # bytes of --dump-outputs, all ranks together (64 MB at most, .npy headers included)
+DUMP_SEED = 20240601    # positions of the sample --dump-outputs keeps of an output larger than its share
 
 
 def parse(argv=None):
@@ -65,6 +68,13 @@ def parse(argv=None):
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (RCCL) and run the collective legs even with one rank")
     ap.add_argument("--verify", action="store_true", help="check frame 0 against the oracle before timing")
     ap.add_argument("--no-also", action="store_true", help="skip the `also` object (the other workloads north_star names, each run as a child process after the headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: repetitions of the timed region (timing), roofline and single-frame "
+                         "runs, RCCL gather, end-to-end and streaming legs, CPU baseline, the `also` side runs (the --no-* switches "
+                         "above pick from these). Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32, or float64 for "
+                         "int32 samples); a fixed, seeded sample of each output when all of them exceed %d MB" % (DUMP_BUDGET // 1000000))
     ap.add_argument("--streaming-child", default="", help="internal: run the streaming boundary leg alone (device,contexts,frames_per_context,job.pkl) and print its JSON")
     return ap.parse_args(argv)
 
@@ -76,6 +86,26 @@ def emit(obj):
     """the ONE JSON line, on the process's real stdout"""
     data = (json.dumps(obj) + "\n").encode()
     os.write(_REAL_STDOUT if _REAL_STDOUT is not None else 1, data)
+
+
+def dump_outputs(dirname, arrays, budget):
+    """--dump-outputs: arrays = {name: what a caller of the timed path receives}, written as dirname/<name>.npy. Floats stay
+    float32; integer samples become float32 up to 16 bits and float64 above (both exact). When the arrays exceed `budget` bytes
+    together, each one is cut to an equal share: the same seeded positions of its flattened samples in every run, so that two
+    builds given the same arguments can be compared element for element."""
+    os.makedirs(dirname, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = (a.reshape(-1), np.float32 if a.dtype.kind == "f" or a.dtype.itemsize <= 2 else np.float64)
+    total = sum(a.size * np.dtype(dt).itemsize for a, dt in conv.values())
+    for name, (flat, dt) in conv.items():
+        if total > budget:
+            keep = max(1, int(budget // len(conv) // np.dtype(dt).itemsize))
+            if keep < flat.size:
+                rng = np.random.default_rng(DUMP_SEED)
+                flat = flat[np.unique(rng.integers(0, flat.size, size=keep))]
+        np.save(os.path.join(dirname, name + ".npy"), flat.astype(dt))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -139,7 +169,7 @@ def also_runs(args):
     t0 = time.time()
     for key, extra, what in ALSO_RUNS:
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),
-               "--no-gather", "--no-end-to-end", "--no-also"] + extra
+               "--full", "--no-gather", "--no-end-to-end", "--no-also"] + extra
         env = dict(os.environ)
         for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
             env.pop(k, None)
@@ -325,7 +355,8 @@ def main():
     for _ in range(args.warmup):
         step()
     sync_all()
-    ctxs[0].call("jxl_vardct_enable_stage_timing", 1)
+    if args.full:
+        ctxs[0].call("jxl_vardct_enable_stage_timing", 1)
 
     def timed_region():
         """EXACTLY args.steps steps between barrier + synchronize on both sides; max over ranks"""
@@ -342,25 +373,53 @@ def main():
         torch.cuda.synchronize()
         return float(dt.item())
 
-    # One timed region of K steps of a few milliseconds is one thin sample (28 ms, +-3 % between variants is inside its
-    # noise): the region is repeated -- at least 5 times and until 0.25 s of timed work have accumulated (the count is agreed on
-    # between the ranks) -- and `value` / `ms_per_step` are the MEDIAN repetition's; min / max / spread are reported beside it.
-    first = timed_region()
-    n_rep = max(5, min(400, int(math.ceil(0.25 / max(first, 1e-6)))))
-    if use_dist:
-        nr = torch.tensor([n_rep], dtype=torch.int64, device="cuda")
-        dist.all_reduce(nr, op=dist.ReduceOp.MAX)
-        n_rep = int(nr.item())
-    reps_s = [first] + [timed_region() for _ in range(n_rep - 1)]
-    elapsed = float(np.median(reps_s))
-    timing = {"repetitions": len(reps_s), "timed_s_total": round(float(np.sum(reps_s)), 4),
-              "ms_per_step_min": round(min(reps_s) * 1e3 / args.steps, 4), "ms_per_step_median": round(elapsed * 1e3 / args.steps, 4),
-              "ms_per_step_max": round(max(reps_s) * 1e3 / args.steps, 4),
-              "spread_pct": round(100.0 * (max(reps_s) - min(reps_s)) / elapsed, 2),
-              "note": "each repetition = exactly `steps` steps between barrier + synchronize; value and ms_per_step are the median repetition"}
+    # `value` / `ms_per_step` come from ONE region of exactly --steps steps (whoever runs the bench sizes --steps by ms_per_step).
+    # A region of a few milliseconds is a thin sample (28 ms, +-3 % between variants is inside its noise): --full repeats
+    # it -- at least 5 times and until 0.25 s of timed work have accumulated (the count is agreed on between the ranks) -- and
+    # reports min / median / max / spread in `timing`.
+    elapsed = timed_region()
+    timing = None
+    if args.full:
+        n_rep = max(5, min(400, int(math.ceil(0.25 / max(elapsed, 1e-6)))))
+        if use_dist:
+            nr = torch.tensor([n_rep], dtype=torch.int64, device="cuda")
+            dist.all_reduce(nr, op=dist.ReduceOp.MAX)
+            n_rep = int(nr.item())
+        reps_s = [elapsed] + [timed_region() for _ in range(n_rep - 1)]
+        med = float(np.median(reps_s))
+        timing = {"repetitions": len(reps_s), "timed_s_total": round(float(np.sum(reps_s)), 4),
+                  "ms_per_step_min": round(min(reps_s) * 1e3 / args.steps, 4), "ms_per_step_median": round(med * 1e3 / args.steps, 4),
+                  "ms_per_step_max": round(max(reps_s) * 1e3 / args.steps, 4),
+                  "spread_pct": round(100.0 * (max(reps_s) - min(reps_s)) / med, 2),
+                  "note": "each repetition = exactly `steps` steps between barrier + synchronize; value and ms_per_step are the first repetition"}
     ms_per_step = elapsed * 1e3 / args.steps
     total_px = float(npx) * n_frames * args.steps
     value = total_px / elapsed / 1e6  # Mpixels/s, whole job
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"frame%d" % my_frames[i]: fr.readOutput() for i, fr in enumerate(frames)}, DUMP_BUDGET // world)
+
+    launches = frames[0].lastLaunchCount()
+    epf_iters = real_stats["epf_iters"] if real_stats else args.epf_iters
+    out_bytes_px = 6.0 if args.workload == "vardct8k_pq" else 12.0
+    line = {
+        "metric": "Mpixels/s decoded (VarDCT 4K frame) at 1/2/4/8 MI355X vs host-CPU jxlatte",
+        "value": round(value, 1), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic" if distinct else "real bitstream %s (parsed by the C++ front-end)" % os.path.basename(args.input),
+        "config": {"workload": "%s: %d independent %dx%d VarDCT frames per GPU (mix=%s, Gab + EPF x%d + XYB, %s out), inputs resident in HBM"
+                               % (args.workload, fpg, W, H, args.mix if distinct else "as coded", epf_iters,
+                                  "f32" if out_bytes_px == 12.0 else "PQ u16"),
+                   "frames_per_gpu": fpg, "frames_total": n_frames, "frame_seeds": "1000 + i, frame i on rank i mod %d" % world if n_frames > 1 else "1234",
+                   "distinct_frames": len(distinct) or 1, "streams": 1 if args.streams == 1 else min(fpg, args.stream_groups) if args.stream_groups else fpg,
+                   "varblock_area_share": synth.type_histogram(distinct[0]) if distinct else real_stats["varblocks"],
+                   "kernel_launches_per_frame": launches, "input_gen_s": round(gen_s, 1)},
+    }
+    if not args.full:
+        if rank == 0:
+            emit(line)
+        if use_dist:
+            dist.destroy_process_group()
+        return
 
     # HIP-event stage times of ctx 0 (averaged over its runs inside the timed region)
     def stage_ms():
@@ -371,7 +430,6 @@ def main():
             out.append(v.value)
         return out
     ms_all_b, ms_idct_b, ms_rest_b = stage_ms()  # inside the timed region (other frames' kernels overlap)
-    launches = frames[0].lastLaunchCount()
     # the same events with frame 0 alone on the device: the kernels' own durations (what rocprofv3 reports per launch)
     # (r4: the runs are enqueued back to back -- the frame's launches are ordered on its streams, so each run still has the device
     # to itself, but the chip holds its clock; with a host synchronisation between the runs it does not, and the figures of one
@@ -456,7 +514,6 @@ def main():
             e2e = {"error": repr(e)[:300]}
 
     # ---- roofline of the dominant kernel (restoration + colour stage) and of the whole path
-    out_bytes_px = 6.0 if args.workload == "vardct8k_pq" else 12.0
     side = 21.0 / 64.0  # per-pixel share of the 8x8-cell side info
     path_bytes = (12.0 + out_bytes_px + side) * npx + 1.58e6  # whole path, algorithmic (24.5 B/px for f32 out)
     rest_bytes = (12.0 + out_bytes_px + 8.0 / 64.0) * npx     # restore stage: planes in + planes out + hfMul/sharpness
@@ -464,7 +521,6 @@ def main():
     rest_s = ms_rest * 1e-3
     achieved = rest_bytes / rest_s / 1e9 if rest_s > 0 else 0.0
     path_gbs = path_bytes * fpg * args.steps / elapsed / 1e9  # per GPU
-    epf_iters = real_stats["epf_iters"] if real_stats else args.epf_iters
     # measured per-launch counters of this kernel (profiles/<round>_traffic.json, written by tools/profile_round.sh from the
     # rocprofv3 --pmc passes of this same command): HBM bytes and VALU wave-instructions. rocprofv3 cannot run inside
     # the bench; the figures are carried over only when workload and variant match, else null.
@@ -541,23 +597,9 @@ def main():
                "cpu_model": cpu_model(), "host_cores": os.cpu_count()}
         cpu.update(jvm_probe(os.path.join(ROOT, "tests", "golden", "samples", "lenna.jxl")))
 
-    line = {
-        "metric": "Mpixels/s decoded (VarDCT 4K frame) at 1/2/4/8 MI355X vs host-CPU jxlatte",
-        "value": round(value, 1), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic" if distinct else "real bitstream %s (parsed by the C++ front-end)" % os.path.basename(args.input),
-        "config": {"workload": "%s: %d independent %dx%d VarDCT frames per GPU (mix=%s, Gab + EPF x%d + XYB, %s out), inputs resident in HBM"
-                               % (args.workload, fpg, W, H, args.mix if distinct else "as coded", epf_iters,
-                                  "f32" if out_bytes_px == 12.0 else "PQ u16"),
-                   "frames_per_gpu": fpg, "frames_total": n_frames, "frame_seeds": "1000 + i, frame i on rank i mod %d" % world if n_frames > 1 else "1234",
-                   "distinct_frames": len(distinct) or 1, "streams": 1 if args.streams == 1 else min(fpg, args.stream_groups) if args.stream_groups else fpg,
-                   "varblock_area_share": synth.type_histogram(distinct[0]) if distinct else real_stats["varblocks"],
-                   "kernel_launches_per_frame": launches,
-                   "single_frame_ms": round(single_ms, 4),
-                   "single_frame_Mpx_s": round(npx / single_ms / 1e3, 1), "input_gen_s": round(gen_s, 1)},
-        "roofline": roofline,
-        "cpu_baseline": cpu,
-    }
+    line["config"].update(single_frame_ms=round(single_ms, 4), single_frame_Mpx_s=round(npx / single_ms / 1e3, 1))
+    line["roofline"] = roofline
+    line["cpu_baseline"] = cpu
     line["timing"] = timing
     if e2e:
         line["untimed"] = e2e
@@ -1035,6 +1077,9 @@ def bench_modular(args, rank, world, local_rank, torch, dist):
         dist.barrier()
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
     elapsed = float(dt.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"image%d_ch%d" % (rank * fpg + j, c): a for j, ms in enumerate(streams)
+                                         for c, a in enumerate(ms.getDecodedBuffer())}, DUMP_BUDGET // world)
     if rank != 0:
         return
     npx = W * H
@@ -1053,7 +1098,7 @@ def bench_modular(args, rank, world, local_rank, torch, dist):
         except Exception:
             pass
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import pyoracle as orc
         orc.modular_apply(mod["chans"], mod["sp"])  # page in
         reps, a = 0, time.perf_counter()

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -88,7 +89,7 @@ def test_also_runs_are_valid_bench_invocations_and_collect_one_line_each(monkeyp
 
     def fake_run(cmd, env=None, capture_output=None, text=None, timeout=None):
         a = bench.parse(cmd[2:])  # argparse exits on an unknown flag
-        assert a.no_also and a.no_gather and a.no_end_to_end and a.gpus == 1
+        assert a.full and a.no_also and a.no_gather and a.no_end_to_end and a.gpus == 1
         assert "WORLD_SIZE" not in env and "RANK" not in env
         calls.append(a)
         if a.workload == "vardct8k_pq":
@@ -107,3 +108,32 @@ def test_also_runs_are_valid_bench_invocations_and_collect_one_line_each(monkeyp
     assert "error" in out["vardct8k_pq"] and "value" not in out["vardct8k_pq"]
     assert out["modular8k"]["frac"] == 0.25 and out["modular8k"]["traffic"] == 123 and out["modular8k"]["cpu_baseline"] == {"value": 9.0}
     assert out["vardct4k_epf1"]["frac"] == 0.1 and out["vardct4k_epf1"]["kernel_frac"] == 0.25
+
+
+def test_dump_outputs_fits_the_budget_and_samples_the_same_positions_every_run(tmp_path):
+    """--dump-outputs: small outputs are written whole; outputs over the budget become one seeded sample per array that fits the
+    budget, at the same positions in every run, with the samples' values exact (float32 / uint16 as float32, int32 as float64)"""
+    import bench
+    assert not bench.parse([]).full and bench.parse([]).dump_outputs == ""
+    assert bench.parse(["--full", "--dump-outputs", str(tmp_path)]).full
+    rng = np.random.default_rng(3)
+    small = {"a": rng.standard_normal((3, 4, 5)).astype(np.float32), "b": rng.integers(0, 65536, (6, 7)).astype(np.uint16)}
+    bench.dump_outputs(str(tmp_path / "small"), small, 1 << 20)
+    got = np.load(str(tmp_path / "small" / "a.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, small["a"].reshape(-1))
+    got = np.load(str(tmp_path / "small" / "b.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, small["b"].reshape(-1).astype(np.float32))
+
+    big = {"f%d" % i: rng.standard_normal((3, 300, 400)).astype(np.float32) for i in range(3)}
+    big["m"] = rng.integers(-2 ** 31, 2 ** 31, (500, 600), dtype=np.int64).astype(np.int32)
+    budget = 400_000
+    for run in ("r1", "r2"):
+        bench.dump_outputs(str(tmp_path / run), big, budget)
+    files = sorted(os.listdir(str(tmp_path / "r1")))
+    assert files == ["f0.npy", "f1.npy", "f2.npy", "m.npy"]
+    assert sum(os.path.getsize(str(tmp_path / "r1" / f)) for f in files) <= budget + 128 * len(files)
+    for f in files:
+        a, b = np.load(str(tmp_path / "r1" / f)), np.load(str(tmp_path / "r2" / f))
+        assert a.dtype == (np.float64 if f == "m.npy" else np.float32) and np.array_equal(a, b)
+        src = big[f[:-4]].reshape(-1)
+        assert 0 < a.size < src.size and np.isin(a, src.astype(a.dtype)).all()

@@ -4,7 +4,7 @@ R=${1:-r5}
 O=gpurun_out/bench_$R
 mkdir -p $O
 L=tests/golden/samples_large
-run() { python bench.py "${@:2}" > $O/$1.json 2> $O/$1.err; python -c "
+run() { python bench.py --full "${@:2}" > $O/$1.json 2> $O/$1.err; python -c "
 import json,sys
 d=json.loads(open('$O/$1.json').read().strip().splitlines()[-1]); print('%-28s value %9.1f  ms/step %.4f' % ('$1', d['value'], d['ms_per_step']))"; }
 run ${R}_bench_vardct4k
