@@ -153,7 +153,7 @@ struct jxl_ctx {
     bool sub = false;      // any jpeg_upsampling shift non-zero
     int sy[3] = {0, 0, 0}, sx[3] = {0, 0, 0};
     DevBuf hfm_sub[3];     // hfMultiplier resampled onto each channel's cell grid
-    struct SpecialLaunch { int items_off, n_items, channel; bool wg_items; };
+    struct SpecialLaunch { int items_off, n_items, channel; };  // lane-per-block items of one channel (chroma-subsampled frames)
     std::vector<SpecialLaunch> special_launches;
     std::vector<TypeLaunch> type_launches;
     int large_first = 0, large_count = 0;
@@ -166,12 +166,11 @@ struct jxl_ctx {
     int last_launches = 0;
     uint64_t tables_gen = 0;  // bumped whenever finalize_tables rebuilds the binned work (batch argument cache key)
     // jxl_vardct_run_batch state (kept by the first context of a batch)
-    DevBuf batch_args, batch_restore_args;
+    DevBuf batch_restore_args;
     std::vector<FusedArgs> batch_restore_host;
     bool batch_restore_valid = false;
     std::vector<std::pair<const jxl_ctx*, uint64_t>> batch_key;
-    // cls 0 / 1 = k_idct_multi classes, 3 = the special 8x8 kernel (MultiArgs blocks in batch_args);
-    // 10 = k_llf_wg3, 11 / 12 = k_idct_wg3<false / true> (Wg3Args blocks in batch_wg3_args; grid_x of 10 = lanes)
+    // cls 11 / 12 = k_idct_wg3_batch<false / true> (Wg3Args blocks in batch_wg3_args)
     struct BatchLaunch { int cls, n_frames, grid_x; size_t lds_bytes, offset; };
     DevBuf batch_wg3_args;
     void* h_map16 = nullptr;   // page-locked frame-sized int16 planes handed to the caller (jxl_vardct_map_coeffs_i16)
@@ -214,7 +213,7 @@ struct jxl_ctx {
     // queue), 5 -> 45.3, 6 -> 46.7, 7 -> 40.0, 8 -> 40.7. So: no stream is created that is not used.
     int n_aux = 1;
     hipStream_t aux[kAux] = {};
-    hipEvent_t fork_ev = nullptr, llf_ev = nullptr, join_ev[kAux] = {};
+    hipEvent_t fork_ev = nullptr, join_ev[kAux] = {};
 
     // ---- Modular state
     std::vector<DevBuf> mod_bufs;
@@ -657,25 +656,21 @@ jxl_status finalize_tables(jxl_ctx* c) {
                 first_of[t] = (uint32_t)c->h_blocks.size();
                 c->h_blocks.insert(c->h_blocks.end(), lists[t].begin(), lists[t].end());
             }
-        const uint32_t ch0 = channel < 0 ? 0 : (uint32_t)channel, ch1 = channel < 0 ? 3 : (uint32_t)channel + 1;
-        // classes 2 / 3 = the persistent three-channel kernel (k_idct_wg3.hip; 3: the 64-point family) for every METHOD_DCT type
-        // above 8x8 of a frame without chroma subsampling; classes 1 / 0 = the per-channel kernels of k_idct.hip (8x8 always; everything for
-        // subsampled frames, whose channels have their own geometry)
-        static const bool use_wg3 = !(getenv("JXL_IDCT_WG3") && atoi(getenv("JXL_IDCT_WG3")) == 0);
+        // frames without chroma subsampling (channel < 0): every type in the persistent three-channel launches of k_idct_wg3.hip
+        // (class 3: 64x32 / 32x64; class 2: everything else, the special 8x8 types behind the others, r6). Chroma-subsampled frames,
+        // whose channels have their own geometry: per channel, classes 1 / 0 of the per-channel kernels of k_idct.hip and the
+        // lane-per-block special kernel
         jxl_ctx::TypeLaunch cl[4] = {{3, channel, {}}, {2, channel, {}}, {1, channel, {}}, {0, channel, {}}};  // launch order: heaviest class first
-        // r6: the special 8x8 types of a frame without chroma subsampling are items of the persistent launch too (wg3_special_items):
-        // they join class 2's segments and get no launch of their own below
-        const bool special_in_wg3 = use_wg3 && channel < 0 && wg3_special_items();
         for (int t : kOrder) {
             if (lists[t].empty()) continue;
             const IdctSegment sg{t, (int)first_of[t], (int)lists[t].size()};
-            const int cls = (use_wg3 && channel < 0 && wg3_handles(t)) ? (wg3_big(t) ? 3 : 2) : idct_class_of(t);
+            const int cls = channel < 0 ? (wg3_big(t) ? 3 : 2) : idct_class_of(t);
             for (auto& l : cl)
                 if (l.cls == cls) l.segs.push_back(sg);
         }
-        if (special_in_wg3)
+        if (channel < 0)
             for (int t : kSpecial) {
-                if (lists[t].empty() || !wg3_handles(t)) continue;
+                if (lists[t].empty()) continue;
                 for (auto& l : cl)
                     if (l.cls == 2) l.segs.push_back(IdctSegment{t, (int)first_of[t], (int)lists[t].size()});
             }
@@ -684,7 +679,8 @@ jxl_status finalize_tables(jxl_ctx* c) {
             if (l.segs.size() > (size_t)(l.cls >= 2 ? Wg3Args::kMaxSeg : MultiArgs::kMaxSeg)) seg_overflow = true;
             if (!l.segs.empty()) c->type_launches.push_back(std::move(l));
         }
-        jxl_ctx::SpecialLaunch sl{(int)items.size(), 0, channel, false};
+        if (channel < 0) return;
+        jxl_ctx::SpecialLaunch sl{(int)items.size(), 0, channel};
         // One wave per item = 64 consecutive blocks of one type and channel. The block lists are group-major (256 x 256 px
         // groups in raster order), so item k of every type covers about the same few groups. An 8 x 8 block's rows are 32-byte
         // pieces of 128-byte lines whose other pieces belong to blocks of other types: launched type after type, every line is
@@ -694,23 +690,16 @@ jxl_status finalize_tables(jxl_ctx* c) {
         // that share lines are in flight together on one L2.
         struct Ord { uint32_t key; WorkItem w; };
         std::vector<Ord> ord;
-        const int grs_c = std::max(1, (((channel < 0 ? c->bw : (c->bw >> c->sx[channel])) + 31) >> 5));
-        // frames without chroma subsampling: one item = 64 blocks with all three channels (k_idct_special_wg);
-        // per-channel launches: one item per channel (the lane-per-block kernel)
-        static const bool special_wg = !(getenv("JXL_SPECIAL_WG") && atoi(getenv("JXL_SPECIAL_WG")) == 0);
-        const bool wg_items = channel < 0 && special_wg;
+        const int grs_c = std::max(1, ((c->bw >> c->sx[channel]) + 31) >> 5);
         for (int t : kSpecial)
-            for (uint32_t o = 0; o < (special_in_wg3 && wg3_handles(t) ? 0u : (uint32_t)lists[t].size()); o += 64)
-                for (uint32_t ch = ch0; ch < (wg_items ? ch0 + 1 : ch1); ch++) {
-                    const DevBlock& b0 = lists[t][o];
-                    ord.push_back(Ord{(uint32_t)((b0.cy >> 5) * grs_c + (b0.cx >> 5)),
-                                      WorkItem{(uint32_t)t | (ch << 8), first_of[t] + o, (uint32_t)std::min<size_t>(64, lists[t].size() - o)}});
-                }
-        static const bool spatial = !(getenv("JXL_SPECIAL_SPATIAL") && atoi(getenv("JXL_SPECIAL_SPATIAL")) == 0);
-        if (spatial && ord.size() > 8) {
+            for (uint32_t o = 0; o < (uint32_t)lists[t].size(); o += 64) {
+                const DevBlock& b0 = lists[t][o];
+                ord.push_back(Ord{(uint32_t)((b0.cy >> 5) * grs_c + (b0.cx >> 5)),
+                                  WorkItem{(uint32_t)t | ((uint32_t)channel << 8), first_of[t] + o, (uint32_t)std::min<size_t>(64, lists[t].size() - o)}});
+            }
+        if (ord.size() > 8) {
             std::stable_sort(ord.begin(), ord.end(), [](const Ord& x, const Ord& y) { return x.key < y.key; });
-            static const int run_env = getenv("JXL_SPECIAL_RUN") ? std::max(1, atoi(getenv("JXL_SPECIAL_RUN"))) : 0;
-            const int run = run_env ? run_env : wg_items ? 12 : 32;  // about the items of the few groups one item spans
+            constexpr int run = 32;  // about the items of the few groups one item spans
             std::vector<WorkItem> q[8];
             for (size_t i = 0; i < ord.size(); i++) q[(i / (size_t)run) % 8].push_back(ord[i].w);
             size_t longest = 0;
@@ -720,7 +709,6 @@ jxl_status finalize_tables(jxl_ctx* c) {
         } else {
             for (const Ord& o : ord) items.push_back(o.w);
         }
-        sl.wg_items = wg_items;
         sl.n_items = (int)items.size() - sl.items_off;
         if (sl.n_items > 0) c->special_launches.push_back(sl);
     };
@@ -777,15 +765,12 @@ jxl_status finalize_tables(jxl_ctx* c) {
     const size_t nc = (size_t)c->bh * c->bw, nt = (size_t)c->th * c->tw;
     // item lists of the persistent / wave kernels
     std::vector<int> wg3_tab[2];
-    {
-        static const bool spatial = !(getenv("JXL_WG3_SPATIAL") && atoi(getenv("JXL_WG3_SPATIAL")) == 0);
-        for (int k = 0; k < 2; k++) {
-            c->wg3_item_count[k] = 0;
-            for (const auto& tl : c->type_launches) {
-                if (tl.cls != 2 + k) continue;
-                wg3_item_table(c->h_blocks.data(), c->bw, tl.segs.data(), (int)tl.segs.size(), k, c->woffs, spatial, wg3_tab[k], wg3_grid_cap(k == 1));
-                c->wg3_item_count[k] = (int)(wg3_tab[k].size() / 8);
-            }
+    for (int k = 0; k < 2; k++) {
+        c->wg3_item_count[k] = 0;
+        for (const auto& tl : c->type_launches) {
+            if (tl.cls != 2 + k) continue;
+            wg3_item_table(c->h_blocks.data(), c->bw, tl.segs.data(), (int)tl.segs.size(), k, c->woffs, wg3_tab[k], wg3_grid_cap(k == 1));
+            c->wg3_item_count[k] = (int)(wg3_tab[k].size() / 8);
         }
     }
     mark("item tables");
@@ -871,9 +856,9 @@ jxl_status finalize_tables(jxl_ctx* c) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));  // lfq_tmp is reused by the next job
     }
     // llf starts as a copy of lf (the LLF of an 8x8 block is its LF sample); k_llf overwrites the cells of the 128 / 256-edge
-    // blocks and (JXL_WG3_LLF_IN_ITEM=0) k_llf_wg3 those of every block above 8x8. With neither, nothing ever writes the llf
-    // planes: the kernels are handed the lf planes under both names and the three plane copies are not made (r4)
-    c->llf_alias = c->large_count == 0 && wg3_llf_in_item();
+    // blocks. Without such blocks nothing ever writes the llf planes: the kernels are handed the lf planes under both names and
+    // the three plane copies are not made (r4)
+    c->llf_alias = c->large_count == 0;
     if (!c->llf_alias)
         for (int ch = 0; ch < 3; ch++)
             HIP_TRY(c, hipMemcpyAsync(c->llf[ch].p, c->lf[ch].p, 4 * nc, hipMemcpyDeviceToDevice, c->stream));
@@ -1146,7 +1131,7 @@ extern "C" int jxl_debug_wg3_item_table(const int32_t* types, const int32_t* n_b
     }
     int32_t woffs[3 * 17] = {};
     std::vector<int> tab;
-    wg3_item_table(blocks.data(), frame_bw, segs.data(), (int)segs.size(), 0, woffs, true, tab, grid);
+    wg3_item_table(blocks.data(), frame_bw, segs.data(), (int)segs.size(), 0, woffs, tab, grid);
     const int n = (int)(tab.size() / 8);
     if (n > cap) return -1;
     std::copy(tab.begin(), tab.end(), out);
@@ -1308,7 +1293,6 @@ jxl_status jxl_ctx_create(int32_t device, jxl_ctx** out) {
     for (int i = 0; i < jxl_ctx::kEvSlots; i++)
         for (int j = 0; j < 2; j++) (void)hipEventCreate(&c->kev[i][j]);
     (void)hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming);
-    (void)hipEventCreateWithFlags(&c->llf_ev, hipEventDisableTiming);
     if (const char* e = getenv("JXL_AUX_STREAMS")) c->n_aux = std::max(0, std::min((int)jxl_ctx::kAux, atoi(e)));
     // (r3: side streams created with hipStreamCreateWithPriority at the highest priority -- meant to keep the few long-running
     // workgroups of the 64-point and special launches from queueing behind the machine-filling main launch -- started those
@@ -1356,9 +1340,7 @@ void jxl_ctx_destroy(jxl_ctx* c) {
         for (int j = 0; j < 2; j++)
             if (c->kev[i][j]) (void)hipEventDestroy(c->kev[i][j]);
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
-    if (c->llf_ev) (void)hipEventDestroy(c->llf_ev);
     if (c->batch_ev) (void)hipEventDestroy(c->batch_ev);
-    c->batch_args.release();
     c->batch_wg3_args.release();
     c->mod_flag.release();
     if (c->mod_flag_host) (void)hipHostFree(c->mod_flag_host);
@@ -1967,101 +1949,51 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
             }
             return fc;
         };
-        // classes 2 / 3 (k_idct_wg3.hip): argument blocks of the two persistent launches and of the LLF launch in front
+        // classes 2 / 3 (k_idct_wg3.hip): argument blocks of the two persistent launches
         // 512 = two 256-thread workgroups per CU (r3; was 768): at 128 VGPRs three of them leave one wave slot per SIMD, and a
         // workgroup of the 64-point launch (512 threads: two waves per SIMD) then fits on no CU until a persistent workgroup of
         // this launch retires -- at its end. With two per CU all 110 workgroups of the 64-point launch are resident at once
         // beside it: single 4K frame 231 -> 214 us, IDCT stage 134 -> 117 us, batch unchanged (49.0 / 48.9 Gpx/s, same box)
         static const int wg3_grid = wg3_grid_cap(false);
         static const int wg3_grid_big = wg3_grid_cap(true);
-        Wg3Args wa[2], wl;
+        Wg3Args wa[2];
         int wn[2] = {0, 0};
-        bool any_llf = false;
-        {
-            std::vector<IdctSegment> all;
-            for (const auto& tl : c->type_launches)
-                if (tl.cls >= 2) {
-                    wn[tl.cls - 2] = build_wg3_args(f, blocks, tl.segs.data(), (int)tl.segs.size(), tl.cls - 2, A, wa[tl.cls - 2]);
-                    if (wn[tl.cls - 2] < 0) return fail(c, JXL_ERR_STATE, "IDCT launch: too many segments");
-                    // (r6: the list may hold holes -- wg3_item_table --: at least one record per item, and the list's length is what the walk is bounded by)
-                    if (c->wg3_item_count[tl.cls - 2] < wn[tl.cls - 2]) return fail(c, JXL_ERR_STATE, "IDCT launch: item list out of date");
-                    if (wn[tl.cls - 2] > 0) wa[tl.cls - 2].total_items = wn[tl.cls - 2] = c->wg3_item_count[tl.cls - 2];
-                    wa[tl.cls - 2].items = c->wg3_items[tl.cls - 2].as<int>();
-                    all.insert(all.end(), tl.segs.begin(), tl.segs.end());
-                }
-            if (!all.empty()) {
-                if (build_wg3_args(f, blocks, all.data(), (int)all.size(), 2, A, wl) < 0) return fail(c, JXL_ERR_STATE, "IDCT launch: too many segments");
-                for (int q = 0; q < wl.n_seg; q++) any_llf = any_llf || (wl.seg[q].type != 0 && !wl.llf_in_item);
+        for (const auto& tl : c->type_launches)
+            if (tl.cls >= 2) {
+                const int k = tl.cls - 2;
+                wn[k] = build_wg3_args(f, blocks, tl.segs.data(), (int)tl.segs.size(), k, A, wa[k]);
+                if (wn[k] < 0) return fail(c, JXL_ERR_STATE, "IDCT launch: too many segments");
+                // (r6: the list may hold holes -- wg3_item_table --: at least one record per item, and the list's length is what the walk is bounded by)
+                if (c->wg3_item_count[k] < wn[k]) return fail(c, JXL_ERR_STATE, "IDCT launch: item list out of date");
+                if (wn[k] > 0) wa[k].total_items = wn[k] = c->wg3_item_count[k];
+                wa[k].items = c->wg3_items[k].as<int>();
             }
-        }
         const int n_k = (int)c->type_launches.size() + (int)c->special_launches.size();
         const bool fork = n_k > 1 && c->n_aux > 0;
         if (wn[0] > 0 || wn[1] > 0) {
-            // Frame without chroma subsampling. The long pole is the persistent launch of everything up to 32 points (with the
-            // 8x8 DCTs: ~80 % of the pixels): it goes on the main stream right behind the LLF launch it depends on. The special
-            // 8x8 transforms need no LLF and start at once on the side stream; the 64-point family follows them there, behind an
-            // event that says the LLF planes are written. (Measured on the 4K default mix: LLF as two launches in front of
-            // everything, the special kernel queued behind the 64-point launch: 112 us; this order: see profiles/.)
+            // Frame without chroma subsampling: at most two launches, neither depending on the other (finalizeLLF runs inside the
+            // items). The 512-thread launch of 64x32 / 32x64 blocks is ONE round of items, i.e. its duration is the latency of a single
+            // item, so it goes first, on the side stream; the launch of everything else (the long pole) on the main stream, then join.
             hipStream_t side = fork ? c->aux[0] : s;
             if (fork) {
                 (void)hipEventRecord(c->fork_ev, s);
                 (void)hipStreamWaitEvent(side, c->fork_ev, 0);
             }
-            static const int plan = getenv("JXL_WG3_PLAN") ? atoi(getenv("JXL_WG3_PLAN")) : 0;
-            // With finalizeLLF inside the items no IDCT launch depends on another. The 64-point launch is ONE round of items (a
-            // 4K frame of the default mix has ~100 of them for 110 workgroups), i.e. its duration is the latency of a single
-            // item -- 28 us alone on the device, 58-72 us beside the other class's workgroups -- so it goes first on the side
-            // stream and the 8x8 special kernel (24 us) behind it, not in front of it
-            static const bool big_first = !(getenv("JXL_WG3_BIG_FIRST") && atoi(getenv("JXL_WG3_BIG_FIRST")) == 0);
-            // experiment (JXL_WG3_BIG_AFTER=1): the 64-point launch on the MAIN stream behind the <= 32-point launch, so that no CU
-            // ever holds two workgroups of each (4 x 128 registers per lane: no room for a restoration workgroup of another frame)
-            static const bool big_after = getenv("JXL_WG3_BIG_AFTER") && atoi(getenv("JXL_WG3_BIG_AFTER")) != 0;
-            const bool big_early = big_first && !big_after && plan != 1 && !any_llf && wn[1] > 0;
-            if (big_early) {
+            if (wn[1] > 0) {
                 launch_idct_wg3(wa[1], true, wg3_grid_big, side);
                 launches++;
             }
-            for (const auto& sl : c->special_launches) {
-                launch_idct_special(frame_of(sl.channel), blocks, items + sl.items_off, sl.n_items, A, side, sl.wg_items);
-                launches++;
-            }
-            if (any_llf) {
-                float* L[3] = {c->llf[0].as<float>(), c->llf[1].as<float>(), c->llf[2].as<float>()};
-                launch_llf_wg3(wl, L, s);
-                launches++;
-                if (fork && wn[1] > 0) {
-                    (void)hipEventRecord(c->llf_ev, s);  // "LLF planes written"
-                    (void)hipStreamWaitEvent(side, c->llf_ev, 0);
-                }
-            }
-            hipStream_t s_small = plan == 1 ? side : s, s_big = plan == 1 ? s : side;
-            if (plan == 1 && fork && any_llf && wn[0] > 0 && wn[1] <= 0) {
-                (void)hipEventRecord(c->llf_ev, s);
-                (void)hipStreamWaitEvent(side, c->llf_ev, 0);
-            }
-            if (plan == 1 && wn[1] > 0) {
-                launch_idct_wg3(wa[1], true, wg3_grid_big, s_big);
-                launches++;
-            }
             if (wn[0] > 0) {
-                launch_idct_wg3(wa[0], false, wg3_grid, s_small);
+                launch_idct_wg3(wa[0], false, wg3_grid, s);
                 launches++;
             }
-            if (plan != 1 && wn[1] > 0 && !big_early) {
-                launch_idct_wg3(wa[1], true, wg3_grid_big, big_after ? s : s_big);
-                launches++;
-            }
-            for (const auto& tl : c->type_launches)  // nothing today: every class 0 / 1 type of such a frame is handled above
-                if (tl.cls < 2) {
-                    launch_idct_multi(frame_of(tl.channel), blocks, tl.cls, tl.segs.data(), (int)tl.segs.size(), 3, 0, A, s);
-                    launches++;
-                }
             if (fork) {
                 (void)hipEventRecord(c->join_ev[0], side);
                 (void)hipStreamWaitEvent(s, c->join_ev[0], 0);
             }
         } else {
-            // fork: every type kernel writes a disjoint set of varblocks
+            // chroma-subsampled frame: per channel, the class launches and the special one; fork: every launch writes a disjoint set
+            // of varblocks
             int used = 0;
             if (fork) {
                 (void)hipEventRecord(c->fork_ev, s);
@@ -2071,11 +2003,11 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
             int k = 0;
             auto pick = [&]() { const int i = k++; return (!fork || i % (used + 1) == 0) ? s : c->aux[i % (used + 1) - 1]; };
             for (const auto& tl : c->type_launches) {
-                launch_idct_multi(frame_of(tl.channel), blocks, tl.cls, tl.segs.data(), (int)tl.segs.size(), tl.channel < 0 ? 3 : 1, tl.channel < 0 ? 0 : tl.channel, A, pick());
+                launch_idct_multi(frame_of(tl.channel), blocks, tl.cls, tl.segs.data(), (int)tl.segs.size(), tl.channel, A, pick());
                 launches++;
             }
             for (const auto& sl : c->special_launches) {
-                launch_idct_special(frame_of(sl.channel), blocks, items + sl.items_off, sl.n_items, A, pick(), sl.wg_items);
+                launch_idct_special(frame_of(sl.channel), blocks, items + sl.items_off, sl.n_items, A, pick());
                 launches++;
             }
             if (fork)
@@ -2234,8 +2166,6 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
 
 // frames whose IDCT stage can share launches: plain 4:4:4 frames made of the merged-launch types
 bool batchable(const jxl_ctx* c) {
-    for (const auto& sl : c->special_launches)
-        if (!sl.wg_items) return false;  // k_idct_special_batch takes workgroup items
     return c->frame_open && !c->sub && c->large_count == 0 && c->llf_count == 0 && (c->p.stages & JXL_STAGE_IDCT);
 }
 }  // namespace
@@ -2252,7 +2182,7 @@ jxl_status jxl_vardct_prepare(jxl_ctx* c) {
 jxl_status jxl_vardct_run(jxl_ctx* c) { return run_frame(c, false); }
 
 // A batch of independent frames (one context each, all on one device): the IDCT stage of the whole batch runs as ONE
-// launch per register class (k_idct_multi_batch, blockIdx.y = frame), on the first context's stream; every frame's
+// launch per register class (k_idct_wg3_batch, blockIdx.y = frame), on the first context's streams; every frame's
 // restoration kernel then runs on its own stream as in jxl_vardct_run. Per-frame argument blocks live in device memory
 // and are rebuilt only when a frame's binned work changed. Frames the batched kernels do not cover (chroma subsampling,
 // 128/256-edge varblocks) make the call fall back to n plain runs. Results are those of n jxl_vardct_run calls.
@@ -2286,92 +2216,45 @@ jxl_status jxl_vardct_run_batch(jxl_ctx* const* ctxs, int32_t n) {
     bool same = (int)c0->batch_key.size() == n;
     for (int i = 0; i < n && same; i++) same = c0->batch_key[i].first == ctxs[i] && c0->batch_key[i].second == ctxs[i]->tables_gen;
     if (!same) {
-        std::vector<MultiArgs> host_args;
         c0->batch_launches.clear();
-        for (int cls : {1, 0, 3}) {  // launch order of jxl_vardct_run: heaviest class first, the special kernel last
-            jxl_ctx::BatchLaunch bl{cls, 0, 0, 0, host_args.size() * sizeof(MultiArgs)};
-            for (int i = 0; i < n; i++) {
-                jxl_ctx* c = ctxs[i];
-                DevFrame f;
-                fill_dev_frame(c, f);
-                float* A[3] = {c->planeA[0].as<float>(), c->planeA[1].as<float>(), c->planeA[2].as<float>()};
-                MultiArgs a{};
-                if (cls == 3) {
-                    if (c->special_launches.empty()) continue;
-                    const auto& sl = c->special_launches[0];
-                    a.f = f;
-                    a.blocks = c->blocks.as<DevBlock>();
-                    a.items = c->items.as<WorkItem>() + sl.items_off;
-                    a.seg_n[0] = sl.n_items;
-                    a.o0 = A[0]; a.o1 = A[1]; a.o2 = A[2];
-                    bl.grid_x = std::max(bl.grid_x, sl.n_items);
-                } else {
-                    const jxl_ctx::TypeLaunch* tl = nullptr;
-                    for (const auto& t : c->type_launches)
-                        if (t.cls == cls) tl = &t;
-                    if (!tl) continue;
-                    size_t lds = 0;
-                    const int g = build_idct_multi_args(f, c->blocks.as<DevBlock>(), tl->segs.data(), (int)tl->segs.size(), 3, 0, A, a, &lds);
-                    if (g < 0) return fail(c0, JXL_ERR_STATE, "IDCT launch: too many segments");
-                    if (g <= 0) continue;
-                    bl.grid_x = std::max(bl.grid_x, g);
-                    bl.lds_bytes = std::max(bl.lds_bytes, lds);
-                }
-                host_args.push_back(a);
-                bl.n_frames++;
-            }
-            if (bl.n_frames > 0) c0->batch_launches.push_back(bl);
-        }
-        // the persistent three-channel kernels (k_idct_wg3.hip): LLF pre-pass of both classes, then the two classes
+        // the persistent three-channel kernels (k_idct_wg3.hip), one launch per class
         std::vector<Wg3Args> wg3_args;
-        static const int wg3_cap = getenv("JXL_WG3_GRID") ? atoi(getenv("JXL_WG3_GRID")) : 768;
-        static const int wg3_cap_big = getenv("JXL_WG3_GRID_BIG") ? atoi(getenv("JXL_WG3_GRID_BIG")) : 512;
-        for (int cls : {10, 11, 12}) {
+        for (int cls : {11, 12}) {
+            const int which = cls - 11;
             jxl_ctx::BatchLaunch bl{cls, 0, 0, 0, wg3_args.size() * sizeof(Wg3Args)};
-            int64_t max_n = 0;
+            int max_n = 0;
             for (int i = 0; i < n; i++) {
                 jxl_ctx* c = ctxs[i];
                 DevFrame f;
                 fill_dev_frame(c, f);
                 float* A[3] = {c->planeA[0].as<float>(), c->planeA[1].as<float>(), c->planeA[2].as<float>()};
-                std::vector<IdctSegment> segs;
-                for (const auto& tl : c->type_launches)
-                    if (tl.cls >= 2 && (cls == 10 || tl.cls == cls - 9)) segs.insert(segs.end(), tl.segs.begin(), tl.segs.end());
-                if (segs.empty()) continue;
+                const jxl_ctx::TypeLaunch* tl = nullptr;
+                for (const auto& t : c->type_launches)
+                    if (t.cls == which + 2) tl = &t;
+                if (!tl) continue;
                 Wg3Args a;
-                const int items = build_wg3_args(f, c->blocks.as<DevBlock>(), segs.data(), (int)segs.size(), cls == 10 ? 2 : cls - 11, A, a);
+                const int items = build_wg3_args(f, c->blocks.as<DevBlock>(), tl->segs.data(), (int)tl->segs.size(), which, A, a);
                 if (items < 0) return fail(c0, JXL_ERR_STATE, "IDCT launch: too many segments");
                 if (items <= 0) continue;
-                if (cls != 10) {
-                    if (c->wg3_item_count[cls - 11] < items) return fail(c0, JXL_ERR_STATE, "IDCT launch: item list out of date");
-                    a.total_items = c->wg3_item_count[cls - 11];
-                    a.items = c->wg3_items[cls - 11].as<int>();
-                }
-                if (cls == 10) {
-                    const int64_t nl = a.llf_in_item ? 0 : wg3_llf_count(a);  // the items do finalizeLLF themselves: no launch
-                    if (nl <= 0) continue;
-                    max_n = std::max(max_n, nl);
-                } else {
-                    max_n = std::max<int64_t>(max_n, items);
-                    bl.lds_bytes = std::max(bl.lds_bytes, wg3_lds_bytes(a));
-                }
+                if (c->wg3_item_count[which] < items) return fail(c0, JXL_ERR_STATE, "IDCT launch: item list out of date");
+                a.total_items = c->wg3_item_count[which];
+                a.items = c->wg3_items[which].as<int>();
+                max_n = std::max(max_n, items);
+                bl.lds_bytes = std::max(bl.lds_bytes, wg3_lds_bytes(a));
                 wg3_args.push_back(a);
                 bl.n_frames++;
             }
             if (bl.n_frames <= 0) continue;
             // persistent grids: the chip-wide cap shared between the frames of the launch
-            const int cap = cls == 11 ? wg3_cap : wg3_cap_big;
-            bl.grid_x = cls == 10 ? (int)std::min<int64_t>(max_n, INT32_MAX) : (int)std::min<int64_t>(max_n, std::max(1, (cap + bl.n_frames - 1) / bl.n_frames));
+            const int cap = wg3_grid_cap(which == 1);
+            bl.grid_x = std::min(max_n, std::max(1, (cap + bl.n_frames - 1) / bl.n_frames));
             c0->batch_launches.push_back(bl);
         }
         HIP_TRY(c0, hipSetDevice(c0->device));
-        if (!c0->batch_args.ensure(std::max<size_t>(sizeof(MultiArgs), host_args.size() * sizeof(MultiArgs))) ||
-            !c0->batch_wg3_args.ensure(std::max<size_t>(sizeof(Wg3Args), wg3_args.size() * sizeof(Wg3Args))))
+        if (!c0->batch_wg3_args.ensure(std::max<size_t>(sizeof(Wg3Args), wg3_args.size() * sizeof(Wg3Args))))
             return fail(c0, JXL_ERR_OOM, "device allocation failed (batch arguments)");
         HIP_TRY(c0, hipStreamSynchronize(c0->stream));  // an earlier batch may still be reading the old blocks
         if (c0->n_aux > 0) HIP_TRY(c0, hipStreamSynchronize(c0->aux[0]));
-        if (!host_args.empty())
-            HIP_TRY(c0, hipMemcpy(c0->batch_args.p, host_args.data(), host_args.size() * sizeof(MultiArgs), hipMemcpyHostToDevice));
         if (!wg3_args.empty())
             HIP_TRY(c0, hipMemcpy(c0->batch_wg3_args.p, wg3_args.data(), wg3_args.size() * sizeof(Wg3Args), hipMemcpyHostToDevice));
         c0->batch_key.clear();
@@ -2390,27 +2273,11 @@ jxl_status jxl_vardct_run_batch(jxl_ctx* const* ctxs, int32_t n) {
         (void)hipEventRecord(c0->fork_ev, s0);
         (void)hipStreamWaitEvent(c0->aux[0], c0->fork_ev, 0);
     }
-    // as in run_frame: the special kernel (no LLF needed) and the 64-point family go to the side stream, the LLF pre-pass and
-    // the launch of everything up to 32 points to the main one; the r1 classes alternate
-    int k = 0;
+    // as in run_frame: the 512-thread class on the side stream, the 256-thread class on the main one
     hipStream_t side = fork ? c0->aux[0] : s0;
     for (const auto& bl : c0->batch_launches) {
-        if (bl.cls >= 10) {
-            const Wg3Args* da = reinterpret_cast<const Wg3Args*>(static_cast<const char*>(c0->batch_wg3_args.p) + bl.offset);
-            if (bl.cls == 10) {
-                launch_llf_wg3_batch(da, bl.n_frames, bl.grid_x, s0);
-                if (fork) {
-                    (void)hipEventRecord(c0->llf_ev, s0);  // "LLF planes written"
-                    (void)hipStreamWaitEvent(side, c0->llf_ev, 0);
-                }
-            } else {
-                launch_idct_wg3_batch(da, bl.n_frames, bl.cls == 12, bl.grid_x, bl.lds_bytes, bl.cls == 12 ? side : s0);
-            }
-            continue;
-        }
-        const MultiArgs* da = reinterpret_cast<const MultiArgs*>(static_cast<const char*>(c0->batch_args.p) + bl.offset);
-        if (bl.cls == 3) launch_idct_special_batch(da, bl.n_frames, bl.grid_x, side);
-        else launch_idct_multi_batch(da, bl.n_frames, bl.grid_x, bl.lds_bytes, bl.cls, (fork && (k++ & 1)) ? side : s0);
+        const Wg3Args* da = reinterpret_cast<const Wg3Args*>(static_cast<const char*>(c0->batch_wg3_args.p) + bl.offset);
+        launch_idct_wg3_batch(da, bl.n_frames, bl.cls == 12, bl.grid_x, bl.lds_bytes, bl.cls == 12 ? side : s0);
     }
     if (fork) {
         (void)hipEventRecord(c0->join_ev[0], c0->aux[0]);

@@ -1,6 +1,6 @@
 // Register-array forms of the 8x8-footprint transforms of PassGroup.invertVarDCT (J/frame/group/PassGroup.java:88-168, 229-328) and of
 // MathHelper.inverseDCT2D for 2..8 points (J/util/MathHelper.java:68-122): a lane holds a whole block of one channel. Shared by
-// k_idct.hip (k_idct_special_wg, the per-channel kernels) and, since r6, by the special-type items of the persistent launch in
+// k_idct.hip (k_idct_special, the lane-per-block kernel of chroma-subsampled frames) and, since r6, by the special-type items of the persistent launch in
 // k_idct_wg3.hip. Included INSIDE namespace jxl of a translation unit that has included jxl_tables.h (JXL_AFV_BASIS_INIT).
 #pragma once
 #include "lut_small.inc"

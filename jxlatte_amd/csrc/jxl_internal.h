@@ -95,18 +95,18 @@ struct MultiArgs {
     static constexpr int kMaxSeg = 12;
     DevFrame f;
     const DevBlock* blocks;
-    const WorkItem* items;
+    const WorkItem* items;  // (no reader left: items are implicit, see below)
     int n_seg;
     int seg_b0[kMaxSeg + 1];  // first workgroup of segment k (a multiple of 8); seg_b0[n_seg] = grid size
     int seg_n[kMaxSeg];       // items in segment k
     int seg_type[kMaxSeg];    // TransformType.type of segment k
     int seg_first[kMaxSeg];   // first block of the type in `blocks`
     int seg_nblocks[kMaxSeg]; // blocks of the type
-    int nch, ch0;             // channels per block group (3, or 1 for a chroma-subsampled frame's per-channel launch), first one
+    int nch, ch0;             // channels per block group (always 1: a chroma-subsampled frame's per-channel launch), the channel
     float *o0, *o1, *o2;
 };
-// work items are implicit: item i of a segment = channel ch0 + i % nch of block group i / nch, a group being
-// medium_blocks_per_wg(type) consecutive blocks (no item table to load before the block records)
+// work items are implicit: item i of a segment = block group i of channel ch0, a group being medium_blocks_per_wg(type)
+// consecutive blocks (no item table to load before the block records)
 struct IdctSegment { int type, first_block, n_blocks; };
 
 // Argument block of the persistent three-channel IDCT launch (k_idct_wg3.hip): type-uniform segments in launch order
@@ -118,7 +118,7 @@ struct Wg3Args {
     float *o0, *o1, *o2;
     int n_seg, total_items;
     int img_floats;  // floats of the largest three-channel LDS image among the segments' types (the tables follow it)
-    int llf_in_item;  // 1: the items transform their blocks' LF patches themselves (finalizeLLF); 0: k_llf_wg3 ran before (llf planes)
+    int llf_in_item;  // always 1: the items transform their blocks' LF patches themselves (finalizeLLF)
     // the item list: 32-byte records {type, first_block, n_blocks, geometry word (wg3_geo), weight offsets of the three channels, 0},
     // total_items of them, in the order the workgroups take them (wg3_item_table: spatial, dealt to the XCDs, cost-balanced)
     const int* items;
@@ -126,37 +126,26 @@ struct Wg3Args {
 };
 
 // the item list of one class's segments in spatial order, dealt to the XCDs in runs (host side)
-void wg3_item_table(const DevBlock* host_blocks, int frame_bw, const IdctSegment* segs, int n_seg, int which, const int32_t* woffs, bool spatial,
+void wg3_item_table(const DevBlock* host_blocks, int frame_bw, const IdctSegment* segs, int n_seg, int which, const int32_t* woffs,
                     std::vector<int>& out, int grid);
 int wg3_grid_cap(bool big);  // workgroups of a single-frame launch (JXL_WG3_GRID / JXL_WG3_GRID_BIG)
-bool wg3_handles(int type);
-bool wg3_special_items();  // r6: the special 8x8 types are items of the persistent launch
-bool wg3_big(int type);  // the 64-point family: its own launch (register / LDS class)
-bool wg3_llf_in_item();  // finalizeLLF inside the k_idct_wg3 items (default) or as a launch of its own writing the llf planes
+bool wg3_handles(int type);  // every type but the 128/256-edge ones (frames without chroma subsampling)
+bool wg3_big(int type);  // 64x32 / 32x64: the 512-thread launch (register / LDS class)
 int build_wg3_args(const DevFrame& f, const DevBlock* blocks, const IdctSegment* segs, int n_seg, int which, float* const out[3],
                    Wg3Args& a);
-void launch_llf_wg3(const Wg3Args& a, float* const llf[3], hipStream_t s);
 void launch_idct_wg3(const Wg3Args& a, bool big, int grid_cap, hipStream_t s);
-int64_t wg3_llf_count(const Wg3Args& a);
 size_t wg3_lds_bytes(const Wg3Args& a);
-void launch_llf_wg3_batch(const Wg3Args* dev_args, int n_frames, int64_t max_llf, hipStream_t s);
 void launch_idct_wg3_batch(const Wg3Args* dev_args, int n_frames, bool big, int grid_x, size_t lds, hipStream_t s);
 
 
 // ---- launchers (defined in the kernel TUs) ---------------------------------------------------
-// One launch per register class (0: every type up to 32x32, 1: the 64-point family), 256-thread workgroups.
-// WorkItem.type = TransformType.type | channel << 8; an item covers up to medium_blocks_per_wg(type) blocks of that channel.
+// Chroma-subsampled frames: one launch per register class (0: every type up to 32x32, 1: the 64-point family) and channel ch,
+// 256-thread workgroups. An item covers up to medium_blocks_per_wg(type) blocks of that channel.
 int idct_class_of(int type);
-void launch_idct_multi(const DevFrame& f, const DevBlock* blocks, int cls, const IdctSegment* segs, int n_seg, int nch, int ch0,
+void launch_idct_multi(const DevFrame& f, const DevBlock* blocks, int cls, const IdctSegment* segs, int n_seg, int ch,
                        float* const out[3], hipStream_t s);
-int build_idct_multi_args(const DevFrame& f, const DevBlock* blocks, const IdctSegment* segs, int n_seg, int nch, int ch0,
-                          float* const out[3], MultiArgs& a, size_t* lds_bytes_out);
-// batch of frames: one MultiArgs block per frame in device memory (blockIdx.y); see k_idct_multi_batch
-void launch_idct_multi_batch(const MultiArgs* dev_args, int n_frames, int grid_x, size_t lds_bytes, int cls, hipStream_t s);
-void launch_idct_special_batch(const MultiArgs* dev_args, int n_frames, int max_items, hipStream_t s);
-// the special 8x8-footprint types: items of up to 64 blocks (one per lane)
-void launch_idct_special(const DevFrame& f, const DevBlock* blocks, const WorkItem* items, int n_items, float* const out[3],
-                         hipStream_t s, bool wg_items);
+// the special 8x8-footprint types: items of up to 64 blocks (one per lane) of one channel, WorkItem.type = TransformType.type | channel << 8
+void launch_idct_special(const DevFrame& f, const DevBlock* blocks, const WorkItem* items, int n_items, float* const out[3], hipStream_t s);
 int medium_blocks_per_wg(int type);
 // finalizeLLF of blocks[first..first+count) (all larger than 8x8) into the llf planes
 void launch_llf(const DevFrame& f, const DevBlock* blocks, int first, int count, float* const llf[3], hipStream_t s);

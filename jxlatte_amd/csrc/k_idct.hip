@@ -13,8 +13,7 @@
 // Three kernel families, all type-uniform per workgroup so there is no divergence:
 //   special : Hornuss, DCT2, DCT4, DCT4x8, DCT8x4, AFV0-3. One LANE per (varblock, channel), the whole
 //             8x8 block lives in VGPRs, every LUT / AFV-basis factor is an instruction literal.
-//   wave    : DCT8, DCT16 and the 16x8 rectangles. One WAVE = 64/max(H,W) blocks, their three channels one after
-//             the other (luma first: its dequantised column stays in registers for chroma-from-luma):
+//   wave    : DCT8, DCT16 and the 16x8 rectangles. One WAVE = 64/max(H,W) blocks of one channel:
 //             lane = one column, coefficient rows streamed from HBM in order (dequantised on the fly),
 //             accumulators in VGPRs, LUT rows wave-uniform (scalar loads); transpose through a
 //             wave-private LDS image; lane = one row for the row pass.
@@ -23,8 +22,9 @@
 //             waves (8 or 16 outputs per lane) so that no lane runs a 2x63x64-instruction chain.
 //   large   : 128/256-edge blocks do not fit LDS: dequant -> column pass -> row pass through a
 //             scratch plane, 64x64 register tiles per wave.
-// Launches: one per register class (k_idct_multi<CLASS>: every type of the class in one grid) + the special kernel;
-// k_idct_multi_batch / k_idct_special_batch are the same bodies over a batch of frames (blockIdx.y = frame).
+// Launches: one per register class and channel (k_idct_multi<CLASS>: every type of the class in one grid) + the special kernel.
+// Since r6 frames without chroma subsampling take the persistent three-channel launch of k_idct_wg3.hip instead; these kernels
+// serve chroma-subsampled frames (and, with k_llf, the large blocks of every frame).
 #include "jxl_internal.h"
 #include "../../include/jxl_tables.h"
 #include <cstdlib>
@@ -517,114 +517,6 @@ __device__ __forceinline__ void medium_item(const DevFrame& f, const DevBlock* _
     }
 }
 
-// The same transform for all three channels of the wave's blocks, luma first: the dequantised luma column stays in
-// registers and feeds chromaFromLuma of X and B, instead of being loaded and dequantised again by separate chroma work
-// items (5 coefficient + 5 weight loads and 5 dequantisations per pixel become 3 + 3 + 3). Used for frames without
-// chroma subsampling; the channel loop is rolled, so the code size is that of medium_item.
-template <int H, int W, int TYPE>
-__device__ __forceinline__ void medium_item3(const DevFrame& f, const DevBlock* __restrict__ blocks, const WorkItem it,
-                                             float* __restrict__ lds_wg, float* __restrict__ o0, float* __restrict__ o1,
-                                             float* __restrict__ o2) {
-    using Cfg = MediumCfg<H, W>;
-    constexpr int LD = Cfg::LD, IMG = Cfg::IMG;
-    constexpr int PI = JXL_TT[TYPE].param_index;
-    constexpr bool FLIP = H >= W;  // TransformType.flip() for METHOD_DCT
-    constexpr int DSH = H / 8, DSW = W / 8;
-    constexpr int RC = 8;
-    const int wave = threadIdx.x >> 6;
-    const int lane = threadIdx.x & 63;
-    const int wfirst = (int)it.first + wave * Cfg::BPW;
-    const int nb = min(max((int)it.count - wave * Cfg::BPW, 0), Cfg::BPW);
-    float* lds = lds_wg + wave * (Cfg::BPW * IMG);
-    const int FW = f.width;
-    const float qbn = f.quant_bias_numerator;
-    // qbn / |q| table, one per WAVE (64 entries, one division per lane): with the wave-private transposes this leaves the
-    // wave path without a single workgroup barrier -- the four waves of a workgroup never wait for each other
-    float* qtab = lds_wg + 4 * Cfg::BPW * IMG + wave * 64;
-    const int bi_col = lane / W, x = lane % W;
-    const int bi_row = lane / H, y = lane % H;
-    JXL_STAMP(0);
-    JXL_STAMP_VAL(7, TYPE);
-    DevBlock b_col{}, b_row{};
-    if (bi_col < nb) b_col = load_block(blocks, wfirst + bi_col);
-    if (bi_row < nb) b_row = load_block(blocks, wfirst + bi_row);
-    qtab[lane] = lane > 0 ? qbn / (float)lane : 0.0f;
-    wave_lds_fence();
-    const int py0 = b_col.cy * 8, px0 = b_col.cx * 8;
-    const float hfm = (float)b_col.hf_mul;
-    const int ty0 = py0 >> 6, tx0 = px0 >> 6;
-    const int tx = (px0 + x) >> 6;
-    const cfloatp lut_h = as_const(f.lut + lut_off(ceil_log2_dev(H)));
-    const cfloatp lut_w = as_const(f.lut + lut_off(ceil_log2_dev(W)));
-    float dyv[H];  // dequantised luma of this lane's column (HFCoefficients.java:186-188 reads it for X and B)
-#pragma unroll
-    for (int n = 0; n < H; n++) dyv[n] = 0.0f;
-#pragma unroll 1
-    for (int pass = 0; pass < 3; pass++) {
-        const int c = pass == 0 ? 1 : pass == 1 ? 0 : 2;
-        // ---- column pass
-        if (bi_col < nb) {
-            const int* qc_plane = f.coeff[c];
-            const float* wc = (FLIP ? f.weights_t : f.weights) + f.woffs[PI * 3 + c];
-            const float sfc = f.scale_factor[c] / hfm;
-            const float qbc = f.quant_bias[c];
-            const float* lfp = f.lf[c] + (int64_t)b_col.cy * f.bw + b_col.cx;
-            float kcfl = 0.0f;
-            MirrorAcc<H> acc;
-#pragma unroll
-            for (int n0 = 0; n0 < H; n0 += RC) {
-                int qcv[RC];
-                float wcv[RC];
-                static_assert(RC == 4 || RC == 8, "a chunk of rows stays inside one cell row of the tiled plane");
-                const int64_t off0 = coeff_off(FW, py0 + n0, px0 + x);
-#pragma unroll
-                for (int r = 0; r < RC; r++) {
-                    qcv[r] = qc_plane[off0 + r * 8];
-                    wcv[r] = wc[(n0 + r) * W + x];  // (FLIP ? transposed table : table)[n][x]
-                }
-#pragma unroll
-                for (int r = 0; r < RC; r++) {
-                    const int n = n0 + r;
-                    if (c != 1 && (n == 0 || ((py0 + n) & 63) == 0)) {  // entering a new CfL tile row
-                        const int ty = (py0 + n) >> 6;
-                        float kX, kB;
-                        cfl_factors(f, ty, tx, (b_col.cfl_zero >> ((ty - ty0) * 5 + (tx - tx0))) & 1u, kX, kB);
-                        kcfl = c == 0 ? kX : kB;
-                    }
-                    float co = dequant1_tab(qcv[r], qbc, qbn, sfc, wcv[r], qtab);
-                    if (c == 1) dyv[n] = co;
-                    else co = co + kcfl * dyv[n];  // chromaFromLuma (:186-188)
-                    if (n < DSH && x < DSW) co = llf_coeff<DSH, DSW>(f, lfp, n, x);  // finalizeLLF (:194-229)
-                    if (n == 0) acc.init(co);
-                    else if (r & 1) acc.template step<true>(co, lut_h + (n - 1) * H);
-                    else acc.template step<false>(co, lut_h + (n - 1) * H);
-                }
-            }
-            float* dcol = lds + bi_col * IMG + x;
-#pragma unroll
-            for (int k = 0; k < H; k++) dcol[k * LD] = acc.get(k);
-        }
-        wave_lds_fence();  // the wave's image is complete before its own row pass reads it
-        // ---- row pass
-        if (bi_row < nb) {
-            const float* row = lds + bi_row * IMG + y * LD;
-            MirrorAcc<W> acc;
-            acc.init(row[0]);
-#pragma unroll 4
-            for (int n = 1; n < W; n += 2) {  // (odd, even) pairs; W is even, so the last odd n stands alone
-                acc.template step<true>(row[n], lut_w + (n - 1) * W);
-                if (n + 1 < W) acc.template step<false>(row[n + 1], lut_w + n * W);
-            }
-            float* o = (c == 0 ? o0 : c == 1 ? o1 : o2) + (int64_t)(b_row.cy * 8 + y) * FW + b_row.cx * 8;
-#pragma unroll
-            for (int k = 0; k < W; k += 4) *reinterpret_cast<float4*>(o + k) = make_float4(acc.get(k), acc.get(k + 1), acc.get(k + 2), acc.get(k + 3));
-        }
-        wave_lds_fence();  // the row pass has read the image before the next channel's column pass overwrites it
-        JXL_STAMP(1 + pass);
-    }
-    JXL_STAMP(5);
-}
-
 // finalizeLLF (HFCoefficients.java:194-229) of every block larger than 8x8, written over the block's own cells
 // of the llf planes (a block covers exactly dctSelectHeight x dctSelectWidth cells). grid = (3, nblocks).
 __global__ __launch_bounds__(256) void k_llf(const DevFrame f, const DevBlock* __restrict__ blocks, int first, float* l0, float* l1,
@@ -825,28 +717,23 @@ __host__ __device__ constexpr bool use_wg_path(int h, int w) { return (h > w ? h
 //      the XCD-aware order applied inside each segment;
 //  (4) work items are implicit (segment descriptors in the kernel arguments) and the block record carries hfMultiplier,
 //      so a workgroup's first dependent load is already its coefficients' address.
-// 4K mixed frame: 12 launches -> 3 (+ the restoration kernel).
-// ALLCH (frames without chroma subsampling): a wave-path item is a block group with all three channels (medium_item3);
-// everything else -- the LDS-staged types, and every type of a per-channel launch -- is (block group, channel)
-template <int H, int W, int TYPE, bool ALLCH>
+// 4K mixed frame: 12 launches -> 3 (+ the restoration kernel). Since r6 only chroma-subsampled frames take these kernels, one launch
+// per channel and class: an item is (block group, channel a.ch0).
+template <int H, int W, int TYPE>
 __device__ __forceinline__ void type_body(const MultiArgs& a, int k, int li, float* lds) {
     constexpr int NB = use_wg_path(H, W) ? 64 / (H < W ? H : W) : 4 * (64 / (H > W ? H : W));
-    constexpr bool ITEM3 = ALLCH && !use_wg_path(H, W);
-    const int g = ITEM3 ? li : ALLCH ? li / 3 : li;
-    const int ch = ITEM3 ? 0 : ALLCH ? li - 3 * g : a.ch0;
     WorkItem it;
-    it.type = (uint32_t)TYPE | ((uint32_t)ch << 8);
-    it.first = (uint32_t)(a.seg_first[k] + g * NB);
-    it.count = (uint32_t)min(NB, a.seg_nblocks[k] - g * NB);
+    it.type = (uint32_t)TYPE | ((uint32_t)a.ch0 << 8);
+    it.first = (uint32_t)(a.seg_first[k] + li * NB);
+    it.count = (uint32_t)min(NB, a.seg_nblocks[k] - li * NB);
     if constexpr (use_wg_path(H, W)) wg64_item<H, W, TYPE>(a.f, a.blocks, it, lds, a.o0, a.o1, a.o2);
-    else if constexpr (ALLCH) medium_item3<H, W, TYPE>(a.f, a.blocks, it, lds, a.o0, a.o1, a.o2);
     else medium_item<H, W, TYPE>(a.f, a.blocks, it, lds, a.o0, a.o1, a.o2);
 }
 
-template <int CLASS, bool ALLCH>
+template <int CLASS>
 __device__ __forceinline__ void idct_multi_body(const MultiArgs& a, float* lds) {
     const int b = (int)blockIdx.x;
-    if (b >= a.seg_b0[a.n_seg]) return;  // batched launch: the grid is sized for the frame with the most items
+    if (b >= a.seg_b0[a.n_seg]) return;
     int k = 0;
     while (k + 1 < a.n_seg && b >= a.seg_b0[k + 1]) k++;
     // XCD-aware item order inside the segment (see k_restore_fused): consecutive workgroup ids go to different XCDs, so
@@ -858,43 +745,31 @@ __device__ __forceinline__ void idct_multi_body(const MultiArgs& a, float* lds) 
     const int t = a.seg_type[k];
     if (CLASS == 0) {
         switch (t) {
-        case 0: type_body<8, 8, 0, ALLCH>(a, k, li, lds); break;
-        case 5: type_body<32, 32, 5, ALLCH>(a, k, li, lds); break;
-        case 7: type_body<8, 16, 7, ALLCH>(a, k, li, lds); break;
-        case 8: type_body<32, 8, 8, ALLCH>(a, k, li, lds); break;
-        case 9: type_body<8, 32, 9, ALLCH>(a, k, li, lds); break;
-        case 10: type_body<32, 16, 10, ALLCH>(a, k, li, lds); break;
-        case 11: type_body<16, 32, 11, ALLCH>(a, k, li, lds); break;
+        case 0: type_body<8, 8, 0>(a, k, li, lds); break;
+        case 5: type_body<32, 32, 5>(a, k, li, lds); break;
+        case 7: type_body<8, 16, 7>(a, k, li, lds); break;
+        case 8: type_body<32, 8, 8>(a, k, li, lds); break;
+        case 9: type_body<8, 32, 9>(a, k, li, lds); break;
+        case 10: type_body<32, 16, 10>(a, k, li, lds); break;
+        case 11: type_body<16, 32, 11>(a, k, li, lds); break;
         default: break;
         }
     } else {
         switch (t) {
-        case 18: type_body<64, 64, 18, ALLCH>(a, k, li, lds); break;
-        case 19: type_body<64, 32, 19, ALLCH>(a, k, li, lds); break;
-        case 20: type_body<32, 64, 20, ALLCH>(a, k, li, lds); break;
-        case 4: type_body<16, 16, 4, ALLCH>(a, k, li, lds); break;
-        case 6: type_body<16, 8, 6, ALLCH>(a, k, li, lds); break;
+        case 18: type_body<64, 64, 18>(a, k, li, lds); break;
+        case 19: type_body<64, 32, 19>(a, k, li, lds); break;
+        case 20: type_body<32, 64, 20>(a, k, li, lds); break;
+        case 4: type_body<16, 16, 4>(a, k, li, lds); break;
+        case 6: type_body<16, 8, 6>(a, k, li, lds); break;
         default: break;
         }
     }
 }
 
-template <int CLASS, bool ALLCH>
+template <int CLASS>
 __global__ __launch_bounds__(256, CLASS == 0 ? 8 : 4) void k_idct_multi(const MultiArgs a) {
     extern __shared__ float lds[];
-    idct_multi_body<CLASS, ALLCH>(a, lds);
-}
-
-// The same launch for a BATCH of independent frames: blockIdx.y selects the frame's argument block in device memory
-// (read through the constant address space: uniform, invariant, scalar loads -- exactly what the kernel-argument
-// segment gives the single-frame form). One frame's share of a class is a few hundred to a few thousand waves; eight
-// frames' shares in one grid keep all 256 CUs busy through the whole launch instead of 4 queues' worth of small kernels.
-template <int CLASS>
-__global__ __launch_bounds__(256, CLASS == 0 ? 8 : 4) void k_idct_multi_batch(const MultiArgs* __restrict__ args) {
-    extern __shared__ float lds[];
-    typedef const __attribute__((address_space(4))) MultiArgs* cargs;
-    const MultiArgs& a = *(const MultiArgs*)((cargs)args + blockIdx.y);
-    idct_multi_body<CLASS, true>(a, lds);
+    idct_multi_body<CLASS>(a, lds);
 }
 
 size_t medium_lds_bytes(int type);
@@ -908,15 +783,15 @@ extern "C" int jxl_debug_set_stamps(void* dev_ptr) {
 
 int idct_class_of(int type) { return (type == 18 || type == 19 || type == 20 || type == 4 || type == 6) ? 1 : 0; }
 
-// segs: the class's types in launch order. Returns the grid size (0: nothing to do).
-int build_idct_multi_args(const DevFrame& f, const DevBlock* blocks, const IdctSegment* segs, int n_seg, int nch, int ch0,
-                          float* const out[3], MultiArgs& a, size_t* lds_bytes_out) {
+// segs: the class's types in launch order, channel ch. Returns the grid size (0: nothing to do).
+static int build_idct_multi_args(const DevFrame& f, const DevBlock* blocks, const IdctSegment* segs, int n_seg, int ch,
+                                 float* const out[3], MultiArgs& a, size_t* lds_bytes_out) {
     a.f = f;
     a.blocks = blocks;
     a.items = nullptr;
     a.o0 = out[0]; a.o1 = out[1]; a.o2 = out[2];
-    a.nch = nch;
-    a.ch0 = ch0;
+    a.nch = 1;
+    a.ch0 = ch;
     a.n_seg = 0;
     int b0 = 0;
     size_t lds_bytes = 0;
@@ -925,9 +800,7 @@ int build_idct_multi_args(const DevFrame& f, const DevBlock* blocks, const IdctS
         if (a.n_seg >= MultiArgs::kMaxSeg) return -1;  // never drop blocks silently (finalize_tables checks the lists it builds)
         const int k = a.n_seg++;
         const int nb = medium_blocks_per_wg(segs[i].type);
-        const int tt_h = JXL_TT[segs[i].type].ph, tt_w = JXL_TT[segs[i].type].pw;
-        const bool item3 = nch == 3 && !use_wg_path(tt_h, tt_w);  // one item = all three channels of a block group
-        const int n_items = ((segs[i].n_blocks + nb - 1) / nb) * (item3 ? 1 : nch);
+        const int n_items = (segs[i].n_blocks + nb - 1) / nb;
         a.seg_b0[k] = b0;
         a.seg_n[k] = n_items;
         a.seg_type[k] = segs[i].type;
@@ -941,29 +814,15 @@ int build_idct_multi_args(const DevFrame& f, const DevBlock* blocks, const IdctS
     return a.n_seg == 0 ? 0 : b0;
 }
 
-void launch_idct_multi(const DevFrame& f, const DevBlock* blocks, int cls, const IdctSegment* segs, int n_seg, int nch, int ch0,
+void launch_idct_multi(const DevFrame& f, const DevBlock* blocks, int cls, const IdctSegment* segs, int n_seg, int ch,
                        float* const out[3], hipStream_t s) {
     if (n_seg <= 0) return;
     MultiArgs a;
     size_t lds_bytes = 0;
-    const int b0 = build_idct_multi_args(f, blocks, segs, n_seg, nch, ch0, out, a, &lds_bytes);
+    const int b0 = build_idct_multi_args(f, blocks, segs, n_seg, ch, out, a, &lds_bytes);
     if (b0 <= 0) return;
-    const dim3 grid(b0), wg(256);
-    if (nch == 3) {
-        if (cls == 0) hipLaunchKernelGGL((k_idct_multi<0, true>), grid, wg, lds_bytes, s, a);
-        else hipLaunchKernelGGL((k_idct_multi<1, true>), grid, wg, lds_bytes, s, a);
-    } else {
-        if (cls == 0) hipLaunchKernelGGL((k_idct_multi<0, false>), grid, wg, lds_bytes, s, a);
-        else hipLaunchKernelGGL((k_idct_multi<1, false>), grid, wg, lds_bytes, s, a);
-    }
-}
-
-// n_frames argument blocks at dev_args (device memory), grid_x = the largest frame's grid
-void launch_idct_multi_batch(const MultiArgs* dev_args, int n_frames, int grid_x, size_t lds_bytes, int cls, hipStream_t s) {
-    if (n_frames <= 0 || grid_x <= 0) return;
-    const dim3 grid(grid_x, n_frames), wg(256);
-    if (cls == 0) hipLaunchKernelGGL((k_idct_multi_batch<0>), grid, wg, lds_bytes, s, dev_args);
-    else hipLaunchKernelGGL((k_idct_multi_batch<1>), grid, wg, lds_bytes, s, dev_args);
+    if (cls == 0) hipLaunchKernelGGL(k_idct_multi<0>, dim3(b0), dim3(256), lds_bytes, s, a);
+    else hipLaunchKernelGGL(k_idct_multi<1>, dim3(b0), dim3(256), lds_bytes, s, a);
 }
 
 // blocks of one channel that one workgroup (work item) handles
@@ -1006,181 +865,10 @@ __global__ __launch_bounds__(64) void k_idct_special(const DevFrame f, const Dev
     idct_special_body(f, blocks, items, o0, o1, o2);
 }
 
-// ---- the nine special 8x8 types, workgroup form (frames without chroma subsampling) -----------------------------------
-// The lane-per-block kernel above makes every lane fetch its own 8 (+ 8 luma) rows one dependent load after the other,
-// dequantises luma again for both chroma channels and divides once per sample: 20-27 us for a few hundred waves, the most
-// expensive kernel of a real 720p frame. Here a 256-thread workgroup takes 64 blocks of one type with all three channels:
-//   A. every lane fetches four 16-byte coefficient groups per channel -- all loads of the item are in flight at once --
-//      dequantises them through the 3 x 64 sign / bias / (a - qbn / a) table (HFCoefficients.java:309-315, as in
-//      k_idct_wg3), applies chroma-from-luma from the luma value it holds, and parks the block images in LDS;
-//   B. lane (channel, block) lifts its 64 samples out of LDS (row stride 65: bank = lane + i), runs the type's transform
-//      (invert_small: PassGroup.java:83-168, 234-325) in registers and puts the pixels back;
-//   C. the lanes of A write the pixels out, 16 bytes each.
-// Same operations per sample as the lane-per-block form, so the same bits.
-#define JXL_SPECIAL_WG_LDS ((192 * 65 + 192) * sizeof(float))
-__device__ __forceinline__ void special_wg_body(const DevFrame& f, const DevBlock* __restrict__ blocks, const WorkItem it, float* o0, float* o1,
-                                                float* o2) {
-    typedef int v4i_t __attribute__((ext_vector_type(4)));
-    typedef float v4f_t __attribute__((ext_vector_type(4)));
-    __shared__ float img[192 * 65];
-    __shared__ float qtab[192];
-    const int tid = threadIdx.x;
-    const int type = (int)(it.type & 0xffu), n = (int)it.count;
-    const float qbn = f.quant_bias_numerator;
-    if (tid < 192) {
-        const int c = tid >> 6, a = tid & 63;
-        qtab[tid] = a == 0 ? 0.0f : a == 1 ? f.quant_bias[c] : (float)a - qbn / (float)a;
-    }
-    const int PI = JXL_TT[type].param_index;
-    const float* wt[3] = {f.weights + f.woffs[PI * 3], f.weights + f.woffs[PI * 3 + 1], f.weights + f.woffs[PI * 3 + 2]};
-    const int W = f.width;
-    // ---- A: loads of the four groups of this lane
-    v4i_t q[4][3];
-    v4f_t wv[3];
-    int gx[4];
-    float hfm[4], kx[4], kb[4], lfv[4][3];
-    const int r = tid & 15, row = r >> 1, half = r & 1;  // the same (row, half) for all four groups: blocks tid/16 + 16 k
-#pragma unroll
-    for (int c = 0; c < 3; c++) wv[c] = *reinterpret_cast<const v4f_t*>(wt[c] + row * 8 + half * 4);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int blk = (tid >> 4) + 16 * k;
-        gx[k] = -1;
-        hfm[k] = 1.0f;
-        kx[k] = kb[k] = 0.0f;
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            q[k][c] = v4i_t{0, 0, 0, 0};
-            lfv[k][c] = 0.0f;
-        }
-        if (blk < n) {
-            const DevBlock b = load_block(blocks, (int)it.first + blk);
-            gx[k] = (int)b.cy | ((int)b.cx << 16);
-            hfm[k] = (float)b.hf_mul;
-            const int64_t off = coeff_off(W, b.cy * 8 + row, b.cx * 8 + half * 4);  // (the block's 16 lanes: 256 consecutive bytes)
-#pragma unroll
-            for (int c = 0; c < 3; c++) q[k][c] = *reinterpret_cast<const v4i_t*>(f.coeff[c] + off);
-            cfl_factors(f, (b.cy * 8) >> 6, (b.cx * 8) >> 6, b.cfl_zero & 1u, kx[k], kb[k]);
-            if (r == 0) {
-#pragma unroll
-                for (int c = 0; c < 3; c++) lfv[k][c] = f.lf[c][(int64_t)b.cy * f.bw + b.cx];
-            }
-        }
-    }
-    __syncthreads();  // qtab
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int blk = (tid >> 4) + 16 * k;
-        if (gx[k] < 0) continue;
-        const float sf[3] = {f.scale_factor[0] / hfm[k], f.scale_factor[1] / hfm[k], f.scale_factor[2] / hfm[k]};
-        float dq[3][4];
-        int big = 0;
-#pragma unroll
-        for (int c = 0; c < 3; c++)
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int qv = q[k][c][i];
-                const int aq = qv < 0 ? -qv : qv;
-                big |= aq;
-                const float m = qtab[c * 64 + (aq & 63)];
-                dq[c][i] = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, m) ^ ((uint32_t)qv & 0x80000000u));
-            }
-        if ((uint32_t)big >= 64u) {
-#pragma unroll
-            for (int c = 0; c < 3; c++)
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int qv = q[k][c][i];
-                    const int aq = qv < 0 ? -qv : qv;
-                    if (aq >= 64) dq[c][i] = (float)qv - qbn / (float)qv;
-                }
-        }
-        float* d0 = img + (0 * 64 + blk) * 65 + row * 8 + half * 4;
-        float* d1 = img + (1 * 64 + blk) * 65 + row * 8 + half * 4;
-        float* d2 = img + (2 * 64 + blk) * 65 + row * 8 + half * 4;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const float dy = dq[1][i] * sf[1] * wv[1][i];
-            float dx = dq[0][i] * sf[0] * wv[0][i] + kx[k] * dy;  // chromaFromLuma (HFCoefficients.java:186-188)
-            float db = dq[2][i] * sf[2] * wv[2][i] + kb[k] * dy;
-            float yy = dy;
-            if (r == 0 && i == 0) {  // finalizeLLF of a 1x1 dctSelect: the LF sample itself (see small_row)
-                dx = lfv[k][0];
-                yy = lfv[k][1];
-                db = lfv[k][2];
-            }
-            d0[i] = dx;
-            d1[i] = yy;
-            d2[i] = db;
-        }
-    }
-    __syncthreads();
-    // ---- B: one lane per (channel, block)
-    if (tid < 192 && (tid & 63) < n) {
-        float co[64], px[64];
-        float* im = img + tid * 65;
-#pragma unroll
-        for (int i = 0; i < 64; i++) co[i] = im[i];
-        switch (type) {
-        case 1: invert_small<1>(co, px); break;
-        case 2: invert_small<2>(co, px); break;
-        case 3: invert_small<3>(co, px); break;
-        case 12: invert_small<12>(co, px); break;
-        case 13: invert_small<13>(co, px); break;
-        case 14: invert_small<14>(co, px); break;
-        case 15: invert_small<15>(co, px); break;
-        case 16: invert_small<16>(co, px); break;
-        case 17: invert_small<17>(co, px); break;
-        default: break;
-        }
-#pragma unroll
-        for (int i = 0; i < 64; i++) im[i] = px[i];
-    }
-    __syncthreads();
-    // ---- C: pixels out
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        if (gx[k] < 0) continue;
-        const int blk = (tid >> 4) + 16 * k;
-        const int cy = gx[k] & 0xffff, cx = (int)((uint32_t)gx[k] >> 16);
-        const int64_t off = (int64_t)(cy * 8 + row) * W + cx * 8 + half * 4;
-        float* o3[3] = {o0, o1, o2};
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const float* sp = img + (c * 64 + blk) * 65 + row * 8 + half * 4;
-            *reinterpret_cast<v4f_t*>(o3[c] + off) = v4f_t{sp[0], sp[1], sp[2], sp[3]};
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_idct_special_wg(const DevFrame f, const DevBlock* __restrict__ blocks,
-                                                         const WorkItem* __restrict__ items, float* o0, float* o1, float* o2) {
-#ifdef JXL_IDCT_PRIO
-    __builtin_amdgcn_s_setprio(JXL_IDCT_PRIO);
-#endif
-    special_wg_body(f, blocks, items[blockIdx.x], o0, o1, o2);
-}
-
-// batch form: MultiArgs block per frame (f, blocks, items, o0..2; seg_n[0] = number of items); items in the workgroup form
-__global__ __launch_bounds__(256) void k_idct_special_batch(const MultiArgs* __restrict__ args) {
-    typedef const __attribute__((address_space(4))) MultiArgs* cargs;
-    const MultiArgs& a = *(const MultiArgs*)((cargs)args + blockIdx.y);
-    if ((int)blockIdx.x >= a.seg_n[0]) return;
-    special_wg_body(a.f, a.blocks, a.items[blockIdx.x], a.o0, a.o1, a.o2);
-}
-
-void launch_idct_special_batch(const MultiArgs* dev_args, int n_frames, int max_items, hipStream_t s) {
-    if (n_frames <= 0 || max_items <= 0) return;
-    hipLaunchKernelGGL(k_idct_special_batch, dim3(max_items, n_frames), dim3(256), 0, s, dev_args);
-}
-
-// wg_items: items name 64 blocks of all three channels (k_idct_special_wg); else one channel each (the lane-per-block kernel:
-// chroma-subsampled frames, whose channels have their own geometry and no chroma-from-luma)
-void launch_idct_special(const DevFrame& f, const DevBlock* blocks, const WorkItem* items, int n_items, float* const out[3],
-                         hipStream_t s, bool wg_items) {
+// one channel per item (chroma-subsampled frames, whose channels have their own geometry and no chroma-from-luma)
+void launch_idct_special(const DevFrame& f, const DevBlock* blocks, const WorkItem* items, int n_items, float* const out[3], hipStream_t s) {
     if (n_items <= 0) return;
-    if (wg_items) hipLaunchKernelGGL(k_idct_special_wg, dim3(n_items), dim3(256), 0, s, f, blocks, items, out[0], out[1], out[2]);
-    else hipLaunchKernelGGL(k_idct_special, dim3(n_items), dim3(64), 0, s, f, blocks, items, out[0], out[1], out[2]);
+    hipLaunchKernelGGL(k_idct_special, dim3(n_items), dim3(64), 0, s, f, blocks, items, out[0], out[1], out[2]);
 }
 
 

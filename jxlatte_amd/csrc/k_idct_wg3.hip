@@ -27,8 +27,8 @@
 //     LDS samples requested ahead;
 //   * finalizeLLF runs inside the item (r3): the lane that holds LLF coefficient (c, ky, kx) of a block prefetches LF sample
 //     (c, y, x) of its dctSelect-sized patch, the lanes exchange the patches through a small LDS table and dequant() forms
-//     forwardDCT2D x llfScale there (llf_coeff3). Until r3 a kernel of its own in front of the launch (k_llf_wg3, still
-//     selectable with JXL_WG3_LLF_IN_ITEM=0): 9-13 us and a dependent launch on every frame's critical path.
+//     forwardDCT2D x llfScale there (llf_coeff3). Until r3 a kernel of its own in front of the launch: 9-13 us and a
+//     dependent launch on every frame's critical path.
 // Bit-exactness: every sum keeps the reference's order, multiplies and adds are separate IEEE f32 operations.
 #include "jxl_internal.h"
 #include <cstdio>
@@ -554,7 +554,7 @@ __device__ __forceinline__ void prefetch(const Wg3Args& a, const Item& it, int t
     }
     // finalizeLLF input: lane t < nb * PER_B holds LF sample (c, y, x) = t % PER_B of block t / PER_B (for an 8x8 block that IS
     // its LLF coefficient); the lanes exchange them through the LDS patch table and dequant() transforms them (r3: this was a
-    // kernel of its own in front of the launch, k_llf_wg3 -- 9 us + a dependent launch on every frame's critical path)
+    // kernel of its own in front of the launch -- 9 us + a dependent launch on every frame's critical path)
     const int lgA = (int)((it.geo >> 8) & 7u), lgDSW = (int)((it.geo >> 12) & 3u);
     const int bl = llf_lane_block(tid, lgA);
     if (it.type >= 0 && bl < it.nb) {
@@ -740,7 +740,7 @@ struct Body {
 // ---- r6: the 8x8-footprint types that are not METHOD_DCT -- Hornuss, DCT2, DCT4, DCT4x8, DCT8x4, AFV0-3 (PassGroup.java:88-168, 234-325)
 // -- as items of this launch (32 blocks x 3 channels, the geometry of an 8x8 DCT item: same requests, same dequantisation, same store
 // mapping; only the weights are the untransposed ones, TransformType.flip() being false for them). Until r6 a launch of their own on a
-// side stream (k_idct_special_wg): 17 us alone for 12 % of the pixels of the default mix, and in the saturated regime -- eight frames in
+// side stream: 17 us alone for 12 % of the pixels of the default mix, and in the saturated regime -- eight frames in
 // flight, where `value` is measured -- a second launch per frame costs the stage 11-19 us per frame however the streams are mapped
 // (profiles/experiments/r6_idct_saturated_mixes_r5kernels.txt: 88 % DCT8 + 12 % AFV0 61 us per frame, either type alone 40-42).
 // Transform: lane (channel, block) holds the block's 64 pixels in registers and reads its coefficients from the image as it goes
@@ -956,6 +956,8 @@ __device__ __forceinline__ void do_dequant(const Wg3Args& a, const Item& it, int
                                            const float* qtab) {
     if constexpr (BIG) {
         switch (it.type) {
+        // (64x64 blocks are Item64 items of the 256-thread class: never handed out here. Kept: without this case and its twin in
+        // do_passes the batch form spills 7 VGPRs instead of 3)
         case 18: Body<64, 64, 18>::dequant(a, it, tid, raw, img, qtab); break;
         case 19: Body<64, 32, 19>::dequant(a, it, tid, raw, img, qtab); break;
         case 20: Body<32, 64, 20>::dequant(a, it, tid, raw, img, qtab); break;
@@ -1138,58 +1140,6 @@ __global__ __launch_bounds__(Cls<BIG>::T, BIG ? WG3_BIG_OCC : WG3_SMALL_OCC) voi
     wg3_body<BIG>(*(const Wg3Args*)((cargs)args + blockIdx.y));
 }
 
-// finalizeLLF (HFCoefficients.java:194-229) of every block of the launch's segments, one lane per coefficient, written over
-// the block's own cells of the llf planes (a block covers exactly dctSelectHeight x dctSelectWidth cells)
-template <int H, int W>
-__device__ __forceinline__ void llf_one(const Wg3Args& a, const Wg3Seg& sg, int t, float* l0, float* l1, float* l2) {
-    constexpr int DSH = H / 8, DSW = W / 8, PER_B = 3 * DSH * DSW;
-    const int b = t / PER_B, rr = t % PER_B;
-    if (b >= sg.n_blocks) return;
-    const int c = rr / (DSH * DSW), k = rr % (DSH * DSW);
-    const v4i rec = ((cv4ip)a.blocks)[sg.first_block + b];
-    const int cy = (int)((uint32_t)rec.x & 0xffffu), cx = (int)((uint32_t)rec.x >> 16);
-    const float v = llf_coeff3<DSH, DSW>(a.f.lut, a.f.lf[c] + (int64_t)cy * a.f.bw + cx, a.f.bw, k / DSW, k % DSW, kLlfScale3);
-    (c == 0 ? l0 : c == 1 ? l1 : l2)[(int64_t)(cy + k / DSW) * a.f.bw + cx + k % DSW] = v;
-}
-
-__device__ __forceinline__ void llf_wg3_body(const Wg3Args& a, float* l0, float* l1, float* l2) {
-    int t = (int)(blockIdx.x * 256 + threadIdx.x);
-    for (int k = 0; k < a.n_seg; k++) {
-        const Wg3Seg sg = a.seg[k];
-        // (the LLF of an 8x8 block is its LF sample: the llf planes start as a copy of the lf planes)
-        const int n = sg.type == 0 ? 0 : sg.n_blocks * 3 * (JXL_TT[sg.type].ph / 8) * (JXL_TT[sg.type].pw / 8);
-        if (t < n) {
-            switch (sg.type) {
-            case 4: llf_one<16, 16>(a, sg, t, l0, l1, l2); break;
-            case 5: llf_one<32, 32>(a, sg, t, l0, l1, l2); break;
-            case 6: llf_one<16, 8>(a, sg, t, l0, l1, l2); break;
-            case 7: llf_one<8, 16>(a, sg, t, l0, l1, l2); break;
-            case 8: llf_one<32, 8>(a, sg, t, l0, l1, l2); break;
-            case 9: llf_one<8, 32>(a, sg, t, l0, l1, l2); break;
-            case 10: llf_one<32, 16>(a, sg, t, l0, l1, l2); break;
-            case 11: llf_one<16, 32>(a, sg, t, l0, l1, l2); break;
-            case 18: llf_one<64, 64>(a, sg, t, l0, l1, l2); break;
-            case 19: llf_one<64, 32>(a, sg, t, l0, l1, l2); break;
-            case 20: llf_one<32, 64>(a, sg, t, l0, l1, l2); break;
-            default: break;
-            }
-            return;
-        }
-        t -= n;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_llf_wg3(const Wg3Args a, float* l0, float* l1, float* l2) {
-    llf_wg3_body(a, l0, l1, l2);
-}
-
-// batch form: the llf planes are the ones the frame's own argument block names (DevFrame::llf)
-__global__ __launch_bounds__(256) void k_llf_wg3_batch(const Wg3Args* __restrict__ args) {
-    typedef const __attribute__((address_space(4))) Wg3Args* cargs;
-    const Wg3Args& a = *(const Wg3Args*)((cargs)args + blockIdx.y);
-    llf_wg3_body(a, const_cast<float*>(a.f.llf[0]), const_cast<float*>(a.f.llf[1]), const_cast<float*>(a.f.llf[2]));
-}
-
 #ifdef JXL_STAMPS
 extern "C" int jxl_debug_set_stamps3(void* dev_ptr) {
     unsigned long long* p = (unsigned long long*)dev_ptr;
@@ -1197,32 +1147,11 @@ extern "C" int jxl_debug_set_stamps3(void* dev_ptr) {
 }
 #endif
 
-bool wg3_llf_in_item() {
-    static const bool v = !(getenv("JXL_WG3_LLF_IN_ITEM") && atoi(getenv("JXL_WG3_LLF_IN_ITEM")) == 0);
-    return v;
-}
-
-bool wg3_handles(int type) {
-    // experiment knob: JXL_WG3_SKIP=<bit mask of types> leaves those types to the per-channel kernels of k_idct.hip
-    static const unsigned skip = getenv("JXL_WG3_SKIP") ? (unsigned)strtoul(getenv("JXL_WG3_SKIP"), nullptr, 0) : 0u;
-    if (type < 32 && ((skip >> type) & 1u)) return false;
-    switch (type) {
-    case 0: case 4: case 5: case 6: case 7: case 8: case 9: case 10: case 11: case 18: case 19: case 20: return true;
-    default: return wg3_special_items() && wg3_is_special(type);
-    }
-}
-// r6: the special 8x8 types as items of the persistent launch (JXL_WG3_SPECIAL=0: their own launch on the side stream, as until r5)
-bool wg3_special_items() {
-    static const bool v = !(getenv("JXL_WG3_SPECIAL") && atoi(getenv("JXL_WG3_SPECIAL")) == 0);
-    return v;
-}
-// r6: 64x64 blocks as items of the 256-thread launch (Item64; JXL_WG3_FOLD64=0: in the 512-thread class's own launch, as until r5).
-// The 64x32 / 32x64 types stay in the 512-thread class (a single block of them has fewer columns / rows than a wave has lanes).
-bool wg3_fold64() {
-    static const bool v = !(getenv("JXL_WG3_FOLD64") && atoi(getenv("JXL_WG3_FOLD64")) == 0);
-    return v;
-}
-bool wg3_big(int type) { return (type == 18 && !wg3_fold64()) || type == 19 || type == 20; }
+// every type but the 128/256-edge ones (r6: the special 8x8 types too)
+bool wg3_handles(int type) { return JXL_TT[type].ph < 128 && JXL_TT[type].pw < 128; }
+// the 512-thread class: 64x32 / 32x64 (a single block of them has fewer columns / rows than a wave has lanes). r6: 64x64 blocks are
+// items of the 256-thread launch (Item64).
+bool wg3_big(int type) { return type == 19 || type == 20; }
 
 int wg3_grid_cap(bool big) {
     // r6: 768 = three 256-thread workgroups per CU. Until r5 512, so that the 64-point and the special launches fitted beside this one;
@@ -1235,7 +1164,7 @@ int wg3_grid_cap(bool big) {
 
 int wg3_blocks_per_item(int type) {
     const int h = JXL_TT[type].ph, w = JXL_TT[type].pw;
-    if (type == 18 && !wg3_big(type)) return 1;  // Item64: one block, channel by channel
+    if (type == 18) return 1;  // Item64: one block, channel by channel
     return ((h > w ? h : w) <= 32 ? 2048 : 4096) / (h * w);
 }
 
@@ -1244,15 +1173,14 @@ static int wg3_img_floats(int type) {
     const int h = JXL_TT[type].ph, w = JXL_TT[type].pw;
     const int nb = wg3_blocks_per_item(type);
     if (wg3_is_special(type)) return 3 * nb * 65;  // SpecialBody
-    if (type == 18 && !wg3_big(type)) return 64 * 65;  // Item64: one channel at a time
+    if (type == 18) return 64 * 65;  // Item64: one channel at a time
     const int img0 = h * (w + 1);
     const int img = w >= 32 ? img0 : img0 + ((w - img0 % 32) + 32) % 32;
     return 3 * nb * img;
 }
 
-// Fills the argument block for the frame's types of one register class (which = 0: up to 32 points, 1: the 64-point family;
-// 2: both, for the LLF launch), in the given launch order. Returns the number of items (0: nothing to launch; -1: more
-// segments than the argument block holds).
+// Fills the argument block for the frame's types of one register class (which = 0: up to 32 points, 1: 64x32 / 32x64), in the
+// given launch order. Returns the number of items (0: nothing to launch; -1: more segments than the argument block holds).
 int build_wg3_args(const DevFrame& f, const DevBlock* blocks, const IdctSegment* segs, int n_seg, int which, float* const out[3],
                    Wg3Args& a) {
     a.f = f;
@@ -1262,10 +1190,10 @@ int build_wg3_args(const DevFrame& f, const DevBlock* blocks, const IdctSegment*
     a.total_items = 0;
     a.img_floats = 0;
     a.items = nullptr;
-    a.llf_in_item = wg3_llf_in_item() ? 1 : 0;
-    static_assert(Wg3Args::kMaxSeg >= 21, "one segment per type wg3_handles() accepts (21 types: the LLF launch passes both classes)");
+    a.llf_in_item = 1;  // (always: the items do finalizeLLF themselves)
+    static_assert(Wg3Args::kMaxSeg >= 21, "one segment per type wg3_handles() accepts");
     for (int i = 0; i < n_seg; i++) {
-        if (segs[i].n_blocks <= 0 || !wg3_handles(segs[i].type) || (which != 2 && wg3_big(segs[i].type) != (which == 1))) continue;
+        if (segs[i].n_blocks <= 0 || !wg3_handles(segs[i].type) || wg3_big(segs[i].type) != (which == 1)) continue;
         // a type twice in the list, or a new type without a larger kMaxSeg: never drop blocks silently, never kill the host
         // process (finalize_tables checks the lists it builds and reports JXL_ERR_STATE)
         if (a.n_seg >= Wg3Args::kMaxSeg) return -1;
@@ -1310,40 +1238,35 @@ static float wg3_item_cost(int type) {  // us per 4K frame tiled with the type (
     }
 }
 
-void wg3_item_table(const DevBlock* hb, int frame_bw, const IdctSegment* segs, int n_seg, int which, const int32_t* woffs, bool spatial,
+void wg3_item_table(const DevBlock* hb, int frame_bw, const IdctSegment* segs, int n_seg, int which, const int32_t* woffs,
                     std::vector<int>& out, int grid) {
     struct Rec { uint32_t key; int type, first, nb; };
     std::vector<Rec> recs;
-    static const int rsh = getenv("JXL_WG3_REGION_SHIFT") ? std::min(12, std::max(0, atoi(getenv("JXL_WG3_REGION_SHIFT")))) : 5;
+    constexpr int rsh = 5;  // spatial regions of 32 x 32 cells
     const int grs = std::max(1, (frame_bw + (1 << rsh) - 1) >> rsh);
     for (int i = 0; i < n_seg; i++) {
-        if (segs[i].n_blocks <= 0 || !wg3_handles(segs[i].type) || (which != 2 && wg3_big(segs[i].type) != (which == 1))) continue;
+        if (segs[i].n_blocks <= 0 || !wg3_handles(segs[i].type) || wg3_big(segs[i].type) != (which == 1)) continue;
         const int nb = wg3_blocks_per_item(segs[i].type);
         for (int o = 0; o < segs[i].n_blocks; o += nb) {
             const DevBlock& b0 = hb[segs[i].first_block + o];
             recs.push_back(Rec{(uint32_t)((b0.cy >> rsh) * grs + (b0.cx >> rsh)), segs[i].type, segs[i].first_block + o, std::min(nb, segs[i].n_blocks - o)});
         }
     }
-    auto emit = [&](const Rec& r) {
+    // (geometry bit 14: the item fetches its coefficients itself -- a 64x64 block in the 256-thread class, Item64)
+    auto record = [&](const Rec& r, int* rec) {
         const int pi3 = (int)JXL_TT[r.type].param_index * 3;
-        // (geometry bit 14: the item fetches its coefficients itself -- a 64x64 block in the 256-thread class, Item64)
-        const int rec[8] = {r.type, r.first, r.nb, (int)(wg3_geo(r.type) | (r.type == 18 && !wg3_big(18) ? 1u << 14 : 0u)), woffs[pi3], woffs[pi3 + 1], woffs[pi3 + 2], 0};
-        out.insert(out.end(), rec, rec + 8);
+        const int v[8] = {r.type, r.first, r.nb, (int)(wg3_geo(r.type) | (r.type == 18 ? 1u << 14 : 0u)), woffs[pi3], woffs[pi3 + 1], woffs[pi3 + 2], 0};
+        std::copy(v, v + 8, rec);
     };
-    if (!spatial) {  // JXL_WG3_SPATIAL=0: the segments' own order, type after type
-        out.clear();
-        for (const Rec& r : recs) emit(r);
-        return;
-    }
     // r6: the special 8x8 items go BEHIND the others (each part in its own spatial order): such an item issues the next item's requests
     // only after its transform (wg3_body), i.e. the item behind it waits for memory -- at the end of a workgroup's list that item is
     // another special one or none (a 4K frame of the default mix has about one special item per workgroup) --, and the 64x64 blocks of
     // the 256-thread class (Item64: nothing of them is prefetched either) behind those.
-    auto tail_rank = [](const Rec& r) { return wg3_is_special(r.type) ? 1 : (r.type == 18 && !wg3_big(18)) ? 2 : 0; };
+    auto tail_rank = [](const Rec& r) { return wg3_is_special(r.type) ? 1 : r.type == 18 ? 2 : 0; };
     std::stable_sort(recs.begin(), recs.end(), [&](const Rec& x, const Rec& y) { return tail_rank(x) < tail_rank(y); });
     const size_t n_normal = (size_t)(std::find_if(recs.begin(), recs.end(), [&](const Rec& r) { return tail_rank(r) > 0; }) - recs.begin());
     const size_t n_special_end = (size_t)(std::find_if(recs.begin(), recs.end(), [&](const Rec& r) { return tail_rank(r) > 1; }) - recs.begin());
-    static const int run = getenv("JXL_WG3_RUN") ? std::max(1, atoi(getenv("JXL_WG3_RUN"))) : 24;
+    constexpr int run = 24;
     out.clear();
     // per part: the eight queues (one per XCD: workgroup w runs on XCD w % 8) in spatial order, dealt in runs of about one group's items
     std::vector<const Rec*> q[3][8];
@@ -1352,16 +1275,18 @@ void wg3_item_table(const DevBlock* hb, int frame_bw, const IdctSegment* segs, i
         std::stable_sort(recs.begin() + (ptrdiff_t)r0, recs.begin() + (ptrdiff_t)r1, [](const Rec& x, const Rec& y) { return x.key < y.key; });
         for (size_t i = r0; i < r1; i++) q[part][((i - r0) / (size_t)(part == 2 ? 1 : run)) % 8].push_back(&recs[i]);
     }
-    static const bool balance = !(getenv("JXL_WG3_BALANCE") && atoi(getenv("JXL_WG3_BALANCE")) == 0);
     const size_t G = (size_t)std::max(0, grid);
-    if (!(balance && G >= 8 && G % 8 == 0 && recs.size() > G)) {
+    if (!(G >= 8 && G % 8 == 0 && recs.size() > G)) {
         // no grid to balance for: the queues interleaved (position p belongs to queue p % 8 while all eight last), part after part
         for (int part = 0; part < 3; part++) {
             size_t longest = 0;
             for (auto& v : q[part]) longest = std::max(longest, v.size());
             for (size_t i = 0; i < longest; i++)
                 for (int x = 0; x < 8; x++)
-                    if (i < q[part][x].size()) emit(*q[part][x][i]);
+                    if (i < q[part][x].size()) {
+                        out.resize(out.size() + 8);
+                        record(*q[part][x][i], out.data() + out.size() - 8);
+                    }
         }
         return;
     }
@@ -1412,41 +1337,15 @@ void wg3_item_table(const DevBlock* hb, int frame_bw, const IdctSegment* segs, i
     for (size_t w = 0; w < G; w++) {
         size_t k = 0;
         for (int part = 0; part < 3; part++)
-            for (const Rec* r : lists[part][w]) {
-                const int pi3 = (int)JXL_TT[r->type].param_index * 3;
-                const int rec[8] = {r->type, r->first, r->nb, (int)(wg3_geo(r->type) | (r->type == 18 && !wg3_big(18) ? 1u << 14 : 0u)), woffs[pi3], woffs[pi3 + 1], woffs[pi3 + 2], 0};
-                std::copy(rec, rec + 8, out.begin() + (ptrdiff_t)((k * G + w) * 8));
-                k++;
-            }
+            for (const Rec* r : lists[part][w]) record(*r, out.data() + (k++ * G + w) * 8);
     }
 }
 
 
-// LLF coefficients of the class's blocks into the llf planes (must precede launch_idct_wg3 on the same stream)
-void launch_llf_wg3(const Wg3Args& a, float* const llf[3], hipStream_t s) {
-    int64_t n = 0;
-    for (int k = 0; k < a.n_seg; k++)
-        if (a.seg[k].type != 0) n += (int64_t)a.seg[k].n_blocks * 3 * (JXL_TT[a.seg[k].type].ph / 8) * (JXL_TT[a.seg[k].type].pw / 8);
-    if (n <= 0) return;
-    hipLaunchKernelGGL(k_llf_wg3, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, llf[0], llf[1], llf[2]);
-}
-
-int64_t wg3_llf_count(const Wg3Args& a) {
-    int64_t n = 0;
-    for (int k = 0; k < a.n_seg; k++)
-        if (a.seg[k].type != 0) n += (int64_t)a.seg[k].n_blocks * 3 * (JXL_TT[a.seg[k].type].ph / 8) * (JXL_TT[a.seg[k].type].pw / 8);
-    return n;
-}
-
 // block images + dequantisation table [3][64] + finalizeLLF tables (cosine LUT 70 + 2, LLF scale 32, LF patches 192) + scale table [3][256]
 size_t wg3_lds_bytes(const Wg3Args& a) { return sizeof(float) * ((size_t)a.img_floats + kWg3AuxFloats + 3 * kWg3SfEntries); }
 
-// batch forms: dev_args[0..n_frames) in device memory; max_llf = the largest wg3_llf_count, grid_x workgroups per frame,
-// lds = the largest wg3_lds_bytes among the frames
-void launch_llf_wg3_batch(const Wg3Args* dev_args, int n_frames, int64_t max_llf, hipStream_t s) {
-    if (n_frames <= 0 || max_llf <= 0) return;
-    hipLaunchKernelGGL(k_llf_wg3_batch, dim3((unsigned)((max_llf + 255) / 256), n_frames), dim3(256), 0, s, dev_args);
-}
+// batch form: dev_args[0..n_frames) in device memory, grid_x workgroups per frame, lds = the largest wg3_lds_bytes among the frames
 
 void launch_idct_wg3_batch(const Wg3Args* dev_args, int n_frames, bool big, int grid_x, size_t lds, hipStream_t s) {
     if (n_frames <= 0 || grid_x <= 0) return;

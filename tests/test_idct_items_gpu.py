@@ -1,6 +1,6 @@
 """r6: the item kinds of the persistent inverse-transform launch (k_idct_wg3.hip) against the oracle, case by case -- the special 8x8
 types (Hornuss, DCT2, DCT4, DCT4x8, DCT8x4, AFV0-3: PassGroup.java:88-168, 234-325) and the 64x64 blocks (Item64) as items, the explicit
-per-workgroup item lists with holes (wg3_item_table), and the switches that put them back into launches of their own. Bit compare through
+per-workgroup item lists with holes (wg3_item_table) walked on other grids, and the launch count of each frame kind. Bit compare through
 the C-ABI, as everywhere (tests/conftest.py)."""
 import numpy as np
 import pytest
@@ -72,13 +72,11 @@ def _types_of(g):
     return [sel[by, bx] for by, bx in np.asarray(g["block_yx"]).reshape(-1, 2)]
 
 
-@pytest.mark.parametrize("env", [{"JXL_WG3_SPECIAL": "0"}, {"JXL_WG3_FOLD64": "0"}, {"JXL_WG3_SPECIAL": "0", "JXL_WG3_FOLD64": "0"},
-                                 {"JXL_WG3_GRID": "8"}, {"JXL_WG3_GRID": "40"}, {"JXL_WG3_GRID": "2048"}, {"JXL_WG3_BALANCE": "0"},
-                                 {"JXL_WG3_SPATIAL": "0"}, {"JXL_WG3_LLF_IN_ITEM": "0"}, {"JXL_WG3_LLF_IN_ITEM": "0", "JXL_WG3_FOLD64": "0"}])
+@pytest.mark.parametrize("env", [{}, {"JXL_WG3_GRID": "8"}, {"JXL_WG3_GRID": "40"}, {"JXL_WG3_GRID": "2048"}, {"JXL_WG3_GRID_BIG": "8"}])
 def test_switches_give_identical_planes(env, orc):
-    """the r5 launch plan (special kernel, 64-point class's own launch), other persistent grids (8: a workgroup walks 1/8 of the frame;
-    40: five workgroups per queue; 2048: more workgroups than can be resident), no balancing, no spatial order, finalizeLLF as a launch of
-    its own in front (the items then take their LLF corner from the llf planes): the same bits. The switches are read once per process, hence a process per case."""
+    """the default grids and other persistent grids (8: a workgroup walks 1/8 of the frame; 40: five workgroups per queue; 2048: more
+    workgroups than can be resident; the 512-thread launch of the 64x32 blocks of the "all" mix on 8): the same bits. The grid caps are
+    read once per process, hence a process per case."""
     import os
     import subprocess
     import sys
@@ -133,3 +131,40 @@ def test_run_batch_walks_the_lists_on_another_grid(orc):
     finally:
         for c in ctxs:
             c.close()
+
+
+# launches of the inverse-transform stage per frame kind (recorded before the launch-plan switches were retired): 4:4:4 frames take the
+# persistent launches (k_idct_wg3.hip), chroma-subsampled ones the per-channel kernels plus one upsampling launch per doubling, frames with
+# 128/256-edge blocks the LLF and large-block launches in addition
+SUBSAMPLED_LAUNCHES = {"420": ((1, 0, 1), (1, 0, 1), 7), "422": ((0, 0, 0), (1, 0, 1), 5), "440": ((1, 0, 1), (0, 0, 0), 5)}
+
+
+def _launches(ctx, frame):
+    fr = host.Frame.from_synth(ctx, frame, stages=abi.STAGE_IDCT)
+    fr.run()
+    return fr.lastLaunchCount()
+
+
+def test_launch_count_of_each_frame_kind(ctx):
+    """pins the launch plan of the IDCT stage: the default mix is ONE launch, 64x32 blocks add the 512-thread class's launch, subsampled
+    frames, frames with large blocks and a batch of three keep the counts they had (measured before the launch-plan switches went)"""
+    got, want = {}, {}
+    got["default"], want["default"] = _launches(ctx, synth.make_vardct_frame(1024, 512, seed=1, mix="default")), 1
+    got["64x32"], want["64x32"] = _launches(ctx, synth.make_vardct_frame(1024, 512, seed=1, mix="DCT8=0.5+DCT64_32=0.5")), 2
+    for mode, (sy, sx, n) in SUBSAMPLED_LAUNCHES.items():
+        base = synth.make_vardct_frame(528, 272, seed=11, mix="dct8", xyb=0)
+        got[mode], want[mode] = _launches(ctx, synth.make_subsampled(base, sy, sx)), n
+    got["large"], want["large"] = _launches(ctx, synth.make_vardct_frame(1024, 512, seed=5, mix="large")), 6
+    ctxs = [_lib.Context(0) for _ in range(3)]
+    try:
+        frames = [host.Frame.from_synth(c, synth.make_vardct_frame(768, 512, seed=30 + i, mix="DCT64=0.3+AFV0=0.2+DCT64_32=0.2+DCT8=0.3"),
+                                        stages=abi.STAGE_IDCT) for i, c in enumerate(ctxs)]
+        host.Frame.runBatch(frames)
+        for fr in frames:
+            fr.readOutput()
+        # (the shared launches count on the first frame: both persistent classes)
+        got["batch"], want["batch"] = [fr.lastLaunchCount() for fr in frames], [2, 0, 0]
+    finally:
+        for c in ctxs:
+            c.close()
+    assert got == want, got

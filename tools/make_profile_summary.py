@@ -78,9 +78,11 @@ share_path = os.path.join(out_dir, "%s_bench_vardct4k.json" % tag)
 if os.path.exists(share_path):
     try:
         cfg = json.loads(open(share_path).read().strip().splitlines()[-1])["config"]["varblock_area_share"]
-        cls = {"k_idct_wg3<false>": ("DCT8", "DCT16", "DCT32", "DCT16_8", "DCT8_16", "DCT32_8", "DCT8_32", "DCT32_16", "DCT16_32"),
-               "k_idct_wg3<true>": ("DCT64", "DCT64_32", "DCT32_64"),
-               "k_idct_special_wg": ("HORNUSS", "DCT2", "DCT4", "DCT4_8", "DCT8_4", "AFV0", "AFV1", "AFV2", "AFV3")}
+        # the 256-thread launch takes every type up to 64x64 and the special 8x8 ones, the 512-thread launch 64x32 / 32x64; the
+        # 128/256-edge types have kernels of their own
+        cls = {"k_idct_wg3<false>": ("DCT8", "DCT16", "DCT32", "DCT16_8", "DCT8_16", "DCT32_8", "DCT8_32", "DCT32_16", "DCT16_32", "DCT64",
+                                     "HORNUSS", "DCT2", "DCT4", "DCT4_8", "DCT8_4", "AFV0", "AFV1", "AFV2", "AFV3"),
+               "k_idct_wg3<true>": ("DCT64_32", "DCT32_64")}
         L += ["", "Coefficient reads of the IDCT launches (4K frame = 99.5 MB of int32 coefficients; FETCH_SIZE doubled as the guide prescribes):", "",
               "| launch | area share | coefficient bytes used (MB) | fetched (MB) | ratio |", "|---|---|---|---|---|"]
         for k, types in cls.items():
