@@ -252,6 +252,46 @@ jxl_status jxl_vardct_commit_coeffs_i16(jxl_ctx* ctx);
 #define JXL_MAP_NO_FILL 1
 jxl_status jxl_vardct_map_coeffs_i16_ex(jxl_ctx* ctx, int16_t* planes[3], int32_t strides[3], int32_t flags);
 jxl_status jxl_vardct_commit_coeffs_i16_groups(jxl_ctx* ctx, const uint8_t* group_written, int32_t n_groups);
+/* ---- sparse coefficient feed: only the non-zero coefficients cross the bus -------------------------------------------------
+ * HFCoefficients' decode loop makes one store per decoded symbol and stops at a block's last non-zero
+ * (HFCoefficients.java:112-127): a list of (position, value) pairs is what the host has in hand before it scatters them into
+ * a cleared int[][] (:68). These entries take that list as it is. An ENTRY names one sample of one (group, channel) in that
+ * channel's own geometry (jxl_vardct_group_size; shifted for chroma-subsampled frames, PassGroup.java:213-226):
+ *     pos = (y << 8) | x,   y < gh[c], x < gw[c]
+ * narrow entry: one uint32_t, pos in the low 16 bits, the value as int16 in the high 16 bits;
+ * wide entry (JXL_SPARSE_WIDE, per call or per run): two uint32_t, pos (its high 16 bits zero), then the value as int32 --
+ * the part jxl_vardct_put_group plays for the int16 entries.
+ * An entry whose value is 0 changes nothing. The device takes the first `count` entries of a list and reads nothing behind
+ * them: what pads a list to the next 16-byte boundary is never interpreted (zero entries, as callers usually write, are
+ * fine). Positions inside one call or one run are distinct (the reference's coefficient order is a permutation,
+ * HFCoefficients.java:112-127); with duplicates the sample receives the SUM of their values (Java int wrap), the same on every
+ * run. An entry whose position lies outside the group's rectangle is never stored anywhere. */
+#define JXL_SPARSE_WIDE 1
+/* One group, like jxl_vardct_put_group_i16 (quantizedCoeffs of one (pass, group), HFCoefficients.java:43,68): pass 0 REPLACES the
+ * group's rectangle (a fresh zeroed int[][] plus the entries), pass > 0 adds (PassGroup.java:174-200, Java int wrap).
+ * entries[c]: n_entries[c] entries of channel c (n_entries[c] == 0 is legal, entries[c] may then be NULL). Buffer rules as for
+ * jxl_vardct_put_group: page-locked, 16-byte aligned lists are read by the device in place, asynchronously (keep them until a
+ * call that waits for the stream has returned); anything else is copied through the staging ring before the call returns. On
+ * the copying path an entry outside the rectangle is JXL_ERR_INVALID_ARGUMENT and nothing is queued; on the in-place path the
+ * device refuses such entries and counts them (jxl_vardct_sparse_rejected). */
+jxl_status jxl_vardct_put_group_sparse(jxl_ctx* ctx, int32_t pass, int32_t group,
+                                       const uint32_t* const entries[3], const int32_t n_entries[3], int32_t flags);
+/* The whole frame from ONE page-locked buffer the library owns: the sparse sibling of jxl_vardct_map_coeffs_i16 / commit. The
+ * entropy decoder appends the entries of each (group, channel) as a RUN: `count` entries starting `offset_words` words into the
+ * buffer (a multiple of 4: runs start on 16-byte boundaries), all of one form (flags: 0 or JXL_SPARSE_WIDE).
+ * map: `words` has room for capacity_words uint32_t and is valid until the next begin_frame; a larger capacity than any
+ * before reallocates (the earlier contents are not kept). It waits only for the previous commits' reads of the buffer.
+ * commit ADDS the runs' entries into the planes as they stand: on a fresh frame they are zero (HFCoefficients.java:68), so
+ * groups no run names read as zero; a second commit is a later pass (PassGroup.java:174-200). Asynchronous (jxl_vardct_run is
+ * ordered behind it); may be mixed with jxl_vardct_put_group* afterwards. One scatter launch per 2048 non-empty runs, however
+ * many groups they name. Every run is checked before anything is queued (group, channel, flags, alignment, extent within
+ * capacity_words): JXL_ERR_INVALID_ARGUMENT leaves no work in flight. JXL_ERR_STATE before map_sparse in this frame. */
+typedef struct jxl_sparse_run { int32_t group, channel, flags, count; int64_t offset_words; } jxl_sparse_run;
+jxl_status jxl_vardct_map_sparse(jxl_ctx* ctx, size_t capacity_words, uint32_t** words);
+jxl_status jxl_vardct_commit_sparse(jxl_ctx* ctx, const jxl_sparse_run* runs, int32_t n_runs);
+/* Entries the device refused (position outside the group's rectangle) since begin_frame -- the guard the reference gets from
+ * Java's array bounds check (HFCoefficients.java:125 would throw ArrayIndexOutOfBoundsException). Waits for the context's stream. */
+jxl_status jxl_vardct_sparse_rejected(jxl_ctx* ctx, int64_t* n);
 /* Page-locked host memory for the buffers that cross the bus (coefficient planes in, pixel planes out; a JNI caller wraps it
  * with NewDirectByteBuffer). put_group / put_group_i16 / read_output recognise such pointers: the device reads / writes them
  * in place at bus speed instead of through a staged copy out of pageable memory, and put_group returns without waiting

@@ -114,6 +114,16 @@ typedef struct jxf_coeff_view { /* HFCoefficients.quantizedCoeffs of one (pass, 
     int32_t h[3], w[3];
 } jxf_coeff_view;
 
+/* The same samples as the decode loop produced them (HFCoefficients.java:112-127: one store per decoded symbol, up to the
+ * block's last non-zero): the NON-ZERO ones of each channel in decode order, in the sparse wire format of jxlatte_amd.h
+ * (jxl_vardct_put_group_sparse). Channel c holds n[c] entries: narrow (one word: value << 16 | y << 8 | x) unless wide[c],
+ * then two words (y << 8 | x, value) -- wide when a value of the channel does not fit int16. h, w as in jxf_coeff_view. */
+typedef struct jxf_sparse_view {
+    const uint32_t* entries[3];
+    int32_t n[3], wide[3];
+    int32_t h[3], w[3];
+} jxf_sparse_view;
+
 typedef struct jxf_quant_view { /* one DCTParams set (HFGlobal.java); arrays are [3][n] flattened */
     int32_t mode;
     float denominator;
@@ -151,6 +161,7 @@ int32_t jxf_next_frame(jxf_dec* d, const jxf_hooks* hooks);
 int32_t jxf_get_frame_info(const jxf_dec* d, jxf_frame_info* out);
 int32_t jxf_get_lfgroup(const jxf_dec* d, int32_t index, jxf_lfgroup_view* out);
 int32_t jxf_get_coeffs(const jxf_dec* d, int32_t pass, int32_t group, jxf_coeff_view* out);
+int32_t jxf_get_coeffs_sparse(const jxf_dec* d, int32_t pass, int32_t group, jxf_sparse_view* out);
 int32_t jxf_get_quant_params(const jxf_dec* d, int32_t index, jxf_quant_view* out);
 int32_t jxf_get_patch(const jxf_dec* d, int32_t index, jxf_patch_view* out);
 /* number of splines of the current frame, and one of them */

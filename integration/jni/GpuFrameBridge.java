@@ -33,6 +33,12 @@ import com.traneptora.jxlatte.util.Point;
  *      script guards the reference's own performGabConvolution / performEdgePreservingFilter (Frame.java:457-461) and invertXYB
  *      (JXLCodestreamDecoder.java:266-267) with the flags this class sets on the frame (gpuRestored, gpuXYB).
  *
+ *   3  the fused cut of 2 with the SPARSE coefficient feed: only the non-zero coefficients cross the bus, as (position, value)
+ *      entries in the library's page-locked entry buffer (mapSparse + one commitSparse per pass). This is the form
+ *      HFCoefficients' decode loop produces (HFCoefficients.java:112-127: one store per decoded symbol); a reference patched at
+ *      that loop would append the entry where it stores the coefficient and never touch the dense int[][] -- this hook, which
+ *      sees the finished arrays, collects the same entries from them.
+ *
  * Otherwise the patched reference behaves as before.
  *
  * NOT COMPILED OR TESTED IN THIS REPOSITORY (no JDK in the build image). Our source, not reference code. Frames with chroma
@@ -52,6 +58,8 @@ public final class GpuFrameBridge {
             return 1;
         if ("2".equals(v))
             return 2;
+        if ("3".equals(v))
+            return 3;
         return 0;
     }
 
@@ -70,7 +78,7 @@ public final class GpuFrameBridge {
      *  (JXLCodestreamDecoder.java:615-637) and the frame's planes are not stored as an LF frame / reference before the transform. */
     private static boolean fuseXYB(Frame frame) {
         FrameHeader header = frame.getFrameHeader();
-        if (MODE != 2 || !frame.globalMetadata.isXYBEncoded())
+        if (MODE < 2 || !frame.globalMetadata.isXYBEncoded())
             return false;
         if (header.upsampling != 1 || header.lfLevel != 0 || header.type == FrameFlags.LF_FRAME)
             return false;
@@ -108,7 +116,7 @@ public final class GpuFrameBridge {
         Dimension padded = frame.getPaddedFrameSize();
         ByteBuffer p = direct(4 * 64);
         p.putInt(padded.width).putInt(padded.height);
-        p.putInt(MODE == 2 ? (1 | 2 | 4 | (xyb ? 8 : 0)) : 1); // stages: JXL_STAGE_IDCT (| GAB | EPF | XYB: the fused cut)
+        p.putInt(MODE >= 2 ? (1 | 2 | 4 | (xyb ? 8 : 0)) : 1); // stages: JXL_STAGE_IDCT (| GAB | EPF | XYB: the fused cut)
         float globalScale = 65536.0f / lfGlobal.globalScale; // HFCoefficients.java:270-275
         p.putFloat(globalScale * (float)Math.pow(0.8D, header.xqmScale - 2D));
         p.putFloat(globalScale);
@@ -217,6 +225,65 @@ public final class GpuFrameBridge {
         }
     }
 
+    /** mode 3: every pass as one commitSparse of the non-zero coefficients. A run = the entries of one (group, channel), starting
+     *  on a 16-byte boundary of the entry buffer; narrow entries (value << 16 | y << 8 | x) unless a value of the run does not fit
+     *  int16, then wide ones (y << 8 | x, value). The entries ADD on the device, so pass p > 0 accumulates (PassGroup.java:174-200). */
+    private static void putCoefficientsSparse(NativeBackend nb, PassGroup[][] passGroups, int numPasses, int numGroups) {
+        for (int pass = 0; pass < numPasses; pass++) {
+            // count first: two words per non-zero cover both entry forms, rounded up to the 16-byte start of the next run
+            long words = 0;
+            for (int group = 0; group < numGroups; group++) {
+                int[][][] q = passGroups[pass][group].hfCoefficients.quantizedCoeffs;
+                for (int c = 0; c < 3; c++) {
+                    long nz = 0;
+                    for (int[] row : q[c])
+                        for (int v : row)
+                            if (v != 0)
+                                nz++;
+                    words += ((2 * nz + 3) & ~3L);
+                }
+            }
+            java.nio.IntBuffer ib = nb.mapSparse(Math.max(4, words)).order(ByteOrder.nativeOrder()).asIntBuffer();
+            int[] runs = new int[5 * 3 * numGroups];
+            int nRuns = 0, at = 0;
+            for (int group = 0; group < numGroups; group++) {
+                int[][][] q = passGroups[pass][group].hfCoefficients.quantizedCoeffs;
+                for (int c = 0; c < 3; c++) {
+                    boolean wide = false;
+                    for (int[] row : q[c])
+                        for (int v : row)
+                            wide |= v < -32768 || v > 32767;
+                    int count = 0, start = at;
+                    for (int y = 0; y < q[c].length; y++) {
+                        int[] row = q[c][y];
+                        for (int x = 0; x < row.length; x++) {
+                            int v = row[x];
+                            if (v == 0)
+                                continue;
+                            if (wide) {
+                                ib.put(at++, y << 8 | x);
+                                ib.put(at++, v);
+                            } else {
+                                ib.put(at++, v << 16 | y << 8 | x);
+                            }
+                            count++;
+                        }
+                    }
+                    while ((at & 3) != 0)
+                        ib.put(at++, 0); // a zero entry changes nothing
+                    if (count == 0)
+                        continue;
+                    runs[nRuns++] = group;
+                    runs[nRuns++] = c;
+                    runs[nRuns++] = wide ? 1 : 0;
+                    runs[nRuns++] = count;
+                    runs[nRuns++] = start;
+                }
+            }
+            nb.commitSparse(java.util.Arrays.copyOf(runs, nRuns));
+        }
+    }
+
     public static synchronized void invertVarDCT(Frame frame, float[][][] buffers, PassGroup[][] passGroups, LFGroup[] lfGroups,
             int numPasses, int numGroups) {
         if (backend == null)
@@ -246,7 +313,9 @@ public final class GpuFrameBridge {
                 ints(m.hfStreamBuffer[0], kh, kw), ints(m.hfStreamBuffer[1], kh, kw), blocks, m.blockList.length,
                 floats(lf[0], ch, cw), floats(lf[1], ch, cw), floats(lf[2], ch, cw));
         }
-        if (MODE == 2 && numPasses == 1) {
+        if (MODE == 3) {
+            putCoefficientsSparse(nb, passGroups, numPasses, numGroups);
+        } else if (MODE == 2 && numPasses == 1) {
             putCoefficientsMapped(nb, frame, passGroups[0], numGroups);
         } else {
             for (int pass = 0; pass < numPasses; pass++) {
@@ -272,7 +341,7 @@ public final class GpuFrameBridge {
             }
         }
         // what the reference must NOT do again for this frame (fields added by tools/patch_reference_for_gpu.sh)
-        frame.gpuRestored = MODE == 2;
+        frame.gpuRestored = MODE >= 2;
         frame.gpuXYB = xyb;
     }
 }

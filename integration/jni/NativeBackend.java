@@ -50,6 +50,17 @@ public final class NativeBackend implements AutoCloseable {
     /** the same planes without the zero-fill: the decoder writes every sample of the groups it then names in commitCoeffsI16Groups */
     public native ByteBuffer[] mapCoeffsI16NoFill();               // jxl_vardct_map_coeffs_i16_ex(JXL_MAP_NO_FILL)
     public native void commitCoeffsI16Groups(byte[] groupWritten); // jxl_vardct_commit_coeffs_i16_groups
+    /** Sparse coefficient feed: only the non-zero coefficients, as the entries HFCoefficients' decode loop produces
+     *  (HFCoefficients.java:112-127). Narrow entry: one int, value << 16 | y << 8 | x; wide: two ints, (y << 8 | x, value).
+     *  nX/nY/nB entries in the three direct buffers (a channel without entries may pass null). Pass 0 replaces the group. */
+    public native void putGroupSparse(int pass, int group, ByteBuffer eX, ByteBuffer eY, ByteBuffer eB, int nX, int nY, int nB,
+        boolean wide);                                             // jxl_vardct_put_group_sparse
+    /** The library's page-locked entry buffer (capacityWords ints): append runs of entries, each starting at a multiple of
+     *  four ints, then commitSparse. Valid until the next beginFrame. */
+    public native ByteBuffer mapSparse(long capacityWords);        // jxl_vardct_map_sparse + NewDirectByteBuffer
+    /** runs: five ints per run {group, channel, flags (1 = wide), count, offsetWords}; the entries ADD into the planes. */
+    public native void commitSparse(int[] runs);                   // jxl_vardct_commit_sparse
+    public native long sparseRejected();                           // jxl_vardct_sparse_rejected
     /** Page-locked direct buffers for planes that cross the bus (coefficients in, pixels out). */
     public static native ByteBuffer hostAlloc(long bytes);         // jxl_host_alloc + NewDirectByteBuffer
     public static native void hostFree(ByteBuffer b);              // jxl_host_free(GetDirectBufferAddress(b))

@@ -8,6 +8,7 @@
  */
 #include <jni.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "jxlatte_amd.h"
@@ -283,6 +284,84 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_commitCoeff
     const jxl_status r = jxl_vardct_commit_coeffs_i16_groups(c, (const uint8_t*)w, (int32_t)n);
     (*e)->ReleaseByteArrayElements(e, written, w, JNI_ABORT);
     if (r) rethrow(e, c, r);
+}
+
+/* ---- sparse coefficient feed: lists of (position, value) entries, the form HFCoefficients' decode loop produces (HFCoefficients.java:112-127) ---- */
+/* n entries of 4 (narrow) or 8 (wide) bytes in each direct buffer; a channel without entries may pass null. The group index is checked
+ * against the open frame (jxl_vardct_group_size) before any buffer is looked at; positions are checked by the library. */
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_putGroupSparse(JNIEnv* e, jobject self, jint pass, jint group, jobject ex,
+        jobject ey, jobject eb, jint nx, jint ny, jint nb, jboolean wide) {
+    jxl_ctx* c = ctx_of(e, self);
+    const int32_t n[3] = {nx, ny, nb};
+    int32_t gw[3], gh[3];
+    CHECK(jxl_vardct_group_size(c, group, gw, gh));
+    {
+        jobject b[3] = {ex, ey, eb};
+        for (int ch = 0; ch < 3; ch++) {
+            if (n[ch] < 0) {
+                bad_arg(e, "jxlatte_amd: putGroupSparse negative entry count");
+                return;
+            }
+            if (n[ch] > 0 && !has_room(e, b[ch], (jlong)n[ch] * (wide ? 8 : 4))) {
+                bad_arg(e, "jxlatte_amd: putGroupSparse entry buffer missing or too small for its count");
+                return;
+            }
+        }
+    }
+    const uint32_t* q[3] = {nx ? (const uint32_t*)ADDR(ex) : NULL, ny ? (const uint32_t*)ADDR(ey) : NULL, nb ? (const uint32_t*)ADDR(eb) : NULL};
+    CHECK(jxl_vardct_put_group_sparse(c, pass, group, q, n, wide ? JXL_SPARSE_WIDE : 0));
+}
+
+/* the library's page-locked entry buffer of capacityWords 32-bit words, as ONE direct buffer of exactly that size */
+JNIEXPORT jobject JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_mapSparse(JNIEnv* e, jobject self, jlong capacityWords) {
+    jxl_ctx* c = ctx_of(e, self);
+    uint32_t* words = NULL;
+    if (capacityWords <= 0) {
+        bad_arg(e, "jxlatte_amd: mapSparse capacity must be positive");
+        return NULL;
+    }
+    jxl_status r = jxl_vardct_map_sparse(c, (size_t)capacityWords, &words);
+    if (r) { rethrow(e, c, r); return NULL; }
+    return (*e)->NewDirectByteBuffer(e, words, capacityWords * 4);
+}
+
+/* runs: five ints per run {group, channel, flags, count, offsetWords}; every run is checked by the library against the frame
+ * and the mapped capacity before anything is queued */
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_commitSparse(JNIEnv* e, jobject self, jintArray runs) {
+    jxl_ctx* c = ctx_of(e, self);
+    if (!runs) { rethrow(e, c, JXL_ERR_INVALID_ARGUMENT); return; }
+    const jsize len = (*e)->GetArrayLength(e, runs);
+    if (len % 5) {
+        bad_arg(e, "jxlatte_amd: commitSparse takes five ints per run");
+        return;
+    }
+    const jsize n = len / 5;
+    jint* v = (jint*)malloc(sizeof(jint) * (size_t)(len ? len : 1));
+    jxl_sparse_run* r = (jxl_sparse_run*)malloc(sizeof(jxl_sparse_run) * (size_t)(n ? n : 1));
+    if (!v || !r) {
+        free(v); free(r);
+        rethrow(e, c, JXL_ERR_OOM);
+        return;
+    }
+    (*e)->GetIntArrayRegion(e, runs, 0, len, v);
+    jxl_status st = JXL_OK;
+    if (!(*e)->ExceptionCheck(e)) {
+        for (jsize i = 0; i < n; i++) {
+            r[i].group = v[5 * i]; r[i].channel = v[5 * i + 1]; r[i].flags = v[5 * i + 2]; r[i].count = v[5 * i + 3];
+            r[i].offset_words = v[5 * i + 4];
+        }
+        st = jxl_vardct_commit_sparse(c, r, (int32_t)n);
+    }
+    free(v); free(r);
+    if (st) rethrow(e, c, st);
+}
+
+JNIEXPORT jlong JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_sparseRejected(JNIEnv* e, jobject self) {
+    jxl_ctx* c = ctx_of(e, self);
+    int64_t n = 0;
+    jxl_status r = jxl_vardct_sparse_rejected(c, &n);
+    if (r) { rethrow(e, c, r); return 0; }
+    return (jlong)n;
 }
 
 JNIEXPORT jobject JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_hostAlloc(JNIEnv* e, jclass k, jlong bytes) {

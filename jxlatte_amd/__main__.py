@@ -14,6 +14,8 @@ def main(argv=None):
     ap.add_argument("--png-depth", type=int, default=-1)
     ap.add_argument("--info", action="store_true", help="print the image / frame headers and stop")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--sparse-coeffs", action="store_true",
+                    help="feed the HF coefficients as lists of non-zero entries (jxl_vardct_put_group_sparse); same pixels")
     a = ap.parse_args(argv)
     from . import frontend
     if a.info:
@@ -25,7 +27,7 @@ def main(argv=None):
     from .decoder import DeviceBackend, JXLDecoder, PNGWriter
     t0 = time.time()
     backend = DeviceBackend(a.device)
-    dec = JXLDecoder(a.input, backend=backend)
+    dec = JXLDecoder(a.input, backend=backend, sparse_coeffs=a.sparse_coeffs)
     image = dec.decode()
     if image is None:
         print("jxlatte_amd: no frames", file=sys.stderr)

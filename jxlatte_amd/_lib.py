@@ -76,6 +76,10 @@ SIGNATURES = {
     "jxl_vardct_commit_coeffs_i16": (i32, [vp]),
     "jxl_vardct_map_coeffs_i16_ex": (i32, [vp, C.POINTER(C.POINTER(C.c_int16)), pi, i32]),
     "jxl_vardct_commit_coeffs_i16_groups": (i32, [vp, C.POINTER(C.c_uint8), i32]),
+    "jxl_vardct_put_group_sparse": (i32, [vp, i32, i32, C.POINTER(C.POINTER(C.c_uint32)), pi, i32]),
+    "jxl_vardct_map_sparse": (i32, [vp, C.c_size_t, C.POINTER(C.POINTER(C.c_uint32))]),
+    "jxl_vardct_commit_sparse": (i32, [vp, C.POINTER(abi.SparseRun), i32]),
+    "jxl_vardct_sparse_rejected": (i32, [vp, C.POINTER(C.c_int64)]),
     "jxl_host_alloc": (vp, [C.c_size_t]),
     "jxl_host_free": (None, [vp]),
     "jxl_vardct_prepare": (i32, [vp]),

@@ -126,6 +126,15 @@ def make_lfquant_desc(lf_quant, scaled_dequant, extra_precision=0, x_factor_lf=1
     return d
 
 
+SPARSE_WIDE = 1
+
+
+class SparseRun(C.Structure):
+    """struct jxl_sparse_run (one run of entries of the sparse coefficient feed)"""
+    _fields_ = [("group", C.c_int32), ("channel", C.c_int32), ("flags", C.c_int32), ("count", C.c_int32),
+                ("offset_words", C.c_int64)]
+
+
 class BlendRect(C.Structure):
     """struct jxl_blend_rect"""
     _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("canvas_y", C.c_int32), ("canvas_x", C.c_int32),

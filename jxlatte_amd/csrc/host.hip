@@ -190,6 +190,19 @@ struct jxl_ctx {
     hipEvent_t grp_ev[kGrpSlots] = {};
     bool grp_inflight[kGrpSlots] = {};
     int grp_slot = 0;
+    // sparse coefficient feed (jxl_vardct_put_group_sparse / map_sparse / commit_sparse; the kernels are in k_sparse.hip)
+    std::vector<uint8_t> grp_written;  // per group: a writer has touched its rectangle since begin_frame (a pass-0 sparse put must clear it)
+    uint32_t* h_sp = nullptr;          // page-locked entry words handed to the caller (jxl_vardct_map_sparse) and their device alias
+    const void* h_sp_dev = nullptr;
+    size_t sp_alloc_words = 0, sp_map_words = 0;
+    bool sp_valid = false;
+    hipEvent_t sp_ev = nullptr;        // "the commits' launches have read h_sp and the run table": what the next map waits for
+    bool sp_inflight = false;
+    SparseRec* h_sp_tab = nullptr;     // page-locked run records of the commits queued since the last map, appended at sp_tab_used
+    const SparseRec* h_sp_tab_dev = nullptr;
+    size_t sp_tab_cap = 0, sp_tab_used = 0;
+    DevBuf sp_rej;                     // count of refused entries (one 64-bit word), zeroed by the frame's first sparse launch
+    bool sp_rej_live = false;
     std::vector<float> h_weights_in;  // the last weight set handed over (set_weights skips an identical one)
     int32_t h_woffs_in[51] = {};
     DevBuf wg3_items[2];       // spatially ordered item lists of the two k_idct_wg3 classes (wg3_item_table)
@@ -1353,6 +1366,10 @@ void jxl_ctx_destroy(jxl_ctx* c) {
     if (c->out_ev) (void)hipEventDestroy(c->out_ev);
     if (c->h_map16) (void)hipHostFree(c->h_map16);
     c->h_map16 = nullptr;
+    if (c->sp_ev) (void)hipEventDestroy(c->sp_ev);
+    if (c->h_sp) (void)hipHostFree(c->h_sp);
+    if (c->h_sp_tab) (void)hipHostFree(c->h_sp_tab);
+    c->sp_rej.release();
     c->wg3_items[0].release();
     c->wg3_items[1].release();
     c->batch_restore_args.release();
@@ -1433,6 +1450,9 @@ jxl_status jxl_vardct_begin_frame(jxl_ctx* c, const jxl_vardct_params* p) {
     c->tables_dirty = true;
     c->frame_open = true;
     c->map16_valid = false;
+    c->sp_valid = false;
+    c->sp_rej_live = false;
+    c->grp_written.assign((size_t)ceil_div(c->W, 256) * ceil_div(c->H, 256), 0);
     c->ev_runs = 0;
     c->result[0] = c->result[1] = c->result[2] = nullptr;
     tm.mark("host vectors");
@@ -1642,6 +1662,37 @@ static const void* pinned_device_ptr(const void* p) {
     return at.type == hipMemoryTypeHost ? at.devicePointer : nullptr;
 }
 
+// the next slot of the page-locked staging ring of the put_group family (set up on first use), free to be written
+constexpr size_t kGrpSlotBytes = 3 * (size_t)256 * 256 * sizeof(int32_t);
+static jxl_status grp_ring_acquire(jxl_ctx* c, int* slot_out) {
+    if (!c->h_grp) {
+        // all or nothing: the ring is published (h_grp set) only when its device address and every event exist, so a
+        // failure here can never leave a later call with a null device address or null events
+        void *hp = nullptr, *dp = nullptr;
+        hipEvent_t ev[jxl_ctx::kGrpSlots] = {};
+        bool ok = hipHostMalloc(&hp, kGrpSlotBytes * jxl_ctx::kGrpSlots, hipHostMallocDefault) == hipSuccess && hp;
+        const bool have_mem = ok;
+        ok = ok && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess && dp;
+        for (int i = 0; i < jxl_ctx::kGrpSlots && ok; i++) ok = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            for (int i = 0; i < jxl_ctx::kGrpSlots; i++)
+                if (ev[i]) (void)hipEventDestroy(ev[i]);
+            if (hp && have_mem) (void)hipHostFree(hp);
+            return fail(c, have_mem ? JXL_ERR_DEVICE : JXL_ERR_OOM, "set-up of the page-locked group staging ring failed");
+        }
+        for (int i = 0; i < jxl_ctx::kGrpSlots; i++) c->grp_ev[i] = ev[i];
+        c->h_grp_dev = dp;
+        c->h_grp = hp;
+    }
+    const int slot = c->grp_slot;
+    c->grp_slot = (slot + 1) % jxl_ctx::kGrpSlots;
+    if (c->grp_inflight[slot]) HIP_TRY(c, hipEventSynchronize(c->grp_ev[slot]));
+    c->grp_inflight[slot] = false;
+    *slot_out = slot;
+    return JXL_OK;
+}
+
 // jxl_vardct_put_group / _i16. The group's three rectangles go to the device in ONE launch that reads host memory itself
 // (k_put_group): page-locked, 16-byte aligned caller buffers are read in place (the caller keeps them until the stream has
 // passed this point -- jxl_ctx_synchronize or a finished frame -- as with the queued copies of r2-r3); anything else is copied
@@ -1675,32 +1726,11 @@ static jxl_status put_group_t(jxl_ctx* c, int32_t pass, int32_t group, const T* 
         in_place = in_place && a.src[ch];
     }
     if ((st = zero_coeff_planes(c))) return st;
+    c->grp_written[group] = 1;
     if (!in_place) {
-        constexpr size_t kSlot = 3 * (size_t)256 * 256 * sizeof(int32_t);
-        if (!c->h_grp) {
-            // all or nothing: the ring is published (h_grp set) only when its device address and every event exist, so a
-            // failure here can never leave a later call with a null device address or null events
-            void *hp = nullptr, *dp = nullptr;
-            hipEvent_t ev[jxl_ctx::kGrpSlots] = {};
-            bool ok = hipHostMalloc(&hp, kSlot * jxl_ctx::kGrpSlots, hipHostMallocDefault) == hipSuccess && hp;
-            const bool have_mem = ok;
-            ok = ok && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess && dp;
-            for (int i = 0; i < jxl_ctx::kGrpSlots && ok; i++) ok = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
-            if (!ok) {
-                (void)hipGetLastError();
-                for (int i = 0; i < jxl_ctx::kGrpSlots; i++)
-                    if (ev[i]) (void)hipEventDestroy(ev[i]);
-                if (hp && have_mem) (void)hipHostFree(hp);
-                return fail(c, have_mem ? JXL_ERR_DEVICE : JXL_ERR_OOM, "set-up of the page-locked group staging ring failed");
-            }
-            for (int i = 0; i < jxl_ctx::kGrpSlots; i++) c->grp_ev[i] = ev[i];
-            c->h_grp_dev = dp;
-            c->h_grp = hp;
-        }
-        const int slot = c->grp_slot;
-        c->grp_slot = (slot + 1) % jxl_ctx::kGrpSlots;
-        if (c->grp_inflight[slot]) HIP_TRY(c, hipEventSynchronize(c->grp_ev[slot]));
-        c->grp_inflight[slot] = false;
+        constexpr size_t kSlot = kGrpSlotBytes;
+        int slot = 0;
+        if ((st = grp_ring_acquire(c, &slot))) return st;
         for (int ch = 0; ch < 3; ch++) {
             const size_t o = kSlot * slot + (size_t)ch * 256 * 256 * sizeof(int32_t);
             T* d = reinterpret_cast<T*>(static_cast<char*>(c->h_grp) + o);
@@ -1873,6 +1903,7 @@ static jxl_status commit_i16(jxl_ctx* c, const uint8_t* written, int32_t n_group
         off += (bytes + 255) & ~(size_t)255;
     }
     c->coeff_zero_pending = false;  // every sample of the three planes has just been written
+    std::fill(c->grp_written.begin(), c->grp_written.end(), (uint8_t)1);
     if (!c->map16_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->map16_ev, hipEventDisableTiming));
     HIP_TRY(c, hipEventRecord(c->map16_ev, c->stream));
     c->map16_inflight = true;
@@ -1885,6 +1916,241 @@ jxl_status jxl_vardct_commit_coeffs_i16_groups(jxl_ctx* c, const uint8_t* group_
     if (!c) return JXL_ERR_INVALID_ARGUMENT;
     if (!group_written) return fail(c, JXL_ERR_INVALID_ARGUMENT, "null group flags");
     return commit_i16(c, group_written, n_groups);
+}
+
+// ---- sparse coefficient feed (the scatter and clear kernels: k_sparse.hip) ----
+static SparseGeom sparse_geom(jxl_ctx* c) {
+    SparseGeom g;
+    for (int ch = 0; ch < 3; ch++) {
+        g.plane[ch] = c->coeff[ch].as<int32_t>();
+        g.sx[ch] = c->sx[ch];
+        g.sy[ch] = c->sy[ch];
+    }
+    g.W = c->W;
+    g.H = c->H;
+    return g;
+}
+
+// what every sparse launch needs first: the refused-entry counter at zero for this frame, the planes zeroed
+static jxl_status sparse_prelaunch(jxl_ctx* c) {
+    if (!c->sp_rej.ensure(sizeof(unsigned long long))) return fail(c, JXL_ERR_OOM, "device allocation failed (sparse feed)");
+    if (!c->sp_rej_live) HIP_TRY(c, hipMemsetAsync(c->sp_rej.p, 0, sizeof(unsigned long long), c->stream));
+    c->sp_rej_live = true;
+    return zero_coeff_planes(c);
+}
+
+// page-locked, 16-byte aligned, and all of it inside one registration: the device reads it in place (never past its last word)
+static const void* sparse_in_place_ptr(const uint32_t* p, size_t words) {
+    if ((uintptr_t)p & 15) return nullptr;
+    const void* alias = pinned_device_ptr(p);
+    if (!alias) return nullptr;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t) const_cast<void*>(alias)) != hipSuccess || !base || !size) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    const uintptr_t lo = (uintptr_t)base, a0 = (uintptr_t)alias;
+    return a0 >= lo && a0 + words * 4 <= lo + size ? alias : nullptr;
+}
+
+jxl_status jxl_vardct_put_group_sparse(jxl_ctx* c, int32_t pass, int32_t group, const uint32_t* const entries[3], const int32_t n_entries[3],
+                                       int32_t flags) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (!c->frame_open) return fail(c, JXL_ERR_STATE, "begin_frame first");
+    const int n_groups = ceil_div(c->W, 256) * ceil_div(c->H, 256);
+    if (group < 0 || group >= n_groups || pass < 0 || !entries || !n_entries) return fail(c, JXL_ERR_INVALID_ARGUMENT, "bad group/pass");
+    if (flags & ~JXL_SPARSE_WIDE) return fail(c, JXL_ERR_INVALID_ARGUMENT, "put_group_sparse: unknown flags");
+    const bool wide = (flags & JXL_SPARSE_WIDE) != 0;
+    const int wpe = wide ? 2 : 1;  // words per entry
+    const void* src[3] = {nullptr, nullptr, nullptr};
+    SparseRect rc[3];
+    bool in_place = true;
+    for (int ch = 0; ch < 3; ch++) {
+        rc[ch] = sparse_rect(c->W, c->H, c->sx[ch], c->sy[ch], group);
+        if (n_entries[ch] < 0 || n_entries[ch] > (1 << 28) || (n_entries[ch] && !entries[ch])) return fail(c, JXL_ERR_INVALID_ARGUMENT, "bad entry list %d", ch);
+        if (!n_entries[ch]) continue;
+        if (in_place) src[ch] = sparse_in_place_ptr(entries[ch], (size_t)n_entries[ch] * wpe);
+        in_place = in_place && src[ch];
+    }
+    if (!in_place)  // the copying path: nothing the device would have to refuse gets as far as the staging ring
+        for (int ch = 0; ch < 3; ch++)
+            if (!sparse_entries_valid(entries[ch], n_entries[ch], wide, rc[ch].gw, rc[ch].gh))
+                return fail(c, JXL_ERR_INVALID_ARGUMENT, "put_group_sparse: an entry of channel %d lies outside the group's %dx%d rectangle", ch, rc[ch].gw, rc[ch].gh);
+    if ((st = sparse_prelaunch(c))) return st;
+    const SparseGeom g = sparse_geom(c);
+    // pass 0 replaces the rectangle (HFCoefficients.java:68: a fresh int[][]); a group nothing has written since begin_frame is still zero
+    if (pass == 0 && c->grp_written[group]) launch_sparse_clear(g, group, c->stream);
+    c->grp_written[group] = 1;
+    const uint32_t wflag = wide ? 0x80000000u : 0u;
+    const int grid = bus_grid(c, false);
+    unsigned long long* rej = c->sp_rej.as<unsigned long long>();
+    if (in_place) {
+        SparseRec recs[3];
+        int n = 0;
+        uint32_t chunks = 0;
+        for (int ch = 0; ch < 3; ch++) {
+            if (!n_entries[ch]) continue;
+            recs[n++] = SparseRec{chunks, 0u, (uint32_t)n_entries[ch] | wflag, (uint32_t)group | (uint32_t)ch << 24 | (uint32_t)ch << 26};
+            chunks += (uint32_t)(((size_t)n_entries[ch] * wpe + 3) >> 2);
+        }
+        launch_sparse_scatter(g, recs, nullptr, n, chunks, src, rej, grid, c->stream);
+    } else {
+        // through the staging ring, one slot per launch; a list longer than a slot (wide entries of a dense group) takes several
+        constexpr uint32_t kSlotChunks = (uint32_t)(kGrpSlotBytes / 16);
+        const uint32_t epc = wide ? 2 : 4;  // entries per chunk
+        int ch = 0;
+        int32_t done = 0;  // entries of channel ch already staged
+        for (;;) {
+            while (ch < 3 && done >= n_entries[ch]) { ch++; done = 0; }
+            if (ch >= 3) break;
+            int slot = 0;
+            if ((st = grp_ring_acquire(c, &slot))) return st;
+            uint32_t* hp = reinterpret_cast<uint32_t*>(static_cast<char*>(c->h_grp) + kGrpSlotBytes * slot);
+            const void* one[3] = {static_cast<const char*>(c->h_grp_dev) + kGrpSlotBytes * slot, nullptr, nullptr};
+            SparseRec recs[3];
+            int n = 0;
+            uint32_t cur = 0;
+            while (ch < 3 && cur < kSlotChunks) {
+                const int32_t take = (int32_t)std::min<int64_t>(n_entries[ch] - done, (int64_t)(kSlotChunks - cur) * epc);
+                if (take > 0) {
+                    memcpy(hp + (size_t)cur * 4, entries[ch] + (size_t)done * wpe, (size_t)take * wpe * 4);
+                    recs[n++] = SparseRec{cur, cur, (uint32_t)take | wflag, (uint32_t)group | (uint32_t)ch << 24};
+                    cur += ((uint32_t)take + epc - 1) / epc;
+                    done += take;
+                }
+                if (done < n_entries[ch]) break;  // the slot is full: the rest of this channel goes into the next one
+                ch++;
+                done = 0;
+            }
+            launch_sparse_scatter(g, recs, nullptr, n, cur, one, rej, grid, c->stream);
+            HIP_TRY(c, hipEventRecord(c->grp_ev[slot], c->stream));
+            c->grp_inflight[slot] = true;
+        }
+    }
+    HIP_TRY(c, hipGetLastError());
+    return JXL_OK;
+}
+
+jxl_status jxl_vardct_map_sparse(jxl_ctx* c, size_t capacity_words, uint32_t** words) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (!c->frame_open) return fail(c, JXL_ERR_STATE, "begin_frame first");
+    if (!words || capacity_words == 0 || capacity_words > ((size_t)1 << 34)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "map_sparse: bad argument");
+    // the buffer may be written again once the commits' launches have READ it: their event, not the whole stream (as map16_ev)
+    if (c->sp_inflight && c->sp_ev) HIP_TRY(c, hipEventSynchronize(c->sp_ev));
+    c->sp_inflight = false;
+    c->sp_tab_used = 0;
+    if (!c->is_feeder && c->device >= 0 && c->device < 64) {
+        c->is_feeder = true;
+        g_feeders[c->device].fetch_add(1, std::memory_order_relaxed);
+    }
+    const size_t need = (capacity_words + 3) & ~(size_t)3;  // the device reads whole 16-byte chunks
+    if (c->sp_alloc_words < need) {
+        if (c->h_sp) (void)hipHostFree(c->h_sp);
+        c->h_sp = nullptr;
+        c->sp_alloc_words = 0;
+        c->sp_valid = false;
+        void *hp = nullptr, *dp = nullptr;
+        if (hipHostMalloc(&hp, need * 4, hipHostMallocDefault) != hipSuccess || !hp) {
+            (void)hipGetLastError();
+            return fail(c, JXL_ERR_OOM, "page-locked allocation of %zu bytes failed", need * 4);
+        }
+        if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess || !dp) {
+            (void)hipGetLastError();
+            (void)hipHostFree(hp);
+            return fail(c, JXL_ERR_DEVICE, "no device address for the page-locked entry buffer");
+        }
+        c->h_sp = static_cast<uint32_t*>(hp);
+        c->h_sp_dev = dp;
+        c->sp_alloc_words = need;
+    }
+    c->sp_map_words = capacity_words;
+    c->sp_valid = true;
+    *words = c->h_sp;
+    return JXL_OK;
+}
+
+jxl_status jxl_vardct_commit_sparse(jxl_ctx* c, const jxl_sparse_run* runs, int32_t n_runs) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (!c->frame_open || !c->sp_valid) return fail(c, JXL_ERR_STATE, "map_sparse first");
+    if (n_runs < 0 || (n_runs && !runs)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "commit_sparse: bad run list");
+    // every run is checked before anything is queued: a failed call leaves no work in flight
+    const int n_groups = ceil_div(c->W, 256) * ceil_div(c->H, 256);
+    size_t n_recs = 0;
+    for (int32_t i = 0; i < n_runs; i++) {
+        const jxl_sparse_run& r = runs[i];
+        if (r.group < 0 || r.group >= n_groups || r.channel < 0 || r.channel > 2) return fail(c, JXL_ERR_INVALID_ARGUMENT, "commit_sparse: run %d names group %d channel %d", i, r.group, r.channel);
+        if (r.flags & ~JXL_SPARSE_WIDE) return fail(c, JXL_ERR_INVALID_ARGUMENT, "commit_sparse: run %d has unknown flags", i);
+        if (r.count < 0 || r.offset_words < 0 || (r.offset_words & 3)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "commit_sparse: run %d: count / offset (16-byte aligned) out of range", i);
+        if ((uint64_t)r.offset_words + (uint64_t)r.count * ((r.flags & JXL_SPARSE_WIDE) ? 2 : 1) > c->sp_map_words)
+            return fail(c, JXL_ERR_INVALID_ARGUMENT, "commit_sparse: run %d ends past the mapped %zu words", i, c->sp_map_words);
+        n_recs += r.count > 0;
+    }
+    if (c->sp_tab_used + n_recs > c->sp_tab_cap) {
+        // the table wraps (or grows): the launches that read its earlier records must have finished
+        if (c->sp_inflight && c->sp_ev) HIP_TRY(c, hipEventSynchronize(c->sp_ev));
+        c->sp_inflight = false;
+        c->sp_tab_used = 0;
+        if (n_recs > c->sp_tab_cap) {
+            const size_t cap = std::max<size_t>(n_recs, 4096);
+            void *hp = nullptr, *dp = nullptr;
+            if (hipHostMalloc(&hp, cap * sizeof(SparseRec), hipHostMallocDefault) != hipSuccess || !hp ||
+                hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess || !dp) {
+                (void)hipGetLastError();
+                if (hp) (void)hipHostFree(hp);
+                return fail(c, JXL_ERR_OOM, "page-locked allocation of the run table failed");
+            }
+            if (c->h_sp_tab) (void)hipHostFree(c->h_sp_tab);
+            c->h_sp_tab = static_cast<SparseRec*>(hp);
+            c->h_sp_tab_dev = static_cast<const SparseRec*>(dp);
+            c->sp_tab_cap = cap;
+        }
+    }
+    if (!c->sp_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->sp_ev, hipEventDisableTiming));
+    if ((st = sparse_prelaunch(c))) return st;
+    const SparseGeom g = sparse_geom(c);
+    const void* src[3] = {c->h_sp_dev, nullptr, nullptr};
+    const int grid = bus_grid(c, false);
+    // one launch per kSparseMaxRuns records (a 4K frame's 1 215 runs: one launch), each with its own chunk prefix sums
+    for (int32_t i = 0; i < n_runs;) {
+        const size_t first = c->sp_tab_used;
+        int n = 0;
+        uint64_t chunks = 0;
+        for (; i < n_runs && n < kSparseMaxRuns; i++) {
+            const jxl_sparse_run& r = runs[i];
+            c->grp_written[r.group] = 1;
+            if (r.count <= 0) continue;
+            const bool wide = (r.flags & JXL_SPARSE_WIDE) != 0;
+            const uint64_t rc = ((uint64_t)r.count * (wide ? 2 : 1) + 3) >> 2;
+            if (chunks + rc > 0x7fffffffu && n) break;
+            c->h_sp_tab[first + n++] = SparseRec{(uint32_t)chunks, (uint32_t)(r.offset_words >> 2), (uint32_t)r.count | (wide ? 0x80000000u : 0u),
+                                                 (uint32_t)r.group | (uint32_t)r.channel << 24};
+            chunks += rc;
+        }
+        c->sp_tab_used += n;
+        launch_sparse_scatter(g, c->h_sp_tab + first, c->h_sp_tab_dev + first, n, (uint32_t)chunks, src, c->sp_rej.as<unsigned long long>(), grid, c->stream);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->sp_ev, c->stream));
+    c->sp_inflight = true;
+    return JXL_OK;
+}
+
+jxl_status jxl_vardct_sparse_rejected(jxl_ctx* c, int64_t* n) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (!c->frame_open) return fail(c, JXL_ERR_STATE, "begin_frame first");
+    if (!n) return fail(c, JXL_ERR_INVALID_ARGUMENT, "null argument");
+    *n = 0;
+    if (!c->sp_rej_live) return JXL_OK;  // no sparse launch in this frame yet
+    unsigned long long v = 0;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(&v, c->sp_rej.p, sizeof v, hipMemcpyDeviceToHost));
+    *n = (int64_t)v;
+    return JXL_OK;
 }
 
 void* jxl_host_alloc(size_t bytes) {

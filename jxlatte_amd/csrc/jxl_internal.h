@@ -154,6 +154,38 @@ void launch_idct_large(const DevFrame& f, const DevBlock* blocks, const DevBlock
                        float* const out[3], float* const scratch[3], hipStream_t s, int* n_launches);
 void launch_accumulate(int32_t* dst, const int32_t* src, int64_t n, hipStream_t s);
 
+// ---- sparse coefficient feed (k_sparse.hip): lists of (position, value) entries scattered into the tiled planes ----
+// One run of entries of one (group, channel), as the scatter kernel sees it: 16 bytes, so that the table of a whole 4K frame
+// (1 215 runs) sits in LDS. The run's geometry (plane, origin, gw, gh) is recomputed from group / channel and SparseGeom.
+struct SparseRec {
+    uint32_t chunk_first;  // prefix sum: index of the run's first 16-byte chunk among the launch's chunks
+    uint32_t chunk_src;    // where that chunk is: in 16-byte units from the base of source `src`
+    uint32_t count_wide;   // entries of the run | wide form << 31
+    uint32_t where;        // group | channel << 24 | source << 26
+};
+static_assert(sizeof(SparseRec) == 16, "one dwordx4 per run record");
+constexpr int kSparseMaxRuns = 2048;  // run records of one launch (32 KB of LDS); longer run lists take more launches
+struct SparseGeom {
+    int32_t* plane[3];      // the tiled coefficient planes (coeff_off)
+    int32_t W, H;           // padded frame
+    int32_t sx[3], sy[3];   // jpeg upsampling shifts per channel
+};
+// the rectangle of `group` in channel ch's own geometry (Frame.getGroupLocation / getGroupSize, Frame.java:883-905)
+struct SparseRect { int32_t W, y0, x0, gw, gh; };
+__host__ __device__ inline SparseRect sparse_rect(int W, int H, int sx, int sy, int group) {
+    const int grs = (W + 255) >> 8, gy = group / grs, gx = group - gy * grs;
+    const int gh = H - gy * 256 < 256 ? H - gy * 256 : 256, gw = W - gx * 256 < 256 ? W - gx * 256 : 256;
+    return SparseRect{W >> sx, (gy * 256) >> sy, (gx * 256) >> sx, gw >> sx, gh >> sy};
+}
+// entries at positions outside [0, gh) x [0, gw) (a wide entry: also any bit above the low 16 of its position word)
+bool sparse_entries_valid(const uint32_t* words, int32_t n_entries, bool wide, int gw, int gh);
+// n_recs <= kSparseMaxRuns records (host memory: copied into the launch's arguments when n_recs <= 3, else `recs_dev` is
+// their device-visible address), total_chunks = sum of their chunks; src[k] device-visible bases of the entry words
+void launch_sparse_scatter(const SparseGeom& g, const SparseRec* recs, const SparseRec* recs_dev, int n_recs, uint32_t total_chunks,
+                           const void* const src[3], unsigned long long* rejected, int grid, hipStream_t s);
+// zero the rectangles of `group` in the three planes (a pass-0 put over a group that has been written before)
+void launch_sparse_clear(const SparseGeom& g, int group, hipStream_t s);
+
 void launch_gab(const float* const in[3], float* const out[3], int h, int w, const float w1[3], const float w2[3],
                 hipStream_t s);
 void launch_epf_sigma(const int32_t* hf_mul, const int32_t* sharpness, int bh, int bw, float global_scale_f,

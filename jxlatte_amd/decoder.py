@@ -311,6 +311,21 @@ def lf_from_lf_frame(lf_buffer, lfg_y, lfg_x, cells_h, cells_w, jpeg_up_y, jpeg_
     return out
 
 
+def put_group_sparse(hf, pass_, grp, sp):
+    """one (pass, group) of frontend.Frontend.coeffs_sparse -> host.Frame.putGroupSparseEntries. A call carries ONE entry form:
+    when only some channels came back wide (a value outside int16), the narrow lists are widened"""
+    wide = any(w for _, w, _ in sp)
+    ents = []
+    for e, w, _ in sp:
+        if wide and not w:
+            t = np.empty(2 * e.size, np.uint32)
+            t[0::2] = e & 0xffff
+            t[1::2] = (e >> 16).astype(np.uint16).view(np.int16).astype(np.int32).view(np.uint32)
+            e = t
+        ents.append(e)
+    hf.putGroupSparseEntries(pass_, grp, ents, wide)
+
+
 class DeviceBackend:
     """the product backend: HIP kernels through the C-ABI (jxlatte_amd._lib / host). No CPU fallback."""
 
@@ -327,7 +342,8 @@ class DeviceBackend:
     def keep_planes(self, planes):
         return self.host.ResidentPlanes.upload(self.ctx, planes)
 
-    def vardct(self, params, weights, woffs, lfgroups, groups, keep=None):
+    def vardct(self, params, weights, woffs, lfgroups, groups, keep=None, sparse=False):
+        """sparse: `groups` yields the entry lists of Frontend.coeffs_sparse, fed through jxl_vardct_put_group_sparse"""
         fr = self.host.Frame(self.ctx, params, weights, woffs)
         for g in lfgroups:
             fr.setLFGroup(g)
@@ -335,7 +351,10 @@ class DeviceBackend:
                 fr.setLFGroupQuant(g["lfg_y"], g["lfg_x"], g["lf_quant"], g["scaled_dequant"], g["extra_precision"], g["x_factor_lf"],
                                    g["b_factor_lf"], g["adaptive_smoothing"])
         for pass_, grp, q in groups:
-            fr.putGroup(pass_, grp, q)
+            if sparse:
+                put_group_sparse(fr, pass_, grp, q)
+            else:
+                fr.putGroup(pass_, grp, q)
         if keep is not None:  # the planes stay on the device for the stages after decodeFrame: host.ResidentPlanes
             return fr.keepPlanes(*keep)
         return fr.decodeFrame()
@@ -536,7 +555,10 @@ def _tt_dims():
 
 
 class JXLDecoder:
-    def __init__(self, source, backend=None):
+    def __init__(self, source, backend=None, sparse_coeffs=False):
+        """sparse_coeffs: hand the HF coefficients to the backend as lists of non-zero entries (jxf_get_coeffs_sparse ->
+        jxl_vardct_put_group_sparse), not as dense planes; same pixels"""
+        self.sparse_coeffs = bool(sparse_coeffs)
         if isinstance(source, (bytes, bytearray, memoryview)):
             data = bytes(source)
         else:
@@ -605,9 +627,11 @@ class JXLDecoder:
     def _vardct_frame(self, fr, fuse_xyb, keep=None):
         p, weights, woffs, lfgroups, groups, hist = self._vardct_inputs(fr, fuse_xyb)
         self.stats[-1]["varblocks"] = {abi.TT_NAME[t]: int(n) for t, n in enumerate(hist) if n}
+        sparse = getattr(self, "sparse_coeffs", False)
+        kw = dict(sparse=True) if sparse else {}
         if keep is not None:
-            return self.backend.vardct(p, weights, woffs, lfgroups, groups(), keep=keep)
-        planes = self.backend.vardct(p, weights, woffs, lfgroups, groups())
+            return self.backend.vardct(p, weights, woffs, lfgroups, groups(sparse), keep=keep, **kw)
+        planes = self.backend.vardct(p, weights, woffs, lfgroups, groups(sparse), **kw)
         return [np.ascontiguousarray(planes[c]) for c in range(3)]
 
     def _up_weights(self, k):
@@ -719,10 +743,10 @@ class JXLDecoder:
             hist += np.bincount(sel, minlength=27)[:27]
             lfgroups.append(g)
 
-        def groups():
+        def groups(sparse=False):
             for pass_ in range(fr.num_passes):
                 for grp in range(fr.num_groups):
-                    yield pass_, grp, fe.coeffs(pass_, grp)
+                    yield pass_, grp, fe.coeffs_sparse(pass_, grp) if sparse else fe.coeffs(pass_, grp)
         return p, weights, woffs, lfgroups, groups, hist
 
     def _modular_buffers(self, fr, buffers, colors):
@@ -1055,9 +1079,10 @@ class PNGWriter:
         out.write(self._chunk(b"IEND", b""))
 
 
-def load_vardct_frame(source, ctx, transfer=abi.TRANSFER_NONE, out_format=abi.OUT_F32):
+def load_vardct_frame(source, ctx, transfer=abi.TRANSFER_NONE, out_format=abi.OUT_F32, sparse=False):
     """Parse the first frame of a VarDCT .jxl file with the front-end and stage it in a host.Frame on `ctx` (inputs
-    resident, nothing run yet): the real-bitstream workload of bench.py. Returns (host.Frame, stats dict)."""
+    resident, nothing run yet): the real-bitstream workload of bench.py. Returns (host.Frame, stats dict).
+    sparse: the coefficients go through the sparse feed (jxl_vardct_put_group_sparse)."""
     from . import host
     if isinstance(source, (bytes, bytearray)):
         data = bytes(source)
@@ -1068,6 +1093,7 @@ def load_vardct_frame(source, ctx, transfer=abi.TRANSFER_NONE, out_format=abi.OU
     dec.fe = frontend.Frontend(data)
     dec.info = dec.fe.image
     dec.backend = None
+    dec.sparse_coeffs = bool(sparse)
     fr = dec.fe.next_frame(None, None)
     if fr is None or fr.encoding != VARDCT:
         raise ValueError("first frame is not a VarDCT frame")
@@ -1081,8 +1107,11 @@ def load_vardct_frame(source, ctx, transfer=abi.TRANSFER_NONE, out_format=abi.OU
         if g.get("lf_quant") is not None:
             hf.setLFGroupQuant(g["lfg_y"], g["lfg_x"], g["lf_quant"], g["scaled_dequant"],
                                g["extra_precision"], g["x_factor_lf"], g["b_factor_lf"], g["adaptive_smoothing"])
-    for pass_, grp, q in groups():
-        hf.putGroup(pass_, grp, q)
+    for pass_, grp, q in groups(sparse):
+        if sparse:
+            put_group_sparse(hf, pass_, grp, q)
+        else:
+            hf.putGroup(pass_, grp, q)
     stats = dict(width=fr.width, height=fr.height, padded_width=fr.padded_width, padded_height=fr.padded_height, groups=fr.num_groups,
                  passes=fr.num_passes, epf_iters=fr.epf_iters, gab=fr.gab,
                  varblocks={abi.TT_NAME[t]: int(n) for t, n in enumerate(hist) if n})

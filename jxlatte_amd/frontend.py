@@ -76,6 +76,11 @@ class CoeffView(C.Structure):
     _fields_ = [("q", C.POINTER(i32) * 3), ("h", _arr(i32, 3)), ("w", _arr(i32, 3))]
 
 
+class SparseView(C.Structure):
+    _fields_ = [("entries", C.POINTER(C.c_uint32) * 3), ("n", _arr(i32, 3)), ("wide", _arr(i32, 3)), ("h", _arr(i32, 3)),
+                ("w", _arr(i32, 3))]
+
+
 class QuantView(C.Structure):
     _fields_ = [("mode", i32), ("denominator", f32), ("n_dct", i32), ("n_par", i32), ("n_p44", i32),
                 ("dct", C.POINTER(f32)), ("par", C.POINTER(f32)), ("p44", C.POINTER(f32))]
@@ -106,6 +111,7 @@ SIGNATURES = {
     "jxf_get_frame_info": (i32, [C.c_void_p, C.POINTER(FrameInfo)]),
     "jxf_get_lfgroup": (i32, [C.c_void_p, i32, C.POINTER(LFGroupView)]),
     "jxf_get_coeffs": (i32, [C.c_void_p, i32, i32, C.POINTER(CoeffView)]),
+    "jxf_get_coeffs_sparse": (i32, [C.c_void_p, i32, i32, C.POINTER(SparseView)]),
     "jxf_get_quant_params": (i32, [C.c_void_p, i32, C.POINTER(QuantView)]),
     "jxf_get_patch": (i32, [C.c_void_p, i32, C.POINTER(PatchView)]),
     "jxf_num_splines": (i32, [C.c_void_p]),
@@ -242,6 +248,12 @@ class Frontend:
         v = CoeffView()
         self._check(self.lib.jxf_get_coeffs(self.h, pass_, group, C.byref(v)))
         return [_np(v.q[c], (v.h[c], v.w[c])) for c in range(3)]
+
+    def coeffs_sparse(self, pass_, group):
+        """per channel (entries, wide, (h, w)): the non-zero coefficients in decode order as packed entries (jxf_get_coeffs_sparse)"""
+        v = SparseView()
+        self._check(self.lib.jxf_get_coeffs_sparse(self.h, pass_, group, C.byref(v)))
+        return [(_np(v.entries[c], (v.n[c] * (2 if v.wide[c] else 1),), np.uint32), bool(v.wide[c]), (v.h[c], v.w[c])) for c in range(3)]
 
     def quant_params(self, index):
         v = QuantView()

@@ -292,6 +292,21 @@ int32_t jxf_get_coeffs(const jxf_dec* d, int32_t pass, int32_t group, jxf_coeff_
     return JXF_OK;
 }
 
+int32_t jxf_get_coeffs_sparse(const jxf_dec* d, int32_t pass, int32_t group, jxf_sparse_view* o) {
+    if (!d || !o || !d->frame) return JXF_ERR_STATE;
+    const Frame& f = *d->frame;
+    if (pass < 0 || pass >= (int32_t)f.coeffs.size() || group < 0 || group >= (int32_t)f.coeffs[pass].size()) return JXF_ERR_ARGUMENT;
+    const GroupCoeffs& g = f.coeffs[pass][group];
+    for (int c = 0; c < 3; c++) {
+        o->entries[c] = g.sparse[c].data();
+        o->wide[c] = g.sparse_wide[c] ? 1 : 0;
+        o->n[c] = (int32_t)(g.sparse[c].size() / (g.sparse_wide[c] ? 2 : 1));
+        o->h[c] = g.h[c];
+        o->w[c] = g.w[c];
+    }
+    return JXF_OK;
+}
+
 int32_t jxf_get_quant_params(const jxf_dec* dc, int32_t index, jxf_quant_view* o) {
     jxf_dec* d = const_cast<jxf_dec*>(dc);
     if (!d || !o || !d->frame || index < 0 || index > 16) return JXF_ERR_ARGUMENT;

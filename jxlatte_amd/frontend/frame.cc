@@ -564,6 +564,8 @@ void Frame::read_hf_coefficients(BitReader& br, int pass, int group) {
         out.h[c] = gh >> fh.jpeg_up_y[c];
         out.w[c] = gw >> fh.jpeg_up_x[c];
         out.q[c].assign((size_t)out.h[c] * out.w[c], 0);
+        out.sparse[c].clear();
+        out.sparse_wide[c] = false;
     }
     int32_t non_zeroes[3][32][32];
     memset(non_zeroes, 0, sizeof non_zeroes);
@@ -612,6 +614,7 @@ void Frame::read_hf_coefficients(BitReader& br, int pass, int group) {
             if (non_zero > order_size - num_blocks) throw BitstreamError("Illegal nonzero count");
             const int hist_ctx = offset + 458 * block_ctx + 37 * hfctx.num_clusters;
             int32_t* plane = out.q[c].data();
+            std::vector<uint32_t>& sparse = out.sparse[c];
             const int pw_ = out.w[c], ph_ = out.h[c];
             uint32_t prev_u = 0;
             for (int k = 0; k < order_size - num_blocks; k++) {
@@ -625,13 +628,26 @@ void Frame::read_hf_coefficients(BitReader& br, int pass, int group) {
                 const int oy = order[2 * (size_t)(k + num_blocks)], ox = order[2 * (size_t)(k + num_blocks) + 1];
                 const int y = (flip ? ox : oy) + py, x = (flip ? oy : ox) + px;
                 if (y >= ph_ || x >= pw_) throw BitstreamError("coefficient outside the group");
-                plane[(size_t)y * pw_ + x] = (int32_t)((uint32_t)unpack_signed(u) << shift);
+                const int32_t v = (int32_t)((uint32_t)unpack_signed(u) << shift);
+                plane[(size_t)y * pw_ + x] = v;
+                if (v != 0) {  // the sparse list: collected wide, narrowed below when every value of the channel fits int16
+                    sparse.push_back((uint32_t)y << 8 | (uint32_t)x);
+                    sparse.push_back((uint32_t)v);
+                    if (v < -32768 || v > 32767) out.sparse_wide[c] = true;
+                }
                 if (u != 0 && --non_zero == 0) break;
             }
             if (non_zero != 0) throw BitstreamError("Illegal final nonzero count");
         }
     }
     dec.check_final("PassGroup HF coefficients");
+    for (int c = 0; c < 3; c++) {
+        if (out.sparse_wide[c]) continue;
+        std::vector<uint32_t>& e = out.sparse[c];
+        const size_t n = e.size() / 2;
+        for (size_t i = 0; i < n; i++) e[i] = e[2 * i + 1] << 16 | e[2 * i];
+        e.resize(n);
+    }
 }
 
 void Frame::read_pass_group(BitReader& br, int pass, int group, const std::vector<int>& replaced_idx) {  // PassGroup.java:50-63

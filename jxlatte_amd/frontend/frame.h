@@ -56,6 +56,11 @@ struct LFGroupData {
 struct GroupCoeffs {
     int h[3] = {0, 0, 0}, w[3] = {0, 0, 0};
     std::vector<int32_t> q[3];
+    // the same samples as the decode loop produced them (HFCoefficients.java:112-127: one store per decoded symbol): the
+    // non-zero ones in decode order, in the sparse wire format of include/jxlatte_amd.h -- narrow entries
+    // (value << 16 | y << 8 | x) unless a value of the channel does not fit int16, then wide ones (y << 8 | x, value)
+    std::vector<uint32_t> sparse[3];
+    bool sparse_wide[3] = {false, false, false};
 };
 
 struct HFPass {

@@ -152,6 +152,48 @@ def transfer(ctx, x, tf, maxValue=0):
     return out
 
 
+def pack_sparse(planes, wide=False):
+    """The sparse wire format of include/jxlatte_amd.h: the non-zero samples of a 2-D integer plane (at most 256 x 256: one
+    group of one channel) as a uint32 array of entries in raster order -- narrow: value << 16 | y << 8 | x; wide: the words
+    (y << 8 | x, value) per entry. A sequence of planes gives a list. wide=False refuses a value outside int16."""
+    if not (isinstance(planes, np.ndarray) and planes.ndim == 2):
+        return [pack_sparse(a, wide) for a in planes]
+    a = planes
+    if a.shape[0] > 256 or a.shape[1] > 256:
+        raise ValueError("a group's plane is at most 256x256, not %dx%d" % a.shape)
+    ys, xs = np.nonzero(a)
+    v = a[ys, xs].astype(np.int64)
+    pos = (ys.astype(np.uint32) << 8) | xs.astype(np.uint32)
+    if wide:
+        if v.size and (v.min() < -2 ** 31 or v.max() >= 2 ** 31):
+            raise ValueError("value outside int32")
+        out = np.empty(2 * v.size, np.uint32)
+        out[0::2] = pos
+        out[1::2] = (v & 0xffffffff).astype(np.uint32)
+        return out
+    if v.size and (v.min() < -32768 or v.max() > 32767):
+        raise ValueError("value outside int16: use wide=True")
+    return ((v & 0xffff).astype(np.uint32) << 16) | pos
+
+
+def unpack_sparse(entries, shape, wide=False):
+    """inverse of pack_sparse: the int32 plane of `shape` that the entries describe (a list of entry arrays with a list of
+    shapes gives a list). Duplicate positions add, as on the device; a position outside the plane is a ValueError."""
+    if not (isinstance(entries, np.ndarray) and entries.ndim == 1):
+        return [unpack_sparse(e, s, wide) for e, s in zip(entries, shape)]
+    e = entries.astype(np.uint32, copy=False)
+    if wide:
+        pos, val = e[0::2], np.ascontiguousarray(e[1::2]).view(np.int32)
+    else:
+        pos, val = e & 0xffff, (e >> 16).astype(np.uint16).view(np.int16).astype(np.int32)
+    ys, xs = (pos >> 8).astype(np.int64), (pos & 255).astype(np.int64)
+    if pos.size and (int(pos.max()) >> 16 or ys.max() >= shape[0] or xs.max() >= shape[1]):
+        raise ValueError("entry outside the %dx%d plane" % tuple(shape))
+    out = np.zeros(shape, np.int64)
+    np.add.at(out, (ys, xs), val.astype(np.int64))
+    return (out & 0xffffffff).astype(np.uint32).view(np.int32)
+
+
 class Frame:
     """VarDCT side of J/frame/Frame.java: decodePassGroups tail (Frame.java:361-374), Gab, EPF and the
     colour transform of JXLCodestreamDecoder.performColorTransforms, as one device submission.
@@ -232,6 +274,47 @@ class Frame:
         else:
             w = np.ascontiguousarray(written, np.uint8)
             self.ctx.call("jxl_vardct_commit_coeffs_i16_groups", w.ctypes.data_as(C.POINTER(C.c_uint8)), int(w.size))
+
+    def putGroupSparse(self, pass_, group, q, wide=None):
+        """putGroup with the sparse wire format (jxl_vardct_put_group_sparse): the non-zero samples of the three planes as
+        (position, value) entries. wide=None picks the narrow form unless a value does not fit int16."""
+        q = [np.asarray(a) for a in q]
+        if wide is None:
+            wide = any(a.size and (int(a.min()) < -32768 or int(a.max()) > 32767) for a in q)
+        self.putGroupSparseEntries(pass_, group, [pack_sparse(a, wide) for a in q], wide)
+
+    def putGroupSparseEntries(self, pass_, group, entries, wide=False):
+        """entries: three uint32 arrays of packed entries (pack_sparse), handed over as they are -- page-locked, 16-byte
+        aligned ones are read by the device in place"""
+        e = [a if (isinstance(a, np.ndarray) and a.dtype == np.uint32 and a.ndim == 1 and a.flags["C_CONTIGUOUS"])
+             else np.ascontiguousarray(a, np.uint32).reshape(-1) for a in entries]
+        per = 2 if wide else 1
+        pp = (C.POINTER(C.c_uint32) * 3)(*[a.ctypes.data_as(C.POINTER(C.c_uint32)) for a in e])
+        n = (C.c_int32 * 3)(*[a.size // per for a in e])
+        self.ctx.call("jxl_vardct_put_group_sparse", pass_, group, pp, n, abi.SPARSE_WIDE if wide else 0)
+        self._keep = getattr(self, "_keep", []) + [e]  # in-place sources: keep them alive until run()
+
+    def mapSparse(self, capacity):
+        """the library's page-locked entry buffer of `capacity` uint32 words as a numpy view (jxl_vardct_map_sparse): write
+        runs of entries into it, then commitSparse(runs)"""
+        p = C.POINTER(C.c_uint32)()
+        self.ctx.call("jxl_vardct_map_sparse", C.c_size_t(int(capacity)), C.byref(p))
+        buf = (C.c_uint32 * int(capacity)).from_address(C.addressof(p.contents))
+        return np.frombuffer(buf, dtype=np.uint32)
+
+    def commitSparse(self, runs):
+        """runs: (group, channel, offset_words, count, wide) per run (jxl_vardct_commit_sparse); entries ADD into the planes"""
+        arr = (abi.SparseRun * max(1, len(runs)))()
+        for i, (g, ch, off, cnt, wide) in enumerate(runs):
+            arr[i].group, arr[i].channel, arr[i].offset_words, arr[i].count = int(g), int(ch), int(off), int(cnt)
+            arr[i].flags = wide if isinstance(wide, int) and not isinstance(wide, bool) else (abi.SPARSE_WIDE if wide else 0)
+        self.ctx.call("jxl_vardct_commit_sparse", arr, len(runs))
+
+    def sparseRejected(self):
+        """entries the device refused since begin_frame (jxl_vardct_sparse_rejected); waits for the stream"""
+        n = C.c_int64()
+        self.ctx.call("jxl_vardct_sparse_rejected", C.byref(n))
+        return n.value
 
     def run(self):
         """enqueue all stages (asynchronous)"""
