@@ -412,6 +412,55 @@ jxl_status jxl_stage_ycbcr(jxl_ctx* ctx, float* const planes[3], int64_t n);
  * max_value = 0 keeps float output in out_f, else writes clamped ints to out_i. */
 jxl_status jxl_stage_transfer(jxl_ctx* ctx, const float* in, int64_t n, int32_t transfer,
                               int32_t max_value, float* out_f, int32_t* out_i);
+/* ---- colour management: JXLImage.transform (J/JXLImage.java:185-286) as one device pass ----
+ * Transfer functions of TransferFunction.java / ColorManagement.getTransferFunction (ColorManagement.java:149-170), both
+ * directions. (The JXL_TRANSFER_* values above keep their meaning for jxl_vardct_params.transfer and jxl_stage_transfer.) */
+#define JXL_TF_LINEAR 0 /* TransferFunction.java:7-27 */
+#define JXL_TF_SRGB   1 /* :29-61, toLinearF / fromLinearF in their float forms */
+#define JXL_TF_BT709  2 /* :63-79 */
+#define JXL_TF_PQ     3 /* :81-93. toLinear is NaN for inputs below ~7.3e-7, zero included (a negative base), as in the reference */
+#define JXL_TF_GAMMA  4 /* GammaTransferFunction.java: pow(f, 1e7 / g) to linear, pow(f, 1e-7 * g) from linear; TF_DCI is g = 3846154 (:95) */
+#define JXL_TF_HLG    5 /* JXL_ERR_UNSUPPORTED: the reference throws too (ColorManagement.java:161-162) */
+/* One call = the stages below in this order, each one switchable; the samples of a pixel meet only in the matrix.
+ *   1. cast          int32 samples -> float, v * (1.0f / in_max[c])     ImageBuffer.castToFloatWithMax (ImageBuffer.java:94-97, 112-127)
+ *   2. toLinearF     of tf_in                                           JXLImage.linearize (:260-267)
+ *   3. grey -> RGB   n_planes == 1 with use_matrix                      JXLImage.fillColor (:143-164)
+ *   4. matrix        (m0 a + m1 b) + m2 c in float                      JXLImage.toneMapLinear (:114-141), MathHelper.java:242-252
+ *   5. scale         f * scale                                          JXLImage.transfer, peak detection (:278-280)
+ *   6. fromLinearF   of tf_out                                          JXLImage.transferInPlace (:244-258, :283)
+ *   7. quantise      max_value > 0: ImageBuffer.castToInt0              ImageBuffer.java:129-145
+ * The scale follows the matrix because transform() calls toneMapLinear before transfer(), where the peak is taken and applied.
+ * Tolerance: the cast, the matrix, the scale, the linear segments and the quantisation of a given float are the reference's
+ * float operations, bit for bit. Every curve that goes through a double pow is within 1 float ulp of the reference's
+ * (float)Math.pow form (NaN, zero and infinite results equal), like JXL_TRANSFER_PQ_EXACT above. LINEAR / SRGB / PQ as tf_out
+ * are jxl_stage_transfer's functions and, with max_value 255 or 65535, its exact threshold tables. */
+typedef struct jxl_color_params {
+    int32_t n_planes;      /* 1 or 3 input planes */
+    int32_t in_is_int;     /* int32 samples, cast with in_max[c]; else float samples */
+    int32_t in_max[3];     /* >= 1 where used */
+    int32_t tf_in;         /* JXL_TF_* of the samples */
+    int32_t gamma_in;      /* JXL_TF_GAMMA: the header's integer, 1 .. 2^24-1 */
+    int32_t use_scale;
+    float scale;
+    int32_t use_matrix;    /* three planes out; a one-plane input is replicated first */
+    float matrix[9];       /* row-major */
+    int32_t tf_out;
+    int32_t gamma_out;
+    int32_t max_value;     /* 0: float planes out, else int32 planes clamped to 0..max_value */
+} jxl_color_params;
+/* n samples per plane. in: n_planes host planes. out: three host planes when n_planes == 3 or use_matrix, else one (out may
+ * be the input planes). JXL_ERR_INVALID_ARGUMENT (nothing written): unknown selector, gamma out of range, n_planes not 1 or
+ * 3, n < 0, a missing plane -- a grey output asked of a matrix included --, in_max < 1, max_value < 0. n == 0 does nothing. */
+jxl_status jxl_stage_color_convert(jxl_ctx* ctx, const void* const in[3], int64_t n, const jxl_color_params* p,
+                                   void* const out[3]);
+/* JXLImage.determinePeak (:214-223) of the image that stages 1-4 of `p` make of in (h x w samples per plane; scale, tf_out
+ * and max_value are not looked at): of its plane 1, or plane 0 when it has one plane. Float samples: per row
+ * MathHelper.max(float...) (MathHelper.java:190-195: the row MINIMUM; a NaN first sample sticks, later NaNs are passed over,
+ * of equal zeros the first stays), then the maximum over rows in Float.compareTo order (NaN greatest, -0 < +0); bit for bit
+ * given the samples, any NaN for NaN. int32 samples that are linear and go through no matrix: the maximum sample divided by
+ * (float)in_max (:219). w <= 2^30. */
+jxl_status jxl_stage_color_peak(jxl_ctx* ctx, const void* const in[3], int32_t h, int32_t w, const jxl_color_params* p,
+                                float* peak);
 /* ModularChannel.inverseHorizontalSqueeze / inverseVerticalSqueeze
  * (ModularChannel.java:361-413). out is (h) x (aw+rw) resp. (ah+rh) x (w). */
 jxl_status jxl_stage_inv_hsqueeze(jxl_ctx* ctx, const int32_t* avg, int32_t aw, const int32_t* res, int32_t rw,

@@ -119,6 +119,10 @@ public final class NativeBackend implements AutoCloseable {
         float intensityTarget);                                    // jxl_stage_xyb (OpsinInverseMatrix.invertXYB)
     public native void stageYcbcr(ByteBuffer p0, ByteBuffer p1, ByteBuffer p2, long n);               // jxl_stage_ycbcr
     public native void stageTransfer(ByteBuffer in, long n, int transfer, int maxValue, ByteBuffer outF, ByteBuffer outI); // jxl_stage_transfer
+    /** params: struct jxl_color_params packed by the caller (4-byte fields, C layout); i1, i2 / o1, o2 null for one plane. */
+    public native void stageColorConvert(ByteBuffer i0, ByteBuffer i1, ByteBuffer i2, long n, ByteBuffer params, ByteBuffer o0, ByteBuffer o1,
+        ByteBuffer o2);                                            // jxl_stage_color_convert (JXLImage.transform)
+    public native float stageColorPeak(ByteBuffer i0, ByteBuffer i1, ByteBuffer i2, int h, int w, ByteBuffer params); // jxl_stage_color_peak
     public native void stageInvHSqueeze(ByteBuffer avg, int aw, ByteBuffer res, int rw, int h, ByteBuffer out); // jxl_stage_inv_hsqueeze
     public native void stageInvVSqueeze(ByteBuffer avg, int ah, ByteBuffer res, int rh, int w, ByteBuffer out); // jxl_stage_inv_vsqueeze
     public native void stageRct(ByteBuffer v0, ByteBuffer v1, ByteBuffer v2, long n, int rctType);    // jxl_stage_rct

@@ -696,6 +696,47 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageTransf
     CHECK(jxl_stage_transfer(c, (const float*)ADDR(in), n, transfer, maxValue, (float*)ADDR(outF), (int32_t*)ADDR(outI)));
 }
 
+/* JXLImage.transform's sample chain (JXLImage.java:185-286): params = struct jxl_color_params in a direct buffer; i1, i2 are null for
+ * one input plane, o1, o2 for one output plane. A thin pass-through: nothing on the Java side calls it yet. */
+static int color_params(JNIEnv* e, jobject params, jxl_color_params* p) {
+    const void* src = params ? (*e)->GetDirectBufferAddress(e, params) : NULL;
+    if (!src || (*e)->GetDirectBufferCapacity(e, params) < (jlong)sizeof *p) {
+        bad_arg(e, "jxlatte_amd: a direct buffer holding jxl_color_params is needed");
+        return 0;
+    }
+    memcpy(p, src, sizeof *p);
+    return 1;
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageColorConvert(JNIEnv* e, jobject self, jobject i0, jobject i1, jobject i2,
+        jlong n, jobject params, jobject o0, jobject o1, jobject o2) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_color_params p;
+    if (!color_params(e, params, &p)) return;
+    NEED(i0, 4 * n); NEED_OPT(i1, 4 * n); NEED_OPT(i2, 4 * n);
+    NEED(o0, 4 * n); NEED_OPT(o1, 4 * n); NEED_OPT(o2, 4 * n);
+    const void* in[3] = {ADDR(i0), ADDR(i1), ADDR(i2)};
+    void* out[3] = {ADDR(o0), ADDR(o1), ADDR(o2)};
+    CHECK(jxl_stage_color_convert(c, in, n, &p, out));
+}
+
+/* JXLImage.determinePeak (:214-223) */
+JNIEXPORT jfloat JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageColorPeak(JNIEnv* e, jobject self, jobject i0, jobject i1, jobject i2,
+        jint h, jint w, jobject params) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_color_params p;
+    float peak = 0.0f;
+    if (!color_params(e, params, &p)) return 0.0f;
+    if (!has_room(e, i0, 4 * area(h, w)) || (i1 && !has_room(e, i1, 4 * area(h, w))) || (i2 && !has_room(e, i2, 4 * area(h, w)))) {
+        bad_arg(e, "jxlatte_amd: direct buffer of a colour plane missing or too small");
+        return 0.0f;
+    }
+    const void* in[3] = {ADDR(i0), ADDR(i1), ADDR(i2)};
+    jxl_status st = jxl_stage_color_peak(c, in, h, w, &p, &peak);
+    if (st != JXL_OK) { rethrow(e, c, st); return 0.0f; }
+    return peak;
+}
+
 JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageInvHSqueeze(JNIEnv* e, jobject self, jobject avg, jint aw, jobject res,
         jint rw, jint h, jobject out) {
     jxl_ctx* c = ctx_of(e, self);

@@ -16,6 +16,11 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--sparse-coeffs", action="store_true",
                     help="feed the HF coefficients as lists of non-zero entries (jxl_vardct_put_group_sparse); same pixels")
+    ap.add_argument("--png-peak-detect", choices=["auto", "on", "off"], default="auto",
+                    help="scale a PQ image by its peak when it is written as SDR: when the peak is below 1 / always / never")
+    ap.add_argument("--device-color", action="store_true",
+                    help="colour management of the PNG (linearise, primaries, peak, output transfer) as one device pass "
+                         "(jxl_stage_color_convert); float samples within 1 ulp of the host path")
     a = ap.parse_args(argv)
     from . import frontend
     if a.info:
@@ -24,7 +29,8 @@ def main(argv=None):
         print("Image: %s\n    Size: %dx%d\n    Bit Depth: %d\n    Extra Channels: %d\n    XYB Encoded: %s\n    Orientation: %d" % (
             a.input, im.width, im.height, im.bits_per_sample, im.num_extra, bool(im.xyb_encoded), im.orientation))
         return 0
-    from .decoder import DeviceBackend, JXLDecoder, PNGWriter
+    from .decoder import PEAK_DETECT_AUTO, PEAK_DETECT_OFF, PEAK_DETECT_ON, DeviceBackend, JXLDecoder, PNGWriter
+    PEAK_DETECT = {"auto": PEAK_DETECT_AUTO, "on": PEAK_DETECT_ON, "off": PEAK_DETECT_OFF}
     t0 = time.time()
     backend = DeviceBackend(a.device)
     dec = JXLDecoder(a.input, backend=backend, sparse_coeffs=a.sparse_coeffs)
@@ -39,7 +45,8 @@ def main(argv=None):
     if a.output:
         hdr = image.isHDR() if a.png_hdr == "auto" else a.png_hdr == "yes"
         with open(a.output, "wb") as f:
-            PNGWriter(image, bitDepth=16 if hdr else a.png_depth, hdr=hdr).write(f)
+            PNGWriter(image, bitDepth=16 if hdr else a.png_depth, hdr=hdr, peakDetect=PEAK_DETECT[a.png_peak_detect],
+                      deviceColor=a.device_color).write(f)
     backend.close()
     return 0
 

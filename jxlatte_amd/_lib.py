@@ -111,6 +111,8 @@ SIGNATURES = {
     "jxl_stage_xyb": (i32, [vp, pf3, i64, pf, pf, pf, f32]),
     "jxl_stage_ycbcr": (i32, [vp, pf3, i64]),
     "jxl_stage_transfer": (i32, [vp, pf, i64, i32, i32, pf, pi]),
+    "jxl_stage_color_convert": (i32, [vp, pv3, i64, C.POINTER(abi.ColorParams), pv3]),
+    "jxl_stage_color_peak": (i32, [vp, pv3, i32, i32, C.POINTER(abi.ColorParams), pf]),
     "jxl_stage_inv_hsqueeze": (i32, [vp, pi, i32, pi, i32, i32, pi]),
     "jxl_stage_inv_vsqueeze": (i32, [vp, pi, i32, pi, i32, i32, pi]),
     "jxl_stage_rct": (i32, [vp, pi3, i64, i32]),

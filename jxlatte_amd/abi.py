@@ -16,6 +16,8 @@ JXL_ERR_OOM = -5
 JXL_ERR_STATE = -6
 
 TRANSFER_NONE, TRANSFER_PQ, TRANSFER_SRGB, TRANSFER_PQ_EXACT = 0, 1, 2, 3
+# jxl_color_params.tf_in / tf_out (jxl_stage_color_convert / jxl_stage_color_peak)
+TF_LINEAR, TF_SRGB, TF_BT709, TF_PQ, TF_GAMMA, TF_HLG = 0, 1, 2, 3, 4, 5
 OUT_F32, OUT_U16, OUT_U8, OUT_RGB8, OUT_RGB16 = 0, 1, 2, 3, 4
 BLEND_REPLACE, BLEND_ADD, BLEND_BLEND, BLEND_MULADD, BLEND_MULT = 0, 1, 2, 3, 4
 BLEND_FLAG_IS_ALPHA, BLEND_FLAG_HAS_EXTRA, BLEND_FLAG_CLAMP, BLEND_FLAG_PREMULT = 1, 2, 4, 8
@@ -146,6 +148,13 @@ class PackParams(C.Structure):
     _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("n_color", C.c_int32), ("has_alpha", C.c_int32),
                 ("premultiplied", C.c_int32), ("bit_depth", C.c_int32), ("big_endian", C.c_int32),
                 ("is_int", C.c_int32 * 4), ("tagged_depth", C.c_int32 * 4)]
+
+
+class ColorParams(C.Structure):
+    """struct jxl_color_params"""
+    _fields_ = [("n_planes", C.c_int32), ("in_is_int", C.c_int32), ("in_max", C.c_int32 * 3), ("tf_in", C.c_int32),
+                ("gamma_in", C.c_int32), ("use_scale", C.c_int32), ("scale", C.c_float), ("use_matrix", C.c_int32),
+                ("matrix", f9), ("tf_out", C.c_int32), ("gamma_out", C.c_int32), ("max_value", C.c_int32)]
 
 
 class SqueezeParam(C.Structure):

@@ -2976,6 +2976,161 @@ jxl_status jxl_stage_transfer(jxl_ctx* c, const float* in, int64_t n, int32_t tr
     return JXL_OK;
 }
 
+// ---- colour management: JXLImage.transform as one pass (k_color.hip) ----
+namespace {
+// 0: p is no integer, 1: an even integer, 2: an odd one (Math.pow treats a negative base by this)
+int pow_kind(double p) {
+    if (std::floor(p) != p) return 0;
+    return std::fmod(p, 2.0) == 0.0 ? 1 : 2;
+}
+
+// the checks both entries share, and jxl_color_params as the kernels take it (pointers and tables are filled in by the caller)
+jxl_status color_args(jxl_ctx* c, const jxl_color_params* p, const void* const in[3], ColorArgs* a) {
+    if (!p || !in) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color: null argument");
+    if (p->n_planes != 1 && p->n_planes != 3) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color: n_planes must be 1 or 3");
+    for (int i = 0; i < p->n_planes; i++)
+        if (!in[i]) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color: input plane %d missing", i);
+    for (int tf : {p->tf_in, p->tf_out}) {
+        if (tf == JXL_TF_HLG) return fail(c, JXL_ERR_UNSUPPORTED, "Not yet implemented");  // ColorManagement.java:161-162
+        if (tf < JXL_TF_LINEAR || tf > JXL_TF_HLG) return fail(c, JXL_ERR_INVALID_ARGUMENT, "Invalid transfer function");  // :169
+    }
+    if ((p->tf_in == JXL_TF_GAMMA && (p->gamma_in < 1 || p->gamma_in >= (1 << 24))) ||
+        (p->tf_out == JXL_TF_GAMMA && (p->gamma_out < 1 || p->gamma_out >= (1 << 24))))
+        return fail(c, JXL_ERR_INVALID_ARGUMENT, "Invalid transfer function");  // :165-169
+    if (p->max_value < 0) return fail(c, JXL_ERR_INVALID_ARGUMENT, "invalid Max Value");
+    memset(a, 0, sizeof *a);
+    a->n_planes = p->n_planes;
+    a->in_is_int = p->in_is_int ? 1 : 0;
+    for (int i = 0; i < p->n_planes && a->in_is_int; i++) {
+        if (p->in_max[i] < 1) return fail(c, JXL_ERR_INVALID_ARGUMENT, "invalid Max Value");  // ImageBuffer.java:115-116
+        a->in_scale[i] = 1.0f / (float)p->in_max[i];
+    }
+    a->tf_in = p->tf_in;
+    a->tf_out = p->tf_out;
+    if (p->tf_in == JXL_TF_GAMMA) a->p_in = 1e7 / p->gamma_in, a->kind_in = pow_kind(a->p_in);     // GammaTransferFunction.java:8-11
+    if (p->tf_out == JXL_TF_GAMMA) a->p_out = 1e-7 * p->gamma_out, a->kind_out = pow_kind(a->p_out);
+    a->use_scale = p->use_scale ? 1 : 0;
+    a->scale = p->scale;
+    a->use_matrix = p->use_matrix ? 1 : 0;
+    memcpy(a->m, p->matrix, sizeof a->m);
+    a->max_value = p->max_value;
+    return JXL_OK;
+}
+
+// the inverse of k_color_peak's order-preserving key of a float (Float.compareTo order)
+float color_peak_value(uint32_t key) {
+    if (key == 0xFFFFFFFFu) return std::numeric_limits<float>::quiet_NaN();
+    const uint32_t b = (key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key;
+    float f;
+    memcpy(&f, &b, 4);
+    return f;
+}
+}  // namespace
+
+jxl_status jxl_stage_color_convert(jxl_ctx* c, const void* const in[3], int64_t n, const jxl_color_params* p, void* const out[3]) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    ColorArgs a;
+    if ((st = color_args(c, p, in, &a))) return st;
+    const int n_out = (p->n_planes == 3 || p->use_matrix) ? 3 : 1;
+    if (!out || n < 0) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color: bad arguments");
+    for (int i = 0; i < n_out; i++)  // the matrix has three planes to write: there is no grey output of it
+        if (!out[i]) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color: output plane %d missing", i);
+    if (n == 0) return JXL_OK;
+    Tmp t;
+    for (int i = 0; i < p->n_planes; i++)
+        if (!(a.in[i] = t.up((const int32_t*)in[i], (size_t)n))) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    for (int i = 0; i < n_out; i++)
+        if (!(a.out[i] = t.up<int32_t>(nullptr, (size_t)n))) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    a.n = n;
+    // what jxl_stage_transfer hands its kernel for the same target
+    const int tr = p->tf_out == JXL_TF_PQ ? JXL_TRANSFER_PQ : p->tf_out == JXL_TF_SRGB ? JXL_TRANSFER_SRGB : JXL_TRANSFER_NONE;
+    a.pq_tab = c->pq_tab.as<float>();
+    a.srgb8_tab = c->srgb8_tab.as<float>();
+    a.pq16_thr = pq16_thresholds_for(c, tr, p->max_value);
+    a.srgb16_tab = srgb16_table_for(c, tr, p->max_value);
+    launch_color_convert(a, c->stream);
+    if ((st = finish(c))) return st;
+    for (int i = 0; i < n_out; i++) HIP_TRY(c, hipMemcpy(out[i], a.out[i], 4 * (size_t)n, hipMemcpyDeviceToHost));
+    return JXL_OK;
+}
+
+jxl_status jxl_stage_color_peak(jxl_ctx* c, const void* const in[3], int32_t h, int32_t w, const jxl_color_params* p, float* peak) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    ColorArgs a;
+    if ((st = color_args(c, p, in, &a))) return st;
+    if (!peak || h < 1 || w < 1 || w > (1 << 30)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color peak: bad arguments");
+    const size_t n = (size_t)h * w;
+    const int pc = p->n_planes == 3 ? 1 : 0;  // determinePeak's plane (JXLImage.java:217)
+    Tmp t;
+    for (int i = 0; i < p->n_planes; i++) {
+        if (!a.use_matrix && i != pc) continue;  // without a matrix only that plane is read
+        if (!(a.in[i] = t.up((const int32_t*)in[i], n))) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    }
+    uint32_t* dkey = t.up<uint32_t>(nullptr, 1);
+    if (!dkey) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    HIP_TRY(c, hipMemsetAsync(dkey, 0, 4, c->stream));
+    a.n = (int64_t)n;
+    launch_color_peak(a, h, w, dkey, c->stream);
+    if ((st = finish(c))) return st;
+    uint32_t key = 0;
+    HIP_TRY(c, hipMemcpy(&key, dkey, 4, hipMemcpyDeviceToHost));
+    if (a.in_is_int && a.tf_in == JXL_TF_LINEAR && !a.use_matrix)
+        *peak = (float)(int32_t)(key ^ 0x80000000u) / (float)p->in_max[pc];  // :219
+    else
+        *peak = color_peak_value(key);
+    return JXL_OK;
+}
+
+// tools/color_bench.py: the two colour kernels alone on resident planes, by stream events: mean milliseconds per launch over
+// `reps` launches after one warm-up launch of each (peak_ms 0 when `with_peak` is 0)
+extern "C" jxl_status jxl_debug_color_kernel_ms(jxl_ctx* c, const void* const in[3], int32_t h, int32_t w, const jxl_color_params* p,
+                                                int32_t with_peak, int32_t reps, float* convert_ms, float* peak_ms) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    ColorArgs a;
+    if ((st = color_args(c, p, in, &a))) return st;
+    if (h < 1 || w < 1 || w > (1 << 30) || reps < 1 || !convert_ms || !peak_ms) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color bench: bad arguments");
+    const size_t n = (size_t)h * w;
+    Tmp t;
+    for (int i = 0; i < p->n_planes; i++)
+        if (!(a.in[i] = t.up((const int32_t*)in[i], n))) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    for (int i = 0; i < 3; i++)
+        if (!(a.out[i] = t.up<int32_t>(nullptr, n))) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    uint32_t* dkey = t.up<uint32_t>(nullptr, 1);
+    if (!dkey) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    a.n = (int64_t)n;
+    const int tr = p->tf_out == JXL_TF_PQ ? JXL_TRANSFER_PQ : p->tf_out == JXL_TF_SRGB ? JXL_TRANSFER_SRGB : JXL_TRANSFER_NONE;
+    a.pq_tab = c->pq_tab.as<float>();
+    a.srgb8_tab = c->srgb8_tab.as<float>();
+    a.pq16_thr = pq16_thresholds_for(c, tr, p->max_value);
+    a.srgb16_tab = srgb16_table_for(c, tr, p->max_value);
+    hipEvent_t ev[2];
+    HIP_TRY(c, hipEventCreate(&ev[0]));
+    HIP_TRY(c, hipEventCreate(&ev[1]));
+    *peak_ms = 0.0f;
+    for (int which = 0; which < (with_peak ? 2 : 1); which++) {
+        for (int r = -1; r < reps; r++) {
+            if (r == 0) (void)hipEventRecord(ev[0], c->stream);
+            if (which == 0) {
+                launch_color_convert(a, c->stream);
+            } else {
+                (void)hipMemsetAsync(dkey, 0, 4, c->stream);
+                launch_color_peak(a, h, w, dkey, c->stream);
+            }
+        }
+        (void)hipEventRecord(ev[1], c->stream);
+        if ((st = finish(c))) break;
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+        *(which == 0 ? convert_ms : peak_ms) = ms / (float)reps;
+    }
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    return st;
+}
+
 jxl_status jxl_stage_inv_hsqueeze(jxl_ctx* c, const int32_t* avg, int32_t aw, const int32_t* res, int32_t rw, int32_t h, int32_t* out) {
     jxl_status st = bind(c);
     if (st) return st;

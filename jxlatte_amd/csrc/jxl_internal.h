@@ -200,6 +200,31 @@ void launch_ycbcr(float* const planes[3], int64_t n, hipStream_t s);
 void launch_transfer(const float* in, int64_t n, int transfer, int max_value, void* out, int out_elem, hipStream_t s,
                      int out_pitch = 1, int out_off = 0, const float* pq_tab = nullptr, const float* srgb8_tab = nullptr,
                      const float* pq16_thr = nullptr, const float* srgb16_tab = nullptr);
+// colour management in one pass (k_color.hip): jxl_color_params as the kernels see it. All pointers are device pointers.
+struct ColorArgs {
+    const void* in[3];  // n_planes planes of float or int32 samples
+    void* out[3];       // float, or int32 when max_value > 0; three planes when n_planes == 3 or use_matrix, else one
+    int64_t n;
+    int n_planes, in_is_int;
+    float in_scale[3];  // 1.0f / in_max[c] (ImageBuffer.castToFloat0)
+    int tf_in, kind_in;  // JXL_TF_*; kind_*: the exponent of a GAMMA curve is 0 no integer, 1 an even, 2 an odd integer
+    double p_in;         // GAMMA: 1e7 / gamma_in
+    int use_scale;
+    float scale;
+    int use_matrix;
+    float m[9];
+    int tf_out, kind_out;
+    double p_out;  // GAMMA: 1e-7 * gamma_out
+    int max_value;
+    const float* pq_tab;      // the tables jxl_stage_transfer would use for (tf_out, max_value), or null
+    const float* srgb8_tab;
+    const float* pq16_thr;
+    const float* srgb16_tab;
+};
+void launch_color_convert(const ColorArgs& a, hipStream_t s);
+// determinePeak over h rows of w samples (w <= 2^30): *result, zeroed by the caller, receives an order-preserving uint32 key of
+// the peak (host.hip: color_peak_value)
+void launch_color_peak(const ColorArgs& a, int h, int w, uint32_t* result, hipStream_t s);
 // PQ as a table of quadratic segments (jxl_fastpow.h): kPqTableFloats floats = float4 {a0 hi, a0 lo, a1, a2} per segment
 constexpr int kPqTableFloats = (129 - 87) * 128 * 4;
 void build_pq_table(float* out /* [kPqTableFloats] */);

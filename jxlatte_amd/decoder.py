@@ -155,6 +155,19 @@ def _to_linear(buf, tf):
     raise ValueError("Invalid transfer function")
 
 
+def _tf_selector(tf):
+    """ColorManagement.getTransferFunction (:149-170) as the device library's (JXL_TF_*, gamma)"""
+    named = {TF_LINEAR: abi.TF_LINEAR, TF_SRGB: abi.TF_SRGB, TF_BT709: abi.TF_BT709, TF_PQ: abi.TF_PQ}
+    if tf in named:
+        return named[tf], 0
+    if tf == TF_HLG:
+        raise UnsupportedOperationException("Not yet implemented")  # ColorManagement.java:161-162
+    gamma = 3846154 if tf == TF_DCI else tf
+    if 0 < gamma < (1 << 24):
+        return abi.TF_GAMMA, gamma  # GammaTransferFunction
+    raise ValueError("Invalid transfer function")
+
+
 # ---- splines (J/frame/features/spline/Spline.java): host-side feature, as in the reference ------------------------------
 _SQRT_H = F(math.sqrt(0.5))
 _SQRT_F = F(math.sqrt(0.125))
@@ -407,6 +420,13 @@ class DeviceBackend:
         code = {TF_PQ: abi.TRANSFER_PQ, TF_SRGB: abi.TRANSFER_SRGB}[tf]
         return self.host.transfer(self.ctx, plane, code, 0)
 
+    def color_convert(self, planes, **params):
+        """JXLImage.transform's sample chain as one pass (host.colorConvert; the keywords are host.colorParams')"""
+        return self.host.colorConvert(self.ctx, planes, **params)
+
+    def color_peak(self, planes, **params):
+        return self.host.determinePeak(self.ctx, planes, **params)
+
     def pack(self, planes, bit_depth, alpha, premultiplied, tagged, big_endian):
         return self.host.packSamples(self.ctx, planes, bit_depth, alpha=alpha, premultiplied=premultiplied, taggedDepth=tagged,
                                      bigEndian=big_endian)
@@ -542,8 +562,59 @@ class JXLImage:
         im.primariesXY, im.whiteXY = np.array(primaries, F), np.array(whitePoint, F)
         return im
 
-    def transform(self, primaries, whitePoint, transfer, peakDetect=PEAK_DETECT_AUTO):
-        """JXLImage.transform (:186-193)"""
+    def _transform_device(self, primaries, whitePoint, transfer, peakDetect):
+        """transform() with the samples on the device: the decisions of transform / linearize / fillColor / toneMapLinear /
+        transfer (JXLImage.java:114-141, 185-193, 260-286) are taken here, the sample work is at most one color_peak and one
+        color_convert call of the backend. Same metadata as the host path; float samples within the 1 ulp of the double-pow
+        curves (include/jxlatte_amd.h)."""
+        tone_map = not (_prim_matches(primaries, self.primariesXY) and _xy_matches(whitePoint, self.whiteXY))
+        if not tone_map and transfer == self.transfer_:
+            return self
+        tf_in, gamma_in = _tf_selector(self.transfer_)
+        tf_out, gamma_out = _tf_selector(transfer)
+        colors = self.getColorChannelCount()
+        depth_max = [(1 << self.bitDepths[c]) - 1 for c in range(colors)]
+        planes = [self.buffer[c] for c in range(colors)]
+        if len({p.dtype for p in planes}) != 1:  # mixed int / float colour planes: the first cast, done here
+            cast_max = depth_max if (self.transfer_ != TF_LINEAR or tone_map) else None
+            planes = [self._as_float(c) if cast_max else self._as_float(c, with_depth=False) for c in range(colors)]
+        front = dict(tfIn=tf_in, gammaIn=gamma_in)
+        if tone_map:
+            front["matrix"] = get_conversion_matrix(primaries, whitePoint, self.primariesXY, self.whiteXY)
+        if tone_map and transfer == TF_LINEAR:  # transfer() of the tone-mapped, linear image returns it as it is (:270-271)
+            out = self.backend.color_convert(planes, inMax=depth_max, **front)
+        else:
+            scale = None
+            if self.taggedTransfer == TF_PQ and peakDetect in (PEAK_DETECT_AUTO, PEAK_DETECT_ON):
+                to_pq = transfer in (TF_PQ, TF_LINEAR)
+                from_pq = tone_map or self.transfer_ in (TF_PQ, TF_LINEAR)  # the tone-mapped image is linear
+                if from_pq and not to_pq:
+                    s = F(F(1) / self.backend.color_peak(planes, inMax=depth_max, **front))
+                    if s > 1.0 or peakDetect == PEAK_DETECT_ON:
+                        scale = s
+            # the first stage that touches the samples casts them: linearize, toneMapLinear and the scale with the depth's
+            # maximum, transferInPlace with the depth itself (:248)
+            first_max = depth_max if (self.transfer_ != TF_LINEAR or tone_map or scale is not None) else [self.bitDepths[c] for c in range(colors)]
+            out = self.backend.color_convert(planes, inMax=first_max, scale=scale, tfOut=tf_out, gammaOut=gamma_out, **front)
+        im = self._clone()
+        if tone_map:
+            if colors == 1:  # fillColor
+                im.buffer = list(out) + list(self.buffer[1:])
+                im.bitDepths = [self.bitDepths[0]] * 2 + list(self.bitDepths)
+                im.colorEncoding = CE_RGB
+            else:
+                im.buffer[:3] = out
+            im.primariesXY, im.whiteXY = np.array(primaries, F), np.array(whitePoint, F)
+        else:
+            im.buffer[:colors] = out
+        im.transfer_ = transfer
+        return im
+
+    def transform(self, primaries, whitePoint, transfer, peakDetect=PEAK_DETECT_AUTO, device=False):
+        """JXLImage.transform (:186-193). device: the whole chain as one pass of a backend that has color_convert -- which also
+        serves the BT.709, DCI and gamma targets; else on the host, one plane and one stage at a time"""
+        if device and hasattr(self.backend, "color_convert"):
+            return self._transform_device(primaries, whitePoint, transfer, peakDetect)
         if _prim_matches(primaries, self.primariesXY) and _xy_matches(whitePoint, self.whiteXY):
             return self.transfer(transfer, peakDetect)
         return self.linearize().fillColor().toneMapLinear(primaries, whitePoint).transfer(transfer, peakDetect)
@@ -1033,7 +1104,8 @@ class JXLDecoder:
 
 # ---- PNGWriter (J/io/PNGWriter.java) ---------------------------------------------------------------------------
 class PNGWriter:
-    def __init__(self, image, bitDepth=-1, hdr=False, peakDetect=PEAK_DETECT_AUTO, deflateLevel=6):
+    def __init__(self, image, bitDepth=-1, hdr=False, peakDetect=PEAK_DETECT_AUTO, deflateLevel=6, deviceColor=False):
+        """deviceColor: JXLImage.transform(..., device=True)"""
         if bitDepth <= 0:
             bitDepth = 16 if (hdr or image.info.bits_per_sample > 8) else 8
         if bitDepth not in (8, 16):
@@ -1044,7 +1116,7 @@ class PNGWriter:
         tf = TF_PQ if hdr else TF_SRGB
         self.has_icc = image.has_icc
         if not image.has_icc:
-            image = image.transform(primaries, WP_D65, tf, peakDetect)
+            image = image.transform(primaries, WP_D65, tf, peakDetect, device=deviceColor)
         self.bitDepth = bitDepth
         self.width, self.height = image.getWidth(), image.getHeight()
         self.alphaIndex = image.getAlphaIndex()

@@ -152,6 +152,55 @@ def transfer(ctx, x, tf, maxValue=0):
     return out
 
 
+def colorParams(planes, tfIn=abi.TF_LINEAR, gammaIn=0, inMax=None, scale=None, matrix=None, tfOut=abi.TF_LINEAR, gammaOut=0,
+                maxValue=0):
+    """jxl_color_params for a list of 1 or 3 equally shaped planes, all int32 (cast with inMax[c]) or all float32"""
+    if len(planes) not in (1, 3) or len({(p.shape, p.dtype) for p in planes}) != 1 or planes[0].dtype not in (np.int32, np.float32):
+        raise ValueError("expected 1 or 3 int32 or float32 planes of one shape")
+    p = abi.ColorParams()
+    p.n_planes = len(planes)
+    p.in_is_int = 1 if planes[0].dtype == np.int32 else 0
+    for c, v in enumerate(inMax if inMax is not None else ()):
+        p.in_max[c] = int(v)
+    p.tf_in, p.gamma_in, p.tf_out, p.gamma_out, p.max_value = int(tfIn), int(gammaIn), int(tfOut), int(gammaOut), int(maxValue)
+    if scale is not None:
+        p.use_scale, p.scale = 1, float(scale)
+    if matrix is not None:
+        p.use_matrix = 1
+        p.matrix = abi.f9(*[float(v) for v in np.asarray(matrix, np.float32).reshape(-1)])
+    return p
+
+
+def _pv(planes):
+    arr = (C.c_void_p * 3)()
+    for c, a in enumerate(planes):
+        arr[c] = a.ctypes.data
+    return arr
+
+
+def colorConvert(ctx, planes, **params):
+    """JXLImage.transform's sample chain in one device pass (jxl_stage_color_convert): cast, toLinearF, grey -> RGB, matrix,
+    peak scale, fromLinearF, castToInt0, each one optional (colorParams). Returns the list of output planes: three when a
+    matrix is given or three planes come in, else one; int32 when maxValue > 0, else float32."""
+    planes = [np.ascontiguousarray(a) for a in planes]
+    p = colorParams(planes, **params)
+    n_out = 3 if (len(planes) == 3 or p.use_matrix) else 1
+    out = [np.empty(planes[0].shape, np.int32 if p.max_value > 0 else np.float32) for _ in range(n_out)]
+    ctx.call("jxl_stage_color_convert", _pv(planes), planes[0].size, C.byref(p), _pv(out))
+    return out
+
+
+def determinePeak(ctx, planes, **params):
+    """JXLImage.determinePeak of what the cast, toLinearF and matrix stages of colorParams make of the 2-D planes
+    (jxl_stage_color_peak): the float the reference computes, as numpy.float32"""
+    planes = [np.ascontiguousarray(a) for a in planes]
+    p = colorParams(planes, **params)
+    h, w = planes[0].shape
+    peak = C.c_float(0)
+    ctx.call("jxl_stage_color_peak", _pv(planes), h, w, C.byref(p), C.byref(peak))
+    return np.float32(peak.value)
+
+
 def pack_sparse(planes, wide=False):
     """The sparse wire format of include/jxlatte_amd.h: the non-zero samples of a 2-D integer plane (at most 256 x 256: one
     group of one channel) as a uint32 array of entries in raster order -- narrow: value << 16 | y << 8 | x; wide: the words
