@@ -123,8 +123,12 @@ def test_lf_only_block_is_flat(orc, t):
 
 
 def test_dequant_rule_on_dct8(orc):
-    """one coefficient q at (0,1) of a DCT8 block: pixel = lf + dequant(q) * sqrt2 cos(...) pattern"""
+    """one coefficient q at (0,1) of a DCT8 block: pixel = lf + dequant(q) * sqrt2 cos(...) pattern; the weight table is made
+    asymmetric, so that the transposed index of flip() (HFCoefficients.java:312-314) is told from the plain one"""
     fr = _single_type_frame(0)
+    wts = np.array(fr["weights"], F, copy=True)
+    wts[fr["woffs"][1]:fr["woffs"][1] + 64] *= np.linspace(0.5, 2.0, 64, dtype=F)
+    fr["weights"] = wts
     fr["coeff"][:] = 0
     for g in fr["lfgroups"]:
         for c in range(3):
@@ -143,6 +147,7 @@ def test_dequant_rule_on_dct8(orc):
         qb, qbn = F(p.quant_bias[1]), F(p.quant_bias_numerator)
         quant = (F(q) - qbn / F(q)) if abs(q) >= 2 else (qb if q > 0 else -qb)
         sfc = F(p.scale_factor[1]) / F(2)
+        assert abs(w[1, 0] - w[0, 1]) > 0.1 * abs(w[1, 0])
         co = F(F(quant * sfc) * w[1, 0])  # flip(): weight index transposed for square DCT
         lut = orc.cosine_lut(3)
         exp = np.tile((co * lut[0])[None, :], (8, 1)).astype(F)
