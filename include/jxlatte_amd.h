@@ -343,8 +343,9 @@ jxl_status jxl_vardct_read_output_wait(jxl_ctx* ctx);
  * Frame.upsample, Frame.initializeNoise, computePatches, Frame.renderSplines, Frame.synthesizeNoise,
  * performColorTransforms. The jxl_stage_* entries take and return host planes; these entries run the same kernels on a set
  * of three float planes that STAYS in device memory, so a frame with upsampling / noise costs one transfer in (its
- * coefficients) and one out (its pixels). Patches and splines stay host code (as in the reference): jxl_planes_download /
- * jxl_planes_upload bracket them, only for frames that have them. */
+ * coefficients) and one out (its pixels). Splines may stay on the device too (jxl_planes_splines). Patches stay host code (as
+ * in the reference: copies out of host-side reference frames): jxl_planes_download / jxl_planes_upload bracket them, only for
+ * frames that have them. */
 /* adopt the top-left height x width window (Frame bounds; the restoration filters worked on the padded size) of the last
  * jxl_vardct_run's result as the resident planes. The run must have produced float planes (no transfer / integer output;
  * XYB stage off if the later stages need XYB samples). */
@@ -357,9 +358,52 @@ jxl_status jxl_planes_noise(jxl_ctx* ctx, int32_t group_dim, uint64_t seed0, con
 jxl_status jxl_planes_xyb(jxl_ctx* ctx, const float matrix[9], const float opsin_bias[3], const float cbrt_opsin_bias[3],
                           float intensity_target);
 jxl_status jxl_planes_ycbcr(jxl_ctx* ctx);
+/* ---- splines: Frame.renderSplines (J/frame/Frame.java:739-746) + Spline.renderSpline (J/frame/features/spline/Spline.java:27-200) ----
+ * The splines of one frame as SplinesBundle.java:22-73 decodes them, plus the two LFChannelCorrelation factors computeCoeffs reads
+ * (Spline.java:133-152). coeff: per spline 4 rows of 32 -- coeffX, coeffY, coeffB, coeffSigma. */
+typedef struct jxl_spline_desc {
+    int32_t quant_adjust;        /* SplinesBundle.quantAdjust */
+    int32_t n_splines;           /* SplinesBundle.numSplines */
+    const int32_t* n_control;    /* [n_splines] control points of each spline (>= 1) */
+    const int32_t* control;      /* all splines back to back: (y, x) pairs, Spline.controlPoints */
+    const int32_t* coeff;        /* [n_splines][4][32] */
+    float base_corr_x, base_corr_b; /* LFChannelCorrelation.baseCorrelationX / B */
+} jxl_spline_desc;
+/* One arc sample of Spline.renderSpline's loop (Spline.java:162-199) that draws: everything of it that does not depend on the
+ * pixel. mul[c] = (0.25f * values[c]) * sigma, the per-arc prefix of `0.25f * values[c] * sigma * factor * factor` (:192, left to
+ * right); x0..y1 the clamped box of :174-179, inclusive. 48 bytes. */
+typedef struct jxl_spline_arc {
+    float y, x;                  /* SplineArc.locationY / locationX */
+    float sigma, inv_sigma;      /* :170-171 */
+    float mul[3];
+    int32_t x0, x1, y0, y1;
+    int32_t reserved;            /* 0 */
+} jxl_spline_arc;
+/* Host only, needs no context and no device: the arcs that Frame.renderSplines draws into a height x width frame, in the
+ * reference's order (splines in order, arcs in order). upsampleControlPoints (Spline.java:27-87), computeIntermediarySamples(1.0f)
+ * (:89-123), computeCoeffs (:133-152), fourierICT (:125-131) and the per-arc part of renderSpline (:159-179) in the reference's
+ * float operations, with its quirks kept: every spline is drawn with the coefficients of spline 0 (the constructor never stores
+ * the id, :23-25), MathHelper.max(float...) is the minimum (MathHelper.java:190-195), MathHelper.round is (int)(d + 0.5f) with
+ * Java's saturating cast (:36-38). A spline with arcLength <= 0 has no arcs (:160-161); an arc whose maxDist is not finite or
+ * whose box is empty is left out. Returns the number of arcs (also when it exceeds cap) and writes the first min(count, cap)
+ * of them to out (out may be NULL when cap is 0), or a negative jxl_status: JXL_ERR_INVALID_ARGUMENT (null pointers, negative
+ * counts, a spline without control points, height or width < 1), JXL_ERR_OOM (the table does not fit memory, or has more than
+ * 2^26 arcs). */
+int64_t    jxl_spline_arcs(const jxl_spline_desc* d, int32_t height, int32_t width, jxl_spline_arc* out, int64_t cap);
+/* Frame.renderSplines (Frame.java:739-746) on three host planes of height x width floats, in place. Every pixel receives the
+ * terms of the arcs whose box holds it in the reference's order, one `+=` per arc and channel (Spline.java:180-197), from one
+ * kernel launch; a pixel no arc touches keeps its bits. Tolerance: every operation is the reference's float operation except
+ * (float)Math.exp(double) (MathHelper.java:53, :61), evaluated in double on the device (jxl_fastpow.h: fp_exp): a sample may
+ * differ only where one of its exp results falls on the other side of a float rounding boundary. n_splines == 0
+ * leaves the planes alone. */
+jxl_status jxl_stage_splines(jxl_ctx* ctx, float* const planes[3], int32_t height, int32_t width, const jxl_spline_desc* d);
+/* the same on the resident planes: its place is after jxl_planes_upsample (and the patches), before jxl_planes_noise
+ * (JXLCodestreamDecoder.java:628-637). Asynchronous. JXL_ERR_STATE without resident planes. */
+jxl_status jxl_planes_splines(jxl_ctx* ctx, const jxl_spline_desc* d);
 /* current size of the resident planes */
 jxl_status jxl_planes_shape(const jxl_ctx* ctx, int32_t* height, int32_t* width);
-/* the host hook (patches, splines, saveBeforeCT references) and the way out: dense height x width float planes */
+/* the host hook (patches, saveBeforeCT references; splines unless jxl_planes_splines draws them) and the way out: dense
+ * height x width float planes */
 jxl_status jxl_planes_download(jxl_ctx* ctx, float* const out[3]);
 jxl_status jxl_planes_upload(jxl_ctx* ctx, const float* const in[3], int32_t height, int32_t width);
 

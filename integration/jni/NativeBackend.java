@@ -87,6 +87,10 @@ public final class NativeBackend implements AutoCloseable {
     public native void planesUpload(ByteBuffer p0, ByteBuffer p1, ByteBuffer p2, int height, int width); // jxl_planes_upload
     public native void planesUpsample(int k, float[] weights);     // jxl_planes_upsample   (Frame.upsample)
     public native void planesNoise(int groupDim, long seed0, float[] lut, float baseCorrX, float baseCorrB); // jxl_planes_noise
+    /** Frame.renderSplines (Frame.java:739-746) on the resident planes, after planesUpsample / the patches and before planesNoise.
+     *  The splines as SplinesBundle holds them, flattened: nControl[s] points per spline, control = all (y, x) pairs, coeff =
+     *  per spline coeffX, coeffY, coeffB, coeffSigma (4 x 32); baseCorrX / B from LFChannelCorrelation. */
+    public native void planesSplines(int quantAdjust, int[] nControl, int[] control, int[] coeff, float baseCorrX, float baseCorrB); // jxl_planes_splines
     public native void planesXYB(float[] matrix, float[] opsinBias, float[] cbrtOpsinBias, float intensityTarget); // jxl_planes_xyb
     public native void planesYCbCr();                              // jxl_planes_ycbcr
     public native int[] planesShape();                             // jxl_planes_shape -> {height, width}
@@ -128,6 +132,11 @@ public final class NativeBackend implements AutoCloseable {
     public native void stageRct(ByteBuffer v0, ByteBuffer v1, ByteBuffer v2, long n, int rctType);    // jxl_stage_rct
     public native void stageModularToFloat(ByteBuffer a, ByteBuffer b, long n, float scale, ByteBuffer out); // jxl_stage_modular_to_float
     public native void stageChromaUpsample(ByteBuffer in, int h, int w, int xShift, int yShift, ByteBuffer out); // jxl_stage_chroma_upsample
+    public native void stageSplines(ByteBuffer p0, ByteBuffer p1, ByteBuffer p2, int height, int width, int quantAdjust, int[] nControl,
+                                    int[] control, int[] coeff, float baseCorrX, float baseCorrB);   // jxl_stage_splines
+    /** host only: the arcs Spline.renderSpline draws, 12 ints per arc (jxl_spline_arc; floats as raw bits) */
+    public static native int[] splineArcs(int height, int width, int quantAdjust, int[] nControl, int[] control, int[] coeff,
+                                          float baseCorrX, float baseCorrB);                         // jxl_spline_arcs
     public static native float[] upsamplingWeights(int k, float[] packed);                            // jxl_upsampling_weights
     public native void stageUpsample(ByteBuffer in, int h, int w, int k, float[] weights, ByteBuffer out); // jxl_stage_upsample
     public native void stageNoiseInit(int h, int w, int groupDim, long seed0, int colors, ByteBuffer o0, ByteBuffer o1, ByteBuffer o2); // jxl_stage_noise_init

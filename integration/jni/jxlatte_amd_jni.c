@@ -496,6 +496,102 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesDownl
     CHECK(jxl_planes_download(c, out));
 }
 
+/* ---- splines (include/jxlatte_amd.h: jxl_spline_arcs, jxl_stage_splines, jxl_planes_splines) ----
+ * A frame's splines arrive as SplinesBundle holds them (SplinesBundle.java:22-73), flattened: nControl[s] control points per
+ * spline, control = all (y, x) pairs back to back, coeff = per spline coeffX, coeffY, coeffB, coeffSigma (4 x 32). The three
+ * arrays are copied and checked against each other before the library sees them; *mem is the copy (free it), NULL with an
+ * exception pending on failure. */
+static jint* spline_desc(JNIEnv* e, jint quantAdjust, jintArray nControl, jintArray control, jintArray coeff, jfloat bcx, jfloat bcb,
+                         jxl_spline_desc* d) {
+    if (!nControl || !control || !coeff) {
+        bad_arg(e, "jxlatte_amd: spline arrays missing");
+        return NULL;
+    }
+    const jsize n = (*e)->GetArrayLength(e, nControl), nc = (*e)->GetArrayLength(e, control), nf = (*e)->GetArrayLength(e, coeff);
+    if ((jlong)nf < (jlong)n * 128) {
+        bad_arg(e, "jxlatte_amd: spline coefficient array too short");
+        return NULL;
+    }
+    jint* mem = (jint*)malloc(sizeof(jint) * ((size_t)n + (size_t)nc + (size_t)nf + 1));
+    if (!mem) {
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/OutOfMemoryError"), "jxlatte_amd: spline arrays");
+        return NULL;
+    }
+    (*e)->GetIntArrayRegion(e, nControl, 0, n, mem);
+    (*e)->GetIntArrayRegion(e, control, 0, nc, mem + n);
+    (*e)->GetIntArrayRegion(e, coeff, 0, nf, mem + n + nc);
+    if ((*e)->ExceptionCheck(e)) { /* an ArrayIndexOutOfBoundsException of a region copy is pending: throw nothing on top */
+        free(mem);
+        return NULL;
+    }
+    jlong points = 0;
+    int ok = 1;
+    for (jsize i = 0; ok && i < n; i++) {
+        ok = mem[i] >= 1;
+        points += mem[i];
+    }
+    if (!ok || 2 * points > (jlong)nc) {
+        bad_arg(e, "jxlatte_amd: spline control point counts and array disagree");
+        free(mem);
+        return NULL;
+    }
+    d->quant_adjust = quantAdjust;
+    d->n_splines = n;
+    d->n_control = (const int32_t*)mem;
+    d->control = (const int32_t*)(mem + n);
+    d->coeff = (const int32_t*)(mem + n + nc);
+    d->base_corr_x = bcx;
+    d->base_corr_b = bcb;
+    return mem;
+}
+
+/* Frame.renderSplines (Frame.java:739-746) on the resident planes */
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesSplines(JNIEnv* e, jobject self, jint quantAdjust, jintArray nControl,
+        jintArray control, jintArray coeff, jfloat baseCorrX, jfloat baseCorrB) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_spline_desc d;
+    jint* mem = spline_desc(e, quantAdjust, nControl, control, coeff, baseCorrX, baseCorrB, &d);
+    if (!mem) return;
+    const jxl_status st = jxl_planes_splines(c, &d);
+    free(mem);
+    CHECK(st);
+}
+
+/* ... on three host planes of height x width floats, in place */
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageSplines(JNIEnv* e, jobject self, jobject p0, jobject p1, jobject p2,
+        jint h, jint w, jint quantAdjust, jintArray nControl, jintArray control, jintArray coeff, jfloat baseCorrX, jfloat baseCorrB) {
+    jxl_ctx* c = ctx_of(e, self);
+    float* pl[3] = {(float*)ADDR(p0), (float*)ADDR(p1), (float*)ADDR(p2)};
+    if (h < 1 || w < 1) { bad_arg(e, "jxlatte_amd: plane size"); return; }
+    NEED(p0, 4 * area(h, w)); NEED(p1, 4 * area(h, w)); NEED(p2, 4 * area(h, w));
+    jxl_spline_desc d;
+    jint* mem = spline_desc(e, quantAdjust, nControl, control, coeff, baseCorrX, baseCorrB, &d);
+    if (!mem) return;
+    const jxl_status st = jxl_stage_splines(c, pl, h, w, &d);
+    free(mem);
+    CHECK(st);
+}
+
+/* the arc table (host only): 12 ints per arc, jxl_spline_arc word for word (the floats as Float.floatToRawIntBits) */
+JNIEXPORT jintArray JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_splineArcs(JNIEnv* e, jclass k, jint h, jint w, jint quantAdjust,
+        jintArray nControl, jintArray control, jintArray coeff, jfloat baseCorrX, jfloat baseCorrB) {
+    (void)k;
+    jxl_spline_desc d;
+    jint* mem = spline_desc(e, quantAdjust, nControl, control, coeff, baseCorrX, baseCorrB, &d);
+    if (!mem) return NULL;
+    jintArray out = NULL;
+    int64_t n = jxl_spline_arcs(&d, h, w, NULL, 0);
+    jxl_spline_arc* arcs = NULL;
+    if (n >= 0 && n > 0x7fffffff / 12) n = JXL_ERR_OOM;
+    if (n > 0 && !(arcs = (jxl_spline_arc*)malloc(sizeof(jxl_spline_arc) * (size_t)n))) n = JXL_ERR_OOM;
+    if (n > 0) n = jxl_spline_arcs(&d, h, w, arcs, n);
+    if (n < 0) rethrow(e, NULL, (jxl_status)n);
+    else if ((out = (*e)->NewIntArray(e, (jsize)(12 * n))) && n) (*e)->SetIntArrayRegion(e, out, 0, (jsize)(12 * n), (const jint*)arcs);
+    free(arcs);
+    free(mem);
+    return out;
+}
+
 JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_runBatch0(JNIEnv* e, jclass k, jlongArray ctxs) {
     (void)k;
     const jsize n = (*e)->GetArrayLength(e, ctxs);

@@ -21,6 +21,9 @@ def main(argv=None):
     ap.add_argument("--device-color", action="store_true",
                     help="colour management of the PNG (linearise, primaries, peak, output transfer) as one device pass "
                          "(jxl_stage_color_convert); float samples within 1 ulp of the host path")
+    ap.add_argument("--device-splines", action="store_true",
+                    help="draw the splines on the device (jxl_planes_splines / jxl_stage_splines) instead of numpy on the host; "
+                         "samples equal except where a float exp rounds the other way")
     a = ap.parse_args(argv)
     from . import frontend
     if a.info:
@@ -33,7 +36,7 @@ def main(argv=None):
     PEAK_DETECT = {"auto": PEAK_DETECT_AUTO, "on": PEAK_DETECT_ON, "off": PEAK_DETECT_OFF}
     t0 = time.time()
     backend = DeviceBackend(a.device)
-    dec = JXLDecoder(a.input, backend=backend, sparse_coeffs=a.sparse_coeffs)
+    dec = JXLDecoder(a.input, backend=backend, sparse_coeffs=a.sparse_coeffs, device_splines=a.device_splines)
     image = dec.decode()
     if image is None:
         print("jxlatte_amd: no frames", file=sys.stderr)

@@ -157,6 +157,41 @@ class ColorParams(C.Structure):
                 ("matrix", f9), ("tf_out", C.c_int32), ("gamma_out", C.c_int32), ("max_value", C.c_int32)]
 
 
+class SplineDesc(C.Structure):
+    """struct jxl_spline_desc (SplinesBundle.java + the two LFChannelCorrelation factors)"""
+    _fields_ = [("quant_adjust", C.c_int32), ("n_splines", C.c_int32), ("n_control", C.POINTER(C.c_int32)),
+                ("control", C.POINTER(C.c_int32)), ("coeff", C.POINTER(C.c_int32)), ("base_corr_x", C.c_float),
+                ("base_corr_b", C.c_float)]
+
+
+class SplineArc(C.Structure):
+    """struct jxl_spline_arc: one drawing arc sample of Spline.renderSpline, 48 bytes"""
+    _fields_ = [("y", C.c_float), ("x", C.c_float), ("sigma", C.c_float), ("inv_sigma", C.c_float), ("mul", C.c_float * 3),
+                ("x0", C.c_int32), ("x1", C.c_int32), ("y0", C.c_int32), ("y1", C.c_int32), ("reserved", C.c_int32)]
+
+
+# the same record as a numpy structured dtype (host.spline_arcs)
+SPLINE_ARC_DTYPE = [("y", "<f4"), ("x", "<f4"), ("sigma", "<f4"), ("inv_sigma", "<f4"), ("mul", "<f4", (3,)), ("x0", "<i4"),
+                    ("x1", "<i4"), ("y0", "<i4"), ("y1", "<i4"), ("reserved", "<i4")]
+
+
+def make_spline_desc(splines, base_corr_x, base_corr_b):
+    """splines: the list frontend.Frontend.splines() returns (dicts of quant_adjust, control [(y, x)...], coeff [4][32]).
+    Returns (desc, keepalive)."""
+    import numpy as np
+    n_control = np.array([len(sp["control"]) for sp in splines], np.int32)
+    control = np.ascontiguousarray(np.concatenate([np.asarray(sp["control"], np.int32).reshape(-1, 2) for sp in splines])
+                                   if splines else np.zeros((0, 2)), np.int32)
+    coeff = np.ascontiguousarray(np.stack([np.asarray(sp["coeff"], np.int32).reshape(4, 32) for sp in splines])
+                                 if splines else np.zeros((0, 4, 32)), np.int32)
+    d = SplineDesc()
+    d.quant_adjust = int(splines[0]["quant_adjust"]) if splines else 0
+    d.n_splines = len(splines)
+    d.n_control, d.control, d.coeff = ptr(n_control, C.c_int32), ptr(control, C.c_int32), ptr(coeff, C.c_int32)
+    d.base_corr_x, d.base_corr_b = float(base_corr_x), float(base_corr_b)
+    return d, (n_control, control, coeff)
+
+
 class SqueezeParam(C.Structure):
     """struct jxl_squeeze_param (SqueezeParam.java)"""
     _fields_ = [("horizontal", C.c_int32), ("in_place", C.c_int32), ("begin_c", C.c_int32), ("num_c", C.c_int32)]

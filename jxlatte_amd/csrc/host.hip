@@ -147,6 +147,15 @@ struct jxl_ctx {
     // resident colour planes between decodeFrame and the colour transform (jxl_planes_*): dense [rp_h][rp_w] floats
     DevBuf rp[3], rp_tmp[3], rp_noise[3];
     int rp_h = 0, rp_w = 0;
+    // spline tables (jxl_stage_splines / jxl_planes_splines): arc records, non-empty tiles, CSR ranges and arc lists laid out
+    // back to back in ONE page-locked buffer and moved by ONE transfer into spl. A buffer of its own, not h_tab: that one holds
+    // the open frame's grids, which a re-run of the frame uploads again.
+    char* h_spl = nullptr;
+    size_t h_spl_cap = 0;
+    bool h_spl_pinned = false;
+    DevBuf spl;
+    hipEvent_t spl_ev = nullptr;   // "the transfer has read h_spl": what the next splines call waits for before it writes
+    bool spl_inflight = false;
     // binned work
     // one merged launch: the segments (types) of one register class; channel >= 0: chroma-subsampled frame, one channel per launch
     struct TypeLaunch { int cls, channel; std::vector<IdctSegment> segs; };
@@ -1345,6 +1354,12 @@ void jxl_ctx_destroy(jxl_ctx* c) {
         else free(c->h_tab);
     }
     for (int i = 0; i < 3; i++) { c->rp[i].release(); c->rp_tmp[i].release(); c->rp_noise[i].release(); }
+    c->spl.release();
+    if (c->spl_ev) (void)hipEventDestroy(c->spl_ev);
+    if (c->h_spl) {
+        if (c->h_spl_pinned) (void)hipHostFree(c->h_spl);
+        else free(c->h_spl);
+    }
     for (auto& b : c->mod_bufs) b.release();
     for (int i = 0; i < jxl_ctx::kEvSlots; i++)
         for (int j = 0; j < 3; j++)
@@ -2816,6 +2831,137 @@ jxl_status jxl_planes_upload(jxl_ctx* c, const float* const in[3], int32_t heigh
     c->rp_h = height;
     c->rp_w = width;
     return JXL_OK;
+}
+
+// ---- splines: Frame.renderSplines as one launch over the binned arc table (spline_host.hip, k_spline.hip) ----
+namespace {
+struct SplineLaunch { const jxl_spline_arc* arcs; const int32_t *tile, *start, *list; int n_tiles, tiles_x; int64_t n_arcs, n_pairs; };
+
+// arc table + bins of `d` for a height x width frame, staged in c->h_spl and queued to c->spl by one transfer; out->n_tiles == 0:
+// nothing to draw
+jxl_status spline_tables(jxl_ctx* c, const jxl_spline_desc* d, int32_t height, int32_t width, SplineLaunch* out) {
+    memset(out, 0, sizeof *out);
+    std::vector<jxl_spline_arc> arcs;
+    const char* why = "";
+    jxl_status st = spline_arc_table(d, height, width, &arcs, &why);
+    if (st) return fail(c, st, "%s", why);
+    if (arcs.empty()) return JXL_OK;
+    SplineBins bins;
+    if (!spline_bin(arcs.data(), (int64_t)arcs.size(), height, width, &bins)) return fail(c, JXL_ERR_OOM, "splines: the tile lists do not fit");
+    const size_t off_tile = tab_up(arcs.size() * sizeof(jxl_spline_arc)), off_start = off_tile + tab_up(bins.tile.size() * 4),
+                 off_list = off_start + tab_up(bins.start.size() * 4), total = off_list + tab_up(bins.list.size() * 4);
+    if (c->spl_inflight && c->spl_ev) (void)hipEventSynchronize(c->spl_ev);
+    c->spl_inflight = false;
+    if (total > c->h_spl_cap) {
+        const size_t cap = std::max(total, c->h_spl_cap + c->h_spl_cap / 2);
+        void* q = nullptr;
+        bool pinned = true;
+        if (hipHostMalloc(&q, cap, hipHostMallocDefault) != hipSuccess || !q) {
+            (void)hipGetLastError();
+            q = malloc(cap);
+            pinned = false;
+            if (!q) return fail(c, JXL_ERR_OOM, "host allocation failed (spline tables)");
+        }
+        if (c->h_spl) {
+            if (c->h_spl_pinned) (void)hipHostFree(c->h_spl);
+            else free(c->h_spl);
+        }
+        c->h_spl = static_cast<char*>(q);
+        c->h_spl_cap = cap;
+        c->h_spl_pinned = pinned;
+    }
+    memcpy(c->h_spl, arcs.data(), arcs.size() * sizeof(jxl_spline_arc));
+    memcpy(c->h_spl + off_tile, bins.tile.data(), bins.tile.size() * 4);
+    memcpy(c->h_spl + off_start, bins.start.data(), bins.start.size() * 4);
+    memcpy(c->h_spl + off_list, bins.list.data(), bins.list.size() * 4);
+    if (!c->spl.ensure(total)) return fail(c, JXL_ERR_OOM, "device allocation failed (spline tables)");
+    HIP_TRY(c, hipMemcpyAsync(c->spl.p, c->h_spl, total, hipMemcpyHostToDevice, c->stream));
+    if (c->h_spl_pinned) {
+        if (!c->spl_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->spl_ev, hipEventDisableTiming));
+        HIP_TRY(c, hipEventRecord(c->spl_ev, c->stream));
+        c->spl_inflight = true;
+    } else {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    char* base = c->spl.as<char>();
+    out->arcs = reinterpret_cast<const jxl_spline_arc*>(base);
+    out->tile = reinterpret_cast<const int32_t*>(base + off_tile);
+    out->start = reinterpret_cast<const int32_t*>(base + off_start);
+    out->list = reinterpret_cast<const int32_t*>(base + off_list);
+    out->n_tiles = (int)bins.tile.size();
+    out->tiles_x = bins.tiles_x;
+    out->n_arcs = (int64_t)arcs.size();
+    out->n_pairs = (int64_t)bins.list.size();
+    return JXL_OK;
+}
+}  // namespace
+
+jxl_status jxl_planes_splines(jxl_ctx* c, const jxl_spline_desc* d) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (c->rp_h <= 0) return fail(c, JXL_ERR_STATE, "no resident planes");
+    SplineLaunch l;
+    if ((st = spline_tables(c, d, c->rp_h, c->rp_w, &l))) return st;
+    if (!l.n_tiles) return JXL_OK;
+    float* pl[3] = {c->rp[0].as<float>(), c->rp[1].as<float>(), c->rp[2].as<float>()};
+    launch_splines(pl, c->rp_h, c->rp_w, l.arcs, l.tile, l.start, l.list, l.n_tiles, l.tiles_x, c->stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, JXL_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
+    return JXL_OK;
+}
+
+jxl_status jxl_stage_splines(jxl_ctx* c, float* const planes[3], int32_t height, int32_t width, const jxl_spline_desc* d) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (!planes || !planes[0] || !planes[1] || !planes[2] || height < 1 || width < 1) return fail(c, JXL_ERR_INVALID_ARGUMENT, "splines: bad arguments");
+    SplineLaunch l;
+    if ((st = spline_tables(c, d, height, width, &l))) return st;
+    if (!l.n_tiles) return JXL_OK;
+    const size_t n = (size_t)height * width;
+    Tmp t;
+    float* dp[3];
+    for (int i = 0; i < 3; i++)
+        if (!(dp[i] = t.up(planes[i], n))) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    launch_splines(dp, height, width, l.arcs, l.tile, l.start, l.list, l.n_tiles, l.tiles_x, c->stream);
+    if ((st = finish(c))) return st;
+    for (int i = 0; i < 3; i++) HIP_TRY(c, hipMemcpy(planes[i], dp[i], 4 * n, hipMemcpyDeviceToHost));
+    return JXL_OK;
+}
+
+// tools/spline_bench.py: the spline kernel alone on device copies of `planes` (which are not written back), by stream events:
+// mean milliseconds per launch over `reps` launches after one warm-up launch; counts[0] = arcs, counts[1] = non-empty tiles,
+// counts[2] = (tile, arc) list entries
+extern "C" jxl_status jxl_debug_spline_kernel_ms(jxl_ctx* c, const float* const planes[3], int32_t height, int32_t width,
+                                                 const jxl_spline_desc* d, int32_t reps, float* ms, int64_t counts[3]) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (!planes || !planes[0] || !planes[1] || !planes[2] || height < 1 || width < 1 || reps < 1 || !ms || !counts)
+        return fail(c, JXL_ERR_INVALID_ARGUMENT, "spline bench: bad arguments");
+    SplineLaunch l;
+    if ((st = spline_tables(c, d, height, width, &l))) return st;
+    counts[0] = l.n_arcs, counts[1] = l.n_tiles, counts[2] = l.n_pairs;
+    *ms = 0.0f;
+    if (!l.n_tiles) return JXL_OK;
+    const size_t n = (size_t)height * width;
+    Tmp t;
+    float* dp[3];
+    for (int i = 0; i < 3; i++)
+        if (!(dp[i] = t.up(planes[i], n))) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    hipEvent_t ev[2];
+    HIP_TRY(c, hipEventCreate(&ev[0]));
+    if (hipEventCreate(&ev[1]) != hipSuccess) {
+        (void)hipEventDestroy(ev[0]);
+        return fail(c, JXL_ERR_DEVICE, "event creation failed");
+    }
+    launch_splines(dp, height, width, l.arcs, l.tile, l.start, l.list, l.n_tiles, l.tiles_x, c->stream);
+    (void)hipEventRecord(ev[0], c->stream);
+    for (int r = 0; r < reps; r++) launch_splines(dp, height, width, l.arcs, l.tile, l.start, l.list, l.n_tiles, l.tiles_x, c->stream);
+    (void)hipEventRecord(ev[1], c->stream);
+    st = finish(c);
+    if (!st && hipEventElapsedTime(ms, ev[0], ev[1]) == hipSuccess) *ms /= (float)reps;
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    return st;
 }
 
 // ---- stage-level entries -----------------------------------------------------------------------------

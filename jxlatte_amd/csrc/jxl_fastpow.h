@@ -84,6 +84,40 @@ __device__ __forceinline__ double fp_pow(double x, double p) {
     return __builtin_nan("");
 }
 
+// exp(x) for the spline stage (MathHelper.erf, MathHelper.java:53, :61: Math.exp on a float widened to double, result cast to
+// float). Same shape as the 2^z half of fp_pow_pos: n = rint(x log2 e), r = x log2 e - n carried as a product in two parts
+// (one fma against the double nearest log2 e, one against what that double leaves out: |r| <= 1/2 is then good to ~1e-16
+// absolute for every |x| that gives a non-zero float), the same series of exp(r ln 2) to r^13, ldexp. Relative error in
+// double 2.0e-16 over [-110, 90], asserted below 1e-15 (numpy restatement with these coefficients against long double over
+// that whole range, tests/test_splines_cpu.py; the kernel's arguments lie in about [-1e4, 3]), so the float cast differs from a correctly rounded exp only where the true value lies within
+// ~1e-15 of a float rounding boundary (~2e-8 of the samples). The double result is normal down to 2^-1022, so the cast rounds
+// correctly through the float subnormals and to 0.0f below 2^-150. x = -inf gives 0, +inf gives +inf, NaN gives NaN.
+__device__ __forceinline__ double fp_exp(double x) {
+    const double n = __builtin_rint(x * 1.4426950408889634);
+    double rr = __builtin_fma(x, 1.4426950408889634, -n);   // log2 e, the nearest double ...
+    rr = __builtin_fma(x, 2.0355273740931033e-17, rr);      // ... and log2 e minus that double
+    double Q = 1.3691488853904124e-12;  // (ln 2)^k / k!, k = 13 .. 0
+    Q = __builtin_fma(Q, rr, 2.5678435993488196e-11);
+    Q = __builtin_fma(Q, rr, 4.4455382718708101e-10);
+    Q = __builtin_fma(Q, rr, 7.0549116208011209e-09);
+    Q = __builtin_fma(Q, rr, 1.0178086009239696e-07);
+    Q = __builtin_fma(Q, rr, 1.3215486790144305e-06);
+    Q = __builtin_fma(Q, rr, 1.5252733804059838e-05);
+    Q = __builtin_fma(Q, rr, 0.00015403530393381606);
+    Q = __builtin_fma(Q, rr, 0.0013333558146428441);
+    Q = __builtin_fma(Q, rr, 0.0096181291076284769);
+    Q = __builtin_fma(Q, rr, 0.055504108664821576);
+    Q = __builtin_fma(Q, rr, 0.24022650695910069);
+    Q = __builtin_fma(Q, rr, 0.69314718055994529);
+    Q = __builtin_fma(Q, rr, 1.0);
+    const int ni = (int)__builtin_fmin(__builtin_fmax(n, -4000.0), 4000.0);
+    double v = __builtin_amdgcn_ldexp(Q, ni);
+    // beyond +-1500 the product above is no longer a reduction (and +-inf makes r NaN): the limits directly. NaN passes both tests
+    v = x < -1500.0 ? 0.0 : v;
+    v = x > 1500.0 ? __builtin_inf() : v;
+    return v;
+}
+
 // TF_PQ.fromLinear (TransferFunction.java:83-87), with the reference's constants
 __device__ __forceinline__ float fp_tf_pq(float f) {
     const double d = fp_pow((double)f, 0.159423828125);

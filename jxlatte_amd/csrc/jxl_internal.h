@@ -400,6 +400,26 @@ void launch_blend(int op, unsigned flags, void* canvas, int cw, const void* fram
 void launch_orient(const void* in, int h, int w, int orientation, void* out, hipStream_t s);
 void launch_pack(const void* const planes[4], const jxl_pack_params& p, bool coerce, void* out, hipStream_t s);
 
+// ---- splines (spline_host.hip: the host side; k_spline.hip: the kernel) ----
+// footprint of one workgroup of k_splines, and the unit of the host's binning
+constexpr int kSplineTileW = 32, kSplineTileH = 8;
+constexpr int64_t kSplineMaxArcs = (int64_t)1 << 26;
+static_assert(sizeof(jxl_spline_arc) == 48, "arc record");
+// the arc table of jxl_spline_arcs, uncapped; JXL_OK or a status (the reason in *why)
+jxl_status spline_arc_table(const jxl_spline_desc* d, int32_t height, int32_t width, std::vector<jxl_spline_arc>* out, const char** why);
+// The binned form of an arc table, as offsets (in int32 words) into one buffer the kernel reads: the non-empty tiles
+// (index ty * tiles_x + tx) in raster order, per non-empty tile its CSR range, and the arc indices of every tile in TABLE ORDER
+struct SplineBins {
+    int tiles_x = 0, tiles_y = 0;
+    std::vector<int32_t> tile;   // [n_tiles]
+    std::vector<int32_t> start;  // [n_tiles + 1]
+    std::vector<int32_t> list;   // [start[n_tiles]]
+};
+// false: the lists do not fit (bad_alloc, or 2^31 entries and more)
+bool spline_bin(const jxl_spline_arc* arcs, int64_t n, int32_t height, int32_t width, SplineBins* out);
+void launch_splines(float* const planes[3], int h, int w, const jxl_spline_arc* arcs, const int32_t* tile, const int32_t* start,
+                    const int32_t* list, int n_tiles, int tiles_x, hipStream_t s);
+
 void launch_idct2d_single(const float* src, float* dst, int h, int w, int transposed, const float* lut, hipStream_t s);
 void launch_fdct2d_single(const float* src, float* dst, int h, int w, const float* lut, hipStream_t s);
 

@@ -191,13 +191,17 @@ def _erf(z):
     return np.where(z < 0, -a, a).astype(F)
 
 
-def _spline_arcs(control):
-    """Spline.upsampleControlPoints + computeIntermediarySamples(1.0f): list of (y, x, arcLength)"""
+def _spline_knots(control):
+    """Spline.upsampleControlPoints (Spline.java:27-87): the knots as two lists of float32 (y, x). Repeated control points
+    divide by a zero t[k + 1] - t[k]: their NaN / inf knots are kept as the float operations give them"""
     cp = [(int(y), int(x)) for y, x in control]
     if len(cp) == 1:
         uy, ux = [F(cp[0][0])], [F(cp[0][1])]
     else:
-        ext = [(cp[0][0] * 2 - cp[1][0], cp[0][1] * 2 - cp[1][1])] + cp + [(cp[-1][0] * 2 - cp[-2][0], cp[-1][1] * 2 - cp[-2][1])]
+        def i32(v):  # Point arithmetic is Java int arithmetic: it wraps (Spline.java:37-43)
+            return ((v + 2**31) % 2**32) - 2**31
+        ext = [(i32(cp[0][0] * 2 - cp[1][0]), i32(cp[0][1] * 2 - cp[1][1]))] + cp + \
+              [(i32(cp[-1][0] * 2 - cp[-2][0]), i32(cp[-1][1] * 2 - cp[-2][1]))]
         n = 16 * (len(ext) - 3) + 1
         uy, ux = [F(0)] * n, [F(0)] * n
         for i in range(len(ext) - 3):
@@ -224,6 +228,12 @@ def _spline_arcs(control):
                     uy[i * 16 + step] = F(F(F(bY[1] - bY[0]) * f) + bY[0])
                     ux[i * 16 + step] = F(F(F(bX[1] - bX[0]) * f) + bX[0])
         uy[-1], ux[-1] = F(cp[-1][0]), F(cp[-1][1])
+    return uy, ux
+
+
+def _spline_arcs(control):
+    """Spline.upsampleControlPoints + computeIntermediarySamples(1.0f): list of (y, x, arcLength)"""
+    uy, ux = _spline_knots(control)
     rd = F(1.0)
     cy, cx = uy[0], ux[0]
     nxt = 0
@@ -256,12 +266,15 @@ def _fourier_ict(coeffs, t):
     return total
 
 
-def render_splines(buffers, splines, base_corr_x, base_corr_b, width, height):
-    """Frame.renderSplines + Spline.renderSpline (Spline.java:157-201). The reference never stores the spline index
-    (Spline.java:22-24), so every spline is drawn with the coefficients of spline 0; `MathHelper.max(float...)` returns the
-    minimum (MathHelper.java:190-195). Both restated as they are."""
+def spline_arc_table(splines, base_corr_x, base_corr_b, width, height):
+    """the per-arc half of Frame.renderSplines + Spline.renderSpline (Spline.java:155-179): the arcs that draw, in the
+    reference's order, as tuples (y, x, sigma, inv_sigma, values[3], (x0, x1, y0, y1)) of float32 / int. The reference never
+    stores the spline index (Spline.java:22-24), so every spline is drawn with the coefficients of spline 0;
+    `MathHelper.max(float...)` returns the minimum (MathHelper.java:190-195). Both restated as they are. The library's
+    jxl_spline_arcs is the same table with mul[c] = (0.25f * values[c]) * sigma."""
+    table = []
     if not splines:
-        return
+        return table
     s0 = splines[0]
     qa = F(F(s0["quant_adjust"]) / F(8))
     inv_qa = F(F(1) / F(F(1) + qa)) if qa >= 0 else F(F(1) - qa)
@@ -277,11 +290,11 @@ def render_splines(buffers, splines, base_corr_x, base_corr_b, width, height):
         if arc_len <= 0:
             continue
         for i, (ay, ax, alen) in enumerate(arcs):
-            prog = min(F(1.0), F(F(F(i) * rd) / arc_len))
-            t = F(F(31) * prog)
-            vals = [F(_fourier_ict(c, t) * alen) for c in (cX, cY, cB)]
-            sigma = _fourier_ict(cS, t)
             with np.errstate(all="ignore"):
+                prog = min(F(1.0), F(F(F(i) * rd) / arc_len))
+                t = F(F(31) * prog)
+                vals = [F(_fourier_ict(c, t) * alen) for c in (cX, cY, cB)]
+                sigma = _fourier_ict(cS, t)
                 inv_sigma = F(F(1) / sigma)
                 max_color = min(F(0.01), vals[0], vals[1], vals[2])  # MathHelper.max(float...) is a minimum
                 md = F(math.sqrt(float(F(F(F(-2) * sigma) * sigma * F(F(F(math.log(0.1)) * F(3)) - max_color))))) \
@@ -295,16 +308,24 @@ def render_splines(buffers, splines, base_corr_x, base_corr_b, width, height):
             yb, ye = max(0, rnd(F(ay - md))), min(height - 1, rnd(F(ay + md)))
             if xb > xe or yb > ye:
                 continue
-            ys = np.arange(yb, ye + 1, dtype=F)[:, None]
-            xs = np.arange(xb, xe + 1, dtype=F)[None, :]
-            dy, dx = (ys - ay).astype(F), (xs - ax).astype(F)
-            dist = np.sqrt(((dy * dy).astype(F) + (dx * dx).astype(F)).astype(np.float64)).astype(F)
-            with np.errstate(all="ignore"):
-                fac = _erf(((F(0.5) * dist).astype(F) + _SQRT_F).astype(F) * inv_sigma)
-                fac = (fac - _erf(((F(0.5) * dist).astype(F) - _SQRT_F).astype(F) * inv_sigma)).astype(F)
-                for c in range(3):
-                    extra = ((((F(0.25) * vals[c]) * sigma).astype(F) * fac).astype(F) * fac).astype(F)
-                    buffers[c][yb:ye + 1, xb:xe + 1] = (buffers[c][yb:ye + 1, xb:xe + 1] + extra).astype(F)
+            table.append((ay, ax, sigma, inv_sigma, vals, (xb, xe, yb, ye)))
+    return table
+
+
+def render_splines(buffers, splines, base_corr_x, base_corr_b, width, height):
+    """Frame.renderSplines + Spline.renderSpline (Spline.java:157-201) on the host: the arcs of spline_arc_table drawn in
+    order, each over its box (:180-197)"""
+    for ay, ax, sigma, inv_sigma, vals, (xb, xe, yb, ye) in spline_arc_table(splines, base_corr_x, base_corr_b, width, height):
+        ys = np.arange(yb, ye + 1, dtype=F)[:, None]
+        xs = np.arange(xb, xe + 1, dtype=F)[None, :]
+        dy, dx = (ys - ay).astype(F), (xs - ax).astype(F)
+        dist = np.sqrt(((dy * dy).astype(F) + (dx * dx).astype(F)).astype(np.float64)).astype(F)
+        with np.errstate(all="ignore"):
+            fac = _erf(((F(0.5) * dist).astype(F) + _SQRT_F).astype(F) * inv_sigma)
+            fac = (fac - _erf(((F(0.5) * dist).astype(F) - _SQRT_F).astype(F) * inv_sigma)).astype(F)
+            for c in range(3):
+                extra = ((((F(0.25) * vals[c]) * sigma).astype(F) * fac).astype(F) * fac).astype(F)
+                buffers[c][yb:ye + 1, xb:xe + 1] = (buffers[c][yb:ye + 1, xb:xe + 1] + extra).astype(F)
 
 
 # ---- backends -------------------------------------------------------------------------------------------------
@@ -403,6 +424,9 @@ class DeviceBackend:
 
     def upsample(self, plane, k, weights):
         return self.host.performUpsampling(self.ctx, plane, k, weights)
+
+    def splines(self, planes, splines, bcx, bcb):
+        return self.host.renderSplines(self.ctx, planes, splines, bcx, bcb)
 
     def noise_init(self, h, w, seed0, group_dim, colors):
         return self.host.initializeNoise(self.ctx, h, w, seed0, group_dim, colors)
@@ -626,10 +650,14 @@ def _tt_dims():
 
 
 class JXLDecoder:
-    def __init__(self, source, backend=None, sparse_coeffs=False):
+    def __init__(self, source, backend=None, sparse_coeffs=False, device_splines=False):
         """sparse_coeffs: hand the HF coefficients to the backend as lists of non-zero entries (jxf_get_coeffs_sparse ->
-        jxl_vardct_put_group_sparse), not as dense planes; same pixels"""
+        jxl_vardct_put_group_sparse), not as dense planes; same pixels.
+        device_splines: Frame.renderSplines runs in the backend (jxl_planes_splines on the resident planes, jxl_stage_splines
+        otherwise) instead of render_splines on the host; the samples agree except where a (float)Math.exp falls on the other
+        side of a float rounding boundary (include/jxlatte_amd.h). A backend without `splines` is an error."""
         self.sparse_coeffs = bool(sparse_coeffs)
+        self.device_splines = bool(device_splines)
         if isinstance(source, (bytes, bytearray, memoryview)):
             data = bytes(source)
         else:
@@ -719,9 +747,10 @@ class JXLDecoder:
     def _chained_tail(self, fr, rp, buffers, colors, save, xyb_done):
         """Frame.upsample .. performColorTransforms (JXLCodestreamDecoder.java:628-637) of the three colour planes with the
         samples moving between host and device only where the next stage lives on the other side: upsampling, noise and the
-        colour transforms are device stages on host.ResidentPlanes; the saveBeforeCT reference, patches and splines are host
-        stages (as in the reference). `rp` is the VarDCT frame's resident result, or None when the colour planes start as the
-        host arrays buffers[:3] (Modular frames). The extra channels in buffers[3:] are host arrays throughout."""
+        colour transforms are device stages on host.ResidentPlanes, and so are the splines with `device_splines`; the
+        saveBeforeCT reference, the patches and (by default) the splines are host stages (as in the reference). `rp` is the
+        VarDCT frame's resident result, or None when the colour planes start as the host arrays buffers[:3] (Modular frames).
+        The extra channels in buffers[3:] are host arrays throughout."""
         info, be = self.info, self.backend
         moves = []
 
@@ -749,7 +778,9 @@ class JXLDecoder:
         if fr.num_patches:
             on_host()
             self._patches(fr, buffers, colors)
-        if fr.has_splines:
+        if fr.has_splines and getattr(self, "device_splines", False):
+            on_device().splines(self.fe.splines(), fr.base_corr_x, fr.base_corr_b)
+        elif fr.has_splines:
             on_host()
             for c in range(3):
                 buffers[c] = self._to_float(buffers[c], info.bits_per_sample).copy()
@@ -1068,7 +1099,12 @@ class JXLDecoder:
             if not resident and fr.has_splines:  # Frame.renderSplines (host-side, as in the reference)
                 for c in range(3):
                     buffers[c] = self._to_float(buffers[c], info.bits_per_sample).copy()
-                render_splines(buffers, self.fe.splines(), fr.base_corr_x, fr.base_corr_b, buffers[0].shape[1], buffers[0].shape[0])
+                if getattr(self, "device_splines", False):  # the stage entry: no silent return to the host render
+                    planes = be.splines(np.stack(buffers[:3]), self.fe.splines(), fr.base_corr_x, fr.base_corr_b)
+                    for c in range(3):
+                        buffers[c] = np.ascontiguousarray(planes[c])
+                else:
+                    render_splines(buffers, self.fe.splines(), fr.base_corr_x, fr.base_corr_b, buffers[0].shape[1], buffers[0].shape[0])
             if noise is not None:
                 planes = np.stack([self._to_float(buffers[c], info.bits_per_sample) for c in range(3)])
                 planes = be.noise_add(planes, noise, np.array(fr.noise, F), fr.base_corr_x, fr.base_corr_b)
@@ -1154,7 +1190,8 @@ class PNGWriter:
 def load_vardct_frame(source, ctx, transfer=abi.TRANSFER_NONE, out_format=abi.OUT_F32, sparse=False):
     """Parse the first frame of a VarDCT .jxl file with the front-end and stage it in a host.Frame on `ctx` (inputs
     resident, nothing run yet): the real-bitstream workload of bench.py. Returns (host.Frame, stats dict).
-    sparse: the coefficients go through the sparse feed (jxl_vardct_put_group_sparse)."""
+    sparse: the coefficients go through the sparse feed (jxl_vardct_put_group_sparse). The frame tail is not run here, so
+    JXLDecoder's `device_splines` has no counterpart: this is the only load_* helper, and it stops before the splines."""
     from . import host
     if isinstance(source, (bytes, bytearray)):
         data = bytes(source)

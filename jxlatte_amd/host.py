@@ -468,8 +468,9 @@ class PinnedArray:
 class ResidentPlanes:
     """the frame's three colour planes on the device between decodeFrame and the blend: Frame.upsample (Frame.java:217-260),
     initializeNoise + synthesizeNoise (:748-831), performColorTransforms (JXLCodestreamDecoder.java:256-276), in the
-    reference's order, with the host hook (download / upload) only where the reference's host-side stages (patches,
-    splines, saveBeforeCT) need the samples."""
+    reference's order; Frame.renderSplines (Frame.java:739-746) may stay on the device too (splines). The host hook
+    (download / upload) is needed only where a host-side stage wants the samples: patches (copies and blends out of host-side
+    reference frames), saveBeforeCT, and the splines unless `splines` draws them."""
 
     def __init__(self, ctx):
         self.ctx = ctx
@@ -496,6 +497,11 @@ class ResidentPlanes:
         assert lut.size == 8
         self.ctx.call("jxl_planes_noise", groupDim, C.c_uint64(seed0), abi.fptr(lut), C.c_float(baseCorrelationX),
                       C.c_float(baseCorrelationB))
+
+    def splines(self, splines, baseCorrelationX, baseCorrelationB):
+        """Frame.renderSplines on the resident planes (jxl_planes_splines): after upsample / the patches, before noise"""
+        d, keep = abi.make_spline_desc(splines, baseCorrelationX, baseCorrelationB)
+        self.ctx.call("jxl_planes_splines", C.byref(d))
 
     def invertXYB(self, matrix, opsin_bias, cbrt_opsin_bias, intensityTarget):
         m = OpsinInverseMatrix(matrix, opsin_bias, cbrt_opsin_bias)
@@ -686,6 +692,33 @@ def synthesizeNoise(ctx, planes, noise, lut, baseCorrelationX, baseCorrelationB)
     pp = (C.POINTER(C.c_float) * 3)(*[abi.fptr(out[c]) for c in range(3)])
     pn = (C.POINTER(C.c_float) * 3)(*[abi.fptr(nz[c]) for c in range(3)])
     ctx.call("jxl_stage_noise_add", pp, pn, out[0].size, abi.fptr(lut), C.c_float(baseCorrelationX), C.c_float(baseCorrelationB))
+    return out
+
+
+def spline_arcs(splines, baseCorrelationX, baseCorrelationB, height, width):
+    """the arcs Frame.renderSplines draws into a height x width frame, in the reference's order (jxl_spline_arcs: host only,
+    no context): a numpy record array of abi.SPLINE_ARC_DTYPE"""
+    from ._lib import JxlError, load
+    lib = load()
+    d, keep = abi.make_spline_desc(splines, baseCorrelationX, baseCorrelationB)
+    n = lib.jxl_spline_arcs(C.byref(d), height, width, None, 0)
+    if n < 0:
+        raise JxlError(int(n), "jxl_spline_arcs")
+    out = np.zeros(int(n), abi.SPLINE_ARC_DTYPE)
+    if n:
+        m = lib.jxl_spline_arcs(C.byref(d), height, width, out.ctypes.data_as(C.POINTER(abi.SplineArc)), n)
+        assert m == n
+    return out
+
+
+def renderSplines(ctx, planes, splines, baseCorrelationX, baseCorrelationB):
+    """Frame.renderSplines (Frame.java:739-746) + Spline.renderSpline (Spline.java:27-200) on three float planes
+    (jxl_stage_splines); returns new planes"""
+    out = np.array(planes, np.float32, order="C", copy=True)
+    if out.ndim != 3 or out.shape[0] != 3:
+        raise ValueError("expected planes of shape (3, H, W)")
+    d, keep = abi.make_spline_desc(splines, baseCorrelationX, baseCorrelationB)
+    ctx.call("jxl_stage_splines", _p3(out, C.c_float), out.shape[1], out.shape[2], C.byref(d))
     return out
 
 
