@@ -343,9 +343,9 @@ jxl_status jxl_vardct_read_output_wait(jxl_ctx* ctx);
  * Frame.upsample, Frame.initializeNoise, computePatches, Frame.renderSplines, Frame.synthesizeNoise,
  * performColorTransforms. The jxl_stage_* entries take and return host planes; these entries run the same kernels on a set
  * of three float planes that STAYS in device memory, so a frame with upsampling / noise costs one transfer in (its
- * coefficients) and one out (its pixels). Splines may stay on the device too (jxl_planes_splines). Patches stay host code (as
- * in the reference: copies out of host-side reference frames): jxl_planes_download / jxl_planes_upload bracket them, only for
- * frames that have them. */
+ * coefficients) and one out (its pixels). Splines may stay on the device too (jxl_planes_splines), and so may the patches
+ * (jxl_planes_patches: the reference frames stay host arrays and are uploaded for the frame that reads them). A host that
+ * applies the patches itself brackets them with jxl_planes_download / jxl_planes_upload, only for frames that have them. */
 /* adopt the top-left height x width window (Frame bounds; the restoration filters worked on the padded size) of the last
  * jxl_vardct_run's result as the resident planes. The run must have produced float planes (no transfer / integer output;
  * XYB stage off if the later stages need XYB samples). */
@@ -400,6 +400,61 @@ jxl_status jxl_stage_splines(jxl_ctx* ctx, float* const planes[3], int32_t heigh
 /* the same on the resident planes: its place is after jxl_planes_upsample (and the patches), before jxl_planes_noise
  * (JXLCodestreamDecoder.java:628-637). Asynchronous. JXL_ERR_STATE without resident planes. */
 jxl_status jxl_planes_splines(jxl_ctx* ctx, const jxl_spline_desc* d);
+/* ---- patches: JXLCodestreamDecoder.computePatches (JXLCodestreamDecoder.java:212-254) + blendBuffers (:415-513) ----
+ * One position of one patch (Patch.positions[j] of patches[i]), the positions of a frame in the order computePatches visits
+ * them: patches in order, positions in order. */
+typedef struct jxl_patch_pos {
+    int32_t y0, x0;          /* Patch.positions[j]: where the rectangle lands in the frame (:231-232) */
+    int32_t h, w;            /* Patch.bounds.size */
+    int32_t ref;             /* Patch.ref: the reference slot (:220-222) */
+    int32_t ref_y0, ref_x0;  /* Patch.bounds.origin: the rectangle's origin in the slot's planes */
+    int32_t blend;           /* row of jxl_patch_desc.blend: Patch.blendingInfos[j] (:240) */
+} jxl_patch_pos;
+/* The patch stage of one frame. Channels are numbered as computePatches numbers them (:238): d < n_color the colour planes,
+ * n_color + e extra channel e. A blend row holds one entry of three ints (mode 0..7, alphaChannel, clamp) per channel d: the
+ * BlendingInfo computePatches hands to blendBuffers for it (blendingInfos[j][0] for every colour channel, [1 + e] for extra
+ * channel e, :239-240). The image facts are those blendBuffers reads (:418-431). */
+typedef struct jxl_patch_desc {
+    int32_t n_pos;
+    const jxl_patch_pos* pos;
+    int32_t n_rows;
+    const int32_t* blend;               /* [n_rows][n_color + n_extra][3] */
+    int32_t n_color;                    /* imageHeader.getColorChannelCount(), which must be the frame's too: 1 or 3 */
+    int32_t n_extra;                    /* imageHeader.getExtraChannelCount() */
+    const int32_t* ec_is_alpha;         /* [n_extra] ExtraChannelInfo.type == ALPHA (:426) */
+    const int32_t* ec_alpha_associated; /* [n_extra] ExtraChannelInfo.alphaAssociated (:431) */
+    int32_t ref_h[4], ref_w[4];         /* size of the planes of reference[k]; 0 x 0: reference[k] == null (:225-226) */
+} jxl_patch_desc;
+/* Host only, needs no context and no device: validates the stage and bins its positions over the 32 x 8 pixel tiles of the kernel.
+ * Walks the positions in order: a position whose slot is absent is skipped (:225-226), then "Patch out of range" (:220-221),
+ * "Patch too large" (:228-229) and "Patch size out of bounds" (:233-237) -- the first offence returns JXL_ERR_INVALID_BITSTREAM
+ * with that text in jxl_last_error(NULL) and its position in *first_bad. Then every (position, channel) with mode != 0 is mapped
+ * to its blend function as blendBuffers does (:466-512, modes 5 / 6 / 7 remapped, old and new swapped for the "below" modes) and
+ * checked as jxl_stage_blend checks one call: "Illegal blend mode" (JXL_ERR_INVALID_BITSTREAM), float functions on int planes,
+ * planes of the wrong type, rectangles outside a plane it reads (JXL_ERR_INVALID_ARGUMENT). frame_type[d]: 0 float, 1 int32;
+ * ref_type[4][n_color + n_extra]: the same, or -1 for a plane that is NULL (reads as zeros). JXL_ERR_UNSUPPORTED: a "below" mode
+ * (5, 7) whose reference rectangle is not the frame rectangle itself in planes of the frame's size -- blendBuffers then reads the
+ * frame away from the pixel it writes, which one in-place launch cannot replay.
+ * Returns the number of non-empty tiles and *n_list, and writes tile[] (index ty * ceil(width / 32) + tx, ascending), start[]
+ * (n + 1 CSR offsets) and list[] (position indices, per tile in stage order) when they fit cap_tiles / cap_list. */
+int64_t    jxl_patch_bins(const jxl_patch_desc* d, int32_t height, int32_t width, const int32_t* frame_type, const int32_t* ref_type,
+                          int32_t* tile, int32_t* start, int32_t* list, int64_t cap_tiles, int64_t cap_list, int64_t* n_list,
+                          int32_t* first_bad);
+/* computePatches (:212-254) on host planes, in place: frame[d] is height x width of frame_type[d]; ref[k * (n_color + n_extra) + d]
+ * is plane d of reference[k] (ref_h[k] x ref_w[k] of ref_type), or NULL: zeros, the `new ImageBuffer` of :441-442 and :449-451.
+ * No casts: the planes have the types blendBuffers would have given them (:433-465) -- the caller's type plan. Everything is
+ * validated as by jxl_patch_bins before anything is queued; then one upload of the planes, ONE kernel launch in which every pixel
+ * replays, in the reference's order (position, then channel), the applications whose rectangle holds it (blendAdd :285-318,
+ * blendMult :320-339, blendBlend :341-379, blendMulAdd :381-413 with copyToCanvas :390 for the alpha channel itself), and one
+ * download of the frame planes some position writes. A pixel no position covers keeps its bits. Bit-exact. */
+jxl_status jxl_stage_patches(jxl_ctx* ctx, const jxl_patch_desc* d, void* const* frame, const int32_t* frame_type, int32_t height,
+                             int32_t width, const void* const* ref, const int32_t* ref_type);
+/* the same with the three colour planes being the resident planes (float; n_color == 3): its place is after jxl_planes_upsample,
+ * before jxl_planes_splines / jxl_planes_noise (JXLCodestreamDecoder.java:628-637). extra[e] (extra_type[e]) are the frame's
+ * extra channels on the host; those some position writes are updated in place (the call then waits for the device), otherwise
+ * the call is asynchronous. JXL_ERR_STATE without resident planes. */
+jxl_status jxl_planes_patches(jxl_ctx* ctx, const jxl_patch_desc* d, void* const* extra, const int32_t* extra_type,
+                              const void* const* ref, const int32_t* ref_type);
 /* current size of the resident planes */
 jxl_status jxl_planes_shape(const jxl_ctx* ctx, int32_t* height, int32_t* width);
 /* the host hook (patches, saveBeforeCT references; splines unless jxl_planes_splines draws them) and the way out: dense

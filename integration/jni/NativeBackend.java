@@ -87,6 +87,10 @@ public final class NativeBackend implements AutoCloseable {
     public native void planesUpload(ByteBuffer p0, ByteBuffer p1, ByteBuffer p2, int height, int width); // jxl_planes_upload
     public native void planesUpsample(int k, float[] weights);     // jxl_planes_upsample   (Frame.upsample)
     public native void planesNoise(int groupDim, long seed0, float[] lut, float baseCorrX, float baseCorrB); // jxl_planes_noise
+    /** computePatches (:212-254) on the resident colour planes, after planesUpsample and before planesSplines / planesNoise; extra[e]:
+     *  the frame's extra channels as direct buffers (written in place where a position stores into them); the rest as stagePatches. */
+    public native void planesPatches(ByteBuffer[] extra, int[] extraType, ByteBuffer[] ref, int[] refType, int[] pos, int[] blend,
+                                     int[] ecIsAlpha, int[] ecAlphaAssociated, int[] refShape);                        // jxl_planes_patches
     /** Frame.renderSplines (Frame.java:739-746) on the resident planes, after planesUpsample / the patches and before planesNoise.
      *  The splines as SplinesBundle holds them, flattened: nControl[s] points per spline, control = all (y, x) pairs, coeff =
      *  per spline coeffX, coeffY, coeffB, coeffSigma (4 x 32); baseCorrX / B from LFChannelCorrelation. */
@@ -132,6 +136,16 @@ public final class NativeBackend implements AutoCloseable {
     public native void stageRct(ByteBuffer v0, ByteBuffer v1, ByteBuffer v2, long n, int rctType);    // jxl_stage_rct
     public native void stageModularToFloat(ByteBuffer a, ByteBuffer b, long n, float scale, ByteBuffer out); // jxl_stage_modular_to_float
     public native void stageChromaUpsample(ByteBuffer in, int h, int w, int xShift, int yShift, ByteBuffer out); // jxl_stage_chroma_upsample
+    /** JXLCodestreamDecoder.computePatches (:212-254) on host planes, in place, as one kernel launch: frame[d] direct buffers of
+     *  height x width samples (frameType[d]: 0 float, 1 int), ref[k * channels + d] = plane d of reference[k]
+     *  (null or refType -1: reads as zeros), pos = 8 ints per position in stage order (y0, x0, h, w, ref, refY0, refX0, blend row),
+     *  blend = rows of channels x (mode, alphaChannel, clamp), refShape = (h, w) per slot, (0, 0) for reference[k] == null. The
+     *  planes carry the types blendBuffers' casts (:433-465) would have given them. */
+    public native void stagePatches(ByteBuffer[] frame, int[] frameType, int height, int width, ByteBuffer[] ref, int[] refType, int[] pos,
+                                    int[] blend, int nColor, int[] ecIsAlpha, int[] ecAlphaAssociated, int[] refShape); // jxl_stage_patches
+    /** host only: computePatches' checks and the tile lists: { tiles, entries, tile[], start[tiles + 1], list[entries] } */
+    public static native int[] patchBins(int height, int width, int[] frameType, int[] refType, int[] pos, int[] blend, int nColor,
+                                         int[] ecIsAlpha, int[] ecAlphaAssociated, int[] refShape);                    // jxl_patch_bins
     public native void stageSplines(ByteBuffer p0, ByteBuffer p1, ByteBuffer p2, int height, int width, int quantAdjust, int[] nControl,
                                     int[] control, int[] coeff, float baseCorrX, float baseCorrB);   // jxl_stage_splines
     /** host only: the arcs Spline.renderSpline draws, 12 ints per arc (jxl_spline_arc; floats as raw bits) */

@@ -592,6 +592,163 @@ JNIEXPORT jintArray JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_spline
     return out;
 }
 
+/* ---- patches (include/jxlatte_amd.h: jxl_patch_bins, jxl_stage_patches, jxl_planes_patches) ----
+ * The patch stage of a frame (JXLCodestreamDecoder.computePatches, :212-254), flattened: pos = 8 ints per position in stage order
+ * (jxl_patch_pos word for word), blend = rows of (nColor + ecIsAlpha.length) x 3 ints, refShape = (h, w) per reference slot (0, 0:
+ * absent). The arrays are copied and checked against each other before the library sees them; *mem is the copy (free it), NULL
+ * with an exception pending on failure. */
+static jint* patch_desc(JNIEnv* e, jintArray pos, jintArray blend, jint nColor, jintArray ecIsAlpha, jintArray ecAlphaAssociated,
+                        jintArray refShape, jxl_patch_desc* d) {
+    if (!pos || !blend || !ecIsAlpha || !ecAlphaAssociated || !refShape) {
+        bad_arg(e, "jxlatte_amd: patch arrays missing");
+        return NULL;
+    }
+    const jsize np = (*e)->GetArrayLength(e, pos), nb = (*e)->GetArrayLength(e, blend), ne = (*e)->GetArrayLength(e, ecIsAlpha);
+    const jlong row = 3 * ((jlong)nColor + ne);
+    if ((nColor != 1 && nColor != 3) || np % 8 || nb % row || (*e)->GetArrayLength(e, ecAlphaAssociated) != ne ||
+        (*e)->GetArrayLength(e, refShape) != 8) {
+        bad_arg(e, "jxlatte_amd: patch arrays disagree");
+        return NULL;
+    }
+    jint* mem = (jint*)malloc(sizeof(jint) * ((size_t)np + (size_t)nb + 2 * (size_t)ne + 8 + 1));
+    if (!mem) {
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/OutOfMemoryError"), "jxlatte_amd: patch arrays");
+        return NULL;
+    }
+    jint* shape = mem + np + nb + 2 * ne;
+    (*e)->GetIntArrayRegion(e, pos, 0, np, mem);
+    (*e)->GetIntArrayRegion(e, blend, 0, nb, mem + np);
+    (*e)->GetIntArrayRegion(e, ecIsAlpha, 0, ne, mem + np + nb);
+    (*e)->GetIntArrayRegion(e, ecAlphaAssociated, 0, ne, mem + np + nb + ne);
+    (*e)->GetIntArrayRegion(e, refShape, 0, 8, shape);
+    if ((*e)->ExceptionCheck(e)) {
+        free(mem);
+        return NULL;
+    }
+    d->n_pos = np / 8;
+    d->pos = (const jxl_patch_pos*)mem;
+    d->n_rows = (int32_t)(nb / row);
+    d->blend = (const int32_t*)(mem + np);
+    d->n_color = nColor;
+    d->n_extra = ne;
+    d->ec_is_alpha = (const int32_t*)(mem + np + nb);
+    d->ec_alpha_associated = (const int32_t*)(mem + np + nb + ne);
+    for (int k = 0; k < 4; k++) d->ref_h[k] = shape[2 * k], d->ref_w[k] = shape[2 * k + 1];
+    return mem;
+}
+/* n plane buffers of a ByteBuffer[] with their types (0 float, 1 int, -1 / null: absent) against the sizes they must have;
+ * 0 with an exception pending when something is missing or too small */
+static int patch_planes(JNIEnv* e, jobjectArray bufs, jintArray types, jsize n, const jlong* bytes, int may_be_null, void** out, jint* type) {
+    if (!bufs || !types || (*e)->GetArrayLength(e, bufs) != n || (*e)->GetArrayLength(e, types) != n) {
+        bad_arg(e, "jxlatte_amd: patch plane arrays missing or of the wrong length");
+        return 0;
+    }
+    (*e)->GetIntArrayRegion(e, types, 0, n, type);
+    for (jsize i = 0; i < n; i++) {
+        jobject b = (*e)->GetObjectArrayElement(e, bufs, i);
+        out[i] = NULL;
+        if (!b || type[i] == -1) {
+            if (!may_be_null) {
+                bad_arg(e, "jxlatte_amd: a frame plane is missing");
+                return 0;
+            }
+            type[i] = -1;
+            continue;
+        }
+        if (!has_room(e, b, bytes[i])) {
+            bad_arg(e, "jxlatte_amd: a patch plane buffer is not direct or too small");
+            return 0;
+        }
+        out[i] = (*e)->GetDirectBufferAddress(e, b);
+    }
+    return !(*e)->ExceptionCheck(e);
+}
+#define PATCH_MAX_CHAN 64
+
+/* computePatches on host planes, in place (jxl_stage_patches), or with extra == frame planes 3.. on the resident colour planes
+ * (jxl_planes_patches: height, width < 0) */
+static void patches_call(JNIEnv* e, jobject self, int resident, jobjectArray frame, jintArray frameType, jint h, jint w, jobjectArray ref,
+                         jintArray refType, jintArray pos, jintArray blend, jint nColor, jintArray ecIsAlpha, jintArray ecAlphaAssociated,
+                         jintArray refShape) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_patch_desc d;
+    jint* mem = patch_desc(e, pos, blend, nColor, ecIsAlpha, ecAlphaAssociated, refShape, &d);
+    if (!mem) return;
+    const int n_chan = d.n_color + d.n_extra, n_frame = resident ? d.n_extra : n_chan;
+    void* fp[PATCH_MAX_CHAN];
+    void* rp[4 * PATCH_MAX_CHAN];
+    jint ft[PATCH_MAX_CHAN], rt[4 * PATCH_MAX_CHAN];
+    jlong fb[PATCH_MAX_CHAN], rb[4 * PATCH_MAX_CHAN];
+    jxl_status st = JXL_OK;
+    if (n_chan > PATCH_MAX_CHAN || (resident && d.n_color != 3)) {
+        bad_arg(e, "jxlatte_amd: channel count");
+    } else {
+        if (resident && jxl_planes_shape(c, &h, &w) != JXL_OK) h = w = 0;
+        for (int i = 0; i < n_frame; i++) fb[i] = 4 * area(h, w);
+        for (int k = 0; k < 4; k++)
+            for (int i = 0; i < n_chan; i++) rb[k * n_chan + i] = 4 * area(d.ref_h[k], d.ref_w[k]);
+        if (patch_planes(e, frame, frameType, n_frame, fb, 0, fp, ft) && patch_planes(e, ref, refType, 4 * n_chan, rb, 1, rp, rt))
+            st = resident ? jxl_planes_patches(c, &d, fp, (const int32_t*)ft, (const void* const*)rp, (const int32_t*)rt)
+                          : jxl_stage_patches(c, &d, fp, (const int32_t*)ft, h, w, (const void* const*)rp, (const int32_t*)rt);
+    }
+    free(mem);
+    if (!(*e)->ExceptionCheck(e)) CHECK(st);
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stagePatches(JNIEnv* e, jobject self, jobjectArray frame, jintArray frameType,
+        jint h, jint w, jobjectArray ref, jintArray refType, jintArray pos, jintArray blend, jint nColor, jintArray ecIsAlpha,
+        jintArray ecAlphaAssociated, jintArray refShape) {
+    if (h < 1 || w < 1) { bad_arg(e, "jxlatte_amd: plane size"); return; }
+    patches_call(e, self, 0, frame, frameType, h, w, ref, refType, pos, blend, nColor, ecIsAlpha, ecAlphaAssociated, refShape);
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesPatches(JNIEnv* e, jobject self, jobjectArray extra, jintArray extraType,
+        jobjectArray ref, jintArray refType, jintArray pos, jintArray blend, jintArray ecIsAlpha, jintArray ecAlphaAssociated, jintArray refShape) {
+    patches_call(e, self, 1, extra, extraType, 0, 0, ref, refType, pos, blend, 3, ecIsAlpha, ecAlphaAssociated, refShape);
+}
+
+/* validation and tile lists (host only): { tiles, list entries, tile[tiles], start[tiles + 1], list[entries] } */
+JNIEXPORT jintArray JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_patchBins(JNIEnv* e, jclass k, jint h, jint w, jintArray frameType,
+        jintArray refType, jintArray pos, jintArray blend, jint nColor, jintArray ecIsAlpha, jintArray ecAlphaAssociated, jintArray refShape) {
+    (void)k;
+    jxl_patch_desc d;
+    jint* mem = patch_desc(e, pos, blend, nColor, ecIsAlpha, ecAlphaAssociated, refShape, &d);
+    if (!mem) return NULL;
+    const int n_chan = d.n_color + d.n_extra;
+    jint ft[PATCH_MAX_CHAN], rt[4 * PATCH_MAX_CHAN];
+    jintArray out = NULL;
+    jint* buf = NULL;
+    if (n_chan > PATCH_MAX_CHAN || !frameType || !refType || (*e)->GetArrayLength(e, frameType) != n_chan ||
+        (*e)->GetArrayLength(e, refType) != 4 * n_chan) {
+        bad_arg(e, "jxlatte_amd: patch plane types missing or of the wrong length");
+    } else {
+        (*e)->GetIntArrayRegion(e, frameType, 0, n_chan, ft);
+        (*e)->GetIntArrayRegion(e, refType, 0, 4 * n_chan, rt);
+        int64_t n_list = 0;
+        int32_t bad = -1;
+        int64_t n = jxl_patch_bins(&d, h, w, (const int32_t*)ft, (const int32_t*)rt, NULL, NULL, NULL, 0, 0, &n_list, &bad);
+        if (n >= 0 && 3 + 2 * n + n_list > 0x7fffffff) n = JXL_ERR_OOM;
+        if (n >= 0 && !(buf = (jint*)malloc(sizeof(jint) * (size_t)(3 + 2 * n + n_list)))) n = JXL_ERR_OOM;
+        if (n >= 0) {
+            buf[0] = (jint)n, buf[1] = (jint)n_list;
+            n = jxl_patch_bins(&d, h, w, (const int32_t*)ft, (const int32_t*)rt, (int32_t*)buf + 2, (int32_t*)buf + 2 + n, (int32_t*)buf + 3 + 2 * n, n,
+                               n_list, &n_list, &bad);
+        }
+        if (n < 0) {
+            const char* cls = n == JXL_ERR_INVALID_BITSTREAM ? "com/traneptora/jxlatte/io/InvalidBitstreamException"
+                            : n == JXL_ERR_UNSUPPORTED       ? "java/lang/UnsupportedOperationException"
+                            : n == JXL_ERR_OOM               ? "java/lang/OutOfMemoryError"
+                                                             : "java/lang/IllegalArgumentException";
+            (*e)->ThrowNew(e, (*e)->FindClass(e, cls), jxl_last_error(NULL));
+        } else if ((out = (*e)->NewIntArray(e, (jsize)(3 + 2 * n + n_list)))) {
+            (*e)->SetIntArrayRegion(e, out, 0, (jsize)(3 + 2 * n + n_list), buf);
+        }
+    }
+    free(buf);
+    free(mem);
+    return out;
+}
+
 JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_runBatch0(JNIEnv* e, jclass k, jlongArray ctxs) {
     (void)k;
     const jsize n = (*e)->GetArrayLength(e, ctxs);

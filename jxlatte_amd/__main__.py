@@ -24,6 +24,9 @@ def main(argv=None):
     ap.add_argument("--device-splines", action="store_true",
                     help="draw the splines on the device (jxl_planes_splines / jxl_stage_splines) instead of numpy on the host; "
                          "samples equal except where a float exp rounds the other way")
+    ap.add_argument("--device-patches", action="store_true",
+                    help="apply all patch positions of a frame in one kernel launch (jxl_planes_patches / jxl_stage_patches) instead "
+                         "of one blend call per position and channel; same samples")
     a = ap.parse_args(argv)
     from . import frontend
     if a.info:
@@ -36,7 +39,8 @@ def main(argv=None):
     PEAK_DETECT = {"auto": PEAK_DETECT_AUTO, "on": PEAK_DETECT_ON, "off": PEAK_DETECT_OFF}
     t0 = time.time()
     backend = DeviceBackend(a.device)
-    dec = JXLDecoder(a.input, backend=backend, sparse_coeffs=a.sparse_coeffs, device_splines=a.device_splines)
+    dec = JXLDecoder(a.input, backend=backend, sparse_coeffs=a.sparse_coeffs, device_splines=a.device_splines,
+                     device_patches=a.device_patches)
     image = dec.decode()
     if image is None:
         print("jxlatte_amd: no frames", file=sys.stderr)

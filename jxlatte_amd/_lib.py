@@ -98,6 +98,9 @@ SIGNATURES = {
     "jxl_spline_arcs": (i64, [C.POINTER(abi.SplineDesc), i32, i32, C.POINTER(abi.SplineArc), i64]),
     "jxl_stage_splines": (i32, [vp, pf3, i32, i32, C.POINTER(abi.SplineDesc)]),
     "jxl_planes_splines": (i32, [vp, C.POINTER(abi.SplineDesc)]),
+    "jxl_patch_bins": (i64, [C.POINTER(abi.PatchDesc), i32, i32, pi, pi, pi, pi, pi, i64, i64, C.POINTER(i64), pi]),
+    "jxl_stage_patches": (i32, [vp, C.POINTER(abi.PatchDesc), pv3, pi, i32, i32, pv3, pi]),
+    "jxl_planes_patches": (i32, [vp, C.POINTER(abi.PatchDesc), pv3, pi, pv3, pi]),
     "jxl_planes_shape": (i32, [vp, pi, pi]),
     "jxl_planes_download": (i32, [vp, pf3]),
     "jxl_planes_upload": (i32, [vp, pf3, i32, i32]),

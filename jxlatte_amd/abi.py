@@ -192,6 +192,41 @@ def make_spline_desc(splines, base_corr_x, base_corr_b):
     return d, (n_control, control, coeff)
 
 
+class PatchPos(C.Structure):
+    """struct jxl_patch_pos: one position of one patch, 32 bytes"""
+    _fields_ = [("y0", C.c_int32), ("x0", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("ref", C.c_int32), ("ref_y0", C.c_int32),
+                ("ref_x0", C.c_int32), ("blend", C.c_int32)]
+
+
+PATCH_POS_DTYPE = [("y0", "<i4"), ("x0", "<i4"), ("h", "<i4"), ("w", "<i4"), ("ref", "<i4"), ("ref_y0", "<i4"), ("ref_x0", "<i4"),
+                   ("blend", "<i4")]
+
+
+class PatchDesc(C.Structure):
+    """struct jxl_patch_desc (the patch stage of one frame: JXLCodestreamDecoder.computePatches)"""
+    _fields_ = [("n_pos", C.c_int32), ("pos", C.POINTER(PatchPos)), ("n_rows", C.c_int32), ("blend", C.POINTER(C.c_int32)),
+                ("n_color", C.c_int32), ("n_extra", C.c_int32), ("ec_is_alpha", C.POINTER(C.c_int32)),
+                ("ec_alpha_associated", C.POINTER(C.c_int32)), ("ref_h", C.c_int32 * 4), ("ref_w", C.c_int32 * 4)]
+
+
+def make_patch_desc(pos, blend, n_color, ec_is_alpha, ec_alpha_associated, ref_shapes):
+    """pos: record array of PATCH_POS_DTYPE in stage order; blend: int32 [n_rows][n_color + n_extra][3] (mode, alphaChannel, clamp);
+    ref_shapes: per reference slot (h, w) or None for an absent slot. Returns (desc, keepalive)."""
+    pos = np.ascontiguousarray(pos, PATCH_POS_DTYPE)
+    n_extra = len(ec_is_alpha)
+    blend = np.ascontiguousarray(blend, np.int32).reshape(-1, int(n_color) + n_extra, 3)
+    isa = np.ascontiguousarray([1 if v else 0 for v in ec_is_alpha], np.int32)
+    assoc = np.ascontiguousarray([1 if v else 0 for v in ec_alpha_associated], np.int32)
+    d = PatchDesc()
+    d.n_pos, d.pos = len(pos), pos.ctypes.data_as(C.POINTER(PatchPos))
+    d.n_rows, d.blend = blend.shape[0], ptr(blend, C.c_int32)
+    d.n_color, d.n_extra = int(n_color), n_extra
+    d.ec_is_alpha, d.ec_alpha_associated = ptr(isa, C.c_int32), ptr(assoc, C.c_int32)
+    for k in range(4):
+        d.ref_h[k], d.ref_w[k] = ref_shapes[k] if ref_shapes[k] is not None else (0, 0)
+    return d, (pos, blend, isa, assoc)
+
+
 class SqueezeParam(C.Structure):
     """struct jxl_squeeze_param (SqueezeParam.java)"""
     _fields_ = [("horizontal", C.c_int32), ("in_place", C.c_int32), ("begin_c", C.c_int32), ("num_c", C.c_int32)]

@@ -156,6 +156,10 @@ struct jxl_ctx {
     DevBuf spl;
     hipEvent_t spl_ev = nullptr;   // "the transfer has read h_spl": what the next splines call waits for before it writes
     bool spl_inflight = false;
+    // the patch stage's host-side planes on the device (jxl_stage_patches / jxl_planes_patches): the frame's planes or extra
+    // channels and the reference slots' planes back to back, uploaded per frame that has patches -- nothing is kept across
+    // frames (the decoder's reference frames alias its canvas and change under later blends). Its tables travel through h_spl.
+    DevBuf pat;
     // binned work
     // one merged launch: the segments (types) of one register class; channel >= 0: chroma-subsampled frame, one channel per launch
     struct TypeLaunch { int cls, channel; std::vector<IdctSegment> segs; };
@@ -1355,6 +1359,7 @@ void jxl_ctx_destroy(jxl_ctx* c) {
     }
     for (int i = 0; i < 3; i++) { c->rp[i].release(); c->rp_tmp[i].release(); c->rp_noise[i].release(); }
     c->spl.release();
+    c->pat.release();
     if (c->spl_ev) (void)hipEventDestroy(c->spl_ev);
     if (c->h_spl) {
         if (c->h_spl_pinned) (void)hipHostFree(c->h_spl);
@@ -2837,19 +2842,8 @@ jxl_status jxl_planes_upload(jxl_ctx* c, const float* const in[3], int32_t heigh
 namespace {
 struct SplineLaunch { const jxl_spline_arc* arcs; const int32_t *tile, *start, *list; int n_tiles, tiles_x; int64_t n_arcs, n_pairs; };
 
-// arc table + bins of `d` for a height x width frame, staged in c->h_spl and queued to c->spl by one transfer; out->n_tiles == 0:
-// nothing to draw
-jxl_status spline_tables(jxl_ctx* c, const jxl_spline_desc* d, int32_t height, int32_t width, SplineLaunch* out) {
-    memset(out, 0, sizeof *out);
-    std::vector<jxl_spline_arc> arcs;
-    const char* why = "";
-    jxl_status st = spline_arc_table(d, height, width, &arcs, &why);
-    if (st) return fail(c, st, "%s", why);
-    if (arcs.empty()) return JXL_OK;
-    SplineBins bins;
-    if (!spline_bin(arcs.data(), (int64_t)arcs.size(), height, width, &bins)) return fail(c, JXL_ERR_OOM, "splines: the tile lists do not fit");
-    const size_t off_tile = tab_up(arcs.size() * sizeof(jxl_spline_arc)), off_start = off_tile + tab_up(bins.tile.size() * 4),
-                 off_list = off_start + tab_up(bins.start.size() * 4), total = off_list + tab_up(bins.list.size() * 4);
+// the staging buffer of the spline and the patch tables: room for `total` bytes in c->h_spl once the transfer before has read it ...
+jxl_status tables_reserve(jxl_ctx* c, size_t total) {
     if (c->spl_inflight && c->spl_ev) (void)hipEventSynchronize(c->spl_ev);
     c->spl_inflight = false;
     if (total > c->h_spl_cap) {
@@ -2870,10 +2864,10 @@ jxl_status spline_tables(jxl_ctx* c, const jxl_spline_desc* d, int32_t height, i
         c->h_spl_cap = cap;
         c->h_spl_pinned = pinned;
     }
-    memcpy(c->h_spl, arcs.data(), arcs.size() * sizeof(jxl_spline_arc));
-    memcpy(c->h_spl + off_tile, bins.tile.data(), bins.tile.size() * 4);
-    memcpy(c->h_spl + off_start, bins.start.data(), bins.start.size() * 4);
-    memcpy(c->h_spl + off_list, bins.list.data(), bins.list.size() * 4);
+    return JXL_OK;
+}
+// ... and its first `total` bytes queued to c->spl by one transfer
+jxl_status tables_send(jxl_ctx* c, size_t total) {
     if (!c->spl.ensure(total)) return fail(c, JXL_ERR_OOM, "device allocation failed (spline tables)");
     HIP_TRY(c, hipMemcpyAsync(c->spl.p, c->h_spl, total, hipMemcpyHostToDevice, c->stream));
     if (c->h_spl_pinned) {
@@ -2883,6 +2877,28 @@ jxl_status spline_tables(jxl_ctx* c, const jxl_spline_desc* d, int32_t height, i
     } else {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
+    return JXL_OK;
+}
+
+// arc table + bins of `d` for a height x width frame, staged in c->h_spl and queued to c->spl by one transfer; out->n_tiles == 0:
+// nothing to draw
+jxl_status spline_tables(jxl_ctx* c, const jxl_spline_desc* d, int32_t height, int32_t width, SplineLaunch* out) {
+    memset(out, 0, sizeof *out);
+    std::vector<jxl_spline_arc> arcs;
+    const char* why = "";
+    jxl_status st = spline_arc_table(d, height, width, &arcs, &why);
+    if (st) return fail(c, st, "%s", why);
+    if (arcs.empty()) return JXL_OK;
+    SplineBins bins;
+    if (!spline_bin(arcs.data(), (int64_t)arcs.size(), height, width, &bins)) return fail(c, JXL_ERR_OOM, "splines: the tile lists do not fit");
+    const size_t off_tile = tab_up(arcs.size() * sizeof(jxl_spline_arc)), off_start = off_tile + tab_up(bins.tile.size() * 4),
+                 off_list = off_start + tab_up(bins.start.size() * 4), total = off_list + tab_up(bins.list.size() * 4);
+    if ((st = tables_reserve(c, total))) return st;
+    memcpy(c->h_spl, arcs.data(), arcs.size() * sizeof(jxl_spline_arc));
+    memcpy(c->h_spl + off_tile, bins.tile.data(), bins.tile.size() * 4);
+    memcpy(c->h_spl + off_start, bins.start.data(), bins.start.size() * 4);
+    memcpy(c->h_spl + off_list, bins.list.data(), bins.list.size() * 4);
+    if ((st = tables_send(c, total))) return st;
     char* base = c->spl.as<char>();
     out->arcs = reinterpret_cast<const jxl_spline_arc*>(base);
     out->tile = reinterpret_cast<const int32_t*>(base + off_tile);
@@ -2962,6 +2978,179 @@ extern "C" jxl_status jxl_debug_spline_kernel_ms(jxl_ctx* c, const float* const 
     (void)hipEventDestroy(ev[0]);
     (void)hipEventDestroy(ev[1]);
     return st;
+}
+
+// ---- patches: computePatches as one launch over the binned positions (patch_host.hip, k_patch.hip) ----
+namespace {
+// One run of the stage on height x width planes. dev_frame[ch] != nullptr: the plane is on the device already (the resident
+// colour planes); otherwise host_frame[ch] is uploaded if some position touches it, and downloaded if some position writes it
+// (*downloaded tells whether that happened: the call has then waited for the device). reps / ms: tools/patch_bench.py (reps
+// launches after the first, timed by events; the planes are then not brought back).
+static jxl_status patch_run(jxl_ctx* c, const jxl_patch_desc* d, int32_t height, int32_t width, void* const* host_frame, void* const* dev_frame,
+                     const int32_t* frame_type, const void* const* ref, const int32_t* ref_type, bool* downloaded, int reps = 0,
+                     float* ms = nullptr, int64_t* counts = nullptr) {
+    if (downloaded) *downloaded = false;
+    PatchStage ps;
+    const char* why = "";
+    jxl_status st = patch_compile(d, height, width, frame_type, ref_type, &ps, &why, nullptr);
+    if (st) return fail(c, st, "%s", why);
+    if (counts) counts[0] = d->n_pos, counts[1] = (int64_t)ps.bins.tile.size(), counts[2] = (int64_t)ps.bins.list.size();
+    if (ps.bins.tile.empty()) return JXL_OK;
+    const int n_chan = ps.n_chan;
+    if (!ref || (!host_frame && !dev_frame)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "patches: bad arguments");
+    // the planes some application reads or writes: only they cross the bus
+    std::vector<uint8_t> need_f((size_t)n_chan, 0), need_r((size_t)n_chan * 4, 0), seen(ps.ops.size() / (size_t)n_chan * 4, 0);
+    for (const PatchRec& r : ps.rec) {
+        if (r.y1 <= r.y0 || r.x1 <= r.x0) continue;
+        uint8_t& done = seen[(size_t)(r.ops / n_chan) * 4 + (size_t)r.slot];
+        if (done) continue;
+        done = 1;
+        for (int ch = 0; ch < n_chan; ch++) {
+            const PatchOp& o = ps.ops[(size_t)r.ops + (size_t)ch];
+            if (o.op == POP_NONE) continue;
+            need_f[(size_t)ch] = need_r[(size_t)r.slot * n_chan + ch] = 1;
+            if ((o.op == POP_BLEND || o.op == POP_MULADD) && !(o.flags & kPatchIsAlpha)) {
+                need_f[(size_t)o.alpha] = 1;
+                if (o.op == POP_BLEND) need_r[(size_t)r.slot * n_chan + o.alpha] = 1;
+            }
+        }
+    }
+    const size_t fbytes = 4 * (size_t)height * width;
+    std::vector<size_t> off_f((size_t)n_chan, 0), off_r((size_t)n_chan * 4, 0);
+    size_t total_planes = 0;
+    for (int ch = 0; ch < n_chan; ch++) {
+        if (!need_f[(size_t)ch] || (dev_frame && dev_frame[ch])) continue;
+        if (!host_frame || !host_frame[ch]) return fail(c, JXL_ERR_INVALID_ARGUMENT, "patches: a frame plane is NULL");
+        off_f[(size_t)ch] = total_planes;
+        total_planes += tab_up(fbytes);
+    }
+    for (int k = 0; k < 4; k++)
+        for (int ch = 0; ch < n_chan; ch++) {
+            const size_t i = (size_t)k * n_chan + ch;
+            if (!need_r[i] || ref_type[i] == -1) { need_r[i] = 0; continue; }
+            if (!ref[i]) return fail(c, JXL_ERR_INVALID_ARGUMENT, "patches: a reference plane is NULL but typed");
+            off_r[i] = total_planes;
+            total_planes += tab_up(4 * (size_t)d->ref_h[k] * d->ref_w[k]);
+        }
+    if (!c->pat.ensure(total_planes)) return fail(c, JXL_ERR_OOM, "device allocation failed (patch planes)");
+    char* arena = c->pat.as<char>();
+    for (int ch = 0; ch < n_chan; ch++)
+        if (need_f[(size_t)ch] && !(dev_frame && dev_frame[ch]))
+            HIP_TRY(c, hipMemcpyAsync(arena + off_f[(size_t)ch], host_frame[ch], fbytes, hipMemcpyHostToDevice, c->stream));
+    for (int k = 0; k < 4; k++)
+        for (int ch = 0; ch < n_chan; ch++) {
+            const size_t i = (size_t)k * n_chan + ch;
+            if (need_r[i]) HIP_TRY(c, hipMemcpyAsync(arena + off_r[i], ref[i], 4 * (size_t)d->ref_h[k] * d->ref_w[k], hipMemcpyHostToDevice, c->stream));
+        }
+    // the tables, back to back in the page-locked staging buffer: one transfer
+    const size_t n_tab = (size_t)n_chan * 5 + 4;
+    const size_t off_ops = tab_up(ps.rec.size() * sizeof(PatchRec)), off_tile = off_ops + tab_up(ps.ops.size() * sizeof(PatchOp)),
+                 off_start = off_tile + tab_up(ps.bins.tile.size() * 4), off_list = off_start + tab_up(ps.bins.start.size() * 4),
+                 off_planes = off_list + tab_up(ps.bins.list.size() * 4), total = off_planes + tab_up(n_tab * 8);
+    if ((st = tables_reserve(c, total))) return st;
+    memcpy(c->h_spl, ps.rec.data(), ps.rec.size() * sizeof(PatchRec));
+    memcpy(c->h_spl + off_ops, ps.ops.data(), ps.ops.size() * sizeof(PatchOp));
+    memcpy(c->h_spl + off_tile, ps.bins.tile.data(), ps.bins.tile.size() * 4);
+    memcpy(c->h_spl + off_start, ps.bins.start.data(), ps.bins.start.size() * 4);
+    memcpy(c->h_spl + off_list, ps.bins.list.data(), ps.bins.list.size() * 4);
+    int64_t* tab = reinterpret_cast<int64_t*>(c->h_spl + off_planes);
+    for (int ch = 0; ch < n_chan; ch++)
+        tab[ch] = !need_f[(size_t)ch] ? 0 : (dev_frame && dev_frame[ch]) ? (int64_t)(intptr_t)dev_frame[ch] : (int64_t)(intptr_t)(arena + off_f[(size_t)ch]);
+    for (size_t i = 0; i < (size_t)n_chan * 4; i++) tab[(size_t)n_chan + i] = need_r[i] ? (int64_t)(intptr_t)(arena + off_r[i]) : 0;
+    for (int k = 0; k < 4; k++) tab[(size_t)n_chan * 5 + (size_t)k] = d->ref_w[k];
+    if ((st = tables_send(c, total))) return st;
+    const char* base = c->spl.as<char>();
+    auto launch = [&]() {
+        launch_patches(reinterpret_cast<const int64_t*>(base + off_planes), n_chan, width, reinterpret_cast<const PatchRec*>(base),
+                       reinterpret_cast<const PatchOp*>(base + off_ops), reinterpret_cast<const int32_t*>(base + off_tile),
+                       reinterpret_cast<const int32_t*>(base + off_start), reinterpret_cast<const int32_t*>(base + off_list),
+                       (int)ps.bins.tile.size(), ps.bins.tiles_x, c->stream);
+    };
+    launch();
+    if (reps > 0) {
+        hipEvent_t ev[2];
+        HIP_TRY(c, hipEventCreate(&ev[0]));
+        if (hipEventCreate(&ev[1]) != hipSuccess) {
+            (void)hipEventDestroy(ev[0]);
+            return fail(c, JXL_ERR_DEVICE, "event creation failed");
+        }
+        (void)hipEventRecord(ev[0], c->stream);
+        for (int r = 0; r < reps; r++) launch();
+        (void)hipEventRecord(ev[1], c->stream);
+        st = finish(c);
+        if (!st && hipEventElapsedTime(ms, ev[0], ev[1]) == hipSuccess) *ms /= (float)reps;
+        (void)hipEventDestroy(ev[0]);
+        (void)hipEventDestroy(ev[1]);
+        return st;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, JXL_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
+    bool any = false;
+    for (int ch = 0; ch < n_chan; ch++) any = any || (ps.written[(size_t)ch] && !(dev_frame && dev_frame[ch]));
+    if (!any) return JXL_OK;
+    if ((st = finish(c))) return st;
+    for (int ch = 0; ch < n_chan; ch++)
+        if (ps.written[(size_t)ch] && !(dev_frame && dev_frame[ch]))
+            HIP_TRY(c, hipMemcpy(host_frame[ch], arena + off_f[(size_t)ch], fbytes, hipMemcpyDeviceToHost));
+    if (downloaded) *downloaded = true;
+    return JXL_OK;
+}
+}  // namespace
+
+int64_t jxl_patch_bins(const jxl_patch_desc* d, int32_t height, int32_t width, const int32_t* frame_type, const int32_t* ref_type, int32_t* tile,
+                       int32_t* start, int32_t* list, int64_t cap_tiles, int64_t cap_list, int64_t* n_list, int32_t* first_bad) {
+    if (!n_list || cap_tiles < 0 || cap_list < 0) return fail(nullptr, JXL_ERR_INVALID_ARGUMENT, "patches: bad arguments");
+    PatchStage ps;
+    const char* why = "";
+    const jxl_status st = patch_compile(d, height, width, frame_type, ref_type, &ps, &why, first_bad);
+    if (st) return fail(nullptr, st, "%s", why);
+    *n_list = (int64_t)ps.bins.list.size();
+    const int64_t nt = (int64_t)ps.bins.tile.size();
+    if (tile && start && list && nt <= cap_tiles && *n_list <= cap_list) {
+        for (int64_t i = 0; i < nt; i++) tile[i] = ps.bins.tile[(size_t)i];
+        for (int64_t i = 0; i <= nt; i++) start[i] = ps.bins.start[(size_t)i];
+        for (int64_t i = 0; i < *n_list; i++) list[i] = ps.bins.list[(size_t)i];
+    }
+    return nt;
+}
+
+jxl_status jxl_stage_patches(jxl_ctx* c, const jxl_patch_desc* d, void* const* frame, const int32_t* frame_type, int32_t height, int32_t width,
+                             const void* const* ref, const int32_t* ref_type) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (!frame) return fail(c, JXL_ERR_INVALID_ARGUMENT, "patches: bad arguments");
+    return patch_run(c, d, height, width, frame, nullptr, frame_type, ref, ref_type, nullptr);
+}
+
+jxl_status jxl_planes_patches(jxl_ctx* c, const jxl_patch_desc* d, void* const* extra, const int32_t* extra_type, const void* const* ref,
+                              const int32_t* ref_type) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (c->rp_h <= 0) return fail(c, JXL_ERR_STATE, "no resident planes");
+    if (!d || d->n_color != 3 || d->n_extra < 0 || (d->n_extra > 0 && (!extra || !extra_type)))
+        return fail(c, JXL_ERR_INVALID_ARGUMENT, "patches: the resident planes are three colour planes");
+    try {
+        const int n_chan = 3 + d->n_extra;
+        std::vector<void*> host((size_t)n_chan, nullptr), dev((size_t)n_chan, nullptr);
+        std::vector<int32_t> type((size_t)n_chan, 0);
+        for (int i = 0; i < 3; i++) dev[(size_t)i] = c->rp[i].p;
+        for (int e = 0; e < d->n_extra; e++) host[(size_t)(3 + e)] = extra[e], type[(size_t)(3 + e)] = extra_type[e];
+        return patch_run(c, d, c->rp_h, c->rp_w, host.data(), dev.data(), type.data(), ref, ref_type, nullptr);
+    } catch (const std::bad_alloc&) {
+        return fail(c, JXL_ERR_OOM, "patches: host allocation failed");
+    }
+}
+
+// tools/patch_bench.py: the patch kernel alone on device copies of the planes (which are not written back), by stream events:
+// mean milliseconds per launch over `reps` launches after one warm-up launch; counts[0] = positions, counts[1] = non-empty
+// tiles, counts[2] = (tile, position) list entries
+jxl_status jxl_debug_patch_kernel_ms(jxl_ctx* c, const jxl_patch_desc* d, void* const* frame, const int32_t* frame_type, int32_t height,
+                                     int32_t width, const void* const* ref, const int32_t* ref_type, int32_t reps, float* ms, int64_t counts[3]) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (!frame || reps < 1 || !ms || !counts) return fail(c, JXL_ERR_INVALID_ARGUMENT, "patch bench: bad arguments");
+    *ms = 0.0f;
+    return patch_run(c, d, height, width, frame, nullptr, frame_type, ref, ref_type, nullptr, reps, ms, counts);
 }
 
 // ---- stage-level entries -----------------------------------------------------------------------------

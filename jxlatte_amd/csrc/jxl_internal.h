@@ -392,7 +392,9 @@ void launch_noise_init(int h, int w, int group_dim, uint64_t seed0, int colors, 
                        hipStream_t s);
 void launch_noise_add(float* const planes[3], const float* const noise[3], int64_t n, const float lut[8], float bcx, float bcb,
                       hipStream_t s);
-// maps (mode, flags, is_int) to the inner blend function; -1 illegal mode, -2 int samples on a float-only function
+// the inner blend functions (k_blend's switch); blend_op maps (mode, flags, is_int) to one; -1 illegal mode, -2 int samples on a
+// float-only function
+enum BlendOp { OP_COPY_FRAME, OP_COPY_REF, OP_ADD_I, OP_ADD_F, OP_MULT, OP_BLEND, OP_MULADD };
 int blend_op(int mode, unsigned flags, int is_int);
 bool blend_needs(int op, bool* frame, bool* ref, bool* frame_alpha, bool* ref_alpha, bool is_alpha);
 void launch_blend(int op, unsigned flags, void* canvas, int cw, const void* frame, int fw, const void* ref, int rw,
@@ -419,6 +421,31 @@ struct SplineBins {
 bool spline_bin(const jxl_spline_arc* arcs, int64_t n, int32_t height, int32_t width, SplineBins* out);
 void launch_splines(float* const planes[3], int h, int w, const jxl_spline_arc* arcs, const int32_t* tile, const int32_t* start,
                     const int32_t* list, int n_tiles, int tiles_x, hipStream_t s);
+
+// ---- patches (patch_host.hip: validation, blend functions, binning -- no device call; k_patch.hip: the kernel) ----
+constexpr int kPatchTileW = 32, kPatchTileH = 8;  // footprint of one workgroup of k_patches, as k_splines'
+// one position as the kernel reads it (wave-uniform, through scalar loads): the rectangle [y0, y1) x [x0, x1) in the frame, the
+// shift (dy, dx) from a frame pixel to its sample in the slot's planes, and its PatchOp row (one op per channel)
+struct PatchRec { int32_t y0, x0, y1, x1, dy, dx, slot, ops; };
+static_assert(sizeof(PatchRec) == 32, "patch record");
+enum PatchOpKind { POP_NONE, POP_ADD_I, POP_ADD_F, POP_MULT, POP_BLEND, POP_MULADD, POP_COPY_REF };
+constexpr int kPatchIsAlpha = 1, kPatchClamp = 2, kPatchPremult = 4, kPatchBelow = 8;
+struct PatchOp { int32_t op, alpha, flags, reserved; };  // alpha: the channel number (n_color + alphaChannel) of the alpha planes
+static_assert(sizeof(PatchOp) == 16, "patch op");
+struct PatchStage {
+    int n_chan = 0;
+    std::vector<PatchRec> rec;     // [n_pos], stage order; a skipped position has an empty rectangle and is in no list
+    std::vector<PatchOp> ops;      // rows of n_chan, one row per (blend row, slot) in use
+    std::vector<uint8_t> written;  // [n_chan]: some position stores into the channel
+    SplineBins bins;               // list entries index rec
+};
+// JXL_OK, or the status of jxl_patch_bins with the reason in *why and the offending position in *first_bad (or -1)
+jxl_status patch_compile(const jxl_patch_desc* d, int32_t height, int32_t width, const int32_t* frame_type, const int32_t* ref_type,
+                         PatchStage* out, const char** why, int32_t* first_bad);
+// planes: device table of int64 -- frame plane pointers [n_chan], slot plane pointers [4][n_chan] (0: reads as zeros), slot
+// widths [4]
+void launch_patches(const int64_t* planes, int n_chan, int w, const PatchRec* rec, const PatchOp* ops, const int32_t* tile,
+                    const int32_t* start, const int32_t* list, int n_tiles, int tiles_x, hipStream_t s);
 
 void launch_idct2d_single(const float* src, float* dst, int h, int w, int transposed, const float* lut, hipStream_t s);
 void launch_fdct2d_single(const float* src, float* dst, int h, int w, const float* lut, hipStream_t s);

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "jxl_internal.h"
+#include "jxl_blend.h"
 
 namespace jxl {
 namespace {
@@ -193,8 +194,7 @@ __global__ __launch_bounds__(256) void k_noise_add(float* p0, float* p1, float* 
     }
 }
 
-// ---- blending (JXLCodestreamDecoder.java:26-40, 285-422) -------------------------------------------------
-enum BlendOp { OP_COPY_FRAME, OP_COPY_REF, OP_ADD_I, OP_ADD_F, OP_MULT, OP_BLEND, OP_MULADD };
+// ---- blending (JXLCodestreamDecoder.java:26-40, 285-422); the per-sample expressions: jxl_blend.h ----------
 struct BlendArgs {
     void* canvas;
     const void* frame;
@@ -219,32 +219,16 @@ __global__ __launch_bounds__(256) void k_blend(BlendArgs a) {
                 break;
             case OP_ADD_I: ((uint32_t*)a.canvas)[ci] = ((const uint32_t*)a.ref)[ri] + ((const uint32_t*)a.frame)[fi]; break;
             case OP_ADD_F: ((float*)a.canvas)[ci] = ((const float*)a.ref)[ri] + ((const float*)a.frame)[fi]; break;
-            case OP_MULT: {
-                float nw = ((const float*)a.frame)[fi];
-                if (a.clamp) nw = clamp_asc(nw, 0.0f, 1.0f);
-                ((float*)a.canvas)[ci] = nw * ((const float*)a.ref)[ri];
-                break;
-            }
+            case OP_MULT: ((float*)a.canvas)[ci] = blend_mult(((const float*)a.frame)[fi], ((const float*)a.ref)[ri], a.clamp); break;
             case OP_BLEND: {
                 const float oldS = ((const float*)a.ref)[ri];
                 const float newS = ((const float*)a.frame)[fi];
                 const float oldA = a.is_alpha ? oldS : a.ref_alpha[ri];
-                float newA = a.is_alpha ? newS : a.frame_alpha[fi];
-                if (a.clamp) newA = clamp_asc(newA, 0.0f, 1.0f);
-                float v;
-                if (a.is_alpha) v = oldA + newA * (1.0f - oldA);
-                else if (a.premult) v = newS + oldS * (1.0f - newA);
-                else v = (newS * newA + oldS * oldA * (1.0f - newA)) / (oldA + newA * (1.0f - oldA));
-                ((float*)a.canvas)[ci] = v;
+                const float newA = a.is_alpha ? newS : a.frame_alpha[fi];
+                ((float*)a.canvas)[ci] = blend_blend(newS, oldS, newA, oldA, a.is_alpha, a.premult, a.clamp);
                 break;
             }
-            default: {
-                const float oldS = ((const float*)a.ref)[ri];
-                const float newS = ((const float*)a.frame)[fi];
-                float newA = a.frame_alpha[fi];
-                if (a.clamp) newA = clamp_asc(newA, 0.0f, 1.0f);
-                ((float*)a.canvas)[ci] = oldS + newA * newS;
-            }
+            default: ((float*)a.canvas)[ci] = blend_muladd(((const float*)a.frame)[fi], ((const float*)a.ref)[ri], a.frame_alpha[fi], a.clamp);
         }
     }
 }

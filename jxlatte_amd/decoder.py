@@ -360,6 +360,127 @@ def put_group_sparse(hf, pass_, grp, sp):
     hf.putGroupSparseEntries(pass_, grp, ents, wide)
 
 
+# ---- the type plan of the patch stage (JXLCodestreamDecoder.blendBuffers' casts, :433-465) ------------------------
+class PatchPlan:
+    """what JXLDecoder._patches would do to the TYPES of the planes, without touching a sample (patch_type_plan)"""
+
+    def __init__(self):
+        self.calls = []       # one dict per backend.blend call, in order: i, j, d, slot, mode, pmode, below, canvas / frame_alpha /
+                              # ref_alpha (dtype, or None where the call passes None)
+        self.segments = []    # dicts: first, last (call indices, inclusive), frame (dtype per channel), ref {slot: [dtype or None]}
+        self.frame_types = None  # after the stage
+        self.ref_types = {}      # slot -> [dtype, or None for a plane still absent]; only the slots some applied patch names
+        self.created = set()     # (slot, channel): reference planes blendBuffers creates as zeros (:441-442, :449-451)
+        self.gather = True       # False: a below mode (5, 7) reads the frame away from the pixel it writes (see jxl_patch_bins)
+        self.pos = None          # the positions in stage order, abi.PATCH_POS_DTYPE (the absent-slot ones included)
+        self.blend = None        # [n_pos][colours + num_extra][3]: one blend row per position, one entry per channel
+
+
+def patch_type_plan(info, patches, frame_buffers, reference, frame_colors):
+    """Simulates JXLDecoder._patches / _blend_buffers(patch=True) over the whole list of patches (the dicts of Frontend.patch) on
+    the dtypes and shapes of `frame_buffers` and `reference` alone. blendBuffers casts planes to float as a side effect, decided
+    on the RAW patch mode compared with the frame blend constants; the casts persist in the frame's buffers and in the reference
+    slot. A cast of a plane no earlier application of the running segment handed to backend.blend commutes with those
+    applications and is hoisted to the segment's entry; a cast of a plane one of them used closes the segment. So a segment is a
+    maximal run of applications during which every plane they use keeps its type, and its entry types are the types after its
+    last application. Raises what _patches would raise by itself, before anything runs: the three InvalidBitstreamExceptions of
+    computePatches in stage order (and the IndexError / AttributeError of a malformed list)."""
+    colors = 1 if info.colour_space == CE_GRAY else 3
+    if colors != frame_colors:
+        raise ValueError("the patch plan covers frames with the image's colour count")
+    has_extra = info.num_extra > 0
+    plan = PatchPlan()
+    ft = [b.dtype for b in frame_buffers]
+    fshape = frame_buffers[0].shape
+    rt = plan.ref_types
+    f32 = np.dtype(np.float32)
+    used, first = {}, 0  # plane key -> dtype it was used with in the running segment
+    pos, rows = [], []
+
+    def close(last):
+        plan.segments.append(dict(first=first, last=last, frame=list(ft), ref={k: list(v) for k, v in rt.items()}))
+
+    for i, p in enumerate(patches):
+        for j in range(p["positions"].shape[0]):
+            pos.append((int(p["positions"][j, 0]), int(p["positions"][j, 1]), p["h"], p["w"], p["ref"], p["y0"], p["x0"], len(rows)))
+            row = np.asarray(p["blend"][j], np.int32).reshape(1 + info.num_extra, 3)
+            rows.append(row[[0] * colors + list(range(1, 1 + info.num_extra))])  # per channel d (:239)
+        if p["ref"] > 3:
+            raise InvalidBitstreamException("Patch out of range")
+        ref = reference[p["ref"]]
+        if ref is None:
+            continue
+        slot = p["ref"]
+        if p["y0"] + p["h"] > ref[0].shape[0] or p["x0"] + p["w"] > ref[0].shape[1]:
+            raise InvalidBitstreamException("Patch too large")
+        if slot not in rt:
+            rt[slot] = [None if b is None else b.dtype for b in ref]
+        r = rt[slot]
+        for j in range(p["positions"].shape[0]):
+            y0, x0 = int(p["positions"][j, 0]), int(p["positions"][j, 1])
+            if y0 < 0 or x0 < 0 or p["h"] + y0 > fshape[0] or p["w"] + x0 > fshape[1]:
+                raise InvalidBitstreamException("Patch size out of bounds")
+            for d in range(colors + info.num_extra):
+                c = 0 if d < colors else d - colors + 1
+                mode, alpha, clamp = (int(v) for v in p["blend"][j, c])
+                if mode == 0:
+                    continue
+                # -- _blend_buffers(d, ..., patch=True): the canvas is the frame plane itself
+                ex = d - colors
+                is_alpha = ex >= 0 and info.ec_type[ex] == 0
+                premult = has_extra and bool(info.ec_alpha_associated[alpha])  # noqa: F841  (an IndexError is the host path's)
+                canvas_dt = ft[d]  # the local `canvas` / `frame_buffer`: an alpha cast below does not reach it
+                if r[d] is None:
+                    r[d] = canvas_dt
+                    plan.created.add((slot, d))
+                a_ref, a_frame = colors + alpha, frame_colors + alpha
+                pmode, below = {5: (abi.BLEND_BLEND, True), 6: (abi.BLEND_MULADD, False), 7: (abi.BLEND_MULADD, True)}.get(mode, (mode - 1, False))
+                if has_extra and mode in (abi.BLEND_BLEND, abi.BLEND_MULADD):
+                    if mode == abi.BLEND_BLEND:
+                        if r[a_ref] is None:
+                            plan.created.add((slot, a_ref))
+                        r[a_ref] = f32
+                    ft[a_frame] = f32
+                fa = ra = None
+                if has_extra:
+                    ra, fa = r[a_ref], ft[a_frame]
+                should_cast = mode == abi.BLEND_MULT or (mode == abi.BLEND_BLEND and has_extra) or \
+                    (mode == abi.BLEND_MULADD and has_extra and not is_alpha)
+                if should_cast or r[d] != canvas_dt:
+                    canvas_dt = r[d] = f32
+                ft[d] = canvas_dt  # canvas_list[idx] = backend.blend(...): the result has the canvas' type
+                if below and (p["y0"] != y0 or p["x0"] != x0 or tuple(ref[0].shape) != tuple(fshape)):
+                    plan.gather = False
+                call = dict(i=i, j=j, d=d, slot=slot, mode=mode, pmode=pmode, below=below, canvas=canvas_dt,
+                            frame_alpha=fa if fa == f32 else None, ref_alpha=ra if ra == f32 else None, pos=len(pos) - p["positions"].shape[0] + j)
+                k = len(plan.calls)
+                now = {}
+                if call["frame_alpha"] is not None:
+                    now[("f", a_frame)] = f32
+                if call["ref_alpha"] is not None:
+                    now[("r", slot, a_ref)] = f32
+                now.update({("f", d): canvas_dt, ("r", slot, d): r[d]})  # (last: the call leaves its result, of the canvas' type, in plane d)
+                types = lambda key: ft[key[1]] if key[0] == "f" else rt[key[1]][key[2]]  # noqa: E731
+                if any(types(key) != dt for key, dt in used.items()):
+                    # (the segment's entry types are those BEFORE this application's casts of the planes it used: they are in `used`)
+                    seg_f, seg_r = list(ft), {s_: list(v) for s_, v in rt.items()}
+                    for key, dt in used.items():
+                        if key[0] == "f":
+                            seg_f[key[1]] = dt
+                        else:
+                            seg_r[key[1]][key[2]] = dt
+                    plan.segments.append(dict(first=first, last=k - 1, frame=seg_f, ref=seg_r))
+                    used, first = {}, k
+                used.update(now)
+                plan.calls.append(call)
+    if plan.calls:
+        close(len(plan.calls) - 1)
+    plan.frame_types = list(ft)
+    plan.pos = np.array(pos, abi.PATCH_POS_DTYPE) if pos else np.zeros(0, abi.PATCH_POS_DTYPE)
+    plan.blend = np.stack(rows) if rows else np.zeros((0, colors + info.num_extra, 3), np.int32)
+    return plan
+
+
 class DeviceBackend:
     """the product backend: HIP kernels through the C-ABI (jxlatte_amd._lib / host). No CPU fallback."""
 
@@ -427,6 +548,9 @@ class DeviceBackend:
 
     def splines(self, planes, splines, bcx, bcb):
         return self.host.renderSplines(self.ctx, planes, splines, bcx, bcb)
+
+    def patches(self, frame, ref, pos, blend, n_color, ec_is_alpha, ec_alpha_associated):
+        return self.host.computePatches(self.ctx, frame, ref, pos, blend, n_color, ec_is_alpha, ec_alpha_associated)
 
     def noise_init(self, h, w, seed0, group_dim, colors):
         return self.host.initializeNoise(self.ctx, h, w, seed0, group_dim, colors)
@@ -650,14 +774,19 @@ def _tt_dims():
 
 
 class JXLDecoder:
-    def __init__(self, source, backend=None, sparse_coeffs=False, device_splines=False):
+    def __init__(self, source, backend=None, sparse_coeffs=False, device_splines=False, device_patches=False):
         """sparse_coeffs: hand the HF coefficients to the backend as lists of non-zero entries (jxf_get_coeffs_sparse ->
         jxl_vardct_put_group_sparse), not as dense planes; same pixels.
         device_splines: Frame.renderSplines runs in the backend (jxl_planes_splines on the resident planes, jxl_stage_splines
         otherwise) instead of render_splines on the host; the samples agree except where a (float)Math.exp falls on the other
-        side of a float rounding boundary (include/jxlatte_amd.h). A backend without `splines` is an error."""
+        side of a float rounding boundary (include/jxlatte_amd.h). A backend without `splines` is an error.
+        device_patches: computePatches runs in the backend as one launch per segment of patch_type_plan (jxl_planes_patches on
+        the resident planes, jxl_stage_patches otherwise) instead of one backend.blend per (position, channel); the same bits.
+        Grey images and frames whose colour count is not the image's keep the blend calls; stats[-1]["patches"] tells. A backend
+        without `patches` is an error."""
         self.sparse_coeffs = bool(sparse_coeffs)
         self.device_splines = bool(device_splines)
+        self.device_patches = bool(device_patches)
         if isinstance(source, (bytes, bytearray, memoryview)):
             data = bytes(source)
         else:
@@ -770,14 +899,25 @@ class JXLDecoder:
                 rp = None
                 moves.append("d2h")
 
+        dev_patches = getattr(self, "device_patches", False) and bool(fr.num_patches)
         if fr.upsampling > 1:
             on_device().upsample(fr.upsampling, self._up_weights(fr.upsampling))
         if save and fr.save_before_ct:
-            on_host()
-            self.reference[fr.save_as_reference] = [b.copy() for b in buffers]
-        if fr.num_patches:
+            if dev_patches and rp is not None:  # a copy comes down, the planes stay
+                planes = rp.download()
+                moves.append("d2h")
+                self.reference[fr.save_as_reference] = [planes[c] for c in range(3)] + [b.copy() for b in buffers[3:]]
+            else:
+                on_host()
+                self.reference[fr.save_as_reference] = [b.copy() for b in buffers]
+        if dev_patches and colors == (1 if info.colour_space == CE_GRAY else 3):
+            if not self._patches_device(fr, buffers, colors, (on_device, on_host, lambda: rp)):
+                on_host()
+                self._patches(fr, buffers, colors)
+        elif fr.num_patches:
             on_host()
             self._patches(fr, buffers, colors)
+            self.stats[-1]["patches"] = dict(path="blend calls")
         if fr.has_splines and getattr(self, "device_splines", False):
             on_device().splines(self.fe.splines(), fr.base_corr_x, fr.base_corr_b)
         elif fr.has_splines:
@@ -988,6 +1128,93 @@ class JXLDecoder:
                     self._blend_buffers(d, frame_buffers, ref, (y0, x0), (y0, x0), (p["y0"], p["x0"]), (p["h"], p["w"]),
                                         frame_colors, mode, alpha, bool(clamp), patch=True, canvas_list=frame_buffers)
 
+    def _patches_device(self, fr, buffers, colors, tail):
+        """computePatches as one backend call per segment of patch_type_plan. `tail`: _chained_tail's (on_device, on_host,
+        resident planes or None) when the backend keeps planes resident -- a segment whose colour planes are float then runs on
+        them (jxl_planes_patches), one whose colour planes are integer on the host arrays (jxl_stage_patches); None: the stage
+        entry only. Leaves `buffers` and self.reference[...] as _patches would: values, dtypes, absent reference planes
+        replaced by zero planes. False (nothing touched): the plan holds an application the in-place launch cannot replay;
+        the caller runs _patches."""
+        info, be = self.info, self.backend
+        f32 = np.dtype(np.float32)
+        n_chan = colors + info.num_extra
+        rp = tail[2]() if tail else None
+        shape = rp.shape if rp is not None else buffers[0].shape
+        stand_in = [np.broadcast_to(F(0), shape) if (rp is not None and c < 3) else buffers[c] for c in range(n_chan)]
+        plan = patch_type_plan(info, [self.fe.patch(i) for i in range(fr.num_patches)], stand_in, self.reference, colors)
+        st = self.stats[-1]["patches"] = dict(path="none", positions=len(plan.pos), applications=len(plan.calls), segments=len(plan.segments))
+        if not plan.calls:
+            return True
+        if not plan.gather:
+            st["path"] = "blend calls (a below mode reads the frame off its own pixel)"
+            return False
+        is_alpha = [t == 0 for t in info.ec_type[:info.num_extra]]
+        assoc = [bool(v) for v in info.ec_alpha_associated[:info.num_extra]]
+        ref_shapes = [None if self.reference[k] is None else tuple(self.reference[k][0].shape) for k in range(4)]
+        call_pos = np.array([c["pos"] for c in plan.calls]), np.array([c["d"] for c in plan.calls])
+
+        def seg_blend(seg):  # the blend rows with the modes of the applications outside the segment set to 0
+            if len(plan.segments) == 1:
+                return plan.blend
+            b = plan.blend.copy()
+            b[:, :, 0] = 0
+            sl = slice(seg["first"], seg["last"] + 1)
+            b[call_pos[0][sl], call_pos[1][sl], 0] = plan.blend[call_pos[0][sl], call_pos[1][sl], 0]
+            return b
+
+        def code(dt):
+            return -1 if dt is None else 0 if dt == f32 else 1
+        if len(plan.segments) > 1:  # every segment is checked before the first one runs (a single one: the entry does it)
+            from . import host as _host
+            for seg in plan.segments:
+                rtypes = [[-1] * n_chan if k not in seg["ref"] or self.reference[k] is None else
+                          [-1 if (k, n) in plan.created or self.reference[k][n] is None else code(seg["ref"][k][n]) for n in range(n_chan)]
+                          for k in range(4)]
+                _host.patch_bins(plan.pos, seg_blend(seg), colors, is_alpha, assoc, shape[0], shape[1],
+                                             [code(t) for t in seg["frame"]], ref_shapes, rtypes)
+        paths = set()
+        for seg in plan.segments:
+            # blendBuffers' casts, hoisted to the segment's entry (the reference's ImageBuffer.castToFloat: _to_float)
+            resident = tail is not None and all(seg["frame"][c] == f32 for c in range(3))
+            if tail and not resident:
+                tail[1]()
+            rp = tail[2]() if tail else None
+            for n in range(n_chan):
+                if rp is not None and n < 3:
+                    continue
+                if buffers[n].dtype != seg["frame"][n]:
+                    if seg["frame"][n] != f32:
+                        raise ValueError("blend: this mode works on float samples")  # (blendBlend on an int alpha plane that is its own alpha)
+                    buffers[n] = self._to_float(buffers[n], self._depth_of(n))
+                buffers[n] = np.ascontiguousarray(buffers[n])
+            for k, types in seg["ref"].items():
+                lst = self.reference[k]
+                for n in range(n_chan):
+                    if lst[n] is not None and types[n] == f32 and lst[n].dtype != f32:
+                        lst[n] = self._to_float(lst[n], self._depth_of(n))
+            ref = [self.reference[k] if k in seg["ref"] else None for k in range(4)]
+            blend = seg_blend(seg)
+            if resident:
+                tail[0]().patches(buffers[3:], ref, plan.pos, blend, is_alpha, assoc)
+                paths.add("resident planes")
+            else:
+                be.patches(buffers, ref, plan.pos, blend, colors, is_alpha, assoc)
+                paths.add("stage entry")
+        st["path"] = " + ".join(sorted(paths))
+        # what the casts and `new ImageBuffer`s of blendBuffers leave behind in planes no application used
+        rp = tail[2]() if tail else None
+        for n in range(n_chan):
+            if not (rp is not None and n < 3) and buffers[n].dtype != plan.frame_types[n]:
+                buffers[n] = self._to_float(buffers[n], self._depth_of(n))
+        for k, types in plan.ref_types.items():
+            lst = self.reference[k]
+            for n in range(n_chan):
+                if lst[n] is None and types[n] is not None:
+                    lst[n] = np.zeros(shape, types[n])
+                elif lst[n] is not None and lst[n].dtype != types[n]:
+                    lst[n] = self._to_float(lst[n], self._depth_of(n))
+        return True
+
     # -- the decode loop (JXLCodestreamDecoder.decode :546-677) ----------------------------------------------------
     def decode(self):
         info, be = self.info, self.backend
@@ -1094,8 +1321,10 @@ class JXLDecoder:
                 noise = be.noise_init(h, w, (self.visibleFrames << 32) | self.invisibleFrames, fr.group_dim, colors)
             if not resident and save and fr.save_before_ct:
                 self.reference[fr.save_as_reference] = [b.copy() for b in buffers]
-            if not resident:
-                self._patches(fr, buffers, colors)
+            if not resident and fr.num_patches:
+                if not (getattr(self, "device_patches", False) and colors == 3 and colors_img == 3 and self._patches_device(fr, buffers, colors, None)):
+                    self._patches(fr, buffers, colors)
+                    self.stats[-1].setdefault("patches", dict(path="blend calls"))
             if not resident and fr.has_splines:  # Frame.renderSplines (host-side, as in the reference)
                 for c in range(3):
                     buffers[c] = self._to_float(buffers[c], info.bits_per_sample).copy()

@@ -503,6 +503,20 @@ class ResidentPlanes:
         d, keep = abi.make_spline_desc(splines, baseCorrelationX, baseCorrelationB)
         self.ctx.call("jxl_planes_splines", C.byref(d))
 
+    def patches(self, extras, ref, pos, blend, ec_is_alpha, ec_alpha_associated):
+        """computePatches on the resident colour planes (jxl_planes_patches): after upsample, before the splines. extras: the
+        frame's extra channels (C-contiguous host planes; those a position writes are updated in place); ref as for
+        computePatches, with 3 + len(extras) planes per slot"""
+        n_chan = 3 + len(extras)
+        ft = np.array([0, 0, 0] + [_patch_type(a) for a in extras], np.int32)
+        for a in extras:
+            if not a.flags["C_CONTIGUOUS"] or a.shape != self.shape:
+                raise ValueError("dense extra channels of the resident planes' size")
+        desc, pp, rt, keep = _patch_call_args(ft, n_chan, ref, pos, blend, 3, ec_is_alpha, ec_alpha_associated)
+        ep = (C.c_void_p * max(1, len(extras)))(*[_vp(a) for a in extras])
+        et = np.ascontiguousarray(ft[3:]) if len(extras) else np.zeros(1, np.int32)
+        self.ctx.call("jxl_planes_patches", C.byref(desc), ep, abi.iptr(et), pp, abi.iptr(rt))
+
     def invertXYB(self, matrix, opsin_bias, cbrt_opsin_bias, intensityTarget):
         m = OpsinInverseMatrix(matrix, opsin_bias, cbrt_opsin_bias)
         self.ctx.call("jxl_planes_xyb", abi.f9(*m.matrix), abi.f3(*m.opsinBias), abi.f3(*m.cbrtOpsinBias), C.c_float(intensityTarget))
@@ -720,6 +734,83 @@ def renderSplines(ctx, planes, splines, baseCorrelationX, baseCorrelationB):
     d, keep = abi.make_spline_desc(splines, baseCorrelationX, baseCorrelationB)
     ctx.call("jxl_stage_splines", _p3(out, C.c_float), out.shape[1], out.shape[2], C.byref(d))
     return out
+
+
+def _patch_type(a):
+    if a.dtype == np.float32:
+        return 0
+    if a.dtype == np.int32:
+        return 1
+    raise TypeError("int32 or float32 planes")
+
+
+def _patch_call_args(frame_types, n_chan, ref, pos, blend, n_color, ec_is_alpha, ec_alpha_associated):
+    """the descriptor and the reference-plane arguments of the patch entries. ref: per slot None or a list of n_chan planes (None:
+    a plane blendBuffers would create as zeros); a slot's planes have the size of its plane 0 (computePatches reads refBuffer[0]) --
+    an all-zero plane of another size (one a frame before created at ITS size) goes as NULL too. Returns (desc, ref pointer
+    array, ref type array, keepalive)."""
+    shapes, planes, types = [None] * 4, [None] * (4 * n_chan), np.full(4 * n_chan, -1, np.int32)
+    for k in range(4):
+        if ref[k] is None:
+            continue
+        if len(ref[k]) != n_chan:
+            raise ValueError("a reference slot holds %d planes, the frame %d" % (len(ref[k]), n_chan))
+        shapes[k] = tuple(ref[k][0].shape)  # (AttributeError on a missing plane 0, as in the reference's refBuffer[0].height)
+        for d, a in enumerate(ref[k]):
+            if a is None:
+                continue
+            if tuple(a.shape) != shapes[k]:
+                if a.any():
+                    raise ValueError("planes of one reference slot differ in size")
+                continue
+            planes[k * n_chan + d] = np.ascontiguousarray(a)
+            types[k * n_chan + d] = _patch_type(a)
+    desc, keep = abi.make_patch_desc(pos, blend, n_color, ec_is_alpha, ec_alpha_associated, shapes)
+    pp = (C.c_void_p * (4 * n_chan))(*[_vp(a) for a in planes])
+    return desc, pp, types, (keep, planes)
+
+
+def patch_bins(pos, blend, n_color, ec_is_alpha, ec_alpha_associated, height, width, frame_types, ref_shapes, ref_types):
+    """validation and tile binning of one frame's patch stage (jxl_patch_bins: host only, no context). frame_types[d] /
+    ref_types[k][d]: 0 float, 1 int32, -1 (reference planes) absent. Returns (tile, start, list); raises what the stage entries
+    raise, with the offending position in `.position`."""
+    from ._lib import _ERR, JxlError, load
+    lib = load()
+    desc, keep = abi.make_patch_desc(pos, blend, n_color, ec_is_alpha, ec_alpha_associated, ref_shapes)
+    ft = np.ascontiguousarray(frame_types, np.int32)
+    rt = np.ascontiguousarray(ref_types, np.int32).reshape(-1)
+    assert ft.size == n_color + len(ec_is_alpha) and rt.size == 4 * ft.size
+    n_list, bad = C.c_int64(0), C.c_int32(-1)
+
+    def call(tile, start, lst):
+        n = lib.jxl_patch_bins(C.byref(desc), height, width, abi.iptr(ft), abi.iptr(rt), abi.iptr(tile) if tile is not None else None,
+                               abi.iptr(start) if start is not None else None, abi.iptr(lst) if lst is not None else None,
+                               0 if tile is None else tile.size, 0 if lst is None else lst.size, C.byref(n_list), C.byref(bad))
+        if n < 0:
+            msg = lib.jxl_last_error(None)
+            err = _ERR.get(int(n), JxlError)(int(n), msg.decode("utf-8", "replace") if msg else "")
+            err.position = bad.value
+            raise err
+        return int(n)
+    n = call(None, None, None)
+    tile, start, lst = np.zeros(max(n, 1), np.int32), np.zeros(n + 1, np.int32), np.zeros(max(n_list.value, 1), np.int32)
+    assert call(tile, start, lst) == n
+    return tile[:n], start, lst[:n_list.value]
+
+
+def computePatches(ctx, frame, ref, pos, blend, n_color, ec_is_alpha, ec_alpha_associated):
+    """JXLCodestreamDecoder.computePatches (JXLCodestreamDecoder.java:212-254) on the frame's planes (jxl_stage_patches): frame = list
+    of C-contiguous int32 / float32 planes, updated IN PLACE and returned; the planes carry the types blendBuffers' casts would
+    have given them (decoder.patch_type_plan)"""
+    n_chan = len(frame)
+    for a in frame:
+        if not a.flags["C_CONTIGUOUS"] or a.shape != frame[0].shape:
+            raise ValueError("dense planes of one size")
+    ft = np.array([_patch_type(a) for a in frame], np.int32)
+    desc, pp, rt, keep = _patch_call_args(ft, n_chan, ref, pos, blend, n_color, ec_is_alpha, ec_alpha_associated)
+    fp = (C.c_void_p * n_chan)(*[_vp(a) for a in frame])
+    ctx.call("jxl_stage_patches", C.byref(desc), fp, abi.iptr(ft), frame[0].shape[0], frame[0].shape[1], pp, abi.iptr(rt))
+    return frame
 
 
 def blend(ctx, mode, canvas, frame, ref, rect, frameAlpha=None, refAlpha=None, isAlpha=False, hasExtra=False, clamp=False,
