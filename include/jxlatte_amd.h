@@ -488,6 +488,12 @@ jxl_status jxl_stage_gab(jxl_ctx* ctx, const float* const in[3], float* const ou
                          int32_t height, int32_t width, const float w1[3], const float w2[3]);
 /* Frame.performEdgePreservingFilter (Frame.java:544-636). inv_sigma: [ceil(h/8)][ceil(w/8)]
  * map for VarDCT, or NULL to use the constant inv_sigma_modular (Frame.java:573-575). */
+/* The fused restoration launch of the frame path -- Gaborish -> EPF -> XYB in one kernel, float planes out -- on caller planes
+ * of ANY height x width >= 8 (the frame path reaches it with padded sizes only). hf_mul / sharpness: ceil(height / 8) x
+ * ceil(width / 8) cell maps (needed when epf_iters > 0); of `params` the restoration and colour fields are read (gab, gab_w1/2,
+ * epf_*, global_scale_f, xyb, opsin_*, intensity_target); stages, transfer and out_format are ignored. */
+jxl_status jxl_stage_restore_fused(jxl_ctx* ctx, const float* const in[3], float* const out[3], int32_t height, int32_t width,
+                                   const int32_t* hf_mul, const int32_t* sharpness, const jxl_vardct_params* params);
 jxl_status jxl_stage_epf(jxl_ctx* ctx, const float* const in[3], float* const out[3],
                          int32_t height, int32_t width, int32_t iterations,
                          const float* inv_sigma, float inv_sigma_modular,

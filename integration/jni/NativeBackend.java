@@ -115,6 +115,10 @@ public final class NativeBackend implements AutoCloseable {
     public native void stageFdct2d(ByteBuffer src, ByteBuffer dst, int h, int w);                      // jxl_stage_fdct2d (MathHelper.forwardDCT2D)
     public native void stageGab(ByteBuffer i0, ByteBuffer i1, ByteBuffer i2, ByteBuffer o0, ByteBuffer o1, ByteBuffer o2, int h, int w,
         float[] w1, float[] w2);                                   // jxl_stage_gab (Frame.performGabConvolution)
+    /** jxl_stage_restore_fused: Gaborish, EPF and XYB as the frame path's one fused launch on planes of any size from 8 x 8; hfMul and
+     *  sharpness are ceil(h / 8) x ceil(w / 8) int maps (may be null without EPF), params a direct buffer holding jxl_vardct_params */
+    public native void stageRestoreFused(ByteBuffer i0, ByteBuffer i1, ByteBuffer i2, ByteBuffer o0, ByteBuffer o1, ByteBuffer o2, int h, int w,
+                                         ByteBuffer hfMul, ByteBuffer sharpness, ByteBuffer params);
     public native void stageEpf(ByteBuffer i0, ByteBuffer i1, ByteBuffer i2, ByteBuffer o0, ByteBuffer o1, ByteBuffer o2, int h, int w,
         int iterations, ByteBuffer invSigma, float invSigmaModular, float[] channelScale, float pass0SigmaScale, float pass2SigmaScale,
         float borderSadMul);                                       // jxl_stage_epf (Frame.performEdgePreservingFilter)

@@ -896,6 +896,25 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageEpf(JN
     CHECK(jxl_stage_epf(c, in, out, h, w, iterations, (const float*)ADDR(invSigma), invSigmaModular, cs, pass0, pass2, borderSadMul));
 }
 
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageRestoreFused(JNIEnv* e, jobject self, jobject i0, jobject i1, jobject i2,
+        jobject o0, jobject o1, jobject o2, jint h, jint w, jobject hfMul, jobject sharpness, jobject params) {
+    jxl_ctx* c = ctx_of(e, self);
+    const float* in[3] = {(const float*)ADDR(i0), (const float*)ADDR(i1), (const float*)ADDR(i2)};
+    float* out[3] = {(float*)ADDR(o0), (float*)ADDR(o1), (float*)ADDR(o2)};
+    jxl_vardct_params p;
+    const void* src = params ? (*e)->GetDirectBufferAddress(e, params) : NULL;
+    if (!src || (*e)->GetDirectBufferCapacity(e, params) < (jlong)sizeof p) {
+        bad_arg(e, "jxlatte_amd: stageRestoreFused needs a direct buffer holding jxl_vardct_params");
+        return;
+    }
+    memcpy(&p, src, sizeof p);
+    NEED(i0, 4 * area(h, w)); NEED(i1, 4 * area(h, w)); NEED(i2, 4 * area(h, w));
+    NEED(o0, 4 * area(h, w)); NEED(o1, 4 * area(h, w)); NEED(o2, 4 * area(h, w));
+    NEED_OPT(hfMul, 4 * area(((jlong)h + 7) / 8, ((jlong)w + 7) / 8));
+    NEED_OPT(sharpness, 4 * area(((jlong)h + 7) / 8, ((jlong)w + 7) / 8));
+    CHECK(jxl_stage_restore_fused(c, in, out, h, w, (const int32_t*)ADDR(hfMul), (const int32_t*)ADDR(sharpness), &p));
+}
+
 JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageEpfSigma(JNIEnv* e, jobject self, jobject hfMul, jobject sharpness, jint bh,
         jint bw, jfloat globalScale, jfloatArray sharpLut, jobject invSigma) {
     jxl_ctx* c = ctx_of(e, self);

@@ -111,6 +111,7 @@ SIGNATURES = {
     "jxl_stage_idct2d": (i32, [vp, pf, pf, i32, i32, i32]),
     "jxl_stage_fdct2d": (i32, [vp, pf, pf, i32, i32]),
     "jxl_stage_gab": (i32, [vp, pf3, pf3, i32, i32, pf, pf]),
+    "jxl_stage_restore_fused": (i32, [vp, pf3, pf3, i32, i32, pi, pi, C.POINTER(abi.VarDCTParams)]),
     "jxl_stage_epf": (i32, [vp, pf3, pf3, i32, i32, i32, pf, f32, pf, f32, f32, f32]),
     "jxl_stage_epf_sigma": (i32, [vp, pi, pi, i32, i32, f32, pf, pf]),
     "jxl_stage_lf_dequant": (i32, [vp, C.POINTER(abi.LFQuantDesc), f32, f32, i32, pf3]),

@@ -1474,6 +1474,7 @@ jxl_status jxl_vardct_begin_frame(jxl_ctx* c, const jxl_vardct_params* p) {
     c->sp_rej_live = false;
     c->grp_written.assign((size_t)ceil_div(c->W, 256) * ceil_div(c->H, 256), 0);
     c->ev_runs = 0;
+    c->kev_valid = false;
     c->result[0] = c->result[1] = c->result[2] = nullptr;
     tm.mark("host vectors");
     return JXL_OK;
@@ -2190,12 +2191,34 @@ jxl_status jxl_vardct_enable_stage_timing(jxl_ctx* c, int32_t on) {
     if (!c) return JXL_ERR_INVALID_ARGUMENT;
     c->timing = on != 0;
     c->ev_runs = 0;
+    c->kev_valid = false;
     return JXL_OK;
 }
 
 }  // extern "C"
 
 namespace {
+// the restoration kernels' parameter block for the stages that run (run_frame, jxl_stage_restore_fused)
+void fill_restore_params(jxl_ctx* c, const jxl_vardct_params& p, bool do_gab, bool do_epf, bool do_xyb, bool do_out, RestoreParams& rp) {
+    rp.gab = do_gab; rp.epf_iters = do_epf ? p.epf_iters : 0; rp.xyb = do_xyb;
+    rp.transfer = !do_out ? JXL_TRANSFER_NONE : p.transfer == JXL_TRANSFER_PQ_EXACT ? JXL_TRANSFER_PQ : p.transfer;
+    rp.max_value = do_out ? out_max_value(p.out_format) : 0;
+    rp.out_elem = do_out ? out_elem_size(p.out_format) : 4;
+    rp.interleaved = do_out && out_interleaved(p.out_format);
+    for (int i = 0; i < 3; i++) {
+        const float mult = 1.0f / (1.0f + 4.0f * (p.gab_w1[i] + p.gab_w2[i]));  // Frame.java:510-517
+        rp.gab_base[i] = mult; rp.gab_adj[i] = p.gab_w1[i] * mult; rp.gab_diag[i] = p.gab_w2[i] * mult;
+        rp.epf[i] = make_epf(p.epf_channel_scale, p.epf_pass0_sigma_scale, p.epf_pass2_sigma_scale, p.epf_border_sad_mul, i, 0.0f);
+    }
+    rp.xybp = make_xyb(p.opsin_matrix, p.opsin_bias, p.cbrt_opsin_bias, p.intensity_target);
+    rp.global_scale_f = p.global_scale_f;
+    rp.pq_tab = p.transfer == JXL_TRANSFER_PQ_EXACT ? nullptr : c->pq_tab.as<float>();  // _EXACT: the double-precision form
+    rp.srgb8_tab = c->srgb8_tab.as<float>();
+    rp.pq16_thr = do_out ? pq16_thresholds_for(c, p.transfer, out_max_value(p.out_format)) : nullptr;
+    rp.srgb16_tab = do_out ? srgb16_table_for(c, p.transfer, out_max_value(p.out_format)) : nullptr;
+    memcpy(rp.sharp_lut, p.epf_sharp_lut, sizeof rp.sharp_lut);
+}
+
 // the frame pipeline; idct_done: the IDCT stage of this frame has already been enqueued (batched launch); collect: the
 // fused restoration launch is not enqueued here, its argument block is handed back instead (*collected = true if it was)
 jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, bool* collected = nullptr) {
@@ -2333,25 +2356,10 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
     // sharpness range check of Frame.java:565-566 (host side: the maps came through the host; scanned by finalize_tables)
     if (do_epf && c->sharp_is_bad) return fail(c, JXL_ERR_INVALID_BITSTREAM, "Invalid EPF Sharpness: %d", c->sharp_bad);
     bool fused = false;
+    c->kev_valid = false;  // only the single-launch fused kernel of THIS run makes its event pair readable (stage-masked, split and batch runs do not)
     if (do_gab || do_epf || do_xyb || do_out) {
         RestoreParams rp{};
-        rp.gab = do_gab; rp.epf_iters = do_epf ? p.epf_iters : 0; rp.xyb = do_xyb;
-        rp.transfer = !do_out ? JXL_TRANSFER_NONE : p.transfer == JXL_TRANSFER_PQ_EXACT ? JXL_TRANSFER_PQ : p.transfer;
-        rp.max_value = do_out ? out_max_value(p.out_format) : 0;
-        rp.out_elem = do_out ? out_elem_size(p.out_format) : 4;
-        rp.interleaved = do_out && out_interleaved(p.out_format);
-        for (int i = 0; i < 3; i++) {
-            const float mult = 1.0f / (1.0f + 4.0f * (p.gab_w1[i] + p.gab_w2[i]));  // Frame.java:510-517
-            rp.gab_base[i] = mult; rp.gab_adj[i] = p.gab_w1[i] * mult; rp.gab_diag[i] = p.gab_w2[i] * mult;
-            rp.epf[i] = make_epf(p.epf_channel_scale, p.epf_pass0_sigma_scale, p.epf_pass2_sigma_scale, p.epf_border_sad_mul, i, 0.0f);
-        }
-        rp.xybp = make_xyb(p.opsin_matrix, p.opsin_bias, p.cbrt_opsin_bias, p.intensity_target);
-        rp.global_scale_f = p.global_scale_f;
-        rp.pq_tab = p.transfer == JXL_TRANSFER_PQ_EXACT ? nullptr : c->pq_tab.as<float>();  // _EXACT: the double-precision form
-        rp.srgb8_tab = c->srgb8_tab.as<float>();
-        rp.pq16_thr = do_out ? pq16_thresholds_for(c, p.transfer, out_max_value(p.out_format)) : nullptr;
-        rp.srgb16_tab = do_out ? srgb16_table_for(c, p.transfer, out_max_value(p.out_format)) : nullptr;
-        memcpy(rp.sharp_lut, p.epf_sharp_lut, sizeof rp.sharp_lut);
+        fill_restore_params(c, p, do_gab, do_epf, do_xyb, do_out, rp);
         void* dst[3];
         for (int i = 0; i < 3; i++) dst[i] = do_out ? c->outbuf[i].p : (void*)oth[i];
         const float* src[3] = {cur[0], cur[1], cur[2]};
@@ -3257,6 +3265,52 @@ jxl_status jxl_stage_epf(jxl_ctx* c, const float* const in[3], float* const out[
     }
     if ((st = finish(c))) return st;
     for (int i = 0; i < 3; i++) HIP_TRY(c, hipMemcpy(out[i], cur[i], 4 * n, hipMemcpyDeviceToHost));
+    return JXL_OK;
+}
+
+jxl_status jxl_stage_restore_fused(jxl_ctx* c, const float* const in[3], float* const out[3], int32_t height, int32_t width,
+                                   const int32_t* hf_mul, const int32_t* sharpness, const jxl_vardct_params* p) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (!in || !out || !p || height < 8 || width < 8) return fail(c, JXL_ERR_INVALID_ARGUMENT, "restore: planes of at least 8x8");
+    const bool do_gab = p->gab != 0, do_epf = p->epf_iters > 0, do_xyb = p->xyb != 0;
+    if (p->epf_iters < 0 || p->epf_iters > 3 || (do_epf && (!hf_mul || !sharpness))) return fail(c, JXL_ERR_INVALID_ARGUMENT, "restore: bad EPF arguments");
+    const size_t n = (size_t)height * width, cells = (size_t)((height + 7) >> 3) * ((width + 7) >> 3);
+    if (do_epf)
+        for (size_t i = 0; i < cells; i++)
+            if (sharpness[i] < 0 || sharpness[i] > 7) return fail(c, JXL_ERR_INVALID_BITSTREAM, "Invalid EPF Sharpness: %d", sharpness[i]);  // Frame.java:565-566
+    Tmp t;
+    float* a[3];
+    float* b[3];
+    float* m[3];
+    for (int i = 0; i < 3; i++) {
+        a[i] = t.up(in[i], n);
+        b[i] = t.up<float>(nullptr, n);
+        m[i] = t.up<float>(nullptr, n);
+        if (!a[i] || !b[i] || !m[i]) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    }
+    int32_t* dhf = do_epf ? t.up(hf_mul, cells) : nullptr;
+    int32_t* dsh = do_epf ? t.up(sharpness, cells) : nullptr;
+    if (do_epf && (!dhf || !dsh)) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    RestoreParams rp{};
+    fill_restore_params(c, *p, do_gab, do_epf, do_xyb, false, rp);
+    const float* src[3] = {a[0], a[1], a[2]};
+    void* dst[3] = {b[0], b[1], b[2]};
+    bool ok;
+    if (epf3_split_on() && rp.epf_iters == 3) {  // as run_frame: the 13-tap iteration alone, then the two-iteration kernel
+        RestoreParams ra = rp, rb = rp;
+        ra.epf_iters = 4;
+        ra.xyb = 0;
+        rb.gab = 0; rb.epf_iters = 2;
+        void* mid[3] = {m[0], m[1], m[2]};
+        const float* mids[3] = {m[0], m[1], m[2]};
+        ok = launch_restore_fused(src, mid, height, width, dhf, dsh, ra, c->stream) && launch_restore_fused(mids, dst, height, width, dhf, dsh, rb, c->stream);
+    } else {
+        ok = launch_restore_fused(src, dst, height, width, dhf, dsh, rp, c->stream);
+    }
+    if (!ok) return fail(c, JXL_ERR_INVALID_ARGUMENT, "restore: the fused kernel does not take these arguments");
+    if ((st = finish(c))) return st;
+    for (int i = 0; i < 3; i++) HIP_TRY(c, hipMemcpy(out[i], b[i], 4 * n, hipMemcpyDeviceToHost));
     return JXL_OK;
 }
 

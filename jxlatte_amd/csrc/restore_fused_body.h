@@ -35,6 +35,7 @@
 #include <algorithm>
 #include "restore_sink.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace jxl {
 
@@ -109,17 +110,16 @@ __device__ __forceinline__ void epf_patch(const float* __restrict__ src, int ry,
         // terms |P(p+k) - P(p+1+k)| * s in the same channel-major, cross-minor order (likewise south/north). So a
         // patch needs one chain per horizontally / vertically adjacent pixel PAIR, not one per (pixel, tap):
         //   hc[py][j] = distance between (py, j-1) and (py, j), j = 0..4;  vc[i][px] = between (i-1, px) and (i, px), i = 0..PH
+        //
+        // A chain STARTS at its first term t0 = |a - b| * s instead of at 0 + t0 (the first channel is peeled off the channel loop for
+        // that: no zero-filled accumulators, one add less per chain). Bit-identical where it can matter: 0 + t0 == t0 for every t0
+        // but -0 (NaNs keep their payload through the add), and |a - b| * s is -0 only for s < 0 or s == -0 with a == b. The chain
+        // then differs from the reference's only when EVERY term is a zero, and only in that zero's sign; the one use of a chain is
+        // v = 1 - dist * bmul * sigma_scale * s_inv, where a zero of either sign gives the same product magnitude (0, or NaN if a
+        // factor is not finite) and 1 - (+-0) is exactly 1. Every non-zero sum sees the same operands in the same order.
         float hc[PH][5], vc[PH + 1][4];
-#pragma unroll
-        for (int py = 0; py < PH; py++)
-#pragma unroll
-            for (int j = 0; j < 5; j++) hc[py][j] = 0.0f;
-#pragma unroll
-        for (int i = 0; i <= PH; i++)
-#pragma unroll
-            for (int px = 0; px < 4; px++) vc[i][px] = 0.0f;
-#pragma unroll 1
-        for (int c = 0; c < 3; c++) {
+        auto chain_channel = [&](int c, auto first_channel) {
+            constexpr bool FIRST = decltype(first_channel)::value;
             float nb[NH * NW];
             const float* pc = src + c * PLANE + (ry - R) * SW + (rx - R);
 #pragma unroll
@@ -132,12 +132,15 @@ __device__ __forceinline__ void epf_patch(const float* __restrict__ src, int ry,
 #pragma unroll
                 for (int j = 0; j < 5; j++) {
                     const int cy = py + R, cx = j - 1 + R;
-                    if (ITER == 2) hc[py][j] = hc[py][j] + adiff<NW>(nb, cy * NW + cx, cy * NW + cx + 1, sc);
-                    else
+                    if (ITER == 2) {
+                        const float t = adiff<NW>(nb, cy * NW + cx, cy * NW + cx + 1, sc);
+                        hc[py][j] = FIRST ? t : hc[py][j] + t;
+                    } else
 #pragma unroll
                         for (int q = 0; q < 5; q++) {
                             const int u = (cy + QY[q]) * NW + cx + QX[q];
-                            hc[py][j] = hc[py][j] + adiff<NW>(nb, u, u + 1, sc);
+                            const float t = adiff<NW>(nb, u, u + 1, sc);
+                            hc[py][j] = (FIRST && q == 0) ? t : hc[py][j] + t;
                         }
                 }
             constexpr int I0 = 0;
@@ -146,15 +149,21 @@ __device__ __forceinline__ void epf_patch(const float* __restrict__ src, int ry,
 #pragma unroll
                 for (int px = 0; px < 4; px++) {
                     const int cy = i - 1 + R, cx = px + R;
-                    if (ITER == 2) vc[i][px] = vc[i][px] + adiff<NW>(nb, cy * NW + cx, (cy + 1) * NW + cx, sc);
-                    else
+                    if (ITER == 2) {
+                        const float t = adiff<NW>(nb, cy * NW + cx, (cy + 1) * NW + cx, sc);
+                        vc[i][px] = FIRST ? t : vc[i][px] + t;
+                    } else
 #pragma unroll
                         for (int q = 0; q < 5; q++) {
                             const int u = (cy + QY[q]) * NW + cx + QX[q];
-                            vc[i][px] = vc[i][px] + adiff<NW>(nb, u, u + NW, sc);
+                            const float t = adiff<NW>(nb, u, u + NW, sc);
+                            vc[i][px] = (FIRST && q == 0) ? t : vc[i][px] + t;
                         }
                 }
-        }
+        };
+        chain_channel(0, std::true_type{});
+#pragma unroll 1
+        for (int c = 1; c < 3; c++) chain_channel(c, std::false_type{});
 #pragma unroll
         for (int py = 0; py < PH; py++)
 #pragma unroll
@@ -296,14 +305,15 @@ struct TileCtx {
 };
 
 // s_inv / border factor of the 4 x PH pixels of a patch
-template <int PH>
+// EDGE = false: the path of interior tiles (whole input tile inside the frame): no coordinate clamps
+template <int PH, bool EDGE>
 __device__ __forceinline__ void patch_sigma(int ry, int rx, const TileCtx& tc, const float* __restrict__ sig, int scy0, int scx0,
                                             const EpfParams& ep, float s_inv[4 * PH], float bmul[4 * PH]) {
     const int gx0 = tc.ix0 + rx;
     // a 4-pixel run touches at most two cells: look up the first and the last, pick per pixel. Out-of-frame
     // positions (only on edge tiles: a uniform branch) get some in-range cell; they are recomputed by the mirror fix-up.
     int cxa = (gx0 >> 3) - scx0, cxb = ((gx0 + 3) >> 3) - scx0;
-    if (tc.edge) {
+    if (EDGE) {
         cxa = (min(max(gx0, 0), tc.W - 1) >> 3) - scx0;
         cxb = (min(max(gx0 + 3, 0), tc.W - 1) >> 3) - scx0;
     }
@@ -316,7 +326,7 @@ __device__ __forceinline__ void patch_sigma(int ry, int rx, const TileCtx& tc, c
         const int gy = tc.iy0 + ry + py;
         const bool rowb = ((gy + 1) & 7) < 2;  // gy & 7 is 7 or 0
         int crow = ((gy >> 3) - scy0) * 16;
-        if (tc.edge) crow = ((min(max(gy, 0), tc.H - 1) >> 3) - scy0) * 16;
+        if (EDGE) crow = ((min(max(gy, 0), tc.H - 1) >> 3) - scy0) * 16;
         const float sa = sig[crow + cxa], sb = sig[crow + cxb];
         const uint32_t bm = rowb ? 0xfu : colb;
 #pragma unroll
@@ -332,7 +342,7 @@ __device__ __forceinline__ void patch_sigma(int ry, int rx, const TileCtx& tc, c
 // LAST: results go to the sink (colour + global store). Otherwise IN PLACE: every thread computes the one patch it owns
 // into registers, the workgroup meets at a barrier (all reads of the old values done), then the patches are written
 // back over the input. One LDS buffer instead of two doubles the workgroups a CU can hold.
-template <int ITER, typename G, bool LAST, int PH, typename Sink>
+template <int ITER, typename G, bool LAST, int PH, bool EDGE, typename Sink>
 __device__ __forceinline__ void epf_stage(float* buf, int m, const TileCtx& tc, const float* __restrict__ sig, int scy0, int scx0,
                                           const EpfParams& ep, Sink sink) {
     constexpr int SW = G::SW, PLANE = G::PLANE;
@@ -357,7 +367,7 @@ __device__ __forceinline__ void epf_stage(float* buf, int m, const TileCtx& tc, 
             if (!patch_of(g, prow, pcol)) continue;
             const int ry = m + prow * PH, rx = m + pcol * 4;
             float s_inv[4 * PH], bmul[4 * PH];
-            patch_sigma<PH>(ry, rx, tc, sig, scy0, scx0, ep, s_inv, bmul);
+            patch_sigma<PH, EDGE>(ry, rx, tc, sig, scy0, scx0, ep, s_inv, bmul);
             float res[3][4 * PH];
             epf_patch<ITER, SW, PLANE, PH>(buf, ry, rx, s_inv, bmul, ep, res);
 #pragma unroll
@@ -375,7 +385,7 @@ __device__ __forceinline__ void epf_stage(float* buf, int m, const TileCtx& tc, 
         float res[3][4 * PH];
         if (act) {
             float s_inv[4 * PH], bmul[4 * PH];
-            patch_sigma<PH>(ry, rx, tc, sig, scy0, scx0, ep, s_inv, bmul);
+            patch_sigma<PH, EDGE>(ry, rx, tc, sig, scy0, scx0, ep, s_inv, bmul);
             epf_patch<ITER, SW, PLANE, PH>(buf, ry, rx, s_inv, bmul, ep, res);
         }
         __syncthreads();
@@ -423,7 +433,8 @@ struct __attribute__((packed, aligned(4))) f2a4 {
 };
 
 // OpsinInverseMatrix.invertXYB + JXLImage.transferInPlace + ImageBuffer.castToInt0 + the global store; SK = sink kind (restore_sink.h)
-template <int SK, bool NT = false>
+// EDGE = false: every position handed over lies inside the frame (interior tiles), so the frame-bound tests go
+template <int SK, bool NT = false, bool EDGE = true>
 struct OutSink {
     const FusedArgs& a;
     const TileCtx& tc;
@@ -433,15 +444,15 @@ struct OutSink {
     // one pixel at region position (y, x)
     __device__ __forceinline__ void operator()(int y, int x, float v0, float v1, float v2) const {
         const int gy = tc.iy0 + y, gx = tc.ix0 + x;
-        if (gy >= tc.H || gx >= tc.W) return;
+        if (EDGE && (gy >= tc.H || gx >= tc.W)) return;
         colour(v0, v1, v2);
         sink_store_k<SK>(a, (uint32_t)(gy * tc.W + gx), v0, v1, v2);
     }
     // up to 4 consecutive pixels of a row (a patch row)
     __device__ __forceinline__ void row4(int y, int x, const float* r0, const float* r1, const float* r2, int nvalid) const {
         const int gy = tc.iy0 + y, gx = tc.ix0 + x;
-        if (gy >= tc.H) return;
-        const int n = min(nvalid, tc.W - gx);
+        if (EDGE && gy >= tc.H) return;
+        const int n = EDGE ? min(nvalid, tc.W - gx) : nvalid;
         if (n <= 0) return;
         float o[3][4];
 #pragma unroll
@@ -460,6 +471,10 @@ struct OutSink {
             if (i < n) sink_store_k<SK>(a, g + i, o[0][i], o[1][i], o[2][i]);
     }
 };
+
+template <bool GAB, int ITERS, int SK, int PH, bool EDGE>
+__device__ __forceinline__ void restore_epf_stages(const FusedArgs& a, float* cur, int m, const TileCtx& tc, const float* __restrict__ sig,
+                                                   int scy0, int scx0);
 
 // SK = SK_PLAIN: float planes out, no transfer function (keeps the transfer code out of the hot variant); the other sink kinds
 // fix transfer function and output format at compile time, SK_GENERIC picks them per sample at run time
@@ -610,8 +625,21 @@ __device__ __forceinline__ void restore_fused_body(const FusedArgs& a) {
         __syncthreads();
     }
 
+    // interior and edge tiles part here, at one workgroup-uniform branch: the interior path carries no coordinate clamp, no mirror
+    // fix-up and no frame-bound test in its sink
+    // (float planes only: the quantising sinks keep the one general path -- a second copy of their transfer code costs them registers)
+    if (SK != SK_PLAIN || tc.edge) restore_epf_stages<GAB, ITERS, SK, PH, true>(a, cur, m, tc, sig, scy0, scx0);
+    else restore_epf_stages<GAB, ITERS, SK, PH, false>(a, cur, m, tc, sig, scy0, scx0);
+}
+
+// the EPF iterations and the sink of one tile (after Gaborish): m = margin of the current region inside the input tile
+template <bool GAB, int ITERS, int SK, int PH, bool EDGE>
+__device__ __forceinline__ void restore_epf_stages(const FusedArgs& a, float* cur, int m, const TileCtx& tc, const float* __restrict__ sig,
+                                                   int scy0, int scx0) {
+    using G = Geo<GAB, ITERS>;
+    constexpr int NTHR = 512 / PH;
     // final sink: XYB + transfer/quantise + global store
-    const OutSink<SK, (ITERS != 4)> sink{a, tc};  // (ITERS == 4: the first half of a two-launch run -- its planes are read again at once)
+    const OutSink<SK, (ITERS != 4), EDGE> sink{a, tc};  // (ITERS == 4: the first half of a two-launch run -- its planes are read again at once)
 
     if (ITERS == 0) {
         const int mm = m;
@@ -623,24 +651,24 @@ __device__ __forceinline__ void restore_fused_body(const FusedArgs& a) {
     }
     if (ITERS == 4) {  // iteration 0 on the whole 64x32 window, straight to the sink
         m += 3;
-        epf_stage<0, G, true, PH>(cur, m, tc, sig, scy0, scx0, a.p.epf[0], sink);
+        epf_stage<0, G, true, PH, EDGE>(cur, m, tc, sig, scy0, scx0, a.p.epf[0], sink);
         return;
     }
     if (ITERS == 3) {
         m += 3;
-        epf_stage<0, G, false, PH>(cur, m, tc, sig, scy0, scx0, a.p.epf[0], sink);
-        if (tc.edge) mirror_fixup<G, NTHR>(cur, m, G::R1 + G::R2, tc);
+        epf_stage<0, G, false, PH, EDGE>(cur, m, tc, sig, scy0, scx0, a.p.epf[0], sink);
+        if (EDGE) mirror_fixup<G, NTHR>(cur, m, G::R1 + G::R2, tc);
         __syncthreads();
     }
     m += 2;
     if (ITERS >= 2) {
-        epf_stage<1, G, false, PH>(cur, m, tc, sig, scy0, scx0, a.p.epf[1], sink);
-        if (tc.edge) mirror_fixup<G, NTHR>(cur, m, G::R2, tc);
+        epf_stage<1, G, false, PH, EDGE>(cur, m, tc, sig, scy0, scx0, a.p.epf[1], sink);
+        if (EDGE) mirror_fixup<G, NTHR>(cur, m, G::R2, tc);
         __syncthreads();
         m += 1;
-        epf_stage<2, G, true, PH>(cur, m, tc, sig, scy0, scx0, a.p.epf[2], sink);
+        epf_stage<2, G, true, PH, EDGE>(cur, m, tc, sig, scy0, scx0, a.p.epf[2], sink);
     } else {
-        epf_stage<1, G, true, PH>(cur, m, tc, sig, scy0, scx0, a.p.epf[1], sink);
+        epf_stage<1, G, true, PH, EDGE>(cur, m, tc, sig, scy0, scx0, a.p.epf[1], sink);
     }
 }
 

@@ -140,6 +140,23 @@ def performEdgePreservingFilter(ctx, buffer, epfIterations, inverseSigma=None, i
     return out
 
 
+def restoreFused(ctx, buffer, params, hfMultiplier=None, sharpness=None):
+    """Gaborish -> EPF -> XYB of Frame.java:505-679 + OpsinInverseMatrix.invertXYB as the frame path's ONE fused launch, on planes of
+    any size >= 8 x 8 (float planes out); params: abi.VarDCTParams (gab, epf_*, xyb, opsin_* ... are read)"""
+    buf = _planes(buffer, np.float32)
+    out = np.empty_like(buf)
+    hf = sh = None
+    if hfMultiplier is not None:
+        hfMultiplier = np.ascontiguousarray(hfMultiplier, np.int32)
+        sharpness = np.ascontiguousarray(sharpness, np.int32)
+        cells = ((buf.shape[1] + 7) // 8, (buf.shape[2] + 7) // 8)
+        if hfMultiplier.shape != cells or sharpness.shape != cells:
+            raise ValueError("expected cell maps of shape %r" % (cells,))
+        hf, sh = abi.iptr(hfMultiplier), abi.iptr(sharpness)
+    ctx.call("jxl_stage_restore_fused", _p3(buf, C.c_float), _p3(out, C.c_float), buf.shape[1], buf.shape[2], hf, sh, C.byref(params))
+    return out
+
+
 def transfer(ctx, x, tf, maxValue=0):
     """JXLImage.transferInPlace (+ ImageBuffer.castToIntWithMax when maxValue > 0)"""
     x = np.ascontiguousarray(x, np.float32)
