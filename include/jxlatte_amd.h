@@ -168,7 +168,22 @@ jxl_status jxl_ctx_synchronize(jxl_ctx* ctx);
 /* HIP stream handle (hipStream_t) the ctx launches on; for event timing by callers. */
 void*      jxl_ctx_stream(jxl_ctx* ctx);
 /* Launch on a caller-owned HIP stream instead (e.g. several frame contexts sharing one stream, or
- * torch's current stream). The ctx no longer owns a stream after this call. */
+ * torch's current stream). The ctx no longer owns a stream after this call.
+ *
+ * Contexts put on one stream (and the context that owns it, once others have been put on it) share
+ * the planes that hold the inverse transforms' output between the two launches of jxl_vardct_run:
+ * one set per frame size and stream instead of one per context. The stream serialises their runs,
+ * and results are never kept in the shared planes, so outputs are those of private streams. What a
+ * caller should know:
+ *  - a run that uses the shared planes holds a per-stream mutex while it enqueues its launches
+ *    (microseconds), so that threads driving different contexts of one stream do not interleave;
+ *  - the inverse transforms' output of such a run is not kept. Nothing could read it before either:
+ *    stages are fixed by jxl_vardct_begin_frame, which starts every frame from zeroed planes, so a
+ *    frame opened with JXL_STAGE_IDCT clear restores zero planes on any context, shared stream or not;
+ *  - stage-masked runs whose result is that output, three EPF iterations, chroma-subsampled frames
+ *    and jxl_vardct_run_batch keep private planes;
+ *  - the environment variable JXL_SHARED_PLANES=0 (read once per process) gives every context
+ *    private planes, as if each had its own stream. */
 jxl_status jxl_ctx_set_stream(jxl_ctx* ctx, void* hip_stream);
 
 /* ---- VarDCT frame path: replaces Frame.decodePassGroups tail .. performColorTransforms */

@@ -92,6 +92,18 @@ struct HSpan {
     size_t size() const { return n; }
 };
 
+// one main stream's shared IDCT-output planes (the pool's rules: "shared intermediate planes" below)
+struct PlanePool {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int refs = 0;  // attached contexts
+    // held while a pooled run enqueues its launches: two host threads that drive contexts of one stream must not interleave the
+    // IDCT launch of one frame with the restoration launch of another (with private planes that order was harmless)
+    std::mutex run_mu;
+    struct Set { size_t bytes; void* p; int users; };  // one allocation: three planes back to back
+    std::vector<Set> sets;
+};
+
 struct jxl_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -229,6 +241,11 @@ struct jxl_ctx {
     bool kev_valid = false;           // the last timed run took the single-launch fused restoration kernel
     int ev_runs = 0;                  // runs recorded since timing was enabled
     bool owns_stream = true;
+    // shared intermediate planes (PlanePool below): the pool of the stream this context launches on, the byte size of the pooled
+    // set it holds a reference on (0: none), and the bytes of its private planeA[] as counted in g_inter_bytes
+    PlanePool* pool = nullptr;
+    size_t pool_set_bytes = 0;
+    size_t priv_a_bytes = 0;
     // fork/join side streams: the per-type IDCT kernels are independent and individually too small to fill
     // 256 CUs, so they run concurrently
     static constexpr int kAux = 12;
@@ -441,6 +458,145 @@ bool epf3_split_on() {
 }
 bool is_small(int t) { return JXL_TT[t].ph == 8 && JXL_TT[t].pw == 8; }
 bool is_large(int t) { return JXL_TT[t].ph >= 128 || JXL_TT[t].pw >= 128; }
+
+// ---- shared intermediate planes ----
+// The IDCT stage's output planes are written by one launch and read by the restoration launch behind it on the same stream; after
+// that they are dead. Contexts that launch on one main stream (jxl_ctx_set_stream) are serialised by it, so they share ONE set of
+// these planes per frame size instead of owning one each: the same addresses are rewritten frame after frame. A pool belongs to a
+// (device, main stream) pair and holds one three-plane set per SIZE CLASS = the exact byte size of a set; a set is never grown or
+// handed to another class, so no launch ever sees its planes move. A set lives while a context of its class holds a reference; it
+// is freed behind a synchronise of the stream (its last user changed size, left the stream or was destroyed). run_frame decides
+// per run whether the intermediate is provably dead (pooled) or outlives the run (the context's private planeA[], allocated on
+// first need). Results never live in a pooled set. JXL_SHARED_PLANES=0: private planes everywhere, as before.
+std::mutex g_pool_mu;  // the registry, every pool's refs and sets (taken inside run_mu, never around it)
+std::vector<PlanePool*> g_pools;
+// key of jxl_vardct_run_batch's cached argument blocks (jxl_ctx::tables_gen). Process-wide, and EVERY value a context gets comes from
+// it, so a (context, value) pair never recurs: not for a new context at a recycled address, not after an invalidation below
+std::atomic<uint64_t> g_tables_gen{0};
+std::atomic<long long> g_inter_bytes[64];  // bytes of intermediate planes allocated per device, private and pooled (jxl_debug_intermediate_bytes)
+
+bool shared_planes_on() {
+    static const bool v = !(getenv("JXL_SHARED_PLANES") && atoi(getenv("JXL_SHARED_PLANES")) == 0);
+    return v;
+}
+void inter_account(int device, long long delta) {
+    if (device >= 0 && device < 64) g_inter_bytes[device].fetch_add(delta, std::memory_order_relaxed);
+}
+// the context's private intermediate planes, (re)allocated to hold `bytes` each
+bool ensure_private_planes(jxl_ctx* c, size_t bytes) {
+    bool ok = true;
+    const void* was = c->planeA[0].p;
+    for (int i = 0; i < 3 && ok; i++) ok = c->planeA[i].ensure(bytes);
+    if (c->planeA[0].p != was) c->tables_gen = ++g_tables_gen;  // (jxl_vardct_run_batch caches argument blocks that hold these addresses)
+    const size_t now = c->planeA[0].cap + c->planeA[1].cap + c->planeA[2].cap;
+    inter_account(c->device, (long long)now - (long long)c->priv_a_bytes);
+    c->priv_a_bytes = now;
+    return ok;
+}
+void release_private_planes(jxl_ctx* c) {
+    for (int i = 0; i < 3; i++) c->planeA[i].release();
+    c->tables_gen = ++g_tables_gen;
+    inter_account(c->device, -(long long)c->priv_a_bytes);
+    c->priv_a_bytes = 0;
+}
+// a set taken out of its pool, to be freed once the registry lock has been given back (the stream's drain must not hold up
+// the pooled runs of every other stream and device)
+struct DeadSet { void* p = nullptr; hipStream_t stream = nullptr; };
+void free_dead_set(const DeadSet& d) {
+    if (!d.p) return;
+    (void)hipStreamSynchronize(d.stream);  // behind the work queued on it
+    (void)hipFree(d.p);
+}
+// g_pool_mu held. The context gives up its reference on a pooled set; the last one out unlinks it (nobody can take it any
+// more) and hands it back for free_dead_set
+DeadSet pool_drop_set_locked(jxl_ctx* c) {
+    DeadSet dead;
+    PlanePool* pl = c->pool;
+    if (!pl || !c->pool_set_bytes) return dead;
+    for (size_t i = 0; i < pl->sets.size(); i++)
+        if (pl->sets[i].bytes == c->pool_set_bytes) {
+            if (--pl->sets[i].users <= 0) {
+                dead.p = pl->sets[i].p;
+                dead.stream = pl->stream;
+                inter_account(pl->device, -(long long)pl->sets[i].bytes);
+                pl->sets.erase(pl->sets.begin() + (long)i);
+            }
+            break;
+        }
+    c->pool_set_bytes = 0;
+    return dead;
+}
+// the caller has synchronised the context's stream (jxl_ctx_set_stream, jxl_ctx_destroy)
+void pool_detach(jxl_ctx* c) {
+    if (!c->pool) return;
+    DeadSet dead;
+    {
+        std::lock_guard<std::mutex> lk(g_pool_mu);
+        dead = pool_drop_set_locked(c);
+        PlanePool* pl = c->pool;
+        c->pool = nullptr;
+        if (--pl->refs <= 0) {
+            g_pools.erase(std::remove(g_pools.begin(), g_pools.end(), pl), g_pools.end());
+            delete pl;
+        }
+    }
+    free_dead_set(dead);
+}
+// The pool of the stream the context launches on, or null. A context handed a stream (jxl_ctx_set_stream) creates the pool; a
+// context that owns its stream joins the pool once OTHER contexts have been put on that stream (it is then serialised with them
+// like any of them), and keeps private planes, exactly as before, as long as it is alone on it.
+PlanePool* pool_lookup_locked(jxl_ctx* c);
+PlanePool* pool_of(jxl_ctx* c) {
+    if (c->pool || !shared_planes_on()) return c->pool;
+    PlanePool* pl;
+    {
+        std::lock_guard<std::mutex> lk(g_pool_mu);
+        pl = pool_lookup_locked(c);
+    }
+    if (pl && c->priv_a_bytes) {  // private planes from before the attachment: nothing uses them once the stream has drained
+        (void)hipStreamSynchronize(c->stream);
+        release_private_planes(c);
+    }
+    return pl;
+}
+PlanePool* pool_lookup_locked(jxl_ctx* c) {
+    PlanePool* pl = nullptr;
+    for (PlanePool* q : g_pools)
+        if (q->device == c->device && q->stream == c->stream) pl = q;
+    if (!pl) {
+        if (c->owns_stream) return nullptr;
+        pl = new PlanePool;
+        pl->device = c->device;
+        pl->stream = c->stream;
+        g_pools.push_back(pl);
+    }
+    pl->refs++;
+    c->pool = pl;
+    return pl;
+}
+// the pooled set of `bytes` (three planes back to back) for a run of this context; null: allocation failed
+void* pool_acquire(jxl_ctx* c, size_t bytes) {
+    PlanePool* pl = c->pool;
+    DeadSet dead;
+    void* p = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_pool_mu);
+        if (c->pool_set_bytes != bytes) dead = pool_drop_set_locked(c);  // the frame size changed
+        for (auto& s : pl->sets)
+            if (s.bytes == bytes) {
+                if (c->pool_set_bytes != bytes) s.users++;
+                c->pool_set_bytes = bytes;
+                p = s.p;
+            }
+        if (!p && hipMalloc(&p, bytes) == hipSuccess) {
+            inter_account(pl->device, (long long)bytes);
+            pl->sets.push_back(PlanePool::Set{bytes, p, 1});
+            c->pool_set_bytes = bytes;
+        }
+    }
+    free_dead_set(dead);
+    return p;
+}
 
 // ---- table staging buffer (jxl_ctx::h_tab) ----
 constexpr size_t kTabAlign = 256;
@@ -893,7 +1049,6 @@ jxl_status finalize_tables(jxl_ctx* c) {
     if (!c->h_tab_pinned) HIP_TRY(c, hipStreamSynchronize(c->stream));
     mark("transfer queued + LF");
     c->tables_dirty = false;
-    static std::atomic<uint64_t> g_tables_gen{0};  // process-wide: a new context at a recycled address never matches an old key
     c->tables_gen = ++g_tables_gen;
     return JXL_OK;
 }
@@ -1163,6 +1318,11 @@ extern "C" int jxl_debug_wg3_item_table(const int32_t* types, const int32_t* n_b
     std::copy(tab.begin(), tab.end(), out);
     return n;
 }
+// Test hook (tests/test_shared_planes_gpu.py): bytes of IDCT-output planes allocated on a device right now -- every context's private
+// set plus every stream pool's sets (PlanePool). Not part of the C-ABI of include/jxlatte_amd.h.
+extern "C" int64_t jxl_debug_intermediate_bytes(int device) {
+    return device >= 0 && device < 64 ? (int64_t)g_inter_bytes[device].load(std::memory_order_relaxed) : -1;
+}
 extern "C" int jxl_debug_clock_probe(int device, double us, double* mhz) {
     static hipStream_t s = nullptr;
     static unsigned long long* d = nullptr;
@@ -1337,6 +1497,8 @@ void jxl_ctx_destroy(jxl_ctx* c) {
     if (c->is_feeder) g_feeders[c->device].fetch_sub(1, std::memory_order_relaxed);
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    pool_detach(c);  // (a pooled set this context was the last user of goes here, behind the synchronise above)
+    release_private_planes(c);
     DevBuf* all[] = {&c->lut, &c->hf_mul, &c->sharp, &c->xfy, &c->bfy, &c->weights, &c->weights_t, &c->inv_sigma, &c->blocks, &c->items,
                      &c->bad_flag};
     for (DevBuf* b : all) b->release();
@@ -1414,9 +1576,11 @@ jxl_status jxl_ctx_set_stream(jxl_ctx* c, void* stream) {
     jxl_status st = bind(c);
     if (st) return st;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    pool_detach(c);  // the old stream's pool; everything this context queued on it has finished
     if (c->owns_stream && c->stream) (void)hipStreamDestroy(c->stream);
     c->stream = (hipStream_t)stream;
     c->owns_stream = false;
+    (void)pool_of(c);  // attach to the target stream's pool (created here if this is its first context)
     return JXL_OK;
 }
 
@@ -1448,11 +1612,13 @@ jxl_status jxl_vardct_begin_frame(jxl_ctx* c, const jxl_vardct_params* p) {
     SectTimer tm("begin2");
     bool ok = true;
     for (int i = 0; i < 3; i++) {
-        ok = ok && c->coeff[i].ensure(4 * npx) && c->planeA[i].ensure(4 * npx) && c->planeB[i].ensure(4 * npx) &&
+        ok = ok && c->coeff[i].ensure(4 * npx) && c->planeB[i].ensure(4 * npx) &&
              c->llf[i].ensure(4 * nc);  // (lf: a window of the table arena, finalize_tables)
         if (out_interleaved(p->out_format)) ok = ok && (i > 0 || c->outbuf[0].ensure(3 * (size_t)out_elem_size(p->out_format) * npx));
         else if (p->out_format != JXL_OUT_F32 || p->transfer != JXL_TRANSFER_NONE) ok = ok && c->outbuf[i].ensure(4 * npx);
     }
+    // the IDCT output planes: private unless the stream has a pool -- then run_frame picks per run, and allocates private ones on first need
+    if (!pool_of(c)) ok = ok && ensure_private_planes(c, 4 * npx);
     ok = ok && c->inv_sigma.ensure(4 * nc);
     tm.mark("ensure");
     ok = ok && tab_begin_frame(c, nc, nt);
@@ -2220,18 +2386,44 @@ void fill_restore_params(jxl_ctx* c, const jxl_vardct_params& p, bool do_gab, bo
 }
 
 // the frame pipeline; idct_done: the IDCT stage of this frame has already been enqueued (batched launch); collect: the
-// fused restoration launch is not enqueued here, its argument block is handed back instead (*collected = true if it was)
-jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, bool* collected = nullptr) {
+// fused restoration launch is not enqueued here, its argument block is handed back instead (*collected = true if it was);
+// may_share: the IDCT output may go to the stream's pooled planes (jxl_vardct_run; the frames of a batch launch together, so theirs are live at once)
+jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, bool* collected = nullptr, bool may_share = false) {
     jxl_status st = bind(c);
     if (st) return st;
     if (!c->frame_open) return fail(c, JXL_ERR_STATE, "begin_frame first");
     st = finalize_tables(c);
     if (st) return st;
-    if ((st = pre_run_zero(c))) return st;
     const jxl_vardct_params& p = c->p;
+    const bool do_gab = (p.stages & JXL_STAGE_GAB) && p.gab;
+    const bool do_epf = (p.stages & JXL_STAGE_EPF) && p.epf_iters > 0;
+    const bool do_xyb = (p.stages & JXL_STAGE_XYB) && p.xyb;
+    const bool do_out = (p.stages & JXL_STAGE_OUT) && (p.transfer != JXL_TRANSFER_NONE || p.out_format != JXL_OUT_F32);
+    // The IDCT output goes to the pooled planes only where it is provably dead after this call: this call runs the IDCT stage into
+    // it (every sample: blocks_cover) and ONE fused restoration launch out of it, into planeB or outbuf. Everything else keeps
+    // it in the context's private planes: stage-masked runs whose result it is, the stage-kernel chain and the EPF x 3 pair
+    // (they ping-pong through it), chroma-subsampled frames (the upsampling swaps the plane sets), batched runs.
+    const size_t npx = (size_t)c->W * c->H;
+    const bool fused_single = (do_gab || do_epf || do_xyb || do_out) && !(epf3_split_on() && do_epf && p.epf_iters == 3) &&
+                              restore_fused_covers(c->H, c->W, do_epf ? p.epf_iters : 0, c->hf_mul.p, c->sharp.p);
+    const bool shared = may_share && !idct_done && !collect && (p.stages & JXL_STAGE_IDCT) && !c->sub && c->blocks_cover && fused_single &&
+                        pool_of(c) != nullptr;
+    // Ordering on a pooled set: every launch of this call that writes it runs on the main stream or on a side stream that waits
+    // for fork_ev, recorded on the main stream below -- behind the restoration launch of the frame before, its last reader
+    std::unique_lock<std::mutex> run_lock;
+    float* A[3];
+    if (shared) {
+        run_lock = std::unique_lock<std::mutex>(c->pool->run_mu);
+        float* base = static_cast<float*>(pool_acquire(c, 3 * 4 * npx));
+        if (!base) return fail(c, JXL_ERR_OOM, "device allocation failed for a %dx%d frame", c->W, c->H);
+        for (int i = 0; i < 3; i++) A[i] = base + (size_t)i * npx;
+    } else {
+        if (!ensure_private_planes(c, 4 * npx)) return fail(c, JXL_ERR_OOM, "device allocation failed for a %dx%d frame", c->W, c->H);
+        for (int i = 0; i < 3; i++) A[i] = c->planeA[i].as<float>();
+    }
+    if ((st = pre_run_zero(c))) return st;  // (a pooled run owes no zero-fill of the output planes: blocks_cover)
     hipStream_t s = c->stream;
     int launches = 0;
-    float* A[3] = {c->planeA[0].as<float>(), c->planeA[1].as<float>(), c->planeA[2].as<float>()};
     float* B[3] = {c->planeB[0].as<float>(), c->planeB[1].as<float>(), c->planeB[2].as<float>()};
     hipEvent_t* evs = c->ev[c->ev_runs % jxl_ctx::kEvSlots];
     if (c->timing) (void)hipEventRecord(evs[0], s);
@@ -2349,10 +2541,6 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
     if (c->timing) (void)hipEventRecord(evs[1], s);
     float** cur = curp;
     float** oth = othp;
-    const bool do_gab = (p.stages & JXL_STAGE_GAB) && p.gab;
-    const bool do_epf = (p.stages & JXL_STAGE_EPF) && p.epf_iters > 0;
-    const bool do_xyb = (p.stages & JXL_STAGE_XYB) && p.xyb;
-    const bool do_out = (p.stages & JXL_STAGE_OUT) && (p.transfer != JXL_TRANSFER_NONE || p.out_format != JXL_OUT_F32);
     // sharpness range check of Frame.java:565-566 (host side: the maps came through the host; scanned by finalize_tables)
     if (do_epf && c->sharp_is_bad) return fail(c, JXL_ERR_INVALID_BITSTREAM, "Invalid EPF Sharpness: %d", c->sharp_bad);
     bool fused = false;
@@ -2397,6 +2585,7 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
             g_restore_kernel_ev[0] = g_restore_kernel_ev[1] = nullptr;
             c->kev_valid = c->timing && fused;
         }
+        if (shared && !fused) return fail(c, JXL_ERR_STATE, "the fused restoration launch declined a run on shared planes");
         if (fused) {
             launches++;
             for (int i = 0; i < 3; i++) c->result[i] = dst[i];
@@ -2473,7 +2662,7 @@ jxl_status jxl_vardct_prepare(jxl_ctx* c) {
     return finalize_tables(c);
 }
 
-jxl_status jxl_vardct_run(jxl_ctx* c) { return run_frame(c, false); }
+jxl_status jxl_vardct_run(jxl_ctx* c) { return run_frame(c, false, nullptr, nullptr, true); }
 
 // A batch of independent frames (one context each, all on one device): the IDCT stage of the whole batch runs as ONE
 // launch per register class (k_idct_wg3_batch, blockIdx.y = frame), on the first context's streams; every frame's
@@ -2496,6 +2685,8 @@ jxl_status jxl_vardct_run_batch(jxl_ctx* const* ctxs, int32_t n) {
         if (!c->frame_open) return fail(c, JXL_ERR_STATE, "begin_frame first");
         st = finalize_tables(c);
         if (st) return st;
+        // the frames of a batch launch together: each keeps its IDCT output in private planes
+        if (!ensure_private_planes(c, 4 * (size_t)c->W * c->H)) return fail(c, JXL_ERR_OOM, "device allocation failed for a %dx%d frame", c->W, c->H);
         if ((st = pre_run_zero(c))) return st;  // (on the frame's own stream: the shared launches are ordered behind it below)
         ok = batchable(c);
     }

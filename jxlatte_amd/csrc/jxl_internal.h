@@ -258,6 +258,12 @@ struct FusedArgs {
     int W, H, bw;
     RestoreParams p;
 };
+// what the fused restoration kernel takes: planes of at least one cell (its mirror fix-up assumes at most one reflection within the
+// halo) and, when EPF iterations run, both cell maps. fill_restore_fused_args declines everything else; run_frame asks the same
+// question before it decides where the IDCT output goes
+inline bool restore_fused_covers(int h, int w, int epf_iters, const void* hf_mul, const void* sharpness) {
+    return w >= 8 && h >= 8 && (epf_iters <= 0 || (hf_mul && sharpness));
+}
 // false if the configuration is not covered by the fused kernel
 bool fill_restore_fused_args(const float* const in[3], void* const out[3], int h, int w, const int32_t* hf_mul,
                              const int32_t* sharpness, const RestoreParams& p, FusedArgs& a);

@@ -10,8 +10,7 @@ namespace jxl {
 
 bool fill_restore_fused_args(const float* const in[3], void* const out[3], int h, int w, const int32_t* hf_mul,
                              const int32_t* sharpness, const RestoreParams& p, FusedArgs& a) {
-    if (w < 8 || h < 8) return false;  // mirror fix-up assumes at most one reflection within the halo
-    if (p.epf_iters > 0 && (!hf_mul || !sharpness)) return false;
+    if (!restore_fused_covers(h, w, p.epf_iters, hf_mul, sharpness)) return false;
     for (int c = 0; c < 3; c++) {
         a.in[c] = in[c];
         a.out[c] = out[c];
