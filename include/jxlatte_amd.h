@@ -482,7 +482,8 @@ jxl_status jxl_planes_upload(jxl_ctx* ctx, const float* const in[3], int32_t hei
 jxl_status jxl_vardct_copy_output_device(jxl_ctx* ctx, void* dst_device);
 /* bytes of one output element for the configured out_format */
 int32_t    jxl_vardct_out_elem_size(const jxl_ctx* ctx);
-/* number of kernel launches the last jxl_vardct_run enqueued (diagnostics) */
+/* number of kernel launches the last jxl_vardct_run enqueued (diagnostics); after jxl_vardct_run_batch the launches the
+ * frames share count on the first context only, so the counts of the batch's contexts add up to its launches */
 int32_t    jxl_vardct_last_launch_count(const jxl_ctx* ctx);
 /* HIP-event timing on the ctx stream, averaged over the runs recorded since timing was enabled
  * (ring of the 32 most recent): which = 0 whole run, 1 IDCT stage, 2 restoration+colour stage (from the end of the IDCT stage's last

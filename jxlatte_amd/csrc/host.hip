@@ -2802,8 +2802,9 @@ jxl_status jxl_vardct_run_batch(jxl_ctx* const* ctxs, int32_t n) {
         launch_restore_fused_batch(fa.data(), c0->batch_restore_args.as<FusedArgs>(), n, s0);
         (void)hipEventRecord(c0->batch_ev, s0);
         for (int i = 1; i < n; i++) (void)hipStreamWaitEvent(ctxs[i]->stream, c0->batch_ev, 0);
-        // run_frame in collect mode has already counted the fused launch for every frame; the shared IDCT launches are
-        // attributed to the first context
+        // run_frame in collect mode has counted the fused launch on every frame, but the batch enqueued ONE: like the shared IDCT
+        // launches it is attributed to the first context, so that the counts of a batch's contexts add up to its launches
+        for (int i = 1; i < n; i++) ctxs[i]->last_launches -= 1;
         c0->last_launches += (int)c0->batch_launches.size();
         return JXL_OK;
     }
