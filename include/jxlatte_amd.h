@@ -661,6 +661,41 @@ typedef struct jxl_pack_params {
 /* out: height * width * (n_color + has_alpha) samples of 1 or 2 bytes */
 jxl_status jxl_stage_pack(jxl_ctx* ctx, const void* const planes[4], const jxl_pack_params* p, void* out);
 
+/* ---- the PNG's samples from the colour planes in one pass: stages 1-6 of jxl_stage_color_convert, then jxl_stage_pack ----
+ * What PNGWriter's constructor makes of an image, JXLImage.transform included, without the float planes between the two: per
+ * pixel the colour stages of `color` (max_value must be 0: they end in float samples), then PNGWriter.java:79-111, 191-203 on
+ * those samples and the alpha plane: an int32 alpha plane is cast with its tagged depth when the image is premultiplied or
+ * the depth is not the PNG's (else clamped as it is), the colours are divided by a premultiplied alpha, every float becomes
+ * (int)(v * max + 0.5f) clamped to 0..max, and the samples leave interleaved, colour then alpha. The bytes are those of
+ * jxl_stage_color_convert (float output) followed by jxl_stage_pack, one for one: the same float operations in the same order,
+ * hence the same tolerance against the reference (the curves' 1 ulp, seen through the quantiser). */
+typedef struct jxl_png_params {
+    jxl_color_params color;     /* the planes and stages 1-6; max_value 0 */
+    int32_t height, width;
+    int32_t has_alpha;          /* an alpha plane follows the colours */
+    int32_t premultiplied;      /* image.isAlphaPremultiplied() */
+    int32_t bit_depth;          /* 8 or 16 */
+    int32_t big_endian;         /* 16-bit samples as DataOutput.writeShort emits them (PNG), else host order */
+    int32_t alpha_is_int;       /* the alpha plane holds int32 samples (else float) */
+    int32_t alpha_tagged_depth; /* image.getTaggedBitDepth(alpha) */
+    int32_t color_tagged_depth; /* image.getTaggedBitDepth(colour): int32 colour planes whose color.in_max[c] is 0 are cast
+                                 * with 2^depth - 1, PNGWriter's coercion of an image that went through no transform */
+} jxl_png_params;
+/* in: color.n_planes host planes of height * width samples; alpha: a host plane or NULL. out: height * width * (nc +
+ * has_alpha) samples of bit_depth / 8 bytes, nc = 3 when color.n_planes == 3 or color.use_matrix, else 1. One upload, one
+ * launch, one download. JXL_ERR_INVALID_ARGUMENT (nothing queued, out untouched): what jxl_stage_color_convert and
+ * jxl_stage_pack refuse, color.max_value != 0, sizes below 1. */
+jxl_status jxl_stage_png_samples(jxl_ctx* ctx, const void* const in[3], const void* alpha, const jxl_png_params* p, void* out);
+/* The same launch on the resident planes (three float planes: color.n_planes 3, in_is_int 0, height and width theirs);
+ * alpha: a host plane in that geometry, uploaded once, or NULL. out is filled on return: the only samples that cross the bus
+ * are the PNG's. JXL_ERR_STATE without resident planes. */
+jxl_status jxl_planes_png_samples(jxl_ctx* ctx, const void* alpha, const jxl_png_params* p, void* out);
+/* jxl_stage_color_peak on the resident planes (row order: that of the planes as they stand, so orient them first). */
+jxl_status jxl_planes_color_peak(jxl_ctx* ctx, const jxl_color_params* p, float* peak);
+/* jxl_stage_orient of the three resident planes, on the device; orientations 5-8 exchange the planes' height and width.
+ * JXL_ERR_STATE: no resident planes, or an orientation outside 1..8. */
+jxl_status jxl_planes_orient(jxl_ctx* ctx, int32_t orientation);
+
 /* ---- Modular path: replaces ModularStream.applyTransforms squeeze/RCT branches ---- */
 /* Default squeeze parameter list of ModularStream.java:110-131 for a channel list whose
  * first nb_meta channels are meta channels. Returns the count (<= cap) or a negative status. */

@@ -166,6 +166,12 @@ public final class NativeBackend implements AutoCloseable {
     public native void stageOrient(ByteBuffer in, int h, int w, int orientation, ByteBuffer out);     // jxl_stage_orient
     /** params: {height, width, nColor, hasAlpha, premultiplied, bitDepth, bigEndian, isInt[4], taggedDepth[4]}. */
     public native void stagePack(ByteBuffer[] planes, int[] params, ByteBuffer out);                  // jxl_stage_pack
+    // the PNG's samples in one pass: params = struct jxl_png_params in a direct buffer; i1, i2, alpha may be null
+    public native void stagePngSamples(ByteBuffer i0, ByteBuffer i1, ByteBuffer i2, ByteBuffer alpha, ByteBuffer params,
+            ByteBuffer out);                                                                          // jxl_stage_png_samples
+    public native void planesPngSamples(ByteBuffer alpha, ByteBuffer params, ByteBuffer out);         // jxl_planes_png_samples
+    public native float planesColorPeak(ByteBuffer params);                                           // jxl_planes_color_peak
+    public native void planesOrient(int orientation);                                                 // jxl_planes_orient
 
     // ---- Modular: plan once (begin), run, read channel by channel
     public static native int[] modularDefaultSqueezeParams(int[] widths, int[] heights, int nbMeta);  // jxl_modular_default_squeeze_params

@@ -1142,6 +1142,65 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stagePack(J
     CHECK(jxl_stage_pack(c, pl, &p, ADDR(out)));
 }
 
+/* ---- the PNG's samples in one pass (PNGWriter's constructor, JXLImage.transform included): params = struct jxl_png_params in a direct
+ * buffer; i1, i2 are null for one colour plane, alpha is null without an alpha channel. Thin pass-throughs. ---- */
+static int png_params(JNIEnv* e, jobject params, jxl_png_params* p) {
+    const void* src = params ? (*e)->GetDirectBufferAddress(e, params) : NULL;
+    if (!src || (*e)->GetDirectBufferCapacity(e, params) < (jlong)sizeof *p) {
+        bad_arg(e, "jxlatte_amd: a direct buffer holding jxl_png_params is needed");
+        return 0;
+    }
+    memcpy(p, src, sizeof *p);
+    if ((p->bit_depth != 8 && p->bit_depth != 16) || p->height < 1 || p->width < 1) {
+        bad_arg(e, "jxlatte_amd: png parameters");
+        return 0;
+    }
+    return 1;
+}
+/* the bytes of the samples `p` asks for */
+static jlong png_bytes(const jxl_png_params* p) {
+    const int nc = (p->color.n_planes == 3 || p->color.use_matrix) ? 3 : 1;
+    return area(p->height, p->width) * (nc + (p->has_alpha ? 1 : 0)) * (p->bit_depth / 8);
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stagePngSamples(JNIEnv* e, jobject self, jobject i0, jobject i1, jobject i2,
+        jobject alpha, jobject params, jobject out) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_png_params p;
+    if (!png_params(e, params, &p)) return;
+    const jlong plane = 4 * area(p.height, p.width);
+    NEED(i0, plane); NEED_OPT(i1, plane); NEED_OPT(i2, plane); NEED_OPT(alpha, plane);
+    NEED(out, png_bytes(&p));
+    const void* in[3] = {ADDR(i0), ADDR(i1), ADDR(i2)};
+    CHECK(jxl_stage_png_samples(c, in, ADDR(alpha), &p, ADDR(out)));
+}
+
+/* the same on the resident planes: height and width must be theirs (the library checks) */
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesPngSamples(JNIEnv* e, jobject self, jobject alpha, jobject params,
+        jobject out) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_png_params p;
+    if (!png_params(e, params, &p)) return;
+    NEED_OPT(alpha, 4 * area(p.height, p.width));
+    NEED(out, png_bytes(&p));
+    CHECK(jxl_planes_png_samples(c, ADDR(alpha), &p, ADDR(out)));
+}
+
+JNIEXPORT jfloat JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesColorPeak(JNIEnv* e, jobject self, jobject params) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_color_params p;
+    float peak = 0.0f;
+    if (!color_params(e, params, &p)) return 0.0f;
+    jxl_status st = jxl_planes_color_peak(c, &p, &peak);
+    if (st != JXL_OK) { rethrow(e, c, st); return 0.0f; }
+    return peak;
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesOrient(JNIEnv* e, jobject self, jint orientation) {
+    jxl_ctx* c = ctx_of(e, self);
+    CHECK(jxl_planes_orient(c, orientation));
+}
+
 /* ---- Modular: plan once, run, read channel by channel (ModularStream.applyTransforms, ModularStream.java:110-131) ---- */
 JNIEXPORT jintArray JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_modularDefaultSqueezeParams(JNIEnv* e, jclass k, jintArray widths,
         jintArray heights, jint nbMeta) {

@@ -6,7 +6,7 @@ import sys
 import time
 
 
-def main(argv=None):
+def parser():
     ap = argparse.ArgumentParser(prog="python -m jxlatte_amd", description=__doc__)
     ap.add_argument("input")
     ap.add_argument("output", nargs="?")
@@ -27,7 +27,15 @@ def main(argv=None):
     ap.add_argument("--device-patches", action="store_true",
                     help="apply all patch positions of a frame in one kernel launch (jxl_planes_patches / jxl_stage_patches) instead "
                          "of one blend call per position and channel; same samples")
-    a = ap.parse_args(argv)
+    ap.add_argument("--device-png", action="store_true",
+                    help="from the coefficients to the PNG's samples on the device: a frame that is the whole image leaves its colour "
+                         "planes there (JXLDecoder device_output), and colour management and sample packing are one kernel "
+                         "(jxl_planes_png_samples / jxl_stage_png_samples); the same bytes as --device-color")
+    return ap
+
+
+def main(argv=None):
+    a = parser().parse_args(argv)
     from . import frontend
     if a.info:
         fe = frontend.Frontend(open(a.input, "rb").read())
@@ -40,7 +48,7 @@ def main(argv=None):
     t0 = time.time()
     backend = DeviceBackend(a.device)
     dec = JXLDecoder(a.input, backend=backend, sparse_coeffs=a.sparse_coeffs, device_splines=a.device_splines,
-                     device_patches=a.device_patches)
+                     device_patches=a.device_patches, device_output=a.device_png)
     image = dec.decode()
     if image is None:
         print("jxlatte_amd: no frames", file=sys.stderr)
@@ -53,7 +61,7 @@ def main(argv=None):
         hdr = image.isHDR() if a.png_hdr == "auto" else a.png_hdr == "yes"
         with open(a.output, "wb") as f:
             PNGWriter(image, bitDepth=16 if hdr else a.png_depth, hdr=hdr, peakDetect=PEAK_DETECT[a.png_peak_detect],
-                      deviceColor=a.device_color).write(f)
+                      deviceColor=a.device_color, deviceSamples=a.device_png).write(f)
     backend.close()
     return 0
 

@@ -133,6 +133,10 @@ SIGNATURES = {
                               C.POINTER(abi.BlendRect)]),
     "jxl_stage_orient": (i32, [vp, vp, i32, i32, i32, vp]),
     "jxl_stage_pack": (i32, [vp, pv3, C.POINTER(abi.PackParams), vp]),
+    "jxl_stage_png_samples": (i32, [vp, pv3, vp, C.POINTER(abi.PngParams), vp]),
+    "jxl_planes_png_samples": (i32, [vp, vp, C.POINTER(abi.PngParams), vp]),
+    "jxl_planes_color_peak": (i32, [vp, C.POINTER(abi.ColorParams), pf]),
+    "jxl_planes_orient": (i32, [vp, i32]),
     "jxl_modular_default_squeeze_params": (i32, [pi, pi, i32, i32, C.POINTER(abi.SqueezeParam), i32]),
     "jxl_modular_squeezed_shapes": (i32, [pi, pi, i32, C.POINTER(abi.SqueezeParam), i32, pi, pi, i32]),
     "jxl_modular_begin": (i32, [vp, C.POINTER(abi.Channel), i32, C.POINTER(abi.SqueezeParam), i32, i32, i32]),

@@ -157,6 +157,13 @@ class ColorParams(C.Structure):
                 ("matrix", f9), ("tf_out", C.c_int32), ("gamma_out", C.c_int32), ("max_value", C.c_int32)]
 
 
+class PngParams(C.Structure):
+    """struct jxl_png_params"""
+    _fields_ = [("color", ColorParams), ("height", C.c_int32), ("width", C.c_int32), ("has_alpha", C.c_int32),
+                ("premultiplied", C.c_int32), ("bit_depth", C.c_int32), ("big_endian", C.c_int32), ("alpha_is_int", C.c_int32),
+                ("alpha_tagged_depth", C.c_int32), ("color_tagged_depth", C.c_int32)]
+
+
 class SplineDesc(C.Structure):
     """struct jxl_spline_desc (SplinesBundle.java + the two LFChannelCorrelation factors)"""
     _fields_ = [("quant_adjust", C.c_int32), ("n_splines", C.c_int32), ("n_control", C.POINTER(C.c_int32)),

@@ -1,0 +1,87 @@
+// The sample functions of the colour kernels (k_color.hip: k_color_convert, k_color_peak; k_png.hip: k_png_samples): the
+// reference's casts, transfer curves and quantiser as device functions, so that every kernel that restates a stage of
+// JXLImage.transform evaluates the very same float operations. Include from a file compiled with -ffp-contract=off.
+#ifndef JXL_COLOR_SAMPLES_H
+#define JXL_COLOR_SAMPLES_H
+#include "jxl_fastpow.h"
+#include "jxl_internal.h"
+
+namespace jxl {
+namespace {
+
+// Java (int)float: NaN -> 0, saturating
+__device__ __forceinline__ int32_t f2i(float v) {
+    if (v != v) return 0;
+    if (v >= 2147483648.0f) return INT32_MAX;
+    if (v <= -2147483648.0f) return INT32_MIN;
+    return (int32_t)v;
+}
+
+// ImageBuffer.castToInt0 (ImageBuffer.java:129-145)
+__device__ __forceinline__ int32_t to_int(float v, int max_value) {
+    const int32_t q = f2i(v * (float)max_value + 0.5f);
+    return q < 0 ? 0 : q > max_value ? max_value : q;
+}
+
+// Math.pow(x, p) for any finite p > 0 (GammaTransferFunction: p = 1e7 / g or 1e-7 * g can be an integer, e.g. g = 5000000).
+// kind: 0 p is not an integer, 1 an even integer, 2 an odd integer (host: pow_kind).
+//   NaN -> NaN; +-0 -> +0 (-0 for -0 and odd p); +-inf -> +inf (-inf for -inf and odd p);
+//   x < 0: NaN for a non-integer p, else +-|x|^p.
+__device__ __forceinline__ double pow_any(double x, double p, int kind) {
+    const double ax = __builtin_fabs(x);
+    const bool neg = __builtin_signbit(x);
+    const bool finite_pos = ax > 0.0 && ax < __builtin_inf();
+    if (neg && kind == 0) return finite_pos || ax != ax ? __builtin_nan("") : ax;  // -0 -> +0, -inf -> +inf
+    double r = ax;  // 0, inf, NaN
+    if (finite_pos) r = fp_pow_pos(ax, p);
+    return neg && kind == 2 ? -r : r;
+}
+
+// TransferFunction.toLinearF. sRGB has its own float form (:55-60); the others are the interface default
+// (float)toLinear((double)f) (:100-102).
+__device__ __forceinline__ float to_linear(float f, int tf, double p, int kind) {
+    if (tf == JXL_TF_SRGB) {
+        if (f < 0.0404482362771082f) return f * 0.07739938080495357f;
+        return (float)fp_pow((double)(f * 0.9478672985781991f + 0.052132701f), 2.4);
+    }
+    if (tf == JXL_TF_BT709) {  // :73-78
+        const double d = (double)f;
+        if (d < 0.081242858298635133011) return (float)(d * 0.22222222222222222222);
+        return (float)fp_pow((d + 0.0992968268094429403) * 0.90967241568627260377, 2.2222222222222222222);
+    }
+    if (tf == JXL_TF_PQ) {  // :89-92. f below ~7.3e-7 (zero included): d < 0.8359375, a negative base, NaN -- as in the reference
+        const double d = fp_pow((double)f, 0.012683313515655965121);
+        return (float)fp_pow(fp_div(d - 0.8359375, 18.8515625 + 18.6875 * d), 6.2725880551301684533);
+    }
+    if (tf == JXL_TF_GAMMA) return (float)pow_any((double)f, p, kind);  // GammaTransferFunction.toLinear
+    return f;
+}
+
+// TransferFunction.fromLinearF as a float. LINEAR / SRGB / PQ: the functions jxl_stage_transfer evaluates (k_restore.hip,
+// apply_transfer: PQ through the segment table when the context has one).
+__device__ __forceinline__ float from_linear(float v, int tf, double p, int kind, const float4* pq_tab) {
+    if (tf == JXL_TF_SRGB) return fp_tf_srgb(v);
+    if (tf == JXL_TF_PQ) return pq_tab ? fp_tf_pq_tab(v, pq_tab) : fp_tf_pq(v);
+    if (tf == JXL_TF_BT709) {  // :65-70
+        const double d = (double)v;
+        if (d < 0.018053968510807807336) return (float)(4.5 * d);
+        return (float)(1.0992968268094429403 * fp_pow(d, 0.45) - 0.0992968268094429403);
+    }
+    if (tf == JXL_TF_GAMMA) return (float)pow_any((double)v, p, kind);  // GammaTransferFunction.fromLinear
+    return v;
+}
+
+// stages 1 + 2 of one 4-byte sample word of input plane c
+__device__ __forceinline__ float linear_word(const ColorArgs& a, int c, uint32_t word) {
+    const float f = a.in_is_int ? (float)(int32_t)word * a.in_scale[c] : __builtin_bit_cast(float, word);
+    return to_linear(f, a.tf_in, a.p_in, a.kind_in);
+}
+
+// stages 1 + 2 of sample i of input plane c
+__device__ __forceinline__ float linear_sample(const ColorArgs& a, int c, int64_t i) {
+    return linear_word(a, c, ((const uint32_t*)a.in[c])[i]);
+}
+
+}  // namespace
+}  // namespace jxl
+#endif  // JXL_COLOR_SAMPLES_H

@@ -3961,6 +3961,141 @@ jxl_status jxl_stage_pack(jxl_ctx* c, const void* const planes[4], const jxl_pac
     return JXL_OK;
 }
 
+
+// ---- the PNG's samples in one pass (k_png.hip): stages 1-6 of jxl_stage_color_convert, then jxl_stage_pack's rule ----
+}  // extern "C"
+namespace {
+// the checks of jxl_stage_color_convert and jxl_stage_pack on one jxl_png_params, and the kernel's arguments (the plane and
+// output pointers are filled in by the caller). `in`: the colour planes as color_args checks them.
+jxl_status png_args(jxl_ctx* c, const jxl_png_params* p, const void* const in[3], const void* alpha, const void* out, PngArgs* a, int* n_color) {
+    if (!p || !in || !out) return fail(c, JXL_ERR_INVALID_ARGUMENT, "png samples: null argument");
+    if (p->height <= 0 || p->width <= 0) return fail(c, JXL_ERR_INVALID_ARGUMENT, "png samples: bad size");
+    if (p->bit_depth != 8 && p->bit_depth != 16) return fail(c, JXL_ERR_INVALID_ARGUMENT, "PNG only supports 8 and 16");  // PNGWriter.java:57-58
+    if (p->color.max_value != 0) return fail(c, JXL_ERR_INVALID_ARGUMENT, "png samples: the colour stages end in float samples (max_value 0)");
+    if ((p->has_alpha && !alpha) || (p->premultiplied && !p->has_alpha)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "png samples: bad channel layout");
+    jxl_color_params cp = p->color;
+    // integer colour planes without a maximum of their own: the cast PNGWriter's coercion makes, with the tagged depth
+    for (int i = 0; i < 3 && cp.in_is_int; i++)
+        if (cp.in_max[i] == 0 && p->color_tagged_depth >= 1 && p->color_tagged_depth <= 31) cp.in_max[i] = ~(~0 << p->color_tagged_depth);
+    jxl_status st = color_args(c, &cp, in, &a->c);
+    if (st) return st;
+    const bool alpha_int = p->has_alpha && p->alpha_is_int;
+    const bool coerce = p->premultiplied || (alpha_int && p->alpha_tagged_depth != p->bit_depth);  // PNGWriter.java:79-88: the colours are float here
+    if (alpha_int && coerce && (p->alpha_tagged_depth < 1 || p->alpha_tagged_depth > 31))
+        return fail(c, JXL_ERR_INVALID_ARGUMENT, "invalid Max Value");  // ImageBuffer.java:115-116
+    a->c.n = (int64_t)p->height * p->width;
+    a->c.pq_tab = c->pq_tab.as<float>();  // what jxl_stage_color_convert hands its kernel for float output
+    a->alpha = nullptr;
+    a->alpha_is_int = alpha_int ? 1 : 0;
+    a->alpha_coerce = coerce ? 1 : 0;
+    const int d = p->alpha_tagged_depth;
+    a->alpha_scale = (alpha_int && d >= 1 && d <= 31) ? 1.0f / (float)(~(~0 << d)) : 0.0f;  // ImageBuffer.java:119
+    a->premultiplied = p->premultiplied ? 1 : 0;
+    a->bit_depth = p->bit_depth;
+    a->big_endian = p->big_endian ? 1 : 0;
+    a->out = nullptr;
+    *n_color = (cp.n_planes == 3 || cp.use_matrix) ? 3 : 1;
+    return JXL_OK;
+}
+
+// upload the alpha plane, launch, download the samples
+// guard: that many bytes behind the samples, in the DEVICE buffer, are set to 0xA5 before the launch and come down with the
+// samples (jxl_debug_png_samples_guard: what the kernel's last lane stores is seen where it stores it)
+jxl_status png_run(jxl_ctx* c, PngArgs& a, int n_color, bool has_alpha, const void* alpha, Tmp& t, void* out, size_t guard = 0) {
+    const size_t n = (size_t)a.c.n;
+    if (has_alpha && !(a.alpha = t.up((const uint32_t*)alpha, n))) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    const size_t ob = n * (size_t)(n_color + (has_alpha ? 1 : 0)) * (size_t)(a.bit_depth / 8);
+    if (!(a.out = t.up<uint8_t>(nullptr, ob + guard))) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    if (guard) HIP_TRY(c, hipMemsetAsync((uint8_t*)a.out + ob, 0xA5, guard, c->stream));
+    launch_png_samples(a, n_color, c->stream);
+    jxl_status st = finish(c);
+    if (st) return st;
+    HIP_TRY(c, hipMemcpy(out, a.out, ob + guard, hipMemcpyDeviceToHost));
+    return JXL_OK;
+}
+}  // namespace
+extern "C" {
+
+jxl_status jxl_stage_png_samples(jxl_ctx* c, const void* const in[3], const void* alpha, const jxl_png_params* p, void* out) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    PngArgs a;
+    int n_color = 0;
+    if ((st = png_args(c, p, in, alpha, out, &a, &n_color))) return st;
+    Tmp t;
+    for (int i = 0; i < p->color.n_planes; i++)
+        if (!(a.c.in[i] = t.up((const uint32_t*)in[i], (size_t)a.c.n))) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    return png_run(c, a, n_color, p->has_alpha != 0, alpha, t, out);
+}
+
+// tests: jxl_stage_png_samples into a device buffer that is `guard` bytes longer; out receives the samples AND those bytes
+jxl_status jxl_debug_png_samples_guard(jxl_ctx* c, const void* const in[3], const void* alpha, const jxl_png_params* p, void* out, int32_t guard) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    PngArgs a;
+    int n_color = 0;
+    if (guard < 0) return fail(c, JXL_ERR_INVALID_ARGUMENT, "png samples: bad guard size");
+    if ((st = png_args(c, p, in, alpha, out, &a, &n_color))) return st;
+    Tmp t;
+    for (int i = 0; i < p->color.n_planes; i++)
+        if (!(a.c.in[i] = t.up((const uint32_t*)in[i], (size_t)a.c.n))) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    return png_run(c, a, n_color, p->has_alpha != 0, alpha, t, out, (size_t)guard);
+}
+
+jxl_status jxl_planes_png_samples(jxl_ctx* c, const void* alpha, const jxl_png_params* p, void* out) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (c->rp_h <= 0) return fail(c, JXL_ERR_STATE, "no resident planes");
+    const void* in[3] = {c->rp[0].p, c->rp[1].p, c->rp[2].p};
+    PngArgs a;
+    int n_color = 0;
+    if ((st = png_args(c, p, in, alpha, out, &a, &n_color))) return st;
+    if (p->color.n_planes != 3 || p->color.in_is_int || p->height != c->rp_h || p->width != c->rp_w)
+        return fail(c, JXL_ERR_INVALID_ARGUMENT, "png samples: the resident planes are three %d x %d float planes", c->rp_h, c->rp_w);
+    for (int i = 0; i < 3; i++) a.c.in[i] = in[i];
+    Tmp t;
+    return png_run(c, a, n_color, p->has_alpha != 0, alpha, t, out);
+}
+
+jxl_status jxl_planes_color_peak(jxl_ctx* c, const jxl_color_params* p, float* peak) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (c->rp_h <= 0) return fail(c, JXL_ERR_STATE, "no resident planes");
+    const void* in[3] = {c->rp[0].p, c->rp[1].p, c->rp[2].p};
+    ColorArgs a;
+    if ((st = color_args(c, p, in, &a))) return st;
+    if (!peak || p->n_planes != 3 || p->in_is_int || c->rp_w > (1 << 30)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color peak: bad arguments");
+    for (int i = 0; i < 3; i++) a.in[i] = in[i];
+    Tmp t;
+    uint32_t* dkey = t.up<uint32_t>(nullptr, 1);
+    if (!dkey) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    HIP_TRY(c, hipMemsetAsync(dkey, 0, 4, c->stream));
+    a.n = (int64_t)c->rp_h * c->rp_w;
+    launch_color_peak(a, c->rp_h, c->rp_w, dkey, c->stream);
+    if ((st = finish(c))) return st;
+    uint32_t key = 0;
+    HIP_TRY(c, hipMemcpy(&key, dkey, 4, hipMemcpyDeviceToHost));
+    *peak = color_peak_value(key);
+    return JXL_OK;
+}
+
+jxl_status jxl_planes_orient(jxl_ctx* c, int32_t orientation) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (c->rp_h <= 0) return fail(c, JXL_ERR_STATE, "no resident planes");
+    if (orientation < 1 || orientation > 8) return fail(c, JXL_ERR_STATE, "orientation %d", orientation);  // IllegalStateException, :107
+    if (orientation == 1) return JXL_OK;
+    const size_t bytes = sizeof(float) * (size_t)c->rp_h * c->rp_w;
+    for (int i = 0; i < 3; i++)
+        if (!c->rp_tmp[i].ensure(bytes)) return fail(c, JXL_ERR_OOM, "device allocation failed (resident planes)");
+    for (int i = 0; i < 3; i++) {
+        launch_orient(c->rp[i].p, c->rp_h, c->rp_w, orientation, c->rp_tmp[i].p, c->stream);
+        std::swap(c->rp[i], c->rp_tmp[i]);
+    }
+    if (orientation > 4) std::swap(c->rp_h, c->rp_w);
+    return JXL_OK;
+}
+
 }  // extern "C"
 
 // ---- Modular: pairing of squeeze steps for the fused kernel (r5) ---------------------------------------------------------------

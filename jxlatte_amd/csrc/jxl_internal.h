@@ -225,6 +225,19 @@ void launch_color_convert(const ColorArgs& a, hipStream_t s);
 // determinePeak over h rows of w samples (w <= 2^30): *result, zeroed by the caller, receives an order-preserving uint32 key of
 // the peak (host.hip: color_peak_value)
 void launch_color_peak(const ColorArgs& a, int h, int w, uint32_t* result, hipStream_t s);
+// the PNG's samples from the colour planes in one pass (k_png.hip): stages 1-6 of ColorArgs (out[], max_value and the integer
+// tables are not looked at), then PNGWriter's coercion, un-premultiplication, quantisation and interleaving
+struct PngArgs {
+    ColorArgs c;
+    const void* alpha;  // device plane of c.n float or int32 samples, or null
+    int alpha_is_int;
+    int alpha_coerce;   // an int32 alpha plane is cast to float first (PNGWriter.java:79-88), else clamped as it is
+    float alpha_scale;  // 1.0f / maxValue(tagged depth)
+    int premultiplied, bit_depth, big_endian;
+    void* out;          // c.n * (n_color + (alpha != null)) samples of bit_depth / 8 bytes
+};
+// n_color: 3 when c.n_planes == 3 or c.use_matrix, else 1
+void launch_png_samples(const PngArgs& p, int n_color, hipStream_t s);
 // PQ as a table of quadratic segments (jxl_fastpow.h): kPqTableFloats floats = float4 {a0 hi, a0 lo, a1, a2} per segment
 constexpr int kPqTableFloats = (129 - 87) * 128 * 4;
 void build_pq_table(float* out /* [kPqTableFloats] */);

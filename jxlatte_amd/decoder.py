@@ -575,6 +575,10 @@ class DeviceBackend:
     def color_peak(self, planes, **params):
         return self.host.determinePeak(self.ctx, planes, **params)
 
+    def png_samples(self, planes, alpha, **params):
+        """PNGWriter's samples in one pass (host.pngSamples; the keywords are host.pngParams')"""
+        return self.host.pngSamples(self.ctx, planes, alpha, **params)
+
     def pack(self, planes, bit_depth, alpha, premultiplied, tagged, big_endian):
         return self.host.packSamples(self.ctx, planes, bit_depth, alpha=alpha, premultiplied=premultiplied, taggedDepth=tagged,
                                      bigEndian=big_endian)
@@ -582,11 +586,16 @@ class DeviceBackend:
 
 # ---- JXLImage (J/JXLImage.java) ---------------------------------------------------------------------------------
 class JXLImage:
-    def __init__(self, buffer, info, backend):
+    def __init__(self, buffer, info, backend, resident=None):
+        """resident: the backend's resident planes (host.ResidentPlanes) holding the three colour planes, whose places in
+        `buffer` are None: JXLDecoder(device_output=True). They are the image's until the backend decodes another frame;
+        `buffer` / getBuffer() download them on first use and keep the host arrays; once another frame has taken the planes,
+        a first use raises IllegalStateException instead (ResidentPlanes.live)."""
         self.info = info
         self.backend = backend
+        self.resident = resident
         self.buffer = buffer  # list of 2-D arrays (int32 or float32), colour channels first
-        self.height, self.width = buffer[0].shape
+        self.height, self.width = buffer[0].shape if resident is None else resident.shape
         self.colorEncoding = info.colour_space
         alphas = [i for i in range(info.num_extra) if info.ec_type[i] == 0]
         self.alphaIndex = alphas[0] if alphas else -1
@@ -599,11 +608,31 @@ class JXLImage:
         self.bitDepths = [info.bits_per_sample if c < colors else info.ec_bits[c - colors] for c in range(len(buffer))]
         self.has_icc = bool(info.use_icc) and not info.xyb_encoded
 
+    resident = None
+
+    @property
+    def buffer(self):
+        if self.resident is not None and self._buffer[0] is None:
+            self.resident._need_live()  # (a later frame of the backend has taken the planes: an error, not its pixels)
+            planes = self.resident.download()
+            for c in range(3):
+                self._buffer[c] = planes[c]
+        return self._buffer
+
+    @buffer.setter
+    def buffer(self, planes):
+        self._buffer = planes
+
+    def onDevice(self):
+        """the colour planes are the backend's resident planes (and nothing has replaced them on this image)"""
+        return self.resident is not None
+
     def _clone(self, buffer=None):
         im = JXLImage.__new__(JXLImage)
         im.__dict__.update(self.__dict__)
         im.buffer = list(self.buffer if buffer is None else buffer)
         im.bitDepths = list(self.bitDepths)
+        im.resident = None  # a clone lives on the host
         return im
 
     def getWidth(self):
@@ -626,6 +655,10 @@ class JXLImage:
 
     def getTaggedBitDepth(self, c):
         return self.bitDepths[c]
+
+    def extraChannel(self, i):
+        """extra channel i (a host array), without touching the colour planes"""
+        return self._buffer[self.getColorChannelCount() + i]
 
     def getBuffer(self, copy=True):
         return [b.copy() for b in self.buffer] if copy else self.buffer
@@ -710,19 +743,21 @@ class JXLImage:
         im.primariesXY, im.whiteXY = np.array(primaries, F), np.array(whitePoint, F)
         return im
 
-    def _transform_device(self, primaries, whitePoint, transfer, peakDetect):
-        """transform() with the samples on the device: the decisions of transform / linearize / fillColor / toneMapLinear /
-        transfer (JXLImage.java:114-141, 185-193, 260-286) are taken here, the sample work is at most one color_peak and one
-        color_convert call of the backend. Same metadata as the host path; float samples within the 1 ulp of the double-pow
-        curves (include/jxlatte_amd.h)."""
+    def _color_plan(self, primaries, whitePoint, transfer, peakDetect, peak_of, planes=None):
+        """the decisions of transform / linearize / fillColor / toneMapLinear / transfer (JXLImage.java:114-141, 185-193, 260-286)
+        for a backend that does the sample work in one pass: None when the image is returned as it is, else (planes, params,
+        tone_map), params being the keywords of host.colorParams for those planes. peak_of(planes, **front) is asked for
+        determinePeak of the front stages, at most once, where transfer() would take it. planes: stand-ins for colour planes
+        that are not on the host (their dtype is what is looked at)."""
         tone_map = not (_prim_matches(primaries, self.primariesXY) and _xy_matches(whitePoint, self.whiteXY))
         if not tone_map and transfer == self.transfer_:
-            return self
+            return None
         tf_in, gamma_in = _tf_selector(self.transfer_)
         tf_out, gamma_out = _tf_selector(transfer)
         colors = self.getColorChannelCount()
         depth_max = [(1 << self.bitDepths[c]) - 1 for c in range(colors)]
-        planes = [self.buffer[c] for c in range(colors)]
+        if planes is None:
+            planes = [self.buffer[c] for c in range(colors)]
         if len({p.dtype for p in planes}) != 1:  # mixed int / float colour planes: the first cast, done here
             cast_max = depth_max if (self.transfer_ != TF_LINEAR or tone_map) else None
             planes = [self._as_float(c) if cast_max else self._as_float(c, with_depth=False) for c in range(colors)]
@@ -730,20 +765,30 @@ class JXLImage:
         if tone_map:
             front["matrix"] = get_conversion_matrix(primaries, whitePoint, self.primariesXY, self.whiteXY)
         if tone_map and transfer == TF_LINEAR:  # transfer() of the tone-mapped, linear image returns it as it is (:270-271)
-            out = self.backend.color_convert(planes, inMax=depth_max, **front)
-        else:
-            scale = None
-            if self.taggedTransfer == TF_PQ and peakDetect in (PEAK_DETECT_AUTO, PEAK_DETECT_ON):
-                to_pq = transfer in (TF_PQ, TF_LINEAR)
-                from_pq = tone_map or self.transfer_ in (TF_PQ, TF_LINEAR)  # the tone-mapped image is linear
-                if from_pq and not to_pq:
-                    s = F(F(1) / self.backend.color_peak(planes, inMax=depth_max, **front))
-                    if s > 1.0 or peakDetect == PEAK_DETECT_ON:
-                        scale = s
-            # the first stage that touches the samples casts them: linearize, toneMapLinear and the scale with the depth's
-            # maximum, transferInPlace with the depth itself (:248)
-            first_max = depth_max if (self.transfer_ != TF_LINEAR or tone_map or scale is not None) else [self.bitDepths[c] for c in range(colors)]
-            out = self.backend.color_convert(planes, inMax=first_max, scale=scale, tfOut=tf_out, gammaOut=gamma_out, **front)
+            return planes, dict(inMax=depth_max, **front), tone_map
+        scale = None
+        if self.taggedTransfer == TF_PQ and peakDetect in (PEAK_DETECT_AUTO, PEAK_DETECT_ON):
+            to_pq = transfer in (TF_PQ, TF_LINEAR)
+            from_pq = tone_map or self.transfer_ in (TF_PQ, TF_LINEAR)  # the tone-mapped image is linear
+            if from_pq and not to_pq:
+                s = F(F(1) / peak_of(planes, inMax=depth_max, **front))
+                if s > 1.0 or peakDetect == PEAK_DETECT_ON:
+                    scale = s
+        # the first stage that touches the samples casts them: linearize, toneMapLinear and the scale with the depth's
+        # maximum, transferInPlace with the depth itself (:248)
+        first_max = depth_max if (self.transfer_ != TF_LINEAR or tone_map or scale is not None) else [self.bitDepths[c] for c in range(colors)]
+        return planes, dict(inMax=first_max, scale=scale, tfOut=tf_out, gammaOut=gamma_out, **front), tone_map
+
+    def _transform_device(self, primaries, whitePoint, transfer, peakDetect):
+        """transform() with the samples on the device: the decisions are _color_plan's, the sample work is at most one
+        color_peak and one color_convert call of the backend. Same metadata as the host path; float samples within the 1 ulp
+        of the double-pow curves (include/jxlatte_amd.h)."""
+        plan = self._color_plan(primaries, whitePoint, transfer, peakDetect, self.backend.color_peak)
+        if plan is None:
+            return self
+        planes, params, tone_map = plan
+        colors = self.getColorChannelCount()
+        out = self.backend.color_convert(planes, **params)
         im = self._clone()
         if tone_map:
             if colors == 1:  # fillColor
@@ -774,7 +819,7 @@ def _tt_dims():
 
 
 class JXLDecoder:
-    def __init__(self, source, backend=None, sparse_coeffs=False, device_splines=False, device_patches=False):
+    def __init__(self, source, backend=None, sparse_coeffs=False, device_splines=False, device_patches=False, device_output=False):
         """sparse_coeffs: hand the HF coefficients to the backend as lists of non-zero entries (jxf_get_coeffs_sparse ->
         jxl_vardct_put_group_sparse), not as dense planes; same pixels.
         device_splines: Frame.renderSplines runs in the backend (jxl_planes_splines on the resident planes, jxl_stage_splines
@@ -783,7 +828,15 @@ class JXLDecoder:
         device_patches: computePatches runs in the backend as one launch per segment of patch_type_plan (jxl_planes_patches on
         the resident planes, jxl_stage_patches otherwise) instead of one backend.blend per (position, channel); the same bits.
         Grey images and frames whose colour count is not the image's keep the blend calls; stats[-1]["patches"] tells. A backend
-        without `patches` is an error."""
+        without `patches` is an error.
+        device_output: a frame that IS the image -- a regular last frame of three float colour planes at the origin, of the
+        image's size after upsampling, blended with REPLACE, the first to reach the canvas, lf_level 0 -- leaves its colour
+        planes on the device when they are there after performColorTransforms, and decode() returns a JXLImage that carries
+        them (JXLImage.resident; getBuffer() downloads on first use, the same bits). A VarDCT frame without a stage after
+        decodeFrame qualifies too. The extra channels are blended and oriented on the host as ever; the orientation of the
+        colour planes is ResidentPlanes.orient. Every other frame takes the usual path. stats[-1]["output"] tells which:
+        "device" or "host"."""
+        self.device_output = bool(device_output)
         self.sparse_coeffs = bool(sparse_coeffs)
         self.device_splines = bool(device_splines)
         self.device_patches = bool(device_patches)
@@ -873,13 +926,14 @@ class JXLDecoder:
         from . import host
         return host.getUpWeights(k, packed)
 
-    def _chained_tail(self, fr, rp, buffers, colors, save, xyb_done):
+    def _chained_tail(self, fr, rp, buffers, colors, save, xyb_done, keep=False):
         """Frame.upsample .. performColorTransforms (JXLCodestreamDecoder.java:628-637) of the three colour planes with the
         samples moving between host and device only where the next stage lives on the other side: upsampling, noise and the
         colour transforms are device stages on host.ResidentPlanes, and so are the splines with `device_splines`; the
         saveBeforeCT reference, the patches and (by default) the splines are host stages (as in the reference). `rp` is the
         VarDCT frame's resident result, or None when the colour planes start as the host arrays buffers[:3] (Modular frames).
-        The extra channels in buffers[3:] are host arrays throughout."""
+        The extra channels in buffers[3:] are host arrays throughout.
+        keep: planes that are on the device at the end stay there (buffers[:3] are then not touched); returns them, or None."""
         info, be = self.info, self.backend
         moves = []
 
@@ -933,8 +987,10 @@ class JXLDecoder:
             on_device().invertXYB(m, bias, cbrt, info.intensity_target)
         if fr.do_ycbcr:
             on_device().ycbcr()
-        on_host()
+        if not keep:
+            on_host()
         self.stats[-1]["plane_moves"] = moves
+        return rp
 
     def _vardct_inputs(self, fr, fuse_xyb):
         """the boundary tensors of one VarDCT frame: (jxl_vardct_params, weights, offsets, LF groups, group iterator)"""
@@ -1013,8 +1069,9 @@ class JXLDecoder:
                 val = src
             buffers[c_out][:h, :w] = val
 
-    def _blend_frame(self, fr, frame_buffers, colors_frame):
-        """JXLCodestreamDecoder.blendFrame + blendBuffers (:424-537)"""
+    def _blend_frame(self, fr, frame_buffers, colors_frame, first=0):
+        """JXLCodestreamDecoder.blendFrame + blendBuffers (:424-537). first: the first canvas channel to blend (the colour
+        planes of a device_output frame are not on the canvas)"""
         info = self.info
         ih, iw = info.height, info.width
         colors = 1 if info.colour_space == CE_GRAY else 3
@@ -1025,7 +1082,7 @@ class JXLDecoder:
         if bh <= 0 or bw <= 0:
             return
         has_extra = info.num_extra > 0
-        for c in range(len(self.canvas)):
+        for c in range(first, len(self.canvas)):
             if c >= colors:
                 e = c - colors
                 mode, alpha_ch, clamp, source = fr.ec_blend_mode[e], fr.ec_blend_alpha[e], fr.ec_blend_clamp[e], fr.ec_blend_source[e]
@@ -1249,14 +1306,20 @@ class JXLDecoder:
             xyb_done = False
             rp = None
             resident = getattr(be, "resident", False) and colors == 3  # row f4: the stages after decodeFrame chained on the device
+            # device_output: this frame is the image (the conditions of __init__'s docstring that the header settles)
+            direct = getattr(self, "device_output", False) and resident and colors_img == 3 and fr.type == REGULAR_FRAME and \
+                bool(fr.is_last) and fr.lf_level == 0 and self.canvas[0] is None and fr.y0 == 0 and fr.x0 == 0 and \
+                fr.width * fr.upsampling == info.width and fr.height * fr.upsampling == info.height and fr.blend_mode == abi.BLEND_REPLACE
+            self.stats[-1]["output"] = "host"
             if fr.encoding == VARDCT:
                 # an LF frame's buffers are read back as XYB LF coefficients (LFCoefficients.java:44-57) and are stored
                 # BEFORE performColorTransforms (JXLCodestreamDecoder.java:615-617): never fuse the inverse XYB into them
                 fuse_xyb = bool(info.xyb_encoded) and simple and fr.lf_level == 0 and fr.type != LF_FRAME
                 # frames with stages between decodeFrame and the colour transform keep their colour planes on the device
                 # through those stages (row f4); LF frames / lfBuffer consumers need the padded planes on the host
-                if not simple and resident and fr.lf_level == 0 and fr.type != LF_FRAME:
-                    rp = self._vardct_frame(fr, False, keep=(fr.height, fr.width))
+                if (not simple or direct) and resident and fr.lf_level == 0 and fr.type != LF_FRAME:
+                    rp = self._vardct_frame(fr, fuse_xyb, keep=(fr.height, fr.width))  # (fuse_xyb: simple frames only)
+                    xyb_done = fuse_xyb
                     for c in range(3):
                         buffers[c] = np.zeros((fr.height, fr.width), F)  # stand-ins until the chained tail downloads
                 else:
@@ -1315,10 +1378,11 @@ class JXLDecoder:
                     buffers[c] = be.upsample(self._to_float(buffers[c], depth), k, wts)
             noise = None
             if resident:
-                self._chained_tail(fr, rp, buffers, colors, save, xyb_done)
+                rp = self._chained_tail(fr, rp, buffers, colors, save, xyb_done, keep=direct)
             elif fr.has_noise:
                 h, w = buffers[0].shape
                 noise = be.noise_init(h, w, (self.visibleFrames << 32) | self.invisibleFrames, fr.group_dim, colors)
+            direct = direct and rp is not None
             if not resident and save and fr.save_before_ct:
                 self.reference[fr.save_as_reference] = [b.copy() for b in buffers]
             if not resident and fr.num_patches:
@@ -1349,7 +1413,22 @@ class JXLDecoder:
                     planes = be.ycbcr(planes)
                 for c in range(3):
                     buffers[c] = np.ascontiguousarray(planes[c])
+            if direct and getattr(self, "trace", None) is not None:  # a listener wants the samples: a copy comes down, the planes stay
+                planes = rp.download()
+                self.stats[-1]["plane_moves"].append("trace")
+                for c in range(3):
+                    buffers[c] = planes[c]
             self._trace("xyb", buffers, False)  # JXLCodestreamDecoder.java:637: the frame's buffers after performColorTransforms
+            if direct:
+                # the frame replaces the whole canvas: its colour planes are the image's; the extra channels take the usual way
+                self.stats[-1]["output"] = "device"
+                for c in range(3, len(self.canvas)):
+                    self.canvas[c] = np.zeros((info.height, info.width), F)
+                self._blend_frame(fr, buffers, colors, first=3)
+                if info.orientation != 1:
+                    rp.orient(info.orientation)
+                extras = [be.orient(np.ascontiguousarray(b), info.orientation) if info.orientation != 1 else b for b in self.canvas[3:]]
+                return JXLImage([None] * 3 + extras, info, be, resident=rp)
             if self.canvas[0] is None:
                 for c in range(len(self.canvas)):
                     self.canvas[c] = np.zeros((info.height, info.width), buffers[0].dtype)
@@ -1369,8 +1448,12 @@ class JXLDecoder:
 
 # ---- PNGWriter (J/io/PNGWriter.java) ---------------------------------------------------------------------------
 class PNGWriter:
-    def __init__(self, image, bitDepth=-1, hdr=False, peakDetect=PEAK_DETECT_AUTO, deflateLevel=6, deviceColor=False):
-        """deviceColor: JXLImage.transform(..., device=True)"""
+    def __init__(self, image, bitDepth=-1, hdr=False, peakDetect=PEAK_DETECT_AUTO, deflateLevel=6, deviceColor=False, deviceSamples=False):
+        """deviceColor: JXLImage.transform(..., device=True).
+        deviceSamples: the colour management and the packing in ONE device pass (backend.png_samples, or
+        ResidentPlanes.pngSamples when the image's colour planes are on the device: JXLDecoder(device_output=True)), after at
+        most one peak call; the same samples as deviceColor gives, byte for byte. bus_bytes = (bytes up, bytes down) of the
+        sample planes. A backend without png_samples is an error."""
         if bitDepth <= 0:
             bitDepth = 16 if (hdr or image.info.bits_per_sample > 8) else 8
         if bitDepth not in (8, 16):
@@ -1380,8 +1463,11 @@ class PNGWriter:
         primaries = PRI_BT2100 if hdr else PRI_SRGB
         tf = TF_PQ if hdr else TF_SRGB
         self.has_icc = image.has_icc
+        self.bus_bytes = None
+        if deviceSamples and self._device_samples(image, bitDepth, primaries, tf, peakDetect, deflateLevel):
+            return
         if not image.has_icc:
-            image = image.transform(primaries, WP_D65, tf, peakDetect, device=deviceColor)
+            image = image.transform(primaries, WP_D65, tf, peakDetect, device=deviceColor or deviceSamples)
         self.bitDepth = bitDepth
         self.width, self.height = image.getWidth(), image.getHeight()
         self.alphaIndex = image.getAlphaIndex()
@@ -1397,6 +1483,55 @@ class PNGWriter:
         tagged += [bitDepth] * (4 - len(tagged))
         # PNGWriter.java:79-111 + the writeIDAT sample order: one device pass
         self.samples = image.backend.pack(color, bitDepth, alpha, image.isAlphaPremultiplied() and alpha is not None, tagged, True)
+
+    def _device_samples(self, image, bitDepth, primaries, tf, peakDetect, deflateLevel):
+        """the constructor with deviceSamples. False (nothing done): a grey image that is tone-mapped -- PNGWriter then takes
+        plane 0 and plane 1 + alphaIndex of the three-plane result for its grey layout, which the one-pass kernel has no
+        output for; the constructor runs the device passes one by one (deviceColor) and bus_bytes stays None."""
+        be = image.backend
+        if not hasattr(be, "png_samples"):
+            raise TypeError("deviceSamples needs a backend with png_samples")
+        colors = image.getColorChannelCount()
+        rp = image.resident
+        h, w = image.getHeight(), image.getWidth()
+        up = 0
+        planes = [np.broadcast_to(F(0), (h, w))] * 3 if rp is not None else None  # stand-ins: the samples are on the device
+
+        def peak_of(pl, **front):
+            nonlocal up
+            if rp is not None:
+                return rp.colorPeak(**front)
+            up += sum(a.nbytes for a in pl) if front.get("matrix") is not None else pl[min(1, len(pl) - 1)].nbytes
+            return be.color_peak(pl, **front)
+        if colors == 1 and not image.has_icc and not (_prim_matches(primaries, image.primariesXY) and _xy_matches(WP_D65, image.whiteXY)):
+            return False  # (before the plan is made: the peak, if one is needed, is then taken once, by transform())
+        plan = None if image.has_icc else image._color_plan(primaries, WP_D65, tf, peakDetect, peak_of, planes=planes)
+        if plan is not None:
+            planes, params = plan[0], plan[1]
+        else:  # the image as it is: every colour stage off; integer planes are cast with their depth's maximum (PNGWriter's coercion)
+            if planes is None:
+                planes = [image.buffer[c] for c in range(colors)]
+                if len({a.dtype for a in planes}) != 1:
+                    planes = [image._as_float(c) for c in range(colors)]
+            params = dict(inMax=[(1 << image.bitDepths[c]) - 1 for c in range(colors)])
+        self.bitDepth = bitDepth
+        self.width, self.height = w, h
+        self.alphaIndex = image.getAlphaIndex()
+        self.colorChannels = colors
+        self.colorMode = (4 if self.alphaIndex >= 0 else 0) if colors == 1 else (6 if self.alphaIndex >= 0 else 2)
+        self.deflateLevel = deflateLevel
+        alpha = np.ascontiguousarray(image.extraChannel(self.alphaIndex)) if self.alphaIndex >= 0 else None
+        kw = dict(premultiplied=image.isAlphaPremultiplied() and alpha is not None, bitDepth=bitDepth, bigEndian=True,
+                  alphaDepth=image.getTaggedBitDepth(colors + self.alphaIndex) if alpha is not None else None,
+                  colorDepth=image.getTaggedBitDepth(0), **params)
+        if rp is not None:
+            self.samples = rp.pngSamples(alpha, **kw)
+        else:
+            planes = [np.ascontiguousarray(a) for a in planes]
+            self.samples = be.png_samples(planes, alpha, **kw)
+            up += sum(a.nbytes for a in planes)
+        self.bus_bytes = (up + (alpha.nbytes if alpha is not None else 0), self.samples.nbytes)
+        return True
 
     @staticmethod
     def _chunk(tag, payload):

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from ._lib import Context, check  # noqa: F401  (re-export)
+from ._lib import Context, IllegalStateException, check  # noqa: F401  (re-export)
 
 
 def _p3(planes, ctype):
@@ -216,6 +216,47 @@ def determinePeak(ctx, planes, **params):
     peak = C.c_float(0)
     ctx.call("jxl_stage_color_peak", _pv(planes), h, w, C.byref(p), C.byref(peak))
     return np.float32(peak.value)
+
+
+def pngParams(planes, shape, alpha=None, premultiplied=False, bitDepth=8, bigEndian=False, alphaDepth=None, colorDepth=None, **color):
+    """jxl_png_params: colorParams(planes, **color) (maxValue stays 0) plus PNGWriter's arguments. alpha: the alpha plane (its
+    dtype tells int32 from float32) or None; alphaDepth / colorDepth: the tagged depths (default: bitDepth)"""
+    p = abi.PngParams()
+    p.color = colorParams(planes, **color)
+    p.height, p.width = int(shape[0]), int(shape[1])
+    p.has_alpha, p.premultiplied = int(alpha is not None), int(bool(premultiplied))
+    p.bit_depth, p.big_endian = int(bitDepth), int(bool(bigEndian))
+    p.alpha_is_int = int(alpha is not None and alpha.dtype == np.int32)
+    p.alpha_tagged_depth = int(bitDepth if alphaDepth is None else alphaDepth)
+    p.color_tagged_depth = int(bitDepth if colorDepth is None else colorDepth)
+    return p
+
+
+def _png_out(p, shape):
+    nch = (3 if (p.color.n_planes == 3 or p.color.use_matrix) else 1) + p.has_alpha
+    return np.empty((shape[0], shape[1], nch), np.uint8 if p.bit_depth == 8 else np.uint16)
+
+
+def _png_alpha(alpha, shape):
+    if alpha is None:
+        return None
+    a = np.ascontiguousarray(alpha)
+    if a.dtype not in (np.int32, np.float32) or a.shape != tuple(shape):
+        raise TypeError("the alpha plane must be int32 or float32 of the colour planes' shape")
+    return a
+
+
+def pngSamples(ctx, planes, alpha=None, **params):
+    """PNGWriter's samples of 1 or 3 colour planes (2-D, all int32 or all float32) and an optional alpha plane in one device
+    pass (jxl_stage_png_samples): colorConvert(planes, maxValue=0, ...) followed by packSamples, byte for byte, without the
+    float planes in between. params: pngParams' keywords. Returns [h][w][channels] uint8 / uint16."""
+    planes = [np.ascontiguousarray(a) for a in planes]
+    shape = planes[0].shape
+    a = _png_alpha(alpha, shape)
+    p = pngParams(planes, shape, alpha=a, **params)
+    out = _png_out(p, shape)
+    ctx.call("jxl_stage_png_samples", _pv(planes), _vp(a), C.byref(p), _vp(out))
+    return out
 
 
 def pack_sparse(planes, wide=False):
@@ -491,6 +532,19 @@ class ResidentPlanes:
 
     def __init__(self, ctx):
         self.ctx = ctx
+        self._claim()
+
+    def _claim(self):
+        """a context has ONE set of resident planes: the object made last (keepPlanes, upload) or refilled last (replace) owns it"""
+        self.gen = self.ctx.planes_gen = getattr(self.ctx, "planes_gen", 0) + 1
+
+    def live(self):
+        """the context's resident planes are still this object's (no later frame or upload has taken them)"""
+        return getattr(self.ctx, "planes_gen", 0) == self.gen
+
+    def _need_live(self):
+        if not self.live():
+            raise IllegalStateException(abi.JXL_ERR_STATE, "the context's resident planes now hold a later frame or upload")
 
     @classmethod
     def upload(cls, ctx, planes):
@@ -541,6 +595,33 @@ class ResidentPlanes:
     def ycbcr(self):
         self.ctx.call("jxl_planes_ycbcr")
 
+    def _stand_ins(self):
+        return [np.broadcast_to(np.float32(0), self.shape)] * 3  # shape and dtype for colorParams; never read
+
+    def orient(self, orientation):
+        """JXLCodestreamDecoder.transposeBuffer of the three planes, on the device (jxl_planes_orient)"""
+        self._need_live()
+        self.ctx.call("jxl_planes_orient", int(orientation))
+
+    def colorPeak(self, **params):
+        """determinePeak of the planes as they stand (jxl_planes_color_peak; colorParams' keywords)"""
+        self._need_live()
+        p = colorParams(self._stand_ins(), **params)
+        peak = C.c_float(0)
+        self.ctx.call("jxl_planes_color_peak", C.byref(p), C.byref(peak))
+        return np.float32(peak.value)
+
+    def pngSamples(self, alpha=None, **params):
+        """pngSamples of the planes as they stand (jxl_planes_png_samples): only the alpha plane goes up, only the PNG's
+        samples come down"""
+        self._need_live()
+        shape = self.shape
+        a = _png_alpha(alpha, shape)
+        p = pngParams(self._stand_ins(), shape, alpha=a, **params)
+        out = _png_out(p, shape)
+        self.ctx.call("jxl_planes_png_samples", _vp(a), C.byref(p), _vp(out))
+        return out
+
     def download(self):
         h, w = self.shape
         out = np.empty((3, h, w), np.float32)
@@ -550,6 +631,7 @@ class ResidentPlanes:
     def replace(self, planes):
         pl = _planes(planes, np.float32)
         self.ctx.call("jxl_planes_upload", _p3(pl, C.c_float), pl[0].shape[0], pl[0].shape[1])
+        self._claim()
 
 
 class ModularChannel:
