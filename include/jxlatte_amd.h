@@ -696,6 +696,28 @@ jxl_status jxl_planes_color_peak(jxl_ctx* ctx, const jxl_color_params* p, float*
  * JXL_ERR_STATE: no resident planes, or an orientation outside 1..8. */
 jxl_status jxl_planes_orient(jxl_ctx* ctx, int32_t orientation);
 
+/* ---- the PFM's samples in one pass: replaces the body of PFMWriter.write (PFMWriter.java:30-48) after the header ----
+ * The planes are the image's own samples (image.getBuffer(false), :30): no colour transform, no peak scale, no transfer
+ * function. An int32 plane is cast as castToFloat(image.getTaggedBitDepth(c)) casts it (:33-35; ImageBuffer.java:99-101,
+ * 112-127): max = ~(~0 << depth) in Java int arithmetic, sample = (float)v * (1.0f / max), the conversion rounded before the one
+ * f32 multiply. Every sample leaves as DataOutputStream.writeFloat writes it (:46): Float.floatToIntBits, so every NaN is
+ * 0x7fc00000 while -0.0f, the infinities and the subnormals keep their bits, most significant byte first. Channels are
+ * interleaved per pixel, pixels left to right, rows bottom to top (:43-47). The header line (:27-29) stays with the caller. */
+typedef struct jxl_pfm_params {
+    int32_t height, width;
+    int32_t n_planes;           /* 1: CE_GRAY ("Pf"), 3: every other image ("PF"); alpha and extra channels are never written */
+    int32_t is_int[3];          /* plane c holds int32 samples (else float); planes of mixed kind are legal */
+    int32_t tagged_depth[3];    /* image.getTaggedBitDepth(c), looked at for the int32 planes only */
+} jxl_pfm_params;
+/* in: n_planes host planes of height * width samples. out: 4 * n_planes * width * height bytes. One upload, one launch, one
+ * download. JXL_ERR_INVALID_ARGUMENT (nothing queued, out untouched): sizes below 1, n_planes other than 1 or 3, an int32 plane
+ * whose depth gives max < 1 ("invalid Max Value", ImageBuffer.java:115-116: depth 0 or 32), a null pointer. */
+jxl_status jxl_stage_pfm_samples(jxl_ctx* ctx, const void* const in[3], const jxl_pfm_params* p, void* out);
+/* The same launch on the three resident float planes, as they stand (after jxl_planes_orient): n_planes 3, no is_int, height
+ * and width theirs -- anything else is JXL_ERR_INVALID_ARGUMENT. out is filled on return: the only bytes that cross the bus are
+ * the PFM's (PFMWriter.java:30-48 without image.getBuffer). JXL_ERR_STATE without resident planes. */
+jxl_status jxl_planes_pfm_samples(jxl_ctx* ctx, const jxl_pfm_params* p, void* out);
+
 /* ---- Modular path: replaces ModularStream.applyTransforms squeeze/RCT branches ---- */
 /* Default squeeze parameter list of ModularStream.java:110-131 for a channel list whose
  * first nb_meta channels are meta channels. Returns the count (<= cap) or a negative status. */

@@ -172,6 +172,10 @@ public final class NativeBackend implements AutoCloseable {
     public native void planesPngSamples(ByteBuffer alpha, ByteBuffer params, ByteBuffer out);         // jxl_planes_png_samples
     public native float planesColorPeak(ByteBuffer params);                                           // jxl_planes_color_peak
     public native void planesOrient(int orientation);                                                 // jxl_planes_orient
+    // the PFM's samples in one pass: params = {height, width, n_planes, is_int[3], tagged_depth[3]}; i1, i2 null for a grey image;
+    // out holds exactly 4 * n_planes * width * height bytes
+    public native void stagePfmSamples(ByteBuffer i0, ByteBuffer i1, ByteBuffer i2, int[] params, ByteBuffer out);  // jxl_stage_pfm_samples
+    public native void planesPfmSamples(int[] params, ByteBuffer out);                                // jxl_planes_pfm_samples
 
     // ---- Modular: plan once (begin), run, read channel by channel
     public static native int[] modularDefaultSqueezeParams(int[] widths, int[] heights, int nbMeta);  // jxl_modular_default_squeeze_params

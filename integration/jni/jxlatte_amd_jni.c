@@ -1201,6 +1201,49 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesOrien
     CHECK(jxl_planes_orient(c, orientation));
 }
 
+/* ---- the PFM's samples in one pass (PFMWriter.write after its header, PFMWriter.java:30-48):
+ * params: {height, width, n_planes, is_int[3], tagged_depth[3]}; i1, i2 are null for a grey image. The output buffer holds exactly
+ * the file's bytes after the header: its capacity must EQUAL 4 * n_planes * width * height. ---- */
+static int pfm_params(JNIEnv* e, jintArray params, jxl_pfm_params* p) {
+    jint pv[9];
+    if (!get_ints(e, params, 9, pv)) return 0;
+    p->height = pv[0]; p->width = pv[1]; p->n_planes = pv[2];
+    for (int i = 0; i < 3; i++) { p->is_int[i] = pv[3 + i]; p->tagged_depth[i] = pv[6 + i]; }
+    if (p->height < 1 || p->width < 1 || (p->n_planes != 1 && p->n_planes != 3)) {
+        bad_arg(e, "jxlatte_amd: pfm parameters");
+        return 0;
+    }
+    return 1;
+}
+/* a direct buffer of exactly `bytes` bytes */
+static int pfm_out_fits(JNIEnv* e, jobject out, jlong bytes) {
+    if (has_room(e, out, bytes) && (*e)->GetDirectBufferCapacity(e, out) == bytes) return 1;
+    bad_arg(e, "jxlatte_amd: the PFM output buffer must hold exactly 4 * n_planes * width * height bytes");
+    return 0;
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stagePfmSamples(JNIEnv* e, jobject self, jobject i0, jobject i1, jobject i2,
+        jintArray params, jobject out) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_pfm_params p;
+    if (!pfm_params(e, params, &p)) return;
+    const jlong plane = 4 * area(p.height, p.width);
+    NEED(i0, plane);
+    if (p.n_planes == 3) { NEED(i1, plane); NEED(i2, plane); }
+    if (!pfm_out_fits(e, out, plane * p.n_planes)) return;
+    const void* in[3] = {ADDR(i0), p.n_planes == 3 ? ADDR(i1) : NULL, p.n_planes == 3 ? ADDR(i2) : NULL};
+    CHECK(jxl_stage_pfm_samples(c, in, &p, ADDR(out)));
+}
+
+/* the same on the resident planes: height and width must be theirs (the library checks) */
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesPfmSamples(JNIEnv* e, jobject self, jintArray params, jobject out) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_pfm_params p;
+    if (!pfm_params(e, params, &p)) return;
+    if (!pfm_out_fits(e, out, 4 * area(p.height, p.width) * p.n_planes)) return;
+    CHECK(jxl_planes_pfm_samples(c, &p, ADDR(out)));
+}
+
 /* ---- Modular: plan once, run, read channel by channel (ModularStream.applyTransforms, ModularStream.java:110-131) ---- */
 JNIEXPORT jintArray JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_modularDefaultSqueezeParams(JNIEnv* e, jclass k, jintArray widths,
         jintArray heights, jint nbMeta) {

@@ -1,6 +1,6 @@
-"""python -m jxlatte_amd in.jxl [out.png] -- the reference's CLI (J/JXLatte.java) on the MI355X back-end:
+"""python -m jxlatte_amd in.jxl [out.png | out.pfm] -- the reference's CLI (J/JXLatte.java) on the MI355X back-end:
 decodes a JPEG XL file (C++ front-end -> device library) and writes a PNG (HDR images as 16-bit BT.2100 PQ, like
---png-hdr=auto). Needs a GPU: there is no CPU fallback."""
+--png-hdr=auto) or a PFM (the image's own float samples). Needs a GPU: there is no CPU fallback."""
 import argparse
 import sys
 import time
@@ -10,6 +10,11 @@ def parser():
     ap = argparse.ArgumentParser(prog="python -m jxlatte_amd", description=__doc__)
     ap.add_argument("input")
     ap.add_argument("output", nargs="?")
+    ap.add_argument("--format", choices=["png", "pfm"], default=None,
+                    help="the output format; without it an output name ending in .pfm (any letter case) gives a PFM and EVERY "
+                         "other name a PNG (the reference stops with 'Unable to determine output format' on an unknown "
+                         "extension; that exit is not adopted). A PFM holds the image's own samples: the --png-* options "
+                         "and --device-color are ignored for it")
     ap.add_argument("--png-hdr", choices=["auto", "yes", "no"], default="auto")
     ap.add_argument("--png-depth", type=int, default=-1)
     ap.add_argument("--info", action="store_true", help="print the image / frame headers and stop")
@@ -30,8 +35,18 @@ def parser():
     ap.add_argument("--device-png", action="store_true",
                     help="from the coefficients to the PNG's samples on the device: a frame that is the whole image leaves its colour "
                          "planes there (JXLDecoder device_output), and colour management and sample packing are one kernel "
-                         "(jxl_planes_png_samples / jxl_stage_png_samples); the same bytes as --device-color")
+                         "(jxl_planes_png_samples / jxl_stage_png_samples); the same bytes as --device-color. With PFM output: "
+                         "the PFM's samples in one kernel (jxl_planes_pfm_samples / jxl_stage_pfm_samples); the same bytes as "
+                         "without it")
     return ap
+
+
+def output_format(a):
+    """'png' or 'pfm' for the parsed arguments: --format, else the output name's extension (JXLatte.java:136-145, 266-276), with
+    PNG for every name that does not end in .pfm"""
+    if a.format:
+        return a.format
+    return "pfm" if a.output and a.output.lower().endswith(".pfm") else "png"
 
 
 def main(argv=None):
@@ -43,7 +58,7 @@ def main(argv=None):
         print("Image: %s\n    Size: %dx%d\n    Bit Depth: %d\n    Extra Channels: %d\n    XYB Encoded: %s\n    Orientation: %d" % (
             a.input, im.width, im.height, im.bits_per_sample, im.num_extra, bool(im.xyb_encoded), im.orientation))
         return 0
-    from .decoder import PEAK_DETECT_AUTO, PEAK_DETECT_OFF, PEAK_DETECT_ON, DeviceBackend, JXLDecoder, PNGWriter
+    from .decoder import PEAK_DETECT_AUTO, PEAK_DETECT_OFF, PEAK_DETECT_ON, DeviceBackend, JXLDecoder, PFMWriter, PNGWriter
     PEAK_DETECT = {"auto": PEAK_DETECT_AUTO, "on": PEAK_DETECT_ON, "off": PEAK_DETECT_OFF}
     t0 = time.time()
     backend = DeviceBackend(a.device)
@@ -57,7 +72,10 @@ def main(argv=None):
     for i, st in enumerate(dec.stats):
         print("    frame %d: %s %dx%d, %d groups" % (i, st["encoding"], st["width"], st["height"], st["groups"]), file=sys.stderr)
     print("Decoded %dx%d in %.3f s" % (image.getWidth(), image.getHeight(), t1 - t0), file=sys.stderr)
-    if a.output:
+    if a.output and output_format(a) == "pfm":
+        with open(a.output, "wb") as f:
+            PFMWriter(image, deviceSamples=a.device_png).write(f)
+    elif a.output:
         hdr = image.isHDR() if a.png_hdr == "auto" else a.png_hdr == "yes"
         with open(a.output, "wb") as f:
             PNGWriter(image, bitDepth=16 if hdr else a.png_depth, hdr=hdr, peakDetect=PEAK_DETECT[a.png_peak_detect],

@@ -164,6 +164,12 @@ class PngParams(C.Structure):
                 ("alpha_tagged_depth", C.c_int32), ("color_tagged_depth", C.c_int32)]
 
 
+class PfmParams(C.Structure):
+    """struct jxl_pfm_params"""
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("n_planes", C.c_int32), ("is_int", C.c_int32 * 3),
+                ("tagged_depth", C.c_int32 * 3)]
+
+
 class SplineDesc(C.Structure):
     """struct jxl_spline_desc (SplinesBundle.java + the two LFChannelCorrelation factors)"""
     _fields_ = [("quant_adjust", C.c_int32), ("n_splines", C.c_int32), ("n_control", C.POINTER(C.c_int32)),

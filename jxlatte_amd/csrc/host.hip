@@ -3,6 +3,7 @@
 // point needs a HIP device and fails with JXL_ERR_DEVICE otherwise.
 #include "jxl_internal.h"
 #include "modular_tend.h"  // kSqueezeSafeIn (jxl_modular_begin picks the plan by it)
+#include "pfm_check.h"     // what the PFM entries refuse
 
 #include <algorithm>
 #include <chrono>
@@ -4094,6 +4095,64 @@ jxl_status jxl_planes_orient(jxl_ctx* c, int32_t orientation) {
     }
     if (orientation > 4) std::swap(c->rp_h, c->rp_w);
     return JXL_OK;
+}
+
+// ---- the PFM's samples in one pass (k_pfm.hip): PFMWriter.write after its header ----
+}  // extern "C"
+namespace {
+// the checks of pfm_check.h on one jxl_pfm_params, and the kernel's arguments (the plane and output pointers are the caller's)
+jxl_status pfm_args(jxl_ctx* c, const jxl_pfm_params* p, const void* out, PfmArgs* a) {
+    const char* bad = out ? pfm_check(p, a->scale) : "pfm samples: null argument";
+    if (bad) return fail(c, JXL_ERR_INVALID_ARGUMENT, "%s", bad);
+    a->h = p->height;
+    a->w = p->width;
+    a->n_planes = p->n_planes;
+    for (int i = 0; i < 3; i++) {
+        a->in[i] = nullptr;
+        a->is_int[i] = (i < p->n_planes && p->is_int[i]) ? 1 : 0;
+    }
+    a->out = nullptr;
+    return JXL_OK;
+}
+
+// launch, download the samples
+jxl_status pfm_run(jxl_ctx* c, PfmArgs& a, Tmp& t, void* out) {
+    const size_t ob = sizeof(float) * (size_t)a.n_planes * (size_t)a.h * (size_t)a.w;
+    if (!(a.out = t.up<uint8_t>(nullptr, ob))) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    launch_pfm_samples(a, c->stream);
+    jxl_status st = finish(c);
+    if (st) return st;
+    HIP_TRY(c, hipMemcpy(out, a.out, ob, hipMemcpyDeviceToHost));
+    return JXL_OK;
+}
+}  // namespace
+extern "C" {
+
+jxl_status jxl_stage_pfm_samples(jxl_ctx* c, const void* const in[3], const jxl_pfm_params* p, void* out) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    PfmArgs a;
+    if ((st = pfm_args(c, p, out, &a))) return st;
+    if (!in) return fail(c, JXL_ERR_INVALID_ARGUMENT, "pfm samples: null argument");
+    for (int i = 0; i < a.n_planes; i++)
+        if (!in[i]) return fail(c, JXL_ERR_INVALID_ARGUMENT, "pfm samples: null plane %d", i);
+    Tmp t;
+    for (int i = 0; i < a.n_planes; i++)
+        if (!(a.in[i] = t.up((const uint32_t*)in[i], (size_t)a.h * a.w))) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    return pfm_run(c, a, t, out);
+}
+
+jxl_status jxl_planes_pfm_samples(jxl_ctx* c, const jxl_pfm_params* p, void* out) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (c->rp_h <= 0) return fail(c, JXL_ERR_STATE, "no resident planes");
+    PfmArgs a;
+    if ((st = pfm_args(c, p, out, &a))) return st;
+    if (p->n_planes != 3 || a.is_int[0] || a.is_int[1] || a.is_int[2] || p->height != c->rp_h || p->width != c->rp_w)
+        return fail(c, JXL_ERR_INVALID_ARGUMENT, "pfm samples: the resident planes are three %d x %d float planes", c->rp_h, c->rp_w);
+    for (int i = 0; i < 3; i++) a.in[i] = c->rp[i].p;
+    Tmp t;
+    return pfm_run(c, a, t, out);
 }
 
 }  // extern "C"

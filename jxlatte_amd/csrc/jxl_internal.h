@@ -238,6 +238,17 @@ struct PngArgs {
 };
 // n_color: 3 when c.n_planes == 3 or c.use_matrix, else 1
 void launch_png_samples(const PngArgs& p, int n_color, hipStream_t s);
+// the PFM's samples from the image's planes in one pass (k_pfm.hip): cast of the int32 planes, floatToIntBits, big-endian words,
+// channels interleaved, rows bottom to top (PFMWriter.java:22-49)
+struct PfmArgs {
+    const void* in[3];  // device planes of h * w float or int32 samples; [0, n_planes) are read
+    int h, w;
+    int n_planes;       // 1 or 3
+    int is_int[3];      // the plane holds int32 samples
+    float scale[3];     // 1.0f / max of the plane's tagged depth (int32 planes)
+    void* out;          // h * w * n_planes words
+};
+void launch_pfm_samples(const PfmArgs& p, hipStream_t s);
 // PQ as a table of quadratic segments (jxl_fastpow.h): kPqTableFloats floats = float4 {a0 hi, a0 lo, a1, a2} per segment
 constexpr int kPqTableFloats = (129 - 87) * 128 * 4;
 void build_pq_table(float* out /* [kPqTableFloats] */);

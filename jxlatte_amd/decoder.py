@@ -579,6 +579,10 @@ class DeviceBackend:
         """PNGWriter's samples in one pass (host.pngSamples; the keywords are host.pngParams')"""
         return self.host.pngSamples(self.ctx, planes, alpha, **params)
 
+    def pfm_samples(self, planes, tagged):
+        """PFMWriter's samples in one pass (host.pfmSamples)"""
+        return self.host.pfmSamples(self.ctx, planes, tagged)
+
     def pack(self, planes, bit_depth, alpha, premultiplied, tagged, big_endian):
         return self.host.packSamples(self.ctx, planes, bit_depth, alpha=alpha, premultiplied=premultiplied, taggedDepth=tagged,
                                      bigEndian=big_endian)
@@ -1549,6 +1553,50 @@ class PNGWriter:
         raw = np.concatenate([np.zeros((self.height, 1), np.uint8), rows], axis=1).tobytes()  # filter type 0 per row
         out.write(self._chunk(b"IDAT", zlib.compress(raw, self.deflateLevel)))
         out.write(self._chunk(b"IEND", b""))
+
+
+# ---- PFMWriter (J/io/PFMWriter.java) ---------------------------------------------------------------------------
+class PFMWriter:
+    def __init__(self, image, deviceSamples=False):
+        """The image's own samples as a PFM: no colour transform, no peak scale, no transfer function (PFMWriter.java:30).
+        deviceSamples: cast, floatToIntBits, byte order, interleaving and the row flip in ONE device pass
+        (ResidentPlanes.pfmSamples when the image's colour planes are on the device: JXLDecoder(device_output=True); else
+        backend.pfm_samples on the host arrays); the same bytes as the default path. bus_bytes = (bytes up, bytes down) of
+        the sample planes. A backend without pfm_samples is an error."""
+        self.width, self.height = image.getWidth(), image.getHeight()
+        self.gray = image.colorEncoding == CE_GRAY
+        colors = 1 if self.gray else 3
+        tagged = [image.getTaggedBitDepth(c) for c in range(colors)]
+        self.bus_bytes = None
+        if deviceSamples:
+            be = image.backend
+            if not hasattr(be, "pfm_samples"):
+                raise TypeError("deviceSamples needs a backend with pfm_samples")
+            if image.onDevice() and (image._buffer[0] is None or image.resident.live()):  # (else the downloaded host arrays)
+                self.samples = image.resident.pfmSamples()
+                up = 0
+            else:
+                planes = [np.ascontiguousarray(a) for a in image.getBuffer(False)[:colors]]
+                self.samples = be.pfm_samples(planes, tagged)
+                up = sum(a.nbytes for a in planes)
+            self.bus_bytes = (up, self.samples.nbytes)
+            return
+        words = []
+        for c, b in enumerate(image.getBuffer(False)[:colors]):
+            if b.dtype != np.float32:  # ImageBuffer.castToFloat(depth): Java int arithmetic, shift counts modulo 32
+                maxv = ~((-1 << (tagged[c] & 31)) & 0xffffffff) & 0xffffffff
+                if maxv < 1:
+                    raise ValueError("invalid Max Value")
+                b = b.astype(F) * F(F(1) / F(maxv))
+            w = np.ascontiguousarray(b, F).view(np.uint32)
+            words.append(np.where(np.isnan(b), np.uint32(0x7fc00000), w))  # Float.floatToIntBits
+        # bottom to top, channels interleaved, DataOutputStream.writeFloat's byte order
+        rows = np.ascontiguousarray(np.stack(words, axis=-1)[::-1])
+        self.samples = rows.astype(">u4").view(np.uint8).reshape(self.height, self.width, colors, 4)
+
+    def write(self, out):
+        out.write(("%s\n%d %d\n1.0\n" % ("Pf" if self.gray else "PF", self.width, self.height)).encode("ascii"))
+        out.write(self.samples.tobytes())
 
 
 def load_vardct_frame(source, ctx, transfer=abi.TRANSFER_NONE, out_format=abi.OUT_F32, sparse=False):

@@ -259,6 +259,32 @@ def pngSamples(ctx, planes, alpha=None, **params):
     return out
 
 
+def pfmParams(planes, shape, taggedDepths=None):
+    """jxl_pfm_params of 1 or 3 planes (each one's dtype tells int32 from float32). taggedDepths: image.getTaggedBitDepth(c)
+    per plane, looked at for the int32 planes only"""
+    p = abi.PfmParams()
+    p.height, p.width, p.n_planes = int(shape[0]), int(shape[1]), len(planes)
+    for c, a in enumerate(planes[:3]):
+        p.is_int[c] = int(a.dtype == np.int32)
+        p.tagged_depth[c] = int(taggedDepths[c]) if taggedDepths is not None else 0
+    return p
+
+
+def pfmSamples(ctx, planes, taggedDepths=None):
+    """PFMWriter.write's samples of 1 (grey) or 3 planes (2-D; int32 and float32 may be mixed) in one device pass
+    (jxl_stage_pfm_samples): int32 planes cast with their tagged depth, Float.floatToIntBits, big-endian, channels interleaved,
+    rows bottom to top. Returns [h][w][planes] uint8 x 4: the file's bytes after the header."""
+    planes = [np.ascontiguousarray(a) for a in planes]
+    shape = planes[0].shape
+    for a in planes:
+        if a.dtype not in (np.int32, np.float32) or a.shape != shape or a.ndim != 2:
+            raise TypeError("the planes must be 2-D int32 or float32 arrays of one shape")
+    p = pfmParams(planes, shape, taggedDepths)
+    out = np.empty((shape[0], shape[1], len(planes), 4), np.uint8)
+    ctx.call("jxl_stage_pfm_samples", _pv(planes), C.byref(p), _vp(out))
+    return out
+
+
 def pack_sparse(planes, wide=False):
     """The sparse wire format of include/jxlatte_amd.h: the non-zero samples of a 2-D integer plane (at most 256 x 256: one
     group of one channel) as a uint32 array of entries in raster order -- narrow: value << 16 | y << 8 | x; wide: the words
@@ -620,6 +646,15 @@ class ResidentPlanes:
         p = pngParams(self._stand_ins(), shape, alpha=a, **params)
         out = _png_out(p, shape)
         self.ctx.call("jxl_planes_png_samples", _vp(a), C.byref(p), _vp(out))
+        return out
+
+    def pfmSamples(self):
+        """pfmSamples of the planes as they stand (jxl_planes_pfm_samples): nothing goes up, only the PFM's bytes come down"""
+        self._need_live()
+        shape = self.shape
+        p = pfmParams(self._stand_ins(), shape)
+        out = np.empty((shape[0], shape[1], 3, 4), np.uint8)
+        self.ctx.call("jxl_planes_pfm_samples", C.byref(p), _vp(out))
         return out
 
     def download(self):
