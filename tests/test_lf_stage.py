@@ -3,6 +3,8 @@
 import numpy as np
 import pytest
 
+import pixel_ref64
+import pixel_ref64_cases
 from conftest import assert_bits_equal
 from jxlatte_amd import abi, host, synth
 
@@ -73,26 +75,57 @@ def test_hip_lf_dequant(ctx, orc, shape, smooth):
     assert_bits_equal(got, exp, "lf %s" % (shape,))
 
 
+def assert_all_smoothing_regimes(q, sd, extra_precision, **kw):
+    """the smoothing gap (tests/pixel_ref64.py) of an interior of >= 50 cells lies in each regime -- 0.5 (factor 1: the output is the
+    sample again), between, >= 0.75 (factor 0: the weighted sum) -- for at least 10 % of the cells; under the production scaledDequant
+    every cell has gap 0.5, where a wrong weight, a wrong gap scale or a gap per channel would pass"""
+    gap = pixel_ref64.lf_stage(q, sd, extra_precision, smooth=True, **kw)[2]
+    if gap is not None and gap.size >= pixel_ref64_cases.LF_MIN_INTERIOR:
+        assert min(pixel_ref64.lf_regimes(gap)) >= pixel_ref64_cases.LF_MIN_SHARE, pixel_ref64.lf_regimes(gap)
+
+
 @pytest.mark.gpu
-def test_frame_with_integer_lf_matches_float_lf_path(ctx, orc):
-    """whole frame fed with the INTEGER LF image (device runs the LF stage) == frame fed with the oracle's dequantised LF"""
+@pytest.mark.parametrize("shape,ep,mul", pixel_ref64_cases.LF_CASES[:-1])
+def test_hip_lf_dequant_in_all_smoothing_regimes(ctx, orc, shape, ep, mul):
+    """scaledDequant x 4 (x 8 at extraPrecision 2), the inputs of tests/test_pixel_ref64_cpu.py: bit-exact against the oracle"""
+    q, sd, a = pixel_ref64_cases.lf_quant(shape), pixel_ref64_cases.lf_sd(mul), pixel_ref64_cases.LF_ARGS
+    assert_all_smoothing_regimes(q, sd, ep, **a)
+    got = host.LFCoefficients.dequantLFCoeff(ctx, q, sd, ep, a["x_factor_lf"], a["b_factor_lf"], True, a["base_corr_x"],
+                                             a["base_corr_b"], a["color_factor"])
+    assert_bits_equal(got, orc.lf_dequant(q, sd, extra_precision=ep, adaptive_smoothing=True, **a), "lf %s x%d" % (shape, mul))
+
+
+def _frame_with_integer_lf(ctx, orc, qmax, sd, extra_precision, check_regimes):
     frame = synth.make_vardct_frame(2304, 264, seed=17, mix="default")  # two LF groups
     rng = np.random.default_rng(5)
     lfq = []
+    corr = dict(base_corr_x=frame["params"].base_corr_x, base_corr_b=frame["params"].base_corr_b, color_factor=frame["params"].color_factor)
     for g in frame["lfgroups"]:
         h, w = g["dct_select"].shape
-        q = rng.integers(-400, 400, size=(3, h, w)).astype(np.int32)
+        q = rng.integers(-qmax, qmax, size=(3, h, w)).astype(np.int32)
         lfq.append(q)
-        lf = orc.lf_dequant(q, SD, extra_precision=1, x_factor_lf=120, b_factor_lf=131, adaptive_smoothing=True,
-                            base_corr_x=frame["params"].base_corr_x, base_corr_b=frame["params"].base_corr_b,
-                            color_factor=frame["params"].color_factor)
+        if check_regimes:
+            assert_all_smoothing_regimes(q, sd, extra_precision, x_factor_lf=120, b_factor_lf=131, **corr)
+        lf = orc.lf_dequant(q, sd, extra_precision=extra_precision, x_factor_lf=120, b_factor_lf=131, adaptive_smoothing=True, **corr)
         g["lf"] = [np.ascontiguousarray(lf[c]) for c in range(3)]
     exp = orc.vardct_frame(frame)
     p = abi.VarDCTParams.from_buffer_copy(frame["params"])
     fr = host.Frame(ctx, p, frame["weights"], frame["woffs"])
     for g, q in zip(frame["lfgroups"], lfq):
         fr.setLFGroup(dict(g, lf=None))
-        fr.setLFGroupQuant(g["lfg_y"], g["lfg_x"], q, SD, 1, 120, 131, True)
+        fr.setLFGroupQuant(g["lfg_y"], g["lfg_x"], q, sd, extra_precision, 120, 131, True)
     for grp in range(synth.num_groups(frame)):
         fr.putGroup(0, grp, synth.group_view(frame, grp))
     assert_bits_equal(fr.decodeFrame(), exp, "integer-LF frame")
+
+
+@pytest.mark.gpu
+def test_frame_with_integer_lf_matches_float_lf_path(ctx, orc):
+    """whole frame fed with the INTEGER LF image (device runs the LF stage) == frame fed with the oracle's dequantised LF"""
+    _frame_with_integer_lf(ctx, orc, 400, SD, 1, False)
+
+
+@pytest.mark.gpu
+def test_frame_with_integer_lf_in_all_smoothing_regimes(ctx, orc):
+    """the same with an LF image of +-2000 under scaledDequant x 4: every LF group's cells lie in all three regimes of the gap"""
+    _frame_with_integer_lf(ctx, orc, 2000, pixel_ref64_cases.lf_sd(4), 0, True)

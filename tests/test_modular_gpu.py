@@ -64,7 +64,7 @@ def test_squeeze_shape_errors(ctx):
         host.ModularChannel.inverseVerticalSqueeze(ctx, np.zeros((5, 4), np.int32), np.zeros((3, 4), np.int32))
 
 
-@pytest.mark.parametrize("rct_type", [0, 1, 2, 3, 4, 5, 6, 7 + 3, 14 + 6, 35 + 5, 41])
+@pytest.mark.parametrize("rct_type", range(42))
 def test_rct(ctx, orc, rct_type):
     v = np.random.default_rng(rct_type).integers(-2 ** 31, 2 ** 31 - 1, size=(3, 19, 23)).astype(np.int32)
     assert_bits_equal(host.rct(ctx, v, rct_type), orc.rct(v, rct_type), "rct %d" % rct_type)
@@ -76,6 +76,35 @@ def test_modular_to_float(ctx, orc):
     b = rng.integers(-70000, 70000, size=(31, 17)).astype(np.int32)
     assert_bits_equal(host.modularToFloat(ctx, a, None, 0.0037), orc.modular_to_float(a, None, 0.0037), "to float")
     assert_bits_equal(host.modularToFloat(ctx, a, b, 1.0 / 255), orc.modular_to_float(a, b, 1.0 / 255), "to float sum")
+    # the full int32 range: the conversion rounds (|v| > 2^24) and the sum wraps
+    a = rng.integers(-2 ** 31, 2 ** 31, size=(31, 17), dtype=np.int64).astype(np.int32)
+    b = rng.integers(-2 ** 31, 2 ** 31, size=(31, 17), dtype=np.int64).astype(np.int32)
+    a[0, :4], b[0, :4] = [2 ** 31 - 1, -2 ** 31, 2 ** 31 - 1, 16777217], [1, -1, 2 ** 31 - 1, 0]
+    wide = a.astype(np.int64) + b
+    assert (np.abs(a.astype(np.int64)) > 2 ** 24).mean() > 0.9 and ((wide > 2 ** 31 - 1) | (wide < -2 ** 31)).mean() > 0.2
+    for scale in (1.0 / 255, 0.0037):
+        assert_bits_equal(host.modularToFloat(ctx, a, None, scale), orc.modular_to_float(a, None, scale), "to float, full range")
+        assert_bits_equal(host.modularToFloat(ctx, a, b, scale), orc.modular_to_float(a, b, scale), "to float, wrapping sum")
+
+
+# the grid of launch_rct and launch_modular_to_float stops at 8192 blocks of 256 threads (k_modular.hip:553, :567): beyond
+# that many elements the kernels' loops take a second trip
+MODULAR_GRID_CAP = 8192 * 256
+
+
+def test_rct_second_loop_trip(ctx, orc):
+    """k_rct counts per plane, so each of the three planes is 2100 x 1000 (the 2 100 000 elements of a 3 x 700 x 1000 array)"""
+    v = np.random.default_rng(6).integers(-2 ** 31, 2 ** 31, size=(3, 2100, 1000), dtype=np.int64).astype(np.int32)
+    assert v[0].size > MODULAR_GRID_CAP
+    assert_bits_equal(host.rct(ctx, v, 6), orc.rct(v, 6), "rct 6 beyond the grid")
+
+
+def test_modular_to_float_second_loop_trip(ctx, orc):
+    rng = np.random.default_rng(7)
+    a = rng.integers(-2 ** 31, 2 ** 31, size=(3, 700, 1000), dtype=np.int64).astype(np.int32)
+    b = rng.integers(-2 ** 31, 2 ** 31, size=(3, 700, 1000), dtype=np.int64).astype(np.int32)
+    assert a.size > MODULAR_GRID_CAP
+    assert_bits_equal(host.modularToFloat(ctx, a, b, 1.0 / 255), orc.modular_to_float(a, b, 1.0 / 255), "to float beyond the grid")
 
 
 @pytest.mark.parametrize("w,h,ch", [(1, 1, 3), (8, 8, 3), (9, 9, 1), (53, 37, 3), (37, 130, 4), (640, 360, 3), (1920, 1080, 3)])
@@ -111,6 +140,33 @@ def test_apply_transforms_with_rct_and_rerun(ctx, orc):
     for i in range(3):
         assert_bits_equal(out[i], e[i], "rct only")
         assert np.array_equal(v[i], keep[i])
+
+
+@pytest.mark.parametrize("rct_type", range(42))
+def test_plan_rct_all_types(ctx, orc, rct_type):
+    """the plan path permutes the channels by pointer shuffling at its own place (host.hip, jxl_modular_begin): every type and
+    permutation behind the squeeze steps of the default plan"""
+    mod = synth.make_modular_frame(53, 37, channels=3, seed=rct_type)
+    out = host.ModularStream(ctx, mod["chans"], mod["sp"], rctType=rct_type, rctBegin=0).applyTransforms()
+    exp = orc.modular_apply(mod["chans"], mod["sp"], rct_type=rct_type, rct_begin=0)
+    assert len(out) == len(exp) == 3
+    for i, (a, b) in enumerate(zip(out, exp)):
+        assert_bits_equal(a, b, "rct %d channel %d" % (rct_type, i))
+
+
+@pytest.mark.parametrize("squeezed", [False, True])
+@pytest.mark.parametrize("rct_begin", [0, 1, 2])
+@pytest.mark.parametrize("rct_type", [7 * p + 6 for p in range(6)])
+def test_plan_rct_begin(ctx, orc, rct_type, rct_begin, squeezed):
+    """five channels, the RCT on three of them from rctBegin, with and without squeeze steps in front: the channels outside the
+    three stay in place"""
+    import pixel_ref64_cases
+    chans, sp = pixel_ref64_cases.rct_five_channels_squeezed() if squeezed else (pixel_ref64_cases.rct_five_channels(), [])
+    out = host.ModularStream(ctx, chans, sp, rctType=rct_type, rctBegin=rct_begin).applyTransforms()
+    exp = orc.modular_apply(chans, sp, rct_type=rct_type, rct_begin=rct_begin)
+    assert len(out) == len(exp) == 5
+    for i, (a, b) in enumerate(zip(out, exp)):
+        assert_bits_equal(a, b, "rct %d at %d channel %d" % (rct_type, rct_begin, i))
 
 
 def test_squeeze_round_trip_property_full_size(ctx, orc):

@@ -370,6 +370,68 @@ def test_pack_gpu(ctx, orc):
         host.packSamples(ctx, fl, 8, premultiplied=True)
 
 
+# ---- the second trip of the grid-stride loops ----------------------------------------------------------------------------
+# grid_for (k_post.hip:314-316) stops at 256 * 64 blocks of 256 threads: beyond that many elements every kernel it sizes takes a
+# second trip through its loop. One case per kernel, just past it.
+POST_GRID_CAP = 256 * 64 * 256
+BIG = (1025, 4100)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("xs,ys", [(1, 0), (0, 1)])
+def test_chroma_upsample_second_loop_trip(ctx, orc, xs, ys):
+    from jxlatte_amd import host
+    assert BIG[0] * BIG[1] > POST_GRID_CAP
+    a = rnd_plane(np.random.default_rng(40 + xs), *BIG, specials=False)
+    assert_bits_equal(host.invertSubsampling(ctx, a, xs, ys), orc.chroma_upsample(a, xs, ys), "beyond the grid %d %d" % (xs, ys))
+
+
+@pytest.mark.gpu
+def test_upsample_second_loop_trip(ctx, orc):
+    from jxlatte_amd import host
+    h, w, k = 1030, 2040, 2
+    assert h * w * k > POST_GRID_CAP  # k_upsample: one thread per input pixel and ky
+    rng = np.random.default_rng(42)
+    a = rnd_plane(rng, h, w, specials=False)
+    wts = orc.upsampling_weights(k, (rng.standard_normal(15) * 0.2).astype(np.float32))
+    assert_bits_equal(host.performUpsampling(ctx, a, k, wts), orc.upsample(a, k, wts), "beyond the grid")
+
+
+@pytest.mark.gpu
+def test_noise_second_loop_trip(ctx, orc):
+    """k_noise_conv (initializeNoise, one colour) and k_noise_add (synthesizeNoise)"""
+    from jxlatte_amd import host
+    h, w = BIG
+    assert h * w > POST_GRID_CAP
+    seed = (9 << 32) | 5
+    nz = orc.noise_init(h, w, seed, 256, 1)
+    assert_bits_equal(host.initializeNoise(ctx, h, w, seed, 256, 1), nz, "noise init beyond the grid")
+    rng = np.random.default_rng(43)
+    p = rng.standard_normal((3, h, w)).astype(np.float32)
+    p[1] += 1.0
+    n3 = np.stack([nz[0], nz[0][::-1], nz[0][:, ::-1]])
+    lut = (rng.random(8) * 1.6 - 0.3).astype(np.float32)
+    assert_bits_equal(host.synthesizeNoise(ctx, p, n3, lut, -0.3, 0.935), orc.noise_add(p, n3, lut, -0.3, 0.935), "noise add beyond the grid")
+
+
+@pytest.mark.gpu
+def test_blend_orient_pack_second_loop_trip(ctx, orc):
+    """k_blend (ADD, float, the whole plane as the rectangle), k_orient_flip (orientation 2, int), k_pack (one float plane, depth 8)"""
+    from jxlatte_amd import host
+    h, w = BIG
+    assert h * w > POST_GRID_CAP
+    rng = np.random.default_rng(44)
+    cv, fr, rf = (rng.standard_normal(BIG).astype(np.float32) for _ in range(3))
+    rect = (h, w, 0, 0, 0, 0, 0, 0)
+    st, exp = orc.blend(abi.BLEND_ADD, cv, fr, rf, rect)
+    assert st == 0
+    assert_bits_equal(host.blend(ctx, abi.BLEND_ADD, cv, fr, rf, rect), exp, "blend beyond the grid")
+    a = rng.integers(-2**31, 2**31, BIG, dtype=np.int64).astype(np.int32)
+    assert_bits_equal(host.transposeBuffer(ctx, a, 2), orc.orient(a, 2), "orientation 2 beyond the grid")
+    f = (fr * np.float32(0.5) + np.float32(0.5))
+    assert_bits_equal(host.packSamples(ctx, [f], 8), orc.pack([f], 8), "pack beyond the grid")
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("fmt,tf", [(abi.OUT_RGB8, abi.TRANSFER_SRGB), (abi.OUT_RGB16, abi.TRANSFER_PQ), (abi.OUT_RGB16, abi.TRANSFER_NONE)])
 @pytest.mark.parametrize("size", [(96, 64), (72, 40)])
