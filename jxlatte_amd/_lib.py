@@ -175,6 +175,12 @@ def load():
             raise
         fn.restype = res
         fn.argtypes = args
+    # JXL_PLANE_A_TILED=0: raster layout in the pooled IDCT-output planes (same-box A/B runs; README, run-time switches). Read here
+    # and handed to the library's hook: the library itself reads no environment variable for it.
+    tiled = os.environ.get("JXL_PLANE_A_TILED")
+    if tiled is not None and hasattr(lib, "jxl_debug_set_plane_a_tiled"):
+        lib.jxl_debug_set_plane_a_tiled.restype, lib.jxl_debug_set_plane_a_tiled.argtypes = C.c_int, [C.c_int]
+        lib.jxl_debug_set_plane_a_tiled(0 if tiled.strip() == "0" else 1)
     _lib = lib
     return lib
 

@@ -190,6 +190,7 @@ struct jxl_ctx {
     int result_elem = 4;
     bool result_interleaved = false;
     int last_launches = 0;
+    int last_plane_a_tiled = 0;  // the last run_frame wrote cell-tiled pooled planes (jxl_debug_last_plane_a_tiled)
     uint64_t tables_gen = 0;  // bumped whenever finalize_tables rebuilds the binned work (batch argument cache key)
     // jxl_vardct_run_batch state (kept by the first context of a batch)
     DevBuf batch_restore_args;
@@ -480,6 +481,9 @@ bool shared_planes_on() {
     static const bool v = !(getenv("JXL_SHARED_PLANES") && atoi(getenv("JXL_SHARED_PLANES")) == 0);
     return v;
 }
+// Cell-tiled pooled planes (plane_tiled.h): process-wide, read per run. The library reads no environment variable for
+// it: the Python package maps JXL_PLANE_A_TILED=0 onto jxl_debug_set_plane_a_tiled (jxlatte_amd/_lib.py), tests flip it in place.
+std::atomic<int> g_plane_a_tiled{1};
 void inter_account(int device, long long delta) {
     if (device >= 0 && device < 64) g_inter_bytes[device].fetch_add(delta, std::memory_order_relaxed);
 }
@@ -1324,6 +1328,11 @@ extern "C" int jxl_debug_wg3_item_table(const int32_t* types, const int32_t* n_b
 extern "C" int64_t jxl_debug_intermediate_bytes(int device) {
     return device >= 0 && device < 64 ? (int64_t)g_inter_bytes[device].load(std::memory_order_relaxed) : -1;
 }
+// Test / A-B hook: the layout run_frame gives the pooled IDCT-output planes from the next run on (0: raster, else cell-tiled where the
+// frame allows it); returns the previous setting. Not part of the C-ABI of include/jxlatte_amd.h.
+extern "C" int jxl_debug_set_plane_a_tiled(int on) { return g_plane_a_tiled.exchange(on ? 1 : 0, std::memory_order_relaxed); }
+// ... and whether the context's last frame run took that layout (tests/test_tiled_plane_a_gpu.py)
+extern "C" int jxl_debug_last_plane_a_tiled(const jxl_ctx* c) { return c ? c->last_plane_a_tiled : 0; }
 extern "C" int jxl_debug_clock_probe(int device, double us, double* mhz) {
     static hipStream_t s = nullptr;
     static unsigned long long* d = nullptr;
@@ -2409,6 +2418,14 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
                               restore_fused_covers(c->H, c->W, do_epf ? p.epf_iters : 0, c->hf_mul.p, c->sharp.p);
     const bool shared = may_share && !idct_done && !collect && (p.stages & JXL_STAGE_IDCT) && !c->sub && c->blocks_cover && fused_single &&
                         pool_of(c) != nullptr;
+    // Layout of a pooled set (plane_tiled.h): cell-tiled when the whole of it is written by the ONE 256-thread IDCT launch and read by a
+    // fused variant that has the tiled loader -- both private to this call, like the planes. A frame with a 512-thread side launch
+    // (64x32 / 32x64 blocks) or 128/256-edge blocks, whose kernels store raster, keeps raster in the pooled set; so do three EPF
+    // iterations in one launch (JXL_EPF3_SPLIT=0) and planes that are no whole cells or too large for 32-bit sample offsets.
+    bool tiled = shared && g_plane_a_tiled.load(std::memory_order_relaxed) != 0 && plane_tiled_ok(c->W, c->H) &&
+                 restore_fused_takes_tiled(do_epf ? p.epf_iters : 0) && c->large_count == 0 && c->special_launches.empty() &&
+                 c->wg3_item_count[0] > 0 && c->wg3_item_count[1] == 0;
+    for (const auto& tl : c->type_launches) tiled = tiled && tl.cls == 2;
     // Ordering on a pooled set: every launch of this call that writes it runs on the main stream or on a side stream that waits
     // for fork_ev, recorded on the main stream below -- behind the restoration launch of the frame before, its last reader
     std::unique_lock<std::mutex> run_lock;
@@ -2463,7 +2480,7 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
         for (const auto& tl : c->type_launches)
             if (tl.cls >= 2) {
                 const int k = tl.cls - 2;
-                wn[k] = build_wg3_args(f, blocks, tl.segs.data(), (int)tl.segs.size(), k, A, wa[k]);
+                wn[k] = build_wg3_args(f, blocks, tl.segs.data(), (int)tl.segs.size(), k, A, wa[k], tiled);
                 if (wn[k] < 0) return fail(c, JXL_ERR_STATE, "IDCT launch: too many segments");
                 // (r6: the list may hold holes -- wg3_item_table --: at least one record per item, and the list's length is what the walk is bounded by)
                 if (c->wg3_item_count[k] < wn[k]) return fail(c, JXL_ERR_STATE, "IDCT launch: item list out of date");
@@ -2582,7 +2599,7 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
                 g_restore_kernel_ev[0] = c->kev[c->ev_runs % jxl_ctx::kEvSlots][0];
                 g_restore_kernel_ev[1] = c->kev[c->ev_runs % jxl_ctx::kEvSlots][1];
             }
-            fused = launch_restore_fused(src, dst, c->H, c->W, c->hf_mul.as<int32_t>(), c->sharp.as<int32_t>(), rp, s);
+            fused = launch_restore_fused(src, dst, c->H, c->W, c->hf_mul.as<int32_t>(), c->sharp.as<int32_t>(), rp, s, tiled);
             g_restore_kernel_ev[0] = g_restore_kernel_ev[1] = nullptr;
             c->kev_valid = c->timing && fused;
         }
@@ -2643,6 +2660,7 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
         c->ev_runs++;
     }
     c->last_launches = launches;
+    c->last_plane_a_tiled = tiled ? 1 : 0;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(c, JXL_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
     return JXL_OK;

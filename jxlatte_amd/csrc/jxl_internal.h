@@ -8,6 +8,7 @@
 #include <stdint.h>
 #include "../../include/jxlatte_amd.h"
 #include "../../include/jxl_transform_types.h"
+#include "plane_tiled.h"
 
 namespace jxl {
 
@@ -123,6 +124,7 @@ struct Wg3Args {
     // total_items of them, in the order the workgroups take them (wg3_item_table: spatial, dealt to the XCDs, cost-balanced)
     const int* items;
     Wg3Seg seg[kMaxSeg];
+    int tiled; // the output planes are cell-tiled (plane_tiled.h): the 256-thread class only, pooled planes only (run_frame)
 };
 
 // the item list of one class's segments in spatial order, dealt to the XCDs in runs (host side)
@@ -132,7 +134,7 @@ int wg3_grid_cap(bool big);  // workgroups of a single-frame launch (JXL_WG3_GRI
 bool wg3_handles(int type);  // every type but the 128/256-edge ones (frames without chroma subsampling)
 bool wg3_big(int type);  // 64x32 / 32x64: the 512-thread launch (register / LDS class)
 int build_wg3_args(const DevFrame& f, const DevBlock* blocks, const IdctSegment* segs, int n_seg, int which, float* const out[3],
-                   Wg3Args& a);
+                   Wg3Args& a, bool tiled = false);
 void launch_idct_wg3(const Wg3Args& a, bool big, int grid_cap, hipStream_t s);
 size_t wg3_lds_bytes(const Wg3Args& a);
 void launch_idct_wg3_batch(const Wg3Args* dev_args, int n_frames, bool big, int grid_x, size_t lds, hipStream_t s);
@@ -280,6 +282,7 @@ struct FusedArgs {
     const int32_t* hf_mul;
     const int32_t* sharpness;
     int W, H, bw;
+    int tiled;  // in[] are cell-tiled planes (plane_tiled.h): run_frame's pooled planes only; epf_iters <= 2
     RestoreParams p;
 };
 // what the fused restoration kernel takes: planes of at least one cell (its mirror fix-up assumes at most one reflection within the
@@ -300,7 +303,10 @@ void launch_restore_fused_q(int sink_kind, const FusedArgs* single, const FusedA
 void launch_restore_fused_batch(const FusedArgs* host_args, const FusedArgs* dev_args, int n, hipStream_t s);
 // returns false if the configuration is not covered by the fused kernel (caller falls back to stage kernels)
 bool launch_restore_fused(const float* const in[3], void* const out[3], int h, int w, const int32_t* hf_mul,
-                          const int32_t* sharpness, const RestoreParams& p, hipStream_t s);
+                          const int32_t* sharpness, const RestoreParams& p, hipStream_t s, bool tiled_in = false);
+// the input layouts the fused kernel is instantiated for: cell-tiled planes feed the 4x1-patch variants without the 13-tap iteration
+// (false under JXL_RESTORE_PH=2, whose 4x2-patch kernels read raster). run_frame asks before it picks the layout of a pooled set.
+bool restore_fused_takes_tiled(int epf_iters);
 
 // one inverse squeeze step over up to 8 channels in a single launch
 struct SqueezeDesc {

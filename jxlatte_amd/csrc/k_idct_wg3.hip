@@ -718,12 +718,31 @@ struct Body {
             if (rb < it.nb) {
                 float* o3[3] = {a.o0, a.o1, a.o2};
                 const int cy = (int)((uint32_t)rowx & 0xffffu), cx = (int)((uint32_t)rowx >> 16);  // (prefetched with the item: Raw::rowx)
-                const int64_t off = (int64_t)(cy * 8 + ry) * f.width + cx * 8;
+                // cell-tiled planes (Wg3Args::tiled, plane_tiled.h; 256-thread class only): the lane's row is row ry & 7 of the cells
+                // (cy + ry / 8, cx ..), a run's x picks the cell -- runs of 4 (8) from a multiple of 4 (8) never leave a cell row. The 8
+                // lanes of an 8x8 block then fill ONE 256-byte cell instead of eight 16-byte pieces of eight lines.
+                const bool tl = !C::BIG && a.tiled;
+                if constexpr (!C::BIG) {
+                    // the plane bases are in scalar registers BEFORE the first store: re-read from the argument block between two stores,
+                    // the scalar load and its wait are all that separates a 16-byte store from the address arithmetic that reuses its data
+                    // registers (tools/scan_store_hazard.py asks for two issue cycles there)
+#pragma unroll
+                    for (int ch = 0; ch < 3; ch++) asm volatile("" : "+s"(o3[ch]));
+                }
+                const int64_t off = tl ? (int64_t)plane_tiled_off(f.width >> 3, cy * 8 + ry, cx * 8) : (int64_t)(cy * 8 + ry) * f.width + cx * 8;
+                [[maybe_unused]] const int xlo = kc_row * (KC / 2), xhi = W - (kc_row + 1) * (KC / 2);  // (wave-uniform)
+                [[maybe_unused]] const int olo_x = tl ? (((xlo >> 3) << 6) | (xlo & 7)) : xlo, ohi_x = tl ? (((xhi >> 3) << 6) | (xhi & 7)) : xhi;
 #pragma unroll
                 for (int ch = 0; ch < 3; ch++) {
                     // two runs of KC/2 consecutive outputs: the low one ascending, the mirrored one ending at W-1-kc*KC/2
-                    float* olo = o3[ch] + off + kc_row * (KC / 2);
-                    float* ohi = o3[ch] + off + W - (kc_row + 1) * (KC / 2);
+                    float *olo, *ohi;
+                    if constexpr (C::BIG) {  // (spelt as it always was: the 512-thread class's register allocation is touchy)
+                        olo = o3[ch] + off + kc_row * (KC / 2);
+                        ohi = o3[ch] + off + W - (kc_row + 1) * (KC / 2);
+                    } else {
+                        olo = o3[ch] + off + olo_x;
+                        ohi = o3[ch] + off + ohi_x;
+                    }
 #pragma unroll
                     for (int kk = 0; kk < KC / 2; kk += 4) {
                         *reinterpret_cast<float4*>(olo + kk) = make_float4(acc.get(ch, kk), acc.get(ch, kk + 1), acc.get(ch, kk + 2), acc.get(ch, kk + 3));
@@ -792,7 +811,8 @@ __device__ __forceinline__ void special_store(const Wg3Args& a, const Item& it, 
         const DevFrame& f = a.f;
         float* o3[3] = {a.o0, a.o1, a.o2};
         const int cy = (int)((uint32_t)rowx & 0xffffu), cx = (int)((uint32_t)rowx >> 16);
-        const int64_t off = (int64_t)(cy * 8 + ry) * f.width + cx * 8;
+        // (cell-tiled planes: the block IS cell (cy, cx) and this lane's row its row ry -- see Body::passes)
+        const int64_t off = a.tiled ? (int64_t)plane_tiled_off(f.width >> 3, cy * 8 + ry, cx * 8) : (int64_t)(cy * 8 + ry) * f.width + cx * 8;
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
             const float* sp = img + (ch * C::NB + rb) * C::IMG + ry * 8;
@@ -831,15 +851,19 @@ struct Item64 {
     }
     // row pass of the channel in the image -> plane `out`
     template <typename PreStore>
-    static __device__ __forceinline__ void row_pass(const DevFrame& f, int tid, const float* __restrict__ img, float* __restrict__ out, int cy, int cx,
-                                                    PreStore pre_store) {
+    static __device__ __forceinline__ void row_pass(const DevFrame& f, int tiled, int tid, const float* __restrict__ img, float* __restrict__ out, int cy,
+                                                    int cx, PreStore pre_store) {
         const cfloatp lut = (cfloatp)(f.lut + lut_off(6));
         const int row = tid & 63, kc = __builtin_amdgcn_readfirstlane(tid >> 6);
         Acc1<KC> acc;
         idct1d1<KC, 64>(acc, lut + kc * (KC / 2), img + row * LD, 1);
         pre_store();
-        float* olo = out + (int64_t)(cy * 8 + row) * f.width + cx * 8 + kc * (KC / 2);
-        float* ohi = out + (int64_t)(cy * 8 + row) * f.width + cx * 8 + 64 - (kc + 1) * (KC / 2);
+        // (cell-tiled planes: both runs are whole cell rows, KC / 2 == 8 -- see Body::passes)
+        static_assert(KC / 2 == 8, "a run is one cell row");
+        const int xlo = kc * (KC / 2), xhi = 64 - (kc + 1) * (KC / 2);
+        const int64_t off = tiled ? (int64_t)plane_tiled_off(f.width >> 3, cy * 8 + row, cx * 8) : (int64_t)(cy * 8 + row) * f.width + cx * 8;
+        float* olo = out + off + (tiled ? (xlo >> 3) << 6 : xlo);
+        float* ohi = out + off + (tiled ? (xhi >> 3) << 6 : xhi);
 #pragma unroll
         for (int kk = 0; kk < KC / 2; kk += 4) {
             *reinterpret_cast<float4*>(olo + kk) = make_float4(acc.get(kk), acc.get(kk + 1), acc.get(kk + 2), acc.get(kk + 3));
@@ -938,7 +962,7 @@ struct Item64 {
             lds_barrier();
             column_pass(f, tid, img);
             if (ci == 2) return;
-            row_pass(f, tid, img, c == 1 ? a.o1 : a.o0, cy, cx, []() {});
+            row_pass(f, a.tiled, tid, img, c == 1 ? a.o1 : a.o0, cy, cx, []() {});
             lds_barrier();  // every lane has read the image before the next channel's samples overwrite it
         }
     }
@@ -946,7 +970,7 @@ struct Item64 {
     static __device__ __forceinline__ void back(const Wg3Args& a, const Item& it, int tid, const float* __restrict__ img, PreStore pre_store) {
         const auto* brec = (const __attribute__((address_space(4))) int*)a.blocks + 4 * it.first;
         const int cy = (int)((uint32_t)brec[0] & 0xffffu), cx = (int)((uint32_t)brec[0] >> 16);
-        row_pass(a.f, tid, img, a.o2, cy, cx, pre_store);
+        row_pass(a.f, a.tiled, tid, img, a.o2, cy, cx, pre_store);
     }
 };
 
@@ -1182,7 +1206,7 @@ static int wg3_img_floats(int type) {
 // Fills the argument block for the frame's types of one register class (which = 0: up to 32 points, 1: 64x32 / 32x64), in the
 // given launch order. Returns the number of items (0: nothing to launch; -1: more segments than the argument block holds).
 int build_wg3_args(const DevFrame& f, const DevBlock* blocks, const IdctSegment* segs, int n_seg, int which, float* const out[3],
-                   Wg3Args& a) {
+                   Wg3Args& a, bool tiled) {
     a.f = f;
     a.blocks = blocks;
     a.o0 = out[0]; a.o1 = out[1]; a.o2 = out[2];
@@ -1191,6 +1215,7 @@ int build_wg3_args(const DevFrame& f, const DevBlock* blocks, const IdctSegment*
     a.img_floats = 0;
     a.items = nullptr;
     a.llf_in_item = 1;  // (always: the items do finalizeLLF themselves)
+    a.tiled = tiled ? 1 : 0;  // (read by the 256-thread class only; run_frame asks for it only where that class writes the whole frame)
     static_assert(Wg3Args::kMaxSeg >= 21, "one segment per type wg3_handles() accepts");
     for (int i = 0; i < n_seg; i++) {
         if (segs[i].n_blocks <= 0 || !wg3_handles(segs[i].type) || wg3_big(segs[i].type) != (which == 1)) continue;

@@ -20,6 +20,7 @@ bool fill_restore_fused_args(const float* const in[3], void* const out[3], int h
     a.W = w;
     a.H = h;
     a.bw = (w + 7) >> 3;
+    a.tiled = 0;
     a.p = p;
     return true;
 }
@@ -38,18 +39,26 @@ void launch_restore_fused_batch(const FusedArgs* host_args, const FusedArgs* dev
     else launch_restore_fused_q(sk, nullptr, host_args, dev_args, n, s);
 }
 
+// JXL_RESTORE_PH=2: 4x2 patches on 256 threads (float planes, raster input only)
+static bool restore_ph2() {
+    static const bool v = getenv("JXL_RESTORE_PH") && atoi(getenv("JXL_RESTORE_PH")) == 2;
+    return v;
+}
+bool restore_fused_takes_tiled(int epf_iters) { return epf_iters >= 0 && epf_iters <= 2 && !restore_ph2(); }
+
 bool launch_restore_fused(const float* const in[3], void* const out[3], int h, int w, const int32_t* hf_mul,
-                          const int32_t* sharpness, const RestoreParams& p, hipStream_t s) {
+                          const int32_t* sharpness, const RestoreParams& p, hipStream_t s, bool tiled_in) {
     FusedArgs a;
     if (!fill_restore_fused_args(in, out, h, w, hf_mul, sharpness, p, a)) return false;
+    if (tiled_in && !(restore_fused_takes_tiled(p.epf_iters) && plane_tiled_ok(w, h))) return false;  // (run_frame asks the same before it picks the layout)
+    a.tiled = tiled_in ? 1 : 0;
     const int sk = sink_kind_of(p);
     if (sk == SK_PLAIN) {
         // 4x1 patches on 512 threads everywhere: twice the waves per CU of 4x2 patches for the same LDS footprint. The
         // 3-iteration variant used to run 4x2 patches (fewer tap loads for its 13-tap first iteration) but spilled 169 VGPRs
         // there: 841 us per 4K frame against 259 us with 4x1 patches and a 128-register budget (JXL_RESTORE_PH=2 selects 4x2,
         // float planes only)
-        static const int ph_env = getenv("JXL_RESTORE_PH") ? atoi(getenv("JXL_RESTORE_PH")) : 0;
-        if (ph_env == 2 && p.epf_iters <= 3) {  // (4 = the 13-tap iteration alone: 4x1 patches only)
+        if (restore_ph2() && p.epf_iters <= 3) {  // (4 = the 13-tap iteration alone: 4x1 patches only; tiled input never gets here)
             const int it = p.epf_iters;
             if (p.gab) {
                 if (it == 0) launch_tph<true, 0, SK_PLAIN, 2>(a, s);

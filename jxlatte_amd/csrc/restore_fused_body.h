@@ -478,7 +478,9 @@ __device__ __forceinline__ void restore_epf_stages(const FusedArgs& a, float* cu
 
 // SK = SK_PLAIN: float planes out, no transfer function (keeps the transfer code out of the hot variant); the other sink kinds
 // fix transfer function and output format at compile time, SK_GENERIC picks them per sample at run time
-template <bool GAB, int ITERS, int SK, int PH>
+// LAY = the layout of the input planes: 0 raster, 1 cell-tiled (plane_tiled.h: run_frame's pooled planes, written by the IDCT launch of
+// the same call). Only the tile load differs: both loaders leave the same LDS image.
+template <bool GAB, int ITERS, int SK, int PH, int LAY = 0>
 __device__ __forceinline__ void restore_fused_body(const FusedArgs& a) {
     using G = Geo<GAB, ITERS>;
     constexpr int NTHR = 512 / PH;
@@ -520,7 +522,38 @@ __device__ __forceinline__ void restore_fused_body(const FusedArgs& a) {
     }
     // load the input tile: clamped coordinates feed Gab, mirrored ones feed EPF directly. Flat row-major
     // walk with incrementally updated (y, x) and 32-bit plane offsets (scalar base + 32-bit lane offset).
-    if (!tc.edge) {
+    if (LAY == 1 && !tc.edge) {
+        // interior tile of cell-tiled planes: the tile is gathered from the NCY x NCX cells it can overlap (6 x 10 for the 70 x 38 tile),
+        // 16 consecutive lanes = the 16 aligned 16-byte pieces of one cell = two whole 128-byte lines. A piece outside the tile is not
+        // loaded (for an interior tile everything inside it lies inside the frame); one that straddles the tile's left or right edge
+        // keeps the samples inside.
+        constexpr int NCX = (G::IW + 6) / 8 + 1, NCY = (G::IH + 6) / 8 + 1, TOTAL = NCX * NCY * 16;
+        const int cells_w = W >> 3;
+        const int ccy0 = tc.iy0 >> 3, ccx0 = tc.ix0 >> 3;
+        const uint32_t base = (uint32_t)(ccy0 * cells_w + ccx0) << 6;
+#pragma unroll
+        for (int k = 0; k < (TOTAL + NTHR - 1) / NTHR; k++) {
+            const int idx = (int)threadIdx.x + k * NTHR;
+            const int cell = idx >> 4, pc = idx & 15;
+            const int cyi = cell / NCX, cxi = cell - cyi * NCX;
+            const int y = ((ccy0 + cyi) << 3) + (pc >> 1) - tc.iy0, x = ((ccx0 + cxi) << 3) + ((pc & 1) << 2) - tc.ix0;  // tile coordinates
+            if ((TOTAL % NTHR == 0 || idx < TOTAL) && (unsigned)y < (unsigned)G::IH && x > -4 && x < G::IW) {
+                const uint32_t g = base + ((uint32_t)(cyi * cells_w + cxi) << 6) + (uint32_t)(pc << 2);
+                const float4 v0 = *reinterpret_cast<const float4*>(a.in[0] + g);
+                const float4 v1 = *reinterpret_cast<const float4*>(a.in[1] + g);
+                const float4 v2 = *reinterpret_cast<const float4*>(a.in[2] + g);
+                float* d = A + y * G::SW + x;
+                const float e0[4] = {v0.x, v0.y, v0.z, v0.w}, e1[4] = {v1.x, v1.y, v1.z, v1.w}, e2[4] = {v2.x, v2.y, v2.z, v2.w};
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if ((unsigned)(x + i) < (unsigned)G::IW) {
+                        d[i] = e0[i];
+                        d[G::PLANE + i] = e1[i];
+                        d[2 * G::PLANE + i] = e2[i];
+                    }
+            }
+        }
+    } else if (!tc.edge) {
         // interior tile: no coordinate fix-ups; two samples per lane and load (the tile origin is only 4-byte aligned)
         static_assert(G::IW % 2 == 0, "pairs");
         constexpr int PAIRS = G::IW / 2, TOTAL = PAIRS * G::IH;
@@ -558,7 +591,7 @@ __device__ __forceinline__ void restore_fused_body(const FusedArgs& a) {
                 gy = mirror_c(gy, H);
                 gx = mirror_c(gx, W);
             }
-            const uint32_t g = (uint32_t)(gy * W + gx);
+            const uint32_t g = LAY == 1 ? plane_tiled_off(W >> 3, gy, gx) : (uint32_t)(gy * W + gx);
             const float v0 = in0[g], v1 = in1[g], v2 = in2[g];
             float* d = A + y * G::SW + x;
             d[0] = v0;
@@ -675,9 +708,9 @@ __device__ __forceinline__ void restore_epf_stages(const FusedArgs& a, float* cu
 #define JXL_RESTORE_BOUNDS(ITERS, PH) __launch_bounds__(512 / PH, ITERS >= 3 ? (PH == 1 ? 4 : JXL_EPF3_PH2_WAVES) : PH == 1 ? 8 : 4)
 // occupancy floor: 8 waves per SIMD (64 VGPRs); the 3-iteration variant holds 48 tap distances per patch and spilled 130
 // VGPRs at that bound, so it is allowed 128 registers (4 waves per SIMD; its 43 KB tile allows 3 workgroups per CU anyway)
-template <bool GAB, int ITERS, int SK, int PH>
+template <bool GAB, int ITERS, int SK, int PH, int LAY = 0>
 __global__ JXL_RESTORE_BOUNDS(ITERS, PH) void k_restore_fused(const FusedArgs a) {
-    restore_fused_body<GAB, ITERS, SK, PH>(a);
+    restore_fused_body<GAB, ITERS, SK, PH, LAY>(a);
 }
 
 // a batch of frames in one launch (jxl_vardct_run_batch): blockIdx.y = frame, argument blocks in device memory read
@@ -688,7 +721,7 @@ __global__ JXL_RESTORE_BOUNDS(ITERS, 1) void k_restore_fused_batch(const FusedAr
     restore_fused_body<GAB, ITERS, SK, 1>(*(const FusedArgs*)((cargs)args + blockIdx.y));
 }
 
-template <bool GAB, int ITERS, int SK, int PH>
+template <bool GAB, int ITERS, int SK, int PH, int LAY = 0>
 void launch_tph(const FusedArgs& a, hipStream_t s) {
     using G = Geo<GAB, ITERS>;
     // experiment knob: extra dynamic LDS per workgroup caps the workgroups per CU (160 KiB / size), leaving wave slots to
@@ -696,7 +729,7 @@ void launch_tph(const FusedArgs& a, hipStream_t s) {
     static const size_t pad = getenv("JXL_RESTORE_LDS_PAD") ? (size_t)atoi(getenv("JXL_RESTORE_LDS_PAD")) : 0;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_restore_fused<GAB, ITERS, SK, PH>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_restore_fused<GAB, ITERS, SK, PH, LAY>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(G::LDS_BYTES + pad));
         attr_set = true;
     }
@@ -706,10 +739,10 @@ void launch_tph(const FusedArgs& a, hipStream_t s) {
     // stage timing (jxl_vardct_enable_stage_timing): the KERNEL's own start and stop -- what rocprofv3 reports for it -- besides the
     // stage's events on the stream, which also hold the boundary to the launch in front (r6)
     if (g_restore_kernel_ev[0] && g_restore_kernel_ev[1])
-        hipExtLaunchKernelGGL((k_restore_fused<GAB, ITERS, SK, PH>), grid, dim3(512 / PH), (uint32_t)(G::LDS_BYTES + pad), s, g_restore_kernel_ev[0],
+        hipExtLaunchKernelGGL((k_restore_fused<GAB, ITERS, SK, PH, LAY>), grid, dim3(512 / PH), (uint32_t)(G::LDS_BYTES + pad), s, g_restore_kernel_ev[0],
                               g_restore_kernel_ev[1], 0u, a);
     else
-        hipLaunchKernelGGL((k_restore_fused<GAB, ITERS, SK, PH>), grid, dim3(512 / PH), G::LDS_BYTES + pad, s, a);
+        hipLaunchKernelGGL((k_restore_fused<GAB, ITERS, SK, PH, LAY>), grid, dim3(512 / PH), G::LDS_BYTES + pad, s, a);
 }
 
 template <bool GAB, int ITERS, int SK>
@@ -732,6 +765,18 @@ void launch_batch_t(const FusedArgs* host_args, const FusedArgs* dev_args, int n
 template <int SK>
 void launch_fused_sk(const FusedArgs& a, hipStream_t s) {
     const int it = a.p.epf_iters;
+    if (a.tiled) {  // cell-tiled input planes (run_frame's pooled planes): the variants restore_fused_takes_tiled() names, 4x1 patches
+        if (a.p.gab) {
+            if (it == 0) launch_tph<true, 0, SK, 1, 1>(a, s);
+            else if (it == 1) launch_tph<true, 1, SK, 1, 1>(a, s);
+            else launch_tph<true, 2, SK, 1, 1>(a, s);
+        } else {
+            if (it == 0) launch_tph<false, 0, SK, 1, 1>(a, s);
+            else if (it == 1) launch_tph<false, 1, SK, 1, 1>(a, s);
+            else launch_tph<false, 2, SK, 1, 1>(a, s);
+        }
+        return;
+    }
     if (a.p.gab) {
         if (it == 0) launch_tph<true, 0, SK, 1>(a, s);
         else if (it == 1) launch_tph<true, 1, SK, 1>(a, s);
