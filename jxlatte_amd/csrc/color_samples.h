@@ -3,25 +3,10 @@
 // JXLImage.transform evaluates the very same float operations. Include from a file compiled with -ffp-contract=off.
 #ifndef JXL_COLOR_SAMPLES_H
 #define JXL_COLOR_SAMPLES_H
-#include "jxl_fastpow.h"
-#include "jxl_internal.h"
+#include "sample_ops.h"
 
 namespace jxl {
 namespace {
-
-// Java (int)float: NaN -> 0, saturating
-__device__ __forceinline__ int32_t f2i(float v) {
-    if (v != v) return 0;
-    if (v >= 2147483648.0f) return INT32_MAX;
-    if (v <= -2147483648.0f) return INT32_MIN;
-    return (int32_t)v;
-}
-
-// ImageBuffer.castToInt0 (ImageBuffer.java:129-145)
-__device__ __forceinline__ int32_t to_int(float v, int max_value) {
-    const int32_t q = f2i(v * (float)max_value + 0.5f);
-    return q < 0 ? 0 : q > max_value ? max_value : q;
-}
 
 // Math.pow(x, p) for any finite p > 0 (GammaTransferFunction: p = 1e7 / g or 1e-7 * g can be an integer, e.g. g = 5000000).
 // kind: 0 p is not an integer, 1 an even integer, 2 an odd integer (host: pow_kind).
@@ -57,11 +42,11 @@ __device__ __forceinline__ float to_linear(float f, int tf, double p, int kind) 
     return f;
 }
 
-// TransferFunction.fromLinearF as a float. LINEAR / SRGB / PQ: the functions jxl_stage_transfer evaluates (k_restore.hip,
-// apply_transfer: PQ through the segment table when the context has one).
-__device__ __forceinline__ float from_linear(float v, int tf, double p, int kind, const float4* pq_tab) {
-    if (tf == JXL_TF_SRGB) return fp_tf_srgb(v);
-    if (tf == JXL_TF_PQ) return pq_tab ? fp_tf_pq_tab(v, pq_tab) : fp_tf_pq(v);
+// TransferFunction.fromLinearF as a float. LINEAR / SRGB / PQ: the functions jxl_stage_transfer evaluates (sample_ops.h,
+// from_linear_f: PQ through the segment table when the context has one).
+__device__ __forceinline__ float from_linear(float v, int tf, double p, int kind, const float* pq_tab) {
+    if (tf == JXL_TF_SRGB) return from_linear_f(v, JXL_TRANSFER_SRGB, pq_tab);  // JXL_TF_* and JXL_TRANSFER_* number the curves differently
+    if (tf == JXL_TF_PQ) return from_linear_f(v, JXL_TRANSFER_PQ, pq_tab);
     if (tf == JXL_TF_BT709) {  // :65-70
         const double d = (double)v;
         if (d < 0.018053968510807807336) return (float)(4.5 * d);

@@ -1137,112 +1137,77 @@ void build_pq_table(float* out) {
 }  // namespace jxl
 
 namespace jxl {
-// The reference's composite for an 8-bit sRGB sample: TF_SRGB.fromLinearF (TransferFunction.java:39-44) then
-// ImageBuffer.castToIntWithMax(255) (ImageBuffer.java:129-147), in the reference's own operations (this file is built with
-// -ffp-contract=off; the double pow is the host libm's, as in the oracle)
-static int srgb8_ref(float f) {
-    const volatile float t = f < 0.00313066844250063f ? f * 12.92f : 1.055f * (float)std::pow((double)f, 0.4166666666666667) + -0.055f;
-    const volatile float v = t * 255.0f + 0.5f;
+// The reference's composite that the threshold tables describe: fromLinearF of `curve` -- TF_SRGB's own float form
+// (TransferFunction.java:39-44) or TF_PQ.fromLinear cast to float (:83-87) -- then ImageBuffer.castToIntWithMax(max)
+// (ImageBuffer.java:129-147), in the reference's own operations (this file is built with -ffp-contract=off; the double pow is the
+// host libm's, as in the oracle)
+static int quant_ref(int curve, int max, float f) {
+    volatile float t;
+    if (curve == JXL_TRANSFER_PQ) {
+        const double d = std::pow((double)f, 0.159423828125);
+        t = (float)std::pow((0.8359375 + 18.8515625 * d) / (1.0 + 18.6875 * d), 78.84375);
+    } else {
+        t = f < 0.00313066844250063f ? f * 12.92f : 1.055f * (float)std::pow((double)f, 0.4166666666666667) + -0.055f;
+    }
+    const volatile float v = t * (float)max + 0.5f;
     if (v != v) return 0;
-    if (v >= 255.0f) return 255;
+    if (v >= (float)max) return max;
     if (v <= 0.0f) return 0;
     return (int)v;
+}
+// the smallest float, as its bit pattern, whose level is >= k: bisection between the positive floats lo and hi, where
+// level(lo) < k <= level(hi) (the level does not decrease with the input)
+static uint32_t first_at_level(int curve, int max, int k, uint32_t lo, uint32_t hi) {
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        float f;
+        memcpy(&f, &mid, 4);
+        if (quant_ref(curve, max, f) >= k) hi = mid; else lo = mid;
+    }
+    return hi;
+}
+// thr[k], k = 1..max: the smallest float of [+0, 1.0f] whose level is >= k (level(+0) = 0, level(1.0f) = max); thr[0] = -inf,
+// thr[max + 1] = +inf. threads: the 16-bit tables take ~4 M pow calls -- on up to 8 threads, once per process, on first use.
+static void build_thresholds(int curve, int max, float* thr, bool threads) {
+    const float inf = std::numeric_limits<float>::infinity();
+    thr[0] = -inf;
+    thr[max + 1] = inf;
+    auto work = [&](int t, int nt) {
+        for (int k = 1 + t; k <= max; k += nt) {
+            const uint32_t b = first_at_level(curve, max, k, 0u, 0x3F800000u);
+            memcpy(&thr[k], &b, 4);
+        }
+    };
+    const int nt = threads ? std::max(1, std::min(8, (int)std::thread::hardware_concurrency())) : 1;
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; t++) th.emplace_back(work, t, nt);
+    work(0, nt);
+    for (auto& x : th) x.join();
 }
 // fp_srgb8's table (jxl_fastpow.h): per segment {base level, up to three thresholds (+inf: none)}
 bool build_srgb8_table(float* out) {
     const float inf = std::numeric_limits<float>::infinity();
     for (int i = 0; i < (127 - 118) * 128; i++) {
         const uint32_t b0 = ((uint32_t)i + (118u << 7)) << 16, b1 = b0 + 0x10000u;  // the segment's floats: bits in [b0, b1)
-        auto at = [](uint32_t b) { float f; memcpy(&f, &b, 4); return srgb8_ref(f); };
+        auto at = [](uint32_t b) { float f; memcpy(&f, &b, 4); return quant_ref(JXL_TRANSFER_SRGB, 255, f); };
         const int base = at(b0), last = at(b1 - 1);
         if (last < base || last - base > 3) return false;
         out[4 * i] = (float)base;
         for (int k = 1; k <= 3; k++) {
             float thr = inf;
-            if (base + k <= last) {  // smallest bit pattern in the segment whose level is >= base + k (levels do not decrease)
-                uint32_t lo = b0, hi = b1 - 1;  // at(lo) < base + k <= at(hi)
-                while (hi - lo > 1) {
-                    const uint32_t mid = lo + (hi - lo) / 2;
-                    if (at(mid) >= base + k) hi = mid; else lo = mid;
-                }
-                memcpy(&thr, &hi, 4);
+            if (base + k <= last) {  // at(b0) < base + k <= at(b1 - 1)
+                const uint32_t b = first_at_level(JXL_TRANSFER_SRGB, 255, base + k, b0, b1 - 1);
+                memcpy(&thr, &b, 4);
             }
             out[4 * i + k] = thr;
         }
     }
     return true;
 }
-}  // namespace jxl
+void build_pq16_thresholds(float* out) { build_thresholds(JXL_TRANSFER_PQ, 65535, out, true); }
+// PQ -> 8 bit: appended to the 16-bit thresholds' buffer (at kPq8ThrOffset)
+void build_pq8_thresholds(float* out /* [257] */) { build_thresholds(JXL_TRANSFER_PQ, 255, out, false); }
 
-namespace jxl {
-// TF_PQ.fromLinear (TransferFunction.java:83-87) then ImageBuffer.castToIntWithMax(65535), in the reference's own operations
-static int pq16_ref(float f) {
-    const double d = std::pow((double)f, 0.159423828125);
-    const volatile float t = (float)std::pow((0.8359375 + 18.8515625 * d) / (1.0 + 18.6875 * d), 78.84375);
-    const volatile float v = t * 65535.0f + 0.5f;
-    if (v != v) return 0;
-    if (v >= 65535.0f) return 65535;
-    if (v <= 0.0f) return 0;
-    return (int)v;
-}
-// thr[k], k = 1..65535: the smallest float whose level is >= k (bisection over the bit patterns of [+0, 1.0f]; the level does
-// not decrease with the input); thr[0] = -inf, thr[65536] = +inf. ~4 M pow calls: on 8 threads, once per process, on first use.
-void build_pq16_thresholds(float* out) {
-    const float inf = std::numeric_limits<float>::infinity();
-    out[0] = -inf;
-    out[65536] = inf;
-    const uint32_t one = 0x3F800000u;
-    auto at = [](uint32_t b) { float f; memcpy(&f, &b, 4); return pq16_ref(f); };
-    auto work = [&](int t, int nt) {
-        for (int k = 1 + t; k <= 65535; k += nt) {
-            uint32_t lo = 0u, hi = one;  // at(lo) = 0 < k <= 65535 = at(hi)
-            while (hi - lo > 1) {
-                const uint32_t mid = lo + (hi - lo) / 2;
-                if (at(mid) >= k) hi = mid; else lo = mid;
-            }
-            memcpy(&out[k], &hi, 4);
-        }
-    };
-    const int nt = std::max(1, std::min(8, (int)std::thread::hardware_concurrency()));
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; t++) th.emplace_back(work, t, nt);
-    work(0, nt);
-    for (auto& x : th) x.join();
-}
-// PQ -> 8 bit: thr[1..255] appended to the 16-bit thresholds' buffer (offset 65537: thr8[0] = -inf, thr8[256] = +inf)
-static int pq8_ref(float f) {
-    const double d = std::pow((double)f, 0.159423828125);
-    const volatile float t = (float)std::pow((0.8359375 + 18.8515625 * d) / (1.0 + 18.6875 * d), 78.84375);
-    const volatile float v = t * 255.0f + 0.5f;
-    if (v != v) return 0;
-    if (v >= 255.0f) return 255;
-    if (v <= 0.0f) return 0;
-    return (int)v;
-}
-void build_pq8_thresholds(float* out /* [257] */) {
-    const float inf = std::numeric_limits<float>::infinity();
-    out[0] = -inf;
-    out[256] = inf;
-    auto at = [](uint32_t b) { float f; memcpy(&f, &b, 4); return pq8_ref(f); };
-    for (int k = 1; k <= 255; k++) {
-        uint32_t lo = 0u, hi = 0x3F800000u;
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (at(mid) >= k) hi = mid; else lo = mid;
-        }
-        memcpy(&out[k], &hi, 4);
-    }
-}
-
-// TF_SRGB.fromLinearF then ImageBuffer.castToIntWithMax(65535), in the reference's own operations
-static int srgb16_ref(float f) {
-    const volatile float t = f < 0.00313066844250063f ? f * 12.92f : 1.055f * (float)std::pow((double)f, 0.4166666666666667) + -0.055f;
-    const volatile float v = t * 65535.0f + 0.5f;
-    if (v != v) return 0;
-    if (v >= 65535.0f) return 65535;
-    if (v <= 0.0f) return 0;
-    return (int)v;
-}
 // fp_srgb16's tables: quadratic segments of c1 x^(1/2.4) - c0 over [2^-9, 1) (as build_pq_table), then the 65 537 thresholds
 void build_srgb16_table(float* out) {
     const long double cn = 0.86602540378443864676L, c1 = (long double)1.055f, c0 = (long double)0.055f;
@@ -1260,26 +1225,7 @@ void build_srgb16_table(float* out) {
         out[4 * i + 2] = (float)((yp - ym) / (2.0L * tn));
         out[4 * i + 3] = (float)((yp + ym - 2.0L * y0) / (2.0L * tn * tn));
     }
-    float* thr = out + kSrgb8TableFloats;
-    const float inf = std::numeric_limits<float>::infinity();
-    thr[0] = -inf;
-    thr[65536] = inf;
-    auto at = [](uint32_t b) { float f; memcpy(&f, &b, 4); return srgb16_ref(f); };
-    auto work = [&](int t, int nt) {
-        for (int k = 1 + t; k <= 65535; k += nt) {
-            uint32_t lo = 0u, hi = 0x3F800000u;  // at(+0) = 0 < k <= 65535 = at(1.0f)
-            while (hi - lo > 1) {
-                const uint32_t mid = lo + (hi - lo) / 2;
-                if (at(mid) >= k) hi = mid; else lo = mid;
-            }
-            memcpy(&thr[k], &hi, 4);
-        }
-    };
-    const int nt = std::max(1, std::min(8, (int)std::thread::hardware_concurrency()));
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; t++) th.emplace_back(work, t, nt);
-    work(0, nt);
-    for (auto& x : th) x.join();
+    build_thresholds(JXL_TRANSFER_SRGB, 65535, out + kSrgb16ThrOffset, true);
 }
 }  // namespace jxl
 
@@ -1350,7 +1296,7 @@ extern "C" void jxl_debug_pq16_thresholds(float* out) { jxl::build_pq16_threshol
 extern "C" void jxl_debug_srgb16_table(float* out) { jxl::build_srgb16_table(out); }
 extern "C" void jxl_debug_pq8_thresholds(float* out) { jxl::build_pq8_thresholds(out); }
 extern "C" int jxl_debug_srgb8_table(float* out) { return jxl::build_srgb8_table(out) ? 0 : -1; }
-extern "C" int jxl_debug_srgb8_ref(float f) { return jxl::srgb8_ref(f); }
+extern "C" int jxl_debug_srgb8_ref(float f) { return jxl::quant_ref(JXL_TRANSFER_SRGB, 255, f); }
 
 namespace {
 int out_elem_size(int fmt) { return (fmt == JXL_OUT_U16 || fmt == JXL_OUT_RGB16) ? 2 : (fmt == JXL_OUT_U8 || fmt == JXL_OUT_RGB8) ? 1 : 4; }
@@ -1367,9 +1313,9 @@ const float* pq16_thresholds_for(jxl_ctx* c, int transfer, int max_value) {
     static std::once_flag once;
     static std::vector<float> thr;
     std::call_once(once, [] {
-        thr.resize(65537 + 257);
+        thr.resize(kPq8ThrOffset + 257);
         build_pq16_thresholds(thr.data());
-        build_pq8_thresholds(thr.data() + 65537);
+        build_pq8_thresholds(thr.data() + kPq8ThrOffset);
     });
     if (!c->pq16_thr.ensure(sizeof(float) * thr.size()) ||
         hipMemcpy(c->pq16_thr.p, thr.data(), sizeof(float) * thr.size(), hipMemcpyHostToDevice) != hipSuccess) {
@@ -1389,7 +1335,7 @@ const float* srgb16_table_for(jxl_ctx* c, int transfer, int max_value) {
     static std::once_flag once;
     static std::vector<float> tab;
     std::call_once(once, [] {
-        tab.resize((size_t)kSrgb8TableFloats + 65537);
+        tab.resize((size_t)kSrgb16ThrOffset + kThr16Floats);
         build_srgb16_table(tab.data());
     });
     if (!c->srgb16_tab.ensure(sizeof(float) * tab.size()) ||

@@ -255,10 +255,13 @@ void launch_pfm_samples(const PfmArgs& p, hipStream_t s);
 constexpr int kPqTableFloats = (129 - 87) * 128 * 4;
 void build_pq_table(float* out /* [kPqTableFloats] */);
 constexpr int kSrgb8TableFloats = (127 - 118) * 128 * 4;
-bool build_srgb8_table(float* out /* [kSrgb8TableFloats] */);
-void build_pq16_thresholds(float* out /* [65537] */);
+bool build_srgb8_table(float* out /* [kSrgb8TableFloats] */);  // false: a segment with more than three thresholds (never)
+constexpr int kThr16Floats = 65537;                   // thresholds of a 16-bit quantiser: thr[0] = -inf .. thr[65536] = +inf
+constexpr int kPq8ThrOffset = kThr16Floats;           // RestoreParams::pq16_thr: the PQ -> 8 bit thresholds follow the 16-bit ones
+constexpr int kSrgb16ThrOffset = kSrgb8TableFloats;   // RestoreParams::srgb16_tab: the thresholds follow the segments
+void build_pq16_thresholds(float* out /* [kThr16Floats] */);
 void build_pq8_thresholds(float* out /* [257] */);
-void build_srgb16_table(float* out /* [kSrgb8TableFloats + 65537]: segments, then thresholds */);  // false: a segment with more than three thresholds (never)
+void build_srgb16_table(float* out /* [kSrgb16ThrOffset + kThr16Floats]: segments, then thresholds */);
 // fused restoration + colour tile kernel (Gab -> EPF iters -> XYB -> optional transfer/quantise)
 struct RestoreParams {
     int gab, epf_iters, xyb, transfer, max_value, out_elem;
@@ -270,10 +273,10 @@ struct RestoreParams {
     float sharp_lut[8];
     const float* pq_tab;  // device: PQ segment table (null: double-precision PQ)
     const float* srgb8_tab;  // device: sRGB -> 8-bit threshold table (fp_srgb8; null: double-precision pow + quantise)
-    const float* pq16_thr;   // device: the 65537 thresholds of PQ -> 16 bit (fp_pq16), then the 257 of PQ -> 8 bit (fp_pq8);
-                             // null: table / f64 float result, then quantise
-    const float* srgb16_tab;  // device: quadratic segments of the sRGB curve over [2^-9, 1) + (at float offset kSrgb8TableFloats) the
-                              // 65537 thresholds of sRGB -> 16 bit (fp_srgb16; null: double-precision pow + quantise)
+    const float* pq16_thr;   // device: the kThr16Floats thresholds of PQ -> 16 bit (fp_pq16), then (at kPq8ThrOffset) the 257 of
+                             // PQ -> 8 bit (fp_pq8); null: table / f64 float result, then quantise
+    const float* srgb16_tab;  // device: quadratic segments of the sRGB curve over [2^-9, 1), then (at kSrgb16ThrOffset) the
+                              // kThr16Floats thresholds of sRGB -> 16 bit (fp_srgb16; null: double-precision pow + quantise)
 };
 // argument block of the fused kernel (one per frame; an array of them for the batched launch)
 struct FusedArgs {

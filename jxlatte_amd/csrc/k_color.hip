@@ -23,20 +23,17 @@
 namespace jxl {
 namespace {
 
-// stages 6 + 7 with integer output: the exact threshold tables of k_transfer where it uses them, else float + castToInt0
+// stages 6 + 7 with integer output: sRGB and PQ as k_transfer quantises them (the exact threshold tables where it uses them),
+// BT.709, gamma and linear as float + castToInt0
 __device__ __forceinline__ int32_t from_linear_int(float v, const ColorArgs& a) {
-    if (a.tf_out == JXL_TF_PQ && a.max_value == 65535 && a.pq_tab && a.pq16_thr)
-        return fp_pq16(v, reinterpret_cast<const float4*>(a.pq_tab), a.pq16_thr);
-    if (a.tf_out == JXL_TF_PQ && a.max_value == 255 && a.pq16_thr) return fp_pq8(v, a.pq16_thr + 65537);
-    if (a.tf_out == JXL_TF_SRGB && a.max_value == 65535 && a.srgb16_tab)
-        return fp_srgb16(v, reinterpret_cast<const float4*>(a.srgb16_tab), a.srgb16_tab + kSrgb8TableFloats);
-    if (a.tf_out == JXL_TF_SRGB && a.max_value == 255 && a.srgb8_tab) return fp_srgb8(v, reinterpret_cast<const float4*>(a.srgb8_tab));
-    return to_int(from_linear(v, a.tf_out, a.p_out, a.kind_out, reinterpret_cast<const float4*>(a.pq_tab)), a.max_value);
+    if (a.tf_out == JXL_TF_PQ) return transfer_quant(v, JXL_TRANSFER_PQ, a.max_value, a.pq_tab, a.srgb8_tab, a.pq16_thr, a.srgb16_tab);
+    if (a.tf_out == JXL_TF_SRGB) return transfer_quant(v, JXL_TRANSFER_SRGB, a.max_value, a.pq_tab, a.srgb8_tab, a.pq16_thr, a.srgb16_tab);
+    return cast_to_int0(from_linear(v, a.tf_out, a.p_out, a.kind_out, a.pq_tab), a.max_value);
 }
 
 __device__ __forceinline__ void store_sample(const ColorArgs& a, int c, int64_t i, float v) {
     if (a.max_value > 0) ((int32_t*)a.out[c])[i] = from_linear_int(v, a);
-    else ((float*)a.out[c])[i] = from_linear(v, a.tf_out, a.p_out, a.kind_out, reinterpret_cast<const float4*>(a.pq_tab));
+    else ((float*)a.out[c])[i] = from_linear(v, a.tf_out, a.p_out, a.kind_out, a.pq_tab);
 }
 
 }  // namespace

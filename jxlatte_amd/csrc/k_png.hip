@@ -34,17 +34,12 @@ struct PngShape {
     static constexpr int kWords = 4 * NCH * BYTES / 4;               // the lane's 4 pixels: 1 .. 8 words
 };
 
-__device__ __forceinline__ uint32_t png_quant(float v, int maxv) {
-    const int32_t q = f2i(v * (float)maxv + 0.5f);
-    return (uint32_t)(q < 0 ? 0 : q > maxv ? maxv : q);
-}
-
 // one pixel: the words of its colour planes (w[c], c < n_planes) and of its alpha plane -> NCH samples, each below 2^(8 BYTES)
 template <int NCH, int BYTES>
 __device__ __forceinline__ void png_pixel(const PngArgs& p, const uint32_t w[3], uint32_t aw, uint32_t q[4]) {
     using S = PngShape<NCH, BYTES>;
     const ColorArgs& a = p.c;
-    const float4* pq_tab = reinterpret_cast<const float4*>(a.pq_tab);
+    const float* pq_tab = a.pq_tab;
     const int maxv = BYTES == 1 ? 255 : 65535;
     float v[3];
     v[0] = linear_word(a, 0, w[0]);
@@ -77,11 +72,11 @@ __device__ __forceinline__ void png_pixel(const PngArgs& p, const uint32_t w[3],
             const int32_t ia = (int32_t)aw;
             q[S::kColors] = (uint32_t)(ia < 0 ? 0 : ia > maxv ? maxv : ia);
         } else {
-            q[S::kColors] = png_quant(fa, maxv);
+            q[S::kColors] = (uint32_t)cast_to_int0(fa, maxv);
         }
     }
 #pragma unroll
-    for (int c = 0; c < S::kColors; c++) q[c] = png_quant(v[c], maxv);
+    for (int c = 0; c < S::kColors; c++) q[c] = (uint32_t)cast_to_int0(v[c], maxv);
 }
 
 template <int NCH, int BYTES>

@@ -5,7 +5,7 @@
 // (file compiled with -ffp-contract=off).
 #include <hip/hip_runtime.h>
 
-#include "jxl_internal.h"
+#include "sample_ops.h"
 #include "jxl_blend.h"
 
 namespace jxl {
@@ -18,13 +18,6 @@ __device__ __forceinline__ int mirror_c(int c, int size) {
         c = tc >= 0 ? tc : (size << 1) + tc;
     }
     return c;
-}
-// Java (int)float
-__device__ __forceinline__ int32_t f2i_sat(float v) {
-    if (v != v) return 0;
-    if (v >= 2147483648.0f) return INT32_MAX;
-    if (v <= -2147483648.0f) return INT32_MIN;
-    return (int32_t)v;
 }
 __device__ __forceinline__ float clamp_asc(float v, float lo, float hi) { return v < lo ? lo : v > hi ? hi : v; }
 
@@ -179,8 +172,8 @@ __global__ __launch_bounds__(256) void k_noise_add(float* p0, float* p1, float* 
         inG = inG < 0.0f ? 0.0f : 3.0f * inG;
         int iR, iG;
         float fR, fG;
-        if (inR >= 7.0f) { iR = 6; fR = 1.0f; } else { iR = f2i_sat(inR); fR = inR - (float)iR; }
-        if (inG >= 7.0f) { iG = 6; fG = 1.0f; } else { iG = f2i_sat(inG); fG = inG - (float)iG; }
+        if (inR >= 7.0f) { iR = 6; fR = 1.0f; } else { iR = java_f2i(inR); fR = inR - (float)iR; }
+        if (inG >= 7.0f) { iG = 6; fG = 1.0f; } else { iG = java_f2i(inG); fG = inG - (float)iG; }
         float sr = (l[iR + 1] - l[iR]) * fR + l[iR];
         float sg = (l[iG + 1] - l[iG]) * fG + l[iG];
         sr = clamp_asc(sr, 0.0f, 1.0f);
@@ -302,8 +295,7 @@ __global__ __launch_bounds__(256) void k_pack(PackArgs a, void* out) {
 #pragma unroll
         for (int c = 0; c < 4; c++) {
             if (c >= a.nch) break;
-            int v = isf[c] ? f2i_sat(fv[c] * (float)maxv + 0.5f) : iv[c];
-            v = v < 0 ? 0 : v > maxv ? maxv : v;
+            const int v = isf[c] ? cast_to_int0(fv[c], maxv) : iv[c] < 0 ? 0 : iv[c] > maxv ? maxv : iv[c];
             const int64_t o = i * a.nch + c;
             if (a.bit_depth == 8) ((uint8_t*)out)[o] = (uint8_t)v;
             else ((uint16_t*)out)[o] = a.big_endian ? (uint16_t)(((v & 0xff) << 8) | (v >> 8)) : (uint16_t)v;

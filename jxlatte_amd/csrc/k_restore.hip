@@ -11,8 +11,7 @@
 // every tap addressed exactly like the reference). They are the general path (any size, any
 // iteration count) and the cross-check for the fused tile kernel in k_restore_fused.hip.
 // Strict f32: sums in reference order, no FMA contraction, correctly rounded division.
-#include "jxl_internal.h"
-#include "jxl_fastpow.h"
+#include "sample_ops.h"
 
 namespace jxl {
 
@@ -159,23 +158,10 @@ void launch_epf_iter(const float* const in[3], float* const out[3], int h, int w
         hipLaunchKernelGGL(k_epf<2>, grid, block, 0, s, in[0], in[1], in[2], out[0], out[1], out[2], h, w, inv_sigma, p);
 }
 
-// OpsinInverseMatrix.invertXYB (OpsinInverseMatrix.java:124-139)
-__device__ __forceinline__ void xyb_px(const XybParams& p, float& X, float& Y, float& B) {
-    const float gammaL = Y + X + p.cob[0];
-    const float gammaM = Y - X + p.cob[1];
-    const float gammaS = B + p.cob[2];
-    const float mixL = (gammaL * gammaL) * gammaL + p.ob[0];
-    const float mixM = (gammaM * gammaM) * gammaM + p.ob[1];
-    const float mixS = (gammaS * gammaS) * gammaS + p.ob[2];
-    X = p.sm[0] * mixL + p.sm[1] * mixM + p.sm[2] * mixS;
-    Y = p.sm[3] * mixL + p.sm[4] * mixM + p.sm[5] * mixS;
-    B = p.sm[6] * mixL + p.sm[7] * mixM + p.sm[8] * mixS;
-}
-
 __global__ __launch_bounds__(256) void k_xyb(float* p0, float* p1, float* p2, int64_t n, XybParams p) {
     for (int64_t i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         float X = p0[i], Y = p1[i], B = p2[i];
-        xyb_px(p, X, Y, B);
+        invert_xyb_px(p, X, Y, B);
         p0[i] = X;
         p1[i] = Y;
         p2[i] = B;
@@ -208,87 +194,19 @@ void launch_ycbcr(float* const planes[3], int64_t n, hipStream_t s) {
     hipLaunchKernelGGL(k_ycbcr, dim3(grid), dim3(256), 0, s, planes[0], planes[1], planes[2], n);
 }
 
-// TransferFunction.TF_PQ.fromLinear through the default fromLinearF (TransferFunction.java:83-87,104-106):
-// double pow, result cast to float. Java's Math.pow is specified to 1 ulp (double); parity bar <= 1 ulp float.
-// PQ / sRGB through jxl_fastpow.h (~110 instead of 463 instructions for the PQ curve, float results identical on all
-// sampled inputs; JXL_EXACT_POW builds the ocml pow() form for comparison)
-#ifdef JXL_EXACT_POW
-__device__ __forceinline__ float tf_pq(float f) {
-    const double d = pow((double)f, 0.159423828125);
-    return (float)pow((0.8359375 + 18.8515625 * d) / (1.0 + 18.6875 * d), 78.84375);
-}
-__device__ __forceinline__ float tf_srgb(float f) {
-    if (f < 0.00313066844250063f) return f * 12.92f;
-    return 1.055f * (float)pow((double)f, 0.4166666666666667) + -0.055f;
-}
-#else
-__device__ __forceinline__ float tf_pq(float f) { return fp_tf_pq(f); }
-__device__ __forceinline__ float tf_srgb(float f) { return fp_tf_srgb(f); }
-#endif
-// Java (int)float: NaN -> 0, saturating
-__device__ __forceinline__ int32_t java_f2i(float v) {
-    if (v != v) return 0;
-    if (v >= 2147483648.0f) return INT32_MAX;
-    if (v <= -2147483648.0f) return INT32_MIN;
-    return (int32_t)v;
-}
-
-__device__ __forceinline__ float apply_transfer(float v, int transfer, const float4* pq_tab) {
-#ifndef JXL_EXACT_POW
-    if (transfer == JXL_TRANSFER_PQ && pq_tab) return fp_tf_pq_tab(v, pq_tab);
-#endif
-    if (transfer == JXL_TRANSFER_PQ) return tf_pq(v);
-    if (transfer == JXL_TRANSFER_SRGB) return tf_srgb(v);
-    return v;
-}
-
-// ImageBuffer.castToInt0 (ImageBuffer.java:129-147)
-__device__ __forceinline__ int32_t quantise(float v, int max_value) {
-    const int32_t q = java_f2i(v * (float)max_value + 0.5f);
-    return q < 0 ? 0 : q > max_value ? max_value : q;
-}
-
+// JXLImage.transferInPlace + ImageBuffer.castToInt0 of one plane (max_value > 0), or the float curve alone
 __global__ __launch_bounds__(256) void k_transfer(const float* in, int64_t n, int transfer, int max_value, void* out,
-                                                  int out_elem, int out_pitch, int out_off, const float4* pq_tab, const float4* srgb8_tab,
+                                                  int out_elem, int out_pitch, int out_off, const float* pq_tab, const float* srgb8_tab,
                                                   const float* pq16_thr, const float* srgb16_tab) {
     for (int64_t i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const int64_t o = i * out_pitch + out_off;
-#ifndef JXL_EXACT_POW
-        if (transfer == JXL_TRANSFER_PQ && max_value == 65535 && pq_tab && pq16_thr) {  // PQ + 16-bit quantisation, exact
-            const int32_t q = fp_pq16(in[i], pq_tab, pq16_thr);
-            if (out_elem == 4) ((int32_t*)out)[o] = q;
-            else ((uint16_t*)out)[o] = (uint16_t)q;
-            continue;
-        }
-        if (transfer == JXL_TRANSFER_PQ && max_value == 255 && pq16_thr) {  // PQ + 8-bit quantisation, exact
-            const int32_t q = fp_pq8(in[i], pq16_thr + 65537);
-            if (out_elem == 4) ((int32_t*)out)[o] = q;
-            else if (out_elem == 2) ((uint16_t*)out)[o] = (uint16_t)q;
-            else ((uint8_t*)out)[o] = (uint8_t)q;
-            continue;
-        }
-        if (transfer == JXL_TRANSFER_SRGB && max_value == 65535 && srgb16_tab) {  // sRGB + 16-bit quantisation, exact
-            const int32_t q = fp_srgb16(in[i], reinterpret_cast<const float4*>(srgb16_tab), srgb16_tab + kSrgb8TableFloats);
-            if (out_elem == 4) ((int32_t*)out)[o] = q;
-            else ((uint16_t*)out)[o] = (uint16_t)q;
-            continue;
-        }
-        if (transfer == JXL_TRANSFER_SRGB && max_value == 255 && srgb8_tab) {  // transfer + quantisation as one threshold look-up
-            const int32_t q = fp_srgb8(in[i], srgb8_tab);
-            if (out_elem == 4) ((int32_t*)out)[o] = q;
-            else if (out_elem == 2) ((uint16_t*)out)[o] = (uint16_t)q;
-            else ((uint8_t*)out)[o] = (uint8_t)q;
-            continue;
-        }
-#endif
-        const float v = apply_transfer(in[i], transfer, pq_tab);
         if (max_value > 0) {
-            const int32_t q = quantise(v, max_value);
+            const int32_t q = transfer_quant(in[i], transfer, max_value, pq_tab, srgb8_tab, pq16_thr, srgb16_tab);
             if (out_elem == 4) ((int32_t*)out)[o] = q;
             else if (out_elem == 2) ((uint16_t*)out)[o] = (uint16_t)q;
             else ((uint8_t*)out)[o] = (uint8_t)q;
         } else {
-            ((float*)out)[o] = v;
+            ((float*)out)[o] = from_linear_f(in[i], transfer, pq_tab);
         }
     }
 }
@@ -300,7 +218,7 @@ void launch_transfer(const float* in, int64_t n, int transfer, int max_value, vo
     int grid = (int)((n + 255) / 256);
     if (grid > 8192) grid = 8192;
     hipLaunchKernelGGL(k_transfer, dim3(grid), dim3(256), 0, s, in, n, transfer, max_value, out, out_elem, out_pitch, out_off,
-                       reinterpret_cast<const float4*>(pq_tab), reinterpret_cast<const float4*>(srgb8_tab), pq16_thr, srgb16_tab);
+                       pq_tab, srgb8_tab, pq16_thr, srgb16_tab);
 }
 
 }  // namespace jxl

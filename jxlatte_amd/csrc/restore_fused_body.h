@@ -439,7 +439,7 @@ struct OutSink {
     const FusedArgs& a;
     const TileCtx& tc;
     __device__ __forceinline__ void colour(float& v0, float& v1, float& v2) const {
-        if (a.p.xyb) sink_colour(a.p.xybp, v0, v1, v2);
+        if (a.p.xyb) invert_xyb_px(a.p.xybp, v0, v1, v2);
     }
     // one pixel at region position (y, x)
     __device__ __forceinline__ void operator()(int y, int x, float v0, float v1, float v2) const {

@@ -2,45 +2,9 @@
 // (JXLImage.java:244-258, TransferFunction.java:39-44,83-87) + ImageBuffer.castToInt0 (ImageBuffer.java:129-147) + the
 // global store of one pixel.
 #pragma once
-#include "jxl_internal.h"
-#include "jxl_fastpow.h"
+#include "sample_ops.h"
 
 namespace jxl {
-
-// Java (int)float
-__device__ __forceinline__ int32_t sink_f2i_java(float v) {
-    if (v != v) return 0;
-    if (v >= 2147483648.0f) return INT32_MAX;
-    if (v <= -2147483648.0f) return INT32_MIN;
-    return (int32_t)v;
-}
-// PQ / sRGB through jxl_fastpow.h (JXL_EXACT_POW builds the ocml pow() form for comparison)
-#ifdef JXL_EXACT_POW
-__device__ __forceinline__ float sink_tf_pq(float f) {
-    const double d = pow((double)f, 0.159423828125);
-    return (float)pow((0.8359375 + 18.8515625 * d) / (1.0 + 18.6875 * d), 78.84375);
-}
-__device__ __forceinline__ float sink_tf_srgb(float f) {
-    if (f < 0.00313066844250063f) return f * 12.92f;
-    return 1.055f * (float)pow((double)f, 0.4166666666666667) + -0.055f;
-}
-#else
-__device__ __forceinline__ float sink_tf_pq(float f) { return fp_tf_pq(f); }
-__device__ __forceinline__ float sink_tf_srgb(float f) { return fp_tf_srgb(f); }
-#endif
-
-// OpsinInverseMatrix.invertXYB of one pixel
-__device__ __forceinline__ void sink_colour(const XybParams& xp, float& v0, float& v1, float& v2) {
-    const float gammaL = v1 + v0 + xp.cob[0];
-    const float gammaM = v1 - v0 + xp.cob[1];
-    const float gammaS = v2 + xp.cob[2];
-    const float mixL = (gammaL * gammaL) * gammaL + xp.ob[0];
-    const float mixM = (gammaM * gammaM) * gammaM + xp.ob[1];
-    const float mixS = (gammaS * gammaS) * gammaS + xp.ob[2];
-    v0 = xp.sm[0] * mixL + xp.sm[1] * mixM + xp.sm[2] * mixS;
-    v1 = xp.sm[3] * mixL + xp.sm[4] * mixM + xp.sm[5] * mixS;
-    v2 = xp.sm[6] * mixL + xp.sm[7] * mixM + xp.sm[8] * mixS;
-}
 
 // ---- sink kinds: what the fused restoration kernels are instantiated for (r4). SK_GENERIC picks transfer function and output
 // format per sample at run time (uniform compares and branches around every store: SALU 4.3x the float-plane variant, r3
@@ -66,24 +30,27 @@ inline int sink_kind_of(const RestoreParams& p) {
     return SK_GENERIC;
 }
 
-// transfer function + ImageBuffer.castToInt0 of one sample (max_value > 0): the threshold-table forms of jxl_fastpow.h where the
-// output format has one (the oracle's integer for every input), else the float transfer and the Java cast
+// transfer function + ImageBuffer.castToInt0 of one sample (max_value > 0), format chosen at run time: the selection rule of
+// transfer_quant (sample_ops.h) spelt out over the argument block, and below, in sink_store_k, that of from_linear_f. The two
+// selections stay restated here on purpose: as calls of the shared functions the selectors are read once in front of the rule
+// and its conditions are combined instead of branched on one by one, and all 22 instantiations of the generic fused kernels --
+// the hot path -- then come out of the compiler as other code (profiles/sample_ops_refactor.md). The cast, the curves and the
+// table offsets are the shared ones.
 __device__ __forceinline__ int32_t sink_quant(const FusedArgs& a, float t) {
 #ifndef JXL_EXACT_POW
     if (a.p.transfer == JXL_TRANSFER_PQ && a.p.max_value == 65535 && a.p.pq_tab && a.p.pq16_thr)
         return fp_pq16(t, reinterpret_cast<const float4*>(a.p.pq_tab), a.p.pq16_thr);
-    if (a.p.transfer == JXL_TRANSFER_PQ && a.p.max_value == 255 && a.p.pq16_thr) return fp_pq8(t, a.p.pq16_thr + 65537);
+    if (a.p.transfer == JXL_TRANSFER_PQ && a.p.max_value == 255 && a.p.pq16_thr) return fp_pq8(t, a.p.pq16_thr + kPq8ThrOffset);
     if (a.p.transfer == JXL_TRANSFER_SRGB && a.p.max_value == 65535 && a.p.srgb16_tab)
-        return fp_srgb16(t, reinterpret_cast<const float4*>(a.p.srgb16_tab), a.p.srgb16_tab + kSrgb8TableFloats);
+        return fp_srgb16(t, reinterpret_cast<const float4*>(a.p.srgb16_tab), a.p.srgb16_tab + kSrgb16ThrOffset);
     if (a.p.transfer == JXL_TRANSFER_SRGB && a.p.max_value == 255 && a.p.srgb8_tab)
         return fp_srgb8(t, reinterpret_cast<const float4*>(a.p.srgb8_tab));
     if (a.p.transfer == JXL_TRANSFER_PQ && a.p.pq_tab) t = fp_tf_pq_tab(t, reinterpret_cast<const float4*>(a.p.pq_tab));
     else
 #endif
-    if (a.p.transfer == JXL_TRANSFER_PQ) t = sink_tf_pq(t);
-    else if (a.p.transfer == JXL_TRANSFER_SRGB) t = sink_tf_srgb(t);
-    const int32_t q = sink_f2i_java(t * (float)a.p.max_value + 0.5f);
-    return q < 0 ? 0 : q > a.p.max_value ? a.p.max_value : q;
+    if (a.p.transfer == JXL_TRANSFER_PQ) t = tf_pq(t);
+    else if (a.p.transfer == JXL_TRANSFER_SRGB) t = tf_srgb(t);
+    return cast_to_int0(t, a.p.max_value);
 }
 // the same for a sink kind known at compile time
 template <int SK>
@@ -91,7 +58,7 @@ __device__ __forceinline__ int32_t sink_quant_k(const FusedArgs& a, float t) {
     if constexpr (SK == SK_PQ_U16 || SK == SK_PQ_RGB16) return fp_pq16(t, reinterpret_cast<const float4*>(a.p.pq_tab), a.p.pq16_thr);
     else if constexpr (SK == SK_SRGB_RGB8) return fp_srgb8(t, reinterpret_cast<const float4*>(a.p.srgb8_tab));
     else if constexpr (SK == SK_SRGB_RGB16)
-        return fp_srgb16(t, reinterpret_cast<const float4*>(a.p.srgb16_tab), a.p.srgb16_tab + kSrgb8TableFloats);
+        return fp_srgb16(t, reinterpret_cast<const float4*>(a.p.srgb16_tab), a.p.srgb16_tab + kSrgb16ThrOffset);
     else return sink_quant(a, t);
 }
 
@@ -136,8 +103,8 @@ __device__ __forceinline__ void sink_store_k(const FusedArgs& a, uint32_t g, flo
             if (a.p.transfer == JXL_TRANSFER_PQ && a.p.pq_tab) t = fp_tf_pq_tab(t, reinterpret_cast<const float4*>(a.p.pq_tab));
             else
 #endif
-            if (a.p.transfer == JXL_TRANSFER_PQ) t = sink_tf_pq(t);
-            else if (a.p.transfer == JXL_TRANSFER_SRGB) t = sink_tf_srgb(t);
+            if (a.p.transfer == JXL_TRANSFER_PQ) t = tf_pq(t);
+            else if (a.p.transfer == JXL_TRANSFER_SRGB) t = tf_srgb(t);
             ((float*)a.out[c])[g] = t;
         }
     }

@@ -2,7 +2,7 @@
 // and its binning into the tiles of k_splines. No device code and no device call: jxl_spline_arcs works without a GPU.
 // Float operations in the reference's order (the library is built with -ffp-contract=off); the double functions pow, cos,
 // sqrt and log are the host libm's, as in jxlatte_amd/decoder.py, whose arc table this one equals bit for bit.
-#include "jxl_internal.h"
+#include "sample_ops.h"
 
 #include <cmath>
 #include <limits>
@@ -105,14 +105,8 @@ bool intermediary_samples(const std::vector<float>& uy, const std::vector<float>
     return true;
 }
 
-// MathHelper.round (MathHelper.java:36-38): (int)(d + 0.5f), Java's cast (NaN -> 0, saturating)
-int32_t java_round(float d) {
-    const float v = d + 0.5f;
-    if (v != v) return 0;
-    if (v >= 2147483648.0f) return std::numeric_limits<int32_t>::max();
-    if (v <= -2147483648.0f) return std::numeric_limits<int32_t>::min();
-    return (int32_t)v;
-}
+// MathHelper.round (MathHelper.java:36-38): (int)(d + 0.5f), Java's cast
+int32_t java_round(float d) { return java_f2i(d + 0.5f); }
 
 }  // namespace
 

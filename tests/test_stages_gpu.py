@@ -186,6 +186,39 @@ def test_quantise_java_int_cast_semantics(ctx, orc):
         assert np.array_equal(host.transfer(ctx, x, abi.TRANSFER_NONE, maxv), orc.transfer(x, abi.TRANSFER_NONE, maxv))
 
 
+@pytest.mark.parametrize("tf,tf_color", [(abi.TRANSFER_NONE, abi.TF_LINEAR), (abi.TRANSFER_SRGB, abi.TF_SRGB), (abi.TRANSFER_PQ, abi.TF_PQ)])
+def test_tableless_quantiser_is_one_function_behind_every_entry(ctx, orc, tf, tf_color):
+    """A max value without a threshold table (1023, 4095) takes the curve + castToInt0 leg of the shared quantiser: the same
+    floats through jxl_stage_transfer and jxl_stage_color_convert (linear in, no matrix, no scale, same target curve) give the
+    same integers, and those are the oracle's castToInt0 of the stage's own float result; jxl_stage_pack of that float result
+    (it quantises to 255 or 65535 without a table) gives what the two other entries make of it at either depth. Against the oracle end to end the
+    curves keep the transfer stage's stated tolerance (1 ulp of the float: a level apart for a few inputs in 10^4); without
+    a curve the integers are the oracle's."""
+    rng = np.random.default_rng(31)
+    sp = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, 1e-45, -1e-45, 1e-39, -1e-39, 1.1754944e-38, -1e-7, 1e-7, 0.99999994, 1.0, 1.0000001,
+                   0.0031306684, 0.0031306685, 2.0 ** 21, 2.0 ** 31 / 1023, 2.0 ** 31 / 4095, 2.0 ** 31, 3e9, -3e9, 1e30, -1e30, 3e38], F)
+    x = np.concatenate([sp, rng.random(2000), rng.uniform(-0.01, 0.01, 500), 1.0 + rng.uniform(-0.01, 0.01, 500),
+                        10.0 ** rng.uniform(-44, 38.5, 500), -(10.0 ** rng.uniform(-44, 38.5, 200))]).astype(F).reshape(1, -1)
+    flt = host.transfer(ctx, x, tf)
+    flt_c, = host.colorConvert(ctx, [x], tfOut=tf_color)
+    assert_bits_equal(flt_c, flt, "float result of the two entries")
+    for maxv in (1023, 4095):
+        got = host.transfer(ctx, x, tf, maxv)
+        got_c, = host.colorConvert(ctx, [x], tfOut=tf_color, maxValue=maxv)
+        assert np.array_equal(got, got_c)
+        assert np.array_equal(got, orc.transfer(flt, abi.TRANSFER_NONE, maxv))
+        exp = orc.transfer(x, tf, maxv)
+        if tf == abi.TRANSFER_NONE:
+            assert np.array_equal(got, exp)
+        else:
+            assert np.abs(got - exp).max() <= 1 and (got != exp).mean() < 1e-3
+    for depth, maxv in ((8, 255), (16, 65535)):
+        q = orc.transfer(flt, abi.TRANSFER_NONE, maxv)
+        assert np.array_equal(host.packSamples(ctx, [flt], depth)[..., 0].astype(np.int32), q)
+        assert np.array_equal(host.transfer(ctx, flt, abi.TRANSFER_NONE, maxv), q)
+        assert np.array_equal(host.colorConvert(ctx, [flt], maxValue=maxv)[0], q)
+
+
 def test_fused_restore_equals_stage_kernels(ctx, orc):
     """the fused tile kernel and the stage-per-kernel path are two implementations of the same reference code"""
     frame = synth.make_vardct_frame(200, 136, seed=21, mix="default")
