@@ -643,6 +643,75 @@ jxl_status jxl_stage_blend(jxl_ctx* ctx, int32_t mode, uint32_t flags, int32_t i
                            void* canvas, int32_t ch, int32_t cw, const void* frame, int32_t fh, int32_t fw,
                            const void* ref, int32_t rh, int32_t rw, const float* frame_alpha, const float* ref_alpha,
                            const jxl_blend_rect* rect);
+
+/* ---- device plane sets: the canvas and the reference frames of JXLCodestreamDecoder.decode kept on the device ----
+ * A plane set is n planes (1..JXL_CANVAS_MAX_PLANES) of h x w 4-byte samples in device memory, each tagged float or int32 as an
+ * ImageBuffer is (ImageBuffer.java:9-10); the tag changes only through the cast below. A context owns its sets and frees what
+ * is left of them when it is destroyed; a set is addressed by a small integer id (>= 0). An unknown id is
+ * JXL_ERR_INVALID_ARGUMENT, more than JXL_CANVAS_MAX_PLANES planes JXL_ERR_UNSUPPORTED. */
+#define JXL_CANVAS_MAX_PLANES 16
+#define JXL_PLANE_FLOAT 0 /* ImageBuffer.TYPE_FLOAT */
+#define JXL_PLANE_INT32 1 /* ImageBuffer.TYPE_INT */
+/* One canvas channel of a blendFrame call, with what blendBuffers resolves before its inner switch (:420-465) already resolved:
+ * frame_plane is the remapped frame index of :420; mode is JXL_BLEND_REPLACE where :437 takes the short cut; flags carry isAlpha
+ * (:426), hasExtra (:423), BlendingInfo.clamp and premult (:431). frame_alpha / ref_alpha: the planes frameColors + alphaChannel
+ * of the frame set and colors + alphaChannel of the reference set (:444-445), looked at only where the mode reads them. */
+typedef struct jxl_canvas_blend_chan {
+    int32_t  frame_plane;
+    int32_t  mode;   /* JXL_BLEND_* 0..4 */
+    uint32_t flags;  /* JXL_BLEND_FLAG_* */
+    int32_t  frame_alpha;
+    int32_t  ref_alpha;
+} jxl_canvas_blend_chan;
+typedef struct jxl_canvas_blend_desc {
+    int32_t canvas, frame; /* set ids; they differ */
+    int32_t ref;           /* set id, -1 for refBuffers == null (every channel is then a copy), or the canvas id itself */
+    int32_t n_chan;        /* the canvas set's plane count: blendFrame visits every canvas channel (:530) */
+    jxl_blend_rect rect;
+    jxl_canvas_blend_chan chan[JXL_CANVAS_MAX_PLANES];
+} jxl_canvas_blend_desc;
+/* shape and plane types of a set, for the check below */
+typedef struct jxl_canvas_shape {
+    int32_t n, h, w;
+    int32_t types[JXL_CANVAS_MAX_PLANES];
+} jxl_canvas_shape;
+/* new ImageBuffer(type, height, width) per plane (JXLCodestreamDecoder.java:640-643, :441-442): zero-filled */
+jxl_status jxl_canvas_create(jxl_ctx* ctx, int32_t n, int32_t h, int32_t w, const int32_t* types, int32_t* id);
+jxl_status jxl_canvas_destroy(jxl_ctx* ctx, int32_t id);
+/* plane count, size and plane tags of a set (ImageBuffer.getType, .height, .width) */
+jxl_status jxl_canvas_describe(jxl_ctx* ctx, int32_t id, jxl_canvas_shape* out);
+/* new ImageBuffer(b) per plane (:653, :631-632): a device copy, independent of its source from then on */
+jxl_status jxl_canvas_clone(jxl_ctx* ctx, int32_t id, int32_t* new_id);
+/* src: h * w samples of `type`, which becomes the plane's tag */
+jxl_status jxl_canvas_upload(jxl_ctx* ctx, int32_t id, int32_t plane, const void* src, int32_t type);
+/* dst: h * w samples; *type (may be NULL): the plane's tag */
+jxl_status jxl_canvas_download(jxl_ctx* ctx, int32_t id, int32_t plane, void* dst, int32_t* type);
+/* A new set of 3 + n_extra planes: the first three are float and hold a copy of the context's resident planes (Frame.getBuffer
+ * of the colour channels at :528 without the host), the others are zero-filled planes of extra_types for the frame's extra
+ * channels -- a blend reads the colours and the alpha of a frame from ONE set. JXL_ERR_STATE without resident planes. */
+jxl_status jxl_canvas_from_planes(jxl_ctx* ctx, int32_t n_extra, const int32_t* extra_types, int32_t* id);
+/* ImageBuffer.castToFloat(depth) of the whole plane in place (ImageBuffer.java:99-127): sample = (float)v * (1.0f / max), max =
+ * ~(~0 << depth); nothing happens to a float plane. "invalid Max Value" (JXL_ERR_INVALID_ARGUMENT) as jxl_stage_pfm_samples. */
+jxl_status jxl_canvas_cast(jxl_ctx* ctx, int32_t id, int32_t plane, int32_t depth);
+/* JXLCodestreamDecoder.blendFrame (:515-537) as ONE launch over every channel, asynchronous on the context's stream. A lane
+ * owns pixels of the rectangle and walks the channels in canvas order, its loads and stores in program order: with ref ==
+ * canvas every sample is read at the position the lane itself writes later, so a later channel that reads an already blended
+ * alpha plane sees the new value, as the reference's aliased ImageBuffer does. No casts happen here: the planes have the
+ * types blendBuffers' casts (:433-465) would have given them -- the caller's type plan. jxl_canvas_blend_check runs first and
+ * nothing is queued when it refuses. */
+jxl_status jxl_canvas_blend(jxl_ctx* ctx, const jxl_canvas_blend_desc* d);
+/* planes 0..2 of the set, which must be float, copied into the context's resident planes (the canvas handed to
+ * transposeBuffer at :672-674 and to the writers); the set stays as it is */
+jxl_status jxl_canvas_to_planes(jxl_ctx* ctx, int32_t id);
+/* What jxl_canvas_blend refuses, without a context or a device (the reason: jxl_last_error of a NULL context). Per channel what
+ * jxl_stage_blend answers: "Illegal blend mode" (JXL_ERR_INVALID_BITSTREAM), a float function on int32 planes, planes of a
+ * channel that differ in type, alpha planes that are not float, a rectangle outside a plane that is read or written
+ * (JXL_ERR_INVALID_ARGUMENT). JXL_ERR_UNSUPPORTED for what one in-place launch cannot replay: a reference that is the canvas
+ * read anywhere but at the pixel that is written (refOffset != patchStart; blendMulAdd's alpha copy with frameOffset !=
+ * patchStart, :390). ref: NULL when d->ref is -1; the canvas' own shape when d->ref == d->canvas. */
+jxl_status jxl_canvas_blend_check(const jxl_canvas_blend_desc* d, const jxl_canvas_shape* canvas, const jxl_canvas_shape* frame,
+                                  const jxl_canvas_shape* ref);
+
 /* JXLCodestreamDecoder.transposeBufferFloat / transposeBufferInt (:43-177): EXIF orientation 1..8 of one plane of
  * 4-byte samples. out is h x w for orientation <= 4, else w x h. */
 jxl_status jxl_stage_orient(jxl_ctx* ctx, const void* in, int32_t h, int32_t w, int32_t orientation, void* out);

@@ -177,6 +177,21 @@ public final class NativeBackend implements AutoCloseable {
     public native void stagePfmSamples(ByteBuffer i0, ByteBuffer i1, ByteBuffer i2, int[] params, ByteBuffer out);  // jxl_stage_pfm_samples
     public native void planesPfmSamples(int[] params, ByteBuffer out);                                // jxl_planes_pfm_samples
 
+    // ---- device plane sets: the canvas and the reference frames on the device; a set is addressed by its id
+    public native int canvasCreate(int h, int w, int[] types);     // jxl_canvas_create (types: 0 float, 1 int32 per plane)
+    public native void canvasDestroy(int id);                      // jxl_canvas_destroy
+    public native int[] canvasDescribe(int id);                    // jxl_canvas_describe -> {n, h, w, type[n]}
+    public native int canvasClone(int id);                         // jxl_canvas_clone
+    public native void canvasUpload(int id, int plane, ByteBuffer src, int type);   // jxl_canvas_upload (src: h * w samples)
+    public native int canvasDownload(int id, int plane, ByteBuffer dst);            // jxl_canvas_download -> the plane's type
+    public native int canvasFromPlanes(int[] extraTypes);          // jxl_canvas_from_planes (extraTypes may be null)
+    public native void canvasCast(int id, int plane, int depth);   // jxl_canvas_cast
+    /** desc: {canvas, frame, ref, nChan, rect[8] as stageBlend's, then per channel {framePlane, mode, flags, frameAlpha, refAlpha}}. */
+    public native void canvasBlend(int[] desc);                    // jxl_canvas_blend
+    public native void canvasToPlanes(int id);                     // jxl_canvas_to_planes
+    /** shapes: {n, h, w, type[n]}; ref null when desc names no reference. Throws what canvasBlend would; no device needed. */
+    public static native void canvasBlendCheck(int[] desc, int[] canvas, int[] frame, int[] ref);    // jxl_canvas_blend_check
+
     // ---- Modular: plan once (begin), run, read channel by channel
     public static native int[] modularDefaultSqueezeParams(int[] widths, int[] heights, int nbMeta);  // jxl_modular_default_squeeze_params
     public static native int[] modularSqueezedShapes(int[] widths, int[] heights, int[] squeezeParams); // jxl_modular_squeezed_shapes

@@ -1244,6 +1244,142 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesPfmSa
     CHECK(jxl_planes_pfm_samples(c, &p, ADDR(out)));
 }
 
+/* ---- device plane sets (the canvas and the reference frames of JXLCodestreamDecoder.decode on the device). A transfer states
+ * no size of its own: the shim asks the library for the set's (jxl_canvas_describe) and the buffer must hold a plane of it. ---- */
+static int canvas_desc(JNIEnv* e, jintArray desc, jxl_canvas_blend_desc* d) {
+    jint head[12];
+    if (!get_ints(e, desc, 12, head)) return 0;
+    if (head[3] < 0 || head[3] > JXL_CANVAS_MAX_PLANES) {
+        bad_arg(e, "jxlatte_amd: canvas blend: channel count");
+        return 0;
+    }
+    jint all[12 + 5 * JXL_CANVAS_MAX_PLANES];
+    if (!get_ints(e, desc, 12 + 5 * head[3], all)) return 0;
+    memset(d, 0, sizeof *d);
+    d->canvas = all[0]; d->frame = all[1]; d->ref = all[2]; d->n_chan = all[3];
+    d->rect.h = all[4]; d->rect.w = all[5]; d->rect.canvas_y = all[6]; d->rect.canvas_x = all[7];
+    d->rect.frame_y = all[8]; d->rect.frame_x = all[9]; d->rect.ref_y = all[10]; d->rect.ref_x = all[11];
+    for (int i = 0; i < d->n_chan; i++) {
+        const jint* v = all + 12 + 5 * i;
+        d->chan[i].frame_plane = v[0]; d->chan[i].mode = v[1]; d->chan[i].flags = (uint32_t)v[2];
+        d->chan[i].frame_alpha = v[3]; d->chan[i].ref_alpha = v[4];
+    }
+    return 1;
+}
+static int canvas_shape(JNIEnv* e, jintArray a, jxl_canvas_shape* s) {
+    jint v[3 + JXL_CANVAS_MAX_PLANES];
+    if (!get_ints(e, a, 3, v)) return 0;
+    if (v[0] < 1 || v[0] > JXL_CANVAS_MAX_PLANES) {
+        bad_arg(e, "jxlatte_amd: canvas shape: plane count");
+        return 0;
+    }
+    if (!get_ints(e, a, 3 + v[0], v)) return 0;
+    memset(s, 0, sizeof *s);
+    s->n = v[0]; s->h = v[1]; s->w = v[2];
+    for (int i = 0; i < s->n; i++) s->types[i] = v[3 + i];
+    return 1;
+}
+
+JNIEXPORT jint JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasCreate(JNIEnv* e, jobject self, jint h, jint w, jintArray types) {
+    jxl_ctx* c = ctx_of(e, self);
+    jint t[JXL_CANVAS_MAX_PLANES];
+    int32_t id = -1;
+    const jsize n = types ? (*e)->GetArrayLength(e, types) : 0;
+    if (n > JXL_CANVAS_MAX_PLANES) { rethrow(e, NULL, JXL_ERR_UNSUPPORTED); return -1; }
+    if (!get_ints(e, types, n, t)) return -1;
+    const jxl_status st = jxl_canvas_create(c, n, h, w, (const int32_t*)t, &id);
+    if (st != JXL_OK) { rethrow(e, c, st); return -1; }
+    return id;
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasDestroy(JNIEnv* e, jobject self, jint id) {
+    jxl_ctx* c = ctx_of(e, self);
+    CHECK(jxl_canvas_destroy(c, id));
+}
+
+JNIEXPORT jintArray JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasDescribe(JNIEnv* e, jobject self, jint id) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_canvas_shape s;
+    const jxl_status st = jxl_canvas_describe(c, id, &s);
+    if (st != JXL_OK) { rethrow(e, c, st); return NULL; }
+    jint v[3 + JXL_CANVAS_MAX_PLANES] = {s.n, s.h, s.w};
+    for (int i = 0; i < s.n; i++) v[3 + i] = s.types[i];
+    jintArray out = (*e)->NewIntArray(e, 3 + s.n);
+    if (out) (*e)->SetIntArrayRegion(e, out, 0, 3 + s.n, v);
+    return out;
+}
+
+JNIEXPORT jint JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasClone(JNIEnv* e, jobject self, jint id) {
+    jxl_ctx* c = ctx_of(e, self);
+    int32_t nid = -1;
+    const jxl_status st = jxl_canvas_clone(c, id, &nid);
+    if (st != JXL_OK) { rethrow(e, c, st); return -1; }
+    return nid;
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasUpload(JNIEnv* e, jobject self, jint id, jint plane, jobject src, jint type) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_canvas_shape s;
+    CHECK(jxl_canvas_describe(c, id, &s));
+    NEED(src, 4 * area(s.h, s.w));
+    CHECK(jxl_canvas_upload(c, id, plane, ADDR(src), type));
+}
+
+JNIEXPORT jint JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasDownload(JNIEnv* e, jobject self, jint id, jint plane, jobject dst) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_canvas_shape s;
+    int32_t type = -1;
+    jxl_status st = jxl_canvas_describe(c, id, &s);
+    if (st != JXL_OK) { rethrow(e, c, st); return -1; }
+    if (!has_room(e, dst, 4 * area(s.h, s.w))) {
+        bad_arg(e, "jxlatte_amd: direct buffer dst missing or too small");
+        return -1;
+    }
+    st = jxl_canvas_download(c, id, plane, ADDR(dst), &type);
+    if (st != JXL_OK) { rethrow(e, c, st); return -1; }
+    return type;
+}
+
+JNIEXPORT jint JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasFromPlanes(JNIEnv* e, jobject self, jintArray extraTypes) {
+    jxl_ctx* c = ctx_of(e, self);
+    jint t[JXL_CANVAS_MAX_PLANES];
+    int32_t id = -1;
+    const jsize n = extraTypes ? (*e)->GetArrayLength(e, extraTypes) : 0;
+    if (n > JXL_CANVAS_MAX_PLANES - 3) { rethrow(e, NULL, JXL_ERR_UNSUPPORTED); return -1; }
+    if (n > 0 && !get_ints(e, extraTypes, n, t)) return -1;
+    const jxl_status st = jxl_canvas_from_planes(c, n, n > 0 ? (const int32_t*)t : NULL, &id);
+    if (st != JXL_OK) { rethrow(e, c, st); return -1; }
+    return id;
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasCast(JNIEnv* e, jobject self, jint id, jint plane, jint depth) {
+    jxl_ctx* c = ctx_of(e, self);
+    CHECK(jxl_canvas_cast(c, id, plane, depth));
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasBlend(JNIEnv* e, jobject self, jintArray desc) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_canvas_blend_desc d;
+    if (!canvas_desc(e, desc, &d)) return;
+    CHECK(jxl_canvas_blend(c, &d));
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasToPlanes(JNIEnv* e, jobject self, jint id) {
+    jxl_ctx* c = ctx_of(e, self);
+    CHECK(jxl_canvas_to_planes(c, id));
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasBlendCheck(JNIEnv* e, jclass k, jintArray desc, jintArray canvas,
+        jintArray frame, jintArray ref) {
+    (void)k;
+    jxl_canvas_blend_desc d;
+    jxl_canvas_shape sc, sf, sr;
+    if (!canvas_desc(e, desc, &d) || !canvas_shape(e, canvas, &sc) || !canvas_shape(e, frame, &sf)) return;
+    if (ref && !canvas_shape(e, ref, &sr)) return;
+    const jxl_status st = jxl_canvas_blend_check(&d, &sc, &sf, ref ? &sr : NULL);
+    if (st != JXL_OK) rethrow(e, NULL, st);
+}
+
 /* ---- Modular: plan once, run, read channel by channel (ModularStream.applyTransforms, ModularStream.java:110-131) ---- */
 JNIEXPORT jintArray JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_modularDefaultSqueezeParams(JNIEnv* e, jclass k, jintArray widths,
         jintArray heights, jint nbMeta) {

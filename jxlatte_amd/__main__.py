@@ -38,6 +38,10 @@ def parser():
                          "(jxl_planes_png_samples / jxl_stage_png_samples); the same bytes as --device-color. With PFM output: "
                          "the PFM's samples in one kernel (jxl_planes_pfm_samples / jxl_stage_pfm_samples); the same bytes as "
                          "without it")
+    ap.add_argument("--device-canvas", action="store_true",
+                    help="keep the canvas and the reference frames of multi-frame images on the device and blend every frame in one "
+                         "launch (JXLDecoder device_canvas; jxl_canvas_blend); the same samples. The image's colour planes stay on "
+                         "the device where they are float: add --device-png to pack the samples there too")
     return ap
 
 
@@ -63,14 +67,15 @@ def main(argv=None):
     t0 = time.time()
     backend = DeviceBackend(a.device)
     dec = JXLDecoder(a.input, backend=backend, sparse_coeffs=a.sparse_coeffs, device_splines=a.device_splines,
-                     device_patches=a.device_patches, device_output=a.device_png)
+                     device_patches=a.device_patches, device_output=a.device_png, device_canvas=a.device_canvas)
     image = dec.decode()
     if image is None:
         print("jxlatte_amd: no frames", file=sys.stderr)
         return 1
     t1 = time.time()
     for i, st in enumerate(dec.stats):
-        print("    frame %d: %s %dx%d, %d groups" % (i, st["encoding"], st["width"], st["height"], st["groups"]), file=sys.stderr)
+        print("    frame %d: %s %dx%d, %d groups%s" % (i, st["encoding"], st["width"], st["height"], st["groups"],
+                                                       ", canvas %s" % st["canvas"] if a.device_canvas else ""), file=sys.stderr)
     print("Decoded %dx%d in %.3f s" % (image.getWidth(), image.getHeight(), t1 - t0), file=sys.stderr)
     if a.output and output_format(a) == "pfm":
         with open(a.output, "wb") as f:

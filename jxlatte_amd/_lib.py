@@ -131,6 +131,18 @@ SIGNATURES = {
     "jxl_stage_noise_add": (i32, [vp, pf3, pf3, i64, pf, f32, f32]),
     "jxl_stage_blend": (i32, [vp, i32, C.c_uint32, i32, vp, i32, i32, vp, i32, i32, vp, i32, i32, pf, pf,
                               C.POINTER(abi.BlendRect)]),
+    "jxl_canvas_create": (i32, [vp, i32, i32, i32, pi, pi]),
+    "jxl_canvas_destroy": (i32, [vp, i32]),
+    "jxl_canvas_describe": (i32, [vp, i32, C.POINTER(abi.CanvasShape)]),
+    "jxl_canvas_clone": (i32, [vp, i32, pi]),
+    "jxl_canvas_upload": (i32, [vp, i32, i32, vp, i32]),
+    "jxl_canvas_download": (i32, [vp, i32, i32, vp, pi]),
+    "jxl_canvas_from_planes": (i32, [vp, i32, pi, pi]),
+    "jxl_canvas_cast": (i32, [vp, i32, i32, i32]),
+    "jxl_canvas_blend": (i32, [vp, C.POINTER(abi.CanvasBlendDesc)]),
+    "jxl_canvas_to_planes": (i32, [vp, i32]),
+    "jxl_canvas_blend_check": (i32, [C.POINTER(abi.CanvasBlendDesc), C.POINTER(abi.CanvasShape), C.POINTER(abi.CanvasShape),
+                                     C.POINTER(abi.CanvasShape)]),
     "jxl_stage_orient": (i32, [vp, vp, i32, i32, i32, vp]),
     "jxl_stage_pack": (i32, [vp, pv3, C.POINTER(abi.PackParams), vp]),
     "jxl_stage_png_samples": (i32, [vp, pv3, vp, C.POINTER(abi.PngParams), vp]),

@@ -143,6 +143,27 @@ class BlendRect(C.Structure):
                 ("frame_y", C.c_int32), ("frame_x", C.c_int32), ("ref_y", C.c_int32), ("ref_x", C.c_int32)]
 
 
+CANVAS_MAX_PLANES = 16
+PLANE_FLOAT, PLANE_INT32 = 0, 1
+
+
+class CanvasBlendChan(C.Structure):
+    """struct jxl_canvas_blend_chan"""
+    _fields_ = [("frame_plane", C.c_int32), ("mode", C.c_int32), ("flags", C.c_uint32), ("frame_alpha", C.c_int32),
+                ("ref_alpha", C.c_int32)]
+
+
+class CanvasBlendDesc(C.Structure):
+    """struct jxl_canvas_blend_desc"""
+    _fields_ = [("canvas", C.c_int32), ("frame", C.c_int32), ("ref", C.c_int32), ("n_chan", C.c_int32), ("rect", BlendRect),
+                ("chan", CanvasBlendChan * CANVAS_MAX_PLANES)]
+
+
+class CanvasShape(C.Structure):
+    """struct jxl_canvas_shape"""
+    _fields_ = [("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("types", C.c_int32 * CANVAS_MAX_PLANES)]
+
+
 class PackParams(C.Structure):
     """struct jxl_pack_params"""
     _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("n_color", C.c_int32), ("has_alpha", C.c_int32),

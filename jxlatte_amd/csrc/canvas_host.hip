@@ -1,0 +1,264 @@
+// Device plane sets: the canvas and the reference frames of JXLCodestreamDecoder.decode (JXLCodestreamDecoder.java:640-657) kept
+// on the device, and blendFrame (:515-537) on them as one launch (k_canvas.hip). A set is ONE allocation, its planes a multiple
+// of 256 bytes apart, so every plane starts 16-byte aligned; a cast rewrites a plane in place (both kinds of sample are 4
+// bytes wide). The context (host.hip) lends its stream and its resident planes through jxl_internal.h's ctx_* functions.
+// Ordering: everything here is queued on the context's stream except the transfers to and from the host, which wait for the
+// stream first and are complete on return (the stream does not synchronise with the null stream).
+#include "jxl_internal.h"
+#include "canvas_check.h"
+#include "pfm_check.h"
+
+#include <new>
+
+namespace jxl {
+
+struct CanvasSet {
+    int32_t n = 0, h = 0, w = 0;
+    int32_t type[JXL_CANVAS_MAX_PLANES] = {};
+    size_t stride = 0;  // bytes between planes
+    char* base = nullptr;
+    uint32_t* plane(int i) const { return reinterpret_cast<uint32_t*>(base + stride * (size_t)i); }
+    size_t plane_bytes() const { return 4 * (size_t)h * (size_t)w; }
+};
+struct CanvasStore {
+    std::vector<CanvasSet*> sets;  // index = id; a destroyed set leaves a null its id is handed out again from
+};
+
+void canvas_store_free(CanvasStore* s) {
+    if (!s) return;
+    for (CanvasSet* k : s->sets)
+        if (k) {
+            (void)hipFree(k->base);
+            delete k;
+        }
+    delete s;
+}
+
+namespace {
+
+#define CV_HIP(c, expr)                                                                                                       \
+    do {                                                                                                                      \
+        hipError_t e_ = (expr);                                                                                               \
+        if (e_ != hipSuccess) return ctx_fail(c, e_ == hipErrorOutOfMemory ? JXL_ERR_OOM : JXL_ERR_DEVICE, hipGetErrorString(e_)); \
+    } while (0)
+
+CanvasSet* find(const CtxLink& l, int32_t id) {
+    CanvasStore* s = *l.canvas;
+    return (s && id >= 0 && (size_t)id < s->sets.size()) ? s->sets[(size_t)id] : nullptr;
+}
+
+// a new set of n planes (contents undefined), registered under *id
+jxl_status new_set(jxl_ctx* c, const CtxLink& l, int32_t n, int32_t h, int32_t w, const int32_t* types, CanvasSet** out, int32_t* id) {
+    if (n > JXL_CANVAS_MAX_PLANES) return ctx_fail(c, JXL_ERR_UNSUPPORTED, "canvas: more than 16 planes");
+    if (n < 1 || h < 1 || w < 1 || !types || !id) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: bad arguments");
+    for (int i = 0; i < n; i++)
+        if (types[i] != JXL_PLANE_FLOAT && types[i] != JXL_PLANE_INT32) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: plane type");
+    CanvasSet* k = nullptr;
+    try {
+        if (!*l.canvas) *l.canvas = new CanvasStore();
+        k = new CanvasSet();
+        std::vector<CanvasSet*>& v = (*l.canvas)->sets;
+        size_t slot = 0;
+        while (slot < v.size() && v[slot]) slot++;
+        if (slot == v.size()) v.push_back(nullptr);
+        k->n = n, k->h = h, k->w = w;
+        for (int i = 0; i < n; i++) k->type[i] = types[i];
+        k->stride = (k->plane_bytes() + 255) & ~(size_t)255;
+        if (hipMalloc(reinterpret_cast<void**>(&k->base), k->stride * (size_t)n) != hipSuccess) {
+            (void)hipGetLastError();
+            delete k;
+            return ctx_fail(c, JXL_ERR_OOM, "device allocation failed (plane set)");
+        }
+        v[slot] = k;
+        *id = (int32_t)slot;
+    } catch (const std::bad_alloc&) {
+        delete k;
+        return ctx_fail(c, JXL_ERR_OOM, "canvas: host allocation failed");
+    }
+    *out = k;
+    return JXL_OK;
+}
+
+void shape_of(const CanvasSet* k, jxl_canvas_shape* s) {
+    s->n = k->n, s->h = k->h, s->w = k->w;
+    for (int i = 0; i < JXL_CANVAS_MAX_PLANES; i++) s->types[i] = i < k->n ? k->type[i] : 0;
+}
+
+}  // namespace
+}  // namespace jxl
+
+using namespace jxl;
+
+extern "C" {
+
+jxl_status jxl_canvas_create(jxl_ctx* c, int32_t n, int32_t h, int32_t w, const int32_t* types, int32_t* id) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    CanvasSet* k;
+    if ((st = new_set(c, l, n, h, w, types, &k, id))) return st;
+    CV_HIP(c, hipMemsetAsync(k->base, 0, k->stride * (size_t)k->n, l.stream));
+    return JXL_OK;
+}
+
+jxl_status jxl_canvas_destroy(jxl_ctx* c, int32_t id) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    CanvasSet* k = find(l, id);
+    if (!k) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+    CV_HIP(c, hipStreamSynchronize(l.stream));  // a queued launch may still use the planes
+    (void)hipFree(k->base);
+    delete k;
+    (*l.canvas)->sets[(size_t)id] = nullptr;
+    return JXL_OK;
+}
+
+jxl_status jxl_canvas_describe(jxl_ctx* c, int32_t id, jxl_canvas_shape* out) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    const CanvasSet* k = find(l, id);
+    if (!k || !out) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+    shape_of(k, out);
+    return JXL_OK;
+}
+
+jxl_status jxl_canvas_clone(jxl_ctx* c, int32_t id, int32_t* new_id) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    const CanvasSet* k = find(l, id);
+    if (!k || !new_id) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+    CanvasSet* q;
+    if ((st = new_set(c, l, k->n, k->h, k->w, k->type, &q, new_id))) return st;
+    CV_HIP(c, hipMemcpyAsync(q->base, k->base, k->stride * (size_t)k->n, hipMemcpyDeviceToDevice, l.stream));
+    return JXL_OK;
+}
+
+jxl_status jxl_canvas_upload(jxl_ctx* c, int32_t id, int32_t plane, const void* src, int32_t type) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    CanvasSet* k = find(l, id);
+    if (!k) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+    if (plane < 0 || plane >= k->n || !src || (type != JXL_PLANE_FLOAT && type != JXL_PLANE_INT32))
+        return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas upload: bad arguments");
+    CV_HIP(c, hipStreamSynchronize(l.stream));
+    CV_HIP(c, hipMemcpy(k->plane(plane), src, k->plane_bytes(), hipMemcpyHostToDevice));
+    k->type[plane] = type;
+    return JXL_OK;
+}
+
+jxl_status jxl_canvas_download(jxl_ctx* c, int32_t id, int32_t plane, void* dst, int32_t* type) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    const CanvasSet* k = find(l, id);
+    if (!k) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+    if (plane < 0 || plane >= k->n || !dst) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas download: bad arguments");
+    CV_HIP(c, hipStreamSynchronize(l.stream));
+    CV_HIP(c, hipGetLastError());
+    CV_HIP(c, hipMemcpy(dst, k->plane(plane), k->plane_bytes(), hipMemcpyDeviceToHost));
+    if (type) *type = k->type[plane];
+    return JXL_OK;
+}
+
+jxl_status jxl_canvas_from_planes(jxl_ctx* c, int32_t n_extra, const int32_t* extra_types, int32_t* id) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    int h, w;
+    float* p[3];
+    if ((st = ctx_planes_get(c, &h, &w, p))) return st;
+    if (n_extra > JXL_CANVAS_MAX_PLANES - 3) return ctx_fail(c, JXL_ERR_UNSUPPORTED, "canvas: more than 16 planes");
+    if (n_extra < 0 || (n_extra > 0 && !extra_types)) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: bad arguments");
+    int32_t types[JXL_CANVAS_MAX_PLANES] = {JXL_PLANE_FLOAT, JXL_PLANE_FLOAT, JXL_PLANE_FLOAT};
+    for (int i = 0; i < n_extra; i++) types[3 + i] = extra_types[i];
+    CanvasSet* k;
+    if ((st = new_set(c, l, 3 + n_extra, h, w, types, &k, id))) return st;
+    for (int i = 0; i < 3; i++) CV_HIP(c, hipMemcpyAsync(k->plane(i), p[i], k->plane_bytes(), hipMemcpyDeviceToDevice, l.stream));
+    if (n_extra > 0) CV_HIP(c, hipMemsetAsync(k->plane(3), 0, k->stride * (size_t)n_extra, l.stream));
+    return JXL_OK;
+}
+
+jxl_status jxl_canvas_cast(jxl_ctx* c, int32_t id, int32_t plane, int32_t depth) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    CanvasSet* k = find(l, id);
+    if (!k) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+    if (plane < 0 || plane >= k->n) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas cast: bad plane");
+    if (k->type[plane] == JXL_PLANE_FLOAT) return JXL_OK;  // ImageBuffer.java:100-101
+    const int32_t max = pfm_depth_max(depth);
+    if (max < 1) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "invalid Max Value");  // ImageBuffer.java:115-116
+    // castToFloat0 (ImageBuffer.java:112-127) element by element, in place: the kernel of jxl_stage_modular_to_float
+    launch_modular_to_float(reinterpret_cast<const int32_t*>(k->plane(plane)), nullptr, (int64_t)k->h * k->w, 1.0f / (float)max,
+                            reinterpret_cast<float*>(k->plane(plane)), l.stream);
+    CV_HIP(c, hipGetLastError());
+    k->type[plane] = JXL_PLANE_FLOAT;
+    return JXL_OK;
+}
+
+jxl_status jxl_canvas_blend_check(const jxl_canvas_blend_desc* d, const jxl_canvas_shape* canvas, const jxl_canvas_shape* frame,
+                                  const jxl_canvas_shape* ref) {
+    const char* why = "";
+    const jxl_status st = canvas_blend_check(d, canvas, frame, ref, nullptr, &why);
+    return st ? ctx_fail(nullptr, st, why) : JXL_OK;
+}
+
+jxl_status jxl_canvas_blend(jxl_ctx* c, const jxl_canvas_blend_desc* d) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    if (!d) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas blend: null argument");
+    const CanvasSet *cv = find(l, d->canvas), *fr = find(l, d->frame), *rf = d->ref >= 0 ? find(l, d->ref) : nullptr;
+    if (!cv || !fr || (d->ref >= 0 && !rf)) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+    jxl_canvas_shape sc, sf, sr;
+    shape_of(cv, &sc);
+    shape_of(fr, &sf);
+    if (rf) shape_of(rf, &sr);
+    CanvasChanOp ops[JXL_CANVAS_MAX_PLANES];
+    const char* why = "";
+    if ((st = canvas_blend_check(d, &sc, &sf, rf ? &sr : nullptr, ops, &why))) return ctx_fail(c, st, why);
+    const jxl_blend_rect& r = d->rect;
+    if (r.h == 0 || r.w == 0) return JXL_OK;
+    CanvasArgs a{};
+    a.n = cv->n, a.h = r.h, a.w = r.w;
+    a.cw = cv->w, a.fw = fr->w, a.rw = rf ? rf->w : 0;
+    const int64_t c_off = (int64_t)r.canvas_y * cv->w + r.canvas_x, f_off = (int64_t)r.frame_y * fr->w + r.frame_x;
+    const int64_t r_off = rf ? (int64_t)r.ref_y * rf->w + r.ref_x : 0, rf_off = rf ? (int64_t)r.frame_y * rf->w + r.frame_x : 0;
+    a.c_align = (int32_t)(c_off & 3);
+    for (int ch = 0; ch < cv->n; ch++) {
+        const jxl_canvas_blend_chan& k = d->chan[ch];
+        const CanvasChanOp& o = ops[ch];
+        CanvasChan& q = a.ch[ch];
+        q.canvas = cv->plane(ch) + c_off;
+        q.frame = o.frame ? fr->plane(k.frame_plane) + f_off : nullptr;
+        q.ref = o.ref ? rf->plane(ch) + (o.frame ? r_off : rf_off) : nullptr;  // (blendMulAdd's alpha copy reads at frameOffset, :390)
+        q.frame_alpha = o.frame_alpha ? fr->plane(k.frame_alpha) + f_off : nullptr;
+        q.ref_alpha = o.ref_alpha ? rf->plane(k.ref_alpha) + r_off : nullptr;
+        q.op = o.op;
+        q.flags = (int32_t)k.flags;
+    }
+    launch_canvas_blend(a, l.stream);
+    CV_HIP(c, hipGetLastError());
+    return JXL_OK;
+}
+
+jxl_status jxl_canvas_to_planes(jxl_ctx* c, int32_t id) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    const CanvasSet* k = find(l, id);
+    if (!k) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+    if (k->n < 3 || k->type[0] != JXL_PLANE_FLOAT || k->type[1] != JXL_PLANE_FLOAT || k->type[2] != JXL_PLANE_FLOAT)
+        return ctx_fail(c, JXL_ERR_STATE, "canvas: the first three planes are not float planes");
+    CV_HIP(c, hipStreamSynchronize(l.stream));  // (the resident planes may be reallocated below)
+    float* p[3];
+    if ((st = ctx_planes_set(c, k->h, k->w, p))) return st;
+    for (int i = 0; i < 3; i++) CV_HIP(c, hipMemcpyAsync(p[i], k->plane(i), k->plane_bytes(), hipMemcpyDeviceToDevice, l.stream));
+    return JXL_OK;
+}
+
+}  // extern "C"

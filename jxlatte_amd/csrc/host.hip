@@ -160,6 +160,8 @@ struct jxl_ctx {
     // resident colour planes between decodeFrame and the colour transform (jxl_planes_*): dense [rp_h][rp_w] floats
     DevBuf rp[3], rp_tmp[3], rp_noise[3];
     int rp_h = 0, rp_w = 0;
+    // device plane sets: the canvas and the reference frames (jxl_canvas_*, canvas_host.hip owns the type)
+    jxl::CanvasStore* canvas = nullptr;
     // spline tables (jxl_stage_splines / jxl_planes_splines): arc records, non-empty tiles, CSR ranges and arc lists laid out
     // back to back in ONE page-locked buffer and moved by ONE transfer into spl. A buffer of its own, not h_tab: that one holds
     // the open frame's grids, which a re-run of the frame uploads again.
@@ -1476,6 +1478,8 @@ void jxl_ctx_destroy(jxl_ctx* c) {
         else free(c->h_tab);
     }
     for (int i = 0; i < 3; i++) { c->rp[i].release(); c->rp_tmp[i].release(); c->rp_noise[i].release(); }
+    canvas_store_free(c->canvas);
+    c->canvas = nullptr;
     c->spl.release();
     c->pat.release();
     if (c->spl_ev) (void)hipEventDestroy(c->spl_ev);
@@ -3002,6 +3006,36 @@ jxl_status jxl_planes_upload(jxl_ctx* c, const float* const in[3], int32_t heigh
     c->rp_w = width;
     return JXL_OK;
 }
+
+// ---- what canvas_host.hip needs of the context (jxl_internal.h) ----
+extern "C++" {
+namespace jxl {
+jxl_status ctx_link(jxl_ctx* c, CtxLink* out) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    out->stream = c->stream;
+    out->canvas = &c->canvas;
+    return JXL_OK;
+}
+jxl_status ctx_fail(jxl_ctx* c, jxl_status st, const char* msg) { return fail(c, st, "%s", msg); }
+jxl_status ctx_planes_get(jxl_ctx* c, int* h, int* w, float* p[3]) {
+    if (c->rp_h <= 0) return fail(c, JXL_ERR_STATE, "no resident planes");
+    *h = c->rp_h;
+    *w = c->rp_w;
+    for (int i = 0; i < 3; i++) p[i] = c->rp[i].as<float>();
+    return JXL_OK;
+}
+jxl_status ctx_planes_set(jxl_ctx* c, int h, int w, float* p[3]) {
+    for (int i = 0; i < 3; i++) {
+        if (!c->rp[i].ensure(sizeof(float) * (size_t)h * w)) return fail(c, JXL_ERR_OOM, "device allocation failed (resident planes)");
+        p[i] = c->rp[i].as<float>();
+    }
+    c->rp_h = h;
+    c->rp_w = w;
+    return JXL_OK;
+}
+}  // namespace jxl
+}  // extern "C++"
 
 // ---- splines: Frame.renderSplines as one launch over the binned arc table (spline_host.hip, k_spline.hip) ----
 namespace {

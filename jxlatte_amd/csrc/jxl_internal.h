@@ -9,6 +9,7 @@
 #include "../../include/jxlatte_amd.h"
 #include "../../include/jxl_transform_types.h"
 #include "plane_tiled.h"
+#include "blend_ops.h"
 
 namespace jxl {
 
@@ -431,11 +432,7 @@ void launch_noise_init(int h, int w, int group_dim, uint64_t seed0, int colors, 
                        hipStream_t s);
 void launch_noise_add(float* const planes[3], const float* const noise[3], int64_t n, const float lut[8], float bcx, float bcb,
                       hipStream_t s);
-// the inner blend functions (k_blend's switch); blend_op maps (mode, flags, is_int) to one; -1 illegal mode, -2 int samples on a
-// float-only function
-enum BlendOp { OP_COPY_FRAME, OP_COPY_REF, OP_ADD_I, OP_ADD_F, OP_MULT, OP_BLEND, OP_MULADD };
-int blend_op(int mode, unsigned flags, int is_int);
-bool blend_needs(int op, bool* frame, bool* ref, bool* frame_alpha, bool* ref_alpha, bool is_alpha);
+// the inner blend functions (k_blend's switch), blend_op and blend_needs: blend_ops.h
 void launch_blend(int op, unsigned flags, void* canvas, int cw, const void* frame, int fw, const void* ref, int rw,
                   const float* frame_alpha, const float* ref_alpha, const jxl_blend_rect& r, hipStream_t s);
 void launch_orient(const void* in, int h, int w, int orientation, void* out, hipStream_t s);
@@ -485,6 +482,34 @@ jxl_status patch_compile(const jxl_patch_desc* d, int32_t height, int32_t width,
 // widths [4]
 void launch_patches(const int64_t* planes, int n_chan, int w, const PatchRec* rec, const PatchOp* ops, const int32_t* tile,
                     const int32_t* start, const int32_t* list, int n_tiles, int tiles_x, hipStream_t s);
+
+// ---- device plane sets (canvas_host.hip: the sets and the jxl_canvas_* entries; k_canvas.hip: the blend kernel) ----
+// one canvas channel as the kernel reads it: every pointer already stands on the rectangle's origin in its plane (patchStart,
+// frameOffset, refOffset -- frameOffset for the reference plane of OP_COPY_REF); a plane the function does not read is null
+struct CanvasChan {
+    uint32_t* canvas;
+    const uint32_t *frame, *ref, *frame_alpha, *ref_alpha;
+    int32_t op, flags;  // BlendOp, JXL_BLEND_FLAG_*
+};
+struct CanvasArgs {
+    int32_t n, h, w;      // channels, blendSize
+    int32_t cw, fw, rw;   // row strides (samples) of the canvas, frame and reference planes
+    int32_t c_align;      // sample index of the rectangle's origin in its canvas plane, modulo 4 (plane bases are 16-byte aligned)
+    int32_t reserved;
+    CanvasChan ch[JXL_CANVAS_MAX_PLANES];
+};
+void launch_canvas_blend(const CanvasArgs& a, hipStream_t s);
+// The context is host.hip's: canvas_host.hip reaches what it needs of it through these. CanvasStore: a context's sets.
+struct CanvasStore;
+void canvas_store_free(CanvasStore* s);  // jxl_ctx_destroy, after the stream has drained
+struct CtxLink {
+    hipStream_t stream;
+    CanvasStore** canvas;  // the context's slot for its store (null until the first set)
+};
+jxl_status ctx_link(jxl_ctx* c, CtxLink* out);                      // hipSetDevice + the fields above
+jxl_status ctx_fail(jxl_ctx* c, jxl_status st, const char* msg);    // records the message (c may be null) and returns st
+jxl_status ctx_planes_get(jxl_ctx* c, int* h, int* w, float* p[3]);  // the resident planes, or JXL_ERR_STATE
+jxl_status ctx_planes_set(jxl_ctx* c, int h, int w, float* p[3]);    // resident planes of h x w to fill (contents undefined)
 
 void launch_idct2d_single(const float* src, float* dst, int h, int w, int transposed, const float* lut, hipStream_t s);
 void launch_fdct2d_single(const float* src, float* dst, int h, int w, const float* lut, hipStream_t s);

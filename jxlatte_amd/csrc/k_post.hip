@@ -338,27 +338,6 @@ void launch_noise_add(float* const planes[3], const float* const noise[3], int64
                        noise[2], n, l, bcx, bcb);
 }
 
-int blend_op(int mode, unsigned flags, int is_int) {
-    const bool is_alpha = flags & JXL_BLEND_FLAG_IS_ALPHA, has_extra = flags & JXL_BLEND_FLAG_HAS_EXTRA;
-    int op;
-    switch (mode) {
-        case JXL_BLEND_REPLACE: op = OP_COPY_FRAME; break;
-        case JXL_BLEND_ADD: op = is_int ? OP_ADD_I : OP_ADD_F; break;
-        case JXL_BLEND_MULT: op = OP_MULT; break;
-        case JXL_BLEND_BLEND: op = has_extra ? OP_BLEND : (is_int ? OP_ADD_I : OP_ADD_F); break;  // :346-349
-        case JXL_BLEND_MULADD: op = !has_extra ? (is_int ? OP_ADD_I : OP_ADD_F) : is_alpha ? OP_COPY_REF : OP_MULADD; break;
-        default: return -1;  // "Illegal blend mode"
-    }
-    if (is_int && op != OP_COPY_FRAME && op != OP_COPY_REF && op != OP_ADD_I) return -2;
-    return op;
-}
-bool blend_needs(int op, bool* frame, bool* ref, bool* frame_alpha, bool* ref_alpha, bool is_alpha) {
-    *frame = op != OP_COPY_REF;
-    *ref = op != OP_COPY_FRAME;
-    *frame_alpha = (op == OP_BLEND && !is_alpha) || op == OP_MULADD;
-    *ref_alpha = op == OP_BLEND && !is_alpha;
-    return true;
-}
 void launch_blend(int op, unsigned flags, void* canvas, int cw, const void* frame, int fw, const void* ref, int rw,
                   const float* frame_alpha, const float* ref_alpha, const jxl_blend_rect& r, hipStream_t s) {
     BlendArgs a{canvas, frame, ref, frame_alpha, ref_alpha, cw, fw, rw, r, op, (flags & JXL_BLEND_FLAG_IS_ALPHA) != 0,

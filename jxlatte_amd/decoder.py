@@ -481,6 +481,152 @@ def patch_type_plan(info, patches, frame_buffers, reference, frame_colors):
     return plan
 
 
+class BlendPlan:
+    """what one blendFrame does to the TYPES of the planes, and the one launch that replays it (blend_type_plan)"""
+
+    def __init__(self):
+        self.verdict = "device"   # or "land: <reason>"
+        self.rect = None          # (h, w, canvas_y, canvas_x, frame_y, frame_x, ref_y, ref_x); None: the rectangle is empty
+        self.casts = []           # whole-plane castToFloat calls to make before the launch: ("c" | "f" | "r", plane, depth), in order
+        self.chans = []           # per canvas channel: (frame_plane, mode, flags, frame_alpha, ref_alpha) of jxl_canvas_blend_chan
+        self.source = None        # the reference slot the blend functions read, or None: every channel is a copy
+        self.aliased = False      # that slot IS the canvas
+        self.ref_zero = False     # that slot is empty: the functions read fresh zero planes (ref_types tells their types)
+        self.canvas_types = self.frame_types = self.ref_types = None  # after the call (ref_types: None without a source)
+
+
+def blend_type_plan(info, fr, canvas_types, frame_types, ref_types):
+    """JXLCodestreamDecoder.blendFrame + blendBuffers (:415-537) replayed on the plane TYPES alone, channel by channel in canvas
+    order: the casts of :433-436 and :446-465 become whole-plane casts in front of ONE launch, the rest the per-channel
+    descriptor of jxl_canvas_blend. canvas_types / frame_types: one numpy dtype per plane. ref_types: per reference slot
+    None (empty), the string "canvas" (the slot is the canvas object itself) or a list of dtypes (None: an absent plane).
+    The verdict is "land: <reason>" where one launch behind hoisted casts would not give the reference's samples:
+      - more than 16 planes; one-colour images; a frame whose colour count is not the image's;
+      - channels that blend from different reference slots (the descriptor names one reference set), a slot with another
+        plane count or an absent plane;
+      - blendMulAdd's copy of the alpha channel (:390) out of a reference that is the canvas, at another offset;
+      - a plane that one channel's function reads or writes as int32 and a LATER channel of the same call casts to float (the
+        hoisted cast would turn the earlier int sum into a float sum).
+    Raises nothing and touches no sample."""
+    f32, i32 = np.dtype(np.float32), np.dtype(np.int32)
+    plan = BlendPlan()
+
+    def land(reason):
+        plan.verdict = "land: " + reason
+        return plan
+
+    colors = 1 if info.colour_space == CE_GRAY else 3
+    n = len(canvas_types)
+    if n > abi.CANVAS_MAX_PLANES or len(frame_types) > abi.CANVAS_MAX_PLANES:
+        return land("more than 16 planes")
+    if colors != 3:
+        return land("one-colour image")
+    frame_colors = len(frame_types) - info.num_extra
+    if frame_colors != colors or n != colors + info.num_extra:
+        return land("the frame's colour count is not the image's")
+    ih, iw = info.height, info.width
+    py, px = min(max(fr.y0, 0), ih), min(max(fr.x0, 0), iw)       # Point.inBounds
+    fy, fx = py - fr.y0, px - fr.x0
+    ly, lx = fr.y0 + fr.height * fr.upsampling, fr.x0 + fr.width * fr.upsampling  # bounds after Frame.upsample()
+    bh, bw = min(ly, ih) - py, min(lx, iw) - px
+    ct, ft = [np.dtype(t) for t in canvas_types], [np.dtype(t) for t in frame_types]
+    plan.canvas_types, plan.frame_types = ct, ft
+    if bh <= 0 or bw <= 0:
+        return plan
+    plan.rect = (bh, bw, py, px, fy, fx, py, px)
+    has_extra = info.num_extra > 0
+    infos = []
+    for c in range(n):
+        if c >= colors:
+            e = c - colors
+            infos.append((fr.ec_blend_mode[e], fr.ec_blend_alpha[e], bool(fr.ec_blend_clamp[e]), fr.ec_blend_source[e]))
+        else:
+            infos.append((fr.blend_mode, fr.blend_alpha, bool(fr.blend_clamp), fr.blend_source))
+    is_copy = [m == abi.BLEND_REPLACE or (ref_types[src] is None and m == abi.BLEND_ADD) for m, _, _, src in infos]  # :437
+    sources = sorted({src for (m, _, _, src), cp in zip(infos, is_copy) if not cp})
+    if len(sources) > 1:
+        return land("channels blend from different reference slots")
+    rt = None
+    if sources:
+        plan.source = sources[0]
+        ref = ref_types[plan.source]
+        if ref is None:
+            plan.ref_zero, rt = True, [None] * n
+        elif isinstance(ref, str):
+            plan.aliased, rt = True, ct  # one object: a cast of either is a cast of both
+        else:
+            if len(ref) != n:
+                return land("the reference slot has another plane count")
+            rt = [None if t is None else np.dtype(t) for t in ref]
+    plan.ref_types = rt
+    int_used = set()  # (set, plane) an earlier channel of this call has read or written as int32
+
+    def key(which):
+        return "c" if which == "r" and plan.aliased else which
+
+    def cast(which, plane, depth):
+        types = {"c": ct, "f": ft, "r": rt}[which]
+        if types[plane] == f32:
+            return True
+        if (key(which), plane) in int_used:
+            return False
+        types[plane] = f32
+        if not (which == "r" and plan.ref_zero):  # (fresh zero planes are made with the type they end with)
+            plan.casts.append((key(which), plane, depth))
+        return True
+
+    hazard = "a plane is read as int32 by one channel and cast to float by a later one"
+    for idx, ((mode, alpha, clamp, _), cp) in enumerate(zip(infos, is_copy)):
+        ex = idx - colors
+        is_alpha = ex >= 0 and info.ec_type[ex] == 0
+        premult = has_extra and bool(info.ec_alpha_associated[alpha])
+        depth = info.bits_per_sample if idx < colors else info.ec_bits[ex]
+        flags = (abi.BLEND_FLAG_IS_ALPHA if is_alpha else 0) | (abi.BLEND_FLAG_HAS_EXTRA if has_extra else 0) | \
+            (abi.BLEND_FLAG_CLAMP if clamp else 0) | (abi.BLEND_FLAG_PREMULT if premult else 0)
+        a_ref, a_frame = (colors + alpha, frame_colors + alpha) if has_extra else (0, 0)
+        if ct[idx] != ft[idx]:  # :433-436
+            if not (cast("f", idx, depth) and cast("c", idx, depth)):
+                return land(hazard)
+        if cp:
+            if ft[idx] == i32:
+                int_used.update({("f", idx), ("c", idx)})
+            plan.chans.append((idx, abi.BLEND_REPLACE, flags, a_frame, a_ref))
+            continue
+        if rt[idx] is None:  # :441-442
+            if not plan.ref_zero:
+                return land("the reference slot lacks a plane")
+            rt[idx] = ct[idx]
+        if has_extra and mode in (abi.BLEND_BLEND, abi.BLEND_MULADD):  # :446-456
+            a_depth = info.ec_bits[alpha]
+            if mode == abi.BLEND_BLEND:
+                if rt[a_ref] is None:
+                    if not plan.ref_zero:
+                        return land("the reference slot lacks a plane")
+                    rt[a_ref] = f32
+                if not cast("r", a_ref, a_depth):
+                    return land(hazard)
+            if not cast("f", a_frame, a_depth):
+                return land(hazard)
+        should_cast = mode == abi.BLEND_MULT or (mode == abi.BLEND_BLEND and has_extra) or \
+            (mode == abi.BLEND_MULADD and has_extra and not is_alpha)
+        if should_cast or rt[idx] != ft[idx]:  # :457-465
+            if not (cast("f", idx, depth) and cast("c", idx, depth) and cast("r", idx, depth)):
+                return land(hazard)
+        if plan.aliased and mode == abi.BLEND_MULADD and has_extra and is_alpha and (fy, fx) != (py, px):
+            # :390 copies ref at frameOffset: rows of the canvas onto other rows of itself, which no lane-owns-its-pixel launch replays
+            return land("the alpha channel is copied from another place of the canvas itself")
+        if ct[idx] != ft[idx] or rt[idx] != ft[idx]:
+            # (an alpha channel that names itself: :455 casts the frame plane behind the comparison of :433 -- the reference's
+            # copy then throws; the calls without the switch keep their own answer)
+            return land("the planes of a channel differ in type")
+        if ft[idx] == i32:  # the copy of :390 or the int sum of :287-301 (a float function on int planes cannot be reached)
+            int_used.update({("f", idx), ("c", idx), (key("r"), idx)})
+        plan.chans.append((idx, mode, flags, a_frame, a_ref))
+    if plan.ref_zero:
+        plan.ref_types = [f32 if t is None else t for t in rt]
+    return plan
+
+
 class DeviceBackend:
     """the product backend: HIP kernels through the C-ABI (jxlatte_amd._lib / host). No CPU fallback."""
 
@@ -823,7 +969,8 @@ def _tt_dims():
 
 
 class JXLDecoder:
-    def __init__(self, source, backend=None, sparse_coeffs=False, device_splines=False, device_patches=False, device_output=False):
+    def __init__(self, source, backend=None, sparse_coeffs=False, device_splines=False, device_patches=False, device_output=False,
+                 device_canvas=False):
         """sparse_coeffs: hand the HF coefficients to the backend as lists of non-zero entries (jxf_get_coeffs_sparse ->
         jxl_vardct_put_group_sparse), not as dense planes; same pixels.
         device_splines: Frame.renderSplines runs in the backend (jxl_planes_splines on the resident planes, jxl_stage_splines
@@ -839,8 +986,19 @@ class JXLDecoder:
         them (JXLImage.resident; getBuffer() downloads on first use, the same bits). A VarDCT frame without a stage after
         decodeFrame qualifies too. The extra channels are blended and oriented on the host as ever; the orientation of the
         colour planes is ResidentPlanes.orient. Every other frame takes the usual path. stats[-1]["output"] tells which:
-        "device" or "host"."""
+        "device" or "host".
+        device_canvas: the canvas and the reference frames saved after the colour transform live on the device as plane sets
+        (host.DeviceCanvas) and blendFrame is one launch per frame (jxl_canvas_blend) behind the whole-plane casts of
+        blend_type_plan; a frame's resident colour planes reach the blend without touching the host. decode() ends with the
+        canvas' colour planes as the image's resident planes when they are float (else it downloads them); getBuffer() gives
+        the default decoder's arrays either way. Where blend_type_plan says "land", and before a frame with patches, every set
+        comes down into host lists (aliases stay aliases) and the image goes on as without the switch. stats[-1]["canvas"]:
+        "device", "host" (the switch is off) or "landed: <reason>". device_output's single-frame path takes precedence. A backend
+        without a context is an error."""
         self.device_output = bool(device_output)
+        self.device_canvas = bool(device_canvas)
+        self._landed = None   # why the canvas is (back) on the host for the rest of this image
+        self._dead_sets = []  # plane sets of the last blend, released once the next call has no use for them
         self.sparse_coeffs = bool(sparse_coeffs)
         self.device_splines = bool(device_splines)
         self.device_patches = bool(device_patches)
@@ -862,6 +1020,22 @@ class JXLDecoder:
         self.invisibleFrames = 0
         self.frames_decoded = 0
         self.stats = []  # per frame: dict(encoding, size, groups, types histogram...) for reporting
+
+    def close(self):
+        """release the plane sets of device_canvas (the context frees what is left of them when it is destroyed)"""
+        self._release_dead()
+        sets = {id(s_): s_ for s_ in [self.canvas] + list(self.reference) if self._is_set(s_)}
+        for s_ in sets.values():
+            s_.release()
+        if self._is_set(self.canvas):
+            self.canvas = None
+        self.reference = [None if self._is_set(r) else r for r in self.reference]
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
     @staticmethod
     def _map(e):
@@ -1072,6 +1246,82 @@ class JXLDecoder:
             else:
                 val = src
             buffers[c_out][:h, :w] = val
+
+    # -- the canvas on the device (device_canvas) -----------------------------------------------------------------
+    def _is_set(self, obj):
+        return hasattr(obj, "canvasShape")  # host.DeviceCanvas (the decoder imports no binding at module level)
+
+    def _release_dead(self):
+        for s_ in self._dead_sets:
+            s_.release()
+        self._dead_sets = []
+
+    def _land(self, reason):
+        """every plane set comes down: self.canvas and each self.reference[k] that is a set become host lists -- ONE list per
+        set, so the aliases stay aliases -- and the sets are released. The canvas is not taken up again within this image."""
+        if self._landed is None:
+            self._landed = reason
+        self._release_dead()
+        done = {}
+        def host_list(s_):
+            if id(s_) not in done:
+                done[id(s_)] = ([s_.download(i) for i in range(len(s_))], s_)
+            return done[id(s_)][0]
+        if self._is_set(self.canvas):
+            self.canvas = host_list(self.canvas)
+        for k in range(4):
+            if self._is_set(self.reference[k]):
+                self.reference[k] = host_list(self.reference[k])
+        for _, s_ in done.values():
+            s_.release()
+
+    def _blend_frame_device(self, fr, buffers, rp):
+        """blendFrame on the plane sets: the type plan, the frame's planes into a set (its resident colour planes without the
+        host), the hoisted casts, one launch. Returns None, or the reason to land (nothing has been touched then)."""
+        host, ctx = self.backend.host, self.backend.ctx
+        info, cv = self.info, self.canvas
+        f32 = np.dtype(np.float32)
+        ftypes = [f32] * 3 + [b.dtype for b in buffers[3:]] if rp is not None else [b.dtype for b in buffers]
+        refs = self.reference
+        ref_types = [None if r is None else "canvas" if r is cv else r.dtypes if self._is_set(r) else
+                     [None if b is None else b.dtype for b in r] for r in refs]
+        plan = blend_type_plan(info, fr, cv.dtypes, ftypes, ref_types)
+        if plan.verdict != "device":
+            return plan.verdict[len("land: "):]
+        if plan.rect is None:
+            return None
+        shape = rp.shape if rp is not None else buffers[0].shape
+        if any(tuple(b.shape) != tuple(shape) for b in (buffers[3:] if rp is not None else buffers)):
+            return "the frame's planes differ in size"
+        self._release_dead()
+        if rp is not None:
+            fset = host.DeviceCanvas.fromPlanes(ctx, [b.dtype for b in buffers[3:]])
+            for i, b in enumerate(buffers[3:]):
+                fset.upload(3 + i, b)
+        else:
+            fset = host.DeviceCanvas.fromArrays(ctx, buffers)
+        self._dead_sets.append(fset)
+        ref = None
+        if plan.source is not None:
+            slot = refs[plan.source]
+            if plan.ref_zero:
+                ref = host.DeviceCanvas.create(ctx, plan.ref_types, info.height, info.width)
+                self._dead_sets.append(ref)
+            elif plan.aliased:
+                ref = cv
+            elif self._is_set(slot):
+                ref = slot
+            else:  # a host list (saved before the colour transform): its casts persist in the list, as today; then it goes up
+                for which, plane, depth in plan.casts:
+                    if which == "r":
+                        slot[plane] = self._to_float(slot[plane], depth)
+                ref = host.DeviceCanvas.fromArrays(ctx, slot)
+                self._dead_sets.append(ref)
+        for which, plane, depth in plan.casts:
+            target = {"c": cv, "f": fset, "r": ref}[which]
+            target.cast(plane, depth)  # (nothing happens to the float planes of an uploaded list)
+        host.canvas_blend(cv, fset, ref, plan.rect, plan.chans)
+        return None
 
     def _blend_frame(self, fr, frame_buffers, colors_frame, first=0):
         """JXLCodestreamDecoder.blendFrame + blendBuffers (:424-537). first: the first canvas channel to blend (the colour
@@ -1294,6 +1544,7 @@ class JXLDecoder:
             self.frames_decoded += 1
             self.stats.append(dict(encoding="vardct" if fr.encoding == VARDCT else "modular", width=fr.width, height=fr.height,
                                    groups=fr.num_groups, passes=fr.num_passes))
+            bus0 = tuple(getattr(getattr(be, "ctx", None), "blend_bus", (0, 0)))  # (host._bus: what the blend path moves)
             if fr.flags & FLAG_USE_LF_FRAME and self.lfBuffer[fr.lf_level] is None:
                 raise InvalidBitstreamException("LF Level too large")  # JXLCodestreamDecoder.java:613-614
             colors = self._colors(fr)
@@ -1312,16 +1563,27 @@ class JXLDecoder:
             resident = getattr(be, "resident", False) and colors == 3  # row f4: the stages after decodeFrame chained on the device
             # device_output: this frame is the image (the conditions of __init__'s docstring that the header settles)
             direct = getattr(self, "device_output", False) and resident and colors_img == 3 and fr.type == REGULAR_FRAME and \
-                bool(fr.is_last) and fr.lf_level == 0 and self.canvas[0] is None and fr.y0 == 0 and fr.x0 == 0 and \
+                bool(fr.is_last) and fr.lf_level == 0 and not self._is_set(self.canvas) and self.canvas[0] is None and fr.y0 == 0 and fr.x0 == 0 and \
                 fr.width * fr.upsampling == info.width and fr.height * fr.upsampling == info.height and fr.blend_mode == abi.BLEND_REPLACE
             self.stats[-1]["output"] = "host"
+            # device_canvas: the canvas lives in a plane set from the first frame that reaches it until something lands it
+            dcan = getattr(self, "device_canvas", False) and not direct
+            if dcan and not hasattr(be, "ctx"):
+                raise RuntimeError("device_canvas needs a backend with a device context")
+            if dcan and self._landed is None and colors_img != 3:
+                self._landed = "one-colour image"
+            if dcan and fr.num_patches and fr.type != LF_FRAME:  # blendBuffers casts a patch's reference in place: no set stays up
+                self._land("a frame with patches")
+            dcan = dcan and self._landed is None
+            self.stats[-1]["canvas"] = "host" if not getattr(self, "device_canvas", False) or direct else \
+                "device" if self._landed is None else "landed: " + self._landed
             if fr.encoding == VARDCT:
                 # an LF frame's buffers are read back as XYB LF coefficients (LFCoefficients.java:44-57) and are stored
                 # BEFORE performColorTransforms (JXLCodestreamDecoder.java:615-617): never fuse the inverse XYB into them
                 fuse_xyb = bool(info.xyb_encoded) and simple and fr.lf_level == 0 and fr.type != LF_FRAME
                 # frames with stages between decodeFrame and the colour transform keep their colour planes on the device
                 # through those stages (row f4); LF frames / lfBuffer consumers need the padded planes on the host
-                if (not simple or direct) and resident and fr.lf_level == 0 and fr.type != LF_FRAME:
+                if (not simple or direct or dcan) and resident and fr.lf_level == 0 and fr.type != LF_FRAME:
                     rp = self._vardct_frame(fr, fuse_xyb, keep=(fr.height, fr.width))  # (fuse_xyb: simple frames only)
                     xyb_done = fuse_xyb
                     for c in range(3):
@@ -1382,7 +1644,7 @@ class JXLDecoder:
                     buffers[c] = be.upsample(self._to_float(buffers[c], depth), k, wts)
             noise = None
             if resident:
-                rp = self._chained_tail(fr, rp, buffers, colors, save, xyb_done, keep=direct)
+                rp = self._chained_tail(fr, rp, buffers, colors, save, xyb_done, keep=direct or dcan)
             elif fr.has_noise:
                 h, w = buffers[0].shape
                 noise = be.noise_init(h, w, (self.visibleFrames << 32) | self.invisibleFrames, fr.group_dim, colors)
@@ -1417,7 +1679,7 @@ class JXLDecoder:
                     planes = be.ycbcr(planes)
                 for c in range(3):
                     buffers[c] = np.ascontiguousarray(planes[c])
-            if direct and getattr(self, "trace", None) is not None:  # a listener wants the samples: a copy comes down, the planes stay
+            if (direct or (dcan and rp is not None)) and getattr(self, "trace", None) is not None:  # a listener wants the samples: a copy comes down, the planes stay
                 planes = rp.download()
                 self.stats[-1]["plane_moves"].append("trace")
                 for c in range(3):
@@ -1433,19 +1695,55 @@ class JXLDecoder:
                     rp.orient(info.orientation)
                 extras = [be.orient(np.ascontiguousarray(b), info.orientation) if info.orientation != 1 else b for b in self.canvas[3:]]
                 return JXLImage([None] * 3 + extras, info, be, resident=rp)
-            if self.canvas[0] is None:
-                for c in range(len(self.canvas)):
-                    self.canvas[c] = np.zeros((info.height, info.width), buffers[0].dtype)
-            if fr.type in (REGULAR_FRAME, SKIP_PROGRESSIVE):
-                if any(self.reference[i] is self.canvas and i != fr.save_as_reference for i in range(4)):
-                    self.canvas = [b.copy() for b in self.canvas]
-                self._blend_frame(fr, buffers, colors)
+            if dcan:
+                if not self._is_set(self.canvas):  # :640-643: every plane of the type of the frame's first buffer
+                    first_type = np.dtype(np.float32) if rp is not None else buffers[0].dtype
+                    self.canvas = be.host.DeviceCanvas.create(be.ctx, [first_type] * len(self.canvas), info.height, info.width)
+                why = None
+                if fr.type in (REGULAR_FRAME, SKIP_PROGRESSIVE):
+                    if any(self.reference[i] is self.canvas and i != fr.save_as_reference for i in range(4)):
+                        self.canvas = self.canvas.clone()  # :645-653
+                    why = self._blend_frame_device(fr, buffers, rp)
+                if why is not None:
+                    # landing: the sets come down, the frame's colour planes too, and this frame is blended as without the switch
+                    # (the copy-on-write above has been made already, on the device)
+                    self._land(why)
+                    self.stats[-1]["canvas"] = "landed: " + why
+                    if rp is not None:
+                        planes = rp.download()
+                        for c in range(3):
+                            buffers[c] = planes[c]
+                    self._blend_frame(fr, buffers, colors)
+            else:
+                if self.canvas[0] is None:
+                    for c in range(len(self.canvas)):
+                        self.canvas[c] = np.zeros((info.height, info.width), buffers[0].dtype)
+                if fr.type in (REGULAR_FRAME, SKIP_PROGRESSIVE):
+                    if any(self.reference[i] is self.canvas and i != fr.save_as_reference for i in range(4)):
+                        self.canvas = [b.copy() for b in self.canvas]
+                    self._blend_frame(fr, buffers, colors)
             if save and not fr.save_before_ct:
                 self.reference[fr.save_as_reference] = self.canvas
+            bus1 = tuple(getattr(getattr(be, "ctx", None), "blend_bus", (0, 0)))
+            self.stats[-1]["blend_bus"] = (bus1[0] - bus0[0], bus1[1] - bus0[1])  # bytes up, bytes down: patches and blendFrame
             if fr.is_last or fr.duration != 0:
                 break
         if not produced:
             return None
+        if self._is_set(self.canvas):
+            self._release_dead()
+            cv, o = self.canvas, info.orientation
+            if all(t == np.float32 for t in cv.dtypes[:3]):
+                # the canvas' colour planes become the image's resident planes; the set lives on for the next animation frame
+                rp = cv.toPlanes()
+                if o != 1:
+                    rp.orient(o)
+                extras = [cv.download(c) for c in range(3, len(cv))]
+                extras = [be.orient(b, o) if o != 1 else b for b in extras]
+                self.stats[-1]["output"] = "device"
+                return JXLImage([None] * 3 + extras, info, be, resident=rp)
+            planes = [cv.download(c) for c in range(len(cv))]
+            return JXLImage([be.orient(b, o) if o != 1 else b for b in planes], info, be)
         oriented = [be.orient(np.ascontiguousarray(b), info.orientation) if info.orientation != 1 else b for b in self.canvas]
         return JXLImage(oriented, info, be)
 

@@ -964,7 +964,166 @@ def blend(ctx, mode, canvas, frame, ref, rect, frameAlpha=None, refAlpha=None, i
     rh, rw = rf.shape if rf is not None else (ra.shape if ra is not None else (0, 0))
     ctx.call("jxl_stage_blend", mode, flags, 1 if is_int else 0, _vp(cv), cv.shape[0], cv.shape[1], _vp(fr), fh, fw,
              _vp(rf), rh, rw, abi.fptr(fa) if fa is not None else None, abi.fptr(ra) if ra is not None else None, C.byref(r))
+    # what jxl_stage_blend moves: the canvas both ways, and up the planes the mode reads (blend_ops.h: blend_op / blend_needs)
+    add = mode == abi.BLEND_ADD or (not hasExtra and mode in (abi.BLEND_BLEND, abi.BLEND_MULADD))
+    copy_ref = mode == abi.BLEND_MULADD and hasExtra and isAlpha
+    reads = [cv, None if copy_ref else fr, None if mode == abi.BLEND_REPLACE else rf,
+             fa if not add and not copy_ref and (mode == abi.BLEND_MULADD or (mode == abi.BLEND_BLEND and not isAlpha)) else None,
+             ra if not add and mode == abi.BLEND_BLEND and not isAlpha else None]
+    _bus(ctx, up=sum(a.nbytes for a in reads if a is not None), down=cv.nbytes)
     return cv
+
+
+# ---- device plane sets: the canvas and the reference frames on the device (jxl_canvas_*) -------------------------------------
+def _bus(ctx, up=0, down=0):
+    """bytes the blend path moved over the bus, per context: ctx.blend_bus = [up, down]. Counted where the binding hands a host
+    array to the library or takes one back: blend() and the DeviceCanvas transfers"""
+    b = getattr(ctx, "blend_bus", None)
+    if b is None:
+        b = ctx.blend_bus = [0, 0]
+    b[0] += int(up)
+    b[1] += int(down)
+
+
+def _plane_code(dtype):
+    dt = np.dtype(dtype)
+    if dt == np.float32:
+        return abi.PLANE_FLOAT
+    if dt == np.int32:
+        return abi.PLANE_INT32
+    raise TypeError("int32 or float32 planes")
+
+
+_PLANE_DTYPE = {abi.PLANE_FLOAT: np.dtype(np.float32), abi.PLANE_INT32: np.dtype(np.int32)}
+
+
+class DeviceCanvas:
+    """a plane set of the context: ImageBuffer[] on the device (the canvas of JXLCodestreamDecoder.java:640-643, a frame's
+    buffers, a reference slot). `types` mirrors the library's tags (abi.PLANE_FLOAT / PLANE_INT32 per plane)."""
+
+    def __init__(self, ctx, id_, types, shape):
+        self.ctx, self.id, self.types, self.shape = ctx, id_, list(types), tuple(shape)
+
+    @classmethod
+    def create(cls, ctx, types, height, width):
+        """zero-filled planes (new ImageBuffer(type, height, width)); types: dtypes or plane codes"""
+        codes = [int(t) if isinstance(t, (int, np.integer)) else _plane_code(t) for t in types]
+        arr = np.array(codes if codes else [0], np.int32)
+        id_ = C.c_int32(-1)
+        ctx.call("jxl_canvas_create", len(codes), int(height), int(width), abi.iptr(arr), C.byref(id_))
+        return cls(ctx, id_.value, codes, (int(height), int(width)))
+
+    @classmethod
+    def fromArrays(cls, ctx, arrays):
+        """a set holding the host planes `arrays` (one shape; int32 or float32 each): one upload per plane"""
+        cv = cls.create(ctx, [a.dtype for a in arrays], *arrays[0].shape)
+        for i, a in enumerate(arrays):
+            cv.upload(i, a)
+        return cv
+
+    @classmethod
+    def fromPlanes(cls, ctx, extraTypes=()):
+        """a set whose first three planes (float) hold a copy of the context's resident planes and whose other planes, of
+        extraTypes, are zero until they are uploaded (jxl_canvas_from_planes): the colours cross no bus"""
+        h, w = C.c_int32(), C.c_int32()
+        ctx.call("jxl_planes_shape", C.byref(h), C.byref(w))
+        codes = [int(t) if isinstance(t, (int, np.integer)) else _plane_code(t) for t in extraTypes]
+        arr = np.array(codes if codes else [0], np.int32)
+        id_ = C.c_int32(-1)
+        ctx.call("jxl_canvas_from_planes", len(codes), abi.iptr(arr), C.byref(id_))
+        return cls(ctx, id_.value, [abi.PLANE_FLOAT] * 3 + codes, (h.value, w.value))
+
+    def _live(self):
+        if self.id is None:
+            raise IllegalStateException(abi.JXL_ERR_STATE, "the plane set has been released")
+
+    @property
+    def dtypes(self):
+        return [_PLANE_DTYPE[t] for t in self.types]
+
+    def __len__(self):
+        return len(self.types)
+
+    def clone(self):
+        """new ImageBuffer(b) per plane (JXLCodestreamDecoder.java:653): a device copy"""
+        self._live()
+        id_ = C.c_int32(-1)
+        self.ctx.call("jxl_canvas_clone", self.id, C.byref(id_))
+        return DeviceCanvas(self.ctx, id_.value, self.types, self.shape)
+
+    def upload(self, plane, array):
+        self._live()
+        a = np.ascontiguousarray(array)
+        if a.shape != self.shape:
+            raise ValueError("a plane of the set's size")
+        code = _plane_code(a.dtype)
+        self.ctx.call("jxl_canvas_upload", self.id, int(plane), _vp(a), code)
+        self.types[plane] = code
+        _bus(self.ctx, up=a.nbytes)
+
+    def download(self, plane):
+        self._live()
+        out = np.empty(self.shape, _PLANE_DTYPE[self.types[plane]])
+        t = C.c_int32(-1)
+        self.ctx.call("jxl_canvas_download", self.id, int(plane), _vp(out), C.byref(t))
+        assert t.value == self.types[plane], "the binding's plane tags have left the library's"
+        _bus(self.ctx, down=out.nbytes)
+        return out
+
+    def cast(self, plane, depth):
+        """ImageBuffer.castToFloat(depth) of the whole plane in place (jxl_canvas_cast); a float plane stays as it is"""
+        self._live()
+        self.ctx.call("jxl_canvas_cast", self.id, int(plane), int(depth))
+        self.types[plane] = abi.PLANE_FLOAT
+
+    def toPlanes(self):
+        """planes 0..2 (float) become the context's resident planes (jxl_canvas_to_planes); the set stays"""
+        self._live()
+        self.ctx.call("jxl_canvas_to_planes", self.id)
+        return ResidentPlanes(self.ctx)
+
+    def release(self):
+        if self.id is not None and getattr(self.ctx, "h", None):
+            self.ctx.call("jxl_canvas_destroy", self.id)
+        self.id = None
+
+    def canvasShape(self):
+        s = abi.CanvasShape()
+        s.n, s.h, s.w = len(self.types), self.shape[0], self.shape[1]
+        for i, t in enumerate(self.types):
+            s.types[i] = t
+        return s
+
+
+def canvasBlendDesc(canvas_id, frame_id, ref_id, rect, chans):
+    """jxl_canvas_blend_desc; chans: per canvas channel (frame_plane, mode, flags, frame_alpha, ref_alpha)"""
+    d = abi.CanvasBlendDesc()
+    d.canvas, d.frame, d.ref, d.n_chan = int(canvas_id), int(frame_id), int(ref_id), len(chans)
+    d.rect = abi.BlendRect(*[int(v) for v in rect])
+    for i, ch in enumerate(chans[:abi.CANVAS_MAX_PLANES]):
+        k = d.chan[i]
+        k.frame_plane, k.mode, k.flags, k.frame_alpha, k.ref_alpha = (int(v) for v in ch)
+    return d
+
+
+def canvas_blend(canvas, frame, ref, rect, chans):
+    """JXLCodestreamDecoder.blendFrame as one launch (jxl_canvas_blend), asynchronous. canvas / frame: DeviceCanvas; ref: a
+    DeviceCanvas (it may be `canvas` itself) or None for refBuffers == null; rect as blend()'s; chans as canvasBlendDesc's"""
+    for s in (canvas, frame, ref):
+        if s is not None:
+            s._live()
+    d = canvasBlendDesc(canvas.id, frame.id, -1 if ref is None else ref.id, rect, chans)
+    canvas.ctx.call("jxl_canvas_blend", C.byref(d))
+
+
+def canvas_blend_check(desc, canvas, frame, ref):
+    """jxl_canvas_blend_check: host only (no context, no device). desc: abi.CanvasBlendDesc; the others abi.CanvasShape (ref:
+    None when desc.ref is -1). Raises what jxl_canvas_blend would"""
+    from . import _lib
+    lib = _lib.load()
+    st = lib.jxl_canvas_blend_check(C.byref(desc), C.byref(canvas) if canvas is not None else None,
+                                    C.byref(frame) if frame is not None else None, C.byref(ref) if ref is not None else None)
+    _lib.check(None, st)
 
 
 def transposeBuffer(ctx, src, orientation):
