@@ -787,6 +787,33 @@ jxl_status jxl_stage_pfm_samples(jxl_ctx* ctx, const void* const in[3], const jx
  * the PFM's (PFMWriter.java:30-48 without image.getBuffer). JXL_ERR_STATE without resident planes. */
 jxl_status jxl_planes_pfm_samples(jxl_ctx* ctx, const jxl_pfm_params* p, void* out);
 
+/* ---- the varblock map drawn onto the picture: replaces Frame.drawVarblocks (Frame.java:464-503), which
+ * JXLCodestreamDecoder.java:638-639 calls right after performColorTransforms when JXLOptions.renderVarblocks is set ----
+ * Every block (cy, cx, type) tints the pixels of its pixelHeight x pixelWidth extent (include/jxl_transform_types.h) at
+ * (cy << 3, cx << 3) by its type (Frame.java:476-479: hue = (((float)type * PHI_BAR) % 1.0f) * 2f * (float)Math.PI, three
+ * factors from (float)Math.cos) and blackens its top row and left column (:488-491); every other pixel of it becomes
+ * factor_c * 0.5f + 0.5f * sample_c / light with light = (float)Math.cbrt(0.25f * (R + B) + 0.5f * G) * 0.5f + 0.25f (:493-497),
+ * every product, sum and quotient rounded on its own. The coordinates are FRAME cells: the caller adds the LF group's offset
+ * (:470-472, :480-481). A pixel outside the planes, or inside no block, is left alone: the block coordinates are those of the
+ * frame before upsampling whatever the planes' size (the reference's own behaviour on an upsampled frame).
+ * (float)Math.cos is the host library's cos and (float)Math.cbrt the device library's double-precision cbrt: each is within
+ * an ulp or two of the correctly rounded double, like Java's (specified to 1 ulp), so a sample can differ from a JVM's where
+ * the double lies that close to the middle between two floats. */
+typedef struct jxl_varblock_desc {
+    int32_t n_blocks;
+    const int32_t* blocks;      /* n_blocks x (cy, cx, type): frame cells (8 x 8 pixels) and TransformType.type, 0..26 */
+    int32_t cells_h, cells_w;   /* the cell grid the blocks live on: every block lies inside it, no two share a cell */
+} jxl_varblock_desc;
+/* in, out: three host planes of height x width floats each (out[c] may be in[c]). One upload, one launch, one download.
+ * JXL_ERR_INVALID_ARGUMENT (nothing queued, out untouched): a null pointer, a size below 1, a type above 26, a block that
+ * leaves the cell grid, two blocks that claim one cell. */
+jxl_status jxl_stage_varblocks(jxl_ctx* ctx, const float* const in[3], int32_t height, int32_t width, const jxl_varblock_desc* d,
+                               float* const out[3]);
+/* The same launch (Frame.java:464-503) on the three resident planes, in place, after jxl_planes_xyb / jxl_planes_ycbcr: nothing
+ * but the cell map (one byte per cell) and the 27 x 3 factors crosses the bus. Asynchronous. The same refusals, with the planes
+ * untouched. JXL_ERR_STATE without resident planes. */
+jxl_status jxl_planes_varblocks(jxl_ctx* ctx, const jxl_varblock_desc* d);
+
 /* ---- Modular path: replaces ModularStream.applyTransforms squeeze/RCT branches ---- */
 /* Default squeeze parameter list of ModularStream.java:110-131 for a channel list whose
  * first nb_meta channels are meta channels. Returns the count (<= cap) or a negative status. */

@@ -176,6 +176,11 @@ public final class NativeBackend implements AutoCloseable {
     // out holds exactly 4 * n_planes * width * height bytes
     public native void stagePfmSamples(ByteBuffer i0, ByteBuffer i1, ByteBuffer i2, int[] params, ByteBuffer out);  // jxl_stage_pfm_samples
     public native void planesPfmSamples(int[] params, ByteBuffer out);                                // jxl_planes_pfm_samples
+    // Frame.drawVarblocks (Frame.java:464-503; JXLCodestreamDecoder.java:638-639): blocks = nBlocks x (cy, cx, type) in frame cells
+    // (block.y + (lfGroupRow << 8), block.x + (lfGroupColumn << 8), dctSelect[block.y][block.x].type) on a cellsH x cellsW grid
+    public native void stageVarblocks(ByteBuffer i0, ByteBuffer i1, ByteBuffer i2, int height, int width, int[] blocks, int nBlocks,
+                                      int cellsH, int cellsW, ByteBuffer o0, ByteBuffer o1, ByteBuffer o2);   // jxl_stage_varblocks
+    public native void planesVarblocks(int[] blocks, int nBlocks, int cellsH, int cellsW);            // jxl_planes_varblocks
 
     // ---- device plane sets: the canvas and the reference frames on the device; a set is addressed by its id
     public native int canvasCreate(int h, int w, int[] types);     // jxl_canvas_create (types: 0 float, 1 int32 per plane)

@@ -1380,6 +1380,62 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasBlend
     if (st != JXL_OK) rethrow(e, NULL, st);
 }
 
+/* ---- the varblock map drawn onto the picture (Frame.drawVarblocks, Frame.java:464-503; jxl_stage_varblocks,
+ * jxl_planes_varblocks). blocks: nBlocks x (cy, cx, type) in frame cells, copied before the library sees it: the array must hold
+ * at least 3 * nBlocks ints. Returns the copy (free it; a one-int allocation for an empty list), NULL with an exception
+ * pending on failure. ---- */
+static jint* varblock_desc(JNIEnv* e, jintArray blocks, jint nBlocks, jint cellsH, jint cellsW, jxl_varblock_desc* d) {
+    if (!blocks || nBlocks < 0 || (jlong)(*e)->GetArrayLength(e, blocks) < 3 * (jlong)nBlocks) {
+        bad_arg(e, "jxlatte_amd: varblock list missing or shorter than 3 * nBlocks");
+        return NULL;
+    }
+    jint* mem = (jint*)malloc(sizeof(jint) * (3 * (size_t)nBlocks + 1));
+    if (!mem) {
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/OutOfMemoryError"), "jxlatte_amd: varblock list");
+        return NULL;
+    }
+    (*e)->GetIntArrayRegion(e, blocks, 0, 3 * nBlocks, mem);
+    if ((*e)->ExceptionCheck(e)) {
+        free(mem);
+        return NULL;
+    }
+    d->n_blocks = nBlocks;
+    d->blocks = (const int32_t*)mem;
+    d->cells_h = cellsH;
+    d->cells_w = cellsW;
+    return mem;
+}
+
+/* on three host planes of height x width floats; o0..o2 receive the result (they may be the input buffers) */
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageVarblocks(JNIEnv* e, jobject self, jobject i0, jobject i1, jobject i2,
+        jint h, jint w, jintArray blocks, jint nBlocks, jint cellsH, jint cellsW, jobject o0, jobject o1, jobject o2) {
+    jxl_ctx* c = ctx_of(e, self);
+    if (h < 1 || w < 1) { bad_arg(e, "jxlatte_amd: plane size"); return; }
+    const jlong plane = 4 * area(h, w);
+    NEED(i0, plane); NEED(i1, plane); NEED(i2, plane);
+    NEED(o0, plane); NEED(o1, plane); NEED(o2, plane);
+    const float* in[3] = {(const float*)ADDR(i0), (const float*)ADDR(i1), (const float*)ADDR(i2)};
+    float* out[3] = {(float*)ADDR(o0), (float*)ADDR(o1), (float*)ADDR(o2)};
+    jxl_varblock_desc d;
+    jint* mem = varblock_desc(e, blocks, nBlocks, cellsH, cellsW, &d);
+    if (!mem) return;
+    const jxl_status st = jxl_stage_varblocks(c, in, h, w, &d, out);
+    free(mem);
+    CHECK(st);
+}
+
+/* the same on the resident planes, in place, after planesXyb / planesYcbcr */
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesVarblocks(JNIEnv* e, jobject self, jintArray blocks, jint nBlocks,
+        jint cellsH, jint cellsW) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_varblock_desc d;
+    jint* mem = varblock_desc(e, blocks, nBlocks, cellsH, cellsW, &d);
+    if (!mem) return;
+    const jxl_status st = jxl_planes_varblocks(c, &d);
+    free(mem);
+    CHECK(st);
+}
+
 /* ---- Modular: plan once, run, read channel by channel (ModularStream.applyTransforms, ModularStream.java:110-131) ---- */
 JNIEXPORT jintArray JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_modularDefaultSqueezeParams(JNIEnv* e, jclass k, jintArray widths,
         jintArray heights, jint nbMeta) {

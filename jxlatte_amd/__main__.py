@@ -42,6 +42,10 @@ def parser():
                     help="keep the canvas and the reference frames of multi-frame images on the device and blend every frame in one "
                          "launch (JXLDecoder device_canvas; jxl_canvas_blend); the same samples. The image's colour planes stay on "
                          "the device where they are float: add --device-png to pack the samples there too")
+    ap.add_argument("--draw-varblocks", action="store_true",
+                    help="the reference's --draw-varblocks: tint every varblock of a VarDCT frame by its transform type and blacken "
+                         "its top row and left column (Frame.drawVarblocks as one device pass: jxl_planes_varblocks on planes "
+                         "that are on the device, jxl_stage_varblocks otherwise)")
     return ap
 
 
@@ -67,7 +71,8 @@ def main(argv=None):
     t0 = time.time()
     backend = DeviceBackend(a.device)
     dec = JXLDecoder(a.input, backend=backend, sparse_coeffs=a.sparse_coeffs, device_splines=a.device_splines,
-                     device_patches=a.device_patches, device_output=a.device_png, device_canvas=a.device_canvas)
+                     device_patches=a.device_patches, device_output=a.device_png, device_canvas=a.device_canvas,
+                     draw_varblocks=a.draw_varblocks)
     image = dec.decode()
     if image is None:
         print("jxlatte_amd: no frames", file=sys.stderr)

@@ -151,6 +151,8 @@ SIGNATURES = {
     "jxl_planes_orient": (i32, [vp, i32]),
     "jxl_stage_pfm_samples": (i32, [vp, pv3, C.POINTER(abi.PfmParams), vp]),
     "jxl_planes_pfm_samples": (i32, [vp, C.POINTER(abi.PfmParams), vp]),
+    "jxl_stage_varblocks": (i32, [vp, pf3, i32, i32, C.POINTER(abi.VarblockDesc), pf3]),
+    "jxl_planes_varblocks": (i32, [vp, C.POINTER(abi.VarblockDesc)]),
     "jxl_modular_default_squeeze_params": (i32, [pi, pi, i32, i32, C.POINTER(abi.SqueezeParam), i32]),
     "jxl_modular_squeezed_shapes": (i32, [pi, pi, i32, C.POINTER(abi.SqueezeParam), i32, pi, pi, i32]),
     "jxl_modular_begin": (i32, [vp, C.POINTER(abi.Channel), i32, C.POINTER(abi.SqueezeParam), i32, i32, i32]),

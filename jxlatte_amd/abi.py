@@ -191,6 +191,22 @@ class PfmParams(C.Structure):
                 ("tagged_depth", C.c_int32 * 3)]
 
 
+class VarblockDesc(C.Structure):
+    """struct jxl_varblock_desc"""
+    _fields_ = [("n_blocks", C.c_int32), ("blocks", C.POINTER(C.c_int32)), ("cells_h", C.c_int32), ("cells_w", C.c_int32)]
+
+
+def make_varblock_desc(blocks, cells):
+    """blocks: n x (cy, cx, type) in frame cells; cells: (cells_h, cells_w). Returns (desc, keep): `keep` owns the memory the
+    descriptor points into"""
+    b = np.ascontiguousarray(np.asarray(blocks, np.int32).reshape(-1, 3))
+    d = VarblockDesc()
+    d.n_blocks = b.shape[0]
+    d.blocks = iptr(b) if b.shape[0] else None
+    d.cells_h, d.cells_w = int(cells[0]), int(cells[1])
+    return d, b
+
+
 class SplineDesc(C.Structure):
     """struct jxl_spline_desc (SplinesBundle.java + the two LFChannelCorrelation factors)"""
     _fields_ = [("quant_adjust", C.c_int32), ("n_splines", C.c_int32), ("n_control", C.POINTER(C.c_int32)),

@@ -4,6 +4,7 @@
 #include "jxl_internal.h"
 #include "modular_tend.h"  // kSqueezeSafeIn (jxl_modular_begin picks the plan by it)
 #include "pfm_check.h"     // what the PFM entries refuse
+#include "varblock_check.h"  // what the varblock entries refuse, their cell map and factor table
 
 #include <algorithm>
 #include <chrono>
@@ -4151,6 +4152,68 @@ jxl_status jxl_planes_pfm_samples(jxl_ctx* c, const jxl_pfm_params* p, void* out
     for (int i = 0; i < 3; i++) a.in[i] = c->rp[i].p;
     Tmp t;
     return pfm_run(c, a, t, out);
+}
+
+// ---- the varblock map drawn onto the picture (k_varblocks.hip): Frame.drawVarblocks, Frame.java:464-503 ----
+}  // extern "C"
+namespace {
+constexpr size_t kVbFactorBytes = sizeof(float) * 32 * 3;  // 27 x 3 used: room for every value of the map's five type bits
+
+// the checks and tables of varblock_check.h for `d`, queued to the device in one transfer (c->spl: the factors, then the cell
+// map); a refusal queues nothing
+jxl_status varblock_tables(jxl_ctx* c, const jxl_varblock_desc* d, VarblockArgs* a) {
+    std::vector<uint8_t> map;
+    const char* bad = varblock_cell_map(d, &map);
+    if (bad) return fail(c, JXL_ERR_INVALID_ARGUMENT, "%s", bad);
+    const size_t total = kVbFactorBytes + map.size();
+    jxl_status st = tables_reserve(c, total);
+    if (st) return st;
+    memset(c->h_spl, 0, kVbFactorBytes);
+    varblock_factors(reinterpret_cast<float*>(c->h_spl));
+    memcpy(c->h_spl + kVbFactorBytes, map.data(), map.size());
+    if ((st = tables_send(c, total))) return st;
+    a->factors = c->spl.as<float>();
+    a->map = c->spl.as<uint8_t>() + kVbFactorBytes;
+    a->cells_h = d->cells_h;
+    a->cells_w = d->cells_w;
+    return JXL_OK;
+}
+}  // namespace
+extern "C" {
+
+jxl_status jxl_stage_varblocks(jxl_ctx* c, const float* const in[3], int32_t height, int32_t width, const jxl_varblock_desc* d,
+                               float* const out[3]) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (!in || !in[0] || !in[1] || !in[2] || !out || !out[0] || !out[1] || !out[2] || height < 1 || width < 1)
+        return fail(c, JXL_ERR_INVALID_ARGUMENT, "varblocks: bad arguments");
+    VarblockArgs a;
+    if ((st = varblock_tables(c, d, &a))) return st;
+    const size_t n = (size_t)height * width;
+    Tmp t;
+    for (int i = 0; i < 3; i++)
+        if (!(a.pl[i] = t.up(in[i], n))) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    a.h = height;
+    a.w = width;
+    launch_varblocks(a, c->stream);
+    if ((st = finish(c))) return st;
+    for (int i = 0; i < 3; i++) HIP_TRY(c, hipMemcpy(out[i], a.pl[i], sizeof(float) * n, hipMemcpyDeviceToHost));
+    return JXL_OK;
+}
+
+jxl_status jxl_planes_varblocks(jxl_ctx* c, const jxl_varblock_desc* d) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (c->rp_h <= 0) return fail(c, JXL_ERR_STATE, "no resident planes");
+    VarblockArgs a;
+    if ((st = varblock_tables(c, d, &a))) return st;
+    for (int i = 0; i < 3; i++) a.pl[i] = c->rp[i].as<float>();
+    a.h = c->rp_h;
+    a.w = c->rp_w;
+    launch_varblocks(a, c->stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, JXL_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
+    return JXL_OK;
 }
 
 }  // extern "C"

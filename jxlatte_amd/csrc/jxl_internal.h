@@ -252,6 +252,16 @@ struct PfmArgs {
     void* out;          // h * w * n_planes words
 };
 void launch_pfm_samples(const PfmArgs& p, hipStream_t s);
+// Frame.drawVarblocks (Frame.java:464-503) on three float planes, in place (k_varblocks.hip); the cell map and the factors are
+// varblock_check.h's
+struct VarblockArgs {
+    float* pl[3];          // device planes of h * w floats
+    int h, w;
+    const uint8_t* map;    // cells_h * cells_w bytes: type | top-row bit | left-column bit, or 0xFF
+    int cells_h, cells_w;
+    const float* factors;  // 27 x 3: rFactor, gFactor, bFactor per type
+};
+void launch_varblocks(const VarblockArgs& p, hipStream_t s);
 // PQ as a table of quadratic segments (jxl_fastpow.h): kPqTableFloats floats = float4 {a0 hi, a0 lo, a1, a2} per segment
 constexpr int kPqTableFloats = (129 - 87) * 128 * 4;
 void build_pq_table(float* out /* [kPqTableFloats] */);

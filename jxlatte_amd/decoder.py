@@ -725,6 +725,10 @@ class DeviceBackend:
         """PNGWriter's samples in one pass (host.pngSamples; the keywords are host.pngParams')"""
         return self.host.pngSamples(self.ctx, planes, alpha, **params)
 
+    def varblocks(self, planes, blocks, cells):
+        """Frame.drawVarblocks in one pass (host.varblocks)"""
+        return self.host.varblocks(self.ctx, planes, blocks, cells)
+
     def pfm_samples(self, planes, tagged):
         """PFMWriter's samples in one pass (host.pfmSamples)"""
         return self.host.pfmSamples(self.ctx, planes, tagged)
@@ -970,7 +974,7 @@ def _tt_dims():
 
 class JXLDecoder:
     def __init__(self, source, backend=None, sparse_coeffs=False, device_splines=False, device_patches=False, device_output=False,
-                 device_canvas=False):
+                 device_canvas=False, draw_varblocks=False):
         """sparse_coeffs: hand the HF coefficients to the backend as lists of non-zero entries (jxf_get_coeffs_sparse ->
         jxl_vardct_put_group_sparse), not as dense planes; same pixels.
         device_splines: Frame.renderSplines runs in the backend (jxl_planes_splines on the resident planes, jxl_stage_splines
@@ -994,7 +998,16 @@ class JXLDecoder:
         the default decoder's arrays either way. Where blend_type_plan says "land", and before a frame with patches, every set
         comes down into host lists (aliases stay aliases) and the image goes on as without the switch. stats[-1]["canvas"]:
         "device", "host" (the switch is off) or "landed: <reason>". device_output's single-frame path takes precedence. A backend
-        without a context is an error."""
+        without a context is an error.
+        draw_varblocks: JXLOptions.renderVarblocks -- every VarDCT frame that reaches performColorTransforms (invisible frames
+        too) gets Frame.drawVarblocks right after it (JXLCodestreamDecoder.java:638-639): each varblock tinted by its transform
+        type, its top row and left column black, after the saveBeforeCT reference is taken and before the blend. One device pass:
+        ResidentPlanes.varblocks where the colour planes are on the device at that point (device_output, device_canvas),
+        backend.varblocks on the host planes otherwise; there is no host restatement, and a backend without `varblocks` is an
+        error. Modular frames are left alone. stats[k]["varblocks"] then says "device planes" or "host planes" (the type
+        histogram it holds without the switch moves to stats[k]["varblock_types"]). A frame of several LF groups whose group
+        size is not 256 raises UnsupportedOperationException: the reference's hard-coded << 11 leaves the frame there."""
+        self.draw_varblocks = bool(draw_varblocks)
         self.device_output = bool(device_output)
         self.device_canvas = bool(device_canvas)
         self._landed = None   # why the canvas is (back) on the host for the rest of this image
@@ -1086,12 +1099,28 @@ class JXLDecoder:
     def _vardct_frame(self, fr, fuse_xyb, keep=None):
         p, weights, woffs, lfgroups, groups, hist = self._vardct_inputs(fr, fuse_xyb)
         self.stats[-1]["varblocks"] = {abi.TT_NAME[t]: int(n) for t, n in enumerate(hist) if n}
+        self._varblock_list = self._gather_varblocks(fr, lfgroups) if getattr(self, "draw_varblocks", False) else None
         sparse = getattr(self, "sparse_coeffs", False)
         kw = dict(sparse=True) if sparse else {}
         if keep is not None:
             return self.backend.vardct(p, weights, woffs, lfgroups, groups(sparse), keep=keep, **kw)
         planes = self.backend.vardct(p, weights, woffs, lfgroups, groups(sparse), **kw)
         return [np.ascontiguousarray(planes[c]) for c in range(3)]
+
+    @staticmethod
+    def _gather_varblocks(fr, lfgroups):
+        """the frame's block list as Frame.drawVarblocks walks it (Frame.java:468-481): (cy, cx, type) in frame cells, and the
+        cell grid they live on. The LF group's offset is the reference's << 11 pixels = << 8 cells"""
+        if len(lfgroups) > 1 and fr.group_dim != 256:
+            raise UnsupportedOperationException("draw_varblocks: several LF groups with group_dim %d (the reference's LF-group "
+                                                "pitch of 2048 pixels holds for 256 only)" % fr.group_dim)
+        rows, cells_h, cells_w = [], 1, 1
+        for g in lfgroups:
+            oy, ox = g["lfg_y"] << 8, g["lfg_x"] << 8
+            yx, sel = g["block_yx"], np.asarray(g["dct_select"])
+            rows.append(np.stack([yx[:, 0] + oy, yx[:, 1] + ox, sel[yx[:, 0], yx[:, 1]]], axis=1).astype(np.int32))
+            cells_h, cells_w = max(cells_h, oy + sel.shape[0]), max(cells_w, ox + sel.shape[1])
+        return np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros((0, 3), np.int32), (cells_h, cells_w)
 
     def _up_weights(self, k):
         info = self.info
@@ -1685,6 +1714,17 @@ class JXLDecoder:
                 for c in range(3):
                     buffers[c] = planes[c]
             self._trace("xyb", buffers, False)  # JXLCodestreamDecoder.java:637: the frame's buffers after performColorTransforms
+            if fr.encoding == VARDCT and getattr(self, "draw_varblocks", False):  # JXLCodestreamDecoder.java:638-639
+                blocks, cells = self._varblock_list
+                self.stats[-1]["varblock_types"] = self.stats[-1]["varblocks"]
+                if rp is not None:
+                    rp.varblocks(blocks, cells)
+                    self.stats[-1]["varblocks"] = "device planes"
+                else:
+                    planes = be.varblocks(np.stack([self._to_float(buffers[c], info.bits_per_sample) for c in range(3)]), blocks, cells)
+                    for c in range(3):
+                        buffers[c] = np.ascontiguousarray(planes[c])
+                    self.stats[-1]["varblocks"] = "host planes"
             if direct:
                 # the frame replaces the whole canvas: its colour planes are the image's; the extra channels take the usual way
                 self.stats[-1]["output"] = "device"

@@ -285,6 +285,17 @@ def pfmSamples(ctx, planes, taggedDepths=None):
     return out
 
 
+def varblocks(ctx, planes, blocks, cells):
+    """Frame.drawVarblocks (Frame.java:464-503) on three float planes (jxl_stage_varblocks): every block (cy, cx, type) of
+    `blocks` -- frame cells of 8 x 8 pixels on the cells = (cells_h, cells_w) grid -- tints its extent by its type and
+    blackens its top row and left column; pixels outside the planes or inside no block stay. Returns new planes"""
+    pl = _planes(planes, np.float32)
+    out = np.empty_like(pl)
+    d, keep = abi.make_varblock_desc(blocks, cells)
+    ctx.call("jxl_stage_varblocks", _p3(pl, C.c_float), pl.shape[1], pl.shape[2], C.byref(d), _p3(out, C.c_float))
+    return out
+
+
 def pack_sparse(planes, wide=False):
     """The sparse wire format of include/jxlatte_amd.h: the non-zero samples of a 2-D integer plane (at most 256 x 256: one
     group of one channel) as a uint32 array of entries in raster order -- narrow: value << 16 | y << 8 | x; wide: the words
@@ -656,6 +667,13 @@ class ResidentPlanes:
         out = np.empty((shape[0], shape[1], 3, 4), np.uint8)
         self.ctx.call("jxl_planes_pfm_samples", C.byref(p), _vp(out))
         return out
+
+    def varblocks(self, blocks, cells):
+        """Frame.drawVarblocks on the planes as they stand, in place (jxl_planes_varblocks): after the colour transforms; only
+        the cell map and the factor table go up"""
+        self._need_live()
+        d, keep = abi.make_varblock_desc(blocks, cells)
+        self.ctx.call("jxl_planes_varblocks", C.byref(d))
 
     def download(self):
         h, w = self.shape
