@@ -194,6 +194,10 @@ struct jxl_ctx {
     bool result_interleaved = false;
     int last_launches = 0;
     int last_plane_a_tiled = 0;  // the last run_frame wrote cell-tiled pooled planes (jxl_debug_last_plane_a_tiled)
+    // the fused restoration launches of the last run (jxl_debug_last_restore_launches): 0 = the stage kernels ran, 2 = the split
+    // three-iteration pair; per launch restore_fused_variant() | kRestoreTiledBit | kRestoreBatchBit
+    int last_restore_n = 0;
+    int32_t last_restore_code[2] = {0, 0};
     uint64_t tables_gen = 0;  // bumped whenever finalize_tables rebuilds the binned work (batch argument cache key)
     // jxl_vardct_run_batch state (kept by the first context of a batch)
     DevBuf batch_restore_args;
@@ -487,6 +491,13 @@ bool shared_planes_on() {
 // Cell-tiled pooled planes (plane_tiled.h): process-wide, read per run. The library reads no environment variable for
 // it: the Python package maps JXL_PLANE_A_TILED=0 onto jxl_debug_set_plane_a_tiled (jxlatte_amd/_lib.py), tests flip it in place.
 std::atomic<int> g_plane_a_tiled{1};
+// jxl_debug_last_restore_launches: above the seven bits of restore_fused_variant()
+constexpr int32_t kRestoreTiledBit = 128, kRestoreBatchBit = 256;
+int32_t restore_launch_code(const RestoreParams& rp, bool tiled, bool batch) {
+    FusedArgs a{};
+    a.p = rp;
+    return restore_fused_variant(a) | (tiled ? kRestoreTiledBit : 0) | (batch ? kRestoreBatchBit : 0);
+}
 void inter_account(int device, long long delta) {
     if (device >= 0 && device < 64) g_inter_bytes[device].fetch_add(delta, std::memory_order_relaxed);
 }
@@ -1282,6 +1293,15 @@ extern "C" int64_t jxl_debug_intermediate_bytes(int device) {
 extern "C" int jxl_debug_set_plane_a_tiled(int on) { return g_plane_a_tiled.exchange(on ? 1 : 0, std::memory_order_relaxed); }
 // ... and whether the context's last frame run took that layout (tests/test_tiled_plane_a_gpu.py)
 extern "C" int jxl_debug_last_plane_a_tiled(const jxl_ctx* c) { return c ? c->last_plane_a_tiled : 0; }
+// Test hook (tests/test_restore_variants_gpu.py): the fused restoration launches of the context's last frame run -- how many (0: the
+// stage kernels ran instead, 1, or 2 for the split three-iteration form) and, per launch, which instantiation:
+// restore_fused_variant() of its arguments (Gaborish 64 | EPF iterations << 3 | sink kind), | 128 for cell-tiled input planes,
+// | 256 for a batch launch, which every context of the batch reports. Not part of the C-ABI of include/jxlatte_amd.h.
+extern "C" int jxl_debug_last_restore_launches(const jxl_ctx* c, int32_t codes[2]) {
+    if (!c) return 0;
+    for (int i = 0; i < 2 && codes; i++) codes[i] = i < c->last_restore_n ? c->last_restore_code[i] : 0;
+    return c->last_restore_n;
+}
 extern "C" int jxl_debug_clock_probe(int device, double us, double* mhz) {
     static hipStream_t s = nullptr;
     static unsigned long long* d = nullptr;
@@ -2513,6 +2533,7 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
     // sharpness range check of Frame.java:565-566 (host side: the maps came through the host; scanned by finalize_tables)
     if (do_epf && c->sharp_is_bad) return fail(c, JXL_ERR_INVALID_BITSTREAM, "Invalid EPF Sharpness: %d", c->sharp_bad);
     bool fused = false;
+    c->last_restore_n = 0;
     c->kev_valid = false;  // only the single-launch fused kernel of THIS run makes its event pair readable (stage-masked, split and batch runs do not)
     if (do_gab || do_epf || do_xyb || do_out) {
         RestoreParams rp{};
@@ -2533,6 +2554,10 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
         if (collect) {
             fused = fill_restore_fused_args(src, dst, c->H, c->W, c->hf_mul.as<int32_t>(), c->sharp.as<int32_t>(), rp, *collect);
             if (collected) *collected = fused;
+            if (fused) {  // (jxl_vardct_run_batch marks it as the batch's launch, or runs the frame again on its own)
+                c->last_restore_n = 1;
+                c->last_restore_code[0] = restore_launch_code(rp, false, false);
+            }
         } else if (split) {
             RestoreParams ra = rp, rb = rp;
             ra.epf_iters = 4;  // restore_fused_body.h: the 13-tap iteration alone
@@ -2544,7 +2569,12 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
             const float* mids[3] = {oth[0], oth[1], oth[2]};
             fused = launch_restore_fused(src, mid, c->H, c->W, c->hf_mul.as<int32_t>(), c->sharp.as<int32_t>(), ra, s) &&
                     launch_restore_fused(mids, dst, c->H, c->W, c->hf_mul.as<int32_t>(), c->sharp.as<int32_t>(), rb, s);
-            if (fused) launches++;
+            if (fused) {
+                launches++;
+                c->last_restore_n = 2;
+                c->last_restore_code[0] = restore_launch_code(ra, false, false);
+                c->last_restore_code[1] = restore_launch_code(rb, false, false);
+            }
         } else {
             if (c->timing) {  // the kernel records its own start / stop (jxl_vardct_last_stage_ms, which = 3)
                 g_restore_kernel_ev[0] = c->kev[c->ev_runs % jxl_ctx::kEvSlots][0];
@@ -2553,6 +2583,10 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
             fused = launch_restore_fused(src, dst, c->H, c->W, c->hf_mul.as<int32_t>(), c->sharp.as<int32_t>(), rp, s, tiled);
             g_restore_kernel_ev[0] = g_restore_kernel_ev[1] = nullptr;
             c->kev_valid = c->timing && fused;
+            if (fused) {
+                c->last_restore_n = 1;
+                c->last_restore_code[0] = restore_launch_code(rp, tiled, false);
+            }
         }
         if (shared && !fused) return fail(c, JXL_ERR_STATE, "the fused restoration launch declined a run on shared planes");
         if (fused) {
@@ -2775,6 +2809,10 @@ jxl_status jxl_vardct_run_batch(jxl_ctx* const* ctxs, int32_t n) {
         // run_frame in collect mode has counted the fused launch on every frame, but the batch enqueued ONE: like the shared IDCT
         // launches it is attributed to the first context, so that the counts of a batch's contexts add up to its launches
         for (int i = 1; i < n; i++) ctxs[i]->last_launches -= 1;
+        for (int i = 0; i < n; i++) {  // every context of the batch reports the shared launch
+            ctxs[i]->last_restore_n = 1;
+            ctxs[i]->last_restore_code[0] = restore_fused_variant(fa[0]) | kRestoreBatchBit;
+        }
         c0->last_launches += (int)c0->batch_launches.size();
         return JXL_OK;
     }

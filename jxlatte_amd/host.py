@@ -517,6 +517,13 @@ class Frame:
     def lastLaunchCount(self):
         return self.ctx.lib.jxl_vardct_last_launch_count(self.ctx.h)
 
+    def lastRestoreLaunches(self):
+        """the fused restoration launches of the context's last run, one code each (jxl_debug_last_restore_launches, a test hook
+        outside the C-ABI): [] when the stage kernels ran instead, two for the split three-iteration form. A code is
+        restore_fused_variant() of the launch -- Gaborish 64 | EPF iterations << 3 | sink kind -- | 128 for cell-tiled input
+        planes | 256 for a batch launch, which every context of the batch reports"""
+        return lastRestoreLaunches(self.ctx)
+
     def keepPlanes(self, height, width):
         """run, and keep the height x width window of the result on the device for the stages that follow decodeFrame
         (JXLCodestreamDecoder.java:628-637): -> ResidentPlanes"""
@@ -538,6 +545,15 @@ class Frame:
         for grp in range(synth.num_groups(frame)):
             fr.putGroup(0, grp, synth.group_view(frame, grp))
         return fr
+
+
+def lastRestoreLaunches(ctx):
+    """Frame.lastRestoreLaunches of a context"""
+    fn = ctx.lib.jxl_debug_last_restore_launches
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]
+    codes = (C.c_int32 * 2)()
+    n = fn(ctx.h, codes)
+    return [int(codes[i]) for i in range(n)]
 
 
 class PinnedArray:

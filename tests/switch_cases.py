@@ -324,6 +324,28 @@ def case_modular():
     return t.bad
 
 
+def case_restore_variants_epf3():
+    """JXL_EPF3_SPLIT=0 (read once per process): the three-iteration instantiations of tests/restore_variants.py, single and batch
+    launches, against the oracle; the launches each case made are held to the table's, and printed ("SEEN <code>") for the parent
+    (tests/test_restore_variants_gpu.py) to add to its inventory"""
+    import restore_variants as rv
+    t = _Tally()
+    ctxs = rv.Contexts()
+    seen = set()
+    for c in rv.all_cases(child=True):
+        try:
+            problems = rv.check_case(c, ctxs, t.check, seen)
+        except AssertionError as e:
+            problems = [str(e)]
+        for msg in problems:
+            t.bad += 1
+            print("FAIL", msg, flush=True)
+    for x in sorted(seen):
+        print("SEEN", x, flush=True)
+    ctxs.close()
+    return t.bad
+
+
 CHILD_CASES = {
     "restore_ph2": case_restore_ph2,
     "restore_ph2_epf3": case_restore_ph2_epf3,
@@ -332,6 +354,7 @@ CHILD_CASES = {
     "transfer16": case_transfer16,
     "bus": case_bus,
     "modular": case_modular,
+    "restore_variants_epf3": case_restore_variants_epf3,
 }
 
 if __name__ == "__main__":

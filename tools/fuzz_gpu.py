@@ -1,5 +1,6 @@
 """Randomised device-vs-oracle parity sweep (GPU box): frame sizes off every tile grid, varblock mixes, aligned / unaligned
-tilings, Gaborish on / off, 0-3 EPF iterations, float / u8 / u16 / interleaved outputs, sRGB / PQ, single runs and batches.
+tilings, Gaborish on / off, 0-3 EPF iterations, float / u8 / u16 / interleaved 8- and 16-bit outputs, sRGB / PQ, single runs and
+batches. Every output, float or integer, must equal the oracle's bit for bit.
     python tools/fuzz_gpu.py [n_cases] [seed]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -23,13 +24,19 @@ def run(n_cases=40, seed=2026, device=0, verbose=True):
                 if mix == "large":
                     w, h = max(w, 256), max(h, 256)
                 kw = dict(epf_iters=int(rng.integers(0, 4)), nonzero_p=float(rng.choice([0.0, 0.02, 0.15, 0.5])))
-                fmt = int(rng.integers(0, 5))
+                fmt = int(rng.integers(0, 8))  # 0 and 4: float planes
                 if fmt == 1:
                     kw.update(transfer=abi.TRANSFER_SRGB, out_format=abi.OUT_U8)
                 elif fmt == 2:
                     kw.update(transfer=abi.TRANSFER_PQ, out_format=abi.OUT_U16)
                 elif fmt == 3:
                     kw.update(transfer=abi.TRANSFER_SRGB, out_format=abi.OUT_RGB8)
+                elif fmt == 5:
+                    kw.update(transfer=abi.TRANSFER_PQ, out_format=abi.OUT_RGB16)
+                elif fmt == 6:
+                    kw.update(transfer=abi.TRANSFER_SRGB, out_format=abi.OUT_RGB16)
+                elif fmt == 7:
+                    kw.update(transfer=abi.TRANSFER_SRGB, out_format=abi.OUT_U16)
                 fr = synth.make_vardct_frame(w, h, seed=int(rng.integers(1, 1 << 30)), mix=mix, aligned=bool(rng.integers(0, 2)), **kw)
                 if rng.integers(0, 4) == 0:
                     fr["params"].gab = 0
@@ -47,7 +54,7 @@ def run(n_cases=40, seed=2026, device=0, verbose=True):
                     ok = np.array_equal(got.view(np.uint32), exp.view(np.uint32))
                 else:
                     e = exp if exp.shape == got.shape else np.moveaxis(exp, 0, -1)
-                    ok = np.abs(got.astype(np.int64) - e.astype(np.int64)).max() <= 1  # transfer stage: <= 1 code value
+                    ok = np.array_equal(got.astype(np.int64), e.astype(np.int64))  # the oracle's code values
                 if not ok:
                     bad += 1
                     p = synths[k]["params"]
