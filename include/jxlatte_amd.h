@@ -592,6 +592,29 @@ jxl_status jxl_stage_inv_vsqueeze(jxl_ctx* ctx, const int32_t* avg, int32_t ah, 
  * v[3] of n samples; rct_type = permutation*7 + type. On return v[] holds the planes in
  * output channel order (the permutation is applied). */
 jxl_status jxl_stage_rct(jxl_ctx* ctx, int32_t* const v[3], int64_t n, int32_t rct_type);
+/* Palette branch of ModularStream.applyTransforms (ModularStream.java:327-378) for one transform: sample (y, x) of output
+ * plane c is the colour its index names -- palette[c][index] for 0 <= index < nb_colors, the implicit colours above that (a
+ * 64-entry cube, then the / 5 ladder, :346-356), kDeltaPalette below zero (:357-366; 0 for c >= 3) -- and, where index <
+ * nb_deltas, that colour plus ModularChannel.prediction (ModularChannel.java:143-183) with predictor d_pred on plane c's own
+ * samples, which are final for every neighbour the predictors read (:95-121). All of it in Java int arithmetic: sums,
+ * products, negations and left shifts wrap at 32 bits, / and % truncate toward zero, shift counts count mod 32.
+ * bit_depth is the image's bitsPerSample (:331). */
+typedef struct jxl_palette_desc {
+    int32_t num_c, nb_colors, nb_deltas, d_pred, bit_depth;
+    int32_t pal_h, pal_w;
+    const int32_t* palette;   /* pal_h x pal_w: channel 0 of the stream */
+    const int32_t* pred;      /* height x width weighted-predictor values as decoded (before (p + 3) >> 3), or NULL */
+} jxl_palette_desc;
+/* index: height x width host samples; out: num_c host planes of height x width (out[0] may be index). Every input goes up
+ * once (the index plane, nb_colors entries of the first num_c palette rows, pred when d_pred is 6) and every output plane comes
+ * down once. One launch -- two when d_pred is neither 0 nor 6 and some pixel has index < nb_deltas: those pixels are then
+ * resolved by a second kernel, in dependency order. With d_pred 6 and no pred plane the prediction is 0.
+ * JXL_ERR_INVALID_ARGUMENT (nothing queued, out untouched): a null pointer, height or width below 1 or more than INT32_MAX
+ * samples, num_c < 1, nb_colors or nb_deltas < 0, pal_w < nb_colors or pal_h < num_c (the reference's
+ * ArrayIndexOutOfBoundsException), d_pred outside 0..13, d_pred 6 with nb_deltas > 0 and no pred plane, bit_depth outside
+ * 1..32. */
+jxl_status jxl_stage_palette(jxl_ctx* ctx, const jxl_palette_desc* d, const int32_t* index, int32_t height, int32_t width,
+                             int32_t* const* out /* num_c planes */);
 /* Frame.decodeFrame modular->buffer (Frame.java:430-455) for one output channel:
  * out = scale * (a + b) (b may be NULL) as float. */
 jxl_status jxl_stage_modular_to_float(jxl_ctx* ctx, const int32_t* a, const int32_t* b, int64_t n,

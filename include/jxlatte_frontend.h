@@ -5,9 +5,12 @@
  * decoding, MA trees and predictors, TOC, LfGlobal / LfGroup / HfGlobal / pass groups). No JVM exists in this image,
  * so the same job is done by this C++ library: it turns a .jxl file into exactly the tensors that
  * include/jxlatte_amd.h takes (quantised coefficients per pass and group, LF images, varblock maps, modular channel
- * lists + transform descriptors). It contains NO transform-stage arithmetic for frame-level data: inverse Squeeze / RCT
- * of the frame's modular stream are delegated to the caller through jxf_hooks (the device library), and the VarDCT
- * pipeline is not present here at all. Plain CPU code (g++), no GPU needed.
+ * lists + transform descriptors). Inverse Squeeze / RCT of the frame's modular stream are delegated to the caller through
+ * jxf_hooks (the device library), and so is its inverse Palette where the caller sets the palette hook: with all three hooks
+ * set, this library runs NO transform-stage arithmetic on frame-level data. What stays on the host: the frame-level Palette
+ * when that hook is null, a Palette with predictor 6 whose weighted-predictor plane was not kept, and every transform of the
+ * per-group sub-streams (LF coefficients, HF metadata, quant tables, modular groups), which are small and sit inside entropy
+ * decoding. The VarDCT pipeline is not present here at all. Plain CPU code (g++), no GPU needed.
  */
 #ifndef JXLATTE_FRONTEND_H
 #define JXLATTE_FRONTEND_H
@@ -93,6 +96,13 @@ typedef struct jxf_hooks {
     int32_t (*squeeze)(void* user, const jxf_chan* in, int32_t n_in, const jxf_squeeze_step* steps, int32_t n_steps,
                        jxf_chan* out, int32_t n_out);
     int32_t (*rct)(void* user, int32_t* v0, int32_t* v1, int32_t* v2, int64_t n, int32_t rct_type);
+    /* palette: one Palette transform (ModularStream.java:327-378) of the frame-level stream. index = height x width indices,
+     *          palette = the stream's channel 0 (pal_h x pal_w; NULL when it is empty), pred = the weighted predictor's
+     *          values as decoded (height x width) or NULL, out[num_c] = the result planes (out[0] is index itself). Bind to
+     *          jxl_stage_palette. OPTIONAL, unlike the two above: NULL keeps the transform in this library. */
+    int32_t (*palette)(void* user, const int32_t* index, int32_t height, int32_t width, const int32_t* palette, int32_t pal_h,
+                       int32_t pal_w, const int32_t* pred, int32_t num_c, int32_t nb_colors, int32_t nb_deltas, int32_t d_pred,
+                       int32_t bit_depth, int32_t* const* out);
 } jxf_hooks;
 
 typedef struct jxf_lfgroup_view { /* one LF group: J/frame/group/LFGroup.java, LFCoefficients (integers), HFMetadata */

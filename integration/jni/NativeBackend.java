@@ -138,6 +138,10 @@ public final class NativeBackend implements AutoCloseable {
     public native void stageInvHSqueeze(ByteBuffer avg, int aw, ByteBuffer res, int rw, int h, ByteBuffer out); // jxl_stage_inv_hsqueeze
     public native void stageInvVSqueeze(ByteBuffer avg, int ah, ByteBuffer res, int rh, int w, ByteBuffer out); // jxl_stage_inv_vsqueeze
     public native void stageRct(ByteBuffer v0, ByteBuffer v1, ByteBuffer v2, long n, int rctType);    // jxl_stage_rct
+    // Palette branch of ModularStream.applyTransforms (ModularStream.java:327-378): params = {numC, nbColors, nbDeltas, dPred, bitDepth};
+    // index / pred (or null): height * width ints; palette: channel 0 of the stream (palH x palW); out: numC planes, out[0] may be index
+    public native void stagePalette(ByteBuffer index, int height, int width, ByteBuffer palette, int palH, int palW, ByteBuffer pred,
+                                    int[] params, ByteBuffer[] out);                                    // jxl_stage_palette
     public native void stageModularToFloat(ByteBuffer a, ByteBuffer b, long n, float scale, ByteBuffer out); // jxl_stage_modular_to_float
     public native void stageChromaUpsample(ByteBuffer in, int h, int w, int xShift, int yShift, ByteBuffer out); // jxl_stage_chroma_upsample
     /** JXLCodestreamDecoder.computePatches (:212-254) on host planes, in place, as one kernel launch: frame[d] direct buffers of

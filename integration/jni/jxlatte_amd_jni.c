@@ -1031,6 +1031,45 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageRct(JN
     CHECK(jxl_stage_rct(c, v, n, rctType));
 }
 
+/* Palette branch of ModularStream.applyTransforms (ModularStream.java:327-378; jxl_stage_palette). params = {numC, nbColors,
+ * nbDeltas, dPred, bitDepth}; index and pred (or null) hold height * width ints, palette palH * palW (null only when that is
+ * 0), out numC buffers of height * width ints each (out[0] may be index). Every size is checked against the buffers'
+ * capacities before the library sees a pointer. */
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stagePalette(JNIEnv* e, jobject self, jobject index, jint h, jint w,
+        jobject palette, jint palH, jint palW, jobject pred, jintArray params, jobjectArray out) {
+    jxl_ctx* c = ctx_of(e, self);
+    jint p[5];
+    if (!get_ints(e, params, 5, p)) return;
+    if (h < 1 || w < 1 || palH < 0 || palW < 0 || p[0] < 1) { bad_arg(e, "jxlatte_amd: palette geometry"); return; }
+    const jlong plane = 4 * area(h, w), pal = 4 * area(palH, palW);
+    NEED(index, plane);
+    NEED_OPT(pred, plane);
+    if (pal > 0) NEED(palette, pal);
+    if (!out || (*e)->GetArrayLength(e, out) < p[0]) { bad_arg(e, "jxlatte_amd: fewer output planes than numC"); return; }
+    int32_t** planes = (int32_t**)malloc(sizeof(int32_t*) * (size_t)p[0]);
+    if (!planes) {
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/OutOfMemoryError"), "jxlatte_amd: palette plane list");
+        return;
+    }
+    for (jint i = 0; i < p[0]; i++) {
+        jobject b = (*e)->GetObjectArrayElement(e, out, i);
+        if (!has_room(e, b, plane)) {
+            free(planes);
+            bad_arg(e, "jxlatte_amd: palette output plane missing or too small");
+            return;
+        }
+        planes[i] = (int32_t*)ADDR(b);
+    }
+    jxl_palette_desc d;
+    d.num_c = p[0]; d.nb_colors = p[1]; d.nb_deltas = p[2]; d.d_pred = p[3]; d.bit_depth = p[4];
+    d.pal_h = palH; d.pal_w = palW;
+    d.palette = pal > 0 ? (const int32_t*)ADDR(palette) : NULL;
+    d.pred = (const int32_t*)ADDR(pred);
+    const jxl_status st = jxl_stage_palette(c, &d, (const int32_t*)ADDR(index), h, w, planes);
+    free(planes);
+    CHECK(st);
+}
+
 JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageModularToFloat(JNIEnv* e, jobject self, jobject a, jobject b, jlong n,
         jfloat scale, jobject out) {
     jxl_ctx* c = ctx_of(e, self);

@@ -46,6 +46,9 @@ def parser():
                     help="the reference's --draw-varblocks: tint every varblock of a VarDCT frame by its transform type and blacken "
                          "its top row and left column (Frame.drawVarblocks as one device pass: jxl_planes_varblocks on planes "
                          "that are on the device, jxl_stage_varblocks otherwise)")
+    ap.add_argument("--device-palette", action="store_true",
+                    help="undo the Palette transforms of the frame-level Modular stream on the device (JXLDecoder device_palette; "
+                         "jxl_stage_palette) instead of in the front-end's loop; the same samples")
     return ap
 
 
@@ -72,7 +75,7 @@ def main(argv=None):
     backend = DeviceBackend(a.device)
     dec = JXLDecoder(a.input, backend=backend, sparse_coeffs=a.sparse_coeffs, device_splines=a.device_splines,
                      device_patches=a.device_patches, device_output=a.device_png, device_canvas=a.device_canvas,
-                     draw_varblocks=a.draw_varblocks)
+                     draw_varblocks=a.draw_varblocks, device_palette=a.device_palette)
     image = dec.decode()
     if image is None:
         print("jxlatte_amd: no frames", file=sys.stderr)

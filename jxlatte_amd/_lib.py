@@ -123,6 +123,7 @@ SIGNATURES = {
     "jxl_stage_inv_hsqueeze": (i32, [vp, pi, i32, pi, i32, i32, pi]),
     "jxl_stage_inv_vsqueeze": (i32, [vp, pi, i32, pi, i32, i32, pi]),
     "jxl_stage_rct": (i32, [vp, pi3, i64, i32]),
+    "jxl_stage_palette": (i32, [vp, C.POINTER(abi.PaletteDesc), pi, i32, i32, C.POINTER(pi)]),
     "jxl_stage_modular_to_float": (i32, [vp, pi, pi, i64, f32, pf]),
     "jxl_stage_chroma_upsample": (i32, [vp, pf, i32, i32, i32, i32, pf]),
     "jxl_upsampling_weights": (i32, [i32, pf, pf]),

@@ -207,6 +207,27 @@ def make_varblock_desc(blocks, cells):
     return d, b
 
 
+class PaletteDesc(C.Structure):
+    """struct jxl_palette_desc"""
+    _fields_ = [("num_c", C.c_int32), ("nb_colors", C.c_int32), ("nb_deltas", C.c_int32), ("d_pred", C.c_int32),
+                ("bit_depth", C.c_int32), ("pal_h", C.c_int32), ("pal_w", C.c_int32), ("palette", C.POINTER(C.c_int32)),
+                ("pred", C.POINTER(C.c_int32))]
+
+
+def make_palette_desc(palette, pred, num_c, nb_colors, nb_deltas, d_pred, bit_depth):
+    """palette: the 2-D palette channel; pred: the weighted predictor's plane or None. Returns (desc, keep): `keep` owns the
+    memory the descriptor points into"""
+    pal = np.ascontiguousarray(palette, np.int32)
+    assert pal.ndim == 2, pal.shape
+    pr = np.ascontiguousarray(pred, np.int32) if pred is not None else None
+    d = PaletteDesc()
+    d.num_c, d.nb_colors, d.nb_deltas, d.d_pred, d.bit_depth = int(num_c), int(nb_colors), int(nb_deltas), int(d_pred), int(bit_depth)
+    d.pal_h, d.pal_w = pal.shape
+    d.palette = iptr(pal) if pal.size else None
+    d.pred = iptr(pr) if pr is not None else None
+    return d, (pal, pr)
+
+
 class SplineDesc(C.Structure):
     """struct jxl_spline_desc (SplinesBundle.java + the two LFChannelCorrelation factors)"""
     _fields_ = [("quant_adjust", C.c_int32), ("n_splines", C.c_int32), ("n_control", C.POINTER(C.c_int32)),

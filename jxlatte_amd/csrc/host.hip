@@ -5,6 +5,8 @@
 #include "modular_tend.h"  // kSqueezeSafeIn (jxl_modular_begin picks the plan by it)
 #include "pfm_check.h"     // what the PFM entries refuse
 #include "varblock_check.h"  // what the varblock entries refuse, their cell map and factor table
+#include "palette_check.h"   // what jxl_stage_palette refuses
+#include "palette_ops.h"     // palette_pred_is_local: which predictors need the chain kernel
 
 #include <algorithm>
 #include <chrono>
@@ -198,6 +200,10 @@ struct jxl_ctx {
     // three-iteration pair; per launch restore_fused_variant() | kRestoreTiledBit | kRestoreBatchBit
     int last_restore_n = 0;
     int32_t last_restore_code[2] = {0, 0};
+    // the last jxl_stage_palette that ran (jxl_debug_last_palette): its kernel launches (1, or 2 with the chain kernel) and its
+    // pixels with index < nb_deltas
+    int last_palette_launches = 0;
+    int64_t last_palette_deltas = 0;
     uint64_t tables_gen = 0;  // bumped whenever finalize_tables rebuilds the binned work (batch argument cache key)
     // jxl_vardct_run_batch state (kept by the first context of a batch)
     DevBuf batch_restore_args;
@@ -1301,6 +1307,14 @@ extern "C" int jxl_debug_last_restore_launches(const jxl_ctx* c, int32_t codes[2
     if (!c) return 0;
     for (int i = 0; i < 2 && codes; i++) codes[i] = i < c->last_restore_n ? c->last_restore_code[i] : 0;
     return c->last_restore_n;
+}
+// Test hook (tests/test_palette_gpu.py) and the decoder's statistics: the kernel launches of the context's last jxl_stage_palette
+// that ran (0: none yet; 1: the lookup kernel alone; 2: the chain kernel behind it) and its pixels with index < nb_deltas. Not
+// part of the C-ABI of include/jxlatte_amd.h.
+extern "C" int jxl_debug_last_palette(const jxl_ctx* c, int64_t* delta_pixels) {
+    if (!c) return 0;
+    if (delta_pixels) *delta_pixels = c->last_palette_deltas;
+    return c->last_palette_launches;
 }
 extern "C" int jxl_debug_clock_probe(int device, double us, double* mhz) {
     static hipStream_t s = nullptr;
@@ -3799,6 +3813,55 @@ jxl_status jxl_stage_rct(jxl_ctx* c, int32_t* const v[3], int64_t n, int32_t rct
     const int perm = rct_type / 7;
     for (int j = 0; j < 3; j++)  // channels.set(start + permutationLut[permutation][j], v[j])
         HIP_TRY(c, hipMemcpy(v[kPermutationLut[perm][j]], d[j], 4 * (size_t)n, hipMemcpyDeviceToHost));
+    return JXL_OK;
+}
+
+// Palette branch of ModularStream.applyTransforms (ModularStream.java:327-378; k_palette.hip)
+jxl_status jxl_stage_palette(jxl_ctx* c, const jxl_palette_desc* d, const int32_t* index, int32_t height, int32_t width,
+                             int32_t* const* out) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    const char* bad = palette_check(d, index, height, width, out);
+    if (bad) return fail(c, JXL_ERR_INVALID_ARGUMENT, "%s", bad);
+    const size_t n = (size_t)height * width;
+    PaletteArgs a;
+    a.plane_stride = (int64_t)((n + 3) & ~(size_t)3);  // every plane starts 16-byte aligned
+    a.h = height;
+    a.w = width;
+    a.num_c = d->num_c;
+    a.nb_colors = d->nb_colors;
+    a.nb_deltas = d->nb_deltas;
+    a.d_pred = d->d_pred;
+    a.bit_depth = d->bit_depth;
+    Tmp t;
+    const size_t entries = (size_t)d->num_c * d->nb_colors;
+    int32_t* dpal = t.up<int32_t>(nullptr, entries);
+    int32_t* dout = t.up<int32_t>(nullptr, (size_t)a.plane_stride * d->num_c);
+    a.delta_count = t.up<unsigned int>(nullptr, 1);
+    a.index = t.up(index, n);
+    a.pred = d->d_pred == 6 && d->pred ? t.up(d->pred, n) : nullptr;
+    if (!dpal || !dout || !a.delta_count || !a.index || (d->d_pred == 6 && d->pred && !a.pred))
+        return fail(c, JXL_ERR_OOM, "device allocation failed");
+    if (entries)  // the first num_c rows of the palette channel, nb_colors of each, back to back
+        HIP_TRY(c, hipMemcpy2D(dpal, sizeof(int32_t) * d->nb_colors, d->palette, sizeof(int32_t) * d->pal_w, sizeof(int32_t) * d->nb_colors,
+                               d->num_c, hipMemcpyHostToDevice));
+    a.palette = dpal;
+    a.out = dout;
+    HIP_TRY(c, hipMemsetAsync(a.delta_count, 0, sizeof(unsigned int), c->stream));
+    launch_palette_lookup(a, c->stream);
+    unsigned int deltas = 0;
+    HIP_TRY(c, hipMemcpyAsync(&deltas, a.delta_count, sizeof deltas, hipMemcpyDeviceToHost, c->stream));
+    if ((st = finish(c))) return st;
+    int launches = 1;
+    if (deltas && !palette_pred_is_local(d->d_pred)) {
+        launch_palette_chain(a, c->stream);
+        if ((st = finish(c))) return st;
+        launches = 2;
+    }
+    for (int i = 0; i < d->num_c; i++)
+        HIP_TRY(c, hipMemcpy(out[i], dout + (size_t)i * a.plane_stride, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    c->last_palette_launches = launches;
+    c->last_palette_deltas = (int64_t)deltas;
     return JXL_OK;
 }
 

@@ -262,6 +262,22 @@ struct VarblockArgs {
     const float* factors;  // 27 x 3: rFactor, gFactor, bFactor per type
 };
 void launch_varblocks(const VarblockArgs& p, hipStream_t s);
+// The inverse Palette transform (ModularStream.java:327-378) on device planes (k_palette.hip); the arithmetic is palette_ops.h's,
+// the checks palette_check.h's
+constexpr int kPaletteLdsInts = 8192;      // a palette of at most this many entries (num_c * nb_colors) is staged in LDS: 32 KiB
+constexpr int kPaletteChainThreads = 256;  // k_palette_chain's workgroup: that many rows of one t-front per pass
+struct PaletteArgs {
+    const int32_t* index;     // h * w
+    const int32_t* palette;   // num_c rows of nb_colors, back to back
+    const int32_t* pred;      // h * w, or null
+    int32_t* out;             // num_c planes, plane_stride apart
+    int64_t plane_stride;     // >= h * w, a multiple of 4
+    int h, w;
+    int num_c, nb_colors, nb_deltas, d_pred, bit_depth;
+    unsigned int* delta_count;  // += the pixels with index < nb_deltas (zeroed by the caller)
+};
+void launch_palette_lookup(const PaletteArgs& p, hipStream_t s);
+void launch_palette_chain(const PaletteArgs& p, hipStream_t s);  // only where d_pred is neither 0 nor 6 and the count is not 0
 // PQ as a table of quadratic segments (jxl_fastpow.h): kPqTableFloats floats = float4 {a0 hi, a0 lo, a1, a2} per segment
 constexpr int kPqTableFloats = (129 - 87) * 128 * 4;
 void build_pq_table(float* out /* [kPqTableFloats] */);

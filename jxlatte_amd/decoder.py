@@ -634,6 +634,7 @@ class DeviceBackend:
         from . import _lib, host
         self.host = host
         self.ctx = _lib.Context(device)
+        self.palette_log = []
 
     def close(self):
         self.ctx.close()
@@ -682,6 +683,13 @@ class DeviceBackend:
 
     def rct(self, a, b, c, rct_type):
         return self.host.rct(self.ctx, np.stack([a, b, c]), rct_type)
+
+    def palette(self, index, palette, pred, num_c, nb_colors, nb_deltas, d_pred, bit_depth):
+        """one frame-level Palette transform (jxl_stage_palette); what it took is appended to self.palette_log"""
+        out = self.host.inversePalette(self.ctx, index, palette, num_c, nb_colors, nb_deltas, d_pred, bit_depth, pred=pred)
+        launches, deltas = self.host.lastPalette(self.ctx)
+        self.__dict__.setdefault("palette_log", []).append(dict(num_c=int(num_c), nb_colors=int(nb_colors), delta_pixels=deltas, launches=launches))
+        return out
 
     def modular_to_float(self, a, b, scale):
         return self.host.modularToFloat(self.ctx, a, b, scale)
@@ -974,7 +982,7 @@ def _tt_dims():
 
 class JXLDecoder:
     def __init__(self, source, backend=None, sparse_coeffs=False, device_splines=False, device_patches=False, device_output=False,
-                 device_canvas=False, draw_varblocks=False):
+                 device_canvas=False, draw_varblocks=False, device_palette=False):
         """sparse_coeffs: hand the HF coefficients to the backend as lists of non-zero entries (jxf_get_coeffs_sparse ->
         jxl_vardct_put_group_sparse), not as dense planes; same pixels.
         device_splines: Frame.renderSplines runs in the backend (jxl_planes_splines on the resident planes, jxl_stage_splines
@@ -1006,7 +1014,13 @@ class JXLDecoder:
         backend.varblocks on the host planes otherwise; there is no host restatement, and a backend without `varblocks` is an
         error. Modular frames are left alone. stats[k]["varblocks"] then says "device planes" or "host planes" (the type
         histogram it holds without the switch moves to stats[k]["varblock_types"]). A frame of several LF groups whose group
-        size is not 256 raises UnsupportedOperationException: the reference's hard-coded << 11 leaves the frame there."""
+        size is not 256 raises UnsupportedOperationException: the reference's hard-coded << 11 leaves the frame there.
+        device_palette: the Palette transforms of the frame-level Modular stream (ModularStream.java:327-378) run in the backend
+        (backend.palette: jxl_stage_palette, one call per transform) instead of the front-end's loop; the same samples. The
+        palettes of the per-group sub-streams stay in the front-end, and so does a palette with predictor 6 whose weighted
+        predictor's plane was not kept. stats[k]["palette"] lists, per transform in the order they were undone, dict(num_c,
+        nb_colors, delta_pixels, launches); it is [] for a frame without one. A backend without `palette` is an error."""
+        self.device_palette = bool(device_palette)
         self.draw_varblocks = bool(draw_varblocks)
         self.device_output = bool(device_output)
         self.device_canvas = bool(device_canvas)
@@ -1563,8 +1577,14 @@ class JXLDecoder:
             self.canvas = [None] * (colors_img + info.num_extra)
         produced = False
         while True:
+            dev_palette = getattr(self, "device_palette", False)
+            if dev_palette:
+                if not hasattr(be, "palette"):
+                    raise RuntimeError("device_palette needs a backend with `palette`")
+                if hasattr(be, "palette_log"):
+                    del be.palette_log[:]
             try:
-                fr = self.fe.next_frame(be.squeeze, be.rct)
+                fr = self.fe.next_frame(be.squeeze, be.rct, be.palette if dev_palette else None)
             except frontend.FrontendError as e:
                 raise self._map(e)
             if fr is None:
@@ -1573,6 +1593,8 @@ class JXLDecoder:
             self.frames_decoded += 1
             self.stats.append(dict(encoding="vardct" if fr.encoding == VARDCT else "modular", width=fr.width, height=fr.height,
                                    groups=fr.num_groups, passes=fr.num_passes))
+            if dev_palette:
+                self.stats[-1]["palette"] = [dict(e) for e in getattr(be, "palette_log", [])]
             bus0 = tuple(getattr(getattr(be, "ctx", None), "blend_bus", (0, 0)))  # (host._bus: what the blend path moves)
             if fr.flags & FLAG_USE_LF_FRAME and self.lfBuffer[fr.lf_level] is None:
                 raise InvalidBitstreamException("LF Level too large")  # JXLCodestreamDecoder.java:613-614

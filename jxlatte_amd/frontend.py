@@ -1,7 +1,8 @@
 """ctypes binding of libjxlatte_frontend.so (include/jxlatte_frontend.h): the host-side JPEG XL bitstream front-end.
 
 Row f2 of the scope table: what the Java host does before the transform stage (container, headers, entropy decoding,
-MA trees, TOC sections). CPU code, no GPU needed; the frame-level inverse Squeeze / RCT are delegated through hooks."""
+MA trees, TOC sections). CPU code, no GPU needed; the frame-level inverse Squeeze / RCT are delegated through hooks, and so is
+the frame-level inverse Palette where the caller gives a hook for it."""
 import ctypes as C
 import os
 import subprocess
@@ -59,10 +60,12 @@ class SqueezeStep(C.Structure):
 
 SQUEEZE_CB = C.CFUNCTYPE(i32, C.c_void_p, C.POINTER(Chan), i32, C.POINTER(SqueezeStep), i32, C.POINTER(Chan), i32)
 RCT_CB = C.CFUNCTYPE(i32, C.c_void_p, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.c_int64, i32)
+PALETTE_CB = C.CFUNCTYPE(i32, C.c_void_p, C.POINTER(i32), i32, i32, C.POINTER(i32), i32, i32, C.POINTER(i32), i32, i32, i32, i32, i32,
+                         C.POINTER(C.POINTER(i32)))
 
 
 class Hooks(C.Structure):
-    _fields_ = [("user", C.c_void_p), ("squeeze", SQUEEZE_CB), ("rct", RCT_CB)]
+    _fields_ = [("user", C.c_void_p), ("squeeze", SQUEEZE_CB), ("rct", RCT_CB), ("palette", PALETTE_CB)]
 
 
 class LFGroupView(C.Structure):
@@ -183,9 +186,11 @@ class Frontend:
         n = self._check(self.lib.jxf_get_up_weights(self.h, k_index, out, 210))
         return np.array(out[:n], np.float32)
 
-    def next_frame(self, squeeze=None, rct=None):
-        """squeeze(in_channels, steps, out_shapes) -> list of out arrays; rct(v0, v1, v2, rct_type) -> (o0, o1, o2).
-        Both operate on numpy int32 arrays; results are copied back into the front-end's buffers."""
+    def next_frame(self, squeeze=None, rct=None, palette=None):
+        """squeeze(in_channels, steps, out_shapes) -> list of out arrays; rct(v0, v1, v2, rct_type) -> (o0, o1, o2);
+        palette(index, palette, pred, num_c, nb_colors, nb_deltas, d_pred, bit_depth) -> num_c arrays of index's shape (index:
+        h x w, palette: the stream's channel 0, pred: the weighted predictor's h x w values or None). All operate on numpy int32
+        arrays; results are copied back into the front-end's buffers. Without `palette` the front-end's own loop runs."""
         def sq_cb(_user, cin, n_in, steps, n_steps, cout, n_out):
             try:
                 ins = [_np(cin[i].data, (cin[i].h, cin[i].w)) for i in range(n_in)]
@@ -215,8 +220,23 @@ class Frontend:
                 self._hook_error = e
                 return -4
 
+        def pal_cb(_user, index, h, w, pal, pal_h, pal_w, pred, num_c, nb_colors, nb_deltas, d_pred, bit_depth, out):
+            try:
+                outs = palette(_np(index, (h, w)), _np(pal, (pal_h, pal_w)), _np(pred, (h, w)) if pred else None, num_c, nb_colors,
+                               nb_deltas, d_pred, bit_depth)
+                assert len(outs) == num_c, (len(outs), num_c)
+                for c in range(num_c):
+                    a = np.ascontiguousarray(outs[c], np.int32)
+                    assert a.shape == (h, w), (a.shape, (h, w))
+                    C.memmove(out[c], a.ctypes.data, a.nbytes)
+                return 0
+            except Exception as e:  # noqa: BLE001
+                self._hook_error = e
+                return -4
+
         self._hook_error = None
         hooks = Hooks()
+        hooks.palette = PALETTE_CB(pal_cb) if palette else PALETTE_CB()
         hooks.squeeze = SQUEEZE_CB(sq_cb) if squeeze else SQUEEZE_CB()
         hooks.rct = RCT_CB(rct_cb) if rct else RCT_CB()
         self._hooks = hooks

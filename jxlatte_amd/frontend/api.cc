@@ -141,6 +141,18 @@ bool rct_hook(void* user, Channel* v[3], int rct_type) {
     return true;
 }
 
+bool palette_hook(void* user, const Channel& pal, const Transform& t, int bit_depth, Channel* out) {
+    HookCtx* hc = (HookCtx*)user;
+    std::vector<int32_t*> planes((size_t)t.num_c);
+    for (int c = 0; c < t.num_c; c++) planes[(size_t)c] = out[c].buf.data();
+    const Channel& index = out[0];
+    const int32_t rc = hc->h->palette(hc->h->user, index.buf.data(), index.h, index.w, pal.buf.empty() ? nullptr : pal.buf.data(), pal.h, pal.w,
+                                      index.pred.empty() ? nullptr : index.pred.data(), t.num_c, t.nb_colors, t.nb_deltas, t.d_pred, bit_depth,
+                                      planes.data());
+    if (rc != 0) throw std::runtime_error("palette hook failed with status " + std::to_string(rc));
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -222,6 +234,7 @@ int32_t jxf_next_frame(jxf_dec* d, const jxf_hooks* hooks) {
         th.required = true;
         th.squeeze = squeeze_hook;
         th.rct = rct_hook;
+        if (hooks && hooks->palette) th.palette = palette_hook;  // optional: without it the front-end's own loop runs
         f.decode(d->br, &th);
         if (f.fh.is_last) d->done = true;
         return JXF_OK;

@@ -592,7 +592,15 @@ void ModularStream::apply_transforms(const TransformHooks* hooks) {  // ModularS
             const int bd = bit_depth_;
             const Channel& fc = channels[first];
             const int H = fc.h, W = fc.w;
-            for (int c = 0; c < t.num_c; c++) {
+            // the sample work through the hook where there is one (a null hook is no error: the loop below then runs, as it does
+            // for every sub-stream); d_pred 6 without the weighted predictor's plane stays here too, the device entry refuses it
+            const bool hooked = hooks && hooks->palette && H > 0 && W > 0 && t.num_c > 0 && pal.buf.size() == (size_t)pal.w * pal.h &&
+                                !(t.d_pred == 6 && t.nb_deltas > 0 && fc.pred.empty());
+            if (hooked) {
+                for (int c = 0; c < t.num_c; c++) channels[first + c].allocate();
+                if (!hooks->palette(hooks->user, pal, t, bd, &channels[first])) throw std::logic_error("palette hook declined");
+            }
+            for (int c = 0; c < t.num_c && !hooked; c++) {
                 Channel& ch = channels[first + c];
                 ch.allocate();
                 const Nb nb{ch.buf.data(), ch.w};

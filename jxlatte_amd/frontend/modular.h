@@ -4,7 +4,8 @@
 //
 // Inverse squeeze / RCT of the FRAME-LEVEL stream are the hot path: ModularStream::apply_transforms takes hooks so the
 // caller routes them to the device library (jxl_modular_apply / jxl_stage_rct); the built-in CPU versions serve the small
-// side streams (LF coefficients, HF metadata, raw quant tables) exactly as the Java host does.
+// side streams (LF coefficients, HF metadata, raw quant tables) exactly as the Java host does. The frame-level inverse Palette
+// goes the same way where the caller gives a palette hook (jxl_stage_palette), and runs here where it gives none.
 #pragma once
 #include <cstdint>
 #include <memory>
@@ -71,6 +72,10 @@ struct TransformHooks {
     // one Squeeze transform (all of its steps, already in application order): avg / residual channels in, merged out
     bool (*squeeze)(void* user, std::vector<Channel>& channels, const std::vector<SqueezeStep>& steps) = nullptr;
     bool (*rct)(void* user, Channel* v[3], int rct_type) = nullptr;
+    // one Palette transform's sample work (ModularStream.java:337-372): out[0 .. t.num_c) are copies of the index channel (allocated,
+    // out[0] IS the index channel) and receive the colours; pal = the stream's channel 0. Optional: without it, or for a stream
+    // decoded without hooks, apply_transforms runs its own loop -- `required` does not cover it
+    bool (*palette)(void* user, const Channel& pal, const Transform& t, int bit_depth, Channel* out) = nullptr;
 };
 
 class ModularStream {

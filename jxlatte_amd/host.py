@@ -806,6 +806,29 @@ def rct(ctx, v, rctType):
     return out
 
 
+def inversePalette(ctx, index, palette, numC, nbColors, nbDeltas, dPred, bitDepth, pred=None):
+    """Palette branch of ModularStream.applyTransforms (ModularStream.java:327-378) for one transform (jxl_stage_palette):
+    index is the h x w index channel, palette the stream's channel 0 (2-D), pred the weighted predictor's values as decoded
+    (read for dPred 6). Returns the numC planes as one (numC, h, w) array"""
+    idx = np.ascontiguousarray(index, np.int32)
+    h, w = idx.shape
+    d, keep = abi.make_palette_desc(palette, pred, numC, nbColors, nbDeltas, dPred, bitDepth)
+    out = np.empty((max(int(numC), 0), h, w), np.int32)
+    pp = (C.POINTER(C.c_int32) * max(len(out), 1))(*[abi.iptr(a) for a in out])
+    ctx.call("jxl_stage_palette", C.byref(d), abi.iptr(idx), h, w, pp)
+    return out
+
+
+def lastPalette(ctx):
+    """(kernel launches, pixels with index < nbDeltas) of the context's last inversePalette that ran
+    (jxl_debug_last_palette, a test hook outside the C-ABI): one launch, or two with the chain kernel behind the lookup"""
+    fn = ctx.lib.jxl_debug_last_palette
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]
+    deltas = C.c_int64(0)
+    n = fn(ctx.h, C.byref(deltas))
+    return int(n), int(deltas.value)
+
+
 def modularToFloat(ctx, a, b, scale):
     """Frame.decodeFrame modular -> float buffer (Frame.java:437-448)"""
     a = np.ascontiguousarray(a, np.int32)
