@@ -734,6 +734,31 @@ jxl_status jxl_canvas_to_planes(jxl_ctx* ctx, int32_t id);
  * patchStart, :390). ref: NULL when d->ref is -1; the canvas' own shape when d->ref == d->canvas. */
 jxl_status jxl_canvas_blend_check(const jxl_canvas_blend_desc* d, const jxl_canvas_shape* canvas, const jxl_canvas_shape* frame,
                                   const jxl_canvas_shape* ref);
+/* The Modular context's result channels as a new plane set: Frame.decodeFrame's modular -> buffer loop (Frame.java:430-455) for
+ * all output planes as ONE launch. Plane i is result channel plane[i].channel (jxl_modular_out_shape's index) cropped to height x
+ * width -- the frame's bounds; the source pitch is the channel's own width -- and either copied as int32 samples
+ * (JXL_PLANE_INT32) or made float as jxl_stage_modular_to_float makes it (JXL_PLANE_FLOAT): scale * (float)(a [+ b]), the sum
+ * in Java int arithmetic (wrapping), the conversion rounded first, then one f32 multiply. The XYB rule (Y, X, B - Y -> X, Y, B
+ * with lfDequant) is the caller's choice of channel, add_channel and scale. The plan is settled first, as
+ * jxl_modular_read_channel settles it; the set owns a copy (the result channels die with the next jxl_modular_begin). */
+typedef struct jxl_modular_plane {
+    int32_t channel;      /* index into the Modular context's result list */
+    int32_t add_channel;  /* -1, or a second channel added first (Java int add, wrapping) */
+    int32_t type;         /* JXL_PLANE_INT32: copy; JXL_PLANE_FLOAT: scale * (float)v */
+    float   scale;
+} jxl_modular_plane;
+typedef struct jxl_modular_planes_desc {
+    int32_t height, width, n_planes;   /* the frame's bounds; every named channel is at least that large */
+    jxl_modular_plane plane[JXL_CANVAS_MAX_PLANES];
+} jxl_modular_planes_desc;
+/* Refused with nothing queued and *id untouched: no plan has run since jxl_modular_begin (JXL_ERR_STATE); more than
+ * JXL_CANVAS_MAX_PLANES planes (JXL_ERR_UNSUPPORTED); JXL_ERR_INVALID_ARGUMENT for n_planes or a size below 1, a channel index
+ * outside the result list, a channel smaller than the bounds, an add_channel on an int32 plane or of another size than its
+ * channel, a type other than the two. */
+jxl_status jxl_canvas_from_modular(jxl_ctx* ctx, const jxl_modular_planes_desc* d, int32_t* id);
+/* jxl_stage_orient of every plane of the set, whatever its type (the kernels move 4-byte words); orientations 5-8 exchange the
+ * set's height and width. JXL_ERR_STATE: an orientation outside 1..8, as jxl_planes_orient. */
+jxl_status jxl_canvas_orient(jxl_ctx* ctx, int32_t id, int32_t orientation);
 
 /* JXLCodestreamDecoder.transposeBufferFloat / transposeBufferInt (:43-177): EXIF orientation 1..8 of one plane of
  * 4-byte samples. out is h x w for orientation <= 4, else w x h. */
@@ -787,6 +812,14 @@ jxl_status jxl_planes_color_peak(jxl_ctx* ctx, const jxl_color_params* p, float*
 /* jxl_stage_orient of the three resident planes, on the device; orientations 5-8 exchange the planes' height and width.
  * JXL_ERR_STATE: no resident planes, or an orientation outside 1..8. */
 jxl_status jxl_planes_orient(jxl_ctx* ctx, int32_t orientation);
+/* jxl_stage_png_samples with the colour planes 0 .. color.n_planes - 1 and the alpha plane (alpha_plane, -1: none) taken from
+ * the plane set `id`: nothing goes up, only the PNG's samples come down. color.n_planes is 1 or 3 and no more than the set
+ * holds; color.in_is_int must equal the tag of every colour plane, alpha_is_int that of the alpha plane, has_alpha must say
+ * whether alpha_plane names one, and height and width are the set's -- else JXL_ERR_INVALID_ARGUMENT. Everything
+ * jxl_stage_png_samples refuses is refused here, with out untouched. */
+jxl_status jxl_canvas_png_samples(jxl_ctx* ctx, int32_t id, int32_t alpha_plane, const jxl_png_params* p, void* out);
+/* jxl_stage_color_peak on planes 0 .. p->n_planes - 1 of the set (in_is_int must equal their tags) */
+jxl_status jxl_canvas_color_peak(jxl_ctx* ctx, int32_t id, const jxl_color_params* p, float* peak);
 
 /* ---- the PFM's samples in one pass: replaces the body of PFMWriter.write (PFMWriter.java:30-48) after the header ----
  * The planes are the image's own samples (image.getBuffer(false), :30): no colour transform, no peak scale, no transfer
@@ -809,6 +842,9 @@ jxl_status jxl_stage_pfm_samples(jxl_ctx* ctx, const void* const in[3], const jx
  * and width theirs -- anything else is JXL_ERR_INVALID_ARGUMENT. out is filled on return: the only bytes that cross the bus are
  * the PFM's (PFMWriter.java:30-48 without image.getBuffer). JXL_ERR_STATE without resident planes. */
 jxl_status jxl_planes_pfm_samples(jxl_ctx* ctx, const jxl_pfm_params* p, void* out);
+/* The same launch on planes 0 .. n_planes - 1 of the plane set `id`: is_int[c] must equal the planes' tags and height and width
+ * the set's (JXL_ERR_INVALID_ARGUMENT otherwise, and for everything jxl_stage_pfm_samples refuses; out untouched). */
+jxl_status jxl_canvas_pfm_samples(jxl_ctx* ctx, int32_t id, const jxl_pfm_params* p, void* out);
 
 /* ---- the varblock map drawn onto the picture: replaces Frame.drawVarblocks (Frame.java:464-503), which
  * JXLCodestreamDecoder.java:638-639 calls right after performColorTransforms when JXLOptions.renderVarblocks is set ----

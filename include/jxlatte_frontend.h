@@ -177,8 +177,35 @@ int32_t jxf_get_patch(const jxf_dec* d, int32_t index, jxf_patch_view* out);
 /* number of splines of the current frame, and one of them */
 int32_t jxf_num_splines(const jxf_dec* d);
 int32_t jxf_get_spline(const jxf_dec* d, int32_t index, jxf_spline_view* out);
-/* channel i of the frame-level modular stream after its inverse transforms */
+/* channel i of the frame-level modular stream after its inverse transforms -- of the ENCODED channel list, meta channels
+ * included, while the transforms are pending (jxf_set_defer_transforms) */
 int32_t jxf_get_modular_channel(const jxf_dec* d, int32_t index, jxf_chan* out);
+
+/* ---- deferred frame-level transforms: the caller undoes them itself (on the device, where the result may stay) ----
+ * on != 0: frames decoded from now on leave the inverse transforms of the FRAME-LEVEL stream undone; per-group and other
+ * sub-streams are untouched. The list is still walked over the channels' shapes at decode time, and a chain the front-end's own
+ * loop refuses ("RCT channel range", "RCT must be performed on three equal size channels", "Palette channel range") is refused
+ * by jxf_next_frame with the same error. Default off: jxf_next_frame then behaves exactly as before. */
+int32_t jxf_set_defer_transforms(jxf_dec* d, int32_t on);
+#define JXF_TRANSFORM_RCT 0
+#define JXF_TRANSFORM_PALETTE 1
+#define JXF_TRANSFORM_SQUEEZE 2
+typedef struct jxf_transform_view { /* J/frame/modular/TransformInfo.java */
+    int32_t kind; /* JXF_TRANSFORM_* */
+    int32_t begin_c, num_c, rct_type, nb_colors, nb_deltas, d_pred;
+    int32_t n_steps;               /* Squeeze: the expanded list the squeeze hook gets (the default plan where none is coded) */
+    const jxf_squeeze_step* steps; /* valid until the next jxf_get_transform */
+} jxf_transform_view;
+/* the current frame's frame-level transform list, in bitstream order (the inverse runs last to first); deferring or not */
+int32_t jxf_get_transform_count(const jxf_dec* d);
+int32_t jxf_get_transform(const jxf_dec* d, int32_t index, jxf_transform_view* out);
+/* 1 while the current frame's transforms are pending */
+int32_t jxf_transforms_pending(const jxf_dec* d);
+/* channels jxf_get_modular_channel answers for now (equals jxf_frame_info.num_modular_channels) */
+int32_t jxf_modular_channel_count(const jxf_dec* d);
+/* Runs the pending transforms exactly as jxf_next_frame would have, through the same hooks. Idempotent: a second call, or a
+ * call on a frame decoded without deferring, does nothing. Afterwards jxf_get_modular_channel means what it means by default. */
+int32_t jxf_apply_transforms(jxf_dec* d, const jxf_hooks* hooks);
 
 #ifdef __cplusplus
 }

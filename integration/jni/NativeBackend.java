@@ -198,6 +198,13 @@ public final class NativeBackend implements AutoCloseable {
     /** desc: {canvas, frame, ref, nChan, rect[8] as stageBlend's, then per channel {framePlane, mode, flags, frameAlpha, refAlpha}}. */
     public native void canvasBlend(int[] desc);                    // jxl_canvas_blend
     public native void canvasToPlanes(int id);                     // jxl_canvas_to_planes
+    /** desc: {height, width, nPlanes, then per plane {channel, addChannel (-1: none), type}}; scales: one float per plane. */
+    public native int canvasFromModular(int[] desc, float[] scales);   // jxl_canvas_from_modular -> the new set's id
+    public native void canvasOrient(int id, int orientation);      // jxl_canvas_orient
+    // the writers on a set: params as the stage entries'; nothing goes up
+    public native void canvasPngSamples(int id, int alphaPlane, ByteBuffer params, ByteBuffer out);   // jxl_canvas_png_samples (alphaPlane -1: none)
+    public native float canvasColorPeak(int id, ByteBuffer params);                                   // jxl_canvas_color_peak
+    public native void canvasPfmSamples(int id, int[] params, ByteBuffer out);                        // jxl_canvas_pfm_samples (out: exactly 4 * n_planes * width * height bytes)
     /** shapes: {n, h, w, type[n]}; ref null when desc names no reference. Throws what canvasBlend would; no device needed. */
     public static native void canvasBlendCheck(int[] desc, int[] canvas, int[] frame, int[] ref);    // jxl_canvas_blend_check
 

@@ -1408,6 +1408,62 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasToPla
     CHECK(jxl_canvas_to_planes(c, id));
 }
 
+/* desc: {height, width, nPlanes, then per plane {channel, addChannel, type}}; scales: one float per plane */
+JNIEXPORT jint JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasFromModular(JNIEnv* e, jobject self, jintArray desc, jfloatArray scales) {
+    jxl_ctx* c = ctx_of(e, self);
+    jint head[3];
+    int32_t id = -1;
+    if (!get_ints(e, desc, 3, head)) return -1;
+    if (head[2] > JXL_CANVAS_MAX_PLANES) { rethrow(e, NULL, JXL_ERR_UNSUPPORTED); return -1; }
+    if (head[2] < 1) { bad_arg(e, "jxlatte_amd: modular planes: plane count"); return -1; }
+    jint all[3 + 3 * JXL_CANVAS_MAX_PLANES];
+    float sc[JXL_CANVAS_MAX_PLANES];
+    if (!get_ints(e, desc, 3 + 3 * head[2], all) || !get_floats(e, scales, head[2], sc)) return -1;
+    jxl_modular_planes_desc d;
+    memset(&d, 0, sizeof d);
+    d.height = all[0]; d.width = all[1]; d.n_planes = all[2];
+    for (int i = 0; i < d.n_planes; i++) {
+        const jint* v = all + 3 + 3 * i;
+        d.plane[i].channel = v[0]; d.plane[i].add_channel = v[1]; d.plane[i].type = v[2]; d.plane[i].scale = sc[i];
+    }
+    const jxl_status st = jxl_canvas_from_modular(c, &d, &id);
+    if (st != JXL_OK) { rethrow(e, c, st); return -1; }
+    return id;
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasOrient(JNIEnv* e, jobject self, jint id, jint orientation) {
+    jxl_ctx* c = ctx_of(e, self);
+    CHECK(jxl_canvas_orient(c, id, orientation));
+}
+
+/* the writers on a set: height and width must be the set's and the type flags its tags (the library checks) */
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasPngSamples(JNIEnv* e, jobject self, jint id, jint alphaPlane,
+        jobject params, jobject out) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_png_params p;
+    if (!png_params(e, params, &p)) return;
+    NEED(out, png_bytes(&p));
+    CHECK(jxl_canvas_png_samples(c, id, alphaPlane, &p, ADDR(out)));
+}
+
+JNIEXPORT jfloat JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasColorPeak(JNIEnv* e, jobject self, jint id, jobject params) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_color_params p;
+    float peak = 0.0f;
+    if (!color_params(e, params, &p)) return 0.0f;
+    jxl_status st = jxl_canvas_color_peak(c, id, &p, &peak);
+    if (st != JXL_OK) { rethrow(e, c, st); return 0.0f; }
+    return peak;
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasPfmSamples(JNIEnv* e, jobject self, jint id, jintArray params, jobject out) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_pfm_params p;
+    if (!pfm_params(e, params, &p)) return;
+    if (!pfm_out_fits(e, out, 4 * area(p.height, p.width) * p.n_planes)) return;
+    CHECK(jxl_canvas_pfm_samples(c, id, &p, ADDR(out)));
+}
+
 JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasBlendCheck(JNIEnv* e, jclass k, jintArray desc, jintArray canvas,
         jintArray frame, jintArray ref) {
     (void)k;

@@ -49,6 +49,11 @@ def parser():
     ap.add_argument("--device-palette", action="store_true",
                     help="undo the Palette transforms of the frame-level Modular stream on the device (JXLDecoder device_palette; "
                          "jxl_stage_palette) instead of in the front-end's loop; the same samples")
+    ap.add_argument("--device-image", action="store_true",
+                    help="back the decoded image by a device plane set, colours and extra channels of any type (JXLDecoder "
+                         "device_image): a Modular frame that is the whole image goes up once and stays (jxl_canvas_from_modular), "
+                         "and with --device-canvas the canvas set becomes the image; add --device-png so that the writers read "
+                         "the set and only the file's samples come down. The same bytes")
     return ap
 
 
@@ -75,7 +80,7 @@ def main(argv=None):
     backend = DeviceBackend(a.device)
     dec = JXLDecoder(a.input, backend=backend, sparse_coeffs=a.sparse_coeffs, device_splines=a.device_splines,
                      device_patches=a.device_patches, device_output=a.device_png, device_canvas=a.device_canvas,
-                     draw_varblocks=a.draw_varblocks, device_palette=a.device_palette)
+                     draw_varblocks=a.draw_varblocks, device_palette=a.device_palette, device_image=a.device_image)
     image = dec.decode()
     if image is None:
         print("jxlatte_amd: no frames", file=sys.stderr)
@@ -83,7 +88,8 @@ def main(argv=None):
     t1 = time.time()
     for i, st in enumerate(dec.stats):
         print("    frame %d: %s %dx%d, %d groups%s" % (i, st["encoding"], st["width"], st["height"], st["groups"],
-                                                       ", canvas %s" % st["canvas"] if a.device_canvas else ""), file=sys.stderr)
+                                                       (", canvas %s" % st["canvas"] if a.device_canvas else "") +
+                                                       (", image %s" % st["image"] if a.device_image else "")), file=sys.stderr)
     print("Decoded %dx%d in %.3f s" % (image.getWidth(), image.getHeight(), t1 - t0), file=sys.stderr)
     if a.output and output_format(a) == "pfm":
         with open(a.output, "wb") as f:

@@ -142,6 +142,11 @@ SIGNATURES = {
     "jxl_canvas_cast": (i32, [vp, i32, i32, i32]),
     "jxl_canvas_blend": (i32, [vp, C.POINTER(abi.CanvasBlendDesc)]),
     "jxl_canvas_to_planes": (i32, [vp, i32]),
+    "jxl_canvas_from_modular": (i32, [vp, C.POINTER(abi.ModularPlanesDesc), pi]),
+    "jxl_canvas_orient": (i32, [vp, i32, i32]),
+    "jxl_canvas_png_samples": (i32, [vp, i32, i32, C.POINTER(abi.PngParams), vp]),
+    "jxl_canvas_color_peak": (i32, [vp, i32, C.POINTER(abi.ColorParams), pf]),
+    "jxl_canvas_pfm_samples": (i32, [vp, i32, C.POINTER(abi.PfmParams), vp]),
     "jxl_canvas_blend_check": (i32, [C.POINTER(abi.CanvasBlendDesc), C.POINTER(abi.CanvasShape), C.POINTER(abi.CanvasShape),
                                      C.POINTER(abi.CanvasShape)]),
     "jxl_stage_orient": (i32, [vp, vp, i32, i32, i32, vp]),

@@ -164,6 +164,16 @@ class CanvasShape(C.Structure):
     _fields_ = [("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("types", C.c_int32 * CANVAS_MAX_PLANES)]
 
 
+class ModularPlane(C.Structure):
+    """struct jxl_modular_plane"""
+    _fields_ = [("channel", C.c_int32), ("add_channel", C.c_int32), ("type", C.c_int32), ("scale", C.c_float)]
+
+
+class ModularPlanesDesc(C.Structure):
+    """struct jxl_modular_planes_desc"""
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("n_planes", C.c_int32), ("plane", ModularPlane * CANVAS_MAX_PLANES)]
+
+
 class PackParams(C.Structure):
     """struct jxl_pack_params"""
     _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("n_color", C.c_int32), ("has_alpha", C.c_int32),

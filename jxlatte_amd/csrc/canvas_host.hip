@@ -6,6 +6,7 @@
 // stream first and are complete on return (the stream does not synchronise with the null stream).
 #include "jxl_internal.h"
 #include "canvas_check.h"
+#include "modplanes_check.h"
 #include "pfm_check.h"
 
 #include <new>
@@ -32,6 +33,17 @@ void canvas_store_free(CanvasStore* s) {
             delete k;
         }
     delete s;
+}
+
+bool canvas_view(const CanvasStore* s, int32_t id, CanvasView* out) {
+    const CanvasSet* k = (s && id >= 0 && (size_t)id < s->sets.size()) ? s->sets[(size_t)id] : nullptr;
+    if (!k) return false;
+    out->n = k->n, out->h = k->h, out->w = k->w;
+    for (int i = 0; i < JXL_CANVAS_MAX_PLANES; i++) {
+        out->type[i] = i < k->n ? k->type[i] : 0;
+        out->plane[i] = i < k->n ? k->plane(i) : nullptr;
+    }
+    return true;
 }
 
 namespace {
@@ -243,6 +255,76 @@ jxl_status jxl_canvas_blend(jxl_ctx* c, const jxl_canvas_blend_desc* d) {
     }
     launch_canvas_blend(a, l.stream);
     CV_HIP(c, hipGetLastError());
+    return JXL_OK;
+}
+
+jxl_status jxl_canvas_from_modular(jxl_ctx* c, const jxl_modular_planes_desc* d, int32_t* id) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    std::vector<ModResult> res;
+    bool ran = false;
+    if ((st = ctx_modular_out(c, &res, &ran))) return st;  // (settled: a speculative plan has been verified or redone)
+    ModPlaneShape shapes[64];
+    std::vector<ModPlaneShape> more;
+    ModPlaneShape* sh = shapes;
+    try {
+        if (res.size() > 64) more.resize(res.size()), sh = more.data();
+    } catch (const std::bad_alloc&) {
+        return ctx_fail(c, JXL_ERR_OOM, "canvas: host allocation failed");
+    }
+    for (size_t i = 0; i < res.size(); i++) sh[i] = ModPlaneShape{res[i].h, res[i].w};
+    const char* why = "";
+    if ((st = modplanes_check(d, sh, (int32_t)res.size(), ran, &why))) return ctx_fail(c, st, why);
+    if (!id) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: bad arguments");
+    int32_t types[JXL_CANVAS_MAX_PLANES];
+    for (int i = 0; i < d->n_planes; i++) types[i] = d->plane[i].type;
+    CanvasSet* k;
+    int32_t new_id = -1;
+    if ((st = new_set(c, l, d->n_planes, d->height, d->width, types, &k, &new_id))) return st;
+    ModPlanesArgs a{};
+    a.h = d->height, a.w = d->width, a.n = d->n_planes;
+    for (int i = 0; i < d->n_planes; i++) {
+        const jxl_modular_plane& p = d->plane[i];
+        ModPlane& q = a.p[i];
+        q.a = res[(size_t)p.channel].d;
+        q.b = p.add_channel >= 0 ? res[(size_t)p.add_channel].d : nullptr;
+        q.out = k->plane(i);
+        q.pitch = res[(size_t)p.channel].w;
+        q.is_float = p.type == JXL_PLANE_FLOAT ? 1 : 0;
+        q.scale = p.scale;
+    }
+    launch_modplanes(a, l.stream);
+    CV_HIP(c, hipGetLastError());
+    *id = new_id;
+    return JXL_OK;
+}
+
+jxl_status jxl_canvas_orient(jxl_ctx* c, int32_t id, int32_t orientation) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    CanvasSet* k = find(l, id);
+    if (!k) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+    if (orientation < 1 || orientation > 8) return ctx_fail(c, JXL_ERR_STATE, "orientation outside 1..8");  // as jxl_planes_orient
+    if (orientation == 1) return JXL_OK;
+    // out of place, into a new allocation of the same layout (h * w is the same either way round); the old one is freed once
+    // the stream has passed the launches that read it
+    char* base = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&base), k->stride * (size_t)k->n) != hipSuccess) {
+        (void)hipGetLastError();
+        return ctx_fail(c, JXL_ERR_OOM, "device allocation failed (plane set)");
+    }
+    for (int i = 0; i < k->n; i++) launch_orient(k->plane(i), k->h, k->w, orientation, base + k->stride * (size_t)i, l.stream);
+    const hipError_t e = hipGetLastError();
+    const hipError_t e2 = hipStreamSynchronize(l.stream);
+    if (e != hipSuccess || e2 != hipSuccess) {
+        (void)hipFree(base);
+        return ctx_fail(c, JXL_ERR_DEVICE, hipGetErrorString(e != hipSuccess ? e : e2));
+    }
+    (void)hipFree(k->base);
+    k->base = base;
+    if (orientation > 4) std::swap(k->h, k->w);
     return JXL_OK;
 }
 

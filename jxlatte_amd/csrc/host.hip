@@ -278,6 +278,7 @@ struct jxl_ctx {
     std::vector<ModOp> mod_ops;        // the plan, one launch per squeeze step (what a reported mismatch falls back to)
     std::vector<ModOp> mod_ops_fused;  // the same plan with every (V, H) pair of steps as one launch (r5): what jxl_modular_run runs
     std::vector<ModChan> mod_out;
+    bool mod_ran = false;  // a plan has run since jxl_modular_begin (jxl_canvas_from_modular)
     // speculative verification of the segmented squeeze walks (jxl_modular_run): report flag (device), its page-locked host
     // copy, the events that order the check stream, and whether a run's flag has not been looked at yet
     DevBuf mod_flag;
@@ -4104,7 +4105,8 @@ jxl_status png_args(jxl_ctx* c, const jxl_png_params* p, const void* const in[3]
 // samples (jxl_debug_png_samples_guard: what the kernel's last lane stores is seen where it stores it)
 jxl_status png_run(jxl_ctx* c, PngArgs& a, int n_color, bool has_alpha, const void* alpha, Tmp& t, void* out, size_t guard = 0) {
     const size_t n = (size_t)a.c.n;
-    if (has_alpha && !(a.alpha = t.up((const uint32_t*)alpha, n))) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    // (a.alpha already set: the alpha plane is on the device, jxl_canvas_png_samples)
+    if (has_alpha && !a.alpha && !(a.alpha = t.up((const uint32_t*)alpha, n))) return fail(c, JXL_ERR_OOM, "device allocation failed");
     const size_t ob = n * (size_t)(n_color + (has_alpha ? 1 : 0)) * (size_t)(a.bit_depth / 8);
     if (!(a.out = t.up<uint8_t>(nullptr, ob + guard))) return fail(c, JXL_ERR_OOM, "device allocation failed");
     if (guard) HIP_TRY(c, hipMemsetAsync((uint8_t*)a.out + ob, 0xA5, guard, c->stream));
@@ -4493,6 +4495,7 @@ jxl_status jxl_modular_begin(jxl_ctx* c, const jxl_channel* chans, int32_t n_cha
     c->mod_ops.clear();
     c->mod_ops_fused.clear();
     c->mod_out.clear();
+    c->mod_ran = false;
     // Every plane starts kVhPad samples into its allocation (kVhPadH for a plane that is the residual of a horizontal step): the
     // fused squeeze kernel (k_modular_vh.hip) tiles the H pairs in chunks that start at pairs 1, 1 + CW, 1 + 2 CW, ..., and with
     // these leads the pieces it loads (V inputs from column c0 + 1, H residuals from pair c0) and the pieces it stores (outputs
@@ -4780,6 +4783,7 @@ jxl_status run_modular_plan(jxl_ctx* c, int mode) {
     c->mod_launches = launches;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(c, JXL_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
+    c->mod_ran = true;
     return JXL_OK;
 }
 
@@ -4861,6 +4865,101 @@ jxl_status jxl_modular_apply(jxl_ctx* c, const jxl_channel* chans, int32_t n_cha
     for (int i = 0; i < n_out; i++)
         if ((st = jxl_modular_read_channel(c, i, out[i].data))) return st;
     return JXL_OK;
+}
+
+}  // extern "C"
+
+// ---- plane sets read by the writers, and the Modular result read by canvas_host.hip (jxl_internal.h) ----
+namespace jxl {
+jxl_status ctx_modular_out(jxl_ctx* c, std::vector<ModResult>* out, bool* ran) {
+    *ran = c->mod_ran;
+    out->clear();
+    if (!c->mod_ran) return JXL_OK;
+    jxl_status st = mod_settle(c);
+    if (st) return st;
+    if ((st = finish(c))) return st;
+    try {
+        for (const ModChan& m : c->mod_out) out->push_back(ModResult{m.d, m.h, m.w});
+    } catch (const std::bad_alloc&) {
+        return fail(c, JXL_ERR_OOM, "host allocation failed");
+    }
+    return JXL_OK;
+}
+}  // namespace jxl
+
+extern "C" {
+
+jxl_status jxl_canvas_png_samples(jxl_ctx* c, int32_t id, int32_t alpha_plane, const jxl_png_params* p, void* out) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    CanvasView v;
+    if (!canvas_view(c->canvas, id, &v)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+    if (!p) return fail(c, JXL_ERR_INVALID_ARGUMENT, "png samples: null argument");
+    const int nc = p->color.n_planes;
+    if ((nc != 1 && nc != 3) || nc > v.n || alpha_plane < -1 || alpha_plane >= v.n || (p->has_alpha != 0) != (alpha_plane >= 0))
+        return fail(c, JXL_ERR_INVALID_ARGUMENT, "png samples: the set has no such planes");
+    const void* in[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < nc; i++) in[i] = v.plane[i];
+    const void* alpha = alpha_plane >= 0 ? v.plane[alpha_plane] : nullptr;
+    PngArgs a;
+    int n_color = 0;
+    if ((st = png_args(c, p, in, alpha, out, &a, &n_color))) return st;
+    bool tags = p->height == v.h && p->width == v.w;
+    for (int i = 0; i < nc; i++) tags = tags && (p->color.in_is_int != 0) == (v.type[i] == JXL_PLANE_INT32);
+    if (alpha_plane >= 0) tags = tags && (p->alpha_is_int != 0) == (v.type[alpha_plane] == JXL_PLANE_INT32);
+    if (!tags) return fail(c, JXL_ERR_INVALID_ARGUMENT, "png samples: the parameters do not describe the set's %d x %d planes", v.h, v.w);
+    for (int i = 0; i < nc; i++) a.c.in[i] = in[i];
+    a.alpha = alpha;
+    Tmp t;
+    return png_run(c, a, n_color, alpha_plane >= 0, nullptr, t, out);
+}
+
+jxl_status jxl_canvas_color_peak(jxl_ctx* c, int32_t id, const jxl_color_params* p, float* peak) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    CanvasView v;
+    if (!canvas_view(c->canvas, id, &v)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+    if (!p || (p->n_planes != 1 && p->n_planes != 3) || p->n_planes > v.n)
+        return fail(c, JXL_ERR_INVALID_ARGUMENT, "color peak: the set has no such planes");
+    const void* in[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < p->n_planes; i++) in[i] = v.plane[i];
+    ColorArgs a;
+    if ((st = color_args(c, p, in, &a))) return st;
+    if (!peak || v.w > (1 << 30)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color peak: bad arguments");
+    for (int i = 0; i < p->n_planes; i++)
+        if ((p->in_is_int != 0) != (v.type[i] == JXL_PLANE_INT32))
+            return fail(c, JXL_ERR_INVALID_ARGUMENT, "color peak: the parameters do not describe the set's planes");
+    const int pc = p->n_planes == 3 ? 1 : 0;  // determinePeak's plane (JXLImage.java:217)
+    for (int i = 0; i < p->n_planes; i++) a.in[i] = in[i];
+    Tmp t;
+    uint32_t* dkey = t.up<uint32_t>(nullptr, 1);
+    if (!dkey) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    HIP_TRY(c, hipMemsetAsync(dkey, 0, 4, c->stream));
+    a.n = (int64_t)v.h * v.w;
+    launch_color_peak(a, v.h, v.w, dkey, c->stream);
+    if ((st = finish(c))) return st;
+    uint32_t key = 0;
+    HIP_TRY(c, hipMemcpy(&key, dkey, 4, hipMemcpyDeviceToHost));
+    if (a.in_is_int && a.tf_in == JXL_TF_LINEAR && !a.use_matrix)
+        *peak = (float)(int32_t)(key ^ 0x80000000u) / (float)p->in_max[pc];  // :219
+    else
+        *peak = color_peak_value(key);
+    return JXL_OK;
+}
+
+jxl_status jxl_canvas_pfm_samples(jxl_ctx* c, int32_t id, const jxl_pfm_params* p, void* out) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    CanvasView v;
+    if (!canvas_view(c->canvas, id, &v)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+    PfmArgs a;
+    if ((st = pfm_args(c, p, out, &a))) return st;
+    bool tags = p->n_planes <= v.n && p->height == v.h && p->width == v.w;
+    for (int i = 0; i < p->n_planes && tags; i++) tags = (a.is_int[i] != 0) == (v.type[i] == JXL_PLANE_INT32);
+    if (!tags) return fail(c, JXL_ERR_INVALID_ARGUMENT, "pfm samples: the parameters do not describe the set's %d x %d planes", v.h, v.w);
+    for (int i = 0; i < p->n_planes; i++) a.in[i] = v.plane[i];
+    Tmp t;
+    return pfm_run(c, a, t, out);
 }
 
 }  // extern "C"

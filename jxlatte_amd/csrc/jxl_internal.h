@@ -536,6 +536,31 @@ jxl_status ctx_link(jxl_ctx* c, CtxLink* out);                      // hipSetDev
 jxl_status ctx_fail(jxl_ctx* c, jxl_status st, const char* msg);    // records the message (c may be null) and returns st
 jxl_status ctx_planes_get(jxl_ctx* c, int* h, int* w, float* p[3]);  // the resident planes, or JXL_ERR_STATE
 jxl_status ctx_planes_set(jxl_ctx* c, int h, int w, float* p[3]);    // resident planes of h x w to fill (contents undefined)
+// the Modular context's result channels (device pointers), settled as jxl_modular_read_channel settles them; *ran: a plan has
+// run since jxl_modular_begin
+struct ModResult { const int32_t* d; int32_t h, w; };
+jxl_status ctx_modular_out(jxl_ctx* c, std::vector<ModResult>* out, bool* ran);
+// a set as the writers of host.hip read it (canvas_host.hip): false for an unknown id
+struct CanvasView {
+    int32_t n, h, w;
+    int32_t type[JXL_CANVAS_MAX_PLANES];
+    const uint32_t* plane[JXL_CANVAS_MAX_PLANES];
+};
+bool canvas_view(const CanvasStore* s, int32_t id, CanvasView* out);
+// jxl_canvas_from_modular's kernel (k_modplanes.hip): plane i of the set from one or two result channels of one pitch
+struct ModPlane {
+    const int32_t *a, *b;  // b: null, or the channel added first
+    uint32_t* out;         // h x w words
+    int32_t pitch;         // the channels' width
+    int32_t is_float;      // scale * (float)v, else the int32 sample as it is
+    float scale;
+    int32_t reserved;
+};
+struct ModPlanesArgs {
+    int32_t h, w, n, reserved;
+    ModPlane p[JXL_CANVAS_MAX_PLANES];
+};
+void launch_modplanes(const ModPlanesArgs& p, hipStream_t s);
 
 void launch_idct2d_single(const float* src, float* dst, int h, int w, int transposed, const float* lut, hipStream_t s);
 void launch_fdct2d_single(const float* src, float* dst, int h, int w, const float* lut, hipStream_t s);

@@ -748,16 +748,21 @@ class DeviceBackend:
 
 # ---- JXLImage (J/JXLImage.java) ---------------------------------------------------------------------------------
 class JXLImage:
-    def __init__(self, buffer, info, backend, resident=None):
-        """resident: the backend's resident planes (host.ResidentPlanes) holding the three colour planes, whose places in
+    def __init__(self, buffer, info, backend, resident=None, planeSet=None):
+        """planeSet: a device plane set (host.DeviceCanvas) holding EVERY plane of the image, colours and extra channels, each of
+        its own type; `buffer` is then a list of None: JXLDecoder(device_image=True). The set is the image's own (sets do not
+        share the resident planes' single-owner rule): `buffer` / getBuffer() download the typed planes on first use and keep
+        the host arrays, the writers read the set; close() or deletion releases it.
+        resident: the backend's resident planes (host.ResidentPlanes) holding the three colour planes, whose places in
         `buffer` are None: JXLDecoder(device_output=True). They are the image's until the backend decodes another frame;
         `buffer` / getBuffer() download them on first use and keep the host arrays; once another frame has taken the planes,
         a first use raises IllegalStateException instead (ResidentPlanes.live)."""
         self.info = info
         self.backend = backend
         self.resident = resident
+        self.planeSet = planeSet
         self.buffer = buffer  # list of 2-D arrays (int32 or float32), colour channels first
-        self.height, self.width = buffer[0].shape if resident is None else resident.shape
+        self.height, self.width = planeSet.shape if planeSet is not None else buffer[0].shape if resident is None else resident.shape
         self.colorEncoding = info.colour_space
         alphas = [i for i in range(info.num_extra) if info.ec_type[i] == 0]
         self.alphaIndex = alphas[0] if alphas else -1
@@ -771,9 +776,29 @@ class JXLImage:
         self.has_icc = bool(info.use_icc) and not info.xyb_encoded
 
     resident = None
+    planeSet = None
+
+    def setLive(self):
+        """the image's planes are in a device plane set that has not been released"""
+        return self.planeSet is not None and self.planeSet.id is not None
+
+    def close(self):
+        """release the image's plane set (the host arrays, once downloaded, stay)"""
+        ps, self.planeSet = self.planeSet, None
+        if ps is not None:
+            ps.release()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
     @property
     def buffer(self):
+        if self.planeSet is not None and self._buffer and self._buffer[0] is None:
+            for c in range(len(self._buffer)):  # the typed planes: bit for bit the default decoder's arrays
+                self._buffer[c] = self.planeSet.download(c)
         if self.resident is not None and self._buffer[0] is None:
             self.resident._need_live()  # (a later frame of the backend has taken the planes: an error, not its pixels)
             planes = self.resident.download()
@@ -787,7 +812,7 @@ class JXLImage:
 
     def onDevice(self):
         """the colour planes are the backend's resident planes (and nothing has replaced them on this image)"""
-        return self.resident is not None
+        return self.resident is not None or self.planeSet is not None
 
     def _clone(self, buffer=None):
         im = JXLImage.__new__(JXLImage)
@@ -795,6 +820,7 @@ class JXLImage:
         im.buffer = list(self.buffer if buffer is None else buffer)
         im.bitDepths = list(self.bitDepths)
         im.resident = None  # a clone lives on the host
+        im.planeSet = None
         return im
 
     def getWidth(self):
@@ -820,7 +846,7 @@ class JXLImage:
 
     def extraChannel(self, i):
         """extra channel i (a host array), without touching the colour planes"""
-        return self._buffer[self.getColorChannelCount() + i]
+        return (self.buffer if self.planeSet is not None else self._buffer)[self.getColorChannelCount() + i]
 
     def getBuffer(self, copy=True):
         return [b.copy() for b in self.buffer] if copy else self.buffer
@@ -982,7 +1008,7 @@ def _tt_dims():
 
 class JXLDecoder:
     def __init__(self, source, backend=None, sparse_coeffs=False, device_splines=False, device_patches=False, device_output=False,
-                 device_canvas=False, draw_varblocks=False, device_palette=False):
+                 device_canvas=False, draw_varblocks=False, device_palette=False, device_image=False):
         """sparse_coeffs: hand the HF coefficients to the backend as lists of non-zero entries (jxf_get_coeffs_sparse ->
         jxl_vardct_put_group_sparse), not as dense planes; same pixels.
         device_splines: Frame.renderSplines runs in the backend (jxl_planes_splines on the resident planes, jxl_stage_splines
@@ -1019,7 +1045,17 @@ class JXLDecoder:
         (backend.palette: jxl_stage_palette, one call per transform) instead of the front-end's loop; the same samples. The
         palettes of the per-group sub-streams stay in the front-end, and so does a palette with predictor 6 whose weighted
         predictor's plane was not kept. stats[k]["palette"] lists, per transform in the order they were undone, dict(num_c,
-        nb_colors, delta_pixels, launches); it is [] for a frame without one. A backend without `palette` is an error."""
+        nb_colors, delta_pixels, launches); it is [] for a frame without one. A backend without `palette` is an error.
+        device_image: the decoded JXLImage is backed by a device plane set (JXLImage.planeSet), colours and extra channels,
+        whatever their types, where one of two routes leads there; PNGWriter / PFMWriter(deviceSamples=True) read the set, so only
+        the file's samples come down. Route "modular frame": a Modular frame that is the whole image (_modular_frame_route lists
+        the conditions) is decoded with the front-end's frame-level transforms deferred; the encoded channels go up once
+        (jxl_modular_begin), the plan runs, and jxl_canvas_from_modular makes the set -- nothing comes down. Route "canvas": with
+        device_canvas, the canvas set at the end of decode() becomes the image's (cloned while the animation continues).
+        Every other frame runs jxf_apply_transforms with the usual hooks and goes on exactly as without the switch.
+        stats[k]["image"]: "device set (modular frame)", "device set (canvas)" or "host: <reason>". device_output's direct path
+        is unchanged and comes first for the frames it covers. A backend without a context is an error."""
+        self.device_image = bool(device_image)
         self.device_palette = bool(device_palette)
         self.draw_varblocks = bool(draw_varblocks)
         self.device_output = bool(device_output)
@@ -1570,12 +1606,75 @@ class JXLDecoder:
         return True
 
     # -- the decode loop (JXLCodestreamDecoder.decode :546-677) ----------------------------------------------------
+    # -- the image as a device plane set (device_image) -----------------------------------------------------------
+    def _modular_frame_route(self, fr, colors, colors_img):
+        """None when the frame qualifies for device_image's "modular frame" route, else the first condition that fails. The
+        chain is looked at first after the encoding: it is what tells the committed images apart."""
+        info = self.info
+        if fr.encoding != MODULAR:
+            return "not a Modular frame"
+        kinds = [t["kind"] for t in self.fe.transforms()]
+        R, P, S = frontend.TRANSFORM_RCT, frontend.TRANSFORM_PALETTE, frontend.TRANSFORM_SQUEEZE
+        if P in kinds:
+            return "a Palette in the frame-level chain"
+        if kinds not in ([], [R], [S], [R, S]):
+            return "a frame-level chain that is not one plan ([], [RCT], [Squeeze] or [RCT, Squeeze])"
+        if fr.type != REGULAR_FRAME or not fr.is_last or fr.lf_level != 0:
+            return "not a regular last frame"
+        if self._is_set(self.canvas) or self.canvas[0] is not None or fr.x0 != 0 or fr.y0 != 0:
+            return "not the first frame on the canvas, at its origin"
+        if fr.upsampling != 1 or any(fr.ec_upsampling[i] != 1 for i in range(info.num_extra)) or \
+                fr.width != info.width or fr.height != info.height:
+            return "upsampled, or not of the image's size"
+        if fr.blend_mode != abi.BLEND_REPLACE or any(fr.ec_blend_mode[i] != abi.BLEND_REPLACE for i in range(info.num_extra)):
+            return "a blend mode other than REPLACE"
+        if fr.num_patches or fr.has_splines or fr.has_noise:
+            return "patches, splines or noise"
+        if fr.gab or fr.epf_iters > 0 or fr.do_ycbcr:
+            return "a restoration filter or YCbCr"
+        if info.xyb_encoded:
+            return "an XYB image"
+        if info.exp_bits != 0 or colors != 3 or colors_img != 3:
+            return "colour planes that are not three int32 planes"
+        if 3 + info.num_extra > abi.CANVAS_MAX_PLANES or fr.num_modular_channels < 1:
+            return "more planes than a set holds"
+        return None
+
+    def _modular_frame_image(self, fr):
+        """device_image, route "modular frame": the encoded channels up once, one plan, one set; nothing comes down"""
+        info, be, fe = self.info, self.backend, self.fe
+        host = be.host
+        chans = [fe.modular_channel(i, copy=False)[0] for i in range(fe.modular_channel_count())]
+        steps, rct_type, rct_begin = [], -1, 0
+        for t in fe.transforms():
+            if t["kind"] == frontend.TRANSFORM_SQUEEZE:
+                steps = t["steps"]
+            else:
+                rct_type, rct_begin = t["rct_type"], t["begin_c"]
+        ms = host.ModularStream(be.ctx, chans, steps, rctType=rct_type, rctBegin=rct_begin)
+        ms.run()
+        host._bus(be.ctx, up=sum(c.nbytes for c in ms.channels))
+        n = 3 + info.num_extra
+        if be.ctx.lib.jxl_modular_out_count(be.ctx.h) != n:
+            raise InvalidBitstreamException("the frame-level stream does not hold the frame's %d channels" % n)
+        if getattr(self, "trace", None) is not None:  # a listener wants the samples: copies come down, the result stays
+            self._trace("mod", ms.getDecodedBuffer(), False)
+        planes = [(c, -1, np.int32, 1.0) for c in range(3)]
+        planes += [(3 + i, -1, np.float32 if info.ec_exp_bits[i] != 0 else np.int32, 1.0) for i in range(info.num_extra)]
+        cv = host.DeviceCanvas.fromModular(be.ctx, fr.height, fr.width, planes)
+        if getattr(self, "trace", None) is not None:
+            self._trace("xyb", [cv.download(c) for c in range(n)], False)
+        if info.orientation != 1:
+            cv.orient(info.orientation)
+        return JXLImage([None] * n, info, be, planeSet=cv)
+
     def decode(self):
         info, be = self.info, self.backend
         colors_img = 1 if info.colour_space == CE_GRAY else 3
         if self.canvas is None:
             self.canvas = [None] * (colors_img + info.num_extra)
         produced = False
+        fr_last = None
         while True:
             dev_palette = getattr(self, "device_palette", False)
             if dev_palette:
@@ -1583,19 +1682,44 @@ class JXLDecoder:
                     raise RuntimeError("device_palette needs a backend with `palette`")
                 if hasattr(be, "palette_log"):
                     del be.palette_log[:]
+            dev_image = getattr(self, "device_image", False)
+            if dev_image and not hasattr(be, "ctx"):
+                raise RuntimeError("device_image needs a backend with a device context")
+            hooks = (be.squeeze, be.rct, be.palette if dev_palette else None)
             try:
-                fr = self.fe.next_frame(be.squeeze, be.rct, be.palette if dev_palette else None)
+                if dev_image:  # the frame-level transforms wait until the route is known
+                    self.fe.set_defer_transforms(True)
+                fr = self.fe.next_frame(*hooks)
             except frontend.FrontendError as e:
                 raise self._map(e)
             if fr is None:
                 break
+            fr_last = fr
             produced = True
             self.frames_decoded += 1
             self.stats.append(dict(encoding="vardct" if fr.encoding == VARDCT else "modular", width=fr.width, height=fr.height,
                                    groups=fr.num_groups, passes=fr.num_passes))
+            bus0 = tuple(getattr(getattr(be, "ctx", None), "blend_bus", (0, 0)))  # (host._bus: what the blend path moves)
+            self.stats[-1]["image"] = "host: device_image is off"
+            if dev_image:
+                why = self._modular_frame_route(fr, self._colors(fr), colors_img)
+                if why is None:
+                    self.visibleFrames += 1
+                    self.invisibleFrames = 0
+                    image = self._modular_frame_image(fr)
+                    bus1 = tuple(getattr(be.ctx, "blend_bus", (0, 0)))
+                    self.stats[-1].update(image="device set (modular frame)", output="device", canvas="host",
+                                          blend_bus=(bus1[0] - bus0[0], bus1[1] - bus0[1]))
+                    if dev_palette:
+                        self.stats[-1]["palette"] = []
+                    return image
+                self.stats[-1]["image"] = "host: " + why
+                try:  # every other frame: the pending transforms through today's hooks, and on exactly as without the switch
+                    self.fe.apply_transforms(*hooks)
+                except frontend.FrontendError as e:
+                    raise self._map(e)
             if dev_palette:
                 self.stats[-1]["palette"] = [dict(e) for e in getattr(be, "palette_log", [])]
-            bus0 = tuple(getattr(getattr(be, "ctx", None), "blend_bus", (0, 0)))  # (host._bus: what the blend path moves)
             if fr.flags & FLAG_USE_LF_FRAME and self.lfBuffer[fr.lf_level] is None:
                 raise InvalidBitstreamException("LF Level too large")  # JXLCodestreamDecoder.java:613-614
             colors = self._colors(fr)
@@ -1795,6 +1919,19 @@ class JXLDecoder:
         if self._is_set(self.canvas):
             self._release_dead()
             cv, o = self.canvas, info.orientation
+            if getattr(self, "device_image", False):
+                # route "canvas": the set becomes the image's, whatever its plane types -- handed over when the image ends
+                # here, cloned while the animation continues (the canvas lives on for its next frame)
+                if fr_last is not None and fr_last.is_last:
+                    ps = cv
+                    self.reference = [None if r is cv else r for r in self.reference]
+                    self.canvas = None
+                else:
+                    ps = cv.clone()
+                if o != 1:
+                    ps.orient(o)
+                self.stats[-1].update(image="device set (canvas)", output="device")
+                return JXLImage([None] * len(ps), info, be, planeSet=ps)
             if all(t == np.float32 for t in cv.dtypes[:3]):
                 # the canvas' colour planes become the image's resident planes; the set lives on for the next animation frame
                 rp = cv.toPlanes()
@@ -1860,9 +1997,16 @@ class PNGWriter:
         h, w = image.getHeight(), image.getWidth()
         up = 0
         planes = [np.broadcast_to(F(0), (h, w))] * 3 if rp is not None else None  # stand-ins: the samples are on the device
+        # the image's plane set (JXLDecoder(device_image=True)): colours and alpha are read where they are. Colour planes of
+        # mixed types have no one-pass form (jxl_color_params states one type): they take the host arrays' way below
+        ps = image.planeSet if image.setLive() and len({image.planeSet.types[c] for c in range(colors)}) == 1 else None
+        if ps is not None:
+            planes = ps._stand_ins(colors)
 
         def peak_of(pl, **front):
             nonlocal up
+            if ps is not None:
+                return ps.colorPeak(nColor=colors, **front)
             if rp is not None:
                 return rp.colorPeak(**front)
             up += sum(a.nbytes for a in pl) if front.get("matrix") is not None else pl[min(1, len(pl) - 1)].nbytes
@@ -1884,10 +2028,19 @@ class PNGWriter:
         self.colorChannels = colors
         self.colorMode = (4 if self.alphaIndex >= 0 else 0) if colors == 1 else (6 if self.alphaIndex >= 0 else 2)
         self.deflateLevel = deflateLevel
-        alpha = np.ascontiguousarray(image.extraChannel(self.alphaIndex)) if self.alphaIndex >= 0 else None
-        kw = dict(premultiplied=image.isAlphaPremultiplied() and alpha is not None, bitDepth=bitDepth, bigEndian=True,
-                  alphaDepth=image.getTaggedBitDepth(colors + self.alphaIndex) if alpha is not None else None,
+        if ps is not None:
+            alpha = None
+            has_alpha = self.alphaIndex >= 0
+        else:
+            alpha = np.ascontiguousarray(image.extraChannel(self.alphaIndex)) if self.alphaIndex >= 0 else None
+            has_alpha = alpha is not None
+        kw = dict(premultiplied=image.isAlphaPremultiplied() and has_alpha, bitDepth=bitDepth, bigEndian=True,
+                  alphaDepth=image.getTaggedBitDepth(colors + self.alphaIndex) if has_alpha else None,
                   colorDepth=image.getTaggedBitDepth(0), **params)
+        if ps is not None:  # one sample call on the set: nothing goes up, alpha included
+            self.samples = ps.pngSamples(nColor=colors, alphaPlane=colors + self.alphaIndex if has_alpha else None, **kw)
+            self.bus_bytes = (0, self.samples.nbytes)
+            return True
         if rp is not None:
             self.samples = rp.pngSamples(alpha, **kw)
         else:
@@ -1932,7 +2085,10 @@ class PFMWriter:
             be = image.backend
             if not hasattr(be, "pfm_samples"):
                 raise TypeError("deviceSamples needs a backend with pfm_samples")
-            if image.onDevice() and (image._buffer[0] is None or image.resident.live()):  # (else the downloaded host arrays)
+            if image.setLive():  # JXLDecoder(device_image=True): the set's planes, int32 or float, as they are
+                self.samples = image.planeSet.pfmSamples(nColor=colors, taggedDepths=tagged)
+                up = 0
+            elif image.resident is not None and (image._buffer[0] is None or image.resident.live()):  # (else the downloaded host arrays)
                 self.samples = image.resident.pfmSamples()
                 up = 0
             else:

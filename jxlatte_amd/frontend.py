@@ -98,6 +98,14 @@ class SplineView(C.Structure):
     _fields_ = [("quant_adjust", i32), ("n_control", i32), ("control", C.POINTER(i32)), ("coeff", C.POINTER(i32))]
 
 
+class TransformView(C.Structure):
+    _fields_ = [("kind", i32), ("begin_c", i32), ("num_c", i32), ("rct_type", i32), ("nb_colors", i32), ("nb_deltas", i32),
+                ("d_pred", i32), ("n_steps", i32), ("steps", C.POINTER(SqueezeStep))]
+
+
+TRANSFORM_RCT, TRANSFORM_PALETTE, TRANSFORM_SQUEEZE = 0, 1, 2
+
+
 class FrontendError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__("jxf status %d: %s" % (status, msg))
@@ -120,6 +128,12 @@ SIGNATURES = {
     "jxf_num_splines": (i32, [C.c_void_p]),
     "jxf_get_spline": (i32, [C.c_void_p, i32, C.POINTER(SplineView)]),
     "jxf_get_modular_channel": (i32, [C.c_void_p, i32, C.POINTER(Chan)]),
+    "jxf_set_defer_transforms": (i32, [C.c_void_p, i32]),
+    "jxf_get_transform_count": (i32, [C.c_void_p]),
+    "jxf_get_transform": (i32, [C.c_void_p, i32, C.POINTER(TransformView)]),
+    "jxf_transforms_pending": (i32, [C.c_void_p]),
+    "jxf_modular_channel_count": (i32, [C.c_void_p]),
+    "jxf_apply_transforms": (i32, [C.c_void_p, C.POINTER(Hooks)]),
 }
 
 _lib = None
@@ -186,11 +200,8 @@ class Frontend:
         n = self._check(self.lib.jxf_get_up_weights(self.h, k_index, out, 210))
         return np.array(out[:n], np.float32)
 
-    def next_frame(self, squeeze=None, rct=None, palette=None):
-        """squeeze(in_channels, steps, out_shapes) -> list of out arrays; rct(v0, v1, v2, rct_type) -> (o0, o1, o2);
-        palette(index, palette, pred, num_c, nb_colors, nb_deltas, d_pred, bit_depth) -> num_c arrays of index's shape (index:
-        h x w, palette: the stream's channel 0, pred: the weighted predictor's h x w values or None). All operate on numpy int32
-        arrays; results are copied back into the front-end's buffers. Without `palette` the front-end's own loop runs."""
+    def _make_hooks(self, squeeze, rct, palette):
+        """jxf_hooks over the three Python callables of next_frame"""
         def sq_cb(_user, cin, n_in, steps, n_steps, cout, n_out):
             try:
                 ins = [_np(cin[i].data, (cin[i].h, cin[i].w)) for i in range(n_in)]
@@ -240,6 +251,15 @@ class Frontend:
         hooks.squeeze = SQUEEZE_CB(sq_cb) if squeeze else SQUEEZE_CB()
         hooks.rct = RCT_CB(rct_cb) if rct else RCT_CB()
         self._hooks = hooks
+        return hooks
+
+    def next_frame(self, squeeze=None, rct=None, palette=None):
+        """squeeze(in_channels, steps, out_shapes) -> list of out arrays; rct(v0, v1, v2, rct_type) -> (o0, o1, o2);
+        palette(index, palette, pred, num_c, nb_colors, nb_deltas, d_pred, bit_depth) -> num_c arrays of index's shape (index:
+        h x w, palette: the stream's channel 0, pred: the weighted predictor's h x w values or None). All operate on numpy int32
+        arrays; results are copied back into the front-end's buffers. Without `palette` the front-end's own loop runs. After
+        set_defer_transforms(True) none of them is called here: the frame-level transforms wait for apply_transforms."""
+        hooks = self._make_hooks(squeeze, rct, palette)
         st = self.lib.jxf_next_frame(self.h, C.byref(hooks))
         if st < 0 and self._hook_error is not None:
             raise self._hook_error
@@ -250,6 +270,39 @@ class Frontend:
         self.frame = FrameInfo()
         self._check(self.lib.jxf_get_frame_info(self.h, C.byref(self.frame)))
         return self.frame
+
+    def set_defer_transforms(self, on):
+        """frames decoded from now on leave the frame-level stream's inverse transforms undone (jxf_set_defer_transforms)"""
+        self._check(self.lib.jxf_set_defer_transforms(self.h, int(bool(on))))
+
+    def transforms(self):
+        """the current frame's frame-level transform list in bitstream order: dicts of kind (TRANSFORM_*), begin_c, num_c,
+        rct_type, nb_colors, nb_deltas, d_pred and, for a Squeeze, steps: the expanded (horizontal, in_place, begin_c, num_c) list"""
+        out = []
+        for i in range(self._check(self.lib.jxf_get_transform_count(self.h))):
+            v = TransformView()
+            self._check(self.lib.jxf_get_transform(self.h, i, C.byref(v)))
+            out.append(dict(kind=v.kind, begin_c=v.begin_c, num_c=v.num_c, rct_type=v.rct_type, nb_colors=v.nb_colors,
+                            nb_deltas=v.nb_deltas, d_pred=v.d_pred,
+                            steps=[(v.steps[j].horizontal, v.steps[j].in_place, v.steps[j].begin_c, v.steps[j].num_c) for j in range(v.n_steps)]))
+        return out
+
+    def transforms_pending(self):
+        return bool(self.lib.jxf_transforms_pending(self.h))
+
+    def modular_channel_count(self):
+        """channels modular_channel answers for: the encoded list, meta channels included, while the transforms are pending"""
+        return self._check(self.lib.jxf_modular_channel_count(self.h))
+
+    def apply_transforms(self, squeeze=None, rct=None, palette=None):
+        """runs the pending frame-level transforms exactly as next_frame would have (same hooks); idempotent"""
+        hooks = self._make_hooks(squeeze, rct, palette)
+        st = self.lib.jxf_apply_transforms(self.h, C.byref(hooks))
+        if st < 0 and self._hook_error is not None:
+            raise self._hook_error
+        self._check(st)
+        if self.frame is not None:
+            self._check(self.lib.jxf_get_frame_info(self.h, C.byref(self.frame)))
 
     def lfgroup(self, idx):
         v = LFGroupView()
@@ -297,7 +350,11 @@ class Frontend:
             out.append(dict(quant_adjust=v.quant_adjust, control=_np(v.control, (v.n_control, 2)), coeff=_np(v.coeff, (4, 32))))
         return out
 
-    def modular_channel(self, index):
+    def modular_channel(self, index, copy=True):
+        """(samples, (hshift, vshift)); copy=False: a view of the front-end's own buffer, valid until the next frame or
+        apply_transforms"""
         c = Chan()
         self._check(self.lib.jxf_get_modular_channel(self.h, index, C.byref(c)))
+        if not copy and c.h * c.w and c.data:
+            return np.ctypeslib.as_array(c.data, shape=(c.h * c.w,)).reshape(c.h, c.w), (c.hshift, c.vshift)
         return _np(c.data, (c.h, c.w)), (c.hshift, c.vshift)

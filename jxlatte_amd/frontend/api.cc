@@ -17,10 +17,12 @@ struct jxf_dec {
     BitReader br;
     std::unique_ptr<Frame> frame;
     bool done = false, skipped_preview = false;
+    bool defer = false;  // jxf_set_defer_transforms
     std::string error;
     // scratch for views
     std::vector<float> qv[3];
     std::vector<int32_t> patch_pos, patch_blend;
+    std::vector<jxf_squeeze_step> steps;
 };
 
 namespace {
@@ -153,6 +155,14 @@ bool palette_hook(void* user, const Channel& pal, const Transform& t, int bit_de
     return true;
 }
 
+void bind_hooks(TransformHooks* th, HookCtx* hc) {
+    th->user = hc;
+    th->required = true;
+    th->squeeze = squeeze_hook;
+    th->rct = rct_hook;
+    if (hc->h && hc->h->palette) th->palette = palette_hook;  // optional: without it the front-end's own loop runs
+}
+
 }  // namespace
 
 extern "C" {
@@ -230,12 +240,8 @@ int32_t jxf_next_frame(jxf_dec* d, const jxf_hooks* hooks) {
         if ((int64_t)f.padded_w * f.padded_h > (1ll << 28)) throw UnsupportedError("frame larger than 2^28 pixels");
         HookCtx hc{hooks, &d->error};
         TransformHooks th;
-        th.user = &hc;
-        th.required = true;
-        th.squeeze = squeeze_hook;
-        th.rct = rct_hook;
-        if (hooks && hooks->palette) th.palette = palette_hook;  // optional: without it the front-end's own loop runs
-        f.decode(d->br, &th);
+        bind_hooks(&th, &hc);
+        f.decode(d->br, &th, d->defer);
         if (f.fh.is_last) d->done = true;
         return JXF_OK;
     });
@@ -360,6 +366,53 @@ int32_t jxf_get_spline(const jxf_dec* d, int32_t index, jxf_spline_view* o) {
     o->control = sp.control.data();
     o->coeff = &sp.coeff[0][0];
     return JXF_OK;
+}
+
+int32_t jxf_set_defer_transforms(jxf_dec* d, int32_t on) {
+    if (!d) return JXF_ERR_ARGUMENT;
+    d->defer = on != 0;
+    return JXF_OK;
+}
+
+int32_t jxf_get_transform_count(const jxf_dec* d) {
+    if (!d || !d->frame) return JXF_ERR_STATE;
+    return (int32_t)d->frame->global_modular.transforms.size();
+}
+
+int32_t jxf_get_transform(const jxf_dec* dc, int32_t index, jxf_transform_view* o) {
+    jxf_dec* d = const_cast<jxf_dec*>(dc);
+    if (!d || !o || !d->frame) return JXF_ERR_STATE;
+    const ModularStream& m = d->frame->global_modular;
+    if (index < 0 || index >= (int32_t)m.transforms.size()) return JXF_ERR_ARGUMENT;
+    const Transform& t = m.transforms[(size_t)index];
+    memset(o, 0, sizeof *o);
+    o->kind = t.tr; o->begin_c = t.begin_c; o->num_c = t.num_c; o->rct_type = t.rct_type;
+    o->nb_colors = t.nb_colors; o->nb_deltas = t.nb_deltas; o->d_pred = t.d_pred;
+    d->steps.clear();
+    if (t.tr == Transform::kSqueeze)
+        for (const SqueezeStep& s : m.squeeze_steps[(size_t)index]) d->steps.push_back(jxf_squeeze_step{s.horizontal, s.in_place, s.begin_c, s.num_c});
+    o->n_steps = (int32_t)d->steps.size();
+    o->steps = d->steps.empty() ? nullptr : d->steps.data();
+    return JXF_OK;
+}
+
+int32_t jxf_transforms_pending(const jxf_dec* d) { return d && d->frame && d->frame->global_modular.transforms_pending() ? 1 : 0; }
+
+int32_t jxf_modular_channel_count(const jxf_dec* d) {
+    if (!d || !d->frame) return JXF_ERR_STATE;
+    return (int32_t)d->frame->global_modular.channels.size();
+}
+
+int32_t jxf_apply_transforms(jxf_dec* d, const jxf_hooks* hooks) {
+    if (!d) return JXF_ERR_ARGUMENT;
+    if (!d->frame) return JXF_ERR_STATE;
+    return guarded(d, [&]() -> int32_t {
+        HookCtx hc{hooks, &d->error};
+        TransformHooks th;
+        bind_hooks(&th, &hc);
+        d->frame->global_modular.apply_transforms(&th);  // idempotent
+        return JXF_OK;
+    });
 }
 
 int32_t jxf_get_modular_channel(const jxf_dec* d, int32_t index, jxf_chan* o) {

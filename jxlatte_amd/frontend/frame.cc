@@ -664,7 +664,7 @@ void Frame::read_pass_group(BitReader& br, int pass, int group, const std::vecto
         copy_back(global_modular.channels[replaced_idx[j]], ms.channels[j], want[j]);
 }
 
-void Frame::decode(BitReader& br, const TransformHooks* hooks) {  // Frame.decodeFrame (:376-461), front part
+void Frame::decode(BitReader& br, const TransformHooks* hooks, bool defer) {  // Frame.decodeFrame (:376-461), front part
     const bool single = toc.lengths.size() == 1;
     const size_t base = br.byte_pos();
     const bool timing = getenv("JXF_TIMING") != nullptr;
@@ -748,7 +748,8 @@ void Frame::decode(BitReader& br, const TransformHooks* hooks) {  // Frame.decod
     }
     lap("pass groups");
     for (Channel& c : global_modular.channels) c.allocate();
-    global_modular.apply_transforms(hooks);
+    if (defer) global_modular.check_transforms();
+    else global_modular.apply_transforms(hooks);
     lap("transforms");
     if (single) {
         br = shared;

@@ -107,7 +107,8 @@ struct Frame {
     // parse the frame header + TOC at the reader position; section payloads follow
     void read_header(BitReader& br, const ImageHeader& image);
     // decode every section (br positioned right after the TOC); leaves br at the end of the frame data
-    void decode(BitReader& br, const TransformHooks* hooks);
+    // defer: the frame-level stream's inverse transforms are left undone (only checked: ModularStream::check_transforms)
+    void decode(BitReader& br, const TransformHooks* hooks, bool defer = false);
     size_t data_bytes() const;
 
     int colour_channels() const { return (ih->xyb_encoded || fh.encoding == kVarDCT) ? 3 : ih->colour_channels(); }

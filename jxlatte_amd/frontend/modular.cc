@@ -560,6 +560,42 @@ void inverse_rct_cpu(Channel* v[3], int rct_type) {  // ModularStream.java:260-3
     }
 }
 
+void ModularStream::check_transforms() const {
+    if (transformed_ || empty) return;
+    struct Shape { int w, h; };
+    std::vector<Shape> sh;
+    for (const Channel& c : channels) sh.push_back(Shape{c.w, c.h});
+    for (int i = (int)transforms.size() - 1; i >= 0; i--) {
+        const Transform& t = transforms[i];
+        if (t.tr == Transform::kSqueeze) {  // the shape replay of the squeeze hook (ModularStream.java:231-259)
+            const std::vector<SqueezeStep>& steps = squeeze_steps[i];
+            for (int j = (int)steps.size() - 1; j >= 0; j--) {
+                const SqueezeStep& s = steps[j];
+                const int begin = s.begin_c, end = begin + s.num_c - 1;
+                const int offset = s.in_place ? end + 1 : (int)sh.size() + begin - end - 1;
+                if (begin < 0 || end < begin || offset < 0 || offset + (end - begin) >= (int)sh.size()) throw BitstreamError("Squeeze channel range");
+                for (int c = begin; c <= end; c++) {
+                    const Shape& r = sh[offset + c - begin];
+                    if (s.horizontal) sh[c].w += r.w;
+                    else sh[c].h += r.h;
+                }
+                sh.erase(sh.begin() + offset, sh.begin() + offset + (end - begin + 1));
+            }
+        } else if (t.tr == Transform::kRCT) {
+            const int start = t.begin_c;
+            if (start < 0 || start + 3 > (int)sh.size()) throw BitstreamError("RCT channel range");
+            const Shape *a = &sh[start], *b = a + 1, *c = a + 2;
+            if (b->w != a->w || b->h != a->h || c->w != b->w || c->h != b->h)
+                throw BitstreamError("RCT must be performed on three equal size channels");
+        } else {
+            const int first = t.begin_c + 1, last = t.begin_c + t.num_c;
+            if (first < 1 || first >= (int)sh.size()) throw BitstreamError("Palette channel range");
+            for (int j = first + 1; j <= last; j++) sh.insert(sh.begin() + j, sh[first]);
+            sh.erase(sh.begin());
+        }
+    }
+}
+
 void ModularStream::apply_transforms(const TransformHooks* hooks) {  // ModularStream.java:224-380
     if (transformed_ || empty) return;
     transformed_ = true;

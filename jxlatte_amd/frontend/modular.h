@@ -87,6 +87,12 @@ class ModularStream {
     void decode_channels(BitReader& br, bool partial, int group_dim);
     // ModularStream.applyTransforms (idempotent)
     void apply_transforms(const TransformHooks* hooks = nullptr);
+    // what apply_transforms' own loop would refuse, found by walking the transform list over the channels' SHAPES only (nothing
+    // is computed): "RCT channel range", "RCT must be performed on three equal size channels", "Palette channel range", and the
+    // hooked Squeeze's "Squeeze channel range" -- a decode that leaves the transforms undone fails where it failed before
+    void check_transforms() const;
+    // the inverse transforms have not run yet (and there is a stream)
+    bool transforms_pending() const { return !transformed_ && !empty; }
 
     std::vector<Channel> channels;
     std::vector<Transform> transforms;

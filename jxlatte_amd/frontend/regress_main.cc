@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
+#include <string>
 #include <vector>
 
 #include "frame.h"
@@ -93,6 +94,49 @@ int main() {
     //    zero), or that are not shifts at all
     expect_throw<BitstreamError>("hshift larger than log2(group size)", [] { sub_channel(Channel(4, 4, 0, 9), 256, 0); });
     expect_throw<BitstreamError>("shift of 32 or more", [] { sub_channel(Channel(4, 4, 40, 0), 256, 0); });
+    // 4. deferred frame-level transforms: the dry walk (ModularStream::check_transforms) refuses what apply_transforms' loop
+    //    refuses, with the same words -- a decode must not start succeeding because the arithmetic moved
+    {
+        auto stream = [](std::vector<Channel> ch, std::vector<Transform> tr) {
+            ModularStream ms;
+            ms.empty = false;
+            ms.channels = std::move(ch);
+            for (Channel& c : ms.channels) c.allocate();
+            ms.squeeze_steps.resize(tr.size());
+            for (size_t i = 0; i < tr.size(); i++)
+                if (tr[i].tr == Transform::kSqueeze) ms.squeeze_steps[i] = tr[i].sp;
+            ms.transforms = std::move(tr);
+            return ms;
+        };
+        auto rct = [](int begin) { Transform t; t.tr = Transform::kRCT; t.begin_c = begin; t.rct_type = 6; return t; };
+        auto pal = [](int begin, int num) { Transform t; t.tr = Transform::kPalette; t.begin_c = begin; t.num_c = num; t.nb_colors = 2; return t; };
+        auto hsq = [](int begin) { Transform t; t.tr = Transform::kSqueeze; t.sp = {SqueezeStep{true, true, begin, 1}}; return t; };
+        struct Case { const char* what; std::vector<Channel> ch; std::vector<Transform> tr; };
+        const std::vector<Case> cases = {
+            {"RCT past the channel list", {Channel(8, 8, 0, 0), Channel(8, 8, 0, 0), Channel(8, 8, 0, 0)}, {rct(1)}},
+            {"RCT over channels of unequal size", {Channel(8, 8, 0, 0), Channel(8, 8, 0, 0), Channel(4, 4, 0, 0)}, {rct(0)}},
+            // (inverse order: the squeeze runs first and merges channels 0 and 1 into one 8 x 8: two channels are left)
+            {"RCT that a squeeze leaves too few channels", {Channel(8, 4, 0, 1), Channel(8, 4, 0, 1), Channel(8, 8, 0, 0)}, {rct(0), hsq(0)}},
+            // (the squeeze makes channel 0 8 x 8 like the others only AFTER the RCT: bitstream order RCT last)
+            {"RCT before the squeeze that would equalise", {Channel(8, 4, 0, 1), Channel(8, 4, 0, 1), Channel(8, 8, 0, 0), Channel(8, 8, 0, 0)}, {hsq(0), rct(0)}},
+            {"Palette past the channel list", {Channel(1, 2, -1, -1), Channel(8, 8, 0, 0)}, {pal(1, 1)}},
+        };
+        for (const Case& k : cases) {
+            std::string dry, loop;
+            try { stream(k.ch, k.tr).check_transforms(); } catch (const BitstreamError& e) { dry = e.what(); }
+            try { stream(k.ch, k.tr).apply_transforms(nullptr); } catch (const BitstreamError& e) { loop = e.what(); }
+            const bool ok = !dry.empty() && dry == loop;
+            printf("%s dry walk: %-47s -> %s | %s\n", ok ? "ok  " : "FAIL", k.what, dry.c_str(), loop.c_str());
+            failures += !ok;
+        }
+        // and a chain the loop accepts passes the walk: squeeze, then RCT over the three 8 x 8 channels it leaves
+        ModularStream good = stream({Channel(8, 4, 0, 1), Channel(8, 4, 0, 1), Channel(8, 8, 0, 0), Channel(8, 8, 0, 0)}, {rct(0), hsq(0)});
+        bool ok = true;
+        try { good.check_transforms(); good.apply_transforms(nullptr); } catch (const std::exception& e) { ok = false; }
+        ok = ok && good.channels.size() == 3 && good.channels[0].w == 8 && !good.transforms_pending();
+        printf("%s dry walk: a valid chain passes and then runs\n", ok ? "ok  " : "FAIL");
+        failures += !ok;
+    }
     printf("%d failure(s)\n", failures);
     return failures ? 1 : 0;
 }

@@ -1090,9 +1090,58 @@ class DeviceCanvas:
         ctx.call("jxl_canvas_from_planes", len(codes), abi.iptr(arr), C.byref(id_))
         return cls(ctx, id_.value, [abi.PLANE_FLOAT] * 3 + codes, (h.value, w.value))
 
+    @classmethod
+    def fromModular(cls, ctx, height, width, planes):
+        """the Modular context's result channels as a new set (jxl_canvas_from_modular; Frame.java:430-455 for all planes as one
+        launch): every plane a channel cropped to height x width. planes: per plane (channel, addChannel or -1, dtype or plane
+        code, scale) -- an int32 plane is a copy, a float plane scale * (float)(a [+ b]). Nothing crosses the bus"""
+        d = modularPlanesDesc(height, width, planes)
+        id_ = C.c_int32(-1)
+        ctx.call("jxl_canvas_from_modular", C.byref(d), C.byref(id_))
+        return cls(ctx, id_.value, [d.plane[i].type for i in range(d.n_planes)], (int(height), int(width)))
+
     def _live(self):
         if self.id is None:
             raise IllegalStateException(abi.JXL_ERR_STATE, "the plane set has been released")
+
+    def _stand_ins(self, n):
+        return [np.broadcast_to(np.zeros((), _PLANE_DTYPE[self.types[c]]), self.shape) for c in range(n)]  # shape and dtype only; never read
+
+    def orient(self, orientation):
+        """JXLCodestreamDecoder.transposeBuffer of every plane, on the device (jxl_canvas_orient)"""
+        self._live()
+        self.ctx.call("jxl_canvas_orient", self.id, int(orientation))
+        if 5 <= int(orientation) <= 8:
+            self.shape = (self.shape[1], self.shape[0])
+
+    def colorPeak(self, nColor=3, **params):
+        """determinePeak of planes 0 .. nColor - 1 as they stand (jxl_canvas_color_peak; colorParams' keywords)"""
+        self._live()
+        p = colorParams(self._stand_ins(nColor), **params)
+        peak = C.c_float(0)
+        self.ctx.call("jxl_canvas_color_peak", self.id, C.byref(p), C.byref(peak))
+        return np.float32(peak.value)
+
+    def pngSamples(self, nColor=3, alphaPlane=None, **params):
+        """pngSamples of planes 0 .. nColor - 1 and the alpha plane alphaPlane of the set (jxl_canvas_png_samples; pngParams'
+        keywords but `alpha`): nothing goes up, only the PNG's samples come down"""
+        self._live()
+        ap = -1 if alphaPlane is None else int(alphaPlane)
+        alpha = None if ap < 0 else np.broadcast_to(np.zeros((), _PLANE_DTYPE[self.types[ap]]), self.shape)
+        p = pngParams(self._stand_ins(nColor), self.shape, alpha=alpha, **params)
+        out = _png_out(p, self.shape)
+        self.ctx.call("jxl_canvas_png_samples", self.id, ap, C.byref(p), _vp(out))
+        _bus(self.ctx, down=out.nbytes)
+        return out
+
+    def pfmSamples(self, nColor=3, taggedDepths=None):
+        """pfmSamples of planes 0 .. nColor - 1 (jxl_canvas_pfm_samples): nothing goes up, only the PFM's bytes come down"""
+        self._live()
+        p = pfmParams(self._stand_ins(nColor), self.shape, taggedDepths)
+        out = np.empty((self.shape[0], self.shape[1], nColor, 4), np.uint8)
+        self.ctx.call("jxl_canvas_pfm_samples", self.id, C.byref(p), _vp(out))
+        _bus(self.ctx, down=out.nbytes)
+        return out
 
     @property
     def dtypes(self):
@@ -1150,6 +1199,18 @@ class DeviceCanvas:
         for i, t in enumerate(self.types):
             s.types[i] = t
         return s
+
+
+def modularPlanesDesc(height, width, planes):
+    """jxl_modular_planes_desc; planes: per plane (channel, addChannel or -1, dtype or plane code, scale)"""
+    d = abi.ModularPlanesDesc()
+    d.height, d.width, d.n_planes = int(height), int(width), len(planes)
+    for i, (ch, add, t, scale) in enumerate(planes[:abi.CANVAS_MAX_PLANES]):
+        k = d.plane[i]
+        k.channel, k.add_channel = int(ch), int(add)
+        k.type = int(t) if isinstance(t, (int, np.integer)) else _plane_code(t)
+        k.scale = float(scale)
+    return d
 
 
 def canvasBlendDesc(canvas_id, frame_id, ref_id, rect, chans):
