@@ -756,6 +756,23 @@ typedef struct jxl_modular_planes_desc {
  * outside the result list, a channel smaller than the bounds, an add_channel on an int32 plane or of another size than its
  * channel, a type other than the two. */
 jxl_status jxl_canvas_from_modular(jxl_ctx* ctx, const jxl_modular_planes_desc* d, int32_t* id);
+/* The same result channels as a new set of UPSAMPLED float planes, k * height x k * width: Frame.upsample's loop over the frame's
+ * buffers (Frame.java:725-728) for all planes as ONE launch. Plane i is Frame.performUpsampling (Frame.java:217-260) of
+ * ImageBuffer.castToFloat (ImageBuffer.java:99-127; Frame.java:226-228) of the cropped channel: every tap is scale * (float)(a [+ b])
+ * as above -- plane[i].scale is the plane's own 1f / maxValue -- read through MathHelper.mirrorCoordinate (MathHelper.java:323-329)
+ * of the height x width crop, and the output is jxl_stage_upsample's, operation for operation (:233-256: window minimum from
+ * Float.MAX_VALUE, maximum from Float.MIN_VALUE, the sum from 0f in iy, ix order, the clamp). k is 2, 4 or 8; weights: k * k * 25
+ * floats as for jxl_stage_upsample (jxl_upsampling_weights). Every plane must be JXL_PLANE_FLOAT: the reference casts before it
+ * upsamples. Complete on return. Refused with nothing queued and *id untouched: everything jxl_canvas_from_modular refuses, with
+ * its status; JXL_ERR_INVALID_ARGUMENT for a k other than 2, 4 or 8, null weights, an int32 plane, and a k * height or k * width
+ * beyond what a set holds (2^31 - 1). */
+jxl_status jxl_canvas_from_modular_up(jxl_ctx* ctx, const jxl_modular_planes_desc* d, int32_t k, const float* weights, int32_t* id);
+/* The inverse of jxl_canvas_to_planes: planes 0..2 of the set become copies of the context's resident planes and are tagged float,
+ * whatever they were -- Frame.getBuffer of the colour channels (JXLCodestreamDecoder.java:528) after the stages that ran on the
+ * resident planes (Frame.renderSplines :739-746, synthesizeNoise :790-831), with the frame's other planes left where they are.
+ * Asynchronous. Refused with the set untouched: an unknown set, fewer than three planes, resident planes of another size than the
+ * set (JXL_ERR_INVALID_ARGUMENT); no resident planes (JXL_ERR_STATE). */
+jxl_status jxl_canvas_take_planes(jxl_ctx* ctx, int32_t id);
 /* jxl_stage_orient of every plane of the set, whatever its type (the kernels move 4-byte words); orientations 5-8 exchange the
  * set's height and width. JXL_ERR_STATE: an orientation outside 1..8, as jxl_planes_orient. */
 jxl_status jxl_canvas_orient(jxl_ctx* ctx, int32_t id, int32_t orientation);

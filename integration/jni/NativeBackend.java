@@ -200,6 +200,10 @@ public final class NativeBackend implements AutoCloseable {
     public native void canvasToPlanes(int id);                     // jxl_canvas_to_planes
     /** desc: {height, width, nPlanes, then per plane {channel, addChannel (-1: none), type}}; scales: one float per plane. */
     public native int canvasFromModular(int[] desc, float[] scales);   // jxl_canvas_from_modular -> the new set's id
+    /** The same channels as upsampled float planes (Frame.performUpsampling of castToFloat of each, Frame.java:217-260): desc and
+     *  scales as canvasFromModular's, every type 0 (float); k 2, 4 or 8; weights: k * k * 25 floats as planesUpsample's. */
+    public native int canvasFromModularUp(int[] desc, float[] scales, int k, float[] weights);   // jxl_canvas_from_modular_up -> the new set's id
+    public native void canvasTakePlanes(int id);                   // jxl_canvas_take_planes (canvasToPlanes' inverse: planes 0..2 <- the resident planes)
     public native void canvasOrient(int id, int orientation);      // jxl_canvas_orient
     // the writers on a set: params as the stage entries'; nothing goes up
     public native void canvasPngSamples(int id, int alphaPlane, ByteBuffer params, ByteBuffer out);   // jxl_canvas_png_samples (alphaPlane -1: none)

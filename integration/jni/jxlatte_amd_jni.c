@@ -1408,27 +1408,52 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasToPla
     CHECK(jxl_canvas_to_planes(c, id));
 }
 
-/* desc: {height, width, nPlanes, then per plane {channel, addChannel, type}}; scales: one float per plane */
-JNIEXPORT jint JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasFromModular(JNIEnv* e, jobject self, jintArray desc, jfloatArray scales) {
-    jxl_ctx* c = ctx_of(e, self);
+/* desc: {height, width, nPlanes, then per plane {channel, addChannel, type}}; scales: one float per plane. 0: an exception is pending */
+static int modular_planes_desc(JNIEnv* e, jintArray desc, jfloatArray scales, jxl_modular_planes_desc* d) {
     jint head[3];
-    int32_t id = -1;
-    if (!get_ints(e, desc, 3, head)) return -1;
-    if (head[2] > JXL_CANVAS_MAX_PLANES) { rethrow(e, NULL, JXL_ERR_UNSUPPORTED); return -1; }
-    if (head[2] < 1) { bad_arg(e, "jxlatte_amd: modular planes: plane count"); return -1; }
+    if (!get_ints(e, desc, 3, head)) return 0;
+    if (head[2] > JXL_CANVAS_MAX_PLANES) { rethrow(e, NULL, JXL_ERR_UNSUPPORTED); return 0; }
+    if (head[2] < 1) { bad_arg(e, "jxlatte_amd: modular planes: plane count"); return 0; }
     jint all[3 + 3 * JXL_CANVAS_MAX_PLANES];
     float sc[JXL_CANVAS_MAX_PLANES];
-    if (!get_ints(e, desc, 3 + 3 * head[2], all) || !get_floats(e, scales, head[2], sc)) return -1;
-    jxl_modular_planes_desc d;
-    memset(&d, 0, sizeof d);
-    d.height = all[0]; d.width = all[1]; d.n_planes = all[2];
-    for (int i = 0; i < d.n_planes; i++) {
+    if (!get_ints(e, desc, 3 + 3 * head[2], all) || !get_floats(e, scales, head[2], sc)) return 0;
+    memset(d, 0, sizeof *d);
+    d->height = all[0]; d->width = all[1]; d->n_planes = all[2];
+    for (int i = 0; i < d->n_planes; i++) {
         const jint* v = all + 3 + 3 * i;
-        d.plane[i].channel = v[0]; d.plane[i].add_channel = v[1]; d.plane[i].type = v[2]; d.plane[i].scale = sc[i];
+        d->plane[i].channel = v[0]; d->plane[i].add_channel = v[1]; d->plane[i].type = v[2]; d->plane[i].scale = sc[i];
     }
+    return 1;
+}
+
+JNIEXPORT jint JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasFromModular(JNIEnv* e, jobject self, jintArray desc, jfloatArray scales) {
+    jxl_ctx* c = ctx_of(e, self);
+    int32_t id = -1;
+    jxl_modular_planes_desc d;
+    if (!modular_planes_desc(e, desc, scales, &d)) return -1;
     const jxl_status st = jxl_canvas_from_modular(c, &d, &id);
     if (st != JXL_OK) { rethrow(e, c, st); return -1; }
     return id;
+}
+
+/* weights: k * k * 25 floats (jxl_upsampling_weights); a k the library refuses is handed on without them */
+JNIEXPORT jint JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasFromModularUp(JNIEnv* e, jobject self, jintArray desc, jfloatArray scales,
+        jint k, jfloatArray weights) {
+    jxl_ctx* c = ctx_of(e, self);
+    int32_t id = -1;
+    jxl_modular_planes_desc d;
+    float w[8 * 8 * 25];
+    if (!modular_planes_desc(e, desc, scales, &d)) return -1;
+    const int known = k == 2 || k == 4 || k == 8;
+    if (known && !get_floats(e, weights, k * k * 25, w)) return -1;
+    const jxl_status st = jxl_canvas_from_modular_up(c, &d, k, known ? w : NULL, &id);
+    if (st != JXL_OK) { rethrow(e, c, st); return -1; }
+    return id;
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasTakePlanes(JNIEnv* e, jobject self, jint id) {
+    jxl_ctx* c = ctx_of(e, self);
+    CHECK(jxl_canvas_take_planes(c, id));
 }
 
 JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasOrient(JNIEnv* e, jobject self, jint id, jint orientation) {

@@ -54,6 +54,10 @@ def parser():
                          "device_image): a Modular frame that is the whole image goes up once and stays (jxl_canvas_from_modular), "
                          "and with --device-canvas the canvas set becomes the image; add --device-png so that the writers read "
                          "the set and only the file's samples come down. The same bytes")
+    ap.add_argument("--device-frames", action="store_true",
+                    help="with --device-canvas: a Modular frame reaches the blend as a plane set made from the Modular context "
+                         "(JXLDecoder device_frames; jxl_canvas_from_modular, jxl_canvas_from_modular_up, jxl_canvas_take_planes): "
+                         "its encoded channels go up once and nothing comes down. The same bytes")
     return ap
 
 
@@ -80,7 +84,8 @@ def main(argv=None):
     backend = DeviceBackend(a.device)
     dec = JXLDecoder(a.input, backend=backend, sparse_coeffs=a.sparse_coeffs, device_splines=a.device_splines,
                      device_patches=a.device_patches, device_output=a.device_png, device_canvas=a.device_canvas,
-                     draw_varblocks=a.draw_varblocks, device_palette=a.device_palette, device_image=a.device_image)
+                     draw_varblocks=a.draw_varblocks, device_palette=a.device_palette, device_image=a.device_image,
+                     device_frames=a.device_frames)
     image = dec.decode()
     if image is None:
         print("jxlatte_amd: no frames", file=sys.stderr)
@@ -89,7 +94,8 @@ def main(argv=None):
     for i, st in enumerate(dec.stats):
         print("    frame %d: %s %dx%d, %d groups%s" % (i, st["encoding"], st["width"], st["height"], st["groups"],
                                                        (", canvas %s" % st["canvas"] if a.device_canvas else "") +
-                                                       (", image %s" % st["image"] if a.device_image else "")), file=sys.stderr)
+                                                       (", image %s" % st["image"] if a.device_image else "") +
+                                                       (", frame %s" % st["frame"] if a.device_frames else "")), file=sys.stderr)
     print("Decoded %dx%d in %.3f s" % (image.getWidth(), image.getHeight(), t1 - t0), file=sys.stderr)
     if a.output and output_format(a) == "pfm":
         with open(a.output, "wb") as f:

@@ -143,6 +143,8 @@ SIGNATURES = {
     "jxl_canvas_blend": (i32, [vp, C.POINTER(abi.CanvasBlendDesc)]),
     "jxl_canvas_to_planes": (i32, [vp, i32]),
     "jxl_canvas_from_modular": (i32, [vp, C.POINTER(abi.ModularPlanesDesc), pi]),
+    "jxl_canvas_from_modular_up": (i32, [vp, C.POINTER(abi.ModularPlanesDesc), i32, pf, pi]),
+    "jxl_canvas_take_planes": (i32, [vp, i32]),
     "jxl_canvas_orient": (i32, [vp, i32, i32]),
     "jxl_canvas_png_samples": (i32, [vp, i32, i32, C.POINTER(abi.PngParams), vp]),
     "jxl_canvas_color_peak": (i32, [vp, i32, C.POINTER(abi.ColorParams), pf]),

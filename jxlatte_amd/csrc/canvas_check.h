@@ -20,6 +20,17 @@ inline bool canvas_shape_ok(const jxl_canvas_shape* s) {
     return true;
 }
 
+// jxl_canvas_take_planes: set is null for an unknown id; planes_h <= 0: the context has no resident planes
+inline jxl_status canvas_take_check(const jxl_canvas_shape* set, int32_t planes_h, int32_t planes_w, const char** why) {
+    const char* dummy;
+    if (!why) why = &dummy;
+    if (!set) return *why = "canvas: unknown set", JXL_ERR_INVALID_ARGUMENT;
+    if (set->n < 3) return *why = "canvas: the set has fewer than three planes", JXL_ERR_INVALID_ARGUMENT;
+    if (planes_h <= 0 || planes_w <= 0) return *why = "no resident planes", JXL_ERR_STATE;
+    if (set->h != planes_h || set->w != planes_w) return *why = "canvas: the resident planes have another size than the set", JXL_ERR_INVALID_ARGUMENT;
+    return JXL_OK;
+}
+
 // JXL_OK and ops[0 .. n_chan), or the status with the reason in *why
 inline jxl_status canvas_blend_check(const jxl_canvas_blend_desc* d, const jxl_canvas_shape* canvas, const jxl_canvas_shape* frame,
                                      const jxl_canvas_shape* ref, CanvasChanOp* ops, const char** why) {

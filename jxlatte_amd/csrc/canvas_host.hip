@@ -91,6 +91,28 @@ jxl_status new_set(jxl_ctx* c, const CtxLink& l, int32_t n, int32_t h, int32_t w
     return JXL_OK;
 }
 
+// The settled result list of the Modular context, checked against `d` (modplanes_check.h); upsampled: for
+// jxl_canvas_from_modular_up, with its factor and weights. Nothing has been queued when this refuses.
+jxl_status modular_results(jxl_ctx* c, const jxl_modular_planes_desc* d, bool upsampled, int32_t up, const float* weights,
+                           std::vector<ModResult>* res) {
+    bool ran = false;
+    jxl_status st = ctx_modular_out(c, res, &ran);  // (settled: a speculative plan has been verified or redone)
+    if (st) return st;
+    ModPlaneShape shapes[64];
+    std::vector<ModPlaneShape> more;
+    ModPlaneShape* sh = shapes;
+    try {
+        if (res->size() > 64) more.resize(res->size()), sh = more.data();
+    } catch (const std::bad_alloc&) {
+        return ctx_fail(c, JXL_ERR_OOM, "canvas: host allocation failed");
+    }
+    for (size_t i = 0; i < res->size(); i++) sh[i] = ModPlaneShape{(*res)[i].h, (*res)[i].w};
+    const char* why = "";
+    st = !upsampled ? modplanes_check(d, sh, (int32_t)res->size(), ran, &why)
+                    : modplanes_up_check(d, sh, (int32_t)res->size(), ran, up, weights != nullptr, &why);
+    return st ? ctx_fail(c, st, why) : JXL_OK;
+}
+
 void shape_of(const CanvasSet* k, jxl_canvas_shape* s) {
     s->n = k->n, s->h = k->h, s->w = k->w;
     for (int i = 0; i < JXL_CANVAS_MAX_PLANES; i++) s->types[i] = i < k->n ? k->type[i] : 0;
@@ -263,19 +285,7 @@ jxl_status jxl_canvas_from_modular(jxl_ctx* c, const jxl_modular_planes_desc* d,
     jxl_status st = ctx_link(c, &l);
     if (st) return st;
     std::vector<ModResult> res;
-    bool ran = false;
-    if ((st = ctx_modular_out(c, &res, &ran))) return st;  // (settled: a speculative plan has been verified or redone)
-    ModPlaneShape shapes[64];
-    std::vector<ModPlaneShape> more;
-    ModPlaneShape* sh = shapes;
-    try {
-        if (res.size() > 64) more.resize(res.size()), sh = more.data();
-    } catch (const std::bad_alloc&) {
-        return ctx_fail(c, JXL_ERR_OOM, "canvas: host allocation failed");
-    }
-    for (size_t i = 0; i < res.size(); i++) sh[i] = ModPlaneShape{res[i].h, res[i].w};
-    const char* why = "";
-    if ((st = modplanes_check(d, sh, (int32_t)res.size(), ran, &why))) return ctx_fail(c, st, why);
+    if ((st = modular_results(c, d, false, 0, nullptr, &res))) return st;
     if (!id) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: bad arguments");
     int32_t types[JXL_CANVAS_MAX_PLANES];
     for (int i = 0; i < d->n_planes; i++) types[i] = d->plane[i].type;
@@ -296,6 +306,54 @@ jxl_status jxl_canvas_from_modular(jxl_ctx* c, const jxl_modular_planes_desc* d,
     }
     launch_modplanes(a, l.stream);
     CV_HIP(c, hipGetLastError());
+    *id = new_id;
+    return JXL_OK;
+}
+
+jxl_status jxl_canvas_from_modular_up(jxl_ctx* c, const jxl_modular_planes_desc* d, int32_t up, const float* weights, int32_t* id) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    std::vector<ModResult> res;
+    if ((st = modular_results(c, d, true, up, weights, &res))) return st;
+    if (!id) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: bad arguments");
+    // the weights go up first: nothing is left behind when their allocation fails
+    const size_t wbytes = sizeof(float) * 25 * (size_t)up * (size_t)up;
+    float* dw = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&dw), wbytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return ctx_fail(c, JXL_ERR_OOM, "device allocation failed (upsampling weights)");
+    }
+    if (hipMemcpy(dw, weights, wbytes, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(dw);
+        return ctx_fail(c, JXL_ERR_DEVICE, "upload of the upsampling weights failed");
+    }
+    int32_t types[JXL_CANVAS_MAX_PLANES];
+    for (int i = 0; i < d->n_planes; i++) types[i] = JXL_PLANE_FLOAT;
+    CanvasSet* k;
+    int32_t new_id = -1;
+    if ((st = new_set(c, l, d->n_planes, d->height * up, d->width * up, types, &k, &new_id))) {
+        (void)hipFree(dw);
+        return st;
+    }
+    ModUpArgs a{};
+    a.h = d->height, a.w = d->width, a.n = d->n_planes;
+    a.weights = dw;
+    for (int i = 0; i < d->n_planes; i++) {
+        const jxl_modular_plane& p = d->plane[i];
+        ModUpPlane& q = a.p[i];
+        q.a = res[(size_t)p.channel].d;
+        q.b = p.add_channel >= 0 ? res[(size_t)p.add_channel].d : nullptr;
+        q.out = reinterpret_cast<float*>(k->plane(i));
+        q.pitch = res[(size_t)p.channel].w;
+        q.scale = p.scale;
+    }
+    launch_modplanes_up(a, up, l.stream);
+    const hipError_t e = hipGetLastError();
+    const hipError_t e2 = hipStreamSynchronize(l.stream);  // the weights are freed on return, as jxl_planes_upsample frees its own
+    (void)hipFree(dw);
+    if (e != hipSuccess || e2 != hipSuccess) return ctx_fail(c, JXL_ERR_DEVICE, hipGetErrorString(e != hipSuccess ? e : e2));
     *id = new_id;
     return JXL_OK;
 }
@@ -340,6 +398,25 @@ jxl_status jxl_canvas_to_planes(jxl_ctx* c, int32_t id) {
     float* p[3];
     if ((st = ctx_planes_set(c, k->h, k->w, p))) return st;
     for (int i = 0; i < 3; i++) CV_HIP(c, hipMemcpyAsync(p[i], k->plane(i), k->plane_bytes(), hipMemcpyDeviceToDevice, l.stream));
+    return JXL_OK;
+}
+
+jxl_status jxl_canvas_take_planes(jxl_ctx* c, int32_t id) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    CanvasSet* k = find(l, id);
+    jxl_canvas_shape sk;
+    if (k) shape_of(k, &sk);
+    int h = 0, w = 0;
+    float* p[3];
+    if (k && ctx_planes_get(c, &h, &w, p) != JXL_OK) h = w = 0;
+    const char* why = "";
+    if ((st = canvas_take_check(k ? &sk : nullptr, h, w, &why))) return ctx_fail(c, st, why);
+    for (int i = 0; i < 3; i++) {
+        CV_HIP(c, hipMemcpyAsync(k->plane(i), p[i], k->plane_bytes(), hipMemcpyDeviceToDevice, l.stream));
+        k->type[i] = JXL_PLANE_FLOAT;
+    }
     return JXL_OK;
 }
 

@@ -561,6 +561,20 @@ struct ModPlanesArgs {
     ModPlane p[JXL_CANVAS_MAX_PLANES];
 };
 void launch_modplanes(const ModPlanesArgs& p, hipStream_t s);
+// jxl_canvas_from_modular_up's kernel (k_modplanes.hip): plane i of the set, k*h x k*w floats, from the h x w crop of one or two
+// result channels of one pitch; weights: k * k * 25 floats in device memory
+struct ModUpPlane {
+    const int32_t *a, *b;  // b: null, or the channel added first
+    float* out;            // k*h x k*w floats
+    int32_t pitch;         // the channels' width
+    float scale;
+};
+struct ModUpArgs {
+    int32_t h, w, n, reserved;  // the crop; planes
+    const float* weights;
+    ModUpPlane p[JXL_CANVAS_MAX_PLANES];
+};
+void launch_modplanes_up(const ModUpArgs& p, int k, hipStream_t s);
 
 void launch_idct2d_single(const float* src, float* dst, int h, int w, int transposed, const float* lut, hipStream_t s);
 void launch_fdct2d_single(const float* src, float* dst, int h, int w, const float* lut, hipStream_t s);

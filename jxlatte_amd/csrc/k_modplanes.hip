@@ -11,8 +11,20 @@
 // lane's addresses are only 4-byte aligned, so the vectors are declared with that alignment and the compiler is told the
 // truth (gfx950 code objects run with unaligned access enabled: global_load_dwordx4 / global_store_dwordx4). The last group of
 // a row whose width is no multiple of 4 loads and stores sample by sample. Plain global loads and stores, 64-bit offsets, no LDS.
+//
+//   k_modplanes_up<K>, per plane i (blockIdx.y): Frame.performUpsampling (Frame.java:217-260) of castToFloat of the cropped
+//   channel, as ONE launch for all planes (jxl_canvas_from_modular_up):
+//     1. a tap is sample (ny, nx) of the h x w crop, ny / nx through MathHelper.mirrorCoordinate: scale * (float)(a [+ b]) as above
+//     2. the output is k_upsample's (k_post.hip), operation for operation: 25 taps, their window minimum from Float.MAX_VALUE and
+//        maximum from Float.MIN_VALUE (kept as the reference has it), the sum from 0f in iy, ix order, the clamp
+//   Shape: k_upsample's -- one thread per (input pixel, ky), K contiguous outputs, the K * K * 25 weights in LDS. Every thread
+//   converts its own 25 taps (no converted tile in LDS): 25 v_cvt_f32_i32 and 25 more v_mul_f32 per thread, +13 .. 19 % VALU
+//   instructions against k_upsample<K>; the int32 taps of neighbouring lanes come from the same cache lines as k_upsample's
+//   float ones, and the kernel keeps k_upsample's resource row.
 #include "jxl_internal.h"
 #include "modular_tend.h"
+
+#include <algorithm>
 
 namespace jxl {
 namespace {
@@ -54,7 +66,68 @@ __global__ __launch_bounds__(256) void k_modplanes(const ModPlanesArgs p) {
     }
 }
 
+// MathHelper.mirrorCoordinate (MathHelper.java:323-329)
+__device__ __forceinline__ int mirror_c(int c, int size) {
+    while (c < 0 || c >= size) {
+        const int tc = ~c;
+        c = tc >= 0 ? tc : (size << 1) + tc;
+    }
+    return c;
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void k_modplanes_up(const ModUpArgs p) {
+    __shared__ float wl[K * K * 25];
+    for (int i = threadIdx.x; i < K * K * 25; i += 256) wl[i] = p.weights[i];
+    __syncthreads();
+    const ModUpPlane q = p.p[blockIdx.y];
+    const bool add = q.b != nullptr;
+    const int h = p.h, w = p.w;
+    const int64_t n = (int64_t)h * w * K;
+    const int64_t ow = (int64_t)w * K;
+    for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        // i = (y*K + ky) * w + x: consecutive threads walk along an output row
+        const int x = (int)(i % w);
+        const int64_t oy = i / w;
+        const int y = (int)(oy / K), ky = (int)(oy % K);
+        float s[25];
+        float mn = 3.4028234663852886e38f;
+        float mx = 1.4e-45f;  // Float.MIN_VALUE (Frame.java:241), not -MAX_VALUE: kept as the reference has it
+#pragma unroll
+        for (int iy = 0; iy < 5; iy++) {
+            const int64_t row = (int64_t)mirror_c(y + iy - 2, h) * q.pitch;
+#pragma unroll
+            for (int ix = 0; ix < 5; ix++) {
+                const int64_t at = row + mirror_c(x + ix - 2, w);
+                int32_t t = q.a[at];
+                if (add) t = wadd(t, q.b[at]);
+                const float v = q.scale * (float)t;
+                s[iy * 5 + ix] = v;
+                if (v < mn) mn = v;
+                if (v > mx) mx = v;
+            }
+        }
+        float* o = q.out + oy * ow + (int64_t)x * K;
+#pragma unroll
+        for (int kx = 0; kx < K; kx++) {
+            const float* wt = wl + (ky * K + kx) * 25;
+            float total = 0.0f;
+#pragma unroll
+            for (int t = 0; t < 25; t++) total += wt[t] * s[t];
+            o[kx] = total < mn ? mn : total > mx ? mx : total;
+        }
+    }
+}
+
 }  // namespace
+
+void launch_modplanes_up(const ModUpArgs& p, int k, hipStream_t s) {
+    if (p.h <= 0 || p.w <= 0 || p.n <= 0 || p.n > JXL_CANVAS_MAX_PLANES || !p.weights) return;
+    const dim3 g((unsigned)std::min<int64_t>(((int64_t)p.h * p.w * k + 255) / 256, 4096), (unsigned)p.n);
+    if (k == 2) hipLaunchKernelGGL(k_modplanes_up<2>, g, dim3(256), 0, s, p);
+    else if (k == 4) hipLaunchKernelGGL(k_modplanes_up<4>, g, dim3(256), 0, s, p);
+    else if (k == 8) hipLaunchKernelGGL(k_modplanes_up<8>, g, dim3(256), 0, s, p);
+}
 
 void launch_modplanes(const ModPlanesArgs& p, hipStream_t s) {
     if (p.h <= 0 || p.w <= 0 || p.n <= 0 || p.n > JXL_CANVAS_MAX_PLANES) return;

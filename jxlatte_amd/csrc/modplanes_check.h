@@ -1,5 +1,5 @@
-// jxl_modular_planes_desc: what jxl_canvas_from_modular refuses. Plain C++ (no device code, no context), so the checks can be
-// compiled and run on their own (tools/native/modplanes_check.cpp).
+// jxl_modular_planes_desc: what jxl_canvas_from_modular and jxl_canvas_from_modular_up refuse. Plain C++ (no device code, no
+// context), so the checks can be compiled and run on their own (tools/native/modplanes_check.cpp, modplanes_up_check.cpp).
 #pragma once
 #include <cstdint>
 
@@ -31,6 +31,22 @@ inline jxl_status modplanes_check(const jxl_modular_planes_desc* d, const ModPla
         const ModPlaneShape& b = out[p.add_channel];
         if (b.h != a.h || b.w != a.w) return *why = "modular planes: the added channel has another size", JXL_ERR_INVALID_ARGUMENT;
     }
+    return JXL_OK;
+}
+
+// jxl_canvas_from_modular_up: everything above, then what the upsampling adds. have_weights: the weights pointer is not null
+inline jxl_status modplanes_up_check(const jxl_modular_planes_desc* d, const ModPlaneShape* out, int32_t n_out, bool ran, int32_t k,
+                                     bool have_weights, const char** why) {
+    const char* dummy;
+    if (!why) why = &dummy;
+    const jxl_status st = modplanes_check(d, out, n_out, ran, why);
+    if (st) return st;
+    if (k != 2 && k != 4 && k != 8) return *why = "modular planes: upsampling factor other than 2, 4 or 8", JXL_ERR_INVALID_ARGUMENT;
+    if (!have_weights) return *why = "modular planes: null weights", JXL_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < d->n_planes; i++)  // the reference casts before it upsamples (Frame.java:228)
+        if (d->plane[i].type != JXL_PLANE_FLOAT) return *why = "modular planes: an upsampled plane is a float plane", JXL_ERR_INVALID_ARGUMENT;
+    if ((int64_t)d->height * k > INT32_MAX || (int64_t)d->width * k > INT32_MAX)
+        return *why = "modular planes: the upsampled size is beyond what a set holds", JXL_ERR_INVALID_ARGUMENT;
     return JXL_OK;
 }
 

@@ -1008,7 +1008,7 @@ def _tt_dims():
 
 class JXLDecoder:
     def __init__(self, source, backend=None, sparse_coeffs=False, device_splines=False, device_patches=False, device_output=False,
-                 device_canvas=False, draw_varblocks=False, device_palette=False, device_image=False):
+                 device_canvas=False, draw_varblocks=False, device_palette=False, device_image=False, device_frames=False):
         """sparse_coeffs: hand the HF coefficients to the backend as lists of non-zero entries (jxf_get_coeffs_sparse ->
         jxl_vardct_put_group_sparse), not as dense planes; same pixels.
         device_splines: Frame.renderSplines runs in the backend (jxl_planes_splines on the resident planes, jxl_stage_splines
@@ -1054,7 +1054,21 @@ class JXLDecoder:
         device_canvas, the canvas set at the end of decode() becomes the image's (cloned while the animation continues).
         Every other frame runs jxf_apply_transforms with the usual hooks and goes on exactly as without the switch.
         stats[k]["image"]: "device set (modular frame)", "device set (canvas)" or "host: <reason>". device_output's direct path
-        is unchanged and comes first for the frames it covers. A backend without a context is an error."""
+        is unchanged and comes first for the frames it covers. A backend without a context is an error.
+        device_frames: with device_canvas, while the canvas is a plane set, a Modular frame reaches the blend as a plane set made
+        from the Modular context, not through the host. The front-end decodes every frame with its frame-level transforms
+        deferred (as device_image does); for a frame that frame_set_rule accepts -- a chain that is one plan, three int32 colour
+        planes, no patches, restoration filter, YCbCr or XYB, extra channels upsampled as the colours are, no `trace` listener;
+        position, blend modes, reference slots, noise and splines are free -- the encoded channels go up once, the plan runs,
+        and the frame's set is jxl_canvas_from_modular (int32 colours where no stage follows, float colours at 1f / maxValue
+        where noise or splines do) or jxl_canvas_from_modular_up (upsampling 2, 4, 8: every plane cast with its own depth and
+        upsampled in one launch). Noise and splines run on the resident planes between jxl_canvas_to_planes and
+        jxl_canvas_take_planes; splines without device_splines still bring the three colour planes down and up
+        (stats[k]["plane_moves"]). The extra channels never move. The same bits as without the switch. Every other frame runs
+        jxf_apply_transforms with the usual hooks and goes on as ever. stats[k]["frame"]: "device set (modular)", "host: <the
+        first condition that failed>" or "host: device_frames is off". device_image's "modular frame" route and device_output's
+        direct path come first for the frames they cover."""
+        self.device_frames = bool(device_frames)
         self.device_image = bool(device_image)
         self.device_palette = bool(device_palette)
         self.draw_varblocks = bool(draw_varblocks)
@@ -1183,14 +1197,15 @@ class JXLDecoder:
         from . import host
         return host.getUpWeights(k, packed)
 
-    def _chained_tail(self, fr, rp, buffers, colors, save, xyb_done, keep=False):
+    def _chained_tail(self, fr, rp, buffers, colors, save, xyb_done, keep=False, upsampled=False):
         """Frame.upsample .. performColorTransforms (JXLCodestreamDecoder.java:628-637) of the three colour planes with the
         samples moving between host and device only where the next stage lives on the other side: upsampling, noise and the
         colour transforms are device stages on host.ResidentPlanes, and so are the splines with `device_splines`; the
         saveBeforeCT reference, the patches and (by default) the splines are host stages (as in the reference). `rp` is the
         VarDCT frame's resident result, or None when the colour planes start as the host arrays buffers[:3] (Modular frames).
         The extra channels in buffers[3:] are host arrays throughout.
-        keep: planes that are on the device at the end stay there (buffers[:3] are then not touched); returns them, or None."""
+        keep: planes that are on the device at the end stay there (buffers[:3] are then not touched); returns them, or None.
+        upsampled: `rp` is already past Frame.upsample (_modular_frame_set)."""
         info, be = self.info, self.backend
         moves = []
 
@@ -1211,7 +1226,7 @@ class JXLDecoder:
                 moves.append("d2h")
 
         dev_patches = getattr(self, "device_patches", False) and bool(fr.num_patches)
-        if fr.upsampling > 1:
+        if fr.upsampling > 1 and not upsampled:
             on_device().upsample(fr.upsampling, self._up_weights(fr.upsampling))
         if save and fr.save_before_ct:
             if dev_patches and rp is not None:  # a copy comes down, the planes stay
@@ -1354,13 +1369,62 @@ class JXLDecoder:
         for _, s_ in done.values():
             s_.release()
 
-    def _blend_frame_device(self, fr, buffers, rp):
+    def _count_frame(self, fr):
+        """the frame counters initializeNoise's seed is made of (JXLCodestreamDecoder.java:620-627); returns whether the frame is
+        saved as a reference"""
+        visible = fr.type in (REGULAR_FRAME, SKIP_PROGRESSIVE) and (fr.duration != 0 or fr.is_last)
+        if visible:
+            self.visibleFrames += 1
+            self.invisibleFrames = 0
+        else:
+            self.invisibleFrames += 1
+        return (fr.save_as_reference != 0 or fr.duration == 0) and not fr.is_last and fr.type != LF_FRAME
+
+    def _frame_done(self, fr, save, bus0):
+        """the end of a frame's turn (:656-658): the canvas into its reference slot, the frame's bus traffic into the stats;
+        returns whether decode() has its image"""
+        if save and not fr.save_before_ct:
+            self.reference[fr.save_as_reference] = self.canvas
+        bus1 = tuple(getattr(getattr(self.backend, "ctx", None), "blend_bus", (0, 0)))
+        self.stats[-1]["blend_bus"] = (bus1[0] - bus0[0], bus1[1] - bus0[1])  # bytes up, bytes down: patches and blendFrame
+        return fr.is_last or fr.duration != 0
+
+    def _canvas_frame(self, fr, buffers, rp, colors, fset=None):
+        """one frame onto the canvas set (:640-655): the set is made when the first frame reaches it, copied when a reference
+        slot shares it, and blended in one launch -- or everything lands and the host blends. The frame's planes: the host
+        arrays `buffers` with the resident colour planes `rp`, or the ready-made set `fset` (device_frames)"""
+        info, be = self.info, self.backend
+        if not self._is_set(self.canvas):  # :640-643: every plane of the type of the frame's first buffer
+            first_type = fset.dtypes[0] if fset is not None else np.dtype(np.float32) if rp is not None else buffers[0].dtype
+            self.canvas = be.host.DeviceCanvas.create(be.ctx, [first_type] * len(self.canvas), info.height, info.width)
+        why = None
+        if fr.type in (REGULAR_FRAME, SKIP_PROGRESSIVE):
+            if any(self.reference[i] is self.canvas and i != fr.save_as_reference for i in range(4)):
+                self.canvas = self.canvas.clone()  # :645-653
+            why = self._blend_frame_device(fr, buffers, rp, fset)
+        if fset is not None and why is not None:  # the frame's planes come down from its set
+            buffers = [fset.download(c) for c in range(len(fset))]
+        if fset is not None and not any(s_ is fset for s_ in self._dead_sets):
+            fset.release()
+        if why is not None:
+            # landing: the sets come down, the frame's colour planes too, and this frame is blended as without the switch
+            # (the copy-on-write above has been made already, on the device)
+            self._land(why)
+            self.stats[-1]["canvas"] = "landed: " + why
+            if rp is not None:
+                planes = rp.download()
+                for c in range(3):
+                    buffers[c] = planes[c]
+            self._blend_frame(fr, buffers, colors)
+
+    def _blend_frame_device(self, fr, buffers, rp, fset=None):
         """blendFrame on the plane sets: the type plan, the frame's planes into a set (its resident colour planes without the
-        host), the hoisted casts, one launch. Returns None, or the reason to land (nothing has been touched then)."""
+        host, or the ready-made set `fset`), the hoisted casts, one launch. Returns None, or the reason to land (nothing has
+        been touched then)."""
         host, ctx = self.backend.host, self.backend.ctx
         info, cv = self.info, self.canvas
         f32 = np.dtype(np.float32)
-        ftypes = [f32] * 3 + [b.dtype for b in buffers[3:]] if rp is not None else [b.dtype for b in buffers]
+        ftypes = fset.dtypes if fset is not None else [f32] * 3 + [b.dtype for b in buffers[3:]] if rp is not None else [b.dtype for b in buffers]
         refs = self.reference
         ref_types = [None if r is None else "canvas" if r is cv else r.dtypes if self._is_set(r) else
                      [None if b is None else b.dtype for b in r] for r in refs]
@@ -1369,11 +1433,14 @@ class JXLDecoder:
             return plan.verdict[len("land: "):]
         if plan.rect is None:
             return None
-        shape = rp.shape if rp is not None else buffers[0].shape
-        if any(tuple(b.shape) != tuple(shape) for b in (buffers[3:] if rp is not None else buffers)):
-            return "the frame's planes differ in size"
+        if fset is None:
+            shape = rp.shape if rp is not None else buffers[0].shape
+            if any(tuple(b.shape) != tuple(shape) for b in (buffers[3:] if rp is not None else buffers)):
+                return "the frame's planes differ in size"
         self._release_dead()
-        if rp is not None:
+        if fset is not None:  # (device_frames: the planes of one launch, one size by construction)
+            pass
+        elif rp is not None:
             fset = host.DeviceCanvas.fromPlanes(ctx, [b.dtype for b in buffers[3:]])
             for i, b in enumerate(buffers[3:]):
                 fset.upload(3 + i, b)
@@ -1607,18 +1674,40 @@ class JXLDecoder:
 
     # -- the decode loop (JXLCodestreamDecoder.decode :546-677) ----------------------------------------------------
     # -- the image as a device plane set (device_image) -----------------------------------------------------------
-    def _modular_frame_route(self, fr, colors, colors_img):
-        """None when the frame qualifies for device_image's "modular frame" route, else the first condition that fails. The
-        chain is looked at first after the encoding: it is what tells the committed images apart."""
-        info = self.info
+    @staticmethod
+    def _one_plan_chain_rule(fr, kinds):
+        """what device_image's "modular frame" route and device_frames ask of the frame-level stream: a Modular frame whose
+        chain is one plan of the Modular context. None, or the condition that fails"""
         if fr.encoding != MODULAR:
             return "not a Modular frame"
-        kinds = [t["kind"] for t in self.fe.transforms()]
         R, P, S = frontend.TRANSFORM_RCT, frontend.TRANSFORM_PALETTE, frontend.TRANSFORM_SQUEEZE
         if P in kinds:
             return "a Palette in the frame-level chain"
         if kinds not in ([], [R], [S], [R, S]):
             return "a frame-level chain that is not one plan ([], [RCT], [Squeeze] or [RCT, Squeeze])"
+        return None
+
+    @staticmethod
+    def _int_rgb_planes_rule(info, fr, colors, colors_img):
+        """the other half the two routes share: three int32 colour planes that reach the blend as decodeFrame leaves them, in a
+        set. None, or the condition that fails"""
+        if fr.gab or fr.epf_iters > 0 or fr.do_ycbcr:
+            return "a restoration filter or YCbCr"
+        if info.xyb_encoded:
+            return "an XYB image"
+        if info.exp_bits != 0 or colors != 3 or colors_img != 3:
+            return "colour planes that are not three int32 planes"
+        if 3 + info.num_extra > abi.CANVAS_MAX_PLANES or fr.num_modular_channels < 1:
+            return "more planes than a set holds"
+        return None
+
+    def _modular_frame_route(self, fr, colors, colors_img):
+        """None when the frame qualifies for device_image's "modular frame" route, else the first condition that fails. The
+        chain is looked at first after the encoding: it is what tells the committed images apart."""
+        info = self.info
+        why = self._one_plan_chain_rule(fr, [t["kind"] for t in self.fe.transforms()] if fr.encoding == MODULAR else [])
+        if why is not None:
+            return why
         if fr.type != REGULAR_FRAME or not fr.is_last or fr.lf_level != 0:
             return "not a regular last frame"
         if self._is_set(self.canvas) or self.canvas[0] is not None or fr.x0 != 0 or fr.y0 != 0:
@@ -1630,18 +1719,62 @@ class JXLDecoder:
             return "a blend mode other than REPLACE"
         if fr.num_patches or fr.has_splines or fr.has_noise:
             return "patches, splines or noise"
-        if fr.gab or fr.epf_iters > 0 or fr.do_ycbcr:
-            return "a restoration filter or YCbCr"
-        if info.xyb_encoded:
-            return "an XYB image"
-        if info.exp_bits != 0 or colors != 3 or colors_img != 3:
-            return "colour planes that are not three int32 planes"
-        if 3 + info.num_extra > abi.CANVAS_MAX_PLANES or fr.num_modular_channels < 1:
-            return "more planes than a set holds"
+        return self._int_rgb_planes_rule(info, fr, colors, colors_img)
+
+    @staticmethod
+    def frame_set_rule(info, fr, kinds, traced=False):
+        """device_frames: None when the header fields say that a frame can reach the resident canvas as a plane set made from
+        the Modular context (_modular_frame_set), else the first condition that fails. info: the image header; fr: the frame
+        header; kinds: the kinds of the frame-level transform chain in bitstream order; traced: a `trace` listener is set.
+        Position, blend modes, is_last, the reference slots, noise and splines are free."""
+        why = JXLDecoder._one_plan_chain_rule(fr, kinds)
+        if why is not None:
+            return why
+        if fr.type not in (REGULAR_FRAME, SKIP_PROGRESSIVE) or fr.lf_level != 0:
+            return "not a regular or skip-progressive frame of LF level 0"
+        if fr.num_patches:
+            return "patches"
+        colors_img = 1 if info.colour_space == CE_GRAY else 3
+        colors = 3 if info.xyb_encoded else colors_img  # (_colors of a Modular frame)
+        why = JXLDecoder._int_rgb_planes_rule(info, fr, colors, colors_img)
+        if why is not None:
+            return why
+        save = (fr.save_as_reference != 0 or fr.duration == 0) and not fr.is_last
+        if save and fr.save_before_ct:
+            return "saved before the colour transform"
+        if any(fr.ec_upsampling[i] != fr.upsampling for i in range(info.num_extra)):
+            return "an extra channel whose upsampling is not the colours'"
+        if fr.upsampling not in (1, 2, 4, 8):
+            return "an upsampling factor other than 1, 2, 4 or 8"
+        if traced:
+            return "a trace listener is set"
         return None
 
-    def _modular_frame_image(self, fr):
-        """device_image, route "modular frame": the encoded channels up once, one plan, one set; nothing comes down"""
+    def _frame_set_route(self, fr, direct):
+        """stats[k]["frame"] of a frame under device_frames: "device set (modular)", or "host: <why not>". The switch acts only
+        while the canvas is a device set; the header's part is frame_set_rule"""
+        if not getattr(self, "device_canvas", False):
+            return "host: device_canvas is off"
+        if not hasattr(self.backend, "ctx"):
+            raise RuntimeError("device_canvas needs a backend with a device context")
+        if direct:
+            return "host: device_output's direct path"
+        if self._landed is not None:
+            return "host: the canvas has landed (%s)" % self._landed
+        kinds = [t["kind"] for t in self.fe.transforms()] if fr.encoding == MODULAR else []
+        why = self.frame_set_rule(self.info, fr, kinds, getattr(self, "trace", None) is not None)
+        return "device set (modular)" if why is None else "host: " + why
+
+    def _direct_frame(self, fr, resident, colors_img):
+        """device_output: this frame is the image (the conditions of __init__'s docstring that the header settles)"""
+        info = self.info
+        return getattr(self, "device_output", False) and resident and colors_img == 3 and fr.type == REGULAR_FRAME and \
+            bool(fr.is_last) and fr.lf_level == 0 and not self._is_set(self.canvas) and self.canvas[0] is None and fr.y0 == 0 and fr.x0 == 0 and \
+            fr.width * fr.upsampling == info.width and fr.height * fr.upsampling == info.height and fr.blend_mode == abi.BLEND_REPLACE
+
+    def _modular_plan_run(self):
+        """the frame-level stream's pending chain as ONE plan of the Modular context: the encoded channels go up once, from the
+        front-end's own buffers (jxl_modular_begin), and the plan is queued. Returns the host.ModularStream"""
         info, be, fe = self.info, self.backend, self.fe
         host = be.host
         chans = [fe.modular_channel(i, copy=False)[0] for i in range(fe.modular_channel_count())]
@@ -1657,6 +1790,50 @@ class JXLDecoder:
         n = 3 + info.num_extra
         if be.ctx.lib.jxl_modular_out_count(be.ctx.h) != n:
             raise InvalidBitstreamException("the frame-level stream does not hold the frame's %d channels" % n)
+        return ms
+
+    def _modular_frame_set(self, fr, save):
+        """device_frames: the frame's buffers after Frame.upsample .. performColorTransforms (JXLCodestreamDecoder.java:628-637)
+        as a plane set made from the Modular context, with the types the default path's buffers have at the blend"""
+        info, be = self.info, self.backend
+        host = be.host
+        self._modular_plan_run()
+        f32, k = np.dtype(np.float32), fr.upsampling
+        tail = bool(fr.has_noise or fr.has_splines)
+
+        def inv_max(depth):  # ImageBuffer.castToFloat's factor (ImageBuffer.java:112-127), as _to_float forms it
+            return float(F(F(1) / F((1 << depth) - 1)))
+        if k > 1:  # Frame.performUpsampling casts every plane with its own depth first (Frame.java:226-228); a float plane stays
+            planes = [(c, -1, f32, inv_max(info.bits_per_sample)) for c in range(3)]
+            planes += [(3 + i, -1, f32, 1.0 if info.ec_exp_bits[i] != 0 else inv_max(info.ec_bits[i])) for i in range(info.num_extra)]
+            fset = host.DeviceCanvas.fromModularUp(be.ctx, fr.height, fr.width, planes, k, self._up_weights(k))
+        else:
+            # the colour planes are float exactly where the default path's are: every device stage casts them (Frame.java:796)
+            planes = [(c, -1, f32, inv_max(info.bits_per_sample)) if tail else (c, -1, np.int32, 1.0) for c in range(3)]
+            planes += [(3 + i, -1, f32 if info.ec_exp_bits[i] != 0 else np.int32, 1.0) for i in range(info.num_extra)]
+            fset = host.DeviceCanvas.fromModular(be.ctx, fr.height, fr.width, planes)
+        self.stats[-1]["plane_moves"] = []
+        if tail:
+            try:
+                buffers = [None] * 3
+                rp = self._chained_tail(fr, fset.toPlanes(), buffers, 3, save, True, keep=True, upsampled=True)
+                if rp is not None:
+                    fset.takePlanes()
+                else:  # the last stage was a host stage (splines without device_splines): its planes go up into the set
+                    for c in range(3):
+                        fset.upload(c, buffers[c])
+                    self.stats[-1]["plane_moves"].append("h2d")
+            except Exception:
+                fset.release()
+                raise
+        return fset
+
+    def _modular_frame_image(self, fr):
+        """device_image, route "modular frame": the encoded channels up once, one plan, one set; nothing comes down"""
+        info, be = self.info, self.backend
+        host = be.host
+        ms = self._modular_plan_run()
+        n = 3 + info.num_extra
         if getattr(self, "trace", None) is not None:  # a listener wants the samples: copies come down, the result stays
             self._trace("mod", ms.getDecodedBuffer(), False)
         planes = [(c, -1, np.int32, 1.0) for c in range(3)]
@@ -1685,9 +1862,10 @@ class JXLDecoder:
             dev_image = getattr(self, "device_image", False)
             if dev_image and not hasattr(be, "ctx"):
                 raise RuntimeError("device_image needs a backend with a device context")
+            dev_frames = getattr(self, "device_frames", False)
             hooks = (be.squeeze, be.rct, be.palette if dev_palette else None)
             try:
-                if dev_image:  # the frame-level transforms wait until the route is known
+                if dev_image or dev_frames:  # the frame-level transforms wait until the route is known
                     self.fe.set_defer_transforms(True)
                 fr = self.fe.next_frame(*hooks)
             except frontend.FrontendError as e:
@@ -1709,11 +1887,18 @@ class JXLDecoder:
                     image = self._modular_frame_image(fr)
                     bus1 = tuple(getattr(be.ctx, "blend_bus", (0, 0)))
                     self.stats[-1].update(image="device set (modular frame)", output="device", canvas="host",
+                                          frame="host: device_image's modular frame route" if dev_frames else "host: device_frames is off",
                                           blend_bus=(bus1[0] - bus0[0], bus1[1] - bus0[1]))
                     if dev_palette:
                         self.stats[-1]["palette"] = []
                     return image
                 self.stats[-1]["image"] = "host: " + why
+            colors = self._colors(fr)
+            resident = getattr(be, "resident", False) and colors == 3  # row f4: the stages after decodeFrame chained on the device
+            direct = self._direct_frame(fr, resident, colors_img)
+            self.stats[-1]["frame"] = self._frame_set_route(fr, direct) if dev_frames else "host: device_frames is off"
+            frame_set = self.stats[-1]["frame"] == "device set (modular)"
+            if (dev_image or dev_frames) and not frame_set:
                 try:  # every other frame: the pending transforms through today's hooks, and on exactly as without the switch
                     self.fe.apply_transforms(*hooks)
                 except frontend.FrontendError as e:
@@ -1722,7 +1907,16 @@ class JXLDecoder:
                 self.stats[-1]["palette"] = [dict(e) for e in getattr(be, "palette_log", [])]
             if fr.flags & FLAG_USE_LF_FRAME and self.lfBuffer[fr.lf_level] is None:
                 raise InvalidBitstreamException("LF Level too large")  # JXLCodestreamDecoder.java:613-614
-            colors = self._colors(fr)
+            if frame_set:
+                # device_frames: the Modular context -> the frame's set -> the blend; no host buffers (the canvas is a set or
+                # becomes one now: _frame_set_route has looked)
+                self.stats[-1].update(output="host", canvas="device")
+                save = self._count_frame(fr)
+                fset = self._modular_frame_set(fr, save)
+                self._canvas_frame(fr, None, None, colors, fset)
+                if self._frame_done(fr, save, bus0):
+                    break
+                continue
             simple = fr.upsampling == 1 and not fr.num_patches and not fr.has_splines and not fr.has_noise and \
                 not (fr.save_before_ct and not fr.is_last)
             ph, pw = fr.padded_height, fr.padded_width
@@ -1735,11 +1929,6 @@ class JXLDecoder:
                 buffers.append(np.zeros((ph, pw), F if is_float else np.int32))
             xyb_done = False
             rp = None
-            resident = getattr(be, "resident", False) and colors == 3  # row f4: the stages after decodeFrame chained on the device
-            # device_output: this frame is the image (the conditions of __init__'s docstring that the header settles)
-            direct = getattr(self, "device_output", False) and resident and colors_img == 3 and fr.type == REGULAR_FRAME and \
-                bool(fr.is_last) and fr.lf_level == 0 and not self._is_set(self.canvas) and self.canvas[0] is None and fr.y0 == 0 and fr.x0 == 0 and \
-                fr.width * fr.upsampling == info.width and fr.height * fr.upsampling == info.height and fr.blend_mode == abi.BLEND_REPLACE
             self.stats[-1]["output"] = "host"
             # device_canvas: the canvas lives in a plane set from the first frame that reaches it until something lands it
             dcan = getattr(self, "device_canvas", False) and not direct
@@ -1803,13 +1992,7 @@ class JXLDecoder:
             buffers = [np.ascontiguousarray(b[:fr.height, :fr.width]) for b in buffers]
             if fr.type == LF_FRAME:
                 continue
-            save = (fr.save_as_reference != 0 or fr.duration == 0) and not fr.is_last and fr.type != LF_FRAME
-            visible = fr.type in (REGULAR_FRAME, SKIP_PROGRESSIVE) and (fr.duration != 0 or fr.is_last)
-            if visible:
-                self.visibleFrames += 1
-                self.invisibleFrames = 0
-            else:
-                self.invisibleFrames += 1
+            save = self._count_frame(fr)
             # Frame.upsample
             for c in range(len(buffers)):
                 k = fr.upsampling if c < colors else fr.ec_upsampling[c - colors]
@@ -1882,24 +2065,7 @@ class JXLDecoder:
                 extras = [be.orient(np.ascontiguousarray(b), info.orientation) if info.orientation != 1 else b for b in self.canvas[3:]]
                 return JXLImage([None] * 3 + extras, info, be, resident=rp)
             if dcan:
-                if not self._is_set(self.canvas):  # :640-643: every plane of the type of the frame's first buffer
-                    first_type = np.dtype(np.float32) if rp is not None else buffers[0].dtype
-                    self.canvas = be.host.DeviceCanvas.create(be.ctx, [first_type] * len(self.canvas), info.height, info.width)
-                why = None
-                if fr.type in (REGULAR_FRAME, SKIP_PROGRESSIVE):
-                    if any(self.reference[i] is self.canvas and i != fr.save_as_reference for i in range(4)):
-                        self.canvas = self.canvas.clone()  # :645-653
-                    why = self._blend_frame_device(fr, buffers, rp)
-                if why is not None:
-                    # landing: the sets come down, the frame's colour planes too, and this frame is blended as without the switch
-                    # (the copy-on-write above has been made already, on the device)
-                    self._land(why)
-                    self.stats[-1]["canvas"] = "landed: " + why
-                    if rp is not None:
-                        planes = rp.download()
-                        for c in range(3):
-                            buffers[c] = planes[c]
-                    self._blend_frame(fr, buffers, colors)
+                self._canvas_frame(fr, buffers, rp, colors)
             else:
                 if self.canvas[0] is None:
                     for c in range(len(self.canvas)):
@@ -1908,11 +2074,7 @@ class JXLDecoder:
                     if any(self.reference[i] is self.canvas and i != fr.save_as_reference for i in range(4)):
                         self.canvas = [b.copy() for b in self.canvas]
                     self._blend_frame(fr, buffers, colors)
-            if save and not fr.save_before_ct:
-                self.reference[fr.save_as_reference] = self.canvas
-            bus1 = tuple(getattr(getattr(be, "ctx", None), "blend_bus", (0, 0)))
-            self.stats[-1]["blend_bus"] = (bus1[0] - bus0[0], bus1[1] - bus0[1])  # bytes up, bytes down: patches and blendFrame
-            if fr.is_last or fr.duration != 0:
+            if self._frame_done(fr, save, bus0):
                 break
         if not produced:
             return None

@@ -1100,6 +1100,20 @@ class DeviceCanvas:
         ctx.call("jxl_canvas_from_modular", C.byref(d), C.byref(id_))
         return cls(ctx, id_.value, [d.plane[i].type for i in range(d.n_planes)], (int(height), int(width)))
 
+    @classmethod
+    def fromModularUp(cls, ctx, height, width, planes, k, upWeights):
+        """the Modular context's result channels as a new set of UPSAMPLED float planes, k * height x k * width
+        (jxl_canvas_from_modular_up): per plane Frame.performUpsampling (Frame.java:217-260) of castToFloat of the cropped
+        channel, all planes as one launch. planes as fromModular's, every one float with its own scale (1f / maxValue);
+        upWeights as performUpsampling's. Nothing but the weights crosses the bus"""
+        d = modularPlanesDesc(height, width, planes)
+        w = np.ascontiguousarray(upWeights, np.float32)
+        if k in (2, 4, 8) and w.size != k * k * 25:
+            raise ValueError("k * k * 25 upsampling weights")
+        id_ = C.c_int32(-1)
+        ctx.call("jxl_canvas_from_modular_up", C.byref(d), int(k), abi.fptr(w), C.byref(id_))
+        return cls(ctx, id_.value, [abi.PLANE_FLOAT] * d.n_planes, (int(height) * int(k), int(width) * int(k)))
+
     def _live(self):
         if self.id is None:
             raise IllegalStateException(abi.JXL_ERR_STATE, "the plane set has been released")
@@ -1187,6 +1201,13 @@ class DeviceCanvas:
         self._live()
         self.ctx.call("jxl_canvas_to_planes", self.id)
         return ResidentPlanes(self.ctx)
+
+    def takePlanes(self):
+        """planes 0..2 become copies of the context's resident planes, tagged float (jxl_canvas_take_planes): toPlanes'
+        inverse, for the colour planes that went through a stage on ResidentPlanes"""
+        self._live()
+        self.ctx.call("jxl_canvas_take_planes", self.id)
+        self.types[:3] = [abi.PLANE_FLOAT] * 3
 
     def release(self):
         if self.id is not None and getattr(self.ctx, "h", None):
