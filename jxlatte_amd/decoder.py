@@ -360,6 +360,22 @@ def put_group_sparse(hf, pass_, grp, sp):
     hf.putGroupSparseEntries(pass_, grp, ents, wide)
 
 
+def feed_frame(hf, lfgroups, groups, sparse):
+    """one VarDCT frame's inputs into a host.Frame: the LF groups, then every (pass, group) of `groups`, dense planes or the
+    entry lists of Frontend.coeffs_sparse. Returns the frame"""
+    for g in lfgroups:
+        hf.setLFGroup(g)
+        if g.get("lf_quant") is not None:
+            hf.setLFGroupQuant(g["lfg_y"], g["lfg_x"], g["lf_quant"], g["scaled_dequant"], g["extra_precision"], g["x_factor_lf"],
+                               g["b_factor_lf"], g["adaptive_smoothing"])
+    for pass_, grp, q in groups:
+        if sparse:
+            put_group_sparse(hf, pass_, grp, q)
+        else:
+            hf.putGroup(pass_, grp, q)
+    return hf
+
+
 # ---- the type plan of the patch stage (JXLCodestreamDecoder.blendBuffers' casts, :433-465) ------------------------
 class PatchPlan:
     """what JXLDecoder._patches would do to the TYPES of the planes, without touching a sample (patch_type_plan)"""
@@ -646,17 +662,7 @@ class DeviceBackend:
 
     def vardct(self, params, weights, woffs, lfgroups, groups, keep=None, sparse=False):
         """sparse: `groups` yields the entry lists of Frontend.coeffs_sparse, fed through jxl_vardct_put_group_sparse"""
-        fr = self.host.Frame(self.ctx, params, weights, woffs)
-        for g in lfgroups:
-            fr.setLFGroup(g)
-            if g.get("lf_quant") is not None:
-                fr.setLFGroupQuant(g["lfg_y"], g["lfg_x"], g["lf_quant"], g["scaled_dequant"], g["extra_precision"], g["x_factor_lf"],
-                                   g["b_factor_lf"], g["adaptive_smoothing"])
-        for pass_, grp, q in groups:
-            if sparse:
-                put_group_sparse(fr, pass_, grp, q)
-            else:
-                fr.putGroup(pass_, grp, q)
+        fr = feed_frame(self.host.Frame(self.ctx, params, weights, woffs), lfgroups, groups, sparse)
         if keep is not None:  # the planes stay on the device for the stages after decodeFrame: host.ResidentPlanes
             return fr.keepPlanes(*keep)
         return fr.decodeFrame()
@@ -813,6 +819,60 @@ class JXLImage:
     def onDevice(self):
         """the colour planes are the backend's resident planes (and nothing has replaced them on this image)"""
         return self.resident is not None or self.planeSet is not None
+
+    # -- where the samples are, for the writers' one-pass kernels: the three operations below and nobody else ask ---------
+    def _home(self, colors, one_type=False):
+        """"set": the live plane set comes first; else "resident": the resident planes, if the host arrays were never
+        downloaded (planes a later decode took then raise IllegalStateException) or the planes are still live; else "host".
+        one_type: a set whose colour planes differ in type is passed over (jxl_color_params states one type for a pass)"""
+        if self.setLive() and not (one_type and len({self.planeSet.types[c] for c in range(colors)}) != 1):
+            return "set"
+        if self.resident is not None and (self._buffer[0] is None or self.resident.live()):
+            return "resident"
+        return "host"
+
+    def _plan_planes(self, colors):
+        """_color_plan's `planes` for a writer: stand-ins (shape and dtype, never read) while the samples are on the device,
+        None for the host arrays"""
+        home = self._home(colors, True)
+        if home == "set":
+            return self.planeSet._stand_ins(colors)
+        return [np.broadcast_to(F(0), (self.height, self.width))] * 3 if home == "resident" else None
+
+    def _peak(self, planes, **front):
+        """determinePeak of the front stages, where the colour planes are: (peak, bytes sent up)"""
+        home = self._home(len(planes), True)
+        if home == "set":
+            return self.planeSet.colorPeak(nColor=len(planes), **front), 0
+        if home == "resident":
+            return self.resident.colorPeak(**front), 0
+        up = sum(a.nbytes for a in planes) if front.get("matrix") is not None else planes[min(1, len(planes) - 1)].nbytes
+        return self.backend.color_peak(planes, **front), up
+
+    def _png_samples(self, planes, **kw):
+        """PNGWriter's samples in one pass (pngParams' keywords): (samples, bytes sent up). A set is read where it is, alpha
+        included; beside the resident planes only the alpha plane goes up; the host arrays `planes` go up whole"""
+        colors, a = len(planes), self.alphaIndex
+        home = self._home(colors, True)
+        if home == "set":
+            return self.planeSet.pngSamples(nColor=colors, alphaPlane=colors + a if a >= 0 else None, **kw), 0
+        alpha = np.ascontiguousarray(self.extraChannel(a)) if a >= 0 else None
+        up = alpha.nbytes if alpha is not None else 0
+        if home == "resident":
+            return self.resident.pngSamples(alpha, **kw), up
+        planes = [np.ascontiguousarray(p) for p in planes]
+        return self.backend.png_samples(planes, alpha, **kw), up + sum(p.nbytes for p in planes)
+
+    def _pfm_samples(self, tagged):
+        """PFMWriter's samples in one pass: (samples, bytes sent up). A set's planes, int32 or float, as they are"""
+        colors = len(tagged)
+        home = self._home(colors)
+        if home == "set":
+            return self.planeSet.pfmSamples(nColor=colors, taggedDepths=tagged), 0
+        if home == "resident":
+            return self.resident.pfmSamples(), 0
+        planes = [np.ascontiguousarray(a) for a in self.getBuffer(False)[:colors]]
+        return self.backend.pfm_samples(planes, tagged), sum(a.nbytes for a in planes)
 
     def _clone(self, buffer=None):
         im = JXLImage.__new__(JXLImage)
@@ -1001,12 +1061,172 @@ class JXLImage:
         return self.linearize().fillColor().toneMapLinear(primaries, whitePoint).transfer(transfer, peakDetect)
 
 
+# ---- a frame's channels between decodeFrame and the blend ---------------------------------------------------------
+def _to_float(a, depth):
+    """ImageBuffer.castToFloat (ImageBuffer.java:112-127): a float plane stays as it is"""
+    if a.dtype == np.float32:
+        return a
+    return (a.astype(F) * F(F(1) / F((1 << depth) - 1))).astype(F)
+
+
+class FramePlanes:
+    """One frame's planes from decodeFrame to the blend (JXLCodestreamDecoder.java:628-655), wherever they are:
+      host  the host list. The extra channels live there; the colours too while they are on the host (None while not)
+      rp    the backend's resident planes (host.ResidentPlanes) while the three colours are on the device, else None
+      set   the ready-made plane set (host.DeviceCanvas) of a device_frames frame: every plane, extras included; else None
+      moves each real crossing of the colours, "h2d" / "d2h", in order: stats[k]["plane_moves"]
+    The five sample stages run on the resident planes where the backend keeps planes resident and the frame has three
+    colours (`resident`; row f4), else through the backend's stage calls on the host arrays; the caller does not know which.
+    Every device stage works on float samples (Frame.java:221, :806; JXLCodestreamDecoder.java:262): _to_float. The stages
+    after the upsampling read planes 0..2 whatever the colour count, as they always have."""
+
+    def __init__(self, backend, info, host, colors, rp=None, fset=None):
+        self.be, self.info, self.host, self.colors, self.rp, self.set = backend, info, host, colors, rp, fset
+        self.resident = bool(getattr(backend, "resident", False)) and colors == 3
+        self.moves = []
+
+    @property
+    def shape(self):
+        return self.set.shape if self.set is not None else self.rp.shape if self.rp is not None else self.host[0].shape
+
+    @property
+    def dtypes(self):
+        """one per plane, as the blend will see them"""
+        if self.set is not None:
+            return self.set.dtypes
+        return [np.dtype(np.float32) if self.rp is not None and c < 3 else b.dtype for c, b in enumerate(self.host)]
+
+    def _floats(self):
+        return np.stack([_to_float(self.host[c], self.info.bits_per_sample) for c in range(3)])
+
+    def _put(self, planes):
+        for c in range(3):
+            self.host[c] = np.ascontiguousarray(planes[c])
+
+    def to_device(self):
+        """the colours as the backend's resident planes (idempotent); returns them"""
+        if self.rp is None:
+            self.rp = self.be.keep_planes(self._floats())
+            self.moves.append("h2d")
+        return self.rp
+
+    def to_host(self, log="d2h"):
+        """the colours as host arrays (idempotent); returns the host list"""
+        if self.rp is not None:
+            self._put(self.rp.download())
+            self.rp = None
+            if log:
+                self.moves.append(log)
+        return self.host
+
+    def snapshot(self, log):
+        """every plane as a host array while the colours stay where they are: a copy of resident colours comes down, logged
+        as `log`"""
+        if self.rp is None:
+            return self.host
+        planes = self.rp.download()
+        self.moves.append(log)
+        return list(planes) + self.host[3:]
+
+    def land(self):
+        """every plane as a host array, for a blend on the host after all (stats[k]["canvas"] tells; no move of the tail)"""
+        return [self.set.download(c) for c in range(len(self.set))] if self.set is not None else self.to_host(log=None)
+
+    def blend_set(self):
+        """a plane set of this frame for jxl_canvas_blend: the ready-made one, the resident colours with the extras uploaded
+        beside them (the colours cross no bus), or the host arrays uploaded"""
+        if self.set is not None:
+            return self.set
+        canvas, ctx = self.be.host.DeviceCanvas, self.be.ctx
+        if self.rp is None:
+            return canvas.fromArrays(ctx, self.host)
+        fset = canvas.fromPlanes(ctx, [b.dtype for b in self.host[3:]])
+        for i, b in enumerate(self.host[3:]):
+            fset.upload(3 + i, b)
+        return fset
+
+    def one_size(self):
+        """(the planes of a ready-made set are those of one launch: one size by construction)"""
+        shape = tuple(self.shape)
+        return self.set is not None or all(tuple(b.shape) == shape for b in self.host[3 if self.rp is not None else 0:])
+
+    # -- device_frames: the colours of the ready-made set visit the resident planes for the stages -----------------------
+    def leave_set(self):
+        self.rp = self.set.toPlanes()
+
+    def rejoin_set(self):
+        if self.rp is not None:
+            self.set.takePlanes()
+            self.rp = None
+        else:  # the last stage was a host stage (splines without device_splines): its planes go up into the set
+            for c in range(3):
+                self.set.upload(c, self.host[c])
+            self.moves.append("h2d")
+
+    # -- the sample stages (JXLCodestreamDecoder.java:628-637) --------------------------------------------------------------
+    def upsample(self, fr, weights):
+        """Frame.upsample (Frame.java:217-260): every channel by its own factor; weights(k) gives the kernel"""
+        info = self.info
+        for c in range(len(self.host)):
+            k = fr.upsampling if c < self.colors else fr.ec_upsampling[c - self.colors]
+            if k > 1 and not (self.resident and c < 3):
+                depth = info.bits_per_sample if c < self.colors else info.ec_bits[c - self.colors]
+                self.host[c] = self.be.upsample(_to_float(self.host[c], depth), k, weights(k))
+        if self.resident and fr.upsampling > 1:
+            self.to_device().upsample(fr.upsampling, weights(fr.upsampling))
+
+    def splines(self, fr, splines, on_device):
+        """Frame.renderSplines: in the backend with `on_device` (no silent return to the host render), else render_splines"""
+        if on_device and self.resident:
+            return self.to_device().splines(splines, fr.base_corr_x, fr.base_corr_b)
+        host = self.to_host()
+        for c in range(3):
+            host[c] = _to_float(host[c], self.info.bits_per_sample).copy()
+        if on_device:  # the stage entry
+            self._put(self.be.splines(np.stack(host[:3]), splines, fr.base_corr_x, fr.base_corr_b))
+        else:
+            render_splines(host, splines, fr.base_corr_x, fr.base_corr_b, host[0].shape[1], host[0].shape[0])
+
+    def noise(self, fr, seed0):
+        """initializeNoise + synthesizeNoise (Frame.java:748-831). initializeNoise depends on the frame counters and the size
+        only: its place before the patches in the reference is moot"""
+        lut = np.array(fr.noise, F)
+        if self.resident:
+            return self.to_device().noise(fr.group_dim, seed0, lut, fr.base_corr_x, fr.base_corr_b)
+        h, w = self.host[0].shape
+        noise = self.be.noise_init(h, w, seed0, fr.group_dim, self.colors)
+        self._put(self.be.noise_add(self._floats(), noise, lut, fr.base_corr_x, fr.base_corr_b))
+
+    def invert_xyb(self, matrix, opsin_bias, cbrt_bias, intensity_target):
+        if self.resident:
+            return self.to_device().invertXYB(matrix, opsin_bias, cbrt_bias, intensity_target)
+        self._put(self.be.xyb(self._floats(), matrix, opsin_bias, cbrt_bias, intensity_target))
+
+    def ycbcr(self):
+        if self.resident:
+            return self.to_device().ycbcr()
+        self._put(self.be.ycbcr(self._floats()))
+
+    def varblocks(self, blocks, cells):
+        """Frame.drawVarblocks in one device pass, where the colours are; returns stats[k]["varblocks"]"""
+        if self.rp is not None:
+            self.rp.varblocks(blocks, cells)
+            return "device planes"
+        self._put(self.be.varblocks(self._floats(), blocks, cells))
+        return "host planes"
+
+
 # ---- JXLDecoder (J/JXLDecoder.java + J/JXLCodestreamDecoder.java) ---------------------------------------------
 def _tt_dims():
     return [(t[5] >> 3, t[6] >> 3) for t in abi.TRANSFORM_TYPES]
 
 
 class JXLDecoder:
+    # the switches' defaults (a decoder made with JXLDecoder.__new__ -- tests, tools, load_vardct_frame -- has them too)
+    sparse_coeffs = device_splines = device_patches = device_output = device_canvas = False
+    draw_varblocks = device_palette = device_image = device_frames = False
+    trace = None  # test hook: see _trace
+
     def __init__(self, source, backend=None, sparse_coeffs=False, device_splines=False, device_patches=False, device_output=False,
                  device_canvas=False, draw_varblocks=False, device_palette=False, device_image=False, device_frames=False):
         """sparse_coeffs: hand the HF coefficients to the backend as lists of non-zero entries (jxf_get_coeffs_sparse ->
@@ -1128,9 +1348,8 @@ class JXLDecoder:
     def _trace(self, stage, planes, fused):
         """test hook (tests/test_jvm_pin.py): `self.trace(frame_index, stage, planes, fused)` at the cut points where the pin-on-arrival
         harness makes the reference dump its planes; None (the default): nothing"""
-        tr = getattr(self, "trace", None)
-        if tr is not None:
-            tr(self.frames_decoded - 1, stage, planes, fused)
+        if self.trace is not None:
+            self.trace(self.frames_decoded - 1, stage, planes, fused)
 
     # -- frame-level pieces ---------------------------------------------------------------------------------------
     def _colors(self, fr):
@@ -1163,8 +1382,8 @@ class JXLDecoder:
     def _vardct_frame(self, fr, fuse_xyb, keep=None):
         p, weights, woffs, lfgroups, groups, hist = self._vardct_inputs(fr, fuse_xyb)
         self.stats[-1]["varblocks"] = {abi.TT_NAME[t]: int(n) for t, n in enumerate(hist) if n}
-        self._varblock_list = self._gather_varblocks(fr, lfgroups) if getattr(self, "draw_varblocks", False) else None
-        sparse = getattr(self, "sparse_coeffs", False)
+        self._varblock_list = self._gather_varblocks(fr, lfgroups) if self.draw_varblocks else None
+        sparse = self.sparse_coeffs
         kw = dict(sparse=True) if sparse else {}
         if keep is not None:
             return self.backend.vardct(p, weights, woffs, lfgroups, groups(sparse), keep=keep, **kw)
@@ -1197,72 +1416,39 @@ class JXLDecoder:
         from . import host
         return host.getUpWeights(k, packed)
 
-    def _chained_tail(self, fr, rp, buffers, colors, save, xyb_done, keep=False, upsampled=False):
-        """Frame.upsample .. performColorTransforms (JXLCodestreamDecoder.java:628-637) of the three colour planes with the
-        samples moving between host and device only where the next stage lives on the other side: upsampling, noise and the
-        colour transforms are device stages on host.ResidentPlanes, and so are the splines with `device_splines`; the
-        saveBeforeCT reference, the patches and (by default) the splines are host stages (as in the reference). `rp` is the
-        VarDCT frame's resident result, or None when the colour planes start as the host arrays buffers[:3] (Modular frames).
-        The extra channels in buffers[3:] are host arrays throughout.
-        keep: planes that are on the device at the end stay there (buffers[:3] are then not touched); returns them, or None.
-        upsampled: `rp` is already past Frame.upsample (_modular_frame_set)."""
-        info, be = self.info, self.backend
-        moves = []
-
-        def on_device():
-            nonlocal rp
-            if rp is None:  # every device stage works on float samples (Frame.java:221, :806; JXLCodestreamDecoder.java:262)
-                rp = be.keep_planes(np.stack([self._to_float(buffers[c], info.bits_per_sample) for c in range(3)]))
-                moves.append("h2d")
-            return rp
-
-        def on_host():
-            nonlocal rp
-            if rp is not None:
-                planes = rp.download()
-                for c in range(3):
-                    buffers[c] = planes[c]
-                rp = None
-                moves.append("d2h")
-
-        dev_patches = getattr(self, "device_patches", False) and bool(fr.num_patches)
-        if fr.upsampling > 1 and not upsampled:
-            on_device().upsample(fr.upsampling, self._up_weights(fr.upsampling))
+    def _chained_tail(self, fr, planes, save, xyb_done, keep=False, upsampled=False):
+        """Frame.upsample .. performColorTransforms (JXLCodestreamDecoder.java:628-637), the one statement of that order, for
+        every backend: upsample, the saveBeforeCT reference, patches, splines, noise, inverse XYB, YCbCr. `planes`
+        (FramePlanes) runs each sample stage where the samples can be and moves the colours between host and device only
+        where the next stage lives on the other side; the saveBeforeCT reference and the patches' blend calls are host stages
+        (as in the reference).
+        keep: colours that are on the device at the end stay there. upsampled: the planes are already past Frame.upsample
+        (_modular_frame_set)."""
+        info = self.info
+        if not upsampled:
+            planes.upsample(fr, self._up_weights)
+        dev_patches = self.device_patches and bool(fr.num_patches)
         if save and fr.save_before_ct:
-            if dev_patches and rp is not None:  # a copy comes down, the planes stay
-                planes = rp.download()
-                moves.append("d2h")
-                self.reference[fr.save_as_reference] = [planes[c] for c in range(3)] + [b.copy() for b in buffers[3:]]
+            if dev_patches and planes.rp is not None:  # a copy comes down, the planes stay
+                self.reference[fr.save_as_reference] = planes.snapshot("d2h")[:3] + [b.copy() for b in planes.host[3:]]
             else:
-                on_host()
-                self.reference[fr.save_as_reference] = [b.copy() for b in buffers]
-        if dev_patches and colors == (1 if info.colour_space == CE_GRAY else 3):
-            if not self._patches_device(fr, buffers, colors, (on_device, on_host, lambda: rp)):
-                on_host()
-                self._patches(fr, buffers, colors)
-        elif fr.num_patches:
-            on_host()
-            self._patches(fr, buffers, colors)
-            self.stats[-1]["patches"] = dict(path="blend calls")
-        if fr.has_splines and getattr(self, "device_splines", False):
-            on_device().splines(self.fe.splines(), fr.base_corr_x, fr.base_corr_b)
-        elif fr.has_splines:
-            on_host()
-            for c in range(3):
-                buffers[c] = self._to_float(buffers[c], info.bits_per_sample).copy()
-            render_splines(buffers, self.fe.splines(), fr.base_corr_x, fr.base_corr_b, buffers[0].shape[1], buffers[0].shape[0])
-        if fr.has_noise:  # initializeNoise depends on the frame counters and the size only: its place before the patches is moot
-            on_device().noise(fr.group_dim, (self.visibleFrames << 32) | self.invisibleFrames, np.array(fr.noise, F),
-                              fr.base_corr_x, fr.base_corr_b)
+                self.reference[fr.save_as_reference] = [b.copy() for b in planes.to_host()]
+        if fr.num_patches:
+            if not (dev_patches and planes.colors == 3 and info.colour_space != CE_GRAY and self._patches_device(fr, planes)):
+                self._patches(fr, planes.to_host(), planes.colors)
+                self.stats[-1].setdefault("patches", dict(path="blend calls"))
+        if fr.has_splines:
+            planes.splines(fr, self.fe.splines(), self.device_splines)
+        if fr.has_noise:
+            planes.noise(fr, (self.visibleFrames << 32) | self.invisibleFrames)
         if info.xyb_encoded and not xyb_done:
-            m, bias, cbrt = self._opsin()
-            on_device().invertXYB(m, bias, cbrt, info.intensity_target)
+            planes.invert_xyb(*self._opsin(), info.intensity_target)
         if fr.do_ycbcr:
-            on_device().ycbcr()
+            planes.ycbcr()
         if not keep:
-            on_host()
-        self.stats[-1]["plane_moves"] = moves
-        return rp
+            planes.to_host()
+        if planes.resident:
+            self.stats[-1]["plane_moves"] = planes.moves
 
     def _vardct_inputs(self, fr, fuse_xyb):
         """the boundary tensors of one VarDCT frame: (jxl_vardct_params, weights, offsets, LF groups, group iterator)"""
@@ -1385,67 +1571,55 @@ class JXLDecoder:
         returns whether decode() has its image"""
         if save and not fr.save_before_ct:
             self.reference[fr.save_as_reference] = self.canvas
-        bus1 = tuple(getattr(getattr(self.backend, "ctx", None), "blend_bus", (0, 0)))
-        self.stats[-1]["blend_bus"] = (bus1[0] - bus0[0], bus1[1] - bus0[1])  # bytes up, bytes down: patches and blendFrame
+        self._bus_since(bus0)
         return fr.is_last or fr.duration != 0
 
-    def _canvas_frame(self, fr, buffers, rp, colors, fset=None):
+    def _blend_bus(self):
+        """host._bus: what the blend path has moved so far, (bytes up, bytes down)"""
+        return tuple(getattr(getattr(self.backend, "ctx", None), "blend_bus", (0, 0)))
+
+    def _bus_since(self, bus0):
+        bus1 = self._blend_bus()
+        self.stats[-1]["blend_bus"] = (bus1[0] - bus0[0], bus1[1] - bus0[1])  # bytes up, bytes down: patches and blendFrame
+
+    def _canvas_frame(self, fr, planes):
         """one frame onto the canvas set (:640-655): the set is made when the first frame reaches it, copied when a reference
-        slot shares it, and blended in one launch -- or everything lands and the host blends. The frame's planes: the host
-        arrays `buffers` with the resident colour planes `rp`, or the ready-made set `fset` (device_frames)"""
+        slot shares it, and blended in one launch -- or everything lands and the host blends"""
         info, be = self.info, self.backend
         if not self._is_set(self.canvas):  # :640-643: every plane of the type of the frame's first buffer
-            first_type = fset.dtypes[0] if fset is not None else np.dtype(np.float32) if rp is not None else buffers[0].dtype
-            self.canvas = be.host.DeviceCanvas.create(be.ctx, [first_type] * len(self.canvas), info.height, info.width)
+            self.canvas = be.host.DeviceCanvas.create(be.ctx, [planes.dtypes[0]] * len(self.canvas), info.height, info.width)
         why = None
         if fr.type in (REGULAR_FRAME, SKIP_PROGRESSIVE):
             if any(self.reference[i] is self.canvas and i != fr.save_as_reference for i in range(4)):
                 self.canvas = self.canvas.clone()  # :645-653
-            why = self._blend_frame_device(fr, buffers, rp, fset)
-        if fset is not None and why is not None:  # the frame's planes come down from its set
-            buffers = [fset.download(c) for c in range(len(fset))]
-        if fset is not None and not any(s_ is fset for s_ in self._dead_sets):
-            fset.release()
+            why = self._blend_frame_device(fr, planes)
+        # landing: the frame's planes come down, then the sets, and this frame is blended as without the switch (the
+        # copy-on-write above has been made already, on the device)
+        buffers = planes.land() if why is not None else None
+        if planes.set is not None and not any(s_ is planes.set for s_ in self._dead_sets):
+            planes.set.release()
         if why is not None:
-            # landing: the sets come down, the frame's colour planes too, and this frame is blended as without the switch
-            # (the copy-on-write above has been made already, on the device)
             self._land(why)
             self.stats[-1]["canvas"] = "landed: " + why
-            if rp is not None:
-                planes = rp.download()
-                for c in range(3):
-                    buffers[c] = planes[c]
-            self._blend_frame(fr, buffers, colors)
+            self._blend_frame(fr, buffers, planes.colors)
 
-    def _blend_frame_device(self, fr, buffers, rp, fset=None):
-        """blendFrame on the plane sets: the type plan, the frame's planes into a set (its resident colour planes without the
-        host, or the ready-made set `fset`), the hoisted casts, one launch. Returns None, or the reason to land (nothing has
-        been touched then)."""
+    def _blend_frame_device(self, fr, planes):
+        """blendFrame on the plane sets: the type plan, the frame's planes into a set (FramePlanes.blend_set), the hoisted
+        casts, one launch. Returns None, or the reason to land (nothing has been touched then)."""
         host, ctx = self.backend.host, self.backend.ctx
         info, cv = self.info, self.canvas
-        f32 = np.dtype(np.float32)
-        ftypes = fset.dtypes if fset is not None else [f32] * 3 + [b.dtype for b in buffers[3:]] if rp is not None else [b.dtype for b in buffers]
         refs = self.reference
         ref_types = [None if r is None else "canvas" if r is cv else r.dtypes if self._is_set(r) else
                      [None if b is None else b.dtype for b in r] for r in refs]
-        plan = blend_type_plan(info, fr, cv.dtypes, ftypes, ref_types)
+        plan = blend_type_plan(info, fr, cv.dtypes, planes.dtypes, ref_types)
         if plan.verdict != "device":
             return plan.verdict[len("land: "):]
         if plan.rect is None:
             return None
-        if fset is None:
-            shape = rp.shape if rp is not None else buffers[0].shape
-            if any(tuple(b.shape) != tuple(shape) for b in (buffers[3:] if rp is not None else buffers)):
-                return "the frame's planes differ in size"
+        if not planes.one_size():
+            return "the frame's planes differ in size"
         self._release_dead()
-        if fset is not None:  # (device_frames: the planes of one launch, one size by construction)
-            pass
-        elif rp is not None:
-            fset = host.DeviceCanvas.fromPlanes(ctx, [b.dtype for b in buffers[3:]])
-            for i, b in enumerate(buffers[3:]):
-                fset.upload(3 + i, b)
-        else:
-            fset = host.DeviceCanvas.fromArrays(ctx, buffers)
+        fset = planes.blend_set()
         self._dead_sets.append(fset)
         ref = None
         if plan.source is not None:
@@ -1496,11 +1670,7 @@ class JXLDecoder:
         colors = 1 if self.info.colour_space == CE_GRAY else 3
         return self.info.bits_per_sample if idx < colors else self.info.ec_bits[idx - colors]
 
-    @staticmethod
-    def _to_float(a, depth):
-        if a.dtype == np.float32:
-            return a
-        return (a.astype(F) * F(F(1) / F((1 << depth) - 1))).astype(F)
+    _to_float = staticmethod(_to_float)
 
     def _blend_buffers(self, idx, frame_buffers, ref_buffers, patch_start, frame_off, ref_off, size, frame_colors, mode,
                        alpha_channel, clamp, patch, canvas_list):
@@ -1585,20 +1755,18 @@ class JXLDecoder:
                     self._blend_buffers(d, frame_buffers, ref, (y0, x0), (y0, x0), (p["y0"], p["x0"]), (p["h"], p["w"]),
                                         frame_colors, mode, alpha, bool(clamp), patch=True, canvas_list=frame_buffers)
 
-    def _patches_device(self, fr, buffers, colors, tail):
-        """computePatches as one backend call per segment of patch_type_plan. `tail`: _chained_tail's (on_device, on_host,
-        resident planes or None) when the backend keeps planes resident -- a segment whose colour planes are float then runs on
-        them (jxl_planes_patches), one whose colour planes are integer on the host arrays (jxl_stage_patches); None: the stage
-        entry only. Leaves `buffers` and self.reference[...] as _patches would: values, dtypes, absent reference planes
-        replaced by zero planes. False (nothing touched): the plan holds an application the in-place launch cannot replay;
-        the caller runs _patches."""
+    def _patches_device(self, fr, planes):
+        """computePatches as one backend call per segment of patch_type_plan on `planes` (FramePlanes). Where its colours can be
+        resident, a segment whose colour planes are float runs on them (jxl_planes_patches) and one whose colour planes are
+        integer on the host arrays (jxl_stage_patches); where they cannot, the stage entry only. Leaves the planes and
+        self.reference[...] as _patches would: values, dtypes, absent reference planes replaced by zero planes. False (nothing
+        touched): the plan holds an application the in-place launch cannot replay; the caller runs _patches."""
         info, be = self.info, self.backend
         f32 = np.dtype(np.float32)
+        colors, buffers, shape = planes.colors, planes.host, planes.shape
         n_chan = colors + info.num_extra
-        rp = tail[2]() if tail else None
-        shape = rp.shape if rp is not None else buffers[0].shape
-        stand_in = [np.broadcast_to(F(0), shape) if (rp is not None and c < 3) else buffers[c] for c in range(n_chan)]
-        plan = patch_type_plan(info, [self.fe.patch(i) for i in range(fr.num_patches)], stand_in, self.reference, colors)
+        typed = [np.broadcast_to(np.zeros((), t), shape) for t in planes.dtypes[:n_chan]]  # (the plan reads dtype and shape only)
+        plan = patch_type_plan(info, [self.fe.patch(i) for i in range(fr.num_patches)], typed, self.reference, colors)
         st = self.stats[-1]["patches"] = dict(path="none", positions=len(plan.pos), applications=len(plan.calls), segments=len(plan.segments))
         if not plan.calls:
             return True
@@ -1632,12 +1800,11 @@ class JXLDecoder:
         paths = set()
         for seg in plan.segments:
             # blendBuffers' casts, hoisted to the segment's entry (the reference's ImageBuffer.castToFloat: _to_float)
-            resident = tail is not None and all(seg["frame"][c] == f32 for c in range(3))
-            if tail and not resident:
-                tail[1]()
-            rp = tail[2]() if tail else None
+            resident = planes.resident and all(seg["frame"][c] == f32 for c in range(3))
+            if not resident:
+                planes.to_host()
             for n in range(n_chan):
-                if rp is not None and n < 3:
+                if planes.rp is not None and n < 3:
                     continue
                 if buffers[n].dtype != seg["frame"][n]:
                     if seg["frame"][n] != f32:
@@ -1652,16 +1819,15 @@ class JXLDecoder:
             ref = [self.reference[k] if k in seg["ref"] else None for k in range(4)]
             blend = seg_blend(seg)
             if resident:
-                tail[0]().patches(buffers[3:], ref, plan.pos, blend, is_alpha, assoc)
+                planes.to_device().patches(buffers[3:], ref, plan.pos, blend, is_alpha, assoc)
                 paths.add("resident planes")
             else:
                 be.patches(buffers, ref, plan.pos, blend, colors, is_alpha, assoc)
                 paths.add("stage entry")
         st["path"] = " + ".join(sorted(paths))
         # what the casts and `new ImageBuffer`s of blendBuffers leave behind in planes no application used
-        rp = tail[2]() if tail else None
         for n in range(n_chan):
-            if not (rp is not None and n < 3) and buffers[n].dtype != plan.frame_types[n]:
+            if not (planes.rp is not None and n < 3) and buffers[n].dtype != plan.frame_types[n]:
                 buffers[n] = self._to_float(buffers[n], self._depth_of(n))
         for k, types in plan.ref_types.items():
             lst = self.reference[k]
@@ -1672,7 +1838,6 @@ class JXLDecoder:
                     lst[n] = self._to_float(lst[n], self._depth_of(n))
         return True
 
-    # -- the decode loop (JXLCodestreamDecoder.decode :546-677) ----------------------------------------------------
     # -- the image as a device plane set (device_image) -----------------------------------------------------------
     @staticmethod
     def _one_plan_chain_rule(fr, kinds):
@@ -1751,26 +1916,40 @@ class JXLDecoder:
         return None
 
     def _frame_set_route(self, fr, direct):
-        """stats[k]["frame"] of a frame under device_frames: "device set (modular)", or "host: <why not>". The switch acts only
-        while the canvas is a device set; the header's part is frame_set_rule"""
-        if not getattr(self, "device_canvas", False):
-            return "host: device_canvas is off"
-        if not hasattr(self.backend, "ctx"):
-            raise RuntimeError("device_canvas needs a backend with a device context")
-        if direct:
-            return "host: device_output's direct path"
-        if self._landed is not None:
-            return "host: the canvas has landed (%s)" % self._landed
-        kinds = [t["kind"] for t in self.fe.transforms()] if fr.encoding == MODULAR else []
-        why = self.frame_set_rule(self.info, fr, kinds, getattr(self, "trace", None) is not None)
-        return "device set (modular)" if why is None else "host: " + why
+        """device_frames: whether the frame reaches the canvas as a plane set; stats[k]["frame"] says "device set (modular)"
+        or "host: <why not>". The switch acts only while the canvas is a device set; the header's part is frame_set_rule"""
+        if not self.device_frames:
+            why = "device_frames is off"
+        elif not self.device_canvas:
+            why = "device_canvas is off"
+        elif direct:
+            why = "device_output's direct path"
+        elif self._landed is not None:
+            why = "the canvas has landed (%s)" % self._landed
+        else:
+            kinds = [t["kind"] for t in self.fe.transforms()] if fr.encoding == MODULAR else []
+            why = self.frame_set_rule(self.info, fr, kinds, self.trace is not None)
+        self.stats[-1]["frame"] = "device set (modular)" if why is None else "host: " + why
+        return why is None
 
-    def _direct_frame(self, fr, resident, colors_img):
+    def _direct_frame(self, fr, colors):
         """device_output: this frame is the image (the conditions of __init__'s docstring that the header settles)"""
         info = self.info
-        return getattr(self, "device_output", False) and resident and colors_img == 3 and fr.type == REGULAR_FRAME and \
-            bool(fr.is_last) and fr.lf_level == 0 and not self._is_set(self.canvas) and self.canvas[0] is None and fr.y0 == 0 and fr.x0 == 0 and \
-            fr.width * fr.upsampling == info.width and fr.height * fr.upsampling == info.height and fr.blend_mode == abi.BLEND_REPLACE
+        return self.device_output and getattr(self.backend, "resident", False) and colors == 3 and info.colour_space != CE_GRAY and \
+            fr.type == REGULAR_FRAME and bool(fr.is_last) and fr.lf_level == 0 and not self._is_set(self.canvas) and \
+            self.canvas[0] is None and fr.y0 == 0 and fr.x0 == 0 and fr.width * fr.upsampling == info.width and \
+            fr.height * fr.upsampling == info.height and fr.blend_mode == abi.BLEND_REPLACE
+
+    def _canvas_route(self, fr, direct):
+        """device_canvas: whether this frame meets the canvas as a plane set. The canvas lives in one from the first frame that
+        reaches it until something lands it; stats[k]["canvas"] tells. device_output's direct frame never sees a canvas"""
+        on = self.device_canvas and not direct
+        if on and self._landed is None and self.info.colour_space == CE_GRAY:
+            self._landed = "one-colour image"
+        if on and fr.num_patches and fr.type != LF_FRAME:  # blendBuffers casts a patch's reference in place: no set stays up
+            self._land("a frame with patches")
+        self.stats[-1]["canvas"] = "host" if not on else "device" if self._landed is None else "landed: " + self._landed
+        return on and self._landed is None
 
     def _modular_plan_run(self):
         """the frame-level stream's pending chain as ONE plan of the Modular context: the encoded channels go up once, from the
@@ -1793,7 +1972,7 @@ class JXLDecoder:
         return ms
 
     def _modular_frame_set(self, fr, save):
-        """device_frames: the frame's buffers after Frame.upsample .. performColorTransforms (JXLCodestreamDecoder.java:628-637)
+        """device_frames: the frame's planes after Frame.upsample .. performColorTransforms (JXLCodestreamDecoder.java:628-637)
         as a plane set made from the Modular context, with the types the default path's buffers have at the blend"""
         info, be = self.info, self.backend
         host = be.host
@@ -1804,309 +1983,262 @@ class JXLDecoder:
         def inv_max(depth):  # ImageBuffer.castToFloat's factor (ImageBuffer.java:112-127), as _to_float forms it
             return float(F(F(1) / F((1 << depth) - 1)))
         if k > 1:  # Frame.performUpsampling casts every plane with its own depth first (Frame.java:226-228); a float plane stays
-            planes = [(c, -1, f32, inv_max(info.bits_per_sample)) for c in range(3)]
-            planes += [(3 + i, -1, f32, 1.0 if info.ec_exp_bits[i] != 0 else inv_max(info.ec_bits[i])) for i in range(info.num_extra)]
-            fset = host.DeviceCanvas.fromModularUp(be.ctx, fr.height, fr.width, planes, k, self._up_weights(k))
+            desc = [(c, -1, f32, inv_max(info.bits_per_sample)) for c in range(3)]
+            desc += [(3 + i, -1, f32, 1.0 if info.ec_exp_bits[i] != 0 else inv_max(info.ec_bits[i])) for i in range(info.num_extra)]
+            fset = host.DeviceCanvas.fromModularUp(be.ctx, fr.height, fr.width, desc, k, self._up_weights(k))
         else:
             # the colour planes are float exactly where the default path's are: every device stage casts them (Frame.java:796)
-            planes = [(c, -1, f32, inv_max(info.bits_per_sample)) if tail else (c, -1, np.int32, 1.0) for c in range(3)]
-            planes += [(3 + i, -1, f32 if info.ec_exp_bits[i] != 0 else np.int32, 1.0) for i in range(info.num_extra)]
-            fset = host.DeviceCanvas.fromModular(be.ctx, fr.height, fr.width, planes)
-        self.stats[-1]["plane_moves"] = []
-        if tail:
+            desc = [(c, -1, f32, inv_max(info.bits_per_sample)) if tail else (c, -1, np.int32, 1.0) for c in range(3)]
+            desc += [(3 + i, -1, f32 if info.ec_exp_bits[i] != 0 else np.int32, 1.0) for i in range(info.num_extra)]
+            fset = host.DeviceCanvas.fromModular(be.ctx, fr.height, fr.width, desc)
+        planes = FramePlanes(be, info, [None] * 3, 3, fset=fset)
+        self.stats[-1]["plane_moves"] = planes.moves
+        if tail:  # noise and splines run on the resident planes between jxl_canvas_to_planes and jxl_canvas_take_planes
             try:
-                buffers = [None] * 3
-                rp = self._chained_tail(fr, fset.toPlanes(), buffers, 3, save, True, keep=True, upsampled=True)
-                if rp is not None:
-                    fset.takePlanes()
-                else:  # the last stage was a host stage (splines without device_splines): its planes go up into the set
-                    for c in range(3):
-                        fset.upload(c, buffers[c])
-                    self.stats[-1]["plane_moves"].append("h2d")
+                planes.leave_set()
+                self._chained_tail(fr, planes, save, True, keep=True, upsampled=True)
+                planes.rejoin_set()
             except Exception:
                 fset.release()
                 raise
-        return fset
+        return planes
 
-    def _modular_frame_image(self, fr):
+    def _modular_frame_image(self, fr, bus0):
         """device_image, route "modular frame": the encoded channels up once, one plan, one set; nothing comes down"""
         info, be = self.info, self.backend
         host = be.host
+        self.visibleFrames += 1
+        self.invisibleFrames = 0
         ms = self._modular_plan_run()
         n = 3 + info.num_extra
-        if getattr(self, "trace", None) is not None:  # a listener wants the samples: copies come down, the result stays
+        if self.trace is not None:  # a listener wants the samples: copies come down, the result stays
             self._trace("mod", ms.getDecodedBuffer(), False)
         planes = [(c, -1, np.int32, 1.0) for c in range(3)]
         planes += [(3 + i, -1, np.float32 if info.ec_exp_bits[i] != 0 else np.int32, 1.0) for i in range(info.num_extra)]
         cv = host.DeviceCanvas.fromModular(be.ctx, fr.height, fr.width, planes)
-        if getattr(self, "trace", None) is not None:
+        if self.trace is not None:
             self._trace("xyb", [cv.download(c) for c in range(n)], False)
         if info.orientation != 1:
             cv.orient(info.orientation)
+        self.stats[-1].update(image="device set (modular frame)", output="device", canvas="host",
+                              frame="host: device_image's modular frame route" if self.device_frames else "host: device_frames is off")
+        self._bus_since(bus0)
+        if self.device_palette:
+            self.stats[-1]["palette"] = []
         return JXLImage([None] * n, info, be, planeSet=cv)
 
-    def decode(self):
-        info, be = self.info, self.backend
-        colors_img = 1 if info.colour_space == CE_GRAY else 3
-        if self.canvas is None:
-            self.canvas = [None] * (colors_img + info.num_extra)
-        produced = False
-        fr_last = None
-        while True:
-            dev_palette = getattr(self, "device_palette", False)
-            if dev_palette:
-                if not hasattr(be, "palette"):
-                    raise RuntimeError("device_palette needs a backend with `palette`")
-                if hasattr(be, "palette_log"):
-                    del be.palette_log[:]
-            dev_image = getattr(self, "device_image", False)
-            if dev_image and not hasattr(be, "ctx"):
-                raise RuntimeError("device_image needs a backend with a device context")
-            dev_frames = getattr(self, "device_frames", False)
-            hooks = (be.squeeze, be.rct, be.palette if dev_palette else None)
-            try:
-                if dev_image or dev_frames:  # the frame-level transforms wait until the route is known
-                    self.fe.set_defer_transforms(True)
-                fr = self.fe.next_frame(*hooks)
-            except frontend.FrontendError as e:
-                raise self._map(e)
-            if fr is None:
-                break
-            fr_last = fr
-            produced = True
+    # -- the decode loop (JXLCodestreamDecoder.decode :546-677) ----------------------------------------------------
+    def _check_switches(self):
+        be = self.backend
+        if self.device_palette and not hasattr(be, "palette"):
+            raise RuntimeError("device_palette needs a backend with `palette`")
+        if self.device_image and not hasattr(be, "ctx"):
+            raise RuntimeError("device_image needs a backend with a device context")
+        if self.device_canvas and not hasattr(be, "ctx"):
+            raise RuntimeError("device_canvas needs a backend with a device context")
+
+    def _hooks(self):
+        be = self.backend
+        return be.squeeze, be.rct, be.palette if self.device_palette else None
+
+    def _next_frame(self):
+        """the next frame header from the front-end, with a fresh stats row; None at the end of the stream. With device_image
+        or device_frames the frame-level transforms wait until the route is known (_pending_transforms)"""
+        if self.device_palette and hasattr(self.backend, "palette_log"):
+            del self.backend.palette_log[:]
+        try:
+            if self.device_image or self.device_frames:
+                self.fe.set_defer_transforms(True)
+            fr = self.fe.next_frame(*self._hooks())
+        except frontend.FrontendError as e:
+            raise self._map(e)
+        if fr is not None:
             self.frames_decoded += 1
             self.stats.append(dict(encoding="vardct" if fr.encoding == VARDCT else "modular", width=fr.width, height=fr.height,
-                                   groups=fr.num_groups, passes=fr.num_passes))
-            bus0 = tuple(getattr(getattr(be, "ctx", None), "blend_bus", (0, 0)))  # (host._bus: what the blend path moves)
-            self.stats[-1]["image"] = "host: device_image is off"
-            if dev_image:
-                why = self._modular_frame_route(fr, self._colors(fr), colors_img)
-                if why is None:
-                    self.visibleFrames += 1
-                    self.invisibleFrames = 0
-                    image = self._modular_frame_image(fr)
-                    bus1 = tuple(getattr(be.ctx, "blend_bus", (0, 0)))
-                    self.stats[-1].update(image="device set (modular frame)", output="device", canvas="host",
-                                          frame="host: device_image's modular frame route" if dev_frames else "host: device_frames is off",
-                                          blend_bus=(bus1[0] - bus0[0], bus1[1] - bus0[1]))
-                    if dev_palette:
-                        self.stats[-1]["palette"] = []
-                    return image
-                self.stats[-1]["image"] = "host: " + why
-            colors = self._colors(fr)
-            resident = getattr(be, "resident", False) and colors == 3  # row f4: the stages after decodeFrame chained on the device
-            direct = self._direct_frame(fr, resident, colors_img)
-            self.stats[-1]["frame"] = self._frame_set_route(fr, direct) if dev_frames else "host: device_frames is off"
-            frame_set = self.stats[-1]["frame"] == "device set (modular)"
-            if (dev_image or dev_frames) and not frame_set:
-                try:  # every other frame: the pending transforms through today's hooks, and on exactly as without the switch
-                    self.fe.apply_transforms(*hooks)
-                except frontend.FrontendError as e:
-                    raise self._map(e)
-            if dev_palette:
-                self.stats[-1]["palette"] = [dict(e) for e in getattr(be, "palette_log", [])]
-            if fr.flags & FLAG_USE_LF_FRAME and self.lfBuffer[fr.lf_level] is None:
-                raise InvalidBitstreamException("LF Level too large")  # JXLCodestreamDecoder.java:613-614
-            if frame_set:
-                # device_frames: the Modular context -> the frame's set -> the blend; no host buffers (the canvas is a set or
-                # becomes one now: _frame_set_route has looked)
-                self.stats[-1].update(output="host", canvas="device")
-                save = self._count_frame(fr)
-                fset = self._modular_frame_set(fr, save)
-                self._canvas_frame(fr, None, None, colors, fset)
-                if self._frame_done(fr, save, bus0):
-                    break
-                continue
-            simple = fr.upsampling == 1 and not fr.num_patches and not fr.has_splines and not fr.has_noise and \
-                not (fr.save_before_ct and not fr.is_last)
-            ph, pw = fr.padded_height, fr.padded_width
-            buffers = []
-            for c in range(colors + info.num_extra):
-                if c < colors:
-                    is_float = bool(info.xyb_encoded) or fr.encoding == VARDCT or info.exp_bits != 0
-                else:
-                    is_float = info.ec_exp_bits[c - colors] != 0
-                buffers.append(np.zeros((ph, pw), F if is_float else np.int32))
-            xyb_done = False
-            rp = None
-            self.stats[-1]["output"] = "host"
-            # device_canvas: the canvas lives in a plane set from the first frame that reaches it until something lands it
-            dcan = getattr(self, "device_canvas", False) and not direct
-            if dcan and not hasattr(be, "ctx"):
-                raise RuntimeError("device_canvas needs a backend with a device context")
-            if dcan and self._landed is None and colors_img != 3:
-                self._landed = "one-colour image"
-            if dcan and fr.num_patches and fr.type != LF_FRAME:  # blendBuffers casts a patch's reference in place: no set stays up
-                self._land("a frame with patches")
-            dcan = dcan and self._landed is None
-            self.stats[-1]["canvas"] = "host" if not getattr(self, "device_canvas", False) or direct else \
-                "device" if self._landed is None else "landed: " + self._landed
-            if fr.encoding == VARDCT:
-                # an LF frame's buffers are read back as XYB LF coefficients (LFCoefficients.java:44-57) and are stored
-                # BEFORE performColorTransforms (JXLCodestreamDecoder.java:615-617): never fuse the inverse XYB into them
-                fuse_xyb = bool(info.xyb_encoded) and simple and fr.lf_level == 0 and fr.type != LF_FRAME
-                # frames with stages between decodeFrame and the colour transform keep their colour planes on the device
-                # through those stages (row f4); LF frames / lfBuffer consumers need the padded planes on the host
-                if (not simple or direct or dcan) and resident and fr.lf_level == 0 and fr.type != LF_FRAME:
-                    rp = self._vardct_frame(fr, fuse_xyb, keep=(fr.height, fr.width))  # (fuse_xyb: simple frames only)
-                    xyb_done = fuse_xyb
-                    for c in range(3):
-                        buffers[c] = np.zeros((fr.height, fr.width), F)  # stand-ins until the chained tail downloads
-                else:
-                    planes = self._vardct_frame(fr, fuse_xyb)
-                    xyb_done = fuse_xyb
-                    for c in range(3):
-                        buffers[c] = planes[c]
-            self._modular_buffers(fr, buffers, colors)
-            # (trace: the cut points of integration/jvm_pin/StageDump.java. For a VarDCT frame the colour planes in `buffers` are
-            # already the fused kernel's result -- `fused` tells the listener to take the stages of planes 0..2 elsewhere)
-            fused = fr.encoding == VARDCT
-            self._trace("idct", buffers, fused)
-            self._trace("sub", buffers, fused)  # Frame.invertSubsampling: VarDCT colour planes only (inside the backend call)
+                                   groups=fr.num_groups, passes=fr.num_passes, output="host"))
+        return fr
 
-            def colour_planes_to_float():
-                # Frame.performGabConvolution / performEdgePreservingFilter cast integer colour planes to float first
-                # (Frame.java:519: ImageBuffer.castToFloat = v * (1f / maxValue)); one-colour frames keep one plane (the backends
-                # feed the three-channel kernels three copies: Frame.java:642,661 read channel 0 in all three rounds)
-                for c in range(colors):
-                    if buffers[c].dtype != np.float32:
-                        maxv = (1 << info.bits_per_sample) - 1
-                        buffers[c] = be.modular_to_float(np.ascontiguousarray(buffers[c], np.int32), None, float(F(1) / F(maxv)))
-                return np.stack(buffers[:colors])
-            if fr.encoding == MODULAR and fr.gab:
-                planes = be.gab(colour_planes_to_float(), list(fr.gab1), list(fr.gab2))
-                for c in range(colors):
-                    buffers[c] = np.ascontiguousarray(planes[c])
-            self._trace("gab", buffers, fused)
-            if fr.encoding == MODULAR and fr.epf_iters > 0:
-                sigma = F(F(1) / F(fr.epf_sigma_modular))  # Frame.java:573-575
-                planes = be.epf(colour_planes_to_float(), fr.epf_iters, None, float(sigma),
-                                dict(channel_scale=list(fr.epf_channel_scale), pass0=fr.epf_pass0_sigma,
-                                     pass2=fr.epf_pass2_sigma, border_sad_mul=fr.epf_border_sad_mul))
-                for c in range(colors):
-                    buffers[c] = np.ascontiguousarray(planes[c])
-            self._trace("epf", buffers, fused)
-            if fr.lf_level > 0:  # JXLCodestreamDecoder.java:616-617: the frame's buffers as they stand after decodeFrame
-                self.lfBuffer[fr.lf_level - 1] = [np.array(b, copy=True) for b in buffers]
-            # crop to the frame bounds: everything after the restoration filters works on header.bounds
-            buffers = [np.ascontiguousarray(b[:fr.height, :fr.width]) for b in buffers]
-            if fr.type == LF_FRAME:
-                continue
-            save = self._count_frame(fr)
-            # Frame.upsample
-            for c in range(len(buffers)):
-                k = fr.upsampling if c < colors else fr.ec_upsampling[c - colors]
-                if k > 1 and not (resident and c < 3):
-                    wts = self._up_weights(k)
-                    depth = info.bits_per_sample if c < colors else info.ec_bits[c - colors]
-                    buffers[c] = be.upsample(self._to_float(buffers[c], depth), k, wts)
-            noise = None
-            if resident:
-                rp = self._chained_tail(fr, rp, buffers, colors, save, xyb_done, keep=direct or dcan)
-            elif fr.has_noise:
-                h, w = buffers[0].shape
-                noise = be.noise_init(h, w, (self.visibleFrames << 32) | self.invisibleFrames, fr.group_dim, colors)
-            direct = direct and rp is not None
-            if not resident and save and fr.save_before_ct:
-                self.reference[fr.save_as_reference] = [b.copy() for b in buffers]
-            if not resident and fr.num_patches:
-                if not (getattr(self, "device_patches", False) and colors == 3 and colors_img == 3 and self._patches_device(fr, buffers, colors, None)):
-                    self._patches(fr, buffers, colors)
-                    self.stats[-1].setdefault("patches", dict(path="blend calls"))
-            if not resident and fr.has_splines:  # Frame.renderSplines (host-side, as in the reference)
-                for c in range(3):
-                    buffers[c] = self._to_float(buffers[c], info.bits_per_sample).copy()
-                if getattr(self, "device_splines", False):  # the stage entry: no silent return to the host render
-                    planes = be.splines(np.stack(buffers[:3]), self.fe.splines(), fr.base_corr_x, fr.base_corr_b)
-                    for c in range(3):
-                        buffers[c] = np.ascontiguousarray(planes[c])
-                else:
-                    render_splines(buffers, self.fe.splines(), fr.base_corr_x, fr.base_corr_b, buffers[0].shape[1], buffers[0].shape[0])
-            if noise is not None:
-                planes = np.stack([self._to_float(buffers[c], info.bits_per_sample) for c in range(3)])
-                planes = be.noise_add(planes, noise, np.array(fr.noise, F), fr.base_corr_x, fr.base_corr_b)
-                for c in range(3):
-                    buffers[c] = np.ascontiguousarray(planes[c])
-            # performColorTransforms
-            if not resident and ((info.xyb_encoded and not xyb_done) or fr.do_ycbcr):
-                planes = np.stack([self._to_float(buffers[c], info.bits_per_sample) for c in range(3)])
-                if info.xyb_encoded and not xyb_done:
-                    m, bias, cbrt = self._opsin()
-                    planes = be.xyb(planes, m, bias, cbrt, info.intensity_target)
-                if fr.do_ycbcr:
-                    planes = be.ycbcr(planes)
-                for c in range(3):
-                    buffers[c] = np.ascontiguousarray(planes[c])
-            if (direct or (dcan and rp is not None)) and getattr(self, "trace", None) is not None:  # a listener wants the samples: a copy comes down, the planes stay
-                planes = rp.download()
-                self.stats[-1]["plane_moves"].append("trace")
-                for c in range(3):
-                    buffers[c] = planes[c]
-            self._trace("xyb", buffers, False)  # JXLCodestreamDecoder.java:637: the frame's buffers after performColorTransforms
-            if fr.encoding == VARDCT and getattr(self, "draw_varblocks", False):  # JXLCodestreamDecoder.java:638-639
-                blocks, cells = self._varblock_list
-                self.stats[-1]["varblock_types"] = self.stats[-1]["varblocks"]
-                if rp is not None:
-                    rp.varblocks(blocks, cells)
-                    self.stats[-1]["varblocks"] = "device planes"
-                else:
-                    planes = be.varblocks(np.stack([self._to_float(buffers[c], info.bits_per_sample) for c in range(3)]), blocks, cells)
-                    for c in range(3):
-                        buffers[c] = np.ascontiguousarray(planes[c])
-                    self.stats[-1]["varblocks"] = "host planes"
-            if direct:
-                # the frame replaces the whole canvas: its colour planes are the image's; the extra channels take the usual way
-                self.stats[-1]["output"] = "device"
-                for c in range(3, len(self.canvas)):
-                    self.canvas[c] = np.zeros((info.height, info.width), F)
-                self._blend_frame(fr, buffers, colors, first=3)
-                if info.orientation != 1:
-                    rp.orient(info.orientation)
-                extras = [be.orient(np.ascontiguousarray(b), info.orientation) if info.orientation != 1 else b for b in self.canvas[3:]]
-                return JXLImage([None] * 3 + extras, info, be, resident=rp)
-            if dcan:
-                self._canvas_frame(fr, buffers, rp, colors)
+    def _pending_transforms(self, fr, frame_set):
+        """a frame that makes no plan of its deferred transforms runs them through the usual hooks and goes on exactly as
+        without the switches; then what every frame's header owes: the palette log, the LF level"""
+        if (self.device_image or self.device_frames) and not frame_set:
+            try:
+                self.fe.apply_transforms(*self._hooks())
+            except frontend.FrontendError as e:
+                raise self._map(e)
+        if self.device_palette:
+            self.stats[-1]["palette"] = [dict(e) for e in getattr(self.backend, "palette_log", [])]
+        if fr.flags & FLAG_USE_LF_FRAME and self.lfBuffer[fr.lf_level] is None:
+            raise InvalidBitstreamException("LF Level too large")  # JXLCodestreamDecoder.java:613-614
+
+    def _host_frame(self, fr, colors, keep):
+        """Frame.decodeFrame and what follows it on the padded planes: the VarDCT call or the Modular channels, the Modular
+        frame's Gab / EPF, the LF-frame bookkeeping, the crop to the frame's bounds. keep: the colours of a VarDCT frame stay on
+        the device for the caller's sake (device_output, device_canvas). Returns (FramePlanes, whether XYB has been inverted)"""
+        info, be = self.info, self.backend
+        resident = getattr(be, "resident", False) and colors == 3  # row f4: the stages after decodeFrame chained on the device
+        simple = fr.upsampling == 1 and not fr.num_patches and not fr.has_splines and not fr.has_noise and \
+            not (fr.save_before_ct and not fr.is_last)
+        buffers = []
+        for c in range(colors + info.num_extra):
+            if c < colors:
+                is_float = bool(info.xyb_encoded) or fr.encoding == VARDCT or info.exp_bits != 0
             else:
-                if self.canvas[0] is None:
-                    for c in range(len(self.canvas)):
-                        self.canvas[c] = np.zeros((info.height, info.width), buffers[0].dtype)
-                if fr.type in (REGULAR_FRAME, SKIP_PROGRESSIVE):
-                    if any(self.reference[i] is self.canvas and i != fr.save_as_reference for i in range(4)):
-                        self.canvas = [b.copy() for b in self.canvas]
-                    self._blend_frame(fr, buffers, colors)
-            if self._frame_done(fr, save, bus0):
+                is_float = info.ec_exp_bits[c - colors] != 0
+            buffers.append(None if c < 3 and fr.encoding == VARDCT else np.zeros((fr.padded_height, fr.padded_width), F if is_float else np.int32))
+        xyb_done, rp = False, None
+        if fr.encoding == VARDCT:
+            # an LF frame's buffers are read back as XYB LF coefficients (LFCoefficients.java:44-57) and are stored
+            # BEFORE performColorTransforms (JXLCodestreamDecoder.java:615-617): never fuse the inverse XYB into them
+            xyb_done = bool(info.xyb_encoded) and simple and fr.lf_level == 0 and fr.type != LF_FRAME
+            # frames with stages between decodeFrame and the colour transform keep their colour planes on the device
+            # through those stages (row f4); LF frames / lfBuffer consumers need the padded planes on the host
+            if (not simple or keep) and resident and fr.lf_level == 0 and fr.type != LF_FRAME:
+                rp = self._vardct_frame(fr, xyb_done, keep=(fr.height, fr.width))  # (fused XYB: simple frames only)
+            else:
+                buffers[:3] = self._vardct_frame(fr, xyb_done)
+        self._modular_buffers(fr, buffers, colors)
+        # (trace: the cut points of integration/jvm_pin/StageDump.java. For a VarDCT frame the colour planes in `buffers` are
+        # already the fused kernel's result, or None while they are on the device -- `fused` tells the listener to take the
+        # stages of planes 0..2 elsewhere)
+        fused = fr.encoding == VARDCT
+        self._trace("idct", buffers, fused)
+        self._trace("sub", buffers, fused)  # Frame.invertSubsampling: VarDCT colour planes only (inside the backend call)
+
+        def colour_planes_to_float():
+            # Frame.performGabConvolution / performEdgePreservingFilter cast integer colour planes to float first
+            # (Frame.java:519: ImageBuffer.castToFloat = v * (1f / maxValue)); one-colour frames keep one plane (the backends
+            # feed the three-channel kernels three copies: Frame.java:642,661 read channel 0 in all three rounds)
+            for c in range(colors):
+                if buffers[c].dtype != np.float32:
+                    maxv = (1 << info.bits_per_sample) - 1
+                    buffers[c] = be.modular_to_float(np.ascontiguousarray(buffers[c], np.int32), None, float(F(1) / F(maxv)))
+            return np.stack(buffers[:colors])
+        if fr.encoding == MODULAR and fr.gab:
+            planes = be.gab(colour_planes_to_float(), list(fr.gab1), list(fr.gab2))
+            buffers[:colors] = [np.ascontiguousarray(planes[c]) for c in range(colors)]
+        self._trace("gab", buffers, fused)
+        if fr.encoding == MODULAR and fr.epf_iters > 0:
+            sigma = F(F(1) / F(fr.epf_sigma_modular))  # Frame.java:573-575
+            planes = be.epf(colour_planes_to_float(), fr.epf_iters, None, float(sigma),
+                            dict(channel_scale=list(fr.epf_channel_scale), pass0=fr.epf_pass0_sigma,
+                                 pass2=fr.epf_pass2_sigma, border_sad_mul=fr.epf_border_sad_mul))
+            buffers[:colors] = [np.ascontiguousarray(planes[c]) for c in range(colors)]
+        self._trace("epf", buffers, fused)
+        if fr.lf_level > 0:  # JXLCodestreamDecoder.java:616-617: the frame's buffers as they stand after decodeFrame
+            self.lfBuffer[fr.lf_level - 1] = [np.array(b, copy=True) for b in buffers]
+        # crop to the frame bounds: everything after the restoration filters works on header.bounds
+        buffers = [b if b is None else np.ascontiguousarray(b[:fr.height, :fr.width]) for b in buffers]
+        return FramePlanes(be, info, buffers, colors, rp=rp), xyb_done
+
+    def _after_colour_transforms(self, fr, planes):
+        """JXLCodestreamDecoder.java:637-639: the trace cut of the frame's buffers after performColorTransforms, then
+        Frame.drawVarblocks with draw_varblocks"""
+        if self.trace is not None:  # a listener wants the samples: a copy comes down, the planes stay
+            self._trace("xyb", planes.snapshot("trace"), False)
+        if fr.encoding == VARDCT and self.draw_varblocks:
+            st = self.stats[-1]
+            st["varblock_types"] = st["varblocks"]
+            st["varblocks"] = planes.varblocks(*self._varblock_list)
+
+    def _direct_image(self, fr, planes):
+        """device_output: the frame replaces the whole canvas: its resident colour planes are the image's; the extra channels
+        take the usual way"""
+        info, be = self.info, self.backend
+        self.stats[-1]["output"] = "device"
+        for c in range(3, len(self.canvas)):
+            self.canvas[c] = np.zeros((info.height, info.width), F)
+        self._blend_frame(fr, planes.host, planes.colors, first=3)
+        if info.orientation != 1:
+            planes.rp.orient(info.orientation)
+        extras = [be.orient(np.ascontiguousarray(b), info.orientation) if info.orientation != 1 else b for b in self.canvas[3:]]
+        return JXLImage([None] * 3 + extras, info, be, resident=planes.rp)
+
+    def _host_canvas_frame(self, fr, planes):
+        """one frame onto the host canvas (:640-655)"""
+        buffers = planes.to_host()
+        if self.canvas[0] is None:
+            for c in range(len(self.canvas)):
+                self.canvas[c] = np.zeros((self.info.height, self.info.width), buffers[0].dtype)
+        if fr.type in (REGULAR_FRAME, SKIP_PROGRESSIVE):
+            if any(self.reference[i] is self.canvas and i != fr.save_as_reference for i in range(4)):
+                self.canvas = [b.copy() for b in self.canvas]
+            self._blend_frame(fr, buffers, planes.colors)
+
+    def _canvas_image(self, last):
+        """the canvas as decode()'s JXLImage, after the frame `last`: oriented host arrays, or, from a canvas set, the set as
+        the image's (device_image), its float colours as the image's resident planes, or its planes downloaded"""
+        info, be, o = self.info, self.backend, self.info.orientation
+        if not self._is_set(self.canvas):
+            return JXLImage([be.orient(np.ascontiguousarray(b), o) if o != 1 else b for b in self.canvas], info, be)
+        self._release_dead()
+        cv = self.canvas
+        if self.device_image:
+            # route "canvas": the set becomes the image's, whatever its plane types -- handed over when the image ends
+            # here, cloned while the animation continues (the canvas lives on for its next frame)
+            if last.is_last:
+                ps = cv
+                self.reference = [None if r is cv else r for r in self.reference]
+                self.canvas = None
+            else:
+                ps = cv.clone()
+            if o != 1:
+                ps.orient(o)
+            self.stats[-1].update(image="device set (canvas)", output="device")
+            return JXLImage([None] * len(ps), info, be, planeSet=ps)
+        if all(t == np.float32 for t in cv.dtypes[:3]):
+            # the canvas' colour planes become the image's resident planes; the set lives on for the next animation frame
+            rp = cv.toPlanes()
+            if o != 1:
+                rp.orient(o)
+            extras = [cv.download(c) for c in range(3, len(cv))]
+            self.stats[-1]["output"] = "device"
+            return JXLImage([None] * 3 + [be.orient(b, o) if o != 1 else b for b in extras], info, be, resident=rp)
+        planes = [cv.download(c) for c in range(len(cv))]
+        return JXLImage([be.orient(b, o) if o != 1 else b for b in planes], info, be)
+
+    def decode(self):
+        """JXLCodestreamDecoder.decode (:546-677): frames until one completes an image; None at the end of the stream"""
+        colors_img = 1 if self.info.colour_space == CE_GRAY else 3
+        self._check_switches()
+        if self.canvas is None:
+            self.canvas = [None] * (colors_img + self.info.num_extra)
+        last = planes = None
+        while True:
+            fr = self._next_frame()                                   # 1. the next frame
+            if fr is None:
                 break
-        if not produced:
-            return None
-        if self._is_set(self.canvas):
-            self._release_dead()
-            cv, o = self.canvas, info.orientation
-            if getattr(self, "device_image", False):
-                # route "canvas": the set becomes the image's, whatever its plane types -- handed over when the image ends
-                # here, cloned while the animation continues (the canvas lives on for its next frame)
-                if fr_last is not None and fr_last.is_last:
-                    ps = cv
-                    self.reference = [None if r is cv else r for r in self.reference]
-                    self.canvas = None
-                else:
-                    ps = cv.clone()
-                if o != 1:
-                    ps.orient(o)
-                self.stats[-1].update(image="device set (canvas)", output="device")
-                return JXLImage([None] * len(ps), info, be, planeSet=ps)
-            if all(t == np.float32 for t in cv.dtypes[:3]):
-                # the canvas' colour planes become the image's resident planes; the set lives on for the next animation frame
-                rp = cv.toPlanes()
-                if o != 1:
-                    rp.orient(o)
-                extras = [cv.download(c) for c in range(3, len(cv))]
-                extras = [be.orient(b, o) if o != 1 else b for b in extras]
-                self.stats[-1]["output"] = "device"
-                return JXLImage([None] * 3 + extras, info, be, resident=rp)
-            planes = [cv.download(c) for c in range(len(cv))]
-            return JXLImage([be.orient(b, o) if o != 1 else b for b in planes], info, be)
-        oriented = [be.orient(np.ascontiguousarray(b), info.orientation) if info.orientation != 1 else b for b in self.canvas]
-        return JXLImage(oriented, info, be)
+            last, bus0, colors = fr, self._blend_bus(), self._colors(fr)
+            why = self._modular_frame_route(fr, colors, colors_img) if self.device_image else "device_image is off"
+            if why is None:                                           # 2. which route
+                return self._modular_frame_image(fr, bus0)
+            self.stats[-1]["image"] = "host: " + why
+            direct = self._direct_frame(fr, colors)
+            frame_set = self._frame_set_route(fr, direct)
+            self._pending_transforms(fr, frame_set)
+            if frame_set:                                             # 3. the frame's planes, 4. the tail
+                self.stats[-1]["canvas"] = "device"  # (the canvas is a set or becomes one now: _frame_set_route has looked)
+                save = self._count_frame(fr)
+                planes = self._modular_frame_set(fr, save)
+                on_set = True
+            else:
+                planes = None  # (the last frame's arrays go right before this frame's are made: the allocator hands their memory on)
+                on_set = self._canvas_route(fr, direct)
+                planes, xyb_done = self._host_frame(fr, colors, keep=direct or on_set)
+                if fr.type == LF_FRAME:
+                    continue
+                save = self._count_frame(fr)
+                self._chained_tail(fr, planes, save, xyb_done, keep=direct or on_set)
+                self._after_colour_transforms(fr, planes)
+            if direct and planes.rp is not None:                      # 5. the canvas
+                return self._direct_image(fr, planes)
+            if on_set:
+                self._canvas_frame(fr, planes)
+            else:
+                self._host_canvas_frame(fr, planes)
+            if self._frame_done(fr, save, bus0):                      # 6. done?
+                break
+        return None if last is None else self._canvas_image(last)
 
 
 # ---- PNGWriter (J/io/PNGWriter.java) ---------------------------------------------------------------------------
@@ -2131,12 +2263,7 @@ class PNGWriter:
             return
         if not image.has_icc:
             image = image.transform(primaries, WP_D65, tf, peakDetect, device=deviceColor or deviceSamples)
-        self.bitDepth = bitDepth
-        self.width, self.height = image.getWidth(), image.getHeight()
-        self.alphaIndex = image.getAlphaIndex()
-        self.colorChannels = 1 if gray else 3
-        self.colorMode = (4 if self.alphaIndex >= 0 else 0) if gray else (6 if self.alphaIndex >= 0 else 2)
-        self.deflateLevel = deflateLevel
+        self._layout(image, bitDepth, 1 if gray else 3, deflateLevel)
         planes = image.getBuffer(False)
         color = [np.ascontiguousarray(planes[c]) for c in range(self.colorChannels)]
         alpha = np.ascontiguousarray(planes[self.colorChannels + self.alphaIndex]) if self.alphaIndex >= 0 else None
@@ -2147,6 +2274,12 @@ class PNGWriter:
         # PNGWriter.java:79-111 + the writeIDAT sample order: one device pass
         self.samples = image.backend.pack(color, bitDepth, alpha, image.isAlphaPremultiplied() and alpha is not None, tagged, True)
 
+    def _layout(self, image, bitDepth, colors, deflateLevel):
+        self.bitDepth, self.colorChannels, self.deflateLevel = bitDepth, colors, deflateLevel
+        self.width, self.height = image.getWidth(), image.getHeight()
+        self.alphaIndex = image.getAlphaIndex()
+        self.colorMode = (4 if self.alphaIndex >= 0 else 0) if colors == 1 else (6 if self.alphaIndex >= 0 else 2)
+
     def _device_samples(self, image, bitDepth, primaries, tf, peakDetect, deflateLevel):
         """the constructor with deviceSamples. False (nothing done): a grey image that is tone-mapped -- PNGWriter then takes
         plane 0 and plane 1 + alphaIndex of the three-plane result for its grey layout, which the one-pass kernel has no
@@ -2155,24 +2288,14 @@ class PNGWriter:
         if not hasattr(be, "png_samples"):
             raise TypeError("deviceSamples needs a backend with png_samples")
         colors = image.getColorChannelCount()
-        rp = image.resident
-        h, w = image.getHeight(), image.getWidth()
         up = 0
-        planes = [np.broadcast_to(F(0), (h, w))] * 3 if rp is not None else None  # stand-ins: the samples are on the device
-        # the image's plane set (JXLDecoder(device_image=True)): colours and alpha are read where they are. Colour planes of
-        # mixed types have no one-pass form (jxl_color_params states one type): they take the host arrays' way below
-        ps = image.planeSet if image.setLive() and len({image.planeSet.types[c] for c in range(colors)}) == 1 else None
-        if ps is not None:
-            planes = ps._stand_ins(colors)
+        planes = image._plan_planes(colors)  # (stand-ins while the samples are on the device)
 
         def peak_of(pl, **front):
             nonlocal up
-            if ps is not None:
-                return ps.colorPeak(nColor=colors, **front)
-            if rp is not None:
-                return rp.colorPeak(**front)
-            up += sum(a.nbytes for a in pl) if front.get("matrix") is not None else pl[min(1, len(pl) - 1)].nbytes
-            return be.color_peak(pl, **front)
+            peak, sent = image._peak(pl, **front)
+            up += sent
+            return peak
         if colors == 1 and not image.has_icc and not (_prim_matches(primaries, image.primariesXY) and _xy_matches(WP_D65, image.whiteXY)):
             return False  # (before the plan is made: the peak, if one is needed, is then taken once, by transform())
         plan = None if image.has_icc else image._color_plan(primaries, WP_D65, tf, peakDetect, peak_of, planes=planes)
@@ -2184,32 +2307,13 @@ class PNGWriter:
                 if len({a.dtype for a in planes}) != 1:
                     planes = [image._as_float(c) for c in range(colors)]
             params = dict(inMax=[(1 << image.bitDepths[c]) - 1 for c in range(colors)])
-        self.bitDepth = bitDepth
-        self.width, self.height = w, h
-        self.alphaIndex = image.getAlphaIndex()
-        self.colorChannels = colors
-        self.colorMode = (4 if self.alphaIndex >= 0 else 0) if colors == 1 else (6 if self.alphaIndex >= 0 else 2)
-        self.deflateLevel = deflateLevel
-        if ps is not None:
-            alpha = None
-            has_alpha = self.alphaIndex >= 0
-        else:
-            alpha = np.ascontiguousarray(image.extraChannel(self.alphaIndex)) if self.alphaIndex >= 0 else None
-            has_alpha = alpha is not None
-        kw = dict(premultiplied=image.isAlphaPremultiplied() and has_alpha, bitDepth=bitDepth, bigEndian=True,
-                  alphaDepth=image.getTaggedBitDepth(colors + self.alphaIndex) if has_alpha else None,
-                  colorDepth=image.getTaggedBitDepth(0), **params)
-        if ps is not None:  # one sample call on the set: nothing goes up, alpha included
-            self.samples = ps.pngSamples(nColor=colors, alphaPlane=colors + self.alphaIndex if has_alpha else None, **kw)
-            self.bus_bytes = (0, self.samples.nbytes)
-            return True
-        if rp is not None:
-            self.samples = rp.pngSamples(alpha, **kw)
-        else:
-            planes = [np.ascontiguousarray(a) for a in planes]
-            self.samples = be.png_samples(planes, alpha, **kw)
-            up += sum(a.nbytes for a in planes)
-        self.bus_bytes = (up + (alpha.nbytes if alpha is not None else 0), self.samples.nbytes)
+        self._layout(image, bitDepth, colors, deflateLevel)
+        has_alpha = self.alphaIndex >= 0
+        self.samples, sent = image._png_samples(
+            planes, premultiplied=image.isAlphaPremultiplied() and has_alpha, bitDepth=bitDepth, bigEndian=True,
+            alphaDepth=image.getTaggedBitDepth(colors + self.alphaIndex) if has_alpha else None,
+            colorDepth=image.getTaggedBitDepth(0), **params)
+        self.bus_bytes = (up + sent, self.samples.nbytes)
         return True
 
     @staticmethod
@@ -2244,19 +2348,9 @@ class PFMWriter:
         tagged = [image.getTaggedBitDepth(c) for c in range(colors)]
         self.bus_bytes = None
         if deviceSamples:
-            be = image.backend
-            if not hasattr(be, "pfm_samples"):
+            if not hasattr(image.backend, "pfm_samples"):
                 raise TypeError("deviceSamples needs a backend with pfm_samples")
-            if image.setLive():  # JXLDecoder(device_image=True): the set's planes, int32 or float, as they are
-                self.samples = image.planeSet.pfmSamples(nColor=colors, taggedDepths=tagged)
-                up = 0
-            elif image.resident is not None and (image._buffer[0] is None or image.resident.live()):  # (else the downloaded host arrays)
-                self.samples = image.resident.pfmSamples()
-                up = 0
-            else:
-                planes = [np.ascontiguousarray(a) for a in image.getBuffer(False)[:colors]]
-                self.samples = be.pfm_samples(planes, tagged)
-                up = sum(a.nbytes for a in planes)
+            self.samples, up = image._pfm_samples(tagged)
             self.bus_bytes = (up, self.samples.nbytes)
             return
         words = []
@@ -2300,17 +2394,7 @@ def load_vardct_frame(source, ctx, transfer=abi.TRANSFER_NONE, out_format=abi.OU
     if transfer != abi.TRANSFER_NONE or out_format != abi.OUT_F32:
         p.stages |= abi.STAGE_OUT
         p.transfer, p.out_format = transfer, out_format
-    hf = host.Frame(ctx, p, weights, woffs)
-    for g in lfgroups:
-        hf.setLFGroup(g)
-        if g.get("lf_quant") is not None:
-            hf.setLFGroupQuant(g["lfg_y"], g["lfg_x"], g["lf_quant"], g["scaled_dequant"],
-                               g["extra_precision"], g["x_factor_lf"], g["b_factor_lf"], g["adaptive_smoothing"])
-    for pass_, grp, q in groups(sparse):
-        if sparse:
-            put_group_sparse(hf, pass_, grp, q)
-        else:
-            hf.putGroup(pass_, grp, q)
+    hf = feed_frame(host.Frame(ctx, p, weights, woffs), lfgroups, groups(sparse), sparse)
     stats = dict(width=fr.width, height=fr.height, padded_width=fr.padded_width, padded_height=fr.padded_height, groups=fr.num_groups,
                  passes=fr.num_passes, epf_iters=fr.epf_iters, gab=fr.gab,
                  varblocks={abi.TT_NAME[t]: int(n) for t, n in enumerate(hist) if n})

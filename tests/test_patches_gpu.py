@@ -36,7 +36,7 @@ def _device(ctx, info, patches, frame, reference):
     fb = [b.copy() for b in frame]
     ref = [None if r is None else [None if a is None else a.copy() for a in r] for r in reference]
     dec = R.shell(info, patches, ref, _stage_backend(ctx))
-    assert dec._patches_device(R.frame_rec(patches), fb, 3, None), dec.stats
+    assert dec._patches_device(R.frame_rec(patches), decoder.FramePlanes(dec.backend, info, fb, 3)), dec.stats
     return fb, ref, dec.stats[-1]["patches"]
 
 
@@ -327,7 +327,7 @@ def _tail(device_backend, device_patches, start_resident):
     dec.info, dec.fe = Info, Fe(patches)
     buffers = [planes[c].copy() for c in range(3)]
     rp = device_backend.keep_planes(planes) if start_resident else None
-    dec._chained_tail(_Rec, rp, buffers, 3, False, False)
+    dec._chained_tail(_Rec, decoder.FramePlanes(device_backend, Info, buffers, 3, rp=rp), False, False)
     return np.stack(buffers[:3]), dec.stats[-1]
 
 

@@ -3,6 +3,7 @@ host buffers as the default decoder with PNGWriter(deviceColor=True); the frames
 device (no download of the planes, only the samples cross the bus); the others take the host arrays through
 jxl_stage_png_samples."""
 import glob
+import io
 import os
 
 import numpy as np
@@ -106,6 +107,12 @@ def test_a_trace_listener_still_gets_the_frame_after_the_colour_transforms(backe
         assert_bits_equal(seen[(True, "xyb")][c], seen[(False, "xyb")][c], "xyb cut, plane %d" % c)
 
 
+def _png_bytes(image):
+    out = io.BytesIO()
+    PNGWriter(image, deviceSamples=True).write(out)
+    return out.getvalue()
+
+
 def test_an_image_whose_planes_a_later_decode_took_raises(backend):
     path = os.path.join(ROOT, "tests", "golden", "samples", "lenna.jxl")
     _, first = _decode(path, backend, device_output=True)
@@ -116,5 +123,10 @@ def test_an_image_whose_planes_a_later_decode_took_raises(backend):
     with pytest.raises(_lib.IllegalStateException):
         PNGWriter(first, deviceSamples=True)
     kept = second.getBuffer()  # downloaded once, then the image's own
+    before = _png_bytes(second)  # (from the resident planes: they are still the image's)
     _decode(path, backend, device_output=True)
     assert all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(second.getBuffer(), kept))
+    # a downloaded image holds its samples: the writer takes the host arrays once the planes are gone, as PFMWriter does
+    after = PNGWriter(second, deviceSamples=True)
+    assert second.getAlphaIndex() < 0 and after.bus_bytes[0] == sum(a.nbytes for a in kept[:3])  # the three planes went up
+    assert _png_bytes(second) == before

@@ -210,7 +210,7 @@ def _tail(device_backend, device_splines, start_resident):
     dec.info, dec.fe = Info, Fe()
     buffers = [planes[c].copy() for c in range(3)]
     rp = device_backend.keep_planes(planes) if start_resident else None
-    dec._chained_tail(_Rec, rp, buffers, 3, False, False)
+    dec._chained_tail(_Rec, decoder.FramePlanes(device_backend, Info, buffers, 3, rp=rp), False, False)
     return np.stack(buffers[:3]), dec.stats[-1]["plane_moves"], planes, splines
 
 

@@ -115,9 +115,9 @@ def main():
 
         def device():
             fb, ref = [b.copy() for b in frame], copy_ref(reference)
-            dec = shell(info, patches, ref, be)
+            dec = shell(info, patches, ref, types.SimpleNamespace(patches=be.patches))  # (the stage entry: no resident planes)
             t0 = time.perf_counter()
-            assert dec._patches_device(rec, fb, 3, None)
+            assert dec._patches_device(rec, decoder.FramePlanes(dec.backend, info, fb, 3))
             return (time.perf_counter() - t0) * 1e3, fb, dec.stats[-1]["patches"]
         device()
         runs = [device() for _ in range(a.reps)]
