@@ -776,6 +776,36 @@ jxl_status jxl_canvas_take_planes(jxl_ctx* ctx, int32_t id);
 /* jxl_stage_orient of every plane of the set, whatever its type (the kernels move 4-byte words); orientations 5-8 exchange the
  * set's height and width. JXL_ERR_STATE: an orientation outside 1..8, as jxl_planes_orient. */
 jxl_status jxl_canvas_orient(jxl_ctx* ctx, int32_t id, int32_t orientation);
+/* ImageBuffer.castToFloat(depth) of every named plane in ONE launch: the hoisted casts of a patch segment or a blend (the frame's
+ * planes and the reference planes of up to four slots: at most 5 * JXL_CANVAS_MAX_PLANES items). Bits and tags afterwards are those
+ * of jxl_canvas_cast called per item; a plane that is float already is skipped. Asynchronous. Refused with nothing queued and no
+ * tag changed (JXL_ERR_INVALID_ARGUMENT), the items looked at in order: an unknown set, a plane outside the set, the same
+ * (set, plane) named twice -- two slots that are one set are one id: the caller names each plane once --, "invalid Max Value"
+ * exactly where jxl_canvas_cast says it (an int32 plane whose depth gives max < 1); before all of these, more items than
+ * 5 * JXL_CANVAS_MAX_PLANES. */
+typedef struct jxl_canvas_cast_item {
+    int32_t set, plane, depth;
+} jxl_canvas_cast_item;
+jxl_status jxl_canvas_cast_planes(jxl_ctx* ctx, int32_t n, const jxl_canvas_cast_item* items);
+/* computePatches (JXLCodestreamDecoder.java:212-254 + blendBuffers :415-513) as jxl_stage_patches defines it, with every plane taken
+ * from device plane sets: frame_set holds the frame's n_color + n_extra planes, of any types; ref_set[k] is the set of reference
+ * slot k, or -1 for reference[k] == null (two slots may name one set). d->ref_h / ref_w are filled from the sets: what the caller
+ * put there is ignored. colors_resident != 0: planes 0..2 of the frame are the context's resident planes (float, of the set's
+ * size) and the set's own planes 0..2 are not touched -- a VarDCT frame's colours never leave the resident planes, only its extra
+ * channels sit in the set; JXL_ERR_STATE without resident planes, JXL_ERR_INVALID_ARGUMENT when their size is not the set's.
+ * No casts: the planes have the types the caller's type plan gave them (jxl_canvas_cast_planes). Everything
+ * jxl_canvas_patches_check refuses is refused with nothing queued. Then the tables go up in one page-locked transfer and ONE
+ * k_patches launch runs on the context's stream: asynchronous, no plane crosses the bus. Nothing writes a reference plane, and the
+ * frame set is never a reference set. */
+jxl_status jxl_canvas_patches(jxl_ctx* ctx, const jxl_patch_desc* d, int32_t frame_set, int32_t colors_resident, const int32_t ref_set[4]);
+/* What jxl_canvas_patches refuses, without a context or a device (the reason: jxl_last_error of a NULL context). First the sets:
+ * a frame or a reference set whose plane count is not n_color + n_extra (JXL_ERR_INVALID_ARGUMENT), more than
+ * JXL_CANVAS_MAX_PLANES planes (JXL_ERR_UNSUPPORTED), colors_resident with n_color != 3, a frame set that is a reference set -- here:
+ * ref[k] == frame, the same shape object -- (JXL_ERR_INVALID_ARGUMENT). Then exactly jxl_patch_bins' validation with the sizes and
+ * plane types of the sets (colours float under colors_resident), its status, message and *first_bad. ref[k]: NULL for
+ * reference[k] == null. */
+jxl_status jxl_canvas_patches_check(const jxl_patch_desc* d, const jxl_canvas_shape* frame, int32_t colors_resident,
+                                    const jxl_canvas_shape* const ref[4], int32_t* first_bad);
 
 /* JXLCodestreamDecoder.transposeBufferFloat / transposeBufferInt (:43-177): EXIF orientation 1..8 of one plane of
  * 4-byte samples. out is h x w for orientation <= 4, else w x h. */

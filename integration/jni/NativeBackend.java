@@ -212,6 +212,19 @@ public final class NativeBackend implements AutoCloseable {
     /** shapes: {n, h, w, type[n]}; ref null when desc names no reference. Throws what canvasBlend would; no device needed. */
     public static native void canvasBlendCheck(int[] desc, int[] canvas, int[] frame, int[] ref);    // jxl_canvas_blend_check
 
+    /** items: 3 ints per plane {set, plane, depth}, each (set, plane) once, at most 80 planes: ImageBuffer.castToFloat(depth) of all
+     *  of them in one launch; float planes are skipped. */
+    public native void canvasCastPlanes(int[] items);              // jxl_canvas_cast_planes
+    /** computePatches on plane sets: frameSet holds the frame's nColor + ecIsAlpha.length planes, refSet the set id of each of the
+     *  four reference slots (-1: absent); pos, blend, ecIsAlpha, ecAlphaAssociated as stagePatches'. colorsResident != 0: planes 0..2
+     *  of the frame are the resident planes. One launch, asynchronous; no plane crosses the bus. */
+    public native void canvasPatches(int frameSet, int colorsResident, int[] refSet, int[] pos, int[] blend, int nColor, int[] ecIsAlpha,
+                                     int[] ecAlphaAssociated);     // jxl_canvas_patches
+    /** What canvasPatches would throw; no device needed. frame: {n, h, w, type[n]}; refs: 4 x 19 ints, per slot {n, h, w, type[16]}
+     *  with n == 0 for an absent slot and n == -1 for a slot that is the frame set itself. Returns -1. */
+    public static native int canvasPatchesCheck(int[] frame, int colorsResident, int[] refs, int[] pos, int[] blend, int nColor,
+                                                int[] ecIsAlpha, int[] ecAlphaAssociated);   // jxl_canvas_patches_check
+
     // ---- Modular: plan once (begin), run, read channel by channel
     public static native int[] modularDefaultSqueezeParams(int[] widths, int[] heights, int nbMeta);  // jxl_modular_default_squeeze_params
     public static native int[] modularSqueezedShapes(int[] widths, int[] heights, int[] squeezeParams); // jxl_modular_squeezed_shapes

@@ -597,16 +597,16 @@ JNIEXPORT jintArray JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_spline
  * (jxl_patch_pos word for word), blend = rows of (nColor + ecIsAlpha.length) x 3 ints, refShape = (h, w) per reference slot (0, 0:
  * absent). The arrays are copied and checked against each other before the library sees them; *mem is the copy (free it), NULL
  * with an exception pending on failure. */
-static jint* patch_desc(JNIEnv* e, jintArray pos, jintArray blend, jint nColor, jintArray ecIsAlpha, jintArray ecAlphaAssociated,
-                        jintArray refShape, jxl_patch_desc* d) {
-    if (!pos || !blend || !ecIsAlpha || !ecAlphaAssociated || !refShape) {
+static jint* patch_desc0(JNIEnv* e, jintArray pos, jintArray blend, jint nColor, jintArray ecIsAlpha, jintArray ecAlphaAssociated,
+                         jintArray refShape, int with_shape, jxl_patch_desc* d) {
+    if (!pos || !blend || !ecIsAlpha || !ecAlphaAssociated || (with_shape && !refShape)) {
         bad_arg(e, "jxlatte_amd: patch arrays missing");
         return NULL;
     }
     const jsize np = (*e)->GetArrayLength(e, pos), nb = (*e)->GetArrayLength(e, blend), ne = (*e)->GetArrayLength(e, ecIsAlpha);
     const jlong row = 3 * ((jlong)nColor + ne);
     if ((nColor != 1 && nColor != 3) || np % 8 || nb % row || (*e)->GetArrayLength(e, ecAlphaAssociated) != ne ||
-        (*e)->GetArrayLength(e, refShape) != 8) {
+        (with_shape && (*e)->GetArrayLength(e, refShape) != 8)) {
         bad_arg(e, "jxlatte_amd: patch arrays disagree");
         return NULL;
     }
@@ -620,7 +620,8 @@ static jint* patch_desc(JNIEnv* e, jintArray pos, jintArray blend, jint nColor, 
     (*e)->GetIntArrayRegion(e, blend, 0, nb, mem + np);
     (*e)->GetIntArrayRegion(e, ecIsAlpha, 0, ne, mem + np + nb);
     (*e)->GetIntArrayRegion(e, ecAlphaAssociated, 0, ne, mem + np + nb + ne);
-    (*e)->GetIntArrayRegion(e, refShape, 0, 8, shape);
+    memset(shape, 0, 8 * sizeof(jint));
+    if (with_shape) (*e)->GetIntArrayRegion(e, refShape, 0, 8, shape);
     if ((*e)->ExceptionCheck(e)) {
         free(mem);
         return NULL;
@@ -635,6 +636,10 @@ static jint* patch_desc(JNIEnv* e, jintArray pos, jintArray blend, jint nColor, 
     d->ec_alpha_associated = (const int32_t*)(mem + np + nb + ne);
     for (int k = 0; k < 4; k++) d->ref_h[k] = shape[2 * k], d->ref_w[k] = shape[2 * k + 1];
     return mem;
+}
+static jint* patch_desc(JNIEnv* e, jintArray pos, jintArray blend, jint nColor, jintArray ecIsAlpha, jintArray ecAlphaAssociated,
+                        jintArray refShape, jxl_patch_desc* d) {
+    return patch_desc0(e, pos, blend, nColor, ecIsAlpha, ecAlphaAssociated, refShape, 1, d);
 }
 /* n plane buffers of a ByteBuffer[] with their types (0 float, 1 int, -1 / null: absent) against the sizes they must have;
  * 0 with an exception pending when something is missing or too small */
@@ -1498,6 +1503,71 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasBlend
     if (ref && !canvas_shape(e, ref, &sr)) return;
     const jxl_status st = jxl_canvas_blend_check(&d, &sc, &sf, ref ? &sr : NULL);
     if (st != JXL_OK) rethrow(e, NULL, st);
+}
+
+/* items: 3 ints per plane {set, plane, depth} (jxl_canvas_cast_item word for word) */
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasCastPlanes(JNIEnv* e, jobject self, jintArray items) {
+    jxl_ctx* c = ctx_of(e, self);
+    jint v[3 * 5 * JXL_CANVAS_MAX_PLANES];
+    jxl_canvas_cast_item it[5 * JXL_CANVAS_MAX_PLANES];
+    const jsize n = items ? (*e)->GetArrayLength(e, items) : -1;
+    if (n < 0 || n % 3) { bad_arg(e, "jxlatte_amd: canvas cast: 3 ints per item"); return; }
+    if (n > 3 * 5 * JXL_CANVAS_MAX_PLANES) { bad_arg(e, "jxlatte_amd: canvas cast: more than 80 planes in one call"); return; }
+    if (n > 0 && !get_ints(e, items, n, v)) return;
+    for (int i = 0; i < n / 3; i++) it[i].set = v[3 * i], it[i].plane = v[3 * i + 1], it[i].depth = v[3 * i + 2];
+    CHECK(jxl_canvas_cast_planes(c, n / 3, it));
+}
+
+/* computePatches on plane sets (jxl_canvas_patches): refSet = 4 set ids (-1: absent); the patch arrays as for stagePatches, without
+ * the slot sizes (the library reads them from the sets) */
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasPatches(JNIEnv* e, jobject self, jint frameSet, jint colorsResident,
+        jintArray refSet, jintArray pos, jintArray blend, jint nColor, jintArray ecIsAlpha, jintArray ecAlphaAssociated) {
+    jxl_ctx* c = ctx_of(e, self);
+    jint ids[4];
+    if (!refSet || (*e)->GetArrayLength(e, refSet) != 4) { bad_arg(e, "jxlatte_amd: canvas patches: 4 reference set ids"); return; }
+    GETI(refSet, 4, ids);
+    jxl_patch_desc d;
+    jint* mem = patch_desc0(e, pos, blend, nColor, ecIsAlpha, ecAlphaAssociated, NULL, 0, &d);
+    if (!mem) return;
+    const jxl_status st = jxl_canvas_patches(c, &d, frameSet, colorsResident, (const int32_t*)ids);
+    free(mem);
+    CHECK(st);
+}
+
+/* jxl_canvas_patches_check (host only). frame: {n, h, w, types...}; refs: 4 x 19 ints, per slot {n, h, w, types[16]} with n == 0 for
+ * an absent slot and n == -1 for a slot that is the frame set itself */
+JNIEXPORT jint JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasPatchesCheck(JNIEnv* e, jclass k, jintArray frame, jint colorsResident,
+        jintArray refs, jintArray pos, jintArray blend, jint nColor, jintArray ecIsAlpha, jintArray ecAlphaAssociated) {
+    (void)k;
+    enum { SLOT = 3 + JXL_CANVAS_MAX_PLANES };
+    jxl_canvas_shape sf, sr[4];
+    const jxl_canvas_shape* rp[4];
+    jint v[4 * SLOT];
+    if (!canvas_shape(e, frame, &sf)) return -1;
+    if (!refs || (*e)->GetArrayLength(e, refs) != 4 * SLOT) { bad_arg(e, "jxlatte_amd: canvas patches: 4 x 19 ints of reference shapes"); return -1; }
+    if (!get_ints(e, refs, 4 * SLOT, v)) return -1;
+    for (int s = 0; s < 4; s++) {
+        const jint* q = v + s * SLOT;
+        if (q[0] < -1 || q[0] > JXL_CANVAS_MAX_PLANES) { bad_arg(e, "jxlatte_amd: canvas shape: plane count"); return -1; }
+        memset(&sr[s], 0, sizeof sr[s]);
+        sr[s].n = q[0]; sr[s].h = q[1]; sr[s].w = q[2];
+        for (int i = 0; i < q[0]; i++) sr[s].types[i] = q[3 + i];
+        rp[s] = q[0] == 0 ? NULL : q[0] == -1 ? &sf : &sr[s];
+    }
+    jxl_patch_desc d;
+    jint* mem = patch_desc0(e, pos, blend, nColor, ecIsAlpha, ecAlphaAssociated, NULL, 0, &d);
+    if (!mem) return -1;
+    int32_t bad = -1;
+    const jxl_status st = jxl_canvas_patches_check(&d, &sf, colorsResident, rp, &bad);
+    free(mem);
+    if (st != JXL_OK) {  /* (the reason is the library's: "Patch too large", ...) */
+        const char* cls = st == JXL_ERR_INVALID_BITSTREAM ? "com/traneptora/jxlatte/io/InvalidBitstreamException"
+                        : st == JXL_ERR_UNSUPPORTED       ? "java/lang/UnsupportedOperationException"
+                        : st == JXL_ERR_OOM               ? "java/lang/OutOfMemoryError"
+                                                          : "java/lang/IllegalArgumentException";
+        (*e)->ThrowNew(e, (*e)->FindClass(e, cls), jxl_last_error(NULL));
+    }
+    return bad;
 }
 
 /* ---- the varblock map drawn onto the picture (Frame.drawVarblocks, Frame.java:464-503; jxl_stage_varblocks,

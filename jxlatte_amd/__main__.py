@@ -58,6 +58,10 @@ def parser():
                     help="with --device-canvas: a Modular frame reaches the blend as a plane set made from the Modular context "
                          "(JXLDecoder device_frames; jxl_canvas_from_modular, jxl_canvas_from_modular_up, jxl_canvas_take_planes): "
                          "its encoded channels go up once and nothing comes down. The same bytes")
+    ap.add_argument("--device-patch-sets", action="store_true",
+                    help="with --device-canvas and --device-patches: a frame with patches no longer lands the canvas; computePatches "
+                         "runs on device plane sets (JXLDecoder device_patch_sets; jxl_canvas_patches, jxl_canvas_cast_planes): the "
+                         "frame's planes go up once and no reference plane crosses the bus. The same bytes")
     return ap
 
 
@@ -85,7 +89,7 @@ def main(argv=None):
     dec = JXLDecoder(a.input, backend=backend, sparse_coeffs=a.sparse_coeffs, device_splines=a.device_splines,
                      device_patches=a.device_patches, device_output=a.device_png, device_canvas=a.device_canvas,
                      draw_varblocks=a.draw_varblocks, device_palette=a.device_palette, device_image=a.device_image,
-                     device_frames=a.device_frames)
+                     device_frames=a.device_frames, device_patch_sets=a.device_patch_sets)
     image = dec.decode()
     if image is None:
         print("jxlatte_amd: no frames", file=sys.stderr)

@@ -151,6 +151,10 @@ SIGNATURES = {
     "jxl_canvas_pfm_samples": (i32, [vp, i32, C.POINTER(abi.PfmParams), vp]),
     "jxl_canvas_blend_check": (i32, [C.POINTER(abi.CanvasBlendDesc), C.POINTER(abi.CanvasShape), C.POINTER(abi.CanvasShape),
                                      C.POINTER(abi.CanvasShape)]),
+    "jxl_canvas_cast_planes": (i32, [vp, i32, C.POINTER(abi.CanvasCastItem)]),
+    "jxl_canvas_patches": (i32, [vp, C.POINTER(abi.PatchDesc), i32, i32, pi]),
+    "jxl_canvas_patches_check": (i32, [C.POINTER(abi.PatchDesc), C.POINTER(abi.CanvasShape), i32,
+                                       C.POINTER(C.POINTER(abi.CanvasShape)), pi]),
     "jxl_stage_orient": (i32, [vp, vp, i32, i32, i32, vp]),
     "jxl_stage_pack": (i32, [vp, pv3, C.POINTER(abi.PackParams), vp]),
     "jxl_stage_png_samples": (i32, [vp, pv3, vp, C.POINTER(abi.PngParams), vp]),

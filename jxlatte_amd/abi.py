@@ -164,6 +164,14 @@ class CanvasShape(C.Structure):
     _fields_ = [("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("types", C.c_int32 * CANVAS_MAX_PLANES)]
 
 
+class CanvasCastItem(C.Structure):
+    """struct jxl_canvas_cast_item"""
+    _fields_ = [("set", C.c_int32), ("plane", C.c_int32), ("depth", C.c_int32)]
+
+
+CANVAS_MAX_CASTS = 5 * CANVAS_MAX_PLANES
+
+
 class ModularPlane(C.Structure):
     """struct jxl_modular_plane"""
     _fields_ = [("channel", C.c_int32), ("add_channel", C.c_int32), ("type", C.c_int32), ("scale", C.c_float)]

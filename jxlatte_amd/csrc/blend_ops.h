@@ -1,5 +1,5 @@
 // Which inner blend function blendBuffers' switch reaches (JXLCodestreamDecoder.java:285-413, 493-512), and which planes it reads.
-// Plain C++ (no device code, no context): shared by k_blend's launcher (k_post.hip), the patch stage (patch_host.hip) and the
+// Plain C++ (no device code, no context): shared by k_blend's launcher (k_post.hip), the patch stage (patch_compile.h) and the
 // checks of canvas_check.h.
 #pragma once
 #include "../../include/jxlatte_amd.h"

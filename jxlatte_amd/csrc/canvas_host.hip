@@ -6,9 +6,11 @@
 // stream first and are complete on return (the stream does not synchronise with the null stream).
 #include "jxl_internal.h"
 #include "canvas_check.h"
+#include "canvas_patch_check.h"
 #include "modplanes_check.h"
 #include "pfm_check.h"
 
+#include <cstring>
 #include <new>
 
 namespace jxl {
@@ -231,6 +233,121 @@ jxl_status jxl_canvas_cast(jxl_ctx* c, int32_t id, int32_t plane, int32_t depth)
                             reinterpret_cast<float*>(k->plane(plane)), l.stream);
     CV_HIP(c, hipGetLastError());
     k->type[plane] = JXL_PLANE_FLOAT;
+    return JXL_OK;
+}
+
+jxl_status jxl_canvas_cast_planes(jxl_ctx* c, int32_t n, const jxl_canvas_cast_item* items) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    jxl_canvas_shape sh;  // (the check looks at one item's set at a time)
+    float scale[kCanvasMaxCasts];
+    const char* why = "";
+    auto lookup = [&](int32_t id) -> const jxl_canvas_shape* {
+        const CanvasSet* k = find(l, id);
+        if (!k) return nullptr;
+        shape_of(k, &sh);
+        return &sh;
+    };
+    if ((st = canvas_cast_list_check(n, items, lookup, scale, &why))) return ctx_fail(c, st, why);
+    CastArgs a{};
+    int64_t blocks = 0;
+    for (int32_t i = 0; i < n; i++) {
+        if (scale[i] == 0.0f) continue;
+        const CanvasSet* k = find(l, items[i].set);
+        CastItem& q = a.it[a.n];
+        q.base = k->plane(items[i].plane);
+        q.n = (int64_t)k->h * k->w;
+        q.scale = scale[i];
+        a.first_block[a.n++] = (int32_t)blocks;
+        blocks += (q.n + kCastRun - 1) / kCastRun;
+        if (blocks > INT32_MAX) return ctx_fail(c, JXL_ERR_UNSUPPORTED, "canvas cast: the planes do not fit one launch");
+    }
+    a.first_block[a.n] = (int32_t)blocks;
+    launch_canvas_cast(a, l.stream);
+    CV_HIP(c, hipGetLastError());
+    for (int32_t i = 0; i < n; i++) find(l, items[i].set)->type[items[i].plane] = JXL_PLANE_FLOAT;
+    return JXL_OK;
+}
+
+jxl_status jxl_canvas_patches_check(const jxl_patch_desc* d, const jxl_canvas_shape* frame, int32_t colors_resident,
+                                    const jxl_canvas_shape* const ref[4], int32_t* first_bad) {
+    const char* why = "";
+    bool aliased = false;
+    for (int k = 0; ref && k < 4; k++) aliased = aliased || (ref[k] && ref[k] == frame);
+    try {
+        PatchStage ps;
+        const jxl_status st = canvas_patches_check(d, frame, colors_resident, ref, aliased, &ps, &why, first_bad);
+        return st ? ctx_fail(nullptr, st, why) : JXL_OK;
+    } catch (const std::bad_alloc&) {
+        return ctx_fail(nullptr, JXL_ERR_OOM, "patches: host allocation failed");
+    }
+}
+
+jxl_status jxl_canvas_patches(jxl_ctx* c, const jxl_patch_desc* d, int32_t frame_set, int32_t colors_resident, const int32_t ref_set[4]) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    if (!d || !ref_set) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas patches: null argument");
+    const CanvasSet* fr = find(l, frame_set);
+    const CanvasSet* rf[4];
+    jxl_canvas_shape sf, sr[4];
+    const jxl_canvas_shape* srp[4];
+    bool aliased = false;
+    if (!fr) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+    shape_of(fr, &sf);
+    for (int k = 0; k < 4; k++) {
+        rf[k] = ref_set[k] == -1 ? nullptr : find(l, ref_set[k]);
+        if (ref_set[k] != -1 && !rf[k]) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+        if (rf[k]) shape_of(rf[k], &sr[k]);
+        srp[k] = rf[k] ? &sr[k] : nullptr;
+        aliased = aliased || rf[k] == fr;
+    }
+    const char* why = "";
+    const char* dev = nullptr;
+    PatchStage ps;
+    size_t off_ops, off_tile, off_start, off_list, off_planes;
+    try {
+        if ((st = canvas_patches_check(d, &sf, colors_resident, srp, aliased, &ps, &why, nullptr))) return ctx_fail(c, st, why);
+        float* rp[3] = {nullptr, nullptr, nullptr};
+        if (colors_resident) {
+            int h = 0, w = 0;
+            if ((st = ctx_planes_get(c, &h, &w, rp))) return st;
+            if (h != fr->h || w != fr->w) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: the resident planes have another size than the set");
+        }
+        if (ps.bins.tile.empty()) return JXL_OK;
+        // the tables, back to back in the page-locked staging buffer: one transfer (the layout of jxl_stage_patches)
+        const int n_chan = ps.n_chan;
+        auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+        off_ops = up(ps.rec.size() * sizeof(PatchRec));
+        off_tile = off_ops + up(ps.ops.size() * sizeof(PatchOp));
+        off_start = off_tile + up(ps.bins.tile.size() * 4);
+        off_list = off_start + up(ps.bins.start.size() * 4);
+        off_planes = off_list + up(ps.bins.list.size() * 4);
+        const size_t total = off_planes + up(((size_t)n_chan * 5 + 4) * 8);
+        char* h_tab = nullptr;
+        if ((st = ctx_tables_reserve(c, total, &h_tab))) return st;
+        memcpy(h_tab, ps.rec.data(), ps.rec.size() * sizeof(PatchRec));
+        memcpy(h_tab + off_ops, ps.ops.data(), ps.ops.size() * sizeof(PatchOp));
+        memcpy(h_tab + off_tile, ps.bins.tile.data(), ps.bins.tile.size() * 4);
+        memcpy(h_tab + off_start, ps.bins.start.data(), ps.bins.start.size() * 4);
+        memcpy(h_tab + off_list, ps.bins.list.data(), ps.bins.list.size() * 4);
+        int64_t* tab = reinterpret_cast<int64_t*>(h_tab + off_planes);
+        for (int ch = 0; ch < n_chan; ch++)
+            tab[ch] = (int64_t)reinterpret_cast<intptr_t>(colors_resident && ch < 3 ? reinterpret_cast<uint32_t*>(rp[ch]) : fr->plane(ch));
+        for (int k = 0; k < 4; k++) {
+            for (int ch = 0; ch < n_chan; ch++) tab[n_chan * (1 + k) + ch] = rf[k] ? (int64_t)reinterpret_cast<intptr_t>(rf[k]->plane(ch)) : 0;
+            tab[n_chan * 5 + k] = rf[k] ? rf[k]->w : 0;
+        }
+        if ((st = ctx_tables_send(c, total, &dev))) return st;
+    } catch (const std::bad_alloc&) {
+        return ctx_fail(c, JXL_ERR_OOM, "patches: host allocation failed");
+    }
+    launch_patches(reinterpret_cast<const int64_t*>(dev + off_planes), ps.n_chan, fr->w, reinterpret_cast<const PatchRec*>(dev),
+                   reinterpret_cast<const PatchOp*>(dev + off_ops), reinterpret_cast<const int32_t*>(dev + off_tile),
+                   reinterpret_cast<const int32_t*>(dev + off_start), reinterpret_cast<const int32_t*>(dev + off_list),
+                   (int)ps.bins.tile.size(), ps.bins.tiles_x, l.stream);
+    CV_HIP(c, hipGetLastError());
     return JXL_OK;
 }
 

@@ -3165,6 +3165,22 @@ jxl_status spline_tables(jxl_ctx* c, const jxl_spline_desc* d, int32_t height, i
 }
 }  // namespace
 
+// the same staging buffer for jxl_canvas_patches (canvas_host.hip; jxl_internal.h)
+extern "C++" {
+namespace jxl {
+jxl_status ctx_tables_reserve(jxl_ctx* c, size_t total, char** host) {
+    const jxl_status st = tables_reserve(c, total);
+    if (!st) *host = c->h_spl;
+    return st;
+}
+jxl_status ctx_tables_send(jxl_ctx* c, size_t total, const char** dev) {
+    const jxl_status st = tables_send(c, total);
+    if (!st) *dev = c->spl.as<char>();
+    return st;
+}
+}  // namespace jxl
+}  // extern "C++"
+
 jxl_status jxl_planes_splines(jxl_ctx* c, const jxl_spline_desc* d) {
     jxl_status st = bind(c);
     if (st) return st;
@@ -3233,7 +3249,7 @@ extern "C" jxl_status jxl_debug_spline_kernel_ms(jxl_ctx* c, const float* const 
     return st;
 }
 
-// ---- patches: computePatches as one launch over the binned positions (patch_host.hip, k_patch.hip) ----
+// ---- patches: computePatches as one launch over the binned positions (patch_compile.h, k_patch.hip) ----
 namespace {
 // One run of the stage on height x width planes. dev_frame[ch] != nullptr: the plane is on the device already (the resident
 // colour planes); otherwise host_frame[ch] is uploaded if some position touches it, and downloaded if some position writes it

@@ -10,6 +10,7 @@
 #include "../../include/jxl_transform_types.h"
 #include "plane_tiled.h"
 #include "blend_ops.h"
+#include "patch_compile.h"
 
 namespace jxl {
 
@@ -471,39 +472,14 @@ constexpr int64_t kSplineMaxArcs = (int64_t)1 << 26;
 static_assert(sizeof(jxl_spline_arc) == 48, "arc record");
 // the arc table of jxl_spline_arcs, uncapped; JXL_OK or a status (the reason in *why)
 jxl_status spline_arc_table(const jxl_spline_desc* d, int32_t height, int32_t width, std::vector<jxl_spline_arc>* out, const char** why);
-// The binned form of an arc table, as offsets (in int32 words) into one buffer the kernel reads: the non-empty tiles
-// (index ty * tiles_x + tx) in raster order, per non-empty tile its CSR range, and the arc indices of every tile in TABLE ORDER
-struct SplineBins {
-    int tiles_x = 0, tiles_y = 0;
-    std::vector<int32_t> tile;   // [n_tiles]
-    std::vector<int32_t> start;  // [n_tiles + 1]
-    std::vector<int32_t> list;   // [start[n_tiles]]
-};
+// SplineBins, the binned form of an arc table: patch_compile.h (the patch stage bins its positions the same way)
 // false: the lists do not fit (bad_alloc, or 2^31 entries and more)
 bool spline_bin(const jxl_spline_arc* arcs, int64_t n, int32_t height, int32_t width, SplineBins* out);
 void launch_splines(float* const planes[3], int h, int w, const jxl_spline_arc* arcs, const int32_t* tile, const int32_t* start,
                     const int32_t* list, int n_tiles, int tiles_x, hipStream_t s);
 
-// ---- patches (patch_host.hip: validation, blend functions, binning -- no device call; k_patch.hip: the kernel) ----
-constexpr int kPatchTileW = 32, kPatchTileH = 8;  // footprint of one workgroup of k_patches, as k_splines'
-// one position as the kernel reads it (wave-uniform, through scalar loads): the rectangle [y0, y1) x [x0, x1) in the frame, the
-// shift (dy, dx) from a frame pixel to its sample in the slot's planes, and its PatchOp row (one op per channel)
-struct PatchRec { int32_t y0, x0, y1, x1, dy, dx, slot, ops; };
-static_assert(sizeof(PatchRec) == 32, "patch record");
-enum PatchOpKind { POP_NONE, POP_ADD_I, POP_ADD_F, POP_MULT, POP_BLEND, POP_MULADD, POP_COPY_REF };
-constexpr int kPatchIsAlpha = 1, kPatchClamp = 2, kPatchPremult = 4, kPatchBelow = 8;
-struct PatchOp { int32_t op, alpha, flags, reserved; };  // alpha: the channel number (n_color + alphaChannel) of the alpha planes
-static_assert(sizeof(PatchOp) == 16, "patch op");
-struct PatchStage {
-    int n_chan = 0;
-    std::vector<PatchRec> rec;     // [n_pos], stage order; a skipped position has an empty rectangle and is in no list
-    std::vector<PatchOp> ops;      // rows of n_chan, one row per (blend row, slot) in use
-    std::vector<uint8_t> written;  // [n_chan]: some position stores into the channel
-    SplineBins bins;               // list entries index rec
-};
-// JXL_OK, or the status of jxl_patch_bins with the reason in *why and the offending position in *first_bad (or -1)
-jxl_status patch_compile(const jxl_patch_desc* d, int32_t height, int32_t width, const int32_t* frame_type, const int32_t* ref_type,
-                         PatchStage* out, const char** why, int32_t* first_bad);
+// ---- patches (patch_compile.h: validation, blend functions, binning -- plain C++, no device call; k_patch.hip: the kernel) ----
+// PatchRec, PatchOp, PatchStage and patch_compile: patch_compile.h
 // planes: device table of int64 -- frame plane pointers [n_chan], slot plane pointers [4][n_chan] (0: reads as zeros), slot
 // widths [4]
 void launch_patches(const int64_t* planes, int n_chan, int w, const PatchRec* rec, const PatchOp* ops, const int32_t* tile,
@@ -525,6 +501,24 @@ struct CanvasArgs {
     CanvasChan ch[JXL_CANVAS_MAX_PLANES];
 };
 void launch_canvas_blend(const CanvasArgs& a, hipStream_t s);
+// jxl_canvas_cast_planes' kernel (k_canvas.hip): ImageBuffer.castToFloat0 of every listed plane in place, one launch. One
+// workgroup converts one run of kCastRun consecutive samples of one item; first_block[i] is the first workgroup of item i
+// (first_block[n] = the grid). The table travels as the kernel's argument: wave-uniform, read through scalar loads.
+constexpr int kCastMaxItems = 5 * JXL_CANVAS_MAX_PLANES;
+constexpr int kCastRun = 4096;
+struct CastItem {
+    uint32_t* base;  // h x w 4-byte samples, int32 before and float after
+    int64_t n;       // h * w
+    float scale;     // 1f / max
+    int32_t reserved;
+};
+struct CastArgs {
+    int32_t n, reserved;
+    int32_t first_block[kCastMaxItems + 2];  // n + 1 entries in use; the even count keeps `it` 8-byte aligned without padding
+    CastItem it[kCastMaxItems];
+};
+static_assert(sizeof(CastArgs) <= 4096, "the cast table is a kernel argument");
+void launch_canvas_cast(const CastArgs& a, hipStream_t s);
 // The context is host.hip's: canvas_host.hip reaches what it needs of it through these. CanvasStore: a context's sets.
 struct CanvasStore;
 void canvas_store_free(CanvasStore* s);  // jxl_ctx_destroy, after the stream has drained
@@ -536,6 +530,10 @@ jxl_status ctx_link(jxl_ctx* c, CtxLink* out);                      // hipSetDev
 jxl_status ctx_fail(jxl_ctx* c, jxl_status st, const char* msg);    // records the message (c may be null) and returns st
 jxl_status ctx_planes_get(jxl_ctx* c, int* h, int* w, float* p[3]);  // the resident planes, or JXL_ERR_STATE
 jxl_status ctx_planes_set(jxl_ctx* c, int h, int w, float* p[3]);    // resident planes of h x w to fill (contents undefined)
+// the page-locked staging buffer of the spline and patch tables: room for `total` bytes at *host once the transfer before has read
+// it, then its first `total` bytes queued to the context's table buffer (*dev) by ONE transfer on the stream
+jxl_status ctx_tables_reserve(jxl_ctx* c, size_t total, char** host);
+jxl_status ctx_tables_send(jxl_ctx* c, size_t total, const char** dev);
 // the Modular context's result channels (device pointers), settled as jxl_modular_read_channel settles them; *ran: a plan has
 // run since jxl_modular_begin
 struct ModResult { const int32_t* d; int32_t h, w; };

@@ -14,10 +14,13 @@
 // bytes per channel. Frame and reference rows start wherever their own offset puts them: their 16-byte loads are declared
 // 4-byte aligned (gfx950 code objects run with unaligned access enabled; global_load_dwordx4 either way). Plain global loads
 // and stores only. The function of a channel is a kernel argument: scalar branches, one instance of the kernel.
+//
+// k_canvas_cast, further down: the whole-plane casts in front of such a launch (and of k_patches on plane sets), all in one.
 #include <hip/hip_runtime.h>
 
 #include "jxl_internal.h"
 #include "jxl_blend.h"
+#include "sample_ops.h"
 
 namespace jxl {
 namespace {
@@ -76,7 +79,42 @@ __global__ __launch_bounds__(256) void k_canvas_blend(const CanvasArgs a) {
     }
 }
 
+// jxl_canvas_cast_planes: ImageBuffer.castToFloat0 (ImageBuffer.java:112-127) of up to kCastMaxItems whole planes in place, ONE
+// launch. A workgroup owns one run of kCastRun consecutive samples of one plane; which plane follows from blockIdx.x and the
+// prefix first_block[] alone, so the item record is wave-uniform (scalar loads from the kernel argument). Inside the run: the
+// 0..3 samples in front of the first 16-byte boundary and the 0..3 behind the last one go sample by sample, everything between
+// as 16-byte loads and stores (a set's planes start 256-byte aligned, so for them only the last run of a plane has a tail).
+// Every lane loads exactly the words it stores, so in place is safe without any ordering between lanes.
+__global__ __launch_bounds__(256) void k_canvas_cast(const CastArgs a) {
+    const int blk = (int)blockIdx.x;
+    int item = 0;
+    while (item + 1 < a.n && blk >= a.first_block[item + 1]) item++;  // wave-uniform
+    const CastItem it = a.it[item];
+    const int64_t s = (int64_t)(blk - a.first_block[item]) * kCastRun;
+    const int len = (int)(it.n - s < kCastRun ? it.n - s : kCastRun);
+    uint32_t* p = it.base + s;
+    const int t = (int)threadIdx.x;
+    int lead = (int)((0u - (uint32_t)(reinterpret_cast<uintptr_t>(p) >> 2)) & 3u);
+    if (lead > len) lead = len;
+    if (t < lead) p[t] = as_u(cast_to_float0((int32_t)p[t], it.scale));
+    const int n4 = (len - lead) >> 2;
+    u32x4* q = reinterpret_cast<u32x4*>(p + lead);
+    for (int g = t; g < n4; g += 256) {
+        u32x4 v = q[g];
+#pragma unroll
+        for (int i = 0; i < 4; i++) v[i] = as_u(cast_to_float0((int32_t)v[i], it.scale));
+        q[g] = v;
+    }
+    const int done = lead + (n4 << 2);
+    if (t < len - done) p[done + t] = as_u(cast_to_float0((int32_t)p[done + t], it.scale));
+}
+
 }  // namespace
+
+void launch_canvas_cast(const CastArgs& a, hipStream_t s) {
+    if (a.n <= 0 || a.first_block[a.n] <= 0) return;
+    hipLaunchKernelGGL(k_canvas_cast, dim3((unsigned)a.first_block[a.n]), dim3(256), 0, s, a);
+}
 
 void launch_canvas_blend(const CanvasArgs& a, hipStream_t s) {
     if (a.n <= 0 || a.h <= 0 || a.w <= 0) return;

@@ -1,5 +1,5 @@
 // JXLCodestreamDecoder.computePatches (JXLCodestreamDecoder.java:212-254) as a pixel-owned gather: every position of a frame in
-// one launch. One workgroup = one non-empty 32 x 8 tile of the host's binning (patch_host.hip), one lane = one pixel, one wave =
+// one launch. One workgroup = one non-empty 32 x 8 tile of the host's binning (patch_compile.h), one lane = one pixel, one wave =
 // two rows of 32 (rows of 128 bytes), as in k_splines. The reference blends in place, in the order (patch, position, channel):
 // a later application reads what an earlier one stored, a colour channel reads the frame's alpha plane that an alpha-channel
 // application may have rewritten, and float sums do not commute with rounding -- but every read of one application is at the

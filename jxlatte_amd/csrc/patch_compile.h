@@ -1,14 +1,47 @@
 // Host side of the patch stage: JXLCodestreamDecoder.computePatches' checks (JXLCodestreamDecoder.java:212-254), the choice of the
 // blend function blendBuffers makes per (position, channel) (:466-512), and the binning of the positions into the tiles of
-// k_patches. No device code and no device call: jxl_patch_bins works without a GPU. No casts happen here: the planes come with
-// the types blendBuffers' side effects (:433-465) would have given them (jxlatte_amd/decoder.py: patch_type_plan).
-#include "jxl_internal.h"
-
+// k_patches. Plain C++ (no device code, no device call, no context): jxl_patch_bins works without a GPU, and the checks can be
+// compiled and run on their own (canvas_patch_check.h). No casts happen here: the planes come with the types blendBuffers' side
+// effects (:433-465) would have given them (jxlatte_amd/decoder.py: patch_type_plan).
+#pragma once
+#include <cstdint>
 #include <limits>
 #include <new>
+#include <vector>
+
+#include "../../include/jxlatte_amd.h"
+#include "blend_ops.h"
 
 namespace jxl {
-namespace {
+
+// The binned form of a table of records, as offsets (in int32 words) into one buffer the kernel reads: the non-empty tiles
+// (index ty * tiles_x + tx) in raster order, per non-empty tile its CSR range, and the record indices of every tile in TABLE ORDER
+// (the spline arcs of k_splines, the positions of k_patches)
+struct SplineBins {
+    int tiles_x = 0, tiles_y = 0;
+    std::vector<int32_t> tile;   // [n_tiles]
+    std::vector<int32_t> start;  // [n_tiles + 1]
+    std::vector<int32_t> list;   // [start[n_tiles]]
+};
+
+constexpr int kPatchTileW = 32, kPatchTileH = 8;  // footprint of one workgroup of k_patches, as k_splines'
+// one position as the kernel reads it (wave-uniform, through scalar loads): the rectangle [y0, y1) x [x0, x1) in the frame, the
+// shift (dy, dx) from a frame pixel to its sample in the slot's planes, and its PatchOp row (one op per channel)
+struct PatchRec { int32_t y0, x0, y1, x1, dy, dx, slot, ops; };
+static_assert(sizeof(PatchRec) == 32, "patch record");
+enum PatchOpKind { POP_NONE, POP_ADD_I, POP_ADD_F, POP_MULT, POP_BLEND, POP_MULADD, POP_COPY_REF };
+constexpr int kPatchIsAlpha = 1, kPatchClamp = 2, kPatchPremult = 4, kPatchBelow = 8;
+struct PatchOp { int32_t op, alpha, flags, reserved; };  // alpha: the channel number (n_color + alphaChannel) of the alpha planes
+static_assert(sizeof(PatchOp) == 16, "patch op");
+struct PatchStage {
+    int n_chan = 0;
+    std::vector<PatchRec> rec;     // [n_pos], stage order; a skipped position has an empty rectangle and is in no list
+    std::vector<PatchOp> ops;      // rows of n_chan, one row per (blend row, slot) in use
+    std::vector<uint8_t> written;  // [n_chan]: some position stores into the channel
+    SplineBins bins;               // list entries index rec
+};
+
+namespace patch_detail {
 
 struct RowInfo {
     int32_t ops = -1;        // first PatchOp of the row, or -1: not compiled yet
@@ -17,8 +50,8 @@ struct RowInfo {
 };
 
 // the ops of one (blend row, slot): blendBuffers' inner switch per channel, checked as jxl_stage_blend checks one call
-jxl_status compile_row(const jxl_patch_desc* d, int row, int slot, const int32_t* frame_type, const int32_t* ref_type, PatchStage* out,
-                       RowInfo* info, const char** why) {
+inline jxl_status compile_row(const jxl_patch_desc* d, int row, int slot, const int32_t* frame_type, const int32_t* ref_type,
+                              PatchStage* out, RowInfo* info, const char** why) {
     const int n_chan = out->n_chan;
     const bool has_extra = d->n_extra > 0;
     info->ops = (int32_t)out->ops.size();
@@ -65,7 +98,7 @@ jxl_status compile_row(const jxl_patch_desc* d, int row, int slot, const int32_t
 }
 
 // two passes over the records: count per tile, prefix sum, fill -- positions visited in stage order, so every list is in stage order
-bool patch_bin(const std::vector<PatchRec>& rec, int32_t height, int32_t width, SplineBins* out) {
+inline bool patch_bin(const std::vector<PatchRec>& rec, int32_t height, int32_t width, SplineBins* out) {
     try {
         const int tx_n = (width + kPatchTileW - 1) / kPatchTileW, ty_n = (height + kPatchTileH - 1) / kPatchTileH;
         out->tiles_x = tx_n;
@@ -100,10 +133,12 @@ bool patch_bin(const std::vector<PatchRec>& rec, int32_t height, int32_t width, 
     return true;
 }
 
-}  // namespace
+}  // namespace patch_detail
 
-jxl_status patch_compile(const jxl_patch_desc* d, int32_t height, int32_t width, const int32_t* frame_type, const int32_t* ref_type,
-                         PatchStage* out, const char** why, int32_t* first_bad) {
+// JXL_OK, or the status of jxl_patch_bins with the reason in *why and the offending position in *first_bad (or -1)
+inline jxl_status patch_compile(const jxl_patch_desc* d, int32_t height, int32_t width, const int32_t* frame_type, const int32_t* ref_type,
+                                PatchStage* out, const char** why, int32_t* first_bad) {
+    using namespace patch_detail;
     const char* dummy;
     int32_t dummy_bad;
     if (!why) why = &dummy;

@@ -23,6 +23,10 @@ __host__ __device__ __forceinline__ int32_t cast_to_int0(float v, int max_value)
     return q < 0 ? 0 : q > max_value ? max_value : q;
 }
 
+// ImageBuffer.castToFloat0 (ImageBuffer.java:112-127) of one sample, scale = 1f / max: the conversion rounded first, then one
+// f32 multiply (k_modular_to_float's expression; no contraction can join the two)
+__host__ __device__ __forceinline__ float cast_to_float0(int32_t v, float scale) { return scale * (float)v; }
+
 // OpsinInverseMatrix.invertXYB of one pixel (OpsinInverseMatrix.java:124-139)
 __device__ __forceinline__ void invert_xyb_px(const XybParams& p, float& X, float& Y, float& B) {
     const float gammaL = Y + X + p.cob[0];

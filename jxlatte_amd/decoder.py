@@ -1084,6 +1084,7 @@ class FramePlanes:
         self.be, self.info, self.host, self.colors, self.rp, self.set = backend, info, host, colors, rp, fset
         self.resident = bool(getattr(backend, "resident", False)) and colors == 3
         self.moves = []
+        self.away = False  # device_patch_sets: the colours of `set` are in the resident planes (rp) or, after a host stage, in `host`
 
     @property
     def shape(self):
@@ -1123,19 +1124,23 @@ class FramePlanes:
         """every plane as a host array while the colours stay where they are: a copy of resident colours comes down, logged
         as `log`"""
         if self.rp is None:
-            return self.host
+            return self.host if self.set is None else self.land()
         planes = self.rp.download()
         self.moves.append(log)
-        return list(planes) + self.host[3:]
+        return list(planes) + (self.host[3:] if self.set is None else [self.set.download(c) for c in range(3, len(self.set))])
 
     def land(self):
         """every plane as a host array, for a blend on the host after all (stats[k]["canvas"] tells; no move of the tail)"""
-        return [self.set.download(c) for c in range(len(self.set))] if self.set is not None else self.to_host(log=None)
+        if self.set is not None:
+            self.settle()
+            return [self.set.download(c) for c in range(len(self.set))]
+        return self.to_host(log=None)
 
     def blend_set(self):
         """a plane set of this frame for jxl_canvas_blend: the ready-made one, the resident colours with the extras uploaded
         beside them (the colours cross no bus), or the host arrays uploaded"""
         if self.set is not None:
+            self.settle()
             return self.set
         canvas, ctx = self.be.host.DeviceCanvas, self.be.ctx
         if self.rp is None:
@@ -1149,6 +1154,37 @@ class FramePlanes:
         """(the planes of a ready-made set are those of one launch: one size by construction)"""
         shape = tuple(self.shape)
         return self.set is not None or all(tuple(b.shape) == shape for b in self.host[3 if self.rp is not None else 0:])
+
+    # -- device_patch_sets: the frame's planes become a set at the patch stage ------------------------------------------------
+    def adopt_set(self):
+        """every plane of the frame in ONE set from here on, which blend_set() hands to the blend. From a host list every
+        plane goes up once; from resident colours only the extra channels do, and the colours stay where they are until
+        settle() copies them into the set (`away`). Returns the set"""
+        canvas, ctx = self.be.host.DeviceCanvas, self.be.ctx
+        if self.rp is None:
+            self.set = canvas.fromArrays(ctx, self.host)
+        else:
+            self.set = canvas.create(ctx, [np.dtype(np.float32)] * 3 + [b.dtype for b in self.host[3:]], *self.shape)
+            for i, b in enumerate(self.host[3:]):
+                self.set.upload(3 + i, b)
+            self.away = True
+        return self.set
+
+    def visit_planes(self):
+        """the colours of an adopted set into the resident planes for the stages that follow the patches; integer colours are
+        cast in the set before they leave it (every device stage works on float samples)"""
+        if not self.away:
+            ints = [(self.set, c, self.info.bits_per_sample) for c in range(3) if self.set.dtypes[c] != np.float32]
+            if ints:
+                self.be.host.canvas_cast_planes(self.be.ctx, ints)
+            self.leave_set()
+            self.away = True
+
+    def settle(self):
+        """the colours back into the adopted set, before the set is read as a whole"""
+        if self.away:
+            self.rejoin_set()
+            self.away = False
 
     # -- device_frames: the colours of the ready-made set visit the resident planes for the stages -----------------------
     def leave_set(self):
@@ -1224,11 +1260,13 @@ def _tt_dims():
 class JXLDecoder:
     # the switches' defaults (a decoder made with JXLDecoder.__new__ -- tests, tools, load_vardct_frame -- has them too)
     sparse_coeffs = device_splines = device_patches = device_output = device_canvas = False
-    draw_varblocks = device_palette = device_image = device_frames = False
+    draw_varblocks = device_palette = device_image = device_frames = device_patch_sets = False
     trace = None  # test hook: see _trace
+    _patch_sets = False  # device_patch_sets acts on the frame in hand (_canvas_route)
 
     def __init__(self, source, backend=None, sparse_coeffs=False, device_splines=False, device_patches=False, device_output=False,
-                 device_canvas=False, draw_varblocks=False, device_palette=False, device_image=False, device_frames=False):
+                 device_canvas=False, draw_varblocks=False, device_palette=False, device_image=False, device_frames=False,
+                 device_patch_sets=False):
         """sparse_coeffs: hand the HF coefficients to the backend as lists of non-zero entries (jxf_get_coeffs_sparse ->
         jxl_vardct_put_group_sparse), not as dense planes; same pixels.
         device_splines: Frame.renderSplines runs in the backend (jxl_planes_splines on the resident planes, jxl_stage_splines
@@ -1287,7 +1325,18 @@ class JXLDecoder:
         (stats[k]["plane_moves"]). The extra channels never move. The same bits as without the switch. Every other frame runs
         jxf_apply_transforms with the usual hooks and goes on as ever. stats[k]["frame"]: "device set (modular)", "host: <the
         first condition that failed>" or "host: device_frames is off". device_image's "modular frame" route and device_output's
-        direct path come first for the frames they cover."""
+        direct path come first for the frames they cover.
+        device_patch_sets: with device_canvas and device_patches, while the canvas is a plane set, on a three-colour image, a
+        frame with patches whose colour count is the image's (patch_sets_rule) no longer lands the canvas: at the patch stage
+        its planes become a plane set (from a host list every plane goes up once; from resident colours only the extra
+        channels do), and computePatches runs per segment of patch_type_plan as one jxl_canvas_cast_planes call for the hoisted
+        casts and one jxl_canvas_patches call, the reference slots read where they are -- a slot that is a plane set (the
+        canvas itself included: one set, one set of tags) keeps its casts; a slot that is a host list (saved before the colour
+        transform) keeps them in the list and goes up as a temporary set. The stages after the patches run on the resident
+        planes and the blend reads the frame's set: nothing goes up again. The same bits. stats[k]["patches"]["path"] is
+        "plane sets" and stats[k]["canvas"] stays "device"; what still lands says why there: a below mode that reads the
+        frame off its own pixel, frame planes of different sizes, a slot with another plane count, more than 16 planes."""
+        self.device_patch_sets = bool(device_patch_sets)
         self.device_frames = bool(device_frames)
         self.device_image = bool(device_image)
         self.device_palette = bool(device_palette)
@@ -1296,6 +1345,7 @@ class JXLDecoder:
         self.device_canvas = bool(device_canvas)
         self._landed = None   # why the canvas is (back) on the host for the rest of this image
         self._dead_sets = []  # plane sets of the last blend, released once the next call has no use for them
+        self._patch_sets = False  # device_patch_sets acts on the frame in hand (_canvas_route)
         self.sparse_coeffs = bool(sparse_coeffs)
         self.device_splines = bool(device_splines)
         self.device_patches = bool(device_patches)
@@ -1434,9 +1484,19 @@ class JXLDecoder:
             else:
                 self.reference[fr.save_as_reference] = [b.copy() for b in planes.to_host()]
         if fr.num_patches:
-            if not (dev_patches and planes.colors == 3 and info.colour_space != CE_GRAY and self._patches_device(fr, planes)):
+            on_sets = self._patch_sets
+            if on_sets:
+                why = self._patches_sets(fr, planes)
+                if why is not None:  # nothing has been touched: everything lands and the stage runs as without the switch
+                    self._land(why)
+                    self.stats[-1]["canvas"] = "landed: " + why
+                    on_sets = False
+            if not on_sets and not (dev_patches and planes.colors == 3 and info.colour_space != CE_GRAY and self._patches_device(fr, planes)):
                 self._patches(fr, planes.to_host(), planes.colors)
                 self.stats[-1].setdefault("patches", dict(path="blend calls"))
+        adopted = planes.set is not None and not upsampled  # (device_patch_sets: the patch stage made the frame's set)
+        if adopted and (fr.has_splines or fr.has_noise or (info.xyb_encoded and not xyb_done) or fr.do_ycbcr):
+            planes.visit_planes()
         if fr.has_splines:
             planes.splines(fr, self.fe.splines(), self.device_splines)
         if fr.has_noise:
@@ -1838,6 +1898,126 @@ class JXLDecoder:
                     lst[n] = self._to_float(lst[n], self._depth_of(n))
         return True
 
+    def _patches_sets(self, fr, planes):
+        """device_patch_sets: computePatches on plane sets. patch_type_plan, handed the sets' dtypes, says which casts and
+        which segments; per segment the hoisted casts of the frame's and the slots' planes are ONE jxl_canvas_cast_planes call
+        and the applications ONE jxl_canvas_patches call. The frame's planes become a set here (FramePlanes.adopt_set). Leaves
+        the planes, self.reference[...] and the canvas' tags as _patches would leave them. Returns None, or -- with nothing
+        touched -- the reason why the canvas lands and the stage runs as without the switch."""
+        info, be = self.info, self.backend
+        host, ctx = be.host, be.ctx
+        f32 = np.dtype(np.float32)
+        colors, shape = planes.colors, tuple(planes.shape)
+        n_chan = colors + info.num_extra
+        refs = self.reference
+        if n_chan > abi.CANVAS_MAX_PLANES:
+            return "more than 16 planes"
+        if not planes.one_size():
+            return "the frame's planes differ in size"
+        if any(r is not None and len(r) != n_chan for r in refs):
+            return "a reference slot with another plane count"
+        # the plan reads dtypes and shapes only: stand-ins for everything that is on the device
+        typed = [np.broadcast_to(np.zeros((), t), shape) for t in planes.dtypes[:n_chan]]
+        view = [r._stand_ins(len(r)) if self._is_set(r) else r for r in refs]
+        plan = patch_type_plan(info, [self.fe.patch(i) for i in range(fr.num_patches)], typed, view, colors)
+        if not plan.gather:
+            return "a below mode reads the frame off its own pixel"
+        self.stats[-1]["patches"] = dict(path="plane sets", positions=len(plan.pos), applications=len(plan.calls), segments=len(plan.segments))
+        if not plan.calls:
+            return None
+        is_alpha = [t == 0 for t in info.ec_type[:info.num_extra]]
+        assoc = [bool(v) for v in info.ec_alpha_associated[:info.num_extra]]
+        call_pos = np.array([c["pos"] for c in plan.calls]), np.array([c["d"] for c in plan.calls])
+
+        def seg_blend(seg):  # the blend rows with the modes of the applications outside the segment set to 0
+            if len(plan.segments) == 1:
+                return plan.blend
+            b = plan.blend.copy()
+            b[:, :, 0] = 0
+            sl = slice(seg["first"], seg["last"] + 1)
+            b[call_pos[0][sl], call_pos[1][sl], 0] = plan.blend[call_pos[0][sl], call_pos[1][sl], 0]
+            return b
+        resident = planes.rp is not None
+        used = sorted(plan.ref_types)  # the slots some applied patch names
+        if len(plan.segments) > 1:  # every segment is checked before the first one runs (a single one: the entry does it)
+            for seg in plan.segments:
+                fs = abi.CanvasShape()
+                fs.n, fs.h, fs.w = n_chan, shape[0], shape[1]
+                for n in range(n_chan):
+                    fs.types[n] = host._plane_code(seg["frame"][n])
+                rs = [None] * 4
+                for k in (k for k in used if k in seg["ref"]):
+                    rs[k] = abi.CanvasShape()
+                    rs[k].n, rs[k].h, rs[k].w = n_chan, view[k][0].shape[0], view[k][0].shape[1]
+                    for n in range(n_chan):  # (a plane still absent reads as zeros of whatever type: the frame plane's)
+                        rs[k].types[n] = host._plane_code(seg["ref"][k][n] if seg["ref"][k][n] is not None else seg["frame"][n])
+                host.canvas_patches_check(plan.pos, seg_blend(seg), colors, is_alpha, assoc, fs, rs, colorsResident=resident)
+        fset = planes.adopt_set()
+        # the slots as sets: a slot that is a set (the canvas itself included) is read where it is; a host list goes up as a
+        # temporary set for this frame, its absent planes as zeros of the type their first use gives them
+        slot_set, temp = {}, []
+        try:
+            for k in used:
+                r = refs[k]
+                if self._is_set(r):
+                    slot_set[k] = r
+                    continue
+                same = next((j for j in slot_set if refs[j] is r), None)
+                if same is not None:
+                    slot_set[k] = slot_set[same]
+                    continue
+                first_type = []
+                for n in range(n_chan):
+                    seen = [seg["ref"][k][n] for seg in plan.segments if k in seg["ref"] and seg["ref"][k][n] is not None]
+                    first_type.append(r[n].dtype if r[n] is not None and tuple(r[n].shape) == tuple(r[0].shape) else seen[0] if seen else f32)
+                ts = host.DeviceCanvas.create(ctx, first_type, *r[0].shape)
+                temp.append(ts)
+                for n in range(n_chan):  # (an all-zero plane of another size -- one a frame before created at ITS size -- reads as zeros)
+                    if r[n] is not None and tuple(r[n].shape) == tuple(r[0].shape):
+                        ts.upload(n, r[n])
+                    elif r[n] is not None and r[n].any():
+                        raise ValueError("planes of one reference slot differ in size")
+                slot_set[k] = ts
+
+            def casts_to(frame_types, ref_types):
+                """the planes whose tags differ from the given types, each once (aliased slots are one set)"""
+                items, named = [], set()
+                for n in range(n_chan):
+                    if not (resident and n < 3) and fset.dtypes[n] != frame_types[n]:
+                        if frame_types[n] != f32:
+                            raise ValueError("blend: this mode works on float samples")
+                        items.append((fset, n, self._depth_of(n)))
+                for k, types in ref_types.items():
+                    s_ = slot_set.get(k)
+                    for n in range(n_chan):
+                        if s_ is not None and types[n] == f32 and s_.dtypes[n] != f32 and (id(s_), n) not in named:
+                            named.add((id(s_), n))
+                            items.append((s_, n, self._depth_of(n)))
+                return items
+            for seg in plan.segments:
+                items = casts_to(seg["frame"], seg["ref"])
+                if items:
+                    host.canvas_cast_planes(ctx, items)
+                host.canvas_patches(fset, [slot_set.get(k) if k in seg["ref"] else None for k in range(4)], plan.pos, seg_blend(seg),
+                                    colors, is_alpha, assoc, colorsResident=resident)
+            # what the casts and `new ImageBuffer`s of blendBuffers leave behind in planes no application used
+            items = casts_to(plan.frame_types, plan.ref_types)
+            if items:
+                host.canvas_cast_planes(ctx, items)
+        finally:
+            self._release_dead()
+            self._dead_sets.extend(temp)  # (released once the stream has passed the launches that read them)
+        for k in used:  # a host list keeps its casts and its new planes in the list
+            lst, types = refs[k], plan.ref_types[k]
+            if self._is_set(lst):
+                continue
+            for n in range(n_chan):
+                if lst[n] is None and types[n] is not None:
+                    lst[n] = np.zeros(shape, types[n])
+                elif lst[n] is not None and lst[n].dtype != types[n]:
+                    lst[n] = self._to_float(lst[n], self._depth_of(n))
+        return None
+
     # -- the image as a device plane set (device_image) -----------------------------------------------------------
     @staticmethod
     def _one_plan_chain_rule(fr, kinds):
@@ -1940,14 +2120,39 @@ class JXLDecoder:
             self.canvas[0] is None and fr.y0 == 0 and fr.x0 == 0 and fr.width * fr.upsampling == info.width and \
             fr.height * fr.upsampling == info.height and fr.blend_mode == abi.BLEND_REPLACE
 
+    @staticmethod
+    def patch_sets_rule(device_patch_sets, device_canvas, device_patches, canvas_on_device, colors_image, colors_frame):
+        """device_patch_sets: None when the switch acts on a frame with patches -- the frame does not land the canvas and its
+        patches run on plane sets (_patches_sets) -- else the first condition that failed. canvas_on_device: nothing has landed
+        the canvas so far; colors_image / colors_frame: the colour counts of the image and of the frame"""
+        if not device_patch_sets:
+            return "device_patch_sets is off"
+        if not device_canvas:
+            return "device_canvas is off"
+        if not device_patches:
+            return "device_patches is off"
+        if not canvas_on_device:
+            return "the canvas has landed"
+        if colors_image != 3:
+            return "one-colour image"
+        if colors_frame != colors_image:
+            return "a frame of another colour count"
+        return None
+
     def _canvas_route(self, fr, direct):
         """device_canvas: whether this frame meets the canvas as a plane set. The canvas lives in one from the first frame that
         reaches it until something lands it; stats[k]["canvas"] tells. device_output's direct frame never sees a canvas"""
         on = self.device_canvas and not direct
         if on and self._landed is None and self.info.colour_space == CE_GRAY:
             self._landed = "one-colour image"
-        if on and fr.num_patches and fr.type != LF_FRAME:  # blendBuffers casts a patch's reference in place: no set stays up
-            self._land("a frame with patches")
+        self._patch_sets = False
+        if on and fr.num_patches and fr.type != LF_FRAME:
+            # blendBuffers casts a patch's reference in place: no set stays up, unless the patches run on the sets themselves
+            colors_img = 1 if self.info.colour_space == CE_GRAY else 3
+            self._patch_sets = self.patch_sets_rule(self.device_patch_sets, self.device_canvas, self.device_patches,
+                                                    self._landed is None, colors_img, self._colors(fr)) is None
+            if not self._patch_sets:
+                self._land("a frame with patches")
         self.stats[-1]["canvas"] = "host" if not on else "device" if self._landed is None else "landed: " + self._landed
         return on and self._landed is None
 
@@ -2229,6 +2434,7 @@ class JXLDecoder:
                     continue
                 save = self._count_frame(fr)
                 self._chained_tail(fr, planes, save, xyb_done, keep=direct or on_set)
+                on_set = on_set and self._landed is None  # (device_patch_sets: the patch stage may have landed the canvas)
                 self._after_colour_transforms(fr, planes)
             if direct and planes.rp is not None:                      # 5. the canvas
                 return self._direct_image(fr, planes)

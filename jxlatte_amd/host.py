@@ -1265,6 +1265,52 @@ def canvas_blend_check(desc, canvas, frame, ref):
     _lib.check(None, st)
 
 
+def canvas_cast_planes(ctx, items):
+    """ImageBuffer.castToFloat of whole planes of plane sets in ONE launch (jxl_canvas_cast_planes), asynchronous. items:
+    (DeviceCanvas, plane, depth), each (set, plane) once; a float plane is skipped. The sets' tags follow"""
+    items = list(items)
+    for s, _, _ in items:
+        s._live()
+    arr = (abi.CanvasCastItem * max(1, len(items)))()
+    for k, (s, plane, depth) in enumerate(items):
+        arr[k].set, arr[k].plane, arr[k].depth = s.id, int(plane), int(depth)
+    ctx.call("jxl_canvas_cast_planes", len(items), arr)
+    for s, plane, _ in items:
+        s.types[plane] = abi.PLANE_FLOAT
+
+
+def canvas_patches(frame, refs, pos, blend, n_color, ec_is_alpha, ec_alpha_associated, colorsResident=False):
+    """JXLCodestreamDecoder.computePatches on plane sets (jxl_canvas_patches): one launch, asynchronous, no plane crosses the bus.
+    frame: the DeviceCanvas of the frame's n_color + n_extra planes; refs: per reference slot a DeviceCanvas or None (two slots may
+    be one set); pos / blend as for computePatches. colorsResident: planes 0..2 of the frame are the context's resident planes
+    (the set's own are left alone). No casts: the planes carry the types of decoder.patch_type_plan (canvas_cast_planes)"""
+    frame._live()
+    for r in refs:
+        if r is not None:
+            r._live()
+    desc, keep = abi.make_patch_desc(pos, blend, n_color, ec_is_alpha, ec_alpha_associated, [None] * 4)
+    ids = np.array([-1 if r is None else r.id for r in refs], np.int32)
+    frame.ctx.call("jxl_canvas_patches", C.byref(desc), frame.id, 1 if colorsResident else 0, abi.iptr(ids))
+
+
+def canvas_patches_check(pos, blend, n_color, ec_is_alpha, ec_alpha_associated, frame, refs, colorsResident=False):
+    """jxl_canvas_patches_check: host only (no context, no device). frame: abi.CanvasShape; refs: per slot an abi.CanvasShape or
+    None -- the frame's own object where the frame set is that slot's set. Raises what jxl_canvas_patches would, with the
+    offending position in `.position`"""
+    from . import _lib
+    lib = _lib.load()
+    desc, keep = abi.make_patch_desc(pos, blend, n_color, ec_is_alpha, ec_alpha_associated, [None] * 4)
+    rp = (C.POINTER(abi.CanvasShape) * 4)(*[C.pointer(r) if r is not None else None for r in refs])
+    bad = C.c_int32(-1)
+    st = lib.jxl_canvas_patches_check(C.byref(desc), C.byref(frame) if frame is not None else None, 1 if colorsResident else 0, rp,
+                                      C.byref(bad))
+    if st != 0:
+        msg = lib.jxl_last_error(None)
+        err = _lib._ERR.get(int(st), _lib.JxlError)(int(st), msg.decode("utf-8", "replace") if msg else "")
+        err.position = bad.value
+        raise err
+
+
 def transposeBuffer(ctx, src, orientation):
     """JXLCodestreamDecoder.transposeBuffer (JXLCodestreamDecoder.java:43-184)"""
     if src.dtype not in (np.int32, np.float32):
