@@ -445,7 +445,8 @@ typedef struct jxl_patch_desc {
  * "Patch too large" (:228-229) and "Patch size out of bounds" (:233-237) -- the first offence returns JXL_ERR_INVALID_BITSTREAM
  * with that text in jxl_last_error(NULL) and its position in *first_bad. Then every (position, channel) with mode != 0 is mapped
  * to its blend function as blendBuffers does (:466-512, modes 5 / 6 / 7 remapped, old and new swapped for the "below" modes) and
- * checked as jxl_stage_blend checks one call: "Illegal blend mode" (JXL_ERR_INVALID_BITSTREAM), float functions on int planes,
+ * checked as jxl_stage_blend checks one call: "Illegal blend mode" (JXL_ERR_INVALID_BITSTREAM; a mode outside 0..7, and mode 1,
+ * which :484 maps to BLEND_REPLACE, for which the switch of :493-512 has no case), float functions on int planes,
  * planes of the wrong type, rectangles outside a plane it reads (JXL_ERR_INVALID_ARGUMENT). frame_type[d]: 0 float, 1 int32;
  * ref_type[4][n_color + n_extra]: the same, or -1 for a plane that is NULL (reads as zeros). JXL_ERR_UNSUPPORTED: a "below" mode
  * (5, 7) whose reference rectangle is not the frame rectangle itself in planes of the frame's size -- blendBuffers then reads the

@@ -62,6 +62,8 @@ inline jxl_status compile_row(const jxl_patch_desc* d, int row, int slot, const 
         if (mode == 0) continue;  // :241-242
         if (mode < 0 || mode > 7) return *why = "Illegal blend mode", JXL_ERR_INVALID_BITSTREAM;  // :510-511
         if (has_extra && (alpha < 0 || alpha >= d->n_extra)) return *why = "patches: alpha channel out of range", JXL_ERR_INVALID_ARGUMENT;
+        // raw mode 1 becomes BLEND_REPLACE (:484), for which the switch of :493-512 has no case: its default throws
+        if (mode == 1) return *why = "Illegal blend mode", JXL_ERR_INVALID_BITSTREAM;
         const bool is_alpha = ch >= d->n_color && d->ec_is_alpha[ch - d->n_color] != 0;  // :426
         const bool premult = has_extra && d->ec_alpha_associated[alpha] != 0;           // :431
         int pmode = mode - 1;  // :471-485
@@ -75,8 +77,7 @@ inline jxl_status compile_row(const jxl_patch_desc* d, int row, int slot, const 
         if (op == -1) return *why = "Illegal blend mode", JXL_ERR_INVALID_BITSTREAM;
         if (op == -2) return *why = "blend: this mode works on float samples", JXL_ERR_INVALID_ARGUMENT;
         // the canvas IS the frame plane and patchStart == frameOffset: copying the frame plane onto itself stores nothing new.
-        // (REPLACE copies `frame`, which is the frame plane unless below; the alpha case of MULADD copies `ref`, which is the
-        // frame plane when below)
+        // (the alpha case of MULADD copies `ref`, which is the frame plane when below; no patch mode reaches OP_COPY_FRAME)
         if (op == OP_COPY_FRAME || (op == OP_COPY_REF && below)) continue;
         bool nf, nr, nfa, nra;
         blend_needs(op, &nf, &nr, &nfa, &nra, is_alpha);

@@ -392,15 +392,23 @@ class PatchPlan:
         self.blend = None        # [n_pos][colours + num_extra][3]: one blend row per position, one entry per channel
 
 
-def patch_type_plan(info, patches, frame_buffers, reference, frame_colors):
+def _patch_upsampling_mismatch(info, fr, mode, c):
+    """computePatches' check of an extra channel's upsampling against the frame's (:243-247). fr: the frame record, looked at
+    for an extra channel with a mode above 3 only"""
+    return mode > 3 and c > 0 and fr.upsampling > 1 and (fr.ec_upsampling[c - 1] << info.ec_dim_shift[c - 1]) != fr.upsampling
+
+
+def patch_type_plan(info, patches, frame_buffers, reference, frame_colors, fr=None):
     """Simulates JXLDecoder._patches / _blend_buffers(patch=True) over the whole list of patches (the dicts of Frontend.patch) on
     the dtypes and shapes of `frame_buffers` and `reference` alone. blendBuffers casts planes to float as a side effect, decided
     on the RAW patch mode compared with the frame blend constants; the casts persist in the frame's buffers and in the reference
     slot. A cast of a plane no earlier application of the running segment handed to backend.blend commutes with those
     applications and is hoisted to the segment's entry; a cast of a plane one of them used closes the segment. So a segment is a
     maximal run of applications during which every plane they use keeps its type, and its entry types are the types after its
-    last application. Raises what _patches would raise by itself, before anything runs: the three InvalidBitstreamExceptions of
-    computePatches in stage order (and the IndexError / AttributeError of a malformed list)."""
+    last application. Raises what _patches would raise by itself, before anything runs: the InvalidBitstreamExceptions of
+    computePatches and of blendBuffers' switch (raw mode 1, "Illegal blend mode") in stage order (and the IndexError /
+    AttributeError of a malformed list). fr: the frame record (upsampling, ec_upsampling) for the check of :243-247; None: the
+    frame is not upsampled."""
     colors = 1 if info.colour_space == CE_GRAY else 3
     if colors != frame_colors:
         raise ValueError("the patch plan covers frames with the image's colour count")
@@ -441,6 +449,10 @@ def patch_type_plan(info, patches, frame_buffers, reference, frame_colors):
                 mode, alpha, clamp = (int(v) for v in p["blend"][j, c])
                 if mode == 0:
                     continue
+                if fr is not None and _patch_upsampling_mismatch(info, fr, mode, c):
+                    raise InvalidBitstreamException("Alpha channel upsampling mismatch during patches")
+                if mode == 1:  # -> BLEND_REPLACE, for which the switch of :493-512 has no case
+                    raise InvalidBitstreamException("Illegal blend mode")
                 # -- _blend_buffers(d, ..., patch=True): the canvas is the frame plane itself
                 ex = d - colors
                 is_alpha = ex >= 0 and info.ec_type[ex] == 0
@@ -1784,11 +1796,37 @@ class JXLDecoder:
             frame_buffer = frame_buffers[fb_idx] = self._to_float(frame_buffer, depth)
             canvas = canvas_list[idx] = self._to_float(canvas, depth)
             ref_buffer = ref_buffers[idx] = self._to_float(ref_buffer, depth)
+        if patch and pmode == abi.BLEND_REPLACE:  # raw mode 1: the switch of :493-512 has no case for it, behind the casts
+            raise InvalidBitstreamException("Illegal blend mode")
         old_buffer, new_buffer = (ref_buffer, frame_buffer) if below else (frame_buffer, ref_buffer)
         fa = frame_alpha if (frame_alpha is not None and frame_alpha.dtype == np.float32) else None
         ra = ref_alpha if (ref_alpha is not None and ref_alpha.dtype == np.float32) else None
-        canvas_list[idx] = self.backend.blend(pmode, canvas, old_buffer, new_buffer, rect, frameAlpha=fa, refAlpha=ra,
-                                              isAlpha=is_alpha, hasExtra=has_extra, clamp=clamp, premult=premult)
+        kw = dict(refAlpha=ra, isAlpha=is_alpha, hasExtra=has_extra, clamp=clamp, premult=premult)
+        if patch and below and tuple(ref_off) != tuple(patch_start):
+            canvas_list[idx] = self._blend_live(pmode, canvas, old_buffer, rect, fa, a_idx_frame == fb_idx, kw)
+            return
+        canvas_list[idx] = self.backend.blend(pmode, canvas, old_buffer, new_buffer, rect, frameAlpha=fa, **kw)
+
+    def _blend_live(self, pmode, canvas, frame, rect, frame_alpha, alpha_is_canvas, kw):
+        """A below patch mode away from its own pixel: the blend function's `ref` is the frame plane, which in the reference IS
+        the canvas, read at patch.bounds.origin while the position's rectangle is written; where the two overlap, later pixels
+        of its loops read what earlier ones stored. backend.blend takes canvas and `ref` as two arrays, so the rectangle goes
+        through it in pieces no pixel of which reads a pixel of the same piece, in raster order, each piece reading the canvas
+        the pieces before it left: whole when the reads lie ahead of the writes, in bands of as many rows as the shift when
+        they lie in earlier rows, in column strips of the shift's width when they lie earlier in the same rows."""
+        h, w, py, px, fy, fx, ry, rx = rect
+        dy, dx = ry - py, rx - px
+        if dy > 0 or (dy == 0 and dx > 0) or h <= 0 or w <= 0:
+            pieces = [(0, 0, h, w)]
+        elif dy < 0:
+            pieces = [(y, 0, min(-dy, h - y), w) for y in range(0, h, -dy)]
+        else:
+            pieces = [(0, x, h, min(-dx, w - x)) for x in range(0, w, -dx)]
+        for y, x, ph, pw in pieces:
+            fa = canvas if (alpha_is_canvas and frame_alpha is not None) else frame_alpha
+            canvas = self.backend.blend(pmode, canvas, frame, canvas, (ph, pw, py + y, px + x, fy + y, fx + x, ry + y, rx + x),
+                                        frameAlpha=fa, **kw)
+        return canvas
 
     def _patches(self, fr, frame_buffers, frame_colors):
         """JXLCodestreamDecoder.computePatches (:204-254)"""
@@ -1812,6 +1850,8 @@ class JXLDecoder:
                     mode, alpha, clamp = (int(v) for v in p["blend"][j, c])
                     if mode == 0:
                         continue
+                    if _patch_upsampling_mismatch(info, fr, mode, c):
+                        raise InvalidBitstreamException("Alpha channel upsampling mismatch during patches")
                     self._blend_buffers(d, frame_buffers, ref, (y0, x0), (y0, x0), (p["y0"], p["x0"]), (p["h"], p["w"]),
                                         frame_colors, mode, alpha, bool(clamp), patch=True, canvas_list=frame_buffers)
 
@@ -1826,7 +1866,7 @@ class JXLDecoder:
         colors, buffers, shape = planes.colors, planes.host, planes.shape
         n_chan = colors + info.num_extra
         typed = [np.broadcast_to(np.zeros((), t), shape) for t in planes.dtypes[:n_chan]]  # (the plan reads dtype and shape only)
-        plan = patch_type_plan(info, [self.fe.patch(i) for i in range(fr.num_patches)], typed, self.reference, colors)
+        plan = patch_type_plan(info, [self.fe.patch(i) for i in range(fr.num_patches)], typed, self.reference, colors, fr)
         st = self.stats[-1]["patches"] = dict(path="none", positions=len(plan.pos), applications=len(plan.calls), segments=len(plan.segments))
         if not plan.calls:
             return True
@@ -1919,7 +1959,7 @@ class JXLDecoder:
         # the plan reads dtypes and shapes only: stand-ins for everything that is on the device
         typed = [np.broadcast_to(np.zeros((), t), shape) for t in planes.dtypes[:n_chan]]
         view = [r._stand_ins(len(r)) if self._is_set(r) else r for r in refs]
-        plan = patch_type_plan(info, [self.fe.patch(i) for i in range(fr.num_patches)], typed, view, colors)
+        plan = patch_type_plan(info, [self.fe.patch(i) for i in range(fr.num_patches)], typed, view, colors, fr)
         if not plan.gather:
             return "a below mode reads the frame off its own pixel"
         self.stats[-1]["patches"] = dict(path="plane sets", positions=len(plan.pos), applications=len(plan.calls), segments=len(plan.segments))

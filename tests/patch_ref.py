@@ -33,7 +33,7 @@ def shell(info, patches, reference, backend):
 
 
 def frame_rec(patches):
-    return types.SimpleNamespace(num_patches=len(patches))
+    return types.SimpleNamespace(num_patches=len(patches), upsampling=1, ec_upsampling=[])
 
 
 def patch(ref, y0, x0, h, w, positions, blend, n_entries=1):

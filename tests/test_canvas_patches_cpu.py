@@ -283,7 +283,10 @@ def test_route_lands_a_list_the_launch_cannot_replay():
     assert isinstance(dec.canvas, list) and dec.reference[1] is dec.canvas  # (the alias stays an alias)
     assert [e for e in log if e[0] == "download"] == [("download", "canvas", n) for n in range(4)]
     assert planes.set is None and not [e for e in log if e[0] in ("canvas_patches", "cast_planes", "upload")]
-    assert st["patches"]["path"].startswith("blend calls") and len([e for e in log if e[0] == "blend"]) == 12
+    # 12 applications. An application whose reads lie in earlier rows of the frame plane it writes goes through backend.blend in
+    # bands of as many rows as the shift (_blend_live): position (0, 0) from origin (1, 2) reads ahead -- one call --, position
+    # (5, 9) from (1, 2) is 12 rows in bands of 4, position (4, 4) from (0, 0) is 9 rows in bands of 4; four channels each
+    assert st["patches"]["path"].startswith("blend calls") and len([e for e in log if e[0] == "blend"]) == 4 * (1 + 3 + 3)
 
 
 @pytest.mark.parametrize("off", [dict(), dict(device_patches=False)], ids=["device_patch_sets off", "device_patches off"])

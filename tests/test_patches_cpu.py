@@ -123,6 +123,10 @@ def _run_host(info, patches, frame, reference):
     def spy(idx, *a, **kw):
         n = len(rec.calls)
         inner(idx, *a, **kw)
+        # (a below mode off its own pixel goes through backend.blend in pieces, every one with the same planes: one application)
+        assert all((c["pmode"], c["given"], c["frame_alpha"], c["ref_alpha"]) == (rec.calls[n]["pmode"], rec.calls[n]["given"],
+                   rec.calls[n]["frame_alpha"], rec.calls[n]["ref_alpha"]) for c in rec.calls[n + 1:])
+        del rec.calls[n + 1:]
         for c in rec.calls[n:]:
             c["d_key"] = ("f", idx)
         seen.append(idx)

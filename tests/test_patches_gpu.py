@@ -71,7 +71,7 @@ def _case(seed, n_extra, is_int, h=37, w=75):
     small = (23, 41)
     reference = [[plane(small, c >= 3) for c in range(n_chan)], [plane((h, w), c >= 3) for c in range(n_chan)], None,
                  [None if c in (1, n_chan - 1) else plane((h, w), c >= 3) for c in range(n_chan)]]
-    modes = [0, 1, 2] + ([3, 4, 5, 6, 7] if not is_int or n_extra == 0 else [])
+    modes = [0, 2] + ([3, 4, 5, 6, 7] if not is_int or n_extra == 0 else [])  # (mode 1 is refused: test_mode_1_is_refused)
     patches = []
     for i in range(int(rng.integers(6, 10))):
         ph, pw = [(1, 1), (3, 5), (9, 40), (12, 70), (2, 33)][int(rng.integers(0, 5))] if rng.random() < 0.5 else (int(rng.integers(1, 20)), int(rng.integers(1, 38)))
@@ -123,7 +123,7 @@ def test_stage_equals_the_oracle_sequence(ctx, oracle, n_extra, is_int):
                 ex = c - 1
                 seen.add((int(m), int(cl), bool(info.ec_alpha_associated[a]) if n_extra else False, ex >= 0 and info.ec_type[ex] == 0))
     assert ran == 12, ran
-    want = {m for m in ([0, 1, 2] if is_int and n_extra else range(8))}
+    want = {m for m in ([0, 2] if is_int and n_extra else range(8)) if m != 1}
     assert {s[0] for s in seen} == want and {s[1] for s in seen} == {0, 1}, sorted(seen)
     if n_extra:
         assert {s[2] for s in seen} == {False, True} and {s[3] for s in seen} == {False, True}, sorted(seen)
@@ -177,15 +177,40 @@ def test_non_finite_samples_and_the_order_witness(ctx, oracle):
     _assert_same(got[:2], exp, "non-finite samples")
 
 
+def test_mode_1_is_refused(ctx, oracle):
+    """patch mode 1 becomes BLEND_REPLACE, for which blendBuffers' switch has no case (JXLCodestreamDecoder.java:484, :510-511):
+    host path, plan and stage entry answer "Illegal blend mode", the device routes before a plane is touched"""
+    info, patches, frame, reference = _case(1001, 1, False)
+    patches = patches + [R.patch(1, 2, 3, 4, 5, [(1, 1)], [[[2, 0, 0], [1, 0, 1]]])]
+    with pytest.raises(decoder.InvalidBitstreamException, match="Illegal blend mode"):
+        R.host_sequence(info, patches, frame, reference, oracle)
+    fb = [b.copy() for b in frame]
+    dec = R.shell(info, patches, [None if r is None else list(r) for r in reference], _stage_backend(ctx))
+    with pytest.raises(decoder.InvalidBitstreamException, match="Illegal blend mode"):
+        dec._patches_device(R.frame_rec(patches), decoder.FramePlanes(dec.backend, info, fb, 3))
+    assert all(R.same_bits(a, b) for a, b in zip(fb, frame))
+    pos, blend = R.pos_table(info, patches)
+    with pytest.raises(_lib.InvalidBitstreamException, match="Illegal blend mode"):
+        host.computePatches(ctx, fb, [None if r is None else list(r) for r in reference], pos, blend, 3, [t == 0 for t in info.ec_type],
+                            [bool(v) for v in info.ec_alpha_associated])
+    assert all(R.same_bits(a, b) for a, b in zip(fb, frame))
+
+
 def test_casts_in_the_middle_run_as_segments(ctx, oracle):
     """int planes added as ints, then a mode that casts a plane already used: two launches with the reference's cast in between"""
     info = R.make_info(1)
     rng = np.random.default_rng(5)
     frame = [rng.integers(0, 255, (30, 50)).astype(np.int32) for _ in range(4)]
     ref = [rng.integers(0, 255, (30, 50)).astype(np.int32) for _ in range(4)]
-    patches = [R.patch(0, 2, 3, 8, 9, [(1, 1), (5, 6)], [[[1, 0, 0], [0, 0, 0]]] * 2),      # mode 1 on ints: no cast, nothing stored
-               R.patch(0, 2, 3, 8, 9, [(4, 4)], [[[0, 0, 0], [1, 0, 0]]]),
-               R.patch(0, 0, 0, 10, 10, [(3, 3), (12, 30)], [[[2, 0, 0], [2, 0, 0]]] * 2)]   # mode 2 with alpha: casts everything
+    cast_all = R.patch(0, 0, 0, 10, 10, [(3, 3), (12, 30)], [[[2, 0, 0], [2, 0, 0]]] * 2)    # mode 2 with alpha: casts everything
+    # mode 1 on ints casts nothing and then meets the switch of blendBuffers, which has no case for it: the list is refused
+    refused = [R.patch(0, 2, 3, 8, 9, [(1, 1), (5, 6)], [[[1, 0, 0], [0, 0, 0]]] * 2), cast_all]
+    with pytest.raises(decoder.InvalidBitstreamException, match="Illegal blend mode"):
+        R.host_sequence(info, refused, frame, [ref, None, None, None], oracle)
+    with pytest.raises(decoder.InvalidBitstreamException, match="Illegal blend mode"):
+        _device(ctx, info, refused, frame, [ref, None, None, None])
+    patches = [R.patch(0, 2, 3, 8, 9, [(1, 1), (5, 6)], [[[0, 0, 0], [6, 0, 0]]] * 2),      # mode 6 on the int alpha channel: a copy, no cast
+               R.patch(0, 2, 3, 8, 9, [(4, 4)], [[[0, 0, 0], [6, 0, 1]]]), cast_all]
     exp = R.host_sequence(info, patches, frame, [ref, None, None, None], oracle)
     got = _device(ctx, info, patches, frame, [ref, None, None, None])
     _assert_same(got[:2], exp, "segments")

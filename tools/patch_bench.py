@@ -111,7 +111,7 @@ def main():
         n_chan = len(frame)
         n_pos = sum(p["positions"].shape[0] for p in patches)
         evals = sum(p["positions"].shape[0] * p["h"] * p["w"] for p in patches if reference[p["ref"]] is not None)
-        rec = types.SimpleNamespace(num_patches=len(patches))
+        rec = types.SimpleNamespace(num_patches=len(patches), upsampling=1, ec_upsampling=[])
 
         def device():
             fb, ref = [b.copy() for b in frame], copy_ref(reference)
@@ -133,7 +133,7 @@ def main():
         fb, ref = [b.copy() for b in frame], copy_ref(reference)
         dec = shell(info, sub, ref, be)
         t0 = time.perf_counter()
-        dec._patches(types.SimpleNamespace(num_patches=len(sub)), fb, 3)
+        dec._patches(types.SimpleNamespace(num_patches=len(sub), upsampling=1, ec_upsampling=[]), fb, 3)
         default_ms = (time.perf_counter() - t0) * 1e3 * (n_pos / min(n_pos, a.default_limit) if scaled else 1.0)
         # the kernel alone, on planes of the plan's types
         plan = decoder.patch_type_plan(info, patches, frame, reference, 3)
