@@ -954,6 +954,32 @@ int32_t    jxl_modular_last_launch_count(const jxl_ctx* ctx);
  * match (diagnostics; the result is exact either way) */
 int32_t    jxl_modular_redo_count(const jxl_ctx* ctx);
 
+/* One frame-level transform as the bitstream lists it (TransformInfo.java). kind: the front-end's numbering. */
+#define JXL_TRANSFORM_RCT     0
+#define JXL_TRANSFORM_PALETTE 1
+#define JXL_TRANSFORM_SQUEEZE 2
+typedef struct jxl_modular_transform {
+    int32_t kind;
+    int32_t begin_c, num_c;       /* RCT: begin_c; Palette: both */
+    int32_t rct_type;
+    int32_t nb_colors, nb_deltas, d_pred;
+    const jxl_squeeze_param* sp;  /* Squeeze: the expanded step list (defaults already filled in) */
+    int32_t n_sp;
+} jxl_modular_transform;
+/* jxl_modular_begin for any transform chain: tr[0 .. n_tr) in bitstream order, undone last to first exactly as
+ * ModularStream.applyTransforms does (ModularStream.java:224-380); chans is the encoded list, meta channels included, and
+ * every begin_c is read against the list as it stands at that point of the inverse walk. An inverse Palette (:327-378) reads
+ * its palette from the device copy of channel 0: nothing crosses the bus between transforms. jxl_modular_run, _out_*,
+ * _read_channel, jxl_canvas_from_modular* work on the result as on jxl_modular_begin's. A chain that jxl_modular_begin can
+ * express ([], [RCT], [Squeeze], [RCT, Squeeze]) is handed to it unchanged.
+ * Refused with nothing queued and the context usable: what jxl_stage_palette refuses for a single transform, with the sizes
+ * of the channels at that point of the walk; a Palette whose index channel begin_c + 1 is not in the list; an RCT outside the
+ * list (JXL_ERR_INVALID_ARGUMENT) or over channels of unequal size (JXL_ERR_INVALID_BITSTREAM); a Squeeze step outside the
+ * list (JXL_ERR_INVALID_BITSTREAM); an unknown kind; and, JXL_ERR_UNSUPPORTED, a Palette with nb_deltas > 0 and d_pred 6 (the
+ * weighted predictor's plane exists only while the host decodes the channel). */
+jxl_status jxl_modular_begin_chain(jxl_ctx* ctx, const jxl_channel* chans, int32_t n_chans,
+                                   const jxl_modular_transform* tr, int32_t n_tr, int32_t bit_depth);
+
 #ifdef __cplusplus
 }
 #endif

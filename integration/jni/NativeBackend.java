@@ -229,6 +229,9 @@ public final class NativeBackend implements AutoCloseable {
     public static native int[] modularDefaultSqueezeParams(int[] widths, int[] heights, int nbMeta);  // jxl_modular_default_squeeze_params
     public static native int[] modularSqueezedShapes(int[] widths, int[] heights, int[] squeezeParams); // jxl_modular_squeezed_shapes
     public native void modularBegin(ByteBuffer[] chans, int[] widths, int[] heights, int[] squeezeParams, int rctType, int rctBegin); // jxl_modular_begin
+    /** any frame-level chain as one plan: transforms = 8 ints per transform in bitstream order (kind, begin_c, num_c, rct_type,
+     *  nb_colors, nb_deltas, d_pred, n_sp), squeezeSteps = the expanded steps of every Squeeze, 4 ints each, back to back */
+    public native void modularBeginChain(ByteBuffer[] chans, int[] widths, int[] heights, int[] transforms, int[] squeezeSteps, int bitDepth); // jxl_modular_begin_chain
     public native void modularRun();                               // jxl_modular_run
     public native int modularOutCount();                           // jxl_modular_out_count
     public native int[] modularOutShape(int idx);                  // jxl_modular_out_shape -> {width, height}

@@ -1695,6 +1695,50 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_modularBegi
     CHECK(jxl_modular_begin(c, ci, n, sp, n_sp, rctType, rctBegin));
 }
 
+/* transforms: 8 ints per transform in bitstream order -- kind, begin_c, num_c, rct_type, nb_colors, nb_deltas, d_pred, n_sp;
+ * squeezeSteps: the expanded steps of every Squeeze, 4 ints each, back to back in the order of the transforms */
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_modularBeginChain(JNIEnv* e, jobject self, jobjectArray chans,
+        jintArray widths, jintArray heights, jintArray transforms, jintArray squeezeSteps, jint bitDepth) {
+    jxl_ctx* c = ctx_of(e, self);
+    const jsize n = (*e)->GetArrayLength(e, chans), n_tr = (*e)->GetArrayLength(e, transforms) / 8;
+    const jsize n_sp = (*e)->GetArrayLength(e, squeezeSteps) / 4;
+    if (n > 256 || n_tr > 64 || n_sp > 256) {
+        rethrow(e, c, JXL_ERR_INVALID_ARGUMENT);
+        return;
+    }
+    jxl_channel ci[256];
+    jxl_modular_transform tr[64];
+    jxl_squeeze_param sp[256];
+    jint w[256], h[256], trv[512], spv[1024];
+    GETI(widths, n, w);
+    GETI(heights, n, h);
+    GETI(transforms, n_tr * 8, trv);
+    GETI(squeezeSteps, n_sp * 4, spv);
+    for (jsize i = 0; i < n; i++) {
+        jobject b = (*e)->GetObjectArrayElement(e, chans, i);
+        if ((*e)->ExceptionCheck(e)) return;
+        ci[i].width = w[i]; ci[i].height = h[i];
+        if (area(h[i], w[i]) > 0) NEED(b, 4 * area(h[i], w[i]));  /* (an empty channel may come without a buffer) */
+        ci[i].data = (int32_t*)ADDR(b);
+    }
+    for (jsize i = 0; i < n_sp; i++) {
+        sp[i].horizontal = spv[4 * i]; sp[i].in_place = spv[4 * i + 1]; sp[i].begin_c = spv[4 * i + 2]; sp[i].num_c = spv[4 * i + 3];
+    }
+    jsize at = 0;
+    for (jsize i = 0; i < n_tr; i++) {
+        const jint* v = trv + 8 * i;
+        tr[i].kind = v[0]; tr[i].begin_c = v[1]; tr[i].num_c = v[2]; tr[i].rct_type = v[3];
+        tr[i].nb_colors = v[4]; tr[i].nb_deltas = v[5]; tr[i].d_pred = v[6]; tr[i].n_sp = v[7];
+        if (v[7] < 0 || v[7] > n_sp - at) {  /* the steps a transform counts are not in squeezeSteps */
+            rethrow(e, c, JXL_ERR_INVALID_ARGUMENT);
+            return;
+        }
+        tr[i].sp = sp + at;
+        at += v[7];
+    }
+    CHECK(jxl_modular_begin_chain(c, ci, n, tr, n_tr, bitDepth));
+}
+
 JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_modularRun(JNIEnv* e, jobject self) {
     jxl_ctx* c = ctx_of(e, self);
     CHECK(jxl_modular_run(c));

@@ -62,6 +62,11 @@ def parser():
                     help="with --device-canvas and --device-patches: a frame with patches no longer lands the canvas; computePatches "
                          "runs on device plane sets (JXLDecoder device_patch_sets; jxl_canvas_patches, jxl_canvas_cast_planes): the "
                          "frame's planes go up once and no reference plane crosses the bus. The same bytes")
+    ap.add_argument("--device-chains", action="store_true",
+                    help="with --device-image or --device-frames: the frame-level transform chain of a Modular frame is one device "
+                         "plan whatever it holds (JXLDecoder device_chains; jxl_modular_begin_chain) -- nested Palettes run as one "
+                         "launch on the uploaded channels -- and with --device-frames a frame with patches stays a plane set "
+                         "through the patch stage. The same bytes")
     return ap
 
 
@@ -89,7 +94,7 @@ def main(argv=None):
     dec = JXLDecoder(a.input, backend=backend, sparse_coeffs=a.sparse_coeffs, device_splines=a.device_splines,
                      device_patches=a.device_patches, device_output=a.device_png, device_canvas=a.device_canvas,
                      draw_varblocks=a.draw_varblocks, device_palette=a.device_palette, device_image=a.device_image,
-                     device_frames=a.device_frames, device_patch_sets=a.device_patch_sets)
+                     device_frames=a.device_frames, device_patch_sets=a.device_patch_sets, device_chains=a.device_chains)
     image = dec.decode()
     if image is None:
         print("jxlatte_amd: no frames", file=sys.stderr)

@@ -168,6 +168,7 @@ SIGNATURES = {
     "jxl_modular_default_squeeze_params": (i32, [pi, pi, i32, i32, C.POINTER(abi.SqueezeParam), i32]),
     "jxl_modular_squeezed_shapes": (i32, [pi, pi, i32, C.POINTER(abi.SqueezeParam), i32, pi, pi, i32]),
     "jxl_modular_begin": (i32, [vp, C.POINTER(abi.Channel), i32, C.POINTER(abi.SqueezeParam), i32, i32, i32]),
+    "jxl_modular_begin_chain": (i32, [vp, C.POINTER(abi.Channel), i32, C.POINTER(abi.ModularTransform), i32, i32]),
     "jxl_modular_run": (i32, [vp]),
     "jxl_modular_out_count": (i32, [vp]),
     "jxl_modular_out_shape": (i32, [vp, i32, pi, pi]),

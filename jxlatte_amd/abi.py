@@ -375,3 +375,26 @@ def make_squeeze_params(sp):
     for i, (h, ip, b, n) in enumerate(sp):
         arr[i].horizontal, arr[i].in_place, arr[i].begin_c, arr[i].num_c = int(h), int(ip), int(b), int(n)
     return arr
+
+
+class ModularTransform(C.Structure):
+    """struct jxl_modular_transform"""
+    _fields_ = [("kind", C.c_int32), ("begin_c", C.c_int32), ("num_c", C.c_int32), ("rct_type", C.c_int32), ("nb_colors", C.c_int32),
+                ("nb_deltas", C.c_int32), ("d_pred", C.c_int32), ("sp", C.POINTER(SqueezeParam)), ("n_sp", C.c_int32)]
+
+
+def make_transforms(transforms):
+    """the dictionaries frontend.transforms() returns (bitstream order; a Squeeze carries `steps`, the expanded step list) ->
+    (ModularTransform array, keepalive)"""
+    arr = (ModularTransform * max(1, len(transforms)))()
+    keep = []
+    for i, t in enumerate(transforms):
+        for k in ("kind", "begin_c", "num_c", "rct_type", "nb_colors", "nb_deltas", "d_pred"):
+            setattr(arr[i], k, int(t.get(k, 0)))
+        steps = list(t.get("steps", ()))
+        if steps:
+            sp = make_squeeze_params(steps)
+            keep.append(sp)
+            arr[i].sp = C.cast(sp, C.POINTER(SqueezeParam))
+        arr[i].n_sp = len(steps)
+    return arr, keep

@@ -6,6 +6,7 @@
 #include "pfm_check.h"     // what the PFM entries refuse
 #include "varblock_check.h"  // what the varblock entries refuse, their cell map and factor table
 #include "palette_check.h"   // what jxl_stage_palette refuses
+#include "modchain_check.h"  // the walk, the refusals and the Palette runs of jxl_modular_begin_chain
 #include "palette_ops.h"     // palette_pred_is_local: which predictors need the chain kernel
 
 #include <algorithm>
@@ -62,7 +63,8 @@ struct DevBuf {
 
 struct ModOp {
     int kind;  // 0 hsqueeze, 1 vsqueeze, 2 rct, 3 copy, 4 batched squeeze step (bt), 5 chain of small steps (chain_*),
-               // 6 a V step and the H step behind it in one launch (vh; r5, only in jxl_ctx::mod_ops_fused)
+               // 6 a V step and the H step behind it in one launch (vh; r5, only in jxl_ctx::mod_ops_fused),
+               // 7 a run of inverse Palette transforms (jxl_ctx::mod_pal_runs[pal_run]; jxl_modular_begin_chain)
     VHBatch vh;
     const SqueezeBatch* chain_dev = nullptr;
     int chain_steps = 0, chain_slots = 0;
@@ -74,6 +76,23 @@ struct ModOp {
     int adim, rdim, other;  // hsq: aw, rw, h; vsq: ah, rh, w
     int64_t n;
     int type;
+    int pal_run = 0;
+};
+
+// A run of consecutive inverse Palette transforms of a chain plan (modchain_check.h): as one k_palette_run launch where it is
+// fusable, and as its stages in order. counter: the word of jxl_ctx::mod_pal_count the launch adds to.
+struct PalStep {
+    PaletteArgs a;
+    int counter;
+    bool chained;  // a delta pixel needs k_palette_chain (d_pred neither 0 nor 6)
+};
+struct PalRun {
+    bool fusable = false;
+    PaletteRunArgs fused;
+    int counter = 0;
+    std::vector<PalStep> steps;
+    bool redone = false;  // its counters reported once: from then on the step form, k_palette_chain included
+    int form = 0;         // of the last run of the plan: 1 fused, 2 steps on trust (the counters decide at settle time), 3 exact
 };
 
 struct ModChan {
@@ -287,6 +306,14 @@ struct jxl_ctx {
     bool mod_pending = false;
     int mod_redos = 0;
     int mod_launches = 0;
+    // the Palette runs of a chain plan (jxl_modular_begin_chain): their counters (device, and a page-locked host copy that
+    // run_modular_plan fills and mod_settle reads), and {fused launches, step launches, redone runs} of the last jxl_modular_run
+    // with its settle (jxl_debug_last_palette_run)
+    std::vector<PalRun> mod_pal_runs;
+    DevBuf mod_pal_count;
+    unsigned int* mod_pal_count_host = nullptr;
+    int mod_pal_counters = 0, mod_pal_count_cap = 0;
+    int32_t mod_pal_stats[3] = {0, 0, 0};
 };
 
 namespace {
@@ -498,6 +525,8 @@ bool shared_planes_on() {
 // Cell-tiled pooled planes (plane_tiled.h): process-wide, read per run. The library reads no environment variable for
 // it: the Python package maps JXL_PLANE_A_TILED=0 onto jxl_debug_set_plane_a_tiled (jxlatte_amd/_lib.py), tests flip it in place.
 std::atomic<int> g_plane_a_tiled{1};
+// The fused Palette run of a chain plan (k_palette_run.hip): process-wide, read per run; 0 forces the step form (A/B runs, tests)
+std::atomic<int> g_palette_fuse{1};
 // jxl_debug_last_restore_launches: above the seven bits of restore_fused_variant()
 constexpr int32_t kRestoreTiledBit = 128, kRestoreBatchBit = 256;
 int32_t restore_launch_code(const RestoreParams& rp, bool tiled, bool batch) {
@@ -1300,6 +1329,15 @@ extern "C" int64_t jxl_debug_intermediate_bytes(int device) {
 extern "C" int jxl_debug_set_plane_a_tiled(int on) { return g_plane_a_tiled.exchange(on ? 1 : 0, std::memory_order_relaxed); }
 // ... and whether the context's last frame run took that layout (tests/test_tiled_plane_a_gpu.py)
 extern "C" int jxl_debug_last_plane_a_tiled(const jxl_ctx* c) { return c ? c->last_plane_a_tiled : 0; }
+// Test hooks (tests/test_modchain_gpu.py) and the decoder's statistics, outside the C-ABI: the form of a chain plan's Palette
+// runs (returns the previous setting), and {fused launches, step launches, redone runs} of the context's last jxl_modular_run
+// with whatever its settle ran again
+extern "C" int jxl_debug_set_palette_fuse(int on) { return g_palette_fuse.exchange(on ? 1 : 0, std::memory_order_relaxed); }
+extern "C" int jxl_debug_last_palette_run(const jxl_ctx* c, int32_t out[3]) {
+    if (!c || !out) return -1;
+    for (int i = 0; i < 3; i++) out[i] = c->mod_pal_stats[i];
+    return 0;
+}
 // Test hook (tests/test_restore_variants_gpu.py): the fused restoration launches of the context's last frame run -- how many (0: the
 // stage kernels ran instead, 1, or 2 for the split three-iteration form) and, per launch, which instantiation:
 // restore_fused_variant() of its arguments (Gaborish 64 | EPF iterations << 3 | sink kind), | 128 for cell-tiled input planes,
@@ -1536,6 +1574,9 @@ void jxl_ctx_destroy(jxl_ctx* c) {
     c->mod_flag.release();
     if (c->mod_flag_host) (void)hipHostFree(c->mod_flag_host);
     c->mod_flag_host = nullptr;
+    c->mod_pal_count.release();
+    if (c->mod_pal_count_host) (void)hipHostFree(c->mod_pal_count_host);
+    c->mod_pal_count_host = nullptr;
     if (c->mod_ev) (void)hipEventDestroy(c->mod_ev);
     if (c->mod_join) (void)hipEventDestroy(c->mod_join);
     c->mod_ev = c->mod_join = nullptr;
@@ -3863,6 +3904,7 @@ jxl_status jxl_stage_palette(jxl_ctx* c, const jxl_palette_desc* d, const int32_
         HIP_TRY(c, hipMemcpy2D(dpal, sizeof(int32_t) * d->nb_colors, d->palette, sizeof(int32_t) * d->pal_w, sizeof(int32_t) * d->nb_colors,
                                d->num_c, hipMemcpyHostToDevice));
     a.palette = dpal;
+    a.pal_pitch = d->nb_colors;
     a.out = dout;
     HIP_TRY(c, hipMemsetAsync(a.delta_count, 0, sizeof(unsigned int), c->stream));
     launch_palette_lookup(a, c->stream);
@@ -4494,11 +4536,8 @@ int32_t jxl_modular_squeezed_shapes(const int32_t* widths, const int32_t* height
     return (int32_t)ch.size();
 }
 
-jxl_status jxl_modular_begin(jxl_ctx* c, const jxl_channel* chans, int32_t n_chans, const jxl_squeeze_param* sp, int32_t n_sp,
-                             int32_t rct_type, int32_t rct_begin) {
-    jxl_status st = bind(c);
-    if (st) return st;
-    if (n_chans < 0 || (n_chans > 0 && !chans) || (n_sp > 0 && !sp) || rct_type >= 42) return fail(c, JXL_ERR_INVALID_ARGUMENT, "modular: bad arguments");
+// a new plan: the one before it goes
+static jxl_status mod_reset(jxl_ctx* c) {
     if (c->mod_flag_host) {  // reports of an earlier plan's speculative runs are void
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         if (c->n_aux > 0) HIP_TRY(c, hipStreamSynchronize(c->aux[0]));
@@ -4512,6 +4551,17 @@ jxl_status jxl_modular_begin(jxl_ctx* c, const jxl_channel* chans, int32_t n_cha
     c->mod_ops_fused.clear();
     c->mod_out.clear();
     c->mod_ran = false;
+    c->mod_pal_runs.clear();
+    c->mod_pal_counters = 0;
+    return JXL_OK;
+}
+
+jxl_status jxl_modular_begin(jxl_ctx* c, const jxl_channel* chans, int32_t n_chans, const jxl_squeeze_param* sp, int32_t n_sp,
+                             int32_t rct_type, int32_t rct_begin) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (n_chans < 0 || (n_chans > 0 && !chans) || (n_sp > 0 && !sp) || rct_type >= 42) return fail(c, JXL_ERR_INVALID_ARGUMENT, "modular: bad arguments");
+    if ((st = mod_reset(c))) return st;
     // Every plane starts kVhPad samples into its allocation (kVhPadH for a plane that is the residual of a horizontal step): the
     // fused squeeze kernel (k_modular_vh.hip) tiles the H pairs in chunks that start at pairs 1, 1 + CW, 1 + 2 CW, ..., and with
     // these leads the pieces it loads (V inputs from column c0 + 1, H residuals from pair c0) and the pieces it stores (outputs
@@ -4713,6 +4763,133 @@ jxl_status jxl_modular_begin(jxl_ctx* c, const jxl_channel* chans, int32_t n_cha
     return JXL_OK;
 }
 
+// Any transform chain (modchain_check.h has the walk, the refusals and the Palette runs' path tables). A chain jxl_modular_begin
+// expresses is its plan, with everything that plan fuses; any other chain is built op by op: a Squeeze step as one exact serial
+// walk per channel (what jxl_stage_inv_hsqueeze / _vsqueeze launch), an RCT in place behind copies of the inputs it touches,
+// a Palette run as PalRun. Every buffer starts 128 bytes into its allocation, the planes of one Palette stage a multiple of 4
+// samples apart: the Palette kernels' 16-byte loads and stores are aligned.
+jxl_status jxl_modular_begin_chain(jxl_ctx* c, const jxl_channel* chans, int32_t n_chans, const jxl_modular_transform* tr, int32_t n_tr,
+                                   int32_t bit_depth) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    ChainPlan plan;
+    try {
+        const char* bad = chain_plan(chans, n_chans, tr, n_tr, bit_depth, &plan);
+        if (bad) return fail(c, (jxl_status)plan.status, "%s", bad);
+    } catch (const std::bad_alloc&) {
+        return fail(c, JXL_ERR_OOM, "host allocation failed");
+    }
+    if (chain_is_plain(tr, n_tr)) {
+        const jxl_modular_transform* rct = n_tr > 0 && tr[0].kind == JXL_TRANSFORM_RCT ? &tr[0] : nullptr;
+        const jxl_modular_transform* sq = n_tr > 0 && tr[n_tr - 1].kind == JXL_TRANSFORM_SQUEEZE ? &tr[n_tr - 1] : nullptr;
+        return jxl_modular_begin(c, chans, n_chans, sq ? sq->sp : nullptr, sq ? sq->n_sp : 0, rct ? rct->rct_type : -1, rct ? rct->begin_c : 0);
+    }
+    if ((st = mod_reset(c))) return st;
+    constexpr int kPad = 32;
+    auto oom = [&](const char* what) {  // nothing stays queued
+        (void)mod_reset(c);
+        return fail(c, JXL_ERR_OOM, "device allocation failed (%s)", what);
+    };
+    std::vector<int32_t*> dev(plan.bufs.size(), nullptr);
+    auto alloc = [&](size_t n_elems) -> int32_t* {
+        c->mod_bufs.emplace_back();
+        if (!c->mod_bufs.back().ensure(4 * (std::max<size_t>(1, n_elems) + 64))) return nullptr;
+        return c->mod_bufs.back().as<int32_t>() + kPad;
+    };
+    for (const ChainPalStage& s : plan.stages) {  // the outputs of a stage: planes of one allocation
+        const size_t stride = ((size_t)s.w * s.h + 3) & ~(size_t)3;
+        int32_t* d = alloc(stride * s.num_c);
+        if (!d) return oom("palette planes");
+        for (int i = 0; i < s.num_c; i++) dev[(size_t)(s.out0 + i)] = d + (size_t)i * stride;
+    }
+    for (size_t i = 0; i < plan.bufs.size(); i++) {
+        const size_t n = (size_t)plan.bufs[i].w * plan.bufs[i].h;
+        if (!dev[i] && !(dev[i] = alloc(n))) return oom("modular channel");
+        if ((int)i < n_chans && n) HIP_TRY(c, hipMemcpy(dev[i], chans[i].data, 4 * n, hipMemcpyHostToDevice));
+    }
+    int counters = 0;
+    for (const ChainOp& co : plan.ops) {
+        ModOp op{};
+        if (co.kind == kChainSqueeze) {
+            const ChainBuf a = plan.bufs[(size_t)co.avg], r = plan.bufs[(size_t)co.res];
+            op.kind = co.horizontal ? 0 : 1;
+            op.a = dev[(size_t)co.avg]; op.b = dev[(size_t)co.res]; op.o = dev[(size_t)co.out];
+            op.adim = co.horizontal ? a.w : a.h; op.rdim = co.horizontal ? r.w : r.h; op.other = co.horizontal ? a.h : a.w;
+            c->mod_ops.push_back(op);
+        } else if (co.kind == kChainRct) {
+            const int64_t n = (int64_t)plan.bufs[(size_t)co.src[0]].w * plan.bufs[(size_t)co.src[0]].h;
+            for (int j = 0; j < 3; j++)
+                if (co.dst[j] != co.src[j]) {  // keep the uploaded input intact so that run() is repeatable
+                    ModOp cp{};
+                    cp.kind = 3; cp.a = dev[(size_t)co.src[j]]; cp.o = dev[(size_t)co.dst[j]]; cp.n = n;
+                    c->mod_ops.push_back(cp);
+                }
+            op.kind = 2; op.v0 = dev[(size_t)co.dst[0]]; op.v1 = dev[(size_t)co.dst[1]]; op.v2 = dev[(size_t)co.dst[2]]; op.n = n; op.type = co.type;
+            c->mod_ops.push_back(op);
+        } else {
+            PalRun run;
+            run.fusable = co.fusable;
+            run.counter = counters++;
+            PaletteRunArgs& f = run.fused;
+            memset(&f, 0, sizeof f);
+            f.src = dev[(size_t)co.source];
+            f.n = (int64_t)plan.bufs[(size_t)co.source].w * plan.bufs[(size_t)co.source].h;
+            f.bit_depth = bit_depth;
+            for (int k = 0; k < co.n_stage; k++) {
+                const ChainPalStage& s = plan.stages[(size_t)(co.stage0 + k)];
+                PalStep ps{};
+                ps.a.index = dev[(size_t)s.index];
+                ps.a.palette = dev[(size_t)s.pal];
+                ps.a.pal_pitch = s.pal_w;
+                ps.a.pred = nullptr;
+                ps.a.out = dev[(size_t)s.out0];
+                ps.a.plane_stride = (int64_t)(((size_t)s.w * s.h + 3) & ~(size_t)3);
+                ps.a.h = s.h; ps.a.w = s.w;
+                ps.a.num_c = s.num_c; ps.a.nb_colors = s.nb_colors; ps.a.nb_deltas = s.nb_deltas; ps.a.d_pred = s.d_pred; ps.a.bit_depth = bit_depth;
+                ps.counter = counters++;
+                ps.chained = !palette_pred_is_local(s.d_pred);
+                run.steps.push_back(ps);
+                if (co.fusable) {
+                    f.st[k] = PaletteRunStage{dev[(size_t)s.pal], s.pal_w, s.num_c, s.nb_colors, s.nb_deltas, ps.chained ? 1 : 0, f.lds_ints};
+                    f.lds_ints += s.num_c * s.nb_colors;
+                }
+            }
+            if (co.fusable) {
+                f.n_stage = co.n_stage;
+                f.n_out = co.n_out;
+                for (int k = 0; k < co.n_out; k++) {
+                    const ChainPalOut& o = plan.outs[(size_t)(co.out0 + k)];
+                    f.out[k].plane = dev[(size_t)o.buf];
+                    f.out[k].depth = o.depth;
+                    for (int d = 0; d < o.depth; d++) {
+                        f.out[k].stage[d] = o.stage[d];
+                        f.out[k].row[d] = o.row[d];
+                    }
+                }
+            }
+            op.kind = 7;
+            op.pal_run = (int)c->mod_pal_runs.size();
+            c->mod_pal_runs.push_back(std::move(run));
+            c->mod_ops.push_back(op);
+        }
+    }
+    if (counters > c->mod_pal_count_cap) {
+        if (c->mod_pal_count_host) (void)hipHostFree(c->mod_pal_count_host);
+        c->mod_pal_count_host = nullptr;
+        c->mod_pal_count_cap = 0;
+        if (!c->mod_pal_count.ensure(sizeof(unsigned int) * (size_t)counters)) return oom("palette counters");
+        HIP_TRY(c, hipHostMalloc((void**)&c->mod_pal_count_host, sizeof(unsigned int) * (size_t)counters, hipHostMallocDefault));
+        c->mod_pal_count_cap = counters;
+    }
+    c->mod_pal_counters = counters;
+    for (PalRun& r : c->mod_pal_runs) {
+        r.fused.impure = c->mod_pal_count.as<unsigned int>() + r.counter;
+        for (PalStep& ps : r.steps) ps.a.delta_count = c->mod_pal_count.as<unsigned int>() + ps.counter;
+    }
+    for (int32_t b : plan.list) c->mod_out.push_back(ModChan{plan.bufs[(size_t)b].w, plan.bufs[(size_t)b].h, dev[(size_t)b], false});
+    return JXL_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -4728,6 +4905,7 @@ jxl_status run_modular_plan(jxl_ctx* c, int mode) {
     int launches = 0;
     const bool speculative = mode == 1;
     hipStream_t s = c->stream, vs = speculative ? c->aux[0] : nullptr;
+    if (c->mod_pal_counters > 0) (void)hipMemsetAsync(c->mod_pal_count.p, 0, sizeof(unsigned int) * (size_t)c->mod_pal_counters, s);
     bool checks_out = false;
     auto join = [&]() {
         if (!checks_out) return;
@@ -4787,6 +4965,39 @@ jxl_status run_modular_plan(jxl_ctx* c, int mode) {
             checks_of(bt, pending);
             break;
         }
+        case 7: {  // a run of inverse Palette transforms (jxl_modular_begin_chain)
+            PalRun& r = c->mod_pal_runs[(size_t)op.pal_run];
+            if (mode != 0 && r.fusable && !r.redone && g_palette_fuse.load(std::memory_order_relaxed)) {
+                launch_palette_run(r.fused, s);
+                r.form = 1;
+                c->mod_pal_stats[0]++;
+                break;
+            }
+            // The stages in order. Whether a stage has delta pixels for k_palette_chain is known only once its counter is
+            // read: the in-order run (mode 0) waits for it stage by stage; the others launch the lookups alone and let
+            // mod_settle look at the counters -- unless they have reported once before: then every chained stage gets its
+            // k_palette_chain (it adds nothing where there is no delta pixel).
+            r.form = mode == 0 || r.redone ? 3 : 2;
+            for (const PalStep& ps : r.steps) {
+                launch_palette_lookup(ps.a, s);
+                launches++;
+                c->mod_pal_stats[1]++;
+                if (!ps.chained) continue;
+                unsigned int deltas = 1;
+                if (mode == 0) {
+                    if (hipMemcpyAsync(&deltas, ps.a.delta_count, sizeof deltas, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                        hipStreamSynchronize(s) != hipSuccess)
+                        return fail(c, JXL_ERR_DEVICE, "palette: reading the delta pixel count failed");
+                }
+                if (r.form == 3 && deltas) {
+                    launch_palette_chain(ps.a, s);
+                    launches++;
+                    c->mod_pal_stats[1]++;
+                }
+            }
+            launches--;  // (the op itself is counted below)
+            break;
+        }
         }
         launches++;
     }
@@ -4794,6 +5005,8 @@ jxl_status run_modular_plan(jxl_ctx* c, int mode) {
     if (mode != 0) {
         join();
         (void)hipMemcpyAsync(c->mod_flag_host, c->mod_flag.p, sizeof(int32_t), hipMemcpyDeviceToHost, s);
+        if (c->mod_pal_counters > 0)
+            (void)hipMemcpyAsync(c->mod_pal_count_host, c->mod_pal_count.p, sizeof(unsigned int) * (size_t)c->mod_pal_counters, hipMemcpyDeviceToHost, s);
         c->mod_pending = true;
     }
     c->mod_launches = launches;
@@ -4808,7 +5021,19 @@ jxl_status mod_settle(jxl_ctx* c) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (!c->mod_pending) return JXL_OK;
     c->mod_pending = false;
-    if (*c->mod_flag_host == 0) return JXL_OK;
+    // the Palette runs that ran on trust: a fused run that met a delta pixel of a chained stage, or a stage whose lookup
+    // counted delta pixels k_palette_chain has not seen, is run again in order, and so is everything behind it
+    bool pal_redo = false;
+    for (PalRun& r : c->mod_pal_runs) {
+        bool reported = r.form == 1 && c->mod_pal_count_host[r.counter] != 0;
+        if (r.form == 2)
+            for (const PalStep& ps : r.steps) reported = reported || (ps.chained && c->mod_pal_count_host[ps.counter] != 0);
+        if (reported) {
+            r.redone = pal_redo = true;
+            c->mod_pal_stats[2]++;
+        }
+    }
+    if (*c->mod_flag_host == 0 && !pal_redo) return JXL_OK;
     *c->mod_flag_host = 0;
     HIP_TRY(c, hipMemset(c->mod_flag.p, 0, sizeof(int32_t)));
     c->mod_redos++;
@@ -4843,6 +5068,7 @@ jxl_status jxl_modular_run(jxl_ctx* c) {
         HIP_TRY(c, hipEventCreateWithFlags(&c->mod_ev, hipEventDisableTiming));
         HIP_TRY(c, hipEventCreateWithFlags(&c->mod_join, hipEventDisableTiming));
     }
+    c->mod_pal_stats[0] = c->mod_pal_stats[1] = c->mod_pal_stats[2] = 0;
     return run_modular_plan(c, mode);
 }
 

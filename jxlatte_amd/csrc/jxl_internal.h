@@ -11,6 +11,7 @@
 #include "plane_tiled.h"
 #include "blend_ops.h"
 #include "patch_compile.h"
+#include "modchain_check.h"
 
 namespace jxl {
 
@@ -267,9 +268,13 @@ void launch_varblocks(const VarblockArgs& p, hipStream_t s);
 // the checks palette_check.h's
 constexpr int kPaletteLdsInts = 8192;      // a palette of at most this many entries (num_c * nb_colors) is staged in LDS: 32 KiB
 constexpr int kPaletteChainThreads = 256;  // k_palette_chain's workgroup: that many rows of one t-front per pass
+// (the fused run's budget, kPaletteRunLdsInts = 12288 entries for all palettes of a run together, and its stage / depth / output
+// limits stand in modchain_check.h: the plain header that decides which runs are fused needs them without this one)
+constexpr int kPaletteRunMaxGrid = 2048;   // k_palette_run's grid bound: 8 workgroups per CU, each stages the run's palettes once
 struct PaletteArgs {
     const int32_t* index;     // h * w
-    const int32_t* palette;   // num_c rows of nb_colors, back to back
+    const int32_t* palette;   // num_c rows of nb_colors, pal_pitch apart
+    int32_t pal_pitch;        // >= nb_colors (jxl_stage_palette: back to back; a plan: the palette channel's own width)
     const int32_t* pred;      // h * w, or null
     int32_t* out;             // num_c planes, plane_stride apart
     int64_t plane_stride;     // >= h * w, a multiple of 4
@@ -279,6 +284,27 @@ struct PaletteArgs {
 };
 void launch_palette_lookup(const PaletteArgs& p, hipStream_t s);
 void launch_palette_chain(const PaletteArgs& p, hipStream_t s);  // only where d_pred is neither 0 nor 6 and the count is not 0
+// A run of consecutive inverse Palette transforms as one launch (k_palette_run.hip); the table is modchain_check.h's
+struct PaletteRunStage {
+    const int32_t* palette;  // the device copy of the palette channel: num_c rows, pal_w apart
+    int32_t pal_w, num_c, nb_colors, nb_deltas;
+    int32_t chained;         // 1: a delta pixel of this stage needs its neighbours (d_pred neither 0 nor 6)
+    int32_t lds_off;         // where the stage's num_c * nb_colors entries start in LDS
+};
+struct PaletteRunOut {
+    int32_t* plane;                                        // n samples, 16-byte aligned
+    int32_t depth;                                         // 1 .. kPalRunMaxDepth
+    int32_t stage[kPalRunMaxDepth], row[kPalRunMaxDepth];  // the lookups from the source to this plane, in order
+};
+struct PaletteRunArgs {
+    const int32_t* src;    // n samples, 16-byte aligned
+    int64_t n;
+    int32_t n_stage, n_out, bit_depth, lds_ints;
+    unsigned int* impure;  // += the workgroups that met a delta pixel of a chained stage (zeroed by the caller)
+    PaletteRunStage st[kPalRunMaxStages];
+    PaletteRunOut out[kPalRunMaxOut];
+};
+void launch_palette_run(const PaletteRunArgs& p, hipStream_t s);
 // PQ as a table of quadratic segments (jxl_fastpow.h): kPqTableFloats floats = float4 {a0 hi, a0 lo, a1, a2} per segment
 constexpr int kPqTableFloats = (129 - 87) * 128 * 4;
 void build_pq_table(float* out /* [kPqTableFloats] */);

@@ -6,7 +6,8 @@
 //   span two rows). A lane reads its 4 indices once (one 16-byte load; the planes start 16-byte aligned and a group starts at a
 //   multiple of 4) and writes all num_c outputs, one 16-byte store per plane; the last group of a plane whose size is no
 //   multiple of 4 goes sample by sample. The num_c x nb_colors palette is staged in LDS when it has at most kPaletteLdsInts
-//   entries, else it is read from global memory (the instantiation is picked by the launcher).
+//   entries, else it is read from global memory (the instantiation is picked by the launcher). Its rows lie pal_pitch apart:
+//   back to back from jxl_stage_palette, the palette channel's own width in a plan of jxl_modular_begin_chain.
 //     A pixel with index < nb_deltas (a "delta pixel") is value + prediction (:368-369). For d_pred 0 the prediction is 0 and for
 //   d_pred 6 it is (pred + 3) >> 3 of the weighted predictor's plane (0 without one): neither reads a neighbour, so both finish
 //   here. For every other predictor the kernel writes the value alone. It counts the delta pixels either way: a wave sums its
@@ -38,13 +39,18 @@ __global__ __launch_bounds__(256) void k_palette_lookup(const PaletteArgs p) {
     __shared__ unsigned int s_count;
     if (threadIdx.x == 0) s_count = 0;
     if (kLds) {
-        const int entries = p.num_c * p.nb_colors;  // <= kPaletteLdsInts
-        for (int j = threadIdx.x; j < entries; j += 256) s_pal[j] = p.palette[j];
+        if (p.pal_pitch == p.nb_colors) {
+            const int entries = p.num_c * p.nb_colors;  // <= kPaletteLdsInts
+            for (int j = threadIdx.x; j < entries; j += 256) s_pal[j] = p.palette[j];
+        } else {  // a plan's palette channel is wider than nb_colors: row by row
+            for (int c = 0; c < p.num_c; c++)
+                for (int j = threadIdx.x; j < p.nb_colors; j += 256) s_pal[c * p.nb_colors + j] = p.palette[(int64_t)c * p.pal_pitch + j];
+        }
     }
     __syncthreads();
     PaletteLookup lk;
     lk.palette = kLds ? s_pal : p.palette;
-    lk.pal_w = p.nb_colors;  // the rows were uploaded back to back
+    lk.pal_w = kLds ? p.nb_colors : p.pal_pitch;  // the rows stand back to back in LDS
     lk.nb_colors = p.nb_colors;
     lk.bit_depth = p.bit_depth;
     const int64_t n = (int64_t)p.h * p.w;

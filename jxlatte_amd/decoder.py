@@ -1173,6 +1173,8 @@ class FramePlanes:
         plane goes up once; from resident colours only the extra channels do, and the colours stay where they are until
         settle() copies them into the set (`away`). Returns the set"""
         canvas, ctx = self.be.host.DeviceCanvas, self.be.ctx
+        if self.set is not None:  # a ready-made set (device_frames with device_chains): it is the one; nothing goes up
+            return self.set
         if self.rp is None:
             self.set = canvas.fromArrays(ctx, self.host)
         else:
@@ -1181,6 +1183,12 @@ class FramePlanes:
                 self.set.upload(3 + i, b)
             self.away = True
         return self.set
+
+    def leave_for_host(self):
+        """a ready-made set comes down for good: every plane a host array, as a frame that never was a set has them"""
+        self.host = [self.set.download(c) for c in range(len(self.set))]
+        self.set.release()
+        self.set = None
 
     def visit_planes(self):
         """the colours of an adopted set into the resident planes for the stages that follow the patches; integer colours are
@@ -1272,13 +1280,13 @@ def _tt_dims():
 class JXLDecoder:
     # the switches' defaults (a decoder made with JXLDecoder.__new__ -- tests, tools, load_vardct_frame -- has them too)
     sparse_coeffs = device_splines = device_patches = device_output = device_canvas = False
-    draw_varblocks = device_palette = device_image = device_frames = device_patch_sets = False
+    draw_varblocks = device_palette = device_image = device_frames = device_patch_sets = device_chains = False
     trace = None  # test hook: see _trace
     _patch_sets = False  # device_patch_sets acts on the frame in hand (_canvas_route)
 
     def __init__(self, source, backend=None, sparse_coeffs=False, device_splines=False, device_patches=False, device_output=False,
                  device_canvas=False, draw_varblocks=False, device_palette=False, device_image=False, device_frames=False,
-                 device_patch_sets=False):
+                 device_patch_sets=False, device_chains=False):
         """sparse_coeffs: hand the HF coefficients to the backend as lists of non-zero entries (jxf_get_coeffs_sparse ->
         jxl_vardct_put_group_sparse), not as dense planes; same pixels.
         device_splines: Frame.renderSplines runs in the backend (jxl_planes_splines on the resident planes, jxl_stage_splines
@@ -1347,7 +1355,18 @@ class JXLDecoder:
         transform) keeps them in the list and goes up as a temporary set. The stages after the patches run on the resident
         planes and the blend reads the frame's set: nothing goes up again. The same bits. stats[k]["patches"]["path"] is
         "plane sets" and stats[k]["canvas"] stays "device"; what still lands says why there: a below mode that reads the
-        frame off its own pixel, frame planes of different sizes, a slot with another plane count, more than 16 planes."""
+        frame off its own pixel, frame planes of different sizes, a slot with another plane count, more than 16 planes.
+        device_chains: acts only together with device_image or device_frames. The plan those two make of a frame's frame-level
+        chain is built from the whole transform list (jxl_modular_begin_chain): any chain of RCT, Palette and Squeeze
+        transforms is one plan -- a Palette reads its palette from the device copy of channel 0, a run of consecutive Palettes
+        is one launch -- except a Palette with nb_deltas > 0 and d_pred 6 ("a Palette with weighted-predictor deltas": that
+        plane exists only inside the front-end's decode). With device_frames a frame with patches is accepted too where
+        patch_sets_rule holds for it: the set made from the Modular context goes through the patch stage as it is (nothing
+        goes up again) and the blend reads it; what _patches_sets refuses lands the canvas with its reason, as without the
+        switch. The same bits. stats[k]["chain"], only with the switch: dict(kinds, runs) for a frame whose chain ran as a
+        plan -- runs: dict(fused, steps, redone), the launches of its Palette runs as one launch each, as single steps, and
+        the runs that ran again because a pixel needed its neighbours."""
+        self.device_chains = bool(device_chains)
         self.device_patch_sets = bool(device_patch_sets)
         self.device_frames = bool(device_frames)
         self.device_image = bool(device_image)
@@ -1478,14 +1497,14 @@ class JXLDecoder:
         from . import host
         return host.getUpWeights(k, packed)
 
-    def _chained_tail(self, fr, planes, save, xyb_done, keep=False, upsampled=False):
+    def _chained_tail(self, fr, planes, save, xyb_done, keep=False, upsampled=False, adopted=False):
         """Frame.upsample .. performColorTransforms (JXLCodestreamDecoder.java:628-637), the one statement of that order, for
         every backend: upsample, the saveBeforeCT reference, patches, splines, noise, inverse XYB, YCbCr. `planes`
         (FramePlanes) runs each sample stage where the samples can be and moves the colours between host and device only
         where the next stage lives on the other side; the saveBeforeCT reference and the patches' blend calls are host stages
         (as in the reference).
         keep: colours that are on the device at the end stay there. upsampled: the planes are already past Frame.upsample
-        (_modular_frame_set)."""
+        (_modular_frame_set). adopted: the planes are a ready-made set that the patch stage takes as it is (device_chains)."""
         info = self.info
         if not upsampled:
             planes.upsample(fr, self._up_weights)
@@ -1503,10 +1522,12 @@ class JXLDecoder:
                     self._land(why)
                     self.stats[-1]["canvas"] = "landed: " + why
                     on_sets = False
+                    if adopted:
+                        planes.leave_for_host()
             if not on_sets and not (dev_patches and planes.colors == 3 and info.colour_space != CE_GRAY and self._patches_device(fr, planes)):
                 self._patches(fr, planes.to_host(), planes.colors)
                 self.stats[-1].setdefault("patches", dict(path="blend calls"))
-        adopted = planes.set is not None and not upsampled  # (device_patch_sets: the patch stage made the frame's set)
+        adopted = planes.set is not None and (adopted or not upsampled)  # (device_patch_sets: the frame's set is the patch stage's)
         if adopted and (fr.has_splines or fr.has_noise or (info.xyb_encoded and not xyb_done) or fr.do_ycbcr):
             planes.visit_planes()
         if fr.has_splines:
@@ -2060,12 +2081,17 @@ class JXLDecoder:
 
     # -- the image as a device plane set (device_image) -----------------------------------------------------------
     @staticmethod
-    def _one_plan_chain_rule(fr, kinds):
+    def _one_plan_chain_rule(fr, kinds, chain=None):
         """what device_image's "modular frame" route and device_frames ask of the frame-level stream: a Modular frame whose
-        chain is one plan of the Modular context. None, or the condition that fails"""
+        chain is one plan of the Modular context. None, or the condition that fails. chain: with device_chains the transform
+        list itself (frontend.transforms()), else None"""
         if fr.encoding != MODULAR:
             return "not a Modular frame"
         R, P, S = frontend.TRANSFORM_RCT, frontend.TRANSFORM_PALETTE, frontend.TRANSFORM_SQUEEZE
+        if chain is not None:  # jxl_modular_begin_chain: every chain but one
+            if any(t["kind"] == P and t["nb_deltas"] > 0 and t["d_pred"] == 6 for t in chain):
+                return "a Palette with weighted-predictor deltas"
+            return None
         if P in kinds:
             return "a Palette in the frame-level chain"
         if kinds not in ([], [R], [S], [R, S]):
@@ -2090,7 +2116,8 @@ class JXLDecoder:
         """None when the frame qualifies for device_image's "modular frame" route, else the first condition that fails. The
         chain is looked at first after the encoding: it is what tells the committed images apart."""
         info = self.info
-        why = self._one_plan_chain_rule(fr, [t["kind"] for t in self.fe.transforms()] if fr.encoding == MODULAR else [])
+        chain = self.fe.transforms() if fr.encoding == MODULAR else []
+        why = self._one_plan_chain_rule(fr, [t["kind"] for t in chain], chain if self.device_chains else None)
         if why is not None:
             return why
         if fr.type != REGULAR_FRAME or not fr.is_last or fr.lf_level != 0:
@@ -2107,17 +2134,18 @@ class JXLDecoder:
         return self._int_rgb_planes_rule(info, fr, colors, colors_img)
 
     @staticmethod
-    def frame_set_rule(info, fr, kinds, traced=False):
+    def frame_set_rule(info, fr, kinds, traced=False, chain=None, patch_sets=False):
         """device_frames: None when the header fields say that a frame can reach the resident canvas as a plane set made from
         the Modular context (_modular_frame_set), else the first condition that fails. info: the image header; fr: the frame
         header; kinds: the kinds of the frame-level transform chain in bitstream order; traced: a `trace` listener is set.
-        Position, blend modes, is_last, the reference slots, noise and splines are free."""
-        why = JXLDecoder._one_plan_chain_rule(fr, kinds)
+        Position, blend modes, is_last, the reference slots, noise and splines are free. With device_chains, chain: the
+        transform list itself, and patch_sets: patch_sets_rule holds for the frame -- its patches then run on the set."""
+        why = JXLDecoder._one_plan_chain_rule(fr, kinds, chain)
         if why is not None:
             return why
         if fr.type not in (REGULAR_FRAME, SKIP_PROGRESSIVE) or fr.lf_level != 0:
             return "not a regular or skip-progressive frame of LF level 0"
-        if fr.num_patches:
+        if fr.num_patches and not (chain is not None and patch_sets):
             return "patches"
         colors_img = 1 if info.colour_space == CE_GRAY else 3
         colors = 3 if info.xyb_encoded else colors_img  # (_colors of a Modular frame)
@@ -2147,8 +2175,13 @@ class JXLDecoder:
         elif self._landed is not None:
             why = "the canvas has landed (%s)" % self._landed
         else:
-            kinds = [t["kind"] for t in self.fe.transforms()] if fr.encoding == MODULAR else []
-            why = self.frame_set_rule(self.info, fr, kinds, self.trace is not None)
+            chain = self.fe.transforms() if fr.encoding == MODULAR else []
+            colors_img = 1 if self.info.colour_space == CE_GRAY else 3
+            patch_sets = self.device_chains and bool(fr.num_patches) and self.patch_sets_rule(
+                self.device_patch_sets, self.device_canvas, self.device_patches, True, colors_img, self._colors(fr)) is None
+            why = self.frame_set_rule(self.info, fr, [t["kind"] for t in chain], self.trace is not None,
+                                      chain if self.device_chains else None, patch_sets)
+            self._patch_sets = why is None and patch_sets  # (the patch stage of _chained_tail looks here)
         self.stats[-1]["frame"] = "device set (modular)" if why is None else "host: " + why
         return why is None
 
@@ -2208,13 +2241,25 @@ class JXLDecoder:
                 steps = t["steps"]
             else:
                 rct_type, rct_begin = t["rct_type"], t["begin_c"]
-        ms = host.ModularStream(be.ctx, chans, steps, rctType=rct_type, rctBegin=rct_begin)
+        if self.device_chains:  # the whole list, whatever it holds (jxl_modular_begin_chain)
+            ms = host.ModularStream(be.ctx, chans, transforms=fe.transforms(), bitDepth=info.bits_per_sample)
+        else:
+            ms = host.ModularStream(be.ctx, chans, steps, rctType=rct_type, rctBegin=rct_begin)
         ms.run()
         host._bus(be.ctx, up=sum(c.nbytes for c in ms.channels))
         n = 3 + info.num_extra
         if be.ctx.lib.jxl_modular_out_count(be.ctx.h) != n:
             raise InvalidBitstreamException("the frame-level stream does not hold the frame's %d channels" % n)
+        if self.device_chains:
+            self._chain_plan = ms  # (_chain_stats reads the plan's counters once something has read its outputs)
         return ms
+
+    def _chain_stats(self):
+        """device_chains: stats[k]["chain"] of the frame whose plan _modular_plan_run queued, once its set has been made"""
+        ms, self._chain_plan = getattr(self, "_chain_plan", None), None
+        if ms is not None:
+            fused, steps, redone = self.backend.host.lastPaletteRun(self.backend.ctx)
+            self.stats[-1]["chain"] = dict(kinds=[t["kind"] for t in ms.transforms], runs=dict(fused=fused, steps=steps, redone=redone))
 
     def _modular_frame_set(self, fr, save):
         """device_frames: the frame's planes after Frame.upsample .. performColorTransforms (JXLCodestreamDecoder.java:628-637)
@@ -2223,7 +2268,8 @@ class JXLDecoder:
         host = be.host
         self._modular_plan_run()
         f32, k = np.dtype(np.float32), fr.upsampling
-        tail = bool(fr.has_noise or fr.has_splines)
+        on_sets = bool(fr.num_patches)  # device_chains: the patch stage takes the set as it is, the stages behind it visit the planes
+        tail = bool(fr.has_noise or fr.has_splines) and not on_sets
 
         def inv_max(depth):  # ImageBuffer.castToFloat's factor (ImageBuffer.java:112-127), as _to_float forms it
             return float(F(F(1) / F((1 << depth) - 1)))
@@ -2236,9 +2282,17 @@ class JXLDecoder:
             desc = [(c, -1, f32, inv_max(info.bits_per_sample)) if tail else (c, -1, np.int32, 1.0) for c in range(3)]
             desc += [(3 + i, -1, f32 if info.ec_exp_bits[i] != 0 else np.int32, 1.0) for i in range(info.num_extra)]
             fset = host.DeviceCanvas.fromModular(be.ctx, fr.height, fr.width, desc)
+        self._chain_stats()
         planes = FramePlanes(be, info, [None] * 3, 3, fset=fset)
         self.stats[-1]["plane_moves"] = planes.moves
-        if tail:  # noise and splines run on the resident planes between jxl_canvas_to_planes and jxl_canvas_take_planes
+        if on_sets:  # the patches on the set, then the stages as behind any adopted set; a refusal has landed everything
+            try:
+                self._chained_tail(fr, planes, save, True, keep=True, upsampled=True, adopted=True)
+            except Exception:
+                if planes.set is not None:
+                    planes.set.release()
+                raise
+        elif tail:  # noise and splines run on the resident planes between jxl_canvas_to_planes and jxl_canvas_take_planes
             try:
                 planes.leave_set()
                 self._chained_tail(fr, planes, save, True, keep=True, upsampled=True)
@@ -2261,6 +2315,7 @@ class JXLDecoder:
         planes = [(c, -1, np.int32, 1.0) for c in range(3)]
         planes += [(3 + i, -1, np.float32 if info.ec_exp_bits[i] != 0 else np.int32, 1.0) for i in range(info.num_extra)]
         cv = host.DeviceCanvas.fromModular(be.ctx, fr.height, fr.width, planes)
+        self._chain_stats()
         if self.trace is not None:
             self._trace("xyb", [cv.download(c) for c in range(n)], False)
         if info.orientation != 1:
@@ -2465,7 +2520,7 @@ class JXLDecoder:
                 self.stats[-1]["canvas"] = "device"  # (the canvas is a set or becomes one now: _frame_set_route has looked)
                 save = self._count_frame(fr)
                 planes = self._modular_frame_set(fr, save)
-                on_set = True
+                on_set = self._landed is None  # (device_chains: the patch stage of a frame with patches may have landed the canvas)
             else:
                 planes = None  # (the last frame's arrays go right before this frame's are made: the allocator hands their memory on)
                 on_set = self._canvas_route(fr, direct)

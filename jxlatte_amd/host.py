@@ -731,13 +731,18 @@ class ModularChannel:
 
 class ModularStream:
     """Transform part of J/frame/modular/ModularStream.java: the channel list as decoded by the host
-    (averages + residuals) plus the squeeze parameters; applyTransforms() undoes Squeeze (and RCT)."""
+    (averages + residuals) plus the squeeze parameters; applyTransforms() undoes Squeeze (and RCT).
+    transforms= (instead of squeezeParams / rctType): the whole frame-level chain in bitstream order, the dictionaries
+    frontend.transforms() returns, undone on the device in one plan (jxl_modular_begin_chain); channels is then the encoded
+    list with its meta channels -- a Palette's palette is channel 0's own data -- and bitDepth the image's."""
 
-    def __init__(self, ctx, channels, squeezeParams, rctType=-1, rctBegin=0):
+    def __init__(self, ctx, channels, squeezeParams=(), rctType=-1, rctBegin=0, transforms=None, bitDepth=8):
         self.ctx = ctx
         self.channels = [np.ascontiguousarray(c, np.int32) for c in channels]
         self.sp = [tuple(int(v) for v in s) for s in squeezeParams]
         self.rctType, self.rctBegin = rctType, rctBegin
+        self.transforms = None if transforms is None else [dict(t) for t in transforms]
+        self.bitDepth = int(bitDepth)
         self.transformed = False
         self._begun = False
 
@@ -768,8 +773,12 @@ class ModularStream:
 
     def begin(self):
         ca = abi.make_channels(self.channels)
-        self.ctx.call("jxl_modular_begin", ca, len(self.channels), abi.make_squeeze_params(self.sp), len(self.sp),
-                      self.rctType, self.rctBegin)
+        if self.transforms is not None:
+            tr, keep = abi.make_transforms(self.transforms)
+            self.ctx.call("jxl_modular_begin_chain", ca, len(self.channels), tr, len(self.transforms), self.bitDepth)
+        else:
+            self.ctx.call("jxl_modular_begin", ca, len(self.channels), abi.make_squeeze_params(self.sp), len(self.sp),
+                          self.rctType, self.rctBegin)
         self._begun = True
 
     def run(self):
@@ -827,6 +836,24 @@ def lastPalette(ctx):
     deltas = C.c_int64(0)
     n = fn(ctx.h, C.byref(deltas))
     return int(n), int(deltas.value)
+
+
+def setPaletteFuse(ctx, on):
+    """forces a chain plan's Palette runs into the step form (on=False) or lets them fuse (jxl_debug_set_palette_fuse, a
+    process-wide hook outside the C-ABI, read per run); returns the previous setting"""
+    fn = ctx.lib.jxl_debug_set_palette_fuse
+    fn.restype, fn.argtypes = C.c_int, [C.c_int]
+    return bool(fn(1 if on else 0))
+
+
+def lastPaletteRun(ctx):
+    """(fused launches, step launches, redone runs) of the context's last jxl_modular_run with whatever its settle ran again
+    (jxl_debug_last_palette_run); read it after the plan's outputs"""
+    fn = ctx.lib.jxl_debug_last_palette_run
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]
+    out = (C.c_int32 * 3)()
+    fn(ctx.h, out)
+    return tuple(int(v) for v in out)
 
 
 def modularToFloat(ctx, a, b, scale):
