@@ -869,6 +869,51 @@ jxl_status jxl_canvas_png_samples(jxl_ctx* ctx, int32_t id, int32_t alpha_plane,
 /* jxl_stage_color_peak on planes 0 .. p->n_planes - 1 of the set (in_is_int must equal their tags) */
 jxl_status jxl_canvas_color_peak(jxl_ctx* ctx, int32_t id, const jxl_color_params* p, float* peak);
 
+/* ---- the image as a device tensor in one pass: the third exit beside the PNG's and the PFM's samples ----
+ * Per pixel: the colour stages 1-6 of `color` exactly as jxl_stage_png_samples evaluates them (max_value must be 0); the alpha
+ * sample (a float plane as it is; an int32 plane as (float)a * (1.0f / (2^depth - 1)) for the float dtypes, and by
+ * jxl_stage_png_samples' rule at bit_depth 8 for JXL_TENSOR_U8); colour / alpha, the correctly rounded f32 division, when
+ * `premultiplied` (whether or not alpha is written; a zero alpha gives what the division gives); for the float dtypes with
+ * use_norm (v - mean[c]) * inv_std[c], two separately rounded f32 operations, c the OUTPUT channel (alpha, when written, is the
+ * channel after the colours); then the conversion: F32 the bits as they are; F16 / BF16 round to nearest even (overflow to
+ * infinity, F16 subnormals kept, every NaN 0x7E00 / 0x7FC0); U8 (int)(v * 255 + 0.5f) clamped to 0..255, the PNG's quantiser.
+ * Output channels: nc = 3 when color.n_planes == 3 or color.use_matrix, else 1, plus 1 with write_alpha. JXL_TENSOR_CHW: channel
+ * c at out + c * height * width elements, rows top to bottom; JXL_TENSOR_HWC: the channels interleaved per pixel.
+ * out_device is DEVICE memory of the context's device, element-aligned (it may be a slice of a larger allocation), dense. The
+ * launch is queued on the context's stream and the stream is synchronised before return; no sample comes down.
+ * JXL_ERR_INVALID_ARGUMENT, nothing queued and out_device untouched: everything jxl_stage_png_samples refuses at bit_depth 8; an
+ * unknown dtype or layout; use_norm with JXL_TENSOR_U8 or with an inv_std that is not finite; write_alpha or premultiplied
+ * without has_alpha; an int32 alpha plane whose depth is outside 1..31 where it is cast; an out_device that is not device memory
+ * of the context's device (a host pointer never reaches a kernel) or whose allocation ends before the tensor does. */
+#define JXL_TENSOR_U8 0
+#define JXL_TENSOR_F16 1
+#define JXL_TENSOR_BF16 2
+#define JXL_TENSOR_F32 3
+#define JXL_TENSOR_CHW 0
+#define JXL_TENSOR_HWC 1
+typedef struct jxl_tensor_params {
+    jxl_color_params color;     /* the planes and stages 1-6; max_value 0 */
+    int32_t height, width;
+    int32_t has_alpha;          /* an alpha plane is given */
+    int32_t premultiplied;      /* the colours are divided by alpha */
+    int32_t write_alpha;        /* alpha is the last output channel */
+    int32_t alpha_is_int;       /* as in jxl_png_params */
+    int32_t alpha_tagged_depth;
+    int32_t color_tagged_depth;
+    int32_t dtype;              /* JXL_TENSOR_U8 / F16 / BF16 / F32 */
+    int32_t layout;             /* JXL_TENSOR_CHW / HWC */
+    int32_t use_norm;           /* float dtypes only */
+    float mean[4], inv_std[4];  /* per output channel */
+} jxl_tensor_params;
+/* in: color.n_planes host planes of height * width samples, alpha: a host plane or NULL; uploaded once. */
+jxl_status jxl_stage_tensor_samples(jxl_ctx* ctx, const void* const in[3], const void* alpha, const jxl_tensor_params* p, void* out_device);
+/* The same launch on the three resident float planes (color.n_planes 3, in_is_int 0, height and width theirs); alpha: a host
+ * plane, uploaded once, or NULL. JXL_ERR_STATE without resident planes. */
+jxl_status jxl_planes_tensor_samples(jxl_ctx* ctx, const void* alpha, const jxl_tensor_params* p, void* out_device);
+/* The same launch on planes 0 .. color.n_planes - 1 and the alpha plane (alpha_plane, -1: none) of the plane set `id`, with
+ * jxl_canvas_png_samples' checks of the set's geometry and tags: nothing crosses the bus in either direction. */
+jxl_status jxl_canvas_tensor_samples(jxl_ctx* ctx, int32_t id, int32_t alpha_plane, const jxl_tensor_params* p, void* out_device);
+
 /* ---- the PFM's samples in one pass: replaces the body of PFMWriter.write (PFMWriter.java:30-48) after the header ----
  * The planes are the image's own samples (image.getBuffer(false), :30): no colour transform, no peak scale, no transfer
  * function. An int32 plane is cast as castToFloat(image.getTaggedBitDepth(c)) casts it (:33-35; ImageBuffer.java:99-101,

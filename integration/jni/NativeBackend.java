@@ -209,6 +209,12 @@ public final class NativeBackend implements AutoCloseable {
     public native void canvasPngSamples(int id, int alphaPlane, ByteBuffer params, ByteBuffer out);   // jxl_canvas_png_samples (alphaPlane -1: none)
     public native float canvasColorPeak(int id, ByteBuffer params);                                   // jxl_canvas_color_peak
     public native void canvasPfmSamples(int id, int[] params, ByteBuffer out);                        // jxl_canvas_pfm_samples (out: exactly 4 * n_planes * width * height bytes)
+    // the image as a device tensor in one pass: params = struct jxl_tensor_params in a direct buffer; out = the DEVICE address of
+    // height * width * channels elements (the library refuses anything that is not device memory of its device, or too short)
+    public native void stageTensorSamples(ByteBuffer i0, ByteBuffer i1, ByteBuffer i2, ByteBuffer alpha, ByteBuffer params,
+            long out);                                                                                // jxl_stage_tensor_samples
+    public native void planesTensorSamples(ByteBuffer alpha, ByteBuffer params, long out);            // jxl_planes_tensor_samples
+    public native void canvasTensorSamples(int id, int alphaPlane, ByteBuffer params, long out);      // jxl_canvas_tensor_samples (alphaPlane -1: none)
     /** shapes: {n, h, w, type[n]}; ref null when desc names no reference. Throws what canvasBlend would; no device needed. */
     public static native void canvasBlendCheck(int[] desc, int[] canvas, int[] frame, int[] ref);    // jxl_canvas_blend_check
 

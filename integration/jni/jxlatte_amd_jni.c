@@ -1494,6 +1494,51 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasPfmSa
     CHECK(jxl_canvas_pfm_samples(c, id, &p, ADDR(out)));
 }
 
+/* ---- the image as a device tensor in one pass: params = struct jxl_tensor_params in a direct buffer, as the PNG natives take
+ * theirs; out = the DEVICE address of the tensor (a long: there is no buffer object for memory the host cannot read). The shim can
+ * check the host planes' sizes; whether `out` is device memory that holds the tensor is the library's question. ---- */
+static int tensor_params(JNIEnv* e, jobject params, jxl_tensor_params* p) {
+    const void* src = params ? (*e)->GetDirectBufferAddress(e, params) : NULL;
+    if (!src || (*e)->GetDirectBufferCapacity(e, params) < (jlong)sizeof *p) {
+        bad_arg(e, "jxlatte_amd: a direct buffer holding jxl_tensor_params is needed");
+        return 0;
+    }
+    memcpy(p, src, sizeof *p);
+    if (p->height < 1 || p->width < 1) {
+        bad_arg(e, "jxlatte_amd: tensor parameters");
+        return 0;
+    }
+    return 1;
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageTensorSamples(JNIEnv* e, jobject self, jobject i0, jobject i1, jobject i2,
+        jobject alpha, jobject params, jlong out) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_tensor_params p;
+    if (!tensor_params(e, params, &p)) return;
+    const jlong plane = 4 * area(p.height, p.width);
+    NEED(i0, plane); NEED_OPT(i1, plane); NEED_OPT(i2, plane); NEED_OPT(alpha, plane);
+    const void* in[3] = {ADDR(i0), ADDR(i1), ADDR(i2)};
+    CHECK(jxl_stage_tensor_samples(c, in, ADDR(alpha), &p, (void*)(intptr_t)out));
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesTensorSamples(JNIEnv* e, jobject self, jobject alpha, jobject params,
+        jlong out) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_tensor_params p;
+    if (!tensor_params(e, params, &p)) return;
+    NEED_OPT(alpha, 4 * area(p.height, p.width));
+    CHECK(jxl_planes_tensor_samples(c, ADDR(alpha), &p, (void*)(intptr_t)out));
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasTensorSamples(JNIEnv* e, jobject self, jint id, jint alphaPlane,
+        jobject params, jlong out) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_tensor_params p;
+    if (!tensor_params(e, params, &p)) return;
+    CHECK(jxl_canvas_tensor_samples(c, id, alphaPlane, &p, (void*)(intptr_t)out));
+}
+
 JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasBlendCheck(JNIEnv* e, jclass k, jintArray desc, jintArray canvas,
         jintArray frame, jintArray ref) {
     (void)k;

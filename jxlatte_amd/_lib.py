@@ -159,6 +159,9 @@ SIGNATURES = {
     "jxl_stage_pack": (i32, [vp, pv3, C.POINTER(abi.PackParams), vp]),
     "jxl_stage_png_samples": (i32, [vp, pv3, vp, C.POINTER(abi.PngParams), vp]),
     "jxl_planes_png_samples": (i32, [vp, vp, C.POINTER(abi.PngParams), vp]),
+    "jxl_stage_tensor_samples": (i32, [vp, pv3, vp, C.POINTER(abi.TensorParams), vp]),
+    "jxl_planes_tensor_samples": (i32, [vp, vp, C.POINTER(abi.TensorParams), vp]),
+    "jxl_canvas_tensor_samples": (i32, [vp, i32, i32, C.POINTER(abi.TensorParams), vp]),
     "jxl_planes_color_peak": (i32, [vp, C.POINTER(abi.ColorParams), pf]),
     "jxl_planes_orient": (i32, [vp, i32]),
     "jxl_stage_pfm_samples": (i32, [vp, pv3, C.POINTER(abi.PfmParams), vp]),

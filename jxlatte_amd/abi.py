@@ -203,6 +203,21 @@ class PngParams(C.Structure):
                 ("alpha_tagged_depth", C.c_int32), ("color_tagged_depth", C.c_int32)]
 
 
+TENSOR_U8, TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 0, 1, 2, 3
+TENSOR_CHW, TENSOR_HWC = 0, 1
+
+
+class TensorParams(C.Structure):
+    """struct jxl_tensor_params"""
+    _fields_ = [("color", ColorParams), ("height", C.c_int32), ("width", C.c_int32), ("has_alpha", C.c_int32),
+                ("premultiplied", C.c_int32), ("write_alpha", C.c_int32), ("alpha_is_int", C.c_int32),
+                ("alpha_tagged_depth", C.c_int32), ("color_tagged_depth", C.c_int32), ("dtype", C.c_int32), ("layout", C.c_int32),
+                ("use_norm", C.c_int32), ("mean", C.c_float * 4), ("inv_std", C.c_float * 4)]
+
+
+assert C.sizeof(TensorParams) == C.sizeof(ColorParams) + 4 * (11 + 8)
+
+
 class PfmParams(C.Structure):
     """struct jxl_pfm_params"""
     _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("n_planes", C.c_int32), ("is_int", C.c_int32 * 3),

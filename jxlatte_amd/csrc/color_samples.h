@@ -62,6 +62,32 @@ __device__ __forceinline__ float linear_word(const ColorArgs& a, int c, uint32_t
     return to_linear(f, a.tf_in, a.p_in, a.kind_in);
 }
 
+// stages 1-6 of one pixel as the writers' one-pass kernels (k_png.hip, k_tensor.hip) evaluate them: the words of its colour planes
+// (w[c], c < n_planes) -> COLORS float samples, COLORS being 3 when n_planes == 3 or use_matrix, else 1
+template <int COLORS>
+__device__ __forceinline__ void color_stages(const ColorArgs& a, const uint32_t w[3], float v[3]) {
+    const float* pq_tab = a.pq_tab;
+    v[0] = linear_word(a, 0, w[0]);
+    if (COLORS == 3) {
+        v[1] = v[2] = v[0];  // fillColor
+        if (a.n_planes == 3) {
+            v[1] = linear_word(a, 1, w[1]);
+            v[2] = linear_word(a, 2, w[2]);
+        }
+        if (a.use_matrix) {
+            const float x = (a.m[0] * v[0] + a.m[1] * v[1]) + a.m[2] * v[2];
+            const float y = (a.m[3] * v[0] + a.m[4] * v[1]) + a.m[5] * v[2];
+            const float z = (a.m[6] * v[0] + a.m[7] * v[1]) + a.m[8] * v[2];
+            v[0] = x; v[1] = y; v[2] = z;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < COLORS; c++) {
+        if (a.use_scale) v[c] = v[c] * a.scale;
+        v[c] = from_linear(v[c], a.tf_out, a.p_out, a.kind_out, pq_tab);
+    }
+}
+
 // stages 1 + 2 of sample i of input plane c
 __device__ __forceinline__ float linear_sample(const ColorArgs& a, int c, int64_t i) {
     return linear_word(a, c, ((const uint32_t*)a.in[c])[i]);

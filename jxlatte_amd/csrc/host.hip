@@ -3110,6 +3110,7 @@ jxl_status ctx_link(jxl_ctx* c, CtxLink* out) {
     if (st) return st;
     out->stream = c->stream;
     out->canvas = &c->canvas;
+    out->device = c->device;
     return JXL_OK;
 }
 jxl_status ctx_fail(jxl_ctx* c, jxl_status st, const char* msg) { return fail(c, st, "%s", msg); }
@@ -4175,6 +4176,12 @@ jxl_status png_run(jxl_ctx* c, PngArgs& a, int n_color, bool has_alpha, const vo
     return JXL_OK;
 }
 }  // namespace
+namespace jxl {
+jxl_status ctx_png_args(jxl_ctx* c, const jxl_png_params* p, const void* const in[3], const void* alpha, const void* out, PngArgs* a,
+                        int* n_color) {
+    return png_args(c, p, in, alpha, out, a, n_color);
+}
+}  // namespace jxl
 extern "C" {
 
 jxl_status jxl_stage_png_samples(jxl_ctx* c, const void* const in[3], const void* alpha, const jxl_png_params* p, void* out) {

@@ -243,6 +243,19 @@ struct PngArgs {
 };
 // n_color: 3 when c.n_planes == 3 or c.use_matrix, else 1
 void launch_png_samples(const PngArgs& p, int n_color, hipStream_t s);
+// the image as a device tensor in one pass (k_tensor.hip): stages 1-6 and the alpha rule of PngArgs (g.bit_depth 8; g.out is not
+// looked at), then un-premultiplication, normalisation and the conversion to `dtype`, stored CHW or HWC
+struct TensorArgs {
+    PngArgs g;
+    int dtype, layout;      // JXL_TENSOR_*
+    int n_out;              // output channels: n_color, + 1 when alpha is written
+    int use_norm;
+    float mean[4], inv_std[4];
+    int wide;               // every group of a lane's 4 pixels may leave as vector stores (tensor_wide_ok); else sample by sample
+    void* out;              // device memory, element-aligned: c.n * n_out elements
+};
+// max_workgroups > 0: a smaller grid bound than the kernel's own (tests reach the grid-stride loop at a small size)
+void launch_tensor_samples(const TensorArgs& p, hipStream_t s, int max_workgroups = 0);
 // the PFM's samples from the image's planes in one pass (k_pfm.hip): cast of the int32 planes, floatToIntBits, big-endian words,
 // channels interleaved, rows bottom to top (PFMWriter.java:22-49)
 struct PfmArgs {
@@ -551,7 +564,12 @@ void canvas_store_free(CanvasStore* s);  // jxl_ctx_destroy, after the stream ha
 struct CtxLink {
     hipStream_t stream;
     CanvasStore** canvas;  // the context's slot for its store (null until the first set)
+    int device;            // the context's device ordinal
 };
+// png_args of host.hip for tensor_host.hip: the checks of the three PNG entries on one jxl_png_params, and the kernel's arguments
+// (plane and output pointers are the caller's to fill in)
+jxl_status ctx_png_args(jxl_ctx* c, const jxl_png_params* p, const void* const in[3], const void* alpha, const void* out, PngArgs* a,
+                        int* n_color);
 jxl_status ctx_link(jxl_ctx* c, CtxLink* out);                      // hipSetDevice + the fields above
 jxl_status ctx_fail(jxl_ctx* c, jxl_status st, const char* msg);    // records the message (c may be null) and returns st
 jxl_status ctx_planes_get(jxl_ctx* c, int* h, int* w, float* p[3]);  // the resident planes, or JXL_ERR_STATE

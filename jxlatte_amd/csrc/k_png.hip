@@ -38,29 +38,9 @@ struct PngShape {
 template <int NCH, int BYTES>
 __device__ __forceinline__ void png_pixel(const PngArgs& p, const uint32_t w[3], uint32_t aw, uint32_t q[4]) {
     using S = PngShape<NCH, BYTES>;
-    const ColorArgs& a = p.c;
-    const float* pq_tab = a.pq_tab;
     const int maxv = BYTES == 1 ? 255 : 65535;
     float v[3];
-    v[0] = linear_word(a, 0, w[0]);
-    if (S::kColors == 3) {
-        v[1] = v[2] = v[0];  // fillColor
-        if (a.n_planes == 3) {
-            v[1] = linear_word(a, 1, w[1]);
-            v[2] = linear_word(a, 2, w[2]);
-        }
-        if (a.use_matrix) {
-            const float x = (a.m[0] * v[0] + a.m[1] * v[1]) + a.m[2] * v[2];
-            const float y = (a.m[3] * v[0] + a.m[4] * v[1]) + a.m[5] * v[2];
-            const float z = (a.m[6] * v[0] + a.m[7] * v[1]) + a.m[8] * v[2];
-            v[0] = x; v[1] = y; v[2] = z;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < S::kColors; c++) {
-        if (a.use_scale) v[c] = v[c] * a.scale;
-        v[c] = from_linear(v[c], a.tf_out, a.p_out, a.kind_out, pq_tab);
-    }
+    color_stages<S::kColors>(p.c, w, v);
     if (S::kAlpha) {
         float fa = __builtin_bit_cast(float, aw);
         if (p.alpha_is_int) fa = (float)(int32_t)aw * p.alpha_scale;  // castToFloat0 with the tagged depth

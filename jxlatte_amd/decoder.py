@@ -751,6 +751,14 @@ class DeviceBackend:
         """PNGWriter's samples in one pass (host.pngSamples; the keywords are host.pngParams')"""
         return self.host.pngSamples(self.ctx, planes, alpha, **params)
 
+    def tensor_samples(self, planes, alpha, out_ptr, **params):
+        """the image as a device tensor in one pass (host.tensorSamples; the keywords are host.tensorParams')"""
+        return self.host.tensorSamples(self.ctx, planes, alpha, out_ptr, **params)
+
+    def tensor_device(self):
+        """the torch device of the memory tensor_samples writes"""
+        return "cuda:%d" % self.ctx.device
+
     def varblocks(self, planes, blocks, cells):
         """Frame.drawVarblocks in one pass (host.varblocks)"""
         return self.host.varblocks(self.ctx, planes, blocks, cells)
@@ -874,6 +882,105 @@ class JXLImage:
             return self.resident.pngSamples(alpha, **kw), up
         planes = [np.ascontiguousarray(p) for p in planes]
         return self.backend.png_samples(planes, alpha, **kw), up + sum(p.nbytes for p in planes)
+
+    def _tensor_samples(self, planes, out_ptr, **kw):
+        """the image as a device tensor in one pass (tensorParams' keywords), written to the device address out_ptr: the bytes
+        sent up, by _png_samples' rule. Nothing comes down from any home"""
+        colors, a = len(planes), self.alphaIndex
+        home = self._home(colors, True)
+        if home == "set":
+            self.planeSet.tensorSamples(out_ptr, nColor=colors, alphaPlane=colors + a if a >= 0 else None, **kw)
+            return 0
+        alpha = np.ascontiguousarray(self.extraChannel(a)) if a >= 0 else None
+        up = alpha.nbytes if alpha is not None and (kw.get("writeAlpha") or kw.get("premultiplied")) else 0
+        if home == "resident":
+            self.resident.tensorSamples(out_ptr, alpha, **kw)
+            return up
+        planes = [np.ascontiguousarray(p) for p in planes]
+        self.backend.tensor_samples(planes, alpha, out_ptr, **kw)
+        return up + sum(p.nbytes for p in planes)
+
+    _TENSOR_TARGETS = ("srgb", "pq", "linear", "as-is")
+
+    def toTensor(self, dtype=None, layout="CHW", target="srgb", peakDetect=PEAK_DETECT_AUTO, alpha="drop", mean=None, std=None, out=None):
+        """The image as a torch tensor on the backend's device, (C, H, W) or (H, W, C), in ONE device pass from wherever its planes
+        are -- no sample crosses the bus downwards.
+        dtype: torch.uint8, float16, bfloat16 or float32 (the default). target: "srgb" (PNGWriter's non-HDR target: sRGB
+        primaries, D65, the sRGB curve), "pq" (its HDR target: BT.2100 primaries, PQ), "linear" (sRGB primaries, D65, linear) or
+        "as-is" (no colour stage; integer planes cast with their depth); an image with an ICC profile is taken as it is whatever
+        is asked, as PNGWriter takes it. A grey image that has to be tone-mapped yields three channels: the shape tells.
+        alpha: "drop" or "append" (the last channel); a premultiplied image's colours are divided either way.
+        mean / std: per output channel, float dtypes only: (v - mean) * (float32(1) / float32(std)).
+        out: a contiguous tensor of the result's shape and dtype on that device -- batch[i] of a batch of equal-sized images is
+        one -- filled in place and returned; the current torch stream is synchronised first. tensor_bus_bytes = (bytes up, 0)."""
+        import torch
+        be = self.backend
+        if not hasattr(be, "tensor_samples"):
+            raise TypeError("toTensor needs a backend with tensor_samples")
+        if dtype is None:
+            dtype = torch.float32
+        names = {torch.uint8: "uint8", torch.float16: "float16", torch.bfloat16: "bfloat16", torch.float32: "float32"}
+        if dtype not in names:
+            raise ValueError("dtype: torch.uint8, float16, bfloat16 or float32")
+        if layout not in ("CHW", "HWC"):
+            raise ValueError("layout: CHW or HWC")
+        if target not in self._TENSOR_TARGETS:
+            raise ValueError("target: one of %s" % (self._TENSOR_TARGETS,))
+        if alpha not in ("drop", "append"):
+            raise ValueError("alpha: drop or append")
+        if alpha == "append" and self.alphaIndex < 0:
+            raise ValueError("the image has no alpha channel to append")
+        if (mean is None) != (std is None):
+            raise ValueError("mean and std come together")
+        if mean is not None and dtype == torch.uint8:
+            raise ValueError("normalisation is for the float dtypes")
+        colors = self.getColorChannelCount()
+        as_is = target == "as-is" or self.has_icc
+        primaries, tf = {"srgb": (PRI_SRGB, TF_SRGB), "pq": (PRI_BT2100, TF_PQ), "linear": (PRI_SRGB, TF_LINEAR)}.get(target, (None, None))
+        tone_map = not as_is and not (_prim_matches(primaries, self.primariesXY) and _xy_matches(WP_D65, self.whiteXY))
+        channels = (3 if (colors == 3 or tone_map) else 1) + (alpha == "append")
+        inv_std = None
+        if mean is not None:
+            mean, std = [float(v) for v in mean], [float(v) for v in std]
+            if len(mean) != channels or len(std) != channels:
+                raise ValueError("mean and std have one entry per output channel (%d)" % channels)
+            with np.errstate(all="ignore"):
+                inv_std = [F(1) / F(s) for s in std]
+            if not all(np.isfinite(v) for v in inv_std):
+                raise ValueError("std: 1 / std is not finite")
+        shape = (channels, self.height, self.width) if layout == "CHW" else (self.height, self.width, channels)
+        device = torch.device(be.tensor_device())
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != device or not out.is_contiguous():
+                raise ValueError("out: a contiguous %s tensor of shape %s on %s" % (names[dtype], shape, device))
+        up = 0
+        planes = self._plan_planes(colors)  # (stand-ins while the samples are on the device)
+
+        def peak_of(pl, **front):
+            nonlocal up
+            peak, sent = self._peak(pl, **front)
+            up += sent
+            return peak
+        plan = None if as_is else self._color_plan(primaries, WP_D65, tf, peakDetect, peak_of, planes=planes)
+        if plan is not None:
+            planes, params = plan[0], plan[1]
+        else:  # the image as it is: every colour stage off; integer planes are cast with their depth's maximum
+            if planes is None:
+                planes = [self.buffer[c] for c in range(colors)]
+                if len({a.dtype for a in planes}) != 1:
+                    planes = [self._as_float(c) for c in range(colors)]
+            params = dict(inMax=[(1 << self.bitDepths[c]) - 1 for c in range(colors)])
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=device)
+        elif device.type == "cuda":
+            torch.cuda.current_stream(device).synchronize()  # what the caller queued on its tensor is done before the library writes
+        has_alpha = self.alphaIndex >= 0
+        sent = self._tensor_samples(
+            planes, out.data_ptr(), premultiplied=self.isAlphaPremultiplied() and has_alpha, writeAlpha=alpha == "append",
+            dtype=names[dtype], layout=layout, alphaDepth=self.getTaggedBitDepth(colors + self.alphaIndex) if has_alpha else None,
+            colorDepth=self.getTaggedBitDepth(0), mean=mean, invStd=inv_std, **params)
+        self.tensor_bus_bytes = (up + sent, 0)
+        return out
 
     def _pfm_samples(self, tagged):
         """PFMWriter's samples in one pass: (samples, bytes sent up). A set's planes, int32 or float, as they are"""

@@ -259,6 +259,51 @@ def pngSamples(ctx, planes, alpha=None, **params):
     return out
 
 
+TENSOR_DTYPES = {"uint8": abi.TENSOR_U8, "float16": abi.TENSOR_F16, "bfloat16": abi.TENSOR_BF16, "float32": abi.TENSOR_F32}
+TENSOR_LAYOUTS = {"CHW": abi.TENSOR_CHW, "HWC": abi.TENSOR_HWC}
+
+
+def tensorParams(planes, shape, alpha=None, premultiplied=False, writeAlpha=False, dtype="float32", layout="CHW", alphaDepth=None,
+                 colorDepth=None, mean=None, invStd=None, **color):
+    """jxl_tensor_params: colorParams(planes, **color) (maxValue stays 0) plus the tensor's arguments. alpha: the alpha plane (its
+    dtype tells int32 from float32) or None; alphaDepth / colorDepth: the tagged depths (default 8); dtype: a key of
+    TENSOR_DTYPES or an abi.TENSOR_* code, layout likewise; mean / invStd: per output channel, both or neither (float dtypes)"""
+    p = abi.TensorParams()
+    p.color = colorParams(planes, **color)
+    p.height, p.width = int(shape[0]), int(shape[1])
+    p.has_alpha, p.premultiplied, p.write_alpha = int(alpha is not None), int(bool(premultiplied)), int(bool(writeAlpha))
+    p.alpha_is_int = int(alpha is not None and alpha.dtype == np.int32)
+    p.alpha_tagged_depth = int(8 if alphaDepth is None else alphaDepth)
+    p.color_tagged_depth = int(8 if colorDepth is None else colorDepth)
+    p.dtype = TENSOR_DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
+    p.layout = TENSOR_LAYOUTS[layout] if isinstance(layout, str) else int(layout)
+    if (mean is None) != (invStd is None):
+        raise ValueError("mean and invStd come together")
+    if mean is not None:
+        p.use_norm = 1
+        for c, (m, s) in enumerate(zip(mean, invStd)):
+            p.mean[c], p.inv_std[c] = float(m), float(s)
+    return p
+
+
+def tensorChannels(p):
+    """the output channels of a jxl_tensor_params"""
+    return (3 if (p.color.n_planes == 3 or p.color.use_matrix) else 1) + int(bool(p.write_alpha))
+
+
+def tensorSamples(ctx, planes, alpha, out_ptr, **params):
+    """The image as a device tensor in one pass (jxl_stage_tensor_samples): the colour stages of pngSamples, un-premultiplication,
+    normalisation and the conversion to the tensor's dtype, stored CHW or HWC at the DEVICE address out_ptr (an integer: memory
+    of the context's device that holds height * width * channels elements). planes / alpha: host arrays, uploaded once.
+    params: tensorParams' keywords. Complete on return; nothing comes down. Returns the jxl_tensor_params it used."""
+    planes = [np.ascontiguousarray(a) for a in planes]
+    shape = planes[0].shape
+    a = _png_alpha(alpha, shape)
+    p = tensorParams(planes, shape, alpha=a, **params)
+    ctx.call("jxl_stage_tensor_samples", _pv(planes), _vp(a), C.byref(p), C.c_void_p(int(out_ptr)))
+    return p
+
+
 def pfmParams(planes, shape, taggedDepths=None):
     """jxl_pfm_params of 1 or 3 planes (each one's dtype tells int32 from float32). taggedDepths: image.getTaggedBitDepth(c)
     per plane, looked at for the int32 planes only"""
@@ -674,6 +719,16 @@ class ResidentPlanes:
         out = _png_out(p, shape)
         self.ctx.call("jxl_planes_png_samples", _vp(a), C.byref(p), _vp(out))
         return out
+
+    def tensorSamples(self, out_ptr, alpha=None, **params):
+        """tensorSamples of the planes as they stand (jxl_planes_tensor_samples) to the device address out_ptr: only the alpha
+        plane goes up, nothing comes down"""
+        self._need_live()
+        shape = self.shape
+        a = _png_alpha(alpha, shape)
+        p = tensorParams(self._stand_ins(), shape, alpha=a, **params)
+        self.ctx.call("jxl_planes_tensor_samples", _vp(a), C.byref(p), C.c_void_p(int(out_ptr)))
+        return p
 
     def pfmSamples(self):
         """pfmSamples of the planes as they stand (jxl_planes_pfm_samples): nothing goes up, only the PFM's bytes come down"""
@@ -1174,6 +1229,16 @@ class DeviceCanvas:
         self.ctx.call("jxl_canvas_png_samples", self.id, ap, C.byref(p), _vp(out))
         _bus(self.ctx, down=out.nbytes)
         return out
+
+    def tensorSamples(self, out_ptr, nColor=3, alphaPlane=None, **params):
+        """tensorSamples of planes 0 .. nColor - 1 and the alpha plane alphaPlane of the set (jxl_canvas_tensor_samples;
+        tensorParams' keywords but `alpha`) to the device address out_ptr: nothing crosses the bus, so nothing is counted"""
+        self._live()
+        ap = -1 if alphaPlane is None else int(alphaPlane)
+        alpha = None if ap < 0 else np.broadcast_to(np.zeros((), _PLANE_DTYPE[self.types[ap]]), self.shape)
+        p = tensorParams(self._stand_ins(nColor), self.shape, alpha=alpha, **params)
+        self.ctx.call("jxl_canvas_tensor_samples", self.id, ap, C.byref(p), C.c_void_p(int(out_ptr)))
+        return p
 
     def pfmSamples(self, nColor=3, taggedDepths=None):
         """pfmSamples of planes 0 .. nColor - 1 (jxl_canvas_pfm_samples): nothing goes up, only the PFM's bytes come down"""
