@@ -164,6 +164,7 @@ struct jxl_ctx {
     bool llf_alias = false;            // no kernel writes the llf planes for this frame: they ARE the lf planes (no copy)
     size_t tab_fixed = 0, off_hfm = 0, off_sharp = 0, off_kx = 0, off_kb = 0, off_lf[3] = {0, 0, 0};
     HSpan<int32_t> h_hf_mul, h_sharp;
+    bool hf_mul_negative = false;  // h_hf_mul holds a negative entry (RestoreParams::hf_mul_negative)
     std::vector<int32_t> h_xfy, h_bfy;
     HSpan<float> h_kx, h_kb;
     std::vector<uint8_t> h_sel;
@@ -529,10 +530,11 @@ std::atomic<int> g_plane_a_tiled{1};
 std::atomic<int> g_palette_fuse{1};
 // jxl_debug_last_restore_launches: above the seven bits of restore_fused_variant()
 constexpr int32_t kRestoreTiledBit = 128, kRestoreBatchBit = 256;
+constexpr int32_t kRestorePlainBit = 512;  // the EPF tails with plain divisions (epf_weights_plain: a negative factor in the weights)
 int32_t restore_launch_code(const RestoreParams& rp, bool tiled, bool batch) {
     FusedArgs a{};
     a.p = rp;
-    return restore_fused_variant(a) | (tiled ? kRestoreTiledBit : 0) | (batch ? kRestoreBatchBit : 0);
+    return restore_fused_variant(a) | (tiled ? kRestoreTiledBit : 0) | (batch ? kRestoreBatchBit : 0) | (epf_weights_plain(rp) ? kRestorePlainBit : 0);
 }
 void inter_account(int device, long long delta) {
     if (device >= 0 && device < 64) g_inter_bytes[device].fetch_add(delta, std::memory_order_relaxed);
@@ -730,6 +732,7 @@ bool tab_begin_frame(jxl_ctx* c, size_t nc, size_t nt) {
     tab_bind_fixed(c, nc, nt);
     tm.mark("reserve");
     std::fill(c->h_hf_mul.begin(), c->h_hf_mul.end(), 1);
+    c->hf_mul_negative = false;
     memset(c->h_sharp.data(), 0, 4 * nc);
     memset(c->h_kx.data(), 0, 4 * nt);
     memset(c->h_kb.data(), 0, 4 * nt);
@@ -1341,7 +1344,8 @@ extern "C" int jxl_debug_last_palette_run(const jxl_ctx* c, int32_t out[3]) {
 // Test hook (tests/test_restore_variants_gpu.py): the fused restoration launches of the context's last frame run -- how many (0: the
 // stage kernels ran instead, 1, or 2 for the split three-iteration form) and, per launch, which instantiation:
 // restore_fused_variant() of its arguments (Gaborish 64 | EPF iterations << 3 | sink kind), | 128 for cell-tiled input planes,
-// | 256 for a batch launch, which every context of the batch reports. Not part of the C-ABI of include/jxlatte_amd.h.
+// | 256 for a batch launch, which every context of the batch reports, | 512 for the instantiations with plain divisions in the EPF
+// tails. Not part of the C-ABI of include/jxlatte_amd.h.
 extern "C" int jxl_debug_last_restore_launches(const jxl_ctx* c, int32_t codes[2]) {
     if (!c) return 0;
     for (int i = 0; i < 2 && codes; i++) codes[i] = i < c->last_restore_n ? c->last_restore_code[i] : 0;
@@ -1354,6 +1358,24 @@ extern "C" int jxl_debug_last_palette(const jxl_ctx* c, int64_t* delta_pixels) {
     if (!c) return 0;
     if (delta_pixels) *delta_pixels = c->last_palette_deltas;
     return c->last_palette_launches;
+}
+// Test hook (tests/test_epf_quot3_gpu.py): epf_quot3 (epf_quot3.h), the fused restoration kernel's three quotients by one denominator,
+// on host arrays, one lane per element: out[k * count + i] = n[k * count + i] / d[i], k = 0..2, for 1 <= d[i] < 16. Not part of the
+// C-ABI of include/jxlatte_amd.h.
+extern "C" int jxl_debug_epf_quot3(const float* n, const float* d, float* out, int64_t count) {  // (on the calling thread's device)
+    if (!n || !d || !out || count <= 0 || count > (int64_t)1 << 28) return -1;
+    float *dn = nullptr, *dd = nullptr, *dout = nullptr;
+    const size_t bytes = sizeof(float) * (size_t)count;
+    bool ok = hipMalloc(&dn, 3 * bytes) == hipSuccess && hipMalloc(&dd, bytes) == hipSuccess && hipMalloc(&dout, 3 * bytes) == hipSuccess;
+    ok = ok && hipMemcpy(dn, n, 3 * bytes, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dd, d, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        jxl::launch_epf_quot3(dn, dd, dout, count, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipMemcpy(out, dout, 3 * bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    (void)hipFree(dn);
+    (void)hipFree(dd);
+    (void)hipFree(dout);
+    return ok ? 0 : -1;
 }
 extern "C" int jxl_debug_clock_probe(int device, double us, double* mhz) {
     static hipStream_t s = nullptr;
@@ -1759,6 +1781,9 @@ jxl_status jxl_vardct_set_lfgroup(jxl_ctx* c, const jxl_lfgroup_desc* g) {
     for (int y = 0; y < eh; y++) {  // row copies into the frame-level grids (element-wise over four grids it was 1.1 ms per 4K frame)
         const size_t d = (size_t)(y0 + y) * c->bw + x0, s = (size_t)y * ew;
         memcpy(&c->h_hf_mul[d], g->hf_mul + s, sizeof(int32_t) * ew);
+        int32_t sign = 0;
+        for (int x = 0; x < ew; x++) sign |= g->hf_mul[s + x];
+        c->hf_mul_negative = c->hf_mul_negative || sign < 0;
         memcpy(&c->h_sharp[d], g->sharpness + s, sizeof(int32_t) * ew);
         memcpy(&c->h_sel[d], g->dct_select + s, ew);
         if (!c->sub)
@@ -2420,6 +2445,7 @@ void fill_restore_params(jxl_ctx* c, const jxl_vardct_params& p, bool do_gab, bo
     rp.pq16_thr = do_out ? pq16_thresholds_for(c, p.transfer, out_max_value(p.out_format)) : nullptr;
     rp.srgb16_tab = do_out ? srgb16_table_for(c, p.transfer, out_max_value(p.out_format)) : nullptr;
     memcpy(rp.sharp_lut, p.epf_sharp_lut, sizeof rp.sharp_lut);
+    rp.hf_mul_negative = c->hf_mul_negative;  // (the frame's map; jxl_stage_restore_fused looks at the map it is given)
 }
 
 // the frame pipeline; idct_done: the IDCT stage of this frame has already been enqueued (batched launch); collect: the
@@ -2847,7 +2873,7 @@ jxl_status jxl_vardct_run_batch(jxl_ctx* const* ctxs, int32_t n) {
             bool got = false;
             const jxl_status st = run_frame(ctxs[i], true, &fa[(size_t)i], &got);  // bookkeeping + argument block, no launch
             if (st) return st;
-            all = got && restore_fused_variant(fa[(size_t)i]) == restore_fused_variant(fa[0]);  // !got: no restoration stage enabled
+            all = got && restore_fused_variant(fa[(size_t)i]) == restore_fused_variant(fa[0]) && epf_weights_plain(fa[(size_t)i].p) == epf_weights_plain(fa[0].p);  // !got: no restoration stage enabled
         }
     }
     if (all) {
@@ -2867,7 +2893,7 @@ jxl_status jxl_vardct_run_batch(jxl_ctx* const* ctxs, int32_t n) {
         for (int i = 1; i < n; i++) ctxs[i]->last_launches -= 1;
         for (int i = 0; i < n; i++) {  // every context of the batch reports the shared launch
             ctxs[i]->last_restore_n = 1;
-            ctxs[i]->last_restore_code[0] = restore_fused_variant(fa[0]) | kRestoreBatchBit;
+            ctxs[i]->last_restore_code[0] = restore_launch_code(fa[0].p, false, true);
         }
         c0->last_launches += (int)c0->batch_launches.size();
         return JXL_OK;
@@ -3597,6 +3623,8 @@ jxl_status jxl_stage_restore_fused(jxl_ctx* c, const float* const in[3], float* 
     if (do_epf && (!dhf || !dsh)) return fail(c, JXL_ERR_OOM, "device allocation failed");
     RestoreParams rp{};
     fill_restore_params(c, *p, do_gab, do_epf, do_xyb, false, rp);
+    rp.hf_mul_negative = 0;
+    for (size_t i = 0; do_epf && i < cells; i++) rp.hf_mul_negative |= hf_mul[i] < 0;
     const float* src[3] = {a[0], a[1], a[2]};
     void* dst[3] = {b[0], b[1], b[2]};
     bool ok;
@@ -3612,6 +3640,19 @@ jxl_status jxl_stage_restore_fused(jxl_ctx* c, const float* const in[3], float* 
         ok = launch_restore_fused(src, dst, height, width, dhf, dsh, rp, c->stream);
     }
     if (!ok) return fail(c, JXL_ERR_INVALID_ARGUMENT, "restore: the fused kernel does not take these arguments");
+    // (jxl_debug_last_restore_launches speaks of this call too)
+    if (epf3_split_on() && rp.epf_iters == 3) {
+        RestoreParams ra = rp, rb = rp;
+        ra.epf_iters = 4;
+        ra.xyb = 0;
+        rb.gab = 0; rb.epf_iters = 2;
+        c->last_restore_n = 2;
+        c->last_restore_code[0] = restore_launch_code(ra, false, false);
+        c->last_restore_code[1] = restore_launch_code(rb, false, false);
+    } else {
+        c->last_restore_n = 1;
+        c->last_restore_code[0] = restore_launch_code(rp, false, false);
+    }
     if ((st = finish(c))) return st;
     for (int i = 0; i < 3; i++) HIP_TRY(c, hipMemcpy(out[i], b[i], 4 * n, hipMemcpyDeviceToHost));
     return JXL_OK;

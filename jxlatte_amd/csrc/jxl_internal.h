@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
+#include <cmath>
 #include <stdint.h>
 #include "../../include/jxlatte_amd.h"
 #include "../../include/jxl_transform_types.h"
@@ -338,6 +339,7 @@ struct RestoreParams {
     XybParams xybp;
     float global_scale_f;
     float sharp_lut[8];
+    int hf_mul_negative;  // the hf_mul map the EPF reads holds a negative entry (no bitstream does: HfMul is 1 + u32; synthetic maps may)
     const float* pq_tab;  // device: PQ segment table (null: double-precision PQ)
     const float* srgb8_tab;  // device: sRGB -> 8-bit threshold table (fp_srgb8; null: double-precision pow + quantise)
     const float* pq16_thr;   // device: the kThr16Floats thresholds of PQ -> 16 bit (fp_pq16), then (at kPq8ThrOffset) the 257 of
@@ -361,6 +363,21 @@ struct FusedArgs {
 inline bool restore_fused_covers(int h, int w, int epf_iters, const void* hf_mul, const void* sharpness) {
     return w >= 8 && h >= 8 && (epf_iters <= 0 || (hf_mul && sharpness));
 }
+// The fused kernel divides the EPF sums by a sum of weights it knows to lie in [1, 13] (epf_quot3.h). A weight is max(1 - x, 0),
+// x = dist * border_sad_mul * sigma_scale * inv_sigma, so that needs x >= 0 or NaN, i.e. no negative factor: a parameter set with one
+// (or a NaN, or a -0 that an inversion would turn into -inf) runs the instantiations that keep the plain divisions. Such a launch
+// reports kRestorePlainBit (jxl_debug_last_restore_launches), and the frames of a batch launch agree on it.
+inline bool epf_weights_plain(const RestoreParams& p) {
+    if (p.epf_iters <= 0) return false;
+    auto bad = [](float v) { return !(v >= 0.0f) || std::signbit(v); };
+    bool plain = p.hf_mul_negative != 0 || bad(p.global_scale_f);
+    for (int k = 0; k < 8; k++) plain = plain || bad(p.sharp_lut[k]);
+    for (int i = 0; i < 3; i++) {  // (every iteration index: which of them run depends on epf_iters alone)
+        plain = plain || bad(p.epf[i].sigma_scale) || bad(p.epf[i].border_sad_mul);
+        for (int c = 0; c < 3; c++) plain = plain || bad(p.epf[i].channel_scale[c]);
+    }
+    return plain;
+}
 // false if the configuration is not covered by the fused kernel
 bool fill_restore_fused_args(const float* const in[3], void* const out[3], int h, int w, const int32_t* hf_mul,
                              const int32_t* sharpness, const RestoreParams& p, FusedArgs& a);
@@ -371,6 +388,8 @@ int restore_fused_variant(const FusedArgs& a);  // which kernel instantiation th
 void launch_restore_fused_gen(const FusedArgs* single, const FusedArgs* host_args, const FusedArgs* dev_args, int n, hipStream_t s);
 void launch_restore_fused_q(int sink_kind, const FusedArgs* single, const FusedArgs* host_args, const FusedArgs* dev_args, int n, hipStream_t s);
 void launch_restore_fused_batch(const FusedArgs* host_args, const FusedArgs* dev_args, int n, hipStream_t s);
+// (test hook) epf_quot3 over arrays in device memory: out[k * count + i] = n[k * count + i] / d[i], k = 0..2
+void launch_epf_quot3(const float* n, const float* d, float* out, int64_t count, hipStream_t s);
 // returns false if the configuration is not covered by the fused kernel (caller falls back to stage kernels)
 bool launch_restore_fused(const float* const in[3], void* const out[3], int h, int w, const int32_t* hf_mul,
                           const int32_t* sharpness, const RestoreParams& p, hipStream_t s, bool tiled_in = false);

@@ -25,6 +25,21 @@ bool fill_restore_fused_args(const float* const in[3], void* const out[3], int h
     return true;
 }
 
+namespace {
+__global__ __launch_bounds__(256) void k_epf_quot3(const float* __restrict__ n, const float* __restrict__ d, float* __restrict__ out, int64_t count) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    float q[3];
+    epf_quot3(n[i], n[count + i], n[2 * count + i], d[i], q);
+    out[i] = q[0];
+    out[count + i] = q[1];
+    out[2 * count + i] = q[2];
+}
+}  // namespace
+void launch_epf_quot3(const float* n, const float* d, float* out, int64_t count, hipStream_t s) {
+    hipLaunchKernelGGL(k_epf_quot3, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, n, d, out, count);
+}
+
 
 // which kernel instantiation the arguments select: Gaborish on/off, EPF iterations, sink kind
 // (epf_iters 0..3, or 4 = the 13-tap iteration alone of the two-launch form: three bits)

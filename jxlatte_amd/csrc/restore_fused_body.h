@@ -34,6 +34,7 @@
 #include "jxl_internal.h"
 #include <algorithm>
 #include "restore_sink.h"
+#include "epf_quot3.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -86,7 +87,9 @@ __device__ __forceinline__ float adiff(const float* p, int u, int v, float s) {
 // One EPF iteration (Frame.java:583-635) on a 4x2 patch whose top-left sample is (ry, rx) in region
 // coordinates of src (3 planes, stride SW). Results for the 8 pixels go to res[c][py*4+px].
 // ITER: 0 = 13 taps with cross distances, 1 = 5 taps with cross distances, 2 = 5 taps single-pixel.
-template <int ITER, int SW, int PLANE, int PH, bool CHAINS = true>
+// PLAINDIV: three plain divisions per pixel instead of epf_quot3_patch -- the form for parameter sets with a negative factor in the
+// weights, whose sums of weights are not bounded (see the weights below; epf_weights_plain() chooses on the host).
+template <int ITER, int SW, int PLANE, int PH, bool PLAINDIV = false, bool CHAINS = true>
 __device__ __forceinline__ void epf_patch(const float* __restrict__ src, int ry, int rx, const float* s_inv /*[NP]*/,
                                           const float* bmul /*[NP]*/, const EpfParams& ep, float res[3][4 * PH]) {
     constexpr int NP = 4 * PH;  // pixels per patch
@@ -257,7 +260,13 @@ __device__ __forceinline__ void epf_patch(const float* __restrict__ src, int ry,
             const float d = dist[i][t] * bmul[i];
             const float v = 1.0f - d * ep.sigma_scale * s;
             // max(v, 0): the reference's `v < 0 ? 0 : v` (Frame.java:676-678) for every v that is not NaN or -0. v = 1 - x is -0 for no x,
-            // and NaN only where inv sigma is not finite or the samples are not -- pixels the `skip` select below replaces anyway
+            // and NaN only where inv sigma is not finite or the samples are not -- pixels the `skip` select below replaces anyway.
+            // x = dist * bmul * sigma_scale * s is >= 0 or NaN when channel_scale[], border_sad_mul, sigma_scale and the inverse sigma
+            // are not negative (epf_weights_plain() is false: the !PLAINDIV instantiations), so every weight lies in [0, 1] and
+            // 1 <= sumW <= 1 + NT for EVERY pixel, skipped ones included (their weights are formed like any other before the select
+            // drops the result) -- what epf_quot3_patch needs of its denominators. (Written as min(max(v, 0), 1), the same value then,
+            // the clamp becomes the subtraction's output modifier and the half-rate v_max_f32 goes: measured, no gain that stands
+            // clear of the run-to-run spread -- profiles/experiments/README.md.)
             const float w = __builtin_fmaxf(v, 0.0f);
             dist[i][t] = w;
             sw = sw + w;
@@ -267,6 +276,45 @@ __device__ __forceinline__ void epf_patch(const float* __restrict__ src, int ry,
     // weighted sums per channel (:615-626): tap radius RT2 only
     constexpr int RT2 = ITER == 0 ? 2 : 1;
     constexpr int MW = 4 + 2 * RT2, MH = PH + 2 * RT2;
+    if constexpr (!PLAINDIV) {
+        // the twelve numerators of the patch first, then the quotients: three per pixel by its one denominator (epf_quot3.h)
+        float num[3][NP];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            float nb[MH * MW];
+            const float* pc = src + c * PLANE + (ry - RT2) * SW + (rx - RT2);
+#pragma unroll
+            for (int y = 0; y < MH; y++)
+#pragma unroll
+                for (int x = 0; x < MW; x++) nb[y * MW + x] = pc[y * SW + x];
+#pragma unroll
+            for (int py = 0; py < PH; py++)
+#pragma unroll
+                for (int px = 0; px < 4; px++) {
+                    const int i = py * 4 + px;
+                    const int cy = py + RT2, cx = px + RT2;
+                    float sc = 0.0f + nb[cy * MW + cx] * 1.0f;
+#pragma unroll
+                    for (int t = 0; t < NT; t++) sc = sc + nb[(cy + TY[t]) * MW + cx + TX[t]] * dist[i][t];
+                    num[c][i] = sc;
+                }
+        }
+        float q[3][NP];
+        epf_quot3_patch<NP>(num, sumW, q);
+#pragma unroll
+        for (int py = 0; py < PH; py++)
+#pragma unroll
+            for (int px = 0; px < 4; px++)
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    const int i = py * 4 + px;
+                    // formed unconditionally, as below; a skipped pixel keeps its centre sample
+                    float qv = q[c][i];
+                    asm volatile("" : "+v"(qv));
+                    res[c][i] = skip[i] ? src[c * PLANE + (ry + py) * SW + rx + px] : qv;
+                }
+        return;
+    }
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         float nb[MH * MW];
@@ -342,7 +390,7 @@ __device__ __forceinline__ void patch_sigma(int ry, int rx, const TileCtx& tc, c
 // LAST: results go to the sink (colour + global store). Otherwise IN PLACE: every thread computes the one patch it owns
 // into registers, the workgroup meets at a barrier (all reads of the old values done), then the patches are written
 // back over the input. One LDS buffer instead of two doubles the workgroups a CU can hold.
-template <int ITER, typename G, bool LAST, int PH, bool EDGE, typename Sink>
+template <int ITER, typename G, bool LAST, int PH, bool EDGE, bool PLAINDIV, typename Sink>
 __device__ __forceinline__ void epf_stage(float* buf, int m, const TileCtx& tc, const float* __restrict__ sig, int scy0, int scx0,
                                           const EpfParams& ep, Sink sink) {
     constexpr int SW = G::SW, PLANE = G::PLANE;
@@ -369,7 +417,7 @@ __device__ __forceinline__ void epf_stage(float* buf, int m, const TileCtx& tc, 
             float s_inv[4 * PH], bmul[4 * PH];
             patch_sigma<PH, EDGE>(ry, rx, tc, sig, scy0, scx0, ep, s_inv, bmul);
             float res[3][4 * PH];
-            epf_patch<ITER, SW, PLANE, PH>(buf, ry, rx, s_inv, bmul, ep, res);
+            epf_patch<ITER, SW, PLANE, PH, PLAINDIV>(buf, ry, rx, s_inv, bmul, ep, res);
 #pragma unroll
             for (int py = 0; py < PH; py++) {
                 const int y = ry + py;
@@ -386,7 +434,7 @@ __device__ __forceinline__ void epf_stage(float* buf, int m, const TileCtx& tc, 
         if (act) {
             float s_inv[4 * PH], bmul[4 * PH];
             patch_sigma<PH, EDGE>(ry, rx, tc, sig, scy0, scx0, ep, s_inv, bmul);
-            epf_patch<ITER, SW, PLANE, PH>(buf, ry, rx, s_inv, bmul, ep, res);
+            epf_patch<ITER, SW, PLANE, PH, PLAINDIV>(buf, ry, rx, s_inv, bmul, ep, res);
         }
         __syncthreads();
         if (act) {
@@ -472,7 +520,7 @@ struct OutSink {
     }
 };
 
-template <bool GAB, int ITERS, int SK, int PH, bool EDGE>
+template <bool GAB, int ITERS, int SK, int PH, bool EDGE, bool PLAINDIV>
 __device__ __forceinline__ void restore_epf_stages(const FusedArgs& a, float* cur, int m, const TileCtx& tc, const float* __restrict__ sig,
                                                    int scy0, int scx0);
 
@@ -480,7 +528,7 @@ __device__ __forceinline__ void restore_epf_stages(const FusedArgs& a, float* cu
 // fix transfer function and output format at compile time, SK_GENERIC picks them per sample at run time
 // LAY = the layout of the input planes: 0 raster, 1 cell-tiled (plane_tiled.h: run_frame's pooled planes, written by the IDCT launch of
 // the same call). Only the tile load differs: both loaders leave the same LDS image.
-template <bool GAB, int ITERS, int SK, int PH, int LAY = 0>
+template <bool GAB, int ITERS, int SK, int PH, int LAY = 0, bool PLAINDIV = false>
 __device__ __forceinline__ void restore_fused_body(const FusedArgs& a) {
     using G = Geo<GAB, ITERS>;
     constexpr int NTHR = 512 / PH;
@@ -661,12 +709,12 @@ __device__ __forceinline__ void restore_fused_body(const FusedArgs& a) {
     // interior and edge tiles part here, at one workgroup-uniform branch: the interior path carries no coordinate clamp, no mirror
     // fix-up and no frame-bound test in its sink
     // (float planes only: the quantising sinks keep the one general path -- a second copy of their transfer code costs them registers)
-    if (SK != SK_PLAIN || tc.edge) restore_epf_stages<GAB, ITERS, SK, PH, true>(a, cur, m, tc, sig, scy0, scx0);
-    else restore_epf_stages<GAB, ITERS, SK, PH, false>(a, cur, m, tc, sig, scy0, scx0);
+    if (SK != SK_PLAIN || tc.edge) restore_epf_stages<GAB, ITERS, SK, PH, true, PLAINDIV>(a, cur, m, tc, sig, scy0, scx0);
+    else restore_epf_stages<GAB, ITERS, SK, PH, false, PLAINDIV>(a, cur, m, tc, sig, scy0, scx0);
 }
 
 // the EPF iterations and the sink of one tile (after Gaborish): m = margin of the current region inside the input tile
-template <bool GAB, int ITERS, int SK, int PH, bool EDGE>
+template <bool GAB, int ITERS, int SK, int PH, bool EDGE, bool PLAINDIV>
 __device__ __forceinline__ void restore_epf_stages(const FusedArgs& a, float* cur, int m, const TileCtx& tc, const float* __restrict__ sig,
                                                    int scy0, int scx0) {
     using G = Geo<GAB, ITERS>;
@@ -684,52 +732,56 @@ __device__ __forceinline__ void restore_epf_stages(const FusedArgs& a, float* cu
     }
     if (ITERS == 4) {  // iteration 0 on the whole 64x32 window, straight to the sink
         m += 3;
-        epf_stage<0, G, true, PH, EDGE>(cur, m, tc, sig, scy0, scx0, a.p.epf[0], sink);
+        epf_stage<0, G, true, PH, EDGE, PLAINDIV>(cur, m, tc, sig, scy0, scx0, a.p.epf[0], sink);
         return;
     }
     if (ITERS == 3) {
         m += 3;
-        epf_stage<0, G, false, PH, EDGE>(cur, m, tc, sig, scy0, scx0, a.p.epf[0], sink);
+        epf_stage<0, G, false, PH, EDGE, PLAINDIV>(cur, m, tc, sig, scy0, scx0, a.p.epf[0], sink);
         if (EDGE) mirror_fixup<G, NTHR>(cur, m, G::R1 + G::R2, tc);
         __syncthreads();
     }
     m += 2;
     if (ITERS >= 2) {
-        epf_stage<1, G, false, PH, EDGE>(cur, m, tc, sig, scy0, scx0, a.p.epf[1], sink);
+        epf_stage<1, G, false, PH, EDGE, PLAINDIV>(cur, m, tc, sig, scy0, scx0, a.p.epf[1], sink);
         if (EDGE) mirror_fixup<G, NTHR>(cur, m, G::R2, tc);
         __syncthreads();
         m += 1;
-        epf_stage<2, G, true, PH, EDGE>(cur, m, tc, sig, scy0, scx0, a.p.epf[2], sink);
+        epf_stage<2, G, true, PH, EDGE, PLAINDIV>(cur, m, tc, sig, scy0, scx0, a.p.epf[2], sink);
     } else {
-        epf_stage<1, G, true, PH, EDGE>(cur, m, tc, sig, scy0, scx0, a.p.epf[1], sink);
+        epf_stage<1, G, true, PH, EDGE, PLAINDIV>(cur, m, tc, sig, scy0, scx0, a.p.epf[1], sink);
     }
 }
 
 #define JXL_RESTORE_BOUNDS(ITERS, PH) __launch_bounds__(512 / PH, ITERS >= 3 ? (PH == 1 ? 4 : JXL_EPF3_PH2_WAVES) : PH == 1 ? 8 : 4)
 // occupancy floor: 8 waves per SIMD (64 VGPRs); the 3-iteration variant holds 48 tap distances per patch and spilled 130
 // VGPRs at that bound, so it is allowed 128 registers (4 waves per SIMD; its 43 KB tile allows 3 workgroups per CU anyway)
-template <bool GAB, int ITERS, int SK, int PH, int LAY = 0>
+// PLAINDIV: the EPF tails with plain divisions (epf_patch), for the parameter sets epf_weights_plain() names
+template <bool GAB, int ITERS, int SK, int PH, int LAY = 0, bool PLAINDIV = false>
 __global__ JXL_RESTORE_BOUNDS(ITERS, PH) void k_restore_fused(const FusedArgs a) {
-    restore_fused_body<GAB, ITERS, SK, PH, LAY>(a);
+    restore_fused_body<GAB, ITERS, SK, PH, LAY, PLAINDIV>(a);
 }
 
 // a batch of frames in one launch (jxl_vardct_run_batch): blockIdx.y = frame, argument blocks in device memory read
 // through the constant address space (uniform scalar loads, as from the kernel-argument segment)
-template <bool GAB, int ITERS, int SK>
+template <bool GAB, int ITERS, int SK, bool PLAINDIV = false>
 __global__ JXL_RESTORE_BOUNDS(ITERS, 1) void k_restore_fused_batch(const FusedArgs* __restrict__ args) {
     typedef const __attribute__((address_space(4))) FusedArgs* cargs;
-    restore_fused_body<GAB, ITERS, SK, 1>(*(const FusedArgs*)((cargs)args + blockIdx.y));
+    restore_fused_body<GAB, ITERS, SK, 1, 0, PLAINDIV>(*(const FusedArgs*)((cargs)args + blockIdx.y));
 }
 
-template <bool GAB, int ITERS, int SK, int PH, int LAY = 0>
+template <bool GAB, int ITERS, int SK, int PH, int LAY = 0, bool PLAINDIV = false>
 void launch_tph(const FusedArgs& a, hipStream_t s) {
     using G = Geo<GAB, ITERS>;
+    if constexpr (ITERS > 0 && !PLAINDIV) {  // a negative factor in the weights: the instantiation that keeps `/`
+        if (epf_weights_plain(a.p)) return launch_tph<GAB, ITERS, SK, PH, LAY, true>(a, s);
+    }
     // experiment knob: extra dynamic LDS per workgroup caps the workgroups per CU (160 KiB / size), leaving wave slots to
     // the latency-bound IDCT kernels of other frames in a batch
     static const size_t pad = getenv("JXL_RESTORE_LDS_PAD") ? (size_t)atoi(getenv("JXL_RESTORE_LDS_PAD")) : 0;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_restore_fused<GAB, ITERS, SK, PH, LAY>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_restore_fused<GAB, ITERS, SK, PH, LAY, PLAINDIV>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(G::LDS_BYTES + pad));
         attr_set = true;
     }
@@ -739,18 +791,21 @@ void launch_tph(const FusedArgs& a, hipStream_t s) {
     // stage timing (jxl_vardct_enable_stage_timing): the KERNEL's own start and stop -- what rocprofv3 reports for it -- besides the
     // stage's events on the stream, which also hold the boundary to the launch in front (r6)
     if (g_restore_kernel_ev[0] && g_restore_kernel_ev[1])
-        hipExtLaunchKernelGGL((k_restore_fused<GAB, ITERS, SK, PH, LAY>), grid, dim3(512 / PH), (uint32_t)(G::LDS_BYTES + pad), s, g_restore_kernel_ev[0],
+        hipExtLaunchKernelGGL((k_restore_fused<GAB, ITERS, SK, PH, LAY, PLAINDIV>), grid, dim3(512 / PH), (uint32_t)(G::LDS_BYTES + pad), s, g_restore_kernel_ev[0],
                               g_restore_kernel_ev[1], 0u, a);
     else
-        hipLaunchKernelGGL((k_restore_fused<GAB, ITERS, SK, PH, LAY>), grid, dim3(512 / PH), G::LDS_BYTES + pad, s, a);
+        hipLaunchKernelGGL((k_restore_fused<GAB, ITERS, SK, PH, LAY, PLAINDIV>), grid, dim3(512 / PH), G::LDS_BYTES + pad, s, a);
 }
 
-template <bool GAB, int ITERS, int SK>
+template <bool GAB, int ITERS, int SK, bool PLAINDIV = false>
 void launch_batch_t(const FusedArgs* host_args, const FusedArgs* dev_args, int n, hipStream_t s) {
     using G = Geo<GAB, ITERS>;
+    if constexpr (ITERS > 0 && !PLAINDIV) {  // (the frames of a batch are of one variant, restore_fused_variant: frame 0 speaks for all)
+        if (epf_weights_plain(host_args[0].p)) return launch_batch_t<GAB, ITERS, SK, true>(host_args, dev_args, n, s);
+    }
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_restore_fused_batch<GAB, ITERS, SK>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_restore_fused_batch<GAB, ITERS, SK, PLAINDIV>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
         attr_set = true;
     }
@@ -758,7 +813,7 @@ void launch_batch_t(const FusedArgs* host_args, const FusedArgs* dev_args, int n
     for (int i = 0; i < n; i++)
         max_tiles = std::max(max_tiles, ((host_args[i].W + G::OW - 1) / G::OW) * ((host_args[i].H + G::OH - 1) / G::OH));
     const dim3 grid(((max_tiles + 7) / 8) * 8, n);
-    hipLaunchKernelGGL((k_restore_fused_batch<GAB, ITERS, SK>), grid, dim3(512), G::LDS_BYTES, s, dev_args);
+    hipLaunchKernelGGL((k_restore_fused_batch<GAB, ITERS, SK, PLAINDIV>), grid, dim3(512), G::LDS_BYTES, s, dev_args);
 }
 
 // one sink kind, every (Gaborish, EPF iterations) combination, 4x1 patches
