@@ -1914,6 +1914,11 @@ class JXLDecoder:
                     ref_buffers[a_idx_ref] = np.zeros(canvas.shape, F)
                 ref_buffers[a_idx_ref] = self._to_float(ref_buffers[a_idx_ref], a_depth)
             frame_buffers[a_idx_frame] = self._to_float(frame_buffers[a_idx_frame], a_depth)
+            if not patch:
+                # :455 casts the very object :420 named when this channel is that alpha, so :461 sees a float frame plane. (Under
+                # computePatches the canvas is that object too, :248; patch_type_plan and the calls here still keep the array they
+                # took before the cast -- DESIGN.md section 3, open.)
+                frame_buffer = frame_buffers[fb_idx]
         if has_extra:
             ref_alpha = ref_buffers[a_idx_ref]
             frame_alpha = frame_buffers[a_idx_frame]
@@ -2325,6 +2330,8 @@ class JXLDecoder:
         on = self.device_canvas and not direct
         if on and self._landed is None and self.info.colour_space == CE_GRAY:
             self._landed = "one-colour image"
+        if on and self._landed is None and len(self.canvas) > abi.CANVAS_MAX_PLANES:
+            self._landed = "more than 16 planes"  # (no set holds them: jxl_canvas_create would refuse before blend_type_plan is asked)
         self._patch_sets = False
         if on and fr.num_patches and fr.type != LF_FRAME:
             # blendBuffers casts a patch's reference in place: no set stays up, unless the patches run on the sets themselves

@@ -1,0 +1,578 @@
+"""Seeded images for tests/jxl_writer.py, shared by test_jxl_writer_cpu.py and test_jxl_writer_routes_gpu.py, and what a decoder must
+make of them, computed from the SOURCE arrays alone: the arrays themselves for a lossless single frame, tests/blend_ref.py applied to
+the source frames for a multi-frame image, tests/pixel_ref64.upsample for an upsampled frame, numpy packing for PNG, PFM and tensor
+samples. Nothing here reads a bitstream.
+
+Every source plane can betray an error (test_jxl_writer_cpu.test_the_cases_themselves asserts it): at least 16 distinct values where
+the plane and its depth have room for them, 0 and the depth's maximum present, unequal to each of its other seven orientations where
+the shape lets an orientation move a sample, and a blended frame differs from the canvas under it.
+
+Sizes are the smallest at which the code can still go wrong: 1x1, 1x7, 7x1, 17x33, 64x65 and 129x255 (one row and one lane past the
+64-wide blocks and the squeeze tiles) for single frames, canvases of at most 96x80 for multi-frame images, frames of 5x7 to 24x20
+under upsampling 2, 4 and 8."""
+import types
+
+import numpy as np
+
+import blend_ref as R
+import jxl_writer as W
+import pixel_ref64 as M
+from jxlatte_amd import upweights
+
+F = np.float32
+SIZES = ((1, 1), (1, 7), (7, 1), (17, 33), (64, 65), (129, 255))  # (height, width)
+RCT, PAL, SQ = "rct", "palette", "squeeze"
+
+
+# ---- source planes ------------------------------------------------------------------------------------------------------------
+def plane(rng, h, w, bits):
+    """full range of the depth, 0 and the maximum planted where there is room"""
+    a = rng.integers(0, 1 << bits, (h, w)).astype(np.int32)
+    if a.size >= 2:
+        flat = a.reshape(-1)
+        i, j = rng.choice(a.size, 2, replace=False)
+        flat[i], flat[j] = 0, (1 << bits) - 1
+    return a
+
+
+def few_colours(rng, h, w, n, colours, bits=8):
+    """n planes that together hold `colours` distinct tuples (what a Palette is for), 0 and the maximum among them"""
+    table = rng.integers(0, 1 << bits, (colours, n))
+    table[0], table[1] = 0, (1 << bits) - 1
+    idx = rng.integers(0, colours, (h, w))
+    if h * w >= colours:
+        idx.reshape(-1)[rng.choice(h * w, colours, replace=False)] = np.arange(colours)
+    return [table[idx, c].astype(np.int32) for c in range(n)]
+
+
+def orient(a, o):
+    """JXLCodestreamDecoder.transposeBuffer (JXLCodestreamDecoder.java:43-112) with numpy"""
+    a = np.asarray(a)
+    return np.ascontiguousarray({1: a, 2: a[:, ::-1], 3: a[::-1, ::-1], 4: a[::-1], 5: a.T, 6: a[::-1].T, 7: a[::-1, ::-1].T, 8: a.T[::-1]}[o])
+
+
+def image(planes, bits=8, grey=False, extra=(), orientation=1, **frame):
+    h, w = planes[0].shape
+    return dict(width=w, height=h, bits=bits, grey=grey, extra=list(extra), orientation=orientation, frames=[dict(planes=planes, **frame)])
+
+
+def _alpha(bits=8, assoc=False):
+    return dict(type="alpha", bits=bits, alpha_associated=assoc)
+
+
+def _other(bits=8):
+    return dict(type="other", bits=bits)
+
+
+# ---- single frames ------------------------------------------------------------------------------------------------------------
+def _single():
+    groups = {}
+    rng = np.random.default_rng(7001)
+    g = groups["predictors"] = {}
+    for p in range(14):
+        g["predictor_%d" % p] = image([plane(rng, 17, 33, 8) for _ in range(3)], predictor=p)
+    g["predictor_6_64x65"] = image([plane(rng, 64, 65, 8) for _ in range(3)], predictor=6)
+    g["tree_two_leaves"] = image([plane(rng, 17, 33, 8) for _ in range(4)], extra=[_alpha()], tree=dict(value=1, predictors=(13, 4)))
+    g = groups["rct"] = {}
+    for t in range(42):
+        g["rct_%d" % t] = image([plane(rng, 17, 33, 8) for _ in range(3)], transforms=[(RCT, 0, t)])
+    g["rct_begin_1"] = image([plane(rng, 17, 33, 8) for _ in range(5)], extra=[_alpha(), _other()], transforms=[(RCT, 1, 6 + 7 * 3)])
+    g["rct_begin_2_12bit"] = image([plane(rng, 5, 7, 12) for _ in range(5)], bits=12, extra=[_alpha(12), _other(12)], transforms=[(RCT, 2, 5 + 7)])
+    g = groups["sizes"] = {}
+    for h, w in SIZES:
+        g["plain_%dx%d" % (h, w)] = image([plane(rng, h, w, 8) for _ in range(3)])
+        g["rct_squeeze_%dx%d" % (h, w)] = image([plane(rng, h, w, 8) for _ in range(3)], transforms=[(RCT, 0, 6), (SQ, None)])
+    g = groups["palette_squeeze"] = {}
+    g["palette"] = image(few_colours(rng, 17, 33, 3, 40), transforms=[(PAL, 0, 3, 0, 0)])
+    g["palette_4_with_alpha"] = image(few_colours(rng, 17, 33, 4, 40), extra=[_alpha()], transforms=[(PAL, 0, 4, 0, 0)])
+    g["palette_deltas_pred5"] = image(few_colours(rng, 17, 33, 3, 40), transforms=[(PAL, 0, 3, 6, 5)])
+    g["palette_deltas_pred13_64x65"] = image(few_colours(rng, 64, 65, 3, 300), transforms=[(PAL, 0, 3, 9, 13)])
+    g["palette_deltas_pred6"] = image([plane(rng, 17, 33, 8)] + few_colours(rng, 17, 33, 1, 40) + [plane(rng, 17, 33, 8)],
+                                      transforms=[(PAL, 1, 1, 5, 6)])
+    g["palette_260_colours"] = image(few_colours(rng, 64, 65, 3, 260), transforms=[(PAL, 0, 3, 0, 0)])
+    g["squeeze_default"] = image([plane(rng, 17, 33, 8) for _ in range(3)], transforms=[(SQ, None)])
+    g["squeeze_default_tall"] = image([plane(rng, 33, 17, 8) for _ in range(3)], transforms=[(SQ, None)])
+    g["squeeze_explicit"] = image([plane(rng, 17, 33, 8) for _ in range(3)],
+                                  transforms=[(SQ, [(True, True, 0, 3), (False, False, 1, 2), (False, True, 0, 1)])])
+    g["squeeze_129x255"] = image([plane(rng, 129, 255, 8) for _ in range(3)], transforms=[(SQ, None)])
+    g = groups["chains"] = {}
+    rgb = lambda: [plane(rng, 17, 33, 8) for _ in range(3)]  # noqa: E731
+    g["chain_rct"] = image(rgb(), transforms=[(RCT, 0, 10)])
+    g["chain_squeeze"] = image(rgb(), transforms=[(SQ, [(True, True, 0, 3), (False, True, 0, 3)])])
+    g["chain_rct_squeeze"] = image(rgb(), transforms=[(RCT, 0, 6), (SQ, None)])
+    g["chain_squeeze_rct"] = image(rgb(), transforms=[(SQ, [(True, True, 0, 3)]), (RCT, 0, 6)])
+    g["chain_rct_rct"] = image(rgb() + [plane(rng, 17, 33, 8)], extra=[_alpha()], transforms=[(RCT, 0, 6 + 7), (RCT, 1, 4 + 7 * 5)])
+    g["chain_palette"] = image(few_colours(rng, 17, 33, 3, 30), transforms=[(PAL, 0, 3, 0, 0)])
+    g["chain_palette_palette"] = image(few_colours(rng, 17, 33, 3, 30), transforms=[(PAL, 0, 3, 0, 0), (PAL, 1, 1, 0, 0)])
+    g["chain_rct_palette_squeeze"] = image(few_colours(rng, 17, 33, 3, 30), transforms=[(RCT, 0, 10), (PAL, 0, 3, 0, 0), (SQ, [(True, False, 1, 1)])])
+    g["chain_palette_squeeze_default"] = image(few_colours(rng, 17, 33, 3, 30), transforms=[(PAL, 0, 3, 0, 0), (SQ, None)])
+    g = groups["depths"] = {}
+    for bits in (1, 8, 12, 16):
+        g["depth_%d" % bits] = image([plane(rng, 17, 33, bits) for _ in range(4)], bits=bits, extra=[_alpha(bits)], transforms=[(RCT, 0, 6)] if bits > 1 else [])
+    g["depth_5_alpha_9"] = image([plane(rng, 17, 33, 5) for _ in range(3)] + [plane(rng, 17, 33, 9)], bits=5, extra=[_alpha(9)])
+    g["depth_24"] = image([plane(rng, 5, 7, 24) for _ in range(3)], bits=24, predictor=1)
+    g["depth_31"] = image([plane(rng, 5, 7, 31) for _ in range(3)], bits=31, predictor=0)
+    g = groups["layouts"] = {}
+    for o in range(1, 9):  # grey and RGB, 0 to 4 extra channels, every orientation
+        grey, n_extra = bool(o & 1), (o - 1) % 5
+        extra = [_alpha(8, assoc=bool(o & 2)) if k % 2 == 0 else _other(8) for k in range(n_extra)]
+        g["orientation_%d_%s_%d_extra" % (o, "grey" if grey else "rgb", n_extra)] = image(
+            [plane(rng, 17, 33, 8) for _ in range((1 if grey else 3) + n_extra)], grey=grey, extra=extra, orientation=o)
+    g["grey_rct_on_extras"] = image([plane(rng, 17, 33, 8) for _ in range(4)], grey=True, extra=[_alpha(), _other(), _other()], transforms=[(RCT, 1, 6)])
+    g["group_size_shift_0_128x128"] = image([plane(rng, 128, 128, 8) for _ in range(3)], group_size_shift=0)
+    g["reference_only_then_regular"] = dict(
+        width=33, height=17, bits=8, frames=[dict(planes=[plane(rng, 9, 11, 8) for _ in range(3)], type=W.REFERENCE_ONLY, save_as_reference=2, save_before_ct=True,
+                                                  is_last=False),
+                                             dict(planes=[plane(rng, 17, 33, 8) for _ in range(3)])])
+    g["skip_progressive"] = image([plane(rng, 17, 33, 8) for _ in range(3)], type=W.SKIP_PROGRESSIVE)
+    return groups
+
+
+SINGLE = _single()
+
+
+def single_names():
+    return [(g, n) for g in SINGLE for n in SINGLE[g]]
+
+
+# ---- upsampled frames ---------------------------------------------------------------------------------------------------------
+def _upsampled():
+    rng = np.random.default_rng(7002)
+    out = {}
+    for k, (h, w) in ((2, (5, 7)), (4, (24, 20)), (8, (9, 11)), (2, (24, 20))):
+        pl = [plane(rng, h, w, 8) for _ in range(4)]
+        out["up%d_%dx%d" % (k, h, w)] = dict(width=w * k, height=h * k, bits=8, extra=[_alpha()], frames=[dict(planes=pl, upsampling=k, transforms=[(RCT, 0, 6)])])
+    # an extra channel with a factor of its own: every channel of the stream has the frame's size (ModularStream.java:86-90), so the
+    # alpha comes out twice the image's size and the blend reads its top left part (JXLCodestreamDecoder.java:521-527)
+    pl = [plane(rng, 20, 24, 8) for _ in range(4)]
+    out["ec_up2_colours_1"] = dict(width=24, height=20, bits=8, extra=[_alpha()], frames=[dict(planes=pl, upsampling=1, ec_upsampling=[2])])
+    return out
+
+
+UPSAMPLED = _upsampled()
+
+
+def upsampled_model(im):
+    """[(model, companion)] per plane of a single upsampled frame: castToFloat with the plane's depth (exact in float32), then
+    Frame.performUpsampling in float64 (pixel_ref64.upsample) with the default weights"""
+    fr = im["frames"][0]
+    n_col = len(fr["planes"]) - len(im["extra"])
+    out = []
+    for c, p in enumerate(fr["planes"]):
+        k = fr["upsampling"] if c < n_col else fr.get("ec_upsampling", [fr["upsampling"]] * len(im["extra"]))[c - n_col]
+        depth = im["bits"] if c < n_col else im["extra"][c - n_col]["bits"]
+        if k == 1:  # not upsampled: the integers themselves
+            out.append((orient(p, im.get("orientation", 1)), None))
+            continue
+        f = (p.astype(F) * (F(1) / F((1 << depth) - 1))).astype(F)
+        x, a, _ = M.upsample(f, k, M.up_weights(k, np.asarray(upweights.DEFAULT_UP[k], F)))
+        x, a = x[:im["height"], :im["width"]], a[:im["height"], :im["width"]]
+        out.append((orient(x, im.get("orientation", 1)), orient(a, im.get("orientation", 1))))
+    return out
+
+
+# ---- the decode loop on source frames ----------------------------------------------------------------------------------------
+class ReferenceThrows(Exception):
+    """the reference ends with a NullPointerException here: a blend mode other than REPLACE / ADD whose source slot holds nothing
+    (JXLCodestreamDecoder.java:437-441). Such a stream is no test of anything"""
+
+
+
+def header_objects(im, fr):
+    """the image and frame headers under the names jxlatte_amd.decoder uses (what tests/blend_ref.py reads)"""
+    extra = im.get("extra", [])
+    n = len(extra)
+    info = types.SimpleNamespace(
+        colour_space=R.CE_GRAY if im.get("grey") else 0, num_extra=n, ec_type=[0 if e.get("type", "alpha") == "alpha" else 1 for e in extra],
+        ec_alpha_associated=[bool(e.get("alpha_associated", False)) for e in extra], ec_bits=[e.get("bits", 8) for e in extra],
+        bits_per_sample=im["bits"], height=im["height"], width=im["width"])
+    h, w = fr["planes"][0].shape
+    x0, y0 = fr.get("crop") or (0, 0)
+    b, eb = fr.get("blend", {}), fr.get("ec_blend", [{}] * n)
+    hdr = types.SimpleNamespace(
+        y0=y0, x0=x0, height=h, width=w, upsampling=fr.get("upsampling", 1), blend_mode=b.get("mode", 0), blend_alpha=b.get("alpha", 0),
+        blend_clamp=b.get("clamp", False), blend_source=b.get("source", 0), ec_blend_mode=[e.get("mode", 0) for e in eb],
+        ec_blend_alpha=[e.get("alpha", 0) for e in eb], ec_blend_clamp=[e.get("clamp", False) for e in eb], ec_blend_source=[e.get("source", 0) for e in eb])
+    return info, hdr
+
+
+def typed_planes(im, fr):
+    """a frame's planes as decodeFrame leaves them: int32, or -- where the channel's header says float samples -- the integers
+    CONVERTED to float32, not reinterpreted: Frame.java:443-448 multiplies the decoded int by a float scale factor of 1"""
+    n_col = len(fr["planes"]) - len(im.get("extra", []))
+    is_float = [bool(im.get("exp_bits", 0))] * n_col + [bool(e.get("exp_bits", 0)) for e in im.get("extra", [])]
+    return [np.asarray(p, np.int32).astype(F) if f else np.asarray(p, np.int32) for p, f in zip(fr["planes"], is_float)]
+
+
+def expected_planes(im):
+    """what decode() must return for an image without upsampling: the oriented planes"""
+    if len(im["frames"]) == 1 and not im["frames"][0].get("patches") and im["frames"][0].get("blend", {}).get("mode", 0) == 0:
+        return [orient(p, im.get("orientation", 1)) for p in typed_planes(im, im["frames"][0])]
+    return decode_model(im)
+
+
+def decode_model(im, trace=None):
+    """JXLCodestreamDecoder.decode's loop (JXLCodestreamDecoder.java:599-676) on the source frames: which frame is saved where
+    (:620, :630-633, :656-657), the canvas made at the first frame in its first plane's type (:640-643), copied when a slot
+    other than the one being written holds it (:645-653), blendFrame (tests/blend_ref.py), and the orientation (:670-674). Frames
+    without upsampling, patches, splines or noise. trace, a list, receives (canvas before, frame planes, rectangle) per blend.
+    Raises blend_ref.NotModelled / TypeClash where the blend does."""
+    import patches_model
+    canvas, reference = None, [None] * 4
+    n_extra = len(im.get("extra", []))
+    n = (1 if im.get("grey") else 3) + n_extra
+    for fr in im["frames"]:
+        assert fr.get("upsampling", 1) == 1
+        info, hdr = header_objects(im, fr)
+        planes = [R.Buf(p) for p in typed_planes(im, fr)]
+        ftype = fr.get("type", W.REGULAR)
+        normal = ftype in (W.REGULAR, W.SKIP_PROGRESSIVE)
+        is_last = fr.get("is_last", True) if normal else False
+        slot = fr.get("save_as_reference", 0)
+        save = (slot != 0 or fr.get("duration", 0) == 0) and not is_last
+        if save and fr.get("save_before_ct", False):
+            reference[slot] = [b.copy() for b in planes]
+        if fr.get("patches"):  # computePatches (:634), by the independent model of tests/patches_model.py
+            patches = [dict(ref=p["ref"], y0=p["y0"], x0=p["x0"], h=p["height"], w=p["width"], positions=[(y, x) for x, y in p["positions"]],
+                            blend=[[(b["mode"], b.get("alpha", 0), b.get("clamp", False)) for b in per] for per in p["blend"]]) for p in fr["patches"]]
+            patches_model.compute_patches(info, None, patches, planes, reference)
+        if canvas is None:
+            canvas = [R.Buf(np.zeros((im["height"], im["width"]), planes[0].a.dtype)) for _ in range(n)]
+        if normal:
+            if any(reference[i] is canvas and i != slot for i in range(4)):
+                canvas = [b.copy() for b in canvas]
+            for mode, source in [(hdr.blend_mode, hdr.blend_source)] + list(zip(hdr.ec_blend_mode, hdr.ec_blend_source)):
+                if reference[source] is None and mode not in (W.REPLACE, W.ADD):
+                    raise ReferenceThrows()  # refBuffers[idx] of a null refBuffers (:441)
+            if trace is not None:
+                trace.append(([b.a.copy() for b in canvas], [b.a.copy() for b in planes], hdr))
+            R.blend_frame(info, hdr, canvas, planes, reference)
+        if save and not fr.get("save_before_ct", False):
+            reference[slot] = canvas
+        if is_last or fr.get("duration", 0) != 0:
+            break
+    return [orient(b.a, im.get("orientation", 1)) for b in canvas]
+
+
+# ---- multi-frame images -------------------------------------------------------------------------------------------------------
+MODES = (W.REPLACE, W.ADD, W.BLEND, W.MULADD, W.MULT)
+MULTI_DRAWS, MULTI_SEED = 60, 7100
+
+
+def _alpha_plane(rng, h, w, bits=8):
+    """alpha exactly 0, exactly 1 and strictly between, each on a fair share of the plane"""
+    a = plane(rng, h, w, bits)
+    r = rng.random((h, w))
+    a[r < 0.2], a[r > 0.8] = 0, (1 << bits) - 1
+    return a
+
+
+def _blend(rng, n_extra, mode=None):
+    return dict(mode=int(rng.choice(MODES)) if mode is None else mode, alpha=int(rng.integers(0, n_extra)), clamp=bool(rng.integers(0, 2)),
+                source=int(rng.integers(0, 4)))
+
+
+def draw_multi(seed):
+    """one multi-frame image: two to four frames on a canvas of at most 96x80 with one or two extra channels (the first is alpha,
+    premultiplied or not); the first frame covers the canvas with REPLACE, the others are crops inside, straddling or outside it,
+    with any blend mode per colour set and per extra channel, any alpha channel, clamp, source slot and save slot"""
+    rng = np.random.default_rng(seed)
+    H, Wd = int(rng.integers(20, 81)), int(rng.integers(20, 97))
+    n_extra = int(rng.integers(1, 3))
+    extra = [_alpha(8, assoc=bool(rng.integers(0, 2)))] + [_other(8)] * (n_extra - 1)
+    grey = seed % 7 == 3
+    n_col = 1 if grey else 3
+    n_frames = int(rng.integers(2, 5))
+    frames = []
+    for k in range(n_frames):
+        last = k == n_frames - 1
+        if k == 0:
+            h, w, crop = H, Wd, None
+        else:
+            h, w = int(rng.integers(1, H + 8)), int(rng.integers(1, Wd + 8))
+            kind = rng.integers(0, 8)
+            if kind == 0:  # outside
+                crop = (Wd + int(rng.integers(0, 5)), int(rng.integers(-3, 3))) if rng.integers(0, 2) else (int(rng.integers(-3, 3)), -h - int(rng.integers(0, 5)))
+            elif kind <= 3:  # straddling an edge, negative offsets among them
+                crop = (int(rng.integers(-w + 1, Wd)), int(rng.integers(-h + 1, H)))
+            else:  # inside
+                h, w = min(h, H), min(w, Wd)
+                crop = (int(rng.integers(0, Wd - w + 1)), int(rng.integers(0, H - h + 1)))
+        planes = [plane(rng, h, w, 8) for _ in range(n_col)] + [_alpha_plane(rng, h, w) if e["type"] == "alpha" else plane(rng, h, w, 8) for e in extra]
+        fr = dict(planes=planes, crop=crop, is_last=last, transforms=[(RCT, 0, int(rng.integers(0, 42)))] if not grey and rng.integers(0, 2) else [])
+        if k == 0:
+            fr["blend"], fr["ec_blend"] = dict(mode=W.REPLACE), [dict(mode=W.REPLACE)] * n_extra
+            if not last and rng.integers(0, 3) == 0:
+                fr["save_before_ct"] = True
+        else:
+            fr["blend"], fr["ec_blend"] = _blend(rng, n_extra), [_blend(rng, n_extra) for _ in range(n_extra)]
+        if not last:
+            fr["save_as_reference"] = int(rng.integers(0, 4))
+        frames.append(fr)
+    return dict(width=Wd, height=H, bits=8, grey=grey, extra=extra, orientation=1 + seed % 8 if seed % 5 == 0 else 1, frames=frames)
+
+
+def _multi():
+    """the drawn table. A draw at which the reference itself would throw (blend_ref.TypeClash: planes of two types in one blend
+    function) is no image at all and is drawn again from the next sub-seed; a draw the model does not replay (NotModelled) is
+    kept in LEFT_OUT and counted"""
+    cases, left_out = {}, []
+    for k in range(MULTI_DRAWS):
+        sub = 0
+        while True:
+            im = draw_multi(MULTI_SEED + 1000 * sub + k)
+            try:
+                exp = decode_model(im)
+                break
+            except (R.TypeClash, ReferenceThrows):
+                sub += 1
+            except R.NotModelled:
+                exp = None
+                break
+        if exp is None:
+            left_out.append(k)
+        else:
+            cases["draw_%02d" % k] = im
+    return cases, left_out
+
+
+def _fixed_multi():
+    """the cases the draws do not promise: every blend mode on the colours and on an extra channel, clamp on and off, premultiplied
+    on and off, each slot, a reference that is the canvas itself, save_before_ct"""
+    rng = np.random.default_rng(7200)
+    out = {}
+
+    def base(h=24, w=40, assoc=False, n_extra=2):
+        extra = [_alpha(8, assoc), _alpha(8, not assoc)][:n_extra]
+        pl = [plane(rng, h, w, 8) for _ in range(3)] + [_alpha_plane(rng, h, w) for _ in range(n_extra)]
+        return extra, pl
+    for mode in MODES:
+        for clamp in (False, True):
+            for assoc in (False, True):
+                extra, p0 = base(assoc=assoc)
+                _, p1 = base(h=15, w=22, assoc=assoc)
+                slot = 1 + (mode + clamp + 2 * assoc) % 3
+                # float operands for the modes that need them: a second full frame is blended onto the first, so the canvas saved in
+                # `slot` is float
+                _, pz = base(assoc=assoc)
+                zeroth = dict(planes=pz, is_last=False, save_as_reference=0)
+                first = dict(planes=p0, is_last=False, save_as_reference=slot,
+                             blend=dict(mode=W.BLEND, alpha=0, source=0), ec_blend=[dict(mode=W.BLEND, alpha=0, source=0)] * 2)
+                second = dict(planes=p1, crop=(-4, 12), blend=dict(mode=mode, alpha=1, clamp=clamp, source=slot),
+                              ec_blend=[dict(mode=mode, alpha=1, clamp=clamp, source=slot), dict(mode=W.BLEND if mode != W.BLEND else W.MULT, alpha=0, clamp=clamp, source=slot)])
+                out["mode_%d_clamp_%d_premultiplied_%d" % (mode, clamp, assoc)] = dict(width=40, height=24, bits=8, extra=extra, frames=[zeroth, first, second])
+    # MULADD on the alpha channel that is its own alpha, integer planes all round: the reference casts the frame's alpha in place
+    # (JXLCodestreamDecoder.java:455), the plane in hand with it (:420), so :461 casts the canvas and the reference too and the
+    # alpha comes out float. The decoder's host blend kept its own stale integer array there: found by draw 54, fixed, kept here
+    extra, p0 = base(n_extra=1)
+    _, p1 = base(h=15, w=22, n_extra=1)
+    out["muladd_on_its_own_integer_alpha"] = dict(width=40, height=24, bits=8, extra=extra, frames=[
+        dict(planes=p0, is_last=False, save_as_reference=1),
+        dict(planes=p1, crop=(5, 4), blend=dict(mode=W.REPLACE, source=1), ec_blend=[dict(mode=W.MULADD, alpha=0, clamp=True, source=1)])])
+    # three frames: slot 0 holds the canvas itself while frame 2 blends onto it; frame 0 is also kept before the colour transform in slot 3
+    extra, p0 = base()
+    _, p1 = base(h=10, w=50)
+    _, p2 = base(h=30, w=9)
+    out["the_canvas_as_reference"] = dict(width=40, height=24, bits=8, extra=extra, frames=[
+        dict(planes=p0, is_last=False, save_as_reference=3, save_before_ct=True),
+        dict(planes=p1, crop=(-5, 3), is_last=False, save_as_reference=0, blend=dict(mode=W.ADD, source=3), ec_blend=[dict(mode=W.REPLACE)] * 2),
+        dict(planes=p2, crop=(20, -2), blend=dict(mode=W.ADD, source=0), ec_blend=[dict(mode=W.ADD, source=3), dict(mode=W.ADD, source=0)])])
+    return out
+
+
+MULTI, LEFT_OUT = _multi()
+MULTI_FIXED = _fixed_multi()
+
+
+# ---- samples from source pixels -----------------------------------------------------------------------------------------------
+def cast_to_float(a, depth):
+    """ImageBuffer.castToFloat (ImageBuffer.java:99-127)"""
+    a = np.asarray(a)
+    return a if a.dtype == np.float32 else (a.astype(F) * (F(1) / F((1 << depth) - 1))).astype(F)
+
+
+def depths_of(im):
+    n_col = 1 if im.get("grey") else 3
+    return [im["bits"]] * n_col + [e.get("bits", 8) for e in im.get("extra", [])]
+
+
+def alpha_index(im):
+    idx = [i for i, e in enumerate(im.get("extra", [])) if e.get("type", "alpha") == "alpha"]
+    return idx[0] if idx else -1
+
+
+def png_samples(im, planes):
+    """PNGWriter's samples (PNGWriter.java:66-111 and its row order) of an sRGB-tagged image, which it takes as it is
+    (JXLImage.transform returns such an image unchanged): (bit depth, [H][W][channels] of uint8 or uint16)"""
+    depths, n_col, ai = depths_of(im), 1 if im.get("grey") else 3, alpha_index(im)
+    bit_depth = 16 if im["bits"] > 8 else 8
+    premult = ai >= 0 and bool(im["extra"][ai].get("alpha_associated", False))
+    maxv = (1 << bit_depth) - 1
+    buf = [np.asarray(p) for p in planes]
+    if premult or any(b.dtype == np.int32 and d != bit_depth for b, d in zip(buf, depths)):  # :79-93
+        buf = [cast_to_float(b, d) for b, d in zip(buf, depths)]
+    if premult:  # :94-104
+        with np.errstate(all="ignore"):
+            buf[:n_col] = [(b / buf[n_col + ai]).astype(F) for b in buf[:n_col]]
+    out = []
+    for c in list(range(n_col)) + ([n_col + ai] if ai >= 0 else []):
+        b = buf[c]
+        if b.dtype == np.int32:  # :106-107
+            v = np.clip(b, 0, maxv)
+        else:  # ImageBuffer.castToInt0 (ImageBuffer.java:129-145): (int) of a float: towards zero, NaN is 0, saturating
+            with np.errstate(all="ignore"):
+                f = (b * F(maxv) + F(0.5)).astype(F)
+            v = np.clip(np.nan_to_num(np.trunc(f.astype(np.float64)), nan=0.0, posinf=2.0 ** 31 - 1, neginf=-2.0 ** 31), 0, maxv).astype(np.int64)
+        out.append(v)
+    return bit_depth, np.stack(out, -1).astype(np.uint16 if bit_depth == 16 else np.uint8)
+
+
+def pfm_bytes(im, planes):
+    """PFMWriter.java: the colour planes cast with their depth, rows bottom to top, channels interleaved, big-endian floats"""
+    n_col = 1 if im.get("grey") else 3
+    f = np.stack([cast_to_float(planes[c], im["bits"]) for c in range(n_col)], -1)[::-1]
+    h, w = f.shape[:2]
+    words = np.where(np.isnan(f), np.uint32(0x7FC00000), np.ascontiguousarray(f).view(np.uint32))  # DataOutputStream.writeFloat: floatToIntBits
+    return ("%s\n%d %d\n1.0\n" % ("Pf" if n_col == 1 else "PF", w, h)).encode("ascii") + words.astype(">u4").tobytes()
+
+
+def tensor_float(im, planes):
+    """toTensor(float32, alpha dropped) of an image that is not premultiplied: [C][H][W], each colour plane cast with its depth"""
+    n_col = 1 if im.get("grey") else 3
+    return np.stack([cast_to_float(planes[c], im["bits"]) for c in range(n_col)])
+
+
+# ---- images made for a route --------------------------------------------------------------------------------------------------
+def _routed():
+    rng = np.random.default_rng(7300)
+    out = {}
+    rgb = lambda h=17, w=33: [plane(rng, h, w, 8) for _ in range(3)]  # noqa: E731
+    out["fourteen_extra"] = image([plane(rng, 5, 7, 8) for _ in range(17)], extra=[_alpha()] + [_other()] * 13)
+    out["full_frame_add"] = image(rgb(), blend=dict(mode=W.ADD, source=0))
+    # a patch of a slot that holds nothing is skipped (JXLCodestreamDecoder.java:225-226): the frame stays its source
+    out["patches_of_an_empty_slot"] = image(rgb(), patches=[dict(ref=2, x0=0, y0=0, width=4, height=3, positions=[(1, 2)], blend=[[dict(mode=2)]])])
+    out["two_frames"] = dict(width=33, height=17, bits=8, extra=[_alpha()], frames=[
+        dict(planes=rgb() + [_alpha_plane(rng, 17, 33)], is_last=False, transforms=[(RCT, 0, 6)]),
+        dict(planes=rgb(9, 40) + [_alpha_plane(rng, 9, 40)], crop=(-3, 5), blend=dict(mode=W.BLEND, alpha=0, source=0),
+             ec_blend=[dict(mode=W.BLEND, alpha=0, source=0)], transforms=[(SQ, None)])])
+    # the one accepted route the committed files reach on one frame only: an [RCT, Squeeze] chain onto the resident canvas at a
+    # negative offset, MULADD on an extra channel
+    out["rct_squeeze_negative_offset_muladd"] = dict(width=33, height=17, bits=8, extra=[_alpha(), _other()], frames=[
+        dict(planes=rgb() + [_alpha_plane(rng, 17, 33), plane(rng, 17, 33, 8)], is_last=False),
+        dict(planes=rgb(20, 21) + [_alpha_plane(rng, 20, 21), plane(rng, 20, 21, 8)], crop=(-6, -7), transforms=[(RCT, 0, 6), (SQ, None)],
+             blend=dict(mode=W.MULADD, alpha=0, clamp=True, source=0), ec_blend=[dict(mode=W.BLEND, alpha=0, source=0), dict(mode=W.MULADD, alpha=0, source=0)])])
+    out["grey_two_frames"] = dict(width=33, height=17, bits=8, grey=True, extra=[_alpha()], frames=[
+        dict(planes=[plane(rng, 17, 33, 8), _alpha_plane(rng, 17, 33)], is_last=False),
+        dict(planes=[plane(rng, 9, 12, 8), _alpha_plane(rng, 9, 12)], crop=(4, 5), blend=dict(mode=W.ADD, source=0), ec_blend=[dict(mode=W.ADD, source=0)])])
+
+    def with_patches(grey):
+        n_col = 1 if grey else 3
+        first = [plane(rng, 17, 33, 8) for _ in range(n_col)] + [_alpha_plane(rng, 17, 33)]
+        second = [plane(rng, 17, 33, 7) for _ in range(n_col)] + [_alpha_plane(rng, 17, 33)]
+        for p in second[:n_col]:
+            p.reshape(-1)[:2] = (0, 255)
+        # patch blend mode 2 is ADD (JXLCodestreamDecoder.java:483-484); mode 0 leaves the channel alone (:469-470)
+        patches = [dict(ref=1, x0=3, y0=2, width=9, height=6, positions=[(0, 0), (20, 9), (24, 11)],
+                        blend=[[dict(mode=2), dict(mode=0)], [dict(mode=2), dict(mode=2)], [dict(mode=0), dict(mode=2)]])]
+        return dict(width=33, height=17, bits=8, grey=grey, extra=[_alpha()], frames=[
+            dict(planes=first, is_last=False, save_as_reference=1), dict(planes=second, patches=patches, transforms=[] if grey else [(RCT, 0, 6)])])
+    out["patches_rgb"] = with_patches(False)
+    out["patches_grey"] = with_patches(True)
+    return out
+
+
+ROUTED = _routed()
+
+
+def _floats():
+    """float samples (exp_bits 8, 32 bits): the second tier. The stream holds integers and the reference converts them
+    (typed_planes), so every sample is a whole number; alpha is 0 or 1 here, the fractions are the integer images' business"""
+    rng = np.random.default_rng(7400)
+    out = {}
+    ext = [dict(type="alpha", bits=32, exp_bits=8)]
+
+    def planes(h, w):
+        pl = [rng.integers(-300, 300, (h, w)).astype(np.int32) for _ in range(3)]
+        pl[0].reshape(-1)[:3] = (-(1 << 31), (1 << 31) - 1, (1 << 24) + 1)  # the conversion rounds the last two
+        return pl + [rng.integers(0, 2, (h, w)).astype(np.int32)]
+    out["float_frame"] = dict(width=33, height=17, bits=32, exp_bits=8, extra=ext, frames=[dict(planes=planes(17, 33), predictor=0)])
+    out["float_frame_orientation_6"] = dict(width=7, height=5, bits=32, exp_bits=8, extra=ext, orientation=6, frames=[dict(planes=planes(5, 7), predictor=0)])
+    out["float_two_frames"] = dict(width=33, height=17, bits=32, exp_bits=8, extra=ext, frames=[
+        dict(planes=planes(17, 33), is_last=False, predictor=0),
+        dict(planes=planes(9, 40), crop=(-3, 5), predictor=0, blend=dict(mode=W.BLEND, alpha=0, clamp=True, source=0),
+             ec_blend=[dict(mode=W.BLEND, alpha=0, source=0)])])
+    # (a float extra channel beside integer colours is no case: the canvas is made in the colours' type, JXLCodestreamDecoder.java:640-643,
+    # and its cast with a depth of 32 -- ~(~0 << 32) is 0 in Java -- throws "invalid Max Value", ImageBuffer.java:115-116, in the
+    # reference and in jxl_canvas_cast_planes alike)
+    return out
+
+
+FLOATS = _floats()
+TABLES = dict(SINGLE, upsampled=UPSAMPLED, multi=MULTI, multi_fixed=MULTI_FIXED, routed=ROUTED, floats=FLOATS)
+
+
+def table(name):
+    return TABLES[name]
+
+
+CANVAS = dict(device_canvas=True)
+FRAMES = dict(device_canvas=True, device_frames=True)
+CHAINS = dict(device_canvas=True, device_patches=True, device_patch_sets=True, device_frames=True, device_chains=True)  # test_device_chains_gpu.SWITCHES
+IMAGE = dict(device_image=True)
+CONFIGS = {
+    "default": {}, "image": IMAGE, "canvas": CANVAS, "canvas_frames": FRAMES, "chains": CHAINS, "palette": dict(device_palette=True),
+    "output": dict(device_output=True), "all": dict(CHAINS, device_image=True, device_palette=True, device_output=True),
+}
+
+# every string the route functions of jxlatte_amd/decoder.py can return -> the generated image that produces it in a real decode:
+# (table, image, JXLDecoder switches, where it shows: (stats key, frame index), or ("rule", frame index) for patch_sets_rule, whose
+# answer no stats entry carries: the test listens at the function). "trace": a trace listener is set on the decoder.
+ROUTE_CASES = {
+    "a Palette with weighted-predictor deltas": ("palette_squeeze", "palette_deltas_pred6", dict(IMAGE, device_chains=True), ("image", 0)),
+    "a Palette in the frame-level chain": ("chains", "chain_palette", IMAGE, ("image", 0)),
+    "a frame-level chain that is not one plan ([], [RCT], [Squeeze] or [RCT, Squeeze])": ("chains", "chain_squeeze_rct", IMAGE, ("image", 0)),
+    "colour planes that are not three int32 planes": ("layouts", "orientation_1_grey_0_extra", IMAGE, ("image", 0)),
+    "more planes than a set holds": ("routed", "fourteen_extra", IMAGE, ("image", 0)),
+    "not a regular last frame": ("routed", "two_frames", IMAGE, ("image", 0)),
+    "not the first frame on the canvas, at its origin": ("routed", "two_frames", IMAGE, ("image", 1)),
+    "upsampled, or not of the image's size": ("upsampled", "up2_5x7", IMAGE, ("image", 0)),
+    "a blend mode other than REPLACE": ("routed", "full_frame_add", IMAGE, ("image", 0)),
+    "patches, splines or noise": ("routed", "patches_of_an_empty_slot", IMAGE, ("image", 0)),
+    "not a regular or skip-progressive frame of LF level 0": ("layouts", "reference_only_then_regular", FRAMES, ("frame", 0)),
+    "patches": ("routed", "patches_rgb", FRAMES, ("frame", 1)),
+    "saved before the colour transform": ("multi_fixed", "the_canvas_as_reference", FRAMES, ("frame", 0)),
+    "an extra channel whose upsampling is not the colours'": ("upsampled", "ec_up2_colours_1", FRAMES, ("frame", 0)),
+    "a trace listener is set": ("routed", "two_frames", dict(FRAMES, trace=True), ("frame", 0)),
+    "device_patch_sets is off": ("routed", "patches_rgb", CANVAS, ("rule", 1)),
+    "device_patches is off": ("routed", "patches_rgb", dict(CANVAS, device_patch_sets=True), ("rule", 1)),
+    "the canvas has landed": ("routed", "patches_grey", CHAINS, ("rule", 1)),
+    "device_frames is off": ("routed", "two_frames", {}, ("frame", 0)),
+    "device_canvas is off": ("routed", "two_frames", dict(device_frames=True), ("frame", 0)),
+    "device_output's direct path": ("predictors", "predictor_5", dict(FRAMES, device_output=True), ("frame", 0)),
+    "the canvas has landed (%s)": ("routed", "grey_two_frames", FRAMES, ("frame", 1)),
+    "one-colour image": ("routed", "grey_two_frames", CANVAS, ("canvas", 0)),
+    "a frame with patches": ("routed", "patches_rgb", CANVAS, ("canvas", 1)),
+    "more than 16 planes": ("routed", "fourteen_extra", CANVAS, ("canvas", 0)),
+}
+UNREACHABLE = {
+    "not a Modular frame": "the writer makes Modular frames only; the committed VarDCT samples reach it (test_device_frames_gpu.test_every_other_sample)",
+    "a restoration filter or YCbCr": "the writer's frame header turns Gaborish and EPF off and never sets do_ycbcr (jxl_writer.write_frame_header)",
+    "an XYB image": "the writer's image header says xyb_encoded = false: a lossless integer image has no XYB form",
+    "an upsampling factor other than 1, 2, 4 or 8": "the header codes the factor as 1 << two bits (FrameHeader.java:114): no bitstream holds another",
+    "a frame of another colour count": "a Modular frame of a non-XYB image has the image's colour count (Frame.java:874-877); it takes a VarDCT frame in a grey image",
+}
+# patch_sets_rule's "one-colour image" and "device_canvas is off" share their text with _canvas_route's and _frame_set_route's
+# strings above, which ARE reached; inside patch_sets_rule they are not: both callers ask only with device_canvas on, and a grey
+# image has landed its canvas ("the canvas has landed") before the colour count is looked at.
+
+# the accepted routes: (table, image, switches, {stats key: expected per frame})
+SET = "device set (modular)"
+ACCEPTED = {
+    "device set (modular)": ("routed", "two_frames", FRAMES, dict(frame=[SET, SET], canvas=["device", "device"])),
+    "device set (modular), [RCT, Squeeze] at a negative offset with MULADD": (
+        "routed", "rct_squeeze_negative_offset_muladd", FRAMES, dict(frame=[SET, SET], canvas=["device", "device"])),
+    "canvas device": ("routed", "two_frames", CANVAS, dict(frame=["host: device_frames is off"] * 2, canvas=["device", "device"])),
+    "patches plane sets": ("routed", "patches_rgb", CHAINS, dict(frame=[SET, SET], canvas=["device", "device"], patches_path=[None, "plane sets"])),
+    "a device chain with Palette": ("chains", "chain_rct_palette_squeeze", dict(IMAGE, device_chains=True), dict(image=["device set (modular frame)"], chain_has_palette=[True])),
+    "device set (modular) under upsampling": ("upsampled", "up4_24x20", FRAMES, dict(frame=[SET], canvas=["device"])),
+}
