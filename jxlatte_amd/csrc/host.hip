@@ -162,8 +162,15 @@ struct jxl_ctx {
     bool blocks_cover = false;         // (finalize_tables) every 8x8 cell belongs to exactly one varblock
     std::vector<uint8_t> cell_mark;    // its proof: one mark per cell
     bool llf_alias = false;            // no kernel writes the llf planes for this frame: they ARE the lf planes (no copy)
-    size_t tab_fixed = 0, off_hfm = 0, off_sharp = 0, off_kx = 0, off_kb = 0, off_lf[3] = {0, 0, 0};
+    size_t tab_fixed = 0, off_hfm = 0, off_sharp = 0, off_kx = 0, off_kb = 0, off_lf[3] = {0, 0, 0}, off_isig = 0, off_dq = 0;
     HSpan<int32_t> h_hf_mul, h_sharp;
+    // the EPF's inverse sigma per cell (Frame.java:552-571): a function of the two maps above and of begin_frame's global_scale_f /
+    // epf_sharp_lut, i.e. a constant of the frame description. finalize_tables forms it (build_inv_sigma) and it travels with the
+    // other grids; the fused restoration kernel loads it (inv_sigma_tab: its window of the arena) where it used to divide twice per
+    // cell in every workgroup. (inv_sigma, the buffer of the stage-kernel chain, is written by k_epf_sigma as before.)
+    HSpan<float> h_isig;
+    DevBuf inv_sigma_tab;
+    DevBuf dq_tab;  // likewise the persistent IDCT launch's two dequantisation tables (wg3_build_tables, DevFrame::dq_tab)
     bool hf_mul_negative = false;  // h_hf_mul holds a negative entry (RestoreParams::hf_mul_negative)
     std::vector<int32_t> h_xfy, h_bfy;
     HSpan<float> h_kx, h_kb;
@@ -697,6 +704,18 @@ void tab_bind_fixed(jxl_ctx* c, size_t nc, size_t nt) {
     c->h_kx = {reinterpret_cast<float*>(c->h_tab + c->off_kx), nt};
     c->h_kb = {reinterpret_cast<float*>(c->h_tab + c->off_kb), nt};
     for (int i = 0; i < 3; i++) c->h_lf[i] = {reinterpret_cast<float*>(c->h_tab + c->off_lf[i]), nc};
+    c->h_isig = {reinterpret_cast<float*>(c->h_tab + c->off_isig), nc};
+}
+// Frame.java:552-571, the expression of k_epf_sigma (k_restore.hip) operation for operation: two correctly rounded f32 divisions, so
+// host and device agree bit for bit (this translation unit is built without contraction and without fast-math). A zero sigma gives
+// inf, a negative multiplier a negative value (RestoreParams::hf_mul_negative sends such a frame to the PLAINDIV instantiations).
+// The sharpness is masked like the kernel's old in-tile form masked it: a frame with a value outside 0..7 never reaches the EPF
+// (run_frame reports it), the mask only keeps the look-up inside the table.
+void build_inv_sigma(const int32_t* hf_mul, const int32_t* sharpness, size_t n, float global_scale_f, const float sharp_lut[8], float* out) {
+    for (size_t i = 0; i < n; i++) {
+        const float sigma = global_scale_f * sharp_lut[sharpness[i] & 7] / (float)hf_mul[i];
+        out[i] = 1.0f / sigma;
+    }
 }
 // diagnostics (JXL_PREPARE_TIMING): host time of a call's sections, to stderr
 struct SectTimer {
@@ -725,6 +744,8 @@ bool tab_begin_frame(jxl_ctx* c, size_t nc, size_t nt) {
     c->off_kx = o; o = tab_up(o + 4 * nt);
     c->off_kb = o; o = tab_up(o + 4 * nt);
     for (int i = 0; i < 3; i++) { c->off_lf[i] = o; o = tab_up(o + 4 * nc); }
+    c->off_isig = o; o = tab_up(o + 4 * nc);
+    c->off_dq = o; o = tab_up(o + 4 * (size_t)kWg3DqTabFloats);
     c->tab_fixed = o;
     tab_wait(c);  // the previous frame's transfer may still be reading the buffer
     tm.mark("tab_wait");
@@ -1025,6 +1046,9 @@ jxl_status finalize_tables(jxl_ctx* c) {
             c->h_kb[i] = c->p.base_corr_b + qb;
         }
     }
+    build_inv_sigma(c->h_hf_mul.data(), c->h_sharp.data(), nc, c->p.global_scale_f, c->p.epf_sharp_lut, c->h_isig.data());
+    wg3_build_tables(c->p.quant_bias, c->p.quant_bias_numerator, c->p.scale_factor, reinterpret_cast<float*>(c->h_tab + c->off_dq));
+    mark("CfL factors, inverse sigma, dequantisation tables");
     // the variable sections behind the fixed ones: block records, special-kernel items, item lists
     size_t o = c->tab_fixed;
     const size_t off_blocks = o, n_blk = sizeof(DevBlock) * c->h_blocks.size();
@@ -1062,6 +1086,8 @@ jxl_status finalize_tables(jxl_ctx* c) {
         c->xfy.view(d + c->off_kx, 4 * nt);
         c->bfy.view(d + c->off_kb, 4 * nt);
         for (int i = 0; i < 3; i++) c->lf[i].view(d + c->off_lf[i], 4 * nc);
+        c->inv_sigma_tab.view(d + c->off_isig, 4 * nc);
+        c->dq_tab.view(d + c->off_dq, 4 * (size_t)kWg3DqTabFloats);
         c->blocks.view(d + off_blocks, std::max<size_t>(16, n_blk));
         c->items.view(d + off_items, std::max<size_t>(16, n_items));
         for (int k = 0; k < 2; k++) c->wg3_items[k].view(d + off_wg3[k], sizeof(int) * wg3_tab[k].size());
@@ -1129,6 +1155,7 @@ void fill_dev_frame(const jxl_ctx* c, DevFrame& f) {
     f.weights_t = c->weights_t.as<float>();
     memcpy(f.woffs, c->woffs, sizeof f.woffs);
     f.lut = c->lut.as<float>();
+    f.dq_tab = c->dq_tab.as<float>();
     f.quant_bias_numerator = c->p.quant_bias_numerator;
     f.base_corr_x = c->p.base_corr_x;
     f.base_corr_b = c->p.base_corr_b;
@@ -1351,6 +1378,25 @@ extern "C" int jxl_debug_last_restore_launches(const jxl_ctx* c, int32_t codes[2
     for (int i = 0; i < 2 && codes; i++) codes[i] = i < c->last_restore_n ? c->last_restore_code[i] : 0;
     return c->last_restore_n;
 }
+// Test hooks (tests/test_frame_constants_{cpu,gpu}.py), not part of the C-ABI of include/jxlatte_amd.h. The first is the host
+// builder of the inverse-sigma plane on caller arrays, no device needed. The second reads back the plane of the open frame as the
+// fused restoration kernel will load it (the frame's tables are finalised first if they are not): returns the number of cells, or
+// -1 (no open frame, `cap` too small, or an error -- jxl_last_error then).
+extern "C" void jxl_debug_build_inv_sigma(const int32_t* hf_mul, const int32_t* sharpness, int64_t n, float global_scale_f,
+                                          const float sharp_lut[8], float* out) {
+    if (hf_mul && sharpness && sharp_lut && out && n > 0) build_inv_sigma(hf_mul, sharpness, (size_t)n, global_scale_f, sharp_lut, out);
+}
+// ... and the third the host builder of the persistent IDCT launch's tables (kWg3DqTabFloats = 1152 floats), no device needed
+extern "C" void jxl_debug_wg3_tables(const float quant_bias[3], float quant_bias_numerator, const float scale_factor[3], float* out) {
+    if (quant_bias && scale_factor && out) wg3_build_tables(quant_bias, quant_bias_numerator, scale_factor, out);
+}
+extern "C" int64_t jxl_debug_read_inv_sigma(jxl_ctx* c, float* out, int64_t cap) {
+    if (!c || !out || bind(c) != JXL_OK || !c->frame_open) return -1;
+    const int64_t nc = (int64_t)c->bh * c->bw;
+    if (cap < nc || finalize_tables(c) != JXL_OK || !c->inv_sigma_tab.p) return -1;
+    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out, c->inv_sigma_tab.p, 4 * (size_t)nc, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return nc;
+}
 // Test hook (tests/test_palette_gpu.py) and the decoder's statistics: the kernel launches of the context's last jxl_stage_palette
 // that ran (0: none yet; 1: the lookup kernel alone; 2: the chain kernel behind it) and its pixels with index < nb_deltas. Not
 // part of the C-ABI of include/jxlatte_amd.h.
@@ -1553,7 +1599,7 @@ void jxl_ctx_destroy(jxl_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     pool_detach(c);  // (a pooled set this context was the last user of goes here, behind the synchronise above)
     release_private_planes(c);
-    DevBuf* all[] = {&c->lut, &c->hf_mul, &c->sharp, &c->xfy, &c->bfy, &c->weights, &c->weights_t, &c->inv_sigma, &c->blocks, &c->items,
+    DevBuf* all[] = {&c->lut, &c->hf_mul, &c->sharp, &c->xfy, &c->bfy, &c->weights, &c->weights_t, &c->inv_sigma, &c->inv_sigma_tab, &c->dq_tab, &c->blocks, &c->items,
                      &c->bad_flag};
     for (DevBuf* b : all) b->release();
     for (int i = 0; i < 3; i++) {
@@ -2468,7 +2514,7 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
     // (they ping-pong through it), chroma-subsampled frames (the upsampling swaps the plane sets), batched runs.
     const size_t npx = (size_t)c->W * c->H;
     const bool fused_single = (do_gab || do_epf || do_xyb || do_out) && !(epf3_split_on() && do_epf && p.epf_iters == 3) &&
-                              restore_fused_covers(c->H, c->W, do_epf ? p.epf_iters : 0, c->hf_mul.p, c->sharp.p);
+                              restore_fused_covers(c->H, c->W, do_epf ? p.epf_iters : 0, c->inv_sigma_tab.p);
     const bool shared = may_share && !idct_done && !collect && (p.stages & JXL_STAGE_IDCT) && !c->sub && c->blocks_cover && fused_single &&
                         pool_of(c) != nullptr;
     // Layout of a pooled set (plane_tiled.h): cell-tiled when the whole of it is written by the ONE 256-thread IDCT launch and read by a
@@ -2634,7 +2680,7 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
             return JXL_OK;
         }
         if (collect) {
-            fused = fill_restore_fused_args(src, dst, c->H, c->W, c->hf_mul.as<int32_t>(), c->sharp.as<int32_t>(), rp, *collect);
+            fused = fill_restore_fused_args(src, dst, c->H, c->W, c->inv_sigma_tab.as<float>(), rp, *collect);
             if (collected) *collected = fused;
             if (fused) {  // (jxl_vardct_run_batch marks it as the batch's launch, or runs the frame again on its own)
                 c->last_restore_n = 1;
@@ -2649,8 +2695,8 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
             if (!do_out)
                 for (int i = 0; i < 3; i++) dst[i] = cur[i];  // the input planes are dead once the first launch has read them
             const float* mids[3] = {oth[0], oth[1], oth[2]};
-            fused = launch_restore_fused(src, mid, c->H, c->W, c->hf_mul.as<int32_t>(), c->sharp.as<int32_t>(), ra, s) &&
-                    launch_restore_fused(mids, dst, c->H, c->W, c->hf_mul.as<int32_t>(), c->sharp.as<int32_t>(), rb, s);
+            fused = launch_restore_fused(src, mid, c->H, c->W, c->inv_sigma_tab.as<float>(), ra, s) &&
+                    launch_restore_fused(mids, dst, c->H, c->W, c->inv_sigma_tab.as<float>(), rb, s);
             if (fused) {
                 launches++;
                 c->last_restore_n = 2;
@@ -2662,7 +2708,7 @@ jxl_status run_frame(jxl_ctx* c, bool idct_done, FusedArgs* collect = nullptr, b
                 g_restore_kernel_ev[0] = c->kev[c->ev_runs % jxl_ctx::kEvSlots][0];
                 g_restore_kernel_ev[1] = c->kev[c->ev_runs % jxl_ctx::kEvSlots][1];
             }
-            fused = launch_restore_fused(src, dst, c->H, c->W, c->hf_mul.as<int32_t>(), c->sharp.as<int32_t>(), rp, s, tiled);
+            fused = launch_restore_fused(src, dst, c->H, c->W, c->inv_sigma_tab.as<float>(), rp, s, tiled);
             g_restore_kernel_ev[0] = g_restore_kernel_ev[1] = nullptr;
             c->kev_valid = c->timing && fused;
             if (fused) {
@@ -3621,6 +3667,12 @@ jxl_status jxl_stage_restore_fused(jxl_ctx* c, const float* const in[3], float* 
     int32_t* dhf = do_epf ? t.up(hf_mul, cells) : nullptr;
     int32_t* dsh = do_epf ? t.up(sharpness, cells) : nullptr;
     if (do_epf && (!dhf || !dsh)) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    // no frame description behind this call: the inverse-sigma plane comes from the stage kernel (k_epf_sigma: the expression of
+    // build_inv_sigma; the sharpness values were checked above, so its range test never fires)
+    float* dsig = do_epf ? t.up<float>(nullptr, cells) : nullptr;
+    if (do_epf && !dsig) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    if (do_epf)
+        launch_epf_sigma(dhf, dsh, (height + 7) >> 3, (width + 7) >> 3, p->global_scale_f, p->epf_sharp_lut, dsig, c->bad_flag.as<int>(), c->stream);
     RestoreParams rp{};
     fill_restore_params(c, *p, do_gab, do_epf, do_xyb, false, rp);
     rp.hf_mul_negative = 0;
@@ -3635,9 +3687,9 @@ jxl_status jxl_stage_restore_fused(jxl_ctx* c, const float* const in[3], float* 
         rb.gab = 0; rb.epf_iters = 2;
         void* mid[3] = {m[0], m[1], m[2]};
         const float* mids[3] = {m[0], m[1], m[2]};
-        ok = launch_restore_fused(src, mid, height, width, dhf, dsh, ra, c->stream) && launch_restore_fused(mids, dst, height, width, dhf, dsh, rb, c->stream);
+        ok = launch_restore_fused(src, mid, height, width, dsig, ra, c->stream) && launch_restore_fused(mids, dst, height, width, dsig, rb, c->stream);
     } else {
-        ok = launch_restore_fused(src, dst, height, width, dhf, dsh, rp, c->stream);
+        ok = launch_restore_fused(src, dst, height, width, dsig, rp, c->stream);
     }
     if (!ok) return fail(c, JXL_ERR_INVALID_ARGUMENT, "restore: the fused kernel does not take these arguments");
     // (jxl_debug_last_restore_launches speaks of this call too)

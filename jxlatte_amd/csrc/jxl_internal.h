@@ -58,6 +58,7 @@ struct DevFrame {
     const float* weights_t;   // same offsets, every matrix transposed (for flip() blocks: coalesced reads)
     int32_t woffs[51];
     const float* lut;         // cosine LUT, all sizes; size s=1<<l starts at lut_off(l)
+    const float* dq_tab;      // [kWg3DqTabFloats]: the dequantisation tables of the persistent launch (wg3_build_tables), per frame
     float scale_factor[3];
     float quant_bias[3];
     float quant_bias_numerator;
@@ -131,6 +132,12 @@ struct Wg3Args {
     int tiled; // the output planes are cell-tiled (plane_tiled.h): the 256-thread class only, pooled planes only (run_frame)
 };
 
+// The two tables the persistent launch keeps in LDS, as a function of the seven floats they depend on: [3][128] dequantised value of
+// q = -64 .. 63 (entry q + 64: 0, +-quantBias[c], (float)q - quantBiasNumerator / (float)q, HFCoefficients.java:309-315), then
+// [3][256] scaleFactor[c] / (float)m for hfMultiplier m = 1 .. 255 (entry 0 as m = 1; :299). Built on the host once per frame
+// description with the expressions the workgroups used to evaluate themselves (correctly rounded f32 division on both sides).
+constexpr int kWg3DqTabFloats = 3 * 128 + 3 * 256;
+void wg3_build_tables(const float quant_bias[3], float quant_bias_numerator, const float scale_factor[3], float* out /* [kWg3DqTabFloats] */);
 // the item list of one class's segments in spatial order, dealt to the XCDs in runs (host side)
 void wg3_item_table(const DevBlock* host_blocks, int frame_bw, const IdctSegment* segs, int n_seg, int which, const int32_t* woffs,
                     std::vector<int>& out, int grid);
@@ -351,17 +358,17 @@ struct RestoreParams {
 struct FusedArgs {
     const float* in[3];
     void* out[3];
-    const int32_t* hf_mul;
-    const int32_t* sharpness;
+    const float* inv_sigma;  // [ceil(H / 8)][bw] inverse sigma per cell (Frame.java:552-571): the frame's plane of the table arena
+                             // (finalize_tables), or what k_epf_sigma made of maps handed over as device planes; null without EPF
     int W, H, bw;
     int tiled;  // in[] are cell-tiled planes (plane_tiled.h): run_frame's pooled planes only; epf_iters <= 2
     RestoreParams p;
 };
 // what the fused restoration kernel takes: planes of at least one cell (its mirror fix-up assumes at most one reflection within the
-// halo) and, when EPF iterations run, both cell maps. fill_restore_fused_args declines everything else; run_frame asks the same
-// question before it decides where the IDCT output goes
-inline bool restore_fused_covers(int h, int w, int epf_iters, const void* hf_mul, const void* sharpness) {
-    return w >= 8 && h >= 8 && (epf_iters <= 0 || (hf_mul && sharpness));
+// halo) and, when EPF iterations run, the inverse-sigma plane of the cells. fill_restore_fused_args declines everything else; run_frame
+// asks the same question before it decides where the IDCT output goes
+inline bool restore_fused_covers(int h, int w, int epf_iters, const void* inv_sigma) {
+    return w >= 8 && h >= 8 && (epf_iters <= 0 || inv_sigma);
 }
 // The fused kernel divides the EPF sums by a sum of weights it knows to lie in [1, 13] (epf_quot3.h). A weight is max(1 - x, 0),
 // x = dist * border_sad_mul * sigma_scale * inv_sigma, so that needs x >= 0 or NaN, i.e. no negative factor: a parameter set with one
@@ -379,8 +386,8 @@ inline bool epf_weights_plain(const RestoreParams& p) {
     return plain;
 }
 // false if the configuration is not covered by the fused kernel
-bool fill_restore_fused_args(const float* const in[3], void* const out[3], int h, int w, const int32_t* hf_mul,
-                             const int32_t* sharpness, const RestoreParams& p, FusedArgs& a);
+bool fill_restore_fused_args(const float* const in[3], void* const out[3], int h, int w, const float* inv_sigma, const RestoreParams& p,
+                             FusedArgs& a);
 // (stage timing) the events the next single-frame launch of the fused restoration kernel records its own start / stop into; else null
 extern thread_local hipEvent_t g_restore_kernel_ev[2];
 int restore_fused_variant(const FusedArgs& a);  // which kernel instantiation the arguments select
@@ -391,8 +398,8 @@ void launch_restore_fused_batch(const FusedArgs* host_args, const FusedArgs* dev
 // (test hook) epf_quot3 over arrays in device memory: out[k * count + i] = n[k * count + i] / d[i], k = 0..2
 void launch_epf_quot3(const float* n, const float* d, float* out, int64_t count, hipStream_t s);
 // returns false if the configuration is not covered by the fused kernel (caller falls back to stage kernels)
-bool launch_restore_fused(const float* const in[3], void* const out[3], int h, int w, const int32_t* hf_mul,
-                          const int32_t* sharpness, const RestoreParams& p, hipStream_t s, bool tiled_in = false);
+bool launch_restore_fused(const float* const in[3], void* const out[3], int h, int w, const float* inv_sigma, const RestoreParams& p,
+                          hipStream_t s, bool tiled_in = false);
 // the input layouts the fused kernel is instantiated for: cell-tiled planes feed the 4x1-patch variants without the 13-tap iteration
 // (false under JXL_RESTORE_PH=2, whose 4x2-patch kernels read raster). run_frame asks before it picks the layout of a pooled set.
 bool restore_fused_takes_tiled(int epf_iters);

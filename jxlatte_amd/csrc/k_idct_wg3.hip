@@ -75,6 +75,7 @@ __constant__ float kLlfScale3[32] = JXL_LLF_SCALE_INIT;
 constexpr int kWg3QTab = 3 * 128;  // dequantisation table: [3][128], entry q + 64 for q = -64 .. 63
 constexpr int kWg3AuxFloats = kWg3QTab + 104 + 192;
 constexpr int kWg3SfEntries = 256;
+static_assert(kWg3DqTabFloats == kWg3QTab + 3 * kWg3SfEntries, "DevFrame::dq_tab holds both tables");
 
 // Diagnostic build only (-DJXL_STAMPS): lane 0 of every workgroup records s_memtime at the phase boundaries of its first
 // two items (rows 2*wg and 2*wg+1 of the stamp buffer)
@@ -1058,21 +1059,19 @@ __device__ __forceinline__ void wg3_body(const Wg3Args& a) {
     if (cur.type < 0) return;
     STAMP3_LIFE(0, __builtin_amdgcn_s_memtime());
     float* img = lds;
-    float* qtab = lds + a.img_floats;  // [3][128]: entry q + 64 = 0, +-quantBias[c], (float)q - qbn / (float)q (HFCoefficients.java:309-315)
-    for (int i = tid0; i < kWg3QTab; i += T) {
-        const int c = i >> 7, q = (i & 127) - 64;
-        qtab[i] = q == 0 ? 0.0f : q == 1 ? a.f.quant_bias[c] : q == -1 ? -a.f.quant_bias[c] : (float)q - a.f.quant_bias_numerator / (float)q;
-    }
+    // [3][128]: entry q + 64 = 0, +-quantBias[c], (float)q - qbn / (float)q (HFCoefficients.java:309-315). Constants of the frame:
+    // wg3_build_tables forms them once on the host, every workgroup copies them (it used to divide ~4.5 times per lane for them)
+    float* qtab = lds + a.img_floats;
+    const float* __restrict__ dqt = a.f.dq_tab;
+    for (int i = tid0; i < kWg3QTab; i += T) qtab[i] = dqt[i];
     // finalizeLLF inside the item: the cosine tables of 2, 4 and 8 points (the first 70 floats of the LUT), the LLF scale
     // table and one LF sample per LLF coefficient of the coming item (lf_patch, written when the item's prefetch has landed)
     float* aux = qtab + kWg3QTab;
     float* lf_patch = aux + 104;
     if (tid0 < 70) aux[tid0] = a.f.lut[tid0];
     else if (tid0 >= 72 && tid0 < 104) aux[tid0] = kLlfScale3[tid0 - 72];
-    for (int i = tid0; i < 3 * kWg3SfEntries; i += T) {  // hfMultiplier values 1 .. 255 (larger ones divide in place)
-        const int c = i / kWg3SfEntries, m = i % kWg3SfEntries;
-        qtab[kWg3AuxFloats + i] = a.f.scale_factor[c] / (float)(m > 0 ? m : 1);
-    }
+    for (int i = tid0; i < 3 * kWg3SfEntries; i += T)  // scaleFactor[c] / m for hfMultiplier values 1 .. 255 (larger ones divide in place)
+        qtab[kWg3AuxFloats + i] = dqt[kWg3QTab + i];
     Raw<NG, WS> raw{};  // (zeroed once: the prefetch leaves the groups outside an item alone)
     Recs<NG> rc;
     load_recs<T, NG>(a, cur, tid0, rc);
@@ -1170,6 +1169,17 @@ extern "C" int jxl_debug_set_stamps3(void* dev_ptr) {
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_stamps3), &p, sizeof p);
 }
 #endif
+
+void wg3_build_tables(const float quant_bias[3], float quant_bias_numerator, const float scale_factor[3], float* out) {
+    for (int i = 0; i < kWg3QTab; i++) {
+        const int c = i >> 7, q = (i & 127) - 64;
+        out[i] = q == 0 ? 0.0f : q == 1 ? quant_bias[c] : q == -1 ? -quant_bias[c] : (float)q - quant_bias_numerator / (float)q;
+    }
+    for (int i = 0; i < 3 * kWg3SfEntries; i++) {
+        const int c = i / kWg3SfEntries, m = i % kWg3SfEntries;
+        out[kWg3QTab + i] = scale_factor[c] / (float)(m > 0 ? m : 1);
+    }
+}
 
 // every type but the 128/256-edge ones (r6: the special 8x8 types too)
 bool wg3_handles(int type) { return JXL_TT[type].ph < 128 && JXL_TT[type].pw < 128; }

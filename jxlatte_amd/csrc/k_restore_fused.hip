@@ -8,15 +8,14 @@
 
 namespace jxl {
 
-bool fill_restore_fused_args(const float* const in[3], void* const out[3], int h, int w, const int32_t* hf_mul,
-                             const int32_t* sharpness, const RestoreParams& p, FusedArgs& a) {
-    if (!restore_fused_covers(h, w, p.epf_iters, hf_mul, sharpness)) return false;
+bool fill_restore_fused_args(const float* const in[3], void* const out[3], int h, int w, const float* inv_sigma, const RestoreParams& p,
+                             FusedArgs& a) {
+    if (!restore_fused_covers(h, w, p.epf_iters, inv_sigma)) return false;
     for (int c = 0; c < 3; c++) {
         a.in[c] = in[c];
         a.out[c] = out[c];
     }
-    a.hf_mul = hf_mul;
-    a.sharpness = sharpness;
+    a.inv_sigma = inv_sigma;
     a.W = w;
     a.H = h;
     a.bw = (w + 7) >> 3;
@@ -61,10 +60,10 @@ static bool restore_ph2() {
 }
 bool restore_fused_takes_tiled(int epf_iters) { return epf_iters >= 0 && epf_iters <= 2 && !restore_ph2(); }
 
-bool launch_restore_fused(const float* const in[3], void* const out[3], int h, int w, const int32_t* hf_mul,
-                          const int32_t* sharpness, const RestoreParams& p, hipStream_t s, bool tiled_in) {
+bool launch_restore_fused(const float* const in[3], void* const out[3], int h, int w, const float* inv_sigma, const RestoreParams& p,
+                          hipStream_t s, bool tiled_in) {
     FusedArgs a;
-    if (!fill_restore_fused_args(in, out, h, w, hf_mul, sharpness, p, a)) return false;
+    if (!fill_restore_fused_args(in, out, h, w, inv_sigma, p, a)) return false;
     if (tiled_in && !(restore_fused_takes_tiled(p.epf_iters) && plane_tiled_ok(w, h))) return false;  // (run_frame asks the same before it picks the layout)
     a.tiled = tiled_in ? 1 : 0;
     const int sk = sink_kind_of(p);

@@ -264,10 +264,11 @@ __device__ __forceinline__ void epf_patch(const float* __restrict__ src, int ry,
             // x = dist * bmul * sigma_scale * s is >= 0 or NaN when channel_scale[], border_sad_mul, sigma_scale and the inverse sigma
             // are not negative (epf_weights_plain() is false: the !PLAINDIV instantiations), so every weight lies in [0, 1] and
             // 1 <= sumW <= 1 + NT for EVERY pixel, skipped ones included (their weights are formed like any other before the select
-            // drops the result) -- what epf_quot3_patch needs of its denominators. (Written as min(max(v, 0), 1), the same value then,
-            // the clamp becomes the subtraction's output modifier and the half-rate v_max_f32 goes: measured, no gain that stands
-            // clear of the run-to-run spread -- profiles/experiments/README.md.)
-            const float w = __builtin_fmaxf(v, 0.0f);
+            // drops the result) -- what epf_quot3_patch needs of its denominators.
+            // !PLAINDIV: v <= 1 or NaN, so min(max(v, 0), 1) == max(v, 0) bit for bit (for NaN both give 0: v_max_f32 is maxnum, and the
+            // code objects run with DX10_CLAMP); hipcc folds that form into the subtraction's clamp output modifier and the half-rate
+            // v_max_f32 goes
+            const float w = !PLAINDIV ? __builtin_fminf(__builtin_fmaxf(v, 0.0f), 1.0f) : __builtin_fmaxf(v, 0.0f);
             dist[i][t] = w;
             sw = sw + w;
         }
@@ -556,17 +557,14 @@ __device__ __forceinline__ void restore_fused_body(const FusedArgs& a) {
     tc.iy0 = oy - G::RT;
     tc.edge = tc.ix0 < 0 || tc.iy0 < 0 || tc.ix0 + G::IW > W || tc.iy0 + G::IH > H;
 
-    // inverse sigma per cell (Frame.java:552-571)
+    // inverse sigma per cell (Frame.java:552-571): a constant of the frame, formed once per frame description (host.hip:
+    // build_inv_sigma, or k_epf_sigma where the maps arrive as device planes) -- the window under the tile is only loaded
     const int scy0 = max(tc.iy0, 0) >> 3, scx0 = max(tc.ix0, 0) >> 3;
-    if (ITERS > 0) {
-        const int cy = scy0 + ((threadIdx.x & 255) >> 4), cx = scx0 + (threadIdx.x & 15);
+    if (ITERS > 0 && threadIdx.x < 256) {
+        const int cy = scy0 + (threadIdx.x >> 4), cx = scx0 + (threadIdx.x & 15);
         float v = 0.0f;
-        if (cy < ((H + 7) >> 3) && cx < a.bw) {
-            const int sharp = a.sharpness[cy * a.bw + cx] & 7;
-            const float sigma = a.p.global_scale_f * a.p.sharp_lut[sharp] / (float)a.hf_mul[cy * a.bw + cx];
-            v = 1.0f / sigma;
-        }
-        sig[threadIdx.x & 255] = v;
+        if (cy < ((H + 7) >> 3) && cx < a.bw) v = a.inv_sigma[cy * a.bw + cx];
+        sig[threadIdx.x] = v;
     }
     // load the input tile: clamped coordinates feed Gab, mirrored ones feed EPF directly. Flat row-major
     // walk with incrementally updated (y, x) and 32-bit plane offsets (scalar base + 32-bit lane offset).
