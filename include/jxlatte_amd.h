@@ -914,6 +914,43 @@ jxl_status jxl_planes_tensor_samples(jxl_ctx* ctx, const void* alpha, const jxl_
  * jxl_canvas_png_samples' checks of the set's geometry and tags: nothing crosses the bus in either direction. */
 jxl_status jxl_canvas_tensor_samples(jxl_ctx* ctx, int32_t id, int32_t alpha_plane, const jxl_tensor_params* p, void* out_device);
 
+/* ---- the image as a device tensor of a GIVEN SIZE in one pass: a box of the planes resampled to out_height x out_width ----
+ * This stage has no counterpart in the reference (which never resamples an image): its contract is stated here and in DESIGN
+ * 4.5o. The separable filter sits between stages 5 and 6 of jxl_stage_tensor_samples, so that it averages LINEAR samples
+ * wherever the colour stages pass through linear light, and the output curve runs per output pixel only.
+ * Tap tables, per axis, in IEEE double on the host (box length L, output length O; these are Pillow's precompute_coeffs):
+ *   s = L / O, fs = max(s, 1), sup = r * fs with r = 1 (JXL_RESIZE_TRIANGLE) or 0.5 (JXL_RESIZE_BOX); for output o:
+ *   c = (o + 0.5) * s, lo = max(0, floor(c - sup + 0.5)), hi = min(L, floor(c + sup + 0.5)); the weight of source j in
+ *   [lo, hi), t = (j + 0.5 - c) / fs: triangle max(0, 1 - |t|); box 1 where -0.5 < t <= 0.5, else 0; the weights are divided by
+ *   their sum (ascending j) and rounded to f32; trailing, then leading taps of f32 weight 0 are dropped, one tap is kept at
+ *   least (an identity size: one tap of weight 1, an exact copy). A range wider than 1024 taps is refused.
+ * Per output element, in f32, every multiply and add rounded separately, the VERTICAL pass first, each sum sequential in
+ * ascending index: V(x) = wy[0] * S(y0, x), V = V + wy[k] * S(y0 + k, x); R = wx[0] * V(x0), R = R + wx[k] * V(x0 + k). S is
+ * the stage 1-5 value of the source pixel; alpha is filtered the same way from its float value (a float plane as it is, an
+ * int32 plane as (float)a * (1.0f / (2^depth - 1)) -- for JXL_TENSOR_U8 as well: there is no integer left to clamp, and the
+ * depth must be 1..31 wherever the plane is read); premultiplied colours are filtered as they are. A zero weight that survives
+ * the trim multiplies like any other (0 * inf is NaN). Behind R: fromLinearF, colour / alpha when premultiplied,
+ * normalisation, the conversion and the layout, exactly as jxl_stage_tensor_samples has them behind its stage 5.
+ * p->height and p->width stay the SOURCE planes' size; the tensor is out_height x out_width, and out_device must hold it.
+ * The box is in whole source pixels, inside the image. JXL_ERR_INVALID_ARGUMENT, nothing queued and out_device untouched:
+ * everything the unresized entry refuses (with the tensor's size the output's), a box outside the image or empty, an output
+ * size <= 0, an unknown filter, more than 1024 taps. The tap tables go up once per call; the stream is synchronised. */
+#define JXL_RESIZE_TRIANGLE 0
+#define JXL_RESIZE_BOX 1
+typedef struct jxl_resize_params {
+    int32_t box_x0, box_y0, box_width, box_height; /* the source box, in source pixels */
+    int32_t out_height, out_width;                 /* the tensor's size */
+    int32_t filter;                                /* JXL_RESIZE_TRIANGLE / BOX */
+} jxl_resize_params;
+jxl_status jxl_stage_tensor_resized(jxl_ctx* ctx, const void* const in[3], const void* alpha, const jxl_tensor_params* p,
+                                    const jxl_resize_params* r, void* out_device);
+/* The same launch on the three resident float planes, as jxl_planes_tensor_samples. */
+jxl_status jxl_planes_tensor_resized(jxl_ctx* ctx, const void* alpha, const jxl_tensor_params* p, const jxl_resize_params* r,
+                                     void* out_device);
+/* The same launch on the planes of the plane set `id`, as jxl_canvas_tensor_samples. */
+jxl_status jxl_canvas_tensor_resized(jxl_ctx* ctx, int32_t id, int32_t alpha_plane, const jxl_tensor_params* p,
+                                     const jxl_resize_params* r, void* out_device);
+
 /* ---- the PFM's samples in one pass: replaces the body of PFMWriter.write (PFMWriter.java:30-48) after the header ----
  * The planes are the image's own samples (image.getBuffer(false), :30): no colour transform, no peak scale, no transfer
  * function. An int32 plane is cast as castToFloat(image.getTaggedBitDepth(c)) casts it (:33-35; ImageBuffer.java:99-101,

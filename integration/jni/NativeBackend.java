@@ -215,6 +215,12 @@ public final class NativeBackend implements AutoCloseable {
             long out);                                                                                // jxl_stage_tensor_samples
     public native void planesTensorSamples(ByteBuffer alpha, ByteBuffer params, long out);            // jxl_planes_tensor_samples
     public native void canvasTensorSamples(int id, int alphaPlane, ByteBuffer params, long out);      // jxl_canvas_tensor_samples (alphaPlane -1: none)
+    // the same, resampled to a given size in the pass: resize = struct jxl_resize_params in a direct buffer (the source box, the
+    // tensor's size, the filter); params' height / width stay the source planes'; out holds out_height x out_width pixels
+    public native void stageTensorResized(ByteBuffer i0, ByteBuffer i1, ByteBuffer i2, ByteBuffer alpha, ByteBuffer params,
+            ByteBuffer resize, long out);                                                             // jxl_stage_tensor_resized
+    public native void planesTensorResized(ByteBuffer alpha, ByteBuffer params, ByteBuffer resize, long out);  // jxl_planes_tensor_resized
+    public native void canvasTensorResized(int id, int alphaPlane, ByteBuffer params, ByteBuffer resize, long out);  // jxl_canvas_tensor_resized
     /** shapes: {n, h, w, type[n]}; ref null when desc names no reference. Throws what canvasBlend would; no device needed. */
     public static native void canvasBlendCheck(int[] desc, int[] canvas, int[] frame, int[] ref);    // jxl_canvas_blend_check
 

@@ -1539,6 +1539,54 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasTenso
     CHECK(jxl_canvas_tensor_samples(c, id, alphaPlane, &p, (void*)(intptr_t)out));
 }
 
+/* ---- the image resampled to a device tensor in one pass: the tensor natives with struct jxl_resize_params in a second direct
+ * buffer. params->height / width stay the SOURCE planes' size (what the shim checks the host planes against); the tensor at `out`
+ * is out_height x out_width. ---- */
+static int resize_params(JNIEnv* e, jobject resize, jxl_resize_params* r) {
+    const void* src = resize ? (*e)->GetDirectBufferAddress(e, resize) : NULL;
+    if (!src || (*e)->GetDirectBufferCapacity(e, resize) < (jlong)sizeof *r) {
+        bad_arg(e, "jxlatte_amd: a direct buffer holding jxl_resize_params is needed");
+        return 0;
+    }
+    memcpy(r, src, sizeof *r);
+    if (r->out_height < 1 || r->out_width < 1 || r->box_width < 1 || r->box_height < 1) {
+        bad_arg(e, "jxlatte_amd: resize parameters");
+        return 0;
+    }
+    return 1;
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageTensorResized(JNIEnv* e, jobject self, jobject i0, jobject i1, jobject i2,
+        jobject alpha, jobject params, jobject resize, jlong out) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_tensor_params p;
+    jxl_resize_params r;
+    if (!tensor_params(e, params, &p) || !resize_params(e, resize, &r)) return;
+    const jlong plane = 4 * area(p.height, p.width);
+    NEED(i0, plane); NEED_OPT(i1, plane); NEED_OPT(i2, plane); NEED_OPT(alpha, plane);
+    const void* in[3] = {ADDR(i0), ADDR(i1), ADDR(i2)};
+    CHECK(jxl_stage_tensor_resized(c, in, ADDR(alpha), &p, &r, (void*)(intptr_t)out));
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesTensorResized(JNIEnv* e, jobject self, jobject alpha, jobject params,
+        jobject resize, jlong out) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_tensor_params p;
+    jxl_resize_params r;
+    if (!tensor_params(e, params, &p) || !resize_params(e, resize, &r)) return;
+    NEED_OPT(alpha, 4 * area(p.height, p.width));
+    CHECK(jxl_planes_tensor_resized(c, ADDR(alpha), &p, &r, (void*)(intptr_t)out));
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasTensorResized(JNIEnv* e, jobject self, jint id, jint alphaPlane,
+        jobject params, jobject resize, jlong out) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_tensor_params p;
+    jxl_resize_params r;
+    if (!tensor_params(e, params, &p) || !resize_params(e, resize, &r)) return;
+    CHECK(jxl_canvas_tensor_resized(c, id, alphaPlane, &p, &r, (void*)(intptr_t)out));
+}
+
 JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasBlendCheck(JNIEnv* e, jclass k, jintArray desc, jintArray canvas,
         jintArray frame, jintArray ref) {
     (void)k;

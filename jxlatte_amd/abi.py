@@ -217,6 +217,17 @@ class TensorParams(C.Structure):
 
 assert C.sizeof(TensorParams) == C.sizeof(ColorParams) + 4 * (11 + 8)
 
+RESIZE_TRIANGLE, RESIZE_BOX = 0, 1
+
+
+class ResizeParams(C.Structure):
+    """struct jxl_resize_params"""
+    _fields_ = [("box_x0", C.c_int32), ("box_y0", C.c_int32), ("box_width", C.c_int32), ("box_height", C.c_int32),
+                ("out_height", C.c_int32), ("out_width", C.c_int32), ("filter", C.c_int32)]
+
+
+assert C.sizeof(ResizeParams) == 28
+
 
 class PfmParams(C.Structure):
     """struct jxl_pfm_params"""

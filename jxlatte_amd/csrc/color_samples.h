@@ -62,11 +62,11 @@ __device__ __forceinline__ float linear_word(const ColorArgs& a, int c, uint32_t
     return to_linear(f, a.tf_in, a.p_in, a.kind_in);
 }
 
-// stages 1-6 of one pixel as the writers' one-pass kernels (k_png.hip, k_tensor.hip) evaluate them: the words of its colour planes
-// (w[c], c < n_planes) -> COLORS float samples, COLORS being 3 when n_planes == 3 or use_matrix, else 1
+// stages 1-5 of one pixel (cast, toLinearF, grey -> RGB, matrix, scale): the words of its colour planes (w[c], c < n_planes) ->
+// COLORS linear float samples, COLORS being 3 when n_planes == 3 or use_matrix, else 1. What a kernel that filters in linear
+// light (k_tensor_resize.hip) evaluates per SOURCE pixel; color_back is then its stage 6, per output sample
 template <int COLORS>
-__device__ __forceinline__ void color_stages(const ColorArgs& a, const uint32_t w[3], float v[3]) {
-    const float* pq_tab = a.pq_tab;
+__device__ __forceinline__ void color_front(const ColorArgs& a, const uint32_t w[3], float v[3]) {
     v[0] = linear_word(a, 0, w[0]);
     if (COLORS == 3) {
         v[1] = v[2] = v[0];  // fillColor
@@ -82,10 +82,21 @@ __device__ __forceinline__ void color_stages(const ColorArgs& a, const uint32_t 
         }
     }
 #pragma unroll
-    for (int c = 0; c < COLORS; c++) {
+    for (int c = 0; c < COLORS; c++)
         if (a.use_scale) v[c] = v[c] * a.scale;
-        v[c] = from_linear(v[c], a.tf_out, a.p_out, a.kind_out, pq_tab);
-    }
+}
+
+// stage 6 of one sample: fromLinearF of the output curve
+__device__ __forceinline__ float color_back(const ColorArgs& a, float v) {
+    return from_linear(v, a.tf_out, a.p_out, a.kind_out, a.pq_tab);
+}
+
+// stages 1-6 of one pixel as the writers' one-pass kernels (k_png.hip, k_tensor.hip) evaluate them
+template <int COLORS>
+__device__ __forceinline__ void color_stages(const ColorArgs& a, const uint32_t w[3], float v[3]) {
+    color_front<COLORS>(a, w, v);
+#pragma unroll
+    for (int c = 0; c < COLORS; c++) v[c] = color_back(a, v[c]);
 }
 
 // stages 1 + 2 of sample i of input plane c

@@ -264,6 +264,24 @@ struct TensorArgs {
 };
 // max_workgroups > 0: a smaller grid bound than the kernel's own (tests reach the grid-stride loop at a small size)
 void launch_tensor_samples(const TensorArgs& p, hipStream_t s, int max_workgroups = 0);
+// the image resampled to a device tensor in one pass (k_tensor_resize.hip): stages 1-5 per source pixel, the separable filter of
+// the tap tables (vertical pass first), then stage 6 and TensorArgs' tail per output pixel. t.g.c.n is the SOURCE planes' size,
+// t.out holds oh * ow * n_out elements (t.wide is not looked at)
+struct ResizeArgs {
+    TensorArgs t;
+    int src_w;                   // the planes' row pitch in samples
+    int x0, y0;                  // the box's first column and row
+    int oh, ow;
+    int tw, th;                  // the output tile of a workgroup: tw * th <= 256, th <= 4
+    int planes;                  // colour planes (n_color) + 1 when the alpha plane is read
+    int lds_w;                   // floats of one (tile row, plane) line of the LDS image (tensor_resize_check.h: resize_tile_fits)
+    int lds_bytes;
+    int skew;                    // the LDS column of footprint column x is x + (x >> 5), else x
+    int wide_in;                 // every plane row starts 16-byte aligned: 16-byte loads (resize_wide_in_ok)
+    const int32_t *yfirst, *yoff, *xfirst, *xoff;  // device: first[O] relative to the box, off[O + 1]
+    const float *wy, *wx;                          // device: the f32 weights, packed
+};
+void launch_tensor_resize(const ResizeArgs& r, hipStream_t s);
 // the PFM's samples from the image's planes in one pass (k_pfm.hip): cast of the int32 planes, floatToIntBits, big-endian words,
 // channels interleaved, rows bottom to top (PFMWriter.java:22-49)
 struct PfmArgs {

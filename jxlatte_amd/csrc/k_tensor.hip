@@ -19,6 +19,7 @@
 // that of a dword for the 1- and 2-byte dtypes). Otherwise, and in the last group of a size that is no multiple of 4, the samples
 // leave one by one. BF16 and F16 share the 2-byte instances (a wave-uniform branch at the conversion).
 #include "color_samples.h"
+#include "tensor_store.h"
 
 namespace jxl {
 namespace {
@@ -31,16 +32,6 @@ struct TensorShape {
     static constexpr int kPixelWords = (kPixelBits + 31) / 32;  // 1 .. 4
     static constexpr int kWords = NCH * BYTES;                  // the lane's 4 pixels: 1 .. 16 words
 };
-
-// f32 -> the element's bits (below 2^(8 BYTES) for the narrow dtypes)
-template <int BYTES>
-__device__ __forceinline__ uint32_t tensor_float_bits(float v, int dtype) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, v);
-    if (BYTES == 4) return u;
-    if (v != v) return dtype == JXL_TENSOR_BF16 ? 0x7FC0u : 0x7E00u;
-    if (dtype == JXL_TENSOR_BF16) return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;  // (no carry out of a finite or infinite f32)
-    return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)v);  // v_cvt_f16_f32: nearest even, subnormals kept, overflow to inf
-}
 
 // one pixel: the words of its colour planes and of its alpha plane -> the bits of its NCH elements
 template <int BYTES, int NCH>
@@ -77,30 +68,6 @@ __device__ __forceinline__ void tensor_pixel(const TensorArgs& t, const uint32_t
         }
 #pragma unroll
         for (int c = 0; c < NCH; c++) q[c] = tensor_float_bits<BYTES>(o[c], t.dtype);
-    }
-}
-
-// element e of a register file that holds consecutive BYTES-wide elements
-template <int BYTES>
-__device__ __forceinline__ void store_element(void* out, int64_t at, const uint32_t* reg, int e) {
-    const uint32_t word = reg[(e * BYTES) >> 2] >> (8 * ((e * BYTES) & 3));
-    if (BYTES == 1) ((uint8_t*)out)[at] = (uint8_t)word;
-    else if (BYTES == 2) ((uint16_t*)out)[at] = (uint16_t)word;
-    else ((uint32_t*)out)[at] = word;
-}
-
-// WORDS consecutive words to a WORDS * 4-byte group whose address is aligned to min(16, the largest power of two in WORDS * 4)
-template <int WORDS>
-__device__ __forceinline__ void store_words(uint32_t* o, const uint32_t* reg) {
-    if constexpr (WORDS % 4 == 0) {
-#pragma unroll
-        for (int j = 0; j < WORDS; j += 4) *reinterpret_cast<uint4*>(o + j) = make_uint4(reg[j], reg[j + 1], reg[j + 2], reg[j + 3]);
-    } else if constexpr (WORDS % 2 == 0) {
-#pragma unroll
-        for (int j = 0; j < WORDS; j += 2) *reinterpret_cast<uint2*>(o + j) = make_uint2(reg[j], reg[j + 1]);
-    } else {  // 4 or 12 bytes: adjacent dword stores (hipcc joins the three into a global_store_dwordx3, as in k_png_samples)
-#pragma unroll
-        for (int j = 0; j < WORDS; j++) o[j] = reg[j];
     }
 }
 

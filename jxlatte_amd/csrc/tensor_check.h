@@ -57,7 +57,7 @@ inline bool tensor_extent_ok(uint64_t base, uint64_t range, uint64_t ptr, uint64
     return off <= range && needed <= range - off;
 }
 
-// the widest store of a group of `words` words (k_tensor.hip: store_words)
+// the widest store of a group of `words` words (tensor_store.h: store_words)
 inline int tensor_store_unit(int words) { return words % 4 == 0 ? 16 : words % 2 == 0 ? 8 : 4; }
 
 // every full group of 4 pixels may leave in the kernel's vector stores: each group's address has its store's alignment

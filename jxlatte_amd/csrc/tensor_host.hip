@@ -2,13 +2,9 @@
 // entries make are theirs (ctx_png_args, host.hip), the tensor's own pure checks are tensor_check.h's; what is left here is the
 // question only the runtime can answer -- is out_device device memory of this context's device, and does its allocation hold the
 // tensor -- and the launch. Nothing is queued before every check has passed; the stream is synchronised before return.
-#include "jxl_internal.h"
-#include "tensor_check.h"
-
-#include <vector>
+#include "tensor_host.h"
 
 namespace jxl {
-namespace {
 
 #define TS_HIP(c, expr)                                                                                                        \
     do {                                                                                                                      \
@@ -16,21 +12,7 @@ namespace {
         if (e_ != hipSuccess) return ctx_fail(c, e_ == hipErrorOutOfMemory ? JXL_ERR_OOM : JXL_ERR_DEVICE, hipGetErrorString(e_)); \
     } while (0)
 
-// device copies of host planes, freed when the entry returns
-struct Staged {
-    std::vector<void*> v;
-    ~Staged() { for (void* p : v) (void)hipFree(p); }
-    const void* up(const void* host, size_t bytes) {
-        void* d = nullptr;
-        if (hipMalloc(&d, bytes < 16 ? 16 : bytes) != hipSuccess) return nullptr;
-        v.push_back(d);
-        if (hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return d;
-    }
-};
-
-// out_device is device memory of the context's device and its allocation holds `bytes` bytes from there on
-jxl_status out_check(jxl_ctx* c, const CtxLink& l, void* out, uint64_t bytes) {
+jxl_status tensor_out_check(jxl_ctx* c, const CtxLink& l, void* out, uint64_t bytes) {
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, out) != hipSuccess) {
         (void)hipGetLastError();  // (an address the runtime does not know: its error is not the stream's)
@@ -49,11 +31,15 @@ jxl_status out_check(jxl_ctx* c, const CtxLink& l, void* out, uint64_t bytes) {
     return JXL_OK;
 }
 
-// every check of an entry but those of its planes' home: the kernel's arguments without the plane pointers
 jxl_status tensor_args(jxl_ctx* c, const CtxLink& l, const jxl_tensor_params* p, const void* const in[3], const void* alpha, void* out,
-                       TensorArgs* t, TensorLayout* lay) {
+                       TensorArgs* t, TensorLayout* lay, int32_t out_height, int32_t out_width) {
     if (!out) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: null argument");
     const char* why = tensor_check_params(p, lay);
+    if (!why && (out_height || out_width)) {  // the tensor is out_height x out_width: its layout, bytes and alignment rule
+        jxl_tensor_params q = *p;
+        q.height = out_height, q.width = out_width;
+        why = tensor_check_params(&q, lay);
+    }
     if (why) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, why);
     jxl_png_params g;
     g.color = p->color;
@@ -64,7 +50,7 @@ jxl_status tensor_args(jxl_ctx* c, const CtxLink& l, const jxl_tensor_params* p,
     int n_color = 0;
     jxl_status st = ctx_png_args(c, &g, in, alpha, out, &t->g, &n_color);
     if (st) return st;
-    if ((st = out_check(c, l, out, lay->bytes))) return st;
+    if ((st = tensor_out_check(c, l, out, lay->bytes))) return st;
     t->dtype = p->dtype, t->layout = p->layout;
     t->n_out = lay->n_out;
     t->use_norm = p->use_norm ? 1 : 0;
@@ -74,8 +60,9 @@ jxl_status tensor_args(jxl_ctx* c, const CtxLink& l, const jxl_tensor_params* p,
     return JXL_OK;
 }
 
-// the alpha plane is read only where it is written or divides the colours
-bool alpha_read(const jxl_tensor_params* p) { return p->has_alpha && (p->write_alpha || p->premultiplied); }
+namespace {
+
+bool alpha_read(const jxl_tensor_params* p) { return tensor_alpha_read(p); }
 
 jxl_status tensor_run(jxl_ctx* c, const CtxLink& l, const TensorArgs& t, int max_workgroups) {
     launch_tensor_samples(t, l.stream, max_workgroups);

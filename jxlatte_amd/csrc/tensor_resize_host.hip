@@ -1,0 +1,183 @@
+// Host side of the resized tensor exit (k_tensor_resize.hip): the three jxl_*_tensor_resized entries beside their unresized
+// siblings (tensor_host.hip), whose checks of the parameters, the planes and out_device they share (tensor_args). Their own pure
+// part -- box, size, filter, the tap tables, the tile -- is tensor_resize_check.h's. Nothing is queued before every check has
+// passed; the tables go up once per call, in one transfer; the stream is synchronised before return.
+#include "tensor_host.h"
+#include "tensor_resize_check.h"
+
+#include <cstring>
+
+namespace jxl {
+namespace {
+
+#define TR_HIP(c, expr)                                                                                                        \
+    do {                                                                                                                      \
+        hipError_t e_ = (expr);                                                                                               \
+        if (e_ != hipSuccess) return ctx_fail(c, e_ == hipErrorOutOfMemory ? JXL_ERR_OOM : JXL_ERR_DEVICE, hipGetErrorString(e_)); \
+    } while (0)
+
+// tests: the tile and the LDS skew of the launches that follow (jxl_debug_tensor_resize_tile, jxl_debug_tensor_resize_skew)
+int g_force_tw = 0, g_force_th = 0;
+bool g_skew = true;
+
+struct Tables {
+    ResizeTaps x, y;
+};
+
+// the entry's checks behind tensor_args, without a device call: the tables and the tile into r
+jxl_status resize_plan(jxl_ctx* c, const CtxLink& l, const jxl_tensor_params* p, const jxl_resize_params* rz, const TensorLayout& lay,
+                       ResizeArgs* r, Tables* tb) {
+    const char* why = resize_build_taps(rz->box_height, rz->out_height, rz->filter, &tb->y);
+    if (!why) why = resize_build_taps(rz->box_width, rz->out_width, rz->filter, &tb->x);
+    if (why) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, why);
+    r->planes = lay.n_color + (tensor_alpha_read(p) ? 1 : 0);
+    // the workgroups the device holds at once: two per compute unit (the kernel's registers allow two waves per SIMD)
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, l.device) != hipSuccess) cus = 0, (void)hipGetLastError();
+    ResizeTile tile;
+    if ((why = resize_pick_tile(tb->x, rz->box_x0, tb->y, r->planes, g_skew, 2 * (int64_t)cus, g_force_tw, g_force_th, &tile)))
+        return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, why);
+    r->src_w = p->width;
+    r->x0 = rz->box_x0, r->y0 = rz->box_y0;
+    r->oh = rz->out_height, r->ow = rz->out_width;
+    r->tw = tile.tw, r->th = tile.th;
+    r->lds_w = tile.lds_w, r->lds_bytes = tile.lds_bytes;
+    r->skew = g_skew ? 1 : 0;
+    return JXL_OK;
+}
+
+// the tables to the device in one transfer, the launch, the synchronisation (the plane pointers of r->t are set)
+jxl_status resize_run(jxl_ctx* c, const CtxLink& l, ResizeArgs* r, const Tables& tb, Staged* s) {
+    const std::vector<int32_t>* iv[4] = {&tb.y.first, &tb.y.off, &tb.x.first, &tb.x.off};
+    size_t words = tb.y.w.size() + tb.x.w.size();
+    for (const auto* v : iv) words += v->size();
+    std::vector<uint32_t> pack(words);
+    size_t at = 0, where[6];
+    for (int i = 0; i < 4; i++) {
+        where[i] = at;
+        std::memcpy(pack.data() + at, iv[i]->data(), iv[i]->size() * 4);
+        at += iv[i]->size();
+    }
+    where[4] = at;
+    std::memcpy(pack.data() + at, tb.y.w.data(), tb.y.w.size() * 4);
+    at += tb.y.w.size();
+    where[5] = at;
+    std::memcpy(pack.data() + at, tb.x.w.data(), tb.x.w.size() * 4);
+    const uint32_t* d = (const uint32_t*)s->up(pack.data(), words * 4);
+    if (!d) return ctx_fail(c, JXL_ERR_OOM, "device allocation failed");
+    r->yfirst = (const int32_t*)(d + where[0]), r->yoff = (const int32_t*)(d + where[1]);
+    r->xfirst = (const int32_t*)(d + where[2]), r->xoff = (const int32_t*)(d + where[3]);
+    r->wy = (const float*)(d + where[4]), r->wx = (const float*)(d + where[5]);
+    uint64_t bases[4];
+    int nb = 0;
+    for (int i = 0; i < r->t.g.c.n_planes; i++) bases[nb++] = (uint64_t)(uintptr_t)r->t.g.c.in[i];
+    if (r->t.g.alpha) bases[nb++] = (uint64_t)(uintptr_t)r->t.g.alpha;
+    r->wide_in = resize_wide_in_ok(r->src_w, bases, nb) ? 1 : 0;
+    launch_tensor_resize(*r, l.stream);
+    TR_HIP(c, hipStreamSynchronize(l.stream));
+    TR_HIP(c, hipGetLastError());
+    return JXL_OK;
+}
+
+// the checks every entry makes first: the pure ones of the resize, then tensor_args with the tensor's size
+jxl_status resize_args(jxl_ctx* c, const CtxLink& l, const jxl_tensor_params* p, const jxl_resize_params* rz, const void* const in[3],
+                       const void* alpha, void* out, ResizeArgs* r, TensorLayout* lay, Tables* tb) {
+    if (!out) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: null argument");
+    const char* why = resize_check_params(p, rz);
+    if (why) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, why);
+    jxl_status st = tensor_args(c, l, p, in, alpha, out, &r->t, lay, rz->out_height, rz->out_width);
+    if (st) return st;
+    return resize_plan(c, l, p, rz, *lay, r, tb);
+}
+
+}  // namespace
+}  // namespace jxl
+
+using namespace jxl;
+
+extern "C" {
+
+jxl_status jxl_stage_tensor_resized(jxl_ctx* c, const void* const in[3], const void* alpha, const jxl_tensor_params* p,
+                                    const jxl_resize_params* rz, void* out_device) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    ResizeArgs r;
+    TensorLayout lay;
+    Tables tb;
+    if ((st = resize_args(c, l, p, rz, in, alpha, out_device, &r, &lay, &tb))) return st;
+    Staged s;
+    const size_t plane = (size_t)p->height * (size_t)p->width * 4;
+    for (int i = 0; i < p->color.n_planes; i++)
+        if (!(r.t.g.c.in[i] = s.up(in[i], plane))) return ctx_fail(c, JXL_ERR_OOM, "device allocation failed");
+    if (tensor_alpha_read(p) && !(r.t.g.alpha = s.up(alpha, plane))) return ctx_fail(c, JXL_ERR_OOM, "device allocation failed");
+    return resize_run(c, l, &r, tb, &s);
+}
+
+jxl_status jxl_planes_tensor_resized(jxl_ctx* c, const void* alpha, const jxl_tensor_params* p, const jxl_resize_params* rz,
+                                     void* out_device) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    int h = 0, w = 0;
+    float* rp[3];
+    if ((st = ctx_planes_get(c, &h, &w, rp))) return st;
+    const void* in[3] = {rp[0], rp[1], rp[2]};
+    ResizeArgs r;
+    TensorLayout lay;
+    Tables tb;
+    if ((st = resize_args(c, l, p, rz, in, alpha, out_device, &r, &lay, &tb))) return st;
+    if (p->color.n_planes != 3 || p->color.in_is_int || p->height != h || p->width != w)
+        return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: the resident planes are three float planes of another size");
+    for (int i = 0; i < 3; i++) r.t.g.c.in[i] = in[i];
+    Staged s;
+    if (tensor_alpha_read(p) && !(r.t.g.alpha = s.up(alpha, (size_t)h * (size_t)w * 4))) return ctx_fail(c, JXL_ERR_OOM, "device allocation failed");
+    return resize_run(c, l, &r, tb, &s);
+}
+
+jxl_status jxl_canvas_tensor_resized(jxl_ctx* c, int32_t id, int32_t alpha_plane, const jxl_tensor_params* p, const jxl_resize_params* rz,
+                                     void* out_device) {
+    CtxLink l;
+    jxl_status st = ctx_link(c, &l);
+    if (st) return st;
+    CanvasView v;
+    if (!canvas_view(*l.canvas, id, &v)) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+    if (!p) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: null argument");
+    const int nc = p->color.n_planes;
+    if ((nc != 1 && nc != 3) || nc > v.n || alpha_plane < -1 || alpha_plane >= v.n || (p->has_alpha != 0) != (alpha_plane >= 0))
+        return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: the set has no such planes");
+    const void* in[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < nc; i++) in[i] = v.plane[i];
+    const void* alpha = alpha_plane >= 0 ? v.plane[alpha_plane] : nullptr;
+    ResizeArgs r;
+    TensorLayout lay;
+    Tables tb;
+    if ((st = resize_args(c, l, p, rz, in, alpha, out_device, &r, &lay, &tb))) return st;
+    bool tags = p->height == v.h && p->width == v.w;
+    for (int i = 0; i < nc; i++) tags = tags && (p->color.in_is_int != 0) == (v.type[i] == JXL_PLANE_INT32);
+    if (alpha_plane >= 0) tags = tags && (p->alpha_is_int != 0) == (v.type[alpha_plane] == JXL_PLANE_INT32);
+    if (!tags) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: the parameters do not describe the set's planes");
+    for (int i = 0; i < nc; i++) r.t.g.c.in[i] = in[i];
+    if (tensor_alpha_read(p)) r.t.g.alpha = alpha;
+    Staged s;
+    return resize_run(c, l, &r, tb, &s);
+}
+
+// tests: the tile of the resized launches that follow, (0, 0) for the host's own choice again. A tile the kernel does not have
+// is refused here; one whose LDS image does not fit a call's footprint is refused by that call
+jxl_status jxl_debug_tensor_resize_tile(int32_t tw, int32_t th) {
+    if (tw || th) {
+        const bool known = (tw == 64 || tw == 32 || tw == 16 || tw == 8 || tw == 4 || tw == 2 || tw == 1) && (th == 4 || th == 2 || th == 1);
+        if (!known) return JXL_ERR_INVALID_ARGUMENT;
+    }
+    g_force_tw = tw, g_force_th = th;
+    return JXL_OK;
+}
+
+// measurements: the LDS skew of the resized launches that follow (on by default)
+jxl_status jxl_debug_tensor_resize_skew(int32_t on) {
+    g_skew = on != 0;
+    return JXL_OK;
+}
+
+}  // extern "C"

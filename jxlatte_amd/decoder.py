@@ -755,6 +755,10 @@ class DeviceBackend:
         """the image as a device tensor in one pass (host.tensorSamples; the keywords are host.tensorParams')"""
         return self.host.tensorSamples(self.ctx, planes, alpha, out_ptr, **params)
 
+    def tensor_resized(self, planes, alpha, out_ptr, size, box, resample, **params):
+        """the image resampled to a device tensor in one pass (host.tensorResized)"""
+        return self.host.tensorResized(self.ctx, planes, alpha, out_ptr, size, box, resample, **params)
+
     def tensor_device(self):
         """the torch device of the memory tensor_samples writes"""
         return "cuda:%d" % self.ctx.device
@@ -883,26 +887,38 @@ class JXLImage:
         planes = [np.ascontiguousarray(p) for p in planes]
         return self.backend.png_samples(planes, alpha, **kw), up + sum(p.nbytes for p in planes)
 
-    def _tensor_samples(self, planes, out_ptr, **kw):
+    def _tensor_samples(self, planes, out_ptr, resize=None, **kw):
         """the image as a device tensor in one pass (tensorParams' keywords), written to the device address out_ptr: the bytes
-        sent up, by _png_samples' rule. Nothing comes down from any home"""
+        sent up, by _png_samples' rule. Nothing comes down from any home. resize: None, or (size, box, resample) -- the
+        resampled pass (tensorResized) from the same home"""
         colors, a = len(planes), self.alphaIndex
         home = self._home(colors, True)
         if home == "set":
-            self.planeSet.tensorSamples(out_ptr, nColor=colors, alphaPlane=colors + a if a >= 0 else None, **kw)
+            ap = colors + a if a >= 0 else None
+            if resize is None:
+                self.planeSet.tensorSamples(out_ptr, nColor=colors, alphaPlane=ap, **kw)
+            else:
+                self.planeSet.tensorResized(out_ptr, *resize, nColor=colors, alphaPlane=ap, **kw)
             return 0
         alpha = np.ascontiguousarray(self.extraChannel(a)) if a >= 0 else None
         up = alpha.nbytes if alpha is not None and (kw.get("writeAlpha") or kw.get("premultiplied")) else 0
         if home == "resident":
-            self.resident.tensorSamples(out_ptr, alpha, **kw)
+            if resize is None:
+                self.resident.tensorSamples(out_ptr, alpha, **kw)
+            else:
+                self.resident.tensorResized(out_ptr, *resize, alpha=alpha, **kw)
             return up
         planes = [np.ascontiguousarray(p) for p in planes]
-        self.backend.tensor_samples(planes, alpha, out_ptr, **kw)
+        if resize is None:
+            self.backend.tensor_samples(planes, alpha, out_ptr, **kw)
+        else:
+            self.backend.tensor_resized(planes, alpha, out_ptr, *resize, **kw)
         return up + sum(p.nbytes for p in planes)
 
     _TENSOR_TARGETS = ("srgb", "pq", "linear", "as-is")
 
-    def toTensor(self, dtype=None, layout="CHW", target="srgb", peakDetect=PEAK_DETECT_AUTO, alpha="drop", mean=None, std=None, out=None):
+    def toTensor(self, dtype=None, layout="CHW", target="srgb", peakDetect=PEAK_DETECT_AUTO, alpha="drop", mean=None, std=None, out=None,
+                 size=None, box=None, resample="triangle"):
         """The image as a torch tensor on the backend's device, (C, H, W) or (H, W, C), in ONE device pass from wherever its planes
         are -- no sample crosses the bus downwards.
         dtype: torch.uint8, float16, bfloat16 or float32 (the default). target: "srgb" (PNGWriter's non-HDR target: sRGB
@@ -912,11 +928,36 @@ class JXLImage:
         alpha: "drop" or "append" (the last channel); a premultiplied image's colours are divided either way.
         mean / std: per output channel, float dtypes only: (v - mean) * (float32(1) / float32(std)).
         out: a contiguous tensor of the result's shape and dtype on that device -- batch[i] of a batch of equal-sized images is
-        one -- filled in place and returned; the current torch stream is synchronised first. tensor_bus_bytes = (bytes up, 0)."""
+        one -- filled in place and returned; the current torch stream is synchronised first. tensor_bus_bytes = (bytes up, 0).
+        size = (h, w): the tensor's size; the image (or `box`) is resampled to it in the same pass -- behind the colour stages'
+        linear intermediate where the plan has one, before the output curve -- with resample "triangle" (bilinear with the
+        support scaled to the ratio: antialiased) or "box". box = (x0, y0, w, h) in whole source pixels: alone it is a crop
+        (an identity-ratio resample: an exact copy). With both left out the pass and its bytes are the unresized ones; images
+        of any size then fill one batch through out=batch[i]. Peak detection stays the whole image's."""
         import torch
         be = self.backend
         if not hasattr(be, "tensor_samples"):
             raise TypeError("toTensor needs a backend with tensor_samples")
+        resize = None
+        if size is not None or box is not None:
+            if not hasattr(be, "tensor_resized"):
+                raise TypeError("toTensor(size=, box=) needs a backend with tensor_resized")
+            if resample not in ("triangle", "box"):
+                raise ValueError("resample: triangle or box")
+            try:
+                bx = (0, 0, self.width, self.height) if box is None else tuple(int(v) for v in box)
+                sz = (bx[3], bx[2]) if size is None else tuple(int(v) for v in size)
+            except (TypeError, ValueError, IndexError):
+                raise ValueError("size: (height, width); box: (x0, y0, width, height)")
+            if len(bx) != 4 or len(sz) != 2 or (box is not None and bx != tuple(box)) or (size is not None and sz != tuple(size)):
+                raise ValueError("size: (height, width); box: (x0, y0, width, height), whole numbers")
+            if bx[0] < 0 or bx[1] < 0 or bx[2] <= 0 or bx[3] <= 0 or bx[0] + bx[2] > self.width or bx[1] + bx[3] > self.height:
+                raise ValueError("box: (x0, y0, width, height) inside the %d x %d image" % (self.width, self.height))
+            if sz[0] <= 0 or sz[1] <= 0:
+                raise ValueError("size: (height, width), both positive")
+            resize = (sz, bx, resample)
+        elif resample not in ("triangle", "box"):
+            raise ValueError("resample: triangle or box")
         if dtype is None:
             dtype = torch.float32
         names = {torch.uint8: "uint8", torch.float16: "float16", torch.bfloat16: "bfloat16", torch.float32: "float32"}
@@ -948,7 +989,8 @@ class JXLImage:
                 inv_std = [F(1) / F(s) for s in std]
             if not all(np.isfinite(v) for v in inv_std):
                 raise ValueError("std: 1 / std is not finite")
-        shape = (channels, self.height, self.width) if layout == "CHW" else (self.height, self.width, channels)
+        oh, ow = (self.height, self.width) if resize is None else resize[0]
+        shape = (channels, oh, ow) if layout == "CHW" else (oh, ow, channels)
         device = torch.device(be.tensor_device())
         if out is not None:
             if not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != device or not out.is_contiguous():
@@ -976,7 +1018,7 @@ class JXLImage:
             torch.cuda.current_stream(device).synchronize()  # what the caller queued on its tensor is done before the library writes
         has_alpha = self.alphaIndex >= 0
         sent = self._tensor_samples(
-            planes, out.data_ptr(), premultiplied=self.isAlphaPremultiplied() and has_alpha, writeAlpha=alpha == "append",
+            planes, out.data_ptr(), resize=resize, premultiplied=self.isAlphaPremultiplied() and has_alpha, writeAlpha=alpha == "append",
             dtype=names[dtype], layout=layout, alphaDepth=self.getTaggedBitDepth(colors + self.alphaIndex) if has_alpha else None,
             colorDepth=self.getTaggedBitDepth(0), mean=mean, invStd=inv_std, **params)
         self.tensor_bus_bytes = (up + sent, 0)

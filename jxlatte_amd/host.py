@@ -304,6 +304,34 @@ def tensorSamples(ctx, planes, alpha, out_ptr, **params):
     return p
 
 
+RESIZE_FILTERS = {"triangle": abi.RESIZE_TRIANGLE, "box": abi.RESIZE_BOX}
+
+
+def resizeParams(shape, size, box=None, resample="triangle"):
+    """jxl_resize_params for planes of `shape` (height, width): size = (out height, out width); box = (x0, y0, width, height) in
+    source pixels (default: the whole image); resample: a key of RESIZE_FILTERS or an abi.RESIZE_* code"""
+    r = abi.ResizeParams()
+    x0, y0, bw, bh = (0, 0, shape[1], shape[0]) if box is None else box
+    r.box_x0, r.box_y0, r.box_width, r.box_height = int(x0), int(y0), int(bw), int(bh)
+    r.out_height, r.out_width = int(size[0]), int(size[1])
+    r.filter = RESIZE_FILTERS[resample] if isinstance(resample, str) else int(resample)
+    return r
+
+
+def tensorResized(ctx, planes, alpha, out_ptr, size, box=None, resample="triangle", **params):
+    """tensorSamples with a resample to `size` in the same pass (jxl_stage_tensor_resized): the box of the planes is filtered
+    behind the colour stages 1-5 (in linear light where the stages pass through it), the output curve and the tensor's tail
+    run per output pixel. out_ptr: DEVICE memory for size[0] * size[1] * channels elements. size / box / resample:
+    resizeParams'; params: tensorParams' keywords. Returns (jxl_tensor_params, jxl_resize_params)."""
+    planes = [np.ascontiguousarray(a) for a in planes]
+    shape = planes[0].shape
+    a = _png_alpha(alpha, shape)
+    p = tensorParams(planes, shape, alpha=a, **params)
+    r = resizeParams(shape, size, box, resample)
+    ctx.call("jxl_stage_tensor_resized", _pv(planes), _vp(a), C.byref(p), C.byref(r), C.c_void_p(int(out_ptr)))
+    return p, r
+
+
 def pfmParams(planes, shape, taggedDepths=None):
     """jxl_pfm_params of 1 or 3 planes (each one's dtype tells int32 from float32). taggedDepths: image.getTaggedBitDepth(c)
     per plane, looked at for the int32 planes only"""
@@ -729,6 +757,17 @@ class ResidentPlanes:
         p = tensorParams(self._stand_ins(), shape, alpha=a, **params)
         self.ctx.call("jxl_planes_tensor_samples", _vp(a), C.byref(p), C.c_void_p(int(out_ptr)))
         return p
+
+    def tensorResized(self, out_ptr, size, box=None, resample="triangle", alpha=None, **params):
+        """tensorResized of the planes as they stand (jxl_planes_tensor_resized) to the device address out_ptr: only the alpha
+        plane goes up, nothing comes down"""
+        self._need_live()
+        shape = self.shape
+        a = _png_alpha(alpha, shape)
+        p = tensorParams(self._stand_ins(), shape, alpha=a, **params)
+        r = resizeParams(shape, size, box, resample)
+        self.ctx.call("jxl_planes_tensor_resized", _vp(a), C.byref(p), C.byref(r), C.c_void_p(int(out_ptr)))
+        return p, r
 
     def pfmSamples(self):
         """pfmSamples of the planes as they stand (jxl_planes_pfm_samples): nothing goes up, only the PFM's bytes come down"""
@@ -1239,6 +1278,17 @@ class DeviceCanvas:
         p = tensorParams(self._stand_ins(nColor), self.shape, alpha=alpha, **params)
         self.ctx.call("jxl_canvas_tensor_samples", self.id, ap, C.byref(p), C.c_void_p(int(out_ptr)))
         return p
+
+    def tensorResized(self, out_ptr, size, box=None, resample="triangle", nColor=3, alphaPlane=None, **params):
+        """tensorResized of planes 0 .. nColor - 1 and the alpha plane alphaPlane of the set (jxl_canvas_tensor_resized) to the
+        device address out_ptr: nothing crosses the bus, so nothing is counted"""
+        self._live()
+        ap = -1 if alphaPlane is None else int(alphaPlane)
+        alpha = None if ap < 0 else np.broadcast_to(np.zeros((), _PLANE_DTYPE[self.types[ap]]), self.shape)
+        p = tensorParams(self._stand_ins(nColor), self.shape, alpha=alpha, **params)
+        r = resizeParams(self.shape, size, box, resample)
+        self.ctx.call("jxl_canvas_tensor_resized", self.id, ap, C.byref(p), C.byref(r), C.c_void_p(int(out_ptr)))
+        return p, r
 
     def pfmSamples(self, nColor=3, taggedDepths=None):
         """pfmSamples of planes 0 .. nColor - 1 (jxl_canvas_pfm_samples): nothing goes up, only the PFM's bytes come down"""
