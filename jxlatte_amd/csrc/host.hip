@@ -1707,8 +1707,10 @@ jxl_status jxl_vardct_begin_frame(jxl_ctx* c, const jxl_vardct_params* p) {
             return fail(c, JXL_ERR_INVALID_ARGUMENT, "jpeg upsampling shift of channel %d out of range", i);
         c->sub = c->sub || c->sy[i] || c->sx[i];
     }
-    if (c->sub && ((p->width & 15) || (p->height & 15)))
-        return fail(c, JXL_ERR_INVALID_ARGUMENT, "a chroma-subsampled frame is padded to multiples of 16 (Frame.getPaddedFrameSize)");
+    // Frame.getPaddedFrameSize (Frame.java:924-941) pads each axis by its own factor: 4:2:2 leaves the height, 4:4:0 the width, at 8
+    const int pad_y = 8 << std::max({c->sy[0], c->sy[1], c->sy[2]}), pad_x = 8 << std::max({c->sx[0], c->sx[1], c->sx[2]});
+    if ((p->width & (pad_x - 1)) || (p->height & (pad_y - 1)))
+        return fail(c, JXL_ERR_INVALID_ARGUMENT, "a chroma-subsampled frame is padded to multiples of %d x %d (Frame.getPaddedFrameSize)", pad_x, pad_y);
     c->p = *p;
     c->W = p->width; c->H = p->height;
     c->bw = c->W / 8; c->bh = c->H / 8;

@@ -76,6 +76,11 @@ class BitWriter:
     def enum(self, v):  # Bitreader.java:65-70
         self.u32(v, (0, 0), (1, 0), (2, 4), (18, 6))
 
+    def f16(self, v):  # Bitreader.java:57-63: sixteen bits of an IEEE half, finite
+        h = np.float16(v)
+        assert np.isfinite(h) and float(h) == float(v), v
+        self.bits(int(h.view(np.uint16)), 16)
+
     def pad(self):  # Bitreader.java:159-166
         self.bits(0, -self.pos % 8)
 
@@ -131,6 +136,67 @@ def write_entropy_header(w, num_dists):
         w.bits(1 if i == 7 else 0, 2)
 
 
+# hybrid-integer configurations (split_exponent, msb_in_token, lsb_in_token) whose tokens stay below 64 for every value of at
+# least sixteen bits: the clusters of an EntropyCoder take different ones, so a symbol read under another cluster's
+# configuration takes another number of raw bits
+CONFIGS = ((0, 0, 0), (4, 1, 0), (2, 0, 1), (3, 1, 1), (4, 2, 0), (1, 0, 0), (2, 1, 0), (3, 0, 1))
+
+
+class EntropyCoder:
+    """a stream of several clusters (EntropyStream.java:106-156): the context map in its simple form (:49-53), prefix codes, one
+    HybridIntegerConfig per cluster (HybridIntegerConfig.java:21-33), every cluster the flat 6-bit code of write_entropy_header"""
+
+    def __init__(self, cluster_map, configs):
+        self.map = np.asarray(cluster_map, I64).reshape(-1)
+        self.configs = [tuple(c) for c in configs]
+        assert self.map.min() >= 0 and int(self.map.max()) + 1 == len(self.configs) <= min(8, len(self.map))
+        for se, msb, lsb in self.configs:
+            assert 0 <= se < 15 and 0 <= msb and 0 <= lsb and msb + lsb <= se
+
+    def write_header(self, w):
+        w.bool(False)  # :112 no LZ77
+        if len(self.map) > 1:
+            nbits = (len(self.configs) - 1).bit_length()
+            w.bool(True)  # :49 simple clustering
+            w.bits(nbits, 2)  # :51
+            if nbits:
+                w.many(self.map.astype(np.uint64), np.full(len(self.map), nbits))  # :52-53
+        w.bool(True)  # :129 prefix codes, log alphabet size 15
+        for se, msb, lsb in self.configs:  # :133-134
+            w.bits(se, 4)  # HybridIntegerConfig.java:22 in ceilLog1p(15) bits
+            w.bits(msb, se.bit_length())  # :27
+            w.bits(lsb, (se - msb).bit_length())  # :30
+        for _ in self.configs:  # :139-147 alphabet size 1 + (1 << 5) + 31 = 64
+            w.bool(True)
+            w.bits(5, 4)
+            w.bits(31, 5)
+        for _ in self.configs:  # :148-149, the code of write_entropy_header
+            w.bits(0, 2)
+            for i in range(18):
+                w.bits(1 if i == 7 else 0, 2)
+
+    def write(self, w, contexts, values):
+        """the inverse of readHybridInteger (:239-252) per symbol, under the configuration of its context's cluster"""
+        u = np.asarray(values, np.uint64).reshape(-1)
+        if u.size == 0:
+            return
+        ctx = np.asarray(contexts, I64).reshape(-1)
+        assert ctx.shape == u.shape and ctx.min() >= 0 and ctx.max() < len(self.map) and int(u.max()) < (1 << 32)
+        cfg = np.array(self.configs, I64)[self.map[ctx]]
+        se, msb, lsb = cfg[:, 0], cfg[:, 1], cfg[:, 2]
+        v = u.astype(I64)
+        b = np.zeros(v.shape, I64)  # the position of the leading one
+        for k in range(1, 33):
+            b += v >= (1 << k)
+        small = v < (1 << se)  # :241-242
+        n = np.where(small, 0, b - msb - lsb)  # :243-244
+        top = (v >> np.maximum(b - msb, 0)) & ((1 << msb) - 1)
+        token = np.where(small, v, (1 << se) + ((b - se) << (msb + lsb)) + (top << lsb) + (v & ((1 << lsb) - 1)))
+        assert int(token.max()) < 64, "the value does not fit the 64 tokens of its cluster's configuration"
+        raw = (v >> lsb) & ((1 << n) - 1)
+        w.many(_REV6[token] | (raw.astype(np.uint64) << np.uint64(6)), 6 + n)
+
+
 # ---- headers --------------------------------------------------------------------------------------------------------------
 def _bit_depth(w, bits, exp_bits):  # BitDepthHeader.java:19-28
     w.bool(exp_bits != 0)
@@ -179,7 +245,7 @@ def write_image_header(w, im):
         w.u32(0, (0, 0), (0, 4), (16, 5), (48, 10))  # :27 no name
         if alpha:
             w.bool(e.get("alpha_associated", False))  # :35
-    w.bool(False)  # :254 xyb_encoded
+    w.bool(im.get("xyb", False))  # :254 xyb_encoded
     if im.get("grey", False):  # ColorEncodingBundle.java:29-76
         w.bool(False)  # :30 all_default
         w.bool(False)  # :31 no ICC
