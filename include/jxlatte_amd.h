@@ -951,6 +951,35 @@ jxl_status jxl_planes_tensor_resized(jxl_ctx* ctx, const void* alpha, const jxl_
 jxl_status jxl_canvas_tensor_resized(jxl_ctx* ctx, int32_t id, int32_t alpha_plane, const jxl_tensor_params* p,
                                      const jxl_resize_params* r, void* out_device);
 
+/* ---- N images resampled into one batch tensor in ONE launch ----
+ * Item i's tensor is dense at out_device + i * out_height * out_width * n_out elements, and its bytes are exactly what the
+ * single-image entry of its source kind -- jxl_stage_tensor_resized (JXL_BATCH_HOST), jxl_planes_tensor_resized
+ * (JXL_BATCH_RESIDENT), jxl_canvas_tensor_resized (JXL_BATCH_SET) -- writes for the same p and r, bit for bit: the arithmetic is
+ * the one stated above, every sum one lane's and sequential, so that neither the tile nor the grid nor the batch changes a bit.
+ * All items share out_height, out_width, dtype, layout and the output channel count; everything else is per item: source size,
+ * box, filter, colour parameters, alpha type and depth, premultiplied, normalisation. Two items may name the same set; at most
+ * one item is JXL_BATCH_RESIDENT (a context has one set of resident planes). n is 1 .. JXL_TENSOR_BATCH_MAX: the descriptors
+ * live in device memory, not in the kernel's argument block.
+ * One transfer carries every descriptor, the work list and the tap tables (a table is shared by the items of one length, output
+ * length and filter); one launch; the stream is synchronised once before return.
+ * All or nothing -- if any item is refused nothing is queued and out_device is untouched: JXL_ERR_INVALID_ARGUMENT (JXL_ERR_STATE
+ * for a resident item without resident planes), jxl_last_error "tensor batch: item <i>: <the single-image entry's reason>".
+ * Refused as a batch: n out of range, null arguments, an unknown source, items that disagree on size, dtype, layout or channel
+ * count, a second resident item, an out_device that is not device memory of the context's device or whose allocation ends
+ * before the n-th tensor does. */
+#define JXL_TENSOR_BATCH_MAX 1024
+#define JXL_BATCH_HOST 0      /* in[], alpha: host planes, uploaded once */
+#define JXL_BATCH_RESIDENT 1  /* the context's three resident float planes; alpha: a host plane or NULL */
+#define JXL_BATCH_SET 2       /* planes 0 .. n_planes-1 and alpha_plane (-1: none) of the plane set set_id */
+typedef struct jxl_tensor_batch_item {
+    int32_t source, set_id, alpha_plane;
+    const void* in[3];
+    const void* alpha;
+    jxl_tensor_params p;      /* this image's planes, colour stages, alpha rule */
+    jxl_resize_params r;      /* this image's box; out_height / out_width / filter */
+} jxl_tensor_batch_item;
+jxl_status jxl_tensor_resized_batch(jxl_ctx* ctx, int32_t n, const jxl_tensor_batch_item* items, void* out_device);
+
 /* ---- the PFM's samples in one pass: replaces the body of PFMWriter.write (PFMWriter.java:30-48) after the header ----
  * The planes are the image's own samples (image.getBuffer(false), :30): no colour transform, no peak scale, no transfer
  * function. An int32 plane is cast as castToFloat(image.getTaggedBitDepth(c)) casts it (:33-35; ImageBuffer.java:99-101,

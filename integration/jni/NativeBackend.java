@@ -221,6 +221,12 @@ public final class NativeBackend implements AutoCloseable {
             ByteBuffer resize, long out);                                                             // jxl_stage_tensor_resized
     public native void planesTensorResized(ByteBuffer alpha, ByteBuffer params, ByteBuffer resize, long out);  // jxl_planes_tensor_resized
     public native void canvasTensorResized(int id, int alphaPlane, ByteBuffer params, ByteBuffer resize, long out);  // jxl_canvas_tensor_resized
+    // n images into one batch tensor in ONE launch: heads = 3 ints per item {source (0 host planes, 1 the resident planes, 2 a set),
+    // set id, alpha plane}; params / resize = n jxl_tensor_params / jxl_resize_params back to back; the host planes of all items in
+    // one direct buffer `planes` (null when no item names one), offsets = 4 longs per item: the byte offsets of its three colour
+    // planes and its alpha plane there, -1: none. Item i is written at out + i * (one tensor's bytes); all or nothing
+    public native void tensorResizedBatch(int[] heads, ByteBuffer planes, long[] offsets, ByteBuffer params, ByteBuffer resize,
+            long out);                                                                                // jxl_tensor_resized_batch
     /** shapes: {n, h, w, type[n]}; ref null when desc names no reference. Throws what canvasBlend would; no device needed. */
     public static native void canvasBlendCheck(int[] desc, int[] canvas, int[] frame, int[] ref);    // jxl_canvas_blend_check
 

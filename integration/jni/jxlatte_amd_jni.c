@@ -1587,6 +1587,71 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasTenso
     CHECK(jxl_canvas_tensor_resized(c, id, alphaPlane, &p, &r, (void*)(intptr_t)out));
 }
 
+/* ---- N images into one batch tensor in one launch: the items of jxl_tensor_resized_batch packed from arrays. heads: three ints
+ * per item (source, set id, alpha plane); params / resize: n jxl_tensor_params / jxl_resize_params back to back in direct buffers;
+ * the host planes of all items lie in ONE direct buffer `planes`, offsets: four longs per item (the byte offsets of its three
+ * colour planes and its alpha plane there, -1: none). The shim checks that every plane an item names lies inside `planes` with
+ * its item's height * width samples; `planes` may be null when no item names one. ---- */
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_tensorResizedBatch(JNIEnv* e, jobject self, jintArray heads, jobject planes,
+        jlongArray offsets, jobject params, jobject resize, jlong out) {
+    jxl_ctx* c = ctx_of(e, self);
+    if (!heads || !offsets) {
+        bad_arg(e, "jxlatte_amd: tensorResizedBatch takes three ints and four longs per item");
+        return;
+    }
+    const jsize len = (*e)->GetArrayLength(e, heads);
+    const jsize n = len / 3;
+    if (len % 3 || n < 1 || n > JXL_TENSOR_BATCH_MAX || (*e)->GetArrayLength(e, offsets) != 4 * n) {
+        bad_arg(e, "jxlatte_amd: tensorResizedBatch takes three ints and four longs per item");
+        return;
+    }
+    NEED(params, (jlong)n * (jlong)sizeof(jxl_tensor_params));
+    NEED(resize, (jlong)n * (jlong)sizeof(jxl_resize_params));
+    const char* base = (const char*)ADDR(planes);
+    const jlong room = base ? (*e)->GetDirectBufferCapacity(e, planes) : 0;
+    const char* ps = (const char*)ADDR(params);
+    const char* rs = (const char*)ADDR(resize);
+    jxl_tensor_batch_item* items = (jxl_tensor_batch_item*)calloc((size_t)n, sizeof *items);
+    jint* hd = (jint*)malloc((size_t)len * sizeof(jint));
+    jlong* off = (jlong*)malloc((size_t)n * 4 * sizeof(jlong));
+    int ok = items && hd && off;
+    if (!ok) (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/OutOfMemoryError"), "jxlatte_amd: batch items");
+    if (ok) {
+        (*e)->GetIntArrayRegion(e, heads, 0, len, hd);
+        (*e)->GetLongArrayRegion(e, offsets, 0, 4 * n, off);
+        ok = !(*e)->ExceptionCheck(e);
+    }
+    for (jsize i = 0; ok && i < n; i++) {
+        jxl_tensor_batch_item* it = &items[i];
+        it->source = hd[3 * i], it->set_id = hd[3 * i + 1], it->alpha_plane = hd[3 * i + 2];
+        memcpy(&it->p, ps + (size_t)i * sizeof it->p, sizeof it->p);
+        memcpy(&it->r, rs + (size_t)i * sizeof it->r, sizeof it->r);
+        if (it->p.height < 1 || it->p.width < 1 || it->r.out_height < 1 || it->r.out_width < 1 || it->r.box_width < 1 || it->r.box_height < 1) {
+            bad_arg(e, "jxlatte_amd: tensor or resize parameters of a batch item");
+            ok = 0;
+            break;
+        }
+        const jlong plane = 4 * area(it->p.height, it->p.width);
+        for (int k = 0; k < 4; k++) {
+            const jlong o = off[4 * i + k];
+            if (o == -1) continue;
+            if (o < 0 || plane > room || o > room - plane) {
+                bad_arg(e, "jxlatte_amd: a plane of a batch item lies outside the planes buffer");
+                ok = 0;
+                break;
+            }
+            if (k < 3) it->in[k] = base + o;
+            else it->alpha = base + o;
+        }
+    }
+    jxl_status st = JXL_OK;
+    if (ok) st = jxl_tensor_resized_batch(c, (int32_t)n, items, (void*)(intptr_t)out);
+    free(items);
+    free(hd);
+    free(off);
+    if (ok) CHECK(st);
+}
+
 JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasBlendCheck(JNIEnv* e, jclass k, jintArray desc, jintArray canvas,
         jintArray frame, jintArray ref) {
     (void)k;

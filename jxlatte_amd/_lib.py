@@ -165,6 +165,7 @@ SIGNATURES = {
     "jxl_stage_tensor_resized": (i32, [vp, pv3, vp, C.POINTER(abi.TensorParams), C.POINTER(abi.ResizeParams), vp]),
     "jxl_planes_tensor_resized": (i32, [vp, vp, C.POINTER(abi.TensorParams), C.POINTER(abi.ResizeParams), vp]),
     "jxl_canvas_tensor_resized": (i32, [vp, i32, i32, C.POINTER(abi.TensorParams), C.POINTER(abi.ResizeParams), vp]),
+    "jxl_tensor_resized_batch": (i32, [vp, i32, C.POINTER(abi.TensorBatchItem), vp]),
     "jxl_planes_color_peak": (i32, [vp, C.POINTER(abi.ColorParams), pf]),
     "jxl_planes_orient": (i32, [vp, i32]),
     "jxl_stage_pfm_samples": (i32, [vp, pv3, C.POINTER(abi.PfmParams), vp]),

@@ -228,6 +228,19 @@ class ResizeParams(C.Structure):
 
 assert C.sizeof(ResizeParams) == 28
 
+TENSOR_BATCH_MAX = 1024
+BATCH_HOST, BATCH_RESIDENT, BATCH_SET = 0, 1, 2
+
+
+class TensorBatchItem(C.Structure):
+    """struct jxl_tensor_batch_item"""
+    _fields_ = [("source", C.c_int32), ("set_id", C.c_int32), ("alpha_plane", C.c_int32), ("in_", C.c_void_p * 3),
+                ("alpha", C.c_void_p), ("p", TensorParams), ("r", ResizeParams)]
+
+
+# three int32 and 4 bytes of padding before the pointers; the two parameter blocks are 4-byte aligned, the whole 8-byte aligned
+assert C.sizeof(TensorBatchItem) == (16 + 4 * C.sizeof(C.c_void_p) + C.sizeof(TensorParams) + C.sizeof(ResizeParams) + 7) // 8 * 8
+
 
 class PfmParams(C.Structure):
     """struct jxl_pfm_params"""

@@ -282,6 +282,10 @@ struct ResizeArgs {
     const float *wy, *wx;                          // device: the f32 weights, packed
 };
 void launch_tensor_resize(const ResizeArgs& r, hipStream_t s);
+// N images in one launch (k_tensor_resize_batch.hip): items[n] with their t.out set, tile_base[n + 1] the prefix sum of their tile
+// counts, counts[0] = n -- all device pointers; dtype and n_color are the batch's, lds_bytes the largest of the items'
+void launch_tensor_resize_batch(const ResizeArgs* items, const int64_t* tile_base, const int32_t* counts, int dtype, int n_color,
+                                unsigned grid, int lds_bytes, hipStream_t s);
 // the PFM's samples from the image's planes in one pass (k_pfm.hip): cast of the int32 planes, floatToIntBits, big-endian words,
 // channels interleaved, rows bottom to top (PFMWriter.java:22-49)
 struct PfmArgs {

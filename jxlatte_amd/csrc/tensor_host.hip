@@ -32,7 +32,7 @@ jxl_status tensor_out_check(jxl_ctx* c, const CtxLink& l, void* out, uint64_t by
 }
 
 jxl_status tensor_args(jxl_ctx* c, const CtxLink& l, const jxl_tensor_params* p, const void* const in[3], const void* alpha, void* out,
-                       TensorArgs* t, TensorLayout* lay, int32_t out_height, int32_t out_width) {
+                       TensorArgs* t, TensorLayout* lay, int32_t out_height, int32_t out_width, bool check_out) {
     if (!out) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: null argument");
     const char* why = tensor_check_params(p, lay);
     if (!why && (out_height || out_width)) {  // the tensor is out_height x out_width: its layout, bytes and alignment rule
@@ -50,7 +50,7 @@ jxl_status tensor_args(jxl_ctx* c, const CtxLink& l, const jxl_tensor_params* p,
     int n_color = 0;
     jxl_status st = ctx_png_args(c, &g, in, alpha, out, &t->g, &n_color);
     if (st) return st;
-    if ((st = tensor_out_check(c, l, out, lay->bytes))) return st;
+    if (check_out && (st = tensor_out_check(c, l, out, lay->bytes))) return st;
     t->dtype = p->dtype, t->layout = p->layout;
     t->n_out = lay->n_out;
     t->use_norm = p->use_norm ? 1 : 0;

@@ -2,6 +2,8 @@
 // siblings (tensor_host.hip), whose checks of the parameters, the planes and out_device they share (tensor_args). Their own pure
 // part -- box, size, filter, the tap tables, the tile -- is tensor_resize_check.h's. Nothing is queued before every check has
 // passed; the tables go up once per call, in one transfer; the stream is synchronised before return.
+// The checks of an image's home and the plan of its launch are functions of tensor_host.h: the batch entry
+// (tensor_batch_host.hip) makes the same ones per item.
 #include "tensor_host.h"
 #include "tensor_resize_check.h"
 
@@ -24,26 +26,11 @@ struct Tables {
     ResizeTaps x, y;
 };
 
-// the entry's checks behind tensor_args, without a device call: the tables and the tile into r
-jxl_status resize_plan(jxl_ctx* c, const CtxLink& l, const jxl_tensor_params* p, const jxl_resize_params* rz, const TensorLayout& lay,
-                       ResizeArgs* r, Tables* tb) {
+// the tables of one image
+jxl_status resize_tables(jxl_ctx* c, const jxl_resize_params* rz, Tables* tb) {
     const char* why = resize_build_taps(rz->box_height, rz->out_height, rz->filter, &tb->y);
     if (!why) why = resize_build_taps(rz->box_width, rz->out_width, rz->filter, &tb->x);
-    if (why) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, why);
-    r->planes = lay.n_color + (tensor_alpha_read(p) ? 1 : 0);
-    // the workgroups the device holds at once: two per compute unit (the kernel's registers allow two waves per SIMD)
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, l.device) != hipSuccess) cus = 0, (void)hipGetLastError();
-    ResizeTile tile;
-    if ((why = resize_pick_tile(tb->x, rz->box_x0, tb->y, r->planes, g_skew, 2 * (int64_t)cus, g_force_tw, g_force_th, &tile)))
-        return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, why);
-    r->src_w = p->width;
-    r->x0 = rz->box_x0, r->y0 = rz->box_y0;
-    r->oh = rz->out_height, r->ow = rz->out_width;
-    r->tw = tile.tw, r->th = tile.th;
-    r->lds_w = tile.lds_w, r->lds_bytes = tile.lds_bytes;
-    r->skew = g_skew ? 1 : 0;
-    return JXL_OK;
+    return why ? ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, why) : JXL_OK;
 }
 
 // the tables to the device in one transfer, the launch, the synchronisation (the plane pointers of r->t are set)
@@ -68,29 +55,97 @@ jxl_status resize_run(jxl_ctx* c, const CtxLink& l, ResizeArgs* r, const Tables&
     r->yfirst = (const int32_t*)(d + where[0]), r->yoff = (const int32_t*)(d + where[1]);
     r->xfirst = (const int32_t*)(d + where[2]), r->xoff = (const int32_t*)(d + where[3]);
     r->wy = (const float*)(d + where[4]), r->wx = (const float*)(d + where[5]);
-    uint64_t bases[4];
-    int nb = 0;
-    for (int i = 0; i < r->t.g.c.n_planes; i++) bases[nb++] = (uint64_t)(uintptr_t)r->t.g.c.in[i];
-    if (r->t.g.alpha) bases[nb++] = (uint64_t)(uintptr_t)r->t.g.alpha;
-    r->wide_in = resize_wide_in_ok(r->src_w, bases, nb) ? 1 : 0;
+    resize_set_wide_in(r);
     launch_tensor_resize(*r, l.stream);
     TR_HIP(c, hipStreamSynchronize(l.stream));
     TR_HIP(c, hipGetLastError());
     return JXL_OK;
 }
 
-// the checks every entry makes first: the pure ones of the resize, then tensor_args with the tensor's size
-jxl_status resize_args(jxl_ctx* c, const CtxLink& l, const jxl_tensor_params* p, const jxl_resize_params* rz, const void* const in[3],
-                       const void* alpha, void* out, ResizeArgs* r, TensorLayout* lay, Tables* tb) {
-    if (!out) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: null argument");
-    const char* why = resize_check_params(p, rz);
-    if (why) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, why);
-    jxl_status st = tensor_args(c, l, p, in, alpha, out, &r->t, lay, rz->out_height, rz->out_width);
+// resize_args, the tables and the plan of a single image
+jxl_status resize_single(jxl_ctx* c, const CtxLink& l, const jxl_tensor_params* p, const jxl_resize_params* rz, const void* const in[3],
+                         const void* alpha, void* out, ResizeArgs* r, TensorLayout* lay, Tables* tb) {
+    jxl_status st = resize_args(c, l, p, rz, in, alpha, out, r, lay);
     if (st) return st;
-    return resize_plan(c, l, p, rz, *lay, r, tb);
+    if ((st = resize_tables(c, rz, tb))) return st;
+    return resize_plan(c, p, rz, *lay, tb->x, tb->y, resize_slots(l), r);
 }
 
 }  // namespace
+
+int64_t resize_slots(const CtxLink& l) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, l.device) != hipSuccess) cus = 0, (void)hipGetLastError();
+    return 2 * (int64_t)cus;
+}
+
+jxl_status resize_plan(jxl_ctx* c, const jxl_tensor_params* p, const jxl_resize_params* rz, const TensorLayout& lay, const ResizeTaps& x,
+                       const ResizeTaps& y, int64_t slots, ResizeArgs* r) {
+    r->planes = lay.n_color + (tensor_alpha_read(p) ? 1 : 0);
+    ResizeTile tile;
+    const char* why = resize_pick_tile(x, rz->box_x0, y, r->planes, g_skew, slots, g_force_tw, g_force_th, &tile);
+    if (why) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, why);
+    r->src_w = p->width;
+    r->x0 = rz->box_x0, r->y0 = rz->box_y0;
+    r->oh = rz->out_height, r->ow = rz->out_width;
+    r->tw = tile.tw, r->th = tile.th;
+    r->lds_w = tile.lds_w, r->lds_bytes = tile.lds_bytes;
+    r->skew = g_skew ? 1 : 0;
+    return JXL_OK;
+}
+
+void resize_set_wide_in(ResizeArgs* r) {
+    uint64_t bases[4];
+    int nb = 0;
+    for (int i = 0; i < r->t.g.c.n_planes; i++) bases[nb++] = (uint64_t)(uintptr_t)r->t.g.c.in[i];
+    if (r->t.g.alpha) bases[nb++] = (uint64_t)(uintptr_t)r->t.g.alpha;
+    r->wide_in = resize_wide_in_ok(r->src_w, bases, nb) ? 1 : 0;
+}
+
+jxl_status resize_args(jxl_ctx* c, const CtxLink& l, const jxl_tensor_params* p, const jxl_resize_params* rz, const void* const in[3],
+                       const void* alpha, void* out, ResizeArgs* r, TensorLayout* lay, bool check_out) {
+    if (!out) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: null argument");
+    const char* why = resize_check_params(p, rz);
+    if (why) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, why);
+    return tensor_args(c, l, p, in, alpha, out, &r->t, lay, rz->out_height, rz->out_width, check_out);
+}
+
+jxl_status resize_home_resident(jxl_ctx* c, int* h, int* w, const void* in[3]) {
+    float* rp[3];
+    jxl_status st = ctx_planes_get(c, h, w, rp);
+    if (st) return st;
+    for (int i = 0; i < 3; i++) in[i] = rp[i];
+    return JXL_OK;
+}
+
+jxl_status resize_home_resident_fits(jxl_ctx* c, const jxl_tensor_params* p, int h, int w) {
+    if (p->color.n_planes != 3 || p->color.in_is_int || p->height != h || p->width != w)
+        return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: the resident planes are three float planes of another size");
+    return JXL_OK;
+}
+
+jxl_status resize_home_set(jxl_ctx* c, const CtxLink& l, int32_t id, int32_t alpha_plane, const jxl_tensor_params* p, CanvasView* v,
+                           const void* in[3], const void** alpha) {
+    if (!canvas_view(*l.canvas, id, v)) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+    if (!p) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: null argument");
+    const int nc = p->color.n_planes;
+    if ((nc != 1 && nc != 3) || nc > v->n || alpha_plane < -1 || alpha_plane >= v->n || (p->has_alpha != 0) != (alpha_plane >= 0))
+        return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: the set has no such planes");
+    in[0] = in[1] = in[2] = nullptr;
+    for (int i = 0; i < nc; i++) in[i] = v->plane[i];
+    *alpha = alpha_plane >= 0 ? v->plane[alpha_plane] : nullptr;
+    return JXL_OK;
+}
+
+jxl_status resize_home_set_fits(jxl_ctx* c, const jxl_tensor_params* p, const CanvasView& v, int32_t alpha_plane) {
+    const int nc = p->color.n_planes;
+    bool tags = p->height == v.h && p->width == v.w;
+    for (int i = 0; i < nc; i++) tags = tags && (p->color.in_is_int != 0) == (v.type[i] == JXL_PLANE_INT32);
+    if (alpha_plane >= 0) tags = tags && (p->alpha_is_int != 0) == (v.type[alpha_plane] == JXL_PLANE_INT32);
+    if (!tags) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: the parameters do not describe the set's planes");
+    return JXL_OK;
+}
+
 }  // namespace jxl
 
 using namespace jxl;
@@ -105,7 +160,7 @@ jxl_status jxl_stage_tensor_resized(jxl_ctx* c, const void* const in[3], const v
     ResizeArgs r;
     TensorLayout lay;
     Tables tb;
-    if ((st = resize_args(c, l, p, rz, in, alpha, out_device, &r, &lay, &tb))) return st;
+    if ((st = resize_single(c, l, p, rz, in, alpha, out_device, &r, &lay, &tb))) return st;
     Staged s;
     const size_t plane = (size_t)p->height * (size_t)p->width * 4;
     for (int i = 0; i < p->color.n_planes; i++)
@@ -120,15 +175,13 @@ jxl_status jxl_planes_tensor_resized(jxl_ctx* c, const void* alpha, const jxl_te
     jxl_status st = ctx_link(c, &l);
     if (st) return st;
     int h = 0, w = 0;
-    float* rp[3];
-    if ((st = ctx_planes_get(c, &h, &w, rp))) return st;
-    const void* in[3] = {rp[0], rp[1], rp[2]};
+    const void* in[3];
+    if ((st = resize_home_resident(c, &h, &w, in))) return st;
     ResizeArgs r;
     TensorLayout lay;
     Tables tb;
-    if ((st = resize_args(c, l, p, rz, in, alpha, out_device, &r, &lay, &tb))) return st;
-    if (p->color.n_planes != 3 || p->color.in_is_int || p->height != h || p->width != w)
-        return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: the resident planes are three float planes of another size");
+    if ((st = resize_single(c, l, p, rz, in, alpha, out_device, &r, &lay, &tb))) return st;
+    if ((st = resize_home_resident_fits(c, p, h, w))) return st;
     for (int i = 0; i < 3; i++) r.t.g.c.in[i] = in[i];
     Staged s;
     if (tensor_alpha_read(p) && !(r.t.g.alpha = s.up(alpha, (size_t)h * (size_t)w * 4))) return ctx_fail(c, JXL_ERR_OOM, "device allocation failed");
@@ -141,23 +194,15 @@ jxl_status jxl_canvas_tensor_resized(jxl_ctx* c, int32_t id, int32_t alpha_plane
     jxl_status st = ctx_link(c, &l);
     if (st) return st;
     CanvasView v;
-    if (!canvas_view(*l.canvas, id, &v)) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
-    if (!p) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: null argument");
-    const int nc = p->color.n_planes;
-    if ((nc != 1 && nc != 3) || nc > v.n || alpha_plane < -1 || alpha_plane >= v.n || (p->has_alpha != 0) != (alpha_plane >= 0))
-        return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: the set has no such planes");
-    const void* in[3] = {nullptr, nullptr, nullptr};
-    for (int i = 0; i < nc; i++) in[i] = v.plane[i];
-    const void* alpha = alpha_plane >= 0 ? v.plane[alpha_plane] : nullptr;
+    const void* in[3];
+    const void* alpha = nullptr;
+    if ((st = resize_home_set(c, l, id, alpha_plane, p, &v, in, &alpha))) return st;
     ResizeArgs r;
     TensorLayout lay;
     Tables tb;
-    if ((st = resize_args(c, l, p, rz, in, alpha, out_device, &r, &lay, &tb))) return st;
-    bool tags = p->height == v.h && p->width == v.w;
-    for (int i = 0; i < nc; i++) tags = tags && (p->color.in_is_int != 0) == (v.type[i] == JXL_PLANE_INT32);
-    if (alpha_plane >= 0) tags = tags && (p->alpha_is_int != 0) == (v.type[alpha_plane] == JXL_PLANE_INT32);
-    if (!tags) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: the parameters do not describe the set's planes");
-    for (int i = 0; i < nc; i++) r.t.g.c.in[i] = in[i];
+    if ((st = resize_single(c, l, p, rz, in, alpha, out_device, &r, &lay, &tb))) return st;
+    if ((st = resize_home_set_fits(c, p, v, alpha_plane))) return st;
+    for (int i = 0; i < p->color.n_planes; i++) r.t.g.c.in[i] = in[i];
     if (tensor_alpha_read(p)) r.t.g.alpha = alpha;
     Staged s;
     return resize_run(c, l, &r, tb, &s);

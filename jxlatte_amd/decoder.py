@@ -759,6 +759,11 @@ class DeviceBackend:
         """the image resampled to a device tensor in one pass (host.tensorResized)"""
         return self.host.tensorResized(self.ctx, planes, alpha, out_ptr, size, box, resample, **params)
 
+    def tensor_resized_batch(self, items, out_ptr):
+        """N images resampled into one batch tensor in one launch (host.tensorResizedBatch). items: per image the keywords of
+        host.tensorBatchItem; out_ptr: the DEVICE address of the batch"""
+        return self.host.tensorResizedBatch(self.ctx, [self.host.tensorBatchItem(**it) for it in items], out_ptr)
+
     def tensor_device(self):
         """the torch device of the memory tensor_samples writes"""
         return "cuda:%d" % self.ctx.device
@@ -938,10 +943,29 @@ class JXLImage:
         be = self.backend
         if not hasattr(be, "tensor_samples"):
             raise TypeError("toTensor needs a backend with tensor_samples")
+        if (size is not None or box is not None) and not hasattr(be, "tensor_resized"):
+            raise TypeError("toTensor(size=, box=) needs a backend with tensor_resized")
+        resize, dtype, name, channels, mean, inv_std = self._tensor_request(torch, dtype, layout, target, alpha, mean, std, size, box, resample)
+        oh, ow = (self.height, self.width) if resize is None else resize[0]
+        shape = (channels, oh, ow) if layout == "CHW" else (oh, ow, channels)
+        device = torch.device(be.tensor_device())
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != device or not out.is_contiguous():
+                raise ValueError("out: a contiguous %s tensor of shape %s on %s" % (name, shape, device))
+        planes, kw, up = self._tensor_plan(target, peakDetect, alpha, name, layout, mean, inv_std)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=device)
+        elif device.type == "cuda":
+            torch.cuda.current_stream(device).synchronize()  # what the caller queued on its tensor is done before the library writes
+        sent = self._tensor_samples(planes, out.data_ptr(), resize=resize, **kw)
+        self.tensor_bus_bytes = (up + sent, 0)
+        return out
+
+    def _tensor_request(self, torch, dtype, layout, target, alpha, mean, std, size, box, resample):
+        """toTensor's arguments checked against the image, before any call: (resize, dtype, its name, channels, mean, inv_std);
+        resize: None, or (size, box, resample)"""
         resize = None
         if size is not None or box is not None:
-            if not hasattr(be, "tensor_resized"):
-                raise TypeError("toTensor(size=, box=) needs a backend with tensor_resized")
             if resample not in ("triangle", "box"):
                 raise ValueError("resample: triangle or box")
             try:
@@ -976,8 +1000,7 @@ class JXLImage:
         if mean is not None and dtype == torch.uint8:
             raise ValueError("normalisation is for the float dtypes")
         colors = self.getColorChannelCount()
-        as_is = target == "as-is" or self.has_icc
-        primaries, tf = {"srgb": (PRI_SRGB, TF_SRGB), "pq": (PRI_BT2100, TF_PQ), "linear": (PRI_SRGB, TF_LINEAR)}.get(target, (None, None))
+        primaries, _, as_is = self._tensor_target(target)
         tone_map = not as_is and not (_prim_matches(primaries, self.primariesXY) and _xy_matches(WP_D65, self.whiteXY))
         channels = (3 if (colors == 3 or tone_map) else 1) + (alpha == "append")
         inv_std = None
@@ -989,12 +1012,19 @@ class JXLImage:
                 inv_std = [F(1) / F(s) for s in std]
             if not all(np.isfinite(v) for v in inv_std):
                 raise ValueError("std: 1 / std is not finite")
-        oh, ow = (self.height, self.width) if resize is None else resize[0]
-        shape = (channels, oh, ow) if layout == "CHW" else (oh, ow, channels)
-        device = torch.device(be.tensor_device())
-        if out is not None:
-            if not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != device or not out.is_contiguous():
-                raise ValueError("out: a contiguous %s tensor of shape %s on %s" % (names[dtype], shape, device))
+        return resize, dtype, names[dtype], channels, mean, inv_std
+
+    def _tensor_target(self, target):
+        """(primaries, transfer, as_is) of a toTensor target"""
+        as_is = target == "as-is" or self.has_icc
+        primaries, tf = {"srgb": (PRI_SRGB, TF_SRGB), "pq": (PRI_BT2100, TF_PQ), "linear": (PRI_SRGB, TF_LINEAR)}.get(target, (None, None))
+        return primaries, tf, as_is
+
+    def _tensor_plan(self, target, peakDetect, alpha, dtype_name, layout, mean, inv_std):
+        """the colour plan of a checked toTensor request, with at most one _peak call: (planes, _tensor_samples' keywords, bytes
+        the peak sent up)"""
+        colors = self.getColorChannelCount()
+        primaries, tf, as_is = self._tensor_target(target)
         up = 0
         planes = self._plan_planes(colors)  # (stand-ins while the samples are on the device)
 
@@ -1012,17 +1042,26 @@ class JXLImage:
                 if len({a.dtype for a in planes}) != 1:
                     planes = [self._as_float(c) for c in range(colors)]
             params = dict(inMax=[(1 << self.bitDepths[c]) - 1 for c in range(colors)])
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=device)
-        elif device.type == "cuda":
-            torch.cuda.current_stream(device).synchronize()  # what the caller queued on its tensor is done before the library writes
         has_alpha = self.alphaIndex >= 0
-        sent = self._tensor_samples(
-            planes, out.data_ptr(), resize=resize, premultiplied=self.isAlphaPremultiplied() and has_alpha, writeAlpha=alpha == "append",
-            dtype=names[dtype], layout=layout, alphaDepth=self.getTaggedBitDepth(colors + self.alphaIndex) if has_alpha else None,
-            colorDepth=self.getTaggedBitDepth(0), mean=mean, invStd=inv_std, **params)
-        self.tensor_bus_bytes = (up + sent, 0)
-        return out
+        kw = dict(premultiplied=self.isAlphaPremultiplied() and has_alpha, writeAlpha=alpha == "append", dtype=dtype_name, layout=layout,
+                  alphaDepth=self.getTaggedBitDepth(colors + self.alphaIndex) if has_alpha else None, colorDepth=self.getTaggedBitDepth(0),
+                  mean=mean, invStd=inv_std, **params)
+        return planes, kw, up
+
+    def _tensor_batch_item(self, planes, resize, **kw):
+        """this image as one item of Backend.tensor_resized_batch, from the home _tensor_samples would read: (item, bytes that
+        go up). item: the keywords of host.tensorBatchItem"""
+        colors, a = len(planes), self.alphaIndex
+        size, box, resample = resize
+        home = self._home(colors, True)
+        if home == "set":
+            return dict(size=size, box=box, resample=resample, canvas=self.planeSet, nColor=colors, alphaPlane=colors + a if a >= 0 else None, **kw), 0
+        alpha = np.ascontiguousarray(self.extraChannel(a)) if a >= 0 else None
+        up = alpha.nbytes if alpha is not None and (kw.get("writeAlpha") or kw.get("premultiplied")) else 0
+        if home == "resident":
+            return dict(size=size, box=box, resample=resample, resident=self.resident, alpha=alpha, **kw), up
+        planes = [np.ascontiguousarray(p) for p in planes]
+        return dict(size=size, box=box, resample=resample, planes=planes, alpha=alpha, **kw), up + sum(p.nbytes for p in planes)
 
     def _pfm_samples(self, tagged):
         """PFMWriter's samples in one pass: (samples, bytes sent up). A set's planes, int32 or float, as they are"""
@@ -1220,6 +1259,60 @@ class JXLImage:
         if _prim_matches(primaries, self.primariesXY) and _xy_matches(whitePoint, self.whiteXY):
             return self.transfer(transfer, peakDetect)
         return self.linearize().fillColor().toneMapLinear(primaries, whitePoint).transfer(transfer, peakDetect)
+
+
+def toTensorBatch(images, size, boxes=None, dtype=None, layout="CHW", target="srgb", peakDetect=PEAK_DETECT_AUTO, alpha="drop", mean=None,
+                  std=None, out=None, resample="triangle"):
+    """N decoded images as ONE torch tensor on their backend's device, (N, C, h, w) or (N, h, w, C), in ONE launch: image i is
+    resampled to `size` = (h, w) exactly as images[i].toTensor(size=size, box=boxes[i], ...) resamples it -- bit for bit -- from
+    wherever its planes are (a plane set, the resident planes, host arrays), each with the colour plan toTensor builds for it
+    (at most one peak detection per image). boxes: None, or per image None or (x0, y0, w, h). The other arguments are
+    toTensor's, one value for the batch. All images are on one backend and their plans give one channel count (a grey image
+    does not join colour ones); ValueError before any call otherwise, and for everything toTensor raises.
+    out: a contiguous tensor of the batch's shape and dtype on that device -- a slice batch[a:a + N] of a larger batch is one --
+    filled in place and returned; the current torch stream is synchronised first. Each image's tensor_bus_bytes is set as
+    toTensor sets it; the batch's total is the returned tensor's bus_bytes = (bytes up, 0)."""
+    import torch
+    images = list(images)
+    if not images:
+        raise ValueError("toTensorBatch: no image")
+    if any(not isinstance(im, JXLImage) for im in images):
+        raise ValueError("toTensorBatch: JXLImage objects")
+    be = images[0].backend
+    if any(im.backend is not be for im in images):
+        raise ValueError("toTensorBatch: the images are on different backends")
+    if not hasattr(be, "tensor_resized_batch"):
+        raise TypeError("toTensorBatch needs a backend with tensor_resized_batch")
+    if size is None:
+        raise ValueError("size: (height, width)")
+    boxes = [None] * len(images) if boxes is None else list(boxes)
+    if len(boxes) != len(images):
+        raise ValueError("boxes: one box (or None) per image")
+    reqs = [im._tensor_request(torch, dtype, layout, target, alpha, mean, std, size, bx, resample) for im, bx in zip(images, boxes)]
+    resize0, dtype, name, channels, _, _ = reqs[0]
+    if any(r[3] != channels for r in reqs):
+        raise ValueError("toTensorBatch: the images give different channel counts (%s)" % sorted({r[3] for r in reqs}))
+    (oh, ow), n = resize0[0], len(images)
+    shape = (n, channels, oh, ow) if layout == "CHW" else (n, oh, ow, channels)
+    device = torch.device(be.tensor_device())
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != device or not out.is_contiguous():
+            raise ValueError("out: a contiguous %s tensor of shape %s on %s" % (name, shape, device))
+    items, sent = [], []
+    for im, req in zip(images, reqs):
+        planes, kw, up = im._tensor_plan(target, peakDetect, alpha, name, layout, req[4], req[5])
+        item, more = im._tensor_batch_item(planes, req[0], **kw)
+        items.append(item)
+        sent.append(up + more)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=device)
+    elif device.type == "cuda":
+        torch.cuda.current_stream(device).synchronize()  # what the caller queued on its tensor is done before the library writes
+    be.tensor_resized_batch(items, out.data_ptr())
+    for im, b in zip(images, sent):
+        im.tensor_bus_bytes = (b, 0)
+    out.bus_bytes = (sum(sent), 0)
+    return out
 
 
 # ---- a frame's channels between decodeFrame and the blend ---------------------------------------------------------

@@ -332,6 +332,54 @@ def tensorResized(ctx, planes, alpha, out_ptr, size, box=None, resample="triangl
     return p, r
 
 
+def tensorBatchItem(size, box=None, resample="triangle", planes=None, alpha=None, canvas=None, resident=None, nColor=3, alphaPlane=None,
+                    **params):
+    """One jxl_tensor_batch_item: an image where it is, its parameters and its box. Exactly one home: `planes` (host arrays, with
+    the host plane `alpha`), `resident` (a ResidentPlanes, with the host plane `alpha`) or `canvas` (a DeviceCanvas: planes
+    0 .. nColor - 1 and the plane alphaPlane). size / box / resample: resizeParams'; params: tensorParams' keywords. The item
+    keeps the host arrays it points to alive (item.keep)."""
+    if (planes is not None) + (resident is not None) + (canvas is not None) != 1:
+        raise ValueError("one home: planes, resident or canvas")
+    it = abi.TensorBatchItem()
+    it.set_id, it.alpha_plane = -1, -1
+    if canvas is not None:
+        canvas._live()
+        ap = -1 if alphaPlane is None else int(alphaPlane)
+        a = None if ap < 0 else np.broadcast_to(np.zeros((), _PLANE_DTYPE[canvas.types[ap]]), canvas.shape)
+        shape, stand, keep = canvas.shape, canvas._stand_ins(nColor), []
+        it.source, it.set_id, it.alpha_plane = abi.BATCH_SET, int(canvas.id), ap
+    elif resident is not None:
+        resident._need_live()
+        shape, stand = resident.shape, resident._stand_ins()
+        a = _png_alpha(alpha, shape)
+        keep = [a]
+        it.source = abi.BATCH_RESIDENT
+        it.alpha = None if a is None else a.ctypes.data
+    else:
+        stand = [np.ascontiguousarray(pl) for pl in planes]
+        shape = stand[0].shape
+        a = _png_alpha(alpha, shape)
+        keep = stand + [a]
+        it.source = abi.BATCH_HOST
+        for c, pl in enumerate(stand):
+            it.in_[c] = pl.ctypes.data
+        it.alpha = None if a is None else a.ctypes.data
+    it.p = tensorParams(stand, shape, alpha=a, **params)
+    it.r = resizeParams(shape, size, box, resample)
+    it.keep = keep
+    return it
+
+
+def tensorResizedBatch(ctx, items, out_ptr):
+    """N images resampled into one batch tensor in ONE launch (jxl_tensor_resized_batch). items: tensorBatchItem()s that agree
+    on size, dtype, layout and channel count; item i is written dense at out_ptr + i * (one tensor's bytes), bit for bit what
+    tensorResized of its home writes. out_ptr: DEVICE memory for all of them. All or nothing; complete on return."""
+    items = list(items)
+    arr = (abi.TensorBatchItem * max(1, len(items)))(*items)  # (the items stay referenced, and with them their host arrays)
+    ctx.call("jxl_tensor_resized_batch", len(items), arr, C.c_void_p(int(out_ptr)))
+    return arr
+
+
 def pfmParams(planes, shape, taggedDepths=None):
     """jxl_pfm_params of 1 or 3 planes (each one's dtype tells int32 from float32). taggedDepths: image.getTaggedBitDepth(c)
     per plane, looked at for the int32 planes only"""
