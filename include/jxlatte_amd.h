@@ -373,6 +373,30 @@ jxl_status jxl_planes_noise(jxl_ctx* ctx, int32_t group_dim, uint64_t seed0, con
 jxl_status jxl_planes_xyb(jxl_ctx* ctx, const float matrix[9], const float opsin_bias[3], const float cbrt_opsin_bias[3],
                           float intensity_target);
 jxl_status jxl_planes_ycbcr(jxl_ctx* ctx);
+/* ---- the LF image as the picture at 1:8 (JXLDecoder(downsample=8)) ----------------------------------------------------------
+ * A VarDCT frame's LF image is the frame at one sample per 8x8 cell. This turns the INTEGER LF images of ALL the frame's LF
+ * groups into three float planes of cells_h x cells_w samples in ONE launch behind ONE transfer: per LF group the LF stage of
+ * jxl_vardct_set_lfgroup_lfquant / jxl_stage_lf_dequant (LFCoefficients.java:65-75 dequant, :78-95 LF chroma-from-luma,
+ * :113-180 adaptiveSmooth -- per LF group: its border cells are copied, nothing is smoothed across a seam), then, with xyb != 0,
+ * OpsinInverseMatrix.invertXYB as jxl_planes_xyb runs it. No HF coefficient is involved: this is a 1:8 preview (the full decode
+ * box-averaged 8x8 up to the restoration filters and the LLF of large varblocks), not the reference's pixels.
+ * groups: the frame's LF groups in any order, each at its (lfg_y, lfg_x) with all three planes cells_h x cells_w; LF group
+ * (gy, gx) must be min(256, cells - 256 g) cells in each axis, and every position of the ceil(cells_h / 256) x
+ * ceil(cells_w / 256) grid must occur exactly once. */
+typedef struct jxl_lf_image_desc {
+    int32_t n_groups;
+    int32_t cells_h, cells_w;       /* the output: ceil(frame_h / 8) x ceil(frame_w / 8) */
+    int32_t color_factor;           /* LFChannelCorrelation.colorFactor, != 0 */
+    const jxl_lfquant_desc* groups; /* [n_groups] */
+    float base_corr_x, base_corr_b;
+    int32_t xyb;                    /* != 0: the inverse XYB follows, with the four fields below as jxl_planes_xyb takes them */
+    float opsin_matrix[9], opsin_bias[3], cbrt_opsin_bias[3], intensity_target;
+} jxl_lf_image_desc;
+/* the planes become the context's resident planes (cells_h x cells_w): jxl_planes_ycbcr, jxl_planes_orient, the writers and the
+ * tensor entries of the resident planes follow as after jxl_planes_from_frame. Nothing comes down. */
+jxl_status jxl_planes_from_lf(jxl_ctx* ctx, const jxl_lf_image_desc* d);
+/* the same launch into three host planes of cells_h x cells_w floats; the resident planes are left alone */
+jxl_status jxl_stage_lf_image(jxl_ctx* ctx, const jxl_lf_image_desc* d, float* const out[3]);
 /* ---- splines: Frame.renderSplines (J/frame/Frame.java:739-746) + Spline.renderSpline (J/frame/features/spline/Spline.java:27-200) ----
  * The splines of one frame as SplinesBundle.java:22-73 decodes them, plus the two LFChannelCorrelation factors computeCoeffs reads
  * (Spline.java:133-152). coeff: per spline 4 rows of 32 -- coeffX, coeffY, coeffB, coeffSigma. */

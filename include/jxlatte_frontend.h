@@ -187,6 +187,14 @@ int32_t jxf_get_modular_channel(const jxf_dec* d, int32_t index, jxf_chan* out);
  * loop refuses ("RCT channel range", "RCT must be performed on three equal size channels", "Palette channel range") is refused
  * by jxf_next_frame with the same error. Default off: jxf_next_frame then behaves exactly as before. */
 int32_t jxf_set_defer_transforms(jxf_dec* d, int32_t on);
+/* ---- LF-only decoding: the frame's LF image and nothing behind it (the 1:8 preview of a VarDCT frame) ----
+ * on != 0: of a VarDCT frame decoded from now on jxf_next_frame reads LfGlobal and, of every LF-group section, the LF
+ * coefficients only -- no HF metadata, no HfGlobal, no pass group. The frame then needs only the bytes up to the end of its
+ * last LF-group section: a missing tail is reported when the NEXT frame is asked for. jxf_get_lfgroup answers lf_quant,
+ * extra_precision and the cell sizes with n_blocks == 0 and null block maps; jxf_get_coeffs* answer JXF_ERR_STATE; the
+ * HfGlobal fields of jxf_frame_info say nothing about the frame. A frame whose LF-group sections carry modular channels (extra channels at
+ * 1:8) is refused with JXF_ERR_UNSUPPORTED. Modular frames ignore the switch. Default off: nothing behaves differently. */
+int32_t jxf_set_lf_only(jxf_dec* d, int32_t on);
 #define JXF_TRANSFORM_RCT 0
 #define JXF_TRANSFORM_PALETTE 1
 #define JXF_TRANSFORM_SQUEEZE 2

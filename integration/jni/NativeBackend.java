@@ -127,6 +127,11 @@ public final class NativeBackend implements AutoCloseable {
     public native void stageLfDequant(int lfgY, int lfgX, int cellsH, int cellsW, ByteBuffer qX, ByteBuffer qY, ByteBuffer qB,
         int extraPrecision, float[] scaledDequant, int xFactorLF, int bFactorLF, boolean adaptiveSmoothing, float baseCorrX,
         float baseCorrB, int colorFactor, ByteBuffer o0, ByteBuffer o1, ByteBuffer o2); // jxl_stage_lf_dequant (LFCoefficients)
+    // the LF image of a frame as the picture at 1:8 in one launch. heads = per LF group {lfgY, lfgX, cellsH, cellsW, extraPrecision,
+    // xFactorLF, bFactorLF, adaptiveSmoothing}; scaledDequant = 3 floats per group; ints = every group's X, Y, B planes back to back;
+    // xyb = null or {matrix[9], opsinBias[3], cbrtOpsinBias[3], intensityTarget}; o0..o2 all null: the planes stay resident
+    public native void lfImage(int[] heads, float[] scaledDequant, ByteBuffer ints, int cellsH, int cellsW, float baseCorrX, float baseCorrB,
+        int colorFactor, float[] xyb, ByteBuffer o0, ByteBuffer o1, ByteBuffer o2);   // jxl_stage_lf_image / jxl_planes_from_lf
     public native void stageXyb(ByteBuffer p0, ByteBuffer p1, ByteBuffer p2, long n, float[] matrix, float[] opsinBias, float[] cbrtOpsinBias,
         float intensityTarget);                                    // jxl_stage_xyb (OpsinInverseMatrix.invertXYB)
     public native void stageYcbcr(ByteBuffer p0, ByteBuffer p1, ByteBuffer p2, long n);               // jxl_stage_ycbcr

@@ -946,6 +946,86 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageLfDequ
     CHECK(jxl_stage_lf_dequant(c, &d, baseCorrX, baseCorrB, colorFactor, out));
 }
 
+/* ---- the LF image of a frame as the picture at 1:8, one launch. heads: eight ints per LF group (lfg_y, lfg_x, cells_h, cells_w,
+ * extra_precision, x_factor_lf, b_factor_lf, adaptive_smoothing); scaledDequant: three floats per group; ints: every group's X, Y, B
+ * planes back to back, in the groups' order, in ONE direct buffer; xyb: null, or 16 floats (matrix, opsin bias, cbrt opsin bias,
+ * intensity target). o0..o2: three host planes of cellsH x cellsW floats (jxl_stage_lf_image), or all null: the planes become the
+ * resident planes (jxl_planes_from_lf). ---- */
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_lfImage(JNIEnv* e, jobject self, jintArray heads, jfloatArray scaledDequant,
+        jobject ints, jint cellsH, jint cellsW, jfloat baseCorrX, jfloat baseCorrB, jint colorFactor, jfloatArray xyb, jobject o0, jobject o1,
+        jobject o2) {
+    jxl_ctx* c = ctx_of(e, self);
+    if (!heads || !scaledDequant) {
+        bad_arg(e, "jxlatte_amd: lfImage takes eight ints and three floats per LF group");
+        return;
+    }
+    const jsize len = (*e)->GetArrayLength(e, heads);
+    const jsize n = len / 8;
+    if (len % 8 || n < 1 || n > (1 << 16) || (*e)->GetArrayLength(e, scaledDequant) != 3 * n) {
+        bad_arg(e, "jxlatte_amd: lfImage takes eight ints and three floats per LF group");
+        return;
+    }
+    jxl_lf_image_desc d;
+    memset(&d, 0, sizeof d);
+    if (xyb) {
+        float v[16];
+        GETF(xyb, 16, v);
+        d.xyb = 1;
+        memcpy(d.opsin_matrix, v, sizeof d.opsin_matrix);
+        memcpy(d.opsin_bias, v + 9, sizeof d.opsin_bias);
+        memcpy(d.cbrt_opsin_bias, v + 12, sizeof d.cbrt_opsin_bias);
+        d.intensity_target = v[15];
+    }
+    const int to_host = o0 || o1 || o2;
+    if (to_host) {
+        NEED(o0, 4 * area(cellsH, cellsW)); NEED(o1, 4 * area(cellsH, cellsW)); NEED(o2, 4 * area(cellsH, cellsW));
+    }
+    jint* hd = (jint*)malloc(sizeof(jint) * (size_t)len);
+    float* sd = (float*)malloc(sizeof(float) * 3 * (size_t)n);
+    jxl_lfquant_desc* g = (jxl_lfquant_desc*)calloc((size_t)n, sizeof *g);
+    int ok = hd && sd && g;
+    if (!ok) (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/OutOfMemoryError"), "jxlatte_amd: lfImage");
+    if (ok) ok = get_ints(e, heads, len, hd) && get_floats(e, scaledDequant, 3 * n, sd);
+    jlong at = 0;  /* int32s of `ints` used so far */
+    for (jsize i = 0; ok && i < n; i++) {
+        const jint* h = hd + 8 * (size_t)i;
+        if (h[2] < 1 || h[3] < 1 || h[2] > 256 || h[3] > 256) {
+            bad_arg(e, "jxlatte_amd: lfImage: bad LF group size");
+            ok = 0;
+            break;
+        }
+        g[i].lfg_y = h[0]; g[i].lfg_x = h[1]; g[i].cells_h = h[2]; g[i].cells_w = h[3];
+        g[i].extra_precision = h[4]; g[i].x_factor_lf = h[5]; g[i].b_factor_lf = h[6]; g[i].adaptive_smoothing = h[7] ? 1 : 0;
+        for (int k = 0; k < 3; k++) {
+            g[i].scaled_dequant[k] = sd[3 * (size_t)i + k];
+            g[i].lf_quant[k] = (const int32_t*)(intptr_t)at;  /* an offset until the buffer's size is known to hold them all */
+            at += (jlong)h[2] * h[3];
+        }
+    }
+    if (ok && !has_room(e, ints, 4 * at)) {
+        bad_arg(e, "jxlatte_amd: direct buffer ints missing or too small");
+        ok = 0;
+    }
+    jxl_status st = JXL_OK;
+    if (ok) {
+        const int32_t* base = (const int32_t*)ADDR(ints);
+        for (jsize i = 0; i < n; i++)
+            for (int k = 0; k < 3; k++) g[i].lf_quant[k] = base + (intptr_t)g[i].lf_quant[k];
+        d.n_groups = (int32_t)n; d.cells_h = cellsH; d.cells_w = cellsW; d.color_factor = colorFactor;
+        d.groups = g; d.base_corr_x = baseCorrX; d.base_corr_b = baseCorrB;
+        if (to_host) {
+            float* out[3] = {(float*)ADDR(o0), (float*)ADDR(o1), (float*)ADDR(o2)};
+            st = jxl_stage_lf_image(c, &d, out);
+        } else {
+            st = jxl_planes_from_lf(c, &d);
+        }
+    }
+    free(g);
+    free(sd);
+    free(hd);
+    if (ok) CHECK(st);
+}
+
 JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageXyb(JNIEnv* e, jobject self, jobject p0, jobject p1, jobject p2, jlong n,
         jfloatArray matrix, jfloatArray bias, jfloatArray cbrtBias, jfloat intensityTarget) {
     jxl_ctx* c = ctx_of(e, self);

@@ -67,6 +67,10 @@ def parser():
                          "plan whatever it holds (JXLDecoder device_chains; jxl_modular_begin_chain) -- nested Palettes run as one "
                          "launch on the uploaded channels -- and with --device-frames a frame with patches stays a plane set "
                          "through the patch stage. The same bytes")
+    ap.add_argument("--downsample", type=int, choices=[1, 8], default=1,
+                    help="8: the image at 1:8 from the LF image of its VarDCT frame (JXLDecoder downsample; jxl_planes_from_lf / "
+                         "jxl_stage_lf_image): no HF section is read, one launch makes the planes. A faithful thumbnail, not the "
+                         "reference's pixels. An image whose frame does not qualify (JXLDecoder.preview_rule) stops with the reason")
     return ap
 
 
@@ -87,15 +91,31 @@ def main(argv=None):
         print("Image: %s\n    Size: %dx%d\n    Bit Depth: %d\n    Extra Channels: %d\n    XYB Encoded: %s\n    Orientation: %d" % (
             a.input, im.width, im.height, im.bits_per_sample, im.num_extra, bool(im.xyb_encoded), im.orientation))
         return 0
-    from .decoder import PEAK_DETECT_AUTO, PEAK_DETECT_OFF, PEAK_DETECT_ON, DeviceBackend, JXLDecoder, PFMWriter, PNGWriter
+    from .decoder import (PEAK_DETECT_AUTO, PEAK_DETECT_OFF, PEAK_DETECT_ON, DeviceBackend, JXLDecoder, PFMWriter, PNGWriter,
+                          UnsupportedOperationException)
     PEAK_DETECT = {"auto": PEAK_DETECT_AUTO, "on": PEAK_DETECT_ON, "off": PEAK_DETECT_OFF}
     t0 = time.time()
     backend = DeviceBackend(a.device)
-    dec = JXLDecoder(a.input, backend=backend, sparse_coeffs=a.sparse_coeffs, device_splines=a.device_splines,
-                     device_patches=a.device_patches, device_output=a.device_png, device_canvas=a.device_canvas,
-                     draw_varblocks=a.draw_varblocks, device_palette=a.device_palette, device_image=a.device_image,
-                     device_frames=a.device_frames, device_patch_sets=a.device_patch_sets, device_chains=a.device_chains)
-    image = dec.decode()
+    try:
+        dec = JXLDecoder(a.input, backend=backend, sparse_coeffs=a.sparse_coeffs, device_splines=a.device_splines,
+                         device_patches=a.device_patches, device_output=a.device_png, device_canvas=a.device_canvas,
+                         draw_varblocks=a.draw_varblocks, device_palette=a.device_palette, device_image=a.device_image,
+                         device_frames=a.device_frames, device_patch_sets=a.device_patch_sets, device_chains=a.device_chains,
+                         downsample=a.downsample)
+    except ValueError as e:
+        if a.downsample == 1:
+            raise
+        print("jxlatte_amd: %s" % e, file=sys.stderr)
+        backend.close()
+        return 2
+    try:
+        image = dec.decode()
+    except UnsupportedOperationException as e:
+        if a.downsample == 1 or not str(e).startswith("downsample=8: "):
+            raise
+        print("jxlatte_amd: %s" % e, file=sys.stderr)  # the frame does not qualify: decode without --downsample
+        backend.close()
+        return 2
     if image is None:
         print("jxlatte_amd: no frames", file=sys.stderr)
         return 1
@@ -104,7 +124,8 @@ def main(argv=None):
         print("    frame %d: %s %dx%d, %d groups%s" % (i, st["encoding"], st["width"], st["height"], st["groups"],
                                                        (", canvas %s" % st["canvas"] if a.device_canvas else "") +
                                                        (", image %s" % st["image"] if a.device_image else "") +
-                                                       (", frame %s" % st["frame"] if a.device_frames else "")), file=sys.stderr)
+                                                       (", frame %s" % st["frame"] if a.device_frames else "") +
+                                                       (", preview %s" % st["preview"] if a.downsample == 8 else "")), file=sys.stderr)
     print("Decoded %dx%d in %.3f s" % (image.getWidth(), image.getHeight(), t1 - t0), file=sys.stderr)
     if a.output and output_format(a) == "pfm":
         with open(a.output, "wb") as f:

@@ -95,6 +95,8 @@ SIGNATURES = {
     "jxl_planes_noise": (i32, [vp, i32, C.c_uint64, pf, f32, f32]),
     "jxl_planes_xyb": (i32, [vp, pf, pf, pf, f32]),
     "jxl_planes_ycbcr": (i32, [vp]),
+    "jxl_planes_from_lf": (i32, [vp, C.POINTER(abi.LFImageDesc)]),
+    "jxl_stage_lf_image": (i32, [vp, C.POINTER(abi.LFImageDesc), pf3]),
     "jxl_spline_arcs": (i64, [C.POINTER(abi.SplineDesc), i32, i32, C.POINTER(abi.SplineArc), i64]),
     "jxl_stage_splines": (i32, [vp, pf3, i32, i32, C.POINTER(abi.SplineDesc)]),
     "jxl_planes_splines": (i32, [vp, C.POINTER(abi.SplineDesc)]),

@@ -128,6 +128,43 @@ def make_lfquant_desc(lf_quant, scaled_dequant, extra_precision=0, x_factor_lf=1
     return d
 
 
+class LFImageDesc(C.Structure):
+    """struct jxl_lf_image_desc (the LF image of a whole frame as the picture at 1:8)"""
+    _fields_ = [
+        ("n_groups", C.c_int32), ("cells_h", C.c_int32), ("cells_w", C.c_int32), ("color_factor", C.c_int32),
+        ("groups", C.POINTER(LFQuantDesc)), ("base_corr_x", C.c_float), ("base_corr_b", C.c_float), ("xyb", C.c_int32),
+        ("opsin_matrix", f9), ("opsin_bias", f3), ("cbrt_opsin_bias", f3), ("intensity_target", C.c_float),
+    ]
+
+
+def make_lf_image_desc(groups, cells, base_corr_x=0.0, base_corr_b=1.0, color_factor=84, xyb=None):
+    """groups: the frame's LF groups, dicts of lfg_y, lfg_x, lf_quant (three C-contiguous int32 planes of the group's size, X, Y, B
+    order), scaled_dequant, extra_precision, x_factor_lf, b_factor_lf, adaptive_smoothing. cells: (cells_h, cells_w) of the output.
+    xyb: None, or (matrix[9], opsin_bias[3], cbrt_opsin_bias[3], intensity_target). Returns (desc, keepalive)."""
+    keep = []
+    arr = (LFQuantDesc * max(1, len(groups)))()
+    for i, g in enumerate(groups):
+        planes = [np.ascontiguousarray(g["lf_quant"][c], np.int32) for c in range(3)]
+        keep.append(planes)
+        if len({a.shape for a in planes}) != 1:
+            raise ValueError("the three LF planes of an LF group must have one size")
+        arr[i] = make_lfquant_desc(planes, g["scaled_dequant"], g.get("extra_precision", 0), g.get("x_factor_lf", 128), g.get("b_factor_lf", 128),
+                                   g.get("adaptive_smoothing", True), g["lfg_y"], g["lfg_x"])
+    d = LFImageDesc()
+    d.n_groups = len(groups)
+    d.cells_h, d.cells_w = cells
+    d.color_factor = color_factor
+    d.groups = C.cast(arr, C.POINTER(LFQuantDesc))
+    d.base_corr_x, d.base_corr_b = base_corr_x, base_corr_b
+    if xyb is not None:
+        matrix, bias, cbrt, intensity_target = xyb
+        d.xyb = 1
+        d.opsin_matrix, d.opsin_bias, d.cbrt_opsin_bias = f9(*[float(v) for v in matrix]), f3(*[float(v) for v in bias]), f3(*[float(v) for v in cbrt])
+        d.intensity_target = intensity_target
+    keep.append(arr)
+    return d, keep
+
+
 SPARSE_WIDE = 1
 
 

@@ -3204,6 +3204,9 @@ jxl_status ctx_planes_set(jxl_ctx* c, int h, int w, float* p[3]) {
     c->rp_w = w;
     return JXL_OK;
 }
+XybParams ctx_make_xyb(const float matrix[9], const float opsin_bias[3], const float cbrt_opsin_bias[3], float intensity_target) {
+    return make_xyb(matrix, opsin_bias, cbrt_opsin_bias, intensity_target);
+}
 }  // namespace jxl
 }  // extern "C++"
 

@@ -622,6 +622,8 @@ jxl_status ctx_link(jxl_ctx* c, CtxLink* out);                      // hipSetDev
 jxl_status ctx_fail(jxl_ctx* c, jxl_status st, const char* msg);    // records the message (c may be null) and returns st
 jxl_status ctx_planes_get(jxl_ctx* c, int* h, int* w, float* p[3]);  // the resident planes, or JXL_ERR_STATE
 jxl_status ctx_planes_set(jxl_ctx* c, int h, int w, float* p[3]);    // resident planes of h x w to fill (contents undefined)
+// the XYB stage's parameters as jxl_planes_xyb / jxl_stage_xyb make them from the header's values
+XybParams ctx_make_xyb(const float matrix[9], const float opsin_bias[3], const float cbrt_opsin_bias[3], float intensity_target);
 // the page-locked staging buffer of the spline and patch tables: room for `total` bytes at *host once the transfer before has read
 // it, then its first `total` bytes queued to the context's table buffer (*dev) by ONE transfer on the stream
 jxl_status ctx_tables_reserve(jxl_ctx* c, size_t total, char** host);

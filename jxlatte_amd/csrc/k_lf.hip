@@ -4,9 +4,10 @@
 // Replaces J/frame/vardct/LFCoefficients.java:65-75 (dequant), :78-95 (chroma from luma), :113-180 (adaptiveSmooth).
 // lfIndex (:105-111,182-…) feeds the entropy decoder's context model and stays on the host.
 //
-// One lane per 8x8 cell. The 3x3 neighbourhood is re-dequantised from the integer LF image (9 x 3 int loads, L1/L2
-// hits) instead of staging a float image: 1/64 of the frame's pixels, the kernel is a few microseconds.
+// One lane per 8x8 cell; the cell's arithmetic is lf_cell.h's (shared with k_lf_image.hip). 1/64 of the frame's pixels, the
+// kernel is a few microseconds.
 #include "jxl_internal.h"
+#include "lf_cell.h"
 
 namespace jxl {
 
@@ -22,44 +23,12 @@ struct LfArgs {
     int smooth;
 };
 
-// dequantised + CfL'd LF sample of channel i at (y, x) (LFCoefficients.java:66-95)
-__device__ __forceinline__ void lf_sample(const LfArgs& a, int y, int x, float v[3]) {
-    const int k = y * a.W + x;
-    const float yv = (float)a.q[1][k] * a.sd[1];
-    v[1] = yv;
-    v[0] = (float)a.q[0][k] * a.sd[0] + a.kX * yv;
-    v[2] = (float)a.q[2][k] * a.sd[2] + a.kB * yv;
-}
-
 __global__ __launch_bounds__(256) void k_lf_dequant(const LfArgs a) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= a.W || y >= a.H) return;
-    float c[3];
-    lf_sample(a, y, x, c);
-    float o[3] = {c[0], c[1], c[2]};
-    if (a.smooth && y > 0 && y + 1 < a.H && x > 0 && x + 1 < a.W) {  // adaptiveSmooth (:113-180); border cells are copied
-        float nb[3][3][3];  // [dy][dx][channel]
-#pragma unroll
-        for (int dy = 0; dy < 3; dy++)
-#pragma unroll
-            for (int dx = 0; dx < 3; dx++) lf_sample(a, y + dy - 1, x + dx - 1, nb[dy][dx]);
-        float gap = 0.5f;
-        float w[3];
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const float sample = nb[1][1][i];
-            const float adjacent = nb[1][0][i] + nb[1][2][i] + nb[0][1][i] + nb[2][1][i];
-            const float diag = nb[0][0][i] + nb[0][2][i] + nb[2][0][i] + nb[2][2][i];
-            w[i] = 0.05226273532324128f * sample + 0.20345139757231578f * adjacent + 0.0334829185968739f * diag;
-            const float g = fabsf(sample - w[i]) * a.sd_gap[i];
-            if (g > gap) gap = g;
-        }
-        const float t = 3.0f - 4.0f * gap;
-        gap = t > 0.0f ? t : 0.0f;  // Math.max(0f, 3f - 4f * g)
-#pragma unroll
-        for (int i = 0; i < 3; i++) o[i] = (c[i] - w[i]) * gap + w[i];
-    }
+    float o[3];
+    lf_cell(a, y, x, o);  // lf_cell.h: dequant, chroma from luma, adaptiveSmooth (border cells are copied)
     const int64_t d = a.out_off + (int64_t)y * a.out_stride + x;
 #pragma unroll
     for (int i = 0; i < 3; i++) a.out[i][d] = o[i];

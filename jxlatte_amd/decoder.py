@@ -679,6 +679,11 @@ class DeviceBackend:
             return fr.keepPlanes(*keep)
         return fr.decodeFrame()
 
+    def lf_image(self, groups, cells, bcx, bcb, color_factor, xyb, keep=False):
+        """a frame's LF image as the picture at 1:8 in one launch (host.lfImage): jxl_planes_from_lf where the planes stay (keep:
+        host.ResidentPlanes come back), jxl_stage_lf_image otherwise"""
+        return self.host.lfImage(self.ctx, groups, cells, bcx, bcb, color_factor, xyb, keep=keep)
+
     def gab(self, planes, w1, w2):
         return self.host.performGabConvolution(self.ctx, planes, w1, w2)
 
@@ -1523,12 +1528,13 @@ class JXLDecoder:
     # the switches' defaults (a decoder made with JXLDecoder.__new__ -- tests, tools, load_vardct_frame -- has them too)
     sparse_coeffs = device_splines = device_patches = device_output = device_canvas = False
     draw_varblocks = device_palette = device_image = device_frames = device_patch_sets = device_chains = False
+    downsample = 1
     trace = None  # test hook: see _trace
     _patch_sets = False  # device_patch_sets acts on the frame in hand (_canvas_route)
 
     def __init__(self, source, backend=None, sparse_coeffs=False, device_splines=False, device_patches=False, device_output=False,
                  device_canvas=False, draw_varblocks=False, device_palette=False, device_image=False, device_frames=False,
-                 device_patch_sets=False, device_chains=False):
+                 device_patch_sets=False, device_chains=False, downsample=1):
         """sparse_coeffs: hand the HF coefficients to the backend as lists of non-zero entries (jxf_get_coeffs_sparse ->
         jxl_vardct_put_group_sparse), not as dense planes; same pixels.
         device_splines: Frame.renderSplines runs in the backend (jxl_planes_splines on the resident planes, jxl_stage_splines
@@ -1607,7 +1613,25 @@ class JXLDecoder:
         goes up again) and the blend reads it; what _patches_sets refuses lands the canvas with its reason, as without the
         switch. The same bits. stats[k]["chain"], only with the switch: dict(kinds, runs) for a frame whose chain ran as a
         plan -- runs: dict(fused, steps, redone), the launches of its Palette runs as one launch each, as single steps, and
-        the runs that ran again because a pixel needed its neighbours."""
+        the runs that ran again because a pixel needed its neighbours.
+        downsample: 1 (the image) or 8: the image at 1:8 from the LF image of its VarDCT frame, without reading one HF section. The
+        front-end stops after the LF coefficients (jxf_set_lf_only), and ONE backend.lf_image call turns every LF group's integers
+        into three planes of ceil(h / 8) x ceil(w / 8) samples: the LF stage per LF group (dequantisation, LF chroma-from-luma,
+        adaptive smoothing) and the inverse XYB. YCbCr, the orientation and everything a JXLImage offers follow on an image of that
+        size; with device_output the planes are the image's resident planes and nothing comes down. This is a faithful thumbnail
+        -- the full decode box-averaged 8 x 8, up to what Gaborish, the EPF and the low frequencies of large varblocks add -- not the
+        reference's pixels. preview_rule lists what a frame needs; one that does not qualify raises
+        UnsupportedOperationException("downsample=8: <reason>") before any HF section is read, and the caller decodes in full.
+        Noise is left out (zero-mean grain). stats[k]["preview"] is "lf image (1:8)", with ", noise left out" where there was
+        some. Refused together with draw_varblocks, device_canvas, device_frames or a `trace` listener. A backend without
+        `lf_image` is an error."""
+        if downsample not in (1, 8):
+            raise ValueError("downsample must be 1 or 8, not %r" % (downsample,))
+        self.downsample = int(downsample)
+        if self.downsample == 8:
+            for name, on in (("draw_varblocks", draw_varblocks), ("device_canvas", device_canvas), ("device_frames", device_frames)):
+                if on:
+                    raise ValueError("downsample=8 cannot be combined with " + name)
         self.device_chains = bool(device_chains)
         self.device_patch_sets = bool(device_patch_sets)
         self.device_frames = bool(device_frames)
@@ -2585,6 +2609,11 @@ class JXLDecoder:
             raise RuntimeError("device_image needs a backend with a device context")
         if self.device_canvas and not hasattr(be, "ctx"):
             raise RuntimeError("device_canvas needs a backend with a device context")
+        if self.downsample == 8:
+            if self.trace is not None:
+                raise ValueError("downsample=8 cannot be combined with a trace listener")
+            if not hasattr(be, "lf_image"):
+                raise RuntimeError("downsample=8 needs a backend with `lf_image`")
 
     def _hooks(self):
         be = self.backend
@@ -2746,10 +2775,84 @@ class JXLDecoder:
         planes = [cv.download(c) for c in range(len(cv))]
         return JXLImage([be.orient(b, o) if o != 1 else b for b in planes], info, be)
 
+    @staticmethod
+    def preview_rule(info, fr):
+        """downsample=8: None when the headers say that the frame's LF image is the image at 1:8, else the first condition that
+        fails. info: the image header; fr: the frame header, or None to ask only what the image header settles, which decode()
+        does before it lets the front-end read the frame -- so that condition comes first here too. A frame qualifies when the
+        image has no extra channels and the frame is VarDCT; regular, of LF level 0, with LF coefficients of its own; the image's
+        only frame (last, at the origin, of the image's size); not upsampled; not chroma-subsampled; without patches and splines.
+        Noise and YCbCr without subsampling are accepted."""
+        if info.num_extra:
+            return "the image has extra channels"
+        if fr is None:
+            return None
+        if fr.encoding != VARDCT:
+            return "not a VarDCT frame"
+        if fr.type != REGULAR_FRAME or fr.lf_level != 0 or fr.flags & FLAG_USE_LF_FRAME:
+            return "not a regular frame of LF level 0 with LF coefficients of its own"
+        if not fr.is_last or fr.x0 != 0 or fr.y0 != 0 or fr.width * fr.upsampling != info.width or fr.height * fr.upsampling != info.height:
+            return "not the image's only frame"
+        if fr.upsampling != 1:
+            return "the frame is upsampled"
+        if any(fr.jpeg_up_y[c] or fr.jpeg_up_x[c] for c in range(3)):
+            return "chroma subsampling"
+        if fr.num_patches or fr.flags & FLAG_PATCHES:
+            return "patches"
+        if fr.has_splines or fr.flags & FLAG_SPLINES:
+            return "splines"
+        return None
+
+    def _preview_image(self):
+        """downsample=8: the image's one VarDCT frame as its LF image (preview_rule), one backend.lf_image call"""
+        info, be = self.info, self.backend
+        why = self.preview_rule(info, None)
+        if why is not None:
+            raise UnsupportedOperationException("downsample=8: " + why)
+        try:
+            self.fe.set_lf_only(True)
+        except frontend.FrontendError as e:
+            raise self._map(e)
+        fr = self._next_frame()
+        if fr is None:
+            return None
+        why = self.preview_rule(info, fr)
+        if why is not None:
+            raise UnsupportedOperationException("downsample=8: " + why)
+        self._count_frame(fr)
+        adaptive = (fr.flags & (FLAG_SKIP_ADAPTIVE_LF | FLAG_USE_LF_FRAME)) == 0
+        groups = []
+        for i in range(fr.num_lf_groups):
+            g = self.fe.lfgroup(i)
+            groups.append(dict(lfg_y=i // fr.lf_group_cols, lfg_x=i % fr.lf_group_cols, lf_quant=g["lf_quant"],
+                               extra_precision=g["extra_precision"], scaled_dequant=list(fr.scaled_dequant),
+                               x_factor_lf=fr.x_factor_lf, b_factor_lf=fr.b_factor_lf, adaptive_smoothing=adaptive))
+        cells = ((fr.height + 7) >> 3, (fr.width + 7) >> 3)
+        xyb = (*self._opsin(), info.intensity_target) if info.xyb_encoded else None
+        grey = info.colour_space == CE_GRAY  # (the canvas of a grey image takes the frame's plane 1: _blend_buffers)
+        keep = self.device_output and getattr(be, "resident", False) and not grey
+        planes = be.lf_image(groups, cells, fr.base_corr_x, fr.base_corr_b, fr.colour_factor, xyb, keep=keep)
+        o = info.orientation
+        st = self.stats[-1]
+        st["preview"] = "lf image (1:8)" + (", noise left out" if fr.has_noise else "")
+        st["output"] = "device" if keep else "host"
+        if keep:
+            if fr.do_ycbcr:
+                planes.ycbcr()
+            if o != 1:
+                planes.orient(o)
+            return JXLImage([None] * 3, info, be, resident=planes)
+        if fr.do_ycbcr:
+            planes = be.ycbcr(planes)
+        planes = [np.ascontiguousarray(planes[c]) for c in ((1,) if grey else range(3))]
+        return JXLImage([be.orient(b, o) if o != 1 else b for b in planes], info, be)
+
     def decode(self):
         """JXLCodestreamDecoder.decode (:546-677): frames until one completes an image; None at the end of the stream"""
         colors_img = 1 if self.info.colour_space == CE_GRAY else 3
         self._check_switches()
+        if self.downsample == 8:
+            return self._preview_image()
         if self.canvas is None:
             self.canvas = [None] * (colors_img + self.info.num_extra)
         last = planes = None

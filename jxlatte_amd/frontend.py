@@ -129,6 +129,7 @@ SIGNATURES = {
     "jxf_get_spline": (i32, [C.c_void_p, i32, C.POINTER(SplineView)]),
     "jxf_get_modular_channel": (i32, [C.c_void_p, i32, C.POINTER(Chan)]),
     "jxf_set_defer_transforms": (i32, [C.c_void_p, i32]),
+    "jxf_set_lf_only": (i32, [C.c_void_p, i32]),
     "jxf_get_transform_count": (i32, [C.c_void_p]),
     "jxf_get_transform": (i32, [C.c_void_p, i32, C.POINTER(TransformView)]),
     "jxf_transforms_pending": (i32, [C.c_void_p]),
@@ -274,6 +275,11 @@ class Frontend:
     def set_defer_transforms(self, on):
         """frames decoded from now on leave the frame-level stream's inverse transforms undone (jxf_set_defer_transforms)"""
         self._check(self.lib.jxf_set_defer_transforms(self.h, int(bool(on))))
+
+    def set_lf_only(self, on):
+        """VarDCT frames decoded from now on stop after the LF coefficients (jxf_set_lf_only): lfgroup() then has n_blocks 0 and
+        empty block maps, coeffs() raises, and the file is needed only up to the end of the frame's last LF-group section"""
+        self._check(self.lib.jxf_set_lf_only(self.h, int(bool(on))))
 
     def transforms(self):
         """the current frame's frame-level transform list in bitstream order: dicts of kind (TRANSFORM_*), begin_c, num_c,

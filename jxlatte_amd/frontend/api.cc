@@ -18,6 +18,7 @@ struct jxf_dec {
     std::unique_ptr<Frame> frame;
     bool done = false, skipped_preview = false;
     bool defer = false;  // jxf_set_defer_transforms
+    bool lf_only = false;  // jxf_set_lf_only
     std::string error;
     // scratch for views
     std::vector<float> qv[3];
@@ -241,7 +242,7 @@ int32_t jxf_next_frame(jxf_dec* d, const jxf_hooks* hooks) {
         HookCtx hc{hooks, &d->error};
         TransformHooks th;
         bind_hooks(&th, &hc);
-        f.decode(d->br, &th, d->defer);
+        f.decode(d->br, &th, d->defer, d->lf_only);
         if (f.fh.is_last) d->done = true;
         return JXF_OK;
     });
@@ -296,15 +297,23 @@ int32_t jxf_get_lfgroup(const jxf_dec* d, int32_t idx, jxf_lfgroup_view* o) {
             const Channel& c = g.lf_quant[kCMap[i]];
             o->lf_quant[i] = c.buf.data(); o->lf_h[i] = c.h; o->lf_w[i] = c.w;
         }
+    if (f.lf_only_decoded) return JXF_OK;  // no HF metadata was read: n_blocks 0, null block maps
     o->n_blocks = g.nb_blocks;
     o->dct_select = g.dct_select.data(); o->hf_mul = g.hf_mul.data(); o->sharpness = g.sharpness.buf.data();
     o->x_from_y = g.x_from_y.buf.data(); o->b_from_y = g.b_from_y.buf.data(); o->block_yx = g.block_yx.data();
     return JXF_OK;
 }
 
+// a frame decoded up to its LF coefficients (jxf_set_lf_only) has no HF coefficients to hand out
+static int32_t lf_only_refusal(const jxf_dec* d) {
+    const_cast<jxf_dec*>(d)->error = "the frame was decoded up to its LF coefficients only (jxf_set_lf_only)";
+    return JXF_ERR_STATE;
+}
+
 int32_t jxf_get_coeffs(const jxf_dec* d, int32_t pass, int32_t group, jxf_coeff_view* o) {
     if (!d || !o || !d->frame) return JXF_ERR_STATE;
     const Frame& f = *d->frame;
+    if (f.lf_only_decoded) return lf_only_refusal(d);
     if (pass < 0 || pass >= (int32_t)f.coeffs.size() || group < 0 || group >= (int32_t)f.coeffs[pass].size()) return JXF_ERR_ARGUMENT;
     const GroupCoeffs& g = f.coeffs[pass][group];
     for (int c = 0; c < 3; c++) { o->q[c] = g.q[c].data(); o->h[c] = g.h[c]; o->w[c] = g.w[c]; }
@@ -314,6 +323,7 @@ int32_t jxf_get_coeffs(const jxf_dec* d, int32_t pass, int32_t group, jxf_coeff_
 int32_t jxf_get_coeffs_sparse(const jxf_dec* d, int32_t pass, int32_t group, jxf_sparse_view* o) {
     if (!d || !o || !d->frame) return JXF_ERR_STATE;
     const Frame& f = *d->frame;
+    if (f.lf_only_decoded) return lf_only_refusal(d);
     if (pass < 0 || pass >= (int32_t)f.coeffs.size() || group < 0 || group >= (int32_t)f.coeffs[pass].size()) return JXF_ERR_ARGUMENT;
     const GroupCoeffs& g = f.coeffs[pass][group];
     for (int c = 0; c < 3; c++) {
@@ -371,6 +381,12 @@ int32_t jxf_get_spline(const jxf_dec* d, int32_t index, jxf_spline_view* o) {
 int32_t jxf_set_defer_transforms(jxf_dec* d, int32_t on) {
     if (!d) return JXF_ERR_ARGUMENT;
     d->defer = on != 0;
+    return JXF_OK;
+}
+
+int32_t jxf_set_lf_only(jxf_dec* d, int32_t on) {
+    if (!d) return JXF_ERR_ARGUMENT;
+    d->lf_only = on != 0;
     return JXF_OK;
 }
 

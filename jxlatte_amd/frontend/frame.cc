@@ -316,6 +316,7 @@ void Frame::read_lf_group(BitReader& br, int idx, std::vector<int>& replaced_idx
             }
         }
     }
+    if (lf_only_decoded) return;  // jxf_set_lf_only: nothing behind the LF coefficients is read (decode() has seen that no channel waits here)
     // modular channels of the frame-level stream carried by this LF group (Frame.decodeLFGroups :262-300)
     {
         std::vector<Channel> sub;
@@ -664,7 +665,8 @@ void Frame::read_pass_group(BitReader& br, int pass, int group, const std::vecto
         copy_back(global_modular.channels[replaced_idx[j]], ms.channels[j], want[j]);
 }
 
-void Frame::decode(BitReader& br, const TransformHooks* hooks, bool defer) {  // Frame.decodeFrame (:376-461), front part
+void Frame::decode(BitReader& br, const TransformHooks* hooks, bool defer, bool lf_only) {  // Frame.decodeFrame (:376-461), front part
+    lf_only_decoded = lf_only && fh.encoding == kVarDCT;
     const bool single = toc.lengths.size() == 1;
     const size_t base = br.byte_pos();
     const bool timing = getenv("JXF_TIMING") != nullptr;
@@ -693,6 +695,9 @@ void Frame::decode(BitReader& br, const TransformHooks* hooks, bool defer) {  //
         if (!c.decoded && c.vshift >= 3 && c.hshift >= 3) lf_replaced.push_back((int)i);
     }
     lf_groups.assign(num_lf_groups, LFGroupData());
+    // the LF-only read stops inside each LF-group section, before its modular sub-stream: a frame that carries channels there
+    // (extra channels at 1:8) cannot be cut short
+    if (lf_only_decoded && !lf_replaced.empty()) throw UnsupportedError("LF-only decoding of a frame with modular LF-group channels");
     if (single) {
         for (int g = 0; g < num_lf_groups; g++) read_lf_group(shared, g, lf_replaced);
     } else {
@@ -712,6 +717,18 @@ void Frame::decode(BitReader& br, const TransformHooks* hooks, bool defer) {  //
     }
     for (int ci : lf_replaced) global_modular.channels[ci].decoded = true;
     lap("LF groups");
+    if (lf_only_decoded) {
+        // nothing after the last LF-group section is read or required: the bytes behind it may be missing, which the next
+        // frame's header then reports
+        coeffs.clear();
+        if (single) {
+            br = shared;
+        } else {
+            const size_t end = std::min(base + data_bytes(), br.size_bytes());
+            br = BitReader(br.data() + end, br.size_bytes() - end);
+        }
+        return;
+    }
     // HfGlobal + pass headers
     BitReader hfg = single ? shared : sec(1 + num_lf_groups);
     read_hf_global(single ? shared : hfg);

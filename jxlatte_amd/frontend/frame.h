@@ -108,7 +108,9 @@ struct Frame {
     void read_header(BitReader& br, const ImageHeader& image);
     // decode every section (br positioned right after the TOC); leaves br at the end of the frame data
     // defer: the frame-level stream's inverse transforms are left undone (only checked: ModularStream::check_transforms)
-    void decode(BitReader& br, const TransformHooks* hooks, bool defer = false);
+    // lf_only: a VarDCT frame stops after the LF coefficients of its LF-group sections (jxf_set_lf_only); Modular frames ignore it
+    void decode(BitReader& br, const TransformHooks* hooks, bool defer = false, bool lf_only = false);
+    bool lf_only_decoded = false;  // this frame was decoded that way: no HF metadata, no HfGlobal, no coefficients
     size_t data_bytes() const;
 
     int colour_channels() const { return (ih->xyb_encoded || fh.encoding == kVarDCT) ? 3 : ih->colour_channels(); }

@@ -82,6 +82,20 @@ class LFCoefficients:
         return out
 
 
+def lfImage(ctx, groups, cells, baseCorrelationX=0.0, baseCorrelationB=1.0, colorFactor=84, xyb=None, keep=False):
+    """The LF image of a VarDCT frame as the picture at 1:8, one launch (jxl_stage_lf_image; keep: jxl_planes_from_lf). groups: the
+    frame's LF groups as abi.make_lf_image_desc takes them; cells: (ceil(h / 8), ceil(w / 8)); xyb: None or (matrix, opsinBias,
+    cbrtOpsinBias, intensityTarget) for the inverse XYB behind the LF stage. Returns float32 [3][cells_h][cells_w], or with keep the
+    context's ResidentPlanes holding them (nothing comes down)."""
+    d, alive = abi.make_lf_image_desc(groups, cells, baseCorrelationX, baseCorrelationB, colorFactor, xyb)
+    if keep:
+        ctx.call("jxl_planes_from_lf", C.byref(d))
+        return ResidentPlanes(ctx)
+    out = np.empty((3, int(cells[0]), int(cells[1])), np.float32)
+    ctx.call("jxl_stage_lf_image", C.byref(d), _p3(out, C.c_float))
+    return out
+
+
 def performColorTransformsYCbCr(ctx, buffer):
     """YCbCr branch of JXLCodestreamDecoder.performColorTransforms (:270-281)"""
     out = np.array(buffer, np.float32, order="C", copy=True)
