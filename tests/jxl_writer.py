@@ -15,6 +15,8 @@ arrays that went in. Size does not matter; every choice is the simplest legal on
 
 encode(image) takes one dict:
   width, height, bits, grey=False, exp_bits=0, orientation=1, animation=False,
+  intensity_target=None | an exact half, opsin=None | dict(matrix[9], opsin_bias[3], quant_bias[3], quant_bias_numerator) of exact
+  halves (XYB images), up_weights=None | {2: [15], 4: [55], 8: [210]} (any subset) -- used by jxl_writer_vardct.py,
   extra=[dict(type="alpha" | "other", bits=8, exp_bits=0, alpha_associated=False)],
   frames=[dict(planes=[2-D integer arrays, colours then extra channels, each of the frame's coded size],
                type=0 (regular) | 2 (reference only) | 3 (skip progressive), crop=None | (x0, y0), upsampling=1, ec_upsampling=[..],
@@ -221,7 +223,8 @@ def write_image_header(w, im):
     w.bits(0x0AFF, 16)  # :208
     _size(w, im["height"], im["width"])
     w.bool(False)  # :213 all_default
-    extra_fields = orientation != 1 or animation
+    target = im.get("intensity_target")
+    extra_fields = orientation != 1 or animation or target is not None
     w.bool(extra_fields)  # :214
     if extra_fields:
         w.bits(orientation - 1, 3)  # :217
@@ -257,9 +260,30 @@ def write_image_header(w, im):
     else:
         w.bool(True)
     if extra_fields:
-        w.bool(True)  # ToneMapping.java:22 default
+        w.bool(target is None)  # ToneMapping.java:22 default
+        if target is not None:
+            w.f16(target)  # :28 intensity_target
+            w.f16(0.0)  # :31 min_nits
+            w.bool(False)  # :36 relative_to_max_display
+            w.f16(0.0)  # :37 linear_below
     w.u64(0)  # :259 extensions
-    w.bool(True)  # :261 default matrix, default upsampling weights
+    opsin, up = im.get("opsin"), im.get("up_weights") or {}
+    assert opsin is None or im.get("xyb", False)  # :263: the matrix is in the stream of an XYB image only
+    w.bool(opsin is None and not up)  # :261 default matrix, default upsampling weights
+    if opsin is not None or up:
+        if im.get("xyb", False):
+            w.bool(opsin is None)  # OpsinInverseMatrix.java:55
+            if opsin is not None:
+                assert len(opsin["matrix"]) == 9
+                for v in list(opsin["matrix"]) + list(opsin["opsin_bias"]) + list(opsin["quant_bias"]):
+                    w.f16(v)  # :62-72 the matrix by rows, opsin_bias, quant_bias
+                w.f16(opsin["quant_bias_numerator"])  # :73
+        w.bits(sum(1 << i for i, k in enumerate((2, 4, 8)) if k in up), 3)  # :266 cw_mask
+        for k, n in ((2, 15), (4, 55), (8, 210)):  # :268-293
+            if k in up:
+                assert len(up[k]) == n
+                for v in up[k]:
+                    w.f16(v)
     w.pad()  # :309
 
 

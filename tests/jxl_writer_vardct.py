@@ -25,7 +25,13 @@ encode(src, variant=None) takes the SOURCE dict:
         reader leaves them: already times 64);
   num_presets, presets=[pass][group]; orders=[pass]{order id: [3 permutations]}, order_clusters=(map of 8, configs);
   hf_clusters=[pass](cluster map of 495 * presets * block clusters, configs);
-  coeff_passes=[pass][3 int arrays of the channel's padded size]: the SOURCE coefficient is sum_p coeff_passes[p] << shift_p.
+  coeff_passes=[pass][3 int arrays of the channel's padded size]: the SOURCE coefficient is sum_p coeff_passes[p] << shift_p;
+  what the frame's tail depends on (every default writes the bytes the writer wrote without these keys):
+  upsampling=1 | 2 | 4 | 8 with image_height, image_width (width and height stay the frame's coded size: the image header carries
+        the image's, the frame header no crop, and ceil(image / upsampling) is the frame);
+  extra=[dict(bits=8, alpha_associated=False, plane=2-D ints of the frame's size, upsampling=k)]: alpha channels, in the global
+        Modular stream at the end of LfGlobal, or -- larger than a group -- as group crops in the pass groups' Modular streams;
+  noise=None | [8 ints of 10 bits]; opsin, up_weights, intensity_target as jxl_writer.write_image_header takes them.
 VARIANTS names writers that are wrong on purpose; the tests show that the front-end tells each from the true one."""
 import numpy as np
 
@@ -34,11 +40,13 @@ from jxl_writer import BitWriter, EntropyCoder, pack_signed
 
 I64 = np.int64
 GROUP_DIM = 256  # FrameHeader.java:121-122
+FLAG_NOISE = 1 << 0  # FrameFlags.java:12
 FLAG_SKIP_ADAPTIVE_LF_SMOOTHING = 1 << 7  # FrameFlags.java:16
 C_MAP = (1, 0, 2)  # Frame.java:42 cMap
 
 VARIANTS = ("predicted_rounded_down", "block_ctx_channel_not_exchanged", "prev_inverted", "nonzero_ctx_without_4", "vertical_not_flipped",
-            "shift_on_token", "lf_buffer_order", "block_info_rows_exchanged", "raw_stream_index_off_by_one")
+            "shift_on_token", "lf_buffer_order", "block_info_rows_exchanged", "raw_stream_index_off_by_one", "noise_lut_after_lf_dequant",
+            "extra_group_stream_index_off_by_one")
 
 # (parameterIndex, orderID, transformMethod, pixelHeight, pixelWidth) by type: TransformType.java:10-36
 TYPES = ((0, 0, 0, 8, 8), (1, 1, 3, 8, 8), (2, 1, 1, 8, 8), (3, 1, 2, 8, 8), (4, 2, 0, 16, 16), (5, 3, 0, 32, 32), (6, 4, 0, 16, 8),
@@ -116,14 +124,29 @@ def num_passes(src):
     return len(src.get("pass_shifts", [])) + 1
 
 
+def image_size(src):
+    """(height, width) of the image header: the frame's own size unless the frame is upsampled"""
+    k = src.get("upsampling", 1)
+    ih, iw = src.get("image_height", src["height"] * k), src.get("image_width", src["width"] * k)
+    assert -(-ih // k) == src["height"] and -(-iw // k) == src["width"]  # FrameHeader.java:161-162 on the image's size (:153)
+    return ih, iw
+
+
+def extras_in_groups(src):
+    """whether the extra channels are left to the pass groups: decodeChannels(reader, true) stops at the first channel larger than
+    a group (ModularStream.java:196-197), and every channel here has the frame's size (:86-90)"""
+    return bool(src.get("extra")) and max(src["height"], src["width"]) > GROUP_DIM
+
+
 # ---- headers ---------------------------------------------------------------------------------------------------------------
 def write_frame_header(w, src):
-    """FrameHeader.java:83-204 for one regular VarDCT frame that is the whole image"""
+    """FrameHeader.java:83-204 for one regular VarDCT frame without a crop: the whole image, or 1 / upsampling of it"""
     xyb = src.get("xyb", True)
     w.bool(False)  # :84 all_default
     w.bits(0, 2)  # :85 REGULAR_FRAME
     w.bits(0, 1)  # :86 VARDCT
-    w.u64(FLAG_SKIP_ADAPTIVE_LF_SMOOTHING if src.get("skip_smoothing", False) else 0)  # :87
+    w.u64((FLAG_SKIP_ADAPTIVE_LF_SMOOTHING if src.get("skip_smoothing", False) else 0) |
+          (FLAG_NOISE if src.get("noise") is not None else 0))  # :87
     sy, sx = src.get("shift_y", [0] * 3), src.get("shift_x", [0] * 3)
     if not xyb:
         w.bool(src.get("do_ycbcr", False))  # :88
@@ -134,7 +157,11 @@ def write_frame_header(w, src):
             w.bits({(0, 0): 0, (1, 1): 1, (0, 1): 2, (1, 0): 3}[(my - sy[c], mx - sx[c])], 2)
     else:
         assert not any(sy) and not any(sx)
-    w.bits(0, 2)  # :114 upsampling 1 (no extra channels: :116 reads nothing)
+    code = {1: 0, 2: 1, 4: 2, 8: 3}
+    w.bits(code[src.get("upsampling", 1)], 2)  # :114
+    extra = src.get("extra", [])
+    for e in extra:
+        w.bits(code[e.get("upsampling", 1)], 2)  # :116
     # :121 no group_size_shift for a VarDCT frame
     if xyb:
         w.bits(src.get("xqm", 3), 3)  # :128-129
@@ -153,6 +180,8 @@ def write_frame_header(w, src):
             w.u32(p, (0, 0), (1, 0), (2, 0), (0, 3))  # :38
     w.bool(False)  # FrameHeader.java:140 no crop
     w.u32(0, (0, 0), (1, 0), (2, 0), (3, 2))  # BlendingInfo.java:27 REPLACE on the full frame: nothing else
+    for _ in extra:
+        W._blend_info(w, {}, True, True)  # :169 one per extra channel: REPLACE on the full frame
     w.bool(True)  # :178 is_last
     w.u32(0, (0, 0), (0, 4), (16, 5), (48, 10))  # :188 no name
     # RestorationFilter.java:46-79
@@ -210,13 +239,16 @@ class Modular:
         left = (channel_index if self.prop == 0 else stream_index) > self.value  # :126
         return (0, self.pred[0]) if left else (1, self.pred[1])
 
-    def write_stream(self, w, channels, stream_index):
-        """ModularStream.java:66-83 and decodeChannels (:191-204): nothing at all for a stream without channels"""
+    def write_stream(self, w, channels, stream_index, header_only=False):
+        """ModularStream.java:66-83 and decodeChannels (:191-204): nothing at all for a stream without channels. header_only: the
+        global stream whose channels are larger than a group, which decodeChannels(reader, true) leaves to the pass groups (:196-197)"""
         if not channels:
             return
         w.bool(True)  # :78 the global tree
         w.bool(True)  # WPParams.java:18 default
         w.u32(0, (0, 0), (1, 0), (2, 4), (18, 8))  # :80 no transforms
+        if header_only:
+            return
         ci = 0
         for a in channels:
             a = np.asarray(a, I64)
@@ -241,13 +273,20 @@ def block_ctx_of(src):
     return list(b["cluster_map"]), max(b["cluster_map"]) + 1, list(b["qf_thresholds"]), [list(t) for t in b["lf_thresholds"]]
 
 
-def write_lf_global(w, src, mod):
+def write_lf_global(w, src, mod, variant=None):
     """LFGlobal.java:30-98"""
+    def noise():
+        for v in src.get("noise") or []:
+            w.bits(v, 10)  # :53-58 eight values of ten bits, in front of the LF dequant fields
+    if variant != "noise_lut_after_lf_dequant":
+        noise()
     lfd = src.get("lf_dequant")
     w.bool(lfd is None)  # :62
     if lfd is not None:
         for v in lfd:
             w.f16(v)  # :64
+    if variant == "noise_lut_after_lf_dequant":
+        noise()
     w.u32(src["global_scale"], (1, 11), (2049, 11), (4097, 12), (8193, 16))  # :68
     w.u32(src["quant_lf"], (16, 0), (1, 5), (1, 8), (1, 16))  # :69
     b = src.get("block_ctx")
@@ -280,7 +319,9 @@ def write_lf_global(w, src, mod):
         w.bits(c["b_factor_lf"], 8)
     w.bool(True)  # LFGlobal.java:82 a global tree
     mod.write_tree(w)
-    # :96-97 the global Modular stream of a VarDCT frame without extra channels has no channel: ModularStream.java:71-76 reads nothing
+    # :96-97 the global Modular stream of a VarDCT frame holds the extra channels, each of the frame's size (ModularStream.java:86-90);
+    # without them it has no channel and :71-76 reads nothing
+    mod.write_stream(w, [e["plane"] for e in src.get("extra", [])], 0, header_only=extras_in_groups(src))
 
 
 def place_blocks(blocks, ch, cw, taken=None):
@@ -454,8 +495,9 @@ COEFF_NUM_NONZERO_CTX = (-1, 0, 31, 62, 62, 93, 93, 93, 93, 123, 123, 123, 123) 
 assert len(COEFF_FREQ_CTX) == 64 == len(COEFF_NUM_NONZERO_CTX)
 
 
-def write_pass_group(w, src, p, group, geo, variant=None):
-    """HFCoefficients.java:49-138; the group's Modular stream after it (PassGroup.java:77-79) has no channel"""
+def write_pass_group(w, src, mod, p, group, geo, variant=None):
+    """HFCoefficients.java:49-138; then the group's Modular stream (PassGroup.java:77-79): the group's crop of every channel that
+    the global stream left undecoded (Pass.java:33-41, Frame.java:327-338), none otherwise"""
     presets = src.get("num_presets", 1)
     preset = src.get("presets", [[0] * geo["num_groups"]] * num_passes(src))[p][group]
     w.bits(preset, ceil_log1p(presets - 1))  # :50-51
@@ -544,6 +586,18 @@ def write_pass_group(w, src, p, group, geo, variant=None):
                     left -= 1
     cm, cfgs = src["hf_clusters"][p]
     EntropyCoder(cm, cfgs).write(w, ctxs, vals)
+    if extras_in_groups(src):
+        assert num_passes(src) == 1  # Pass.java:22-39: the one pass has minShift 0 <= 0 < maxShift 3 and takes every channel
+        crops = []
+        for e in src["extra"]:
+            a = np.asarray(e["plane"], I64)
+            stride = -(-a.shape[1] // GROUP_DIM)  # Frame.java:330-336
+            oy, ox = (group // stride) * GROUP_DIM, (group % stride) * GROUP_DIM
+            crops.append(a[oy:oy + GROUP_DIM, ox:ox + GROUP_DIM])
+        stream = 18 + 3 * geo["num_lf_groups"] + geo["num_groups"] * p + group  # PassGroup.java:77-78
+        if variant == "extra_group_stream_index_off_by_one":
+            stream += 1
+        mod.write_stream(w, crops, stream)
 
 
 # ---- the frame ---------------------------------------------------------------------------------------------------------------
@@ -553,7 +607,12 @@ def encode(src, variant=None):
     mod = Modular(src)
     n_pass = num_passes(src)
     head = BitWriter()
-    W.write_image_header(head, dict(width=src["width"], height=src["height"], bits=8, xyb=src.get("xyb", True)))
+    ih, iw = image_size(src)
+    extra = [dict(type="alpha", bits=e.get("bits", 8), alpha_associated=e.get("alpha_associated", False)) for e in src.get("extra", [])]
+    for e in src.get("extra", []):
+        assert np.asarray(e["plane"]).shape == (src["height"], src["width"])
+    W.write_image_header(head, dict(width=iw, height=ih, bits=8, xyb=src.get("xyb", True), extra=extra, opsin=src.get("opsin"),
+                                    up_weights=src.get("up_weights"), intensity_target=src.get("intensity_target")))
     write_frame_header(head, src)
     head.bool(False)  # Frame.java:153 no permutation
     head.pad()  # :168
@@ -564,7 +623,7 @@ def encode(src, variant=None):
         if not single or not sections:
             sections.append(BitWriter())
         return sections[-1]
-    write_lf_global(section(), src, mod)
+    write_lf_global(section(), src, mod, variant)
     for i in range(geo["num_lf_groups"]):
         write_lf_group(section(), src, mod, i, geo, variant)
     w = section()  # Frame.java:418-423: HfGlobal and every pass's HFPass come from one reader
@@ -573,7 +632,7 @@ def encode(src, variant=None):
         write_hf_pass(w, src, p, geo)
     for p in range(n_pass):
         for grp in range(geo["num_groups"]):  # :326
-            write_pass_group(section(), src, p, grp, geo, variant)
+            write_pass_group(section(), src, mod, p, grp, geo, variant)
     bodies = [s.tobytes() for s in sections]
     assert len(bodies) == (1 if single else 2 + geo["num_lf_groups"] + geo["num_groups"] * n_pass)
     for b in bodies:

@@ -8,7 +8,14 @@ writer takes, and what a decoder must make of it, computed from the SOURCE alone
 
 Conditions, checked here when a case is built: no cell's inverse sigma is within 1e-5 of the EPF's copy threshold
 (vardct_ref64.epf_undecided_cells is empty), and no entry of a case's quant tables is in the "either neighbour" set of
-quant_weights_ref; a draw that violates one is made again with the next seed.
+quant_weights_ref; a draw that violates one is made again with the next seed. The cases of the frame's tail (TAIL_CASES) have two
+more, checked on the model alone (tail_model): of an upsampled frame's outputs some are clamped to their window and most are not
+(between 0.5 % and 50 %), and the inputs of a noisy frame's noise strength, 3 (Y +- X), lie under 0, at or over 7 and between them in
+at least five of the LUT's seven segments -- the two clamps a strength has: the LUT holds ten-bit values below 1, so clampAsc of the
+interpolated strength itself (Frame.java:825-826) can never act. Observed: clamped outputs
+up2_19x15_of_37x29 3.7 %, up4_ragged 1.2 %, up8_40x40 1.3 %, up2_custom_weights 3.1 %, noise_up2 8.6 %, noise_up2_of_271x39 3.9 %,
+opsin_custom_up2 0.7 %, alpha_up2 1.6 %; noise inputs under 0 / at or over 7 of 2 x the samples: noise_40x40 1988 / 16 of 3200, noise_264x264 68470 / 3 of
+139392, noise_up2 10876 / 1044 and noise_up2_of_271x39 9839 / 2 of 21760, noise_corr 2327 / 9 of 3200, all seven segments in each.
 
 The reference has no group_size_shift for a VarDCT frame (FrameHeader.java:121): groups are 256 x 256 and LF groups 2048 x 2048, so the
 multi-group case is 264 x 264 (2 x 2 groups) and the case of two LF groups 2056 x 16."""
@@ -23,6 +30,7 @@ import jxl_writer_vardct as V
 import pixel_ref64 as P
 import quant_weights_ref as Q
 import vardct_ref64 as M
+from jxlatte_amd import upweights
 
 F = np.float32
 I64 = np.int64
@@ -33,6 +41,10 @@ def _f16(v):
 
 
 # ---- the parameters a decoder derives from the headers ------------------------------------------------------------------------
+DEFAULT_OPSIN = (11.031566901960783, -9.866943921568629, -0.16462299647058826, -3.254147380392157, 4.418770392156863,
+                 -0.16462299647058826, -3.6588512862745097, 2.7129230470588235, 1.9459282392156863)  # OpsinInverseMatrix.java:11-15
+
+
 def params_of(src):
     """jxl_vardct_params as the reference computes them from the fields the case wrote"""
     ph, pw = V.padded_size(src)
@@ -52,18 +64,19 @@ def params_of(src):
     lut = epf and src.get("sharp_lut") or [F(F(i) / F(7)) for i in range(8)]
     lut = [F(F(v) * F(sg[0])) for v in lut]  # :77-78
     cs = epf and src.get("channel_scale") or [40.0, 5.0, 3.5]
-    bias = [F(-0.0037930732552754493)] * 3  # OpsinInverseMatrix.java:17-21
+    o = src.get("opsin") or {}  # OpsinInverseMatrix.java:54-75: the custom fields are halves, taken as they are
+    bias = [F(v) for v in o.get("opsin_bias", [-0.0037930732552754493] * 3)]  # :17-21
     return types.SimpleNamespace(
-        width=pw, height=ph, scale_factor=scale_factor, quant_bias=[F(0.945349926692846), F(0.9299455010825141), F(0.9500648966626564)],  # :23-25
-        quant_bias_numerator=F(0.145), base_corr_x=F(c["base_x"]), base_corr_b=F(c["base_b"]), color_factor=c["colour_factor"],
+        width=pw, height=ph, scale_factor=scale_factor,
+        quant_bias=[F(v) for v in o.get("quant_bias", (0.945349926692846, 0.9299455010825141, 0.9500648966626564))],  # :23-25
+        quant_bias_numerator=F(o.get("quant_bias_numerator", 0.145)), base_corr_x=F(c["base_x"]), base_corr_b=F(c["base_b"]), color_factor=c["colour_factor"],
         gab=int(src.get("gab", True)), gab_w1=[F(v) for v in gw[0]], gab_w2=[F(v) for v in gw[1]], epf_iters=src.get("epf_iters", 0),
         global_scale_f=gs, epf_sharp_lut=lut, epf_channel_scale=[F(v) for v in cs], epf_pass0_sigma_scale=F(sg[1]),
         epf_pass2_sigma_scale=F(sg[2]), epf_border_sad_mul=F(sg[3]), xyb=int(xyb),
         # :11-15; getMatrix (:94-100) multiplies by the identity for sRGB / D65 (ColorManagement.java:139-140)
-        opsin_matrix=[F(v) for v in (11.031566901960783, -9.866943921568629, -0.16462299647058826, -3.254147380392157,
-                                     4.418770392156863, -0.16462299647058826, -3.6588512862745097, 2.7129230470588235,
-                                     1.9459282392156863)],
-        opsin_bias=bias, cbrt_opsin_bias=[F(np.cbrt(np.float64(b))) for b in bias], intensity_target=F(255.0),
+        opsin_matrix=[F(v) for v in o.get("matrix", DEFAULT_OPSIN)],
+        # bakeCbrtBias (:81-84): the float of the double cube root; ToneMapping.java:15, :28
+        opsin_bias=bias, cbrt_opsin_bias=[F(np.cbrt(np.float64(b))) for b in bias], intensity_target=F(src.get("intensity_target", 255.0)),
         jpeg_upsampling_y=list(src.get("shift_y", [0] * 3)), jpeg_upsampling_x=list(src.get("shift_x", [0] * 3)),
         scaled_dequant=scaled_dequant, x_factor_lf=c["x_factor_lf"], b_factor_lf=c["b_factor_lf"])
 
@@ -222,7 +235,110 @@ def conditions(src):
                 return "an inverse sigma at the EPF's copy threshold"
     if src.get("quant") is not None and Q.tables(quant_params(src)).near.any():
         return "a quant weight whose distance sits on a band index"
+    if src.get("upsampling", 1) > 1 or src.get("noise") is not None:
+        t = tail_model(src)
+        if src.get("upsampling", 1) > 1 and not 0.005 <= t["clamped"] <= 0.5:
+            return "%.2f %% of the upsampled outputs clamped" % (100 * t["clamped"])
+        if src.get("noise") is not None and not (t["below"] > 0 and t["above"] > 0 and len(t["segments"]) >= 5):
+            return "the noise strength's inputs miss a clamp or reach %d LUT segments" % len(t["segments"])
     return None
+
+
+# ---- the frame's tail: upsampling, noise, the colour transforms (JXLCodestreamDecoder.java:628-637) ---------------------------
+EPF_STAGES = 7  # vardct_ref64.decode: the inverse transforms, Gaborish and the EPF
+NOISE_SEED0 = 1 << 32  # (visibleFrames << 32) | invisibleFrames at the image's first, visible frame (:622-629)
+
+
+def frame_bounds(src):
+    """(height, width) of the frame's bounds: the coded size rounded up to the subsampling factors (FrameHeader.java:196-199)"""
+    my, mx = max(src.get("shift_y", [0] * 3)), max(src.get("shift_x", [0] * 3))
+    return -(-src["height"] // (1 << my)) << my, -(-src["width"] // (1 << mx)) << mx
+
+
+def packed_up_weights(src, k, default=False):
+    """the 15 / 55 / 210 coefficients of factor k: the case's own where it wrote some (ImageHeader.java:268-293), else the defaults"""
+    up = src.get("up_weights") or {}
+    return np.asarray(upweights.DEFAULT_UP[k] if default or k not in up else up[k], F)
+
+
+def upsample_model(x, a, k, packed):
+    """pixel_ref64.upsample per plane. The companion of the weighted sum is the same sum of the input's companion under the absolute
+    weights; the clamp hands out one of the window's samples instead, so the window's largest companion is held too (the clamp is
+    continuous, not linear: an output moves by no more than the sum or the window's extremes do)"""
+    wt = P.up_weights(k, packed)
+    outs, mags, clamped = [], [], []
+    for c in range(len(x)):
+        o, _, cl = P.upsample(x[c], k, wt)
+        _, lin, _ = P.upsample(a[c], k, wt)
+        top = P._windows(np.asarray(a[c], np.float64)).max(axis=(0, 1))
+        outs.append(o)
+        mags.append(np.maximum(lin, np.repeat(np.repeat(top, k, 0), k, 1)))
+        clamped.append(cl)
+    return np.stack(outs), np.stack(mags), np.stack(clamped)
+
+
+def tail_model(src, seed0=NOISE_SEED0, noise_group_dim=V.GROUP_DIM, exchange_cb_cr=False, default_up_weights=False, params=None,
+               model=None, upsample_padded=False):
+    """what a decoder must make of the SOURCE after performColorTransforms, on the frame's upsampled bounds (the crop to the image
+    is the blend's): the model after the EPF cropped to the frame's bounds, Frame.upsample, initializeNoise at the upsampled size
+    with the frame counters' seed and synthesizeNoise, invertXYB, the YCbCr loop; the magnitude companion through every step. The
+    keyword arguments make the WRONG expectations of test_jxl_writer_vardct_cpu.py. Returns a dict: x, a, and the figures the
+    cases' conditions read (clamped: the share of clamped upsampled outputs; below / above: how many inputs of noise_strength lie
+    under 0 / at or over 7 / 3; segments: the LUT segments the others reach)"""
+    p = params or params_of(src)
+    if model is None:
+        model = M.decode(model_frame(src, params=p), EPF_STAGES)[:2]
+    h, w = frame_bounds(src)
+    x, a = model[0], model[1]
+    if not upsample_padded:  # the window is mirrored at the frame's bounds: the padding of the last blocks is never read
+        x, a = x[:, :h, :w], a[:, :h, :w]
+    out = {}
+    k = src.get("upsampling", 1)
+    if k > 1:
+        x, a, cl = upsample_model(x, a, k, packed_up_weights(src, k, default_up_weights))
+        x, a, cl = x[:, :h * k, :w * k], a[:, :h * k, :w * k], cl[:, :h * k, :w * k]
+        out["clamped"] = float(cl.mean())
+    if src.get("noise") is not None:
+        lut = np.asarray(src["noise"], np.float64) / 1024.0  # LFGlobal.java:58
+        nz, na, _ = P.noise_init(x.shape[1], x.shape[2], seed0, noise_group_dim)
+        y, _, raw = P.noise_add(x, nz, lut, p.base_corr_x, p.base_corr_b)
+        _, mag, _ = P.noise_add(x, na, lut, p.base_corr_x, p.base_corr_b)  # (the high-pass's own companion for |noise|)
+        v = 3.0 * np.stack([x[1] + x[0], x[1] - x[0]])  # Frame.java:801-804
+        out.update(below=int((v < 0).sum()), above=int((v >= 7.0).sum()),
+                   segments=sorted(set(np.floor(v[(v >= 0) & (v < 7.0)]).astype(int).tolist())))
+        x, a = y, mag + a  # the strength is continuous in the planes, not linear: the input's companion is added, not dropped
+    if p.xyb:
+        x, a = M.xyb(x, a, p.opsin_matrix, p.opsin_bias, p.cbrt_opsin_bias, float(p.intensity_target))
+    if src.get("do_ycbcr", False):
+        if exchange_cb_cr:
+            x, a = x[::-1], a[::-1]
+        x, a = M.ycbcr(x, a)
+    out.update(x=x, a=a)
+    return out
+
+
+def extra_model(src, e):
+    """one extra channel of the frame as the blend puts it on the image's float canvas: castToFloat with the channel's depth
+    (tests/blend_ref.py, the reference's ImageBuffer.castToFloat), upsampled first by the model where ec_upsampling > 1
+    (Frame.java:226-228 casts there). Returns (plane of the image's size, companion | None where the plane is exact)"""
+    import blend_ref as B
+    import jxl_writer_cases as WC
+    ih, iw = V.image_size(src)
+    k, bits = e.get("upsampling", 1), e.get("bits", 8)
+    buf = B.Buf(np.asarray(e["plane"], np.int32))
+    mag = None
+    if k > 1:
+        buf.cast_to_float(bits)
+        x, mag, _ = P.upsample(buf.a, k, P.up_weights(k, packed_up_weights(src, k)))
+        buf, mag = B.Buf(x.astype(F)), mag[:ih, :iw]
+        model = x[:ih, :iw]
+    im = dict(width=iw, height=ih, bits=8, extra=[dict(type="alpha", bits=bits, alpha_associated=e.get("alpha_associated", False))])
+    fh, fw = buf.a.shape
+    info, hdr = WC.header_objects(im, dict(planes=[np.zeros((fh, fw), F)]))
+    hdr.upsampling = 1  # (the planes are past Frame.upsample: the blend reads them at their own size)
+    canvas = [B.Buf(np.zeros((ih, iw), F)) for _ in range(4)]
+    B.blend_frame(info, hdr, canvas, [B.Buf(np.zeros((fh, fw), F)) for _ in range(3)] + [buf], [None] * 4)
+    return (canvas[3].a, None) if k == 1 else (model, mag)
 
 
 def fit(make, seed):
@@ -353,6 +469,64 @@ def _case(fn, *a, **kw):
     return functools.partial(fit, lambda seed: fn(seed, *a, **kw))
 
 
+# ---- the cases of the frame's tail -----------------------------------------------------------------------------------------------
+RAGGED_TYPES = MID_TYPES[:18] + (4, 5, 6, 7, 8, 9, 10, 11)
+# a noise LUT (ten-bit integers, LFGlobal.java:58) with rising and falling segments that touches both ends of its range
+NOISE_LUT = (0, 300, 1023, 640, 900, 120, 0, 512)
+# what puts the inputs of the noise strength, 3 (Y +- X), on both sides of [0, 7): LF integers of +-600 at a dequantiser of 1 / 187
+NOISE_FIELD = dict(lf_amp=600, global_scale=1500, quant_lf=16, noise=list(NOISE_LUT))
+
+
+def up_weights_case(seed):
+    """fifteen coefficients that are not the default ones: each default moved by up to a fifth of itself, as an exact half"""
+    rng = np.random.default_rng(seed)
+    packed = [_f16(float(v) * (1.0 + rng.uniform(-0.2, 0.2))) for v in upweights.DEFAULT_UP[2]]
+    return draw(seed, 40, 40, upsampling=2, up_weights={2: packed})
+
+
+def _opsin(rng):
+    """OpsinInverseMatrix.java:61-73: a matrix near the default one, biases and quantisation biases of their usual size, all halves"""
+    return dict(matrix=[_f16(v * (1.0 + rng.uniform(-0.1, 0.1))) for v in DEFAULT_OPSIN],
+                opsin_bias=[_f16(v) for v in (-0.0045, -0.003, -0.0036)], quant_bias=[_f16(v) for v in (0.9, 0.85, 0.97)],
+                quant_bias_numerator=_f16(0.2))
+
+
+def opsin_case(seed, **kw):
+    return draw(seed, 40, 40, opsin=_opsin(np.random.default_rng(seed)), **kw)
+
+
+def alpha_case(seed, width, height, k=1, **kw):
+    """an alpha channel of eight bits with 0 and 255 in it, of the frame's size; k: the factor of the colours and of the alpha"""
+    rng = np.random.default_rng(seed)
+    plane = rng.integers(0, 256, (height, width))
+    plane.reshape(-1)[rng.choice(plane.size, 2, replace=False)] = (0, 255)
+    return draw(seed, width, height, extra=[dict(bits=8, alpha_associated=False, plane=plane, upsampling=k)], upsampling=k, **kw)
+
+
+TAIL_CASES = {
+    "up2_19x15_of_37x29": (_case(draw, 19, 15, upsampling=2, image_width=37, image_height=29), 31),
+    "up4_ragged": (_case(draw, 67, 83, allowed=RAGGED_TYPES, upsampling=4), 32),
+    "up8_40x40": (_case(draw, 40, 40, upsampling=8), 33),
+    "up2_custom_weights": (functools.partial(fit, up_weights_case), 34),
+    "noise_40x40": (_case(draw, 40, 40, **NOISE_FIELD), 35),
+    "noise_264x264": (_case(draw, 264, 264, allowed=MID_TYPES, density=0.03, **NOISE_FIELD), 36),
+    "noise_up2": (_case(draw, 136, 20, upsampling=2, **NOISE_FIELD), 37),
+    # (not in the list the cases were asked for: noise is initialised at the upsampled frame's size, 272 x 40, which the image crops)
+    "noise_up2_of_271x39": (_case(draw, 136, 20, upsampling=2, image_width=271, image_height=39, **NOISE_FIELD), 46),
+    "noise_corr": (_case(draw, 40, 40, corr=dict(colour_factor=100, base_x=_f16(0.05), base_b=_f16(0.9), x_factor_lf=140,
+                                                  b_factor_lf=100), **NOISE_FIELD), 38),
+    "ycbcr_444": (_case(draw, 40, 40, xyb=False, do_ycbcr=True), 39),
+    "opsin_custom": (functools.partial(fit, functools.partial(opsin_case, intensity_target=1000.0)), 40),
+    "opsin_custom_epf2": (functools.partial(fit, functools.partial(opsin_case, epf_iters=2, **SMOOTH)), 41),
+    "opsin_custom_up2": (functools.partial(fit, functools.partial(opsin_case, upsampling=2)), 42),
+    "alpha_40x40": (functools.partial(fit, functools.partial(alpha_case, width=40, height=40)), 43),
+    # (the tree splits on the stream index between the second and the third group's Modular stream: 18 + 3 + group)
+    "alpha_264x264": (functools.partial(fit, functools.partial(alpha_case, width=264, height=264, allowed=MID_TYPES, density=0.03,
+                                                               tree=dict(property=1, value=22, predictors=(4, 5)))), 44),
+    "alpha_up2": (functools.partial(fit, functools.partial(alpha_case, width=40, height=40, k=2)), 45),
+}
+
+
 CASES = {
     "one_dct8": (_case(draw, 8, 8, allowed=(0,), dense=True), 11),
     "ragged_67x83": (_case(draw, 67, 83, allowed=MID_TYPES[:18] + (4, 5, 6, 7, 8, 9, 10, 11)), 12),
@@ -381,6 +555,8 @@ for _t in range(27):  # each type alone in a frame of its own pixel size
 QUANT_CASES = tuple("quant_%d" % _s for _s in range(8))
 for _s in range(8):
     CASES["quant_%d" % _s] = (quant_case(_s), 0)
+OLD_CASES = tuple(sorted(CASES))  # the cases whose bytes tests/golden/jxl_writer_vardct_sha256.json records
+CASES.update(TAIL_CASES)
 
 _built = {}
 
@@ -421,4 +597,20 @@ VARIANT_CASES = {
     "lf_buffer_order": ("one_dct8", "lf_rough", "s420"),
     "block_info_rows_exchanged": ("ragged_67x83", "type_05"),
     "raw_stream_index_off_by_one": QUANT_CASES,
+    "noise_lut_after_lf_dequant": ("noise_40x40", "noise_up2", "noise_up2_of_271x39", "noise_corr"),
+    "extra_group_stream_index_off_by_one": ("alpha_264x264",),
 }
+
+
+@functools.lru_cache(maxsize=None)
+def expected_image(name):
+    """tail_model of the case: the planes after the colour transforms on the frame's upsampled bounds, with their companion"""
+    t = tail_model(source(name), model=expected(name, EPF_STAGES))
+    return t["x"], t["a"]
+
+
+def expected_extras(name):
+    """[(plane of the image's size, companion | None)] of the case's extra channels"""
+    src = source(name)
+    return [extra_model(src, e) for e in src.get("extra", [])]
+

@@ -1,8 +1,13 @@
 """The VarDCT route pinned to known coefficients, on the CPU: every case of jxl_writer_vardct_cases.py is written by
 jxl_writer_vardct.py, read by the front-end -- whose every integer must be the SOURCE's -- and decoded on the oracle backend, whose
-planes at the cut points idct / gab / epf / xyb must be the float64 models' of the SOURCE within K u (A + |model|). Then the
-discrimination: nine writers that compute a context or a placement the wrong way, three expectations made the wrong way."""
+planes at the cut points idct / gab / epf / xyb must be the float64 models' of the SOURCE within K u (A + |model|); the cut after
+the colour transforms holds the frame's whole tail (upsampling, noise, inverse XYB, YCbCr), and the image what the blend makes of
+it and of the extra channels. Then the discrimination: eleven writers that compute a context, a placement or a field's place the
+wrong way, ten expectations made the wrong way. The cases this file had before the tail's still encode to the bytes they had."""
+import hashlib
+import json
 import math
+import os
 
 import numpy as np
 import pytest
@@ -59,15 +64,17 @@ def views_differ(data, src):
     shifts = list(src.get("pass_shifts", [])) + [0]
     xyb = src.get("xyb", True)
     info = fe.image
-    want = dict(type=0, encoding=0, do_ycbcr=int(src.get("do_ycbcr", False)), upsampling=1, group_dim=256,
+    extra = src.get("extra", [])
+    want = dict(type=0, encoding=0, do_ycbcr=int(src.get("do_ycbcr", False)), upsampling=src.get("upsampling", 1), group_dim=256,
                 xqm=src.get("xqm", 3) if xyb else 2, bqm=src.get("bqm", 2) if xyb else 2, lf_level=0,
-                flags=V.FLAG_SKIP_ADAPTIVE_LF_SMOOTHING if src.get("skip_smoothing", False) else 0, num_passes=len(shifts),
+                flags=(V.FLAG_SKIP_ADAPTIVE_LF_SMOOTHING if src.get("skip_smoothing", False) else 0) |
+                (V.FLAG_NOISE if src.get("noise") is not None else 0), num_passes=len(shifts),
                 x0=0, y0=0, width=-(-src["width"] // (1 << max(sx))) << max(sx), height=-(-src["height"] // (1 << max(sy))) << max(sy),
                 padded_width=geo["pw"], padded_height=geo["ph"], is_last=1, gab=p.gab, epf_iters=p.epf_iters,
                 num_groups=geo["num_groups"], num_lf_groups=geo["num_lf_groups"], group_cols=geo["cols"], lf_group_cols=geo["lcols"],
                 global_scale=src["global_scale"], quant_lf=src["quant_lf"], colour_factor=p.color_factor, x_factor_lf=p.x_factor_lf,
                 b_factor_lf=p.b_factor_lf, quant_all_default=int(src.get("quant") is None), num_hf_presets=src.get("num_presets", 1),
-                num_patches=0, has_splines=0, has_noise=0, num_modular_channels=0)
+                num_patches=0, has_splines=0, has_noise=int(src.get("noise") is not None), num_modular_channels=len(extra))
     for k, v in want.items():
         if getattr(fr, k) != v:
             return "FrameInfo.%s: %r for %r" % (k, getattr(fr, k), v)
@@ -81,8 +88,30 @@ def views_differ(data, src):
     for k, v in scal.items():
         if F(getattr(fr, k)) != F(v):
             return "FrameInfo.%s: %r for %r" % (k, getattr(fr, k), v)
-    if bool(info.xyb_encoded) != xyb or (info.width, info.height) != (src["width"], src["height"]):
+    if bool(info.xyb_encoded) != xyb or (info.height, info.width) != V.image_size(src) or info.num_extra != len(extra):
         return "ImageInfo"
+    if F(info.intensity_target) != p.intensity_target:
+        return "ImageInfo.intensity_target: %r for %r" % (info.intensity_target, p.intensity_target)
+    if list(fr.ec_upsampling)[:len(extra)] != [e.get("upsampling", 1) for e in extra]:
+        return "FrameInfo.ec_upsampling: %r" % list(fr.ec_upsampling)[:len(extra)]
+    if src.get("noise") is not None and [F(v) for v in fr.noise] != [F(v) / F(1024) for v in src["noise"]]:  # LFGlobal.java:58
+        return "FrameInfo.noise: %r for %r" % (list(fr.noise), src["noise"])
+    up = src.get("up_weights") or {}
+    for idx, k in enumerate((2, 4, 8)):
+        if bool(info.custom_up[idx]) != (k in up):
+            return "ImageInfo.custom_up: %r" % list(info.custom_up)
+        if k in up and [F(v) for v in fe.up_weights(idx)] != [F(v) for v in up[k]]:
+            return "upsampling weights of factor %d" % k
+    for i, e in enumerate(extra):  # the channel whole, and every group's crop of it
+        got, a = np.asarray(fe.modular_channel(i)[0])[:src["height"], :src["width"]], np.asarray(e["plane"])
+        if got.shape != a.shape:
+            return "extra channel %d: shape %r" % (i, got.shape)
+        for grp in range(geo["num_groups"]):
+            gy, gx = (grp // geo["cols"]) * 256, (grp % geo["cols"]) * 256
+            if not np.array_equal(got[gy:gy + 256, gx:gx + 256], a[gy:gy + 256, gx:gx + 256]):
+                return "extra channel %d group %d" % (i, grp)
+        if info.ec_bits[i] != e.get("bits", 8) or bool(info.ec_alpha_associated[i]) != e.get("alpha_associated", False):
+            return "extra channel %d header" % i
     if [F(v) for v in info.quant_bias] != p.quant_bias or F(info.quant_bias_numerator) != p.quant_bias_numerator or \
             [F(v) for v in info.opsin_matrix] != p.opsin_matrix or [F(v) for v in info.opsin_bias] != p.opsin_bias:
         return "ImageInfo opsin"
@@ -135,6 +164,16 @@ def test_front_end_hands_out_the_source(name):
     assert views_differ(C.encoded(name), C.source(name)) is None
 
 
+def test_the_earlier_cases_encode_to_the_bytes_they_had():
+    """the writer's new keys default to the bytes it wrote without them: tests/golden/jxl_writer_vardct_sha256.json holds the SHA-256
+    of every case's codestream as the writer made it before it knew upsampling, extra channels, noise or a custom opsin matrix"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jxl_writer_vardct_sha256.json")) as f:
+        want = json.load(f)
+    assert sorted(want) == list(C.OLD_CASES) and len(want) == 55
+    for name in C.OLD_CASES:
+        assert hashlib.sha256(C.encoded(name)).hexdigest() == want[name], name
+
+
 def test_cases_are_what_they_claim():
     """the properties the cases are there for, checked on the SOURCE"""
     s = C.source
@@ -170,6 +209,30 @@ def test_cases_are_what_they_claim():
         filtered = np.repeat(np.repeat(sig <= M.COPY_THRESHOLD, 8, 0), 8, 1)
         assert 0.5 < filtered.mean() < 1.0 and (np.abs(e - g) > 1000 * M.U * (ga + np.abs(g)))[:, filtered].mean() > 0.25, n
         assert len(np.unique(s(n)["lfgroups"][0]["sharpness"])) >= 6  # (25 cells)
+    # the tail's cases: some upsampled outputs are clamped and most are not; the noise strength's inputs lie under 0 and over 7 / 3
+    # and between them in at least five of the LUT's seven segments; the LUT rises and falls and holds both ends of its range
+    for n in sorted(C.TAIL_CASES):
+        t = C.tail_model(s(n)) if s(n).get("upsampling", 1) > 1 or s(n).get("noise") is not None else {}
+        print(n, {k: v for k, v in t.items() if k not in ("x", "a")})
+        if s(n).get("upsampling", 1) > 1:
+            assert 0.005 <= t["clamped"] <= 0.5, (n, t["clamped"])
+        if s(n).get("noise") is not None:
+            assert t["below"] > 0 and t["above"] > 0 and len(t["segments"]) >= 5, n
+            d = np.diff(s(n)["noise"])
+            assert (d > 0).any() and (d < 0).any() and min(s(n)["noise"]) == 0 and max(s(n)["noise"]) == 1023
+    up = s("up2_19x15_of_37x29")
+    assert V.image_size(up) == (29, 37) and (2 * up["height"], 2 * up["width"]) == (30, 38)  # the image crops the upsampled frame
+    assert V.padded_size(s("up4_ragged")) == (88, 72) and V.image_size(s("up4_ragged")) == (332, 268) and V.image_size(s("up8_40x40")) == (320, 320)
+    assert V.image_size(s("noise_up2_of_271x39")) == (39, 271) and V.image_size(s("noise_up2")) == (40, 272) and V.geometry(s("noise_up2"))["num_groups"] == 1  # one group before, two after
+    assert V.geometry(s("noise_264x264"))["num_groups"] == 4
+    assert [float(F(v)) for v in s("up2_custom_weights")["up_weights"][2]] != [float(F(v)) for v in C.upweights.DEFAULT_UP[2]]
+    assert s("noise_corr")["corr"]["base_x"] != 0.0 and s("noise_corr")["corr"]["base_b"] != 1.0
+    assert s("opsin_custom")["intensity_target"] == 1000.0 and s("opsin_custom_epf2")["epf_iters"] == 2
+    assert not V.extras_in_groups(s("alpha_40x40")) and V.extras_in_groups(s("alpha_264x264"))
+    assert s("alpha_264x264")["tree"] == dict(property=1, value=22, predictors=(4, 5))  # the group streams are 21 .. 24
+    for n in ("alpha_40x40", "alpha_264x264", "alpha_up2"):
+        a = np.asarray(s(n)["extra"][0]["plane"])
+        assert a.min() == 0 and a.max() == 255 and len(np.unique(a)) >= 200
     for n in NAMES:
         assert C.conditions(s(n)) is None, n
         for cm, cfgs in s(n)["hf_clusters"]:
@@ -183,8 +246,7 @@ def cut_ratios(name, out):
     if "idct" in out:
         rows = [(cut, stage, R.ratio(out[cut], name, stage), R.bound(name, stage)) for cut, stage, _ in R.CUTS]
     fs = R.final_stage(name)
-    if fs is not None:
-        rows.append(("xyb", fs, R.ratio(out["xyb"], name, fs), R.bound(name, fs)))
+    rows.append(("xyb", fs, R.ratio(out["xyb"], name, fs), R.bound(name, fs)))
     return rows
 
 
@@ -193,6 +255,27 @@ def test_oracle_decode_is_the_model_at_every_cut(name, backend):
     for cut, stage, r, k in cut_ratios(name, decoded(name, backend)):
         print("%s %s (stages %d): needs K = %.2f of %d" % (name, cut, stage, r, k))
         assert r <= k, (name, cut, r, k)
+
+
+@pytest.mark.parametrize("name", sorted(C.TAIL_CASES))
+def test_oracle_image_is_the_model_cropped_to_the_image(name, backend):
+    """what decode() returns: the colour planes are the tail's model cropped to the image's size, within the K of the cut after the
+    colour transforms; an extra channel is its source cast to float, bit for bit, or -- upsampled -- the model's within K_UPSAMPLE"""
+    src, out = C.source(name), decoded(name, backend)
+    planes = out["image"].getBuffer()
+    ih, iw = V.image_size(src)
+    assert len(planes) == 3 + len(src.get("extra", [])) and all(p.shape == (ih, iw) and p.dtype == np.float32 for p in planes)
+    fs = R.final_stage(name)
+    r, k = R.ratio(np.stack(planes[:3]), name, fs), R.bound(name, fs)
+    print("%s image: needs K = %.2f of %d" % (name, r, k))
+    assert r <= k, (name, r, k)
+    for i, (x, a) in enumerate(C.expected_extras(name)):
+        if a is None:
+            assert np.array_equal(planes[3 + i].view(np.uint32), np.asarray(x, F).view(np.uint32)), (name, i)
+        else:
+            r = M.error_ratio(planes[3 + i], x, a)
+            print("%s extra channel %d: needs K = %.2f of %d" % (name, i, r, R.K_UPSAMPLE))
+            assert r <= R.K_UPSAMPLE, (name, i, r)
 
 
 def test_measured_rows_are_twice_the_largest_ratio(backend):
@@ -216,7 +299,7 @@ def test_measured_rows_are_twice_the_largest_ratio(backend):
 
 # ---- discrimination ------------------------------------------------------------------------------------------------------------
 def test_every_writer_variant_is_listed():
-    assert set(C.VARIANT_CASES) == set(V.VARIANTS) and len(V.VARIANTS) == 9
+    assert set(C.VARIANT_CASES) == set(V.VARIANTS) and len(V.VARIANTS) == 11
 
 
 @pytest.mark.parametrize("variant", V.VARIANTS)
@@ -243,10 +326,17 @@ def _default_weights(name):
     return C.model_frame(C.source(name), weights=(t.w, t.offs))
 
 
+def _default_quant_bias(name):
+    src = dict(C.source(name))
+    src["opsin"] = {k: v for k, v in src["opsin"].items() if k not in ("quant_bias", "quant_bias_numerator")}
+    return C.model_frame(C.source(name), params=C.params_of(src))
+
+
 CASE_VARIANTS = {
     "scale_factor with xqm and bqm exchanged": (_swapped_qm, ("xqm0_bqm7",)),
     "extra_precision ignored": (lambda name: C.model_frame(C.source(name), extra_precision=0), ("lf_rough",)),
     "default weights for the custom ones": (_default_weights, C.QUANT_CASES),
+    "default quant_bias for the custom one": (_default_quant_bias, ("opsin_custom", "opsin_custom_epf2", "opsin_custom_up2")),
 }
 
 
@@ -259,3 +349,53 @@ def test_a_wrong_expectation_leaves_the_bound(what, backend):
         k = R.bound(name, R.IDCT)
         print("%s on %s: %.4g K" % (what, name, r / k))
         assert r > LARGE * k, (what, name, r, k)
+
+
+def _without(name, key):
+    src = dict(C.source(name))
+    del src[key]
+    return C.params_of(src)
+
+
+# expectations of the frame's tail made the wrong way, held against the cut after the colour transforms
+TAIL_VARIANTS = {
+    "noise seeded with (0 << 32) | 0": (lambda name: C.tail_model(C.source(name), seed0=0), ("noise_40x40", "noise_264x264", "noise_up2", "noise_up2_of_271x39", "noise_corr")),
+    "noise groups of the size before upsampling": (lambda name: C.tail_model(C.source(name), noise_group_dim=2 * V.GROUP_DIM), ("noise_up2", "noise_up2_of_271x39")),
+    "Cb and Cr exchanged": (lambda name: C.tail_model(C.source(name), exchange_cb_cr=True), ("ycbcr_444", "s420", "s422", "s440")),
+    "default upsampling weights for the custom ones": (lambda name: C.tail_model(C.source(name), default_up_weights=True), ("up2_custom_weights",)),
+    # (Frame.performUpsampling runs on the reference's padded buffers, Frame.java:232-245: beside the right and lower edge of a frame
+    # whose size is no multiple of 8 its window holds the last blocks' padding. The decoder mirrors at the frame's bounds, as the
+    # format's upsampling is defined; DESIGN section 3, Findings)
+    "upsampling of the padded planes": (lambda name: C.tail_model(C.source(name), upsample_padded=True), ("up2_19x15_of_37x29", "up4_ragged")),
+    "intensity_target 255 for the one written": (lambda name: C.tail_model(C.source(name), params=_without(name, "intensity_target")), ("opsin_custom",)),
+}
+
+
+@pytest.mark.parametrize("what", sorted(TAIL_VARIANTS))
+def test_a_wrong_expectation_of_the_tail_leaves_the_bound(what, backend):
+    make, names = TAIL_VARIANTS[what]
+    for name in names:
+        t = make(name)
+        r = R.ratio(decoded(name, backend)["xyb"], name, R.TAIL, model=(t["x"], t["a"]))
+        k = R.bound(name, R.TAIL)
+        print("%s on %s: %.4g K" % (what, name, r / k))
+        assert r > LARGE * k, (what, name, r, k)
+
+
+ALPHA_CASES = ("alpha_40x40", "alpha_264x264", "alpha_up2")
+
+
+@pytest.mark.parametrize("name", ALPHA_CASES)
+def test_png_samples_of_an_alpha_case_are_the_packed_model(name, backend):
+    """PNGWriter on the oracle-backed image: RGBA of eight bits, every sample inside jxl_writer_vardct_run.sample_bounds"""
+    from jxlatte_amd.decoder import PNGWriter
+    from test_jxl_writer_cpu import png_of
+    w = PNGWriter(decoded(name, backend)["image"])
+    got = png_of(w).astype(np.int64)
+    lo, hi = R.sample_bounds(name, "srgb")
+    assert w.bitDepth == 8 and got.shape == lo.shape
+    print("%s: %d of %d samples have two admissible values" % (name, int((lo != hi).sum()), lo.size))
+    assert ((lo <= got) & (got <= hi)).all(), (name, int(((got < lo) | (got > hi)).sum()))
+    assert (lo != hi).mean() < 0.1 and len(np.unique(got[..., :3])) > 50  # (nine samples of ten have one admissible value)
+    if name != "alpha_up2":
+        assert np.array_equal(got[..., 3], np.asarray(C.source(name)["extra"][0]["plane"]))

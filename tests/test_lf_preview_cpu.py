@@ -34,7 +34,15 @@ from jxlatte_amd.decoder import JXLDecoder, UnsupportedOperationException
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SAMPLES = os.path.join(ROOT, "tests", "golden", "samples")
 F = np.float32
-WRITER = ("one_dct8", "ragged_67x83", "groups_264x264", "two_lf_groups_2056x16", "passes_2", "lf_rough", "corr", "rgb")
+WRITER = ("one_dct8", "ragged_67x83", "groups_264x264", "two_lf_groups_2056x16", "passes_2", "lf_rough", "corr", "rgb",
+          "noise_40x40", "ycbcr_444", "opsin_custom")  # (noise is left out, YCbCr without subsampling and any opsin matrix are accepted)
+# the writer cases that downsample=8 refuses, with the reason preview_rule gives (the first condition that fails, in its order)
+WRITER_RULE = dict(up2_19x15_of_37x29="not the image's only frame",  # 2 x 19 is not 37: the size test comes before the factor's
+                   up4_ragged="the frame is upsampled", up8_40x40="the frame is upsampled", up2_custom_weights="the frame is upsampled",
+                   noise_up2="the frame is upsampled", noise_up2_of_271x39="not the image's only frame", opsin_custom_up2="the frame is upsampled",
+                   alpha_40x40="the image has extra channels", alpha_264x264="the image has extra channels",
+                   alpha_up2="the image has extra channels", s420="chroma subsampling", s422="chroma subsampling",
+                   s440="chroma subsampling")
 FILES = ("white", "lenna", "bbb", "bench")
 SEAM_CASE = "two_lf_groups_2056x32"
 
@@ -260,9 +268,12 @@ def test_preview_of_a_writer_case_is_the_composition_of_its_source(orc, name):
     assert be.vardct_calls == 0 and len(be.lf_calls) == 1
     pre = compose(orc, groups, cells, float(p.base_corr_x), float(p.base_corr_b), p.color_factor)
     want = pre if xyb is None else orc.xyb(pre, *[list(v) for v in xyb[:3]], xyb[3])
+    if src.get("do_ycbcr", False):
+        want = orc.ycbcr(want)
     assert (im.getHeight(), im.getWidth()) == cells == (-(-src["height"] // 8), -(-src["width"] // 8))
     assert_bits_equal(np.stack(im.getBuffer(copy=False)), want, name)
-    assert dec.stats[-1]["preview"] == "lf image (1:8)" and dec.stats[-1]["output"] == "host" and dec.decode() is None
+    note = "lf image (1:8)" + (", noise left out" if src.get("noise") is not None else "")
+    assert dec.stats[-1]["preview"] == note and dec.stats[-1]["output"] == "host" and dec.decode() is None
     # before the inverse XYB: the float64 model of the SOURCE, within the LF stage's K (jxl_writer_vardct_run.K_LF)
     for g, d in zip(src["lfgroups"], groups):
         x = np.stack(C.lf_planes(src, g, p))
@@ -350,6 +361,25 @@ def test_preview_rule_on_header_fields():
     assert rule(jpeg_up_x=[1, 0, 1]) == rule(jpeg_up_y=[0, 0, 1]) == "chroma subsampling"
     assert rule(num_patches=2, flags=2) == "patches" and rule(has_splines=1, flags=16) == "splines"
     assert JXLDecoder.preview_rule(types.SimpleNamespace(num_extra=1, width=40, height=24), types.SimpleNamespace(**ok)) == "the image has extra channels"
+
+
+@pytest.mark.parametrize("name", sorted(WRITER_RULE))
+def test_preview_rule_on_the_writer_cases(orc, name):
+    """every writer case outside WRITER is refused for the reason the rule gives, by the rule and by a decode; the others pass it"""
+    fe, fr, _ = lf_only(encoded(name), False)
+    assert JXLDecoder.preview_rule(fe.image, fr) == WRITER_RULE[name]
+    be = make_backend(orc)
+    with pytest.raises(UnsupportedOperationException) as e:
+        JXLDecoder(encoded(name), backend=be, downsample=8).decode()
+    assert str(e.value) == "downsample=8: " + WRITER_RULE[name] and be.vardct_calls == 0 and not be.lf_calls
+
+
+def test_the_writer_rule_table_covers_the_tail_cases():
+    also = ("noise_264x264", "noise_corr", "opsin_custom_epf2")  # accepted like their siblings in WRITER; not decoded here
+    assert set(C.TAIL_CASES) == (set(WRITER) | set(WRITER_RULE) | set(also)) & set(C.TAIL_CASES)
+    for name in WRITER + also:
+        fe, fr, _ = lf_only(encoded(name), False)
+        assert JXLDecoder.preview_rule(fe.image, fr) is None, name
 
 
 def test_s420_is_refused_for_its_subsampling():

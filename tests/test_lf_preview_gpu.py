@@ -117,7 +117,7 @@ def test_the_entries_refuse_what_the_validator_refuses(ctx):
 
 
 # ---- the decoder ---------------------------------------------------------------------------------------------------------------------
-NAMES = ("lenna", "bbb", "bench", "white", "two_lf_groups_2056x16", "rgb")
+NAMES = ("lenna", "bbb", "bench", "white", "two_lf_groups_2056x16", "rgb", "noise_40x40", "ycbcr_444", "opsin_custom")
 
 
 @pytest.fixture(scope="module")
@@ -149,7 +149,8 @@ def test_device_decode_equals_the_cpu_decode(backend, orc, name, device_output):
     dec = JXLDecoder(data_of(name), backend=backend, downsample=8, device_output=device_output)
     im = dec.decode()
     st = dec.stats[-1]
-    assert st["preview"] == note == "lf image (1:8)" and st["output"] == ("device" if device_output else "host")
+    assert note == "lf image (1:8)" + (", noise left out" if name == "noise_40x40" else "")
+    assert st["preview"] == note and st["output"] == ("device" if device_output else "host")
     assert im.onDevice() == device_output and (im.getHeight(), im.getWidth()) == exp[0].shape
     assert_bits_equal(np.stack(im.getBuffer(copy=False)), np.stack(exp), name)
     assert dec.decode() is None
@@ -184,3 +185,11 @@ def test_a_refused_frame_raises_on_the_device_backend_too(backend):
     with pytest.raises(UnsupportedOperationException) as e:
         JXLDecoder(L.sample("patches-lossless"), backend=backend, downsample=8).decode()
     assert str(e.value) == "downsample=8: the image has extra channels"
+
+
+@pytest.mark.parametrize("name", sorted(L.WRITER_RULE))
+def test_a_refused_writer_case_raises_on_the_device_backend_too(backend, name):
+    from jxlatte_amd.decoder import UnsupportedOperationException
+    with pytest.raises(UnsupportedOperationException) as e:
+        JXLDecoder(L.encoded(name), backend=backend, downsample=8).decode()
+    assert str(e.value) == "downsample=8: " + L.WRITER_RULE[name]

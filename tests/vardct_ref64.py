@@ -485,6 +485,23 @@ def xyb(x, a, matrix, opsin_bias, cbrt_opsin_bias, intensity_target, mut=None):
     return np.einsum("ij,jhw->ihw", m, mix), np.einsum("ij,jhw->ihw", np.abs(m), mixa)
 
 
+YCBCR_OFFSET = 0.50196078431372549019  # the float literals of JXLCodestreamDecoder.java:275-279
+YCBCR_R_CR, YCBCR_G_CB, YCBCR_G_CR, YCBCR_B_CB = 1.402, 0.34413628620102214650, 0.71413628620102214650, 1.772
+
+
+def ycbcr(x, a):
+    """the YCbCr loop of JXLCodestreamDecoder.performColorTransforms (JXLCodestreamDecoder.java:270-281): plane 0 is Cb, plane 1 Y,
+    plane 2 Cr; the result is R, G, B. The reference runs it over getPaddedFrameSize() of the frame's bounds (:271), a region that
+    holds the bounds, on buffers of at least that size; it works sample by sample, so on planes cropped to the bounds it is the
+    whole plane."""
+    x, a = np.asarray(x, D), np.asarray(a, D)
+    off, r_cr, g_cb, g_cr, b_cb = (float(np.float32(v)) for v in (YCBCR_OFFSET, YCBCR_R_CR, YCBCR_G_CB, YCBCR_G_CR, YCBCR_B_CB))
+    yh, ya = x[1] + off, a[1] + off
+    out = np.stack([yh + r_cr * x[2], yh - g_cb * x[0] - g_cr * x[2], yh + b_cb * x[0]])
+    mag = np.stack([ya + r_cr * a[2], ya + g_cb * a[0] + g_cr * a[2], ya + b_cb * a[0]])
+    return out, mag
+
+
 def decode(frame, stages, mut=None):
     """the stages of one frame as the reference runs them (Frame.java:455-463: inverse transforms, invertSubsampling, Gaborish,
     EPF; JXLCodestreamDecoder: invertXYB). stages: 2 adds Gaborish, 4 the EPF, 8 the inverse XYB to the inverse transforms.
