@@ -62,8 +62,10 @@ __device__ __forceinline__ float epf_quot_by(float n, float d, float r1) {
 // wave-uniform branch per patch (a branch per pixel pinned the register allocation of the fused kernel's 64-register variants into
 // scratch): every numerator of the patch inside the window -> the shared-reciprocal sequence for all of them, else the plain
 // divisions for all of them.
-template <int NP>
-__device__ __forceinline__ void epf_quot3_patch(const float n[3][NP], const float d[NP], float out[3][NP]) {
+// plain(c, i, q): what the plain-division branch -- and only that branch -- stores for quotient q of channel c, pixel i. The fused
+// kernel keeps its select of skipped pixels there (restore_fused_body.h, epf_patch, says why the fast branch needs none).
+template <int NP, typename Plain>
+__device__ __forceinline__ void epf_quot3_patch(const float n[3][NP], const float d[NP], float out[3][NP], Plain plain) {
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(!epf_quot3_in_window<NP>(n)) == 0, 1)) {
 #pragma unroll
         for (int i = 0; i < NP; i++) {
@@ -75,8 +77,12 @@ __device__ __forceinline__ void epf_quot3_patch(const float n[3][NP], const floa
 #pragma unroll
         for (int i = 0; i < NP; i++)
 #pragma unroll
-            for (int c = 0; c < 3; c++) out[c][i] = n[c][i] / d[i];
+            for (int c = 0; c < 3; c++) out[c][i] = plain(c, i, n[c][i] / d[i]);
     }
+}
+template <int NP>
+__device__ __forceinline__ void epf_quot3_patch(const float n[3][NP], const float d[NP], float out[3][NP]) {
+    epf_quot3_patch<NP>(n, d, out, [](int, int, float q) { return q; });
 }
 
 // one pixel: out[c] = nc / d (the patch form with NP = 1; what jxl_debug_epf_quot3 runs, one lane per element)

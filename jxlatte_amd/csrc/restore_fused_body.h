@@ -260,7 +260,8 @@ __device__ __forceinline__ void epf_patch(const float* __restrict__ src, int ry,
             const float d = dist[i][t] * bmul[i];
             const float v = 1.0f - d * ep.sigma_scale * s;
             // max(v, 0): the reference's `v < 0 ? 0 : v` (Frame.java:676-678) for every v that is not NaN or -0. v = 1 - x is -0 for no x,
-            // and NaN only where inv sigma is not finite or the samples are not -- pixels the `skip` select below replaces anyway.
+            // and NaN only where inv sigma is not finite or the samples are not -- skipped pixels, whose result is their centre sample
+            // whatever their weights (the `skip` select of the plain divisions; on the fast path a NaN weight clamps to 0, see there).
             // x = dist * bmul * sigma_scale * s is >= 0 or NaN when channel_scale[], border_sad_mul, sigma_scale and the inverse sigma
             // are not negative (epf_weights_plain() is false: the !PLAINDIV instantiations), so every weight lies in [0, 1] and
             // 1 <= sumW <= 1 + NT for EVERY pixel, skipped ones included (their weights are formed like any other before the select
@@ -300,20 +301,19 @@ __device__ __forceinline__ void epf_patch(const float* __restrict__ src, int ry,
                     num[c][i] = sc;
                 }
         }
-        float q[3][NP];
-        epf_quot3_patch<NP>(num, sumW, q);
-#pragma unroll
-        for (int py = 0; py < PH; py++)
-#pragma unroll
-            for (int px = 0; px < 4; px++)
-#pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    const int i = py * 4 + px;
-                    // formed unconditionally, as below; a skipped pixel keeps its centre sample
-                    float qv = q[c][i];
-                    asm volatile("" : "+v"(qv));
-                    res[c][i] = skip[i] ? src[c * PLANE + (ry + py) * SW + rx + px] : qv;
-                }
+        // A skipped pixel (:608-612) needs no select here. Its inverse sigma arrives as s = +inf (the window load of
+        // restore_fused_body makes every NaN and every value above 1 / 0.3f that), and with no negative factor in the weights:
+        //   x = d * sigma_scale * s is +inf or NaN (d >= 0 or NaN; 0 * inf is NaN), v = 1 - x is -inf or NaN, and the clamped weight is
+        //   exactly +0 (maxnum and DX10_CLAMP, as above) for every tap;  sumW = 1 + 0 + ... is exactly 1, inside epf_quot3_patch's window;
+        //   the numerator is (0 + centre * 1) + nb * 0 + ..., i.e. centre + (+-0) + ... = centre bit for bit when the centre is
+        //   not +-0 and every neighbour is finite;  and epf_quot_by(n, 1, 1) is n (r0 = r1 = 1, every error term 0).
+        // Where that fails -- a centre that is +-0 (numerator +0 whatever its sign) or a neighbour that is not finite (nb * 0 is NaN) -- the
+        // numerator is 0 or NaN, outside the guard's window [2^-100, 2^90], and the whole wave takes the plain divisions, where the
+        // select stays: its predicate holds for +inf. (Denormal and huge centres go there too, as they always did.)
+        epf_quot3_patch<NP>(num, sumW, res, [&](int c, int i, float q) {
+            const float s = s_inv[i];
+            return ((s != s) || (s > (1.0f / 0.3f))) ? src[c * PLANE + (ry + i / 4) * SW + rx + i % 4] : q;
+        });
         return;
     }
 #pragma unroll
@@ -534,7 +534,14 @@ __device__ __forceinline__ void restore_fused_body(const FusedArgs& a) {
     using G = Geo<GAB, ITERS>;
     constexpr int NTHR = 512 / PH;
     extern __shared__ float lds[];
-    float* A = lds;                   // the tile: 3 planes, every stage works in place
+    // cell-tiled input: the tile starts three floats into the allocation, so that the whole-piece loader below may write up to three
+    // samples in front of row 0 of the first plane. LDS_BYTES does not grow for it: the tile's last three floats -- pad columns of
+    // the third plane's spare row IH, which no loader and no write-back reaches -- now lie over the first three sigma cells, and
+    // are as before only ever read, by a patch's over-read, for results that are dropped. (The sigma window in front of the tile
+    // would serve too -- its row 15 is never read --, but a base of 1 KiB takes the paired LDS reads of the EPF stages out of their
+    // immediate range: +21 address instructions per thread, counted; three floats cost 3.)
+    constexpr int FRONT = LAY == 1 ? 3 : 0;
+    float* A = lds + FRONT;           // the tile: 3 planes, every stage works in place
     float* sig = lds + 3 * G::PLANE;  // [16][16] inverse sigma of the cells under the tile
     const int W = a.W, H = a.H;
     TileCtx tc;
@@ -564,6 +571,9 @@ __device__ __forceinline__ void restore_fused_body(const FusedArgs& a) {
         const int cy = scy0 + (threadIdx.x >> 4), cx = scx0 + (threadIdx.x & 15);
         float v = 0.0f;
         if (cy < ((H + 7) >> 3) && cx < a.bw) v = a.inv_sigma[cy * a.bw + cx];
+        // every cell the reference skips (:608-612: NaN, or above 1 / 0.3f) as +inf, whichever producer wrote the plane: the
+        // skip rule holds for +inf as for the value it replaces, and the fast-division tails of epf_patch rely on the infinity
+        if (v != v || v > (1.0f / 0.3f)) v = __builtin_inff();
         sig[threadIdx.x] = v;
     }
     // load the input tile: clamped coordinates feed Gab, mirrored ones feed EPF directly. Flat row-major
@@ -571,32 +581,53 @@ __device__ __forceinline__ void restore_fused_body(const FusedArgs& a) {
     if (LAY == 1 && !tc.edge) {
         // interior tile of cell-tiled planes: the tile is gathered from the NCY x NCX cells it can overlap (6 x 10 for the 70 x 38 tile),
         // 16 consecutive lanes = the 16 aligned 16-byte pieces of one cell = two whole 128-byte lines. A piece outside the tile is not
-        // loaded (for an interior tile everything inside it lies inside the frame); one that straddles the tile's left or right edge
-        // keeps the samples inside.
+        // loaded (for an interior tile everything inside it lies inside the frame).
         constexpr int NCX = (G::IW + 6) / 8 + 1, NCY = (G::IH + 6) / 8 + 1, TOTAL = NCX * NCY * 16;
         const int cells_w = W >> 3;
         const int ccy0 = tc.iy0 >> 3, ccx0 = tc.ix0 >> 3;
-        const uint32_t base = (uint32_t)(ccy0 * cells_w + ccx0) << 6;
+        // A piece that straddles the tile's left or right edge is stored WHOLE, like every other: no test per sample. Its samples
+        // outside the tile land in the row's pad columns IW .. IW + 2 (SW = IW + 3): up to three past the right edge in the piece's own
+        // row, up to three in front of column 0 at the end of the row above -- for row 0 of the first plane those are the three floats
+        // in front of the tile (FRONT), for the other planes the spare row IH of the plane in front.
+        // Nobody reads a pad column's value: Gaborish reads columns 0 .. IW - 1, and what an EPF patch reads past its region feeds
+        // only results that are dropped. So it does not matter either that the pieces of two rows may write different garbage to the
+        // same pad word in any order.
+        // The lane's pieces are NTHR / 16 cells apart: cell row, cell column, coordinates and offset advance by constants.
+        static_assert(NTHR % 16 == 0, "a lane keeps its piece index");
+        constexpr int CSTEP = NTHR / 16, DY = CSTEP / NCX, DX = CSTEP % NCX;
+        const int pc = threadIdx.x & 15;
+        const int cyi0 = (int)(threadIdx.x >> 4) / NCX;
+        int cxi = (int)(threadIdx.x >> 4) - cyi0 * NCX;
+        int y = ((ccy0 + cyi0) << 3) + (pc >> 1) - tc.iy0, x = ((ccx0 + cxi) << 3) + ((pc & 1) << 2) - tc.ix0;  // tile coordinates
+        // the address: a workgroup-uniform base per plane (the tile's first cell; 64-bit scalar arithmetic) + the lane's BYTE offset
+        // from there in 32 bits (under NCY x cells_w cells of 256 bytes), which is the form a global load takes a scalar base in
+        const size_t tile0 = (size_t)(uint32_t)(ccy0 * cells_w + ccx0) << 6;
+        const char* const in0 = reinterpret_cast<const char*>(a.in[0] + tile0);
+        const char* const in1 = reinterpret_cast<const char*>(a.in[1] + tile0);
+        const char* const in2 = reinterpret_cast<const char*>(a.in[2] + tile0);
+        uint32_t g = ((uint32_t)(cyi0 * cells_w + cxi) << 8) + (uint32_t)(pc << 4);
+        const uint32_t gstep = (uint32_t)(DY * cells_w + DX) << 8, gwrap = (uint32_t)(cells_w - NCX) << 8;
 #pragma unroll
         for (int k = 0; k < (TOTAL + NTHR - 1) / NTHR; k++) {
-            const int idx = (int)threadIdx.x + k * NTHR;
-            const int cell = idx >> 4, pc = idx & 15;
-            const int cyi = cell / NCX, cxi = cell - cyi * NCX;
-            const int y = ((ccy0 + cyi) << 3) + (pc >> 1) - tc.iy0, x = ((ccx0 + cxi) << 3) + ((pc & 1) << 2) - tc.ix0;  // tile coordinates
-            if ((TOTAL % NTHR == 0 || idx < TOTAL) && (unsigned)y < (unsigned)G::IH && x > -4 && x < G::IW) {
-                const uint32_t g = base + ((uint32_t)(cyi * cells_w + cxi) << 6) + (uint32_t)(pc << 2);
-                const float4 v0 = *reinterpret_cast<const float4*>(a.in[0] + g);
-                const float4 v1 = *reinterpret_cast<const float4*>(a.in[1] + g);
-                const float4 v2 = *reinterpret_cast<const float4*>(a.in[2] + g);
+            // (a piece index past TOTAL lies in cell row NCY, whose y is past the tile: 8 NCY - 7 >= IH)
+            if ((unsigned)y < (unsigned)G::IH && (unsigned)(x + 3) < (unsigned)(G::IW + 3)) {
+                const float4 v0 = *reinterpret_cast<const float4*>(in0 + g);
+                const float4 v1 = *reinterpret_cast<const float4*>(in1 + g);
+                const float4 v2 = *reinterpret_cast<const float4*>(in2 + g);
                 float* d = A + y * G::SW + x;
-                const float e0[4] = {v0.x, v0.y, v0.z, v0.w}, e1[4] = {v1.x, v1.y, v1.z, v1.w}, e2[4] = {v2.x, v2.y, v2.z, v2.w};
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-                    if ((unsigned)(x + i) < (unsigned)G::IW) {
-                        d[i] = e0[i];
-                        d[G::PLANE + i] = e1[i];
-                        d[2 * G::PLANE + i] = e2[i];
-                    }
+                d[0] = v0.x, d[1] = v0.y, d[2] = v0.z, d[3] = v0.w;
+                d[G::PLANE] = v1.x, d[G::PLANE + 1] = v1.y, d[G::PLANE + 2] = v1.z, d[G::PLANE + 3] = v1.w;
+                d[2 * G::PLANE] = v2.x, d[2 * G::PLANE + 1] = v2.y, d[2 * G::PLANE + 2] = v2.z, d[2 * G::PLANE + 3] = v2.w;
+            }
+            cxi += DX;
+            y += 8 * DY;
+            x += 8 * DX;
+            g += gstep;
+            if (cxi >= NCX) {
+                cxi -= NCX;
+                y += 8;
+                x -= 8 * NCX;
+                g += gwrap;
             }
         }
     } else if (!tc.edge) {

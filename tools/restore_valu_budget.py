@@ -18,6 +18,7 @@ It classifies mnemonics by regular expression and prints a table; it judges noth
   * The labels are the compiler's and change with every build: --branches lists the barriers, the workgroup-uniform branches and
     the labels, from which the edge-only ranges are read off (the tile load's `else` arm, each mirror fix-up between a uniform branch
     and its target, and since the stage paths split the whole edge arm behind the uniform branch that follows Gaborish's last barrier).
+    --skip FROM.. (no TO) reaches to the end of the kernel: the plain-division blocks that the compiler places behind s_endpgm.
   * --per-pixel THREADS/PIXELS scales the per-thread counts (default 512 threads per 62 x 30 output pixels).
 """
 import argparse
@@ -92,7 +93,8 @@ def main():
             weight[j] *= n
     for s in a.skip:
         lo, hi = s.split("..")
-        for j in range(label_at[lo], label_at[hi]):
+        # (an empty TO: to the end of the kernel's text -- the out-of-line blocks placed behind s_endpgm)
+        for j in range(label_at[lo], label_at[hi] if hi else len(body)):
             weight[j] = 0.0
     if a.branches:
         for i, l in enumerate(body):
