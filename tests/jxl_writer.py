@@ -1,4 +1,4 @@
-"""A writer of bare JPEG XL codestreams that hold lossless Modular frames only: test infrastructure, numpy only.
+"""A writer of bare JPEG XL codestreams that hold Modular frames only, every sample coded losslessly: test infrastructure, numpy only.
 
 It is a second reading of the format, made from the reference's reader (the Java file and line each field is read at is cited
 beside the code that writes it) and not from jxlatte_amd/frontend: what this module writes, the front-end must read back as the
@@ -23,8 +23,18 @@ encode(image) takes one dict:
                blend=dict(mode, alpha, clamp, source), ec_blend=[dict..], duration=0, is_last=True, save_as_reference=0,
                save_before_ct=False, group_size_shift=1, predictor=5 | tree=dict(value=v, predictors=(left, right)),
                transforms=[("rct", begin_c, rct_type) | ("palette", begin_c, num_c, nb_deltas, d_pred) | ("squeeze", None | [(horizontal,
-               in_place, begin_c, num_c), ..])], patches=None | [..])]
-Float samples travel as their int32 bit patterns (exp_bits 8, bits 32)."""
+               in_place, begin_c, num_c), ..])], patches=None | [..],
+               ycbcr=False, lf_dequant=None | [3 exact halves: the dequantiser is value / 128],
+               restoration=dict(gab=False, gab_weights=None | [(w1, w2)] * 3, epf_iters=0, epf_channel_scale=None | [3],
+                                pass0, pass2, border_sad_mul (all three or none: the custom sigma block of a Modular frame),
+                                sigma_for_modular=1.0))]
+Float samples travel as their int32 bit patterns (exp_bits 8, bits 32).
+
+What is not lossless integer RGB (every default writes the bytes the writer wrote without these keys): xyb=True makes the image
+XYB-encoded; a Modular frame of such an image has no do_ycbcr bit (FrameHeader.java:88) and THREE colour planes, in a grey image too
+(LFGlobal.java:88-96), which are the stream's channels in stream order: Y, X, B - Y (Frame.java:430-455). A frame with ycbcr=True has
+three colour planes as well (LFGlobal.java:89: ecStart is 1 only without do_ycbcr), in stream order Cb, Y, Cr.
+VARIANTS names writers that are wrong on purpose (encode(im, variant=..)); the tests show that a decode tells each from the true one."""
 import numpy as np
 
 REGULAR, LF_FRAME, REFERENCE_ONLY, SKIP_PROGRESSIVE = 0, 1, 2, 3  # FrameFlags.java:4-7
@@ -32,6 +42,7 @@ REPLACE, ADD, BLEND, MULADD, MULT = 0, 1, 2, 3, 4  # FrameFlags.java:18-22
 FLAG_PATCHES = 2  # FrameFlags.java:13
 EC_ALPHA, EC_DEPTH = 0, 1  # ExtraChannelType.java:5-6
 I64 = np.int64
+VARIANTS = ("sigma_for_modular_before_sigma_block", "quant_mul_in_a_modular_frame", "do_ycbcr_bit_in_an_xyb_image")
 
 
 # ---- bits ---------------------------------------------------------------------------------------------------------------
@@ -301,7 +312,55 @@ def _blend_info(w, b, extra, full_frame):  # BlendingInfo.java:26-43
 _CROP = ((0, 8), (256, 11), (2304, 14), (18688, 30))
 
 
-def write_frame_header(w, im, fr):
+def write_restoration(w, vardct, gab, gab_weights=None, epf_iters=0, sharp_lut=None, channel_scale=None, sigma=None,
+                      sigma_for_modular=1.0, variant=None):
+    """RestorationFilter.java:46-79, for either encoding. gab_weights: three (w1, w2) pairs; sharp_lut: VarDCT only (:57); sigma: the
+    custom sigma block, (quant_mul, pass0, pass2, border_sad_mul) in a VarDCT frame and (pass0, pass2, border_sad_mul) in a Modular
+    one (:70 reads quant_mul for VarDCT only); sigma_for_modular: a Modular frame with EPF iterations always holds it, last (:74-75)"""
+    w.bool(False)  # :47 all_default
+    w.bool(gab)  # :48
+    if gab:
+        w.bool(gab_weights is not None)  # :49
+        if gab_weights is not None:
+            assert len(gab_weights) == 3
+            for w1, w2 in gab_weights:  # :51-54
+                w.f16(w1)
+                w.f16(w2)
+    w.bits(epf_iters, 2)  # :56
+    if epf_iters > 0:
+        if vardct:
+            w.bool(sharp_lut is not None)  # :57-58
+            if sharp_lut is not None:
+                for v in sharp_lut:
+                    w.f16(v)  # :61
+        else:
+            assert sharp_lut is None
+        w.bool(channel_scale is not None)  # :63
+        if channel_scale is not None:
+            assert len(channel_scale) == 3
+            for v in channel_scale:
+                w.f16(v)  # :66
+            w.bits(0, 32)  # :67
+        if not vardct and variant == "sigma_for_modular_before_sigma_block":
+            w.f16(sigma_for_modular)
+        w.bool(sigma is not None)  # :69
+        if sigma is not None:
+            assert len(sigma) == (4 if vardct else 3)
+            if not vardct and variant == "quant_mul_in_a_modular_frame":
+                w.f16(0.5)
+            for v in sigma:
+                w.f16(v)  # :70-73
+        if not vardct and variant != "sigma_for_modular_before_sigma_block":
+            w.f16(sigma_for_modular)  # :74-75
+    w.u64(0)  # :76 extensions
+
+
+def colour_planes(im, fr):
+    """the colour channels of a Modular frame's stream (LFGlobal.java:88-96)"""
+    return 1 if im.get("grey", False) and not im.get("xyb", False) and not fr.get("ycbcr", False) else 3
+
+
+def write_frame_header(w, im, fr, variant=None):
     """FrameHeader.java:83-204"""
     n_extra = len(im.get("extra", []))
     ftype = fr.get("type", REGULAR)
@@ -314,7 +373,13 @@ def write_frame_header(w, im, fr):
     w.bits(ftype, 2)  # :85
     w.bits(1, 1)  # :86 Modular
     w.u64(FLAG_PATCHES if fr.get("patches") else 0)  # :87
-    w.bool(False)  # :88 do_ycbcr (the image is not XYB)
+    if not im.get("xyb", False) or variant == "do_ycbcr_bit_in_an_xyb_image":
+        w.bool(fr.get("ycbcr", False))  # :88 do_ycbcr: in the stream of an image that is not XYB only
+    else:
+        assert not fr.get("ycbcr", False)
+    if fr.get("ycbcr", False):
+        for _ in range(3):
+            w.bits(0, 2)  # :91-110 jpeg_upsampling mode 0 per channel: no subsampling
     w.bits({1: 0, 2: 1, 4: 2, 8: 3}[up], 2)  # :114
     ec_up = fr.get("ec_upsampling", [up] * n_extra)
     for k in ec_up:
@@ -356,10 +421,12 @@ def write_frame_header(w, im, fr):
     else:
         assert not fr.get("save_before_ct", False), "the header has no place for save_before_ct here"
     w.u32(0, (0, 0), (0, 4), (16, 5), (48, 10))  # :188 no name
-    w.bool(False)  # RestorationFilter.java:47 not all_default (the default has Gaborish and two EPF iterations)
-    w.bool(False)  # :48 gab
-    w.bits(0, 2)  # :56 epf_iterations
-    w.u64(0)  # :76 extensions
+    rf = fr.get("restoration", {})  # RestorationFilter.java:47 never all_default: the default has Gaborish and two EPF iterations
+    assert not set(rf) - {"gab", "gab_weights", "epf_iters", "epf_channel_scale", "pass0", "pass2", "border_sad_mul", "sigma_for_modular"}
+    block = [rf[k] for k in ("pass0", "pass2", "border_sad_mul") if k in rf]
+    assert len(block) in (0, 3)
+    write_restoration(w, False, rf.get("gab", False), rf.get("gab_weights"), rf.get("epf_iters", 0), None, rf.get("epf_channel_scale"),
+                      block or None, rf.get("sigma_for_modular", 1.0), variant)
     w.u64(0)  # FrameHeader.java:195 extensions
 
 
@@ -777,13 +844,18 @@ def write_patches(w, patches, num_alpha):
     write_symbols(w, syms)
 
 
-def write_frame(im, fr):
+def write_frame(im, fr, variant=None):
     head = BitWriter()
-    write_frame_header(head, im, fr)
+    write_frame_header(head, im, fr, variant)
     w = BitWriter()
     if fr.get("patches"):
         write_patches(w, fr["patches"], sum(1 for e in im.get("extra", []) if e.get("type", "alpha") == "alpha"))
-    w.bool(True)  # LFGlobal.java:62 default LF dequantisation
+    lfd = fr.get("lf_dequant")
+    w.bool(lfd is None)  # LFGlobal.java:62 default LF dequantisation
+    if lfd is not None:
+        assert len(lfd) == 3
+        for v in lfd:
+            w.f16(v)  # :64 times 1 / 128
     w.bool(True)  # :82 a global tree
     leaf = write_tree(w, fr)
     w.bool(True)  # ModularStream.java:78 use the global tree
@@ -842,11 +914,13 @@ def write_frame(im, fr):
     return head.tobytes() + body  # :177 padded, then the section (a single entry is read from the same reader, :388-390)
 
 
-def encode(im):
+def encode(im, variant=None):
+    assert variant is None or variant in VARIANTS
     for fr in im["frames"]:
+        assert len(fr["planes"]) == colour_planes(im, fr) + len(im.get("extra", []))
         gd = 128 << fr.get("group_size_shift", 1)
         for p in fr["planes"]:
             assert p.shape == fr["planes"][0].shape and p.shape[0] <= gd and p.shape[1] <= gd, "every channel fits one group"
     w = BitWriter()
     write_image_header(w, im)
-    return w.tobytes() + b"".join(write_frame(im, fr) for fr in im["frames"])
+    return w.tobytes() + b"".join(write_frame(im, fr, variant) for fr in im["frames"])

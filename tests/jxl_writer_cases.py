@@ -512,6 +512,9 @@ TABLES = dict(SINGLE, upsampled=UPSAMPLED, multi=MULTI, multi_fixed=MULTI_FIXED,
 
 
 def table(name):
+    if name == "lossy":  # the frames that are not lossless integer RGB: tests/jxl_writer_lossy_cases.py (which imports this module)
+        import jxl_writer_lossy_cases as L
+        return {n: L.image(n) for n in L.NAMES}
     return TABLES[name]
 
 
@@ -553,13 +556,17 @@ ROUTE_CASES = {
     "one-colour image": ("routed", "grey_two_frames", CANVAS, ("canvas", 0)),
     "a frame with patches": ("routed", "patches_rgb", CANVAS, ("canvas", 1)),
     "more than 16 planes": ("routed", "fourteen_extra", CANVAS, ("canvas", 0)),
+    # table "lossy": not exact, held to jxl_writer_lossy_cases.model under its K (jxl_writer_lossy_run.check)
+    "a restoration filter or YCbCr": ("lossy", "xyb_13x21_gab1_epf2", IMAGE, ("image", 0)),
+    "an XYB image": ("lossy", "xyb_13x21_gab0_epf0", FRAMES, ("frame", 0)),
 }
 UNREACHABLE = {
     "not a Modular frame": "the writer makes Modular frames only; the committed VarDCT samples reach it (test_device_frames_gpu.test_every_other_sample)",
-    "a restoration filter or YCbCr": "the writer's frame header turns Gaborish and EPF off and never sets do_ycbcr (jxl_writer.write_frame_header)",
-    "an XYB image": "the writer's image header says xyb_encoded = false: a lossless integer image has no XYB form",
     "an upsampling factor other than 1, 2, 4 or 8": "the header codes the factor as 1 << two bits (FrameHeader.java:114): no bitstream holds another",
-    "a frame of another colour count": "a Modular frame of a non-XYB image has the image's colour count (Frame.java:874-877); it takes a VarDCT frame in a grey image",
+    # the frame exists -- a grey image with an XYB frame has three colour planes (lossy: grey_tagged_xyb_9x11_gab1_epf2) -- but
+    # patch_sets_rule looks at the image's count first, and a frame's count differs from the image's only where the image's is 1
+    # (test_jxl_writer_lossy_cpu.test_no_stream_reaches_a_frame_of_another_colour_count)
+    "a frame of another colour count": "only a one-colour image holds a frame of another count, and the rule answers 'one-colour image' or 'the canvas has landed' first",
 }
 # patch_sets_rule's "one-colour image" and "device_canvas is off" share their text with _canvas_route's and _frame_set_route's
 # strings above, which ARE reached; inside patch_sets_rule they are not: both callers ask only with device_canvas on, and a grey

@@ -184,36 +184,9 @@ def write_frame_header(w, src):
         W._blend_info(w, {}, True, True)  # :169 one per extra channel: REPLACE on the full frame
     w.bool(True)  # :178 is_last
     w.u32(0, (0, 0), (0, 4), (16, 5), (48, 10))  # :188 no name
-    # RestorationFilter.java:46-79
-    iters = src.get("epf_iters", 0)
-    w.bool(False)  # :47 all_default
-    w.bool(src.get("gab", True))  # :48
-    if src.get("gab", True):
-        gw = src.get("gab_weights")
-        w.bool(gw is not None)  # :49
-        if gw is not None:
-            for c in range(3):  # :51-54
-                w.f16(gw[0][c])
-                w.f16(gw[1][c])
-    w.bits(iters, 2)  # :56
-    if iters > 0:
-        lut = src.get("sharp_lut")
-        w.bool(lut is not None)  # :57-58
-        if lut is not None:
-            for v in lut:
-                w.f16(v)  # :61
-        cs = src.get("channel_scale")
-        w.bool(cs is not None)  # :63
-        if cs is not None:
-            for v in cs:
-                w.f16(v)  # :66
-            w.bits(0, 32)  # :67
-        sg = src.get("sigma")
-        w.bool(sg is not None)  # :69
-        if sg is not None:
-            for v in sg:
-                w.f16(v)  # :70-73 quant_mul, pass0, pass2, border_sad_mul
-    w.u64(0)  # :76 extensions
+    gw = src.get("gab_weights")
+    W.write_restoration(w, True, src.get("gab", True), None if gw is None else list(zip(gw[0], gw[1])), src.get("epf_iters", 0),
+                        src.get("sharp_lut"), src.get("channel_scale"), src.get("sigma"))  # RestorationFilter.java:46-79
     w.u64(0)  # FrameHeader.java:195 extensions
 
 

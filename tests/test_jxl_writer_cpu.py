@@ -21,8 +21,9 @@ Arbitration. Where the writer (or its expectation) and the front-end or decoder 
 
 A grey frame in an RGB image does not exist in the format as the reference reads it: Frame.getColorChannelCount (Frame.java:874-877)
 gives a Modular frame of an image that is not XYB-encoded the IMAGE's colour count, and LFGlobal.java:88-96 sizes the stream from the
-image header too. So patch_sets_rule's "a frame of another colour count" needs a VarDCT frame in a grey image, which this writer
-does not make (jxl_writer_cases.UNREACHABLE)."""
+image header too. A frame of another colour count is a three-colour frame (XYB, do_ycbcr or VarDCT) in a grey image; the writer makes
+one (jxl_writer_lossy_cases: grey_tagged_xyb_9x11_gab1_epf2), but patch_sets_rule never says "a frame of another colour count" of it:
+it looks at the image's colour count first (jxl_writer_cases.UNREACHABLE)."""
 import io
 import os
 import re

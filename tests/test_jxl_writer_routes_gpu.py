@@ -17,6 +17,7 @@ import torch
 
 import jxl_writer as W
 import jxl_writer_cases as C
+import jxl_writer_lossy_run as RUN
 from conftest import assert_bits_equal
 from jxlatte_amd import frontend
 from jxlatte_amd.decoder import JXLDecoder, PFMWriter, PNGWriter
@@ -158,7 +159,9 @@ def test_a_real_decode_reaches_the_refusal(backend, reason, monkeypatch):
             assert said.startswith("host: " + head) and said.endswith(tail) and len(said) > len("host: " + head + tail), said
         else:
             assert dec.stats[k][where] == "host: " + reason
-        if table != "upsampled":  # and the image is still its source's
+        if table == "lossy":  # within the bound of its expectation from the SOURCE
+            RUN.check(name, dict(planes=got.getBuffer()), "%s, refused for %r" % (name, reason), cuts=False)
+        elif table != "upsampled":  # and the image is still its source's
             check_image(im, got, C.expected_planes(im), name)
     finally:
         dec.close()
