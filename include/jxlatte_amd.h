@@ -365,10 +365,27 @@ jxl_status jxl_vardct_read_output_wait(jxl_ctx* ctx);
  * jxl_vardct_run's result as the resident planes. The run must have produced float planes (no transfer / integer output;
  * XYB stage off if the later stages need XYB samples). */
 jxl_status jxl_planes_from_frame(jxl_ctx* ctx, int32_t height, int32_t width);
+/* the same for ANY window of the result: rows [y0, y0 + height), columns [x0, x0 + width), which must lie inside it
+ * (JXL_ERR_INVALID_ARGUMENT otherwise). jxl_planes_from_frame is the (0, 0) case. A region decode runs a sub-frame of whole LF
+ * groups and adopts the region's box with this. */
+jxl_status jxl_planes_from_frame_at(jxl_ctx* ctx, int32_t y0, int32_t x0, int32_t height, int32_t width);
 /* Frame.performUpsampling (Frame.java:217-260) of the three planes, k = 2, 4, 8; weights as for jxl_stage_upsample */
 jxl_status jxl_planes_upsample(jxl_ctx* ctx, int32_t k, const float* weights);
 /* Frame.initializeNoise (Frame.java:748-788) + Frame.synthesizeNoise (:790-831) on the resident planes */
 jxl_status jxl_planes_noise(jxl_ctx* ctx, int32_t group_dim, uint64_t seed0, const float lut[8], float base_corr_x, float base_corr_b);
+/* ---- noise on a window of a frame ----
+ * The resident planes are the window [y0, y0 + rp_h) x [x0, x0 + rp_w) of a frame_h x frame_w frame (rp_h x rp_w: their size).
+ * The result is Frame.initializeNoise + synthesizeNoise of the WHOLE frame restricted to the window, bit for bit: XorShiro runs
+ * for exactly the groups that the window, grown by 2 and clipped to the frame, touches, seeded with their absolute origin and
+ * advanced through all three channels in the reference's order; the 5x5 high-pass mirrors against the frame's size. Two
+ * launches. JXL_ERR_INVALID_ARGUMENT where the window is not inside the frame, group_dim is not a power of two >= 16 or the frame
+ * has more than 2^30 pixels; JXL_ERR_STATE without resident planes. */
+jxl_status jxl_planes_noise_at(jxl_ctx* ctx, int32_t group_dim, uint64_t seed0, const float lut[8], float base_corr_x, float base_corr_b,
+                               int32_t frame_h, int32_t frame_w, int32_t y0, int32_t x0);
+/* the same on three host planes of height x width floats (X, Y, B), in place; the resident planes are left alone */
+jxl_status jxl_stage_noise_window(jxl_ctx* ctx, float* const planes[3], int32_t height, int32_t width, int32_t group_dim, uint64_t seed0,
+                                  const float lut[8], float base_corr_x, float base_corr_b, int32_t frame_h, int32_t frame_w, int32_t y0,
+                                  int32_t x0);
 /* OpsinInverseMatrix.invertXYB / the YCbCr branch of performColorTransforms on the resident planes */
 jxl_status jxl_planes_xyb(jxl_ctx* ctx, const float matrix[9], const float opsin_bias[3], const float cbrt_opsin_bias[3],
                           float intensity_target);

@@ -195,6 +195,30 @@ int32_t jxf_set_defer_transforms(jxf_dec* d, int32_t on);
  * HfGlobal fields of jxf_frame_info say nothing about the frame. A frame whose LF-group sections carry modular channels (extra channels at
  * 1:8) is refused with JXF_ERR_UNSUPPORTED. Modular frames ignore the switch. Default off: nothing behaves differently. */
 int32_t jxf_set_lf_only(jxf_dec* d, int32_t on);
+/* ---- region decoding: only the sections that a box of the frame needs ----
+ * The box is in the FRAME's coordinates and is set before jxf_next_frame; w == 0 clears it. Of a VarDCT frame with more than one
+ * TOC section jxf_next_frame then reads LfGlobal, HfGlobal with the pass headers, and only
+ *   - the pass-group sections of the groups that the box, grown by the margin M and clipped to the padded frame, touches
+ *     (padding columns and rows lie in the last real pixel's group), in every pass, and
+ *   - the LF-group sections (LF coefficients and HF metadata) of the LF groups that hold those groups.
+ * M = (gab ? 1 : 0) + {0, 2, 3, 6}[epf_iters] is how far Gaborish and the edge-preserving filter carry a sample: further than M
+ * from an unread group every pixel of a read group is the full decode's. An unselected section is neither opened nor checked
+ * against the file's length, so a file that ends inside one decodes; a missing tail is reported when the NEXT frame is asked for.
+ * jxf_get_lfgroup / jxf_get_coeffs* of an unselected LF group / group answer JXF_ERR_STATE. Modular frames, single-section
+ * frames, frames whose LF-group or pass-group sections carry modular channels, and frames that the box is not inside of, are
+ * decoded whole (applied == 0). Together with jxf_set_lf_only: JXF_ERR_STATE from jxf_next_frame. */
+int32_t jxf_set_region(jxf_dec* d, int32_t x0, int32_t y0, int32_t w, int32_t h);
+typedef struct jxf_region_plan { /* what the current frame did with the box */
+    int32_t applied;                                          /* 1: the selection above was made; 0: every section was read */
+    int32_t margin;                                           /* M */
+    int32_t group_x0, group_y0, group_w, group_h;             /* the groups read, in groups (the whole grid when not applied) */
+    int32_t lf_group_x0, lf_group_y0, lf_group_w, lf_group_h; /* the LF groups read, in LF groups */
+    int32_t groups_read, groups_total, lf_groups_read, lf_groups_total;
+    int64_t section_bytes_read, section_bytes_total;          /* TOC lengths: read (all passes) / of the frame */
+} jxf_region_plan;
+int32_t jxf_get_region_plan(const jxf_dec* d, jxf_region_plan* out);
+/* NOT part of the interface: the tests show with it that a smaller margin is wrong. m = -1: the frame's own M again */
+int32_t jxf_debug_set_region_margin(jxf_dec* d, int32_t m);
 #define JXF_TRANSFORM_RCT 0
 #define JXF_TRANSFORM_PALETTE 1
 #define JXF_TRANSFORM_SQUEEZE 2

@@ -87,6 +87,10 @@ public final class NativeBackend implements AutoCloseable {
     public native void planesUpload(ByteBuffer p0, ByteBuffer p1, ByteBuffer p2, int height, int width); // jxl_planes_upload
     public native void planesUpsample(int k, float[] weights);     // jxl_planes_upsample   (Frame.upsample)
     public native void planesNoise(int groupDim, long seed0, float[] lut, float baseCorrX, float baseCorrB); // jxl_planes_noise
+    public native void planesFromFrameAt(int y0, int x0, int height, int width); // jxl_planes_from_frame_at: any window of the result
+    // the resident planes are the window at (y0, x0) of a frameH x frameW frame: the whole frame's noise restricted to it
+    public native void planesNoiseAt(int groupDim, long seed0, float[] lut, float baseCorrX, float baseCorrB, int frameH, int frameW,
+        int y0, int x0);                                               // jxl_planes_noise_at
     /** computePatches (:212-254) on the resident colour planes, after planesUpsample and before planesSplines / planesNoise; extra[e]:
      *  the frame's extra channels as direct buffers (written in place where a position stores into them); the rest as stagePatches. */
     public native void planesPatches(ByteBuffer[] extra, int[] extraType, ByteBuffer[] ref, int[] refType, int[] pos, int[] blend,
@@ -169,6 +173,9 @@ public final class NativeBackend implements AutoCloseable {
     public native void stageNoiseInit(int h, int w, int groupDim, long seed0, int colors, ByteBuffer o0, ByteBuffer o1, ByteBuffer o2); // jxl_stage_noise_init
     public native void stageNoiseAdd(ByteBuffer p0, ByteBuffer p1, ByteBuffer p2, ByteBuffer n0, ByteBuffer n1, ByteBuffer n2, long n,
         float[] lut, float baseCorrX, float baseCorrB);            // jxl_stage_noise_add
+    // p0..p2: the window at (y0, x0) of a frameH x frameW frame, h x w floats each, in place
+    public native void stageNoiseWindow(ByteBuffer p0, ByteBuffer p1, ByteBuffer p2, int h, int w, int groupDim, long seed0, float[] lut,
+        float baseCorrX, float baseCorrB, int frameH, int frameW, int y0, int x0); // jxl_stage_noise_window
     /** rect: {h, w, canvasY, canvasX, frameY, frameX, refY, refX}. */
     public native void stageBlend(int mode, int flags, boolean isInt, ByteBuffer canvas, int ch, int cw, ByteBuffer frame, int fh, int fw,
         ByteBuffer ref, int rh, int rw, ByteBuffer frameAlpha, ByteBuffer refAlpha, int[] rect); // jxl_stage_blend

@@ -444,6 +444,11 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesFromF
     CHECK(jxl_planes_from_frame(c, h, w));
 }
 
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesFromFrameAt(JNIEnv* e, jobject self, jint y0, jint x0, jint h, jint w) {
+    jxl_ctx* c = ctx_of(e, self);
+    CHECK(jxl_planes_from_frame_at(c, y0, x0, h, w));
+}
+
 JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesUpload(JNIEnv* e, jobject self, jobject p0, jobject p1, jobject p2,
         jint h, jint w) {
     jxl_ctx* c = ctx_of(e, self);
@@ -465,6 +470,14 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesNoise
     float l[8];
     (*e)->GetFloatArrayRegion(e, lut, 0, 8, l);
     CHECK(jxl_planes_noise(c, groupDim, (uint64_t)seed0, l, bcx, bcb));
+}
+
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesNoiseAt(JNIEnv* e, jobject self, jint groupDim, jlong seed0,
+        jfloatArray lut, jfloat bcx, jfloat bcb, jint frameH, jint frameW, jint y0, jint x0) {
+    jxl_ctx* c = ctx_of(e, self);
+    float l[8];
+    GETF(lut, 8, l);
+    CHECK(jxl_planes_noise_at(c, groupDim, (uint64_t)seed0, l, bcx, bcb, frameH, frameW, y0, x0));
 }
 
 JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesXYB(JNIEnv* e, jobject self, jfloatArray matrix, jfloatArray bias,
@@ -1219,6 +1232,17 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageNoiseA
     GETF(lut, 8, l);
     NEED(p0, 4 * n); NEED(p1, 4 * n); NEED(p2, 4 * n); NEED(n0, 4 * n); NEED(n1, 4 * n); NEED(n2, 4 * n);
     CHECK(jxl_stage_noise_add(c, pl, nz, n, l, baseCorrX, baseCorrB));
+}
+
+/* p0..p2: the window at (y0, x0) of a frameH x frameW frame, h x w floats each, in place */
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageNoiseWindow(JNIEnv* e, jobject self, jobject p0, jobject p1, jobject p2,
+        jint h, jint w, jint groupDim, jlong seed0, jfloatArray lut, jfloat baseCorrX, jfloat baseCorrB, jint frameH, jint frameW, jint y0, jint x0) {
+    jxl_ctx* c = ctx_of(e, self);
+    float* pl[3] = {(float*)ADDR(p0), (float*)ADDR(p1), (float*)ADDR(p2)};
+    float l[8];
+    GETF(lut, 8, l);
+    NEED(p0, 4 * area(h, w)); NEED(p1, 4 * area(h, w)); NEED(p2, 4 * area(h, w));
+    CHECK(jxl_stage_noise_window(c, pl, h, w, groupDim, (uint64_t)seed0, l, baseCorrX, baseCorrB, frameH, frameW, y0, x0));
 }
 
 /* rect: {h, w, canvas_y, canvas_x, frame_y, frame_x, ref_y, ref_x} (JXLCodestreamDecoder.java:26-40, 285-422) */

@@ -71,7 +71,22 @@ def parser():
                     help="8: the image at 1:8 from the LF image of its VarDCT frame (JXLDecoder downsample; jxl_planes_from_lf / "
                          "jxl_stage_lf_image): no HF section is read, one launch makes the planes. A faithful thumbnail, not the "
                          "reference's pixels. An image whose frame does not qualify (JXLDecoder.preview_rule) stops with the reason")
+    ap.add_argument("--region", type=region_arg, default=None, metavar="X0,Y0,W,H",
+                    help="decode only this box of the image as delivered (JXLDecoder region): the front-end reads the groups the box "
+                         "needs and no others (jxf_set_region), and the output is the box: the full decode's pixels there, bit for "
+                         "bit. An image whose frame does not qualify (JXLDecoder.region_rule) stops with the reason")
     return ap
+
+
+def region_arg(text):
+    """--region=x0,y0,w,h -> a tuple of four integers"""
+    try:
+        box = tuple(int(v) for v in text.split(","))
+    except ValueError:
+        box = ()
+    if len(box) != 4:
+        raise argparse.ArgumentTypeError("expected x0,y0,w,h, not %r" % text)
+    return box
 
 
 def output_format(a):
@@ -101,9 +116,9 @@ def main(argv=None):
                          device_patches=a.device_patches, device_output=a.device_png, device_canvas=a.device_canvas,
                          draw_varblocks=a.draw_varblocks, device_palette=a.device_palette, device_image=a.device_image,
                          device_frames=a.device_frames, device_patch_sets=a.device_patch_sets, device_chains=a.device_chains,
-                         downsample=a.downsample)
+                         downsample=a.downsample, region=a.region)
     except ValueError as e:
-        if a.downsample == 1:
+        if a.downsample == 1 and a.region is None:
             raise
         print("jxlatte_amd: %s" % e, file=sys.stderr)
         backend.close()
@@ -111,9 +126,9 @@ def main(argv=None):
     try:
         image = dec.decode()
     except UnsupportedOperationException as e:
-        if a.downsample == 1 or not str(e).startswith("downsample=8: "):
+        if not ((a.downsample == 8 and str(e).startswith("downsample=8: ")) or (a.region is not None and str(e).startswith("region: "))):
             raise
-        print("jxlatte_amd: %s" % e, file=sys.stderr)  # the frame does not qualify: decode without --downsample
+        print("jxlatte_amd: %s" % e, file=sys.stderr)  # the frame does not qualify: decode without --downsample / --region
         backend.close()
         return 2
     if image is None:
@@ -125,7 +140,9 @@ def main(argv=None):
                                                        (", canvas %s" % st["canvas"] if a.device_canvas else "") +
                                                        (", image %s" % st["image"] if a.device_image else "") +
                                                        (", frame %s" % st["frame"] if a.device_frames else "") +
-                                                       (", preview %s" % st["preview"] if a.downsample == 8 else "")), file=sys.stderr)
+                                                       (", preview %s" % st["preview"] if a.downsample == 8 else "") +
+                                                       (", region: %d of %d groups read (%s)" % (st["region"]["groups_read"], st["region"]["groups_total"],
+                                                                                                  st["region"]["path"]) if "region" in st else "")), file=sys.stderr)
     print("Decoded %dx%d in %.3f s" % (image.getWidth(), image.getHeight(), t1 - t0), file=sys.stderr)
     if a.output and output_format(a) == "pfm":
         with open(a.output, "wb") as f:

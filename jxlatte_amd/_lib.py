@@ -93,6 +93,9 @@ SIGNATURES = {
     "jxl_planes_from_frame": (i32, [vp, i32, i32]),
     "jxl_planes_upsample": (i32, [vp, i32, pf]),
     "jxl_planes_noise": (i32, [vp, i32, C.c_uint64, pf, f32, f32]),
+    "jxl_planes_from_frame_at": (i32, [vp, i32, i32, i32, i32]),
+    "jxl_planes_noise_at": (i32, [vp, i32, C.c_uint64, pf, f32, f32, i32, i32, i32, i32]),
+    "jxl_stage_noise_window": (i32, [vp, pf3, i32, i32, i32, C.c_uint64, pf, f32, f32, i32, i32, i32, i32]),
     "jxl_planes_xyb": (i32, [vp, pf, pf, pf, f32]),
     "jxl_planes_ycbcr": (i32, [vp]),
     "jxl_planes_from_lf": (i32, [vp, C.POINTER(abi.LFImageDesc)]),

@@ -14,7 +14,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libjxlatte_amd.so")
-SOURCES = ["k_idct.hip", "k_idct_wg3.hip", "k_restore.hip", "k_restore_fused.hip", "k_restore_fused_gen.hip", "k_restore_fused_q.hip", "k_modular.hip", "k_modular_vh.hip", "k_modplanes.hip", "k_lf.hip", "k_lf_image.hip", "lf_image_host.hip", "k_post.hip", "k_sparse.hip", "k_color.hip", "k_png.hip", "k_pfm.hip", "k_tensor.hip", "tensor_host.hip", "k_tensor_resize.hip", "tensor_resize_host.hip", "k_tensor_resize_batch.hip", "tensor_batch_host.hip", "k_varblocks.hip", "k_palette.hip", "k_palette_run.hip", "k_spline.hip", "spline_host.hip", "k_patch.hip", "k_canvas.hip", "canvas_host.hip", "host.hip"]
+SOURCES = ["k_idct.hip", "k_idct_wg3.hip", "k_restore.hip", "k_restore_fused.hip", "k_restore_fused_gen.hip", "k_restore_fused_q.hip", "k_modular.hip", "k_modular_vh.hip", "k_modplanes.hip", "k_lf.hip", "k_lf_image.hip", "lf_image_host.hip", "k_post.hip", "k_noise_window.hip", "noise_window_host.hip", "k_sparse.hip", "k_color.hip", "k_png.hip", "k_pfm.hip", "k_tensor.hip", "tensor_host.hip", "k_tensor_resize.hip", "tensor_resize_host.hip", "k_tensor_resize_batch.hip", "tensor_batch_host.hip", "k_varblocks.hip", "k_palette.hip", "k_palette_run.hip", "k_spline.hip", "spline_host.hip", "k_patch.hip", "k_canvas.hip", "canvas_host.hip", "host.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-function"]

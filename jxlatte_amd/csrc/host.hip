@@ -3085,6 +3085,25 @@ jxl_status jxl_planes_from_frame(jxl_ctx* c, int32_t height, int32_t width) {
     return JXL_OK;
 }
 
+jxl_status jxl_planes_from_frame_at(jxl_ctx* c, int32_t y0, int32_t x0, int32_t height, int32_t width) {
+    jxl_status st = bind(c);
+    if (st) return st;
+    if (!c->result[0]) return fail(c, JXL_ERR_STATE, "nothing has been run");
+    if (c->result_elem != 4 || c->result_interleaved || ((c->p.stages & JXL_STAGE_OUT) && (c->p.transfer != JXL_TRANSFER_NONE || c->p.out_format != JXL_OUT_F32)))
+        return fail(c, JXL_ERR_STATE, "the frame's result is not a set of float planes");
+    if (y0 < 0 || x0 < 0 || height <= 0 || width <= 0 || (int64_t)y0 + height > c->H || (int64_t)x0 + width > c->W)
+        return fail(c, JXL_ERR_INVALID_ARGUMENT, "planes: window outside the frame");
+    const size_t at = (size_t)y0 * (size_t)c->W + (size_t)x0;  // floats into a result plane of H x W
+    for (int i = 0; i < 3; i++) {
+        if (!c->rp[i].ensure(sizeof(float) * (size_t)height * width)) return fail(c, JXL_ERR_OOM, "device allocation failed (resident planes)");
+        HIP_TRY(c, hipMemcpy2DAsync(c->rp[i].p, sizeof(float) * (size_t)width, (const float*)c->result[i] + at, sizeof(float) * (size_t)c->W,
+                                    sizeof(float) * (size_t)width, (size_t)height, hipMemcpyDeviceToDevice, c->stream));
+    }
+    c->rp_h = height;
+    c->rp_w = width;
+    return JXL_OK;
+}
+
 jxl_status jxl_planes_shape(const jxl_ctx* c, int32_t* height, int32_t* width) {
     if (!c || !height || !width) return JXL_ERR_INVALID_ARGUMENT;
     *height = c->rp_h;

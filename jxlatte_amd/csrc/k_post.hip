@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sample_ops.h"
+#include "noise_ops.h"
 #include "jxl_blend.h"
 
 namespace jxl {
@@ -165,25 +166,11 @@ __global__ __launch_bounds__(256) void k_noise_add(float* p0, float* p1, float* 
     if (threadIdx.x < 8) l[threadIdx.x] = lut.v[threadIdx.x];
     __syncthreads();
     for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float bx = p0[i], by = p1[i], bb = p2[i];
-        float inR = by + bx;
-        inR = inR < 0.0f ? 0.0f : 3.0f * inR;
-        float inG = by - bx;
-        inG = inG < 0.0f ? 0.0f : 3.0f * inG;
-        int iR, iG;
-        float fR, fG;
-        if (inR >= 7.0f) { iR = 6; fR = 1.0f; } else { iR = java_f2i(inR); fR = inR - (float)iR; }
-        if (inG >= 7.0f) { iG = 6; fG = 1.0f; } else { iG = java_f2i(inG); fG = inG - (float)iG; }
-        float sr = (l[iR + 1] - l[iR]) * fR + l[iR];
-        float sg = (l[iG + 1] - l[iG]) * fG + l[iG];
-        sr = clamp_asc(sr, 0.0f, 1.0f);
-        sg = clamp_asc(sg, 0.0f, 1.0f);
-        const float nr = sr * (0.00171875f * n0[i] + 0.21828125f * n2[i]);
-        const float ng = sg * (0.00171875f * n1[i] + 0.21828125f * n2[i]);
-        const float nrg = nr + ng;
-        p1[i] = by + nrg;
-        p0[i] = bx + (bcx * nrg + nr - ng);
-        p2[i] = bb + bcb * nrg;
+        float bx = p0[i], by = p1[i], bb = p2[i];
+        noise_add_px(l, n0[i], n1[i], n2[i], bcx, bcb, bx, by, bb);  // noise_ops.h
+        p1[i] = by;
+        p0[i] = bx;
+        p2[i] = bb;
     }
 }
 

@@ -673,7 +673,8 @@ class DeviceBackend:
         return self.host.ResidentPlanes.upload(self.ctx, planes)
 
     def vardct(self, params, weights, woffs, lfgroups, groups, keep=None, sparse=False):
-        """sparse: `groups` yields the entry lists of Frontend.coeffs_sparse, fed through jxl_vardct_put_group_sparse"""
+        """sparse: `groups` yields the entry lists of Frontend.coeffs_sparse, fed through jxl_vardct_put_group_sparse.
+        keep: (h, w), or (y, x, h, w) for a window that does not begin at the origin (jxl_planes_from_frame_at)"""
         fr = feed_frame(self.host.Frame(self.ctx, params, weights, woffs), lfgroups, groups, sparse)
         if keep is not None:  # the planes stay on the device for the stages after decodeFrame: host.ResidentPlanes
             return fr.keepPlanes(*keep)
@@ -734,6 +735,10 @@ class DeviceBackend:
 
     def noise_add(self, planes, noise, lut, bcx, bcb):
         return self.host.synthesizeNoise(self.ctx, planes, noise, lut, bcx, bcb)
+
+    def noise_window(self, planes, group_dim, seed0, lut, bcx, bcb, frame_h, frame_w, y0, x0):
+        """initializeNoise + synthesizeNoise of a frame_h x frame_w frame on `planes`, its window at (y0, x0) (host.noiseWindow)"""
+        return self.host.noiseWindow(self.ctx, planes, group_dim, seed0, lut, bcx, bcb, frame_h, frame_w, y0, x0)
 
     def blend(self, mode, canvas, frame, ref, rect, **kw):
         return self.host.blend(self.ctx, mode, canvas, frame, ref, rect, **kw)
@@ -817,6 +822,7 @@ class JXLImage:
 
     resident = None
     planeSet = None
+    region = None  # JXLDecoder(region=): the box of the whole image that this image is
 
     def setLive(self):
         """the image's planes are in a device plane set that has not been released"""
@@ -1490,10 +1496,18 @@ class FramePlanes:
         else:
             render_splines(host, splines, fr.base_corr_x, fr.base_corr_b, host[0].shape[1], host[0].shape[0])
 
-    def noise(self, fr, seed0):
+    def noise(self, fr, seed0, at=None):
         """initializeNoise + synthesizeNoise (Frame.java:748-831). initializeNoise depends on the frame counters and the size
-        only: its place before the patches in the reference is moot"""
+        only: its place before the patches in the reference is moot. at: (frame_h, frame_w, y0, x0) when the planes are that
+        window of the frame: the whole frame's noise restricted to it (ResidentPlanes.noiseAt / backend.noise_window; a backend
+        without `noise_window` is an error)"""
         lut = np.array(fr.noise, F)
+        if at is not None:
+            if self.resident:
+                return self.to_device().noiseAt(fr.group_dim, seed0, lut, fr.base_corr_x, fr.base_corr_b, *at)
+            if not hasattr(self.be, "noise_window"):
+                raise RuntimeError("noise on a region needs a backend with `noise_window`")
+            return self._put(self.be.noise_window(self._floats(), fr.group_dim, seed0, lut, fr.base_corr_x, fr.base_corr_b, *at))
         if self.resident:
             return self.to_device().noise(fr.group_dim, seed0, lut, fr.base_corr_x, fr.base_corr_b)
         h, w = self.host[0].shape
@@ -1529,12 +1543,13 @@ class JXLDecoder:
     sparse_coeffs = device_splines = device_patches = device_output = device_canvas = False
     draw_varblocks = device_palette = device_image = device_frames = device_patch_sets = device_chains = False
     downsample = 1
+    region = None
     trace = None  # test hook: see _trace
     _patch_sets = False  # device_patch_sets acts on the frame in hand (_canvas_route)
 
     def __init__(self, source, backend=None, sparse_coeffs=False, device_splines=False, device_patches=False, device_output=False,
                  device_canvas=False, draw_varblocks=False, device_palette=False, device_image=False, device_frames=False,
-                 device_patch_sets=False, device_chains=False, downsample=1):
+                 device_patch_sets=False, device_chains=False, downsample=1, region=None):
         """sparse_coeffs: hand the HF coefficients to the backend as lists of non-zero entries (jxf_get_coeffs_sparse ->
         jxl_vardct_put_group_sparse), not as dense planes; same pixels.
         device_splines: Frame.renderSplines runs in the backend (jxl_planes_splines on the resident planes, jxl_stage_splines
@@ -1624,7 +1639,35 @@ class JXLDecoder:
         UnsupportedOperationException("downsample=8: <reason>") before any HF section is read, and the caller decodes in full.
         Noise is left out (zero-mean grain). stats[k]["preview"] is "lf image (1:8)", with ", noise left out" where there was
         some. Refused together with draw_varblocks, device_canvas, device_frames or a `trace` listener. A backend without
-        `lf_image` is an error."""
+        `lf_image` is an error.
+        region: None (the image) or a box (x0, y0, w, h) in the coordinates of the image as delivered (after the orientation):
+        decode() returns a JXLImage of h x w pixels whose planes are the full decode's planes[y0:y0 + h, x0:x0 + w] bit for bit,
+        and the front-end reads only the sections the box needs (jxf_set_region): the groups that the box, mapped into the frame
+        (region_in_frame) and grown by the restoration filters' reach M, touches, and the LF groups that hold them. Those LF
+        groups, renumbered from their corner, go through backend.vardct as a frame of their own -- the groups that were not read
+        are never sent and count as zero -- and the box is cut out of its result: jxl_planes_from_frame_at where the planes stay
+        on the device, a slice otherwise. The tail runs on box-sized planes; noise, the one stage that depends on where a pixel
+        lies in the frame, through jxl_planes_noise_at / jxl_stage_noise_window. With device_output the planes are the image's
+        resident planes. region_rule lists what a frame needs; one that does not qualify raises
+        UnsupportedOperationException("region: <reason>") before backend.vardct is called. A single-section frame is read whole
+        and cropped. stats[k]["region"]: dict(box, frame_box, margin, groups_read, groups_total, lf_groups_read, lf_groups_total,
+        section_bytes_read, section_bytes_total, subframe (x, y, w, h), path: "groups" or "whole frame (single section)"). An
+        empty box or one that is not inside the image is a ValueError. Refused together with downsample=8, draw_varblocks,
+        device_canvas, device_frames, device_image or a `trace` listener."""
+        if region is not None:
+            try:
+                box = tuple(region)
+                ok = len(box) == 4 and all(int(v) == v for v in box)
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError("region must be four integers (x0, y0, w, h), not %r" % (region,))
+            region = tuple(int(v) for v in box)
+            for name, on in (("downsample=8", downsample == 8), ("draw_varblocks", draw_varblocks), ("device_canvas", device_canvas),
+                             ("device_frames", device_frames), ("device_image", device_image)):
+                if on:
+                    raise ValueError("region cannot be combined with " + name)
+        self.region = region
         if downsample not in (1, 8):
             raise ValueError("downsample must be 1 or 8, not %r" % (downsample,))
         self.downsample = int(downsample)
@@ -1657,6 +1700,8 @@ class JXLDecoder:
         except frontend.FrontendError as e:
             raise self._map(e)
         self.info = self.fe.image
+        if self.region is not None:
+            self.region_in_frame(self.info, self.region)  # (a ValueError before any frame is read)
         self.reference = [None] * 4
         self.lfBuffer = [None] * 5
         self.canvas = None
@@ -1726,8 +1771,8 @@ class JXLDecoder:
                                    p44=None if q["p44"] is None else [list(r) for r in q["p44"]]))
         return hfglobal.generate_weights(params)
 
-    def _vardct_frame(self, fr, fuse_xyb, keep=None):
-        p, weights, woffs, lfgroups, groups, hist = self._vardct_inputs(fr, fuse_xyb)
+    def _vardct_frame(self, fr, fuse_xyb, keep=None, sub=None):
+        p, weights, woffs, lfgroups, groups, hist = self._vardct_inputs(fr, fuse_xyb, sub)
         self.stats[-1]["varblocks"] = {abi.TT_NAME[t]: int(n) for t, n in enumerate(hist) if n}
         self._varblock_list = self._gather_varblocks(fr, lfgroups) if self.draw_varblocks else None
         sparse = self.sparse_coeffs
@@ -1763,14 +1808,15 @@ class JXLDecoder:
         from . import host
         return host.getUpWeights(k, packed)
 
-    def _chained_tail(self, fr, planes, save, xyb_done, keep=False, upsampled=False, adopted=False):
+    def _chained_tail(self, fr, planes, save, xyb_done, keep=False, upsampled=False, adopted=False, noise_at=None):
         """Frame.upsample .. performColorTransforms (JXLCodestreamDecoder.java:628-637), the one statement of that order, for
         every backend: upsample, the saveBeforeCT reference, patches, splines, noise, inverse XYB, YCbCr. `planes`
         (FramePlanes) runs each sample stage where the samples can be and moves the colours between host and device only
         where the next stage lives on the other side; the saveBeforeCT reference and the patches' blend calls are host stages
         (as in the reference).
         keep: colours that are on the device at the end stay there. upsampled: the planes are already past Frame.upsample
-        (_modular_frame_set). adopted: the planes are a ready-made set that the patch stage takes as it is (device_chains)."""
+        (_modular_frame_set). adopted: the planes are a ready-made set that the patch stage takes as it is (device_chains).
+        noise_at: (frame_h, frame_w, y0, x0) when the planes are that window of the frame and not the frame (region)."""
         info = self.info
         if not upsampled:
             planes.upsample(fr, self._up_weights)
@@ -1799,7 +1845,7 @@ class JXLDecoder:
         if fr.has_splines:
             planes.splines(fr, self.fe.splines(), self.device_splines)
         if fr.has_noise:
-            planes.noise(fr, (self.visibleFrames << 32) | self.invisibleFrames)
+            planes.noise(fr, (self.visibleFrames << 32) | self.invisibleFrames, at=noise_at)
         if info.xyb_encoded and not xyb_done:
             planes.invert_xyb(*self._opsin(), info.intensity_target)
         if fr.do_ycbcr:
@@ -1809,13 +1855,33 @@ class JXLDecoder:
         if planes.resident:
             self.stats[-1]["plane_moves"] = planes.moves
 
-    def _vardct_inputs(self, fr, fuse_xyb):
-        """the boundary tensors of one VarDCT frame: (jxl_vardct_params, weights, offsets, LF groups, group iterator)"""
+    @staticmethod
+    def _subframe(fr, plan):
+        """region: the LF-group rectangle of a region plan (Frontend.region_plan) as a frame of its own: dict(x, y, w, h: its
+        place in the padded frame -- the origin is a multiple of the LF-group size --, lf: [(index in the frame, lfg_y, lfg_x)
+        in the sub-frame], groups: [(index in the frame, index in the sub-frame's own group grid)] of the groups that were read)"""
+        gd = fr.group_dim
+        lfd = gd << 3
+        ox, oy = plan["lf_group_x0"] * lfd, plan["lf_group_y0"] * lfd
+        w = min(fr.padded_width, (plan["lf_group_x0"] + plan["lf_group_w"]) * lfd) - ox
+        h = min(fr.padded_height, (plan["lf_group_y0"] + plan["lf_group_h"]) * lfd) - oy
+        lf = [((plan["lf_group_y0"] + y) * fr.lf_group_cols + plan["lf_group_x0"] + x, y, x)
+              for y in range(plan["lf_group_h"]) for x in range(plan["lf_group_w"])]
+        cols = (w + gd - 1) // gd
+        groups = [(gy * fr.group_cols + gx, (gy - (plan["lf_group_y0"] << 3)) * cols + gx - (plan["lf_group_x0"] << 3))
+                  for gy in range(plan["group_y0"], plan["group_y0"] + plan["group_h"])
+                  for gx in range(plan["group_x0"], plan["group_x0"] + plan["group_w"])]
+        return dict(x=ox, y=oy, w=w, h=h, lf=lf, groups=groups)
+
+    def _vardct_inputs(self, fr, fuse_xyb, sub=None):
+        """the boundary tensors of one VarDCT frame: (jxl_vardct_params, weights, offsets, LF groups, group iterator). sub: a
+        sub-frame of whole LF groups (_subframe) in the frame's place: its size, its LF groups and the groups that were read,
+        both numbered in the sub-frame's own grids"""
         info, fe = self.info, self.fe
         p = abi.VarDCTParams()
         for c in range(3):
             p.jpeg_upsampling_y[c], p.jpeg_upsampling_x[c] = fr.jpeg_up_y[c], fr.jpeg_up_x[c]
-        p.width, p.height = fr.padded_width, fr.padded_height
+        p.width, p.height = (fr.padded_width, fr.padded_height) if sub is None else (sub["w"], sub["h"])
         stages = abi.STAGE_IDCT | abi.STAGE_GAB | abi.STAGE_EPF | (abi.STAGE_XYB if fuse_xyb else 0)
         p.stages = stages
         gs = F(F(65536.0) / F(fr.global_scale))  # HFCoefficients.java:270-275
@@ -1844,9 +1910,10 @@ class JXLDecoder:
         weights, woffs = self._weights(fr)
         adaptive = (fr.flags & (FLAG_SKIP_ADAPTIVE_LF | FLAG_USE_LF_FRAME)) == 0
         lfgroups, hist = [], np.zeros(27, np.int64)
-        for i in range(fr.num_lf_groups):
+        lf_list = [(i, i // fr.lf_group_cols, i % fr.lf_group_cols) for i in range(fr.num_lf_groups)] if sub is None else sub["lf"]
+        for i, lfg_y, lfg_x in lf_list:
             g = fe.lfgroup(i)
-            g.update(lfg_y=i // fr.lf_group_cols, lfg_x=i % fr.lf_group_cols, lf=None,
+            g.update(lfg_y=lfg_y, lfg_x=lfg_x, lf=None,
                      scaled_dequant=list(fr.scaled_dequant), x_factor_lf=fr.x_factor_lf, b_factor_lf=fr.b_factor_lf,
                      adaptive_smoothing=adaptive)
             if fr.flags & FLAG_USE_LF_FRAME:
@@ -1858,10 +1925,12 @@ class JXLDecoder:
             hist += np.bincount(sel, minlength=27)[:27]
             lfgroups.append(g)
 
+        group_list = [(g, g) for g in range(fr.num_groups)] if sub is None else sub["groups"]
+
         def groups(sparse=False):
             for pass_ in range(fr.num_passes):
-                for grp in range(fr.num_groups):
-                    yield pass_, grp, fe.coeffs_sparse(pass_, grp) if sparse else fe.coeffs(pass_, grp)
+                for grp, as_ in group_list:
+                    yield pass_, as_, fe.coeffs_sparse(pass_, grp) if sparse else fe.coeffs(pass_, grp)
         return p, weights, woffs, lfgroups, groups, hist
 
     def _modular_buffers(self, fr, buffers, colors):
@@ -2609,6 +2678,8 @@ class JXLDecoder:
             raise RuntimeError("device_image needs a backend with a device context")
         if self.device_canvas and not hasattr(be, "ctx"):
             raise RuntimeError("device_canvas needs a backend with a device context")
+        if self.region is not None and self.trace is not None:
+            raise ValueError("region cannot be combined with a trace listener")
         if self.downsample == 8:
             if self.trace is not None:
                 raise ValueError("downsample=8 cannot be combined with a trace listener")
@@ -2847,12 +2918,107 @@ class JXLDecoder:
         planes = [np.ascontiguousarray(planes[c]) for c in ((1,) if grey else range(3))]
         return JXLImage([be.orient(b, o) if o != 1 else b for b in planes], info, be)
 
+    @staticmethod
+    def region_in_frame(info, region):
+        """region: the box (x0, y0, w, h) of the image as delivered -> the box (x0, y0, w, h) of the frame's coded pixels that
+        JXLCodestreamDecoder.transposeBuffer (the orientation) turns into it. A pure function of the image header. ValueError
+        for an empty box or one that is not inside the image"""
+        x0, y0, w, h = region
+        H, W, o = info.height, info.width, info.orientation
+        dh, dw = (W, H) if o > 4 else (H, W)
+        if w <= 0 or h <= 0:
+            raise ValueError("region %r is empty" % (tuple(region),))
+        if x0 < 0 or y0 < 0 or x0 + w > dw or y0 + h > dh:
+            raise ValueError("region %r is not inside the %d x %d image" % (tuple(region), dw, dh))
+        return {1: (x0, y0, w, h), 2: (W - x0 - w, y0, w, h), 3: (W - x0 - w, H - y0 - h, w, h), 4: (x0, H - y0 - h, w, h),
+                5: (y0, x0, h, w), 6: (y0, H - x0 - w, h, w), 7: (W - y0 - h, H - x0 - w, h, w), 8: (W - y0 - h, x0, h, w)}[o]
+
+    @staticmethod
+    def region_rule(info, fr):
+        """region: None when the headers say that the image is one VarDCT frame whose stages all have a small, known reach, else
+        the first condition that fails. fr None: only what the image header settles (asked before the frame is read). Noise,
+        YCbCr and any opsin matrix qualify"""
+        if info.num_extra:
+            return "the image has extra channels"
+        if fr is None:
+            return None
+        if fr.encoding != VARDCT:
+            return "not a VarDCT frame"
+        if fr.type != REGULAR_FRAME or fr.lf_level != 0 or fr.flags & FLAG_USE_LF_FRAME:
+            return "not a regular frame of LF level 0 with LF coefficients of its own"
+        if not fr.is_last or fr.x0 != 0 or fr.y0 != 0 or fr.width * fr.upsampling != info.width or \
+                fr.height * fr.upsampling != info.height or fr.blend_mode != abi.BLEND_REPLACE:
+            return "not the image's only frame"
+        if fr.upsampling != 1:
+            return "the frame is upsampled"
+        if any(fr.jpeg_up_y[c] or fr.jpeg_up_x[c] for c in range(3)):
+            return "chroma subsampling"
+        if fr.num_patches or fr.flags & FLAG_PATCHES:
+            return "patches"
+        if fr.has_splines or fr.flags & FLAG_SPLINES:
+            return "splines"
+        return None
+
+    def _region_image(self):
+        """region: the box of the image's one VarDCT frame (region_rule) from the sections it needs: the front-end's selection,
+        the selected LF groups as a sub-frame through backend.vardct, the box cut out of its result, the tail on the box"""
+        info, be = self.info, self.backend
+        why = self.region_rule(info, None)
+        if why is not None:
+            raise UnsupportedOperationException("region: " + why)
+        fx, fy, fw, fh = frame_box = self.region_in_frame(info, self.region)
+        try:
+            self.fe.set_region(frame_box)
+        except frontend.FrontendError as e:
+            raise self._map(e)
+        fr = self._next_frame()
+        if fr is None:
+            return None
+        why = self.region_rule(info, fr)
+        if why is not None:
+            raise UnsupportedOperationException("region: " + why)
+        self._count_frame(fr)
+        plan = self.fe.region_plan()
+        sub = self._subframe(fr, plan)
+        st = self.stats[-1]
+        st["region"] = dict(box=tuple(self.region), frame_box=frame_box, margin=plan["margin"],
+                            groups_read=plan["groups_read"], groups_total=plan["groups_total"],
+                            lf_groups_read=plan["lf_groups_read"], lf_groups_total=plan["lf_groups_total"],
+                            section_bytes_read=plan["section_bytes_read"], section_bytes_total=plan["section_bytes_total"],
+                            subframe=(sub["x"], sub["y"], sub["w"], sub["h"]),
+                            path="groups" if plan["applied"] else "whole frame (single section)")
+        grey = info.colour_space == CE_GRAY  # (the canvas of a grey image takes the frame's plane 1: _blend_buffers)
+        resident = bool(getattr(be, "resident", False))
+        keep = self.device_output and resident and not grey
+        xyb_done = bool(info.xyb_encoded) and not fr.has_noise  # (the inverse XYB is fused where no stage comes before it)
+        wy, wx = fy - sub["y"], fx - sub["x"]
+        if resident:
+            rp = self._vardct_frame(fr, xyb_done, keep=(wy, wx, fh, fw), sub=sub)
+            planes = FramePlanes(be, info, [None] * 3, 3, rp=rp)
+        else:
+            full = self._vardct_frame(fr, xyb_done, sub=sub)
+            planes = FramePlanes(be, info, [np.ascontiguousarray(b[wy:wy + fh, wx:wx + fw]) for b in full], 3)
+        self._chained_tail(fr, planes, False, xyb_done, keep=keep, noise_at=(fr.height, fr.width, fy, fx))
+        o = info.orientation
+        st["output"] = "device" if keep else "host"
+        if keep:
+            if o != 1:
+                planes.rp.orient(o)
+            image = JXLImage([None] * 3, info, be, resident=planes.rp)
+        else:
+            host = [planes.host[1]] if grey else planes.host[:3]
+            image = JXLImage([be.orient(np.ascontiguousarray(b), o) if o != 1 else b for b in host], info, be)
+        image.region = tuple(self.region)
+        return image
+
     def decode(self):
         """JXLCodestreamDecoder.decode (:546-677): frames until one completes an image; None at the end of the stream"""
         colors_img = 1 if self.info.colour_space == CE_GRAY else 3
         self._check_switches()
         if self.downsample == 8:
             return self._preview_image()
+        if self.region is not None:
+            return self._region_image()
         if self.canvas is None:
             self.canvas = [None] * (colors_img + self.info.num_extra)
         last = planes = None

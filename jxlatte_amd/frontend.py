@@ -103,6 +103,13 @@ class TransformView(C.Structure):
                 ("d_pred", i32), ("n_steps", i32), ("steps", C.POINTER(SqueezeStep))]
 
 
+class RegionPlan(C.Structure):
+    _fields_ = [("applied", i32), ("margin", i32), ("group_x0", i32), ("group_y0", i32), ("group_w", i32), ("group_h", i32),
+                ("lf_group_x0", i32), ("lf_group_y0", i32), ("lf_group_w", i32), ("lf_group_h", i32),
+                ("groups_read", i32), ("groups_total", i32), ("lf_groups_read", i32), ("lf_groups_total", i32),
+                ("section_bytes_read", C.c_int64), ("section_bytes_total", C.c_int64)]
+
+
 TRANSFORM_RCT, TRANSFORM_PALETTE, TRANSFORM_SQUEEZE = 0, 1, 2
 
 
@@ -130,6 +137,9 @@ SIGNATURES = {
     "jxf_get_modular_channel": (i32, [C.c_void_p, i32, C.POINTER(Chan)]),
     "jxf_set_defer_transforms": (i32, [C.c_void_p, i32]),
     "jxf_set_lf_only": (i32, [C.c_void_p, i32]),
+    "jxf_set_region": (i32, [C.c_void_p, i32, i32, i32, i32]),
+    "jxf_get_region_plan": (i32, [C.c_void_p, C.POINTER(RegionPlan)]),
+    "jxf_debug_set_region_margin": (i32, [C.c_void_p, i32]),
     "jxf_get_transform_count": (i32, [C.c_void_p]),
     "jxf_get_transform": (i32, [C.c_void_p, i32, C.POINTER(TransformView)]),
     "jxf_transforms_pending": (i32, [C.c_void_p]),
@@ -280,6 +290,18 @@ class Frontend:
         """VarDCT frames decoded from now on stop after the LF coefficients (jxf_set_lf_only): lfgroup() then has n_blocks 0 and
         empty block maps, coeffs() raises, and the file is needed only up to the end of the frame's last LF-group section"""
         self._check(self.lib.jxf_set_lf_only(self.h, int(bool(on))))
+
+    def set_region(self, box):
+        """VarDCT frames of several sections decoded from now on read only the sections that `box` = (x0, y0, w, h), in frame
+        coordinates, needs (jxf_set_region); None clears it. lfgroup() / coeffs() of what was not read raise; region_plan() tells"""
+        x0, y0, w, h = (0, 0, 0, 0) if box is None else box
+        self._check(self.lib.jxf_set_region(self.h, int(x0), int(y0), int(w), int(h)))
+
+    def region_plan(self):
+        """what the current frame did with the box (jxf_get_region_plan), as a dict of the struct's fields"""
+        v = RegionPlan()
+        self._check(self.lib.jxf_get_region_plan(self.h, C.byref(v)))
+        return {name: int(getattr(v, name)) for name, _ in RegionPlan._fields_}
 
     def transforms(self):
         """the current frame's frame-level transform list in bitstream order: dicts of kind (TRANSFORM_*), begin_c, num_c,

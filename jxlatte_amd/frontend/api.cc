@@ -2,6 +2,7 @@
 #include <cstdio>
 #include <cstring>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -19,6 +20,7 @@ struct jxf_dec {
     bool done = false, skipped_preview = false;
     bool defer = false;  // jxf_set_defer_transforms
     bool lf_only = false;  // jxf_set_lf_only
+    RegionRequest region;  // jxf_set_region, jxf_debug_set_region_margin
     std::string error;
     // scratch for views
     std::vector<float> qv[3];
@@ -242,7 +244,8 @@ int32_t jxf_next_frame(jxf_dec* d, const jxf_hooks* hooks) {
         HookCtx hc{hooks, &d->error};
         TransformHooks th;
         bind_hooks(&th, &hc);
-        f.decode(d->br, &th, d->defer, d->lf_only);
+        if (d->lf_only && d->region.w > 0) throw std::logic_error("jxf_set_lf_only and jxf_set_region exclude each other");
+        f.decode(d->br, &th, d->defer, d->lf_only, d->region.w > 0 ? &d->region : nullptr);
         if (f.fh.is_last) d->done = true;
         return JXF_OK;
     });
@@ -284,10 +287,17 @@ int32_t jxf_get_frame_info(const jxf_dec* d, jxf_frame_info* o) {
     return JXF_OK;
 }
 
+// a frame of which only a region's sections were read (jxf_set_region) has nothing to hand out for the others
+static int32_t region_refusal(const jxf_dec* d) {
+    const_cast<jxf_dec*>(d)->error = "the section was not read: it lies outside the region (jxf_set_region)";
+    return JXF_ERR_STATE;
+}
+
 int32_t jxf_get_lfgroup(const jxf_dec* d, int32_t idx, jxf_lfgroup_view* o) {
     if (!d || !o || !d->frame) return JXF_ERR_STATE;
     const Frame& f = *d->frame;
     if (idx < 0 || idx >= (int32_t)f.lf_groups.size()) return JXF_ERR_ARGUMENT;
+    if (!f.lf_group_read(idx)) return region_refusal(d);
     const LFGroupData& g = f.lf_groups[idx];
     memset(o, 0, sizeof *o);
     o->cells_h = g.cells_h; o->cells_w = g.cells_w; o->extra_precision = g.extra_precision; o->has_lf_quant = g.has_lf_quant;
@@ -315,6 +325,7 @@ int32_t jxf_get_coeffs(const jxf_dec* d, int32_t pass, int32_t group, jxf_coeff_
     const Frame& f = *d->frame;
     if (f.lf_only_decoded) return lf_only_refusal(d);
     if (pass < 0 || pass >= (int32_t)f.coeffs.size() || group < 0 || group >= (int32_t)f.coeffs[pass].size()) return JXF_ERR_ARGUMENT;
+    if (!f.group_read(group)) return region_refusal(d);
     const GroupCoeffs& g = f.coeffs[pass][group];
     for (int c = 0; c < 3; c++) { o->q[c] = g.q[c].data(); o->h[c] = g.h[c]; o->w[c] = g.w[c]; }
     return JXF_OK;
@@ -325,6 +336,7 @@ int32_t jxf_get_coeffs_sparse(const jxf_dec* d, int32_t pass, int32_t group, jxf
     const Frame& f = *d->frame;
     if (f.lf_only_decoded) return lf_only_refusal(d);
     if (pass < 0 || pass >= (int32_t)f.coeffs.size() || group < 0 || group >= (int32_t)f.coeffs[pass].size()) return JXF_ERR_ARGUMENT;
+    if (!f.group_read(group)) return region_refusal(d);
     const GroupCoeffs& g = f.coeffs[pass][group];
     for (int c = 0; c < 3; c++) {
         o->entries[c] = g.sparse[c].data();
@@ -387,6 +399,39 @@ int32_t jxf_set_defer_transforms(jxf_dec* d, int32_t on) {
 int32_t jxf_set_lf_only(jxf_dec* d, int32_t on) {
     if (!d) return JXF_ERR_ARGUMENT;
     d->lf_only = on != 0;
+    return JXF_OK;
+}
+
+int32_t jxf_set_region(jxf_dec* d, int32_t x0, int32_t y0, int32_t w, int32_t h) {
+    if (!d) return JXF_ERR_ARGUMENT;
+    if (w == 0) {
+        d->region.x0 = d->region.y0 = d->region.w = d->region.h = 0;
+        return JXF_OK;
+    }
+    if (x0 < 0 || y0 < 0 || w < 0 || h <= 0) {
+        d->error = "jxf_set_region: an empty or negative box";
+        return JXF_ERR_ARGUMENT;
+    }
+    d->region.x0 = x0; d->region.y0 = y0; d->region.w = w; d->region.h = h;
+    return JXF_OK;
+}
+
+int32_t jxf_debug_set_region_margin(jxf_dec* d, int32_t m) {
+    if (!d || m < -1 || m > (1 << 20)) return JXF_ERR_ARGUMENT;
+    d->region.margin = m;
+    return JXF_OK;
+}
+
+int32_t jxf_get_region_plan(const jxf_dec* d, jxf_region_plan* o) {
+    if (!d || !o || !d->frame) return JXF_ERR_STATE;
+    const RegionPlan& p = d->frame->region_plan;
+    memset(o, 0, sizeof *o);
+    o->applied = p.applied; o->margin = p.margin;
+    o->group_x0 = p.gx0; o->group_y0 = p.gy0; o->group_w = p.gw; o->group_h = p.gh;
+    o->lf_group_x0 = p.lx0; o->lf_group_y0 = p.ly0; o->lf_group_w = p.lw; o->lf_group_h = p.lh;
+    o->groups_read = p.groups_read; o->groups_total = p.groups_total;
+    o->lf_groups_read = p.lf_groups_read; o->lf_groups_total = p.lf_groups_total;
+    o->section_bytes_read = p.bytes_read; o->section_bytes_total = p.bytes_total;
     return JXF_OK;
 }
 

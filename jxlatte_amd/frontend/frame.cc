@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <exception>
+#include <stdexcept>
 
 #include "../../include/jxl_transform_types.h"
 
@@ -665,9 +666,58 @@ void Frame::read_pass_group(BitReader& br, int pass, int group, const std::vecto
         copy_back(global_modular.channels[replaced_idx[j]], ms.channels[j], want[j]);
 }
 
-void Frame::decode(BitReader& br, const TransformHooks* hooks, bool defer, bool lf_only) {  // Frame.decodeFrame (:376-461), front part
+// jxf_set_region on a VarDCT frame of several sections: the box grown by the margin and clipped to the padded frame (padding
+// lies in the last real pixel's group), the groups it touches, the LF groups that hold them, and what their sections weigh
+void Frame::select_region(const RegionRequest& rq) {
+    // a box that is not inside this frame selects nothing of it: the frame is decoded whole
+    if (rq.x0 < 0 || rq.y0 < 0 || rq.w <= 0 || rq.h <= 0 || (int64_t)rq.x0 + rq.w > fh.width || (int64_t)rq.y0 + rq.h > fh.height) return;
+    RegionPlan& rp = region_plan;
+    const int m = rp.margin, gd = fh.group_dim, group_rows = num_groups / group_cols;
+    const int ex0 = std::max(0, rq.x0 - m), ey0 = std::max(0, rq.y0 - m);
+    const int ex1 = (int)std::min<int64_t>(padded_w, (int64_t)rq.x0 + rq.w + m), ey1 = (int)std::min<int64_t>(padded_h, (int64_t)rq.y0 + rq.h + m);
+    const int gx0 = std::min(ex0 / gd, group_cols - 1), gy0 = std::min(ey0 / gd, group_rows - 1);
+    const int gx1 = std::min((ex1 - 1) / gd, group_cols - 1), gy1 = std::min((ey1 - 1) / gd, group_rows - 1);
+    rp.applied = 1;
+    rp.gx0 = gx0; rp.gy0 = gy0; rp.gw = gx1 - gx0 + 1; rp.gh = gy1 - gy0 + 1;
+    rp.lx0 = gx0 >> 3; rp.ly0 = gy0 >> 3; rp.lw = (gx1 >> 3) - rp.lx0 + 1; rp.lh = (gy1 >> 3) - rp.ly0 + 1;
+    rp.groups_read = rp.gw * rp.gh;
+    rp.lf_groups_read = rp.lw * rp.lh;
+    lf_selected.assign((size_t)num_lf_groups, 0);
+    group_selected.assign((size_t)num_groups, 0);
+    auto bytes = [&](int logical) -> int64_t {
+        const uint32_t slot = toc.permutation.empty() ? (uint32_t)logical : toc.permutation[(size_t)logical];
+        if (slot >= toc.lengths.size()) throw BitstreamError("TOC permutation out of range");
+        return (int64_t)toc.lengths[slot];
+    };
+    int64_t total = bytes(0) + bytes(1 + num_lf_groups);  // LfGlobal, HfGlobal
+    for (int y = rp.ly0; y < rp.ly0 + rp.lh; y++)
+        for (int x = rp.lx0; x < rp.lx0 + rp.lw; x++) {
+            lf_selected[(size_t)y * lf_group_cols + x] = 1;
+            total += bytes(1 + y * lf_group_cols + x);
+        }
+    for (int y = gy0; y <= gy1; y++)
+        for (int x = gx0; x <= gx1; x++) {
+            const int g = y * group_cols + x;
+            group_selected[(size_t)g] = 1;
+            for (int p = 0; p < fh.passes.num_passes; p++) total += bytes(2 + num_lf_groups + p * num_groups + g);
+        }
+    rp.bytes_read = total;
+}
+
+void Frame::decode(BitReader& br, const TransformHooks* hooks, bool defer, bool lf_only, const RegionRequest* region) {  // Frame.decodeFrame (:376-461), front part
     lf_only_decoded = lf_only && fh.encoding == kVarDCT;
     const bool single = toc.lengths.size() == 1;
+    lf_selected.clear();
+    group_selected.clear();
+    region_plan = RegionPlan();
+    region_plan.margin = region && region->margin >= 0 ? region->margin : region_margin();
+    region_plan.gw = group_cols;
+    region_plan.gh = num_groups / group_cols;
+    region_plan.lw = lf_group_cols;
+    region_plan.lh = num_lf_groups / lf_group_cols;
+    region_plan.groups_read = region_plan.groups_total = num_groups;
+    region_plan.lf_groups_read = region_plan.lf_groups_total = num_lf_groups;
+    region_plan.bytes_read = region_plan.bytes_total = (int64_t)data_bytes();
     const size_t base = br.byte_pos();
     const bool timing = getenv("JXF_TIMING") != nullptr;
     auto t_prev = std::chrono::steady_clock::now();
@@ -695,6 +745,13 @@ void Frame::decode(BitReader& br, const TransformHooks* hooks, bool defer, bool 
         if (!c.decoded && c.vshift >= 3 && c.hshift >= 3) lf_replaced.push_back((int)i);
     }
     lf_groups.assign(num_lf_groups, LFGroupData());
+    if (region && region->w > 0 && fh.encoding == kVarDCT && !single) {
+        // a frame whose LF-group or pass-group sections carry modular channels is decoded whole: a channel that LfGlobal left
+        // undecoded waits for one of those sections
+        bool waiting = false;
+        for (const Channel& c : global_modular.channels) waiting |= !c.decoded;
+        if (!waiting) select_region(*region);
+    }
     // the LF-only read stops inside each LF-group section, before its modular sub-stream: a frame that carries channels there
     // (extra channels at 1:8) cannot be cut short
     if (lf_only_decoded && !lf_replaced.empty()) throw UnsupportedError("LF-only decoding of a frame with modular LF-group channels");
@@ -705,6 +762,7 @@ void Frame::decode(BitReader& br, const TransformHooks* hooks, bool defer, bool 
         std::exception_ptr err;
 #pragma omp parallel for schedule(dynamic)
         for (int g = 0; g < num_lf_groups; g++) {
+            if (!lf_group_read(g)) continue;  // jxf_set_region: the section is not opened
             try {
                 BitReader r = sec(1 + g);
                 read_lf_group(r, g, lf_replaced);
@@ -751,6 +809,7 @@ void Frame::decode(BitReader& br, const TransformHooks* hooks, bool defer, bool 
             std::exception_ptr err;
 #pragma omp parallel for schedule(dynamic)
             for (int g = 0; g < num_groups; g++) {
+                if (!group_read(g)) continue;  // jxf_set_region: the section is not opened
                 try {
                     BitReader r = sec(2 + num_lf_groups + p * num_groups + g);
                     read_pass_group(r, p, g, replaced);
@@ -773,7 +832,9 @@ void Frame::decode(BitReader& br, const TransformHooks* hooks, bool defer, bool 
     } else {
         br = BitReader(br.data(), br.size_bytes());
         // advance past the frame payload
-        const size_t end = base + data_bytes();
+        size_t end = base + data_bytes();
+        // (a region read has not looked at the unselected sections: bytes missing from them are the next frame's header's to report)
+        if (region_plan.applied) end = std::min(end, br.size_bytes());
         if (end > br.size_bytes()) throw BitstreamError("Unable to read full TOC entry");
         BitReader adv(br.data() + end, br.size_bytes() - end);
         br = adv;

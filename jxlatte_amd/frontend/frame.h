@@ -69,6 +69,20 @@ struct HFPass {
     std::shared_ptr<EntropyCode> code;
 };
 
+// jxf_set_region: a box in frame coordinates; w == 0: none. margin < 0: the frame's own (region_margin)
+struct RegionRequest {
+    int x0 = 0, y0 = 0, w = 0, h = 0;
+    int margin = -1;
+};
+// what a frame did with the request (jxf_region_plan): the rectangles are in groups / LF groups, the counts are sections' groups
+struct RegionPlan {
+    int applied = 0, margin = 0;
+    int gx0 = 0, gy0 = 0, gw = 0, gh = 0;
+    int lx0 = 0, ly0 = 0, lw = 0, lh = 0;
+    int groups_read = 0, groups_total = 0, lf_groups_read = 0, lf_groups_total = 0;
+    int64_t bytes_read = 0, bytes_total = 0;
+};
+
 // the part of a frame-level modular channel that sub-stream `idx` of group size `dim` carries, and the checked copy of the
 // decoded part back into it (frame.cc; both validate untrusted geometry and throw BitstreamError)
 Channel sub_channel(const Channel& full, int dim, int idx);
@@ -109,14 +123,26 @@ struct Frame {
     // decode every section (br positioned right after the TOC); leaves br at the end of the frame data
     // defer: the frame-level stream's inverse transforms are left undone (only checked: ModularStream::check_transforms)
     // lf_only: a VarDCT frame stops after the LF coefficients of its LF-group sections (jxf_set_lf_only); Modular frames ignore it
-    void decode(BitReader& br, const TransformHooks* hooks, bool defer = false, bool lf_only = false);
+    // region: of a VarDCT frame of several sections only the LF groups and groups that the box, grown by the restoration
+    // filters' reach, touches are read (jxf_set_region); every other frame is decoded whole and says so in region_plan
+    void decode(BitReader& br, const TransformHooks* hooks, bool defer = false, bool lf_only = false, const RegionRequest* region = nullptr);
     bool lf_only_decoded = false;  // this frame was decoded that way: no HF metadata, no HfGlobal, no coefficients
+    RegionPlan region_plan;
+    std::vector<uint8_t> lf_selected, group_selected;  // per LF group / group: its sections were read. Empty: all were
+    bool lf_group_read(int i) const { return lf_selected.empty() || lf_selected[(size_t)i]; }
+    bool group_read(int i) const { return group_selected.empty() || group_selected[(size_t)i]; }
+    // how far a pixel's value reaches across a group edge: Gaborish 1, the EPF 2, 3 or 6 for 1, 2 or 3 iterations
+    int region_margin() const {
+        static const int kEpf[4] = {0, 2, 3, 6};
+        return (fh.rf.gab ? 1 : 0) + kEpf[fh.rf.epf_iters < 0 ? 0 : fh.rf.epf_iters > 3 ? 3 : fh.rf.epf_iters];
+    }
     size_t data_bytes() const;
 
     int colour_channels() const { return (ih->xyb_encoded || fh.encoding == kVarDCT) ? 3 : ih->colour_channels(); }
 
   private:
     BitReader section(const BitReader& base, size_t base_byte, int logical_index, bool single) const;
+    void select_region(const RegionRequest& rq);
     void read_lf_global(BitReader& br);
     void read_lf_group(BitReader& br, int idx, std::vector<int>& replaced_idx);
     void read_hf_global(BitReader& br);

@@ -659,11 +659,14 @@ class Frame:
         planes | 256 for a batch launch, which every context of the batch reports"""
         return lastRestoreLaunches(self.ctx)
 
-    def keepPlanes(self, height, width):
-        """run, and keep the height x width window of the result on the device for the stages that follow decodeFrame
-        (JXLCodestreamDecoder.java:628-637): -> ResidentPlanes"""
+    def keepPlanes(self, *window):
+        """run, and keep a window of the result on the device for the stages that follow decodeFrame
+        (JXLCodestreamDecoder.java:628-637): -> ResidentPlanes. window: (height, width), the top-left window
+        (jxl_planes_from_frame), or (y0, x0, height, width), any window (jxl_planes_from_frame_at)"""
+        if len(window) not in (2, 4):
+            raise TypeError("keepPlanes takes (height, width) or (y0, x0, height, width)")
         self.run()
-        self.ctx.call("jxl_planes_from_frame", height, width)
+        self.ctx.call("jxl_planes_from_frame" if len(window) == 2 else "jxl_planes_from_frame_at", *[int(v) for v in window])
         return ResidentPlanes(self.ctx)
 
     @classmethod
@@ -756,6 +759,15 @@ class ResidentPlanes:
         assert lut.size == 8
         self.ctx.call("jxl_planes_noise", groupDim, C.c_uint64(seed0), abi.fptr(lut), C.c_float(baseCorrelationX),
                       C.c_float(baseCorrelationB))
+
+    def noiseAt(self, groupDim, seed0, lut, baseCorrelationX, baseCorrelationB, frameHeight, frameWidth, y0, x0):
+        """the planes are the window at (y0, x0) of a frameHeight x frameWidth frame: the whole frame's initializeNoise +
+        synthesizeNoise restricted to it (jxl_planes_noise_at)"""
+        self._need_live()
+        lut = np.ascontiguousarray(lut, np.float32)
+        assert lut.size == 8
+        self.ctx.call("jxl_planes_noise_at", groupDim, C.c_uint64(seed0 & 0xFFFFFFFFFFFFFFFF), abi.fptr(lut), C.c_float(baseCorrelationX),
+                      C.c_float(baseCorrelationB), int(frameHeight), int(frameWidth), int(y0), int(x0))
 
     def splines(self, splines, baseCorrelationX, baseCorrelationB):
         """Frame.renderSplines on the resident planes (jxl_planes_splines): after upsample / the patches, before noise"""
@@ -1069,6 +1081,17 @@ def initializeNoise(ctx, height, width, seed0, groupDim=256, colors=3):
     out = np.empty((colors, height, width), np.float32)
     pp = (C.POINTER(C.c_float) * 3)(*[abi.fptr(out[c]) for c in range(colors)])
     ctx.call("jxl_stage_noise_init", height, width, groupDim, C.c_uint64(seed0 & 0xFFFFFFFFFFFFFFFF), colors, pp)
+    return out
+
+
+def noiseWindow(ctx, planes, groupDim, seed0, lut, baseCorrelationX, baseCorrelationB, frameHeight, frameWidth, y0, x0):
+    """Frame.initializeNoise + synthesizeNoise of a frameHeight x frameWidth frame on `planes` ([3][h][w] float32, X, Y, B), the
+    frame's window at (y0, x0) (jxl_stage_noise_window); returns the new planes"""
+    out = np.array(planes, np.float32, order="C", copy=True)
+    lut = np.ascontiguousarray(lut, np.float32)
+    assert out.ndim == 3 and out.shape[0] == 3 and lut.size == 8
+    ctx.call("jxl_stage_noise_window", _p3(out, C.c_float), out.shape[1], out.shape[2], groupDim, C.c_uint64(seed0 & 0xFFFFFFFFFFFFFFFF),
+             abi.fptr(lut), C.c_float(baseCorrelationX), C.c_float(baseCorrelationB), int(frameHeight), int(frameWidth), int(y0), int(x0))
     return out
 
 
