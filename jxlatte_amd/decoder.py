@@ -333,15 +333,22 @@ def lf_from_lf_frame(lf_buffer, lfg_y, lfg_x, cells_h, cells_w, jpeg_up_y, jpeg_
     """LFCoefficients.java:44-57 (USE_LF_FRAME): the dequantised LF of LF group (lfg_y, lfg_x) is a copy out of the planes a
     preceding LF frame left in lfBuffer[] -- rows pY .. pY + size, columns from pX, with pY = lfg_y << 8, pX = lfg_x << 8 for
     every channel (the reference does not shift the origin of a subsampled channel; kept) -- after ImageBuffer.castToFloat
-    (integer planes: v * (1f / maxValue)). Returns three float32 planes in X, Y, B order."""
+    (integer planes: v * (1f / maxValue)). Returns three float32 planes in X, Y, B order, each exactly the size the LF group
+    entry of the device expects: the planes travel as bare pointers, and a numpy slice that runs past the stored planes comes
+    back short without a word. The reference's System.arraycopy (:53) throws there; so does this -- a consuming frame whose LF
+    groups reach beyond the LF frame's planes (a crop larger than the image, say) is an invalid bitstream."""
     py, px = lfg_y << 8, lfg_x << 8
     out = []
     for c in range(3):
         b = lf_buffer[c]
-        if b.dtype != np.float32:
-            b = (b.astype(np.float32) * (F(1) / F((1 << bits_per_sample) - 1))).astype(np.float32)
         h, w = cells_h >> jpeg_up_y[c], cells_w >> jpeg_up_x[c]
-        out.append(np.ascontiguousarray(b[py:py + h, px:px + w], np.float32))
+        win = b[py:py + h, px:px + w]
+        if win.shape != (h, w):
+            raise InvalidBitstreamException("LF frame too small: LF group (%d, %d) needs %d x %d cells at (%d, %d) of stored planes of %d x %d"
+                                            % (lfg_y, lfg_x, w, h, px, py, b.shape[1], b.shape[0]))
+        if win.dtype != np.float32:
+            win = (win.astype(np.float32) * (F(1) / F((1 << bits_per_sample) - 1))).astype(np.float32)
+        out.append(np.ascontiguousarray(win, np.float32))
     return out
 
 

@@ -19,7 +19,9 @@ encode(image) takes one dict:
   halves (XYB images), up_weights=None | {2: [15], 4: [55], 8: [210]} (any subset) -- used by jxl_writer_vardct.py,
   extra=[dict(type="alpha" | "other", bits=8, exp_bits=0, alpha_associated=False)],
   frames=[dict(planes=[2-D integer arrays, colours then extra channels, each of the frame's coded size],
-               type=0 (regular) | 2 (reference only) | 3 (skip progressive), crop=None | (x0, y0), upsampling=1, ec_upsampling=[..],
+               type=0 (regular) | 1 (LF frame, with lf_level=1..4 and planes of ceil(image / 8 ** lf_level); write_frame is its entry,
+               jxl_writer_vardct.encode_stream the stream's) | 2 (reference only) | 3 (skip progressive), crop=None | (x0, y0),
+               upsampling=1, ec_upsampling=[..],
                blend=dict(mode, alpha, clamp, source), ec_blend=[dict..], duration=0, is_last=True, save_as_reference=0,
                save_before_ct=False, group_size_shift=1, predictor=5 | tree=dict(value=v, predictors=(left, right)),
                transforms=[("rct", begin_c, rct_type) | ("palette", begin_c, num_c, nb_deltas, d_pred) | ("squeeze", None | [(horizontal,
@@ -367,7 +369,11 @@ def write_frame_header(w, im, fr, variant=None):
     up = fr.get("upsampling", 1)
     h, wd = fr["planes"][0].shape
     crop = fr.get("crop")
-    if crop is None and (h * up, wd * up) != (im["height"], im["width"]):
+    level = fr.get("lf_level", 0)  # an LF frame's: 1..4
+    assert (ftype == LF_FRAME) == (level > 0) and level <= 4
+    if level:  # FrameHeader.java:163-164: the coded size of an LF frame is ceil(image / 8 ** lf_level); it has no crop (:140)
+        assert crop is None and up == 1 and (h, wd) == (-(-im["height"] // (1 << 3 * level)), -(-im["width"] // (1 << 3 * level)))
+    elif crop is None and (h * up, wd * up) != (im["height"], im["width"]):
         crop = (0, 0)
     w.bool(False)  # :84 all_default
     w.bits(ftype, 2)  # :85
@@ -387,7 +393,10 @@ def write_frame_header(w, im, fr, variant=None):
     w.bits(fr.get("group_size_shift", 1), 2)  # :121
     if ftype != REFERENCE_ONLY:
         w.u32(1, (1, 0), (2, 0), (3, 0), (4, 3))  # PassesInfo.java:25 one pass
-    w.bool(crop is not None)  # :140
+    if level:
+        w.bits(level - 1, 2)  # :139 lf_level, of an LF frame only
+    if not level or variant == "crop_bit_in_an_lf_frame_header":
+        w.bool(crop is not None)  # :140: not in an LF frame
     x0 = y0 = 0
     if crop is not None:
         if ftype != REFERENCE_ONLY:
@@ -412,8 +421,8 @@ def write_frame_header(w, im, fr, variant=None):
     if normal:
         w.bool(is_last)  # :178
     save = fr.get("save_as_reference", 0)
-    if not is_last:
-        w.bits(save, 2)  # :179
+    if not is_last and ftype != LF_FRAME:
+        w.bits(save, 2)  # :179: not in an LF frame
     else:
         assert save == 0
     if ftype == REFERENCE_ONLY or (full and normal and (duration == 0 or save != 0) and not is_last and blend.get("mode", REPLACE) == REPLACE):

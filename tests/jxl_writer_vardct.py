@@ -5,7 +5,7 @@ at is cited beside the code that writes it; J = com/traneptora/jxlatte), not fro
 SOURCE arrays, the front-end must hand out as the same integers. Every context of the HF coefficient stream is computed here
 (predicted non-zeros, block context, non-zero context, coefficient context with `prev`), and every entropy stream has several
 clusters with different hybrid-integer configurations (jxl_writer.EntropyCoder), so a symbol read under a wrong context desynchronises
-the stream. No ANS, no LZ77, no TOC permutation.
+the stream. No ANS, no LZ77.
 
 One fact of the reference that shapes the cases: a VarDCT frame has no group_size_shift field -- FrameHeader.java:121 reads it for
 Modular frames only, so group_dim is 256 and an LF group 2048 pixels for every VarDCT frame.
@@ -31,8 +31,18 @@ encode(src, variant=None) takes the SOURCE dict:
         the image's, the frame header no crop, and ceil(image / upsampling) is the frame);
   extra=[dict(bits=8, alpha_associated=False, plane=2-D ints of the frame's size, upsampling=k)]: alpha channels, in the global
         Modular stream at the end of LfGlobal, or -- larger than a group -- as group crops in the pass groups' Modular streams;
-  noise=None | [8 ints of 10 bits]; opsin, up_weights, intensity_target as jxl_writer.write_image_header takes them.
-VARIANTS names writers that are wrong on purpose; the tests show that the front-end tells each from the true one."""
+  noise=None | [8 ints of 10 bits]; opsin, up_weights, intensity_target as jxl_writer.write_image_header takes them;
+  what makes the frame one of several (encode_stream writes one image header and a list of frames, each from write_frame here or from
+  jxl_writer.write_frame; encode is the stream of one frame):
+  lf_level=0 | 1..4: an LF frame of that level, whose coded size width x height is ceil(image / 8 ** lf_level);
+  use_lf_frame=False: the frame's LF comes from the LF frame stored before it -- as the REFERENCE reads such a frame, which is not in
+        every point as the format has it: the header holds no jpeg-upsampling modes and no upsampling fields (FrameHeader.java:91, :113),
+        an LF group neither extra_precision nor an LF stream (LFCoefficients.java:44-57), and every cell's LF index is 0 (:24);
+        lf_quant of the LF groups is then not written (only the variant that is wrong about the LF index reads it);
+  crop=None | (x0, y0): width x height at that origin of the image; is_last=True;
+  permutation=None | [entries]: the TOC's (Frame.java:153-168): logical section i lies in slot permutation[i] (:190), the lengths are
+        in slot order; perm_clusters=(map of 8, configs) is its entropy stream's.
+VARIANTS and LF_VARIANTS name writers that are wrong on purpose; the tests show that the front-end tells each from the true one."""
 import numpy as np
 
 import jxl_writer as W
@@ -41,12 +51,17 @@ from jxl_writer import BitWriter, EntropyCoder, pack_signed
 I64 = np.int64
 GROUP_DIM = 256  # FrameHeader.java:121-122
 FLAG_NOISE = 1 << 0  # FrameFlags.java:12
+FLAG_USE_LF_FRAME = 1 << 5  # FrameFlags.java:15
 FLAG_SKIP_ADAPTIVE_LF_SMOOTHING = 1 << 7  # FrameFlags.java:16
 C_MAP = (1, 0, 2)  # Frame.java:42 cMap
 
 VARIANTS = ("predicted_rounded_down", "block_ctx_channel_not_exchanged", "prev_inverted", "nonzero_ctx_without_4", "vertical_not_flipped",
             "shift_on_token", "lf_buffer_order", "block_info_rows_exchanged", "raw_stream_index_off_by_one", "noise_lut_after_lf_dequant",
             "extra_group_stream_index_off_by_one")
+# writers that are wrong about an LF frame, a frame that uses one, or a permuted TOC (the cases of jxl_writer_lfframe_cases.py)
+LF_VARIANTS = ("upsampling_bits_in_a_use_lf_frame_header", "lf_stream_in_a_use_lf_frame_group",
+               "lf_index_from_thresholds_in_a_use_lf_frame_group", "crop_bit_in_an_lf_frame_header", "toc_lengths_in_logical_order",
+               "toc_permutation_inverted")
 
 # (parameterIndex, orderID, transformMethod, pixelHeight, pixelWidth) by type: TransformType.java:10-36
 TYPES = ((0, 0, 0, 8, 8), (1, 1, 3, 8, 8), (2, 1, 1, 8, 8), (3, 1, 2, 8, 8), (4, 2, 0, 16, 16), (5, 3, 0, 32, 32), (6, 4, 0, 16, 8),
@@ -125,10 +140,11 @@ def num_passes(src):
 
 
 def image_size(src):
-    """(height, width) of the image header: the frame's own size unless the frame is upsampled"""
-    k = src.get("upsampling", 1)
+    """(height, width) of the image header: the frame's own size unless the frame is upsampled, an LF frame or a crop"""
+    k = src.get("upsampling", 1) << (3 * src.get("lf_level", 0))
     ih, iw = src.get("image_height", src["height"] * k), src.get("image_width", src["width"] * k)
-    assert -(-ih // k) == src["height"] and -(-iw // k) == src["width"]  # FrameHeader.java:161-162 on the image's size (:153)
+    # FrameHeader.java:161-164 on the image's size (:153), or on the crop's (:150-151)
+    assert src.get("crop") is not None or (-(-ih // k) == src["height"] and -(-iw // k) == src["width"])
     return ih, iw
 
 
@@ -139,18 +155,26 @@ def extras_in_groups(src):
 
 
 # ---- headers ---------------------------------------------------------------------------------------------------------------
-def write_frame_header(w, src):
-    """FrameHeader.java:83-204 for one regular VarDCT frame without a crop: the whole image, or 1 / upsampling of it"""
+def frame_flags(src):
+    return (FLAG_SKIP_ADAPTIVE_LF_SMOOTHING if src.get("skip_smoothing", False) else 0) | \
+        (FLAG_NOISE if src.get("noise") is not None else 0) | (FLAG_USE_LF_FRAME if src.get("use_lf_frame", False) else 0)
+
+
+def write_frame_header(w, src, variant=None):
+    """FrameHeader.java:83-204 for one VarDCT frame: regular -- the whole image, 1 / upsampling of it, or a crop -- or an LF frame"""
     xyb = src.get("xyb", True)
+    level, use_lf = src.get("lf_level", 0), src.get("use_lf_frame", False)
+    assert 0 <= level <= 4
     w.bool(False)  # :84 all_default
-    w.bits(0, 2)  # :85 REGULAR_FRAME
+    w.bits(W.LF_FRAME if level else W.REGULAR, 2)  # :85
     w.bits(0, 1)  # :86 VARDCT
-    w.u64((FLAG_SKIP_ADAPTIVE_LF_SMOOTHING if src.get("skip_smoothing", False) else 0) |
-          (FLAG_NOISE if src.get("noise") is not None else 0))  # :87
+    w.u64(frame_flags(src))  # :87
     sy, sx = src.get("shift_y", [0] * 3), src.get("shift_x", [0] * 3)
     if not xyb:
         w.bool(src.get("do_ycbcr", False))  # :88
-    if src.get("do_ycbcr", False):
+    if use_lf:  # :91, :113: neither the jpeg-upsampling modes nor the upsampling fields are in the stream
+        assert not any(sy) and not any(sx) and src.get("upsampling", 1) == 1 and not src.get("extra")
+    elif src.get("do_ycbcr", False):
         # :91-110 read a mode per channel, :196-203 turn it into max - mode: the mode is the channel's sampling factor
         my, mx = max(sy), max(sx)
         for c in range(3):
@@ -158,10 +182,11 @@ def write_frame_header(w, src):
     else:
         assert not any(sy) and not any(sx)
     code = {1: 0, 2: 1, 4: 2, 8: 3}
-    w.bits(code[src.get("upsampling", 1)], 2)  # :114
     extra = src.get("extra", [])
-    for e in extra:
-        w.bits(code[e.get("upsampling", 1)], 2)  # :116
+    if not use_lf or variant == "upsampling_bits_in_a_use_lf_frame_header":
+        w.bits(code[src.get("upsampling", 1)], 2)  # :114
+        for e in extra:
+            w.bits(code[e.get("upsampling", 1)], 2)  # :116
     # :121 no group_size_shift for a VarDCT frame
     if xyb:
         w.bits(src.get("xqm", 3), 3)  # :128-129
@@ -178,11 +203,35 @@ def write_frame_header(w, src):
             w.bits({1: 0, 2: 1, 4: 2, 8: 3}[d], 2)  # :35
         for p in last:
             w.u32(p, (0, 0), (1, 0), (2, 0), (0, 3))  # :38
-    w.bool(False)  # FrameHeader.java:140 no crop
-    w.u32(0, (0, 0), (1, 0), (2, 0), (3, 2))  # BlendingInfo.java:27 REPLACE on the full frame: nothing else
-    for _ in extra:
-        W._blend_info(w, {}, True, True)  # :169 one per extra channel: REPLACE on the full frame
-    w.bool(True)  # :178 is_last
+    crop = src.get("crop")
+    if level:
+        w.bits(level - 1, 2)  # FrameHeader.java:139 lf_level, of an LF frame only
+        # :140 no crop bit, :155 and :166 no blending info, :178 no is_last, :179 no save_as_reference in an LF frame; its coded size
+        # is ceil(image / 8 ** lf_level) (:163-164)
+        assert crop is None and not extra
+        if variant == "crop_bit_in_an_lf_frame_header":
+            w.bool(False)
+    else:
+        w.bool(crop is not None)  # :140
+        full = True
+        if crop is not None:
+            x0, y0 = crop
+            w.u32(int(pack_signed(x0)), *W._CROP)  # :144-147
+            w.u32(int(pack_signed(y0)), *W._CROP)
+            w.u32(src["width"] * src.get("upsampling", 1), *W._CROP)  # :150-151
+            w.u32(src["height"] * src.get("upsampling", 1), *W._CROP)
+            ih, iw = image_size(src)
+            full = x0 <= 0 and y0 <= 0 and y0 + src["height"] * src.get("upsampling", 1) >= ih and \
+                x0 + src["width"] * src.get("upsampling", 1) >= iw  # :157-159
+        W._blend_info(w, {}, len(extra) > 0, full)  # BlendingInfo.java:27 REPLACE: on the full frame nothing else
+        for _ in extra:
+            W._blend_info(w, {}, True, full)  # :169 one per extra channel
+        is_last = src.get("is_last", True)
+        w.bool(is_last)  # :178
+        if not is_last:
+            w.bits(0, 2)  # :179 save_as_reference
+            if full:
+                w.bool(False)  # :180-184 save_before_ct: a full REPLACE frame of duration 0 that is not the last
     w.u32(0, (0, 0), (0, 4), (16, 5), (48, 10))  # :188 no name
     gw = src.get("gab_weights")
     W.write_restoration(w, True, src.get("gab", True), None if gw is None else list(zip(gw[0], gw[1])), src.get("epf_iters", 0),
@@ -329,8 +378,11 @@ def place_blocks(blocks, ch, cw, taken=None):
     return out
 
 
-def lf_index(src, g, y, x):
-    """LFCoefficients.getLFIndex (LFCoefficients.java:182-202)"""
+def lf_index(src, g, y, x, variant=None):
+    """LFCoefficients.getLFIndex (LFCoefficients.java:182-202); 0 in a frame that uses an LF frame: lfIndex is allocated (:24) and the
+    constructor returns (:56) before populateLFIndex (:102)"""
+    if src.get("use_lf_frame", False) and variant != "lf_index_from_thresholds_in_a_use_lf_frame_group":
+        return 0
     thr = block_ctx_of(src)[3]
     sy, sx = src.get("shift_y", [0] * 3), src.get("shift_x", [0] * 3)
     idx = [sum(int(g["lf_quant"][i][y >> sy[i], x >> sx[i]]) > t for t in thr[i]) for i in range(3)]
@@ -341,13 +393,15 @@ def write_lf_group(w, src, mod, index, geo, variant=None):
     """LFGroup.java:25-49: LFCoefficients.java:59-62, the frame's Modular channels of this group (none), HFMetadata.java:23-35"""
     g = src["lfgroups"][index]
     ch, cw = np.asarray(g["hf_mul"]).shape
-    w.bits(g.get("extra_precision", 0), 2)  # LFCoefficients.java:59
-    q = [np.asarray(a, I64) for a in g["lf_quant"]]
-    sy, sx = src.get("shift_y", [0] * 3), src.get("shift_x", [0] * 3)
-    for c in range(3):
-        assert q[c].shape == (ch >> sy[c], cw >> sx[c])  # :37-40
-    order = (0, 1, 2) if variant == "lf_buffer_order" else C_MAP  # :39: info[cMap[i]] is channel i: the stream holds Y, X, B
-    mod.write_stream(w, [q[c] for c in order], 1 + index)  # :60
+    # LFCoefficients.java:44-57: a frame that uses an LF frame copies its LF out of lfBuffer and returns before :59-60
+    if not src.get("use_lf_frame", False) or variant == "lf_stream_in_a_use_lf_frame_group":
+        w.bits(g.get("extra_precision", 0), 2)  # LFCoefficients.java:59
+        q = [np.asarray(a, I64) for a in g["lf_quant"]]
+        sy, sx = src.get("shift_y", [0] * 3), src.get("shift_x", [0] * 3)
+        for c in range(3):
+            assert q[c].shape == (ch >> sy[c], cw >> sx[c])  # :37-40
+        order = (0, 1, 2) if variant == "lf_buffer_order" else C_MAP  # :39: info[cMap[i]] is channel i: the stream holds Y, X, B
+        mod.write_stream(w, [q[c] for c in order], 1 + index)  # :60
     # LFGroup.java:36-39: stream 1 + numLFGroups + index has no channel
     blocks = sorted(g["blocks"])  # raster order of the corners: the order placeBlock reproduces for a complete tiling
     assert place_blocks(blocks, ch, cw) == [(y, x) for y, x, _ in blocks]
@@ -495,7 +549,7 @@ def write_pass_group(w, src, mod, p, group, geo, variant=None):
         bh, bw = cells(t)
         nb = bh * bw
         oid = order_id(t)
-        li = lf_index(src, g, by, bx)  # :87
+        li = lf_index(src, g, by, bx, variant)  # :87
         for c in C_MAP:  # :89
             sgy, sgx = gry >> sy[c], grx >> sx[c]
             if gry != sgy << sy[c] or grx != sgx << sx[c]:  # :92-95
@@ -574,21 +628,28 @@ def write_pass_group(w, src, mod, p, group, geo, variant=None):
 
 
 # ---- the frame ---------------------------------------------------------------------------------------------------------------
-def encode(src, variant=None):
-    assert variant is None or variant in VARIANTS
+def write_toc_permutation(w, perm, clusters):
+    """Frame.java:155-156 and readPermutation (:195-215) with skip 0: an entropy stream of eight contexts, `end`, then the Lehmer code"""
+    coder = EntropyCoder(*clusters)
+    coder.write_header(w)  # :155
+    ctx = lambda v: min(7, ceil_log1p(v))  # noqa: E731  :196
+    code, end = lehmer(perm, 0)
+    ctxs, vals = [ctx(len(perm))], [end]  # :197
+    for i in range(end):  # :201-202
+        ctxs.append(ctx(code[i - 1] if i > 0 else 0))
+        vals.append(code[i])
+    coder.write(w, ctxs, vals)  # (prefix codes: the final state of :157 is always valid)
+
+
+def write_frame(src, variant=None):
+    """one frame from its header to its last section, a whole number of bytes (Frame.java:124 pads before the next header)"""
     geo = geometry(src)
     mod = Modular(src)
     n_pass = num_passes(src)
-    head = BitWriter()
-    ih, iw = image_size(src)
-    extra = [dict(type="alpha", bits=e.get("bits", 8), alpha_associated=e.get("alpha_associated", False)) for e in src.get("extra", [])]
     for e in src.get("extra", []):
         assert np.asarray(e["plane"]).shape == (src["height"], src["width"])
-    W.write_image_header(head, dict(width=iw, height=ih, bits=8, xyb=src.get("xyb", True), extra=extra, opsin=src.get("opsin"),
-                                    up_weights=src.get("up_weights"), intensity_target=src.get("intensity_target")))
-    write_frame_header(head, src)
-    head.bool(False)  # Frame.java:153 no permutation
-    head.pad()  # :168
+    head = BitWriter()
+    write_frame_header(head, src, variant)
     sections = []
     single = geo["num_groups"] == 1 and n_pass == 1  # :146-151
 
@@ -608,6 +669,54 @@ def encode(src, variant=None):
             write_pass_group(section(), src, mod, p, grp, geo, variant)
     bodies = [s.tobytes() for s in sections]
     assert len(bodies) == (1 if single else 2 + geo["num_lf_groups"] + geo["num_groups"] * n_pass)
-    for b in bodies:
-        head.u32(len(b), (0, 10), (1024, 14), (17408, 22), (4211712, 30))  # :173
+    perm = src.get("permutation")
+    head.bool(perm is not None)  # Frame.java:153
+    lengths = [len(b) for b in bodies]
+    if perm is not None:
+        perm = [int(v) for v in perm]
+        assert sorted(perm) == list(range(len(bodies)))
+        inverse = [perm.index(slot) for slot in range(len(perm))]
+        write_toc_permutation(head, inverse if variant == "toc_permutation_inverted" else perm, src["perm_clusters"])
+        # :190: section i is read from slot permutation[i] (a single section from slot 0: the permutation is read and not used);
+        # :169-174: the lengths are the slots', in the order the slots lie in the stream
+        bodies = [bodies[i] for i in inverse]
+        if variant != "toc_lengths_in_logical_order":
+            lengths = [len(b) for b in bodies]
+    head.pad()  # :168
+    for n in lengths:
+        head.u32(n, (0, 10), (1024, 14), (17408, 22), (4211712, 30))  # :173
     return head.tobytes() + b"".join(bodies)  # :177 padded, then the sections
+
+
+def image_of(src):
+    """the image header's dict (jxl_writer.write_image_header) of a stream whose frames are like this one"""
+    ih, iw = image_size(src)
+    extra = [dict(type="alpha", bits=e.get("bits", 8), alpha_associated=e.get("alpha_associated", False)) for e in src.get("extra", [])]
+    return dict(width=iw, height=ih, bits=8, xyb=src.get("xyb", True), extra=extra, opsin=src.get("opsin"),
+                up_weights=src.get("up_weights"), intensity_target=src.get("intensity_target"))
+
+
+def encode_stream(image, frames, variant=None):
+    """one image header (a dict as jxl_writer.write_image_header takes it), then the frames: a SOURCE dict of this module, or a frame
+    dict of jxl_writer (one with "planes"). Only the last frame is the last: every other is an LF frame, or has is_last=False.
+    A variant reaches the frames of the writer that knows it"""
+    assert variant is None or variant in VARIANTS + LF_VARIANTS + W.VARIANTS
+    head = BitWriter()
+    W.write_image_header(head, image)  # (padded: ImageHeader.java:309)
+    out = [head.tobytes()]
+    for i, fr in enumerate(frames):
+        modular = "planes" in fr
+        level = fr.get("lf_level", 0)
+        last = fr.get("is_last", True) and not level
+        assert last == (i == len(frames) - 1)
+        if modular:
+            out.append(W.write_frame(image, fr, variant if variant in W.VARIANTS + ("crop_bit_in_an_lf_frame_header",) else None))
+        else:
+            assert image_size(fr) == (image["height"], image["width"]) and fr.get("xyb", True) == image.get("xyb", False)
+            out.append(write_frame(fr, variant if variant in VARIANTS + LF_VARIANTS else None))
+    return b"".join(out)
+
+
+def encode(src, variant=None):
+    assert variant is None or variant in VARIANTS + LF_VARIANTS
+    return encode_stream(image_of(src), [src], variant)

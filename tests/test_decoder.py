@@ -332,8 +332,8 @@ def test_device_decode_matches_oracle_decode_large(device_backend, oracle_backen
 
 def test_lf_from_lf_frame_region_and_cast():
     """USE_LF_FRAME (LFCoefficients.java:44-57): an LF group's dequantised LF is a window of the planes the LF frame left
-    behind, origin (lfg << 8) for every channel, integer planes cast as ImageBuffer.castToFloat does. No sample bitstream
-    uses LF frames and no encoder exists here: this pins the host-side assembly only."""
+    behind, origin (lfg << 8) for every channel, integer planes cast as ImageBuffer.castToFloat does. This pins the host-side
+    assembly alone, subsampled windows included; whole streams with LF frames are test_jxl_writer_lfframe_cpu.py's."""
     from jxlatte_amd.decoder import lf_from_lf_frame
     rng = np.random.default_rng(2)
     planes = [rng.standard_normal((300, 520)).astype(np.float32) for _ in range(3)]

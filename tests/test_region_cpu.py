@@ -9,8 +9,9 @@
   * region_in_frame against numpy's eight transforms; the ValueErrors, the refused combinations, the CLI, the struct's layout;
   * the windowed noise validator (jxlatte_amd/csrc/noise_window_check.h) under the sanitizers.
 
-The writer has no TOC permutation and no generated or sample file carries an orientation: the first is not tested, the second
-through the image header's field (test_an_oriented_image_end_to_end)."""
+A region of a frame whose TOC is permuted is test_jxl_writer_lfframe_cpu.py's (the group sections are looked up through the
+permutation). No generated or sample file carries an orientation: that is tested through the image header's field
+(test_an_oriented_image_end_to_end)."""
 import ctypes as C_
 import functools
 import io
