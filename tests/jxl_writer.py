@@ -25,7 +25,8 @@ encode(image) takes one dict:
                blend=dict(mode, alpha, clamp, source), ec_blend=[dict..], duration=0, is_last=True, save_as_reference=0,
                save_before_ct=False, group_size_shift=1, predictor=5 | tree=dict(value=v, predictors=(left, right)),
                transforms=[("rct", begin_c, rct_type) | ("palette", begin_c, num_c, nb_deltas, d_pred) | ("squeeze", None | [(horizontal,
-               in_place, begin_c, num_c), ..])], patches=None | [..],
+               in_place, begin_c, num_c), ..])], patches=None | [..], patch_clusters=None | (map of 10, configs),
+               splines=None | dict(quant_adjust, splines=[..], clusters) as write_splines takes it, noise=None | [8 ints of 10 bits],
                ycbcr=False, lf_dequant=None | [3 exact halves: the dequantiser is value / 128],
                restoration=dict(gab=False, gab_weights=None | [(w1, w2)] * 3, epf_iters=0, epf_channel_scale=None | [3],
                                 pass0, pass2, border_sad_mul (all three or none: the custom sigma block of a Modular frame),
@@ -41,10 +42,15 @@ import numpy as np
 
 REGULAR, LF_FRAME, REFERENCE_ONLY, SKIP_PROGRESSIVE = 0, 1, 2, 3  # FrameFlags.java:4-7
 REPLACE, ADD, BLEND, MULADD, MULT = 0, 1, 2, 3, 4  # FrameFlags.java:18-22
-FLAG_PATCHES = 2  # FrameFlags.java:13
+FLAG_NOISE, FLAG_PATCHES, FLAG_SPLINES = 1, 2, 16  # FrameFlags.java:12-14
 EC_ALPHA, EC_DEPTH = 0, 1  # ExtraChannelType.java:5-6
 I64 = np.int64
 VARIANTS = ("sigma_for_modular_before_sigma_block", "quant_mul_in_a_modular_frame", "do_ycbcr_bit_in_an_xyb_image")
+# writers that are wrong about the patch dictionary, the splines or their place in LfGlobal (jxl_writer_features_cases.py); both
+# frame writers know them
+FEATURE_VARIANTS = ("spline_start_y_before_x", "spline_points_as_first_differences", "spline_count_without_the_one",
+                    "quant_adjust_before_the_start_positions", "spline_coefficients_y_x_b_sigma", "splines_before_patches",
+                    "noise_before_splines", "patch_position_differences_unsigned")
 
 
 # ---- bits ---------------------------------------------------------------------------------------------------------------
@@ -378,7 +384,8 @@ def write_frame_header(w, im, fr, variant=None):
     w.bool(False)  # :84 all_default
     w.bits(ftype, 2)  # :85
     w.bits(1, 1)  # :86 Modular
-    w.u64(FLAG_PATCHES if fr.get("patches") else 0)  # :87
+    w.u64((FLAG_PATCHES if fr.get("patches") else 0) | (FLAG_SPLINES if fr.get("splines") else 0) |
+          (FLAG_NOISE if fr.get("noise") is not None else 0))  # :87
     if not im.get("xyb", False) or variant == "do_ycbcr_bit_in_an_xyb_image":
         w.bool(fr.get("ycbcr", False))  # :88 do_ycbcr: in the stream of an image that is not XYB only
     else:
@@ -829,36 +836,114 @@ def write_tree(w, fr):
     return leaf
 
 
-def write_patches(w, patches, num_alpha):
+def write_patches(w, patches, num_alpha, clusters=None, variant=None):
     """LFGlobal.java:34-43 and Patch.readPatch (Patch.java:21-64): one stream of ten contexts on the same coder. patches:
     [dict(ref, x0, y0, width, height, positions=[(x, y)], blend=[[dict(mode, alpha, clamp)]] per position: the colours, then each
-    extra channel)]; mode is the patch blend mode 0..7"""
-    write_entropy_header(w, 10)
-    syms = [len(patches)]  # LFGlobal.java:36
+    extra channel)]; mode is the patch blend mode 0..7. clusters=(map of 10, configs): the stream on an EntropyCoder with that
+    clustering, every symbol under the context the reader names; without it the one flat cluster the writer always wrote"""
+    syms, ctxs = [len(patches)], [0]  # LFGlobal.java:36
+
+    def put(ctx, *vals):
+        syms.extend(int(v) for v in vals)
+        ctxs.extend([ctx] * len(vals))
     for p in patches:
-        syms += [p["ref"], p["x0"], p["y0"], p["width"] - 1, p["height"] - 1, len(p["positions"]) - 1]  # Patch.java:23-29
+        put(1, p["ref"])  # Patch.java:23
+        put(3, p["x0"], p["y0"])  # :24-25
+        put(2, p["width"] - 1, p["height"] - 1)  # :26-27
+        put(7, len(p["positions"]) - 1)  # :29
         px = py = 0
         for j, (x, y) in enumerate(p["positions"]):
             if j == 0:
-                syms += [x, y]  # :36-37
+                put(4, x, y)  # :36-37
+            elif variant == "patch_position_differences_unsigned":  # a difference that is not negative written as it is
+                put(6, *[d if d >= 0 else int(pack_signed(d)) for d in (x - px, y - py)])
             else:
-                syms += [int(pack_signed(x - px)), int(pack_signed(y - py))]  # :39-42
+                put(6, int(pack_signed(x - px)), int(pack_signed(y - py)))  # :39-42
             px, py = x, y
             for b in p["blend"][j]:
-                syms.append(b["mode"])  # :47
+                put(5, b["mode"])  # :47
                 if b["mode"] > 3 and num_alpha > 1:
-                    syms.append(b.get("alpha", 0))  # :52-53
+                    put(8, b.get("alpha", 0))  # :52-53
                 if b["mode"] > 2:
-                    syms.append(1 if b.get("clamp", False) else 0)  # :57-58
-    write_symbols(w, syms)
+                    put(9, 1 if b.get("clamp", False) else 0)  # :57-58
+    if clusters is None:
+        write_entropy_header(w, 10)
+        write_symbols(w, syms)
+    else:
+        assert len(clusters[0]) == 10
+        coder = EntropyCoder(*clusters)
+        coder.write_header(w)
+        coder.write(w, ctxs, syms)
+
+
+def write_splines(w, sp, variant=None):
+    """SplinesBundle.java:24-75: one stream of six contexts. sp: dict(quant_adjust, splines=[dict(control=[(x, y), ..],
+    coeff=[X[32], Y[32], B[32], sigma[32]])], clusters=(map of 6, configs))"""
+    coder = EntropyCoder(*sp["clusters"])
+    assert len(sp["clusters"][0]) == 6 and len(sp["clusters"][1]) >= 3
+    coder.write_header(w)  # :25
+    syms, ctxs = [], []
+
+    def put(ctx, *vals):
+        syms.extend(int(v) for v in vals)
+        ctxs.extend([ctx] * len(vals))
+    splines = sp["splines"]
+    put(2, len(splines) - (0 if variant == "spline_count_without_the_one" else 1))  # :26
+    if variant == "quant_adjust_before_the_start_positions":
+        put(0, pack_signed(sp["quant_adjust"]))
+    px = py = 0
+    for i, s in enumerate(splines):  # :28-36 the first start position raw, the later ones signed differences; x before y
+        x, y = s["control"][0]
+        if i == 0:
+            assert x >= 0 and y >= 0
+            pair = (x, y)
+        else:
+            pair = (pack_signed(x - px), pack_signed(y - py))
+        put(1, *(pair[::-1] if variant == "spline_start_y_before_x" else pair))
+        px, py = x, y
+    if variant != "quant_adjust_before_the_start_positions":
+        put(0, pack_signed(sp["quant_adjust"]))  # :37
+    for s in splines:
+        pts = [(int(x), int(y)) for x, y in s["control"]]
+        put(3, len(pts) - 1)  # :45
+        dx = dy = 0
+        for j in range(1, len(pts)):  # :50-63: the reader sums the symbols twice, so they are second differences
+            fx, fy = pts[j][0] - pts[j - 1][0], pts[j][1] - pts[j - 1][1]
+            if variant == "spline_points_as_first_differences":
+                put(4, pack_signed(fx), pack_signed(fy))
+            else:
+                put(4, pack_signed(fx - dx), pack_signed(fy - dy))  # :51-52 x before y
+            dx, dy = fx, fy
+        cx, cy, cb, cs = s["coeff"]
+        assert all(len(c) == 32 for c in s["coeff"])
+        for c in ((cy, cx, cb, cs) if variant == "spline_coefficients_y_x_b_sigma" else (cx, cy, cb, cs)):  # :64-71
+            put(5, *[pack_signed(v) for v in c])
+    coder.write(w, ctxs, syms)
 
 
 def write_frame(im, fr, variant=None):
     head = BitWriter()
     write_frame_header(head, im, fr, variant)
     w = BitWriter()
-    if fr.get("patches"):
-        write_patches(w, fr["patches"], sum(1 for e in im.get("extra", []) if e.get("type", "alpha") == "alpha"))
+    def patches():
+        if fr.get("patches"):  # LFGlobal.java:34-43
+            write_patches(w, fr["patches"], sum(1 for e in im.get("extra", []) if e.get("type", "alpha") == "alpha"),
+                          fr.get("patch_clusters"), variant)
+
+    def splines():
+        if fr.get("splines"):  # :46-49
+            write_splines(w, fr["splines"], variant)
+
+    def noise():
+        for v in fr.get("noise") or []:
+            w.bits(v, 10)  # :53-58
+    order = [patches, splines, noise]  # :34-61
+    if variant == "splines_before_patches":
+        order = [splines, patches, noise]
+    elif variant == "noise_before_splines":
+        order = [patches, noise, splines]
+    for field in order:
+        field()
     lfd = fr.get("lf_dequant")
     w.bool(lfd is None)  # LFGlobal.java:62 default LF dequantisation
     if lfd is not None:
@@ -924,7 +1009,7 @@ def write_frame(im, fr, variant=None):
 
 
 def encode(im, variant=None):
-    assert variant is None or variant in VARIANTS
+    assert variant is None or variant in VARIANTS + FEATURE_VARIANTS
     for fr in im["frames"]:
         assert len(fr["planes"]) == colour_planes(im, fr) + len(im.get("extra", []))
         gd = 128 << fr.get("group_size_shift", 1)

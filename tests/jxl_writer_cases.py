@@ -561,7 +561,11 @@ ROUTE_CASES = {
     "an XYB image": ("lossy", "xyb_13x21_gab0_epf0", FRAMES, ("frame", 0)),
 }
 UNREACHABLE = {
-    "not a Modular frame": "the writer makes Modular frames only; the committed VarDCT samples reach it (test_device_frames_gpu.test_every_other_sample)",
+    # (not unreachable by a generated stream any more -- jxl_writer_vardct.encode_stream mixes the two writers -- but by the images of
+    # THIS module's tables, which ROUTE_CASES draws from)
+    "not a Modular frame": "the tables here hold Modular frames only; the generated VarDCT frames of jxl_writer_features_cases reach it in a real "
+                           "decode (test_jxl_writer_features_gpu.py, the chains set), and the committed VarDCT samples do "
+                           "(test_device_frames_gpu.test_every_other_sample)",
     "an upsampling factor other than 1, 2, 4 or 8": "the header codes the factor as 1 << two bits (FrameHeader.java:114): no bitstream holds another",
     # the frame exists -- a grey image with an XYB frame has three colour planes (lossy: grey_tagged_xyb_9x11_gab1_epf2) -- but
     # patch_sets_rule looks at the image's count first, and a frame's count differs from the image's only where the image's is 1

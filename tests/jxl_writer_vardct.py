@@ -42,7 +42,14 @@ encode(src, variant=None) takes the SOURCE dict:
   crop=None | (x0, y0): width x height at that origin of the image; is_last=True;
   permutation=None | [entries]: the TOC's (Frame.java:153-168): logical section i lies in slot permutation[i] (:190), the lengths are
         in slot order; perm_clusters=(map of 8, configs) is its entropy stream's.
-VARIANTS and LF_VARIANTS name writers that are wrong on purpose; the tests show that the front-end tells each from the true one."""
+  the features of LfGlobal and the reference slots (jxl_writer_features_cases.py):
+  patches=None | [..] with patch_clusters=None | (map of 10, configs), and splines=None | dict(..): as jxl_writer.write_patches and
+        write_splines take them; they set flags 2 and 16 and lie in front of the noise values, in that order (LFGlobal.java:34-61);
+  type=REGULAR | SKIP_PROGRESSIVE | REFERENCE_ONLY (a reference-only frame has no passes field, no crop origin, no blending info and
+        no is_last bit, and is never the last: FrameHeader.java:138-178); save_as_reference=0..3 of a frame that is not the last (:179);
+        save_before_ct where :180-184 read it -- an assertion where the header has no place for the bit.
+VARIANTS, LF_VARIANTS and FEATURE_VARIANTS name writers that are wrong on purpose; the tests show that the front-end tells each from
+the true one."""
 import numpy as np
 
 import jxl_writer as W
@@ -51,6 +58,7 @@ from jxl_writer import BitWriter, EntropyCoder, pack_signed
 I64 = np.int64
 GROUP_DIM = 256  # FrameHeader.java:121-122
 FLAG_NOISE = 1 << 0  # FrameFlags.java:12
+FLAG_PATCHES, FLAG_SPLINES = W.FLAG_PATCHES, W.FLAG_SPLINES  # :13-14
 FLAG_USE_LF_FRAME = 1 << 5  # FrameFlags.java:15
 FLAG_SKIP_ADAPTIVE_LF_SMOOTHING = 1 << 7  # FrameFlags.java:16
 C_MAP = (1, 0, 2)  # Frame.java:42 cMap
@@ -62,6 +70,9 @@ VARIANTS = ("predicted_rounded_down", "block_ctx_channel_not_exchanged", "prev_i
 LF_VARIANTS = ("upsampling_bits_in_a_use_lf_frame_header", "lf_stream_in_a_use_lf_frame_group",
                "lf_index_from_thresholds_in_a_use_lf_frame_group", "crop_bit_in_an_lf_frame_header", "toc_lengths_in_logical_order",
                "toc_permutation_inverted")
+
+# writers that are wrong about the patch dictionary, the splines or their place in LfGlobal (the cases of jxl_writer_features_cases.py)
+FEATURE_VARIANTS = W.FEATURE_VARIANTS
 
 # (parameterIndex, orderID, transformMethod, pixelHeight, pixelWidth) by type: TransformType.java:10-36
 TYPES = ((0, 0, 0, 8, 8), (1, 1, 3, 8, 8), (2, 1, 1, 8, 8), (3, 1, 2, 8, 8), (4, 2, 0, 16, 16), (5, 3, 0, 32, 32), (6, 4, 0, 16, 8),
@@ -157,16 +168,18 @@ def extras_in_groups(src):
 # ---- headers ---------------------------------------------------------------------------------------------------------------
 def frame_flags(src):
     return (FLAG_SKIP_ADAPTIVE_LF_SMOOTHING if src.get("skip_smoothing", False) else 0) | \
-        (FLAG_NOISE if src.get("noise") is not None else 0) | (FLAG_USE_LF_FRAME if src.get("use_lf_frame", False) else 0)
+        (FLAG_NOISE if src.get("noise") is not None else 0) | (FLAG_USE_LF_FRAME if src.get("use_lf_frame", False) else 0) | \
+        (FLAG_PATCHES if src.get("patches") else 0) | (FLAG_SPLINES if src.get("splines") else 0)
 
 
 def write_frame_header(w, src, variant=None):
     """FrameHeader.java:83-204 for one VarDCT frame: regular -- the whole image, 1 / upsampling of it, or a crop -- or an LF frame"""
     xyb = src.get("xyb", True)
     level, use_lf = src.get("lf_level", 0), src.get("use_lf_frame", False)
-    assert 0 <= level <= 4
+    ftype = src.get("type", W.REGULAR)
+    assert 0 <= level <= 4 and ftype in (W.REGULAR, W.SKIP_PROGRESSIVE, W.REFERENCE_ONLY) and not (level and ftype != W.REGULAR)
     w.bool(False)  # :84 all_default
-    w.bits(W.LF_FRAME if level else W.REGULAR, 2)  # :85
+    w.bits(W.LF_FRAME if level else ftype, 2)  # :85
     w.bits(0, 1)  # :86 VARDCT
     w.u64(frame_flags(src))  # :87
     sy, sx = src.get("shift_y", [0] * 3), src.get("shift_x", [0] * 3)
@@ -193,7 +206,10 @@ def write_frame_header(w, src, variant=None):
         w.bits(src.get("bqm", 2), 3)
     shifts, ds, last = src.get("pass_shifts", []), src.get("downsample", []), src.get("last_pass", [])
     n = len(shifts) + 1
-    w.u32(n, (1, 0), (2, 0), (3, 0), (4, 3))  # PassesInfo.java:25
+    if ftype == W.REFERENCE_ONLY:
+        assert n == 1  # FrameHeader.java:138: a reference-only frame has the default PassesInfo and no field for it
+    else:
+        w.u32(n, (1, 0), (2, 0), (3, 0), (4, 3))  # PassesInfo.java:25
     if n != 1:
         w.u32(len(ds), (0, 0), (1, 0), (2, 0), (3, 1))  # :26
         assert len(ds) < n and len(last) == len(ds)
@@ -216,22 +232,34 @@ def write_frame_header(w, src, variant=None):
         full = True
         if crop is not None:
             x0, y0 = crop
-            w.u32(int(pack_signed(x0)), *W._CROP)  # :144-147
-            w.u32(int(pack_signed(y0)), *W._CROP)
+            if ftype != W.REFERENCE_ONLY:
+                w.u32(int(pack_signed(x0)), *W._CROP)  # :144-147
+                w.u32(int(pack_signed(y0)), *W._CROP)
+            else:
+                assert (x0, y0) == (0, 0)  # :143
             w.u32(src["width"] * src.get("upsampling", 1), *W._CROP)  # :150-151
             w.u32(src["height"] * src.get("upsampling", 1), *W._CROP)
             ih, iw = image_size(src)
             full = x0 <= 0 and y0 <= 0 and y0 + src["height"] * src.get("upsampling", 1) >= ih and \
                 x0 + src["width"] * src.get("upsampling", 1) >= iw  # :157-159
-        W._blend_info(w, {}, len(extra) > 0, full)  # BlendingInfo.java:27 REPLACE: on the full frame nothing else
-        for _ in extra:
-            W._blend_info(w, {}, True, full)  # :169 one per extra channel
-        is_last = src.get("is_last", True)
-        w.bool(is_last)  # :178
+        normal = ftype != W.REFERENCE_ONLY  # :155
+        if normal:
+            W._blend_info(w, {}, len(extra) > 0, full)  # BlendingInfo.java:27 REPLACE: on the full frame nothing else
+            for _ in extra:
+                W._blend_info(w, {}, True, full)  # :169 one per extra channel
+        is_last = src.get("is_last", True) if normal else False  # :178: a reference-only frame is not the last
+        if normal:
+            w.bool(is_last)
+        save = src.get("save_as_reference", 0)
+        assert 0 <= save <= 3
         if not is_last:
-            w.bits(0, 2)  # :179 save_as_reference
-            if full:
-                w.bool(False)  # :180-184 save_before_ct: a full REPLACE frame of duration 0 that is not the last
+            w.bits(save, 2)  # :179 save_as_reference
+        else:
+            assert save == 0, "the header has no place for save_as_reference in the last frame"
+        if not normal or (full and not is_last):
+            w.bool(src.get("save_before_ct", False))  # :180-184: reference only, or a full REPLACE frame of duration 0 that is not the last
+        else:
+            assert not src.get("save_before_ct", False), "the header has no place for save_before_ct here"
     w.u32(0, (0, 0), (0, 4), (16, 5), (48, 10))  # :188 no name
     gw = src.get("gab_weights")
     W.write_restoration(w, True, src.get("gab", True), None if gw is None else list(zip(gw[0], gw[1])), src.get("epf_iters", 0),
@@ -297,11 +325,24 @@ def block_ctx_of(src):
 
 def write_lf_global(w, src, mod, variant=None):
     """LFGlobal.java:30-98"""
+    def patches():
+        if src.get("patches"):  # :34-43; Patch.readPatch takes the image's alpha channels (:39)
+            W.write_patches(w, src["patches"], len(src.get("extra", [])), src.get("patch_clusters"), variant)
+
+    def splines():
+        if src.get("splines"):  # :46-49
+            W.write_splines(w, src["splines"], variant)
+
     def noise():
         for v in src.get("noise") or []:
             w.bits(v, 10)  # :53-58 eight values of ten bits, in front of the LF dequant fields
-    if variant != "noise_lut_after_lf_dequant":
-        noise()
+    order = [patches, splines] + ([noise] if variant != "noise_lut_after_lf_dequant" else [])  # :34-61
+    if variant == "splines_before_patches":
+        order = [splines, patches, noise]
+    elif variant == "noise_before_splines":
+        order = [patches, noise, splines]
+    for field in order:
+        field()
     lfd = src.get("lf_dequant")
     w.bool(lfd is None)  # :62
     if lfd is not None:
@@ -700,23 +741,23 @@ def encode_stream(image, frames, variant=None):
     """one image header (a dict as jxl_writer.write_image_header takes it), then the frames: a SOURCE dict of this module, or a frame
     dict of jxl_writer (one with "planes"). Only the last frame is the last: every other is an LF frame, or has is_last=False.
     A variant reaches the frames of the writer that knows it"""
-    assert variant is None or variant in VARIANTS + LF_VARIANTS + W.VARIANTS
+    assert variant is None or variant in VARIANTS + LF_VARIANTS + FEATURE_VARIANTS + W.VARIANTS
     head = BitWriter()
     W.write_image_header(head, image)  # (padded: ImageHeader.java:309)
     out = [head.tobytes()]
     for i, fr in enumerate(frames):
         modular = "planes" in fr
         level = fr.get("lf_level", 0)
-        last = fr.get("is_last", True) and not level
+        last = fr.get("is_last", True) and not level and fr.get("type", W.REGULAR) != W.REFERENCE_ONLY
         assert last == (i == len(frames) - 1)
         if modular:
-            out.append(W.write_frame(image, fr, variant if variant in W.VARIANTS + ("crop_bit_in_an_lf_frame_header",) else None))
+            out.append(W.write_frame(image, fr, variant if variant in W.VARIANTS + FEATURE_VARIANTS + ("crop_bit_in_an_lf_frame_header",) else None))
         else:
             assert image_size(fr) == (image["height"], image["width"]) and fr.get("xyb", True) == image.get("xyb", False)
-            out.append(write_frame(fr, variant if variant in VARIANTS + LF_VARIANTS else None))
+            out.append(write_frame(fr, variant if variant in VARIANTS + LF_VARIANTS + FEATURE_VARIANTS else None))
     return b"".join(out)
 
 
 def encode(src, variant=None):
-    assert variant is None or variant in VARIANTS + LF_VARIANTS
+    assert variant is None or variant in VARIANTS + LF_VARIANTS + FEATURE_VARIANTS
     return encode_stream(image_of(src), [src], variant)

@@ -61,7 +61,11 @@ def measured_row(src, stage):
 
 
 def bound(name, stage):
-    src = C.source(name)
+    return bound_of_source(C.source(name), stage)
+
+
+def bound_of_source(src, stage):
+    """the table's K of `stage` for a frame's SOURCE, whichever stream holds the frame"""
     key = measured_row(src, stage)
     if key is not None:
         return MEASURED[key]
