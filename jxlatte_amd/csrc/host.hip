@@ -3214,6 +3214,19 @@ jxl_status ctx_planes_get(jxl_ctx* c, int* h, int* w, float* p[3]) {
     for (int i = 0; i < 3; i++) p[i] = c->rp[i].as<float>();
     return JXL_OK;
 }
+jxl_status ctx_home_resident(jxl_ctx* c, const void* alpha, ImageHome* m) {
+    int h = 0, w = 0;
+    float* rp[3];
+    jxl_status st = ctx_planes_get(c, &h, &w, rp);
+    if (st) return st;
+    const void* planes[3] = {rp[0], rp[1], rp[2]};
+    *m = home_resident(h, w, planes, alpha);
+    return JXL_OK;
+}
+ImageHome ctx_home_set(jxl_ctx* c, int32_t id, int32_t n_color, int32_t alpha_plane, bool has_alpha) {
+    CanvasView v;
+    return home_set(canvas_view(c->canvas, id, &v) ? &v : nullptr, n_color, alpha_plane, has_alpha);
+}
 jxl_status ctx_planes_set(jxl_ctx* c, int h, int w, float* p[3]) {
     for (int i = 0; i < 3; i++) {
         if (!c->rp[i].ensure(sizeof(float) * (size_t)h * w)) return fail(c, JXL_ERR_OOM, "device allocation failed (resident planes)");
@@ -3834,6 +3847,52 @@ float color_peak_value(uint32_t key) {
     memcpy(&f, &b, 4);
     return f;
 }
+
+// ---- an image's home (image_home.h) at the exits of this file: the PNG's samples, the PFM's, the colour peak ----
+// the words of the PNG and PFM entries (`what`: "png samples", "pfm samples") for a home's refusal
+jxl_status samples_home_fail(jxl_ctx* c, const char* what, HomeRefusal r, const ImageHome& m) {
+    if (r == HOME_UNKNOWN_SET) return fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+    if (r == HOME_NO_SUCH_PLANES) return fail(c, JXL_ERR_INVALID_ARGUMENT, "%s: the set has no such planes", what);
+    if (m.kind == HOME_RESIDENT) return fail(c, JXL_ERR_INVALID_ARGUMENT, "%s: the resident planes are three %d x %d float planes", what, m.h, m.w);
+    return fail(c, JXL_ERR_INVALID_ARGUMENT, "%s: the parameters do not describe the set's %d x %d planes", what, m.h, m.w);
+}
+
+// the colour peak of an image wherever it is (host planes: m.h x m.w is the caller's to set): the home's first half, color_args,
+// its second half, the planes the kernel reads to the device, the launch, the key back and decoded
+jxl_status color_peak_from_home(jxl_ctx* c, const ImageHome& m, const jxl_color_params* p, float* peak) {
+    if (m.planes == HOME_UNKNOWN_SET) return fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
+    if (m.planes) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color peak: the set has no such planes");
+    ColorArgs a;
+    jxl_status st = color_args(c, p, m.in(), &a);
+    if (st) return st;
+    if (!peak || m.h < 1 || m.w < 1 || m.w > (1 << 30)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color peak: bad arguments");
+    if (home_describes(m, m.h, m.w, p->n_planes, p->in_is_int, 0))  // (the resident entry has one text for all it refuses here)
+        return m.kind == HOME_RESIDENT ? fail(c, JXL_ERR_INVALID_ARGUMENT, "color peak: bad arguments")
+                                       : fail(c, JXL_ERR_INVALID_ARGUMENT, "color peak: the parameters do not describe the set's planes");
+    const size_t n = (size_t)m.h * m.w;
+    const int pc = p->n_planes == 3 ? 1 : 0;  // determinePeak's plane (JXLImage.java:217)
+    Tmp t;
+    for (int i = 0; i < p->n_planes; i++) {
+        if (!home_uploads(m).color) {
+            a.in[i] = m.color[i];
+        } else if (a.use_matrix || i == pc) {  // without a matrix only that plane is read
+            if (!(a.in[i] = t.up((const int32_t*)m.color[i], n))) return fail(c, JXL_ERR_OOM, "device allocation failed");
+        }
+    }
+    uint32_t* dkey = t.up<uint32_t>(nullptr, 1);
+    if (!dkey) return fail(c, JXL_ERR_OOM, "device allocation failed");
+    HIP_TRY(c, hipMemsetAsync(dkey, 0, 4, c->stream));
+    a.n = (int64_t)n;
+    launch_color_peak(a, m.h, m.w, dkey, c->stream);
+    if ((st = finish(c))) return st;
+    uint32_t key = 0;
+    HIP_TRY(c, hipMemcpy(&key, dkey, 4, hipMemcpyDeviceToHost));
+    if (a.in_is_int && a.tf_in == JXL_TF_LINEAR && !a.use_matrix)
+        *peak = (float)(int32_t)(key ^ 0x80000000u) / (float)p->in_max[pc];  // :219
+    else
+        *peak = color_peak_value(key);
+    return JXL_OK;
+}
 }  // namespace
 
 jxl_status jxl_stage_color_convert(jxl_ctx* c, const void* const in[3], int64_t n, const jxl_color_params* p, void* const out[3]) {
@@ -3867,29 +3926,9 @@ jxl_status jxl_stage_color_convert(jxl_ctx* c, const void* const in[3], int64_t 
 jxl_status jxl_stage_color_peak(jxl_ctx* c, const void* const in[3], int32_t h, int32_t w, const jxl_color_params* p, float* peak) {
     jxl_status st = bind(c);
     if (st) return st;
-    ColorArgs a;
-    if ((st = color_args(c, p, in, &a))) return st;
-    if (!peak || h < 1 || w < 1 || w > (1 << 30)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color peak: bad arguments");
-    const size_t n = (size_t)h * w;
-    const int pc = p->n_planes == 3 ? 1 : 0;  // determinePeak's plane (JXLImage.java:217)
-    Tmp t;
-    for (int i = 0; i < p->n_planes; i++) {
-        if (!a.use_matrix && i != pc) continue;  // without a matrix only that plane is read
-        if (!(a.in[i] = t.up((const int32_t*)in[i], n))) return fail(c, JXL_ERR_OOM, "device allocation failed");
-    }
-    uint32_t* dkey = t.up<uint32_t>(nullptr, 1);
-    if (!dkey) return fail(c, JXL_ERR_OOM, "device allocation failed");
-    HIP_TRY(c, hipMemsetAsync(dkey, 0, 4, c->stream));
-    a.n = (int64_t)n;
-    launch_color_peak(a, h, w, dkey, c->stream);
-    if ((st = finish(c))) return st;
-    uint32_t key = 0;
-    HIP_TRY(c, hipMemcpy(&key, dkey, 4, hipMemcpyDeviceToHost));
-    if (a.in_is_int && a.tf_in == JXL_TF_LINEAR && !a.use_matrix)
-        *peak = (float)(int32_t)(key ^ 0x80000000u) / (float)p->in_max[pc];  // :219
-    else
-        *peak = color_peak_value(key);
-    return JXL_OK;
+    ImageHome m = home_host(in, nullptr);
+    m.h = h, m.w = w;
+    return color_peak_from_home(c, m, p, peak);
 }
 
 // tools/color_bench.py: the two colour kernels alone on resident planes, by stream events: mean milliseconds per launch over
@@ -4292,6 +4331,27 @@ jxl_status png_run(jxl_ctx* c, PngArgs& a, int n_color, bool has_alpha, const vo
     HIP_TRY(c, hipMemcpy(out, a.out, ob + guard, hipMemcpyDeviceToHost));
     return JXL_OK;
 }
+
+// the PNG's samples of an image wherever it is: the home's first half, png_args, its second half, the colour planes that are
+// not on the device yet, png_run
+jxl_status png_from_home(jxl_ctx* c, const ImageHome& m, const jxl_png_params* p, void* out, size_t guard = 0) {
+    if (m.planes == HOME_UNKNOWN_SET) return samples_home_fail(c, "png samples", m.planes, m);
+    if (!p) return fail(c, JXL_ERR_INVALID_ARGUMENT, "png samples: null argument");
+    if (m.planes) return samples_home_fail(c, "png samples", m.planes, m);
+    PngArgs a;
+    int n_color = 0;
+    jxl_status st = png_args(c, p, m.in(), m.alpha, out, &a, &n_color);
+    if (st) return st;
+    const HomeRefusal r = home_describes(m, p->height, p->width, p->color.n_planes, p->color.in_is_int, p->alpha_is_int);
+    if (r) return samples_home_fail(c, "png samples", r, m);
+    const HomeUploads up = home_uploads(m);
+    Tmp t;
+    for (int i = 0; i < p->color.n_planes; i++)
+        if (!(a.c.in[i] = up.color ? t.up((const uint32_t*)m.color[i], (size_t)a.c.n) : m.color[i]))
+            return fail(c, JXL_ERR_OOM, "device allocation failed");
+    if (!up.alpha) a.alpha = m.alpha;  // a set's alpha plane, whenever one is named
+    return png_run(c, a, n_color, p->has_alpha != 0, m.alpha, t, out, guard);
+}
 }  // namespace
 namespace jxl {
 jxl_status ctx_png_args(jxl_ctx* c, const jxl_png_params* p, const void* const in[3], const void* alpha, const void* out, PngArgs* a,
@@ -4304,64 +4364,29 @@ extern "C" {
 jxl_status jxl_stage_png_samples(jxl_ctx* c, const void* const in[3], const void* alpha, const jxl_png_params* p, void* out) {
     jxl_status st = bind(c);
     if (st) return st;
-    PngArgs a;
-    int n_color = 0;
-    if ((st = png_args(c, p, in, alpha, out, &a, &n_color))) return st;
-    Tmp t;
-    for (int i = 0; i < p->color.n_planes; i++)
-        if (!(a.c.in[i] = t.up((const uint32_t*)in[i], (size_t)a.c.n))) return fail(c, JXL_ERR_OOM, "device allocation failed");
-    return png_run(c, a, n_color, p->has_alpha != 0, alpha, t, out);
+    return png_from_home(c, home_host(in, alpha), p, out);
 }
 
 // tests: jxl_stage_png_samples into a device buffer that is `guard` bytes longer; out receives the samples AND those bytes
 jxl_status jxl_debug_png_samples_guard(jxl_ctx* c, const void* const in[3], const void* alpha, const jxl_png_params* p, void* out, int32_t guard) {
     jxl_status st = bind(c);
     if (st) return st;
-    PngArgs a;
-    int n_color = 0;
     if (guard < 0) return fail(c, JXL_ERR_INVALID_ARGUMENT, "png samples: bad guard size");
-    if ((st = png_args(c, p, in, alpha, out, &a, &n_color))) return st;
-    Tmp t;
-    for (int i = 0; i < p->color.n_planes; i++)
-        if (!(a.c.in[i] = t.up((const uint32_t*)in[i], (size_t)a.c.n))) return fail(c, JXL_ERR_OOM, "device allocation failed");
-    return png_run(c, a, n_color, p->has_alpha != 0, alpha, t, out, (size_t)guard);
+    return png_from_home(c, home_host(in, alpha), p, out, (size_t)guard);
 }
 
 jxl_status jxl_planes_png_samples(jxl_ctx* c, const void* alpha, const jxl_png_params* p, void* out) {
+    ImageHome m;
     jxl_status st = bind(c);
-    if (st) return st;
-    if (c->rp_h <= 0) return fail(c, JXL_ERR_STATE, "no resident planes");
-    const void* in[3] = {c->rp[0].p, c->rp[1].p, c->rp[2].p};
-    PngArgs a;
-    int n_color = 0;
-    if ((st = png_args(c, p, in, alpha, out, &a, &n_color))) return st;
-    if (p->color.n_planes != 3 || p->color.in_is_int || p->height != c->rp_h || p->width != c->rp_w)
-        return fail(c, JXL_ERR_INVALID_ARGUMENT, "png samples: the resident planes are three %d x %d float planes", c->rp_h, c->rp_w);
-    for (int i = 0; i < 3; i++) a.c.in[i] = in[i];
-    Tmp t;
-    return png_run(c, a, n_color, p->has_alpha != 0, alpha, t, out);
+    if (st || (st = ctx_home_resident(c, alpha, &m))) return st;
+    return png_from_home(c, m, p, out);
 }
 
 jxl_status jxl_planes_color_peak(jxl_ctx* c, const jxl_color_params* p, float* peak) {
+    ImageHome m;
     jxl_status st = bind(c);
-    if (st) return st;
-    if (c->rp_h <= 0) return fail(c, JXL_ERR_STATE, "no resident planes");
-    const void* in[3] = {c->rp[0].p, c->rp[1].p, c->rp[2].p};
-    ColorArgs a;
-    if ((st = color_args(c, p, in, &a))) return st;
-    if (!peak || p->n_planes != 3 || p->in_is_int || c->rp_w > (1 << 30)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color peak: bad arguments");
-    for (int i = 0; i < 3; i++) a.in[i] = in[i];
-    Tmp t;
-    uint32_t* dkey = t.up<uint32_t>(nullptr, 1);
-    if (!dkey) return fail(c, JXL_ERR_OOM, "device allocation failed");
-    HIP_TRY(c, hipMemsetAsync(dkey, 0, 4, c->stream));
-    a.n = (int64_t)c->rp_h * c->rp_w;
-    launch_color_peak(a, c->rp_h, c->rp_w, dkey, c->stream);
-    if ((st = finish(c))) return st;
-    uint32_t key = 0;
-    HIP_TRY(c, hipMemcpy(&key, dkey, 4, hipMemcpyDeviceToHost));
-    *peak = color_peak_value(key);
-    return JXL_OK;
+    if (st || (st = ctx_home_resident(c, nullptr, &m))) return st;
+    return color_peak_from_home(c, m, p, peak);
 }
 
 jxl_status jxl_planes_orient(jxl_ctx* c, int32_t orientation) {
@@ -4409,34 +4434,39 @@ jxl_status pfm_run(jxl_ctx* c, PfmArgs& a, Tmp& t, void* out) {
     HIP_TRY(c, hipMemcpy(out, a.out, ob, hipMemcpyDeviceToHost));
     return JXL_OK;
 }
+
+// the PFM's samples of an image wherever it is: that a set is there, pfm_args, the home's second half (the PFM asks a set for no
+// plane by index: a set with fewer planes than the parameters count is one they do not describe), host planes to the device,
+// pfm_run
+jxl_status pfm_from_home(jxl_ctx* c, const ImageHome& m, const jxl_pfm_params* p, void* out) {
+    if (m.planes == HOME_UNKNOWN_SET) return samples_home_fail(c, "pfm samples", m.planes, m);
+    PfmArgs a;
+    jxl_status st = pfm_args(c, p, out, &a);
+    if (st) return st;
+    if (home_describes(m, p->height, p->width, p->n_planes, p->is_int, 0)) return samples_home_fail(c, "pfm samples", HOME_NOT_DESCRIBED, m);
+    if (!m.in()) return fail(c, JXL_ERR_INVALID_ARGUMENT, "pfm samples: null argument");
+    for (int i = 0; i < a.n_planes; i++)
+        if (!m.color[i]) return fail(c, JXL_ERR_INVALID_ARGUMENT, "pfm samples: null plane %d", i);
+    Tmp t;
+    for (int i = 0; i < a.n_planes; i++)
+        if (!(a.in[i] = home_uploads(m).color ? t.up((const uint32_t*)m.color[i], (size_t)a.h * a.w) : m.color[i]))
+            return fail(c, JXL_ERR_OOM, "device allocation failed");
+    return pfm_run(c, a, t, out);
+}
 }  // namespace
 extern "C" {
 
 jxl_status jxl_stage_pfm_samples(jxl_ctx* c, const void* const in[3], const jxl_pfm_params* p, void* out) {
     jxl_status st = bind(c);
     if (st) return st;
-    PfmArgs a;
-    if ((st = pfm_args(c, p, out, &a))) return st;
-    if (!in) return fail(c, JXL_ERR_INVALID_ARGUMENT, "pfm samples: null argument");
-    for (int i = 0; i < a.n_planes; i++)
-        if (!in[i]) return fail(c, JXL_ERR_INVALID_ARGUMENT, "pfm samples: null plane %d", i);
-    Tmp t;
-    for (int i = 0; i < a.n_planes; i++)
-        if (!(a.in[i] = t.up((const uint32_t*)in[i], (size_t)a.h * a.w))) return fail(c, JXL_ERR_OOM, "device allocation failed");
-    return pfm_run(c, a, t, out);
+    return pfm_from_home(c, home_host(in, nullptr), p, out);
 }
 
 jxl_status jxl_planes_pfm_samples(jxl_ctx* c, const jxl_pfm_params* p, void* out) {
+    ImageHome m;
     jxl_status st = bind(c);
-    if (st) return st;
-    if (c->rp_h <= 0) return fail(c, JXL_ERR_STATE, "no resident planes");
-    PfmArgs a;
-    if ((st = pfm_args(c, p, out, &a))) return st;
-    if (p->n_planes != 3 || a.is_int[0] || a.is_int[1] || a.is_int[2] || p->height != c->rp_h || p->width != c->rp_w)
-        return fail(c, JXL_ERR_INVALID_ARGUMENT, "pfm samples: the resident planes are three %d x %d float planes", c->rp_h, c->rp_w);
-    for (int i = 0; i < 3; i++) a.in[i] = c->rp[i].p;
-    Tmp t;
-    return pfm_run(c, a, t, out);
+    if (st || (st = ctx_home_resident(c, nullptr, &m))) return st;
+    return pfm_from_home(c, m, p, out);
 }
 
 // ---- the varblock map drawn onto the picture (k_varblocks.hip): Frame.drawVarblocks, Frame.java:464-503 ----
@@ -5258,74 +5288,19 @@ extern "C" {
 jxl_status jxl_canvas_png_samples(jxl_ctx* c, int32_t id, int32_t alpha_plane, const jxl_png_params* p, void* out) {
     jxl_status st = bind(c);
     if (st) return st;
-    CanvasView v;
-    if (!canvas_view(c->canvas, id, &v)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
-    if (!p) return fail(c, JXL_ERR_INVALID_ARGUMENT, "png samples: null argument");
-    const int nc = p->color.n_planes;
-    if ((nc != 1 && nc != 3) || nc > v.n || alpha_plane < -1 || alpha_plane >= v.n || (p->has_alpha != 0) != (alpha_plane >= 0))
-        return fail(c, JXL_ERR_INVALID_ARGUMENT, "png samples: the set has no such planes");
-    const void* in[3] = {nullptr, nullptr, nullptr};
-    for (int i = 0; i < nc; i++) in[i] = v.plane[i];
-    const void* alpha = alpha_plane >= 0 ? v.plane[alpha_plane] : nullptr;
-    PngArgs a;
-    int n_color = 0;
-    if ((st = png_args(c, p, in, alpha, out, &a, &n_color))) return st;
-    bool tags = p->height == v.h && p->width == v.w;
-    for (int i = 0; i < nc; i++) tags = tags && (p->color.in_is_int != 0) == (v.type[i] == JXL_PLANE_INT32);
-    if (alpha_plane >= 0) tags = tags && (p->alpha_is_int != 0) == (v.type[alpha_plane] == JXL_PLANE_INT32);
-    if (!tags) return fail(c, JXL_ERR_INVALID_ARGUMENT, "png samples: the parameters do not describe the set's %d x %d planes", v.h, v.w);
-    for (int i = 0; i < nc; i++) a.c.in[i] = in[i];
-    a.alpha = alpha;
-    Tmp t;
-    return png_run(c, a, n_color, alpha_plane >= 0, nullptr, t, out);
+    return png_from_home(c, ctx_home_set(c, id, p ? p->color.n_planes : 0, alpha_plane, p && p->has_alpha), p, out);
 }
 
 jxl_status jxl_canvas_color_peak(jxl_ctx* c, int32_t id, const jxl_color_params* p, float* peak) {
     jxl_status st = bind(c);
     if (st) return st;
-    CanvasView v;
-    if (!canvas_view(c->canvas, id, &v)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
-    if (!p || (p->n_planes != 1 && p->n_planes != 3) || p->n_planes > v.n)
-        return fail(c, JXL_ERR_INVALID_ARGUMENT, "color peak: the set has no such planes");
-    const void* in[3] = {nullptr, nullptr, nullptr};
-    for (int i = 0; i < p->n_planes; i++) in[i] = v.plane[i];
-    ColorArgs a;
-    if ((st = color_args(c, p, in, &a))) return st;
-    if (!peak || v.w > (1 << 30)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color peak: bad arguments");
-    for (int i = 0; i < p->n_planes; i++)
-        if ((p->in_is_int != 0) != (v.type[i] == JXL_PLANE_INT32))
-            return fail(c, JXL_ERR_INVALID_ARGUMENT, "color peak: the parameters do not describe the set's planes");
-    const int pc = p->n_planes == 3 ? 1 : 0;  // determinePeak's plane (JXLImage.java:217)
-    for (int i = 0; i < p->n_planes; i++) a.in[i] = in[i];
-    Tmp t;
-    uint32_t* dkey = t.up<uint32_t>(nullptr, 1);
-    if (!dkey) return fail(c, JXL_ERR_OOM, "device allocation failed");
-    HIP_TRY(c, hipMemsetAsync(dkey, 0, 4, c->stream));
-    a.n = (int64_t)v.h * v.w;
-    launch_color_peak(a, v.h, v.w, dkey, c->stream);
-    if ((st = finish(c))) return st;
-    uint32_t key = 0;
-    HIP_TRY(c, hipMemcpy(&key, dkey, 4, hipMemcpyDeviceToHost));
-    if (a.in_is_int && a.tf_in == JXL_TF_LINEAR && !a.use_matrix)
-        *peak = (float)(int32_t)(key ^ 0x80000000u) / (float)p->in_max[pc];  // :219
-    else
-        *peak = color_peak_value(key);
-    return JXL_OK;
+    return color_peak_from_home(c, ctx_home_set(c, id, p ? p->n_planes : 0, -1, false), p, peak);  // (a null p: planes no set has)
 }
 
 jxl_status jxl_canvas_pfm_samples(jxl_ctx* c, int32_t id, const jxl_pfm_params* p, void* out) {
     jxl_status st = bind(c);
     if (st) return st;
-    CanvasView v;
-    if (!canvas_view(c->canvas, id, &v)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
-    PfmArgs a;
-    if ((st = pfm_args(c, p, out, &a))) return st;
-    bool tags = p->n_planes <= v.n && p->height == v.h && p->width == v.w;
-    for (int i = 0; i < p->n_planes && tags; i++) tags = (a.is_int[i] != 0) == (v.type[i] == JXL_PLANE_INT32);
-    if (!tags) return fail(c, JXL_ERR_INVALID_ARGUMENT, "pfm samples: the parameters do not describe the set's %d x %d planes", v.h, v.w);
-    for (int i = 0; i < p->n_planes; i++) a.in[i] = v.plane[i];
-    Tmp t;
-    return pfm_run(c, a, t, out);
+    return pfm_from_home(c, ctx_home_set(c, id, p ? p->n_planes : 0, -1, false), p, out);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 #include "blend_ops.h"
 #include "patch_compile.h"
 #include "modchain_check.h"
+#include "image_home.h"
 
 namespace jxl {
 
@@ -622,6 +623,10 @@ jxl_status ctx_link(jxl_ctx* c, CtxLink* out);                      // hipSetDev
 jxl_status ctx_fail(jxl_ctx* c, jxl_status st, const char* msg);    // records the message (c may be null) and returns st
 jxl_status ctx_planes_get(jxl_ctx* c, int* h, int* w, float* p[3]);  // the resident planes, or JXL_ERR_STATE
 jxl_status ctx_planes_set(jxl_ctx* c, int h, int w, float* p[3]);    // resident planes of h x w to fill (contents undefined)
+// an image's home (image_home.h) for the exits: the resident planes with the host plane `alpha` (JXL_ERR_STATE without); planes
+// 0 .. n_color - 1 of the set `id` and its plane alpha_plane (an unknown id and planes it has not are the home's first half)
+jxl_status ctx_home_resident(jxl_ctx* c, const void* alpha, ImageHome* m);
+ImageHome ctx_home_set(jxl_ctx* c, int32_t id, int32_t n_color, int32_t alpha_plane, bool has_alpha);
 // the XYB stage's parameters as jxl_planes_xyb / jxl_stage_xyb make them from the header's values
 XybParams ctx_make_xyb(const float matrix[9], const float opsin_bias[3], const float cbrt_opsin_bias[3], float intensity_target);
 // the page-locked staging buffer of the spline and patch tables: room for `total` bytes at *host once the transfer before has read
@@ -632,12 +637,7 @@ jxl_status ctx_tables_send(jxl_ctx* c, size_t total, const char** dev);
 // run since jxl_modular_begin
 struct ModResult { const int32_t* d; int32_t h, w; };
 jxl_status ctx_modular_out(jxl_ctx* c, std::vector<ModResult>* out, bool* ran);
-// a set as the writers of host.hip read it (canvas_host.hip): false for an unknown id
-struct CanvasView {
-    int32_t n, h, w;
-    int32_t type[JXL_CANVAS_MAX_PLANES];
-    const uint32_t* plane[JXL_CANVAS_MAX_PLANES];
-};
+// a set as the exits read it (CanvasView: image_home.h; canvas_host.hip): false for an unknown id
 bool canvas_view(const CanvasStore* s, int32_t id, CanvasView* out);
 // jxl_canvas_from_modular's kernel (k_modplanes.hip): plane i of the set from one or two result channels of one pitch
 struct ModPlane {

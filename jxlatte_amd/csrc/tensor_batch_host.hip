@@ -1,8 +1,9 @@
-// Host side of the batched resized tensor exit (k_tensor_resize_batch.hip): jxl_tensor_resized_batch. Per item it makes the
-// checks of the single-image entry of the item's source kind -- through the functions those entries call themselves
-// (tensor_host.h), in their order -- and plans the item's launch as they do; what is the batch's own (its refusals, the sharing
-// of tables, the work list, the LDS size, the tensors' places) is tensor_batch_check.h's. Nothing is queued before every item has
-// passed; the descriptors, the work list and the tables go up in ONE transfer; one launch; the stream is synchronised once.
+// Host side of the batched resized tensor exit (k_tensor_resize_batch.hip): jxl_tensor_resized_batch. Per item it resolves the
+// image's home from the item's source kind (one switch) and makes the checks of the single-image entries on it -- through the
+// functions those entries call themselves (tensor_host.h), in their order -- and plans the item's launch as they do; what is
+// the batch's own (its refusals, the sharing of tables, the work list, the LDS size, the tensors' places) is
+// tensor_batch_check.h's. Nothing is queued before every item has passed; the descriptors, the work list and the tables go up in
+// ONE transfer; one launch; the stream is synchronised once.
 #include "tensor_batch_check.h"
 #include "tensor_host.h"
 
@@ -12,12 +13,6 @@
 
 namespace jxl {
 namespace {
-
-#define TB_HIP(c, expr)                                                                                                        \
-    do {                                                                                                                      \
-        hipError_t e_ = (expr);                                                                                               \
-        if (e_ != hipSuccess) return ctx_fail(c, e_ == hipErrorOutOfMemory ? JXL_ERR_OOM : JXL_ERR_DEVICE, hipGetErrorString(e_)); \
-    } while (0)
 
 // tests: the bound of the batch launches' grid (jxl_debug_tensor_batch_grid), 0: the host's own
 int g_batch_grid = 0;
@@ -83,24 +78,24 @@ jxl_status jxl_tensor_resized_batch(jxl_ctx* c, int32_t n, const jxl_tensor_batc
     const int64_t slots = slots_all / n > 1 ? slots_all / n : 1;  // an item's share of the workgroups in flight
     BatchTableSet set;
     std::vector<Item> plan((size_t)n);
-    std::vector<CanvasView> views((size_t)n);
+    std::vector<ImageHome> homes((size_t)n);
     std::vector<int64_t> tiles((size_t)n);
     std::vector<int> lds((size_t)n);
     int n_color = 0;
     for (int i = 0; i < n; i++) {
         const jxl_tensor_batch_item& it = items[i];
         Item& m = plan[(size_t)i];
-        const void* in[3] = {it.in[0], it.in[1], it.in[2]};
-        const void* alpha = it.alpha;
-        int h = 0, w = 0;
-        if (it.source == JXL_BATCH_RESIDENT && (st = resize_home_resident(c, &h, &w, in))) return item_fail(c, i, st);
-        if (it.source == JXL_BATCH_SET && (st = resize_home_set(c, l, it.set_id, it.alpha_plane, &it.p, &views[(size_t)i], in, &alpha)))
-            return item_fail(c, i, st);
+        ImageHome& home = homes[(size_t)i];
+        switch (it.source) {
+            case JXL_BATCH_HOST: home = home_host(it.in, it.alpha), st = JXL_OK; break;
+            case JXL_BATCH_RESIDENT: st = ctx_home_resident(c, it.alpha, &home); break;
+            default: st = tensor_home_set(c, it.set_id, it.alpha_plane, &it.p, &home);
+        }
+        if (st) return item_fail(c, i, st);
         TensorLayout lay;
         void* out = (char*)out_device + off[(size_t)i];
-        if ((st = resize_args(c, l, &it.p, &it.r, in, alpha, out, &m.r, &lay, false))) return item_fail(c, i, st);
-        if (it.source == JXL_BATCH_RESIDENT && (st = resize_home_resident_fits(c, &it.p, h, w))) return item_fail(c, i, st);
-        if (it.source == JXL_BATCH_SET && (st = resize_home_set_fits(c, &it.p, views[(size_t)i], it.alpha_plane))) return item_fail(c, i, st);
+        if ((st = resize_args(c, l, &it.p, &it.r, home.in(), home.alpha, out, &m.r, &lay, false))) return item_fail(c, i, st);
+        if ((st = tensor_home_fits(c, home, &it.p))) return item_fail(c, i, st);
         if ((m.ty = set.find(0, it.r.box_height, it.r.out_height, it.r.filter, &why)) < 0 ||
             (m.tx = set.find(1, it.r.box_width, it.r.out_width, it.r.filter, &why)) < 0)
             return item_fail(c, i, JXL_ERR_INVALID_ARGUMENT, why);
@@ -108,27 +103,17 @@ jxl_status jxl_tensor_resized_batch(jxl_ctx* c, int32_t n, const jxl_tensor_batc
         tiles[(size_t)i] = batch_item_tiles(m.r.oh, m.r.ow, m.r.tw, m.r.th);
         lds[(size_t)i] = m.r.lds_bytes;
         n_color = lay.n_color;  // (one value: the items agree on n_out, which is n_color, + 1 with alpha written)
-        // the planes that are on the device already; host planes go up behind the last check
-        if (it.source != JXL_BATCH_HOST)
-            for (int k = 0; k < it.p.color.n_planes; k++) m.r.t.g.c.in[k] = in[k];
-        if (it.source == JXL_BATCH_SET && tensor_alpha_read(&it.p)) m.r.t.g.alpha = alpha;
     }
     std::vector<int64_t> base;
     if ((why = batch_tile_base(tiles, &base))) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, why);
     const int lds_bytes = batch_lds_bytes(lds);
     const unsigned grid = batch_grid(base[(size_t)n], g_batch_grid > 0 ? g_batch_grid : kBatchGrid);
 
-    // every check has passed: host planes up, once per item
+    // every check has passed: each item's planes to their places, host planes up once per item
     Staged s;
     for (int i = 0; i < n; i++) {
-        const jxl_tensor_batch_item& it = items[i];
         ResizeArgs& r = plan[(size_t)i].r;
-        const size_t plane = (size_t)it.p.height * (size_t)it.p.width * 4;
-        if (it.source == JXL_BATCH_HOST)
-            for (int k = 0; k < it.p.color.n_planes; k++)
-                if (!(r.t.g.c.in[k] = s.up(it.in[k], plane))) return ctx_fail(c, JXL_ERR_OOM, "device allocation failed");
-        if (it.source != JXL_BATCH_SET && tensor_alpha_read(&it.p) && !(r.t.g.alpha = s.up(it.alpha, plane)))
-            return ctx_fail(c, JXL_ERR_OOM, "device allocation failed");
+        if ((st = tensor_place(c, homes[(size_t)i], &items[i].p, &r.t.g, &s))) return st;
         resize_set_wide_in(&r);
     }
 
@@ -165,13 +150,13 @@ jxl_status jxl_tensor_resized_batch(jxl_ctx* c, int32_t n, const jxl_tensor_batc
     std::memcpy(pack.data() + at_base, base.data(), 8 * ((size_t)n + 1));
     const int32_t counts[2] = {n, (int32_t)set.tables.size()};
     std::memcpy(pack.data() + at_counts, counts, 8);
-    TB_HIP(c, hipMemcpy(dev, pack.data(), block, hipMemcpyHostToDevice));
+    TENSOR_HIP(c, hipMemcpy(dev, pack.data(), block, hipMemcpyHostToDevice));
     const int64_t stats[8] = {set.asked, (int64_t)set.tables.size(), (int64_t)block, base[(size_t)n], grid, lds_bytes, plan[0].r.tw, plan[0].r.th};
     std::memcpy(g_stats, stats, sizeof stats);
     launch_tensor_resize_batch((const ResizeArgs*)(dev + at_items), (const int64_t*)(dev + at_base), (const int32_t*)(dev + at_counts),
                                first.dtype, n_color, grid, lds_bytes, l.stream);
-    TB_HIP(c, hipStreamSynchronize(l.stream));
-    TB_HIP(c, hipGetLastError());
+    TENSOR_HIP(c, hipStreamSynchronize(l.stream));
+    TENSOR_HIP(c, hipGetLastError());
     return JXL_OK;
 }
 

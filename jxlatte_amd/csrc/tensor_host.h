@@ -1,6 +1,6 @@
 // What the tensor entries' host files (tensor_host.hip, tensor_resize_host.hip, tensor_batch_host.hip) share: the staging of
-// host planes, the runtime check of out_device, the checks of one jxl_tensor_params, and -- of the resized entries -- the checks
-// of an image's home and the plan of its launch.
+// host planes, the runtime check of out_device, the checks of one jxl_tensor_params, an image's home (image_home.h) in these
+// entries' words, and -- of the resized entries -- the plan of a launch.
 #ifndef JXL_TENSOR_HOST_H
 #define JXL_TENSOR_HOST_H
 #include "jxl_internal.h"
@@ -10,6 +10,13 @@
 #include <vector>
 
 namespace jxl {
+
+// a failed HIP call ends the entry: JXL_ERR_OOM or JXL_ERR_DEVICE with the runtime's words
+#define TENSOR_HIP(c, expr)                                                                                                    \
+    do {                                                                                                                      \
+        hipError_t e_ = (expr);                                                                                               \
+        if (e_ != hipSuccess) return ctx_fail(c, e_ == hipErrorOutOfMemory ? JXL_ERR_OOM : JXL_ERR_DEVICE, hipGetErrorString(e_)); \
+    } while (0)
 
 // device copies of host planes, freed when the entry returns
 struct Staged {
@@ -41,15 +48,15 @@ jxl_status tensor_args(jxl_ctx* c, const CtxLink& l, const jxl_tensor_params* p,
 // the alpha plane is read only where it is written or divides the colours
 inline bool tensor_alpha_read(const jxl_tensor_params* p) { return p->has_alpha && (p->write_alpha || p->premultiplied); }
 
+// ---- an image's home (image_home.h) in the tensor entries' words; host planes are home_host, resident ones ctx_home_resident ----
+// a set's planes 0 .. n_planes - 1 and its plane alpha_plane: the first half (the set, a null p, the planes asked for)
+jxl_status tensor_home_set(jxl_ctx* c, int32_t id, int32_t alpha_plane, const jxl_tensor_params* p, ImageHome* m);
+// the second half, behind tensor_args / resize_args: the parameters describe the home
+jxl_status tensor_home_fits(jxl_ctx* c, const ImageHome& m, const jxl_tensor_params* p);
+// the plane pointers of g: planes on the device as they are, the others uploaded (the alpha plane only where it is read)
+jxl_status tensor_place(jxl_ctx* c, const ImageHome& m, const jxl_tensor_params* p, PngArgs* g, Staged* s);
+
 // ---- the resized entries (tensor_resize_host.hip), one image at a time or many (tensor_batch_host.hip) ----
-// The checks of an image's home, each in two halves around resize_args as the single-image entries order them. Resident planes:
-// the planes (JXL_ERR_STATE without), then that the parameters describe them
-jxl_status resize_home_resident(jxl_ctx* c, int* h, int* w, const void* in[3]);
-jxl_status resize_home_resident_fits(jxl_ctx* c, const jxl_tensor_params* p, int h, int w);
-// a plane set: the set and the planes asked of it, then that the parameters carry its geometry and tags
-jxl_status resize_home_set(jxl_ctx* c, const CtxLink& l, int32_t id, int32_t alpha_plane, const jxl_tensor_params* p, CanvasView* v,
-                           const void* in[3], const void** alpha);
-jxl_status resize_home_set_fits(jxl_ctx* c, const jxl_tensor_params* p, const CanvasView& v, int32_t alpha_plane);
 // the workgroups the device holds at once: two per compute unit (the kernel's registers allow two waves per SIMD)
 int64_t resize_slots(const CtxLink& l);
 // the checks every resized entry makes first: the pure ones of the resize, then tensor_args with the tensor's size

@@ -1,16 +1,12 @@
-// Host side of the tensor exit (k_tensor.hip): the three jxl_*_tensor_samples entries beside the PNG's three. The checks the PNG
-// entries make are theirs (ctx_png_args, host.hip), the tensor's own pure checks are tensor_check.h's; what is left here is the
-// question only the runtime can answer -- is out_device device memory of this context's device, and does its allocation hold the
-// tensor -- and the launch. Nothing is queued before every check has passed; the stream is synchronised before return.
+// Host side of the tensor exit (k_tensor.hip): the three jxl_*_tensor_samples entries beside the PNG's three, each of them "resolve
+// the image's home, then samples_from_home". The checks the PNG entries make are theirs (ctx_png_args, host.hip), the tensor's own
+// pure checks are tensor_check.h's, those of a home image_home.h's -- in this file they get the tensor entries' words, for the
+// resized and the batch entries too (tensor_host.h). What is left here is the question only the runtime can answer -- is
+// out_device device memory of this context's device, and does its allocation hold the tensor -- and the launch. Nothing is queued
+// before every check has passed; the stream is synchronised before return.
 #include "tensor_host.h"
 
 namespace jxl {
-
-#define TS_HIP(c, expr)                                                                                                        \
-    do {                                                                                                                      \
-        hipError_t e_ = (expr);                                                                                               \
-        if (e_ != hipSuccess) return ctx_fail(c, e_ == hipErrorOutOfMemory ? JXL_ERR_OOM : JXL_ERR_DEVICE, hipGetErrorString(e_)); \
-    } while (0)
 
 jxl_status tensor_out_check(jxl_ctx* c, const CtxLink& l, void* out, uint64_t bytes) {
     hipPointerAttribute_t at;
@@ -61,13 +57,50 @@ jxl_status tensor_args(jxl_ctx* c, const CtxLink& l, const jxl_tensor_params* p,
 }
 
 namespace {
+// the tensor entries' words for a home's refusal
+jxl_status home_fail(jxl_ctx* c, HomeRefusal r, const ImageHome& m) {
+    const char* why = r == HOME_UNKNOWN_SET       ? "canvas: unknown set"
+                      : r == HOME_NO_SUCH_PLANES  ? "tensor samples: the set has no such planes"
+                      : m.kind == HOME_RESIDENT   ? "tensor samples: the resident planes are three float planes of another size"
+                                                  : "tensor samples: the parameters do not describe the set's planes";
+    return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, why);
+}
+}  // namespace
 
-bool alpha_read(const jxl_tensor_params* p) { return tensor_alpha_read(p); }
+jxl_status tensor_home_set(jxl_ctx* c, int32_t id, int32_t alpha_plane, const jxl_tensor_params* p, ImageHome* m) {
+    *m = ctx_home_set(c, id, p ? p->color.n_planes : 0, alpha_plane, p && p->has_alpha);
+    if (m->planes == HOME_UNKNOWN_SET) return home_fail(c, m->planes, *m);
+    if (!p) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: null argument");
+    return m->planes ? home_fail(c, m->planes, *m) : JXL_OK;
+}
 
-jxl_status tensor_run(jxl_ctx* c, const CtxLink& l, const TensorArgs& t, int max_workgroups) {
+jxl_status tensor_home_fits(jxl_ctx* c, const ImageHome& m, const jxl_tensor_params* p) {
+    const HomeRefusal r = home_describes(m, p->height, p->width, p->color.n_planes, p->color.in_is_int, p->alpha_is_int);
+    return r ? home_fail(c, r, m) : JXL_OK;
+}
+
+jxl_status tensor_place(jxl_ctx* c, const ImageHome& m, const jxl_tensor_params* p, PngArgs* g, Staged* s) {
+    const HomeUploads up = home_uploads(m);
+    const size_t plane = (size_t)p->height * (size_t)p->width * 4;
+    for (int i = 0; i < p->color.n_planes; i++)
+        if (!(g->c.in[i] = up.color ? s->up(m.color[i], plane) : m.color[i])) return ctx_fail(c, JXL_ERR_OOM, "device allocation failed");
+    if (tensor_alpha_read(p) && !(g->alpha = up.alpha ? s->up(m.alpha, plane) : m.alpha)) return ctx_fail(c, JXL_ERR_OOM, "device allocation failed");
+    return JXL_OK;
+}
+
+namespace {
+
+// the body of the three entries: tensor_args, the home's second half, the planes' places, the launch
+jxl_status samples_from_home(jxl_ctx* c, const CtxLink& l, const ImageHome& m, const jxl_tensor_params* p, void* out, int max_workgroups) {
+    TensorArgs t;
+    TensorLayout lay;
+    jxl_status st = tensor_args(c, l, p, m.in(), m.alpha, out, &t, &lay);
+    if (st || (st = tensor_home_fits(c, m, p))) return st;
+    Staged s;
+    if ((st = tensor_place(c, m, p, &t.g, &s))) return st;
     launch_tensor_samples(t, l.stream, max_workgroups);
-    TS_HIP(c, hipStreamSynchronize(l.stream));
-    TS_HIP(c, hipGetLastError());
+    TENSOR_HIP(c, hipStreamSynchronize(l.stream));
+    TENSOR_HIP(c, hipGetLastError());
     return JXL_OK;
 }
 
@@ -75,15 +108,7 @@ jxl_status stage_entry(jxl_ctx* c, const void* const in[3], const void* alpha, c
     CtxLink l;
     jxl_status st = ctx_link(c, &l);
     if (st) return st;
-    TensorArgs t;
-    TensorLayout lay;
-    if ((st = tensor_args(c, l, p, in, alpha, out, &t, &lay))) return st;
-    Staged s;
-    const size_t plane = (size_t)lay.pixels * 4;
-    for (int i = 0; i < p->color.n_planes; i++)
-        if (!(t.g.c.in[i] = s.up(in[i], plane))) return ctx_fail(c, JXL_ERR_OOM, "device allocation failed");
-    if (alpha_read(p) && !(t.g.alpha = s.up(alpha, plane))) return ctx_fail(c, JXL_ERR_OOM, "device allocation failed");
-    return tensor_run(c, l, t, max_workgroups);
+    return samples_from_home(c, l, home_host(in, alpha), p, out, max_workgroups);
 }
 
 }  // namespace
@@ -106,46 +131,18 @@ jxl_status jxl_debug_tensor_samples_grid(jxl_ctx* c, const void* const in[3], co
 
 jxl_status jxl_planes_tensor_samples(jxl_ctx* c, const void* alpha, const jxl_tensor_params* p, void* out_device) {
     CtxLink l;
+    ImageHome m;
     jxl_status st = ctx_link(c, &l);
-    if (st) return st;
-    int h = 0, w = 0;
-    float* rp[3];
-    if ((st = ctx_planes_get(c, &h, &w, rp))) return st;
-    const void* in[3] = {rp[0], rp[1], rp[2]};
-    TensorArgs t;
-    TensorLayout lay;
-    if ((st = tensor_args(c, l, p, in, alpha, out_device, &t, &lay))) return st;
-    if (p->color.n_planes != 3 || p->color.in_is_int || p->height != h || p->width != w)
-        return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: the resident planes are three float planes of another size");
-    for (int i = 0; i < 3; i++) t.g.c.in[i] = in[i];
-    Staged s;
-    if (alpha_read(p) && !(t.g.alpha = s.up(alpha, (size_t)lay.pixels * 4))) return ctx_fail(c, JXL_ERR_OOM, "device allocation failed");
-    return tensor_run(c, l, t, 0);
+    if (st || (st = ctx_home_resident(c, alpha, &m))) return st;
+    return samples_from_home(c, l, m, p, out_device, 0);
 }
 
 jxl_status jxl_canvas_tensor_samples(jxl_ctx* c, int32_t id, int32_t alpha_plane, const jxl_tensor_params* p, void* out_device) {
     CtxLink l;
+    ImageHome m;
     jxl_status st = ctx_link(c, &l);
-    if (st) return st;
-    CanvasView v;
-    if (!canvas_view(*l.canvas, id, &v)) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
-    if (!p) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: null argument");
-    const int nc = p->color.n_planes;
-    if ((nc != 1 && nc != 3) || nc > v.n || alpha_plane < -1 || alpha_plane >= v.n || (p->has_alpha != 0) != (alpha_plane >= 0))
-        return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: the set has no such planes");
-    const void* in[3] = {nullptr, nullptr, nullptr};
-    for (int i = 0; i < nc; i++) in[i] = v.plane[i];
-    const void* alpha = alpha_plane >= 0 ? v.plane[alpha_plane] : nullptr;
-    TensorArgs t;
-    TensorLayout lay;
-    if ((st = tensor_args(c, l, p, in, alpha, out_device, &t, &lay))) return st;
-    bool tags = p->height == v.h && p->width == v.w;
-    for (int i = 0; i < nc; i++) tags = tags && (p->color.in_is_int != 0) == (v.type[i] == JXL_PLANE_INT32);
-    if (alpha_plane >= 0) tags = tags && (p->alpha_is_int != 0) == (v.type[alpha_plane] == JXL_PLANE_INT32);
-    if (!tags) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: the parameters do not describe the set's planes");
-    for (int i = 0; i < nc; i++) t.g.c.in[i] = in[i];
-    if (alpha_read(p)) t.g.alpha = alpha;
-    return tensor_run(c, l, t, 0);
+    if (st || (st = tensor_home_set(c, id, alpha_plane, p, &m))) return st;
+    return samples_from_home(c, l, m, p, out_device, 0);
 }
 
 }  // extern "C"

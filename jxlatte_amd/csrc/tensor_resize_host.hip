@@ -2,8 +2,8 @@
 // siblings (tensor_host.hip), whose checks of the parameters, the planes and out_device they share (tensor_args). Their own pure
 // part -- box, size, filter, the tap tables, the tile -- is tensor_resize_check.h's. Nothing is queued before every check has
 // passed; the tables go up once per call, in one transfer; the stream is synchronised before return.
-// The checks of an image's home and the plan of its launch are functions of tensor_host.h: the batch entry
-// (tensor_batch_host.hip) makes the same ones per item.
+// Each entry resolves its image's home (image_home.h, in the words of tensor_host.hip) and calls resized_from_home. The plan of a
+// launch is a function of tensor_host.h: the batch entry (tensor_batch_host.hip) plans each item with it.
 #include "tensor_host.h"
 #include "tensor_resize_check.h"
 
@@ -11,12 +11,6 @@
 
 namespace jxl {
 namespace {
-
-#define TR_HIP(c, expr)                                                                                                        \
-    do {                                                                                                                      \
-        hipError_t e_ = (expr);                                                                                               \
-        if (e_ != hipSuccess) return ctx_fail(c, e_ == hipErrorOutOfMemory ? JXL_ERR_OOM : JXL_ERR_DEVICE, hipGetErrorString(e_)); \
-    } while (0)
 
 // tests: the tile and the LDS skew of the launches that follow (jxl_debug_tensor_resize_tile, jxl_debug_tensor_resize_skew)
 int g_force_tw = 0, g_force_th = 0;
@@ -57,18 +51,25 @@ jxl_status resize_run(jxl_ctx* c, const CtxLink& l, ResizeArgs* r, const Tables&
     r->wy = (const float*)(d + where[4]), r->wx = (const float*)(d + where[5]);
     resize_set_wide_in(r);
     launch_tensor_resize(*r, l.stream);
-    TR_HIP(c, hipStreamSynchronize(l.stream));
-    TR_HIP(c, hipGetLastError());
+    TENSOR_HIP(c, hipStreamSynchronize(l.stream));
+    TENSOR_HIP(c, hipGetLastError());
     return JXL_OK;
 }
 
-// resize_args, the tables and the plan of a single image
-jxl_status resize_single(jxl_ctx* c, const CtxLink& l, const jxl_tensor_params* p, const jxl_resize_params* rz, const void* const in[3],
-                         const void* alpha, void* out, ResizeArgs* r, TensorLayout* lay, Tables* tb) {
-    jxl_status st = resize_args(c, l, p, rz, in, alpha, out, r, lay);
-    if (st) return st;
-    if ((st = resize_tables(c, rz, tb))) return st;
-    return resize_plan(c, p, rz, *lay, tb->x, tb->y, resize_slots(l), r);
+// the body of the three entries: resize_args, the tables and the plan of a single image, the home's second half, the planes'
+// places, the launch
+jxl_status resized_from_home(jxl_ctx* c, const CtxLink& l, const ImageHome& m, const jxl_tensor_params* p, const jxl_resize_params* rz,
+                             void* out) {
+    ResizeArgs r;
+    TensorLayout lay;
+    Tables tb;
+    jxl_status st = resize_args(c, l, p, rz, m.in(), m.alpha, out, &r, &lay);
+    if (st || (st = resize_tables(c, rz, &tb))) return st;
+    if ((st = resize_plan(c, p, rz, lay, tb.x, tb.y, resize_slots(l), &r))) return st;
+    if ((st = tensor_home_fits(c, m, p))) return st;
+    Staged s;
+    if ((st = tensor_place(c, m, p, &r.t.g, &s))) return st;
+    return resize_run(c, l, &r, tb, &s);
 }
 
 }  // namespace
@@ -110,42 +111,6 @@ jxl_status resize_args(jxl_ctx* c, const CtxLink& l, const jxl_tensor_params* p,
     return tensor_args(c, l, p, in, alpha, out, &r->t, lay, rz->out_height, rz->out_width, check_out);
 }
 
-jxl_status resize_home_resident(jxl_ctx* c, int* h, int* w, const void* in[3]) {
-    float* rp[3];
-    jxl_status st = ctx_planes_get(c, h, w, rp);
-    if (st) return st;
-    for (int i = 0; i < 3; i++) in[i] = rp[i];
-    return JXL_OK;
-}
-
-jxl_status resize_home_resident_fits(jxl_ctx* c, const jxl_tensor_params* p, int h, int w) {
-    if (p->color.n_planes != 3 || p->color.in_is_int || p->height != h || p->width != w)
-        return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: the resident planes are three float planes of another size");
-    return JXL_OK;
-}
-
-jxl_status resize_home_set(jxl_ctx* c, const CtxLink& l, int32_t id, int32_t alpha_plane, const jxl_tensor_params* p, CanvasView* v,
-                           const void* in[3], const void** alpha) {
-    if (!canvas_view(*l.canvas, id, v)) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
-    if (!p) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: null argument");
-    const int nc = p->color.n_planes;
-    if ((nc != 1 && nc != 3) || nc > v->n || alpha_plane < -1 || alpha_plane >= v->n || (p->has_alpha != 0) != (alpha_plane >= 0))
-        return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: the set has no such planes");
-    in[0] = in[1] = in[2] = nullptr;
-    for (int i = 0; i < nc; i++) in[i] = v->plane[i];
-    *alpha = alpha_plane >= 0 ? v->plane[alpha_plane] : nullptr;
-    return JXL_OK;
-}
-
-jxl_status resize_home_set_fits(jxl_ctx* c, const jxl_tensor_params* p, const CanvasView& v, int32_t alpha_plane) {
-    const int nc = p->color.n_planes;
-    bool tags = p->height == v.h && p->width == v.w;
-    for (int i = 0; i < nc; i++) tags = tags && (p->color.in_is_int != 0) == (v.type[i] == JXL_PLANE_INT32);
-    if (alpha_plane >= 0) tags = tags && (p->alpha_is_int != 0) == (v.type[alpha_plane] == JXL_PLANE_INT32);
-    if (!tags) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: the parameters do not describe the set's planes");
-    return JXL_OK;
-}
-
 }  // namespace jxl
 
 using namespace jxl;
@@ -157,55 +122,25 @@ jxl_status jxl_stage_tensor_resized(jxl_ctx* c, const void* const in[3], const v
     CtxLink l;
     jxl_status st = ctx_link(c, &l);
     if (st) return st;
-    ResizeArgs r;
-    TensorLayout lay;
-    Tables tb;
-    if ((st = resize_single(c, l, p, rz, in, alpha, out_device, &r, &lay, &tb))) return st;
-    Staged s;
-    const size_t plane = (size_t)p->height * (size_t)p->width * 4;
-    for (int i = 0; i < p->color.n_planes; i++)
-        if (!(r.t.g.c.in[i] = s.up(in[i], plane))) return ctx_fail(c, JXL_ERR_OOM, "device allocation failed");
-    if (tensor_alpha_read(p) && !(r.t.g.alpha = s.up(alpha, plane))) return ctx_fail(c, JXL_ERR_OOM, "device allocation failed");
-    return resize_run(c, l, &r, tb, &s);
+    return resized_from_home(c, l, home_host(in, alpha), p, rz, out_device);
 }
 
 jxl_status jxl_planes_tensor_resized(jxl_ctx* c, const void* alpha, const jxl_tensor_params* p, const jxl_resize_params* rz,
                                      void* out_device) {
     CtxLink l;
+    ImageHome m;
     jxl_status st = ctx_link(c, &l);
-    if (st) return st;
-    int h = 0, w = 0;
-    const void* in[3];
-    if ((st = resize_home_resident(c, &h, &w, in))) return st;
-    ResizeArgs r;
-    TensorLayout lay;
-    Tables tb;
-    if ((st = resize_single(c, l, p, rz, in, alpha, out_device, &r, &lay, &tb))) return st;
-    if ((st = resize_home_resident_fits(c, p, h, w))) return st;
-    for (int i = 0; i < 3; i++) r.t.g.c.in[i] = in[i];
-    Staged s;
-    if (tensor_alpha_read(p) && !(r.t.g.alpha = s.up(alpha, (size_t)h * (size_t)w * 4))) return ctx_fail(c, JXL_ERR_OOM, "device allocation failed");
-    return resize_run(c, l, &r, tb, &s);
+    if (st || (st = ctx_home_resident(c, alpha, &m))) return st;
+    return resized_from_home(c, l, m, p, rz, out_device);
 }
 
 jxl_status jxl_canvas_tensor_resized(jxl_ctx* c, int32_t id, int32_t alpha_plane, const jxl_tensor_params* p, const jxl_resize_params* rz,
                                      void* out_device) {
     CtxLink l;
+    ImageHome m;
     jxl_status st = ctx_link(c, &l);
-    if (st) return st;
-    CanvasView v;
-    const void* in[3];
-    const void* alpha = nullptr;
-    if ((st = resize_home_set(c, l, id, alpha_plane, p, &v, in, &alpha))) return st;
-    ResizeArgs r;
-    TensorLayout lay;
-    Tables tb;
-    if ((st = resize_single(c, l, p, rz, in, alpha, out_device, &r, &lay, &tb))) return st;
-    if ((st = resize_home_set_fits(c, p, v, alpha_plane))) return st;
-    for (int i = 0; i < p->color.n_planes; i++) r.t.g.c.in[i] = in[i];
-    if (tensor_alpha_read(p)) r.t.g.alpha = alpha;
-    Staged s;
-    return resize_run(c, l, &r, tb, &s);
+    if (st || (st = tensor_home_set(c, id, alpha_plane, p, &m))) return st;
+    return resized_from_home(c, l, m, p, rz, out_device);
 }
 
 // tests: the tile of the resized launches that follow, (0, 0) for the host's own choice again. A tile the kernel does not have
