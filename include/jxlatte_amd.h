@@ -624,6 +624,22 @@ jxl_status jxl_stage_color_convert(jxl_ctx* ctx, const void* const in[3], int64_
  * (float)in_max (:219). w <= 2^30. */
 jxl_status jxl_stage_color_peak(jxl_ctx* ctx, const void* const in[3], int32_t h, int32_t w, const jxl_color_params* p,
                                 float* peak);
+/* HDR -> SDR in the colour passes (jxlatte_amd/csrc/tone_map_ops.h has the definition; not the reference's): per pixel, behind
+ * stage 4 and instead of stage 5, the BT.2408 Annex 5 curve on the pixel's luminance (standard PQ, no black lift), all three
+ * samples multiplied by the one factor, then -- gamut 1 -- the least mix toward the pixel's own grey that brings it into [0, 1].
+ * lum: the Y row of the RGB -> XYZ matrix of the primaries the samples are in behind stage 4; unit_nits: nits of a linear 1.0;
+ * source_nits: the content's mastering peak; target_nits: the peak of the display the output is for (a linear 1.0 behind it). */
+typedef struct jxl_tone_map { float lum[3]; float unit_nits, source_nits, target_nits; int32_t gamut; } jxl_tone_map;
+/* arms (tm != NULL) or clears (NULL) tone mapping for the colour passes of this context: while armed, jxl_stage_color_convert,
+ * the three *_png_samples, the three *_tensor_samples, the three *_tensor_resized entries and jxl_tensor_resized_batch (all items
+ * share the block) apply it and write three colour channels, a one-plane image as three equal ones, as with use_matrix; a
+ * jxl_color_params with use_scale set is JXL_ERR_INVALID_ARGUMENT there (nothing written). jxl_stage_color_peak, the PFM
+ * entries and everything else ignore it. JXL_ERR_INVALID_ARGUMENT (the context keeps what it had): non-finite or non-positive
+ * nits, source_nits > 10000, a non-finite weight, a weight sum outside (0, 2], gamut other than 0 or 1. */
+jxl_status jxl_ctx_set_tone_map(jxl_ctx* ctx, const jxl_tone_map* tm);
+/* 1 while tone mapping is armed, else 0 (a null ctx: 0): what a caller that sizes an output buffer from a jxl_color_params asks,
+ * since an armed context writes three colour channels of a one-plane image */
+int32_t jxl_ctx_tone_map_armed(const jxl_ctx* ctx);
 /* ModularChannel.inverseHorizontalSqueeze / inverseVerticalSqueeze
  * (ModularChannel.java:361-413). out is (h) x (aw+rw) resp. (ah+rh) x (w). */
 jxl_status jxl_stage_inv_hsqueeze(jxl_ctx* ctx, const int32_t* avg, int32_t aw, const int32_t* res, int32_t rw,

@@ -144,6 +144,8 @@ public final class NativeBackend implements AutoCloseable {
     public native void stageColorConvert(ByteBuffer i0, ByteBuffer i1, ByteBuffer i2, long n, ByteBuffer params, ByteBuffer o0, ByteBuffer o1,
         ByteBuffer o2);                                            // jxl_stage_color_convert (JXLImage.transform)
     public native float stageColorPeak(ByteBuffer i0, ByteBuffer i1, ByteBuffer i2, int h, int w, ByteBuffer params); // jxl_stage_color_peak
+    /** tm: struct jxl_tone_map packed by the caller (7 four-byte fields) arms HDR to SDR tone mapping in the colour passes, null clears it. */
+    public native void setToneMap(ByteBuffer tm);                  // jxl_ctx_set_tone_map
     public native void stageInvHSqueeze(ByteBuffer avg, int aw, ByteBuffer res, int rw, int h, ByteBuffer out); // jxl_stage_inv_hsqueeze
     public native void stageInvVSqueeze(ByteBuffer avg, int ah, ByteBuffer res, int rh, int w, ByteBuffer out); // jxl_stage_inv_vsqueeze
     public native void stageRct(ByteBuffer v0, ByteBuffer v1, ByteBuffer v2, long n, int rctType);    // jxl_stage_rct

@@ -1090,6 +1090,23 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageColorC
     CHECK(jxl_stage_color_convert(c, in, n, &p, out));
 }
 
+/* jxl_ctx_set_tone_map: tm = struct jxl_tone_map in a direct buffer arms the context's colour passes, null clears them */
+JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_setToneMap(JNIEnv* e, jobject self, jobject tm) {
+    jxl_ctx* c = ctx_of(e, self);
+    jxl_tone_map t;
+    if (!tm) {
+        CHECK(jxl_ctx_set_tone_map(c, NULL));
+        return;
+    }
+    const void* src = (*e)->GetDirectBufferAddress(e, tm);
+    if (!src || (*e)->GetDirectBufferCapacity(e, tm) < (jlong)sizeof t) {
+        bad_arg(e, "jxlatte_amd: a direct buffer holding jxl_tone_map is needed");
+        return;
+    }
+    memcpy(&t, src, sizeof t);
+    CHECK(jxl_ctx_set_tone_map(c, &t));
+}
+
 /* JXLImage.determinePeak (:214-223) */
 JNIEXPORT jfloat JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stageColorPeak(JNIEnv* e, jobject self, jobject i0, jobject i1, jobject i2,
         jint h, jint w, jobject params) {
@@ -1306,8 +1323,8 @@ static int png_params(JNIEnv* e, jobject params, jxl_png_params* p) {
     return 1;
 }
 /* the bytes of the samples `p` asks for */
-static jlong png_bytes(const jxl_png_params* p) {
-    const int nc = (p->color.n_planes == 3 || p->color.use_matrix) ? 3 : 1;
+static jlong png_bytes(const jxl_ctx* c, const jxl_png_params* p) {
+    const int nc = (p->color.n_planes == 3 || p->color.use_matrix || jxl_ctx_tone_map_armed(c)) ? 3 : 1;
     return area(p->height, p->width) * (nc + (p->has_alpha ? 1 : 0)) * (p->bit_depth / 8);
 }
 
@@ -1318,7 +1335,7 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_stagePngSam
     if (!png_params(e, params, &p)) return;
     const jlong plane = 4 * area(p.height, p.width);
     NEED(i0, plane); NEED_OPT(i1, plane); NEED_OPT(i2, plane); NEED_OPT(alpha, plane);
-    NEED(out, png_bytes(&p));
+    NEED(out, png_bytes(c, &p));
     const void* in[3] = {ADDR(i0), ADDR(i1), ADDR(i2)};
     CHECK(jxl_stage_png_samples(c, in, ADDR(alpha), &p, ADDR(out)));
 }
@@ -1330,7 +1347,7 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_planesPngSa
     jxl_png_params p;
     if (!png_params(e, params, &p)) return;
     NEED_OPT(alpha, 4 * area(p.height, p.width));
-    NEED(out, png_bytes(&p));
+    NEED(out, png_bytes(c, &p));
     CHECK(jxl_planes_png_samples(c, ADDR(alpha), &p, ADDR(out)));
 }
 
@@ -1576,7 +1593,7 @@ JNIEXPORT void JNICALL Java_com_traneptora_jxlatte_gpu_NativeBackend_canvasPngSa
     jxl_ctx* c = ctx_of(e, self);
     jxl_png_params p;
     if (!png_params(e, params, &p)) return;
-    NEED(out, png_bytes(&p));
+    NEED(out, png_bytes(c, &p));
     CHECK(jxl_canvas_png_samples(c, id, alphaPlane, &p, ADDR(out)));
 }
 

@@ -75,7 +75,34 @@ def parser():
                     help="decode only this box of the image as delivered (JXLDecoder region): the front-end reads the groups the box "
                          "needs and no others (jxf_set_region), and the output is the box: the full decode's pixels there, bit for "
                          "bit. An image whose frame does not qualify (JXLDecoder.region_rule) stops with the reason")
+    ap.add_argument("--tone-map", type=tone_map_arg, default=None, metavar="NITS[,SOURCE_NITS]",
+                    help="HDR to SDR inside the PNG's device colour pass (PNGWriter toneMap; jxl_ctx_set_tone_map): the BT.2408 "
+                         "luminance curve to a display of NITS, from SOURCE_NITS (default: the image's intensity target), then a "
+                         "desaturation into gamut. Replaces peak detection; writes an SDR PNG; turns --device-color on when "
+                         "neither it nor --device-png is given")
+    ap.add_argument("--no-gamut-map", action="store_true", help="with --tone-map: leave out-of-gamut samples to the quantiser's clipping")
     return ap
+
+
+def tone_map_arg(text):
+    """--tone-map=nits[,source_nits] -> (nits, source_nits or None), finite and positive"""
+    try:
+        v = tuple(float(t) for t in text.split(","))
+    except ValueError:
+        v = ()
+    if len(v) not in (1, 2) or any(not (x > 0 and x != float("inf")) for x in v) or (len(v) == 2 and v[1] > 10000):
+        raise argparse.ArgumentTypeError("expected NITS[,SOURCE_NITS], positive numbers (SOURCE_NITS at most 10000), not %r" % text)
+    return (v[0], v[1] if len(v) == 2 else None)
+
+
+def tone_map_of(a):
+    """the ToneMap of the parsed arguments, or None; --tone-map turns --device-color on if no device colour switch was given"""
+    if a.tone_map is None:
+        return None
+    from .decoder import ToneMap
+    if not (a.device_color or a.device_png):
+        a.device_color = True
+    return ToneMap(targetNits=a.tone_map[0], sourceNits=a.tone_map[1], gamut=not a.no_gamut_map)
 
 
 def region_arg(text):
@@ -148,10 +175,11 @@ def main(argv=None):
         with open(a.output, "wb") as f:
             PFMWriter(image, deviceSamples=a.device_png).write(f)
     elif a.output:
-        hdr = image.isHDR() if a.png_hdr == "auto" else a.png_hdr == "yes"
+        tone_map = tone_map_of(a)
+        hdr = (image.isHDR() and tone_map is None) if a.png_hdr == "auto" else a.png_hdr == "yes"
         with open(a.output, "wb") as f:
             PNGWriter(image, bitDepth=16 if hdr else a.png_depth, hdr=hdr, peakDetect=PEAK_DETECT[a.png_peak_detect],
-                      deviceColor=a.device_color, deviceSamples=a.device_png).write(f)
+                      deviceColor=a.device_color, deviceSamples=a.device_png, toneMap=tone_map).write(f)
     backend.close()
     return 0
 

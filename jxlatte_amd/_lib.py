@@ -62,6 +62,8 @@ SIGNATURES = {
     "jxl_ctx_synchronize": (i32, [vp]),
     "jxl_ctx_stream": (vp, [vp]),
     "jxl_ctx_set_stream": (i32, [vp, vp]),
+    "jxl_ctx_set_tone_map": (i32, [vp, C.POINTER(abi.ToneMapParams)]),
+    "jxl_ctx_tone_map_armed": (i32, [vp]),
     "jxl_vardct_begin_frame": (i32, [vp, C.POINTER(abi.VarDCTParams)]),
     "jxl_vardct_set_weights": (i32, [vp, pf, C.c_size_t, pi]),
     "jxl_vardct_set_lfgroup": (i32, [vp, C.POINTER(abi.LFGroupDesc)]),
@@ -268,6 +270,10 @@ class Context:
 
     def synchronize(self):
         self.call("jxl_ctx_synchronize")
+
+    def toneMapArmed(self):
+        """jxl_ctx_set_tone_map has armed the colour passes: they write three colour channels, of a one-plane image too"""
+        return bool(self.lib.jxl_ctx_tone_map_armed(self.h))
 
     @property
     def stream(self):

@@ -233,6 +233,12 @@ class ColorParams(C.Structure):
                 ("matrix", f9), ("tf_out", C.c_int32), ("gamma_out", C.c_int32), ("max_value", C.c_int32)]
 
 
+class ToneMapParams(C.Structure):
+    """struct jxl_tone_map"""
+    _fields_ = [("lum", C.c_float * 3), ("unit_nits", C.c_float), ("source_nits", C.c_float), ("target_nits", C.c_float),
+                ("gamut", C.c_int32)]
+
+
 class PngParams(C.Structure):
     """struct jxl_png_params"""
     _fields_ = [("color", ColorParams), ("height", C.c_int32), ("width", C.c_int32), ("has_alpha", C.c_int32),

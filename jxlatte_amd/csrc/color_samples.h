@@ -62,9 +62,19 @@ __device__ __forceinline__ float linear_word(const ColorArgs& a, int c, uint32_t
     return to_linear(f, a.tf_in, a.p_in, a.kind_in);
 }
 
+// tone_map_ops.h on one pixel. Inlined: out of line (__noinline__) every calling kernel got a stack -- 256 to 464 bytes of scratch
+// per lane -- and lost more occupancy than the inlined branch's ~20 VGPRs cost (profiles/tone_map.md has both tables)
+struct ToneMapped { float r, g, b; };
+__device__ __forceinline__ ToneMapped tone_map_stage(const ToneMapArgs& tm, float r, float g, float b) {
+    float v[3] = {r, g, b};
+    tone_map_pixel(tm, v);
+    return ToneMapped{v[0], v[1], v[2]};
+}
+
 // stages 1-5 of one pixel (cast, toLinearF, grey -> RGB, matrix, scale): the words of its colour planes (w[c], c < n_planes) ->
-// COLORS linear float samples, COLORS being 3 when n_planes == 3 or use_matrix, else 1. What a kernel that filters in linear
-// light (k_tensor_resize.hip) evaluates per SOURCE pixel; color_back is then its stage 6, per output sample
+// COLORS linear float samples, COLORS being 3 when n_planes == 3, use_matrix or use_tone_map, else 1. With use_tone_map the tone
+// mapping stands behind the matrix and the scale is not applied. What a kernel that filters in linear light
+// (k_tensor_resize.hip) evaluates per SOURCE pixel; color_back is then its stage 6, per output sample
 template <int COLORS>
 __device__ __forceinline__ void color_front(const ColorArgs& a, const uint32_t w[3], float v[3]) {
     v[0] = linear_word(a, 0, w[0]);
@@ -79,6 +89,11 @@ __device__ __forceinline__ void color_front(const ColorArgs& a, const uint32_t w
             const float y = (a.m[3] * v[0] + a.m[4] * v[1]) + a.m[5] * v[2];
             const float z = (a.m[6] * v[0] + a.m[7] * v[1]) + a.m[8] * v[2];
             v[0] = x; v[1] = y; v[2] = z;
+        }
+        if (a.use_tone_map) {
+            const ToneMapped o = tone_map_stage(a.tm, v[0], v[1], v[2]);
+            v[0] = o.r; v[1] = o.g; v[2] = o.b;
+            return;
         }
     }
 #pragma unroll

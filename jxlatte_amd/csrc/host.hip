@@ -8,6 +8,7 @@
 #include "palette_check.h"   // what jxl_stage_palette refuses
 #include "modchain_check.h"  // the walk, the refusals and the Palette runs of jxl_modular_begin_chain
 #include "palette_ops.h"     // palette_pred_is_local: which predictors need the chain kernel
+#include "tone_map_check.h"  // what jxl_ctx_set_tone_map refuses, and the kernels' block
 
 #include <algorithm>
 #include <chrono>
@@ -190,6 +191,9 @@ struct jxl_ctx {
     // resident colour planes between decodeFrame and the colour transform (jxl_planes_*): dense [rp_h][rp_w] floats
     DevBuf rp[3], rp_tmp[3], rp_noise[3];
     int rp_h = 0, rp_w = 0;
+    // jxl_ctx_set_tone_map: the block every ColorArgs built from a jxl_color_params carries while armed
+    bool tone_map_armed = false;
+    jxl::ToneMapArgs tone_map{};
     // device plane sets: the canvas and the reference frames (jxl_canvas_*, canvas_host.hip owns the type)
     jxl::CanvasStore* canvas = nullptr;
     // spline tables (jxl_stage_splines / jxl_planes_splines): arc records, non-empty tiles, CSR ranges and arc lists laid out
@@ -1688,6 +1692,21 @@ jxl_status jxl_ctx_set_stream(jxl_ctx* c, void* stream) {
     (void)pool_of(c);  // attach to the target stream's pool (created here if this is its first context)
     return JXL_OK;
 }
+
+jxl_status jxl_ctx_set_tone_map(jxl_ctx* c, const jxl_tone_map* tm) {
+    if (!c) return JXL_ERR_INVALID_ARGUMENT;
+    if (!tm) {
+        c->tone_map_armed = false;
+        return JXL_OK;
+    }
+    const char* why = tone_map_check(tm);
+    if (why) return fail(c, JXL_ERR_INVALID_ARGUMENT, "%s", why);
+    tone_map_fill(tm, &c->tone_map);
+    c->tone_map_armed = true;
+    return JXL_OK;
+}
+
+int32_t jxl_ctx_tone_map_armed(const jxl_ctx* c) { return c && c->tone_map_armed ? 1 : 0; }
 
 // ---- VarDCT frame ---------------------------------------------------------------------------------
 jxl_status jxl_vardct_begin_frame(jxl_ctx* c, const jxl_vardct_params* p) {
@@ -3207,6 +3226,7 @@ jxl_status ctx_link(jxl_ctx* c, CtxLink* out) {
     return JXL_OK;
 }
 jxl_status ctx_fail(jxl_ctx* c, jxl_status st, const char* msg) { return fail(c, st, "%s", msg); }
+bool ctx_tone_map_armed(const jxl_ctx* c) { return c && c->tone_map_armed; }
 jxl_status ctx_planes_get(jxl_ctx* c, int* h, int* w, float* p[3]) {
     if (c->rp_h <= 0) return fail(c, JXL_ERR_STATE, "no resident planes");
     *h = c->rp_h;
@@ -3807,7 +3827,8 @@ int pow_kind(double p) {
 }
 
 // the checks both entries share, and jxl_color_params as the kernels take it (pointers and tables are filled in by the caller)
-jxl_status color_args(jxl_ctx* c, const jxl_color_params* p, const void* const in[3], ColorArgs* a) {
+// tone: the entry applies the context's armed tone mapping (every entry but the peak's)
+jxl_status color_args(jxl_ctx* c, const jxl_color_params* p, const void* const in[3], ColorArgs* a, bool tone = true) {
     if (!p || !in) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color: null argument");
     if (p->n_planes != 1 && p->n_planes != 3) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color: n_planes must be 1 or 3");
     for (int i = 0; i < p->n_planes; i++)
@@ -3820,6 +3841,8 @@ jxl_status color_args(jxl_ctx* c, const jxl_color_params* p, const void* const i
         (p->tf_out == JXL_TF_GAMMA && (p->gamma_out < 1 || p->gamma_out >= (1 << 24))))
         return fail(c, JXL_ERR_INVALID_ARGUMENT, "Invalid transfer function");  // :165-169
     if (p->max_value < 0) return fail(c, JXL_ERR_INVALID_ARGUMENT, "invalid Max Value");
+    tone = tone && c->tone_map_armed;
+    if (tone && p->use_scale) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color: the scale and the armed tone mapping exclude each other");
     memset(a, 0, sizeof *a);
     a->n_planes = p->n_planes;
     a->in_is_int = p->in_is_int ? 1 : 0;
@@ -3836,6 +3859,8 @@ jxl_status color_args(jxl_ctx* c, const jxl_color_params* p, const void* const i
     a->use_matrix = p->use_matrix ? 1 : 0;
     memcpy(a->m, p->matrix, sizeof a->m);
     a->max_value = p->max_value;
+    a->use_tone_map = tone ? 1 : 0;
+    if (tone) a->tm = c->tone_map;
     return JXL_OK;
 }
 
@@ -3863,7 +3888,7 @@ jxl_status color_peak_from_home(jxl_ctx* c, const ImageHome& m, const jxl_color_
     if (m.planes == HOME_UNKNOWN_SET) return fail(c, JXL_ERR_INVALID_ARGUMENT, "canvas: unknown set");
     if (m.planes) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color peak: the set has no such planes");
     ColorArgs a;
-    jxl_status st = color_args(c, p, m.in(), &a);
+    jxl_status st = color_args(c, p, m.in(), &a, false);
     if (st) return st;
     if (!peak || m.h < 1 || m.w < 1 || m.w > (1 << 30)) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color peak: bad arguments");
     if (home_describes(m, m.h, m.w, p->n_planes, p->in_is_int, 0))  // (the resident entry has one text for all it refuses here)
@@ -3900,7 +3925,7 @@ jxl_status jxl_stage_color_convert(jxl_ctx* c, const void* const in[3], int64_t 
     if (st) return st;
     ColorArgs a;
     if ((st = color_args(c, p, in, &a))) return st;
-    const int n_out = (p->n_planes == 3 || p->use_matrix) ? 3 : 1;
+    const int n_out = (p->n_planes == 3 || p->use_matrix || a.use_tone_map) ? 3 : 1;
     if (!out || n < 0) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color: bad arguments");
     for (int i = 0; i < n_out; i++)  // the matrix has three planes to write: there is no grey output of it
         if (!out[i]) return fail(c, JXL_ERR_INVALID_ARGUMENT, "color: output plane %d missing", i);
@@ -4311,7 +4336,7 @@ jxl_status png_args(jxl_ctx* c, const jxl_png_params* p, const void* const in[3]
     a->bit_depth = p->bit_depth;
     a->big_endian = p->big_endian ? 1 : 0;
     a->out = nullptr;
-    *n_color = (cp.n_planes == 3 || cp.use_matrix) ? 3 : 1;
+    *n_color = (cp.n_planes == 3 || cp.use_matrix || a->c.use_tone_map) ? 3 : 1;
     return JXL_OK;
 }
 

@@ -14,6 +14,7 @@
 #include "patch_compile.h"
 #include "modchain_check.h"
 #include "image_home.h"
+#include "tone_map_ops.h"
 
 namespace jxl {
 
@@ -217,7 +218,7 @@ void launch_transfer(const float* in, int64_t n, int transfer, int max_value, vo
 // colour management in one pass (k_color.hip): jxl_color_params as the kernels see it. All pointers are device pointers.
 struct ColorArgs {
     const void* in[3];  // n_planes planes of float or int32 samples
-    void* out[3];       // float, or int32 when max_value > 0; three planes when n_planes == 3 or use_matrix, else one
+    void* out[3];       // float, or int32 when max_value > 0; three planes when n_planes == 3, use_matrix or use_tone_map, else one
     int64_t n;
     int n_planes, in_is_int;
     float in_scale[3];  // 1.0f / in_max[c] (ImageBuffer.castToFloat0)
@@ -234,6 +235,8 @@ struct ColorArgs {
     const float* srgb8_tab;
     const float* pq16_thr;
     const float* srgb16_tab;
+    int use_tone_map;  // tone_map_ops.h behind the matrix, instead of the scale; three planes out, as with use_matrix
+    ToneMapArgs tm;
 };
 void launch_color_convert(const ColorArgs& a, hipStream_t s);
 // determinePeak over h rows of w samples (w <= 2^30): *result, zeroed by the caller, receives an order-preserving uint32 key of
@@ -250,7 +253,7 @@ struct PngArgs {
     int premultiplied, bit_depth, big_endian;
     void* out;          // c.n * (n_color + (alpha != null)) samples of bit_depth / 8 bytes
 };
-// n_color: 3 when c.n_planes == 3 or c.use_matrix, else 1
+// n_color: 3 when c.n_planes == 3, c.use_matrix or c.use_tone_map, else 1
 void launch_png_samples(const PngArgs& p, int n_color, hipStream_t s);
 // the image as a device tensor in one pass (k_tensor.hip): stages 1-6 and the alpha rule of PngArgs (g.bit_depth 8; g.out is not
 // looked at), then un-premultiplication, normalisation and the conversion to `dtype`, stored CHW or HWC
@@ -621,6 +624,7 @@ jxl_status ctx_png_args(jxl_ctx* c, const jxl_png_params* p, const void* const i
                         int* n_color);
 jxl_status ctx_link(jxl_ctx* c, CtxLink* out);                      // hipSetDevice + the fields above
 jxl_status ctx_fail(jxl_ctx* c, jxl_status st, const char* msg);    // records the message (c may be null) and returns st
+bool ctx_tone_map_armed(const jxl_ctx* c);                          // jxl_ctx_set_tone_map: the colour passes write three colour channels
 jxl_status ctx_planes_get(jxl_ctx* c, int* h, int* w, float* p[3]);  // the resident planes, or JXL_ERR_STATE
 jxl_status ctx_planes_set(jxl_ctx* c, int h, int w, float* p[3]);    // resident planes of h x w to fill (contents undefined)
 // an image's home (image_home.h) for the exits: the resident planes with the host plane `alpha` (JXL_ERR_STATE without); planes

@@ -7,6 +7,7 @@
 //     3. grey -> RGB three copies of the one plane (when a matrix follows)  JXLImage.fillColor (:141-164)
 //     4. matrix      (m0 a + m1 b) + m2 c, every product and sum a float    MathHelper.matrixMutliply3InPlace
 //     5. scale       f * scale (peak detection)                             JXLImage.java:278-280
+//        or, with use_tone_map, the HDR -> SDR operator of tone_map_ops.h (not the reference's), which makes three planes of one
 //     6. fromLinearF of the target                                          TransferFunction.java:39-44, 65-70, 83-87, GammaTransferFunction
 //     7. quantise    (int)(v * max + 0.5f), clamped                         ImageBuffer.castToInt0 (:129-145)
 //   The scale follows the matrix: JXLImage.transform runs toneMapLinear BEFORE transfer(), and transfer() is where the peak is
@@ -41,7 +42,7 @@ __device__ __forceinline__ void store_sample(const ColorArgs& a, int c, int64_t 
 __global__ __launch_bounds__(256) void k_color_convert(const ColorArgs a) {
     for (int64_t i = blockIdx.x * 256LL + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * 256) {
         float r = linear_sample(a, 0, i);
-        if (a.n_planes == 1 && !a.use_matrix) {  // grey stays grey
+        if (a.n_planes == 1 && !a.use_matrix && !a.use_tone_map) {  // grey stays grey
             if (a.use_scale) r = r * a.scale;
             store_sample(a, 0, i, r);
             continue;
@@ -57,7 +58,10 @@ __global__ __launch_bounds__(256) void k_color_convert(const ColorArgs a) {
             const float z = (a.m[6] * r + a.m[7] * g) + a.m[8] * b;
             r = x; g = y; b = z;
         }
-        if (a.use_scale) {
+        if (a.use_tone_map) {  // tone_map_ops.h, in the scale's place
+            const ToneMapped o = tone_map_stage(a.tm, r, g, b);
+            r = o.r; g = o.g; b = o.b;
+        } else if (a.use_scale) {
             r = r * a.scale; g = g * a.scale; b = b * a.scale;
         }
         store_sample(a, 0, i, r);

@@ -29,7 +29,7 @@ void launch_tensor_resize(const ResizeArgs& r, hipStream_t s) {
     const int64_t tiles = resize_tiles(r);
     if (tiles <= 0) return;
     const unsigned grid = (unsigned)(tiles < 65536 ? tiles : 65536);
-    const int n_color = (r.t.g.c.n_planes == 3 || r.t.g.c.use_matrix) ? 3 : 1;
+    const int n_color = (r.t.g.c.n_planes == 3 || r.t.g.c.use_matrix || r.t.g.c.use_tone_map) ? 3 : 1;
     if (r.t.dtype == JXL_TENSOR_U8) launch_resize<1>(r, n_color, grid, s);
     else if (r.t.dtype == JXL_TENSOR_F32) launch_resize<4>(r, n_color, grid, s);
     else launch_resize<2>(r, n_color, grid, s);

@@ -56,6 +56,7 @@ jxl_status jxl_tensor_resized_batch(jxl_ctx* c, int32_t n, const jxl_tensor_batc
     // what the items must agree on, from the pure checks of each (the first refusals of the single-image entries); then the
     // tensors' places and ONE question to the runtime about the whole extent
     BatchShape first{};
+    const bool tone = ctx_tone_map_armed(c);  // (all items share the armed block)
     uint64_t bytes_each = 0;
     for (int i = 0; i < n; i++) {
         const jxl_tensor_batch_item& it = items[i];
@@ -63,7 +64,7 @@ jxl_status jxl_tensor_resized_batch(jxl_ctx* c, int32_t n, const jxl_tensor_batc
         if ((why = resize_check_params(&it.p, &it.r))) return item_fail(c, i, JXL_ERR_INVALID_ARGUMENT, why);
         jxl_tensor_params q = it.p;  // (the tensor is out_height x out_width: tensor_args' second question)
         q.height = it.r.out_height, q.width = it.r.out_width;
-        if ((why = tensor_check_params(&it.p, &lay)) || (why = tensor_check_params(&q, &lay))) return item_fail(c, i, JXL_ERR_INVALID_ARGUMENT, why);
+        if ((why = tensor_check_params(&it.p, &lay, tone)) || (why = tensor_check_params(&q, &lay, tone))) return item_fail(c, i, JXL_ERR_INVALID_ARGUMENT, why);
         const BatchShape sh = batch_shape(it.p, it.r, lay);
         if (i == 0) first = sh, bytes_each = lay.bytes;
         else if ((why = batch_check_agree(first, sh))) return item_fail(c, i, JXL_ERR_INVALID_ARGUMENT, why);

@@ -12,7 +12,7 @@
 namespace jxl {
 
 struct TensorLayout {
-    int n_color;       // 3 when color.n_planes == 3 or color.use_matrix, else 1
+    int n_color;       // 3 when color.n_planes == 3, color.use_matrix or the context's tone mapping is armed, else 1
     int n_out;         // + 1 when alpha is written
     int elem;          // bytes of one element
     uint64_t pixels;   // height * width
@@ -23,8 +23,9 @@ inline int tensor_elem_bytes(int32_t dtype) {
     return dtype == JXL_TENSOR_U8 ? 1 : (dtype == JXL_TENSOR_F16 || dtype == JXL_TENSOR_BF16) ? 2 : dtype == JXL_TENSOR_F32 ? 4 : 0;
 }
 
-// nullptr, or why the parameters are refused; *out is filled when they are not
-inline const char* tensor_check_params(const jxl_tensor_params* p, TensorLayout* out) {
+// nullptr, or why the parameters are refused; *out is filled when they are not. tone_map: the context's tone mapping is armed
+// (jxl_ctx_set_tone_map), which makes three colour channels as use_matrix does
+inline const char* tensor_check_params(const jxl_tensor_params* p, TensorLayout* out, bool tone_map = false) {
     if (!p || !out) return "tensor samples: null argument";
     if (p->height <= 0 || p->width <= 0) return "tensor samples: bad size";
     const int elem = tensor_elem_bytes(p->dtype);
@@ -40,7 +41,7 @@ inline const char* tensor_check_params(const jxl_tensor_params* p, TensorLayout*
     const bool alpha_read = p->has_alpha && (p->write_alpha || p->premultiplied);
     const bool cast = p->dtype != JXL_TENSOR_U8 || p->premultiplied || p->alpha_tagged_depth != 8;
     if (alpha_read && p->alpha_is_int && cast && (p->alpha_tagged_depth < 1 || p->alpha_tagged_depth > 31)) return "invalid Max Value";
-    out->n_color = (p->color.n_planes == 3 || p->color.use_matrix) ? 3 : 1;
+    out->n_color = (p->color.n_planes == 3 || p->color.use_matrix || tone_map) ? 3 : 1;
     out->n_out = out->n_color + (p->write_alpha ? 1 : 0);
     out->elem = elem;
     out->pixels = (uint64_t)p->height * (uint64_t)p->width;  // < 2^62: no wrap

@@ -30,11 +30,12 @@ jxl_status tensor_out_check(jxl_ctx* c, const CtxLink& l, void* out, uint64_t by
 jxl_status tensor_args(jxl_ctx* c, const CtxLink& l, const jxl_tensor_params* p, const void* const in[3], const void* alpha, void* out,
                        TensorArgs* t, TensorLayout* lay, int32_t out_height, int32_t out_width, bool check_out) {
     if (!out) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, "tensor samples: null argument");
-    const char* why = tensor_check_params(p, lay);
+    const bool tone = ctx_tone_map_armed(c);
+    const char* why = tensor_check_params(p, lay, tone);
     if (!why && (out_height || out_width)) {  // the tensor is out_height x out_width: its layout, bytes and alignment rule
         jxl_tensor_params q = *p;
         q.height = out_height, q.width = out_width;
-        why = tensor_check_params(&q, lay);
+        why = tensor_check_params(&q, lay, tone);
     }
     if (why) return ctx_fail(c, JXL_ERR_INVALID_ARGUMENT, why);
     jxl_png_params g;

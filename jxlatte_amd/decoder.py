@@ -662,6 +662,66 @@ def blend_type_plan(info, fr, canvas_types, frame_types, ref_types):
     return plan
 
 
+class ToneMap:
+    """HDR -> SDR on the device (csrc/tone_map_ops.h has the operator): the BT.2408 luminance curve from the content's
+    peak to a display of targetNits, then -- gamut -- the least desaturation that brings a pixel into [0, 1].
+    sourceNits: the content's mastering peak (default: the image's intensity target). unitNits: the nits of a linear 1.0 (default:
+    the intensity target for an XYB-encoded image; else 10000 for an image tagged PQ, else the intensity target)."""
+
+    def __init__(self, targetNits=203.0, sourceNits=None, unitNits=None, gamut=True):
+        for name, v in (("targetNits", targetNits), ("sourceNits", sourceNits), ("unitNits", unitNits)):
+            if v is None and name != "targetNits":
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not math.isfinite(v) or not v > 0:
+                raise ValueError("ToneMap: %s is a finite, positive number of nits" % name)
+        if sourceNits is not None and sourceNits > 10000:
+            raise ValueError("ToneMap: sourceNits is at most 10000")
+        self.targetNits = float(targetNits)
+        self.sourceNits = None if sourceNits is None else float(sourceNits)
+        self.unitNits = None if unitNits is None else float(unitNits)
+        self.gamut = bool(gamut)
+
+    def resolve(self, image):
+        """(unitNits, sourceNits, targetNits, gamut) for `image`: the defaults filled in from its header"""
+        target = float(image.info.intensity_target)
+        source = target if self.sourceNits is None else self.sourceNits
+        if self.unitNits is not None:
+            unit = self.unitNits
+        else:
+            unit = target if image.info.xyb_encoded else 10000.0 if image.taggedTransfer == TF_PQ else target
+        return (unit, source, self.targetNits, self.gamut)
+
+    def __repr__(self):
+        return "ToneMap(targetNits=%r, sourceNits=%r, unitNits=%r, gamut=%r)" % (self.targetNits, self.sourceNits, self.unitNits, self.gamut)
+
+
+def _tone_map_check(toneMap, backend, transfer=None):
+    """what every toneMap= entry refuses before any call"""
+    if not isinstance(toneMap, ToneMap):
+        raise ValueError("toneMap: a ToneMap")
+    if not hasattr(backend, "set_tone_map"):
+        raise ValueError("toneMap needs the device path")
+    if transfer == TF_PQ:
+        raise ValueError("toneMap: the output is SDR; a linear, sRGB, BT.709 or gamma target")
+
+
+class _ToneMapArmed:
+    """the backend's colour passes tone-map while this is open: armed on entry, always cleared on exit"""
+
+    def __init__(self, backend, primaries, whitePoint, resolved):
+        self.backend = backend
+        unit, source, target, gamut = resolved
+        self.args = ([float(v) for v in _primaries_to_xyz(primaries, whitePoint)[1]], unit, source, target, gamut)
+
+    def __enter__(self):
+        self.backend.set_tone_map(*self.args)
+        return self
+
+    def __exit__(self, *exc):
+        self.backend.set_tone_map(None)
+        return False
+
+
 class DeviceBackend:
     """the product backend: HIP kernels through the C-ABI (jxlatte_amd._lib / host). No CPU fallback."""
 
@@ -763,6 +823,10 @@ class DeviceBackend:
 
     def color_peak(self, planes, **params):
         return self.host.determinePeak(self.ctx, planes, **params)
+
+    def set_tone_map(self, lum, unitNits=None, sourceNits=None, targetNits=None, gamut=True):
+        """arm the HDR -> SDR stage of this backend's colour passes (host.setToneMap), or clear it (lum None)"""
+        self.host.setToneMap(self.ctx, None if lum is None else self.host.toneMapParams(lum, unitNits, sourceNits, targetNits, gamut))
 
     def png_samples(self, planes, alpha, **params):
         """PNGWriter's samples in one pass (host.pngSamples; the keywords are host.pngParams')"""
@@ -941,7 +1005,7 @@ class JXLImage:
     _TENSOR_TARGETS = ("srgb", "pq", "linear", "as-is")
 
     def toTensor(self, dtype=None, layout="CHW", target="srgb", peakDetect=PEAK_DETECT_AUTO, alpha="drop", mean=None, std=None, out=None,
-                 size=None, box=None, resample="triangle"):
+                 size=None, box=None, resample="triangle", toneMap=None):
         """The image as a torch tensor on the backend's device, (C, H, W) or (H, W, C), in ONE device pass from wherever its planes
         are -- no sample crosses the bus downwards.
         dtype: torch.uint8, float16, bfloat16 or float32 (the default). target: "srgb" (PNGWriter's non-HDR target: sRGB
@@ -956,30 +1020,42 @@ class JXLImage:
         linear intermediate where the plan has one, before the output curve -- with resample "triangle" (bilinear with the
         support scaled to the ratio: antialiased) or "box". box = (x0, y0, w, h) in whole source pixels: alone it is a crop
         (an identity-ratio resample: an exact copy). With both left out the pass and its bytes are the unresized ones; images
-        of any size then fill one batch through out=batch[i]. Peak detection stays the whole image's."""
+        of any size then fill one batch through out=batch[i]. Peak detection stays the whole image's.
+        toneMap: a ToneMap -- HDR to SDR per source pixel behind the primaries matrix, in place of peak detection (which is not
+        consulted); a resample then filters tone-mapped linear light. Three colour channels, of a grey image too. Targets "srgb"
+        and "linear"; ValueError for "pq", "as-is" and an image with an ICC profile."""
         import torch
         be = self.backend
+        if toneMap is not None:
+            _tone_map_check(toneMap, be)
+            if target in ("pq", "as-is") or self.has_icc:
+                raise ValueError("toneMap: the output is SDR in known primaries; target srgb or linear, and no ICC profile")
         if not hasattr(be, "tensor_samples"):
             raise TypeError("toTensor needs a backend with tensor_samples")
         if (size is not None or box is not None) and not hasattr(be, "tensor_resized"):
             raise TypeError("toTensor(size=, box=) needs a backend with tensor_resized")
-        resize, dtype, name, channels, mean, inv_std = self._tensor_request(torch, dtype, layout, target, alpha, mean, std, size, box, resample)
+        resize, dtype, name, channels, mean, inv_std = self._tensor_request(torch, dtype, layout, target, alpha, mean, std, size, box, resample,
+                                                                             toneMap is not None)
         oh, ow = (self.height, self.width) if resize is None else resize[0]
         shape = (channels, oh, ow) if layout == "CHW" else (oh, ow, channels)
         device = torch.device(be.tensor_device())
         if out is not None:
             if not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != device or not out.is_contiguous():
                 raise ValueError("out: a contiguous %s tensor of shape %s on %s" % (name, shape, device))
-        planes, kw, up = self._tensor_plan(target, peakDetect, alpha, name, layout, mean, inv_std)
+        planes, kw, up = self._tensor_plan(target, peakDetect, alpha, name, layout, mean, inv_std, toneMap)
         if out is None:
             out = torch.empty(shape, dtype=dtype, device=device)
         elif device.type == "cuda":
             torch.cuda.current_stream(device).synchronize()  # what the caller queued on its tensor is done before the library writes
-        sent = self._tensor_samples(planes, out.data_ptr(), resize=resize, **kw)
+        if toneMap is None:
+            sent = self._tensor_samples(planes, out.data_ptr(), resize=resize, **kw)
+        else:
+            with _ToneMapArmed(be, self._tensor_target(target)[0], WP_D65, toneMap.resolve(self)):
+                sent = self._tensor_samples(planes, out.data_ptr(), resize=resize, **kw)
         self.tensor_bus_bytes = (up + sent, 0)
         return out
 
-    def _tensor_request(self, torch, dtype, layout, target, alpha, mean, std, size, box, resample):
+    def _tensor_request(self, torch, dtype, layout, target, alpha, mean, std, size, box, resample, toneMapped=False):
         """toTensor's arguments checked against the image, before any call: (resize, dtype, its name, channels, mean, inv_std);
         resize: None, or (size, box, resample)"""
         resize = None
@@ -1020,7 +1096,7 @@ class JXLImage:
         colors = self.getColorChannelCount()
         primaries, _, as_is = self._tensor_target(target)
         tone_map = not as_is and not (_prim_matches(primaries, self.primariesXY) and _xy_matches(WP_D65, self.whiteXY))
-        channels = (3 if (colors == 3 or tone_map) else 1) + (alpha == "append")
+        channels = (3 if (colors == 3 or tone_map or toneMapped) else 1) + (alpha == "append")
         inv_std = None
         if mean is not None:
             mean, std = [float(v) for v in mean], [float(v) for v in std]
@@ -1038,7 +1114,7 @@ class JXLImage:
         primaries, tf = {"srgb": (PRI_SRGB, TF_SRGB), "pq": (PRI_BT2100, TF_PQ), "linear": (PRI_SRGB, TF_LINEAR)}.get(target, (None, None))
         return primaries, tf, as_is
 
-    def _tensor_plan(self, target, peakDetect, alpha, dtype_name, layout, mean, inv_std):
+    def _tensor_plan(self, target, peakDetect, alpha, dtype_name, layout, mean, inv_std, toneMap=None):
         """the colour plan of a checked toTensor request, with at most one _peak call: (planes, _tensor_samples' keywords, bytes
         the peak sent up)"""
         colors = self.getColorChannelCount()
@@ -1051,7 +1127,7 @@ class JXLImage:
             peak, sent = self._peak(pl, **front)
             up += sent
             return peak
-        plan = None if as_is else self._color_plan(primaries, WP_D65, tf, peakDetect, peak_of, planes=planes)
+        plan = None if as_is else self._color_plan(primaries, WP_D65, tf, peakDetect, peak_of, planes=planes, toneMap=toneMap)
         if plan is not None:
             planes, params = plan[0], plan[1]
         else:  # the image as it is: every colour stage off; integer planes are cast with their depth's maximum
@@ -1209,14 +1285,15 @@ class JXLImage:
         im.primariesXY, im.whiteXY = np.array(primaries, F), np.array(whitePoint, F)
         return im
 
-    def _color_plan(self, primaries, whitePoint, transfer, peakDetect, peak_of, planes=None):
+    def _color_plan(self, primaries, whitePoint, transfer, peakDetect, peak_of, planes=None, toneMap=None):
         """the decisions of transform / linearize / fillColor / toneMapLinear / transfer (JXLImage.java:114-141, 185-193, 260-286)
         for a backend that does the sample work in one pass: None when the image is returned as it is, else (planes, params,
         tone_map), params being the keywords of host.colorParams for those planes. peak_of(planes, **front) is asked for
         determinePeak of the front stages, at most once, where transfer() would take it. planes: stand-ins for colour planes
-        that are not on the host (their dtype is what is looked at)."""
+        that are not on the host (their dtype is what is looked at). toneMap: a ToneMap is armed around the pass -- there is
+        always a pass then, through linear light, and peak_of is not asked."""
         tone_map = not (_prim_matches(primaries, self.primariesXY) and _xy_matches(whitePoint, self.whiteXY))
-        if not tone_map and transfer == self.transfer_:
+        if not tone_map and transfer == self.transfer_ and toneMap is None:
             return None
         tf_in, gamma_in = _tf_selector(self.transfer_)
         tf_out, gamma_out = _tf_selector(transfer)
@@ -1230,6 +1307,8 @@ class JXLImage:
         front = dict(tfIn=tf_in, gammaIn=gamma_in)
         if tone_map:
             front["matrix"] = get_conversion_matrix(primaries, whitePoint, self.primariesXY, self.whiteXY)
+        if toneMap is not None:
+            return planes, dict(inMax=depth_max, tfOut=tf_out, gammaOut=gamma_out, **front), tone_map
         if tone_map and transfer == TF_LINEAR:  # transfer() of the tone-mapped, linear image returns it as it is (:270-271)
             return planes, dict(inMax=depth_max, **front), tone_map
         scale = None
@@ -1245,33 +1324,45 @@ class JXLImage:
         first_max = depth_max if (self.transfer_ != TF_LINEAR or tone_map or scale is not None) else [self.bitDepths[c] for c in range(colors)]
         return planes, dict(inMax=first_max, scale=scale, tfOut=tf_out, gammaOut=gamma_out, **front), tone_map
 
-    def _transform_device(self, primaries, whitePoint, transfer, peakDetect):
+    def _transform_device(self, primaries, whitePoint, transfer, peakDetect, toneMap=None):
         """transform() with the samples on the device: the decisions are _color_plan's, the sample work is at most one
         color_peak and one color_convert call of the backend. Same metadata as the host path; float samples within the 1 ulp
         of the double-pow curves (include/jxlatte_amd.h)."""
-        plan = self._color_plan(primaries, whitePoint, transfer, peakDetect, self.backend.color_peak)
+        plan = self._color_plan(primaries, whitePoint, transfer, peakDetect, self.backend.color_peak, toneMap=toneMap)
         if plan is None:
             return self
         planes, params, tone_map = plan
         colors = self.getColorChannelCount()
-        out = self.backend.color_convert(planes, **params)
+        if toneMap is None:
+            out = self.backend.color_convert(planes, **params)
+        else:
+            with _ToneMapArmed(self.backend, primaries, whitePoint, toneMap.resolve(self)):
+                out = self.backend.color_convert(planes, **params)
         im = self._clone()
-        if tone_map:
+        if tone_map or toneMap is not None:  # three planes
             if colors == 1:  # fillColor
                 im.buffer = list(out) + list(self.buffer[1:])
                 im.bitDepths = [self.bitDepths[0]] * 2 + list(self.bitDepths)
                 im.colorEncoding = CE_RGB
             else:
                 im.buffer[:3] = out
-            im.primariesXY, im.whiteXY = np.array(primaries, F), np.array(whitePoint, F)
+            if tone_map:
+                im.primariesXY, im.whiteXY = np.array(primaries, F), np.array(whitePoint, F)
         else:
             im.buffer[:colors] = out
         im.transfer_ = transfer
         return im
 
-    def transform(self, primaries, whitePoint, transfer, peakDetect=PEAK_DETECT_AUTO, device=False):
+    def transform(self, primaries, whitePoint, transfer, peakDetect=PEAK_DETECT_AUTO, device=False, toneMap=None):
         """JXLImage.transform (:186-193). device: the whole chain as one pass of a backend that has color_convert -- which also
-        serves the BT.709, DCI and gamma targets; else on the host, one plane and one stage at a time"""
+        serves the BT.709, DCI and gamma targets; else on the host, one plane and one stage at a time.
+        toneMap: a ToneMap -- HDR to SDR in the same pass, behind the primaries matrix and in place of peak detection; the
+        device path only, and not towards PQ. The result has three colour planes."""
+        if toneMap is not None:
+            if not device or not hasattr(self.backend, "color_convert"):
+                raise ValueError("toneMap needs the device path")
+            _tone_map_check(toneMap, self.backend, transfer)
+            return self._transform_device(primaries, whitePoint, transfer, peakDetect, toneMap)
         if device and hasattr(self.backend, "color_convert"):
             return self._transform_device(primaries, whitePoint, transfer, peakDetect)
         if _prim_matches(primaries, self.primariesXY) and _xy_matches(whitePoint, self.whiteXY):
@@ -1280,7 +1371,7 @@ class JXLImage:
 
 
 def toTensorBatch(images, size, boxes=None, dtype=None, layout="CHW", target="srgb", peakDetect=PEAK_DETECT_AUTO, alpha="drop", mean=None,
-                  std=None, out=None, resample="triangle"):
+                  std=None, out=None, resample="triangle", toneMap=None):
     """N decoded images as ONE torch tensor on their backend's device, (N, C, h, w) or (N, h, w, C), in ONE launch: image i is
     resampled to `size` = (h, w) exactly as images[i].toTensor(size=size, box=boxes[i], ...) resamples it -- bit for bit -- from
     wherever its planes are (a plane set, the resident planes, host arrays), each with the colour plan toTensor builds for it
@@ -1289,7 +1380,9 @@ def toTensorBatch(images, size, boxes=None, dtype=None, layout="CHW", target="sr
     does not join colour ones); ValueError before any call otherwise, and for everything toTensor raises.
     out: a contiguous tensor of the batch's shape and dtype on that device -- a slice batch[a:a + N] of a larger batch is one --
     filled in place and returned; the current torch stream is synchronised first. Each image's tensor_bus_bytes is set as
-    toTensor sets it; the batch's total is the returned tensor's bus_bytes = (bytes up, 0)."""
+    toTensor sets it; the batch's total is the returned tensor's bus_bytes = (bytes up, 0).
+    toneMap: toTensor's, one value for the batch: its per-image defaults must resolve to the same numbers for every image
+    (ValueError naming two images that differ otherwise)."""
     import torch
     images = list(images)
     if not images:
@@ -1301,12 +1394,22 @@ def toTensorBatch(images, size, boxes=None, dtype=None, layout="CHW", target="sr
         raise ValueError("toTensorBatch: the images are on different backends")
     if not hasattr(be, "tensor_resized_batch"):
         raise TypeError("toTensorBatch needs a backend with tensor_resized_batch")
+    resolved = None
+    if toneMap is not None:
+        _tone_map_check(toneMap, be)
+        if target in ("pq", "as-is") or any(im.has_icc for im in images):
+            raise ValueError("toneMap: the output is SDR in known primaries; target srgb or linear, and no ICC profile")
+        each = [toneMap.resolve(im) for im in images]
+        for i, r in enumerate(each):
+            if r != each[0]:
+                raise ValueError("toTensorBatch: toneMap resolves differently for image 0 %r and image %d %r" % (each[0], i, r))
+        resolved = each[0]
     if size is None:
         raise ValueError("size: (height, width)")
     boxes = [None] * len(images) if boxes is None else list(boxes)
     if len(boxes) != len(images):
         raise ValueError("boxes: one box (or None) per image")
-    reqs = [im._tensor_request(torch, dtype, layout, target, alpha, mean, std, size, bx, resample) for im, bx in zip(images, boxes)]
+    reqs = [im._tensor_request(torch, dtype, layout, target, alpha, mean, std, size, bx, resample, toneMap is not None) for im, bx in zip(images, boxes)]
     resize0, dtype, name, channels, _, _ = reqs[0]
     if any(r[3] != channels for r in reqs):
         raise ValueError("toTensorBatch: the images give different channel counts (%s)" % sorted({r[3] for r in reqs}))
@@ -1318,7 +1421,7 @@ def toTensorBatch(images, size, boxes=None, dtype=None, layout="CHW", target="sr
             raise ValueError("out: a contiguous %s tensor of shape %s on %s" % (name, shape, device))
     items, sent = [], []
     for im, req in zip(images, reqs):
-        planes, kw, up = im._tensor_plan(target, peakDetect, alpha, name, layout, req[4], req[5])
+        planes, kw, up = im._tensor_plan(target, peakDetect, alpha, name, layout, req[4], req[5], toneMap)
         item, more = im._tensor_batch_item(planes, req[0], **kw)
         items.append(item)
         sent.append(up + more)
@@ -1326,7 +1429,11 @@ def toTensorBatch(images, size, boxes=None, dtype=None, layout="CHW", target="sr
         out = torch.empty(shape, dtype=dtype, device=device)
     elif device.type == "cuda":
         torch.cuda.current_stream(device).synchronize()  # what the caller queued on its tensor is done before the library writes
-    be.tensor_resized_batch(items, out.data_ptr())
+    if resolved is None:
+        be.tensor_resized_batch(items, out.data_ptr())
+    else:
+        with _ToneMapArmed(be, images[0]._tensor_target(target)[0], WP_D65, resolved):
+            be.tensor_resized_batch(items, out.data_ptr())
     for im, b in zip(images, sent):
         im.tensor_bus_bytes = (b, 0)
     out.bus_bytes = (sum(sent), 0)
@@ -3069,12 +3176,21 @@ class JXLDecoder:
 
 # ---- PNGWriter (J/io/PNGWriter.java) ---------------------------------------------------------------------------
 class PNGWriter:
-    def __init__(self, image, bitDepth=-1, hdr=False, peakDetect=PEAK_DETECT_AUTO, deflateLevel=6, deviceColor=False, deviceSamples=False):
+    def __init__(self, image, bitDepth=-1, hdr=False, peakDetect=PEAK_DETECT_AUTO, deflateLevel=6, deviceColor=False, deviceSamples=False,
+                 toneMap=None):
         """deviceColor: JXLImage.transform(..., device=True).
         deviceSamples: the colour management and the packing in ONE device pass (backend.png_samples, or
         ResidentPlanes.pngSamples when the image's colour planes are on the device: JXLDecoder(device_output=True)), after at
         most one peak call; the same samples as deviceColor gives, byte for byte. bus_bytes = (bytes up, bytes down) of the
-        sample planes. A backend without png_samples is an error."""
+        sample planes. A backend without png_samples is an error.
+        toneMap: a ToneMap -- HDR to SDR inside the device colour pass (deviceColor or deviceSamples), in place of peak
+        detection; not with hdr, and not for an image with an ICC profile."""
+        if toneMap is not None:
+            if not (deviceColor or deviceSamples):
+                raise ValueError("toneMap needs the device path")
+            _tone_map_check(toneMap, image.backend, TF_PQ if hdr else None)
+            if image.has_icc:
+                raise ValueError("toneMap: an image with an ICC profile is written as it is")
         if bitDepth <= 0:
             bitDepth = 16 if (hdr or image.info.bits_per_sample > 8) else 8
         if bitDepth not in (8, 16):
@@ -3085,10 +3201,10 @@ class PNGWriter:
         tf = TF_PQ if hdr else TF_SRGB
         self.has_icc = image.has_icc
         self.bus_bytes = None
-        if deviceSamples and self._device_samples(image, bitDepth, primaries, tf, peakDetect, deflateLevel):
+        if deviceSamples and self._device_samples(image, bitDepth, primaries, tf, peakDetect, deflateLevel, toneMap):
             return
         if not image.has_icc:
-            image = image.transform(primaries, WP_D65, tf, peakDetect, device=deviceColor or deviceSamples)
+            image = image.transform(primaries, WP_D65, tf, peakDetect, device=deviceColor or deviceSamples, toneMap=toneMap)
         self._layout(image, bitDepth, 1 if gray else 3, deflateLevel)
         planes = image.getBuffer(False)
         color = [np.ascontiguousarray(planes[c]) for c in range(self.colorChannels)]
@@ -3106,7 +3222,7 @@ class PNGWriter:
         self.alphaIndex = image.getAlphaIndex()
         self.colorMode = (4 if self.alphaIndex >= 0 else 0) if colors == 1 else (6 if self.alphaIndex >= 0 else 2)
 
-    def _device_samples(self, image, bitDepth, primaries, tf, peakDetect, deflateLevel):
+    def _device_samples(self, image, bitDepth, primaries, tf, peakDetect, deflateLevel, toneMap=None):
         """the constructor with deviceSamples. False (nothing done): a grey image that is tone-mapped -- PNGWriter then takes
         plane 0 and plane 1 + alphaIndex of the three-plane result for its grey layout, which the one-pass kernel has no
         output for; the constructor runs the device passes one by one (deviceColor) and bus_bytes stays None."""
@@ -3122,9 +3238,9 @@ class PNGWriter:
             peak, sent = image._peak(pl, **front)
             up += sent
             return peak
-        if colors == 1 and not image.has_icc and not (_prim_matches(primaries, image.primariesXY) and _xy_matches(WP_D65, image.whiteXY)):
+        if colors == 1 and not image.has_icc and (toneMap is not None or not (_prim_matches(primaries, image.primariesXY) and _xy_matches(WP_D65, image.whiteXY))):
             return False  # (before the plan is made: the peak, if one is needed, is then taken once, by transform())
-        plan = None if image.has_icc else image._color_plan(primaries, WP_D65, tf, peakDetect, peak_of, planes=planes)
+        plan = None if image.has_icc else image._color_plan(primaries, WP_D65, tf, peakDetect, peak_of, planes=planes, toneMap=toneMap)
         if plan is not None:
             planes, params = plan[0], plan[1]
         else:  # the image as it is: every colour stage off; integer planes are cast with their depth's maximum (PNGWriter's coercion)
@@ -3135,10 +3251,14 @@ class PNGWriter:
             params = dict(inMax=[(1 << image.bitDepths[c]) - 1 for c in range(colors)])
         self._layout(image, bitDepth, colors, deflateLevel)
         has_alpha = self.alphaIndex >= 0
-        self.samples, sent = image._png_samples(
-            planes, premultiplied=image.isAlphaPremultiplied() and has_alpha, bitDepth=bitDepth, bigEndian=True,
-            alphaDepth=image.getTaggedBitDepth(colors + self.alphaIndex) if has_alpha else None,
-            colorDepth=image.getTaggedBitDepth(0), **params)
+        kw = dict(premultiplied=image.isAlphaPremultiplied() and has_alpha, bitDepth=bitDepth, bigEndian=True,
+                  alphaDepth=image.getTaggedBitDepth(colors + self.alphaIndex) if has_alpha else None,
+                  colorDepth=image.getTaggedBitDepth(0), **params)
+        if toneMap is None:
+            self.samples, sent = image._png_samples(planes, **kw)
+        else:
+            with _ToneMapArmed(be, primaries, WP_D65, toneMap.resolve(image)):
+                self.samples, sent = image._png_samples(planes, **kw)
         self.bus_bytes = (up + sent, self.samples.nbytes)
         return True
 

@@ -202,6 +202,22 @@ def colorParams(planes, tfIn=abi.TF_LINEAR, gammaIn=0, inMax=None, scale=None, m
     return p
 
 
+def toneMapParams(lum, unitNits, sourceNits, targetNits, gamut=True):
+    """jxl_tone_map: the luminance weights of the primaries the samples are in behind the matrix stage, the nits of a linear 1.0,
+    the content's mastering peak, the display's peak, and whether the gamut step runs"""
+    t = abi.ToneMapParams()
+    t.lum = (C.c_float * 3)(*[float(v) for v in lum])
+    t.unit_nits, t.source_nits, t.target_nits, t.gamut = float(unitNits), float(sourceNits), float(targetNits), int(bool(gamut))
+    return t
+
+
+def setToneMap(ctx, tm):
+    """arm (tm: a jxl_tone_map of toneMapParams) or clear (None) the HDR -> SDR stage of the context's colour passes
+    (jxl_ctx_set_tone_map): while armed colorConvert, pngSamples, tensorSamples, tensorResized and tensorResizedBatch, from every
+    home, apply it behind the matrix and write three colour channels; a scale is refused"""
+    ctx.call("jxl_ctx_set_tone_map", None if tm is None else C.byref(tm))
+
+
 def _pv(planes):
     arr = (C.c_void_p * 3)()
     for c, a in enumerate(planes):
@@ -212,10 +228,10 @@ def _pv(planes):
 def colorConvert(ctx, planes, **params):
     """JXLImage.transform's sample chain in one device pass (jxl_stage_color_convert): cast, toLinearF, grey -> RGB, matrix,
     peak scale, fromLinearF, castToInt0, each one optional (colorParams). Returns the list of output planes: three when a
-    matrix is given or three planes come in, else one; int32 when maxValue > 0, else float32."""
+    matrix is given, three planes come in or the context's tone mapping is armed (setToneMap), else one; int32 when maxValue > 0, else float32."""
     planes = [np.ascontiguousarray(a) for a in planes]
     p = colorParams(planes, **params)
-    n_out = 3 if (len(planes) == 3 or p.use_matrix) else 1
+    n_out = 3 if (len(planes) == 3 or p.use_matrix or ctx.toneMapArmed()) else 1
     out = [np.empty(planes[0].shape, np.int32 if p.max_value > 0 else np.float32) for _ in range(n_out)]
     ctx.call("jxl_stage_color_convert", _pv(planes), planes[0].size, C.byref(p), _pv(out))
     return out
@@ -246,8 +262,8 @@ def pngParams(planes, shape, alpha=None, premultiplied=False, bitDepth=8, bigEnd
     return p
 
 
-def _png_out(p, shape):
-    nch = (3 if (p.color.n_planes == 3 or p.color.use_matrix) else 1) + p.has_alpha
+def _png_out(ctx, p, shape):
+    nch = (3 if (p.color.n_planes == 3 or p.color.use_matrix or ctx.toneMapArmed()) else 1) + p.has_alpha
     return np.empty((shape[0], shape[1], nch), np.uint8 if p.bit_depth == 8 else np.uint16)
 
 
@@ -268,7 +284,7 @@ def pngSamples(ctx, planes, alpha=None, **params):
     shape = planes[0].shape
     a = _png_alpha(alpha, shape)
     p = pngParams(planes, shape, alpha=a, **params)
-    out = _png_out(p, shape)
+    out = _png_out(ctx, p, shape)
     ctx.call("jxl_stage_png_samples", _pv(planes), _vp(a), C.byref(p), _vp(out))
     return out
 
@@ -300,9 +316,9 @@ def tensorParams(planes, shape, alpha=None, premultiplied=False, writeAlpha=Fals
     return p
 
 
-def tensorChannels(p):
-    """the output channels of a jxl_tensor_params"""
-    return (3 if (p.color.n_planes == 3 or p.color.use_matrix) else 1) + int(bool(p.write_alpha))
+def tensorChannels(p, toneMap=False):
+    """the output channels of a jxl_tensor_params (toneMap: on a context whose tone mapping is armed)"""
+    return (3 if (p.color.n_planes == 3 or p.color.use_matrix or toneMap) else 1) + int(bool(p.write_alpha))
 
 
 def tensorSamples(ctx, planes, alpha, out_ptr, **params):
@@ -818,7 +834,7 @@ class ResidentPlanes:
         shape = self.shape
         a = _png_alpha(alpha, shape)
         p = pngParams(self._stand_ins(), shape, alpha=a, **params)
-        out = _png_out(p, shape)
+        out = _png_out(self.ctx, p, shape)
         self.ctx.call("jxl_planes_png_samples", _vp(a), C.byref(p), _vp(out))
         return out
 
@@ -1349,7 +1365,7 @@ class DeviceCanvas:
         ap = -1 if alphaPlane is None else int(alphaPlane)
         alpha = None if ap < 0 else np.broadcast_to(np.zeros((), _PLANE_DTYPE[self.types[ap]]), self.shape)
         p = pngParams(self._stand_ins(nColor), self.shape, alpha=alpha, **params)
-        out = _png_out(p, self.shape)
+        out = _png_out(self.ctx, p, self.shape)
         self.ctx.call("jxl_canvas_png_samples", self.id, ap, C.byref(p), _vp(out))
         _bus(self.ctx, down=out.nbytes)
         return out
