@@ -75,7 +75,14 @@ struct Geo {
     static constexpr int SW = IW + 3;                                         // LDS row stride (patch over-read <= 3)
     static constexpr int SH = IH + 1;
     static constexpr int PLANE = SW * SH;
-    static constexpr size_t LDS_BYTES = sizeof(float) * (3 * PLANE + 16 * 16);
+    // behind the image and the sigma cells: the handoff area of the 5-tap iterations' pair chains (epf_stage). North part: 9 rows of
+    // 64 chains -- row 0 from the edge pass, row w + 1 the south chains of wave w's bottom window row; west part: 5 columns of 32 --
+    // column 0 from the edge pass, column k + 1 the east chains of patch column 4 k + 3. (The last row and column have no reader.)
+    // 16-byte aligned: a patch takes its four north chains in one read.
+    static constexpr bool HAND = R1 != 0 || R2 != 0;
+    static constexpr int HOFF = (3 * PLANE + 16 * 16 + 3) & ~3;
+    static constexpr int HNORTH = 9 * 64, HWEST = 5 * 32;
+    static constexpr size_t LDS_BYTES = sizeof(float) * (HAND ? HOFF + HNORTH + HWEST : 3 * PLANE + 16 * 16);
 };
 
 // canonical |P[u] - P[v]| * s: operands ordered by index so equal terms are literally the same expression
@@ -84,14 +91,95 @@ __device__ __forceinline__ float adiff(const float* p, int u, int v, float s) {
     return u < v ? fabsf(p[u] - p[v]) * s : fabsf(p[v] - p[u]) * s;
 }
 
+// The pair chains of a 4 x PH patch at (ry, rx), iterations 1 and 2 (epf_patch explains them and why they are exact):
+//   hc[py][j] = distance between (py, j-1) and (py, j), j = 0..4;  vc[i][px] = between (i-1, px) and (i, px), i = 0..PH
+// OWN = 1: only the chains to the east and south neighbours, j and i from 1 -- hc[.][0] and vc[0][.] are left as they are (the
+// west and north chains are what the patches to the left and above form as THEIR east and south chains, epf_stage)
+template <int ITER, int SW, int PLANE, int PH, int OWN>
+__device__ __forceinline__ void epf_pair_chains(const float* __restrict__ src, int ry, int rx, const EpfParams& ep, float hc[PH][5],
+                                                float vc[PH + 1][4]) {
+    constexpr int R = ITER == 1 ? 2 : 1;
+    constexpr int NW = 4 + 2 * R, NH = PH + 2 * R;
+    constexpr int QY[5] = {0, 0, 0, -1, 1};
+    constexpr int QX[5] = {0, -1, 1, 0, 0};
+    auto chain_channel = [&](int c, auto first_channel) {
+        constexpr bool FIRST = decltype(first_channel)::value;
+        float nb[NH * NW];
+        const float* pc = src + c * PLANE + (ry - R) * SW + (rx - R);
+#pragma unroll
+        for (int y = 0; y < NH; y++)
+#pragma unroll
+            for (int x = 0; x < NW; x++) nb[y * NW + x] = pc[y * SW + x];
+        const float sc = ep.channel_scale[c];
+#pragma unroll
+        for (int py = 0; py < PH; py++)
+#pragma unroll
+            for (int j = OWN; j < 5; j++) {
+                const int cy = py + R, cx = j - 1 + R;
+                if (ITER == 2) {
+                    const float t = adiff<NW>(nb, cy * NW + cx, cy * NW + cx + 1, sc);
+                    hc[py][j] = FIRST ? t : hc[py][j] + t;
+                } else
+#pragma unroll
+                    for (int q = 0; q < 5; q++) {
+                        const int u = (cy + QY[q]) * NW + cx + QX[q];
+                        const float t = adiff<NW>(nb, u, u + 1, sc);
+                        hc[py][j] = (FIRST && q == 0) ? t : hc[py][j] + t;
+                    }
+            }
+#pragma unroll
+        for (int i = OWN; i <= PH; i++)
+#pragma unroll
+            for (int px = 0; px < 4; px++) {
+                const int cy = i - 1 + R, cx = px + R;
+                if (ITER == 2) {
+                    const float t = adiff<NW>(nb, cy * NW + cx, (cy + 1) * NW + cx, sc);
+                    vc[i][px] = FIRST ? t : vc[i][px] + t;
+                } else
+#pragma unroll
+                    for (int q = 0; q < 5; q++) {
+                        const int u = (cy + QY[q]) * NW + cx + QX[q];
+                        const float t = adiff<NW>(nb, u, u + NW, sc);
+                        vc[i][px] = (FIRST && q == 0) ? t : vc[i][px] + t;
+                    }
+            }
+    };
+    chain_channel(0, std::true_type{});
+#pragma unroll 1
+    for (int c = 1; c < 3; c++) chain_channel(c, std::false_type{});
+}
+
+// ONE pair chain, by the edge pass of epf_stage: the distance between (y, x) and its neighbour D floats further (D = 1: to the east,
+// D = SW: to the south), the terms of epf_pair_chains in their order: channel-major, cross-minor, first minus second, started at the
+// first term. Equal to hc[.][j] / vc[i][.] of any patch that holds the pair, bit for bit.
+template <int ITER, int SW, int PLANE, int D>
+__device__ __forceinline__ float epf_pair_chain(const float* __restrict__ src, int y, int x, const EpfParams& ep) {
+    constexpr int QY[5] = {0, 0, 0, -1, 1};
+    constexpr int QX[5] = {0, -1, 1, 0, 0};
+    float d = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const float* p = src + c * PLANE + y * SW + x;
+        const float sc = ep.channel_scale[c];
+#pragma unroll
+        for (int q = 0; q < (ITER == 2 ? 1 : 5); q++) {
+            const int o = QY[q] * SW + QX[q];
+            const float t = fabsf(p[o] - p[o + D]) * sc;
+            d = (c == 0 && q == 0) ? t : d + t;
+        }
+    }
+    return d;
+}
+
 // One EPF iteration (Frame.java:583-635) on a 4x2 patch whose top-left sample is (ry, rx) in region
 // coordinates of src (3 planes, stride SW). Results for the 8 pixels go to res[c][py*4+px].
 // ITER: 0 = 13 taps with cross distances, 1 = 5 taps with cross distances, 2 = 5 taps single-pixel.
 // PLAINDIV: three plain divisions per pixel instead of epf_quot3_patch -- the form for parameter sets with a negative factor in the
 // weights, whose sums of weights are not bounded (see the weights below; epf_weights_plain() chooses on the host).
-template <int ITER, int SW, int PLANE, int PH, bool PLAINDIV = false, bool CHAINS = true>
+template <int ITER, int SW, int PLANE, int PH, bool PLAINDIV = false, bool CHAINS = true, bool GIVEN = false>
 __device__ __forceinline__ void epf_patch(const float* __restrict__ src, int ry, int rx, const float* s_inv /*[NP]*/,
-                                          const float* bmul /*[NP]*/, const EpfParams& ep, float res[3][4 * PH]) {
+                                          const float* bmul /*[NP]*/, const EpfParams& ep, float res[3][4 * PH],
+                                          const float* given_h = nullptr /*[5]*/, const float* given_v = nullptr /*[2][4]*/) {
     constexpr int NP = 4 * PH;  // pixels per patch
     constexpr int R = ITER == 0 ? 3 : ITER == 1 ? 2 : 1;  // neighbourhood radius
     constexpr int NW = 4 + 2 * R, NH = PH + 2 * R;
@@ -120,53 +208,19 @@ __device__ __forceinline__ void epf_patch(const float* __restrict__ src, int ry,
         // then differs from the reference's only when EVERY term is a zero, and only in that zero's sign; the one use of a chain is
         // v = 1 - dist * bmul * sigma_scale * s_inv, where a zero of either sign gives the same product magnitude (0, or NaN if a
         // factor is not finite) and 1 - (+-0) is exactly 1. Every non-zero sum sees the same operands in the same order.
+        //
+        // GIVEN: the stage formed the chains already -- the patch's own to the east and south, the west and north ones taken from the
+        // patches that formed them as theirs (epf_stage): the same pairs, so the same terms in the same order.
         float hc[PH][5], vc[PH + 1][4];
-        auto chain_channel = [&](int c, auto first_channel) {
-            constexpr bool FIRST = decltype(first_channel)::value;
-            float nb[NH * NW];
-            const float* pc = src + c * PLANE + (ry - R) * SW + (rx - R);
+        if constexpr (GIVEN) {
+            static_assert(PH == 1, "exchanged chains: 4x1 patches");
 #pragma unroll
-            for (int y = 0; y < NH; y++)
+            for (int j = 0; j < 5; j++) hc[0][j] = given_h[j];
 #pragma unroll
-                for (int x = 0; x < NW; x++) nb[y * NW + x] = pc[y * SW + x];
-            const float sc = ep.channel_scale[c];
-#pragma unroll
-            for (int py = 0; py < PH; py++)
-#pragma unroll
-                for (int j = 0; j < 5; j++) {
-                    const int cy = py + R, cx = j - 1 + R;
-                    if (ITER == 2) {
-                        const float t = adiff<NW>(nb, cy * NW + cx, cy * NW + cx + 1, sc);
-                        hc[py][j] = FIRST ? t : hc[py][j] + t;
-                    } else
-#pragma unroll
-                        for (int q = 0; q < 5; q++) {
-                            const int u = (cy + QY[q]) * NW + cx + QX[q];
-                            const float t = adiff<NW>(nb, u, u + 1, sc);
-                            hc[py][j] = (FIRST && q == 0) ? t : hc[py][j] + t;
-                        }
-                }
-            constexpr int I0 = 0;
-#pragma unroll
-            for (int i = I0; i <= PH; i++)
-#pragma unroll
-                for (int px = 0; px < 4; px++) {
-                    const int cy = i - 1 + R, cx = px + R;
-                    if (ITER == 2) {
-                        const float t = adiff<NW>(nb, cy * NW + cx, (cy + 1) * NW + cx, sc);
-                        vc[i][px] = FIRST ? t : vc[i][px] + t;
-                    } else
-#pragma unroll
-                        for (int q = 0; q < 5; q++) {
-                            const int u = (cy + QY[q]) * NW + cx + QX[q];
-                            const float t = adiff<NW>(nb, u, u + NW, sc);
-                            vc[i][px] = (FIRST && q == 0) ? t : vc[i][px] + t;
-                        }
-                }
-        };
-        chain_channel(0, std::true_type{});
-#pragma unroll 1
-        for (int c = 1; c < 3; c++) chain_channel(c, std::false_type{});
+            for (int px = 0; px < 4; px++) vc[0][px] = given_v[px], vc[1][px] = given_v[4 + px];
+        } else {
+            epf_pair_chains<ITER, SW, PLANE, PH, 0>(src, ry, rx, ep, hc, vc);
+        }
 #pragma unroll
         for (int py = 0; py < PH; py++)
 #pragma unroll
@@ -398,6 +452,93 @@ __device__ __forceinline__ void epf_stage(float* buf, int m, const TileCtx& tc, 
     const int rw = G::IW - 2 * m, rh = G::IH - 2 * m;
     constexpr int NTHR = 512 / PH;
     const int pcols = (rw + 3) >> 2, prows = (rh + PH - 1) / PH;
+    if constexpr (PH == 1 && ITER != 0) {
+        // 5-tap iterations on 4x1 patches: EVERY PAIR CHAIN OF THE WINDOW IS FORMED ONCE. A thread forms the four chains of its
+        // pixels to their south neighbours and the four to their east neighbours (epf_pair_chains, OWN); its north chains are the
+        // south chains of the patch above and its west chain is the last east chain of the patch to the left -- the same pixel
+        // pairs, hence the same terms |P(u) - P(v)| * s with the same first and second operand in the same channel-major,
+        // cross-minor order, started at the same first term: the same bits (the argument of epf_patch, applied across patches).
+        // On edge tiles every chain is formed from the LDS image as mirror_fixup left it, so this holds on mirrored rows and
+        // columns as well. Weights, sums, quotients and sinks are untouched.
+        //
+        // thread -> patch: a wave is 4 window rows x 16 patch columns (wave w: rows 4 w .. 4 w + 3), and each 16-lane DPP row of it is
+        // a 4 x 4 block of patches, lane = 4 * row + column. A 32-lane half is then still 8 patches x 4 rows, so the bank argument
+        // below holds as it stands. The chains travel
+        //   * inside a 4 x 4 block by DPP: north from the lane one row up (row_shr:4), west from the lane to the left (quad_perm);
+        //   * across blocks and waves through the handoff area (Geo::HOFF): the bottom row of every wave writes its south chains, every
+        //     fourth patch column its last east chain;
+        //   * for the window's own top row and left column from the edge pass: ONE wave forms those 64 + 32 chains, one per lane, from
+        //     the halo that is in LDS anyway (radius 2 / 1 around the region: inside the input tile since m >= the radius).
+        // One more barrier per stage separates "chains formed and handed off" from "weights". Lanes that DPP serves ignore what they
+        // read from the handoff area (row_shr writes only lanes with a source in their DPP row; the others keep `old`).
+        // (!HAND: Geo<., 4>, whose one iteration is the 13-tap one -- instantiated by restore_epf_stages' plain `if`s, never run)
+        static_assert(!G::HAND || (G::OW > 48 && G::WH == 32 && NTHR == 512), "13..16 patch columns, 32 window rows on 8 waves");
+        extern __shared__ __attribute__((aligned(16))) float lds[];
+        float* const hnorth = lds + G::HOFF;
+        float* const hwest = hnorth + G::HNORTH;
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const int pcol = ((lane >> 4) << 2) + (lane & 3), prow = (wave << 2) + ((lane >> 2) & 3);
+        const bool act = prow < prows && pcol < pcols;
+        const int ry = m + prow, rx = m + pcol * 4;
+        // A lane without a patch of the region (rows 30, 31 and the like) still owns one of the 64 x 32 window, and forms it like any
+        // other where all that this reads lies inside the LDS image (`whole`: a constant once m is known, true for every stage of
+        // every variant -- the spare row IH and the pad columns included): nothing but its store is masked, so no value that
+        // crosses a barrier needs a defined content for masked lanes. What such a lane hands on feeds dropped results only.
+        constexpr int R = ITER == 1 ? 2 : 1;
+        // (Not with the plain divisions: unmasked, their two-iteration variants spill 12 bytes; masked they hold 64 registers.)
+        const bool whole = !PLAINDIV && m + 31 + R <= G::IH && m + 63 + R <= G::IW + 2;
+        float s_inv[4], bmul[4];
+        float hc[5], vc[2][4];
+        if (whole || act) {
+            patch_sigma<1, EDGE>(ry, rx, tc, sig, scy0, scx0, ep, s_inv, bmul);
+            float (*h1)[5] = reinterpret_cast<float (*)[5]>(hc);
+            epf_pair_chains<ITER, SW, PLANE, 1, 1>(buf, ry, rx, ep, h1, vc);
+            if ((lane & 12) == 12) {
+                float* d = hnorth + (wave + 1) * 64 + pcol * 4;
+                *reinterpret_cast<float4*>(d) = make_float4(vc[1][0], vc[1][1], vc[1][2], vc[1][3]);
+            }
+            if ((lane & 3) == 3) hwest[((pcol >> 2) + 1) * 32 + prow] = hc[4];
+        }
+        // the edge pass (its two halves on two waves measured the same: profiles/restore_chain_once.md)
+        if (__builtin_amdgcn_readfirstlane(wave) == NTHR / 64 - 1) {
+            if (lane < rw) hnorth[lane] = epf_pair_chain<ITER, SW, PLANE, SW>(buf, m - 1, m + lane, ep);
+            if (lane < rh) hwest[lane] = epf_pair_chain<ITER, SW, PLANE, 1>(buf, m + lane, m - 1, ep);
+        }
+        __syncthreads();
+        float res[3][4];
+        if (whole || act) {
+            const float4 n4 = *reinterpret_cast<const float4*>(hnorth + wave * 64 + pcol * 4);
+            const float w1 = hwest[(pcol >> 2) * 32 + prow];
+            const float nn[4] = {n4.x, n4.y, n4.z, n4.w};
+            // update_dpp(old, src, ctrl, row mask, bank mask, bound_ctrl = false): 0x114 = row_shr:4; a lane of the block's top row has
+            // no source and keeps `old`, what it read from the handoff area
+#pragma unroll
+            for (int px = 0; px < 4; px++)
+                vc[0][px] = __int_as_float(
+                    __builtin_amdgcn_update_dpp(__float_as_int(nn[px]), __float_as_int(vc[1][px]), 0x114, 0xf, 0xf, false));
+            // west: quad_perm:[0,0,1,2] (0x90) -- a quad is one row of the block, every lane takes the chain of the lane to its left,
+            // the first lane of the quad its own, for which the handoff value stands in
+            const float wl = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(hc[4]), 0x90, 0xf, 0xf, true));
+            hc[0] = (lane & 3) == 0 ? w1 : wl;
+            epf_patch<ITER, SW, PLANE, 1, PLAINDIV, true, true>(buf, ry, rx, s_inv, bmul, ep, res, hc, &vc[0][0]);
+        }
+        if constexpr (LAST) {
+            if (act) sink.row4(ry, rx, &res[0][0], &res[1][0], &res[2][0], min(4, G::IW - m - rx));
+        } else {
+            __syncthreads();
+            if (act) {
+#pragma unroll
+                for (int px = 0; px < 4; px++) {
+                    const int x = rx + px;
+                    if (x < G::IW - m) {
+#pragma unroll
+                        for (int c = 0; c < 3; c++) buf[c * PLANE + ry * SW + x] = res[c][px];
+                    }
+                }
+            }
+        }
+        return;
+    }
     // thread -> patch. LDS banks are (address / 4) mod 32 for ds_read_b32 / ds_read2 / ds_write, and lanes conflict within a
     // 32-lane half. A patch is 4 floats wide, so 16 patches of one row put their first words on only 8 banks: the row-major
     // assignment (lane -> 16 patches x 2 rows) made every tap read and every write-back a 2-way conflict (44 % of all LDS
@@ -533,7 +674,7 @@ template <bool GAB, int ITERS, int SK, int PH, int LAY = 0, bool PLAINDIV = fals
 __device__ __forceinline__ void restore_fused_body(const FusedArgs& a) {
     using G = Geo<GAB, ITERS>;
     constexpr int NTHR = 512 / PH;
-    extern __shared__ float lds[];
+    extern __shared__ __attribute__((aligned(16))) float lds[];
     // cell-tiled input: the tile starts three floats into the allocation, so that the whole-piece loader below may write up to three
     // samples in front of row 0 of the first plane. LDS_BYTES does not grow for it: the tile's last three floats -- pad columns of
     // the third plane's spare row IH, which no loader and no write-back reaches -- now lie over the first three sigma cells, and
